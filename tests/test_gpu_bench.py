@@ -21,9 +21,17 @@ def _bench(*args):
 
 
 @pytest.mark.parametrize("cfg", ["c3", "c5"])
-def test_bench_line_contract(hiplib, cfg):
+def test_bench_line_contract(hiplib, cfg, tmp_path):
+    import numpy as np
     extra = ["--pulses", "4"] if cfg == "c5" else []
-    d = _bench("--config", cfg, "--steps", "2", "--warmup", "1", "--cpu-paths", "4096", *extra)
+    d = _bench("--config", cfg, "--steps", "2", "--warmup", "1", "--cpu-paths", "4096", "--dump-outputs", str(tmp_path), *extra)
+    # --dump-outputs: the last timed step's histogram (c5: the sweep's cube of 4 pulses), float32
+    h = np.load(tmp_path / "histogram.npy")
+    assert h.dtype == np.float32 and np.isfinite(h).all() and h.any()
+    if cfg == "c5":
+        assert h.shape[0] == 4
+    else:
+        assert h.ndim == 1 and 0 < h[4] <= d["config"]["paths_per_gpu_per_step"]     # weight channel: samples that landed
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k

@@ -1,7 +1,6 @@
 # kernel timeline of a rolling sequence on ONE handle (every launch of the timed region, fills and copies included):
 # where the gaps between launches are.  Output: gpurun_out/r03_timeline_<cfg>.txt
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=16
 cd $GRAFT_REPO_ROOT
 for cfg in ${CFGS:-c3 c2}; do
   rm -rf gpurun_out/tl_$cfg

@@ -1,7 +1,6 @@
 # SQ counters of the C2 bench kernels (wait share, VALU lane utilisation) + an A/B of chain_min without the split
 set -e
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=16
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04sq
 mkdir -p $O
