@@ -39,6 +39,7 @@
 #include <limits>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #if defined(__SSE2__)
 #include <xmmintrin.h>
@@ -1880,18 +1881,43 @@ static float receiver_sample_ray(const OScene &sc, float time, bool mix, float w
     return signal_power * s.gain * geom_gain * extents;
 }
 
+// Where render_sample / receive_sample add their floats.  HistSink: the histogram alone (bfo_render).  AddendSink: also, per
+// cell, S = sum |a| and N = the number of non-zero addends a (bfo_render_addends): what bounds the error of ANY fp32
+// summation order of the same addends, |fl(sum) - sum| <= gamma_{N-1} S.  Zero addends are not counted: the device skips
+// them (the 1x1 range loop adds 0.f to every bin the path does not fall in).
+struct HistSink {
+    double *h;
+    void add(size_t i, float a) const { h[i] += (double) a; }
+};
+struct AddendSink {
+    double *h, *s;
+    uint32_t *n;
+    void add(size_t i, float a) const {
+        h[i] += (double) a;
+        if (a != 0.f) {
+            s[i] += std::fabs((double) a);
+            n[i] += 1;
+        }
+    }
+};
+
 // ImageBlock::put, box-filter branch (filter radius <= 0.5 + RayEpsilon) — src/librender/imageblock.cpp:113,166-172 for a
 // block at offset 0 without border: pos = pos_ - 0.5; lo = ceil(pos - 0.5); the sample is added to pixel lo iff
 // 0 <= lo < size (the validity of the values is checked by the caller, :85-111).  SignalBlock::put is the same code
 // (signalblock.cpp:115,162-169).
-static bool imageblock_put_box(double *data, uint32_t w, uint32_t h, uint32_t nchan, float posx, float posy, const float *value, int offx = 0,
+template <typename Sink>
+static bool imageblock_put_box(const Sink &data, uint32_t w, uint32_t h, uint32_t nchan, float posx, float posy, const float *value, int offx = 0,
                                int offy = 0) {
     // pos = pos_ - (m_offset - m_border_size + .5f) with border 0; lo = ceil(pos - .5f)
     int lox = (int) std::ceil((posx - ((float) offx + .5f)) - .5f), loy = (int) std::ceil((posy - ((float) offy + .5f)) - .5f);
     if (!(lox >= 0 && lox < (int) w && loy >= 0 && loy < (int) h)) return false;
-    double *dst = data + (size_t) nchan * ((size_t) loy * w + (size_t) lox);
-    for (uint32_t k = 0; k < nchan; ++k) dst[k] += (double) value[k];
+    const size_t dst = (size_t) nchan * ((size_t) loy * w + (size_t) lox);
+    for (uint32_t k = 0; k < nchan; ++k) data.add(dst + k, value[k]);
     return true;
+}
+static bool imageblock_put_box(double *data, uint32_t w, uint32_t h, uint32_t nchan, float posx, float posy, const float *value, int offx = 0,
+                               int offy = 0) {
+    return imageblock_put_box(HistSink{data}, w, h, nchan, posx, posy, value, offx, offy);
 }
 
 // Reconstruction filters — src/rfilters/{box,tent,gaussian,mitchell,catmullrom,lanczos}.cpp (eval) and
@@ -2025,7 +2051,8 @@ static uint32_t launch_channels(const bf_launch &lp) {
 
 // one render_sample(); accumulates into hist (double accumulators so the CPU
 // sum itself is not the error source when compared with the GPU's fp32 atomics)
-static SampleOut render_sample(const OScene &sc, const bf_launch &lp, Sampler &smp, double *hist, uint64_t global_path) {
+template <typename Sink>
+static SampleOut render_sample(const OScene &sc, const bf_launch &lp, Sampler &smp, const Sink &hist, uint64_t global_path) {
     SampleOut out;
     // pixel of this sample: row-major over the film, spp consecutive paths per pixel (the reference's wavefront
     // branch, integrator.cpp:171-187; its scalar branch walks Morton-ordered blocks, same sample set per pixel)
@@ -2104,8 +2131,8 @@ static SampleOut render_sample(const OScene &sc, const bf_launch &lp, Sampler &s
             imageblock_put_wide(f, offx, offy, bw, bh, posx, posy, [&](int x, int y, float weight) {
                 const int gx = offx + x - border - (int) cx, gy = offy + y - border - (int) cy;      // film->put(block): crop-relative storage
                 if (gx < 0 || gx >= (int) film_w || gy < 0 || gy >= (int) film_h) return;
-                double *dst = hist + (size_t) nchan * ((size_t) gy * film_w + (size_t) gx);
-                for (uint32_t k = 0; k < nchan; ++k) dst[k] += (double) (aovs[k] * weight);
+                const size_t dst = (size_t) nchan * ((size_t) gy * film_w + (size_t) gx);
+                for (uint32_t k = 0; k < nchan; ++k) hist.add(dst + k, aovs[k] * weight);
             });
         }
         out.put = ok;
@@ -2120,7 +2147,8 @@ static SampleOut render_sample(const OScene &sc, const bf_launch &lp, Sampler &s
 // (receive_type "raw") + SignalBlock::put box branch (signalblock.cpp:162-169).
 // The reference runs in scalar_spectral (Q9): four wavelength lanes that carry
 // identical values for uniform spectra, so hsum() is 4 x the lane value.
-static SampleOut receive_sample(const OScene &sc, const bf_launch &lp, Sampler &smp, double *hist) {
+template <typename Sink>
+static SampleOut receive_sample(const OScene &sc, const bf_launch &lp, Sampler &smp, const Sink &hist) {
     SampleOut out;
     const bf_sensor &s = sc.sensor;
     float fx, fy, ax = .5f, ay = .5f;
@@ -2184,8 +2212,8 @@ static SampleOut receive_sample(const OScene &sc, const bf_launch &lp, Sampler &
             imageblock_put_wide(s.rfilter, wot, wof, (int) lp.bins, (int) lp.bins_y, tf0, tf1, [&](int x, int y, float weight) {
                 const int gx = x - border, gy = y - border;          // block cell -> window cell
                 if (gx < 0 || gx >= (int) lp.bins || gy < 0 || gy >= (int) lp.bins_y) return;
-                double *dst = hist + (size_t) (3 + P) * ((size_t) gy * lp.bins + (size_t) gx);
-                for (uint32_t k = 0; k < 3 + P; ++k) dst[k] += (double) (v[k] * weight);
+                const size_t dst = (size_t) (3 + P) * ((size_t) gy * lp.bins + (size_t) gx);
+                for (uint32_t k = 0; k < 3 + P; ++k) hist.add(dst + k, v[k] * weight);
             });
         }
         return out;
@@ -2196,10 +2224,10 @@ static SampleOut receive_sample(const OScene &sc, const bf_launch &lp, Sampler &
     out.put = ok;
     if (ok) {
         size_t off = (size_t) (3 + P) * ((size_t) ly * lp.bins + (size_t) lx);
-        hist[off + 0] += (double) a0;
-        hist[off + 1] += (double) a1;
-        hist[off + 2] += (double) a2;
-        for (uint32_t k = 0; k < P; ++k) hist[off + 3 + k] += (double) aov[k];
+        hist.add(off + 0, a0);
+        hist.add(off + 1, a1);
+        hist.add(off + 2, a2);
+        for (uint32_t k = 0; k < P; ++k) hist.add(off + 3 + k, aov[k]);
     }
     return out;
 }
@@ -2353,10 +2381,15 @@ uint32_t bfo_launch_channels(const bf_launch *lp) { return launch_channels(*lp);
  *             this is what the HIP path implements)
  * rng_mode 1: reference-literal single stream — sampler->seed(block_id *
  *             pixel_count + i) once per pixel, spp samples drawn in sequence
- *             (integrator.cpp:219-231); serial by construction. */
-bf_status bfo_render(const bfo_scene *s, const bf_launch *lp, int rng_mode, int n_threads, float *hist_out,
-                     bf_path_record *records_out, bf_stats *stats_out) {
+ *             (integrator.cpp:219-231); serial by construction.
+ * render_impl<true> also returns, per channel, the histogram in double (ref_out), the sum of the addends' magnitudes
+ * (S_out) and the number of non-zero addends (N_out): AddendSink. */
+extern "C++" {
+template <bool kAddends>
+static bf_status render_impl(const bfo_scene *s, const bf_launch *lp, int rng_mode, int n_threads, float *hist_out, double *ref_out,
+                             double *S_out, uint32_t *N_out, bf_path_record *records_out, bf_stats *stats_out) {
     if (!s || !lp || !hist_out) return BF_ERR_INVALID;
+    if (kAddends && (!ref_out || !S_out || !N_out)) return BF_ERR_INVALID;
     const bool is_receive = lp->mode == BF_MODE_RECEIVE_RAW || lp->mode == BF_MODE_RECEIVE_IQ;
     if (is_receive && (s->sc.sensor.type != BF_RECEIVER_OMNI && s->sc.sensor.type != BF_RECEIVER_WIGNER && s->sc.sensor.type != BF_RECEIVER_PHASED)) {
         g_err = "receive mode needs a receiver";
@@ -2386,6 +2419,8 @@ bf_status bfo_render(const bfo_scene *s, const bf_launch *lp, int rng_mode, int 
     if (rng_mode == 1) n_threads = 1;
     if (n_threads < 1) n_threads = 1;
     std::vector<std::vector<double>> th_hist(n_threads, std::vector<double>(nchan, 0.0));
+    std::vector<std::vector<double>> th_S(kAddends ? n_threads : 0, std::vector<double>(nchan, 0.0));
+    std::vector<std::vector<uint32_t>> th_N(kAddends ? n_threads : 0, std::vector<uint32_t>(nchan, 0u));
     std::vector<bf_stats> th_stats(n_threads);
     for (auto &t : th_stats) std::memset(&t, 0, sizeof(t));
     auto t0 = std::chrono::steady_clock::now();
@@ -2405,13 +2440,18 @@ bf_status bfo_render(const bfo_scene *s, const bf_launch *lp, int rng_mode, int 
         t_tris = 0;
         Sampler smp;
         if (rng_mode == 1) smp.rng.seed(lp->seed + 0);
+        using Sink = typename std::conditional<kAddends, AddendSink, HistSink>::type;
+        Sink sink;
+        if constexpr (kAddends)
+            sink = Sink{th_hist[tid].data(), th_S[tid].data(), th_N[tid].data()};
+        else
+            sink = Sink{th_hist[tid].data()};
         for (uint64_t i = lo; i < hi; ++i) {
             if (rng_mode == 0) smp.rng.seed(lp->seed + lp->path_offset + i);
             // literal scalar mode on a multi-pixel film: one stream per pixel (render_block, integrator.cpp:221)
             if (rng_mode == 1 && film_multi(*lp) && (lp->path_offset + i) % lp->spp == 0)
                 smp.rng.seed(lp->seed + (lp->path_offset + i) / lp->spp);
-            SampleOut o = is_receive ? receive_sample(sc, *lp, smp, th_hist[tid].data())
-                                     : render_sample(sc, *lp, smp, th_hist[tid].data(), lp->path_offset + i);
+            SampleOut o = is_receive ? receive_sample(sc, *lp, smp, sink) : render_sample(sc, *lp, smp, sink, lp->path_offset + i);
             bf_stats &st = th_stats[tid];
             st.n_paths++;
             st.n_rays_closest += o.pr.n_closest;
@@ -2443,6 +2483,17 @@ bf_status bfo_render(const bfo_scene *s, const bf_launch *lp, int rng_mode, int 
         double acc = 0;
         for (int t = 0; t < n_threads; ++t) acc += th_hist[t][k];
         hist_out[k] = (float) acc;
+        if constexpr (kAddends) {
+            double sa = 0;
+            uint32_t na = 0;
+            for (int t = 0; t < n_threads; ++t) {
+                sa += th_S[t][k];
+                na += th_N[t][k];
+            }
+            ref_out[k] = acc;
+            S_out[k] = sa;
+            N_out[k] = na;
+        }
     }
     if (stats_out) {
         std::memset(stats_out, 0, sizeof(*stats_out));
@@ -2458,6 +2509,18 @@ bf_status bfo_render(const bfo_scene *s, const bf_launch *lp, int rng_mode, int 
         stats_out->kernel_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
     }
     return BF_OK;
+}
+}  // extern "C++"
+
+bf_status bfo_render(const bfo_scene *s, const bf_launch *lp, int rng_mode, int n_threads, float *hist_out,
+                     bf_path_record *records_out, bf_stats *stats_out) {
+    return render_impl<false>(s, lp, rng_mode, n_threads, hist_out, nullptr, nullptr, nullptr, records_out, stats_out);
+}
+/* bfo_render plus, per channel: ref_out (double) the histogram before its rounding to float, S_out the sum of |a| over the
+ * cell's addends a, N_out the number of non-zero addends (the floats the render adds, exactly) */
+bf_status bfo_render_addends(const bfo_scene *s, const bf_launch *lp, int rng_mode, int n_threads, float *hist_out, double *ref_out,
+                             double *S_out, uint32_t *N_out, bf_path_record *records_out, bf_stats *stats_out) {
+    return render_impl<true>(s, lp, rng_mode, n_threads, hist_out, ref_out, S_out, N_out, records_out, stats_out);
 }
 
 bf_status bfo_trace_closest(const bfo_scene *s, uint64_t n, const float *rays, float *out_t, uint32_t *out_prim,

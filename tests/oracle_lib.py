@@ -2,6 +2,7 @@
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple
 
 import numpy as np
 
@@ -10,6 +11,12 @@ from beifong_amd import capi
 ORACLE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
 LIB = os.path.join(ORACLE_DIR, "libbf_oracle.so")
 _lib = None
+
+
+class Addends(NamedTuple):
+    ref: np.ndarray      # float64: the histogram before its rounding to float32
+    S: np.ndarray        # float64: sum of |a| over the cell's addends a
+    N: np.ndarray        # uint32: number of non-zero addends
 
 
 def build():
@@ -41,6 +48,7 @@ def load_from(path):
     lib.bfo_launch_channels.argtypes = [C.POINTER(capi.bf_launch)]
     lib.bfo_launch_channels.restype = C.c_uint32
     lib.bfo_render.argtypes = [vp, C.POINTER(capi.bf_launch), C.c_int, C.c_int, vp, vp, C.POINTER(capi.bf_stats)]
+    lib.bfo_render_addends.argtypes = [vp, C.POINTER(capi.bf_launch), C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(capi.bf_stats)]
     lib.bfo_trace_closest.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bfo_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bfo_ray_intersect_full.argtypes = [vp, vp, vp]
@@ -102,14 +110,23 @@ class OracleScene:
         except Exception:
             pass
 
-    def render(self, launch, rng_mode=0, threads=1, records=False):
+    def render(self, launch, rng_mode=0, threads=1, records=False, addends=False):
+        """(hist, records, stats); addends=True appends Addends(ref, S, N) per channel: the histogram in float64, the sum of
+        the magnitudes of the cell's addends and the number of its non-zero addends (tests/hist_bound.py bounds with them)."""
         n = self.lib.bfo_launch_channels(C.byref(launch))
         hist = np.zeros(n, np.float32)
         rec = np.zeros(launch.n_paths, capi.PATH_RECORD_DTYPE) if records else None
         st = capi.bf_stats()
-        s = self.lib.bfo_render(self.handle, C.byref(launch), rng_mode, threads, _ptr(hist), _ptr(rec), C.byref(st))
+        if addends:
+            ref, S, N = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.uint32)
+            s = self.lib.bfo_render_addends(self.handle, C.byref(launch), rng_mode, threads, _ptr(hist), _ptr(ref), _ptr(S), _ptr(N),
+                                            _ptr(rec), C.byref(st))
+        else:
+            s = self.lib.bfo_render(self.handle, C.byref(launch), rng_mode, threads, _ptr(hist), _ptr(rec), C.byref(st))
         if s != 0:
             raise RuntimeError(f"bfo_render failed: {self.lib.bfo_last_error().decode()}")
+        if addends:
+            return hist, rec, st, Addends(ref, S, N)
         return hist, rec, st
 
     def trace_closest(self, rays):

@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 
 from beifong_amd import capi, scenes
+from tests.hist_bound import assert_close_hists as _close_hist, assert_fp32_sum, count_channels
 from tests.oracle_lib import OracleScene
+from tests.scene_builders import _bus_receive_with_mesh, bus_radar_shifted, bus_receive_shifted  # (tools/soak_parity.py imports the first from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -18,11 +20,6 @@ def _same_records(a, b):
     for k in ("L", "aux"):
         assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
     assert np.array_equal(a["n_rays"], b["n_rays"]) and np.array_equal(a["valid"], b["valid"])
-
-
-def _close_hist(hb, hs, n_paths, amax):
-    atol = n_paths * 2.0 ** -24 * max(amax, 1.0) * 4
-    assert np.allclose(hb, hs, rtol=2e-5, atol=atol), float(np.abs(hb - hs).max())
 
 
 @pytest.mark.parametrize("mega", [False, True])
@@ -42,12 +39,13 @@ def test_batch_of_seeds_equals_stand_alone_renders(hiplib, mega):
                               flags=lp.flags)
         hs, rs, ss = g.render(l1, records=True)
         _same_records(rb[k], rs)
-        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()))
-        assert hb[k][4] == hs[4]
         rays += ss.n_rays_closest + ss.n_rays_shadow
         l1.flags = 0
-        ho, ro, _ = o.render(l1, records=True, threads=8)
+        ho, ro, _, add = o.render(l1, records=True, threads=8, addends=True)
         _same_records(rb[k], ro)
+        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, l1, sd)
+        assert_fp32_sum(hb[k], add.ref, add.S, add.N, f"batch render {k}", counts=count_channels(l1, sd))
+        assert hb[k][4] == hs[4]
     assert sb.n_rays_closest + sb.n_rays_shadow == rays and sb.n_paths == lp.n_paths * len(seeds)
     assert np.array_equal(rb[0]["L"], rb[3]["L"])          # same seed, same render
 
@@ -61,19 +59,22 @@ def test_batch_global_atomics_and_single_render(hiplib):
     lp2 = capi.make_launch(lp.mode, lp.n_paths, seed=lp.seed, bins=lp.bins, bin_width=lp.bin_width, color_mode=lp.color_mode,
                            flags=capi.BF_FLAG_GLOBAL_ATOMICS)
     hb2, rb2, _ = g.render_batch(lp2, 3, seeds=seeds[:3], records=True)
+    o = OracleScene(sd)
     for k in (0, 7, 15):
         l1 = capi.make_launch(lp.mode, lp.n_paths, seed=int(seeds[k]), bins=lp.bins, bin_width=lp.bin_width, color_mode=lp.color_mode)
         hs, rs, _ = g.render(l1, records=True)
+        add = o.render(l1, threads=16, addends=True)[3]
         _same_records(rb[k], rs)
-        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, l1, sd)
         if k < 3:
             _same_records(rb2[k], rs)
-            _close_hist(hb2[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+            _close_hist(hb2[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, l1, sd)
     h1, r1, _ = g.render_batch(lp, 1, seeds=[99], records=True)
     l1 = capi.make_launch(lp.mode, lp.n_paths, seed=99, bins=lp.bins, bin_width=lp.bin_width, color_mode=lp.color_mode)
     hs, rs, _ = g.render(l1, records=True)
     _same_records(r1[0], rs)
-    _close_hist(h1[0], hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+    add = o.render(l1, threads=16, addends=True)[3]
+    _close_hist(h1[0], hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, l1, sd)
 
 
 @pytest.mark.parametrize("iq", [False, True])
@@ -94,7 +95,11 @@ def test_batch_with_mesh_offsets_equals_translated_scenes(hiplib, iq):
         g2.translate_meshes(off)
         hs, rs, _ = g2.render(lp, records=True)
         _same_records(rb[k], rs)
-        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+        sdk = bus_receive_shifted(off)                    # the oracle on the scene rebuilt with the shifted bus: same paths
+        _, ro, _, add = OracleScene(sdk).render(lp, records=True, threads=16, addends=True)
+        _same_records(rs, ro)
+        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, lp, sdk)
+        assert_fp32_sum(hb[k], add.ref, add.S, add.N, f"batch with offset {k}", counts=count_channels(lp, sdk))
     assert not np.array_equal(rb[0]["L"], rb[2]["L"])
     # per-render seeds AND offsets, against the oracle on a rebuilt scene
     from beifong_amd import meshgen
@@ -110,19 +115,6 @@ def test_batch_with_mesh_offsets_equals_translated_scenes(hiplib, iq):
     _same_records(rb[k], ro)
 
 
-def _bus_receive_with_mesh(v, f, t_bins=256, dr=0.1, lambda_band_nm=None):
-    """scenes.bus_receive with the bus vertices replaced (same endpoints, materials, ADC)."""
-    from beifong_amd import meshgen
-    orig_bus, orig_place = meshgen.bus, meshgen.place
-    try:
-        meshgen.bus = lambda n, seed=1: (v, f)
-        meshgen.place = lambda vv, yaw_deg=0.0, translate=(0, 0, 0): vv
-        sd, _ = scenes.bus_receive(n_tris=len(f), n_paths=64, t_bins=t_bins, dr=dr, lambda_band_nm=lambda_band_nm)
-    finally:
-        meshgen.bus, meshgen.place = orig_bus, orig_place
-    return sd
-
-
 def test_batch_deep_tail_paths_with_offsets(hiplib):
     """Enough paths that the wavefront iterations hand a populated pool to the tail kernel (lane, quad and row traversals
     all see shifted meshes), range mode with vertex normals (make_si interpolates them at the shifted hit)."""
@@ -132,11 +124,16 @@ def test_batch_deep_tail_paths_with_offsets(hiplib):
     hb, rb, sb = g.render_batch(lp, 3, offsets=offsets, records=True)
     assert sb.n_rays_tail > 0
     g2 = capi.Scene(sd)
+    mesh = scenes.bus_mesh(20000)                          # the mesh scenes.bus_radar(n_tris=20000) placed
     for k, off in enumerate(offsets):
         g2.translate_meshes(off)
         hs, rs, _ = g2.render(lp, records=True)
         _same_records(rb[k], rs)
-        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+        sdk, _ = bus_radar_shifted(mesh, off, n_paths=lp.n_paths, bins=256, dr=0.1)
+        _, ro, _, add = OracleScene(sdk).render(lp, records=True, threads=16, addends=True)
+        _same_records(rs, ro)
+        _close_hist(hb[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, lp, sdk)
+        assert_fp32_sum(hb[k], add.ref, add.S, add.N, f"deep-tail batch with offset {k}", counts=count_channels(lp, sdk))
 
 
 def test_batch_rejects_what_it_cannot_do(hiplib):

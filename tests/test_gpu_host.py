@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from beifong_amd import capi, scenes
+from tests.hist_bound import assert_fp32_sum, count_channels
 from tests.oracle_lib import OracleScene
 from tests.test_host import HOST, RECEIVE_SCENE, TRANS_RAD_LIKE
 
@@ -280,8 +281,9 @@ def test_file_loaded_mesh_renders_on_hip(mitsuba, hiplib, tmp_path, kind):
     bmp = np.array(sensor.film().bitmap(raw=True)).reshape(-1)
     lp = scene.integrator().launch_for(sensor)
     assert lp.n_paths == 40000 and bmp[4] == 40000
-    ho, ro, so = OracleScene(desc).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(desc).render(lp, records=True, threads=8, addends=True)
     assert np.allclose(bmp, ho, rtol=2e-5, atol=40000 * 2.0 ** -24 * max(1.0, float(np.abs(ro["L"]).max())) * 4)
+    assert_fp32_sum(bmp, add.ref, add.S, add.N, "plugin surface film", counts=count_channels(lp, desc))
     assert bmp[5:].sum() > 0
     # per path, on the very description the host flattened
     g = capi.Scene(desc)

@@ -11,13 +11,10 @@ import numpy as np
 import pytest
 
 from beifong_amd import capi, scenes
+from tests.hist_bound import assert_close_hists as _close_hist
+from tests.oracle_lib import OracleScene
 
 pytestmark = pytest.mark.gpu
-
-
-def _close_hist(hb, hs, n_paths, amax):
-    atol = n_paths * 2.0 ** -24 * max(amax, 1.0) * 4
-    assert np.allclose(hb, hs, rtol=2e-5, atol=atol), float(np.abs(hb - hs).max())
 
 
 def test_sharded_render_on_one_device_is_the_plain_render(hiplib):
@@ -26,7 +23,8 @@ def test_sharded_render_on_one_device_is_the_plain_render(hiplib):
     assert g.info().device == 0
     hs, rs, ss = g.render(lp, records=True)
     hm, sm = capi.render_sharded([g], lp)
-    _close_hist(hm, hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+    add = OracleScene(sd).render(lp, threads=16, addends=True)[3]
+    _close_hist(hm, hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, lp, sd)
     assert hm[3] == hs[3] and hm[4] == hs[4] == lp.n_paths           # alpha and weight channels: integer sums, exact
     assert (sm.n_paths, sm.n_rays_closest, sm.n_rays_shadow, sm.n_bounces) == (ss.n_paths, ss.n_rays_closest, ss.n_rays_shadow, ss.n_bounces)
 
@@ -46,7 +44,8 @@ def test_sharded_device_entry_and_a_communicator_of_one(hiplib):
     devs = (C.c_int * 1)(0)
     capi.check(hiplib, hiplib.bf_allreduce_device(devs, 1, bufs, d.numel(), streams), "bf_allreduce_device")
     s.synchronize()
-    _close_hist(d.cpu().numpy(), hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+    add = OracleScene(sd).render(lp, threads=16, addends=True)[3]
+    _close_hist(d.cpu().numpy(), hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, lp, sd)
     # the same device twice is a caller error, not a hang inside RCCL
     devs2 = (C.c_int * 2)(0, 0)
     bufs2 = (C.c_void_p * 2)(C.c_void_p(d.data_ptr()), C.c_void_p(d.data_ptr()))
@@ -65,7 +64,8 @@ def test_sharded_rolling_shards_need_a_flush_and_reduce_by_hand(hiplib):
     capi.render_sharded_device([g], lr, [d.data_ptr()])
     g.flush()
     g.sync()
-    _close_hist(d.cpu().numpy(), hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+    add = OracleScene(sd).render(lp, threads=16, addends=True)[3]
+    _close_hist(d.cpu().numpy(), hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, lp, sd)
 
 
 def test_entry_points_run_on_the_handles_device(hiplib):

@@ -11,7 +11,9 @@ import pytest
 
 from beifong_amd import capi, meshgen, scenes
 from beifong_amd.scenedesc import SceneDesc, Transform4f
+from tests.hist_bound import assert_fp32_sum, assert_two_fp32_sums, count_channels
 from tests.oracle_lib import OracleScene
+from tests.scene_builders import _fuzz_scene, _live_fuzz_scene, _zoo_scene
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -102,7 +104,7 @@ def _render_compare(sd, lp, hist_rtol=2e-5):
     """Both device pipelines (wavefront = default, megakernel = ablation flag)
     against the oracle."""
     o = OracleScene(sd)
-    oracle_out = o.render(lp, records=True, threads=8)
+    oracle_out = o.render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     flags0 = lp.flags
     lp.flags = flags0 | capi.BF_FLAG_MEGAKERNEL
@@ -113,7 +115,7 @@ def _render_compare(sd, lp, hist_rtol=2e-5):
 
 def _render_compare_one(g, lp, oracle_out, hist_rtol):
     hg, rg, sg = g.render(lp, records=True)
-    ho, ro, so = oracle_out
+    ho, ro, so, add = oracle_out
     # integer counters and per-path results: exact
     assert np.array_equal(rg["n_rays"], ro["n_rays"])
     assert np.array_equal(rg["valid"], ro["valid"])
@@ -128,6 +130,8 @@ def _render_compare_one(g, lp, oracle_out, hist_rtol):
     amax = float(np.abs(ro["L"]).max()) if len(ro) else 0.0
     atol = n * 2.0 ** -24 * max(amax, 1.0) * 4
     assert np.allclose(hg, ho, rtol=hist_rtol, atol=atol), np.abs(hg - ho).max()
+    # and every cell at its own scale: an fp32 sum of the oracle's addends (tests/hist_bound.py)
+    assert_fp32_sum(hg, add.ref, add.S, add.N, f"render flags {lp.flags:#x}", counts=count_channels(lp, g.holder))
     rmse = float(np.sqrt(np.mean((hg / n - ho / n) ** 2)))
     # BASELINE.json target: per-range-bin RMSE < 1e-4 (relative to the largest bin when bins exceed 1)
     assert rmse < 1e-4 * max(1.0, float(np.abs(ho / n).max()))
@@ -237,6 +241,9 @@ def test_render_global_atomics_flag_matches_lds(hiplib):
     lp.flags = capi.BF_FLAG_GLOBAL_ATOMICS | capi.BF_FLAG_STATS
     h2, _, st = g.render(lp)
     assert np.allclose(h1, h2, rtol=2e-5, atol=1e-3)
+    add = OracleScene(sd).render(lp, threads=16, addends=True)[3]
+    assert_two_fp32_sums(h1, h2, add.S, add.N, "LDS vs global atomics", counts=count_channels(lp, sd))
+    assert_fp32_sum(h2, add.ref, add.S, add.N, "global atomics", counts=count_channels(lp, sd))
     assert st.n_nodes_visited > 0 and st.n_tris_tested > 0
 
 
@@ -269,7 +276,7 @@ def test_bench_step_every_path_bit_exact(hiplib):
     rays — through the default pipeline (16 Mi-slot pool, planned launches, tail kernel): every one of the 16.7 M
     per-path records (radiance bits, path length bits, validity, ray count) and every counter equal to the oracle's."""
     sd, lp = scenes.bus_radar(n_tris=200_000, n_paths=1 << 24, bins=256, dr=0.1, seed=1)
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=16)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=16, addends=True)
     g = capi.Scene(sd)
     for rep in range(2):                          # the second render of a shape is the planned (host-sync-free) one
         hg, rg, sg = g.render(lp, records=True)
@@ -282,6 +289,7 @@ def test_bench_step_every_path_bit_exact(hiplib):
         rmse = float(np.sqrt(np.mean((hg / n - ho / n) ** 2)))
         assert rmse < 1e-4                           # BASELINE.json's per-range-bin target
         assert np.allclose(hg, ho, rtol=2e-4, atol=n * 2.0 ** -24 * float(np.abs(ro["L"]).max()) * 4)
+        assert_fp32_sum(hg, add.ref, add.S, add.N, f"bench step render {rep}", counts=count_channels(lp, sd))
     assert sg.n_rays_closest + sg.n_rays_shadow > 44_000_000
 
 
@@ -294,7 +302,7 @@ def test_full_size_c2_recv_every_path_bit_exact(hiplib, iq):
                                 lambda_band_nm=(8.6e6 * 0.999, 8.6e6 * 1.001) if iq else None)
     if iq:
         lp.mode = capi.BF_MODE_RECEIVE_IQ
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=16)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=16, addends=True)
     hg, rg, sg = capi.Scene(sd).render(lp, records=True)
     assert np.array_equal(rg["n_rays"], ro["n_rays"]) and np.array_equal(rg["valid"], ro["valid"])
     assert np.array_equal(rg["aux"].view(np.uint32), ro["aux"].view(np.uint32))
@@ -304,6 +312,7 @@ def test_full_size_c2_recv_every_path_bit_exact(hiplib, iq):
     assert np.array_equal(a[:, 2], b[:, 2])                                   # W: samples per ADC cell
     scale = max(float(np.abs(b[:, :2]).max()), 1e-30)
     assert np.abs(a[:, :2] - b[:, :2]).max() < 2e-4 * scale
+    assert_fp32_sum(hg, add.ref, add.S, add.N, f"C2-recv iq={iq}", counts=count_channels(lp, sd))
 
 
 def test_occluded_sample_with_non_finite_bsdf_value_poisons_the_path(hiplib):
@@ -448,8 +457,10 @@ def test_concurrent_renders_on_two_streams(hiplib):
             h.zero_()
             handles[j].render_device(lp, h.data_ptr(), stream=streams[j].cuda_stream)
     torch.cuda.synchronize()
-    for h in hists:
+    add = OracleScene(sd).render(lp, threads=16, addends=True)[3]
+    for k, h in enumerate(hists):
         assert np.allclose(h.cpu().numpy(), ref, rtol=1e-4, atol=1e-2)
+        assert_two_fp32_sums(h.cpu().numpy(), ref, add.S, add.N, f"stream render {k}", counts=count_channels(lp, sd))
 
 
 def test_planned_render_matches_first_render(hiplib):
@@ -458,14 +469,14 @@ def test_planned_render_matches_first_render(hiplib):
     give every path the same result (and the oracle's)."""
     sd, lp = scenes.bus_radar(n_tris=20000, n_paths=1 << 16, bins=256, dr=0.1)
     o = OracleScene(sd)
-    oracle_out = o.render(lp, records=True, threads=8)
+    oracle_out = o.render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     for _ in range(3):                       # 1st: synchronous, 2nd/3rd: planned (3rd after feedback)
         _render_compare_one(g, lp, oracle_out, 2e-5)
     lp2 = capi.make_launch(lp.mode, 1 << 16, seed=lp.seed + 17, bins=lp.bins, bin_width=lp.bin_width, color_mode=lp.color_mode)
-    _render_compare_one(g, lp2, o.render(lp2, records=True, threads=8), 2e-5)     # new seed, same plan
+    _render_compare_one(g, lp2, o.render(lp2, records=True, threads=8, addends=True), 2e-5)     # new seed, same plan
     lp3 = capi.make_launch(lp.mode, 3000, seed=lp.seed, bins=lp.bins, bin_width=lp.bin_width, color_mode=lp.color_mode)
-    _render_compare_one(g, lp3, o.render(lp3, records=True, threads=8), 2e-5)     # other shape: plan not applicable
+    _render_compare_one(g, lp3, o.render(lp3, records=True, threads=8, addends=True), 2e-5)     # other shape: plan not applicable
 
 
 def test_update_endpoints_equals_fresh_scene(hiplib):
@@ -483,7 +494,7 @@ def test_update_endpoints_equals_fresh_scene(hiplib):
         assert np.array_equal(r_u["aux"].view(np.uint32), r_f["aux"].view(np.uint32))
         assert np.array_equal(r_u["n_rays"], r_f["n_rays"])
         o = OracleScene(sd1)
-        _render_compare_one(g, lp, o.render(lp, records=True, threads=8), 2e-5)
+        _render_compare_one(g, lp, o.render(lp, records=True, threads=8, addends=True), 2e-5)
     h0, _, _ = capi.Scene(sd0).render(lp)
     assert not np.allclose(h0, h_u)                       # the radar really moved
     sd_other, _ = scenes.trans_rad(spp=16)
@@ -533,7 +544,7 @@ def test_small_pool_regenerates_paths_into_freed_slots(hiplib, monkeypatch):
     in the host-driven first render, in planned renders and across the tail kernel."""
     sd, lp = scenes.bus_radar(n_tris=20000, n_paths=50000, bins=256, dr=0.1)
     o = OracleScene(sd)
-    oracle_out = o.render(lp, records=True, threads=8)
+    oracle_out = o.render(lp, records=True, threads=8, addends=True)
     for pool, tail in (("4096", "512"), ("8192", "100000"), ("1024", "0")):
         monkeypatch.setenv("BF_WF_POOL", pool)
         monkeypatch.setenv("BF_WF_TAIL", tail)
@@ -554,7 +565,7 @@ def test_receive_iq_mode(hiplib, tx):
     assert np.count_nonzero(cells[:, 0]) > 5 and np.count_nonzero(cells[:, 1]) > 5
     g = capi.Scene(sd)
     o = OracleScene(sd)
-    out = o.render(lp, records=True, threads=8)
+    out = o.render(lp, records=True, threads=8, addends=True)
     for _ in range(2):
         _render_compare_one(g, lp, out, 2e-5)              # second render: planned
 
@@ -576,7 +587,7 @@ def test_translate_meshes_equals_rebuilt_scene(hiplib):
             assert np.array_equal(r_t[k].view(np.uint32), r_f[k].view(np.uint32))
         assert np.array_equal(r_t["n_rays"], r_f["n_rays"])
         assert not np.array_equal(r_t["L"], r0["L"])
-        _render_compare_one(g, lp, OracleScene(sd1).render(lp, records=True, threads=8), 2e-5)
+        _render_compare_one(g, lp, OracleScene(sd1).render(lp, records=True, threads=8, addends=True), 2e-5)
     g.translate_meshes([0, 0, 0])
     _, r_b, _ = g.render(lp, records=True)
     assert np.array_equal(r_b["L"].view(np.uint32), r0["L"].view(np.uint32))
@@ -611,58 +622,6 @@ def test_pulse_sweep_range_doppler_peak(hiplib):
     h_k, _, _ = g.render(lp)
     assert np.allclose(h_k.reshape(1, 3), cube[k], rtol=1e-4, atol=1e-6 * np.abs(cube[k]).max())
 
-
-def _planar_uv(v):
-    """Texture coordinates for the zoo meshes: an oblique planar projection, with a patch collapsed to one point so
-    that some triangles carry a degenerate parameterisation (mesh.cpp:500-502 keeps coordinate_system(n) there)."""
-    v = np.asarray(v, np.float32)
-    uv = np.stack([0.37 * v[:, 0] + 0.11 * v[:, 2], 0.29 * v[:, 1] - 0.2 * v[:, 2]], 1).astype(np.float32)
-    uv[v[:, 2] > np.quantile(v[:, 2], 0.9)] = [0.25, 0.75]
-    return uv
-
-
-def _zoo_scene(two_emitters=True, receive=False, uv=False):
-    """Small scene exercising the branches the radar configs do not: several emitters (uniform emitter
-    selection, scene.cpp:180-230 / 249-299), one-sided materials, a mesh with and a mesh without normals."""
-    sd = SceneDesc()
-    T = Transform4f
-    d0 = T.rotate([1, 0, 0], 90) * T.rotate([0, 1, 0], 90)
-    ap = T.translate([0, 0, 0.3]) * d0 * T.scale([20e-3, 50e-3, 1])
-    c, lmin, lmax = sd.physics.c, sd.physics.lambda_min_nm, sd.physics.lambda_max_nm
-    if receive:
-        txa = sd.add_rectangle(ap, sd.add_diffuse(0.0))
-        rxa = sd.add_rectangle(ap, sd.add_diffuse(0.5))
-        tau = 2.0 * 0.1 / c
-        f_c = c / (0.5 * (lmin + lmax) * 1e-9)
-        sd.add_wigner_transmitter(txa, signaltype="pulse", amplitude=1.0, freq_centre=f_c, freq_ext=1.0 / tau, pulse_len=tau,
-                                  prf=1.0 / (64 * tau), gain=1.0)
-        if two_emitters:
-            tx2 = sd.add_rectangle(T.translate([0.0, 1.0, 0.6]) * d0 * T.scale([0.1, 0.1, 1]), sd.add_diffuse(0.0))
-            sd.add_area_transmitter(tx2, 0.5)
-        sd.set_receiver(rxa, kind="omnidirectional", adc_sampling_start=0.0, adc_sampling_end=64 * tau, t_bins=64, f_bins=1,
-                        t_bandwidth=64 * tau, f_bandwidth=2.0 * c / (lmin * 1e-9), freq_centre=f_c,
-                        freq_ext=c / (lmin * 1e-9) - c / (lmax * 1e-9))
-        lp = capi.make_launch(capi.BF_MODE_RECEIVE_RAW, 30000, seed=9, bins=64, bins_y=1)
-    else:
-        txa = sd.add_rectangle(ap, sd.add_diffuse(0.0))
-        sd.add_area_emitter(txa, 500.0)
-        if two_emitters:
-            sd.add_spot(T.look_at([0.5, -1.0, 2.0], [4.0, 0.0, 0.0], [0, 0, 1]), intensity=30.0, cutoff_angle=30.0, beam_width=20.0)
-            tx3 = sd.add_rectangle(T.translate([2.0, 2.0, 2.5]) * T.rotate([1, 0, 0], 180) * T.scale([0.3, 0.3, 1]), sd.add_diffuse(0.0))
-            sd.add_area_emitter(tx3, 20.0)
-        sd.set_perspective(T.translate([0, 0, 0.3]) * d0, fov=60.0, near_clip=0.1, far_clip=100.0)
-        lp = capi.make_launch(capi.BF_MODE_RANGE, 30000, seed=9, bins=128, bin_width=0.1, color_mode=capi.BF_COLOR_RGB)
-    sd.add_rectangle(T.scale([20, 20, 1]), sd.add_diffuse(0.4, twosided=False))
-    v, f, n = meshgen.car_body(6000, seed=3)
-    vc = meshgen.place(v, 25.0, (4.0, 0.5, 0.8))
-    # uv=True: anisotropic roughness, so that the shading frame's s (from dp_du, interaction.h:159-162) shapes the lobe
-    sd.add_mesh(vc, f, sd.add_roughconductor(alpha=0.3, alpha_v=0.05 if uv else None, twosided=False, specular_reflectance=0.7),
-                normals=meshgen.vertex_normals(vc, f), texcoords=_planar_uv(vc) if uv else None)
-    v, f = meshgen.bus(4000, seed=6)
-    vb = meshgen.place(v, -40.0, (7.0, -3.0, 1.7), scale=0.5)
-    sd.add_mesh(vb, f, sd.add_diffuse(0.9, twosided=True), texcoords=_planar_uv(vb) if uv else None)
-    sd.finalize()
-    return sd, lp
 
 
 @pytest.mark.parametrize("receive", [False, True])
@@ -734,7 +693,7 @@ def test_phased_array_steering_update(hiplib):
     g = capi.Scene(sd0)
     h0, _, _ = g.render(lp)
     g.update_endpoints(sd1)
-    _render_compare_one(g, lp, OracleScene(sd1).render(lp, records=True, threads=8), 2e-5)
+    _render_compare_one(g, lp, OracleScene(sd1).render(lp, records=True, threads=8, addends=True), 2e-5)
     h1, _, _ = g.render(lp)
     assert not np.allclose(h0, h1)
     sd2, _ = scenes.phased_receive(n_tris=20000, n_paths=20000, n_elems=3)
@@ -770,7 +729,7 @@ def test_cross_seed_statistical_agreement(hiplib):
 
 def _film_compare(sd, lp, film, chan):
     """Multi-pixel film: per-path records exact, per-pixel histograms to summation order, both pipelines."""
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     out = None
     for flags in (capi.BF_FLAG_MEGAKERNEL, 0, capi.BF_FLAG_GLOBAL_ATOMICS):
@@ -785,6 +744,7 @@ def _film_compare(sd, lp, film, chan):
         assert np.array_equal(a[:, :, 3:5], b[:, :, 3:5])                    # alpha and weight: integer counts
         amax = float(np.abs(ro["L"]).max())
         assert np.allclose(a, b, rtol=2e-5, atol=lp.spp * 2.0 ** -24 * max(amax, 1.0) * 4)
+        assert_fp32_sum(hg, add.ref, add.S, add.N, f"film {film} flags {flags:#x}", counts=count_channels(lp, sd))
         out = a
     lp.flags = 0
     return out
@@ -839,124 +799,11 @@ def test_multi_pixel_range_image_of_the_zoo(hiplib, mode, film):
         assert np.allclose(parts[0][0] + parts[1][0], img.ravel(), rtol=2e-5, atol=1e-4)
 
 
-def _fuzz_receive_endpoints(sd, rng):
-    """gen-3 endpoints for _fuzz_scene: one or two transmitters (wigner pulse / linfmcw, area), an omnidirectional or
-    Wigner receiver with a random ADC, RECEIVE_RAW (with or without phase AOVs) or RECEIVE_IQ."""
-    T = Transform4f
-    c, lmin, lmax = sd.physics.c, sd.physics.lambda_min_nm, sd.physics.lambda_max_nm
-    tau = float(rng.uniform(0.5, 3.0)) * 0.1 / c
-    f_c = c / (0.5 * (lmin + lmax) * 1e-9)
-    t_bins, f_bins = int(rng.integers(1, 96)), int(rng.choice([1, 1, 2, 5]))
-    pose = T.translate([0.2, -0.3, 1.2]) * T.rotate([1, 0, 0], float(rng.uniform(100, 260))) * T.scale([0.05, 0.08, 1])
-    for k in range(int(rng.integers(1, 3))):
-        tx = sd.add_rectangle(pose if k == 0 else T.translate([float(rng.uniform(-2, 2)), float(rng.uniform(-2, 2)), 3.0]) *
-                              T.rotate([1, 0, 0], 180) * T.scale([0.1, 0.2, 1]), sd.add_diffuse(0.0))
-        if rng.random() < 0.6:
-            sd.add_wigner_transmitter(tx, signaltype="linfmcw" if rng.random() < 0.4 else "pulse", amplitude=float(rng.uniform(0.5, 2)),
-                                      freq_centre=f_c, freq_ext=1.0 / tau, pulse_len=tau, prf=1.0 / (t_bins * tau), gain=float(rng.uniform(0.5, 2)))
-        else:
-            sd.add_area_transmitter(tx, float(rng.uniform(0.5, 5)))
-    rx = sd.add_rectangle(pose, sd.add_diffuse(0.5))
-    sd.set_receiver(rx, kind="wigner" if rng.random() < 0.4 else "omnidirectional", adc_sampling_start=float(rng.choice([0.0, 2 * tau])),
-                    adc_sampling_end=t_bins * tau, t_bins=t_bins, f_bins=f_bins, t_bandwidth=t_bins * tau,
-                    f_bandwidth=2.0 * c / (lmin * 1e-9), freq_centre=f_c, freq_ext=c / (lmin * 1e-9) - c / (lmax * 1e-9),
-                    gain=float(rng.uniform(0.5, 2)), sig_is_delta=bool(rng.integers(2)))
-    sd.finalize()
-    iq = rng.random() < 0.3
-    lp = capi.make_launch(capi.BF_MODE_RECEIVE_IQ if iq else capi.BF_MODE_RECEIVE_RAW, 6000, seed=int(rng.integers(1 << 30)), bins=t_bins,
-                          bins_y=f_bins, max_depth=int(rng.choice([-1, 2, 3, 8])), rr_depth=int(rng.choice([1, 3, 5, 50])),
-                          phase_bins=0 if iq or rng.random() < 0.5 else int(rng.integers(1, 20)))
-    return sd, lp
-
-
-def _fuzz_scene(seed, receive=False):
-    """A random small scene of the render modes: a box of 3-6 rectangles and 1-3 meshes with random materials
-    (diffuse / rough conductor, Beckmann / GGX, one- and two-sided, isotropic or not, visible-normal sampling or
-    not), a spot or area emitter (or both), fluxmeter or perspective sensor (possibly with a small film), random
-    mode, colour mode, depth limits and bin widths."""
-    rng = np.random.default_rng(1000 + seed + (500 if receive else 0))
-    sd = SceneDesc()
-    T = Transform4f
-
-    def material():
-        two = bool(rng.integers(2))
-        if rng.random() < 0.45:
-            return sd.add_diffuse(float(rng.uniform(0.05, 0.95)), twosided=two)
-        au = float(rng.choice([0.05, 0.15, 0.4, 0.8]))
-        return sd.add_roughconductor(alpha=au, alpha_v=float(rng.choice([0.05, 0.3])) if rng.random() < 0.3 else None, twosided=two,
-                                     distribution="ggx" if rng.random() < 0.5 else "beckmann", sample_visible=bool(rng.integers(2)),
-                                     specular_reflectance=float(rng.uniform(0.3, 1.0)) if rng.random() < 0.6 else None)
-
-    # floor + a few random walls
-    sd.add_rectangle(T.scale([6, 6, 1]), material())
-    for _ in range(int(rng.integers(2, 6))):
-        ax = rng.standard_normal(3)
-        ax /= np.linalg.norm(ax)
-        sd.add_rectangle(T.translate(list(rng.uniform(-3, 3, 2)) + [float(rng.uniform(0.3, 3))]) * T.rotate(list(ax), float(rng.uniform(0, 360))) *
-                         T.scale([float(rng.uniform(0.3, 2.5)), float(rng.uniform(0.3, 2.5)), 1]), material())
-    for k in range(int(rng.integers(1, 4))):
-        kind = int(rng.integers(3))
-        if kind == 0:
-            v, f = meshgen.triangle_soup(int(rng.integers(50, 3000)), seed=seed * 7 + k, extent=1.0, size=float(rng.uniform(0.05, 0.5)))
-            n = None
-        elif kind == 1:
-            v, f, n = meshgen.car_body(int(rng.integers(500, 4000)), seed=seed * 7 + k)
-            v = v * 0.4
-        else:
-            v, f = meshgen.bus(int(rng.integers(500, 4000)), seed=seed * 7 + k)
-            v = v * 0.25
-            n = None
-        v = meshgen.place(v, float(rng.uniform(0, 360)), tuple(rng.uniform(-2, 2, 2)) + (float(rng.uniform(0.5, 2.0)),))
-        if kind == 1 or rng.random() < 0.4:
-            n = meshgen.vertex_normals(v, f)
-        sd.add_mesh(v, f, material(), normals=n, texcoords=_planar_uv(v) if rng.random() < 0.4 else None)
-    if receive:
-        return _fuzz_receive_endpoints(sd, rng)
-    em = int(rng.integers(4))
-    if em == 3:
-        sd.add_point(list(rng.uniform(-3, 3, 2)) + [float(rng.uniform(1.5, 4))], intensity=float(rng.uniform(5, 50)))
-        if rng.random() < 0.5:
-            em = 1                                     # ... plus an area light
-    if em in (0, 2):
-        sd.add_spot(T.look_at(list(rng.uniform(-3, 3, 2)) + [float(rng.uniform(2, 4))], list(rng.uniform(-1, 1, 3)), [0, 0, 1]),
-                    intensity=float(rng.uniform(5, 50)), cutoff_angle=float(rng.uniform(15, 60)), beam_width=float(rng.uniform(5, 14)))
-    if em in (1, 2):
-        r = sd.add_rectangle(T.translate([float(rng.uniform(-2, 2)), float(rng.uniform(-2, 2)), 3.5]) * T.rotate([1, 0, 0], 180) *
-                             T.scale([float(rng.uniform(0.05, 1.0)), float(rng.uniform(0.05, 1.0)), 1]), sd.add_diffuse(0.0))
-        sd.add_area_emitter(r, float(rng.uniform(1, 40)))
-    film, spp = None, 0
-    kind = rng.random()
-    if kind < 0.4:
-        rx = sd.add_rectangle(T.translate([0.2, -0.3, 1.0]) * T.rotate([1, 0, 0], float(rng.uniform(90, 270))) * T.scale([0.05, 0.08, 1]),
-                              sd.add_diffuse(0.5))
-        if rng.random() < 0.5:
-            sd.set_fluxmeter(rx)
-        else:
-            sd.set_irradiancemeter(rx)
-    elif kind < 0.5:
-        sd.set_radiancemeter(T.look_at(list(rng.uniform(-3, 3, 2)) + [float(rng.uniform(0.5, 3))], list(rng.uniform(-1, 1, 2)) + [0.5], [0, 0, 1]))
-    else:
-        if rng.random() < 0.5:
-            film = (int(rng.integers(1, 7)), int(rng.integers(1, 5)))
-        sd.set_perspective(T.look_at(list(rng.uniform(-3, 3, 2)) + [float(rng.uniform(0.5, 3))], [0, 0, 0.8], [0, 0, 1]),
-                           fov=float(rng.uniform(30, 100)), near_clip=0.05, far_clip=100.0, film=film or (1, 1))
-    sd.finalize()
-    mode = int(rng.choice([capi.BF_MODE_PATH, capi.BF_MODE_RANGE, capi.BF_MODE_TIME]))
-    n_paths = 6000
-    if film:
-        spp = n_paths // (film[0] * film[1])
-        n_paths = spp * film[0] * film[1]
-    lp = capi.make_launch(mode, n_paths, seed=int(rng.integers(1 << 30)), bins=int(rng.integers(1, 200)),
-                          bin_width=float(rng.uniform(0.02, 0.5)) if mode == capi.BF_MODE_RANGE else float(rng.uniform(1e-10, 2e-9)),
-                          color_mode=int(rng.integers(2)), max_depth=int(rng.choice([-1, 1, 2, 3, 8])), rr_depth=int(rng.choice([1, 3, 5, 50])),
-                          film=film, spp=spp)
-    return sd, lp
-
 
 @pytest.mark.parametrize("seed", range(16))
 def test_fuzz_random_scenes_render(hiplib, seed):
     sd, lp = _fuzz_scene(seed)
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     for flags in (capi.BF_FLAG_MEGAKERNEL, 0):
         lp.flags = flags
@@ -967,6 +814,7 @@ def test_fuzz_random_scenes_render(hiplib, seed):
         assert (sg.n_rays_closest, sg.n_rays_shadow, sg.n_bounces, sg.n_invalid) == (so.n_rays_closest, so.n_rays_shadow, so.n_bounces, so.n_invalid)
         amax = float(np.nanmax(np.abs(ro["L"])))           # seed 2 has a NaN sample: dropped by both, bit-equal in the records
         assert np.allclose(hg, ho, rtol=2e-5, atol=lp.n_paths * 2.0 ** -24 * max(amax, 1.0) * 4), seed
+        assert_fp32_sum(hg, add.ref, add.S, add.N, f"fuzz seed {seed} flags {flags:#x}", counts=count_channels(lp, sd))
 
 
 @pytest.mark.parametrize("seed", range(12))
@@ -981,7 +829,7 @@ def test_fuzz_random_scenes_receive(hiplib, seed, hook):
         if sd.sensor.type == capi.BF_RECEIVER_OMNI and seed % 2:
             extra |= capi.BF_FLAG_MIX_RESAMPLE
     lp.flags = extra
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     for flags in (capi.BF_FLAG_MEGAKERNEL | extra, extra):
         lp.flags = flags
@@ -992,6 +840,45 @@ def test_fuzz_random_scenes_receive(hiplib, seed, hook):
         assert (sg.n_rays_closest, sg.n_rays_shadow, sg.n_bounces, sg.n_invalid) == (so.n_rays_closest, so.n_rays_shadow, so.n_bounces, so.n_invalid)
         amax = float(np.nanmax(np.abs(ro["L"])))
         assert np.allclose(hg, ho, rtol=2e-5, atol=lp.n_paths * 2.0 ** -24 * max(amax, 1.0) * 4), seed
+        assert_fp32_sum(hg, add.ref, add.S, add.N, f"fuzz seed {seed} flags {flags:#x}", counts=count_channels(lp, sd))
+
+
+def _fuzz_compare(sd, lp, oracle_out, flags_list, what):
+    """the fuzz families' asserts on both pipelines: records bit for bit, counters, the old tolerance and the per-cell bound"""
+    ho, ro, so, add = oracle_out
+    g = capi.Scene(sd)
+    for flags in flags_list:
+        lp.flags = flags
+        hg, rg, sg = g.render(lp, records=True)
+        assert np.array_equal(rg["n_rays"], ro["n_rays"]) and np.array_equal(rg["valid"], ro["valid"]), what
+        assert np.array_equal(rg["aux"].view(np.uint32), ro["aux"].view(np.uint32)), what
+        assert np.array_equal(rg["L"].view(np.uint32), ro["L"].view(np.uint32)), what
+        assert (sg.n_rays_closest, sg.n_rays_shadow, sg.n_bounces, sg.n_invalid) == (so.n_rays_closest, so.n_rays_shadow, so.n_bounces, so.n_invalid)
+        amax = float(np.nanmax(np.abs(ro["L"])))
+        assert np.allclose(hg, ho, rtol=2e-5, atol=lp.n_paths * 2.0 ** -24 * max(amax, 1.0) * 4), what
+        assert_fp32_sum(hg, add.ref, add.S, add.N, f"{what} flags {flags:#x}", counts=count_channels(lp, sd))
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_fuzz_live_scenes_render(hiplib, seed):
+    """_fuzz_scene redrawn until the paths carry radiance (_live_fuzz_scene): the histogram cells are then non-trivial sums."""
+    sd, lp, out = _live_fuzz_scene(seed)
+    _fuzz_compare(sd, lp, out, (capi.BF_FLAG_MEGAKERNEL, 0), f"live render seed {seed}")
+
+
+@pytest.mark.parametrize("seed", range(12))
+@pytest.mark.parametrize("hook", [False, True])
+def test_fuzz_live_scenes_receive(hiplib, seed, hook):
+    """test_fuzz_random_scenes_receive on the live redraws: hook as there (Doppler; mix_resample on odd seeds' omni receivers)."""
+    sd, lp, out = _live_fuzz_scene(seed, receive=True)
+    extra = 0
+    if hook:
+        extra = capi.BF_FLAG_DOPPLER
+        if sd.sensor.type == capi.BF_RECEIVER_OMNI and seed % 2:
+            extra |= capi.BF_FLAG_MIX_RESAMPLE
+        lp.flags = extra
+        out = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
+    _fuzz_compare(sd, lp, out, (capi.BF_FLAG_MEGAKERNEL | extra, extra), f"live receive seed {seed} hook {hook}")
 
 
 @pytest.mark.timeout(300)
@@ -1002,7 +889,7 @@ def test_trace_scheduling_extremes_complete_without_guard(hiplib, monkeypatch):
     before the whole wave is idle.  The render must complete, the iteration guard must not have dropped a ray
     (bf_stats.n_guard == 0; a non-zero count makes bf_render fail with BF_ERR_DEVICE), every path as the oracle's."""
     sd, lp = scenes.bus_radar(n_tris=20000, n_paths=1 << 16, bins=256, dr=0.1)
-    out = OracleScene(sd).render(lp, records=True, threads=8)
+    out = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     for strag, refill in (("64", "0"), ("1", "63"), ("12", "44")):
         monkeypatch.setenv("BF_TRACE_STRAGGLERS", strag)
         monkeypatch.setenv("BF_TRACE_REFILL", refill)
@@ -1064,7 +951,7 @@ def test_c5_full_size_sweep(hiplib):
         assert np.array_equal(rb[j]["n_rays"], rs["n_rays"])
         assert np.allclose(hb[j], hs, rtol=1e-4, atol=1e-5 * scale)
         v1 = np.ascontiguousarray((v + offsets[kk][None, :]).astype(np.float32))
-        from tests.test_gpu_batch import _bus_receive_with_mesh
+        from tests.scene_builders import _bus_receive_with_mesh
         sd1 = _bus_receive_with_mesh(v1, f, t_bins=1024, dr=0.03, lambda_band_nm=(lam0 * 0.999, lam0 * 1.001))
         _, ro, _ = OracleScene(sd1).render(lp, records=True, threads=8)
         for key in ("L", "aux"):
@@ -1107,7 +994,7 @@ def test_doppler_hook_off_by_default_and_bit_exact_when_on(hiplib):
     assert not np.array_equal(h1, h_on)
     # the planned (asynchronous) second render of a shape keeps the per-slot shift
     g = capi.Scene(sd)
-    out = OracleScene(sd).render(lp_on, records=True, threads=8)
+    out = OracleScene(sd).render(lp_on, records=True, threads=8, addends=True)
     for _ in range(3):
         _render_compare_one(g, lp_on, out, 2e-5)
 
@@ -1155,7 +1042,7 @@ def test_quantised_nodes_opt_in_is_bit_exact(hiplib, monkeypatch):
     sd, lp = scenes.bus_radar(n_tris=20000, n_paths=1 << 16, bins=256, dr=0.1)
     g = capi.Scene(sd)
     assert g.info().trace_node_bytes == 64 and g.info().node_bytes == 128
-    out = OracleScene(sd).render(lp, records=True, threads=8)
+    out = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     _, _, st = _render_compare_one(g, lp, out, 2e-5)
     assert st.n_rays_traced > 0
     monkeypatch.delenv("BF_QUANT_BVH")
@@ -1191,7 +1078,7 @@ def test_lean_and_general_kernels_agree(hiplib, monkeypatch, case):
         sd, lp = scenes.bus_receive(n_tris=20000, n_paths=30000)
         if case == "bus_receive_iq":
             lp.mode = capi.BF_MODE_RECEIVE_IQ
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     out = {}
     for lean in ("1", "0"):
         monkeypatch.setenv("BF_LEAN", lean)
@@ -1214,6 +1101,8 @@ def test_lean_and_general_kernels_agree(hiplib, monkeypatch, case):
         out[lean] = (h1, r1)
     assert np.array_equal(out["1"][1], out["0"][1])
     assert np.allclose(out["1"][0], out["0"][0], rtol=2e-5, atol=1e-3)
+    assert_two_fp32_sums(out["1"][0], out["0"][0], add.S, add.N, f"lean vs general {case}", counts=count_channels(lp, sd))
+    assert_fp32_sum(out["1"][0], add.ref, add.S, add.N, f"lean {case}", counts=count_channels(lp, sd))
 
 
 @pytest.mark.parametrize("receive", [False, True])

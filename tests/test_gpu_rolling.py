@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 
 from beifong_amd import capi, scenes
+from tests.hist_bound import assert_close_hists as _close_hist, assert_fp32_sum, assert_two_fp32_sums, count_channels
 from tests.oracle_lib import OracleScene
+from tests.scene_builders import bus_receive_shifted
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +23,6 @@ def _same_records(a, b):
     for k in ("L", "aux"):
         assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
     assert np.array_equal(a["n_rays"], b["n_rays"]) and np.array_equal(a["valid"], b["valid"])
-
-
-def _close_hist(hb, hs, n_paths, amax):
-    atol = n_paths * 2.0 ** -24 * max(amax, 1.0) * 4
-    assert np.allclose(hb, hs, rtol=2e-5, atol=atol), float(np.abs(hb - hs).max())
 
 
 def _launch_like(lp, seed, flags=0, n_paths=None, path_offset=0):
@@ -63,18 +60,19 @@ class _Sequence:
         return h, recs
 
 
-def _check_against_stand_alone(g, lp, seq, h, recs, oracle=None, offsets=None):
+def _check_against_stand_alone(g, lp, seq, h, recs, oracle, offsets=None):
     rays = 0
     for k, seed in enumerate(seq.seeds):
         l1 = _launch_like(lp, seed, flags=lp.flags, path_offset=seq.offsets[k])
         hs, rs, ss = g.render(l1, records=True)
         _same_records(recs[k], rs)
-        _close_hist(h[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()))
+        flags, l1.flags = l1.flags, 0
+        _, ro, _, add = oracle.render(l1, records=True, threads=8, addends=True)
+        _same_records(recs[k], ro)
+        l1.flags = flags
+        assert_fp32_sum(h[k], add.ref, add.S, add.N, f"rolling render {k}", counts=count_channels(l1, oracle.holder))
+        _close_hist(h[k], hs, lp.n_paths, float(np.abs(rs["L"]).max()), add, l1, oracle.holder)
         rays += ss.n_rays_closest + ss.n_rays_shadow
-        if oracle is not None:
-            l1.flags = 0
-            _, ro, _ = oracle.render(l1, records=True, threads=8)
-            _same_records(recs[k], ro)
     return rays
 
 
@@ -116,10 +114,15 @@ def test_rolling_heavy_eviction_loses_no_path(hiplib, bins, iters, monkeypatch):
     g.flush()
     h, recs = seq.results()
     assert [float(hk[4]) for hk in h] == [float(n)] * len(seeds)
+    o = OracleScene(sd)
     for k in (0, 5, 11):
-        hs, rs, _ = g.render(_launch_like(lp, seeds[k]), records=True)
+        l1 = _launch_like(lp, seeds[k])
+        hs, rs, _ = g.render(l1, records=True)
         _same_records(recs[k], rs)
-        _close_hist(h[k], hs, n, float(np.abs(rs["L"]).max()))
+        # per cell against the oracle: late samples of a 4096-bin render take the base-channel table / global atomics
+        add = o.render(l1, threads=16, addends=True)[3]
+        assert_fp32_sum(h[k], add.ref, add.S, add.N, f"heavy eviction bins {bins} render {k}", counts=count_channels(l1, sd))
+        _close_hist(h[k], hs, n, float(np.abs(rs["L"]).max()), add, l1, sd)
 
 
 def test_rolling_survivor_area_overrun_is_loud_and_loses_nothing(hiplib, monkeypatch):
@@ -218,7 +221,8 @@ def test_rolling_path_offsets_shard_a_render(hiplib):
     whole = _launch_like(lp, lp.seed, n_paths=K * int(lp.n_paths))
     hw, rw, _ = g.render(whole, records=True)
     _same_records(np.concatenate(recs), rw)
-    _close_hist(h.sum(axis=0), hw, K * lp.n_paths, float(np.abs(rw["L"]).max()))
+    add = OracleScene(sd).render(whole, threads=16, addends=True)[3]
+    _close_hist(h.sum(axis=0), hw, K * lp.n_paths, float(np.abs(rw["L"]).max()), add, whole, sd)
 
 
 def test_everything_else_flushes_an_open_sequence(hiplib):
@@ -227,9 +231,11 @@ def test_everything_else_flushes_an_open_sequence(hiplib):
     import torch
     sd, lp = scenes.bus_receive(n_tris=20000, n_paths=8192, t_bins=256, dr=0.1)
     g = capi.Scene(sd)
-    ref_h, ref_r = {}, {}
+    ref_h, ref_r, ref_a = {}, {}, {}
+    o = OracleScene(sd)
     for seed in (1, 2, 3, 4):
         ref_h[seed], ref_r[seed], _ = g.render(_launch_like(lp, seed), records=True)
+        ref_a[seed] = o.render(_launch_like(lp, seed), threads=16, addends=True)[3]
 
     def run(seed, then):
         seq = _Sequence(g, lp, [seed])
@@ -237,7 +243,7 @@ def test_everything_else_flushes_an_open_sequence(hiplib):
         then()
         h, recs = seq.results()              # no explicit flush
         _same_records(recs[0], ref_r[seed])
-        _close_hist(h[0], ref_h[seed], lp.n_paths, float(np.abs(ref_r[seed]["L"]).max()))
+        _close_hist(h[0], ref_h[seed], lp.n_paths, float(np.abs(ref_r[seed]["L"]).max()), ref_a[seed], lp, sd)
 
     run(1, lambda: g.render(_launch_like(lp, 77)))
     sd2, _ = scenes.bus_receive(n_tris=20000, n_paths=8192, t_bins=256, dr=0.1)
@@ -304,11 +310,11 @@ def test_rolling_sequence_across_endpoint_updates(hiplib, mode, iters, monkeypat
     for k, (sd, lp) in enumerate(frames):
         recs = np.ascontiguousarray(r[k]).view(capi.PATH_RECORD_DTYPE).reshape(-1)
         l1 = _launch_like(lp, 1000 + k)
-        _, ro, _ = OracleScene(sd).render(l1, records=True, threads=8)          # the scene REBUILT for frame k
+        _, ro, _, add = OracleScene(sd).render(l1, records=True, threads=8, addends=True)          # the scene REBUILT for frame k
         _same_records(recs, ro)
         hs, rs, _ = capi.Scene(sd).render(l1, records=True)                      # a fresh handle, stand-alone
         _same_records(recs, rs)
-        _close_hist(h[k], hs, n, float(np.abs(rs["L"]).max()))
+        _close_hist(h[k], hs, n, float(np.abs(rs["L"]).max()), add, l1, sd)
     # the handle's tables are the last frame's again (home buffers): a plain render sees them
     _, rl, _ = g.render(_launch_like(frames[-1][1], 77), records=True)
     _, rf, _ = capi.Scene(frames[-1][0]).render(_launch_like(frames[-1][1], 77), records=True)
@@ -450,7 +456,13 @@ def test_rolling_batches_with_mesh_offsets(hiplib, iq):
     for k in range(K * calls):
         got = np.ascontiguousarray(rr[k]).view(capi.PATH_RECORD_DTYPE).reshape(-1)
         _same_records(got, rb[k])
-        _close_hist(h[k], hb[k], lp.n_paths, float(np.abs(rb[k]["L"]).max()))
+        # S and N from the oracle on the scene rebuilt with render k's shifted bus and its seed (the same paths)
+        l1 = _launch_like(lp, seeds[k])
+        sdk = bus_receive_shifted(offsets[k])
+        _, ro, _, add = OracleScene(sdk).render(l1, records=True, threads=16, addends=True)
+        _same_records(got, ro)
+        _close_hist(h[k], hb[k], lp.n_paths, float(np.abs(rb[k]["L"]).max()), add, l1, sdk)
+        assert_fp32_sum(h[k], add.ref, add.S, add.N, f"rolling batch with offset {k}", counts=count_channels(l1, sdk))
     assert not np.array_equal(rb[0]["L"], rb[7]["L"])
     # a rolling batch without offsets after one with offsets opens a new sequence (the shape differs) and is correct too
     g.render_batch_device(lr, K, hist[0].data_ptr(), seeds=seeds[:K], records_ptr=rec[0].data_ptr())
@@ -468,7 +480,7 @@ def test_rolling_fuzz_scenes(hiplib, seed, receive):
     bins, the Doppler hook / mix_resample on odd receive seeds) as rolling sequences of five renders: records and
     histograms of every render against the stand-alone render (which the fuzz tests hold to the oracle), and the first and
     last against the oracle directly."""
-    from tests.test_gpu_parity import _fuzz_scene
+    from tests.scene_builders import _fuzz_scene
     sd, lp = _fuzz_scene(seed, receive=receive)
     if lp.spp:
         pytest.skip("multi-pixel films do not roll")
@@ -488,8 +500,10 @@ def test_rolling_fuzz_scenes(hiplib, seed, receive):
         amax = float(np.nanmax(np.abs(rs["L"]))) if len(rs) else 0.0
         assert np.allclose(h[k], hs, rtol=2e-5, atol=lp.n_paths * 2.0 ** -24 * max(amax, 1.0) * 4, equal_nan=True), (seed, k)
         if k in (0, 4):
-            _, ro, _ = o.render(l1, records=True, threads=8)
+            _, ro, _, add = o.render(l1, records=True, threads=8, addends=True)
             _same_records(recs[k], ro)
+            assert_two_fp32_sums(h[k], hs, add.S, add.N, f"rolling fuzz seed {seed} render {k}", counts=count_channels(l1, sd))
+            assert_fp32_sum(h[k], add.ref, add.S, add.N, f"rolling fuzz seed {seed} render {k}", counts=count_channels(l1, sd))
 
 
 @pytest.mark.parametrize("share", ["", "1", "8"])

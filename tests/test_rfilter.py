@@ -12,6 +12,7 @@ import pytest
 from beifong_amd import capi, scenes
 from beifong_amd.scenedesc import Transform4f
 from tests import oracle_lib
+from tests.hist_bound import assert_fp32_sum, count_channels
 
 KINDS = {"box": 0, "tent": 1, "gaussian": 2, "mitchell": 3, "catmullrom": 4, "lanczos": 5}
 DEFAULTS = {"box": (0.5, 0.0), "tent": (0.0, 0.0), "gaussian": (0.5, 0.0), "mitchell": (1 / 3, 1 / 3), "catmullrom": (0.0, 0.0),
@@ -231,13 +232,18 @@ def _hist_close(hg, ho, n, amax):
     assert np.allclose(hg, ho, rtol=3e-5, atol=n * 2.0 ** -24 * max(amax, 1.0) * 4), np.abs(hg - ho).max()
 
 
+def _hist_bound(hg, add, lp, sd, what):
+    # every cell an fp32 sum of the oracle's addends (tests/hist_bound.py); the box filter's counts exact
+    assert_fp32_sum(hg, add.ref, add.S, add.N, what, counts=count_channels(lp, sd))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,props,block", [("gaussian", {}, 32), ("gaussian", {"stddev": 0.9}, 4), ("lanczos", {}, 0), ("mitchell", {}, 2),
                                               ("tent", {}, 32), ("box", {"radius": 0.85}, 3)])
 def test_film_with_a_wide_filter(hiplib, oracle, kind, props, block):
     """A W x H range image through a perspective camera (the zoo scene of test_gpu_parity) with a filter that spreads every
     sample over its neighbours — negative lobes included; both device pipelines and the global-atomics fallback."""
-    from tests.test_gpu_parity import _zoo_scene
+    from tests.scene_builders import _zoo_scene
     from tests.oracle_lib import OracleScene
     film, spp, bins = (9, 6), 48, 64
     sd, _ = _zoo_scene(two_emitters=True)
@@ -248,7 +254,7 @@ def test_film_with_a_wide_filter(hiplib, oracle, kind, props, block):
     sd.finalize()
     lp = capi.make_launch(capi.BF_MODE_RANGE, film[0] * film[1] * spp, seed=5, bins=bins, bin_width=0.2, color_mode=capi.BF_COLOR_RGB, film=film,
                           spp=spp)
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     chan = 5 + bins
     for flags in (capi.BF_FLAG_MEGAKERNEL, 0, capi.BF_FLAG_GLOBAL_ATOMICS):
@@ -257,6 +263,7 @@ def test_film_with_a_wide_filter(hiplib, oracle, kind, props, block):
         _records_equal(rg, ro)
         assert sg.n_invalid == so.n_invalid == 0
         _hist_close(hg, ho, spp * 16, float(np.abs(ro["L"]).max()))
+        _hist_bound(hg, add, lp, sd, f"film {kind} block {block} flags {flags:#x}")
     img = hg.reshape(film[1], film[0], chan)
     # the filter really spread the samples: the weight channel is no longer the integer sample count of the box filter
     assert not np.array_equal(img[:, :, 4], np.full((film[1], film[0]), float(spp)))
@@ -280,7 +287,7 @@ def test_single_pixel_film_with_the_default_gaussian(hiplib, oracle, mode):
         lp.bins, lp.bin_width = 64, 0.25
     sd.sensor.rfilter = _host_filter("gaussian").flatten(32)
     sd.finalize()
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     n = lp.n_paths
     amax = float(np.abs(ro["L"]).max())
@@ -289,6 +296,7 @@ def test_single_pixel_film_with_the_default_gaussian(hiplib, oracle, mode):
         hg, rg, sg = g.render(lp, records=True)
         _records_equal(rg, ro)
         _hist_close(hg, ho, n, amax)
+        _hist_bound(hg, add, lp, sd, f"1x1 gaussian mode {mode} flags {flags:#x}")
     assert 0 < hg[4] < n and hg[4] != np.round(hg[4])           # W: the sum of the samples' weights
     # two shards as a rolling sequence on one handle
     half = n // 2 + 5
@@ -305,6 +313,7 @@ def test_single_pixel_film_with_the_default_gaussian(hiplib, oracle, mode):
     torch.cuda.synchronize()
     parts = dev.cpu().numpy()
     _hist_close(parts.sum(0), ho, n, amax)
+    _hist_bound(parts.sum(0), add, lp, sd, f"1x1 gaussian mode {mode} rolling shards")
 
 
 @pytest.mark.gpu
@@ -323,7 +332,7 @@ def test_adc_with_a_wide_filter(hiplib, oracle, kind, f_bins, iq):
         lp.mode = capi.BF_MODE_RECEIVE_IQ
     sd.sensor.rfilter = _host_filter(kind).flatten(0)
     sd.finalize()
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     for flags in (capi.BF_FLAG_MEGAKERNEL, 0):
         lp.flags = flags
@@ -331,6 +340,7 @@ def test_adc_with_a_wide_filter(hiplib, oracle, kind, f_bins, iq):
         _records_equal(rg, ro)
         assert sg.n_invalid == so.n_invalid
         _hist_close(hg, ho, lp.n_paths, float(np.abs(ro["L"]).max()))
+        _hist_bound(hg, add, lp, sd, f"ADC {kind} f_bins {f_bins} iq {iq} flags {flags:#x}")
     cells = hg.reshape(f_bins, 64, 3)
     assert (cells[:, :, 2] != 0).sum() > 8 and not np.array_equal(cells[:, :, 2], np.round(cells[:, :, 2]))
 
@@ -350,7 +360,7 @@ def test_batched_and_rolling_batched_renders_with_a_wide_filter(hiplib, oracle):
     want = []
     for sdd in seeds:
         lp.seed = sdd
-        want.append(o.render(lp, records=True, threads=8))
+        want.append(o.render(lp, records=True, threads=8, addends=True))
     g = capi.Scene(sd)
     lp.seed = 0
     hist, rec, st = g.render_batch(lp, len(seeds), seeds=seeds, records=True)
@@ -358,6 +368,7 @@ def test_batched_and_rolling_batched_renders_with_a_wide_filter(hiplib, oracle):
     for k in range(len(seeds)):
         _records_equal(rec[k], want[k][1])
         _hist_close(hist[k], want[k][0], lp.n_paths, float(np.abs(want[k][1]["L"]).max()))
+        _hist_bound(hist[k], want[k][3], lp, sd, f"batched render {k}")
     # the same four renders as two rolling batch calls of two
     dev = torch.zeros((4, hist.shape[1]), dtype=torch.float32, device="cuda")
     lp.flags = capi.BF_FLAG_ROLLING
@@ -368,6 +379,7 @@ def test_batched_and_rolling_batched_renders_with_a_wide_filter(hiplib, oracle):
     got = dev.cpu().numpy()
     for k in range(len(seeds)):
         _hist_close(got[k], want[k][0], lp.n_paths, float(np.abs(want[k][1]["L"]).max()))
+        _hist_bound(got[k], want[k][3], lp, sd, f"rolling batched render {k}")
 
 
 @pytest.mark.gpu
@@ -376,7 +388,7 @@ def test_fuzz_filters_films_and_modes(hiplib, oracle, seed):
     """Random filter (kind, parameters, block size) x film (1 x 1 ... 13 x 9) x mode (path / range / time) x launch form (plain,
     one-kernel, global atomics, two path_offset shards) on the zoo scene: records per path and the filtered histograms against the
     oracle."""
-    from tests.test_gpu_parity import _zoo_scene
+    from tests.scene_builders import _zoo_scene
     from tests.oracle_lib import OracleScene
     rng = np.random.default_rng(1000 + seed)
     kind = ["gaussian", "tent", "mitchell", "catmullrom", "lanczos", "box"][seed % 6]
@@ -398,15 +410,20 @@ def test_fuzz_filters_films_and_modes(hiplib, oracle, seed):
         kw.update(film=film, spp=spp)
     n = film[0] * film[1] * spp
     lp = capi.make_launch(mode, n, **kw)
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     amax = float(np.abs(ro["L"]).max())
+    # the scene is live: a tenth of the paths or more carry radiance, and it reaches range / time bins
+    assert np.count_nonzero(np.isfinite(ro["L"]) & (ro["L"] != 0)) >= 0.1 * n
+    if mode != capi.BF_MODE_PATH:
+        assert (add.N.reshape(-1, len(ho) // (film[0] * film[1]))[:, 5:] >= 1).sum() >= 3
     for flags in (0, capi.BF_FLAG_MEGAKERNEL, capi.BF_FLAG_GLOBAL_ATOMICS):
         lp.flags = flags
         hg, rg, sg = g.render(lp, records=True)
         _records_equal(rg, ro)
         assert sg.n_invalid == so.n_invalid and (sg.kernel_variant == capi.BF_VARIANT_WIDE or flags == capi.BF_FLAG_MEGAKERNEL)
         _hist_close(hg, ho, max(spp, 64) * 16, amax)
+        _hist_bound(hg, add, lp, sd, f"fuzz filter seed {seed} flags {flags:#x}")
     lp.flags = 0
     half = n // 2 + 3
     parts = []
@@ -414,6 +431,7 @@ def test_fuzz_filters_films_and_modes(hiplib, oracle, seed):
         l2 = capi.make_launch(mode, cnt, path_offset=off, **kw)
         parts.append(g.render(l2)[0])
     _hist_close(parts[0] + parts[1], ho, max(spp, 64) * 16, amax)
+    _hist_bound(parts[0] + parts[1], add, lp, sd, f"fuzz filter seed {seed} shards")
 
 
 WINDOW_XML = """<scene version='2.0.0'>
@@ -470,13 +488,14 @@ def test_adc_window(hiplib, oracle, kind):
     with pytest.raises(capi.BeifongError, match="window"):
         g.render(lp)                                            # the launch still names the whole ADC
     lp.bins, lp.bins_y = wt, wf
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     for flags in (0, capi.BF_FLAG_MEGAKERNEL):
         lp.flags = flags
         hg, rg, sg = g.render(lp, records=True)
         _records_equal(rg, ro)
         assert sg.n_invalid == so.n_invalid and sg.kernel_variant in (0, capi.BF_VARIANT_WIDE)       # a window off the origin: general kernels
         _hist_close(hg, ho, lp.n_paths, float(np.abs(ro["L"]).max()))
+        _hist_bound(hg, add, lp, sd, f"ADC window {kind} flags {flags:#x}")
     _records_equal(rg, full[1])                                 # the window changes where samples land, not the paths
     crop = full[0].reshape(8, 64, 3)[of:of + wf, ot:ot + wt]
     assert np.allclose(hg.reshape(wf, wt, 3), crop, rtol=3e-5, atol=lp.n_paths * 2.0 ** -24 * 4 * max(1.0, float(np.abs(ro["L"]).max())))
@@ -532,7 +551,7 @@ def test_film_crop_window_like_the_reference_test():
 def test_film_crop_window(hiplib, oracle, kind, block):
     """A crop window of a 40 x 30 film through the perspective camera: per-path records and the (filtered) histogram against the
     oracle, both pipelines; with the box filter every pixel of the crop holds its spp samples."""
-    from tests.test_gpu_parity import _zoo_scene
+    from tests.scene_builders import _zoo_scene
     from tests.oracle_lib import OracleScene
     film, crop, spp, bins = (40, 30), (7, 4, 17, 9), 40, 32
     sd, _ = _zoo_scene(two_emitters=True)
@@ -544,7 +563,7 @@ def test_film_crop_window(hiplib, oracle, kind, block):
     sd.finalize()
     cw, ch = crop[2], crop[3]
     lp = capi.make_launch(capi.BF_MODE_RANGE, cw * ch * spp, seed=9, bins=bins, bin_width=0.2, color_mode=capi.BF_COLOR_RGB, film=(cw, ch), spp=spp)
-    ho, ro, so = OracleScene(sd).render(lp, records=True, threads=8)
+    ho, ro, so, add = OracleScene(sd).render(lp, records=True, threads=8, addends=True)
     g = capi.Scene(sd)
     for flags in (0, capi.BF_FLAG_MEGAKERNEL, capi.BF_FLAG_GLOBAL_ATOMICS):
         lp.flags = flags
@@ -552,6 +571,7 @@ def test_film_crop_window(hiplib, oracle, kind, block):
         _records_equal(rg, ro)
         assert sg.n_invalid == so.n_invalid and not (sg.kernel_variant & capi.BF_VARIANT_LEAN)
         _hist_close(hg, ho, spp * 16, float(np.abs(ro["L"]).max()))
+        _hist_bound(hg, add, lp, sd, f"crop {kind} block {block} flags {flags:#x}")
     img = hg.reshape(ch, cw, 5 + bins)
     if kind == "box":
         assert np.array_equal(img[:, :, 4], np.full((ch, cw), float(spp)))
