@@ -756,10 +756,9 @@ static bf_status flatten(const bf_scene_desc *desc, Flat &f, bool with_meshes) {
     return BF_OK;
 }
 
-bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
-    if (!desc || !out) return fail(BF_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (desc->n_shapes && !desc->shapes) return fail(BF_ERR_INVALID, "shapes is null");
+// what bf_scene_create and bf_scene_update_endpoints both require of the material table and the film (a back_material out of
+// range would send the kernels' load_material past the device table)
+static bf_status check_materials_and_film(const bf_scene_desc *desc) {
     if (desc->n_materials == 0 || !desc->materials) return fail(BF_ERR_INVALID, "at least one material is required");
     for (uint32_t i = 0; i < desc->n_materials; ++i) {
         const uint32_t b = desc->materials[i].back_material;
@@ -769,6 +768,24 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     }
     if (desc->sensor.film_width == 0 || desc->sensor.film_height == 0)
         return fail(BF_ERR_INVALID, "sensor film is %u x %u", desc->sensor.film_width, desc->sensor.film_height);
+    return BF_OK;
+}
+
+// the kernel-profile bits a scene derives from its material table (lean_profile: the lean kernels have one BSDF per material)
+static bool materials_have_back(const bf_scene_desc *desc) {
+    for (uint32_t i = 0; i < desc->n_materials; ++i)
+        if (desc->materials[i].back_material != 0) return true;
+    return false;
+}
+
+bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
+    if (!desc || !out) return fail(BF_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (desc->n_shapes && !desc->shapes) return fail(BF_ERR_INVALID, "shapes is null");
+    {
+        bf_status mst = check_materials_and_film(desc);
+        if (mst != BF_OK) return mst;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(BF_ERR_DEVICE, "no HIP device available: the HIP path has no CPU fallback");
@@ -940,8 +957,7 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     sc->n_materials = desc->n_materials;
     sc->d.n_materials = desc->n_materials;
     sc->d.tab_cache = (sc->tun.tab_cache && desc->n_materials <= bfd::kTabMaxMaterials && rects.size() <= bfd::kTabMaxRects) ? 1u : 0u;
-    sc->any_back_material = false;
-    for (uint32_t i = 0; i < desc->n_materials; ++i) sc->any_back_material = sc->any_back_material || desc->materials[i].back_material != 0;
+    sc->any_back_material = materials_have_back(desc);
     sc->any_resample = false;
     for (const auto &e : emitters) sc->any_resample = sc->any_resample || e.resample != 0u;
     sc->shapes_host = shapes;
@@ -987,6 +1003,10 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
 bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, void *stream_) {
     if (!scene || !desc) return fail(BF_ERR_INVALID, "null argument");
     if (desc->n_shapes && !desc->shapes) return fail(BF_ERR_INVALID, "shapes is null");
+    {
+        bf_status mst = check_materials_and_film(desc);
+        if (mst != BF_OK) return mst;
+    }
     Flat f;
     bf_status st = flatten(desc, f, false);
     if (st != BF_OK) return st;
@@ -1094,8 +1114,10 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
             scene->roll.multi = true;
         }
     }
+    // every profile bit bf_scene_create derived from the tables just replaced (lean_profile reads them at the next render)
     scene->sensor_host = f.sensor;
     scene->any_resample = resample_new;
+    scene->any_back_material = materials_have_back(desc);
     scene->film_w = desc->sensor.film_width;
     scene->adc_t = f.window_t ? f.window_t : f.sensor.t_bins;
     scene->adc_f = f.window_f ? f.window_f : f.sensor.f_bins;
@@ -1940,16 +1962,14 @@ static bf_status wf_roll_flush(const bf_scene *scene, hipStream_t stream, bool s
     scene->wf_trace_launches += done_iters;
     r.open = false;
     scene->peers_rolling->fetch_sub(1, std::memory_order_relaxed);
+    r.multi = false;
+    lp.multi = 0u;
     if (scene->tables_in_pool) {
-        // the sequence's last table version becomes the handle's tables again (home buffers), behind the flush's kernels
+        // the sequence's last table version becomes the handle's tables again (home buffers), behind the flush's kernels.
+        // The block is found from the sensor record, the one table every update repoints (d.rects stays at the home
+        // buffer of a scene without rectangles).  The handle's state is back home before any copy can fail.
         const bf_scene::TabLayout &t = scene->tab;
-        const char *blk = (const char *) scene->d.rects - t.o_rects;
-        const uint32_t nr = scene->d.n_rects, ne = scene->d.n_emitters, ns = scene->info.n_shapes, nm = scene->n_materials;
-        if (nr) HIP_TRY(hipMemcpyAsync((void *) scene->home_rects, blk + t.o_rects, nr * sizeof(bfd::DRect), hipMemcpyDeviceToDevice, stream));
-        if (ns) HIP_TRY(hipMemcpyAsync((void *) scene->home_shapes, blk + t.o_shapes, ns * sizeof(bfd::DShape), hipMemcpyDeviceToDevice, stream));
-        if (ne) HIP_TRY(hipMemcpyAsync((void *) scene->home_emitters, blk + t.o_emit, ne * sizeof(bfd::DEmitter), hipMemcpyDeviceToDevice, stream));
-        if (nm) HIP_TRY(hipMemcpyAsync((void *) scene->home_materials, blk + t.o_mat, nm * sizeof(bfd::DMaterial), hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync((void *) scene->home_sensor, blk + t.o_sensor, sizeof(bfd::DSensor), hipMemcpyDeviceToDevice, stream));
+        const char *blk = (const char *) scene->d.sensor - t.o_sensor;
         bfd::DScene &d = const_cast<bf_scene *>(scene)->d;
         d.rects = scene->home_rects;
         d.shapes = scene->home_shapes;
@@ -1958,9 +1978,13 @@ static bf_status wf_roll_flush(const bf_scene *scene, hipStream_t stream, bool s
         d.sensor = scene->home_sensor;
         scene->tables_in_pool = false;
         scene->tab_next = 0;
+        const uint32_t nr = scene->d.n_rects, ne = scene->d.n_emitters, ns = scene->info.n_shapes, nm = scene->n_materials;
+        if (nr) HIP_TRY(hipMemcpyAsync((void *) scene->home_rects, blk + t.o_rects, nr * sizeof(bfd::DRect), hipMemcpyDeviceToDevice, stream));
+        if (ns) HIP_TRY(hipMemcpyAsync((void *) scene->home_shapes, blk + t.o_shapes, ns * sizeof(bfd::DShape), hipMemcpyDeviceToDevice, stream));
+        if (ne) HIP_TRY(hipMemcpyAsync((void *) scene->home_emitters, blk + t.o_emit, ne * sizeof(bfd::DEmitter), hipMemcpyDeviceToDevice, stream));
+        if (nm) HIP_TRY(hipMemcpyAsync((void *) scene->home_materials, blk + t.o_mat, nm * sizeof(bfd::DMaterial), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync((void *) scene->home_sensor, blk + t.o_sensor, sizeof(bfd::DSensor), hipMemcpyDeviceToDevice, stream));
     }
-    r.multi = false;
-    lp.multi = 0u;
     if (sync_timing) return wf_collect_timing(scene, stream);
     return BF_OK;
 }

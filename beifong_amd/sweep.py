@@ -53,7 +53,10 @@ def render_sweep(frames, n_streams=4, lib=None, device=None, rolling=True):
                 stats["updated"] += 1
             else:
                 if handles[j] is not None:
-                    streams[j].synchronize()          # the old handle's last render must be done before it goes
+                    # the old handle's rolling sequence is still open: finish its paths (bf_scene_destroy abandons them), and
+                    # let its last render be done before it goes
+                    handles[j].flush(stream=streams[j].cuda_stream)
+                    streams[j].synchronize()
                     handles[j].close()
                 handles[j] = capi.Scene(sd, lib)
                 keys[j] = key

@@ -505,6 +505,18 @@ def test_update_endpoints_equals_fresh_scene(hiplib):
         g.update_endpoints(sd_far)                        # same layout, but outside the bound the boxes allow for
 
 
+def _check_sweep_frames(cube, frames, what):
+    """Every frame of a render_sweep against the scene rebuilt for it: the oracle's addends (per cell), a fresh handle's
+    stand-alone render, and the weight channel (every path of the frame binned)."""
+    for k, (sd, lp) in enumerate(frames):
+        h, _, _ = capi.Scene(sd).render(lp)
+        assert np.allclose(cube[k], h, rtol=1e-4, atol=1e-2)
+        add = OracleScene(sd).render(lp, threads=8, addends=True)[3]
+        assert_fp32_sum(cube[k], add.ref, add.S, add.N, f"{what} frame {k}", counts=count_channels(lp, sd))
+        assert_two_fp32_sums(cube[k], h, add.S, add.N, f"{what} frame {k} vs stand-alone", counts=count_channels(lp, sd))
+        assert cube[k][4] == lp.n_paths, (what, k, cube[k][4])
+
+
 def test_render_sweep_reuses_device_scenes(hiplib):
     """The frame loop of animated_trans_rad.py: radar yaw sweep over a static scene, frames rotated
     over HIP streams, BVH built once per stream handle."""
@@ -516,9 +528,29 @@ def test_render_sweep_reuses_device_scenes(hiplib):
     cube = sweep.render_sweep(frames, n_streams=3)
     assert cube.shape == (9, 5 + 256)
     assert sweep.render_sweep.last_stats == {"created": 3, "updated": 6}
-    for k in (0, 4, 8):
-        h, _, _ = capi.Scene(frames[k][0]).render(frames[k][1])
-        assert np.allclose(cube[k], h, rtol=1e-4, atol=1e-2)
+    _check_sweep_frames(cube, frames, "yaw sweep")
+
+
+def test_render_sweep_changes_geometry_on_a_slot(hiplib):
+    """Two streams, frames alternating between two meshes in runs, so that a slot's next frame sometimes keeps its mesh
+    (an endpoint update joins the slot's rolling sequence) and sometimes brings the other one (a new handle).  Regression:
+    the old handle was closed with its rolling sequence still open, and bf_scene_destroy abandons the paths still in its
+    pool: the slot's earlier frames came back with a weight channel below n_paths."""
+    pytest.importorskip("torch")
+    from beifong_amd import sweep
+    mesh_a = scenes.bus_mesh(5000)
+    v, f = meshgen.bus(5000, seed=2)
+    v = np.ascontiguousarray(meshgen.place(v, yaw_deg=25.0, translate=(8.0, -2.0, 1.7)), dtype=np.float32)
+    f = np.ascontiguousarray(f, dtype=np.uint32)
+    mesh_b = (v, f, np.ascontiguousarray(meshgen.vertex_normals(v, f)))
+    order = "AAAABBAABBBB"            # slot 0 gets frames 0, 2, 4, ... = A A B A B B, slot 1 the same
+    yaws = np.linspace(-15, 15, len(order))
+    frames = [scenes.bus_radar(n_paths=1 << 14, mesh=mesh_a if m == "A" else mesh_b, radar_yaw_deg=float(y), seed=20 + k)
+              for k, (m, y) in enumerate(zip(order, yaws))]
+    cube = sweep.render_sweep(frames, n_streams=2)
+    assert cube.shape == (len(order), 5 + 256)
+    assert sweep.render_sweep.last_stats == {"created": 8, "updated": 4}
+    _check_sweep_frames(cube, frames, "geometry changes")
 
 
 @pytest.mark.parametrize("tx,P", [("wigner", 16), ("area", 7), ("area", 1)])
