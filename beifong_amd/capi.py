@@ -18,13 +18,13 @@ BF_SHAPE_RECTANGLE, BF_SHAPE_MESH = range(2)
 BF_EMITTER_SPOT, BF_EMITTER_AREA, BF_TRANSMITTER_AREA, BF_TRANSMITTER_WIGNER, BF_TRANSMITTER_PHASED, BF_EMITTER_POINT = range(6)
 BF_SIGNAL_CW, BF_SIGNAL_PULSE, BF_SIGNAL_LINFMCW = range(3)
 BF_SENSOR_FLUXMETER, BF_SENSOR_PERSPECTIVE, BF_RECEIVER_OMNI, BF_RECEIVER_WIGNER, BF_RECEIVER_PHASED, BF_SENSOR_IRRADIANCEMETER, BF_SENSOR_RADIANCEMETER = range(7)
-BF_ABI_VERSION = 4          # include/beifong_hip.h: BF_ABI_VERSION
+BF_ABI_VERSION = 5          # include/beifong_hip.h: BF_ABI_VERSION
 BF_VELEM_FLOATS = 32
 BF_SI_FLOATS = 27
 BF_MODE_PATH, BF_MODE_RANGE, BF_MODE_TIME, BF_MODE_RECEIVE_RAW, BF_MODE_RECEIVE_IQ = range(5)
 BF_COLOR_RGB, BF_COLOR_MONO = range(2)
 BF_FLAG_STATS, BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL, BF_FLAG_DOPPLER, BF_FLAG_MIX_RESAMPLE = 1, 2, 4, 8, 16
-BF_FLAG_ROLLING, BF_FLAG_TIMING, BF_FLAG_COUNT = 32, 64, 128
+BF_FLAG_ROLLING, BF_FLAG_TIMING, BF_FLAG_COUNT, BF_FLAG_FAST = 32, 64, 128, 256
 
 M16 = C.c_float * 16
 
@@ -57,7 +57,7 @@ class bf_emitter(C.Structure):
 
 
 BF_FILTER_RESOLUTION = 31
-BF_VARIANT_LEAN, BF_VARIANT_WIDE = 1, 2
+BF_VARIANT_LEAN, BF_VARIANT_WIDE, BF_VARIANT_FAST = 1, 2, 4
 
 
 class bf_rfilter(C.Structure):

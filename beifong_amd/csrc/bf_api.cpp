@@ -64,6 +64,31 @@ extern "C" hipError_t bfk_launch_tail(const bfd::DScene *sc, const bfd::DLaunch 
                                       uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
                                       hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap);
 extern "C" hipError_t bfk_roll_set(bfd::DRoll *ring, float4 *offsets, uint32_t idx, const bfd::DRoll *d, const float *offset3, hipStream_t stream);
+// BF_FLAG_FAST: the same launchers from the fast-arithmetic build of bf_kernels.hip / bf_wavefront.hip (bf_ns.h)
+extern "C" hipError_t bfk_launch_render_fast(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+                                             unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
+                                             hipStream_t stream);
+extern "C" hipError_t bfk_wf_shade_fast(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                        float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                        hipStream_t stream, int waves);
+extern "C" hipError_t bfk_wf_trace_fast(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
+                                        hipStream_t stream, int waves);
+extern "C" hipError_t bfk_launch_tail_fast(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
+                                           uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
+                                           hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap);
+
+namespace {
+// the kernels one render runs: the exact build, or the fast-arithmetic one (BF_FLAG_FAST)
+struct Kernels {
+    decltype(&bfk_launch_render) render;
+    decltype(&bfk_wf_shade) shade;
+    decltype(&bfk_wf_trace) trace;
+    decltype(&bfk_launch_tail) tail;
+};
+const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail};
+const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast};
+const Kernels &kernels_for(uint32_t flags) { return (flags & BF_FLAG_FAST) ? kFast : kExact; }
+}  // namespace
 
 namespace {
 
@@ -1402,6 +1427,7 @@ namespace {
 // Everything the launches of one render (or of one call of a rolling sequence) share.
 struct WfCtx {
     const bf_scene *scene;
+    const Kernels *k;
     const bfd::DLaunch *lp;
     float *hist;
     bf_path_record *rec;
@@ -1448,8 +1474,8 @@ static bf_status wf_collect_timing(const bf_scene *scene, hipStream_t stream) {
 }
 
 // pool size, masks, scheduling knobs and grids for `lp` on this handle
-static bf_status wf_setup(const bf_scene *scene, const bfd::DLaunch &lp, uint64_t pool_paths, float *hist_dev, bf_path_record *records_dev,
-                          hipStream_t stream, bool count_nodes, bool timed, WfCtx &c, bool rolling = false) {
+static bf_status wf_setup(const bf_scene *scene, const Kernels &k, const bfd::DLaunch &lp, uint64_t pool_paths, float *hist_dev,
+                          bf_path_record *records_dev, hipStream_t stream, bool count_nodes, bool timed, WfCtx &c, bool rolling = false) {
     uint64_t want = std::min<uint64_t>(scene->tun.pool, std::max<uint64_t>(pool_paths, 64));
     uint32_t n_main = (uint32_t) ((want + 63) & ~uint64_t(63)), n_surv = 0;
     if (rolling) {
@@ -1487,6 +1513,7 @@ static bf_status wf_setup(const bf_scene *scene, const bfd::DLaunch &lp, uint64_
         wf.m_hit[b] = scene->wf_masks + (4 * b + 3) * nb;
     }
     c.scene = scene;
+    c.k = &k;
     c.lp = &lp;
     c.hist = hist_dev;
     c.rec = records_dev;
@@ -1536,20 +1563,20 @@ static bf_status wf_iteration(const WfCtx &c, uint32_t it, int first) {
     if (first != 1) {
         // first launch of a rolling call (first == 2): the evicting variant — long paths make room for the new render's
         HIP_TRY(wf_tic(c, 1));
-        HIP_TRY(bfk_wf_shade(&scene->d, c.lp, &wf, it, first == 2 ? 3 : 0, c.hist, c.rec, c.grid_shade, c.lds_shade, c.stream,
-                             scene->tun.shade_waves));
+        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first == 2 ? 3 : 0, c.hist, c.rec, c.grid_shade, c.lds_shade, c.stream,
+                           scene->tun.shade_waves));
         HIP_TRY(wf_toc(c));
     }
     if (first != 0) {
         HIP_TRY(wf_tic(c, 1));
-        HIP_TRY(bfk_wf_shade(&scene->d, c.lp, &wf, it, first, c.hist, c.rec, c.grid_shade, c.lds_shade, c.stream, scene->tun.shade_waves));
+        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first, c.hist, c.rec, c.grid_shade, c.lds_shade, c.stream, scene->tun.shade_waves));
         HIP_TRY(wf_toc(c));
     }
     return BF_OK;
 }
 static bf_status wf_trace_launch(const WfCtx &c, uint32_t it) {
     HIP_TRY(wf_tic(c, 0));
-    HIP_TRY(bfk_wf_trace(&c.scene->d, &c.scene->wf, it, c.count_nodes ? 1 : 0, c.grid_trace, c.stream, c.scene->tun.trace_waves));
+    HIP_TRY(c.k->trace(&c.scene->d, &c.scene->wf, it, c.count_nodes ? 1 : 0, c.grid_trace, c.stream, c.scene->tun.trace_waves));
     HIP_TRY(wf_toc(c));
     return BF_OK;
 }
@@ -1570,8 +1597,8 @@ static bf_status wf_tail_launch(const WfCtx &c, uint32_t it, uint32_t est_live, 
     }
     scene->wf.tail_share = share;
     HIP_TRY(wf_tic(c, 2));
-    HIP_TRY(bfk_launch_tail(&scene->d, c.lp, &scene->wf, it, est_live, c.hist, c.rec, c.count_nodes ? 1 : 0, c.lds_tail, c.stream,
-                            scene->tun.tail_waves, scene->tun.tail_spread, scene->tun.tail_blocks));
+    HIP_TRY(c.k->tail(&scene->d, c.lp, &scene->wf, it, est_live, c.hist, c.rec, c.count_nodes ? 1 : 0, c.lds_tail, c.stream,
+                      scene->tun.tail_waves, scene->tun.tail_spread, scene->tun.tail_blocks));
     HIP_TRY(wf_toc(c));
     return BF_OK;
 }
@@ -1614,10 +1641,10 @@ static bf_status read_guards(const bf_scene *scene, unsigned long long *lost, un
 // bounce `it` while wf_trace(it) is still running, so the device never idles on
 // the decision; once at most wf_tail_threshold() slots are live, one tail launch
 // finishes them (including the paths those slots still have to start).
-static bf_status wf_render(const bf_scene *scene, const bfd::DLaunch &lp, float *hist_dev, bf_path_record *records_dev,
+static bf_status wf_render(const bf_scene *scene, const Kernels &k, const bfd::DLaunch &lp, float *hist_dev, bf_path_record *records_dev,
                            hipStream_t stream, bool count_nodes, bool stats) {
     WfCtx c;
-    bf_status st = wf_setup(scene, lp, lp.n_paths, hist_dev, records_dev, stream, count_nodes, stats, c);
+    bf_status st = wf_setup(scene, k, lp, lp.n_paths, hist_dev, records_dev, stream, count_nodes, stats, c);
     if (st != BF_OK) return st;
     bfd::WF &wf = scene->wf;
     HIP_TRY(hipMemsetAsync(wf.n_live, 0, (bfd::kWfMaxIter + 2) * sizeof(uint32_t), stream));
@@ -1785,7 +1812,7 @@ static bf_status wf_roll_render(const bf_scene *scene, const bf_launch *launch, 
     if (r.multi) {                 // the endpoints moved since the sequence was opened: per-path tables from now on (general kernels)
         lp.multi = 1u;
         lp.lean = 0u;
-        scene->last_variant = 0u;
+        scene->last_variant &= (uint32_t) BF_VARIANT_FAST;
     }
     lp.roll_newest = newest;
     lp.roll_lo = newest + 1u > r.window ? newest + 1u - r.window : 0u;
@@ -1803,7 +1830,7 @@ static bf_status wf_roll_render(const bf_scene *scene, const bf_launch *launch, 
         // bf_device_core.h: Shift — slack for the largest offset of the sequence so far (older paths just get wider boxes)
         lp.box_slack = 1e-6f * (scene->origin_scale_built + 2.f * r.dmax);
     }
-    if ((st = wf_setup(scene, lp, (uint64_t) K * lp.batch_paths, nullptr, nullptr, stream, r.count_nodes, r.timed, c, true)) != BF_OK) return st;
+    if ((st = wf_setup(scene, kernels_for(r.shape.flags), lp, (uint64_t) K * lp.batch_paths, nullptr, nullptr, stream, r.count_nodes, r.timed, c, true)) != BF_OK) return st;
     lp.roll = scene->roll_ring;           // wf_setup may have (re)allocated the pool and the ring with it
     lp.batch_offsets = with_offsets ? scene->roll_offsets : nullptr;
     scene->wf.offsets = lp.batch_offsets;
@@ -1897,7 +1924,7 @@ static bf_status wf_roll_flush(const bf_scene *scene, hipStream_t stream, bool s
     }
     bfd::DLaunch &lp = r.lp;
     WfCtx c;
-    if ((st = wf_setup(scene, lp, (uint64_t) r.per_call * lp.batch_paths, nullptr, nullptr, stream, r.count_nodes, r.timed, c, true)) != BF_OK) return st;
+    if ((st = wf_setup(scene, kernels_for(r.shape.flags), lp, (uint64_t) r.per_call * lp.batch_paths, nullptr, nullptr, stream, r.count_nodes, r.timed, c, true)) != BF_OK) return st;
     bfd::WF &wf = scene->wf;
     volatile uint32_t *hq = scene->wf_host;
     const bool fb_ready = scene->wf_fb_pending && hipEventQuery(scene->wf_fb_event) == hipSuccess;
@@ -2127,6 +2154,11 @@ static bf_status render_common(const bf_scene *scene, const bf_launch *launch, c
     const bool rolling = (launch->flags & BF_FLAG_ROLLING) != 0u && launch->n_paths != 0u &&
                          (uint64_t) n_renders * launch->n_paths <= scene->tun.pool && n_renders <= bfd::kRollRing;
     if (launch->flags & BF_FLAG_ROLLING) {
+        // one sequence, one arithmetic: its long paths are finished by the kernels of the mode it was opened with
+        if (scene->roll.open && ((launch->flags ^ scene->roll.shape.flags) & BF_FLAG_FAST))
+            return fail(BF_ERR_INVALID, "BF_FLAG_ROLLING: the open rolling sequence of this handle was started %s BF_FLAG_FAST; "
+                                        "flush it (bf_scene_flush) before rolling renders of the other mode",
+                        (scene->roll.shape.flags & BF_FLAG_FAST) ? "with" : "without");
         if (multi_pixel || (launch->flags & BF_FLAG_MEGAKERNEL))
             return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_ROLLING: multi-pixel films and the one-kernel variant do not roll");
         if (stats_out)
@@ -2162,6 +2194,8 @@ static bf_status render_common(const bf_scene *scene, const bf_launch *launch, c
     lp.lean = lean_profile(scene, launch, receive_mode, multi_pixel) ? 1u : 0u;
     lp.wide = scene->sensor_host.filt_n != 0u ? 1u : 0u;
     scene->last_variant = (lp.lean ? (uint32_t) BF_VARIANT_LEAN : 0u) | (lp.wide ? (uint32_t) BF_VARIANT_WIDE : 0u);      // reconstruction filter wider than a pixel: the kernels' kWide variants
+    if (launch->flags & BF_FLAG_FAST) scene->last_variant |= (uint32_t) BF_VARIANT_FAST;
+    const Kernels &kern = kernels_for(launch->flags);
     lp.count = ((launch->flags & (BF_FLAG_STATS | BF_FLAG_COUNT)) || stats_out) ? 1u : 0u;
     lp.doppler = (receive_mode && (launch->flags & BF_FLAG_DOPPLER)) ? 1u : 0u;
     lp.resample = (receive_mode && scene->any_resample) ? 1u : 0u;
@@ -2233,10 +2267,10 @@ static bf_status render_common(const bf_scene *scene, const bf_launch *launch, c
     }
     if (launch->n_paths) {
         if (launch->flags & BF_FLAG_MEGAKERNEL) {
-            HIP_TRY(bfk_launch_render(&scene->d, &lp, hist_dev, records_dev, scene->counters,
-                                      (launch->flags & BF_FLAG_STATS) ? 1 : 0, grid, lds, stream));
+            HIP_TRY(kern.render(&scene->d, &lp, hist_dev, records_dev, scene->counters,
+                                (launch->flags & BF_FLAG_STATS) ? 1 : 0, grid, lds, stream));
         } else {
-            bf_status wst = wf_render(scene, lp, hist_dev, records_dev, stream, (launch->flags & BF_FLAG_STATS) != 0,
+            bf_status wst = wf_render(scene, kern, lp, hist_dev, records_dev, stream, (launch->flags & BF_FLAG_STATS) != 0,
                                       stats_out != nullptr);
             if (wst != BF_OK) return wst;
         }

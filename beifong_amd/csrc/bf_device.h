@@ -14,12 +14,14 @@
 //   rects, shapes, materials, emitters : small tables (scenes hold a handful)
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "bf_ns.h"
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/beifong_hip.h"
 
-namespace bfd {
+BF_NS_BEGIN
 
 #ifndef BF_TRI_STRIDE
 #define BF_TRI_STRIDE 3
@@ -260,4 +262,4 @@ enum {
     CTR_COUNT
 };
 
-}  // namespace bfd
+BF_NS_END  // namespace bfd

@@ -7,7 +7,7 @@
 #include "bf_device.h"
 #include "bf_device_math.h"
 
-namespace bfd {
+BF_NS_BEGIN
 
 struct Hit {
     float t, u, v;
@@ -1246,4 +1246,4 @@ BF_DEV float sensor_sample_ray(const DScene &sc, float px, float py, float ax, f
     }
 }
 
-}  // namespace bfd
+BF_NS_END  // namespace bfd

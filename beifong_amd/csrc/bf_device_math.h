@@ -5,15 +5,18 @@
 // enoki's generic array code does: dot = fma chain from lane 0, cross = fmsub
 // form, normalize = v * (1/sqrt(dot))), and nowhere else — the translation
 // unit is compiled with -ffp-contract=off.  Division and sqrt are IEEE
-// (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt).  Scalar
+// (hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt); the BF_FAST build (BF_FLAG_FAST, bf_ns.h) drops that flag and
+// keeps IEEE division only where it says div_ieee / rcp_ieee.  Scalar
 // transcendentals (sin, cos, acos, exp, log, erf) follow the fp32 specification
 // below (bf_exp, bf_log, ...): fixed IEEE operation sequences shared with the
 // oracle, within 2.5 ulp of the libm calls the reference's scalar variant makes.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "bf_ns.h"
 #include <stdint.h>
 
-namespace bfd {
+BF_NS_BEGIN
 
 #define BF_DEV __device__ __forceinline__
 #define BF_HD __host__ __device__ __forceinline__
@@ -31,6 +34,18 @@ BF_DEV float fmsub(float a, float b, float c) { return __builtin_fmaf(a, b, -c);
 BF_DEV float fnmadd(float a, float b, float c) { return __builtin_fmaf(-a, b, c); }
 BF_DEV float sqr(float x) { return x * x; }
 BF_DEV float rcp(float x) { return 1.f / x; }
+// A correctly rounded fp32 a / b in both builds (bf_ns.h).  The fast build keeps it for the conversions between frequency and
+// wavelength, whose results enter the mix_resample beat |f_after - f_rx|: a difference of two nearly equal frequencies, where one
+// ulp of either moves a return across an ADC row.  fp64 division is exact IEEE under either flag, and rounding its quotient to
+// fp32 gives the correctly rounded fp32 quotient (53 >= 2 * 24 + 2: the double rounding is innocuous).
+BF_DEV float div_ieee(float a, float b) {
+#if BF_FAST
+    return (float) ((double) a / (double) b);
+#else
+    return a / b;
+#endif
+}
+BF_DEV float rcp_ieee(float x) { return div_ieee(1.f, x); }
 BF_DEV float safe_sqrt(float x) { return __builtin_sqrtf(__builtin_fmaxf(x, 0.f)); }
 
 // ---------------------------------------------------------------------------
@@ -443,4 +458,4 @@ BF_DEV float erfinv_giles(float x) {
     return p * x;
 }
 
-}  // namespace bfd
+BF_NS_END  // namespace bfd

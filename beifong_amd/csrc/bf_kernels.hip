@@ -22,7 +22,7 @@
 
 #include "bf_path_logic.h"
 
-namespace bfd {
+BF_NS_BEGIN
 
 // RESUME = false: the whole render in one launch (ablation of the wavefront
 // pipeline, BF_FLAG_MEGAKERNEL).
@@ -547,10 +547,10 @@ __global__ __launch_bounds__(kBlock) void bf_trace_kernel(DScene sc, uint64_t n,
     }
 }
 
-}  // namespace bfd
+BF_NS_END  // namespace bfd
 
 // host-callable launchers (used by bf_api.cpp, which is plain C++)
-extern "C" hipError_t bfk_launch_render(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+extern "C" hipError_t BF_LAUNCHER(bfk_launch_render)(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
                                         unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
                                         hipStream_t stream) {
     bfd::WF none;
@@ -580,7 +580,7 @@ extern "C" hipError_t bfk_launch_render(const bfd::DScene *sc, const bfd::DLaunc
 //   spread     : spread the survivors thinly while the chip has room: a wave that starts with ~16 paths instead of 64
 //                runs them four lanes per ray (traverse_quad) from its first bounce and waits for the longest of 16
 //   block_cap  : at most this many workgroups (0: no cap)
-extern "C" hipError_t bfk_launch_tail(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
+extern "C" hipError_t BF_LAUNCHER(bfk_launch_tail)(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
                                       uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
                                       hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
     // one lane per live slot (gathered from the alive masks), at most one thread per pool slot
@@ -624,7 +624,8 @@ extern "C" hipError_t bfk_launch_tail(const bfd::DScene *sc, const bfd::DLaunch 
     return hipGetLastError();
 }
 
-namespace bfd {
+#if !BF_FAST      // the rest (probes, ray queries, mesh translation, host helpers) exists in the exact build only
+BF_NS_BEGIN
 // Developer probe (tools/fetch_probe.py, profiles/README.md): what rocprofv3's FETCH_SIZE reports for the access patterns of
 // this engine, on a table of known size that is read exactly once per launch.
 //   MODE 0: streaming — thread g loads row g (16 B per lane, coalesced): every 128-byte line fully used by one wave
@@ -641,7 +642,7 @@ template <int MODE> __global__ void bf_gather_probe(const float4 *__restrict__ t
     const float4 v = table[row];
     if (v.x == 12345.678f) out[g & 1023u] = v;      // (never true: keeps the load)
 }
-}  // namespace bfd
+BF_NS_END  // namespace bfd
 extern "C" hipError_t bfk_gather_probe(int mode, const float4 *table, uint32_t n_rows, float4 *out, hipStream_t stream) {
     const uint32_t n = mode == 2 ? n_rows / 8u : n_rows;
     const dim3 grid((n + 255u) / 256u), block(256);
@@ -651,7 +652,7 @@ extern "C" hipError_t bfk_gather_probe(int mode, const float4 *table, uint32_t n
     return hipGetLastError();
 }
 
-namespace bfd {
+BF_NS_BEGIN
 // one descriptor of a rolling sequence's ring (kernel arguments are captured at launch: no staging buffer to keep alive)
 __global__ void bf_roll_set_kernel(DRoll *ring, float4 *offsets, uint32_t idx, DRoll d, float4 off) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -659,14 +660,14 @@ __global__ void bf_roll_set_kernel(DRoll *ring, float4 *offsets, uint32_t idx, D
         offsets[idx] = off;
     }
 }
-}  // namespace bfd
+BF_NS_END  // namespace bfd
 extern "C" hipError_t bfk_roll_set(bfd::DRoll *ring, float4 *offsets, uint32_t idx, const bfd::DRoll *d, const float *offset3, hipStream_t stream) {
     const float4 off = offset3 ? make_float4(offset3[0], offset3[1], offset3[2], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
     hipLaunchKernelGGL(bfd::bf_roll_set_kernel, dim3(1), dim3(64), 0, stream, ring, offsets, idx, *d, off);
     return hipGetLastError();
 }
 
-namespace bfd {
+BF_NS_BEGIN
 // bf_scene_translate_meshes: triangles and node boxes of the pristine copies shifted by `d`.
 __global__ void bf_translate_kernel(const float4 *__restrict__ tris0, float4 *__restrict__ tris, uint32_t n_tri_rows,
                                     const float4 *__restrict__ nodes0, float4 *__restrict__ nodes, float4 *__restrict__ qnodes, uint32_t n_nodes,
@@ -753,7 +754,7 @@ __global__ void bf_translate_kernel(const float4 *__restrict__ tris0, float4 *__
         wnodes[2u * i + 1u] = make_float4(hi[1], hi[2], b.z, b.w);
     }
 }
-}  // namespace bfd
+BF_NS_END  // namespace bfd
 
 extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, uint32_t n_tri_rows, const float4 *nodes0,
                                            float4 *nodes, float4 *qnodes, uint32_t n_nodes, const float4 *wnodes0, float4 *wnodes,
@@ -786,7 +787,7 @@ extern "C" int bfdbg_tail_profile_clear(void) {
  * precomputed emitter constants follow the same specification as the kernels. */
 extern "C" float bfk_host_cos(float x) { return bfd::bf_cos(x); }
 
-namespace bfd {
+BF_NS_BEGIN
 __global__ void bf_elementary_kernel(int op, uint64_t n, const float *__restrict__ x, float *__restrict__ y) {
     uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -802,7 +803,7 @@ __global__ void bf_elementary_kernel(int op, uint64_t n, const float *__restrict
     }
     y[i] = r;
 }
-}  // namespace bfd
+BF_NS_END  // namespace bfd
 
 extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y) {
     unsigned grid = (unsigned) ((n + 255) / 256);
@@ -823,3 +824,4 @@ extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const 
                            out_prim, out_shape, out_uv, out_hit, out_si);
     return hipGetLastError();
 }
+#endif  // !BF_FAST

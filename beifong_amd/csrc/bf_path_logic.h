@@ -20,7 +20,7 @@
 #include "bf_device_core.h"
 #include "bf_wavefront.h"
 
-namespace bfd {
+BF_NS_BEGIN
 
 constexpr uint32_t kFlagValid = 1u << 24, kFlagFilmOk = 1u << 25, kFlagTermPending = 1u << 26, kDepthMask = 0xffffffu;
 // multi-pixel films: the sample landed in the left / upper neighbour of the pixel it was drawn in (ImageBlock::put)
@@ -326,12 +326,12 @@ template <class W> BF_DEV float phased_sample_wigner(const float *__restrict__ t
 }
 BF_DEV float tx_eval_signal(CEmitter &e, float time, float frequency) {
     if (e.signal_type == BF_SIGNAL_LINFMCW) {
-        float t = fmodulo_j(time, rcp(e.prf));
+        float t = fmodulo_j(time, rcp_ieee(e.prf));
         float ti = 0 + e.pulse_len / 2;
-        float fi = e.freq_centre + (e.freq_ext / e.pulse_len) * (t - ti);
+        float fi = e.freq_centre + div_ieee(e.freq_ext, e.pulse_len) * (t - ti);
         return rect_j((t - ti) / e.pulse_len) > 0.f ? wchirp_j(t - ti, frequency - fi, e.pulse_len, e.amplitude) : 0.f;
     } else if (e.signal_type == BF_SIGNAL_PULSE) {
-        float t = fmodulo_j(time, rcp(e.prf));
+        float t = fmodulo_j(time, rcp_ieee(e.prf));
         float ti = 0 + e.pulse_len / 2;
         float fi = e.freq_centre;
         return rect_j((t - ti) / e.pulse_len) > 0.f ? wchirp_j(t - ti, frequency - fi, e.pulse_len, e.amplitude) : 0.f;
@@ -344,9 +344,9 @@ BF_DEV float freq_of(float c, float lambda_nm) { return (float) ((double) c * (1
 // `frequencies` uninitialised there: refused at scene creation (bf_api.cpp).
 BF_DEV float tx_delta_frequency(CEmitter &e, float time) {
     if (e.signal_type == BF_SIGNAL_LINFMCW) {
-        float t = fmodulo_j(time, rcp(e.prf));
+        float t = fmodulo_j(time, rcp_ieee(e.prf));
         float ti = 0 + e.pulse_len / 2;
-        return e.freq_centre + (e.freq_ext / e.pulse_len) * (t - ti);
+        return e.freq_centre + div_ieee(e.freq_ext, e.pulse_len) * (t - ti);
     }
     return e.freq_centre;
 }
@@ -354,7 +354,7 @@ BF_DEV float tx_delta_frequency(CEmitter &e, float time) {
 // overwritten with MTS_C * rcp(frequency) * 1e9 (a double product rounded to Float) before anything else reads it, and the signal
 // power is 1
 BF_DEV float tx_resampled_lambda(const DScene &sc, CEmitter &e, float time) {
-    return (float) ((double) (sc.c * rcp(tx_delta_frequency(e, time))) * 1e9);
+    return (float) ((double) (sc.c * rcp_ieee(tx_delta_frequency(e, time))) * 1e9);
 }
 
 // Transmitter::eval — areatransmitter.cpp:65-73, wignertransmitter.cpp:193-271
@@ -465,22 +465,22 @@ BF_DEV float receiver_sample_ray(const DScene &sc, float time, bool mix, float w
             // sample_delta_frequency(time) (:149-166): the instantaneous frequency at the sampled receive time, weight 1
             freq = s.freq_centre;
             if (s.rx_signal == BF_SIGNAL_LINFMCW) {
-                float t = fmodulo_j(time, rcp(s.rx_prf));
+                float t = fmodulo_j(time, rcp_ieee(s.rx_prf));
                 float ti = 0 + s.rx_pulse_len / 2;
-                freq = s.freq_centre + (s.freq_ext / s.rx_pulse_len) * (t - ti);
+                freq = s.freq_centre + div_ieee(s.freq_ext, s.rx_pulse_len) * (t - ti);
             }
         } else {
             // the uniform sample above, weighted with eval_signal(time, f) (:118-142)
             signal_power = s.rx_amplitude * s.rx_amplitude;
             if (s.rx_signal != BF_SIGNAL_CW) {
-                float t = fmodulo_j(time, rcp(s.rx_prf));
+                float t = fmodulo_j(time, rcp_ieee(s.rx_prf));
                 float ti = 0 + s.rx_pulse_len / 2;
-                float fi = s.rx_signal == BF_SIGNAL_LINFMCW ? s.freq_centre + (s.freq_ext / s.rx_pulse_len) * (t - ti) : s.freq_centre;
+                float fi = s.rx_signal == BF_SIGNAL_LINFMCW ? s.freq_centre + div_ieee(s.freq_ext, s.rx_pulse_len) * (t - ti) : s.freq_centre;
                 signal_power = rect_j((t - ti) / s.rx_pulse_len) > 0.f ? wchirp_j(t - ti, freq - fi, s.rx_pulse_len, s.rx_amplitude) : 0.f;
             }
         }
     }
-    lambda0 = (float) ((double) (sc.c * rcp(freq)) * 1e9);
+    lambda0 = (float) ((double) (sc.c * rcp_ieee(freq)) * 1e9);
     if (s.type == BF_RECEIVER_PHASED) {
         // phasedreceiver.cpp:299-365: geom_gain = W(ds) * pdf * (1 - (ds.d . ds.n)^4), ds.d the LOCAL cosine direction
         float w = phased_sample_wigner(s.velems, s.n_velems, s.wid, o, local, lambda0);
@@ -1282,4 +1282,4 @@ template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, fl
     }
 }
 
-}  // namespace bfd
+BF_NS_END  // namespace bfd

@@ -16,9 +16,11 @@
 // and writes 1 KiB contiguous per array.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "bf_ns.h"
 #include <stdint.h>
 
-namespace bfd {
+BF_NS_BEGIN
 
 constexpr uint32_t kWfMaxIter = 4096;   // ring of per-bounce live counters
 constexpr uint32_t kShadeChain = 8;        // wf_shade: vertices per visit while rays resolve early (C5: 8 beats 3 by 4 %, C2-C4 indifferent; profiles/r02_chain_sweep.txt)
@@ -121,4 +123,4 @@ struct WF {
     uint32_t surv_claims_max;       // claims one wave may make per launch: n_waves * max <= survivor batches, so no batch is claimed twice in a launch
 };
 
-}  // namespace bfd
+BF_NS_END  // namespace bfd

@@ -23,7 +23,7 @@
 // operations in the same order.
 #include "bf_path_logic.h"
 
-namespace bfd {
+BF_NS_BEGIN
 
 // OR-reduce per-lane bit contributions into the per-batch mask words.  Dense,
 // aligned rounds (every lane holds slot batch*64 + lane) store the ballot
@@ -1042,7 +1042,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t
     }
 }
 
-}  // namespace bfd
+BF_NS_END  // namespace bfd
 
 #ifdef BF_SHADE_PROF
 // developer build: wave entries [0..31] (24..31: cycles between stamps) and lanes [32..63] per section of wf_shade
@@ -1058,7 +1058,7 @@ extern "C" int bfdbg_shade_lane_profile(unsigned long long *out, int clear) {
 }
 #endif
 
-extern "C" hipError_t bfk_wf_shade(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
                                    float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
                                    hipStream_t stream, int waves) {
     // `waves`: register budget of the shading kernel (waves per SIMD); 3 is the sweet spot (168 VGPRs)
@@ -1117,7 +1117,7 @@ extern "C" hipError_t bfk_wf_shade(const bfd::DScene *sc, const bfd::DLaunch *lp
     return hipGetLastError();
 }
 
-extern "C" hipError_t bfk_wf_trace(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
+extern "C" hipError_t BF_LAUNCHER(bfk_wf_trace)(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
                                    hipStream_t stream, int waves) {
     const bool shift = wf->offsets != nullptr, quant = sc->qnodes != nullptr;
 #define BF_TRACE_LAUNCH2(S, W, SH, Q) \

@@ -132,6 +132,7 @@ int bfh_integrator_launch(void *integrator, void *endpoint, bf_launch *out) {
         out->rr_depth = in->rr_depth();
         out->time_c = 3.0e8f;
         in->configure(*out);
+        if (in->fast_math()) out->flags |= BF_FLAG_FAST;
         if (auto *se = dynamic_cast<Sensor *>((Object *) endpoint)) {
             out->n_paths = se->sampler()->sample_count();
             out->seed = se->sampler()->base_seed();

@@ -28,6 +28,7 @@ public:
     }
     int max_depth() const override { return m_integrator->max_depth(); }
     bool doppler() const override { return m_integrator->doppler(); }
+    bool fast_math() const override { return SamplingIntegrator::fast_math() || m_integrator->fast_math(); }
     int rr_depth() const override { return m_integrator->rr_depth(); }
 private:
     ref<SamplingIntegrator> m_integrator;

@@ -624,6 +624,8 @@ SamplingIntegrator::SamplingIntegrator(const Properties &props) : Integrator(pro
     // not a reference property: switches on Shape::doppler at the three call sites the reference carries commented
     // out (pathtimefrequency.cpp:124-126,141-144,180-183); false = the reference's HEAD
     m_doppler = props.bool_("doppler", false);
+    // not a reference property: the kernels' fast-arithmetic build (BF_FLAG_FAST); false = bit-identical to the oracle
+    m_fast_math = props.bool_("fast_math", false);
 }
 
 static uint32_t color_mode_of_variant() {
@@ -661,6 +663,7 @@ bool SamplingIntegrator::render(Scene *scene, Sensor *sensor) {
     lp.rr_depth = rr_depth();
     lp.time_c = 3.0e8f;
     configure(lp);
+    if (fast_math()) lp.flags |= BF_FLAG_FAST;
     if (lp.mode == BF_MODE_RECEIVE_RAW) Throw("this integrator only supports receive(), not render()");
     uint32_t n = bf_launch_channels(&lp);
     if (n != channels.size() * film->width() * film->height())
@@ -681,6 +684,7 @@ void SamplingIntegrator::receive_launch(const Receiver *receiver, bf_launch &lp)
     std::memset(&lp, 0, sizeof(lp));
     if (rt == "mix_resample") lp.flags |= BF_FLAG_MIX_RESAMPLE;
     if (doppler()) lp.flags |= BF_FLAG_DOPPLER;
+    if (fast_math()) lp.flags |= BF_FLAG_FAST;
     lp.color_mode = BF_COLOR_MONO;
     lp.n_paths = receiver->sampler()->sample_count();
     lp.seed = receiver->sampler()->base_seed();

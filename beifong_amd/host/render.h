@@ -288,6 +288,11 @@ public:
     virtual int rr_depth() const { return m_rr_depth; }
     /// "doppler" (not a reference property, default false = the reference's HEAD): BF_FLAG_DOPPLER for receive()
     virtual bool doppler() const { return m_doppler; }
+    /// "fast_math" (not a reference property, default false): BF_FLAG_FAST for render() and receive() — approximate fp32
+    /// division and square root in the kernels, held to the tolerance contract of include/beifong_hip.h instead of
+    /// bit-equality with the oracle
+    virtual bool fast_math() const { return m_fast_math; }
+    void set_fast_math(bool on) { m_fast_math = on; }
     /// SamplingIntegrator properties (integrator.cpp:27-43): edge of the image blocks (0: MTS_BLOCK_SIZE) and samples per pass
     uint32_t block_size() const { return m_block_size; }
     size_t samples_per_pass() const { return m_samples_per_pass; }
@@ -298,6 +303,7 @@ public:
 protected:
     int m_max_depth = -1, m_rr_depth = 5;
     bool m_doppler = false;
+    bool m_fast_math = false;
     uint32_t m_block_size = 0;
     size_t m_samples_per_pass = (size_t) -1;
 };

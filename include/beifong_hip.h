@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define BF_ABI_VERSION 4
+#define BF_ABI_VERSION 5
 
 typedef int bf_status;
 enum {
@@ -293,6 +293,25 @@ enum {
     BF_FLAG_ROLLING = 32u,     /* bf_render_device only: the render joins the handle's ROLLING SEQUENCE (below, bf_scene_flush) */
     BF_FLAG_TIMING = 64u,      /* rolling sequences: HIP events around every kernel launch; bf_scene_flush's statistics carry
                                   the per-kernel sums (trace_ms / shade_ms / tail_ms).  Set it on every render of the sequence. */
+    BF_FLAG_FAST = 256u,       /* opt-in fast arithmetic: the shading, tracing and tail kernels (and the one-kernel variant)
+                                  come from a second compile of the same sources with approximate fp32 division and square
+                                  root (v_rcp_f32 * a, v_sqrt_f32; no FMA contraction, the engine's own transcendentals;
+                                  conversions between frequency and wavelength stay correctly rounded).
+                                  Every other render is bit-identical per path to the oracle; a fast one is held to this
+                                  TOLERANCE CONTRACT instead (tests/fast_contract.py):
+                                  - a path AGREES with the oracle's when valid and n_rays are equal, |aux - aux_O| <=
+                                    1e-5 |aux_O| and |L - L_O| <= 1e-4 |L_O| + 1e-7 max_p |L_O,p|; the share of paths that
+                                    do not (a ray that grazes an edge, a Russian-roulette draw against a throughput one ulp
+                                    away) is below 1 % in every tested scene;
+                                  - the histogram is the fp32 sum of the fast render's own paths (same binning rule), so the
+                                    total weight and n_paths are exact, and sum_c |h - h_O| stays within the rounding of the
+                                    sums, 1e-4 of sum_c S_O, and what the diverged paths and the agreeing paths within
+                                    1e-5 |aux_O| of a cell edge can move.
+                                  Fast paths are bit-identical among themselves: stand-alone, batched, rolling (also across
+                                  endpoint updates), sharded, lean or general kernels, one-kernel variant.  A rolling render
+                                  whose BF_FLAG_FAST differs from the open sequence's fails with BF_ERR_INVALID and leaves the
+                                  sequence intact.  bf_stats.kernel_variant carries BF_VARIANT_FAST.  The ray queries
+                                  (bf_trace_closest / bf_trace_any / bf_ray_intersect) ignore the flag: always exact. */
     BF_FLAG_COUNT = 128u,      /* keep the ray / bounce / path counters of a render that returns no bf_stats of its own (a rolling
                                   sequence whose flush will be asked for statistics, the shards of bf_render_sharded_device).
                                   Implied by BF_FLAG_STATS and by a non-NULL stats_out; without any of them the counters stay
@@ -352,10 +371,11 @@ typedef struct bf_stats {
                                   lean profile (one area-type emitter, perspective camera or omnidirectional receiver, 1 x 1
                                   film, ...: every radar scene of the reference) and everything else is compiled out of the
                                   kernels; BF_VARIANT_WIDE = reconstruction filter wider than a pixel; 0 = general kernels.
-                                  Same results either way (BF_LEAN=0 in the environment forces the general ones)            */
+                                  Same results either way (BF_LEAN=0 in the environment forces the general ones).  ORed with
+                                  BF_VARIANT_FAST when the fast-arithmetic build ran (BF_FLAG_FAST)                           */
     uint32_t reserved_;
 } bf_stats;
-enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2 };
+enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4 };
 
 typedef struct bf_scene_info {
     uint32_t n_shapes, n_rects, n_triangles, n_bvh_nodes;
