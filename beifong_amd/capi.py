@@ -139,7 +139,7 @@ ABI_STRUCTS = [bf_material, bf_shape, bf_emitter, bf_sensor, bf_scene_desc, bf_l
 # every symbol include/beifong_hip.h declares
 EXPORTED_SYMBOLS = [
     "bf_abi_sizeof", "bf_abi_fingerprint", "bf_version", "bf_last_error", "bf_device_count", "bf_set_device", "bf_scene_create",
-    "bf_scene_destroy", "bf_scene_update_endpoints", "bf_scene_translate_meshes", "bf_scene_get_info", "bf_scene_clone", "bf_launch_channels", "bf_render_device", "bf_render",
+    "bf_scene_destroy", "bf_scene_update_endpoints", "bf_scene_translate_meshes", "bf_scene_transform_meshes", "bf_scene_get_info", "bf_scene_clone", "bf_launch_channels", "bf_render_device", "bf_render",
     "bf_scene_flush", "bf_scene_sync", "bf_shard_range", "bf_render_sharded_device", "bf_render_sharded", "bf_allreduce_device",
     "bf_render_batch_device", "bf_render_batch",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
@@ -183,6 +183,7 @@ def load_library(path=None):
     lib.bf_scene_clone.argtypes = [vp, C.POINTER(vp)]
     lib.bf_scene_update_endpoints.argtypes = [vp, C.POINTER(bf_scene_desc), vp]
     lib.bf_scene_translate_meshes.argtypes = [vp, C.POINTER(C.c_float * 3), vp]
+    lib.bf_scene_transform_meshes.argtypes = [vp, C.c_uint32, vp, vp]
     lib.bf_launch_channels.argtypes = [C.POINTER(bf_launch)]
     lib.bf_launch_channels.restype = C.c_uint32
     lib.bf_render_device.argtypes = [vp, C.POINTER(bf_launch), vp, vp, vp, C.POINTER(bf_stats)]
@@ -258,6 +259,34 @@ def render_sharded_device(scenes, launch, hist_ptrs, streams=None, lib=None):
     check(lib, lib.bf_render_sharded_device(handles, len(scenes), C.byref(launch), hp, sp, None), "bf_render_sharded_device")
 
 
+def rigid_table(transforms, n_shapes):
+    """The float32[n_shapes, 3, 4] table bf_scene_transform_meshes reads, from a {shape_index: 3x4 or 4x4} dict (shapes
+    left out: the identity) or an [n_shapes, 3, 4] array.  Checks shapes and indices only; the library checks rigidity."""
+    n_shapes = int(n_shapes)
+    if isinstance(transforms, dict):
+        xf = np.zeros((n_shapes, 3, 4), np.float32)
+        xf[:, :, :3] = np.eye(3, dtype=np.float32)
+        for k, m in transforms.items():
+            k = int(k)
+            if not 0 <= k < n_shapes:
+                raise ValueError(f"shape index {k} out of range for a scene of {n_shapes} shapes")
+            m = np.asarray(m)
+            if m.shape not in ((3, 4), (4, 4)):
+                raise ValueError(f"shape {k}: a transform is 3x4 or 4x4, got {m.shape}")
+            if m.shape == (4, 4) and not np.array_equal(m[3], [0, 0, 0, 1]):
+                raise ValueError(f"shape {k}: the last row of a 4x4 transform must be (0, 0, 0, 1)")
+            xf[k] = m[:3].astype(np.float32)
+        return xf
+    xf = np.asarray(transforms)
+    if xf.ndim != 3 or xf.shape[1:] != (3, 4):
+        raise ValueError(f"transforms must be [n_shapes, 3, 4], got {xf.shape}")
+    if xf.shape[0] != n_shapes:
+        raise ValueError(f"{xf.shape[0]} transforms for a scene of {n_shapes} shapes")
+    if not np.issubdtype(xf.dtype, np.floating):
+        raise TypeError(f"transforms must be floating point, got {xf.dtype}")
+    return np.ascontiguousarray(xf, dtype=np.float32)
+
+
 class Scene:
     """Device-resident immutable scene (bf_scene)."""
 
@@ -301,6 +330,14 @@ class Scene:
         off = (C.c_float * 3)(*[float(x) for x in offset])
         check(self.lib, self.lib.bf_scene_translate_meshes(self.handle, C.byref(off), C.c_void_p(stream) if stream else None),
               "bf_scene_translate_meshes")
+
+    def transform_meshes(self, transforms, stream=0):
+        """bf_scene_transform_meshes: mesh shape k rigidly to transforms[k] (absolute from the vertices as created), BVHs
+        re-fitted on the device.  `transforms`: {shape_index: 3x4 or 4x4} (shapes left out stay as created) or an
+        [n_shapes, 3, 4] array."""
+        xf = rigid_table(transforms, self.info().n_shapes)
+        check(self.lib, self.lib.bf_scene_transform_meshes(self.handle, xf.shape[0], _ptr(xf), C.c_void_p(stream) if stream else None),
+              "bf_scene_transform_meshes")
 
     def info(self):
         i = bf_scene_info()

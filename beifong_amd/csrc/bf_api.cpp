@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <new>
 #include <string>
@@ -50,6 +51,10 @@ extern "C" float bfk_host_cos(float x);
 extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, uint32_t n_tri_rows, const float4 *nodes0,
                                            float4 *nodes, float4 *qnodes, uint32_t n_nodes, const float4 *wnodes0, float4 *wnodes,
                                            uint32_t n_wchildren, const float *d, hipStream_t stream);
+extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
+                                       const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
+                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
+                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, hipStream_t stream);
 extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y);
 extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const float *rays, int any_hit, float *out_t,
                                        uint32_t *out_prim, uint32_t *out_shape, float *out_uv, uint8_t *out_hit,
@@ -255,6 +260,19 @@ struct bf_scene {
     uint32_t film_w = 1, film_h = 1;       // the sensor's film (bf_sensor.film_width / film_height)
     uint32_t adc_t = 0, adc_f = 0;         // what a receive-mode launch bins into: the ADC's window, or the whole ADC
     float4 *tris0 = nullptr, *nodes0 = nullptr, *wnodes0 = nullptr;   // pristine geometry, kept once bf_scene_translate_meshes is used
+    // bf_scene_transform_meshes: the pristine vertex normals once a transform has moved them, whether d.normals is
+    // this handle's own array (copy on write, as geom_private for the rest) and whether it holds moved normals now
+    float4 *normals0 = nullptr;
+    bool normals_private = false, normals_moved = false;
+    // the refit's state, built on the handle's first transform (nothing of it costs bf_scene_create anything)
+    struct Refit {
+        bool ready = false;
+        std::vector<uint32_t> off4, off16;       // level d of the four- / sixteen-wide tree: [off[d], off[d + 1]) of lvl4 / lvl16
+        uint32_t *lvl4 = nullptr, *lvl16 = nullptr;
+        float4 *ubox4 = nullptr, *ubox16 = nullptr;      // unpadded bounds of every child record (two float4 each)
+        float *xf = nullptr;                     // device: 16 floats per shape (bfk_launch_rigid)
+        std::vector<float> mesh_box;             // per shape: lo.xyz, hi.xyz of its pristine triangles (inverted: none)
+    } refit;
     // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
     std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
     std::vector<float *> array_dev;
@@ -1155,18 +1173,10 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
     return mark_last(scene, stream);
 }
 
-bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void *stream_) {
-    if (!scene || !offset) return fail(BF_ERR_INVALID, "null argument");
-    if (!(std::isfinite(offset[0]) && std::isfinite(offset[1]) && std::isfinite(offset[2])))
-        return fail(BF_ERR_INVALID, "bf_scene_translate_meshes: non-finite offset");
-    if (scene->d.n_tris == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
+// The geometry a handle moves (bf_scene_translate_meshes, bf_scene_transform_meshes): make d.tris / d.nodes / d.wnodes / d.qnodes
+// writable by this handle and keep the pristine rows in tris0 / nodes0 / wnodes0, which every later call starts from (both
+// calls are absolute).
+static bf_status own_geometry(bf_scene *scene, hipStream_t stream, const char *who) {
     const size_t tri_bytes = ((size_t) scene->d.n_tris * bfd::kTriStride + kTriPad) * sizeof(float4), node_bytes = (size_t) scene->d.n_nodes * 8 * sizeof(float4);
     const size_t wnode_bytes = scene->d.wnodes ? (size_t) scene->d.n_wnodes * 32 * sizeof(float4) : 0;
     const bool shared = scene->geom_token.use_count() > 1 && !scene->geom_private;
@@ -1183,7 +1193,7 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
             if (he != hipSuccess) {
                 for (int j = 0; j < k; ++j)
                     if (cp.p[j]) (void) hipFree(cp.p[j]);
-                return fail(BF_ERR_NOMEM, "bf_scene_translate_meshes: hipMalloc(%zu bytes): %s", bytes[k], hipGetErrorString(he));
+                return fail(BF_ERR_NOMEM, "%s: hipMalloc(%zu bytes): %s", who, bytes[k], hipGetErrorString(he));
             }
             cp.p[k] = (float4 *) q;
         }
@@ -1192,8 +1202,8 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
         return BF_OK;
     };
     if (shared) {
-        // copy on write: the arrays are shared with clones (bf_scene_clone) — this handle gets its own translated
-        // copies; the source of the translation is the geometry as created if this handle has it (it translated in
+        // copy on write: the arrays are shared with clones (bf_scene_clone) — this handle gets its own moved
+        // copies; the source of the motion is the geometry as created if this handle has it (it translated in
         // place before it was cloned), else the shared arrays themselves
         const size_t bytes[4] = {tri_bytes, node_bytes, wnode_bytes, scene->d.qnodes ? node_bytes / 2 : 0};
         bf_status cst = alloc_all(bytes);
@@ -1206,7 +1216,7 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
         scene->d.tris = cp.p[0];
         scene->d.nodes = cp.p[1];
         scene->d.wnodes = cp.p[2];
-        if (scene->d.qnodes) scene->d.qnodes = cp.p[3];       // re-quantised from the translated fp32 nodes by the kernel below
+        if (scene->d.qnodes) scene->d.qnodes = cp.p[3];       // re-quantised from the moved fp32 nodes by the caller's kernels
         scene->geom_private = true;       // (the token stays shared: tris0 / nodes0 may still READ the shared arrays)
     } else if (!scene->tris0) {
         // first use: keep the geometry as created, so that every later offset is applied to it (no drift)
@@ -1220,9 +1230,206 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
         scene->nodes0 = cp.p[1];
         scene->wnodes0 = cp.p[2];
     }
+    return BF_OK;
+}
+
+bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void *stream_) {
+    if (!scene || !offset) return fail(BF_ERR_INVALID, "null argument");
+    if (!(std::isfinite(offset[0]) && std::isfinite(offset[1]) && std::isfinite(offset[2])))
+        return fail(BF_ERR_INVALID, "bf_scene_translate_meshes: non-finite offset");
+    if (scene->d.n_tris == 0) return BF_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    {
+        bf_status ost = order_after_last(scene, stream);
+        if (ost == BF_OK) ost = close_sequence(scene, stream);
+        if (ost != BF_OK) return ost;
+    }
+    bf_status gst = own_geometry(scene, stream, __func__);
+    if (gst != BF_OK) return gst;
+    if (scene->normals_moved) {
+        // a rigid transform moved the vertex normals: a translation applies to the geometry as created
+        HIP_TRY(hipMemcpyAsync(const_cast<float4 *>(scene->d.normals), scene->normals0, (size_t) scene->d.n_tris * 3 * sizeof(float4),
+                               hipMemcpyDeviceToDevice, stream));
+        scene->normals_moved = false;
+    }
+    const size_t wnode_bytes = scene->d.wnodes ? (size_t) scene->d.n_wnodes * 32 * sizeof(float4) : 0;
     HIP_TRY(bfk_launch_translate(scene->tris0, const_cast<float4 *>(scene->d.tris), scene->d.n_tris * bfd::kTriStride, scene->nodes0,
                                  const_cast<float4 *>(scene->d.nodes), const_cast<float4 *>(scene->d.qnodes), scene->d.n_nodes, scene->wnodes0,
                                  const_cast<float4 *>(scene->d.wnodes), wnode_bytes ? scene->d.n_wnodes * 16u : 0u, offset, stream));
+    return mark_last(scene, stream);
+}
+
+// First transform of a handle: the level lists of both trees (from the child references of the pristine nodes, read back once),
+// the unpadded-bound scratch, the device transform table and every mesh's pristine box (read back once).  Runs before
+// own_geometry, so that a failure here leaves the handle's arrays as they were.
+static bf_status refit_prepare(bf_scene *scene, hipStream_t stream) {
+    bf_scene::Refit &rf = scene->refit;
+    HIP_TRY(hipStreamSynchronize(stream));      // the rows may still be written by work enqueued on `stream`
+    // the pristine rows: the handle's own copies once it has moved, else the arrays it renders
+    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
+    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
+    // levels by breadth-first order from the root: children reference deeper nodes only
+    auto levels = [](const std::vector<int32_t> &refs, uint32_t width, int32_t root, std::vector<uint32_t> &off, std::vector<uint32_t> &flat) {
+        off.assign(1, 0u);
+        flat.clear();
+        if (root < 0) return;
+        flat.push_back((uint32_t) root);
+        for (size_t begin = 0; begin < flat.size();) {
+            const size_t end = flat.size();
+            off.push_back((uint32_t) end);
+            for (size_t i = begin; i < end; ++i)
+                for (uint32_t k = 0; k < width; ++k) {
+                    const int32_t r = refs[(size_t) flat[i] * width + k];
+                    if (r >= 0) flat.push_back((uint32_t) r);
+                }
+            begin = end;
+        }
+    };
+    auto upload_u32 = [&](const std::vector<uint32_t> &v, uint32_t **out) -> bf_status {
+        *out = nullptr;
+        if (v.empty()) return BF_OK;
+        HIP_TRY(hipMalloc((void **) out, v.size() * sizeof(uint32_t)));
+        scene->owned.push_back(*out);
+        HIP_TRY(hipMemcpy(*out, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return BF_OK;
+    };
+    auto alloc = [&](size_t bytes, void **out) -> bf_status {
+        *out = nullptr;
+        if (!bytes) return BF_OK;
+        HIP_TRY(hipMalloc(out, bytes));
+        scene->owned.push_back(*out);
+        return BF_OK;
+    };
+    bf_status st;
+    std::vector<uint32_t> flat;
+    if (scene->d.n_nodes) {
+        std::vector<int32_t> refs((size_t) scene->d.n_nodes * 4);       // row 6 of every Node4
+        HIP_TRY(hipMemcpy2D(refs.data(), 16, (const char *) nodes0 + 6 * sizeof(float4), 8 * sizeof(float4), 16, scene->d.n_nodes,
+                            hipMemcpyDeviceToHost));
+        levels(refs, 4, scene->d.root, rf.off4, flat);
+        if ((st = upload_u32(flat, &rf.lvl4)) != BF_OK) return st;
+        if ((st = alloc((size_t) scene->d.n_nodes * 8 * sizeof(float4), (void **) &rf.ubox4)) != BF_OK) return st;
+    } else {
+        rf.off4.assign(1, 0u);
+    }
+    if (scene->d.wnodes && scene->d.n_wnodes) {
+        std::vector<int32_t> refs((size_t) scene->d.n_wnodes * 16);     // word 6 of every Node16 child record
+        HIP_TRY(hipMemcpy2D(refs.data(), 4, (const char *) wnodes0 + 6 * sizeof(float), 8 * sizeof(float), 4, refs.size(),
+                            hipMemcpyDeviceToHost));
+        levels(refs, 16, scene->d.wroot, rf.off16, flat);
+        if ((st = upload_u32(flat, &rf.lvl16)) != BF_OK) return st;
+        if ((st = alloc((size_t) scene->d.n_wnodes * 32 * sizeof(float4), (void **) &rf.ubox16)) != BF_OK) return st;
+    } else {
+        rf.off16.assign(1, 0u);
+    }
+    if ((st = alloc((size_t) scene->info.n_shapes * 16 * sizeof(float), (void **) &rf.xf)) != BF_OK) return st;
+    std::vector<float4> tris((size_t) scene->d.n_tris * bfd::kTriStride);
+    HIP_TRY(hipMemcpy(tris.data(), tris0, tris.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    const float inf = std::numeric_limits<float>::infinity();
+    rf.mesh_box.assign((size_t) scene->info.n_shapes * 6, 0.f);
+    for (uint32_t k = 0; k < scene->info.n_shapes; ++k)
+        for (int a = 0; a < 3; ++a) rf.mesh_box[6 * k + a] = inf, rf.mesh_box[6 * k + 3 + a] = -inf;
+    for (size_t t = 0; t < scene->d.n_tris; ++t) {
+        const float4 *r = &tris[t * bfd::kTriStride];
+        uint32_t shape;
+        std::memcpy(&shape, &r[1].w, 4);
+        float *b = &rf.mesh_box[6 * (size_t) shape];
+        for (int j = 0; j < 3; ++j) {
+            const float p[3] = {r[j].x, r[j].y, r[j].z};
+            for (int a = 0; a < 3; ++a) b[a] = std::min(b[a], p[a]), b[3 + a] = std::max(b[3 + a], p[a]);
+        }
+    }
+    rf.ready = true;
+    return BF_OK;
+}
+
+bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const float *to_world, void *stream_) {
+    if (!scene || !to_world) return fail(BF_ERR_INVALID, "null argument");
+    if (n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: %u transforms for a scene of %u shapes", n_shapes, scene->info.n_shapes);
+    // everything is checked before anything changes: a failed call leaves the scene as it was
+    std::vector<uint8_t> moves(n_shapes, 0);
+    for (uint32_t k = 0; k < n_shapes; ++k) {
+        const float *m = to_world + 12 * (size_t) k;
+        for (int j = 0; j < 12; ++j)
+            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: shape %u: non-finite entry", k);
+        for (int j = 0; j < 12; ++j) moves[k] |= m[j] != ((j % 5 == 0) ? 1.f : 0.f);
+        if (!moves[k]) continue;
+        double e = 0.0;
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) {
+                double d = a == b ? -1.0 : 0.0;
+                for (int r = 0; r < 3; ++r) d += (double) m[4 * r + a] * (double) m[4 * r + b];
+                e = std::max(e, std::fabs(d));
+            }
+        const double det = (double) m[0] * ((double) m[5] * m[10] - (double) m[6] * m[9]) - (double) m[1] * ((double) m[4] * m[10] - (double) m[6] * m[8]) +
+                           (double) m[2] * ((double) m[4] * m[9] - (double) m[5] * m[8]);
+        if (!(e <= 1e-5) || !(det > 0.0))
+            return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: shape %u: not a rigid motion (|R^T R - I| = %g, det R = %g)", k, e, det);
+        const bfd::DShape &sh = scene->shapes_host[k];
+        if (sh.type != BF_SHAPE_MESH)
+            return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: shape %u is not a mesh: its entry must be the identity", k);
+        if (sh.emitter >= 0)
+            return fail(BF_ERR_UNSUPPORTED, "bf_scene_transform_meshes: mesh shape %u carries emitter %d (its sampling tables are built "
+                                            "from the triangles as created); create a new scene", k, sh.emitter);
+    }
+    if (scene->d.n_tris == 0) return BF_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    {
+        bf_status ost = order_after_last(scene, stream);
+        if (ost == BF_OK) ost = close_sequence(scene, stream);
+        if (ost != BF_OK) return ost;
+    }
+    bf_status st = BF_OK;
+    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
+    if ((st = own_geometry(scene, stream, __func__)) != BF_OK) return st;
+    if (scene->d.normals && !scene->normals_private) {
+        // the vertex normals move too: into an array of the handle's own; the rows it rendered so far (shared with clones, or a
+        // clone's snapshot) stay untouched as the pristine normals0
+        const size_t bytes = (size_t) scene->d.n_tris * 3 * sizeof(float4);
+        void *q = nullptr;
+        hipError_t he = hipMalloc(&q, bytes);
+        if (he != hipSuccess) return fail(BF_ERR_NOMEM, "bf_scene_transform_meshes: hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(he));
+        scene->owned.push_back(q);
+        if (!scene->normals0) scene->normals0 = const_cast<float4 *>(scene->d.normals);
+        scene->d.normals = (const float4 *) q;
+        scene->normals_private = true;
+    }
+    bf_scene::Refit &rf = scene->refit;
+    // ray origins now lie on the moved meshes: raise the bound the boxes are padded for (bf_bvh.h) to cover them — never lowered
+    float oscale = scene->origin_scale_built;
+    for (uint32_t k = 0; k < n_shapes; ++k) {
+        const float *b = &rf.mesh_box[6 * (size_t) k];
+        if (!moves[k] || !(b[0] <= b[3])) continue;
+        const float *m = to_world + 12 * (size_t) k;
+        for (int r = 0; r < 3; ++r) {
+            double v = std::fabs((double) m[4 * r + 3]);
+            for (int c = 0; c < 3; ++c) v += std::fabs((double) m[4 * r + c]) * std::max(std::fabs((double) b[c]), std::fabs((double) b[3 + c]));
+            oscale = std::max(oscale, (float) (v * (1.0 + 1e-5)));
+        }
+    }
+    scene->origin_scale_built = oscale;
+    {
+        const size_t bytes = (size_t) n_shapes * 16 * sizeof(float);
+        bf_scene::Stage *stg = nullptr;
+        if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
+        float *h = (float *) stg->host;
+        for (uint32_t k = 0; k < n_shapes; ++k) {
+            std::memcpy(h + 16 * (size_t) k, to_world + 12 * (size_t) k, 12 * sizeof(float));
+            h[16 * k + 12] = moves[k] ? 1.f : 0.f;
+            h[16 * k + 13] = h[16 * k + 14] = h[16 * k + 15] = 0.f;
+        }
+        HIP_TRY(hipMemcpyAsync(rf.xf, h, bytes, hipMemcpyHostToDevice, stream));
+        if ((st = stage_release_after(stg, stream)) != BF_OK) return st;
+    }
+    HIP_TRY(bfk_launch_rigid(scene->tris0, const_cast<float4 *>(scene->d.tris), scene->normals0, const_cast<float4 *>(scene->d.normals),
+                             scene->d.n_tris, rf.xf, scene->nodes0, const_cast<float4 *>(scene->d.nodes), const_cast<float4 *>(scene->d.qnodes),
+                             scene->d.n_nodes, rf.lvl4, rf.off4.data(), (uint32_t) rf.off4.size() - 1u, rf.ubox4, scene->wnodes0,
+                             const_cast<float4 *>(scene->d.wnodes), rf.lvl16, rf.off16.data(), (uint32_t) rf.off16.size() - 1u, rf.ubox16,
+                             2e-7f * oscale, stream));
+    scene->normals_moved = scene->d.normals != nullptr;
     return mark_last(scene, stream);
 }
 
@@ -1282,13 +1489,17 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
     };
     if (src->tris0 || src->geom_private) {
         // `src` has been translated (in place, or into its own copies): the clone takes a snapshot of the geometry
-        // src renders now as ITS geometry "as created"; normals / texture coordinates stay shared
+        // src renders now as ITS geometry "as created"; texture coordinates (and normals no transform moved) stay shared
         const size_t tri_bytes = ((size_t) src->d.n_tris * bfd::kTriStride + kTriPad) * sizeof(float4), node_bytes = (size_t) src->d.n_nodes * 8 * sizeof(float4);
         const size_t wnode_bytes = src->d.wnodes ? (size_t) src->d.n_wnodes * 32 * sizeof(float4) : 0;
         if ((st = dup(src->d.tris, tri_bytes, (const void **) &sc->d.tris)) != BF_OK) return fail_out(st);
         if ((st = dup(src->d.nodes, node_bytes, (const void **) &sc->d.nodes)) != BF_OK) return fail_out(st);
         if ((st = dup(src->d.wnodes, wnode_bytes, (const void **) &sc->d.wnodes)) != BF_OK) return fail_out(st);
         if (src->d.qnodes && (st = dup(src->d.qnodes, node_bytes / 2, (const void **) &sc->d.qnodes)) != BF_OK) return fail_out(st);
+        // normals a rigid transform moved are part of the snapshot (the clone's own copy is never written: its first transform
+        // moves them into another array, as for any handle)
+        if (src->normals_private && (st = dup(src->d.normals, (size_t) src->d.n_tris * 3 * sizeof(float4), (const void **) &sc->d.normals)) != BF_OK)
+            return fail_out(st);
         sc->geom_private = true;
         sc->geom_token = std::make_shared<char>(0);      // the snapshot is the clone's alone: `src` keeps translating in place
     }

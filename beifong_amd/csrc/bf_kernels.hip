@@ -668,6 +668,51 @@ extern "C" hipError_t bfk_roll_set(bfd::DRoll *ring, float4 *offsets, uint32_t i
 }
 
 BF_NS_BEGIN
+// The 64-byte copy of one four-wide node that wf_trace reads (bf_bvh.h: Node4Q): bf::quantise_node4 (bf_bvh.cpp) operation for
+// operation, from the node's fp32 child boxes (rows 0..5) and child references (row 6).  Used after a mesh translation and after
+// a rigid-motion refit.
+BF_DEV void quantise_node4_dev(float4 lx, float4 ly, float4 lz, float4 hx, float4 hy, float4 hz, float4 refs, float4 *__restrict__ q) {
+    const float cl[3][4] = {{lx.x, lx.y, lx.z, lx.w}, {ly.x, ly.y, ly.z, ly.w}, {lz.x, lz.y, lz.z, lz.w}};
+    const float chh[3][4] = {{hx.x, hx.y, hx.z, hx.w}, {hy.x, hy.y, hy.z, hy.w}, {hz.x, hz.y, hz.z, hz.w}};
+    const int child[4] = {__float_as_int(refs.x), __float_as_int(refs.y), __float_as_int(refs.z), __float_as_int(refs.w)};
+    float nlo[3], scale[3];
+    uint32_t exps = 0, qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
+    for (int a = 0; a < 3; ++a) {
+        float lo = BF_INF, hi = -BF_INF;
+        for (int k = 0; k < 4; ++k)
+            if (child[k] != kNoNode) {
+                lo = __builtin_fminf(lo, cl[a][k]);
+                hi = __builtin_fmaxf(hi, chh[a][k]);
+            }
+        nlo[a] = lo;
+        int e = 0;
+        (void) __builtin_frexpf((hi - lo) * (1.f / 255.f), &e);
+        e = max(-100, min(100, e));
+        if (!(lo + 255.f * __builtin_ldexpf(1.f, e) >= hi)) ++e;
+        scale[a] = __builtin_ldexpf(1.f, e);
+        exps |= (uint32_t) (e + 127) << (8 * a);
+        for (int k = 0; k < 4; ++k) {
+            uint32_t ql = 255u, qh = 0u;
+            if (child[k] != kNoNode) {
+                const float inv = 1.f / scale[a];
+                float fl = __builtin_floorf((cl[a][k] - lo) * inv), fh = __builtin_ceilf((chh[a][k] - lo) * inv);
+                fl = __builtin_fminf(255.f, __builtin_fmaxf(0.f, fl));
+                fh = __builtin_fminf(255.f, __builtin_fmaxf(0.f, fh));
+                while (fl > 0.f && lo + fl * scale[a] > cl[a][k]) fl -= 1.f;
+                while (fh < 255.f && lo + fh * scale[a] < chh[a][k]) fh += 1.f;
+                ql = (uint32_t) fl;
+                qh = (uint32_t) fh;
+            }
+            qlo[a] |= ql << (8 * k);
+            qhi[a] |= qh << (8 * k);
+        }
+    }
+    q[0] = make_float4(nlo[0], nlo[1], nlo[2], __uint_as_float(exps));
+    q[1] = refs;
+    q[2] = make_float4(__uint_as_float(qlo[0]), __uint_as_float(qlo[1]), __uint_as_float(qlo[2]), __uint_as_float(qhi[0]));
+    q[3] = make_float4(__uint_as_float(qhi[1]), __uint_as_float(qhi[2]), 0.f, 0.f);
+}
+
 // bf_scene_translate_meshes: triangles and node boxes of the pristine copies shifted by `d`.
 __global__ void bf_translate_kernel(const float4 *__restrict__ tris0, float4 *__restrict__ tris, uint32_t n_tri_rows,
                                     const float4 *__restrict__ nodes0, float4 *__restrict__ nodes, float4 *__restrict__ qnodes, uint32_t n_nodes,
@@ -698,49 +743,7 @@ __global__ void bf_translate_kernel(const float4 *__restrict__ tris0, float4 *__
         o[0] = lx; o[1] = ly; o[2] = lz; o[3] = hx; o[4] = hy; o[5] = hz;
         o[6] = s[6];
         o[7] = s[7];
-        if (qnodes) {
-            // re-quantise the shifted node for wf_trace: bf::quantise_node4 (bf_bvh.cpp) operation for operation
-            const float cl[3][4] = {{lx.x, lx.y, lx.z, lx.w}, {ly.x, ly.y, ly.z, ly.w}, {lz.x, lz.y, lz.z, lz.w}};
-            const float chh[3][4] = {{hx.x, hx.y, hx.z, hx.w}, {hy.x, hy.y, hy.z, hy.w}, {hz.x, hz.y, hz.z, hz.w}};
-            const int child[4] = {__float_as_int(s[6].x), __float_as_int(s[6].y), __float_as_int(s[6].z), __float_as_int(s[6].w)};
-            float nlo[3], scale[3];
-            uint32_t exps = 0, qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
-            for (int a = 0; a < 3; ++a) {
-                float lo = BF_INF, hi = -BF_INF;
-                for (int k = 0; k < 4; ++k)
-                    if (child[k] != kNoNode) {
-                        lo = __builtin_fminf(lo, cl[a][k]);
-                        hi = __builtin_fmaxf(hi, chh[a][k]);
-                    }
-                nlo[a] = lo;
-                int e = 0;
-                (void) __builtin_frexpf((hi - lo) * (1.f / 255.f), &e);
-                e = max(-100, min(100, e));
-                if (!(lo + 255.f * __builtin_ldexpf(1.f, e) >= hi)) ++e;
-                scale[a] = __builtin_ldexpf(1.f, e);
-                exps |= (uint32_t) (e + 127) << (8 * a);
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t ql = 255u, qh = 0u;
-                    if (child[k] != kNoNode) {
-                        const float inv = 1.f / scale[a];
-                        float fl = __builtin_floorf((cl[a][k] - lo) * inv), fh = __builtin_ceilf((chh[a][k] - lo) * inv);
-                        fl = __builtin_fminf(255.f, __builtin_fmaxf(0.f, fl));
-                        fh = __builtin_fminf(255.f, __builtin_fmaxf(0.f, fh));
-                        while (fl > 0.f && lo + fl * scale[a] > cl[a][k]) fl -= 1.f;
-                        while (fh < 255.f && lo + fh * scale[a] < chh[a][k]) fh += 1.f;
-                        ql = (uint32_t) fl;
-                        qh = (uint32_t) fh;
-                    }
-                    qlo[a] |= ql << (8 * k);
-                    qhi[a] |= qh << (8 * k);
-                }
-            }
-            float4 *q = qnodes + 4u * i;
-            q[0] = make_float4(nlo[0], nlo[1], nlo[2], __uint_as_float(exps));
-            q[1] = s[6];
-            q[2] = make_float4(__uint_as_float(qlo[0]), __uint_as_float(qlo[1]), __uint_as_float(qlo[2]), __uint_as_float(qhi[0]));
-            q[3] = make_float4(__uint_as_float(qhi[1]), __uint_as_float(qhi[2]), 0.f, 0.f);
-        }
+        if (qnodes) quantise_node4_dev(lx, ly, lz, hx, hy, hz, s[6], qnodes + 4u * i);      // re-quantised for wf_trace
     }
     if (i < n_wchildren) {                      // one child record of a sixteen-wide node (bf_bvh.h: Node16), same re-padding
         const float4 a = wnodes0[2u * i], b = wnodes0[2u * i + 1u];
@@ -764,6 +767,176 @@ extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, ui
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(bfd::bf_translate_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, tris0, tris, n_tri_rows, nodes0, nodes,
                        qnodes, n_nodes, wnodes0, wnodes, n_wchildren, d[0], d[1], d[2]);
+    return hipGetLastError();
+}
+
+BF_NS_BEGIN
+// bf_scene_transform_meshes.  Step 1: every triangle slot from its pristine rows through its shape's rigid
+// 3x4 [R | t] (xf: 16 floats per shape, the 12 of the matrix, then word 12 = 1 if the shape moves at all).
+//   p' = fl(fl(fl(fl(r0 x) + fl(r1 y)) + fl(r2 z)) + t)   per row, every product and sum rounded (no FMA: __fmul_rn / __fadd_rn)
+//   n' = R n                                              same order, without t, not renormalised
+// The .w words (prim, shape, tag) stay; a shape whose entry is the identity keeps its rows bit for bit.
+BF_DEV float3 rigid_apply(const float *__restrict__ m, float x, float y, float z, bool with_t) {
+    float r[3];
+    for (int k = 0; k < 3; ++k) {
+        const float s = __fadd_rn(__fadd_rn(__fmul_rn(m[4 * k + 0], x), __fmul_rn(m[4 * k + 1], y)), __fmul_rn(m[4 * k + 2], z));
+        r[k] = with_t ? __fadd_rn(s, m[4 * k + 3]) : s;
+    }
+    return make_float3(r[0], r[1], r[2]);
+}
+
+__global__ void bf_rigid_tris_kernel(const float4 *__restrict__ tris0, float4 *__restrict__ tris, const float4 *__restrict__ nrm0,
+                                     float4 *__restrict__ nrm, uint32_t n_tris, const float *__restrict__ xf) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tris) return;
+    const float4 *s = tris0 + kTriStride * i;
+    float4 v[3] = {s[0], s[1], s[2]};
+    const float *m = xf + 16u * __float_as_uint(v[1].w);
+    const bool moves = m[12] != 0.f;
+    if (moves)
+        for (int j = 0; j < 3; ++j) {
+            const float3 p = rigid_apply(m, v[j].x, v[j].y, v[j].z, true);
+            v[j] = make_float4(p.x, p.y, p.z, v[j].w);
+        }
+    float4 *o = tris + kTriStride * i;
+    o[0] = v[0];
+    o[1] = v[1];
+    o[2] = v[2];
+    if (nrm) {
+        for (int j = 0; j < 3; ++j) {
+            float4 n = nrm0[3u * i + j];
+            if (moves) {
+                const float3 r = rigid_apply(m, n.x, n.y, n.z, false);
+                n = make_float4(r.x, r.y, r.z, n.w);
+            }
+            nrm[3u * i + j] = n;
+        }
+    }
+}
+
+// the builder's padding (bf_bvh.cpp: Builder::pad) of an UNPADDED box; abs_pad = 2e-7 origin_scale
+BF_DEV void refit_pad(float *lo, float *hi, float abs_pad) {
+    float m = 0.f;
+    for (int a = 0; a < 3; ++a)
+        m = __builtin_fmaxf(m, __builtin_fmaxf(hi[a] - lo[a], __builtin_fmaxf(__builtin_fabsf(lo[a]), __builtin_fabsf(hi[a]))));
+    const float e = 2e-6f * m + abs_pad + 1e-30f;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] -= e;
+        hi[a] += e;
+    }
+}
+BF_DEV void refit_grow_tris(const float4 *__restrict__ tris, uint32_t first, uint32_t count, float *lo, float *hi) {
+    for (uint32_t t = 0; t < count; ++t)
+        for (int j = 0; j < 3; ++j) {
+            const float4 p = tris[kTriStride * (first + t) + j];
+            lo[0] = __builtin_fminf(lo[0], p.x), lo[1] = __builtin_fminf(lo[1], p.y), lo[2] = __builtin_fminf(lo[2], p.z);
+            hi[0] = __builtin_fmaxf(hi[0], p.x), hi[1] = __builtin_fmaxf(hi[1], p.y), hi[2] = __builtin_fmaxf(hi[2], p.z);
+        }
+}
+// union of the W unpadded child records of node `ref` (ubox: two float4 per child record, (lo.xyz, hi.x), (hi.yz, -, -))
+template <int W> BF_DEV void refit_grow_node(const float4 *__restrict__ ubox, int32_t ref, float *lo, float *hi) {
+    const float4 *c = ubox + 2u * W * (uint32_t) ref;
+    for (int j = 0; j < W; ++j) {
+        const float4 a = c[2 * j], b = c[2 * j + 1];
+        lo[0] = __builtin_fminf(lo[0], a.x), lo[1] = __builtin_fminf(lo[1], a.y), lo[2] = __builtin_fminf(lo[2], a.z);
+        hi[0] = __builtin_fmaxf(hi[0], a.w), hi[1] = __builtin_fmaxf(hi[1], b.x), hi[2] = __builtin_fmaxf(hi[2], b.y);
+    }
+}
+
+// Step 2: one tree level of the four-wide nodes (bf_bvh.h: Node4), one thread per child slot.  A leaf child's box is the union
+// of its <= kMaxLeaf moved triangles, an internal child's the union of that child's unpadded records, written by the launch of
+// the level below.  The unpadded union goes to `ubox` (so padding never compounds up the tree), the padded one into the node.
+// The references and empty slots (inverted boxes) come from the pristine node: the node written may be a fresh copy-on-write
+// array, so every word of the slot's column is written.
+__global__ void bf_refit4_kernel(const uint32_t *__restrict__ level, uint32_t n, const float4 *__restrict__ nodes0, float4 *__restrict__ nodes,
+                                 float4 *__restrict__ ubox, const float4 *__restrict__ tris, float abs_pad) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= 4u * n) return;
+    const uint32_t node = level[g >> 2], k = g & 3u;
+    const float *src = reinterpret_cast<const float *>(nodes0 + 8u * node);
+    float *row = reinterpret_cast<float *>(nodes + 8u * node);
+    const int32_t ref = __float_as_int(src[24 + k]);
+    float lo[3] = {BF_INF, BF_INF, BF_INF}, hi[3] = {-BF_INF, -BF_INF, -BF_INF};
+    if (ref >= 0) {
+        refit_grow_node<4>(ubox, ref, lo, hi);
+    } else if (ref != kNoNode) {
+        const uint32_t enc = ~(uint32_t) ref;
+        refit_grow_tris(tris, enc >> 3, (enc & 7u) + 1u, lo, hi);
+    }
+    ubox[8u * node + 2u * k] = make_float4(lo[0], lo[1], lo[2], hi[0]);
+    ubox[8u * node + 2u * k + 1u] = make_float4(hi[1], hi[2], 0.f, 0.f);
+    if (ref != kNoNode) {
+        refit_pad(lo, hi, abs_pad);
+    } else {
+        for (int a = 0; a < 3; ++a) lo[a] = src[4 * a + k], hi[a] = src[4 * (3 + a) + k];
+    }
+    for (int a = 0; a < 3; ++a) {
+        row[4 * a + k] = lo[a];
+        row[4 * (3 + a) + k] = hi[a];
+    }
+    row[24 + k] = src[24 + k];
+    row[28 + k] = src[28 + k];
+}
+
+// the same for the sixteen-wide nodes (bf_bvh.h: Node16): leaves hold up to kWideLeaf contiguous triangles
+__global__ void bf_refit16_kernel(const uint32_t *__restrict__ level, uint32_t n, const float4 *__restrict__ wnodes0, float4 *__restrict__ wnodes,
+                                  float4 *__restrict__ ubox, const float4 *__restrict__ tris, float abs_pad) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= 16u * n) return;
+    const uint32_t node = level[g >> 4], k = g & 15u;
+    const float4 a = wnodes0[32u * node + 2u * k], b = wnodes0[32u * node + 2u * k + 1u];
+    float4 *c = wnodes + 32u * node + 2u * k;
+    const int32_t ref = __float_as_int(b.z);
+    float lo[3] = {BF_INF, BF_INF, BF_INF}, hi[3] = {-BF_INF, -BF_INF, -BF_INF};
+    if (ref >= 0) {
+        refit_grow_node<16>(ubox, ref, lo, hi);
+    } else if (ref != kNoNode) {
+        const uint32_t enc = ~(uint32_t) ref;
+        refit_grow_tris(tris, enc >> 4, (enc & 15u) + 1u, lo, hi);
+    }
+    ubox[32u * node + 2u * k] = make_float4(lo[0], lo[1], lo[2], hi[0]);
+    ubox[32u * node + 2u * k + 1u] = make_float4(hi[1], hi[2], 0.f, 0.f);
+    if (ref == kNoNode) {
+        c[0] = a;
+        c[1] = b;
+        return;
+    }
+    refit_pad(lo, hi, abs_pad);
+    c[0] = make_float4(lo[0], lo[1], lo[2], hi[0]);
+    c[1] = make_float4(hi[1], hi[2], b.z, b.w);
+}
+
+// Step 3 (BF_QUANT_BVH=1 scenes): the quantised copies from the refitted fp32 nodes
+__global__ void bf_requant_kernel(const float4 *__restrict__ nodes, float4 *__restrict__ qnodes, uint32_t n_nodes) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes) return;
+    const float4 *s = nodes + 8u * i;
+    quantise_node4_dev(s[0], s[1], s[2], s[3], s[4], s[5], s[6], qnodes + 4u * i);
+}
+BF_NS_END  // namespace bfd
+
+// The whole refit in stream order: the triangle transform, then one launch per level of each tree, deepest first
+// (nodes0 / wnodes0: the pristine trees the topology is read from; lvl4 / lvl16: node indices grouped by depth, level d = [off[d], off[d + 1]) on the device, offsets on the host), then the
+// re-quantisation.  The topology does not change, so the traversal stack bounds (stack_need, the spill columns) and the tail's
+// row count that bf_scene_create derived from it stay valid.
+extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
+                                       const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
+                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
+                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, hipStream_t stream) {
+    if (n_tris == 0) return hipSuccess;
+    hipLaunchKernelGGL(bfd::bf_rigid_tris_kernel, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, tris0, tris, nrm0, nrm, n_tris, xf);
+    for (uint32_t d = n_lvl4; d-- > 0;) {
+        const uint32_t n = lvl4_off[d + 1] - lvl4_off[d];
+        if (n) hipLaunchKernelGGL(bfd::bf_refit4_kernel, dim3((4u * n + 255u) / 256u), dim3(256), 0, stream, lvl4 + lvl4_off[d], n, nodes0, nodes, ubox4,
+                                  (const float4 *) tris, abs_pad);
+    }
+    for (uint32_t d = n_lvl16; wnodes && d-- > 0;) {
+        const uint32_t n = lvl16_off[d + 1] - lvl16_off[d];
+        if (n) hipLaunchKernelGGL(bfd::bf_refit16_kernel, dim3((16u * n + 255u) / 256u), dim3(256), 0, stream, lvl16 + lvl16_off[d], n, wnodes0, wnodes,
+                                  ubox16, (const float4 *) tris, abs_pad);
+    }
+    if (qnodes && n_nodes)
+        hipLaunchKernelGGL(bfd::bf_requant_kernel, dim3((n_nodes + 255u) / 256u), dim3(256), 0, stream, (const float4 *) nodes, qnodes, n_nodes);
     return hipGetLastError();
 }
 

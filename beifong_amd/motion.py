@@ -1,0 +1,101 @@
+"""Per-mesh rigid motion (bf_scene_transform_meshes): the numpy statement of what the library does to a
+mesh, and small helpers to build the 3x4 transforms it takes.
+
+`apply_rigid` is the contract written out: a scene created from its outputs renders every path bit-identically to the
+scene created from the original arrays and moved on the device.
+"""
+import math
+
+import numpy as np
+
+f32 = np.float32
+
+
+def rotation(axis, deg):
+    """float32[3, 3]: rotation by `deg` degrees about `axis` (right-handed; evaluated in float64, rounded once)."""
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    ang = math.radians(float(deg))
+    s, c = math.sin(ang), math.cos(ang)
+    x, y, z = a
+    return np.array([[c + x * x * (1 - c), x * y * (1 - c) - z * s, x * z * (1 - c) + y * s],
+                     [y * x * (1 - c) + z * s, c + y * y * (1 - c), y * z * (1 - c) - x * s],
+                     [z * x * (1 - c) - y * s, z * y * (1 - c) + x * s, c + z * z * (1 - c)]], dtype=np.float64).astype(f32)
+
+
+def rigid(r=None, t=(0.0, 0.0, 0.0)):
+    """float32[3, 4] = [R | t]; R defaults to the identity."""
+    m = np.zeros((3, 4), f32)
+    m[:, :3] = np.eye(3, dtype=f32) if r is None else np.asarray(r, dtype=f32).reshape(3, 3)
+    m[:, 3] = np.asarray(t, dtype=f32).reshape(3)
+    return m
+
+
+def about(r, pivot, t=(0.0, 0.0, 0.0)):
+    """float32[3, 4]: rotate by R about `pivot`, then translate by t (p' = R (p - pivot) + pivot + t, folded into [R | t'])."""
+    r = np.asarray(r, dtype=np.float64).reshape(3, 3)
+    pivot = np.asarray(pivot, dtype=np.float64).reshape(3)
+    return rigid(r.astype(f32), (pivot - r @ pivot + np.asarray(t, dtype=np.float64)).astype(f32))
+
+
+def is_identity(m):
+    m = np.asarray(m, dtype=f32).reshape(3, 4)
+    return bool(np.array_equal(m, rigid()))
+
+
+def apply_rigid(positions, normals, m):
+    """Positions (and vertex normals, or None) of a mesh moved by the 3x4 `m` as the device moves them:
+
+        p'_r = fl(fl(fl(fl(m_r0 x) + fl(m_r1 y)) + fl(m_r2 z)) + m_r3)       every product and sum rounded to float32
+        n'_r = fl(fl(fl(m_r0 nx) + fl(m_r1 ny)) + fl(m_r2 nz))              no translation, not renormalised
+
+    An identity `m` returns the arrays unchanged (bit for bit, signed zeros included).  Returns (positions', normals')."""
+    m = np.asarray(m, dtype=f32).reshape(3, 4)
+    p = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, dtype=f32).reshape(-1, 3)
+    if is_identity(m):
+        return p.copy(), None if n is None else n.copy()
+
+    def rot(v):
+        x, y, z = v[:, 0], v[:, 1], v[:, 2]
+        out = np.empty_like(v)
+        for r in range(3):
+            a = m[r, 0] * x          # float32 scalar * float32 array: rounded to float32
+            b = m[r, 1] * y
+            c = m[r, 2] * z
+            s = a + b
+            out[:, r] = s + c
+        return out
+
+    p2 = rot(p)
+    p2 += m[:, 3][None, :]
+    return p2, None if n is None else rot(n)
+
+
+def moved_description(sd, transforms):
+    """A new SceneDesc equal to `sd` with every mesh's positions and normals replaced by apply_rigid(..., transforms[k]):
+    the scene bf_scene_create would have to rebuild for the pose bf_scene_transform_meshes gives a handle of `sd`.
+    `transforms`: float[n_shapes, 3, 4].  Indices, texture coordinates, materials and endpoints are `sd`'s (kept alive)."""
+    import ctypes as C
+
+    from . import capi
+    from .scenedesc import SceneDesc
+    xf = np.asarray(transforms, dtype=f32).reshape(len(sd.shapes), 3, 4)
+    out = SceneDesc()
+    C.memmove(C.byref(out.physics), C.byref(sd.physics), C.sizeof(capi.bf_physics))
+    C.memmove(C.byref(out.sensor), C.byref(sd.sensor), C.sizeof(capi.bf_sensor))
+    out.materials, out.emitters = list(sd.materials), list(sd.emitters)
+    out._keep.append(sd)
+    for k, s in enumerate(sd.shapes):
+        s2 = capi.bf_shape()
+        C.memmove(C.byref(s2), C.byref(s), C.sizeof(capi.bf_shape))
+        if s.type == capi.BF_SHAPE_MESH and s.n_vertices and not is_identity(xf[k]):
+            p = np.ctypeslib.as_array(s.positions, shape=(s.n_vertices, 3))
+            n = np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None
+            p2, n2 = apply_rigid(p, n, xf[k])
+            out._keep += [p2, n2]
+            s2.positions = p2.ctypes.data_as(C.POINTER(C.c_float))
+            if n2 is not None:
+                s2.normals = n2.ctypes.data_as(C.POINTER(C.c_float))
+        out.shapes.append(s2)
+    return out.finalize()

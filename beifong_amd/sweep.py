@@ -183,6 +183,46 @@ def render_pulse_sweep(sd, launch, offsets, n_streams=2, lib=None, device=None, 
         sw.close()
 
 
+def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None):
+    """Coherent pulse sweep in which every mesh moves on its own: two targets at different speeds, a
+    turning car.
+
+    `sd`          scene description; its meshes as described are the pose the transforms start from;
+    `launch`      a BF_MODE_RECEIVE_IQ launch (any mode works); every pulse uses the same seed, as in render_pulse_sweep;
+    `transforms`  float[n_pulses, n_shapes, 3, 4]: the rigid transform of every shape at every pulse, absolute from the
+                  description (identity for rectangles and for meshes that do not move).
+
+    The scene is built once; the pulses rotate over `n_streams` handles (bf_scene_clone), one transform
+    (bf_scene_transform_meshes: a BVH refit on the device) and one render per pulse.  Returns the cube
+    float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), as render_pulse_sweep does."""
+    import torch
+    xf = np.asarray(transforms, dtype=np.float32)
+    if xf.ndim != 4 or xf.shape[2:] != (3, 4):
+        raise ValueError(f"transforms must be [n_pulses, n_shapes, 3, 4], got {xf.shape}")
+    n = xf.shape[0]
+    lib = lib or capi.load_library()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    n_streams = max(1, min(int(n_streams), n))
+    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
+    first = capi.Scene(sd, lib)
+    handles = [first] + [first.clone() for _ in range(n_streams - 1)]
+    try:
+        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
+        for s in streams:           # the cube was zero-filled on the current stream
+            s.wait_stream(torch.cuda.current_stream(dev))
+        for k in range(n):
+            j = k % n_streams
+            with torch.cuda.stream(streams[j]):
+                handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
+                handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
+        for s in streams:
+            s.synchronize()
+        return cube.cpu().numpy().reshape(n, -1, 3)
+    finally:
+        for h in reversed(handles):
+            h.close()
+
+
 def range_doppler(cube, window=True):
     """Slow-time FFT of a pulse-sweep cube: complex64[n_doppler, cells], zero Doppler at row 0 (numpy.fft order)."""
     z = cube[:, :, 0].astype(np.complex64) + 1j * cube[:, :, 1].astype(np.complex64)

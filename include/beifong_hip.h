@@ -441,6 +441,33 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
  * the reference rebuilds the scene per frame, animated_trans_rad.py:307-373).
  * Stream-ordered like bf_scene_update_endpoints. */
 bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void *stream);
+
+/* Rigidly move every mesh shape k to to_world[12*k .. 12*k+11] (3x4 row-major [R | t]), ABSOLUTE — relative to the
+ * vertices the scene was created with.  Entry k of a non-mesh shape must be the identity.  Each mesh moves on its own
+ * (two targets at different speeds, a turning car): the four- and sixteen-wide BVHs are re-fitted bottom-up on the
+ * device (same topology, boxes recomputed from the moved triangles), no rebuild.  DESIGN.md 6d.
+ *   Positions: p'.x = fl(fl(fl(fl(r00 x) + fl(r01 y)) + fl(r02 z)) + t0), the same for y and z — every product and sum
+ *     rounded in fp32, no FMA (beifong_amd/motion.py: apply_rigid is the same expression in numpy).  A shape whose
+ *     entry is exactly the identity keeps its vertices bit for bit.
+ *   Vertex normals: n' = R n0 in the same order, without t and not renormalised.  The triangle records' prim / shape
+ *     / tag words and the texture coordinates are untouched.
+ *   Equivalence: every path renders bit-identically to a bf_scene_create of the same description with the moved
+ *     position and normal arrays, in every mode (range, time, receive, IQ, BF_FLAG_FAST, batches, rolling sequences,
+ *     shards, the one-kernel variant), and bf_ray_intersect returns the same hits.
+ *   Validation: rigid only — |R^T R - I|_inf <= 1e-5 and det R > 0 — else BF_ERR_INVALID; also BF_ERR_INVALID for a
+ *     non-finite entry, a non-identity entry of a non-mesh shape and n_shapes != the scene's shape count.  A
+ *     non-identity entry for a mesh that carries an emitter / transmitter gives BF_ERR_UNSUPPORTED (its sampling tables
+ *     were built from the triangles as created; receivers and sensors sit on rectangles).  The error text names the
+ *     shape.  A call that fails leaves the scene exactly as it was.
+ *   With bf_scene_translate_meshes: both calls are absolute from the geometry as created and the latest call of either
+ *     kind defines the geometry (translate(o) after a transform puts every mesh at p0 + o, normals as created).
+ *     Batched mesh_offsets apply on top of the current geometry: fl(p' + off).
+ *   Stream-ordered like bf_scene_translate_meshes; an open rolling sequence on the handle is finished first.  A handle
+ *     that shares its geometry with clones copies on write (triangles, nodes, vertex normals); a clone of a moved handle
+ *     starts from the geometry that handle renders at that moment.  The first call on a handle reads the tree's
+ *     topology and every mesh's box back once.  The bound on ray origins the boxes are padded for is raised to cover
+ *     the moved meshes (never lowered).  bf_scene_info.bbox_* keeps reporting the box as created. */
+bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const float *to_world, void *stream);
 bf_status bf_scene_get_info(const bf_scene *scene, bf_scene_info *info);
 
 /* A second handle on the same scene for another stream: the big read-only arrays (BVH, triangles,
