@@ -141,7 +141,7 @@ EXPORTED_SYMBOLS = [
     "bf_abi_sizeof", "bf_abi_fingerprint", "bf_version", "bf_last_error", "bf_device_count", "bf_set_device", "bf_scene_create",
     "bf_scene_destroy", "bf_scene_update_endpoints", "bf_scene_translate_meshes", "bf_scene_transform_meshes", "bf_scene_get_info", "bf_scene_clone", "bf_launch_channels", "bf_render_device", "bf_render",
     "bf_scene_flush", "bf_scene_sync", "bf_shard_range", "bf_render_sharded_device", "bf_render_sharded", "bf_allreduce_device",
-    "bf_render_batch_device", "bf_render_batch",
+    "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
 ]
 
@@ -197,6 +197,8 @@ def load_library(path=None):
     lib.bf_allreduce_device.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp), C.c_uint64, C.POINTER(vp)]
     lib.bf_render_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.POINTER(bf_batch), vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_render_batch.argtypes = [vp, C.POINTER(bf_launch), C.POINTER(bf_batch), vp, vp, C.POINTER(bf_stats)]
+    lib.bf_render_motion_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(bf_stats)]
+    lib.bf_render_motion_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_trace_closest.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bf_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bf_ray_intersect.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
@@ -285,6 +287,23 @@ def rigid_table(transforms, n_shapes):
     if not np.issubdtype(xf.dtype, np.floating):
         raise TypeError(f"transforms must be floating point, got {xf.dtype}")
     return np.ascontiguousarray(xf, dtype=np.float32)
+
+
+def motion_tables(transforms, n_shapes, seeds=None):
+    """The float32[n_renders, n_shapes, 3, 4] table and uint64[n_renders] seeds (or None) bf_render_motion_batch reads, from an
+    [n_renders, n_shapes, 3, 4] array (every render's table checked by rigid_table).  Shapes only; the library checks rigidity."""
+    xf = np.asarray(transforms)
+    if xf.ndim != 4 or xf.shape[2:] != (3, 4):
+        raise ValueError(f"transforms must be [n_renders, n_shapes, 3, 4], got {xf.shape}")
+    if xf.shape[0] == 0:
+        raise ValueError("transforms: no renders")
+    xf = np.stack([rigid_table(xf[k], n_shapes) for k in range(xf.shape[0])])
+    sa = None
+    if seeds is not None:
+        sa = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+        if sa.size != xf.shape[0]:
+            raise ValueError(f"{sa.size} seeds for {xf.shape[0]} renders")
+    return np.ascontiguousarray(xf), sa
 
 
 class Scene:
@@ -414,6 +433,29 @@ class Scene:
                                                         C.c_void_p(records_ptr) if records_ptr else None,
                                                         C.c_void_p(stream) if stream else None,
                                                         C.byref(st) if st is not None else None), "bf_render_batch_device")
+        return st
+
+    def render_motion_batch(self, launch, transforms, seeds=None, records=False):
+        """bf_render_motion_batch: render k moves every mesh shape s to transforms[k, s] (absolute from the geometry as
+        created; the handle's own pose is untouched) -> float32[n_renders, channels] (+ records [n_renders, n_paths], stats).
+        `transforms`: [n_renders, n_shapes, 3, 4]; `seeds`: one per render, or None for launch.seed everywhere."""
+        xf, sa = motion_tables(transforms, self.info().n_shapes, seeds)
+        n_renders = xf.shape[0]
+        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
+        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
+        st = bf_stats()
+        check(self.lib, self.lib.bf_render_motion_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), xf.shape[1], _ptr(xf),
+                                                        _ptr(hist), _ptr(rec), C.byref(st)), "bf_render_motion_batch")
+        return hist, rec, st
+
+    def render_motion_batch_device(self, launch, transforms, hist_ptr, seeds=None, stream=0, records_ptr=None, want_stats=False):
+        """bf_render_motion_batch_device: accumulate render k of the motion batch into hist_ptr[k * channels ..] (device)."""
+        xf, sa = motion_tables(transforms, self.info().n_shapes, seeds)
+        st = bf_stats() if want_stats else None
+        check(self.lib, self.lib.bf_render_motion_batch_device(self.handle, C.byref(launch), xf.shape[0], _ptr(sa), xf.shape[1], _ptr(xf),
+                                                               C.c_void_p(hist_ptr), C.c_void_p(records_ptr) if records_ptr else None,
+                                                               C.c_void_p(stream) if stream else None,
+                                                               C.byref(st) if st is not None else None), "bf_render_motion_batch_device")
         return st
 
     def trace_closest(self, rays):

@@ -54,7 +54,8 @@ extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, ui
 extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
                                        const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
                                        const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
-                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, hipStream_t stream);
+                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
+                                       uint64_t vstride, uint32_t xf_stride, hipStream_t stream);
 extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y);
 extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const float *rays, int any_hit, float *out_t,
                                        uint32_t *out_prim, uint32_t *out_shape, float *out_uv, uint8_t *out_hit,
@@ -273,6 +274,11 @@ struct bf_scene {
         float *xf = nullptr;                     // device: 16 floats per shape (bfk_launch_rigid)
         std::vector<float> mesh_box;             // per shape: lo.xyz, hi.xyz of its pristine triangles (inverted: none)
     } refit;
+    // bf_render_motion_batch_device: the geometry versions of a batch's renders, one every `motion_rows` float4 rows.
+    // The handle's own (never shared with clones), grown on demand, freed with the handle; stream-ordered behind the renders
+    // of the previous call like every other write of the handle (order_after_last)
+    float4 *motion_arena = nullptr;
+    size_t motion_cap = 0;                      // float4 rows allocated
     // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
     std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
     std::vector<float *> array_dev;
@@ -450,6 +456,7 @@ bf_status bf_scene_destroy(bf_scene *s) {
     for (hipEvent_t e : s->wf_timing) (void) hipEventDestroy(e);
     if (s->counters) (void) hipFree(s->counters);
     if (s->tab_pool) (void) hipFree(s->tab_pool);
+    if (s->motion_arena) (void) hipFree(s->motion_arena);
     for (auto &st : s->stage) {
         if (st.ev) {
             (void) hipEventSynchronize(st.ev);
@@ -1344,16 +1351,14 @@ static bf_status refit_prepare(bf_scene *scene, hipStream_t stream) {
     return BF_OK;
 }
 
-bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const float *to_world, void *stream_) {
-    if (!scene || !to_world) return fail(BF_ERR_INVALID, "null argument");
-    if (n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: %u transforms for a scene of %u shapes", n_shapes, scene->info.n_shapes);
-    // everything is checked before anything changes: a failed call leaves the scene as it was
-    std::vector<uint8_t> moves(n_shapes, 0);
+// The checks of one transform table ([n_shapes][12], bf_scene_transform_meshes' rules): moves[k] = 1 if shape k's entry is not
+// exactly the identity.  `who` names the call (and the render, for a batch) in the error text, which also names the shape.
+static bf_status check_rigid_table(const bf_scene *scene, uint32_t n_shapes, const float *to_world, const char *who, uint8_t *moves) {
     for (uint32_t k = 0; k < n_shapes; ++k) {
         const float *m = to_world + 12 * (size_t) k;
+        moves[k] = 0;
         for (int j = 0; j < 12; ++j)
-            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: shape %u: non-finite entry", k);
+            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "%s shape %u: non-finite entry", who, k);
         for (int j = 0; j < 12; ++j) moves[k] |= m[j] != ((j % 5 == 0) ? 1.f : 0.f);
         if (!moves[k]) continue;
         double e = 0.0;
@@ -1366,13 +1371,43 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
         const double det = (double) m[0] * ((double) m[5] * m[10] - (double) m[6] * m[9]) - (double) m[1] * ((double) m[4] * m[10] - (double) m[6] * m[8]) +
                            (double) m[2] * ((double) m[4] * m[9] - (double) m[5] * m[8]);
         if (!(e <= 1e-5) || !(det > 0.0))
-            return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: shape %u: not a rigid motion (|R^T R - I| = %g, det R = %g)", k, e, det);
+            return fail(BF_ERR_INVALID, "%s shape %u: not a rigid motion (|R^T R - I| = %g, det R = %g)", who, k, e, det);
         const bfd::DShape &sh = scene->shapes_host[k];
         if (sh.type != BF_SHAPE_MESH)
-            return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: shape %u is not a mesh: its entry must be the identity", k);
+            return fail(BF_ERR_INVALID, "%s shape %u is not a mesh: its entry must be the identity", who, k);
         if (sh.emitter >= 0)
-            return fail(BF_ERR_UNSUPPORTED, "bf_scene_transform_meshes: mesh shape %u carries emitter %d (its sampling tables are built "
-                                            "from the triangles as created); create a new scene", k, sh.emitter);
+            return fail(BF_ERR_UNSUPPORTED, "%s mesh shape %u carries emitter %d (its sampling tables are built "
+                                            "from the triangles as created); create a new scene", who, k, sh.emitter);
+    }
+    return BF_OK;
+}
+
+// The bound on ray origins the boxes must be padded for once the meshes stand at to_world: `oscale` raised to cover every
+// moved mesh (its pristine box through |R| plus |t|, with a little margin)
+static float moved_origin_scale(const bf_scene *scene, uint32_t n_shapes, const float *to_world, const uint8_t *moves, float oscale) {
+    const bf_scene::Refit &rf = scene->refit;
+    for (uint32_t k = 0; k < n_shapes; ++k) {
+        const float *b = &rf.mesh_box[6 * (size_t) k];
+        if (!moves[k] || !(b[0] <= b[3])) continue;
+        const float *m = to_world + 12 * (size_t) k;
+        for (int r = 0; r < 3; ++r) {
+            double v = std::fabs((double) m[4 * r + 3]);
+            for (int c = 0; c < 3; ++c) v += std::fabs((double) m[4 * r + c]) * std::max(std::fabs((double) b[c]), std::fabs((double) b[3 + c]));
+            oscale = std::max(oscale, (float) (v * (1.0 + 1e-5)));
+        }
+    }
+    return oscale;
+}
+
+bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const float *to_world, void *stream_) {
+    if (!scene || !to_world) return fail(BF_ERR_INVALID, "null argument");
+    if (n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: %u transforms for a scene of %u shapes", n_shapes, scene->info.n_shapes);
+    // everything is checked before anything changes: a failed call leaves the scene as it was
+    std::vector<uint8_t> moves(n_shapes, 0);
+    {
+        bf_status cst = check_rigid_table(scene, n_shapes, to_world, "bf_scene_transform_meshes:", moves.data());
+        if (cst != BF_OK) return cst;
     }
     if (scene->d.n_tris == 0) return BF_OK;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -1399,17 +1434,7 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
     }
     bf_scene::Refit &rf = scene->refit;
     // ray origins now lie on the moved meshes: raise the bound the boxes are padded for (bf_bvh.h) to cover them — never lowered
-    float oscale = scene->origin_scale_built;
-    for (uint32_t k = 0; k < n_shapes; ++k) {
-        const float *b = &rf.mesh_box[6 * (size_t) k];
-        if (!moves[k] || !(b[0] <= b[3])) continue;
-        const float *m = to_world + 12 * (size_t) k;
-        for (int r = 0; r < 3; ++r) {
-            double v = std::fabs((double) m[4 * r + 3]);
-            for (int c = 0; c < 3; ++c) v += std::fabs((double) m[4 * r + c]) * std::max(std::fabs((double) b[c]), std::fabs((double) b[3 + c]));
-            oscale = std::max(oscale, (float) (v * (1.0 + 1e-5)));
-        }
-    }
+    const float oscale = moved_origin_scale(scene, n_shapes, to_world, moves.data(), scene->origin_scale_built);
     scene->origin_scale_built = oscale;
     {
         const size_t bytes = (size_t) n_shapes * 16 * sizeof(float);
@@ -1428,7 +1453,7 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
                              scene->d.n_tris, rf.xf, scene->nodes0, const_cast<float4 *>(scene->d.nodes), const_cast<float4 *>(scene->d.qnodes),
                              scene->d.n_nodes, rf.lvl4, rf.off4.data(), (uint32_t) rf.off4.size() - 1u, rf.ubox4, scene->wnodes0,
                              const_cast<float4 *>(scene->d.wnodes), rf.lvl16, rf.off16.data(), (uint32_t) rf.off16.size() - 1u, rf.ubox16,
-                             2e-7f * oscale, stream));
+                             2e-7f * oscale, 1u, 0u, 0u, stream));
     scene->normals_moved = scene->d.normals != nullptr;
     return mark_last(scene, stream);
 }
@@ -1716,6 +1741,7 @@ static bf_status wf_setup(const bf_scene *scene, const Kernels &k, const bfd::DL
     wf.offsets = lp.batch_offsets;
     wf.has_dop = (lp.doppler || lp.resample) ? 1u : 0u;
     wf.box_slack = lp.box_slack;
+    wf.geom_stride = lp.geom_stride;
     const size_t nb = wf.n_slots / 64;
     for (int b = 0; b < 2; ++b) {      // alive | trace | shadow of one parity are contiguous: one memset per bounce
         wf.m_alive[b] = scene->wf_masks + (4 * b + 0) * nb;
@@ -2298,10 +2324,10 @@ static bool lean_profile(const bf_scene *scene, const bf_launch *launch, bool re
     return et == BF_EMITTER_AREA && scene->sensor_host.type == BF_SENSOR_PERSPECTIVE && !multi_pixel && launch->mode != BF_MODE_TIME;
 }
 
-static bf_status render_common(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
-                               bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
-    if (!scene || !launch || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
-    BF_ENTER(scene);
+// A render or batch on a handle its caller holds (BF_ENTER).  geom_stride != 0: the batch's renders read per-render geometry
+// versions, geom_stride float4 rows apart from the arrays scene->d points at (bf_render_motion_batch_device; kGeom kernels).
+static bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
+                               bf_path_record *records_dev, void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0) {
     const uint32_t n_renders = batch ? batch->n_renders : 1u;
     if (batch) {
         if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
@@ -2414,6 +2440,7 @@ static bf_status render_common(const bf_scene *scene, const bf_launch *launch, c
         return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_DOPPLER with a resample_freq transmitter: both rewrite the path's wavelength (one slot of path state)");
     lp.mix = (receive_mode && (launch->flags & BF_FLAG_MIX_RESAMPLE)) ? 1u : 0u;
     lp.n_chan_all = lp.n_chan * n_renders;
+    lp.geom_stride = geom_stride;
     lp.lds_hist = (lp.n_chan_all <= (uint32_t) bfd::kMaxLdsHist && !(launch->flags & BF_FLAG_GLOBAL_ATOMICS)) ? 1u : 0u;
     lp.lds_floats = lp.lds_hist ? lp.n_chan_all : 0u;
     size_t lds = sizeof(int) * bfd::kStackDepth * bfd::kBlock + (lp.lds_hist ? sizeof(float) * lp.n_chan_all : 0);
@@ -2514,6 +2541,195 @@ static bf_status render_common(const bf_scene *scene, const bf_launch *launch, c
         }
     }
     return mark_last(scene, stream);
+}
+
+static bf_status render_common(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
+                               bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
+    if (!scene || !launch || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
+    BF_ENTER(scene);
+    return render_locked(scene, launch, batch, hist_dev, records_dev, stream_, stats_out);
+}
+
+// bf_render_motion_batch_device.  Render k reads geometry version k: the pristine rows moved by to_world[k] and
+// both trees re-fitted, by the kernels and the arithmetic of bf_scene_transform_meshes, for all renders of a chunk at once
+// (grid y = version).  Layout of one version, in float4 rows from its start: triangles (+ the kTriPad rows behind them),
+// vertex normals, four-wide nodes, sixteen-wide nodes, quantised nodes, then the refit's scratch (unpadded child bounds of
+// both trees).  The handle's own geometry, pose, padding bound and clones are not touched.
+namespace {
+struct MotionLayout {
+    size_t tris = 0, normals = 0, nodes = 0, wnodes = 0, qnodes = 0, ubox4 = 0, ubox16 = 0, rows = 0;
+};
+// while a chunk renders, the handle's kernel arguments point at version 0 of the arena; restored on every return path
+struct GeomSwap {
+    bf_scene *s;
+    bfd::DScene saved;
+    GeomSwap(bf_scene *sc, const bfd::DScene &view) : s(sc), saved(sc->d) { sc->d = view; }
+    ~GeomSwap() { s->d = saved; }
+};
+}  // namespace
+static MotionLayout motion_layout(const bf_scene *scene) {
+    const bfd::DScene &d = scene->d;
+    MotionLayout L;
+    size_t r = 0;
+    auto take = [&](size_t &at, size_t rows) {
+        at = r;
+        r += (rows + 7) & ~size_t(7);      // every array on a 128-byte line
+    };
+    take(L.tris, (size_t) d.n_tris * bfd::kTriStride + kTriPad);
+    take(L.normals, d.normals ? (size_t) d.n_tris * 3 : 0);
+    take(L.nodes, (size_t) d.n_nodes * 8);
+    take(L.wnodes, d.wnodes ? (size_t) d.n_wnodes * 32 : 0);
+    take(L.qnodes, d.qnodes ? (size_t) d.n_nodes * 4 : 0);
+    take(L.ubox4, (size_t) d.n_nodes * 8);
+    take(L.ubox16, d.wnodes ? (size_t) d.n_wnodes * 32 : 0);
+    L.rows = r;
+    return L;
+}
+
+// default arena budget of bf_render_motion_batch_device (BF_MOTION_BATCH_MB overrides it at call time)
+static constexpr size_t kMotionBatchMB = 2048;
+
+static void add_stats(bf_stats &a, const bf_stats &b) {
+    a.n_paths += b.n_paths;
+    a.n_rays_closest += b.n_rays_closest;
+    a.n_rays_shadow += b.n_rays_shadow;
+    a.n_nodes_visited += b.n_nodes_visited;
+    a.n_tris_tested += b.n_tris_tested;
+    a.n_invalid += b.n_invalid;
+    a.n_bounces += b.n_bounces;
+    a.kernel_ms += b.kernel_ms;
+    a.trace_ms += b.trace_ms;
+    a.shade_ms += b.shade_ms;
+    a.tail_ms += b.tail_ms;
+    a.n_launches_trace += b.n_launches_trace;
+    a.n_bounce_iters += b.n_bounce_iters;
+    a.n_rays_tail += b.n_rays_tail;
+    a.n_rays_traced += b.n_rays_traced;
+    a.n_nodes_lds += b.n_nodes_lds;
+    a.n_nodes_tail += b.n_nodes_tail;
+    a.n_wnodes_tail += b.n_wnodes_tail;
+    a.n_tris_tail += b.n_tris_tail;
+    a.n_bounces_tail += b.n_bounces_tail;
+    a.n_shade_loads += b.n_shade_loads;
+    a.n_shade_stores += b.n_shade_stores;
+    a.n_shade_shadow += b.n_shade_shadow;
+    a.n_shade_rays += b.n_shade_rays;
+    a.n_guard += b.n_guard;
+}
+
+bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_shapes,
+                                        const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
+    if (!scene || !launch || !to_world || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: n_renders is 0");
+    if (n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: %u transforms per render for a scene of %u shapes", n_shapes, scene->info.n_shapes);
+    if (launch->flags & BF_FLAG_ROLLING)
+        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: BF_FLAG_ROLLING: a motion batch is one launch sequence of its own");
+    if (launch->spp && launch->film_width && launch->film_height)
+        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: multi-pixel films are rendered one launch at a time");
+    // every render's table is checked before anything is enqueued: a failed call leaves the scene as it was
+    std::vector<uint8_t> moves((size_t) n_renders * n_shapes, 0);
+    for (uint32_t k = 0; k < n_renders; ++k) {
+        char who[96];
+        std::snprintf(who, sizeof(who), "bf_render_motion_batch_device: render %u,", k);
+        bf_status cst = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves.data() + (size_t) n_shapes * k);
+        if (cst != BF_OK) return cst;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    const uint64_t n_chan = bf_launch_channels(launch);
+    if (scene->d.n_tris == 0) {
+        // nothing to move: an ordinary batch
+        bf_batch b = {n_renders, seeds, nullptr};
+        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
+    }
+    {
+        bf_status ost = order_after_last(scene, stream);
+        if (ost == BF_OK) ost = close_sequence(scene, stream);
+        if (ost != BF_OK) return ost;
+    }
+    bf_status st = BF_OK;
+    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
+    // the pristine rows: the handle's own copies once it has moved, else the arrays it renders (a clone's snapshot included)
+    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
+    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
+    const float4 *normals0 = scene->normals0 ? scene->normals0 : scene->d.normals;
+    // one padding bound for every version of the call: the handle's, raised to cover all moved meshes of all renders
+    float oscale = scene->origin_scale_built;
+    for (uint32_t k = 0; k < n_renders; ++k)
+        oscale = moved_origin_scale(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, moves.data() + (size_t) n_shapes * k, oscale);
+    // chunks of renders whose versions fit the arena budget (at least one render per chunk)
+    const MotionLayout L = motion_layout(scene);
+    if (L.rows > UINT32_MAX)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_motion_batch_device: one geometry version of this scene is %zu float4 rows (at most 2^32 - 1)", L.rows);
+    size_t budget_mb = kMotionBatchMB;
+    if (const char *e = getenv("BF_MOTION_BATCH_MB")) {
+        char *end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && *end == '\0') budget_mb = (size_t) v;
+    }
+    const size_t version_bytes = L.rows * sizeof(float4);
+    const uint32_t per_chunk = (uint32_t) std::max<size_t>(1, std::min<size_t>({(size_t) n_renders, 65535, (budget_mb << 20) / version_bytes}));
+    const size_t need = (size_t) per_chunk * L.rows;
+    if (scene->motion_cap < need) {
+        // the old arena may still be read by the renders of an earlier call: wait for them before it goes
+        if (scene->motion_arena) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipFree(scene->motion_arena));
+            scene->motion_arena = nullptr;
+            scene->motion_cap = 0;
+        }
+        void *q = nullptr;
+        hipError_t he = hipMalloc(&q, need * sizeof(float4));
+        if (he != hipSuccess)
+            return fail(BF_ERR_NOMEM, "bf_render_motion_batch_device: hipMalloc(%zu bytes) for %u geometry versions: %s (BF_MOTION_BATCH_MB "
+                                      "caps the arena)", need * sizeof(float4), per_chunk, hipGetErrorString(he));
+        scene->motion_arena = (float4 *) q;
+        scene->motion_cap = need;
+    }
+    float4 *const a = scene->motion_arena;
+    bfd::DScene view = scene->d;
+    view.tris = a + L.tris;
+    view.normals = scene->d.normals ? a + L.normals : nullptr;
+    view.nodes = a + L.nodes;
+    view.wnodes = scene->d.wnodes ? a + L.wnodes : nullptr;
+    view.qnodes = scene->d.qnodes ? a + L.qnodes : nullptr;
+    const bf_scene::Refit &rf = scene->refit;
+    if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+    for (uint32_t k0 = 0; k0 < n_renders; k0 += per_chunk) {
+        const uint32_t kc = std::min(per_chunk, n_renders - k0);
+        {
+            // the chunk's transform tables (bfk_launch_rigid: 16 floats per shape, word 12 = the shape moves)
+            const size_t bytes = (size_t) kc * n_shapes * 16 * sizeof(float);
+            bf_scene::Stage *stg = nullptr;
+            if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
+            float *h = (float *) stg->host;
+            for (uint32_t v = 0; v < kc; ++v)
+                for (uint32_t k = 0; k < n_shapes; ++k) {
+                    const size_t r = (size_t) (k0 + v) * n_shapes + k;
+                    float *o = h + 16 * ((size_t) v * n_shapes + k);
+                    std::memcpy(o, to_world + 12 * r, 12 * sizeof(float));
+                    o[12] = moves[r] ? 1.f : 0.f;
+                    o[13] = o[14] = o[15] = 0.f;
+                }
+            if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
+            HIP_TRY(bfk_launch_rigid(tris0, a + L.tris, normals0, scene->d.normals ? a + L.normals : nullptr, scene->d.n_tris, (const float *) stg->dev,
+                                     nodes0, a + L.nodes, scene->d.qnodes ? a + L.qnodes : nullptr, scene->d.n_nodes, rf.lvl4, rf.off4.data(),
+                                     (uint32_t) rf.off4.size() - 1u, a + L.ubox4, wnodes0, scene->d.wnodes ? a + L.wnodes : nullptr, rf.lvl16,
+                                     rf.off16.data(), (uint32_t) rf.off16.size() - 1u, a + L.ubox16, 2e-7f * oscale, kc, L.rows, n_shapes * 16u,
+                                     stream));
+        }
+        bf_batch b = {kc, seeds ? seeds + k0 : nullptr, nullptr};
+        bf_stats cs;
+        {
+            GeomSwap swap(scene, view);
+            st = render_locked(scene, launch, &b, hist_dev + (size_t) k0 * n_chan, records_dev ? records_dev + (size_t) k0 * launch->n_paths : nullptr,
+                               stream_, stats_out ? &cs : nullptr, (uint32_t) L.rows);
+        }
+        if (st != BF_OK) return st;
+        if (stats_out) add_stats(*stats_out, cs);
+    }
+    return BF_OK;
 }
 
 bf_status bf_render_device(const bf_scene *scene, const bf_launch *launch, float *hist_dev, bf_path_record *records_dev,
@@ -2873,10 +3089,11 @@ bf_status bf_render_sharded(bf_scene *const *scenes, uint32_t n_devices, const b
     return st;
 }
 
-static bf_status render_host(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_out,
-                             bf_path_record *records_out, bf_stats *stats_out) {
+// host buffers around a device render: `run(d_hist, d_rec, stats)` renders n_renders renders of `launch` into them
+extern "C++" template <class Run>
+static bf_status render_host_with(const bf_scene *scene, const bf_launch *launch, uint64_t n_renders, float *hist_out,
+                                  bf_path_record *records_out, bf_stats *stats_out, Run &&run) {
     if (!scene || !launch || !hist_out) return fail(BF_ERR_INVALID, "null argument");
-    const uint64_t n_renders = batch ? batch->n_renders : 1u;
     if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
     const uint64_t nchan = (uint64_t) bf_launch_channels(launch) * n_renders, n_rec = launch->n_paths * n_renders;
     if (nchan == 0) return fail(BF_ERR_INVALID, "unknown mode");
@@ -2892,7 +3109,7 @@ static bf_status render_host(const bf_scene *scene, const bf_launch *launch, con
         return fail(BF_ERR_DEVICE, "bf_render: %s", hipGetErrorString(e));
     }
     bf_stats local;
-    bf_status st = render_common(scene, launch, batch, d_hist, d_rec, nullptr, stats_out ? stats_out : &local);
+    bf_status st = run(d_hist, d_rec, stats_out ? stats_out : &local);
     if (st == BF_OK) {
         e = hipMemcpy(hist_out, d_hist, nchan * sizeof(float), hipMemcpyDeviceToHost);
         if (e == hipSuccess && d_rec)
@@ -2902,6 +3119,20 @@ static bf_status render_host(const bf_scene *scene, const bf_launch *launch, con
     (void) hipFree(d_hist);
     if (d_rec) (void) hipFree(d_rec);
     return st;
+}
+
+static bf_status render_host(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_out,
+                             bf_path_record *records_out, bf_stats *stats_out) {
+    return render_host_with(scene, launch, batch ? batch->n_renders : 1u, hist_out, records_out, stats_out,
+                            [&](float *h, bf_path_record *r, bf_stats *st) { return render_common(scene, launch, batch, h, r, nullptr, st); });
+}
+
+bf_status bf_render_motion_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_shapes,
+                                 const float *to_world, float *hist_out, bf_path_record *records_out, bf_stats *stats_out) {
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_motion_batch: n_renders is 0");
+    return render_host_with(scene, launch, n_renders, hist_out, records_out, stats_out, [&](float *h, bf_path_record *r, bf_stats *st) {
+        return bf_render_motion_batch_device(scene, launch, n_renders, seeds, n_shapes, to_world, h, r, nullptr, st);
+    });
 }
 
 bf_status bf_render(const bf_scene *scene, const bf_launch *launch, float *hist_out, bf_path_record *records_out,

@@ -91,7 +91,10 @@ struct DEmitter {
 //             every path reads the rectangle / shape / emitter / material / sensor tables of ITS render through the
 //             sequence's descriptor ring (DRoll) — per-lane pointers, so those reads are vector loads — instead of the
 //             launch's kernel arguments
-constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16;
+//   kGeom     a batched launch whose renders each read their OWN geometry version (bf_render_motion_batch_device: DLaunch::geom_stride):
+//             triangles, vertex normals and the three node arrays of render k sit geom_stride float4 rows after render 0's
+//             (path_scene below) — per-lane pointers, so geometry reads of the root node become vector loads
+constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32;
 // rare<V>(c): a condition the lean profile guarantees to be false
 template <int V> __device__ __forceinline__ constexpr bool rare(bool c) { return (V & kLean) ? false : c; }
 
@@ -239,6 +242,9 @@ struct DLaunch {
     uint32_t count;                 // 1: somebody will read the statistics counters (BF_FLAG_STATS, or a render with stats_out): wf_shade and
                                     // the tail add theirs up — ten same-line atomics per WAVE, ~15 us each per launch at the end of a
                                     // persistent grid whose waves all finish together; 0: only the live count the host steers by
+    uint32_t geom_stride;           // batched launch with per-render geometry versions (kGeom kernels): float4 rows from one render's
+                                    // tris / normals / nodes / wnodes / qnodes to the next render's; 0: one geometry for all renders
+                                    // (in the struct's tail padding: the other kernels' argument layout stays as it was)
 };
 
 // device counters (uint64 each)

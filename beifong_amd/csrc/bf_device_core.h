@@ -131,6 +131,17 @@ BF_DEV Shift make_shift(const float4 *__restrict__ offsets, uint32_t render, flo
     return Shift{true, mk(q.x, q.y, q.z), slack};
 }
 BF_DEV V3 shifted(V3 p, const Shift &sh) { return sh.on ? p + sh.d : p; }
+
+// Geometry version of a render (kGeom launches, bf_render_motion_batch_device): every array of render k's moved geometry sits
+// `rows` = k * DLaunch::geom_stride float4 rows after render 0's, so the view is one multiply-add per render index.  Absent
+// arrays (no vertex normals, no sixteen-wide or quantised tree) stay absent.
+BF_DEV void geom_version(DScene &r, uint64_t rows) {
+    r.tris += rows;
+    r.nodes += rows;
+    if (r.normals) r.normals += rows;
+    if (r.wnodes) r.wnodes += rows;
+    if (r.qnodes) r.qnodes += rows;
+}
 BF_DEV void ray_inverse_shift(V3 o, V3 d, const Shift &sh, V3 &id, V3 &oid, V3 &ohi) {
     ray_inverse(sh.on ? o - sh.d : o, d, id, oid);
     ohi = oid;

@@ -563,6 +563,25 @@ extern "C" hipError_t BF_LAUNCHER(bfk_launch_render)(const bfd::DScene *sc, cons
     else                                                                                                                                 \
         hipLaunchKernelGGL((bfd::bf_render_kernel<S, R, P>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, *lp, g_hist,         \
                            records, counters, WF_, IT_)
+    if (lp->geom_stride) {
+        // per-render geometry versions (bf_render_motion_batch_device)
+#define BF_RENDER_GEOM(S, P)                                                                                                          \
+    if (lp->wide)                                                                                                                     \
+        hipLaunchKernelGGL((bfd::bf_render_kernel<S, false, P, BF_TAIL_WAVES, bfd::kWide | bfd::kGeom>), dim3(grid), dim3(bfd::kBlock), \
+                           lds_bytes, stream, *sc, *lp, g_hist, records, counters, none, 0u);                                         \
+    else                                                                                                                              \
+        hipLaunchKernelGGL((bfd::bf_render_kernel<S, false, P, BF_TAIL_WAVES, bfd::kGeom>), dim3(grid), dim3(bfd::kBlock), lds_bytes, \
+                           stream, *sc, *lp, g_hist, records, counters, none, 0u)
+        if (stats) {
+            if (spill) { BF_RENDER_GEOM(true, true); }
+            else { BF_RENDER_GEOM(true, false); }
+        } else {
+            if (spill) { BF_RENDER_GEOM(false, true); }
+            else { BF_RENDER_GEOM(false, false); }
+        }
+#undef BF_RENDER_GEOM
+        return hipGetLastError();
+    }
     if (stats) {
         if (spill) { BF_RENDER_LAUNCH(true, false, true, none, 0u); }
         else { BF_RENDER_LAUNCH(true, false, false, none, 0u); }
@@ -598,7 +617,16 @@ extern "C" hipError_t BF_LAUNCHER(bfk_launch_tail)(const bfd::DScene *sc, const 
     unsigned long long *counters = wf->counters;
     const bool two = tail_waves == 2;
 #define BF_TAIL_LAUNCH(S, P)                                                                                                           \
-    if (lp->multi)                                                                                                                     \
+    if (lp->geom_stride && lp->wide)                                                                                                   \
+        hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kWide | bfd::kGeom>), dim3(grid), dim3(bfd::kBlock), lds_bytes,   \
+                           stream, *sc, *lp, g_hist, records, counters, *wf, it);                                                      \
+    else if (lp->geom_stride && lp->lean)                                                                                              \
+        hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kLean | bfd::kGeom>), dim3(grid), dim3(bfd::kBlock), lds_bytes,   \
+                           stream, *sc, *lp, g_hist, records, counters, *wf, it);                                                      \
+    else if (lp->geom_stride)                                                                                                          \
+        hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kGeom>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc,   \
+                           *lp, g_hist, records, counters, *wf, it);                                                                   \
+    else if (lp->multi)                                                                                                                     \
         hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kMulti>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, \
                            *lp, g_hist, records, counters, *wf, it);                                                                  \
     else if (lp->wide)                                                                                                                      \
@@ -776,6 +804,9 @@ BF_NS_BEGIN
 //   p' = fl(fl(fl(fl(r0 x) + fl(r1 y)) + fl(r2 z)) + t)   per row, every product and sum rounded (no FMA: __fmul_rn / __fadd_rn)
 //   n' = R n                                              same order, without t, not renormalised
 // The .w words (prim, shape, tag) stay; a shape whose entry is the identity keeps its rows bit for bit.
+// Version dimension (bf_render_motion_batch_device: one geometry version per render): blockIdx.y = version v
+// writes the rows `vstride` float4 rows further per version and reads its transforms `xf_stride` floats further; the single
+// transform of bf_scene_transform_meshes is the launch with one version.
 BF_DEV float3 rigid_apply(const float *__restrict__ m, float x, float y, float z, bool with_t) {
     float r[3];
     for (int k = 0; k < 3; ++k) {
@@ -786,9 +817,12 @@ BF_DEV float3 rigid_apply(const float *__restrict__ m, float x, float y, float z
 }
 
 __global__ void bf_rigid_tris_kernel(const float4 *__restrict__ tris0, float4 *__restrict__ tris, const float4 *__restrict__ nrm0,
-                                     float4 *__restrict__ nrm, uint32_t n_tris, const float *__restrict__ xf) {
+                                     float4 *__restrict__ nrm, uint32_t n_tris, const float *__restrict__ xf, uint64_t vstride, uint32_t xf_stride) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_tris) return;
+    tris += vstride * blockIdx.y;
+    if (nrm) nrm += vstride * blockIdx.y;
+    xf += (size_t) xf_stride * blockIdx.y;
     const float4 *s = tris0 + kTriStride * i;
     float4 v[3] = {s[0], s[1], s[2]};
     const float *m = xf + 16u * __float_as_uint(v[1].w);
@@ -849,9 +883,12 @@ template <int W> BF_DEV void refit_grow_node(const float4 *__restrict__ ubox, in
 // The references and empty slots (inverted boxes) come from the pristine node: the node written may be a fresh copy-on-write
 // array, so every word of the slot's column is written.
 __global__ void bf_refit4_kernel(const uint32_t *__restrict__ level, uint32_t n, const float4 *__restrict__ nodes0, float4 *__restrict__ nodes,
-                                 float4 *__restrict__ ubox, const float4 *__restrict__ tris, float abs_pad) {
+                                 float4 *__restrict__ ubox, const float4 *__restrict__ tris, float abs_pad, uint64_t vstride) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= 4u * n) return;
+    nodes += vstride * blockIdx.y;          // (version dimension: as bf_rigid_tris_kernel)
+    ubox += vstride * blockIdx.y;
+    tris += vstride * blockIdx.y;
     const uint32_t node = level[g >> 2], k = g & 3u;
     const float *src = reinterpret_cast<const float *>(nodes0 + 8u * node);
     float *row = reinterpret_cast<float *>(nodes + 8u * node);
@@ -880,9 +917,12 @@ __global__ void bf_refit4_kernel(const uint32_t *__restrict__ level, uint32_t n,
 
 // the same for the sixteen-wide nodes (bf_bvh.h: Node16): leaves hold up to kWideLeaf contiguous triangles
 __global__ void bf_refit16_kernel(const uint32_t *__restrict__ level, uint32_t n, const float4 *__restrict__ wnodes0, float4 *__restrict__ wnodes,
-                                  float4 *__restrict__ ubox, const float4 *__restrict__ tris, float abs_pad) {
+                                  float4 *__restrict__ ubox, const float4 *__restrict__ tris, float abs_pad, uint64_t vstride) {
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= 16u * n) return;
+    wnodes += vstride * blockIdx.y;
+    ubox += vstride * blockIdx.y;
+    tris += vstride * blockIdx.y;
     const uint32_t node = level[g >> 4], k = g & 15u;
     const float4 a = wnodes0[32u * node + 2u * k], b = wnodes0[32u * node + 2u * k + 1u];
     float4 *c = wnodes + 32u * node + 2u * k;
@@ -907,9 +947,11 @@ __global__ void bf_refit16_kernel(const uint32_t *__restrict__ level, uint32_t n
 }
 
 // Step 3 (BF_QUANT_BVH=1 scenes): the quantised copies from the refitted fp32 nodes
-__global__ void bf_requant_kernel(const float4 *__restrict__ nodes, float4 *__restrict__ qnodes, uint32_t n_nodes) {
+__global__ void bf_requant_kernel(const float4 *__restrict__ nodes, float4 *__restrict__ qnodes, uint32_t n_nodes, uint64_t vstride) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
+    nodes += vstride * blockIdx.y;
+    qnodes += vstride * blockIdx.y;
     const float4 *s = nodes + 8u * i;
     quantise_node4_dev(s[0], s[1], s[2], s[3], s[4], s[5], s[6], qnodes + 4u * i);
 }
@@ -918,25 +960,31 @@ BF_NS_END  // namespace bfd
 // The whole refit in stream order: the triangle transform, then one launch per level of each tree, deepest first
 // (nodes0 / wnodes0: the pristine trees the topology is read from; lvl4 / lvl16: node indices grouped by depth, level d = [off[d], off[d + 1]) on the device, offsets on the host), then the
 // re-quantisation.  The topology does not change, so the traversal stack bounds (stack_need, the spill columns) and the tail's
-// row count that bf_scene_create derived from it stay valid.
+// row count that bf_scene_create derived from it stay valid.  n_versions > 1 (bf_render_motion_batch_device): every launch covers
+// all versions at once (grid y = version; the outputs and scratch of version v lie v * vstride float4 rows after version 0's, its
+// transforms v * xf_stride floats after the first table), so K versions cost the launches of one.
 extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
                                        const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
                                        const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
-                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, hipStream_t stream) {
-    if (n_tris == 0) return hipSuccess;
-    hipLaunchKernelGGL(bfd::bf_rigid_tris_kernel, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, tris0, tris, nrm0, nrm, n_tris, xf);
+                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
+                                       uint64_t vstride, uint32_t xf_stride, hipStream_t stream) {
+    if (n_tris == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bfd::bf_rigid_tris_kernel, dim3((n_tris + 255u) / 256u, n_versions), dim3(256), 0, stream, tris0, tris, nrm0, nrm, n_tris,
+                       xf, vstride, xf_stride);
     for (uint32_t d = n_lvl4; d-- > 0;) {
         const uint32_t n = lvl4_off[d + 1] - lvl4_off[d];
-        if (n) hipLaunchKernelGGL(bfd::bf_refit4_kernel, dim3((4u * n + 255u) / 256u), dim3(256), 0, stream, lvl4 + lvl4_off[d], n, nodes0, nodes, ubox4,
-                                  (const float4 *) tris, abs_pad);
+        if (n) hipLaunchKernelGGL(bfd::bf_refit4_kernel, dim3((4u * n + 255u) / 256u, n_versions), dim3(256), 0, stream, lvl4 + lvl4_off[d], n, nodes0,
+                                  nodes, ubox4, (const float4 *) tris, abs_pad, vstride);
     }
     for (uint32_t d = n_lvl16; wnodes && d-- > 0;) {
         const uint32_t n = lvl16_off[d + 1] - lvl16_off[d];
-        if (n) hipLaunchKernelGGL(bfd::bf_refit16_kernel, dim3((16u * n + 255u) / 256u), dim3(256), 0, stream, lvl16 + lvl16_off[d], n, wnodes0, wnodes,
-                                  ubox16, (const float4 *) tris, abs_pad);
+        if (n) hipLaunchKernelGGL(bfd::bf_refit16_kernel, dim3((16u * n + 255u) / 256u, n_versions), dim3(256), 0, stream, lvl16 + lvl16_off[d], n,
+                                  wnodes0, wnodes, ubox16, (const float4 *) tris, abs_pad, vstride);
     }
     if (qnodes && n_nodes)
-        hipLaunchKernelGGL(bfd::bf_requant_kernel, dim3((n_nodes + 255u) / 256u), dim3(256), 0, stream, (const float4 *) nodes, qnodes, n_nodes);
+        hipLaunchKernelGGL(bfd::bf_requant_kernel, dim3((n_nodes + 255u) / 256u, n_versions), dim3(256), 0, stream, (const float4 *) nodes, qnodes,
+                           n_nodes, vstride);
     return hipGetLastError();
 }
 

@@ -93,20 +93,24 @@ BF_DEV float shape_doppler(const DScene &sc, const SI &si, float lambda_nm) {
 }
 // The scene a path of render `render` sees.  Plain launches and sequences whose endpoints stand still: the launch's own
 // (wave-uniform: the tables are read through the scalar cache).  kMulti: the table pointers and physics of the path's render out
-// of the descriptor ring — a per-lane record, so everything read through them is a vector load.
+// of the descriptor ring — a per-lane record, so everything read through them is a vector load.  kGeom: the geometry arrays of
+// the path's render (DLaunch::geom_stride rows per render; the topology — root, stack bounds, spill columns — is shared).
 template <int V> BF_DEV DScene path_scene(const DScene &sc, const DLaunch &lp, uint32_t render) {
-    if (!(V & kMulti)) return sc;
+    if (!(V & (kMulti | kGeom))) return sc;
     DScene r = sc;
-    const BF_CAS DRoll &e = as_const(lp.roll)[render & (kRollRing - 1u)];
-    r.rects = e.rects;
-    r.shapes = e.shapes;
-    r.emitters = e.emitters;
-    r.materials = e.materials;
-    r.sensor = e.sensor;
-    r.c = e.c;
-    r.lambda_min = e.lambda_min;
-    r.lambda_max = e.lambda_max;
-    r.tab_on = 0u;                 // (the workgroup's LDS copies hold one version)
+    if (V & kMulti) {
+        const BF_CAS DRoll &e = as_const(lp.roll)[render & (kRollRing - 1u)];
+        r.rects = e.rects;
+        r.shapes = e.shapes;
+        r.emitters = e.emitters;
+        r.materials = e.materials;
+        r.sensor = e.sensor;
+        r.c = e.c;
+        r.lambda_min = e.lambda_min;
+        r.lambda_max = e.lambda_max;
+        r.tab_on = 0u;                 // (the workgroup's LDS copies hold one version)
+    }
+    if (V & kGeom) geom_version(r, (uint64_t) render * lp.geom_stride);
     return r;
 }
 // the mesh shift of the path's render (batched launches with moving meshes; off otherwise)

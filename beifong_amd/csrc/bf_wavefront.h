@@ -86,6 +86,8 @@ struct WF {
     uint32_t has_dop;        // BF_FLAG_DOPPLER: dop(i) = wavelength shift accumulated by the slot's path (nm)
     const float4 *offsets;   // batched launches with moving meshes: DLaunch::batch_offsets (wf_trace has no DLaunch)
     float box_slack;
+    uint32_t geom_stride;    // DLaunch::geom_stride (wf_trace has no DLaunch): render(i)'s geometry version is geom_stride float4 rows after
+                             // render 0's (in the padding before m_alive: the other kernels' argument layout stays as it was)
     // batch masks, double buffered by bounce parity: [2][n_slots / 64]
     unsigned long long *m_alive[2];
     unsigned long long *m_trace[2];

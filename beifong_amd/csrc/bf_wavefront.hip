@@ -796,7 +796,9 @@ constexpr int kLdsStack = 16;
 #endif
 constexpr uint32_t kTraceGuard = 1u << 24;      // wf_trace: inner-loop iterations between two refills (see the guard below)
 
-template <bool STATS, int W, bool SHIFT, bool QUANT>
+// GEOM: batched launch with a geometry version per render (WF::geom_stride): a ray walks the nodes and triangles of its own
+// render's version.  The LDS copy of the tree's top holds one version, so these rays read the top nodes from memory as well.
+template <bool STATS, int W, bool SHIFT, bool QUANT, bool GEOM = false>
 __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t it) {
     __shared__ int s_stack[kLdsStack * kBlock];
     __shared__ float4 s_top[kTopNodes * (QUANT ? kTopStrideQ : kTopStride)];
@@ -804,10 +806,10 @@ __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t
     const int lane = threadIdx.x & 63;
     const int nxt = (it & 1) ^ 1;
     uint32_t c_nodes = 0, c_tris = 0, c_top = 0;
-    const int n_top = (int) min(sc.n_nodes, kTopNodes);
-    if (QUANT)
+    const int n_top = GEOM ? 0 : (int) min(sc.n_nodes, kTopNodes);
+    if (QUANT && !GEOM)
         load_top_qnodes(sc.qnodes, (uint32_t) n_top, s_top, threadIdx.x, kBlock);
-    else
+    else if (!GEOM)
         load_top_nodes(sc.nodes, (uint32_t) n_top, s_top, threadIdx.x, kBlock);
     __syncthreads();
     const uint32_t n_waves = gridDim.x * (kBlock / 64), wave_id = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -821,6 +823,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t
     uint32_t job = 0;
     V3 o = mk(0, 0, 0), d = mk(0, 0, 1), id = mk(0, 0, 0), oid = mk(0, 0, 0), ohi = mk(0, 0, 0);
     Shift shf = no_shift();          // SHIFT: batched launch with moving meshes (the ray's render selects the offset)
+    uint64_t grows = 0;              // GEOM: float4 rows from render 0's geometry version to the ray's
     float mint = 0.f, maxt = 0.f;
     Hit best;
     best.t = BF_INF;
@@ -875,6 +878,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t
                         best.slot = __float_as_int(hq.w);
                         best.prim = wf.hit_prim(slot);
                     }
+                    if (GEOM) grows = (uint64_t) wf.render(slot) * wf.geom_stride;
                     if (SHIFT) {
                         shf = make_shift(wf.offsets, wf.render(slot), wf.box_slack);
                         ray_inverse_shift(o, d, shf, id, oid, ohi);
@@ -908,7 +912,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t
                 break;
             }
 #if BF_TRACE_IFIF
-            if (!QUANT) {
+            if (!QUANT && !GEOM) {
                 // "if-if": ONE step for every lane that holds a ray — a lane at an internal node fetches the node (LDS copy
                 // or memory), a lane at a leaf its (one or two) triangles, into the same registers; the wave waits ONCE for
                 // both kinds, then the node lanes decide and the leaf lanes intersect.  Every lane advances every iteration
@@ -982,17 +986,23 @@ __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t
                         c_top += node < n_top ? 1u : 0u;
                     }
                     if (QUANT)
-                        node = node4q_step_top(sc.qnodes, s_top, n_top, node, id, oid, SHIFT ? ohi : oid, mint,
+                        node = node4q_step_top(GEOM ? sc.qnodes + grows : sc.qnodes, s_top, n_top, node, id, oid, SHIFT ? ohi : oid, mint,
                                                any ? maxt : __builtin_fminf(maxt, best.t), st);
                     else
-                        node = node4_step_top(sc.nodes, s_top, n_top, node, id, oid, SHIFT ? ohi : oid, mint,
+                        node = node4_step_top(GEOM ? sc.nodes + grows : sc.nodes, s_top, n_top, node, id, oid, SHIFT ? ohi : oid, mint,
                                               any ? maxt : __builtin_fminf(maxt, best.t), st);
                 }
             }
             // (b) intersect the postponed leaves together
             if (has && node < 0 && node != kNoNode) {
-                found = SHIFT ? leaf_intersect<STATS>(sc, node, any, o, d, mint, maxt, best, c_tris, shf)
-                              : leaf_intersect<STATS>(sc, node, any, o, d, mint, maxt, best, c_tris);
+                if (GEOM) {
+                    DScene scg = sc;
+                    scg.tris += grows;
+                    found = leaf_intersect<STATS>(scg, node, any, o, d, mint, maxt, best, c_tris);
+                } else {
+                    found = SHIFT ? leaf_intersect<STATS>(sc, node, any, o, d, mint, maxt, best, c_tris, shf)
+                                  : leaf_intersect<STATS>(sc, node, any, o, d, mint, maxt, best, c_tris);
+                }
                 node = found ? kNoNode : st.pop_or_none();
             }
             }
@@ -1077,7 +1087,20 @@ extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd
 #define BF_SHADE_LAUNCH_MULTI(F)                         \
     if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kMulti);   \
     else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kMulti)
-    if (lp->multi) {
+#define BF_SHADE_LAUNCH_GEOM(F, V)                           \
+    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kGeom | (V));  \
+    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kGeom | (V))
+#define BF_SHADE_LAUNCH_GEOM_V(F)                                          \
+    if (lp->lean && !lp->wide) { BF_SHADE_LAUNCH_GEOM(F, bfd::kLean); }    \
+    else if (lp->wide) { BF_SHADE_LAUNCH_GEOM(F, bfd::kWide); }            \
+    else { BF_SHADE_LAUNCH_GEOM(F, 0); }
+    if (lp->geom_stride) {
+        // per-render geometry versions (bf_render_motion_batch_device): three waves per SIMD; never a rolling sequence, so
+        // neither its evicting (3) nor its wake (2) launch
+        if (first >= 2) return hipErrorInvalidValue;
+        if (first) { BF_SHADE_LAUNCH_GEOM_V(1); }
+        else { BF_SHADE_LAUNCH_GEOM_V(0); }
+    } else if (lp->multi) {
         // the sequence's endpoints moved between its renders: per-path tables (bf_device.h: kMulti; general kernels, box filter)
         if (first == 3) { BF_SHADE_LAUNCH_MULTI(3); }
         else if (first == 2) { BF_SHADE_LAUNCH_MULTI(2); }
@@ -1113,6 +1136,8 @@ extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd
 #undef BF_SHADE_LAUNCH_WIDE
 #undef BF_SHADE_LAUNCH_LEAN
 #undef BF_SHADE_LAUNCH_MULTI
+#undef BF_SHADE_LAUNCH_GEOM
+#undef BF_SHADE_LAUNCH_GEOM_V
 #undef BF_SHADE_LAUNCH_RX
     return hipGetLastError();
 }
@@ -1120,6 +1145,21 @@ extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd
 extern "C" hipError_t BF_LAUNCHER(bfk_wf_trace)(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
                                    hipStream_t stream, int waves) {
     const bool shift = wf->offsets != nullptr, quant = sc->qnodes != nullptr;
+    if (wf->geom_stride) {
+        // per-render geometry versions (bf_render_motion_batch_device; never with mesh offsets): no LDS copy of the top nodes
+#define BF_TRACE_GEOM(S, W)                                                                                                   \
+    if (quant) hipLaunchKernelGGL((bfd::wf_trace<S, W, false, true, true>), dim3(grid), dim3(bfd::kBlock), 0, stream, *sc, *wf, it); \
+    else hipLaunchKernelGGL((bfd::wf_trace<S, W, false, false, true>), dim3(grid), dim3(bfd::kBlock), 0, stream, *sc, *wf, it)
+        if (stats) {
+            if (waves >= 5) { BF_TRACE_GEOM(true, 5); }
+            else { BF_TRACE_GEOM(true, 4); }
+        } else {
+            if (waves >= 5) { BF_TRACE_GEOM(false, 5); }
+            else { BF_TRACE_GEOM(false, 4); }
+        }
+#undef BF_TRACE_GEOM
+        return hipGetLastError();
+    }
 #define BF_TRACE_LAUNCH2(S, W, SH, Q) \
     hipLaunchKernelGGL((bfd::wf_trace<S, W, SH, Q>), dim3(grid), dim3(bfd::kBlock), 0, stream, *sc, *wf, it)
 #define BF_TRACE_LAUNCH1(S, W)                      \

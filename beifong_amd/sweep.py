@@ -183,7 +183,7 @@ def render_pulse_sweep(sd, launch, offsets, n_streams=2, lib=None, device=None, 
         sw.close()
 
 
-def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None):
+def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None, per_pulse=False):
     """Coherent pulse sweep in which every mesh moves on its own: two targets at different speeds, a
     turning car.
 
@@ -192,9 +192,11 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
     `transforms`  float[n_pulses, n_shapes, 3, 4]: the rigid transform of every shape at every pulse, absolute from the
                   description (identity for rectangles and for meshes that do not move).
 
-    The scene is built once; the pulses rotate over `n_streams` handles (bf_scene_clone), one transform
-    (bf_scene_transform_meshes: a BVH refit on the device) and one render per pulse.  Returns the cube
-    float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), as render_pulse_sweep does."""
+    The scene is built once and the pulses are split into `n_streams` contiguous groups, one per handle (bf_scene_clone)
+    and stream.  Each group is ONE motion batch (bf_render_motion_batch_device: a geometry version per pulse, one launch
+    sequence and one tail for the group).  per_pulse=True is the reference path: the pulses rotate over the handles, one
+    transform (bf_scene_transform_meshes: a BVH refit on the device) and one render per pulse; per-path results are the
+    same.  Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), as render_pulse_sweep does."""
     import torch
     xf = np.asarray(transforms, dtype=np.float32)
     if xf.ndim != 4 or xf.shape[2:] != (3, 4):
@@ -210,11 +212,19 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
         cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
         for s in streams:           # the cube was zero-filled on the current stream
             s.wait_stream(torch.cuda.current_stream(dev))
-        for k in range(n):
-            j = k % n_streams
-            with torch.cuda.stream(streams[j]):
-                handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
-                handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
+        if per_pulse:
+            for k in range(n):
+                j = k % n_streams
+                with torch.cuda.stream(streams[j]):
+                    handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
+                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
+        else:
+            bounds = np.linspace(0, n, n_streams + 1).astype(int)
+            for j in range(n_streams):
+                lo, hi = int(bounds[j]), int(bounds[j + 1])
+                if hi > lo:
+                    with torch.cuda.stream(streams[j]):
+                        handles[j].render_motion_batch_device(launch, xf[lo:hi], cube[lo].data_ptr(), stream=streams[j].cuda_stream)
         for s in streams:
             s.synchronize()
         return cube.cpu().numpy().reshape(n, -1, 3)

@@ -581,6 +581,41 @@ bf_status bf_render_batch(const bf_scene *scene, const bf_launch *launch,
                           const bf_batch *batch, float *hist_out,
                           bf_path_record *records_out, bf_stats *stats_out);
 
+/* A batch whose renders each move the meshes by their OWN rigid transforms: render k of n_renders renders the scene with
+ * every mesh shape s at to_world[k][s] (3x4 row-major [R | t], bf_scene_transform_meshes' convention), seed seeds[k]
+ * (NULL: launch->seed for every render) into hist_dev + k * bf_launch_channels(launch) and, if records_dev is not NULL,
+ * records_dev + k * launch->n_paths.  One launch sequence for the whole batch, so the renders share one tail (the
+ * many-target case of sweep.render_motion_sweep).  DESIGN.md 6d.
+ *   Equivalence: render k is bit-identical, path for path (L, aux, valid, n_rays), to bf_scene_transform_meshes(to_world[k])
+ *     followed by a stand-alone render with seed seeds[k] on a handle of the same scene, in every mode (BF_FLAG_FAST, the
+ *     one-kernel variant BF_FLAG_MEGAKERNEL, BF_NO_WIDE_BVH, BF_QUANT_BVH included); histograms are the fp32 sums of those
+ *     paths.  Transforms are ABSOLUTE from the geometry as created, not from the pose the handle holds now.
+ *   How: one geometry version per render (moved triangles and vertex normals, re-fitted four- and sixteen-wide nodes,
+ *     quantised nodes for BF_QUANT_BVH scenes), built by bf_scene_transform_meshes' kernels with a version dimension, all
+ *     versions of a chunk padded for one origin bound that covers every moved mesh of the batch.  The versions live in an
+ *     arena of the handle's own (never shared with clones, grown on demand, freed with the handle), capped by the
+ *     environment variable BF_MOTION_BATCH_MB read at call time (default 2048 MiB); a batch that does not fit renders in
+ *     consecutive chunks of renders, each its own launch sequence, with the same per-path results (at least one render
+ *     per chunk, whatever the cap).
+ *   The handle does not change: its own pose (transform_meshes / translate_meshes), its clones and the bound on ray
+ *     origins its boxes are padded for stay as they were.
+ *   Validation, before anything is enqueued (a failed call leaves the scene as it was); the error text names the render
+ *     and the shape:
+ *     BF_ERR_INVALID      a non-rigid, non-finite, or non-identity entry for a non-mesh shape (bf_scene_transform_meshes'
+ *                         checks); n_shapes != the scene's shape count; n_renders == 0; a multi-pixel film;
+ *                         BF_FLAG_ROLLING
+ *     BF_ERR_UNSUPPORTED  a non-identity entry for a mesh that carries an emitter
+ *   Launch checks are bf_render_batch_device's.  An open rolling sequence on the handle is finished first.
+ *   Stream-ordered like bf_render_batch_device; stats_out (optional) adds up the chunks (n_paths = n_renders * n_paths). */
+bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders,
+                                        const uint64_t *seeds, uint32_t n_shapes, const float *to_world,
+                                        float *hist_dev, bf_path_record *records_dev, void *stream,
+                                        bf_stats *stats_out);
+/* The same with host buffers: hist_out [n_renders][channels], records_out [n_renders][n_paths] or NULL. */
+bf_status bf_render_motion_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders,
+                                 const uint64_t *seeds, uint32_t n_shapes, const float *to_world,
+                                 float *hist_out, bf_path_record *records_out, bf_stats *stats_out);
+
 /* Scene::ray_intersect / ray_test over a batch of HOST rays (tests, tools).
  * rays: [n][8] = o.xyz, mint, d.xyz, maxt.  Outputs may be NULL.
  * out_t = +inf on miss; out_prim = global primitive index (shape prefix sum,
