@@ -143,6 +143,9 @@ EXPORTED_SYMBOLS = [
     "bf_scene_flush", "bf_scene_sync", "bf_shard_range", "bf_render_sharded_device", "bf_render_sharded", "bf_allreduce_device",
     "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
+    "bf_bsdf_eval_pdf", "bf_bsdf_eval_pdf_device", "bf_bsdf_sample", "bf_bsdf_sample_device",
+    "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
+    "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
 ]
 
 _lib = None
@@ -203,6 +206,16 @@ def load_library(path=None):
     lib.bf_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bf_ray_intersect.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
     lib.bf_eval_elementary.argtypes = [C.c_int, C.c_uint64, vp, vp]
+    for f in ("bf_bsdf_eval_pdf", "bf_bsdf_sample"):
+        getattr(lib, f).argtypes = [vp, C.c_uint64, vp, vp, vp]
+        getattr(lib, f + "_device").argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
+    lib.bf_emitter_sample_direction.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp]
+    lib.bf_emitter_sample_direction_device.argtypes = [vp, C.c_uint32, C.c_uint64, vp, vp, vp]
+    lib.bf_sensor_sample_ray.argtypes = [vp, C.c_uint64, vp, vp]
+    lib.bf_sensor_sample_ray_device.argtypes = [vp, C.c_uint64, vp, vp, vp]
+    lib.bf_ray_intersect_device.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
+    lib.bf_trace_any_device.argtypes = [vp, C.c_uint64, vp, vp, vp]
+    lib.bf_eval_microfacet.argtypes = [C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint64, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -216,6 +229,51 @@ def check(lib, status, what):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _rows(a, width, dtype, what):
+    """A query's input rows: an array of `dtype` whose last axis is `width` (any leading shape, flattened to [n, width]);
+    a wrong dtype or shape is a ValueError before any library call."""
+    a = np.asarray(a)
+    if a.dtype != dtype:
+        raise ValueError(f"{what}: dtype {a.dtype}, expected {np.dtype(dtype)}")
+    if a.ndim == 0 or a.shape[-1] != width:
+        raise ValueError(f"{what}: shape {a.shape}, expected [..., {width}]")
+    return np.ascontiguousarray(a.reshape(-1, width))
+
+
+def _indices(a, n, what):
+    a = np.asarray(a)
+    if a.dtype != np.uint32:
+        raise ValueError(f"{what}: dtype {a.dtype}, expected uint32")
+    a = np.ascontiguousarray(a.reshape(-1))
+    if a.size != n:
+        raise ValueError(f"{what}: {a.size} indices for {n} queries")
+    return a
+
+
+def _stream(stream):
+    return C.c_void_p(stream) if stream else None
+
+
+def _dev(ptr, what):
+    if not isinstance(ptr, int) or isinstance(ptr, bool):
+        raise ValueError(f"{what}: a device pointer (int, e.g. tensor.data_ptr()) is expected, got {type(ptr).__name__}")
+    return C.c_void_p(ptr) if ptr else None
+
+
+MF_EVAL, MF_PDF, MF_SMITH_G1, MF_SAMPLE = range(4)
+
+
+def eval_microfacet(op, distribution, alpha_u, alpha_v, sample_visible, rows, lib=None):
+    """bf_eval_microfacet: MicrofacetDistribution on the device.  rows float32[..., 8] = wi.xyz, m.xyz, s.xy ->
+    float32[n, 4] (op MF_SAMPLE: m.xyz, pdf; otherwise the value in column 0)."""
+    rows = _rows(rows, 8, np.float32, "eval_microfacet rows")
+    lib = lib or load_library()
+    out = np.zeros((rows.shape[0], 4), np.float32)
+    check(lib, lib.bf_eval_microfacet(int(op), int(distribution), float(alpha_u), float(alpha_v), int(bool(sample_visible)),
+                                      rows.shape[0], _ptr(rows), _ptr(out)), "bf_eval_microfacet")
+    return out
 
 
 def make_launch(mode, n_paths, seed=0, path_offset=0, bins=0, bin_width=0.0, color_mode=BF_COLOR_RGB,
@@ -316,10 +374,21 @@ class Scene:
         check(self.lib, self.lib.bf_scene_create(C.byref(desc_holder.desc), C.byref(h)), "bf_scene_create")
         self.handle = h
 
+    @classmethod
+    def borrow(cls, handle, owner=None, lib=None):
+        """A Scene on a bf_scene handle another layer owns (the host layer's Scene): every query and render works on it,
+        close() leaves it alone; `owner` is kept alive."""
+        s = cls.__new__(cls)
+        s.lib = lib or load_library()
+        s.holder = owner
+        s.handle = C.c_void_p(handle)
+        s._borrowed = True
+        return s
+
     def close(self):
-        if self.handle:
+        if self.handle and not getattr(self, "_borrowed", False):
             self.lib.bf_scene_destroy(self.handle)
-            self.handle = None
+        self.handle = None
 
     def clone(self):
         """bf_scene_clone: another handle on the same geometry (own endpoint tables, path pool, counters) for another stream."""
@@ -488,3 +557,69 @@ class Scene:
         hit = np.empty(n, np.uint8)
         check(self.lib, self.lib.bf_trace_any(self.handle, n, _ptr(rays), _ptr(hit)), "bf_trace_any")
         return hit
+
+    # ---- plugin-level queries on the device (include/beifong_hip.h: bf_bsdf_eval_pdf ...) --------------------------------
+    # Host forms take and return numpy arrays; the _device forms take data_ptr() integers of device buffers the caller
+    # allocated (rows as in the header) and a stream, as render_device does, and return nothing (asynchronous).
+
+    def bsdf_eval_pdf(self, materials, wi_wo):
+        """BSDF::eval / pdf: materials uint32[n], wi_wo float32[n, 6] (local wi, wo) -> float32[n, 2] = eval, pdf."""
+        wi_wo = _rows(wi_wo, 6, np.float32, "bsdf_eval_pdf wi_wo")
+        mats = _indices(materials, wi_wo.shape[0], "bsdf_eval_pdf materials")
+        out = np.zeros((wi_wo.shape[0], 2), np.float32)
+        check(self.lib, self.lib.bf_bsdf_eval_pdf(self.handle, wi_wo.shape[0], _ptr(mats), _ptr(wi_wo), _ptr(out)), "bf_bsdf_eval_pdf")
+        return out
+
+    def bsdf_sample(self, materials, wi_u):
+        """BSDF::sample: materials uint32[n], wi_u float32[n, 6] = wi.xyz, sample1, sample2.xy -> float32[n, 5] = wo.xyz,
+        pdf, weight."""
+        wi_u = _rows(wi_u, 6, np.float32, "bsdf_sample wi_u")
+        mats = _indices(materials, wi_u.shape[0], "bsdf_sample materials")
+        out = np.zeros((wi_u.shape[0], 5), np.float32)
+        check(self.lib, self.lib.bf_bsdf_sample(self.handle, wi_u.shape[0], _ptr(mats), _ptr(wi_u), _ptr(out)), "bf_bsdf_sample")
+        return out
+
+    def emitter_sample_direction(self, emitter, rows):
+        """Emitter::sample_direction of emitter `emitter`: rows float32[n, 5] = ref_p.xyz, sample.xy -> float32[n, 8] = d.xyz,
+        dist, pdf, delta, spectrum, pdf_direction."""
+        rows = _rows(rows, 5, np.float32, "emitter_sample_direction rows")
+        out = np.zeros((rows.shape[0], 8), np.float32)
+        check(self.lib, self.lib.bf_emitter_sample_direction(self.handle, int(emitter), rows.shape[0], _ptr(rows), _ptr(out)),
+              "bf_emitter_sample_direction")
+        return out
+
+    def sensor_sample_ray(self, rows):
+        """Sensor::sample_ray: rows float32[n, 4] = film position.xy, aperture.xy -> float32[n, 9] = o.xyz, mint, d.xyz,
+        weight, maxt."""
+        rows = _rows(rows, 4, np.float32, "sensor_sample_ray rows")
+        out = np.zeros((rows.shape[0], 9), np.float32)
+        check(self.lib, self.lib.bf_sensor_sample_ray(self.handle, rows.shape[0], _ptr(rows), _ptr(out)), "bf_sensor_sample_ray")
+        return out
+
+    def bsdf_eval_pdf_device(self, n, materials_ptr, wi_wo_ptr, out_ptr, stream=0):
+        check(self.lib, self.lib.bf_bsdf_eval_pdf_device(self.handle, int(n), _dev(materials_ptr, "materials"), _dev(wi_wo_ptr, "wi_wo"),
+                                                         _dev(out_ptr, "out"), _stream(stream)), "bf_bsdf_eval_pdf_device")
+
+    def bsdf_sample_device(self, n, materials_ptr, wi_u_ptr, out_ptr, stream=0):
+        check(self.lib, self.lib.bf_bsdf_sample_device(self.handle, int(n), _dev(materials_ptr, "materials"), _dev(wi_u_ptr, "wi_u"),
+                                                       _dev(out_ptr, "out"), _stream(stream)), "bf_bsdf_sample_device")
+
+    def emitter_sample_direction_device(self, emitter, n, in_ptr, out_ptr, stream=0):
+        check(self.lib, self.lib.bf_emitter_sample_direction_device(self.handle, int(emitter), int(n), _dev(in_ptr, "in"),
+                                                                    _dev(out_ptr, "out"), _stream(stream)),
+              "bf_emitter_sample_direction_device")
+
+    def sensor_sample_ray_device(self, n, in_ptr, out_ptr, stream=0):
+        check(self.lib, self.lib.bf_sensor_sample_ray_device(self.handle, int(n), _dev(in_ptr, "in"), _dev(out_ptr, "out"),
+                                                             _stream(stream)), "bf_sensor_sample_ray_device")
+
+    def ray_intersect_device(self, n, rays_ptr, si_ptr, prim_ptr=None, shape_ptr=None, stream=0):
+        """bf_ray_intersect_device: rays float32[n, 8] -> si float32[n, BF_SI_FLOATS] (+ prim / shape uint32[n]) on the device."""
+        check(self.lib, self.lib.bf_ray_intersect_device(self.handle, int(n), _dev(rays_ptr, "rays"), _dev(si_ptr, "si"),
+                                                         _dev(prim_ptr or 0, "prim"), _dev(shape_ptr or 0, "shape"), _stream(stream)),
+              "bf_ray_intersect_device")
+
+    def trace_any_device(self, n, rays_ptr, hit_ptr, stream=0):
+        """bf_trace_any_device: rays float32[n, 8] -> hit uint8[n] on the device."""
+        check(self.lib, self.lib.bf_trace_any_device(self.handle, int(n), _dev(rays_ptr, "rays"), _dev(hit_ptr, "hit"), _stream(stream)),
+              "bf_trace_any_device")

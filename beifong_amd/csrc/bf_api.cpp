@@ -60,6 +60,12 @@ extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, 
 extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const float *rays, int any_hit, float *out_t,
                                        uint32_t *out_prim, uint32_t *out_shape, float *out_uv, uint8_t *out_hit,
                                        float *out_si, hipStream_t stream);
+// plugin-level queries (bf_kernels.hip: bf_query_kernel, bf_microfacet_kernel); op 0 BSDF eval + pdf, 1 BSDF sample, 2 emitter
+// sample_direction, 3 sensor sample_ray
+extern "C" hipError_t bfk_launch_query(int op, const bfd::DScene *sc, uint64_t n, const uint32_t *materials, uint32_t emitter,
+                                       const float *in, float *out, hipStream_t stream);
+extern "C" hipError_t bfk_launch_microfacet(int op, uint32_t type, float alpha_u, float alpha_v, uint32_t sample_visible, uint64_t n,
+                                            const float *in, float *out, hipStream_t stream);
 
 extern "C" hipError_t bfk_wf_shade(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
                                    float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
@@ -3217,6 +3223,146 @@ bf_status bf_eval_elementary(int op, uint64_t n, const float *x, float *y) {
     (void) hipFree(d_x);
     (void) hipFree(d_y);
     if (e != hipSuccess) return fail(BF_ERR_DEVICE, "bf_eval_elementary: %s", hipGetErrorString(e));
+    return BF_OK;
+}
+
+// ---- device-side queries (include/beifong_hip.h: "Plugin-level queries") -------------------------------------------------
+// Both forms of every query go through BF_ENTER and are ordered like a render: they wait for the handle's last work on another
+// stream (order_after_last) and record themselves as its last work (mark_last), so a later endpoint update or mesh transform
+// cannot overwrite a table a query still reads.  Queries only read the scene, so an open rolling sequence stays open.
+enum { kQueryEvalPdf = 0, kQuerySample = 1, kQueryEmitter = 2, kQuerySensor = 3 };
+static constexpr uint64_t kQueryMax = 0xffffffffull;      // queries per call: the launch grid is (n + 255) / 256 blocks
+
+static bf_status query_device(const bf_scene *scene, int op, uint64_t n, const uint32_t *materials, uint32_t emitter,
+                              const float *in, float *out, void *stream_, const char *who) {
+    if (!scene) return fail(BF_ERR_INVALID, "%s: null scene", who);
+    const bool per_material = op == kQueryEvalPdf || op == kQuerySample;
+    if (n && (!in || !out || (per_material && !materials))) return fail(BF_ERR_INVALID, "%s: null pointer with n = %llu", who, (unsigned long long) n);
+    if (n > kQueryMax) return fail(BF_ERR_INVALID, "%s: %llu queries (at most %llu per call)", who, (unsigned long long) n, (unsigned long long) kQueryMax);
+    BF_ENTER(scene);
+    if (op == kQueryEmitter) {
+        if (emitter >= scene->emitter_types.size())
+            return fail(BF_ERR_INVALID, "%s: emitter %u out of range (%zu emitters)", who, emitter, scene->emitter_types.size());
+        const uint32_t t = scene->emitter_types[emitter];
+        if (t != BF_EMITTER_SPOT && t != BF_EMITTER_AREA && t != BF_EMITTER_POINT)
+            return fail(BF_ERR_UNSUPPORTED, "%s: emitter %u is a transmitter (type %u): no probe", who, emitter, t);
+    }
+    if (op == kQuerySensor) {
+        const uint32_t t = scene->sensor_host.type;
+        if (t != BF_SENSOR_FLUXMETER && t != BF_SENSOR_PERSPECTIVE && t != BF_SENSOR_IRRADIANCEMETER && t != BF_SENSOR_RADIANCEMETER)
+            return fail(BF_ERR_UNSUPPORTED, "%s: the scene's endpoint is a receiver (type %u): no probe", who, t);
+    }
+    if (n == 0) return BF_OK;
+    hipStream_t stream = (hipStream_t) stream_;
+    bf_status st = order_after_last(scene, stream);
+    if (st != BF_OK) return st;
+    HIP_TRY(bfk_launch_query(op, &scene->d, n, materials, emitter, in, out, stream));
+    return mark_last(scene, stream);
+}
+
+// host form: stage the rows, run the device form on the null stream, copy back and wait for that stream
+static bf_status query_host(const bf_scene *scene, int op, uint64_t n, const uint32_t *materials, uint32_t emitter, const float *in,
+                            uint32_t in_floats, float *out, uint32_t out_floats, const char *who) {
+    const bool per_material = op == kQueryEvalPdf || op == kQuerySample;
+    // the refusals of the device form first (it launches nothing for n = 0), then the material indices, which only the host sees
+    bf_status st = query_device(scene, op, 0, materials, emitter, in, out, nullptr, who);
+    if (st != BF_OK) return st;
+    if (n && (!in || !out || (per_material && !materials))) return fail(BF_ERR_INVALID, "%s: null pointer with n = %llu", who, (unsigned long long) n);
+    if (n > kQueryMax) return fail(BF_ERR_INVALID, "%s: %llu queries (at most %llu per call)", who, (unsigned long long) n, (unsigned long long) kQueryMax);
+    if (per_material)
+        for (uint64_t i = 0; i < n; ++i)
+            if (materials[i] >= scene->n_materials)
+                return fail(BF_ERR_INVALID, "%s: query %llu: material %u out of range (%u materials)", who, (unsigned long long) i, materials[i],
+                            scene->n_materials);
+    if (n == 0) return BF_OK;
+    DeviceGuard on_device(scene->device);
+    float *d_in = nullptr, *d_out = nullptr;
+    uint32_t *d_mat = nullptr;
+    hipError_t e = hipMalloc((void **) &d_in, n * in_floats * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **) &d_out, n * out_floats * sizeof(float));
+    if (e == hipSuccess && per_material) e = hipMalloc((void **) &d_mat, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, n * in_floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && per_material) e = hipMemcpy(d_mat, materials, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        st = query_device(scene, op, n, d_mat, emitter, d_in, d_out, nullptr, who);
+        if (st == BF_OK) e = hipMemcpyAsync(out, d_out, n * out_floats * sizeof(float), hipMemcpyDeviceToHost, nullptr);
+        if (st == BF_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    }
+    (void) hipFree(d_in);
+    (void) hipFree(d_out);
+    if (d_mat) (void) hipFree(d_mat);
+    if (st != BF_OK) return st;
+    if (e != hipSuccess) return fail(BF_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+    return BF_OK;
+}
+
+bf_status bf_bsdf_eval_pdf_device(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_wo, float *out,
+                                  void *stream) {
+    return query_device(scene, kQueryEvalPdf, n, materials, 0, wi_wo, out, stream, __func__);
+}
+bf_status bf_bsdf_eval_pdf(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_wo, float *out) {
+    return query_host(scene, kQueryEvalPdf, n, materials, 0, wi_wo, 6, out, 2, __func__);
+}
+bf_status bf_bsdf_sample_device(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_u, float *out, void *stream) {
+    return query_device(scene, kQuerySample, n, materials, 0, wi_u, out, stream, __func__);
+}
+bf_status bf_bsdf_sample(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_u, float *out) {
+    return query_host(scene, kQuerySample, n, materials, 0, wi_u, 6, out, 5, __func__);
+}
+bf_status bf_emitter_sample_direction_device(const bf_scene *scene, uint32_t emitter, uint64_t n, const float *in, float *out,
+                                             void *stream) {
+    return query_device(scene, kQueryEmitter, n, nullptr, emitter, in, out, stream, __func__);
+}
+bf_status bf_emitter_sample_direction(const bf_scene *scene, uint32_t emitter, uint64_t n, const float *in, float *out) {
+    return query_host(scene, kQueryEmitter, n, nullptr, emitter, in, 5, out, 8, __func__);
+}
+bf_status bf_sensor_sample_ray_device(const bf_scene *scene, uint64_t n, const float *in, float *out, void *stream) {
+    return query_device(scene, kQuerySensor, n, nullptr, 0, in, out, stream, __func__);
+}
+bf_status bf_sensor_sample_ray(const bf_scene *scene, uint64_t n, const float *in, float *out) {
+    return query_host(scene, kQuerySensor, n, nullptr, 0, in, 4, out, 9, __func__);
+}
+
+// the ray queries on device rays: bf_trace_any / bf_ray_intersect's kernel as it is, on the caller's stream
+static bf_status trace_device(const bf_scene *scene, uint64_t n, const float *rays, int any_hit, uint8_t *out_hit, float *out_si,
+                              uint32_t *out_prim, uint32_t *out_shape, void *stream_, const char *who) {
+    if (!scene) return fail(BF_ERR_INVALID, "%s: null scene", who);
+    if (n && (!rays || (any_hit ? !out_hit : !out_si))) return fail(BF_ERR_INVALID, "%s: null pointer with n = %llu", who, (unsigned long long) n);
+    BF_ENTER(scene);
+    if (n == 0) return BF_OK;
+    hipStream_t stream = (hipStream_t) stream_;
+    bf_status st = order_after_last(scene, stream);
+    if (st != BF_OK) return st;
+    HIP_TRY(bfk_launch_trace(&scene->d, n, rays, any_hit, nullptr, out_prim, out_shape, nullptr, out_hit, out_si, stream));
+    return mark_last(scene, stream);
+}
+bf_status bf_ray_intersect_device(const bf_scene *scene, uint64_t n, const float *rays, float *out_si, uint32_t *out_prim,
+                                  uint32_t *out_shape, void *stream) {
+    return trace_device(scene, n, rays, 0, nullptr, out_si, out_prim, out_shape, stream, __func__);
+}
+bf_status bf_trace_any_device(const bf_scene *scene, uint64_t n, const float *rays, uint8_t *out_hit, void *stream) {
+    return trace_device(scene, n, rays, 1, out_hit, nullptr, nullptr, nullptr, stream, __func__);
+}
+
+bf_status bf_eval_microfacet(int op, uint32_t distribution, float alpha_u, float alpha_v, uint32_t sample_visible, uint64_t n,
+                             const float *in, float *out) {
+    if (op < 0 || op > 3) return fail(BF_ERR_INVALID, "bf_eval_microfacet: op %d (0 eval, 1 pdf, 2 smith_g1, 3 sample)", op);
+    if (distribution != BF_MF_BECKMANN && distribution != BF_MF_GGX)
+        return fail(BF_ERR_INVALID, "bf_eval_microfacet: distribution %u (BF_MF_BECKMANN or BF_MF_GGX)", distribution);
+    if (n && (!in || !out)) return fail(BF_ERR_INVALID, "bf_eval_microfacet: null pointer with n = %llu", (unsigned long long) n);
+    if (n > kQueryMax) return fail(BF_ERR_INVALID, "bf_eval_microfacet: %llu queries (at most %llu per call)", (unsigned long long) n,
+                                   (unsigned long long) kQueryMax);
+    if (n == 0) return BF_OK;
+    float *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc((void **) &d_in, n * 8 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **) &d_out, n * 4 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(d_in, in, n * 8 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = bfk_launch_microfacet(op, distribution, alpha_u, alpha_v, sample_visible, n, d_in, d_out, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * 4 * sizeof(float), hipMemcpyDeviceToHost, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    (void) hipFree(d_in);
+    (void) hipFree(d_out);
+    if (e != hipSuccess) return fail(BF_ERR_DEVICE, "bf_eval_microfacet: %s", hipGetErrorString(e));
     return BF_OK;
 }
 

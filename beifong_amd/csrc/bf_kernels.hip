@@ -1045,4 +1045,145 @@ extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const 
                            out_prim, out_shape, out_uv, out_hit, out_si);
     return hipGetLastError();
 }
+
+// Plugin-level queries (bf_bsdf_eval_pdf, bf_bsdf_sample, bf_emitter_sample_direction, bf_sensor_sample_ray): one lane per
+// query through the device functions the renders call, general profile (V = 0), so every material, emitter and sensor type
+// is reachable.  Inputs and outputs are the row layouts of include/beifong_hip.h.
+BF_NS_BEGIN
+enum { kQueryEvalPdf = 0, kQuerySample = 1, kQueryEmitter = 2, kQuerySensor = 3 };
+template <int OP>
+__global__ __launch_bounds__(256) void bf_query_kernel(DScene sc, uint64_t n, const uint32_t *__restrict__ materials,
+                                                       uint32_t emitter, const float *__restrict__ in, float *__restrict__ out) {
+    const uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    if (OP == kQueryEvalPdf || OP == kQuerySample) {
+        const float *q = in + 6 * i;
+        const V3 wi = mk(q[0], q[1], q[2]);
+        const uint32_t k = materials[i];
+        float *o = out + (OP == kQueryEvalPdf ? 2 : 5) * i;
+        if (k >= sc.n_materials) {      // the _device forms cannot refuse an index they only see here: NaN rows
+            for (int c = 0; c < (OP == kQueryEvalPdf ? 2 : 5); ++c) o[c] = __builtin_nanf("");
+            return;
+        }
+        bf_material mat = load_material(sc, k);
+        // TwoSidedBRDF with two nested BSDFs (twosided.cpp:108-178), as the shading vertex selects it
+        if (mat.back_material != 0u && wi.z < 0.f) mat = load_material(sc, mat.back_material - 1u);
+        if (OP == kQueryEvalPdf) {
+            float ev, pdf;
+            bsdf_eval_pdf(mat, wi, mk(q[3], q[4], q[5]), ev, pdf);
+            o[0] = ev;
+            o[1] = pdf;
+        } else {
+            BSDFSample bs;
+            const float w = bsdf_sample(mat, wi, q[4], q[5], bs);      // q[3]: sample1, unused by a single-lobe BSDF
+            o[0] = bs.wo.x;
+            o[1] = bs.wo.y;
+            o[2] = bs.wo.z;
+            o[3] = bs.pdf;
+            o[4] = w;
+        }
+    } else if (OP == kQueryEmitter) {
+        const float *q = in + 5 * i;
+        const V3 ref_p = mk(q[0], q[1], q[2]);
+        CEmitter &e = c_emitters(sc)[emitter];
+        DirSample ds;
+        const float spec = emitter_sample_direction<0>(sc, e, ref_p, q[3], q[4], ds);
+        float pdf_dir = 0.f;
+        if (e.type != BF_EMITTER_SPOT && e.type != BF_EMITTER_POINT) {
+            CRect &rc = c_rects(sc)[e.rect];
+            const V3 p = xf_point(rc.to_world, mk(q[3] * 2.f - 1.f, q[4] * 2.f - 1.f, 0.f));
+            pdf_dir = emitter_pdf_direction<0>(sc, e, ref_p, p, mk(rc.n[0], rc.n[1], rc.n[2]));
+        }
+        float *o = out + 8 * i;
+        o[0] = ds.d.x;
+        o[1] = ds.d.y;
+        o[2] = ds.d.z;
+        o[3] = ds.dist;
+        o[4] = ds.pdf;
+        o[5] = ds.delta ? 1.f : 0.f;
+        o[6] = spec;
+        o[7] = pdf_dir;
+    } else {
+        const float *q = in + 4 * i;
+        V3 ro, rd;
+        float mint, maxt;
+        float w = sensor_sample_ray<0>(sc, q[0], q[1], q[2], q[3], ro, rd, mint, maxt);
+        // irradiancemeter.cpp:82: the path's sensor weight divides by the surface area (bf_path_logic.h, the same expression)
+        if (c_sensor(sc).type == BF_SENSOR_IRRADIANCEMETER) w = 1.f * kPi / c_rects(sc)[c_sensor(sc).rect].area;
+        float *o = out + 9 * i;
+        o[0] = ro.x;
+        o[1] = ro.y;
+        o[2] = ro.z;
+        o[3] = mint;
+        o[4] = rd.x;
+        o[5] = rd.y;
+        o[6] = rd.z;
+        o[7] = w;
+        o[8] = maxt;
+    }
+}
+
+// MicrofacetDistribution unit access (bf_eval_microfacet; op numbering of the oracle's bfo_microfacet): in [n][8] = wi.xyz,
+// m.xyz, s.xy; out [n][4]: op 0 eval(m), 1 pdf(wi, m), 2 smith_g1(v = m, m = wi), 3 sample(wi, s) -> m.xyz, pdf
+__global__ __launch_bounds__(256) void bf_microfacet_kernel(int op, uint32_t type, float alpha_u, float alpha_v, uint32_t sample_visible,
+                                                            uint64_t n, const float *__restrict__ in, float *__restrict__ out) {
+    const uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    bf_material mat = {};
+    mat.distribution = type;
+    mat.alpha_u = alpha_u;
+    mat.alpha_v = alpha_v;
+    mat.sample_visible = sample_visible;
+    const Microfacet d = mf_make(mat);
+    const float *q = in + 8 * i;
+    const V3 wi = mk(q[0], q[1], q[2]), m = mk(q[3], q[4], q[5]);
+    float r[4] = {0.f, 0.f, 0.f, 0.f};
+    if (op == 0) {
+        r[0] = mf_eval(d, m);
+    } else if (op == 1) {
+        r[0] = mf_pdf(d, wi, m);
+    } else if (op == 2) {
+        r[0] = mf_smith_g1(d, m, wi);
+    } else {
+        V3 ms;
+        mf_sample(d, wi, q[6], q[7], ms, r[3]);
+        r[0] = ms.x;
+        r[1] = ms.y;
+        r[2] = ms.z;
+    }
+    float *o = out + 4 * i;
+    for (int c = 0; c < 4; ++c) o[c] = r[c];
+}
+BF_NS_END  // namespace bfd
+
+static unsigned query_grid(uint64_t n) { return (unsigned) ((n + 255) / 256); }
+
+extern "C" hipError_t bfk_launch_query(int op, const bfd::DScene *sc, uint64_t n, const uint32_t *materials, uint32_t emitter,
+                                       const float *in, float *out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid(query_grid(n)), block(256);
+    switch (op) {
+        case bfd::kQueryEvalPdf:
+            hipLaunchKernelGGL(bfd::bf_query_kernel<bfd::kQueryEvalPdf>, grid, block, 0, stream, *sc, n, materials, emitter, in, out);
+            break;
+        case bfd::kQuerySample:
+            hipLaunchKernelGGL(bfd::bf_query_kernel<bfd::kQuerySample>, grid, block, 0, stream, *sc, n, materials, emitter, in, out);
+            break;
+        case bfd::kQueryEmitter:
+            hipLaunchKernelGGL(bfd::bf_query_kernel<bfd::kQueryEmitter>, grid, block, 0, stream, *sc, n, materials, emitter, in, out);
+            break;
+        default:
+            hipLaunchKernelGGL(bfd::bf_query_kernel<bfd::kQuerySensor>, grid, block, 0, stream, *sc, n, materials, emitter, in, out);
+            break;
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t bfk_launch_microfacet(int op, uint32_t type, float alpha_u, float alpha_v, uint32_t sample_visible, uint64_t n,
+                                            const float *in, float *out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(bfd::bf_microfacet_kernel, dim3(query_grid(n)), dim3(256), 0, stream, op, type, alpha_u, alpha_v, sample_visible,
+                       n, in, out);
+    return hipGetLastError();
+}
 #endif  // !BF_FAST

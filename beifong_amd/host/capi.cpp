@@ -117,6 +117,19 @@ const bf_scene_desc *bfh_scene_flat_desc(void *scene, void *endpoint) {
         return nullptr;
     }
 }
+/// the device scene (bf_scene *) the integrator renders `endpoint` with (NULL: the scene's default endpoint), created on first
+/// use; owned by the scene and replaced when the scene is flattened for another endpoint, so callers fetch it per use
+void *bfh_scene_device(void *scene, void *endpoint) {
+    try {
+        Scene *s = as_scene(scene);
+        const Endpoint *e = endpoint ? dynamic_cast<Endpoint *>((Object *) endpoint) : s->default_endpoint();
+        if (!e) Throw("object is not a sensor or receiver");
+        return s->device_scene(e);
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return nullptr;
+    }
+}
 /// the bf_launch the integrator would issue for this endpoint
 int bfh_integrator_launch(void *integrator, void *endpoint, bf_launch *out) {
     BFH_TRY({

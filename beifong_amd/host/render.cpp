@@ -560,6 +560,12 @@ static void check_core_abi() {
     (void) ok;
 }
 
+const Endpoint *Scene::default_endpoint() const {
+    if (!m_sensors.empty()) return m_sensors[0].get();
+    if (!m_receivers.empty()) return m_receivers[0].get();
+    Throw("the scene has no sensor and no receiver: nothing to flatten it for");
+}
+
 bf_scene *Scene::device_scene(const Endpoint *endpoint) {
     check_core_abi();
     flat_desc(endpoint);

@@ -324,6 +324,9 @@ public:
     /// one device scene per GPU 0 .. n - 1 (cached; [0] is device_scene()): the handles bf_render_sharded takes
     std::vector<bf_scene *> device_scenes(const Endpoint *endpoint, int n);
     const bf_scene_desc *flat_desc(const Endpoint *endpoint);
+    /// the endpoint a query without one runs for: the first sensor, else the first receiver (Scene::ray_intersect and the
+    /// plugin queries of the Python layer run on device_scene() of it, the handle the integrator renders with)
+    const Endpoint *default_endpoint() const;
     const Class *class_() const override;
 
 private:

@@ -51,6 +51,8 @@ def lib():
     l.bfh_shape_info.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(C.c_float)]
     l.bfh_scene_flat_desc.argtypes = [vp, vp]
     l.bfh_scene_flat_desc.restype = C.POINTER(capi.bf_scene_desc)
+    l.bfh_scene_device.argtypes = [vp, vp]
+    l.bfh_scene_device.restype = vp
     l.bfh_integrator_launch.argtypes = [vp, vp, C.POINTER(capi.bf_launch)]
     l.bfh_integrator_render.argtypes = [vp, vp, vp]
     l.bfh_integrator_receive.argtypes = [vp, vp, vp]
@@ -298,6 +300,23 @@ class Sensor(_Handle):
     def film(self):
         return _Storage(self)
 
+    def sample_ray(self, time, wavelength_sample, position_sample, aperture_sample):
+        """Sensor::sample_ray on the device (bf_sensor_sample_ray) for this sensor of its scene.  position_sample /
+        aperture_sample: [2] or [n, 2] (film position in [0, 1]^2 of the crop window).  `time` and `wavelength_sample`
+        are not read by the sensor types covered (perspective, fluxmeter, irradiancemeter, radiancemeter).
+        Returns (Ray with o, d, mint, maxt, weight [n])."""
+        scene = self._owner
+        if not isinstance(scene, Scene):
+            raise HostError("sample_ray: the sensor is not bound to a loaded scene")
+        pos = np.atleast_2d(np.asarray(position_sample, np.float32))
+        ap = np.atleast_2d(np.asarray(aperture_sample, np.float32))
+        if pos.shape[-1] != 2 or ap.shape[-1] != 2:
+            raise ValueError("sample_ray: position_sample and aperture_sample are [2] or [n, 2]")
+        pos, ap = np.broadcast_arrays(pos, ap)
+        rows = np.ascontiguousarray(np.concatenate([pos, ap], axis=1), np.float32)
+        out = scene._queries(self).sensor_sample_ray(rows)
+        return Ray(out[:, 0:3], out[:, 4:7], out[:, 3], out[:, 8]), out[:, 7]
+
     def sampler(self):
         return Sampler(self)
 
@@ -310,7 +329,135 @@ class Receiver(_Handle):
         return Sampler(self)
 
 
+class _Record:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(sorted(self.__dict__))})"
+
+
+class Ray(_Record):
+    """A batch of rays: o, d [n, 3], mint, maxt [n]."""
+
+    def __init__(self, o, d, mint, maxt):
+        super().__init__(o=o, d=d, mint=mint, maxt=maxt)
+
+
+class Frame(_Record):
+    pass
+
+
+class SurfaceInteraction(_Record):
+    """Scene::ray_intersect's SurfaceInteraction3f over a batch of rays (bf_ray_intersect): t, p, n, sh_frame (s, t, n), wi
+    (local shading frame), uv (the hit's primitive parameterisation, prim_uv of the C record), dp_du, dp_dv, shape and
+    prim_index (uint32, 0xffffffff on a miss).  A miss has t = inf and zeros elsewhere."""
+
+    def is_valid(self):
+        return np.isfinite(self.t)
+
+
+class BSDFSample(_Record):
+    pass
+
+
+class DirectionSample(_Record):
+    pass
+
+
+# math.h RayEpsilon (Epsilon * 1500): the mint of Ray3f(o, d)
+RAY_EPSILON = np.float32(np.float32(2.0 ** -24) * np.float32(1500.0))
+
+
+def _ray_rows(rays, d=None, mint=None, maxt=None):
+    """[n, 8] rays (o.xyz, mint, d.xyz, maxt), or o and d [n, 3] / [3] with optional mint (RayEpsilon) and maxt (inf)."""
+    if d is None:
+        r = np.asarray(rays, np.float32)
+        if r.ndim == 0 or r.shape[-1] != 8:
+            raise ValueError("rays: [n, 8] = o.xyz, mint, d.xyz, maxt (or pass o and d)")
+        return np.ascontiguousarray(r.reshape(-1, 8))
+    o, d = np.broadcast_arrays(np.atleast_2d(np.asarray(rays, np.float32)), np.atleast_2d(np.asarray(d, np.float32)))
+    if o.shape[-1] != 3:
+        raise ValueError("o and d: [n, 3]")
+    n = o.shape[0]
+    r = np.empty((n, 8), np.float32)
+    r[:, 0:3], r[:, 4:7] = o, d
+    r[:, 3] = RAY_EPSILON if mint is None else np.broadcast_to(np.asarray(mint, np.float32), n)
+    r[:, 7] = np.inf if maxt is None else np.broadcast_to(np.asarray(maxt, np.float32), n)
+    return r
+
+
+class BSDF:
+    """The BSDF of a shape, evaluated on the device (bf_bsdf_eval_pdf / bf_bsdf_sample) on the material table entry the
+    integrator renders the shape with.  Directions are in the local shading frame, as si.wi is in bsdf.eval(ctx, si, wo);
+    every argument is [3] / [2] or a batch [n, 3] / [n, 2] (broadcast against each other)."""
+
+    def __init__(self, scene, material):
+        self._scene = scene
+        self.material = int(material)
+
+    def _run(self, what, a, b):
+        rows = np.ascontiguousarray(np.concatenate([a, b], axis=1), np.float32)
+        mats = np.full(rows.shape[0], self.material, np.uint32)
+        q = self._scene._queries()
+        return getattr(q, what)(mats, rows)
+
+    @staticmethod
+    def _batch(*arrays):
+        return np.broadcast_arrays(*[np.atleast_2d(np.asarray(a, np.float32)) for a in arrays])
+
+    def eval(self, wi, wo):
+        wi, wo = self._batch(wi, wo)
+        return self._run("bsdf_eval_pdf", wi, wo)[:, 0]
+
+    def pdf(self, wi, wo):
+        wi, wo = self._batch(wi, wo)
+        return self._run("bsdf_eval_pdf", wi, wo)[:, 1]
+
+    def eval_pdf(self, wi, wo):
+        wi, wo = self._batch(wi, wo)
+        out = self._run("bsdf_eval_pdf", wi, wo)
+        return out[:, 0], out[:, 1]
+
+    def sample(self, wi, sample1, sample2):
+        """BSDF::sample -> (BSDFSample with wo [n, 3], pdf [n]; weight [n] = eval / pdf)."""
+        wi = np.atleast_2d(np.asarray(wi, np.float32))
+        s1 = np.asarray(sample1, np.float32).reshape(-1, 1)
+        s2 = np.atleast_2d(np.asarray(sample2, np.float32))
+        n = max(wi.shape[0], s1.shape[0], s2.shape[0])
+        u = np.concatenate([np.broadcast_to(s1, (n, 1)), np.broadcast_to(s2, (n, 2))], axis=1)
+        out = self._run("bsdf_sample", np.broadcast_to(wi, (n, 3)), u)
+        return BSDFSample(wo=out[:, 0:3], pdf=out[:, 3]), out[:, 4]
+
+
+class Emitter:
+    """Emitter k of the scene (the integrator's emitter order), sampled on the device (bf_emitter_sample_direction)."""
+
+    def __init__(self, scene, index, type_):
+        self._scene = scene
+        self.index = int(index)
+        self.type = int(type_)
+
+    def sample_direction(self, ref_p, sample):
+        """Emitter::sample_direction(it, sample) for reference points ref_p [3] / [n, 3] and samples [2] / [n, 2] ->
+        (DirectionSample with d, dist, pdf, delta, pdf_direction; spectrum [n])."""
+        p = np.atleast_2d(np.asarray(ref_p, np.float32))
+        u = np.atleast_2d(np.asarray(sample, np.float32))
+        n = max(p.shape[0], u.shape[0])
+        rows = np.ascontiguousarray(np.concatenate([np.broadcast_to(p, (n, 3)), np.broadcast_to(u, (n, 2))], axis=1))
+        out = self._scene._queries().emitter_sample_direction(self.index, rows)
+        return DirectionSample(d=out[:, 0:3], dist=out[:, 3], pdf=out[:, 4], delta=out[:, 5] != 0, pdf_direction=out[:, 7]), out[:, 6]
+
+
 class Shape(_Handle):
+    def bsdf(self):
+        """This shape's BSDF, evaluated on the device on the scene the integrator renders with."""
+        scene = self._owner
+        if not isinstance(scene, Scene) or getattr(self, "_index", None) is None:
+            raise HostError("bsdf: the shape is not bound to a loaded scene")
+        desc = scene.flat_desc(scene._default_endpoint()).desc
+        return BSDF(scene, desc.shapes[self._index].material)
+
     def primitive_count(self):
         p, a = C.c_uint(), C.c_float()
         check(lib().bfh_shape_info(self._ptr, C.byref(p), C.byref(a)))
@@ -363,7 +510,46 @@ class Scene(_Handle):
         return [Receiver(lib().bfh_scene_receiver(self._ptr, i), owner=self) for i in range(self._counts()[2])]
 
     def shapes(self):
-        return [Shape(lib().bfh_scene_shape(self._ptr, i), owner=self) for i in range(self._counts()[0])]
+        out = []
+        for i in range(self._counts()[0]):
+            sh = Shape(lib().bfh_scene_shape(self._ptr, i), owner=self)
+            sh._index = i
+            out.append(sh)
+        return out
+
+    # ---- device-side queries: on the bf_scene the integrator renders with (bfh_scene_device) --------------------------------
+    def _default_endpoint(self):
+        c = self._counts()
+        if c[1]:
+            return Sensor(lib().bfh_scene_sensor(self._ptr, 0), owner=self)
+        if c[2]:
+            return Receiver(lib().bfh_scene_receiver(self._ptr, 0), owner=self)
+        raise HostError("the scene has no sensor and no receiver")
+
+    def _queries(self, endpoint=None):
+        """A capi.Scene on the device handle of `endpoint` (default: the first sensor, else the first receiver).  The host
+        scene owns the handle and replaces it when it is flattened for another endpoint: fetched per call, never kept."""
+        ep = endpoint if endpoint is not None else self._default_endpoint()
+        h = lib().bfh_scene_device(self._ptr, ep._ptr)
+        if not h:
+            raise HostError(lib().bfh_last_error().decode())
+        return capi.Scene.borrow(h, owner=self)
+
+    def ray_intersect(self, rays, d=None, mint=None, maxt=None):
+        """Scene::ray_intersect over a batch: rays [n, 8] (o.xyz, mint, d.xyz, maxt), or o and d with optional mint / maxt
+        -> SurfaceInteraction."""
+        r = self._queries().ray_intersect(_ray_rows(rays, d, mint, maxt))
+        return SurfaceInteraction(t=r["t"], p=r["p"], n=r["n"], sh_frame=Frame(s=r["sh_s"], t=r["sh_t"], n=r["sh_n"]), wi=r["wi"],
+                                  uv=r["prim_uv"], dp_du=r["dp_du"], dp_dv=r["dp_dv"], shape=r["shape"], prim_index=r["prim"])
+
+    def ray_test(self, rays, d=None, mint=None, maxt=None):
+        """Scene::ray_test over a batch -> bool [n]."""
+        return self._queries().trace_any(_ray_rows(rays, d, mint, maxt)).astype(bool)
+
+    def emitters(self):
+        """The emitters in the order the integrator samples them (standalone emitters, then shape emitters in shape order)."""
+        desc = self.flat_desc(self._default_endpoint()).desc
+        return [Emitter(self, k, desc.emitters[k].type) for k in range(desc.n_emitters)]
 
     def flat_desc(self, endpoint):
         """The bf_scene_desc the integrator hands to the HIP library (tests feed

@@ -644,6 +644,72 @@ bf_status bf_ray_intersect(const bf_scene *scene, uint64_t n, const float *rays,
  * 5 erf, 6 tan.  Needs no scene. */
 bf_status bf_eval_elementary(int op, uint64_t n, const float *x, float *y);
 
+/* ---------------- plugin-level queries on the device ------------------------------------------------------------------
+ * The BSDF, emitter and sensor functions the render kernels call, one query per lane, general kernels (every material,
+ * emitter and sensor type; never the lean profile, never BF_FLAG_FAST).  Every path-level result of a render is built from
+ * exactly these values, so each query is bit-identical to the oracle's function of the same name (tests/test_gpu_queries.py).
+ *
+ * Two forms each, like bf_render / bf_render_device:
+ *   host form      host arrays, synchronous: stages the rows, runs the _device form on the null stream, copies back and
+ *                  waits for that stream
+ *   _device form   device pointers (e.g. torch tensors' data_ptr()) and a hipStream_t (NULL = default stream); asynchronous
+ *
+ * What a query sees: the scene as the handle's next render would — after a preceding bf_scene_update_endpoints or
+ *   bf_scene_transform_meshes / bf_scene_translate_meshes on the same stream, the tables a joined endpoint update moved into
+ *   the rolling pool included.  Never the geometry versions of a motion batch (bf_render_motion_batch_device).
+ * Ordering: like a render, a query waits for the handle's previous work when it is issued on another stream, and the
+ *   handle's next call waits for the query, so a later update cannot overwrite a table a query is still reading.  One host
+ *   thread at a time per handle (BF_ERR_INVALID otherwise).
+ * Rolling sequences: queries only read the scene.  A query issued between two rolling renders leaves the sequence open and
+ *   its histograms unchanged.
+ * Refusals, before anything is enqueued (a refused call changes nothing):
+ *   BF_ERR_INVALID      a null scene; a null pointer with n > 0; n > 2^32 - 1; an emitter index out of range; a material
+ *                       index out of range (host forms: checked on the host; the _device forms cannot see the indices and
+ *                       write NaN to the rows of out-of-range ones); a bf_eval_microfacet op or distribution out of range
+ *   BF_ERR_UNSUPPORTED  transmitter-type emitters (BF_TRANSMITTER_*) and receiver-type sensors (BF_RECEIVER_*): no probe
+ *   n == 0 returns BF_OK and launches nothing.
+ * Directions of the BSDF queries are in the local shading frame, as si.wi is in BSDF::eval(ctx, si, wo). */
+
+/* BSDF::eval and BSDF::pdf (diffuse.cpp:78-135, roughconductor.cpp:145-392, twosided.cpp:62-180; eval includes the cosine
+ * foreshortening).  materials[n]: index into the scene's material table (the twosided back material is selected for
+ * wi.z < 0 as the renders do); wi_wo[n][6] = wi.xyz, wo.xyz; out[n][2] = eval, pdf. */
+bf_status bf_bsdf_eval_pdf(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_wo, float *out);
+bf_status bf_bsdf_eval_pdf_device(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_wo, float *out,
+                                  void *stream);
+
+/* BSDF::sample (diffuse.cpp:78-100, roughconductor.cpp:145-218, twosided.cpp:94-130).  wi_u[n][6] = wi.xyz, sample1,
+ * sample2.xy (sample1 is unused by these single-lobe BSDFs); out[n][5] = wo.xyz, pdf, weight (eval / pdf). */
+bf_status bf_bsdf_sample(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_u, float *out);
+bf_status bf_bsdf_sample_device(const bf_scene *scene, uint64_t n, const uint32_t *materials, const float *wi_u, float *out,
+                                void *stream);
+
+/* Emitter::sample_direction of emitter `emitter` (spot.cpp:97-164, point.cpp:78-103, area.cpp:76-120 -> shape.cpp:323-356).
+ * in[n][5] = ref_p.xyz, sample.xy; out[n][8] = d.xyz, dist, pdf, delta (0 / 1), grey spectrum (weight), pdf_direction of the
+ * sampled point (area.cpp:122-150; 0 for the delta emitters). */
+bf_status bf_emitter_sample_direction(const bf_scene *scene, uint32_t emitter, uint64_t n, const float *in, float *out);
+bf_status bf_emitter_sample_direction_device(const bf_scene *scene, uint32_t emitter, uint64_t n, const float *in, float *out,
+                                             void *stream);
+
+/* Sensor::sample_ray of the scene's sensor (perspective.cpp:172-199, fluxmeter.cpp:63-85, irradiancemeter.cpp:63-85,
+ * radiancemeter.cpp:91-108).  in[n][4] = film position.xy in [0, 1]^2 of the crop window, aperture sample.xy; out[n][9] =
+ * o.xyz, mint, d.xyz, ray weight, maxt.  Time and wavelength samples are not read by these sensors. */
+bf_status bf_sensor_sample_ray(const bf_scene *scene, uint64_t n, const float *in, float *out);
+bf_status bf_sensor_sample_ray_device(const bf_scene *scene, uint64_t n, const float *in, float *out, void *stream);
+
+/* Scene::ray_intersect / ray_test on DEVICE rays [n][8], stream-ordered: the kernel of bf_ray_intersect / bf_trace_any,
+ * so the results are bit-identical to theirs.  out_si[n][BF_SI_FLOATS] (required), out_prim / out_shape may be NULL;
+ * out_hit[n] = 0 / 1. */
+bf_status bf_ray_intersect_device(const bf_scene *scene, uint64_t n, const float *rays, float *out_si, uint32_t *out_prim,
+                                  uint32_t *out_shape, void *stream);
+bf_status bf_trace_any_device(const bf_scene *scene, uint64_t n, const float *rays, uint8_t *out_hit, void *stream);
+
+/* MicrofacetDistribution on the device (include/mitsuba/render/microfacet.h:60-400; the golden vectors of
+ * src/librender/tests/test_microfacet.py).  Needs no scene.  distribution: BF_MF_*; in[n][8] = wi.xyz, m.xyz, s.xy;
+ * op 0: out[i][0] = eval(m); 1: pdf(wi, m); 2: smith_g1(v = m, m = wi); 3: sample(wi, s) -> out[i] = m.xyz, pdf.
+ * Ops 0-2 write 0 to out[i][1..3]. */
+bf_status bf_eval_microfacet(int op, uint32_t distribution, float alpha_u, float alpha_v, uint32_t sample_visible, uint64_t n,
+                             const float *in, float *out);
+
 #ifdef __cplusplus
 }
 #endif
