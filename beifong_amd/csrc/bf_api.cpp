@@ -185,7 +185,6 @@ struct bf_tunables {
     bool tab_cache = true;                   // BF_TAB_CACHE=0: materials / rectangles stay in device memory (no LDS copies)
     bool shade_split = false;                // BF_SHADE_SPLIT=1: wf_shade walks the alive masks twice: slots without a real hit first, real hits second (measured: no net gain)
     uint32_t chain_min = 16;                 // BF_CHAIN_MIN: resolved real hits chain only while at least this many lanes hold one (0: always)
-    uint32_t rf_min = 16, rf_th = 44, rf_tm = 24;      // BF_RF_MIN / BF_RF_TH / BF_RF_TM: wf_shade's lane refill and phase vote (bf_wavefront.h)
     uint32_t grid_share = 3;                 // BF_GRID_SHARE: small pools (< grid_small slots) of handles that roll side by side launch 1 / min(peers, this) of the persistent grids (0 / 1: off)
     uint32_t grid_small = 1u << 22;          // BF_GRID_SMALL
     bool roll_join = true;                   // BF_ROLL_JOIN=0: bf_scene_update_endpoints flushes an open rolling sequence (round 3's behaviour)
@@ -222,9 +221,6 @@ static bf_tunables read_tunables() {
     t.tab_cache = num("BF_TAB_CACHE", 1) != 0;
     t.shade_split = num("BF_SHADE_SPLIT", 0) != 0;
     t.chain_min = (uint32_t) std::max<long long>(0, std::min<long long>(num("BF_CHAIN_MIN", 16), 64));
-    t.rf_min = (uint32_t) std::max<long long>(1, std::min<long long>(num("BF_RF_MIN", 16), 64));
-    t.rf_th = (uint32_t) std::max<long long>(1, std::min<long long>(num("BF_RF_TH", 44), 64));
-    t.rf_tm = (uint32_t) std::max<long long>(0, std::min<long long>(num("BF_RF_TM", 24), 64));
     t.grid_share = (uint32_t) std::max<long long>(0, std::min<long long>(num("BF_GRID_SHARE", 3), 16));
     t.grid_small = (uint32_t) std::max<long long>(0, std::min<long long>(num("BF_GRID_SMALL", 1ll << 22), 1ll << 30));
     t.roll_join = num("BF_ROLL_JOIN", 1) != 0;
@@ -512,7 +508,7 @@ static bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream) {
 }
 
 static int32_t bfd_no_node() { return INT32_MIN; }
-static constexpr size_t kTriPad = 4;      // float4 rows of padding behind the triangle array (bf_wavefront.hip: the if-if step of wf_trace)
+static constexpr size_t kTriPad = 4;      // float4 rows of padding behind the triangle array (read by no kernel; part of the geometry layout)
 static_assert(bf::kTopNodes == bfd::kTopNodes, "the builder's breadth-first prefix is what wf_trace caches");
 static_assert(bfd::CTR_GUARD + 2 == bfd::CTR_COUNT && bfd::CTR_SURV_GUARD + 1 == bfd::CTR_COUNT,
               "the two sticky guard words are the last counters: renders clear the ones before them");
@@ -897,7 +893,7 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     if (sc->tun.wide_rows_log >= 0) wide_rlog = std::min<uint32_t>(wide_rlog, (uint32_t) sc->tun.wide_rows_log);
     for (int k = 0; k < 3 && !btris.empty(); ++k)
         sc->origin_scale_built = std::max({sc->origin_scale_built, std::fabs(bvh.lo[k]), std::fabs(bvh.hi[k])});
-    // (+ kTriPad rows behind the last triangle: wf_trace's if-if step reads seven rows from a leaf's first triangle)
+    // (+ kTriPad rows of padding behind the last triangle)
     std::vector<float4> tri_data(bfd::kTriStride * btris.size() + (btris.empty() ? 0 : kTriPad), make_float4(0, 0, 0, 0)), nrm_data;
     if (any_normals) nrm_data.resize(3 * btris.size());
     std::vector<float4> uv_data;
@@ -1613,31 +1609,9 @@ static bf_status wf_ensure(const bf_scene *scene, uint32_t capacity) {
         return e;
     };
     size_t n = capacity, nb = capacity / 64;
-#if BF_STATE_AOS
-#if BF_STATE_AOS == 2
-    HIP_TRY(alloc((void **) &wf.recA, n * 128));
-    wf.recB = wf.recA + 4;
-#else
     HIP_TRY(alloc((void **) &wf.recA, n * 64));
     HIP_TRY(alloc((void **) &wf.recB, n * 64));
-#endif
     HIP_TRY(alloc((void **) &wf.recC, n * 64));
-#else
-    HIP_TRY(alloc((void **) &wf.ray0_, n * 16));
-    HIP_TRY(alloc((void **) &wf.ray1_, n * 16));
-    HIP_TRY(alloc((void **) &wf.sa_, n * 16));
-    HIP_TRY(alloc((void **) &wf.sb_, n * 16));
-    HIP_TRY(alloc((void **) &wf.sd_, n * 16));
-    HIP_TRY(alloc((void **) &wf.se_, n * 16));
-    HIP_TRY(alloc((void **) &wf.hit_, n * 16));
-    HIP_TRY(alloc((void **) &wf.hit_prim_, n * 4));
-    HIP_TRY(alloc((void **) &wf.sh0_, n * 16));
-    HIP_TRY(alloc((void **) &wf.sh1_, n * 16));
-    HIP_TRY(alloc((void **) &wf.sh2_, n * 4));
-    HIP_TRY(alloc((void **) &wf.sh3_, n * 4));
-    HIP_TRY(alloc((void **) &wf.render_, n * 4));
-    HIP_TRY(alloc((void **) &wf.dop_, n * 4));
-#endif
     HIP_TRY(alloc((void **) &scene->wf_masks, 8 * nb * sizeof(unsigned long long)));
     HIP_TRY(alloc((void **) &wf.n_live, (bfd::kWfMaxIter + 2) * sizeof(uint32_t)));
     HIP_TRY(alloc((void **) &scene->roll_ring, bfd::kRollRing * sizeof(bfd::DRoll)));
@@ -1766,9 +1740,6 @@ static bf_status wf_setup(const bf_scene *scene, const Kernels &k, const bfd::DL
     c.mask_bytes = 4 * nb * sizeof(unsigned long long);
     wf.hit_split = scene->tun.shade_split ? 1u : 0u;
     wf.chain_min = scene->tun.chain_min;
-    wf.rf_min = scene->tun.rf_min;
-    wf.rf_th = scene->tun.rf_th;
-    wf.rf_tm = scene->tun.rf_tm;
     c.lds_shade = ((sizeof(float) * lp.lds_floats + 15) & ~size_t(15)) + (scene->d.tab_cache ? bfd::kTabBytes : 0u);      // histogram | tables
     c.lds_tail = sizeof(int) * bfd::kStackDepth * bfd::kBlock + c.lds_shade;
     // persistent grids: shade is register-heavy (3 workgroups per CU at 168 VGPRs), trace runs
@@ -1858,9 +1829,6 @@ static bf_status wf_guard_error(unsigned long long lost, unsigned long long refu
 // every path of a completed render / sequence was binned exactly once (CTR_FILM counts film_put calls): the loud form of the
 // tests' "sum of the weight channel + invalid samples == paths"
 static bf_status check_film_count(const unsigned long long *c, uint64_t n_paths) {
-#ifdef BF_NO_FILM_CTR      // developer A/B build without the counter
-    return BF_OK;
-#endif
     if (c[bfd::CTR_FILM] != n_paths)
         return fail(BF_ERR_DEVICE, "%llu of %llu paths were binned: paths were lost or binned twice (a scheduling bug; please report the "
                                    "scene and the launch)", (unsigned long long) c[bfd::CTR_FILM], (unsigned long long) n_paths);

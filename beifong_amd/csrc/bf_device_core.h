@@ -168,13 +168,10 @@ BF_DEV int pick_child(float4 ch, uint32_t key) {
 // case of a four-wide tree is three per level — in a per-thread HBM column (DScene::spill, entry
 // k at spill[k * spill_stride]).  SPILL = false: the host guarantees BVH4::stack_need <= N_LDS
 // (bf_bvh.h) and the overflow path is compiled out.
-// pop(): BF_FLAT_POP = 1 (default) reads the entry through ONE flat load on a selected pointer; 0 branches between an LDS and a
-// global load.  The branch looked like the obvious win (a flat load is a vector-memory instruction and waits for both
-// counters) and measured 1.3 % SLOWER in wf_trace (3.85 -> 3.90 ms per C2 step, profiles/r04_flat_ops_ab.txt): the extra
-// divergence costs more than the flat path, so the select stays.
-#ifndef BF_FLAT_POP
-#define BF_FLAT_POP 1
-#endif
+// pop() reads the entry through ONE flat load on a selected pointer.  A branch between an LDS and a global load looked like
+// the obvious win (a flat load is a vector-memory instruction and waits for both counters) and measured 1.3 % SLOWER in
+// wf_trace (3.85 -> 3.90 ms per C2 step, profiles/r04_flat_ops_ab.txt): the extra divergence costs more than the flat path,
+// so the select stays.
 template <int N_LDS, bool SPILL>
 struct LaneStack {
     // The two homes of an entry are named by address space: with generic pointers the compiler turns pop()'s choice into a
@@ -193,12 +190,7 @@ struct LaneStack {
     }
     BF_DEV int pop() {
         --sp;
-#if BF_FLAT_POP
         return (!SPILL || sp < N_LDS) ? ((int *) lds)[sp * kBlock] : ((int *) spill)[(size_t) (sp - N_LDS) * spill_stride];
-#else
-        if (!SPILL || sp < N_LDS) return lds[sp * kBlock];
-        return spill[(size_t) (sp - N_LDS) * spill_stride];
-#endif
     }
     BF_DEV int pop_or_none() { return sp ? pop() : kNoNode; }
     // up to three entries a, b, c in that order (pa implies pb implies pc: the caller's entries are sorted, the absent ones
@@ -236,9 +228,6 @@ BF_DEV LaneStack<N_LDS, SPILL> make_stack(const DScene &sc, int *lds_column) {
     return st;
 }
 
-#ifndef BF_NODE_SORT_PAIRS
-#define BF_NODE_SORT_PAIRS 1
-#endif
 // Visit internal node `node`: test its (up to) four child boxes against the ray segment
 // [mint, tmax], push the hit children far-to-near and return the nearest one (or the next
 // stack entry, or kNoNode when the traversal is finished).
@@ -251,7 +240,6 @@ BF_DEV int node4_decide(const float4 lx, const float4 ly, const float4 lz, const
     const bool h2 = slab_fma(lx.z, ly.z, lz.z, hx.z, hy.z, hz.z, id, oid, ohi, mint, tmax, t2) && __float_as_int(ch.z) != kNoNode;
     const bool h3 = slab_fma(lx.w, ly.w, lz.w, hx.w, hy.w, hz.w, id, oid, ohi, mint, tmax, t3) && __float_as_int(ch.w) != kNoNode;
     uint32_t k0 = child_key(h0, t0, 0u), k1 = child_key(h1, t1, 1u), k2 = child_key(h2, t2, 2u), k3 = child_key(h3, t3, 3u);
-#if BF_NODE_SORT_PAIRS
     // 5-comparator sorting network on (key, child) PAIRS: the children come out in traversal order (no selects by slot
     // afterwards), the three far ones go onto the stack with predicated writes (LaneStack::push3)
     int c0 = __float_as_int(ch.x), c1 = __float_as_int(ch.y), c2 = __float_as_int(ch.z), c3 = __float_as_int(ch.w);
@@ -274,17 +262,6 @@ BF_DEV int node4_decide(const float4 lx, const float4 ly, const float4 lz, const
     st.push3(c3, k3 < kMissKey, c2, k2 < kMissKey, c1, k1 < kMissKey);
     if (k0 < kMissKey) return c0;
     return st.pop_or_none();
-#else
-    // 5-comparator sorting network
-    const uint32_t a = min(k0, k1), b = max(k0, k1), c = min(k2, k3), d = max(k2, k3);
-    const uint32_t lo = min(a, c), x = max(a, c), y = min(b, d), hi = max(b, d);
-    const uint32_t m1 = min(x, y), m2 = max(x, y);
-    if (hi < kMissKey) st.push(pick_child(ch, hi));
-    if (m2 < kMissKey) st.push(pick_child(ch, m2));
-    if (m1 < kMissKey) st.push(pick_child(ch, m1));
-    if (lo < kMissKey) return pick_child(ch, lo);
-    return st.pop_or_none();
-#endif
 }
 template <class Stack>
 BF_DEV int node4_step(const float4 *__restrict__ nodes, int node, V3 id, V3 oid, V3 ohi, float mint, float tmax, Stack &st) {

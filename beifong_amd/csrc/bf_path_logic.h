@@ -161,7 +161,7 @@ struct MaskCursor {
     unsigned long long sub;     // slots of a batch this wave serves (all ones, or a 32- / 16-slot share: the tail's spreading)
     unsigned long long w;       // this lane's word of the chunk, & sub
     unsigned long long nz;      // wave-uniform: chunk words that are non-zero and not consumed yet
-    // the sources of the generating launches (wf_shade<1>, <2> with lane refill): the walk covers `b_end` batches starting at
+    // rotated / complemented walks (every cursor of the kernels is plain at present): the walk covers `b_end` batches starting at
     // physical batch `rot` (wrapping at `mod`), of the complemented words (inv: slots WITHOUT a live path) or — masks == nullptr —
     // of every slot.  Plain cursors: rot = 0, inv = 0, pb == b.
     uint32_t rot, mod, inv, pb;
@@ -845,21 +845,11 @@ BF_DEV void lds_add(float *p, float v) {          // ds_add_f32
 BF_DEV void glb_add(float *p, float v) {          // global_atomic_add_f32
     (void) __hip_atomic_fetch_add((glb_float_ptr) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-#ifndef BF_FLAT_HIST
-#define BF_FLAT_HIST 0
-#endif
 BF_DEV void hist_add(float *s_hist, float *g_hist, bool lds, uint32_t idx, float v) {
-#if BF_FLAT_HIST
-    if (lds)
-        atomicAdd(&s_hist[idx], v);
-    else
-        atomicAdd(&g_hist[idx], v);
-#else
     if (lds)
         lds_add(s_hist + idx, v);
     else
         glb_add(g_hist + idx, v);
-#endif
 }
 // Where the samples of render `render` go: plain launch = the histogram; batched launch = block `render` of it (LDS and
 // global alike); rolling sequence = the render's own histogram (DRoll::hist), privatised in LDS only for the newest
@@ -988,9 +978,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                      FilmAcc &acc, bf_path_record *records) {
     const DScene sc = path_scene<RX>(sc0, lp, s.render);
     const bool valid = (s.flags & kFlagValid) != 0;
-#ifndef BF_NO_FILM_CTR
     ++acc.n_put;
-#endif
     float rec_L, rec_aux;
     float *const s_base = s_hist + lp.base_off;                               // rolling launches: base-channel table (DLaunch::base_off)
     const HistDst hd = hist_dst(lp, s.render, s_hist, g_hist, lds_hist);      // this render's block of the histogram
@@ -1252,9 +1240,6 @@ template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, fl
             hist_add(hd.s, hd.g, hd.lds, 4, acc.W);
         }
     }
-#ifdef BF_NO_FLUSH      // developer timing probe: what the flush of the LDS histograms costs (the histograms stay empty)
-    return;
-#endif
     if (lds_hist) {
         __syncthreads();
         if (lp.roll) {

@@ -12,12 +12,12 @@
 // pulls the next set bits of its segment's masks into its idle lanes
 // (__popcll / n-th-set-bit select), so sparse pools still run full waves.
 //
-// All per-slot arrays are SoA float4/uint4: a wave touching one dense batch reads
-// and writes 1 KiB contiguous per array.
+// The per-slot state is three 64-byte records per slot (below).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "bf_ns.h"
+#include <stddef.h>
 #include <stdint.h>
 
 BF_NS_BEGIN
@@ -30,58 +30,31 @@ constexpr uint32_t kTraceBlocksPerCU = 8;
 constexpr uint32_t kTailSmallPool = 1u << 22;   // pools below this never fill the chip: earlier hand-over to the tail (bf_api.cpp: wf_tail_threshold)
 constexpr uint32_t kTailRowJobs = 12;      // tail: up to three passes of four row-traversed rays beat one quad pass of sixteen
 
-// Per-slot state layout.  BF_STATE_AOS = 1 (default since round 3): three 64-byte RECORDS per slot,
+// Per-slot state layout: three 64-byte RECORDS per slot,
 //   A = ray0, ray1, hit, (hit_prim, render, dop, -)      what wf_trace reads / writes for a closest-hit ray: ONE line
 //   B = sa, sb, sd, se                                   the rest of the path state (wf_shade; wf_trace adds a released
 //                                                        NEE contribution to sa.w / se.w)
 //   C = sh0, sh1, (sh2, sh3, -, -), -                    the NEE shadow request
 // Most launches GATHER sparse slots through the mask cursor (a few per cent to a third of a batch alive): with one
-// array per row (BF_STATE_AOS = 0, rounds 1-2: "a wave touching one dense batch reads 1 KiB contiguous per array") a
-// gathered lane touches seven cache lines for its state and six more to write it back; with records, two and two.
-#ifndef BF_STATE_AOS
-#define BF_STATE_AOS 1
-#endif
+// array per row (rounds 1-2: "a wave touching one dense batch reads 1 KiB contiguous per array") a gathered lane touches seven cache lines for its state and six more to write it back; with records, two and two.
 #define BF_HD __host__ __device__ __forceinline__
 
 struct WF {
-#if BF_STATE_AOS
-    // BF_STATE_AOS = 2: records A and B of a slot are the two halves of ONE 128-byte line (recB = recA + 4, stride 8)
-    static constexpr size_t kAB = BF_STATE_AOS == 2 ? 8 : 4;
     float4 *recA, *recB, *recC;     // [n_slots][4] float4 each
-    BF_HD float4 &ray0(uint32_t i) const { return recA[kAB * (size_t) i + 0]; }       // o.xyz, mint
-    BF_HD float4 &ray1(uint32_t i) const { return recA[kAB * (size_t) i + 1]; }       // d.xyz, maxt
-    BF_HD float4 &hit(uint32_t i) const { return recA[kAB * (size_t) i + 2]; }        // t, u, v, triangle slot
-    BF_HD uint32_t &hit_prim(uint32_t i) const { return reinterpret_cast<uint32_t *>(recA + kAB * (size_t) i + 3)[0]; }
-    BF_HD uint32_t &render(uint32_t i) const { return reinterpret_cast<uint32_t *>(recA + kAB * (size_t) i + 3)[1]; }
-    BF_HD float &dop(uint32_t i) const { return reinterpret_cast<float *>(recA + kAB * (size_t) i + 3)[2]; }
-    BF_HD float4 &sa(uint32_t i) const { return recB[kAB * (size_t) i + 0]; }         // throughput, eta, emission_weight, result
-    BF_HD float4 &sb(uint32_t i) const { return recB[kAB * (size_t) i + 1]; }         // aux, bs_pdf, depth|flags (bits), n_rays (bits)
-    BF_HD uint4 &sd(uint32_t i) const { return reinterpret_cast<uint4 *>(recB)[kAB * (size_t) i + 2]; }   // rng state lo/hi, path index lo/hi
-    BF_HD float4 &se(uint32_t i) const { return recB[kAB * (size_t) i + 3]; }         // receive mode: ray.time, t_rx, lambda0, phase / Q
+    BF_HD float4 &ray0(uint32_t i) const { return recA[4 * (size_t) i + 0]; }       // o.xyz, mint
+    BF_HD float4 &ray1(uint32_t i) const { return recA[4 * (size_t) i + 1]; }       // d.xyz, maxt
+    BF_HD float4 &hit(uint32_t i) const { return recA[4 * (size_t) i + 2]; }        // t, u, v, triangle slot
+    BF_HD uint32_t &hit_prim(uint32_t i) const { return reinterpret_cast<uint32_t *>(recA + 4 * (size_t) i + 3)[0]; }
+    BF_HD uint32_t &render(uint32_t i) const { return reinterpret_cast<uint32_t *>(recA + 4 * (size_t) i + 3)[1]; }
+    BF_HD float &dop(uint32_t i) const { return reinterpret_cast<float *>(recA + 4 * (size_t) i + 3)[2]; }
+    BF_HD float4 &sa(uint32_t i) const { return recB[4 * (size_t) i + 0]; }         // throughput, eta, emission_weight, result
+    BF_HD float4 &sb(uint32_t i) const { return recB[4 * (size_t) i + 1]; }         // aux, bs_pdf, depth|flags (bits), n_rays (bits)
+    BF_HD uint4 &sd(uint32_t i) const { return reinterpret_cast<uint4 *>(recB)[4 * (size_t) i + 2]; }   // rng state lo/hi, path index lo/hi
+    BF_HD float4 &se(uint32_t i) const { return recB[4 * (size_t) i + 3]; }         // receive mode: ray.time, t_rx, lambda0, phase / Q
     BF_HD float4 &sh0(uint32_t i) const { return recC[4 * (size_t) i + 0]; }        // shadow ray o.xyz, mint
     BF_HD float4 &sh1(uint32_t i) const { return recC[4 * (size_t) i + 1]; }        // d.xyz, maxt
     BF_HD float &sh2(uint32_t i) const { return reinterpret_cast<float *>(recC + 4 * (size_t) i + 2)[0]; }   // contribution released when unoccluded
     BF_HD float &sh3(uint32_t i) const { return reinterpret_cast<float *>(recC + 4 * (size_t) i + 2)[1]; }   // BF_MODE_RECEIVE_IQ: its imaginary part
-#else
-    float4 *ray0_, *ray1_, *sa_, *sb_, *se_, *hit_, *sh0_, *sh1_;
-    uint4 *sd_;
-    uint32_t *hit_prim_, *render_;
-    float *sh2_, *sh3_, *dop_;
-    BF_HD float4 &ray0(uint32_t i) const { return ray0_[i]; }
-    BF_HD float4 &ray1(uint32_t i) const { return ray1_[i]; }
-    BF_HD float4 &hit(uint32_t i) const { return hit_[i]; }
-    BF_HD uint32_t &hit_prim(uint32_t i) const { return hit_prim_[i]; }
-    BF_HD uint32_t &render(uint32_t i) const { return render_[i]; }
-    BF_HD float &dop(uint32_t i) const { return dop_[i]; }
-    BF_HD float4 &sa(uint32_t i) const { return sa_[i]; }
-    BF_HD float4 &sb(uint32_t i) const { return sb_[i]; }
-    BF_HD uint4 &sd(uint32_t i) const { return sd_[i]; }
-    BF_HD float4 &se(uint32_t i) const { return se_[i]; }
-    BF_HD float4 &sh0(uint32_t i) const { return sh0_[i]; }
-    BF_HD float4 &sh1(uint32_t i) const { return sh1_[i]; }
-    BF_HD float &sh2(uint32_t i) const { return sh2_[i]; }
-    BF_HD float &sh3(uint32_t i) const { return sh3_[i]; }
-#endif
     uint32_t has_render;     // batched / rolling launches: render(i) = render index of the slot's current path (selects seed, histogram, mesh offset)
     uint32_t has_dop;        // BF_FLAG_DOPPLER: dop(i) = wavelength shift accumulated by the slot's path (nm)
     const float4 *offsets;   // batched launches with moving meshes: DLaunch::batch_offsets (wf_trace has no DLaunch)
@@ -99,9 +72,7 @@ struct WF {
     uint32_t hit_split;             // 1: two passes as above; 0: one walk of the alive masks (BF_SHADE_SPLIT=0)
     uint32_t chain_min;             // a chained round shades resolved REAL hits only while at least this many lanes hold one (the
                                     // others are stored and picked up — packed — by the next launch); 0: always chain
-    // wf_shade with lane refill (bf_wavefront.hip, BF_SHADE_REFILL): settled lanes are written back and replaced once rf_min of a wave's
-    // lanes are out of work; a pass over the real hits runs once rf_th lanes hold one, or fewer than rf_tm lanes hold cheap work
-    uint32_t rf_min, rf_th, rf_tm;
+    uint32_t reserved[3];           // unused: keeps the kernels' argument layout (WF is passed by value)
     uint32_t *n_live;               // [kWfMaxIter + 2] live slots after shading bounce `it`
     unsigned long long *counters;   // CTR_* (bf_device.h)
     uint32_t trace_refill, trace_stragglers;   // wf_trace scheduling thresholds (see bf_wavefront.hip)
@@ -124,5 +95,6 @@ struct WF {
     uint32_t tail_share;            // tail kernel: 1, 2 or 4 waves share every batch (16 paths per wave walk four lanes per ray from the first bounce)
     uint32_t surv_claims_max;       // claims one wave may make per launch: n_waves * max <= survivor batches, so no batch is claimed twice in a launch
 };
+static_assert(sizeof(WF) == 216 && offsetof(WF, n_live) == 136, "WF is a kernel argument: its layout is the kernels' argument layout");
 
 BF_NS_END  // namespace bfd
