@@ -142,6 +142,7 @@ EXPORTED_SYMBOLS = [
     "bf_scene_destroy", "bf_scene_update_endpoints", "bf_scene_translate_meshes", "bf_scene_transform_meshes", "bf_scene_get_info", "bf_scene_clone", "bf_launch_channels", "bf_render_device", "bf_render",
     "bf_scene_flush", "bf_scene_sync", "bf_shard_range", "bf_render_sharded_device", "bf_render_sharded", "bf_allreduce_device",
     "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
+    "bf_scene_update_vertices", "bf_scene_update_vertices_device", "bf_render_deform_batch_device", "bf_render_deform_batch",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
     "bf_bsdf_eval_pdf", "bf_bsdf_eval_pdf_device", "bf_bsdf_sample", "bf_bsdf_sample_device",
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
@@ -202,6 +203,12 @@ def load_library(path=None):
     lib.bf_render_batch.argtypes = [vp, C.POINTER(bf_launch), C.POINTER(bf_batch), vp, vp, C.POINTER(bf_stats)]
     lib.bf_render_motion_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_render_motion_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(bf_stats)]
+    lib.bf_scene_update_vertices.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    lib.bf_scene_update_vertices_device.argtypes = [vp, C.c_uint32, vp, vp, C.c_float, vp]
+    lib.bf_render_deform_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_float, C.c_uint32,
+                                                  vp, vp, vp, vp, C.POINTER(bf_stats)]
+    lib.bf_render_deform_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp,
+                                           C.POINTER(bf_stats)]
     lib.bf_trace_closest.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bf_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bf_ray_intersect.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
@@ -362,6 +369,56 @@ def motion_tables(transforms, n_shapes, seeds=None):
         if sa.size != xf.shape[0]:
             raise ValueError(f"{sa.size} seeds for {xf.shape[0]} renders")
     return np.ascontiguousarray(xf), sa
+
+
+def vertex_array(a, name, n_vertices=None, n_renders=None):
+    """A float32 vertex array for a vertex update, checked: [nv, 3] (or flat [3 nv]) for one update, [K, nv, 3] for a batch.
+    float32 only (the rows hold the floats given: nothing is converted behind the caller's back)."""
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise TypeError(f"{name} must be float32, got {a.dtype}")
+    if n_renders is None:
+        if a.ndim == 1 and a.size % 3 == 0:
+            a = a.reshape(-1, 3)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{name} must be [n_vertices, 3], got {a.shape}")
+    else:
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"{name} must be [n_renders, n_vertices, 3], got {a.shape}")
+        if a.shape[0] != n_renders:
+            raise ValueError(f"{name}: {a.shape[0]} slices for {n_renders} renders")
+    if n_vertices is not None and a.shape[-2] != n_vertices:
+        raise ValueError(f"{name}: {a.shape[-2]} vertices for a mesh of {n_vertices}")
+    return np.ascontiguousarray(a)
+
+
+def deform_tables(positions, normals=None, n_vertices=None):
+    """What bf_render_deform_batch reads, from {shape: positions[K, nv, 3]} (and {shape: normals[K, nv, 3]} for some or all
+    of them): (n_renders, uint32 shapes, [positions arrays], [normals arrays or None] or None).  `positions` may also be a
+    list of (shape, array) pairs; a shape listed twice is refused here.  n_vertices: {shape: count} to check against."""
+    items = list(positions.items()) if isinstance(positions, dict) else [(k, v) for k, v in positions]
+    if not items:
+        raise ValueError("positions: no deforming shape")
+    shapes = [int(k) for k, _ in items]
+    if len(set(shapes)) != len(shapes):
+        raise ValueError(f"a shape is listed twice: {shapes}")
+    if any(k < 0 for k in shapes):
+        raise ValueError(f"negative shape index in {shapes}")
+    first = np.asarray(items[0][1])
+    if first.ndim != 3:
+        raise ValueError(f"positions of shape {shapes[0]} must be [n_renders, n_vertices, 3], got {first.shape}")
+    n_renders = first.shape[0]
+    if n_renders == 0:
+        raise ValueError("positions: no renders")
+    nv = n_vertices or {}
+    pos = [vertex_array(v, f"positions of shape {k}", nv.get(k), n_renders) for k, v in zip(shapes, (v for _, v in items))]
+    nrm = None
+    if normals is not None:
+        for k in normals:
+            if int(k) not in shapes:
+                raise ValueError(f"normals for shape {k}, which has no positions in this call")
+        nrm = [vertex_array(normals[k], f"normals of shape {k}", p.shape[1], n_renders) if k in normals else None for k, p in zip(shapes, pos)]
+    return n_renders, np.asarray(shapes, np.uint32), pos, nrm
 
 
 class Scene:
@@ -525,6 +582,81 @@ class Scene:
                                                                C.c_void_p(hist_ptr), C.c_void_p(records_ptr) if records_ptr else None,
                                                                C.c_void_p(stream) if stream else None,
                                                                C.byref(st) if st is not None else None), "bf_render_motion_batch_device")
+        return st
+
+    def mesh_vertex_count(self, shape):
+        """Vertices of mesh shape `shape` in the description this Scene was created from (None if unknown)."""
+        shapes = getattr(self.holder, "shapes", None)
+        if shapes is None or not 0 <= int(shape) < len(shapes):
+            return None
+        return int(shapes[int(shape)].n_vertices)
+
+    def update_vertices(self, shape, positions, normals=None, stream=0):
+        """bf_scene_update_vertices: replace the base vertices [nv, 3] float32 (and vertex normals) of mesh shape `shape`;
+        the handle's pose is applied on top, the BVHs are re-fitted on the device."""
+        shape = int(shape)
+        if shape < 0:
+            raise ValueError(f"shape index {shape}")
+        p = vertex_array(positions, "positions", self.mesh_vertex_count(shape))
+        n = vertex_array(normals, "normals", p.shape[0]) if normals is not None else None
+        check(self.lib, self.lib.bf_scene_update_vertices(self.handle, shape, _ptr(p), _ptr(n), C.c_void_p(stream) if stream else None),
+              "bf_scene_update_vertices")
+
+    def update_vertices_device(self, shape, positions_ptr, normals_ptr, bound, stream=0):
+        """bf_scene_update_vertices_device: the same from device arrays (float32 [nv, 3], e.g. a torch tensor's data_ptr(),
+        valid until `stream` has run the call); bound >= max |coordinate| is the caller's promise, checked on the device."""
+        check(self.lib, self.lib.bf_scene_update_vertices_device(self.handle, int(shape), C.c_void_p(int(positions_ptr)),
+                                                                 C.c_void_p(int(normals_ptr)) if normals_ptr else None, float(bound),
+                                                                 C.c_void_p(stream) if stream else None), "bf_scene_update_vertices_device")
+
+    def _deform_args(self, n_renders, transforms, seeds):
+        xf = sa = None
+        if transforms is not None:
+            xf, sa = motion_tables(transforms, self.info().n_shapes, seeds)
+            if xf.shape[0] != n_renders:
+                raise ValueError(f"{xf.shape[0]} transform tables for {n_renders} renders")
+        elif seeds is not None:
+            sa = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(-1)
+            if sa.size != n_renders:
+                raise ValueError(f"{sa.size} seeds for {n_renders} renders")
+        return xf, sa
+
+    def render_deform_batch(self, launch, positions, normals=None, transforms=None, seeds=None, records=False):
+        """bf_render_deform_batch: render k sees shape s at positions[s][k] ([K, nv, 3] float32 each; normals likewise for
+        some or all of them), then every mesh at transforms[k] (None: none) -> float32[K, channels] (+ records, stats)."""
+        nv = {int(k): self.mesh_vertex_count(k) for k in (positions.keys() if isinstance(positions, dict) else [k for k, _ in positions])}
+        n_renders, shapes, pos, nrm = deform_tables(positions, normals, {k: v for k, v in nv.items() if v is not None})
+        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        pp = (C.c_void_p * len(pos))(*[p.ctypes.data for p in pos])
+        np_ = (C.c_void_p * len(pos))(*[(q.ctypes.data if q is not None else None) for q in nrm]) if nrm is not None else None
+        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
+        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
+        st = bf_stats()
+        check(self.lib, self.lib.bf_render_deform_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), len(pos), _ptr(shapes), pp, np_,
+                                                        xf.shape[1] if xf is not None else 0, _ptr(xf), _ptr(hist), _ptr(rec), C.byref(st)),
+              "bf_render_deform_batch")
+        return hist, rec, st
+
+    def render_deform_batch_device(self, launch, n_renders, positions_ptrs, hist_ptr, bound, normals_ptrs=None, transforms=None, seeds=None,
+                                   stream=0, records_ptr=None, want_stats=False):
+        """bf_render_deform_batch_device: positions_ptrs = {shape: device pointer to float32 [K, nv, 3]} (normals_ptrs likewise
+        for some of them); render k accumulates into hist_ptr[k * channels ..] (device)."""
+        shapes = [int(k) for k in positions_ptrs]
+        if len(set(shapes)) != len(shapes):
+            raise ValueError(f"a shape is listed twice: {shapes}")
+        n_renders = int(n_renders)
+        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        sh = np.asarray(shapes, np.uint32)
+        pp = (C.c_void_p * len(shapes))(*[int(positions_ptrs[k]) for k in positions_ptrs])
+        np_ = None
+        if normals_ptrs:
+            np_ = (C.c_void_p * len(shapes))(*[(int(normals_ptrs[k]) if normals_ptrs.get(k) else None) for k in positions_ptrs])
+        st = bf_stats() if want_stats else None
+        check(self.lib, self.lib.bf_render_deform_batch_device(self.handle, C.byref(launch), n_renders, _ptr(sa), len(shapes), _ptr(sh), pp, np_,
+                                                               float(bound), xf.shape[1] if xf is not None else 0, _ptr(xf), C.c_void_p(hist_ptr),
+                                                               C.c_void_p(records_ptr) if records_ptr else None,
+                                                               C.c_void_p(stream) if stream else None,
+                                                               C.byref(st) if st is not None else None), "bf_render_deform_batch_device")
         return st
 
     def trace_closest(self, rays):

@@ -51,6 +51,13 @@ extern "C" float bfk_host_cos(float x);
 extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, uint32_t n_tri_rows, const float4 *nodes0,
                                            float4 *nodes, float4 *qnodes, uint32_t n_nodes, const float4 *wnodes0, float4 *wnodes,
                                            uint32_t n_wchildren, const float *d, hipStream_t stream);
+extern "C" hipError_t bfk_launch_deform_tris(const uint4 *corners, const bfd::DDeformSrc *src, const float4 *tris0, float4 *tris, const float4 *nrm0,
+                                             float4 *nrm, uint32_t n_tris, const float *xf, uint32_t n_versions, uint64_t vstride,
+                                             uint32_t xf_stride, float bound, uint32_t *bad, hipStream_t stream);
+extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
+                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes,
+                                       const uint32_t *lvl16, const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad,
+                                       uint32_t n_versions, uint64_t vstride, hipStream_t stream);
 extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
                                        const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
                                        const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
@@ -162,6 +169,16 @@ inline V3 normalize(V3 a) {
 // clones (bf_scene_clone), freed with the last of them.
 struct bf_geometry {
     std::vector<void *> owned;
+    // vertex updates (bf_scene_update_vertices): what every mesh shape was created with, and the device corner
+    // table built from it at the first update of any handle that shares these arrays (one uint4 per triangle slot in leaf order:
+    // the slot's three vertex indices within its shape, then the shape)
+    struct MeshTopo {
+        uint32_t n_vertices = 0, n_faces = 0, prim0 = 0;
+        bool has_normals = false;
+        std::vector<uint32_t> indices;
+    };
+    std::vector<MeshTopo> topo;            // per shape (non-mesh shapes: empty)
+    uint4 *corners = nullptr;
     ~bf_geometry() {
         for (void *p : owned) (void) hipFree(p);
     }
@@ -281,6 +298,23 @@ struct bf_scene {
     // of the previous call like every other write of the handle (order_after_last)
     float4 *motion_arena = nullptr;
     size_t motion_cap = 0;                      // float4 rows allocated
+    // bf_scene_update_vertices: the update writes the handle's BASE rows (tris0 / normals0), which must then be the
+    // handle's own allocations, and runs the handle's latest pose on top of them.  pose_kind: 0 none, 1 a translation, 2 a rigid
+    // table; pose_xf: the table as bfk_launch_rigid reads it (16 floats per shape).  Once `deformed`, the boxes of nodes0 / wnodes0
+    // no longer bound the base rows (only their topology is read), so translations run through the refit too.
+    bool base_private = false, normals0_private = false, deformed = false;
+    int pose_kind = 0;
+    std::vector<float> pose_xf;
+    // the device forms' violation counter ([0] slots refused, [1] a refused shape + 1), its pinned mirror and the event behind the
+    // copy that follows every device-form gather
+    uint32_t *deform_bad = nullptr, *deform_bad_host = nullptr;
+    hipEvent_t deform_ev = nullptr;
+    mutable bool deform_pending = false;
+    mutable uint32_t deform_reported = 0;       // of the device count, how much has been reported already
+    // the host form's upload buffer (pinned + device mirror), grown on demand; vtx_ev: behind the gather that read it last
+    void *vtx_host = nullptr, *vtx_dev = nullptr;
+    size_t vtx_cap = 0;
+    hipEvent_t vtx_ev = nullptr;
     // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
     std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
     std::vector<float *> array_dev;
@@ -402,6 +436,9 @@ struct DeviceGuard {
 static bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
 static bf_status mark_last(const bf_scene *scene, hipStream_t stream);
 static bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
+static bf_status apply_pose(bf_scene *scene, hipStream_t stream);
+static bf_status refit_prepare(bf_scene *scene, hipStream_t stream);
+static bf_status deform_report(const bf_scene *scene, bool wait);
 
 extern "C" {
 
@@ -459,6 +496,15 @@ bf_status bf_scene_destroy(bf_scene *s) {
     if (s->counters) (void) hipFree(s->counters);
     if (s->tab_pool) (void) hipFree(s->tab_pool);
     if (s->motion_arena) (void) hipFree(s->motion_arena);
+    if (s->deform_bad) (void) hipFree(s->deform_bad);
+    if (s->deform_bad_host) (void) hipHostFree(s->deform_bad_host);
+    if (s->deform_ev) (void) hipEventDestroy(s->deform_ev);
+    if (s->vtx_ev) {
+        (void) hipEventSynchronize(s->vtx_ev);
+        (void) hipEventDestroy(s->vtx_ev);
+    }
+    if (s->vtx_host) (void) hipHostFree(s->vtx_host);
+    if (s->vtx_dev) (void) hipFree(s->vtx_dev);
     for (auto &st : s->stage) {
         if (st.ev) {
             (void) hipEventSynchronize(st.ev);
@@ -877,6 +923,18 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     sc->adc_f = flat.window_f ? flat.window_f : flat.sensor.f_bins;
     sc->film_h = desc->sensor.film_height;
     sc->origin_scale_built = origin_scale;
+    // what a vertex update needs of the description later (bf_scene_update_vertices): every mesh's sizes, first primitive and indices
+    sc->geom->topo.resize(desc->n_shapes);
+    for (uint32_t i = 0; i < desc->n_shapes; ++i) {
+        const bf_shape &s = desc->shapes[i];
+        if (s.type != BF_SHAPE_MESH || !s.n_faces) continue;
+        bf_geometry::MeshTopo &tp = sc->geom->topo[i];
+        tp.n_vertices = s.n_vertices;
+        tp.n_faces = s.n_faces;
+        tp.has_normals = s.normals != nullptr;
+        tp.indices.assign(s.indices, s.indices + 3 * (size_t) s.n_faces);
+    }
+    for (size_t t = meta.size(); t-- > 0;) sc->geom->topo[meta[t].shape].prim0 = meta[t].prim;      // (faces in order: the first one's)
     bf::BVH bvh;
     bf::build_bvh(btris, bvh, origin_scale);
     bf::BVH4 bvh4;
@@ -1221,6 +1279,7 @@ static bf_status own_geometry(bf_scene *scene, hipStream_t stream, const char *w
             scene->tris0 = const_cast<float4 *>(scene->d.tris);
             scene->nodes0 = const_cast<float4 *>(scene->d.nodes);
             scene->wnodes0 = const_cast<float4 *>(scene->d.wnodes);
+            scene->base_private = false;
         }
         scene->d.tris = cp.p[0];
         scene->d.nodes = cp.p[1];
@@ -1238,6 +1297,7 @@ static bf_status own_geometry(bf_scene *scene, hipStream_t stream, const char *w
         scene->tris0 = cp.p[0];
         scene->nodes0 = cp.p[1];
         scene->wnodes0 = cp.p[2];
+        scene->base_private = true;
     }
     return BF_OK;
 }
@@ -1254,8 +1314,26 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
         if (ost == BF_OK) ost = close_sequence(scene, stream);
         if (ost != BF_OK) return ost;
     }
+    if (scene->deformed && !scene->refit.ready) {
+        bf_status rst = refit_prepare(scene, stream);
+        if (rst != BF_OK) return rst;
+    }
     bf_status gst = own_geometry(scene, stream, __func__);
     if (gst != BF_OK) return gst;
+    // the pose a later vertex update runs on top of its new base rows: [I | offset] for every shape
+    scene->pose_kind = 1;
+    scene->pose_xf.assign((size_t) scene->info.n_shapes * 16, 0.f);
+    for (uint32_t k = 0; k < scene->info.n_shapes; ++k) {
+        float *m = &scene->pose_xf[16 * (size_t) k];
+        m[0] = m[5] = m[10] = m[12] = 1.f;
+        m[3] = offset[0], m[7] = offset[1], m[11] = offset[2];
+    }
+    if (scene->deformed) {
+        // the boxes of nodes0 / wnodes0 are those of the geometry as created, not of the updated base: the same vertices
+        // (fl(v + offset) either way) under re-fitted boxes
+        bf_status pst = apply_pose(scene, stream);
+        return pst != BF_OK ? pst : mark_last(scene, stream);
+    }
     if (scene->normals_moved) {
         // a rigid transform moved the vertex normals: a translation applies to the geometry as created
         HIP_TRY(hipMemcpyAsync(const_cast<float4 *>(scene->d.normals), scene->normals0, (size_t) scene->d.n_tris * 3 * sizeof(float4),
@@ -1449,6 +1527,8 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
             h[16 * k + 13] = h[16 * k + 14] = h[16 * k + 15] = 0.f;
         }
         HIP_TRY(hipMemcpyAsync(rf.xf, h, bytes, hipMemcpyHostToDevice, stream));
+        scene->pose_kind = 2;       // (what a later vertex update runs on top of its new base rows)
+        scene->pose_xf.assign(h, h + (size_t) n_shapes * 16);
         if ((st = stage_release_after(stg, stream)) != BF_OK) return st;
     }
     HIP_TRY(bfk_launch_rigid(scene->tris0, const_cast<float4 *>(scene->d.tris), scene->normals0, const_cast<float4 *>(scene->d.normals),
@@ -1457,6 +1537,247 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
                              const_cast<float4 *>(scene->d.wnodes), rf.lvl16, rf.off16.data(), (uint32_t) rf.off16.size() - 1u, rf.ubox16,
                              2e-7f * oscale, 1u, 0u, 0u, stream));
     scene->normals_moved = scene->d.normals != nullptr;
+    return mark_last(scene, stream);
+}
+
+// ---- vertex updates -------------------------------------------------------------------------------------------
+// The handle's latest pose (pose_kind / pose_xf) over its base rows, by the kernels of bf_scene_transform_meshes.  A translation
+// leaves the vertex normals as the base has them (bf_scene_translate_meshes does).
+static bf_status apply_pose(bf_scene *scene, hipStream_t stream) {
+    bf_scene::Refit &rf = scene->refit;
+    const uint32_t n_shapes = scene->info.n_shapes;
+    if (scene->pose_xf.size() != (size_t) n_shapes * 16) {
+        scene->pose_xf.assign((size_t) n_shapes * 16, 0.f);
+        for (uint32_t k = 0; k < n_shapes; ++k) scene->pose_xf[16 * (size_t) k] = scene->pose_xf[16 * (size_t) k + 5] = scene->pose_xf[16 * (size_t) k + 10] = 1.f;
+    }
+    // ray origins lie on the posed meshes: raise (never lower) the bound the boxes are padded for
+    float oscale = scene->origin_scale_built;
+    for (uint32_t k = 0; k < n_shapes; ++k) {
+        const float *b = &rf.mesh_box[6 * (size_t) k], *m = &scene->pose_xf[16 * (size_t) k];
+        if (!(b[0] <= b[3])) continue;
+        for (int r = 0; r < 3; ++r) {
+            double v = std::fabs((double) m[4 * r + 3]);
+            for (int c = 0; c < 3; ++c) v += std::fabs((double) m[4 * r + c]) * std::max(std::fabs((double) b[c]), std::fabs((double) b[3 + c]));
+            oscale = std::max(oscale, (float) (v * (1.0 + 1e-5)));
+        }
+    }
+    scene->origin_scale_built = oscale;
+    const size_t bytes = (size_t) n_shapes * 16 * sizeof(float);
+    bf_scene::Stage *stg = nullptr;
+    bf_status st = stage_acquire(scene, bytes, &stg);
+    if (st != BF_OK) return st;
+    std::memcpy(stg->host, scene->pose_xf.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(rf.xf, stg->host, bytes, hipMemcpyHostToDevice, stream));
+    if ((st = stage_release_after(stg, stream)) != BF_OK) return st;
+    const bool turn_normals = scene->pose_kind != 1 && scene->normals0 != nullptr;
+    if (!turn_normals && scene->normals0)
+        HIP_TRY(hipMemcpyAsync(const_cast<float4 *>(scene->d.normals), scene->normals0, (size_t) scene->d.n_tris * 3 * sizeof(float4),
+                               hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(bfk_launch_rigid(scene->tris0, const_cast<float4 *>(scene->d.tris), turn_normals ? scene->normals0 : nullptr,
+                             turn_normals ? const_cast<float4 *>(scene->d.normals) : nullptr, scene->d.n_tris, rf.xf, scene->nodes0,
+                             const_cast<float4 *>(scene->d.nodes), const_cast<float4 *>(scene->d.qnodes), scene->d.n_nodes, rf.lvl4, rf.off4.data(),
+                             (uint32_t) rf.off4.size() - 1u, rf.ubox4, scene->wnodes0, const_cast<float4 *>(scene->d.wnodes), rf.lvl16,
+                             rf.off16.data(), (uint32_t) rf.off16.size() - 1u, rf.ubox16, 2e-7f * oscale, 1u, 0u, 0u, stream));
+    scene->normals_moved = scene->pose_kind == 2 && scene->d.normals != nullptr;
+    return BF_OK;
+}
+
+// The corner table (shared with clones, built once from the indices the scene was created with and the prim / shape words of
+// the triangle rows) and this handle's violation counter.
+static bf_status deform_prepare(bf_scene *scene, hipStream_t stream) {
+    bf_geometry &g = *scene->geom;
+    if (!g.corners) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        const float4 *rows = scene->tris0 ? scene->tris0 : scene->d.tris;
+        std::vector<uint32_t> w((size_t) scene->d.n_tris * bfd::kTriStride);       // the .w words: prim, shape, tag per slot
+        HIP_TRY(hipMemcpy2D(w.data(), 4, (const char *) rows + 12, sizeof(float4), 4, w.size(), hipMemcpyDeviceToHost));
+        std::vector<uint4> corners(scene->d.n_tris);
+        for (size_t t = 0; t < corners.size(); ++t) {
+            const uint32_t prim = w[3 * t], shape = w[3 * t + 1];
+            if (shape >= g.topo.size() || prim < g.topo[shape].prim0 || prim - g.topo[shape].prim0 >= g.topo[shape].n_faces)
+                return fail(BF_ERR_DEVICE, "bf_scene_update_vertices: triangle slot %zu names primitive %u of shape %u, which the scene "
+                                           "description does not have", t, prim, shape);
+            const uint32_t *ix = &g.topo[shape].indices[3 * (size_t) (prim - g.topo[shape].prim0)];
+            corners[t] = make_uint4(ix[0], ix[1], ix[2], shape);
+        }
+        void *q = nullptr;
+        HIP_TRY(hipMalloc(&q, corners.size() * sizeof(uint4)));
+        g.owned.push_back(q);
+        HIP_TRY(hipMemcpy(q, corners.data(), corners.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        g.corners = (uint4 *) q;
+        for (bf_geometry::MeshTopo &tp : g.topo) std::vector<uint32_t>().swap(tp.indices);      // the table holds them now
+    }
+    if (!scene->deform_bad) {
+        HIP_TRY(hipMalloc((void **) &scene->deform_bad, 2 * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(scene->deform_bad, 0, 2 * sizeof(uint32_t)));
+        HIP_TRY(hipHostMalloc((void **) &scene->deform_bad_host, 2 * sizeof(uint32_t)));
+        scene->deform_bad_host[0] = scene->deform_bad_host[1] = 0u;
+        HIP_TRY(hipEventCreateWithFlags(&scene->deform_ev, hipEventDisableTiming));
+    }
+    return BF_OK;
+}
+
+// Behind every gather of a device form: the counter on its way to the host.  deform_report() turns a non-zero count into
+// BF_ERR_DEVICE once (bf_scene_sync and renders with stats wait for the copy; a plain render looks only if it has landed).
+static bf_status deform_watch(bf_scene *scene, hipStream_t stream) {
+    HIP_TRY(hipMemcpyAsync(scene->deform_bad_host, scene->deform_bad, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(scene->deform_ev, stream));
+    scene->deform_pending = true;
+    return BF_OK;
+}
+static bf_status deform_report(const bf_scene *scene, bool wait) {
+    if (!scene->deform_pending) return BF_OK;
+    if (wait) {
+        HIP_TRY(hipEventSynchronize(scene->deform_ev));
+    } else if (hipEventQuery(scene->deform_ev) != hipSuccess) {
+        (void) hipGetLastError();
+        return BF_OK;
+    }
+    scene->deform_pending = false;
+    // the device counter only ever grows (nothing clears it under a gather in flight): what is new since the last report
+    const uint32_t total = scene->deform_bad_host[0], shape1 = scene->deform_bad_host[1];
+    const uint32_t n = total - scene->deform_reported;
+    scene->deform_reported = total;
+    if (!n) return BF_OK;
+    return fail(BF_ERR_DEVICE, "a device-form vertex update of this scene gave %u triangles (of shape %u, if not of others too) a corner "
+                               "that is not finite or lies beyond the declared bound: those triangles kept their previous vertices, "
+                               "and every render issued since that update is invalid", n, shape1 ? shape1 - 1u : 0u);
+}
+
+// the checks of one shape of a vertex update; *topo_out = its topology
+static bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who,
+                                    const bf_geometry::MeshTopo **topo_out) {
+    if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", who, shape, scene->info.n_shapes);
+    const bfd::DShape &sh = scene->shapes_host[shape];
+    if (sh.type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", who, shape);
+    if (sh.emitter >= 0)
+        return fail(BF_ERR_UNSUPPORTED, "%s mesh shape %u carries emitter %d (its sampling tables are built from the triangles as "
+                                        "created); create a new scene", who, shape, sh.emitter);
+    const bf_geometry::MeshTopo &tp = scene->geom->topo[shape];
+    if (with_normals && !tp.has_normals)
+        return fail(BF_ERR_INVALID, "%s shape %u was created without vertex normals: it cannot take any", who, shape);
+    *topo_out = &tp;
+    return BF_OK;
+}
+
+// one update with the arrays on the device already; box6: the new base box of the shape
+static bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geometry::MeshTopo &tp, const float *pos_dev,
+                                        const float *nrm_dev, float bound, const float *box6, bool watch, hipStream_t stream) {
+    bf_status st = BF_OK;
+    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
+    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
+    if ((st = own_geometry(scene, stream, "bf_scene_update_vertices")) != BF_OK) return st;
+    const size_t tri_bytes = ((size_t) scene->d.n_tris * bfd::kTriStride + kTriPad) * sizeof(float4), nrm_bytes = (size_t) scene->d.n_tris * 3 * sizeof(float4);
+    auto fresh = [&](size_t bytes, const void *from, float4 **out) -> bf_status {
+        void *q = nullptr;
+        hipError_t he = hipMalloc(&q, bytes);
+        if (he != hipSuccess) return fail(BF_ERR_NOMEM, "bf_scene_update_vertices: hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(he));
+        scene->owned.push_back(q);
+        if (from) HIP_TRY(hipMemcpyAsync(q, from, bytes, hipMemcpyDeviceToDevice, stream));
+        *out = (float4 *) q;
+        return BF_OK;
+    };
+    if (!scene->base_private) {
+        // the base rows are still the arrays shared with clones: this handle's own copy from now on
+        float4 *q = nullptr;
+        if ((st = fresh(tri_bytes, scene->tris0, &q)) != BF_OK) return st;
+        scene->tris0 = q;
+        scene->base_private = true;
+    }
+    if (scene->d.normals && !scene->normals_private) {
+        // as bf_scene_transform_meshes: the rendered normals in an array of the handle's own, the base ones kept beside them
+        float4 *q = nullptr;
+        if ((st = fresh(nrm_bytes, nullptr, &q)) != BF_OK) return st;
+        if (!scene->normals0) scene->normals0 = const_cast<float4 *>(scene->d.normals);
+        scene->d.normals = q;
+        scene->normals_private = true;
+    }
+    if (nrm_dev && !scene->normals0_private) {
+        float4 *q = nullptr;
+        if ((st = fresh(nrm_bytes, scene->normals0, &q)) != BF_OK) return st;
+        scene->normals0 = q;
+        scene->normals0_private = true;
+    }
+    // the per-shape source table: this shape alone deforms
+    const size_t bytes = (size_t) scene->info.n_shapes * sizeof(bfd::DDeformSrc);
+    bf_scene::Stage *stg = nullptr;
+    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
+    std::memset(stg->host, 0, bytes);
+    bfd::DDeformSrc &e = ((bfd::DDeformSrc *) stg->host)[shape];
+    e.pos = pos_dev;
+    e.nrm = nrm_dev;
+    e.nv = tp.n_vertices;
+    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
+    HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, scene->tris0, scene->tris0,
+                                   nrm_dev ? scene->normals0 : nullptr, nrm_dev ? scene->normals0 : nullptr, scene->d.n_tris, nullptr, 1u, 0u, 0u,
+                                   bound, scene->deform_bad, stream));
+    HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel, not only by the copy
+    if (watch && (st = deform_watch(scene, stream)) != BF_OK) return st;
+    std::memcpy(&scene->refit.mesh_box[6 * (size_t) shape], box6, 6 * sizeof(float));
+    scene->deformed = true;
+    return apply_pose(scene, stream);
+}
+
+static bf_status update_enter(bf_scene *scene, hipStream_t stream) {
+    bf_status ost = order_after_last(scene, stream);
+    if (ost == BF_OK) ost = close_sequence(scene, stream);
+    return ost;
+}
+
+bf_status bf_scene_update_vertices(bf_scene *scene, uint32_t shape, const float *positions, const float *normals, void *stream_) {
+    if (!scene || !positions) return fail(BF_ERR_INVALID, "bf_scene_update_vertices: null argument");
+    const bf_geometry::MeshTopo *tp = nullptr;
+    bf_status st = check_deform_shape(scene, shape, normals != nullptr, "bf_scene_update_vertices:", &tp);
+    if (st != BF_OK) return st;
+    const size_t n = 3 * (size_t) tp->n_vertices;
+    const float inf = std::numeric_limits<float>::infinity();
+    float box[6] = {inf, inf, inf, -inf, -inf, -inf};
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i])))
+            return fail(BF_ERR_INVALID, "bf_scene_update_vertices: shape %u: non-finite value at vertex %zu", shape, i / 3);
+        box[i % 3] = std::min(box[i % 3], positions[i]);
+        box[3 + i % 3] = std::max(box[3 + i % 3], positions[i]);
+    }
+    if (scene->d.n_tris == 0 || n == 0) return BF_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    if ((st = update_enter(scene, stream)) != BF_OK) return st;
+    // the caller's arrays through the handle's upload buffer (the staging ring is for small tables): free again on return
+    const size_t bytes = n * sizeof(float) * (normals ? 2 : 1);
+    if (scene->vtx_ev) HIP_TRY(hipEventSynchronize(scene->vtx_ev));      // the previous update's gather may still read it
+    if (scene->vtx_cap < bytes) {
+        if (scene->vtx_host) (void) hipHostFree(scene->vtx_host);
+        if (scene->vtx_dev) (void) hipFree(scene->vtx_dev);
+        scene->vtx_host = scene->vtx_dev = nullptr;
+        scene->vtx_cap = 0;
+        HIP_TRY(hipHostMalloc(&scene->vtx_host, bytes));
+        HIP_TRY(hipMalloc(&scene->vtx_dev, bytes));
+        scene->vtx_cap = bytes;
+    }
+    if (!scene->vtx_ev) HIP_TRY(hipEventCreateWithFlags(&scene->vtx_ev, hipEventDisableTiming));
+    std::memcpy(scene->vtx_host, positions, n * sizeof(float));
+    if (normals) std::memcpy((float *) scene->vtx_host + n, normals, n * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(scene->vtx_dev, scene->vtx_host, bytes, hipMemcpyHostToDevice, stream));
+    st = update_vertices_locked(scene, shape, *tp, (const float *) scene->vtx_dev, normals ? (const float *) scene->vtx_dev + n : nullptr, inf,
+                                box, false, stream);
+    HIP_TRY(hipEventRecord(scene->vtx_ev, stream));
+    if (st != BF_OK) return st;
+    return mark_last(scene, stream);
+}
+
+bf_status bf_scene_update_vertices_device(bf_scene *scene, uint32_t shape, const float *positions_dev, const float *normals_dev, float bound,
+                                          void *stream_) {
+    if (!scene || !positions_dev) return fail(BF_ERR_INVALID, "bf_scene_update_vertices_device: null argument");
+    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(BF_ERR_INVALID, "bf_scene_update_vertices_device: shape %u: bound must be positive and finite", shape);
+    const bf_geometry::MeshTopo *tp = nullptr;
+    bf_status st = check_deform_shape(scene, shape, normals_dev != nullptr, "bf_scene_update_vertices_device:", &tp);
+    if (st != BF_OK) return st;
+    if (scene->d.n_tris == 0 || tp->n_vertices == 0) return BF_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    if ((st = update_enter(scene, stream)) != BF_OK) return st;
+    const float box[6] = {-bound, -bound, -bound, bound, bound, bound};
+    if ((st = update_vertices_locked(scene, shape, *tp, positions_dev, normals_dev, bound, box, true, stream)) != BF_OK) return st;
     return mark_last(scene, stream);
 }
 
@@ -2303,6 +2624,12 @@ static bool lean_profile(const bf_scene *scene, const bf_launch *launch, bool re
 static bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
                                bf_path_record *records_dev, void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0) {
     const uint32_t n_renders = batch ? batch->n_renders : 1u;
+    {
+        // a device-form vertex update whose gather refused triangles (bf_scene_update_vertices_device) is reported by the handle's
+        // next render, once: the render waits for that gather's count (one event, a few bytes) before it enqueues anything
+        bf_status dst = deform_report(scene, true);
+        if (dst != BF_OK) return dst;
+    }
     if (batch) {
         if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
         if (launch->spp && launch->film_width && launch->film_height)
@@ -2591,51 +2918,18 @@ static void add_stats(bf_stats &a, const bf_stats &b) {
     a.n_guard += b.n_guard;
 }
 
-bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_shapes,
-                                        const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
-    if (!scene || !launch || !to_world || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
-    if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: n_renders is 0");
-    if (n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: %u transforms per render for a scene of %u shapes", n_shapes, scene->info.n_shapes);
-    if (launch->flags & BF_FLAG_ROLLING)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: BF_FLAG_ROLLING: a motion batch is one launch sequence of its own");
-    if (launch->spp && launch->film_width && launch->film_height)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: multi-pixel films are rendered one launch at a time");
-    // every render's table is checked before anything is enqueued: a failed call leaves the scene as it was
-    std::vector<uint8_t> moves((size_t) n_renders * n_shapes, 0);
-    for (uint32_t k = 0; k < n_renders; ++k) {
-        char who[96];
-        std::snprintf(who, sizeof(who), "bf_render_motion_batch_device: render %u,", k);
-        bf_status cst = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves.data() + (size_t) n_shapes * k);
-        if (cst != BF_OK) return cst;
-    }
+// The part every batch of geometry versions shares (motion batches, deform batches): chunks of renders whose versions fit the arena
+// budget (BF_MOTION_BATCH_MB; at least one render per chunk), the arena grown on demand, and per chunk prepare(k0, kc, a, L) — which
+// enqueues the chunk's versions into the arena `a` — followed by the chunk's renders with the handle's kernel arguments pointing
+// at version 0.  `fn` names the caller in error text.
+extern "C++" template <class Prepare>
+static bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, float *hist_dev,
+                                 bf_path_record *records_dev, void *stream_, bf_stats *stats_out, const char *fn, Prepare &&prepare) {
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
     const uint64_t n_chan = bf_launch_channels(launch);
-    if (scene->d.n_tris == 0) {
-        // nothing to move: an ordinary batch
-        bf_batch b = {n_renders, seeds, nullptr};
-        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
-    }
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
-    bf_status st = BF_OK;
-    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
-    // the pristine rows: the handle's own copies once it has moved, else the arrays it renders (a clone's snapshot included)
-    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
-    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
-    const float4 *normals0 = scene->normals0 ? scene->normals0 : scene->d.normals;
-    // one padding bound for every version of the call: the handle's, raised to cover all moved meshes of all renders
-    float oscale = scene->origin_scale_built;
-    for (uint32_t k = 0; k < n_renders; ++k)
-        oscale = moved_origin_scale(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, moves.data() + (size_t) n_shapes * k, oscale);
-    // chunks of renders whose versions fit the arena budget (at least one render per chunk)
     const MotionLayout L = motion_layout(scene);
     if (L.rows > UINT32_MAX)
-        return fail(BF_ERR_UNSUPPORTED, "bf_render_motion_batch_device: one geometry version of this scene is %zu float4 rows (at most 2^32 - 1)", L.rows);
+        return fail(BF_ERR_UNSUPPORTED, "%s: one geometry version of this scene is %zu float4 rows (at most 2^32 - 1)", fn, L.rows);
     size_t budget_mb = kMotionBatchMB;
     if (const char *e = getenv("BF_MOTION_BATCH_MB")) {
         char *end = nullptr;
@@ -2656,8 +2950,8 @@ bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch
         void *q = nullptr;
         hipError_t he = hipMalloc(&q, need * sizeof(float4));
         if (he != hipSuccess)
-            return fail(BF_ERR_NOMEM, "bf_render_motion_batch_device: hipMalloc(%zu bytes) for %u geometry versions: %s (BF_MOTION_BATCH_MB "
-                                      "caps the arena)", need * sizeof(float4), per_chunk, hipGetErrorString(he));
+            return fail(BF_ERR_NOMEM, "%s: hipMalloc(%zu bytes) for %u geometry versions: %s (BF_MOTION_BATCH_MB caps the arena)", fn,
+                        need * sizeof(float4), per_chunk, hipGetErrorString(he));
         scene->motion_arena = (float4 *) q;
         scene->motion_cap = need;
     }
@@ -2668,31 +2962,11 @@ bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch
     view.nodes = a + L.nodes;
     view.wnodes = scene->d.wnodes ? a + L.wnodes : nullptr;
     view.qnodes = scene->d.qnodes ? a + L.qnodes : nullptr;
-    const bf_scene::Refit &rf = scene->refit;
     if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
     for (uint32_t k0 = 0; k0 < n_renders; k0 += per_chunk) {
         const uint32_t kc = std::min(per_chunk, n_renders - k0);
-        {
-            // the chunk's transform tables (bfk_launch_rigid: 16 floats per shape, word 12 = the shape moves)
-            const size_t bytes = (size_t) kc * n_shapes * 16 * sizeof(float);
-            bf_scene::Stage *stg = nullptr;
-            if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
-            float *h = (float *) stg->host;
-            for (uint32_t v = 0; v < kc; ++v)
-                for (uint32_t k = 0; k < n_shapes; ++k) {
-                    const size_t r = (size_t) (k0 + v) * n_shapes + k;
-                    float *o = h + 16 * ((size_t) v * n_shapes + k);
-                    std::memcpy(o, to_world + 12 * r, 12 * sizeof(float));
-                    o[12] = moves[r] ? 1.f : 0.f;
-                    o[13] = o[14] = o[15] = 0.f;
-                }
-            if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
-            HIP_TRY(bfk_launch_rigid(tris0, a + L.tris, normals0, scene->d.normals ? a + L.normals : nullptr, scene->d.n_tris, (const float *) stg->dev,
-                                     nodes0, a + L.nodes, scene->d.qnodes ? a + L.qnodes : nullptr, scene->d.n_nodes, rf.lvl4, rf.off4.data(),
-                                     (uint32_t) rf.off4.size() - 1u, a + L.ubox4, wnodes0, scene->d.wnodes ? a + L.wnodes : nullptr, rf.lvl16,
-                                     rf.off16.data(), (uint32_t) rf.off16.size() - 1u, a + L.ubox16, 2e-7f * oscale, kc, L.rows, n_shapes * 16u,
-                                     stream));
-        }
+        bf_status st = prepare(k0, kc, a, L);
+        if (st != BF_OK) return st;
         bf_batch b = {kc, seeds ? seeds + k0 : nullptr, nullptr};
         bf_stats cs;
         {
@@ -2704,6 +2978,186 @@ bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch
         if (stats_out) add_stats(*stats_out, cs);
     }
     return BF_OK;
+}
+
+bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_shapes,
+                                        const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
+    if (!scene || !launch || !to_world || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: n_renders is 0");
+    if (n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: %u transforms per render for a scene of %u shapes", n_shapes, scene->info.n_shapes);
+    if (launch->flags & BF_FLAG_ROLLING)
+        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: BF_FLAG_ROLLING: a motion batch is one launch sequence of its own");
+    if (launch->spp && launch->film_width && launch->film_height)
+        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: multi-pixel films are rendered one launch at a time");
+    // every render's table is checked before anything is enqueued: a failed call leaves the scene as it was
+    std::vector<uint8_t> moves((size_t) n_renders * n_shapes, 0);
+    for (uint32_t k = 0; k < n_renders; ++k) {
+        char who[96];
+        std::snprintf(who, sizeof(who), "bf_render_motion_batch_device: render %u,", k);
+        bf_status cst = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves.data() + (size_t) n_shapes * k);
+        if (cst != BF_OK) return cst;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    if (scene->d.n_tris == 0) {
+        // nothing to move: an ordinary batch
+        bf_batch b = {n_renders, seeds, nullptr};
+        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
+    }
+    {
+        bf_status ost = order_after_last(scene, stream);
+        if (ost == BF_OK) ost = close_sequence(scene, stream);
+        if (ost != BF_OK) return ost;
+    }
+    bf_status st = BF_OK;
+    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
+    // the pristine rows: the handle's own copies once it has moved, else the arrays it renders (a clone's snapshot included)
+    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
+    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
+    const float4 *normals0 = scene->normals0 ? scene->normals0 : scene->d.normals;
+    // one padding bound for every version of the call: the handle's, raised to cover all moved meshes of all renders
+    float oscale = scene->origin_scale_built;
+    for (uint32_t k = 0; k < n_renders; ++k)
+        oscale = moved_origin_scale(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, moves.data() + (size_t) n_shapes * k, oscale);
+    const bf_scene::Refit &rf = scene->refit;
+    return render_versions(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, "bf_render_motion_batch_device",
+                           [&](uint32_t k0, uint32_t kc, float4 *a, const MotionLayout &L) -> bf_status {
+        // the chunk's transform tables (bfk_launch_rigid: 16 floats per shape, word 12 = the shape moves)
+        const size_t bytes = (size_t) kc * n_shapes * 16 * sizeof(float);
+        bf_scene::Stage *stg = nullptr;
+        bf_status pst = stage_acquire(scene, bytes, &stg);
+        if (pst != BF_OK) return pst;
+        float *h = (float *) stg->host;
+        for (uint32_t v = 0; v < kc; ++v)
+            for (uint32_t k = 0; k < n_shapes; ++k) {
+                const size_t r = (size_t) (k0 + v) * n_shapes + k;
+                float *o = h + 16 * ((size_t) v * n_shapes + k);
+                std::memcpy(o, to_world + 12 * r, 12 * sizeof(float));
+                o[12] = moves[r] ? 1.f : 0.f;
+                o[13] = o[14] = o[15] = 0.f;
+            }
+        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
+        HIP_TRY(bfk_launch_rigid(tris0, a + L.tris, normals0, scene->d.normals ? a + L.normals : nullptr, scene->d.n_tris, (const float *) stg->dev,
+                                 nodes0, a + L.nodes, scene->d.qnodes ? a + L.qnodes : nullptr, scene->d.n_nodes, rf.lvl4, rf.off4.data(),
+                                 (uint32_t) rf.off4.size() - 1u, a + L.ubox4, wnodes0, scene->d.wnodes ? a + L.wnodes : nullptr, rf.lvl16,
+                                 rf.off16.data(), (uint32_t) rf.off16.size() - 1u, a + L.ubox16, 2e-7f * oscale, kc, L.rows, n_shapes * 16u,
+                                 stream));
+        return BF_OK;
+    });
+}
+
+// bf_render_deform_batch_device: the motion batch with a vertex gather in front.  Version k = the deforming shapes
+// from slice k of their arrays, every other mesh from the handle's base rows, then to_world[k] (absolute; NULL: none), in ONE pass
+// over the rows (bf_deform_tris_kernel applies rigid_apply to what it gathered: the arithmetic of an update followed by a
+// transform call), then the level kernels with the version dimension.  Arena, chunking and rendering as the motion batch.
+bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_deform,
+                                        const uint32_t *shapes, const float *const *positions_dev, const float *const *normals_dev, float bound,
+                                        uint32_t n_shapes, const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_,
+                                        bf_stats *stats_out) {
+    const char *fn = "bf_render_deform_batch_device:";
+    if (!scene || !launch || !hist_dev || (n_deform && (!shapes || !positions_dev))) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
+    if (to_world && n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
+    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a deform batch is one launch sequence of its own", fn);
+    if (launch->spp && launch->film_width && launch->film_height)
+        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
+    if (n_deform && (!(bound > 0.f) || !std::isfinite(bound))) return fail(BF_ERR_INVALID, "%s bound must be positive and finite", fn);
+    n_shapes = scene->info.n_shapes;
+    std::vector<bfd::DDeformSrc> src(n_shapes);
+    std::memset(src.data(), 0, src.size() * sizeof(bfd::DDeformSrc));
+    for (uint32_t j = 0; j < n_deform; ++j) {
+        const bf_geometry::MeshTopo *tp = nullptr;
+        const float *nj = normals_dev ? normals_dev[j] : nullptr;
+        bf_status cst = check_deform_shape(scene, shapes[j], nj != nullptr, fn, &tp);
+        if (cst != BF_OK) return cst;
+        if (!positions_dev[j]) return fail(BF_ERR_INVALID, "%s shape %u: null positions", fn, shapes[j]);
+        if (src[shapes[j]].pos) return fail(BF_ERR_INVALID, "%s shape %u is listed twice", fn, shapes[j]);
+        src[shapes[j]].pos = positions_dev[j];
+        src[shapes[j]].nrm = nj;
+        src[shapes[j]].nv = tp->n_vertices;
+    }
+    std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
+    for (uint32_t k = 0; to_world && k < n_renders; ++k) {
+        char who[96];
+        std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
+        bf_status cst = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves.data() + (size_t) n_shapes * k);
+        if (cst != BF_OK) return cst;
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    if (scene->d.n_tris == 0) {
+        bf_batch b = {n_renders, seeds, nullptr};
+        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
+    }
+    {
+        bf_status ost = order_after_last(scene, stream);
+        if (ost == BF_OK) ost = close_sequence(scene, stream);
+        if (ost != BF_OK) return ost;
+    }
+    bf_status st = BF_OK;
+    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
+    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
+    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
+    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
+    const float4 *normals0 = scene->normals0 ? scene->normals0 : scene->d.normals;
+    // one padding bound for every version: the handle's, raised to cover every mesh of every render where it stands then (a
+    // deforming shape's base box is [-bound, bound]^3 for the call)
+    bf_scene::Refit &rf = scene->refit;
+    float oscale = scene->origin_scale_built;
+    {
+        const std::vector<float> kept = rf.mesh_box;
+        std::vector<uint8_t> all(n_shapes, 1);
+        static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        std::vector<float> id((size_t) 12 * n_shapes);
+        for (uint32_t k = 0; k < n_shapes; ++k) std::memcpy(&id[12 * (size_t) k], ident, sizeof(ident));
+        for (uint32_t k = 0; k < n_shapes; ++k)
+            if (src[k].pos)
+                for (int a = 0; a < 3; ++a) rf.mesh_box[6 * (size_t) k + a] = -bound, rf.mesh_box[6 * (size_t) k + 3 + a] = bound;
+        oscale = moved_origin_scale(scene, n_shapes, id.data(), all.data(), oscale);
+        for (uint32_t k = 0; to_world && k < n_renders; ++k)
+            oscale = moved_origin_scale(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, moves.data() + (size_t) n_shapes * k, oscale);
+        rf.mesh_box = kept;      // the handle's own base is not touched
+    }
+    st = render_versions(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, "bf_render_deform_batch_device",
+                         [&](uint32_t k0, uint32_t kc, float4 *a, const MotionLayout &L) -> bf_status {
+        // the chunk's tables: the sources advanced to slice k0, then (if any) the transforms as bfk_launch_rigid reads them
+        const size_t src_bytes = (src.size() * sizeof(bfd::DDeformSrc) + 15) & ~size_t(15);
+        const size_t bytes = src_bytes + (to_world ? (size_t) kc * n_shapes * 16 * sizeof(float) : 0);
+        bf_scene::Stage *stg = nullptr;
+        bf_status pst = stage_acquire(scene, bytes, &stg);
+        if (pst != BF_OK) return pst;
+        bfd::DDeformSrc *hs = (bfd::DDeformSrc *) stg->host;
+        for (uint32_t k = 0; k < n_shapes; ++k) {
+            hs[k] = src[k];
+            if (hs[k].pos) hs[k].pos += (size_t) k0 * 3 * hs[k].nv;
+            if (hs[k].nrm) hs[k].nrm += (size_t) k0 * 3 * hs[k].nv;
+        }
+        float *h = (float *) ((char *) stg->host + src_bytes);
+        for (uint32_t v = 0; to_world && v < kc; ++v)
+            for (uint32_t k = 0; k < n_shapes; ++k) {
+                const size_t r = (size_t) (k0 + v) * n_shapes + k;
+                float *o = h + 16 * ((size_t) v * n_shapes + k);
+                std::memcpy(o, to_world + 12 * r, 12 * sizeof(float));
+                o[12] = moves[r] ? 1.f : 0.f;
+                o[13] = o[14] = o[15] = 0.f;
+            }
+        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
+        HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, tris0, a + L.tris, normals0,
+                                       scene->d.normals ? a + L.normals : nullptr, scene->d.n_tris,
+                                       to_world ? (const float *) ((const char *) stg->dev + src_bytes) : nullptr, kc, L.rows, n_shapes * 16u,
+                                       bound, scene->deform_bad, stream));
+        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernel
+        HIP_TRY(bfk_launch_refit(a + L.tris, nodes0, a + L.nodes, scene->d.qnodes ? a + L.qnodes : nullptr, scene->d.n_nodes, rf.lvl4,
+                                 rf.off4.data(), (uint32_t) rf.off4.size() - 1u, a + L.ubox4, wnodes0, scene->d.wnodes ? a + L.wnodes : nullptr,
+                                 rf.lvl16, rf.off16.data(), (uint32_t) rf.off16.size() - 1u, a + L.ubox16, 2e-7f * oscale, kc, L.rows, stream));
+        return BF_OK;
+    });
+    if (st != BF_OK || !n_deform) return st;
+    // the violation count of all chunks travels to the host behind the last one; a batch with stats waits for it and reports itself
+    if ((st = deform_watch(scene, stream)) != BF_OK) return st;
+    return stats_out ? deform_report(scene, true) : BF_OK;
 }
 
 bf_status bf_render_device(const bf_scene *scene, const bf_launch *launch, float *hist_dev, bf_path_record *records_dev,
@@ -2759,7 +3213,7 @@ bf_status bf_scene_sync(bf_scene *scene) {
     bf_status gst = read_guards(scene, &lost, &refused);
     if (gst != BF_OK) return gst;
     if (lost || refused) return wf_guard_error(lost, refused);
-    return BF_OK;
+    return deform_report(scene, true);
 }
 
 /* test hook (not part of the ABI): pre-load the sticky guard word, as if wf_trace had dropped `n` rays */
@@ -3107,6 +3561,64 @@ bf_status bf_render_motion_batch(bf_scene *scene, const bf_launch *launch, uint3
     return render_host_with(scene, launch, n_renders, hist_out, records_out, stats_out, [&](float *h, bf_path_record *r, bf_stats *st) {
         return bf_render_motion_batch_device(scene, launch, n_renders, seeds, n_shapes, to_world, h, r, nullptr, st);
     });
+}
+
+bf_status bf_render_deform_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_deform,
+                                 const uint32_t *shapes, const float *const *positions, const float *const *normals, uint32_t n_shapes,
+                                 const float *to_world, float *hist_out, bf_path_record *records_out, bf_stats *stats_out) {
+    const char *fn = "bf_render_deform_batch:";
+    if (!scene || (n_deform && (!shapes || !positions))) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
+    // the host arrays are checked here (finite; their largest |coordinate| is the bound the device form is given), the rest there
+    std::vector<size_t> count(n_deform, 0);
+    float bound = 0.f;
+    for (uint32_t j = 0; j < n_deform; ++j) {
+        const bf_geometry::MeshTopo *tp = nullptr;
+        const float *nj = normals ? normals[j] : nullptr;
+        bf_status cst = check_deform_shape(scene, shapes[j], nj != nullptr, fn, &tp);
+        if (cst != BF_OK) return cst;
+        if (!positions[j]) return fail(BF_ERR_INVALID, "%s shape %u: null positions", fn, shapes[j]);
+        count[j] = (size_t) n_renders * 3 * tp->n_vertices;
+        for (size_t i = 0; i < count[j]; ++i) {
+            if (!std::isfinite(positions[j][i]) || (nj && !std::isfinite(nj[i])))
+                return fail(BF_ERR_INVALID, "%s render %zu, shape %u: non-finite value at vertex %zu", fn, i / (3 * (size_t) tp->n_vertices), shapes[j],
+                            (i / 3) % tp->n_vertices);
+            bound = std::max(bound, std::fabs(positions[j][i]));
+        }
+    }
+    bound = std::max(bound, std::numeric_limits<float>::min());
+    DeviceGuard on_device(scene->device);
+    std::vector<void *> tmp;
+    std::vector<const float *> dpos(n_deform, nullptr), dnrm(n_deform, nullptr);
+    auto cleanup = [&]() {
+        for (void *p : tmp) (void) hipFree(p);
+    };
+    auto up = [&](const float *from, size_t n, const float **out) -> hipError_t {
+        *out = nullptr;
+        if (!from || !n) return hipSuccess;
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, n * sizeof(float));
+        if (e != hipSuccess) return e;
+        tmp.push_back(q);
+        *out = (const float *) q;
+        return hipMemcpy(q, from, n * sizeof(float), hipMemcpyHostToDevice);
+    };
+    for (uint32_t j = 0; j < n_deform; ++j) {
+        hipError_t e = up(positions[j], count[j], &dpos[j]);
+        if (e == hipSuccess && normals) e = up(normals[j], count[j], &dnrm[j]);
+        if (e != hipSuccess) {
+            cleanup();
+            return fail(BF_ERR_NOMEM, "%s shape %u: %s", fn, shapes[j], hipGetErrorString(e));
+        }
+        if (!dpos[j]) dpos[j] = (const float *) (uintptr_t) 16;      // (a mesh without vertices: never read)
+    }
+    bf_status st = render_host_with(scene, launch, n_renders, hist_out, records_out, stats_out, [&](float *h, bf_path_record *r, bf_stats *s) {
+        return bf_render_deform_batch_device(scene, launch, n_renders, seeds, n_deform, shapes, dpos.data(), normals ? dnrm.data() : nullptr, bound,
+                                             n_shapes, to_world, h, r, nullptr, s);
+    });
+    (void) hipDeviceSynchronize();      // the renders read the arrays freed below
+    cleanup();
+    return st;
 }
 
 bf_status bf_render(const bf_scene *scene, const bf_launch *launch, float *hist_out, bf_path_record *records_out,

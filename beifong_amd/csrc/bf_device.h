@@ -195,6 +195,16 @@ struct DRoll {
     uint32_t pad;
 };
 static_assert(sizeof(DRoll) == 88, "descriptor ring entry");
+// One shape's entry of a vertex update (bf_scene_update_vertices, bf_render_deform_batch_device; bf_deform_tris_kernel):
+// where the caller's arrays of the shape lie on the device.  pos == nullptr: the shape does not deform in this call.
+struct DDeformSrc {
+    const float *pos;           // [n_versions][3 * nv]
+    const float *nrm;           // the same shape, or nullptr: the base normals stay
+    uint32_t nv;                // vertices of the shape (floats per version = 3 nv)
+    uint32_t pad;
+};
+static_assert(sizeof(DDeformSrc) == 24, "per-shape table of bf_deform_tris_kernel");
+
 constexpr uint32_t kRollRing = 256;    // renders per sequence (descriptor ring; the host flushes a longer one in between)
 constexpr uint32_t kRollWindow = 4;    // newest renders whose histogram blocks a workgroup privatises in LDS; older ones take global atomics
 constexpr uint32_t kRollBase = 32;     // newest renders whose five BASE channels (X, Y, Z, alpha, weight: one address each per render, so

@@ -963,15 +963,11 @@ BF_NS_END  // namespace bfd
 // row count that bf_scene_create derived from it stay valid.  n_versions > 1 (bf_render_motion_batch_device): every launch covers
 // all versions at once (grid y = version; the outputs and scratch of version v lie v * vstride float4 rows after version 0's, its
 // transforms v * xf_stride floats after the first table), so K versions cost the launches of one.
-extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
-                                       const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
-                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
-                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
-                                       uint64_t vstride, uint32_t xf_stride, hipStream_t stream) {
-    if (n_tris == 0 || n_versions == 0) return hipSuccess;
-    if (n_versions > 65535u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bfd::bf_rigid_tris_kernel, dim3((n_tris + 255u) / 256u, n_versions), dim3(256), 0, stream, tris0, tris, nrm0, nrm, n_tris,
-                       xf, vstride, xf_stride);
+// steps 2 and 3 alone: both trees re-fitted over the triangle rows `tris` holds already, then the re-quantisation
+static hipError_t launch_refit_levels(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes,
+                                      const uint32_t *lvl4, const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0,
+                                      float4 *wnodes, const uint32_t *lvl16, const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16,
+                                      float abs_pad, uint32_t n_versions, uint64_t vstride, hipStream_t stream) {
     for (uint32_t d = n_lvl4; d-- > 0;) {
         const uint32_t n = lvl4_off[d + 1] - lvl4_off[d];
         if (n) hipLaunchKernelGGL(bfd::bf_refit4_kernel, dim3((4u * n + 255u) / 256u, n_versions), dim3(256), 0, stream, lvl4 + lvl4_off[d], n, nodes0,
@@ -986,6 +982,126 @@ extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const 
         hipLaunchKernelGGL(bfd::bf_requant_kernel, dim3((n_nodes + 255u) / 256u, n_versions), dim3(256), 0, stream, (const float4 *) nodes, qnodes,
                            n_nodes, vstride);
     return hipGetLastError();
+}
+
+extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
+                                       const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
+                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
+                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
+                                       uint64_t vstride, uint32_t xf_stride, hipStream_t stream) {
+    if (n_tris == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bfd::bf_rigid_tris_kernel, dim3((n_tris + 255u) / 256u, n_versions), dim3(256), 0, stream, tris0, tris, nrm0, nrm, n_tris,
+                       xf, vstride, xf_stride);
+    return launch_refit_levels(tris, nodes0, nodes, qnodes, n_nodes, lvl4, lvl4_off, n_lvl4, ubox4, wnodes0, wnodes, lvl16, lvl16_off, n_lvl16,
+                               ubox16, abs_pad, n_versions, vstride, stream);
+}
+
+BF_NS_BEGIN
+// bf_scene_update_vertices / bf_render_deform_batch_device.  One thread per triangle slot (leaf order), grid y =
+// version, `vstride` as bf_rigid_tris_kernel.  corners[slot] = the slot's three vertex indices within its shape and the shape's
+// index; src[shape] says where the caller's arrays of that shape lie (pos == nullptr: the shape does not deform).
+//   deforming slot : the row is the three positions (and, where given, the three normals) of version v, float for float
+//   any other slot : the base row
+// then, where `xf` is given (a batch: per version and shape, as bf_rigid_tris_kernel), the shape's rigid [R | t] by rigid_apply —
+// the arithmetic of a transform call on the gathered rows.  The .w words are the base's.  `tris` may be `tris0` itself (the
+// single update writes the base in place, one version): every lane reads its own rows before it writes them.
+// Every gathered position must be finite with |c| <= bound and every gathered normal finite; a slot that fails keeps its base
+// row, and its wave adds the number of such slots to bad[0] with ONE atomic (bad[1] = some failing shape + 1).
+__global__ __launch_bounds__(256) void bf_deform_tris_kernel(const uint4 *__restrict__ corners, const DDeformSrc *__restrict__ src,
+                                                             const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm,
+                                                             uint32_t n_tris, const float *__restrict__ xf, uint64_t vstride,
+                                                             uint32_t xf_stride, float bound, uint32_t *__restrict__ bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, ver = blockIdx.y;
+    bool viol = false;
+    uint32_t shape = 0;
+    if (i < n_tris) {
+        const uint4 c = corners[i];                       // one 16-byte load
+        shape = c.w;
+        const DDeformSrc s = src[shape];
+        const float4 *b = tris0 + kTriStride * i;
+        float4 *o = tris + vstride * ver + kTriStride * i;
+        float4 v[3] = {b[0], b[1], b[2]};
+        float4 n[3];
+        const float4 *nb = nrm0 + 3u * i;
+        float4 *no = nrm ? nrm + vstride * ver + 3u * i : nullptr;
+        if (nrm)
+            for (int j = 0; j < 3; ++j) n[j] = nb[j];
+        bool changed = false;
+        if (s.pos) {
+            // the nine (eighteen) scattered loads are issued before the first use
+            const float *p = s.pos + (size_t) ver * 3u * s.nv;
+            const float *p0 = p + 3u * c.x, *p1 = p + 3u * c.y, *p2 = p + 3u * c.z;
+            const float g[9] = {p0[0], p0[1], p0[2], p1[0], p1[1], p1[2], p2[0], p2[1], p2[2]};
+            float h[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            const bool with_n = nrm && s.nrm;
+            if (with_n) {
+                const float *q = s.nrm + (size_t) ver * 3u * s.nv;
+                const float *q0 = q + 3u * c.x, *q1 = q + 3u * c.y, *q2 = q + 3u * c.z;
+                h[0] = q0[0], h[1] = q0[1], h[2] = q0[2], h[3] = q1[0], h[4] = q1[1], h[5] = q1[2], h[6] = q2[0], h[7] = q2[1], h[8] = q2[2];
+            }
+            bool ok = true;
+            for (int k = 0; k < 9; ++k) ok = ok && (__builtin_fabsf(g[k]) <= bound) && (__builtin_fabsf(h[k]) < BF_INF);      // false for NaN
+            if (ok) {
+                for (int j = 0; j < 3; ++j) {
+                    v[j] = make_float4(g[3 * j], g[3 * j + 1], g[3 * j + 2], v[j].w);
+                    if (with_n) n[j] = make_float4(h[3 * j], h[3 * j + 1], h[3 * j + 2], n[j].w);
+                }
+                changed = true;
+            } else {
+                viol = true;
+            }
+        }
+        if (xf) {
+            const float *m = xf + (size_t) xf_stride * ver + 16u * shape;
+            if (m[12] != 0.f) {
+                for (int j = 0; j < 3; ++j) {
+                    const float3 p = rigid_apply(m, v[j].x, v[j].y, v[j].z, true);
+                    v[j] = make_float4(p.x, p.y, p.z, v[j].w);
+                    if (nrm) {
+                        const float3 r = rigid_apply(m, n[j].x, n[j].y, n[j].z, false);
+                        n[j] = make_float4(r.x, r.y, r.z, n[j].w);
+                    }
+                }
+                changed = true;
+            }
+        }
+        if (changed || o != b) {
+            o[0] = v[0];
+            o[1] = v[1];
+            o[2] = v[2];
+        }
+        if (nrm && (changed || no != nb))
+            for (int j = 0; j < 3; ++j) no[j] = n[j];
+    }
+    const unsigned long long vm = __ballot(viol);
+    if (vm != 0ull && viol && (__ffsll(vm) - 1) == (int) (threadIdx.x & 63u)) {
+        atomicAdd(bad, (uint32_t) __popcll(vm));
+        bad[1] = shape + 1u;
+    }
+}
+BF_NS_END  // namespace bfd
+
+// The vertex gather alone (bf_scene_update_vertices: the output is the handle's base, bfk_launch_rigid follows with its pose) ...
+extern "C" hipError_t bfk_launch_deform_tris(const uint4 *corners, const bfd::DDeformSrc *src, const float4 *tris0, float4 *tris, const float4 *nrm0,
+                                             float4 *nrm, uint32_t n_tris, const float *xf, uint32_t n_versions, uint64_t vstride,
+                                             uint32_t xf_stride, float bound, uint32_t *bad, hipStream_t stream) {
+    if (n_tris == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bfd::bf_deform_tris_kernel, dim3((n_tris + 255u) / 256u, n_versions), dim3(256), 0, stream, corners, src, tris0, tris, nrm0,
+                       nrm, n_tris, xf, vstride, xf_stride, bound, bad);
+    return hipGetLastError();
+}
+// ... and the refit of both trees behind it (bf_render_deform_batch_device: gather + rigid transform in one pass over the rows, then
+// the level kernels with the version dimension, as bfk_launch_rigid runs them)
+extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
+                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes,
+                                       const uint32_t *lvl16, const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad,
+                                       uint32_t n_versions, uint64_t vstride, hipStream_t stream) {
+    if (n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u) return hipErrorInvalidValue;
+    return launch_refit_levels(tris, nodes0, nodes, qnodes, n_nodes, lvl4, lvl4_off, n_lvl4, ubox4, wnodes0, wnodes, lvl16, lvl16_off, n_lvl16,
+                               ubox16, abs_pad, n_versions, vstride, stream);
 }
 
 #ifdef BF_TAIL_PROF

@@ -107,6 +107,37 @@ int bfh_shape_info(void *shape, unsigned *prims, float *area) {
         *area = s->surface_area();
     })
 }
+/* Mesh::vertex_positions_buffer / vertex_normals_buffer / parameters_changed (mesh.h:48-55, 243).  which: 0 positions, 1 normals.
+   bfh_shape_vertices: *n = floats in the buffer (0: a mesh without normals), copied to `out` if it is not NULL. */
+static Mesh *as_mesh(void *o) {
+    auto *m = dynamic_cast<Mesh *>((Object *) o);
+    if (!m) Throw("the shape is not a mesh: it has no vertex buffers");
+    return m;
+}
+int bfh_shape_vertices(void *shape, int which, float *out, unsigned long long *n) {
+    BFH_TRY({
+        Mesh *m = as_mesh(shape);
+        const std::vector<float> *v = which ? m->normals() : m->positions();
+        *n = v ? v->size() : 0;
+        if (out && v) std::memcpy(out, v->data(), v->size() * sizeof(float));
+    })
+}
+int bfh_shape_set_vertices(void *shape, int which, const float *data, unsigned long long n) {
+    BFH_TRY({
+        Mesh *m = as_mesh(shape);
+        if (which) m->set_vertex_normals(data, (size_t) n);
+        else m->set_vertex_positions(data, (size_t) n);
+    })
+}
+int bfh_scene_mesh_changed(void *scene, void *shape) {
+    BFH_TRY({
+        auto *s = dynamic_cast<Shape *>((Object *) shape);
+        if (!s) Throw("object is not a Shape");
+        as_scene(scene)->mesh_changed(s);
+    })
+}
+/// bf_scene_create calls this Scene has made so far (a test's proof that parameters_changed updated the cached handle)
+int bfh_scene_device_creations(void *scene, unsigned long long *out) { BFH_TRY(*out = as_scene(scene)->device_creations()) }
 /// flattened description the integrator hands to bf_scene_create (for tests: the
 /// same pointer can be given to the CPU oracle)
 const bf_scene_desc *bfh_scene_flat_desc(void *scene, void *endpoint) {

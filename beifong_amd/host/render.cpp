@@ -376,6 +376,18 @@ void Mesh::recompute_vertex_normals() {
     m_normals.swap(nrm);
 }
 
+static void write_vertices(std::vector<float> &dst, const float *data, size_t n, const char *what) {
+    if (!data || n != dst.size()) Throw("Mesh: %s: %zu floats given, the mesh has %zu (the topology is fixed)", what, n, dst.size());
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(data[i])) Throw("Mesh: %s: non-finite value at vertex %zu", what, i / 3);
+    std::memcpy(dst.data(), data, n * sizeof(float));      // in place: descriptions flattened earlier keep pointing at the array
+}
+void Mesh::set_vertex_positions(const float *data, size_t n) { write_vertices(m_positions, data, n, "vertex positions"); }
+void Mesh::set_vertex_normals(const float *data, size_t n) {
+    if (m_normals.empty()) Throw("Mesh: the mesh has no vertex normals: it cannot take any");
+    write_vertices(m_normals, data, n, "vertex normals");
+}
+
 // ---- scene --------------------------------------------------------------------
 struct Scene::Flat {
     const Endpoint *endpoint = nullptr;
@@ -572,6 +584,7 @@ bf_scene *Scene::device_scene(const Endpoint *endpoint) {
     if (!m_flat->device) {
         bf_status st = bf_scene_create(&m_flat->desc, &m_flat->device);
         if (st != BF_OK) Throw("bf_scene_create failed (status %d): %s", st, bf_last_error());
+        ++m_device_creations;
     }
     return m_flat->device;
 }
@@ -591,11 +604,35 @@ std::vector<bf_scene *> Scene::device_scenes(const Endpoint *endpoint, int n) {
             bf_status st = bf_scene_create(&m_flat->desc, &s);
             (void) bf_set_device(home);
             if (st != BF_OK) Throw("bf_scene_create on GPU %d failed (status %d): %s", dev, st, bf_last_error());
+            ++m_device_creations;
             m_flat->more.push_back(s);
         }
         r.push_back(m_flat->more[g - 1]);
     }
     return r;
+}
+
+void Scene::mesh_changed(const Shape *shape) {
+    size_t index = m_shapes.size();
+    for (size_t i = 0; i < m_shapes.size(); ++i)
+        if (m_shapes[i].get() == shape) index = i;
+    if (index == m_shapes.size()) Throw("parameters_changed: the shape does not belong to this scene");
+    if (shape->is_rectangle() || !shape->positions()) Throw("parameters_changed: shape %zu is not a mesh: it has no vertex buffers", index);
+    if (!m_flat) return;      // nothing cached: the next flatten reads the new arrays
+    std::vector<bf_scene *> handles;
+    if (m_flat->device) handles.push_back(m_flat->device);
+    handles.insert(handles.end(), m_flat->more.begin(), m_flat->more.end());
+    int home = 0;
+    for (bf_scene *h : handles) {
+        bf_scene_info info;
+        if (bf_scene_get_info(h, &info) != BF_OK) Throw("bf_scene_get_info: %s", bf_last_error());
+        if (h == handles.front()) home = info.device;
+        if (bf_set_device(info.device) != BF_OK) Throw("bf_set_device(%d): %s", info.device, bf_last_error());
+        bf_status st = bf_scene_update_vertices(h, (uint32_t) index, shape->positions()->data(),
+                                                shape->normals() ? shape->normals()->data() : nullptr, nullptr);
+        (void) bf_set_device(home);
+        if (st != BF_OK) Throw("bf_scene_update_vertices failed (status %d): %s", st, bf_last_error());
+    }
 }
 
 /// one render on gpu_count() GPUs: the plain entry for one, sample shards + RCCL all-reduce for more (bf_render_sharded)

@@ -245,6 +245,10 @@ public:
     const std::vector<uint32_t> *faces() const override { return &m_faces; }
     bool has_vertex_normals() const { return !m_normals.empty(); }
     bool has_vertex_texcoords() const { return !m_texcoords.empty(); }
+    /// Mesh::vertex_positions_buffer / vertex_normals_buffer written from outside (mesh.h:48-55): n floats = 3 * vertex_count(),
+    /// finite; the topology is fixed.  Normals only on a mesh that has them.  Scene::mesh_changed pushes them to the device.
+    void set_vertex_positions(const float *data, size_t n);
+    void set_vertex_normals(const float *data, size_t n);
     const Class *class_() const override;
 
 protected:
@@ -327,10 +331,17 @@ public:
     /// the endpoint a query without one runs for: the first sensor, else the first receiver (Scene::ray_intersect and the
     /// plugin queries of the Python layer run on device_scene() of it, the handle the integrator renders with)
     const Endpoint *default_endpoint() const;
+    /// Mesh::parameters_changed (mesh.h:243): the vertices of `shape` were written.  The cached device scenes are UPDATED through
+    /// bf_scene_update_vertices (a BVH refit on the device), not created again; without a cached device scene nothing is to
+    /// be done, the next flatten reads the new arrays.  Throws for a shape that is not a mesh of this scene.
+    void mesh_changed(const Shape *shape);
+    /// how many times this Scene has called bf_scene_create so far (all endpoints, all GPUs)
+    uint64_t device_creations() const { return m_device_creations; }
     const Class *class_() const override;
 
 private:
     struct Flat;
+    uint64_t m_device_creations = 0;
     void flatten(const Endpoint *endpoint);
     std::vector<ref<Shape>> m_shapes;
     std::vector<ref<Sensor>> m_sensors;

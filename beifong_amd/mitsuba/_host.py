@@ -49,6 +49,10 @@ def lib():
         getattr(l, f).argtypes = [vp, C.c_int]
         getattr(l, f).restype = vp
     l.bfh_shape_info.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(C.c_float)]
+    l.bfh_shape_vertices.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_ulonglong)]
+    l.bfh_shape_set_vertices.argtypes = [vp, C.c_int, vp, C.c_ulonglong]
+    l.bfh_scene_mesh_changed.argtypes = [vp, vp]
+    l.bfh_scene_device_creations.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     l.bfh_scene_flat_desc.argtypes = [vp, vp]
     l.bfh_scene_flat_desc.restype = C.POINTER(capi.bf_scene_desc)
     l.bfh_scene_device.argtypes = [vp, vp]
@@ -468,6 +472,45 @@ class Shape(_Handle):
         check(lib().bfh_shape_info(self._ptr, C.byref(p), C.byref(a)))
         return a.value
 
+    # ---- Mesh::vertex_positions_buffer / parameters_changed (mesh.h:48-55, 243) ----------------------------------------------
+    def _buffer(self, which):
+        n = C.c_ulonglong()
+        check(lib().bfh_shape_vertices(self._ptr, which, None, C.byref(n)))       # HostError for a shape that is not a mesh
+        out = np.empty(n.value, np.float32)
+        if n.value:
+            check(lib().bfh_shape_vertices(self._ptr, which, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out
+
+    def _set_buffer(self, which, array, name):
+        a = np.asarray(array)
+        if a.dtype != np.float32:
+            raise TypeError(f"{name} must be float32, got {a.dtype}")
+        a = np.ascontiguousarray(a).reshape(-1)
+        check(lib().bfh_shape_set_vertices(self._ptr, which, a.ctypes.data_as(C.c_void_p), a.size))
+
+    def vertex_positions_buffer(self):
+        """float32 [3 * n_vertices]: a copy of the mesh's world-space vertex positions"""
+        return self._buffer(0)
+
+    def vertex_normals_buffer(self):
+        """float32 [3 * n_vertices] (empty for a mesh without vertex normals)"""
+        return self._buffer(1)
+
+    def set_vertex_positions(self, array):
+        """write the host mesh (same vertex count, finite float32); parameters_changed() pushes it to the device"""
+        self._set_buffer(0, array, "vertex positions")
+
+    def set_vertex_normals(self, array):
+        self._set_buffer(1, array, "vertex normals")
+
+    def parameters_changed(self):
+        """The vertex buffers were written: the scene's cached device handles are updated through bf_scene_update_vertices (a
+        BVH refit on the device), not rebuilt; a scene without one flattens the new vertices at its next render."""
+        scene = self._owner
+        if not isinstance(scene, Scene):
+            raise HostError("parameters_changed: the shape is not bound to a loaded scene")
+        check(lib().bfh_scene_mesh_changed(scene._ptr, self._ptr))
+
 
 def _bound(obj):
     """An object made by load_dict outside a scene stands for its instance in the scene that was loaded with it last."""
@@ -502,6 +545,12 @@ class Scene(_Handle):
 
     def integrator(self):
         return Integrator(lib().bfh_scene_integrator(self._ptr), owner=self)
+
+    def device_creations(self):
+        """how many device scenes (bf_scene_create) this scene has built so far"""
+        n = C.c_ulonglong()
+        check(lib().bfh_scene_device_creations(self._ptr, C.byref(n)))
+        return n.value
 
     def sensors(self):
         return [Sensor(lib().bfh_scene_sensor(self._ptr, i), owner=self) for i in range(self._counts()[1])]

@@ -99,3 +99,43 @@ def moved_description(sd, transforms):
                 s2.normals = n2.ctypes.data_as(C.POINTER(C.c_float))
         out.shapes.append(s2)
     return out.finalize()
+
+
+def deformed_description(sd, vertices):
+    """A new SceneDesc equal to `sd` with the arrays named in `vertices` replaced: {shape: positions} or
+    {shape: (positions, normals)}, float32 [n_vertices, 3] each (normals None: the mesh keeps the ones it has).  The scene
+    bf_scene_create would have to rebuild for the base bf_scene_update_vertices gives a handle of `sd`; composes with
+    moved_description (deform first, then move: the pose is applied on top of the new base).  Indices, texture coordinates,
+    materials and endpoints are `sd`'s (kept alive); nothing is converted: the arrays must be float32 already."""
+    import ctypes as C
+
+    from . import capi
+    from .scenedesc import SceneDesc
+    out = SceneDesc()
+    C.memmove(C.byref(out.physics), C.byref(sd.physics), C.sizeof(capi.bf_physics))
+    C.memmove(C.byref(out.sensor), C.byref(sd.sensor), C.sizeof(capi.bf_sensor))
+    out.materials, out.emitters = list(sd.materials), list(sd.emitters)
+    out._keep.append(sd)
+    todo = {int(k): v for k, v in vertices.items()}
+    for k in todo:
+        if not 0 <= k < len(sd.shapes):
+            raise ValueError(f"shape index {k} out of range for a scene of {len(sd.shapes)} shapes")
+    for k, s in enumerate(sd.shapes):
+        s2 = capi.bf_shape()
+        C.memmove(C.byref(s2), C.byref(s), C.sizeof(capi.bf_shape))
+        if k in todo:
+            if s.type != capi.BF_SHAPE_MESH:
+                raise ValueError(f"shape {k} is not a mesh")
+            v = todo[k]
+            p, n = v if isinstance(v, tuple) else (v, None)
+            p = capi.vertex_array(p, f"positions of shape {k}", s.n_vertices)
+            out._keep.append(p)
+            s2.positions = p.ctypes.data_as(C.POINTER(C.c_float))
+            if n is not None:
+                if not s.normals:
+                    raise ValueError(f"shape {k} has no vertex normals: it cannot take any")
+                n = capi.vertex_array(n, f"normals of shape {k}", s.n_vertices)
+                out._keep.append(n)
+                s2.normals = n.ctypes.data_as(C.POINTER(C.c_float))
+        out.shapes.append(s2)
+    return out.finalize()

@@ -233,6 +233,68 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
             h.close()
 
 
+def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False):
+    """Coherent pulse sweep in which meshes DEFORM between the pulses: a walking pedestrian, a vibrating
+    panel.  The deforming counterpart of render_motion_sweep.
+
+    `positions`   {shape: float32[n_pulses, n_vertices, 3]}: the vertices of every deforming mesh at every pulse;
+    `transforms`  None, or float[n_pulses, n_shapes, 3, 4] as in render_motion_sweep, applied on top.
+
+    The scene is built once; the pulses are split into `n_streams` contiguous groups, one per handle and stream, each ONE
+    deform batch (bf_render_deform_batch_device) reading its slices of the vertex arrays, which are uploaded once.
+    per_pulse=True is the reference path: the pulses rotate over the handles, one bf_scene_update_vertices_device (+ one
+    bf_scene_transform_meshes) and one render per pulse; per-path results are the same.  Returns the cube
+    float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W)."""
+    import torch
+    n, shapes, pos, _ = capi.deform_tables(positions, None, {k: int(sd.shapes[int(k)].n_vertices) for k in positions if 0 <= int(k) < len(sd.shapes)})
+    xf = None
+    if transforms is not None:
+        xf = np.asarray(transforms, dtype=np.float32)
+        if xf.ndim != 4 or xf.shape[2:] != (3, 4) or xf.shape[0] != n:
+            raise ValueError(f"transforms must be [{n}, n_shapes, 3, 4], got {xf.shape}")
+    bound = max(float(np.abs(p).max()) for p in pos)
+    if not np.isfinite(bound):
+        raise ValueError("positions: non-finite value")
+    bound = max(bound, float(np.finfo(np.float32).tiny))
+    lib = lib or capi.load_library()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    n_streams = max(1, min(int(n_streams), n))
+    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
+    first = capi.Scene(sd, lib)
+    handles = [first] + [first.clone() for _ in range(n_streams - 1)]
+    try:
+        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
+        dpos = [torch.from_numpy(p).to(dev) for p in pos]
+        for s in streams:           # the cube and the vertex arrays were written on the current stream
+            s.wait_stream(torch.cuda.current_stream(dev))
+        if per_pulse:
+            for k in range(n):
+                j = k % n_streams
+                with torch.cuda.stream(streams[j]):
+                    for sh, d in zip(shapes, dpos):
+                        handles[j].update_vertices_device(int(sh), d[k].data_ptr(), None, bound, stream=streams[j].cuda_stream)
+                    if xf is not None:
+                        handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
+                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
+        else:
+            bounds = np.linspace(0, n, n_streams + 1).astype(int)
+            for j in range(n_streams):
+                lo, hi = int(bounds[j]), int(bounds[j + 1])
+                if hi > lo:
+                    with torch.cuda.stream(streams[j]):
+                        handles[j].render_deform_batch_device(launch, hi - lo, {int(sh): d[lo].data_ptr() for sh, d in zip(shapes, dpos)},
+                                                              cube[lo].data_ptr(), bound, transforms=None if xf is None else xf[lo:hi],
+                                                              stream=streams[j].cuda_stream)
+        for s in streams:
+            s.synchronize()
+        for h in handles:
+            h.sync()                # a vertex beyond `bound` (there is none: it was computed above) would be reported here
+        return cube.cpu().numpy().reshape(n, -1, 3)
+    finally:
+        for h in reversed(handles):
+            h.close()
+
+
 def range_doppler(cube, window=True):
     """Slow-time FFT of a pulse-sweep cube: complex64[n_doppler, cells], zero Doppler at row 0 (numpy.fft order)."""
     z = cube[:, :, 0].astype(np.complex64) + 1j * cube[:, :, 1].astype(np.complex64)

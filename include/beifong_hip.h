@@ -468,6 +468,37 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
  *     topology and every mesh's box back once.  The bound on ray origins the boxes are padded for is raised to cover
  *     the moved meshes (never lowered).  bf_scene_info.bbox_* keeps reporting the box as created. */
 bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const float *to_world, void *stream);
+/* Replace the BASE vertices of mesh shape `shape`: the positions (and vertex normals) "the scene was created with", for a
+ * mesh whose vertices come out of a simulation or a skinning step each frame.  Same n_vertices, same indices: the topology
+ * is fixed, so the trees are re-fitted bottom-up on the device (bf_scene_transform_meshes' level kernels), never rebuilt,
+ * and the traversal stack bounds and the tail's row count stay valid; quantised nodes are re-quantised.  DESIGN.md 6d.
+ *   Base replacement: the pose the handle holds (its latest bf_scene_transform_meshes / bf_scene_translate_meshes) is
+ *     applied on top of the new base by the arithmetic of those calls.  No arithmetic touches the values themselves: a
+ *     triangle row holds the floats given.
+ *   Equivalence: after the call every path, in every mode a rigid transform supports, and every bf_ray_intersect /
+ *     bf_trace_* result is bit-identical to a bf_scene_create of the same description with shape `shape` carrying
+ *     `positions` (and `normals`), followed by the same transform call.
+ *   Normals: NULL keeps the base normals the mesh has; non-NULL on a mesh created without normals is BF_ERR_INVALID.
+ *     Normals are not recomputed.  Texture coordinates and the rows' prim / shape / tag words are untouched.
+ *   Origin bound: the host form computes the shape's new box and raises (never lowers) the bound on ray origins the boxes
+ *     are padded for.  The device form cannot see the values: the caller declares bound >= max |coordinate| of the
+ *     vertices passed and [-bound, bound]^3 is taken as the shape's base box.  The gather kernel checks every corner it
+ *     reads (position finite with |c| <= bound, normal finite).  A triangle with a failing corner KEEPS ITS PREVIOUS ROW
+ *     and is counted; the kernel always runs to completion.  A non-zero count is reported once, as BF_ERR_DEVICE naming a
+ *     shape, by bf_scene_sync or by the handle's next render (which waits for that gather's count before it enqueues
+ *     anything: one event and eight bytes per device-form update); every render issued between the bad update and
+ *     the report is invalid.  A deform batch reports its own violations if it is given stats_out, else the next call does.
+ *   Validation, before anything is enqueued (a failed call leaves the scene as it was): BF_ERR_INVALID for a non-mesh
+ *     shape, an index out of range, NULL positions, a non-finite host value, a non-positive or non-finite bound;
+ *     BF_ERR_UNSUPPORTED for a mesh that carries an emitter / transmitter.  The error text names the shape.
+ *   Ordering and sharing as bf_scene_transform_meshes: stream-ordered (the host arrays are free again when the call
+ *     returns; device arrays must stay valid until the stream has run the call), an open rolling sequence is finished
+ *     first, copy on write against clones, a clone taken afterwards starts from what the handle renders then.  The first
+ *     update of a scene builds a device table of every triangle slot's three vertex indices, shared by its clones. */
+bf_status bf_scene_update_vertices(bf_scene *scene, uint32_t shape, const float *positions /* host [3 * n_vertices] */,
+                                   const float *normals /* host [3 * n_vertices] or NULL */, void *stream);
+bf_status bf_scene_update_vertices_device(bf_scene *scene, uint32_t shape, const float *positions_dev, const float *normals_dev,
+                                          float bound, void *stream);
 bf_status bf_scene_get_info(const bf_scene *scene, bf_scene_info *info);
 
 /* A second handle on the same scene for another stream: the big read-only arrays (BVH, triangles,
@@ -615,6 +646,30 @@ bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch
 bf_status bf_render_motion_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders,
                                  const uint64_t *seeds, uint32_t n_shapes, const float *to_world,
                                  float *hist_out, bf_path_record *records_out, bf_stats *stats_out);
+
+/* The motion batch for deforming meshes: render k of n_renders sees deforming shape shapes[j] at the vertices
+ * positions[j] + k * 3 * n_vertices(shapes[j]) (normals likewise, where given), every other mesh at the handle's base
+ * vertices, and then every mesh at to_world[k] (NULL: no transform; else [n_renders][n_shapes][12], absolute, checked
+ * as in a motion batch).  One geometry version per render in the motion batch's arena (BF_MOTION_BATCH_MB, chunking
+ * unchanged), gathered, transformed and re-fitted for all renders of a chunk at once.  The handle's own base, pose and
+ * clones do not change.  DESIGN.md 6d.
+ *   Equivalence: render k is bit-identical, path for path, to bf_scene_update_vertices(slice k) +
+ *     bf_scene_transform_meshes(to_world[k]) + a stand-alone render with seeds[k] on a second handle.
+ *   bound: as bf_scene_update_vertices_device, for all arrays of the call (the host form computes it); a violation is
+ *     counted and reported the same way, the triangle keeping the handle's base row in that version.
+ *   BF_ERR_INVALID before anything is enqueued: what bf_scene_update_vertices refuses, a shape listed twice,
+ *     n_renders == 0, a multi-pixel film, BF_FLAG_ROLLING, and what a motion batch refuses of to_world.  The error text
+ *     names render and shape. */
+bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds,
+                                        uint32_t n_deform, const uint32_t *shapes,
+                                        const float *const *positions_dev /* [n_deform] device pointers */,
+                                        const float *const *normals_dev /* NULL, or [n_deform] (entries may be NULL) */, float bound,
+                                        uint32_t n_shapes, const float *to_world, float *hist_dev, bf_path_record *records_dev,
+                                        void *stream, bf_stats *stats_out);
+bf_status bf_render_deform_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds,
+                                 uint32_t n_deform, const uint32_t *shapes, const float *const *positions /* [n_deform] host pointers */,
+                                 const float *const *normals, uint32_t n_shapes, const float *to_world, float *hist_out,
+                                 bf_path_record *records_out, bf_stats *stats_out);
 
 /* Scene::ray_intersect / ray_test over a batch of HOST rays (tests, tools).
  * rays: [n][8] = o.xyz, mint, d.xyz, maxt.  Outputs may be NULL.
