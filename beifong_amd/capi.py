@@ -5,6 +5,7 @@ fails loudly when the extension is missing — there is no CPU fallback.
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -104,6 +105,12 @@ class bf_path_record(C.Structure):
 
 
 PATH_RECORD_DTYPE = np.dtype([("L", "<f4"), ("aux", "<f4"), ("valid", "<u4"), ("n_rays", "<u4")])
+# the device trees as bf_scene_read_bvh returns them (bf_bvh.h: Node4, Node16)
+NODE4_DTYPE = np.dtype([("lox", "<f4", (4,)), ("loy", "<f4", (4,)), ("loz", "<f4", (4,)), ("hix", "<f4", (4,)), ("hiy", "<f4", (4,)),
+                        ("hiz", "<f4", (4,)), ("child", "<i4", (4,)), ("pad", "<i4", (4,))])
+NODE16_CHILD_DTYPE = np.dtype([("lo", "<f4", (3,)), ("hi", "<f4", (3,)), ("child", "<i4"), ("pad", "<u4")])      # one child record
+NODE16_DTYPE = np.dtype([("c", NODE16_CHILD_DTYPE, (16,))])
+EMPTY_CHILD = -(1 << 31)
 
 
 class bf_stats(C.Structure):
@@ -143,6 +150,7 @@ EXPORTED_SYMBOLS = [
     "bf_scene_flush", "bf_scene_sync", "bf_shard_range", "bf_render_sharded_device", "bf_render_sharded", "bf_allreduce_device",
     "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
     "bf_scene_update_vertices", "bf_scene_update_vertices_device", "bf_render_deform_batch_device", "bf_render_deform_batch",
+    "bf_scene_rebuild_bvh", "bf_scene_read_bvh",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
     "bf_bsdf_eval_pdf", "bf_bsdf_eval_pdf_device", "bf_bsdf_sample", "bf_bsdf_sample_device",
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
@@ -204,6 +212,8 @@ def load_library(path=None):
     lib.bf_render_motion_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_render_motion_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_scene_update_vertices.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    lib.bf_scene_rebuild_bvh.argtypes = [vp, vp]
+    lib.bf_scene_read_bvh.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, C.POINTER(C.c_int32)]
     lib.bf_scene_update_vertices_device.argtypes = [vp, C.c_uint32, vp, vp, C.c_float, vp]
     lib.bf_render_deform_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_float, C.c_uint32,
                                                   vp, vp, vp, vp, C.POINTER(bf_stats)]
@@ -483,6 +493,39 @@ class Scene:
         xf = rigid_table(transforms, self.info().n_shapes)
         check(self.lib, self.lib.bf_scene_transform_meshes(self.handle, xf.shape[0], _ptr(xf), C.c_void_p(stream) if stream else None),
               "bf_scene_transform_meshes")
+
+    def rebuild_bvh(self, stream=None):
+        """bf_scene_rebuild_bvh: both trees rebuilt on the device, in place, over the geometry the handle renders now (base
+        vertices as last updated, pose on top).  Host-synchronous; results stay bit-identical, traversal gets the tree a new
+        Scene of the same vertices would have."""
+        check(self.lib, self.lib.bf_scene_rebuild_bvh(self.handle, _stream(stream)), "bf_scene_rebuild_bvh")
+
+    def read_bvh(self, width=4):
+        """bf_scene_read_bvh: (nodes, rows, root_child) of the four- or sixteen-wide tree.  nodes: NODE4_DTYPE / NODE16_DTYPE
+        array; rows: float32[n_triangles, 3, 4] in leaf order (x, y, z and the primitive / shape / tag word, viewable as
+        uint32); root_child: the root's child reference."""
+        width = int(width)
+        if width not in (4, 16):
+            raise ValueError(f"read_bvh: width {width} (4 or 16)")
+        dt = NODE4_DTYPE if width == 4 else NODE16_DTYPE
+        root = C.c_int32(0)
+        n = self.info().n_bvh_nodes
+        if width == 16:
+            # the sixteen-wide node count is not in bf_scene_info: a call with no buffer is refused with BF_ERR_INVALID and the
+            # text "needs <n> bytes", which the header documents as the way to learn the size
+            st = self.lib.bf_scene_read_bvh(self.handle, 16, None, 0, None, C.byref(root))
+            n = 0
+            if st != BF_OK:
+                msg = self.lib.bf_last_error().decode()
+                m = re.search(r"needs (\d+) bytes", msg)
+                if st != BF_ERR_INVALID or not m:
+                    check(self.lib, st, "bf_scene_read_bvh")
+                n = int(m.group(1)) // dt.itemsize
+        nodes = np.zeros(n, dtype=dt)
+        rows = np.zeros((self.info().n_triangles, 3, 4), dtype=np.float32)
+        check(self.lib, self.lib.bf_scene_read_bvh(self.handle, width, _ptr(nodes) if n else None, nodes.nbytes,
+                                                   _ptr(rows) if rows.size else None, C.byref(root)), "bf_scene_read_bvh")
+        return nodes, rows, int(root.value)
 
     def info(self):
         i = bf_scene_info()

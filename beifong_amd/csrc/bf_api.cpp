@@ -40,6 +40,7 @@ const char *ncclGetErrorString(ncclResult_t result);
 #include <map>
 #include <mutex>
 
+#include "bf_build.h"
 #include "bf_bvh.h"
 #include "bf_device.h"
 #include "bf_wavefront.h"
@@ -287,6 +288,7 @@ struct bf_scene {
     // the refit's state, built on the handle's first transform (nothing of it costs bf_scene_create anything)
     struct Refit {
         bool ready = false;
+        bool have_boxes = false;                 // xf and mesh_box exist (they survive bf_scene_rebuild_bvh: neither depends on the slot order)
         std::vector<uint32_t> off4, off16;       // level d of the four- / sixteen-wide tree: [off[d], off[d + 1]) of lvl4 / lvl16
         uint32_t *lvl4 = nullptr, *lvl16 = nullptr;
         float4 *ubox4 = nullptr, *ubox16 = nullptr;      // unpadded bounds of every child record (two float4 each)
@@ -1410,6 +1412,10 @@ static bf_status refit_prepare(bf_scene *scene, hipStream_t stream) {
     } else {
         rf.off16.assign(1, 0u);
     }
+    if (rf.have_boxes) {
+        rf.ready = true;
+        return BF_OK;
+    }
     if ((st = alloc((size_t) scene->info.n_shapes * 16 * sizeof(float), (void **) &rf.xf)) != BF_OK) return st;
     std::vector<float4> tris((size_t) scene->d.n_tris * bfd::kTriStride);
     HIP_TRY(hipMemcpy(tris.data(), tris0, tris.size() * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1427,6 +1433,7 @@ static bf_status refit_prepare(bf_scene *scene, hipStream_t stream) {
             for (int a = 0; a < 3; ++a) b[a] = std::min(b[a], p[a]), b[3 + a] = std::max(b[3 + a], p[a]);
         }
     }
+    rf.have_boxes = true;
     rf.ready = true;
     return BF_OK;
 }
@@ -1779,6 +1786,207 @@ bf_status bf_scene_update_vertices_device(bf_scene *scene, uint32_t shape, const
     const float box[6] = {-bound, -bound, -bound, bound, bound, bound};
     if ((st = update_vertices_locked(scene, shape, *tp, positions_dev, normals_dev, bound, box, true, stream)) != BF_OK) return st;
     return mark_last(scene, stream);
+}
+
+// ---- rebuild of both trees on the device (bf_build.hip) ---------------------------------------------------------------
+static int g_rebuild_fail_alloc = 0;      // test hook: the n-th allocation of the swap phase fails
+/* test hook (not part of the ABI): nth > 0: the builder's nth device allocation fails; nth < 0: the |nth|-th allocation of the
+   rebuild's own arrays fails; 0: off */
+bf_status bfdbg_rebuild_fail_alloc(int nth) {
+    bfk_build_fail_alloc(nth > 0 ? nth : 0);
+    g_rebuild_fail_alloc = nth < 0 ? -nth : 0;
+    return BF_OK;
+}
+
+// one of the handle's own allocations, freed now (arrays the shared geometry owns are not in the list: they go with its last user)
+static void release_owned(bf_scene *scene, const void *p) {
+    if (!p) return;
+    for (size_t i = 0; i < scene->owned.size(); ++i)
+        if (scene->owned[i] == p) {
+            (void) hipFree(scene->owned[i]);
+            scene->owned.erase(scene->owned.begin() + (long) i);
+            return;
+        }
+}
+
+bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
+    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_rebuild_bvh: null scene");
+    if (scene->d.n_tris == 0) return BF_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    {
+        bf_status ost = order_after_last(scene, stream);
+        if (ost == BF_OK) ost = close_sequence(scene, stream);
+        if (ost != BF_OK) return ost;
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    const uint32_t n = scene->d.n_tris;
+    const bool want_wide = scene->d.wnodes != nullptr, want_quant = scene->d.qnodes != nullptr, posed = scene->tris0 != nullptr;
+    bfk_build_in bin = {scene->d.tris, n, scene->origin_scale_built, want_wide ? 1 : 0, stream};
+    bfk_build_out bo;
+    {
+        char text[384];
+        text[0] = 0;
+        const int bst = bfk_build_bvh(&bin, &bo, text, sizeof(text));
+        if (bst) return fail(bst == 1 ? BF_ERR_NOMEM : (bst == 3 ? BF_ERR_UNSUPPORTED : BF_ERR_DEVICE), "bf_scene_rebuild_bvh: %s", text);
+    }
+    // everything the new tree needs is allocated and filled before the handle changes: a failure frees it and leaves the scene as it was
+    std::vector<void *> fresh = {bo.nodes, bo.wnodes};
+    int n_alloc = 0;
+    auto drop = [&]() {
+        for (void *p : fresh)
+            if (p) (void) hipFree(p);
+        if (bo.order) (void) hipFree(bo.order);
+    };
+    auto take = [&](size_t bytes, float4 **out) -> bf_status {
+        void *q = nullptr;
+        const bool inject = g_rebuild_fail_alloc && ++n_alloc == g_rebuild_fail_alloc;
+        hipError_t he = inject ? hipErrorOutOfMemory : hipMalloc(&q, bytes);
+        if (he != hipSuccess) {
+            (void) hipGetLastError();
+            drop();
+            return fail(BF_ERR_NOMEM, "bf_scene_rebuild_bvh: hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(he));
+        }
+        fresh.push_back(q);
+        *out = (float4 *) q;
+        return BF_OK;
+    };
+    if (want_wide && 16u * std::max(1u, bo.depth16) > (uint32_t) bfd::kWideStack) {
+        drop();
+        return fail(BF_ERR_UNSUPPORTED, "bf_scene_rebuild_bvh: the rebuilt sixteen-wide tree is %u levels deep: its row stack (%u entries) "
+                                        "exceeds %d", bo.depth16, 16u * bo.depth16, bfd::kWideStack);
+    }
+    const size_t tri_rows = (size_t) n * bfd::kTriStride, tri_bytes = (tri_rows + kTriPad) * sizeof(float4), nrm_bytes = (size_t) n * 3 * sizeof(float4);
+    const size_t node_bytes = (size_t) bo.n_nodes * 8 * sizeof(float4), wnode_bytes = want_wide ? ((size_t) bo.n_wnodes + 1) * 32 * sizeof(float4) : 0;
+    const float4 *old_normals0 = scene->normals0 && scene->normals0 != scene->d.normals ? scene->normals0 : nullptr;
+    float4 *tris = nullptr, *tris0 = nullptr, *normals = nullptr, *normals0 = nullptr, *uvs = nullptr, *corners = nullptr, *qnodes = nullptr;
+    float4 *nodes0 = nullptr, *wnodes0 = nullptr, *spill = nullptr;
+    bf_status st = BF_OK;
+    if ((st = take(tri_bytes, &tris)) != BF_OK) return st;
+    if (posed && (st = take(tri_bytes, &tris0)) != BF_OK) return st;
+    if (scene->d.normals && (st = take(nrm_bytes, &normals)) != BF_OK) return st;
+    if (old_normals0 && (st = take(nrm_bytes, &normals0)) != BF_OK) return st;
+    if (scene->d.uvs && (st = take((size_t) n * sizeof(float4), &uvs)) != BF_OK) return st;
+    if (scene->geom->corners && (st = take((size_t) n * sizeof(uint4), &corners)) != BF_OK) return st;
+    if (want_quant && bo.n_nodes && (st = take(node_bytes / 2, &qnodes)) != BF_OK) return st;
+    if (posed && node_bytes && (st = take(node_bytes, &nodes0)) != BF_OK) return st;
+    if (posed && wnode_bytes && (st = take(wnode_bytes, &wnodes0)) != BF_OK) return st;
+    const uint32_t old_spill = scene->d.stack_need > 16 ? scene->d.stack_need - 16 : 1, new_spill = bo.stack4 > 16 ? bo.stack4 - 16 : 1;
+    if (new_spill > old_spill && (st = take((size_t) scene->d.spill_stride * new_spill * sizeof(int), &spill)) != BF_OK) return st;
+    auto enqueue = [&]() -> hipError_t {
+        hipError_t e = bfk_build_gather(bo.order, n, scene->d.tris, tris, bfd::kTriStride, stream);
+        if (e == hipSuccess) e = hipMemsetAsync(tris + tri_rows, 0, kTriPad * sizeof(float4), stream);
+        if (e == hipSuccess && tris0) e = bfk_build_gather(bo.order, n, scene->tris0, tris0, bfd::kTriStride, stream);
+        if (e == hipSuccess && tris0) e = hipMemsetAsync(tris0 + tri_rows, 0, kTriPad * sizeof(float4), stream);
+        if (e == hipSuccess && normals) e = bfk_build_gather(bo.order, n, scene->d.normals, normals, 3, stream);
+        if (e == hipSuccess && normals0) e = bfk_build_gather(bo.order, n, old_normals0, normals0, 3, stream);
+        if (e == hipSuccess && uvs) e = bfk_build_gather(bo.order, n, scene->d.uvs, uvs, 1, stream);
+        if (e == hipSuccess && corners) e = bfk_build_gather(bo.order, n, (const float4 *) scene->geom->corners, corners, 1, stream);
+        // the quantised copies by the refit's own kernel (no levels to re-fit: the boxes are the builder's)
+        const uint32_t no_levels[1] = {0u};
+        if (e == hipSuccess && qnodes)
+            e = bfk_launch_refit(tris, bo.nodes, bo.nodes, qnodes, bo.n_nodes, nullptr, no_levels, 0u, nullptr, nullptr, nullptr, nullptr, no_levels, 0u,
+                                 nullptr, 0.f, 1u, 0u, stream);
+        if (e == hipSuccess && nodes0) e = hipMemcpyAsync(nodes0, bo.nodes, node_bytes, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess && wnodes0) e = hipMemcpyAsync(wnodes0, bo.wnodes, wnode_bytes, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        return e;
+    };
+    {
+        const hipError_t e = enqueue();
+        if (e != hipSuccess) {
+            drop();
+            return fail(BF_ERR_DEVICE, "bf_scene_rebuild_bvh: %s", hipGetErrorString(e));
+        }
+    }
+    (void) hipFree(bo.order);
+    bo.order = nullptr;
+
+    // the swap.  The new arrays belong to a geometry object of the handle's own (copy on write: clones keep the old one alive and
+    // unchanged; a clone taken from now on shares the new one as it would share a created scene's)
+    auto g2 = std::make_shared<bf_geometry>();
+    g2->topo = scene->geom->topo;
+    g2->corners = (uint4 *) corners;
+    for (void *p : fresh)
+        if (p && p != spill) g2->owned.push_back(p);
+    const void *gone[] = {scene->tris0, scene->nodes0, scene->wnodes0, scene->d.tris, scene->d.nodes, scene->d.wnodes, scene->d.qnodes, scene->d.normals,
+                          scene->normals0, scene->refit.lvl4, scene->refit.lvl16, scene->refit.ubox4, scene->refit.ubox16, spill ? scene->d.spill : nullptr};
+    for (const void *p : gone) release_owned(scene, p);
+    scene->geom = g2;
+    scene->geom_token = std::make_shared<char>(0);
+    bfd::DScene &d = scene->d;
+    d.tris = tris;
+    d.nodes = bo.nodes;
+    d.qnodes = qnodes;
+    d.wnodes = want_wide ? bo.wnodes : nullptr;
+    d.normals = normals;
+    d.uvs = uvs;
+    d.n_nodes = bo.n_nodes;
+    d.root = bo.root;
+    d.wroot = want_wide ? bo.wroot : bfd_no_node();
+    d.n_wnodes = want_wide ? bo.n_wnodes : 0u;
+    if (want_wide) {
+        uint32_t rlog = 2;
+        while (rlog > 0 && (16u << rlog) * std::max(1u, bo.depth16) > (uint32_t) bfd::kWideStack) --rlog;
+        if (scene->tun.wide_rows_log >= 0) rlog = std::min<uint32_t>(rlog, (uint32_t) scene->tun.wide_rows_log);
+        d.wrows_log = rlog;
+    }
+    d.stack_need = bo.stack4;
+    if (spill) {
+        d.spill = (int *) spill;
+        scene->owned.push_back(spill);
+    }
+    scene->tris0 = tris0;
+    scene->nodes0 = posed ? nodes0 : nullptr;
+    scene->wnodes0 = posed ? wnodes0 : nullptr;
+    scene->normals0 = normals0;
+    // the handle's own arrays throughout; the boxes kept beside a pose are the POSED geometry's (only their topology is read from now
+    // on, as after a vertex update), so the pose stays absolute from the permuted base rows
+    scene->geom_private = posed;
+    scene->base_private = posed;
+    scene->normals_private = normals0 != nullptr;
+    scene->normals0_private = normals0 != nullptr;
+    if (posed) scene->deformed = true;
+    // the level lists follow the topology: rebuilt at the next refit; the per-mesh boxes and the transform table do not depend on it
+    scene->refit.ready = false;
+    scene->refit.lvl4 = scene->refit.lvl16 = nullptr;
+    scene->refit.ubox4 = scene->refit.ubox16 = nullptr;
+    scene->refit.off4.clear();
+    scene->refit.off16.clear();
+    float oscale = scene->origin_scale_built;
+    for (int k = 0; k < 3; ++k) oscale = std::max({oscale, std::fabs(bo.lo[k]), std::fabs(bo.hi[k])});
+    scene->origin_scale_built = oscale;      // (what the builder padded for: kept, never lowered)
+    bf_scene_info &inf = scene->info;
+    inf.n_bvh_nodes = bo.n_nodes;
+    inf.bvh_depth = bo.depth4;
+    inf.bvh_stack_need = bo.stack4;
+    {
+        float m = 0.f;
+        for (int k = 0; k < 3; ++k) m = std::max({m, bo.hi[k] - bo.lo[k], std::fabs(bo.lo[k]), std::fabs(bo.hi[k])});
+        const float e = 2e-6f * m + 2e-7f * oscale + 1e-30f;
+        for (int k = 0; k < 3; ++k) inf.bbox_min[k] = bo.lo[k] - e, inf.bbox_max[k] = bo.hi[k] + e;
+    }
+    return mark_last(scene, stream);
+}
+
+bf_status bf_scene_read_bvh(const bf_scene *scene, uint32_t width, void *nodes_out, uint64_t nodes_bytes, float *tri_rows_out, int32_t *root_child) {
+    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_read_bvh: null scene");
+    if (width != 4u && width != 16u) return fail(BF_ERR_INVALID, "bf_scene_read_bvh: width %u (4 or 16)", width);
+    BF_ENTER(scene);
+    {
+        bf_status cst = close_sequence(scene, scene->roll.stream);
+        if (cst != BF_OK) return cst;
+    }
+    if (scene->has_last) HIP_TRY(hipEventSynchronize(scene->last_done));
+    if (width == 16u && !scene->d.wnodes) return fail(BF_ERR_UNSUPPORTED, "bf_scene_read_bvh: the scene has no sixteen-wide tree");
+    const uint64_t need = width == 4u ? (uint64_t) scene->d.n_nodes * sizeof(bf::Node4) : (uint64_t) scene->d.n_wnodes * sizeof(bf::Node16);
+    if (nodes_bytes < need || (need && !nodes_out))
+        return fail(BF_ERR_INVALID, "bf_scene_read_bvh: nodes_out needs %llu bytes (%llu given)", (unsigned long long) need, (unsigned long long) nodes_bytes);
+    if (need) HIP_TRY(hipMemcpy(nodes_out, width == 4u ? scene->d.nodes : scene->d.wnodes, need, hipMemcpyDeviceToHost));
+    if (tri_rows_out && scene->d.n_tris)
+        HIP_TRY(hipMemcpy(tri_rows_out, scene->d.tris, (size_t) scene->d.n_tris * bfd::kTriStride * sizeof(float4), hipMemcpyDeviceToHost));
+    if (root_child) *root_child = width == 4u ? scene->d.root : scene->d.wroot;
+    return BF_OK;
 }
 
 bf_status bf_scene_get_info(const bf_scene *scene, bf_scene_info *info) {

@@ -584,6 +584,14 @@ class Scene(_Handle):
             raise HostError(lib().bfh_last_error().decode())
         return capi.Scene.borrow(h, owner=self)
 
+    def rebuild_accel(self, endpoint=None):
+        """Rebuild the acceleration structures of the cached device scene on the device (capi.Scene.rebuild_bvh): worth it after
+        its meshes have been moved or deformed far from where the trees were built.  Does nothing if no device scene has been
+        built yet (the first render builds one from the current vertices anyway)."""
+        if self.device_creations() == 0:
+            return
+        self._queries(endpoint).rebuild_bvh()
+
     def ray_intersect(self, rays, d=None, mint=None, maxt=None):
         """Scene::ray_intersect over a batch: rays [n, 8] (o.xyz, mint, d.xyz, maxt), or o and d with optional mint / maxt
         -> SurfaceInteraction."""

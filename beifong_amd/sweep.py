@@ -233,7 +233,7 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
             h.close()
 
 
-def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False):
+def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False, rebuild_every=None):
     """Coherent pulse sweep in which meshes DEFORM between the pulses: a walking pedestrian, a vibrating
     panel.  The deforming counterpart of render_motion_sweep.
 
@@ -243,9 +243,15 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
     The scene is built once; the pulses are split into `n_streams` contiguous groups, one per handle and stream, each ONE
     deform batch (bf_render_deform_batch_device) reading its slices of the vertex arrays, which are uploaded once.
     per_pulse=True is the reference path: the pulses rotate over the handles, one bf_scene_update_vertices_device (+ one
-    bf_scene_transform_meshes) and one render per pulse; per-path results are the same.  Returns the cube
-    float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W)."""
+    bf_scene_transform_meshes) and one render per pulse; per-path results are the same.
+    rebuild_every=k (an integer): a working handle's trees are rebuilt on the device (bf_scene_rebuild_bvh) after every k-th
+    frame's update of that handle, so a mesh that drifts far from its first frame keeps a tree made for where it is; the
+    batched path then renders its group in batches of k frames, the handle's base vertices set to the frame before each.
+    Results do not change.  Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W)."""
     import torch
+    if rebuild_every is not None and int(rebuild_every) < 1:
+        raise ValueError("rebuild_every must be a positive integer or None")
+    every = None if rebuild_every is None else int(rebuild_every)
     n, shapes, pos, _ = capi.deform_tables(positions, None, {k: int(sd.shapes[int(k)].n_vertices) for k in positions if 0 <= int(k) < len(sd.shapes)})
     xf = None
     if transforms is not None:
@@ -267,6 +273,7 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
         dpos = [torch.from_numpy(p).to(dev) for p in pos]
         for s in streams:           # the cube and the vertex arrays were written on the current stream
             s.wait_stream(torch.cuda.current_stream(dev))
+        updates = [0] * n_streams
         if per_pulse:
             for k in range(n):
                 j = k % n_streams
@@ -275,15 +282,24 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
                         handles[j].update_vertices_device(int(sh), d[k].data_ptr(), None, bound, stream=streams[j].cuda_stream)
                     if xf is not None:
                         handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
+                    updates[j] += 1
+                    if every and updates[j] % every == 0:
+                        handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
                     handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
         else:
             bounds = np.linspace(0, n, n_streams + 1).astype(int)
             for j in range(n_streams):
                 lo, hi = int(bounds[j]), int(bounds[j + 1])
-                if hi > lo:
+                for c0 in range(lo, hi, every or max(1, hi - lo)):
+                    c1 = min(hi, c0 + every) if every else hi
                     with torch.cuda.stream(streams[j]):
-                        handles[j].render_deform_batch_device(launch, hi - lo, {int(sh): d[lo].data_ptr() for sh, d in zip(shapes, dpos)},
-                                                              cube[lo].data_ptr(), bound, transforms=None if xf is None else xf[lo:hi],
+                        if every and c0 > lo:
+                            # the k-th frame since the last rebuild has just been rendered: the trees follow the meshes to it
+                            for sh, d in zip(shapes, dpos):
+                                handles[j].update_vertices_device(int(sh), d[c0 - 1].data_ptr(), None, bound, stream=streams[j].cuda_stream)
+                            handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
+                        handles[j].render_deform_batch_device(launch, c1 - c0, {int(sh): d[c0].data_ptr() for sh, d in zip(shapes, dpos)},
+                                                              cube[c0].data_ptr(), bound, transforms=None if xf is None else xf[c0:c1],
                                                               stream=streams[j].cuda_stream)
         for s in streams:
             s.synchronize()

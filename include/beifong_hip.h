@@ -499,6 +499,45 @@ bf_status bf_scene_update_vertices(bf_scene *scene, uint32_t shape, const float 
                                    const float *normals /* host [3 * n_vertices] or NULL */, void *stream);
 bf_status bf_scene_update_vertices_device(bf_scene *scene, uint32_t shape, const float *positions_dev, const float *normals_dev,
                                           float bound, void *stream);
+
+/* Rebuild both acceleration structures ON THE DEVICE, in place, over the geometry the handle renders now (its base vertices
+ * as last updated, its pose on top).  Transforms and vertex updates keep the topology the scene was created with and only
+ * re-fit its boxes, so a mesh that deforms frame after frame drifts away from the tree that was built for it (slower
+ * traversal, same results); this call gives the handle the tree bf_scene_create would build for the same vertices —
+ * same heuristic: binned SAH, 16 bins, leaves of at most 2 triangles, the same depth bound and box padding — without a new
+ * handle: pose, path pool, launch plan, endpoint tables and clones all stay.
+ *   Ordering: an open rolling sequence is finished first, the call waits for the handle's last work, enqueues on `stream` and
+ *     returns when the new tree is in place.  It is HOST-SYNCHRONOUS, like bf_scene_create (a few words of tree sizes are read
+ *     back per level).
+ *   Clones: a handle that shares geometry with clones gets its own copy (copy on write: the clones keep rendering the old
+ *     arrays); a clone taken afterwards shares the rebuilt arrays as it would share a created scene's (a posed handle's clone
+ *     takes its snapshot, as ever).
+ *   After the call:
+ *     - every path in every mode and every bf_ray_intersect / bf_trace_* result is bit-identical to what the handle produced
+ *       before the call (closest hits do not depend on the accelerator), hence to bf_scene_create on the same vertices;
+ *     - bf_scene_transform_meshes, bf_scene_translate_meshes, bf_scene_update_vertices(_device), motion batches and deform
+ *       batches keep working: they re-fit the NEW topology;
+ *     - what those calls cache lazily is invalidated or permuted with the triangle slots: the level lists are rebuilt at the
+ *       next re-fit, the per-mesh boxes are kept, the vertex-index table of bf_scene_update_vertices and every per-slot row
+ *       (triangles and vertex normals, posed and base, texture coordinates) move into the new leaf order, and a batch lays
+ *       its geometry versions out for the new node counts;
+ *     - the pose stays "absolute from the base": the next transform starts from the base vertices, not from the posed ones;
+ *     - the ray-origin bound the boxes are padded for is kept, never lowered;
+ *     - bf_scene_get_info reports the new n_bvh_nodes, bvh_depth and bvh_stack_need (and the current bounding box).
+ *   The tree is a pure function of the triangle rows: two rebuilds of the same geometry give byte-identical arrays.
+ *   A scene without mesh triangles: BF_OK, nothing happens.  scene == NULL: BF_ERR_INVALID.  If the call fails (BF_ERR_NOMEM,
+ *   BF_ERR_DEVICE; BF_ERR_UNSUPPORTED if a depth or stack bound cannot be met) the scene is exactly as it was. */
+bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream);
+/* Read-back of a tree for tests and tools, after the handle's last work (an open rolling sequence is finished first).
+ * width 4: bf_scene_info::n_bvh_nodes nodes of 128 bytes (lo.x[4], lo.y[4], lo.z[4], hi.x[4], hi.y[4], hi.z[4], child[4], pad[4]);
+ * width 16: the tail kernel's nodes of 512 bytes (16 child records of 8 words: lo.xyz, hi.xyz, reference, 0).  A child reference
+ * >= 0 is a node index; < 0 is a leaf, ~ref = (first_slot << 3 | count - 1) for width 4, (first_slot << 4 | count - 1) for
+ * width 16; INT32_MIN marks an unused slot (inverted box).  tri_rows_out (or NULL): the 12 floats of every triangle slot in
+ * leaf order (three rows of x, y, z and a word: primitive, shape, tag).  *root_child: the root's child reference.
+ * nodes_bytes too small: BF_ERR_INVALID, and bf_last_error() says "needs <n> bytes"; width 16 on a scene without the
+ * sixteen-wide tree (BF_NO_WIDE_BVH, no triangles): BF_ERR_UNSUPPORTED. */
+bf_status bf_scene_read_bvh(const bf_scene *scene, uint32_t width /* 4 or 16 */, void *nodes_out, uint64_t nodes_bytes,
+                            float *tri_rows_out /* 12 floats per slot, or NULL */, int32_t *root_child);
 bf_status bf_scene_get_info(const bf_scene *scene, bf_scene_info *info);
 
 /* A second handle on the same scene for another stream: the big read-only arrays (BVH, triangles,
