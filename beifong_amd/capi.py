@@ -25,7 +25,7 @@ BF_SI_FLOATS = 27
 BF_MODE_PATH, BF_MODE_RANGE, BF_MODE_TIME, BF_MODE_RECEIVE_RAW, BF_MODE_RECEIVE_IQ = range(5)
 BF_COLOR_RGB, BF_COLOR_MONO = range(2)
 BF_FLAG_STATS, BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL, BF_FLAG_DOPPLER, BF_FLAG_MIX_RESAMPLE = 1, 2, 4, 8, 16
-BF_FLAG_ROLLING, BF_FLAG_TIMING, BF_FLAG_COUNT, BF_FLAG_FAST = 32, 64, 128, 256
+BF_FLAG_ROLLING, BF_FLAG_TIMING, BF_FLAG_COUNT, BF_FLAG_FAST, BF_FLAG_MOMENT = 32, 64, 128, 256, 512
 
 M16 = C.c_float * 16
 
@@ -58,7 +58,7 @@ class bf_emitter(C.Structure):
 
 
 BF_FILTER_RESOLUTION = 31
-BF_VARIANT_LEAN, BF_VARIANT_WIDE, BF_VARIANT_FAST = 1, 2, 4
+BF_VARIANT_LEAN, BF_VARIANT_WIDE, BF_VARIANT_FAST, BF_VARIANT_MOMENT = 1, 2, 4, 8
 
 
 class bf_rfilter(C.Structure):
@@ -305,6 +305,51 @@ def make_launch(mode, n_paths, seed=0, path_offset=0, bins=0, bin_width=0.0, col
     lp.bins_y = bins_y
     lp.phase_bins = phase_bins
     return lp
+
+
+def _moment_shape(lp):
+    """(cells, channels per cell, first-moment offsets, m2_ offsets, offset of W) of a BF_FLAG_MOMENT launch
+    (include/beifong_hip.h: the layout at the flag)."""
+    if not lp.flags & BF_FLAG_MOMENT:
+        raise ValueError("the launch does not carry BF_FLAG_MOMENT")
+    if lp.mode == BF_MODE_RECEIVE_RAW:
+        return lp.bins * lp.bins_y, 4 + lp.phase_bins, np.array([0]), np.array([3 + lp.phase_bins]), 2
+    if lp.mode == BF_MODE_RECEIVE_IQ:
+        return lp.bins * lp.bins_y, 5, np.array([0, 1]), np.array([3, 4]), 2
+    a = {BF_MODE_PATH: 0, BF_MODE_RANGE: lp.bins, BF_MODE_TIME: 3 * lp.bins}[lp.mode]
+    pixels = lp.film_width * lp.film_height if (lp.spp and lp.film_width and lp.film_height) else 1
+    first = np.arange(5, 8 + a)                # nested AOVs, nested.X .Y .Z
+    return pixels, 11 + 2 * a, first, first + a + 3, 4
+
+
+def moment_layout(lp):
+    """(first, second): flat histogram indices pairing every first-moment channel of a BF_FLAG_MOMENT launch with its m2_
+    channel, shape [pixels or ADC cells, pairs].  Render modes pair the nested AOVs and nested.X/.Y/.Z (moment.cpp:39-52),
+    receive modes Y (RAW) or I and Q."""
+    cells, c, first, second, _ = _moment_shape(lp)
+    base = (np.arange(cells, dtype=np.int64) * c)[:, None]
+    return base + first[None, :].astype(np.int64), base + second[None, :].astype(np.int64)
+
+
+def moment_estimate(hist, lp):
+    """(mean, var_of_mean, rel_stderr) of every paired channel of a BF_FLAG_MOMENT histogram, in float64, shape as
+    moment_layout's.  n = the pixel's or ADC cell's W, or the launch's n_paths for a 1 x 1 film; mean = m1 / n,
+    var_of_mean = max(m2 / n - mean^2, 0) / (n - 1), rel_stderr = sqrt(var_of_mean) / |mean| (inf where mean = 0;
+    everything nan where n < 2)."""
+    cells, c, _, _, w_off = _moment_shape(lp)
+    h = np.asarray(hist, np.float64).reshape(-1)
+    if h.size != cells * c:
+        raise ValueError(f"histogram of {h.size} floats, the launch has {cells * c}")
+    first, second = moment_layout(lp)
+    receive = lp.mode in (BF_MODE_RECEIVE_RAW, BF_MODE_RECEIVE_IQ)
+    n = h[np.arange(cells) * c + w_off][:, None] if (receive or cells > 1) else np.full((1, 1), float(lp.n_paths))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = h[first] / n
+        var = np.maximum(h[second] / n - mean * mean, 0.0) / (n - 1.0)
+        rel = np.where(mean != 0.0, np.sqrt(var) / np.abs(mean), np.inf)
+    bad = np.broadcast_to(n < 2.0, mean.shape)
+    mean, var, rel = (np.where(bad, np.nan, x) for x in (mean, var, rel))
+    return mean, var, rel
 
 
 def shard_range(n_paths, shard, n_shards, lib=None):

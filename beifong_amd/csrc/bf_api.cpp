@@ -97,8 +97,19 @@ extern "C" hipError_t bfk_launch_tail_fast(const bfd::DScene *sc, const bfd::DLa
                                            uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
                                            hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap);
 
+// BF_FLAG_MOMENT: the launchers of the kernels' second-moment variants (bf_device.h: kMoment; exact build only, same wf_trace)
+extern "C" hipError_t bfk_launch_render_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+                                               unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
+                                               hipStream_t stream);
+extern "C" hipError_t bfk_wf_shade_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                          float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                          hipStream_t stream, int waves);
+extern "C" hipError_t bfk_launch_tail_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
+                                             uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
+                                             hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap);
+
 namespace {
-// the kernels one render runs: the exact build, or the fast-arithmetic one (BF_FLAG_FAST)
+// the kernels one render runs: the exact build, the fast-arithmetic one (BF_FLAG_FAST) or the second-moment variants (BF_FLAG_MOMENT)
 struct Kernels {
     decltype(&bfk_launch_render) render;
     decltype(&bfk_wf_shade) shade;
@@ -107,7 +118,9 @@ struct Kernels {
 };
 const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail};
 const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast};
-const Kernels &kernels_for(uint32_t flags) { return (flags & BF_FLAG_FAST) ? kFast : kExact; }
+const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment};
+// (BF_FLAG_MOMENT | BF_FLAG_FAST is refused before any kernel is chosen: render_locked)
+const Kernels &kernels_for(uint32_t flags) { return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : kExact); }
 }  // namespace
 
 namespace {
@@ -471,6 +484,17 @@ static uint32_t film_pixels(const bf_launch *lp) {
 
 uint32_t bf_launch_channels(const bf_launch *lp) {
     if (!lp) return 0;
+    if (lp->flags & BF_FLAG_MOMENT) {
+        // beifong_hip.h, BF_FLAG_MOMENT: 5 + 2 (A + 3) channels per pixel (moment.cpp:39-52), m2_Y / m2_I m2_Q per ADC cell
+        switch (lp->mode) {
+            case BF_MODE_PATH: return 11 * film_pixels(lp);
+            case BF_MODE_RANGE: return (11 + 2 * lp->bins) * film_pixels(lp);
+            case BF_MODE_TIME: return (11 + 6 * lp->bins) * film_pixels(lp);
+            case BF_MODE_RECEIVE_RAW: return (4 + lp->phase_bins) * lp->bins * lp->bins_y;
+            case BF_MODE_RECEIVE_IQ: return 5 * lp->bins * lp->bins_y;
+        }
+        return 0;
+    }
     switch (lp->mode) {
         case BF_MODE_PATH: return 5 * film_pixels(lp);
         case BF_MODE_RANGE: return (5 + lp->bins) * film_pixels(lp);
@@ -2552,13 +2576,13 @@ static bf_status wf_roll_render(const bf_scene *scene, const bf_launch *launch, 
     if (r.multi) {                 // the endpoints moved since the sequence was opened: per-path tables from now on (general kernels)
         lp.multi = 1u;
         lp.lean = 0u;
-        scene->last_variant &= (uint32_t) BF_VARIANT_FAST;
+        scene->last_variant &= (uint32_t) (BF_VARIANT_FAST | BF_VARIANT_MOMENT);
     }
     lp.roll_newest = newest;
     lp.roll_lo = newest + 1u > r.window ? newest + 1u - r.window : 0u;
     lp.n_chan_all = (lp.roll_newest - lp.roll_lo + 1u) * lp.n_chan;
     lp.base_off = lp.lds_hist ? r.window * lp.n_chan : 0u;        // fixed for the sequence: behind the full window
-    lp.lds_floats = lp.base_off + 5u * bfd::kRollBase;
+    lp.lds_floats = lp.base_off + ((r.shape.flags & BF_FLAG_MOMENT) ? bfd::kRollBaseChMoment : bfd::kRollBaseCh) * bfd::kRollBase;
     WfCtx c;
     if (with_offsets) {
         for (uint32_t j = 0; j < K; ++j)
@@ -2896,6 +2920,11 @@ static bf_status render_locked(const bf_scene *scene, const bf_launch *launch, c
             return fail(BF_ERR_INVALID, "path_offset + n_paths = %llu exceeds film_width * film_height * spp = %llu",
                         (unsigned long long) (launch->path_offset + launch->n_paths), (unsigned long long) (px * launch->spp));
     }
+    if ((launch->flags & BF_FLAG_MOMENT) && (launch->flags & BF_FLAG_FAST))
+        return fail(BF_ERR_INVALID, "BF_FLAG_MOMENT | BF_FLAG_FAST: the fast-arithmetic tolerance contract says nothing about squared "
+                                    "samples; render second moments with the exact kernels");
+    if (multi_pixel && (launch->flags & BF_FLAG_MOMENT) && (uint64_t) launch->film_width * launch->film_height * (11ull + 6ull * launch->bins) > (1ull << 31))
+        return fail(BF_ERR_UNSUPPORTED, "film %u x %u with %u bins and BF_FLAG_MOMENT is too large", launch->film_width, launch->film_height, launch->bins);
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const bool rolling = (launch->flags & BF_FLAG_ROLLING) != 0u && launch->n_paths != 0u &&
                          (uint64_t) n_renders * launch->n_paths <= scene->tun.pool && n_renders <= bfd::kRollRing;
@@ -2905,6 +2934,11 @@ static bf_status render_locked(const bf_scene *scene, const bf_launch *launch, c
             return fail(BF_ERR_INVALID, "BF_FLAG_ROLLING: the open rolling sequence of this handle was started %s BF_FLAG_FAST; "
                                         "flush it (bf_scene_flush) before rolling renders of the other mode",
                         (scene->roll.shape.flags & BF_FLAG_FAST) ? "with" : "without");
+        // ... and one channel layout: its histograms' base-channel table has five or eleven entries per render
+        if (scene->roll.open && ((launch->flags ^ scene->roll.shape.flags) & BF_FLAG_MOMENT))
+            return fail(BF_ERR_INVALID, "BF_FLAG_ROLLING: the open rolling sequence of this handle was started %s BF_FLAG_MOMENT; "
+                                        "flush it (bf_scene_flush) before rolling renders of the other layout",
+                        (scene->roll.shape.flags & BF_FLAG_MOMENT) ? "with" : "without");
         if (multi_pixel || (launch->flags & BF_FLAG_MEGAKERNEL))
             return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_ROLLING: multi-pixel films and the one-kernel variant do not roll");
         if (stats_out)
@@ -2941,6 +2975,7 @@ static bf_status render_locked(const bf_scene *scene, const bf_launch *launch, c
     lp.wide = scene->sensor_host.filt_n != 0u ? 1u : 0u;
     scene->last_variant = (lp.lean ? (uint32_t) BF_VARIANT_LEAN : 0u) | (lp.wide ? (uint32_t) BF_VARIANT_WIDE : 0u);      // reconstruction filter wider than a pixel: the kernels' kWide variants
     if (launch->flags & BF_FLAG_FAST) scene->last_variant |= (uint32_t) BF_VARIANT_FAST;
+    if (launch->flags & BF_FLAG_MOMENT) scene->last_variant |= (uint32_t) BF_VARIANT_MOMENT;
     const Kernels &kern = kernels_for(launch->flags);
     lp.count = ((launch->flags & (BF_FLAG_STATS | BF_FLAG_COUNT)) || stats_out) ? 1u : 0u;
     lp.doppler = (receive_mode && (launch->flags & BF_FLAG_DOPPLER)) ? 1u : 0u;
@@ -3124,6 +3159,7 @@ static void add_stats(bf_stats &a, const bf_stats &b) {
     a.n_shade_shadow += b.n_shade_shadow;
     a.n_shade_rays += b.n_shade_rays;
     a.n_guard += b.n_guard;
+    a.kernel_variant |= b.kernel_variant;      // (the chunks of one batch run the same kernels)
 }
 
 // The part every batch of geometry versions shares (motion batches, deform batches): chunks of renders whose versions fit the arena

@@ -91,7 +91,9 @@ struct DEmitter {
 //   kGeom     a batched launch whose renders each read their OWN geometry version (bf_render_motion_batch_device: DLaunch::geom_stride):
 //             triangles, vertex normals and the three node arrays of render k sit geom_stride float4 rows after render 0's
 //             (path_scene below) — per-lane pointers, so geometry reads of the root node become vector loads
-constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32;
+//   kMoment   the launch carries second moments (BF_FLAG_MOMENT; chosen by the host through the *_moment launchers): film_put adds nested.XYZ and the square of every
+//             first-moment addend (the channel layout at the flag in beifong_hip.h); every other variant has none of that code
+constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64;
 // rare<V>(c): a condition the lean profile guarantees to be false
 template <int V> __device__ __forceinline__ constexpr bool rare(bool c) { return (V & kLean) ? false : c; }
 
@@ -209,6 +211,7 @@ constexpr uint32_t kRollRing = 256;    // renders per sequence (descriptor ring;
 constexpr uint32_t kRollWindow = 4;    // newest renders whose histogram blocks a workgroup privatises in LDS; older ones take global atomics
 constexpr uint32_t kRollBase = 32;     // newest renders whose five BASE channels (X, Y, Z, alpha, weight: one address each per render, so
                                        // global float atomics on them serialise at L2) a workgroup sums in LDS behind the window
+constexpr uint32_t kRollBaseCh = 5, kRollBaseChMoment = 11;      // ... eleven with BF_FLAG_MOMENT: + nested.XYZ and their squares
 
 struct DLaunch {
     uint32_t mode, color_mode;
@@ -240,7 +243,8 @@ struct DLaunch {
     uint32_t roll_newest;           // render index of the call this launch belongs to
     uint32_t roll_lo;               // oldest render whose histogram block is in the LDS window [roll_lo, roll_newest]
     uint32_t lds_floats;            // floats of dynamic LDS the histogram code zeroes: the privatised histogram (n_chan_all, if lds_hist)
-                                    // followed, in a rolling launch, by the base-channel table [kRollBase][5] at float offset base_off
+                                    // followed, in a rolling launch, by the base-channel table [kRollBase][5] ([11] for a moment
+                                    // sequence) at float offset base_off
     uint32_t base_off;
     uint32_t has_records;           // rolling sequence: some render of it writes per-path records (DRoll::records)
     uint32_t lean;                  // 1: scene and launch fit the lean profile: the kernels' kLean variants

@@ -48,7 +48,7 @@ template <bool STATS, bool RESUME, bool SPILL, int TW = BF_TAIL_WAVES, int VX = 
 __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DScene sc_arg, DLaunch lp, float *__restrict__ g_hist,
                                                            bf_path_record *__restrict__ records,
                                                            unsigned long long *__restrict__ counters, WF wf, uint32_t wf_it) {
-    constexpr int kRX = 2 | VX;       // mode class decided at run time; VX: kWide (the filtered put) or kLean (bf_device.h: kernel variant word)
+    constexpr int kRX = 2 | VX;       // mode class decided at run time; VX: kWide (the filtered put), kLean, kMoment ... (bf_device.h: kernel variant word)
     extern __shared__ __align__(16) unsigned char s_raw[];
     int *s_stack = reinterpret_cast<int *>(s_raw);                         // [kStackDepth][kBlock]
     float *s_hist = reinterpret_cast<float *>(s_raw + sizeof(int) * kStackDepth * kBlock);
@@ -550,12 +550,38 @@ __global__ __launch_bounds__(kBlock) void bf_trace_kernel(DScene sc, uint64_t n,
 BF_NS_END  // namespace bfd
 
 // host-callable launchers (used by bf_api.cpp, which is plain C++)
-extern "C" hipError_t BF_LAUNCHER(bfk_launch_render)(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
-                                        unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
-                                        hipStream_t stream) {
+// moment: the kMoment variants (BF_FLAG_MOMENT; the *_moment launchers below)
+static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+                                unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream,
+                                bool moment) {
     bfd::WF none;
     memset(&none, 0, sizeof(none));
     const bool spill = sc->stack_need > (uint32_t) bfd::kStackDepth;
+#if !BF_FAST
+    if (moment) {
+        // BF_FLAG_MOMENT (never with BF_FLAG_FAST): the kMoment variants of the forms below
+#define BF_RENDER_MOM2(S, P, V)                                                                                                        \
+    hipLaunchKernelGGL((bfd::bf_render_kernel<S, false, P, BF_TAIL_WAVES, bfd::kMoment | (V)>), dim3(grid), dim3(bfd::kBlock), lds_bytes, \
+                       stream, *sc, *lp, g_hist, records, counters, none, 0u)
+#define BF_RENDER_MOM(S, P)                                                                    \
+    if (lp->geom_stride && lp->wide) BF_RENDER_MOM2(S, P, bfd::kWide | bfd::kGeom);            \
+    else if (lp->geom_stride) BF_RENDER_MOM2(S, P, bfd::kGeom);                                \
+    else if (lp->wide) BF_RENDER_MOM2(S, P, bfd::kWide);                                       \
+    else BF_RENDER_MOM2(S, P, 0)
+        if (stats) {
+            if (spill) { BF_RENDER_MOM(true, true); }
+            else { BF_RENDER_MOM(true, false); }
+        } else {
+            if (spill) { BF_RENDER_MOM(false, true); }
+            else { BF_RENDER_MOM(false, false); }
+        }
+#undef BF_RENDER_MOM
+#undef BF_RENDER_MOM2
+        return hipGetLastError();
+    }
+#else
+    if (moment) return hipErrorInvalidValue;
+#endif
 #define BF_RENDER_LAUNCH(S, R, P, WF_, IT_)                                                                                              \
     if (lp->wide)                                                                                                                        \
         hipLaunchKernelGGL((bfd::bf_render_kernel<S, R, P, BF_TAIL_WAVES, bfd::kWide>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, \
@@ -599,9 +625,9 @@ extern "C" hipError_t BF_LAUNCHER(bfk_launch_render)(const bfd::DScene *sc, cons
 //   spread     : spread the survivors thinly while the chip has room: a wave that starts with ~16 paths instead of 64
 //                runs them four lanes per ray (traverse_quad) from its first bounce and waits for the longest of 16
 //   block_cap  : at most this many workgroups (0: no cap)
-extern "C" hipError_t BF_LAUNCHER(bfk_launch_tail)(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
-                                      uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
-                                      hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
+static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, uint32_t n_slots,
+                              float *g_hist, bf_path_record *records, int stats, size_t lds_bytes, hipStream_t stream,
+                              int tail_waves, unsigned spread, unsigned block_cap, bool moment) {
     // one lane per live slot (gathered from the alive masks), at most one thread per pool slot
     // (any grid finishes the job: waves loop over their segment of the alive masks; the cap keeps the
     // launch within the scene's traversal-spill columns)
@@ -616,6 +642,34 @@ extern "C" hipError_t BF_LAUNCHER(bfk_launch_tail)(const bfd::DScene *sc, const 
     const bool spill = sc->stack_need > (uint32_t) bfd::kStackDepth;
     unsigned long long *counters = wf->counters;
     const bool two = tail_waves == 2;
+#if !BF_FAST
+    if (moment) {
+        // BF_FLAG_MOMENT (never with BF_FLAG_FAST): the kMoment variants of the forms below, three waves per SIMD
+#define BF_TAIL_MOM2(S, P, V)                                                                                                          \
+    hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kMoment | (V)>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, \
+                       *lp, g_hist, records, counters, *wf, it)
+#define BF_TAIL_MOM(S, P)                                                                      \
+    if (lp->geom_stride && lp->wide) BF_TAIL_MOM2(S, P, bfd::kWide | bfd::kGeom);              \
+    else if (lp->geom_stride && lp->lean) BF_TAIL_MOM2(S, P, bfd::kLean | bfd::kGeom);         \
+    else if (lp->geom_stride) BF_TAIL_MOM2(S, P, bfd::kGeom);                                  \
+    else if (lp->multi) BF_TAIL_MOM2(S, P, bfd::kMulti);                                       \
+    else if (lp->wide) BF_TAIL_MOM2(S, P, bfd::kWide);                                         \
+    else if (lp->lean) BF_TAIL_MOM2(S, P, bfd::kLean);                                         \
+    else BF_TAIL_MOM2(S, P, 0)
+        if (stats) {
+            if (spill) { BF_TAIL_MOM(true, true); }
+            else { BF_TAIL_MOM(true, false); }
+        } else {
+            if (spill) { BF_TAIL_MOM(false, true); }
+            else { BF_TAIL_MOM(false, false); }
+        }
+#undef BF_TAIL_MOM
+#undef BF_TAIL_MOM2
+        return hipGetLastError();
+    }
+#else
+    if (moment) return hipErrorInvalidValue;
+#endif
 #define BF_TAIL_LAUNCH(S, P)                                                                                                           \
     if (lp->geom_stride && lp->wide)                                                                                                   \
         hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kWide | bfd::kGeom>), dim3(grid), dim3(bfd::kBlock), lds_bytes,   \
@@ -651,6 +705,28 @@ extern "C" hipError_t BF_LAUNCHER(bfk_launch_tail)(const bfd::DScene *sc, const 
 #undef BF_TAIL_LAUNCH
     return hipGetLastError();
 }
+extern "C" hipError_t BF_LAUNCHER(bfk_launch_render)(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+                                        unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
+                                        hipStream_t stream) {
+    return render_launch(sc, lp, g_hist, records, counters, stats, grid, lds_bytes, stream, false);
+}
+extern "C" hipError_t BF_LAUNCHER(bfk_launch_tail)(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
+                                      uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
+                                      hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
+    return tail_launch(sc, lp, wf, it, n_slots, g_hist, records, stats, lds_bytes, stream, tail_waves, spread, block_cap, false);
+}
+#if !BF_FAST
+extern "C" hipError_t bfk_launch_render_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+                                               unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
+                                               hipStream_t stream) {
+    return render_launch(sc, lp, g_hist, records, counters, stats, grid, lds_bytes, stream, true);
+}
+extern "C" hipError_t bfk_launch_tail_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
+                                             uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
+                                             hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
+    return tail_launch(sc, lp, wf, it, n_slots, g_hist, records, stats, lds_bytes, stream, tail_waves, spread, block_cap, true);
+}
+#endif
 
 #if !BF_FAST      // the rest (probes, ray queries, mesh translation, host helpers) exists in the exact build only
 BF_NS_BEGIN

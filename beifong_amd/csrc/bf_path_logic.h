@@ -877,6 +877,8 @@ struct FilmAcc {
     float X, Y, Z, A, W;    // base channels of the 1x1 film (render modes)
     uint32_t invalid;
     uint32_t n_put;         // paths binned by this lane (CTR_FILM: the loud "no path was lost" check of the host)
+    float nX, nY, nZ;       // kMoment: nested.XYZ (the unweighted result) of the 1x1 film ...
+    float qX, qY, qZ;       // ... and their squares (the other variants never touch them: no registers)
 };
 
 // ImageBlock::put / SignalBlock::put, the branch for reconstruction filters wider than a pixel (imageblock.cpp:115-165,
@@ -898,6 +900,11 @@ struct WideSample {
     uint32_t emask;           // candidates that take the sample (bit i: bin i of the three)
     bool e3;                  // three values per bin (time mode) or one
     float e0, e1, e2;
+    // kMoment (put_wide<true>): m2_ of a candidate bin sits m2off channels behind it; render modes: nested.XYZ at channel nch,
+    // their squares at qch; receive modes: the squares of v0 (and of v1: I/Q) at qch
+    uint32_t m2off, nch, qch;
+    float n0, n1, n2;
+    bool q2;
 };
 BF_DEV float filt_eval(CSensor &se, float x) {
     const int idx = min((int) __builtin_fabsf(x * se.filt_scale), 31);
@@ -907,7 +914,7 @@ BF_DEV void put_wide_add(const HistDst &hd, uint32_t idx, float v, float w) {
     const float a = v * w;          // value[k] * weight (imageblock.cpp:160)
     if (a != 0.f) hist_add(hd.s, hd.g, hd.lds, idx, a);
 }
-BF_DEV void put_wide(CSensor &se, const WideSample &ws, const HistDst &hd) {
+template <bool MOM = false> BF_DEV void put_wide(CSensor &se, const WideSample &ws, const HistDst &hd) {
     const int border = (int) se.filt_border, n = (int) se.filt_n;
     const float r = se.filt_radius;
     // pos = pos_ - (m_offset - m_border_size + .5f)
@@ -943,6 +950,26 @@ BF_DEV void put_wide(CSensor &se, const WideSample &ws, const HistDst &hd) {
                 if (ws.e3) {
                     put_wide_add(hd, c + 1u, ws.e1, w);
                     put_wide_add(hd, c + 2u, ws.e2, w);
+                }
+                if (MOM && ws.five) {          // render modes only: an ADC cell's phase bins have no m2_ channel (Y A W [phase bins] m2_Y)
+                    put_wide_add(hd, c + ws.m2off, ws.e0 * ws.e0, w);
+                    if (ws.e3) {
+                        put_wide_add(hd, c + ws.m2off + 1u, ws.e1 * ws.e1, w);
+                        put_wide_add(hd, c + ws.m2off + 2u, ws.e2 * ws.e2, w);
+                    }
+                }
+            }
+            if (MOM) {
+                if (ws.five) {
+                    put_wide_add(hd, cell + ws.nch + 0u, ws.n0, w);
+                    put_wide_add(hd, cell + ws.nch + 1u, ws.n1, w);
+                    put_wide_add(hd, cell + ws.nch + 2u, ws.n2, w);
+                    put_wide_add(hd, cell + ws.qch + 0u, ws.n0 * ws.n0, w);
+                    put_wide_add(hd, cell + ws.qch + 1u, ws.n1 * ws.n1, w);
+                    put_wide_add(hd, cell + ws.qch + 2u, ws.n2 * ws.n2, w);
+                } else {
+                    put_wide_add(hd, cell + ws.qch, ws.v0 * ws.v0, w);
+                    if (ws.q2) put_wide_add(hd, cell + ws.qch + 1u, ws.v1 * ws.v1, w);
                 }
             }
         }
@@ -986,6 +1013,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
     g_hist = hd.g;
     lds_hist = hd.lds;
     constexpr bool wide = (RX & kWide) != 0;       // reconstruction filter wider than a pixel (uniform; the radar scenes use box)
+    constexpr bool mom = (RX & kMoment) != 0;      // BF_FLAG_MOMENT: second moments next to every first-moment channel (beifong_hip.h)
     if (mode_receive<RX>(lp)) {
         // receive_sample tail — integrator.cpp:1625-1665; SignalBlock::put — signalblock.cpp:162-169
         CSensor &se = c_sensor(sc);
@@ -1001,6 +1029,9 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
         float a1 = valid ? 1.f : 0.f;
         if (lp.iq) a1 = valid ? 4.f * (__builtin_fabsf(s.aux) * s.phase) : 0.f;   // I, Q, W instead of Y, A, W
         bool ok = __builtin_isfinite(a0) && __builtin_isfinite(a1);
+        // moment cells: Y A W [phase bins] m2_Y, or I Q W m2_I m2_Q; a square that is not finite drops the sample
+        const float q0 = mom ? a0 * a0 : 0.f, q1 = (mom && lp.iq) ? a1 * a1 : 0.f;
+        if (mom) ok = ok && __builtin_isfinite(q0) && __builtin_isfinite(q1);
         // PhaseIntegrator::sample (phase.cpp:93-141): S{k}.Y takes hsum(L), before the receiver weight,
         // iff rect((phase - centre_k) / width) > 0; evaluated exactly as written there for the (at most
         // three) candidate bins around phase / width
@@ -1038,7 +1069,10 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 ws.bh = ws.H = (int) lp.bins_y;
                 ws.cropx = (int) wot;
                 ws.cropy = (int) wof;
-                ws.C = 3u + P;
+                ws.C = 3u + P + (mom ? (lp.iq ? 2u : 1u) : 0u);
+                ws.m2off = ws.nch = 0u;
+                ws.qch = 3u + P;
+                ws.q2 = lp.iq != 0u;
                 ws.v0 = a0;
                 ws.v1 = a1;
                 ws.v2 = 1.f;
@@ -1049,15 +1083,19 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 ws.e3 = false;
                 ws.e0 = pv;
                 ws.e1 = ws.e2 = 0.f;
-                put_wide(se, ws, hd);
+                put_wide<mom>(se, ws, hd);
             } else {
                 ++acc.invalid;
             }
         } else if ((ok = ok && lx >= 0.f && lx < (float) lp.bins && ly >= 0.f && ly < (float) lp.bins_y)) {
-            uint32_t off = (3u + P) * ((uint32_t) ly * lp.bins + (uint32_t) lx);
+            uint32_t off = (3u + P + (mom ? (lp.iq ? 2u : 1u) : 0u)) * ((uint32_t) ly * lp.bins + (uint32_t) lx);
             if (a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 0u, a0);
             if (a1 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 1u, a1);
             hist_add(s_hist, g_hist, lds_hist, off + 2u, 1.f);
+            if (mom) {
+                if (q0 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 3u + P, q0);
+                if (lp.iq && q1 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 4u, q1);
+            }
             for (int i = 0; i < 3; ++i)
                 if ((pmask >> i & 1u) && pv != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 3u + (uint32_t) (pk0 - 1 + i), pv);
             acc.W += 1.f;
@@ -1083,6 +1121,26 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
         if (is_time && lp.color_mode == BF_COLOR_RGB) srgb_to_xyz_grey(s.result, a0, a1, a2);
         bool ok = (s.flags & kFlagFilmOk) && __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z);
         if (is_range || is_time) ok = ok && __builtin_isfinite(a0) && __builtin_isfinite(a1) && __builtin_isfinite(a2);
+        // moment.cpp:72-91: nested.XYZ = the XYZ of the nested (unweighted) result, then the square of every nested channel.
+        // A nested AOVs; per pixel: X Y Z A W | AOVs | nested.XYZ at nch | m2_ AOVs (m2off behind each) | m2_ nested.XYZ at qch
+        const uint32_t n_aov = is_range ? lp.bins : (is_time ? 3u * lp.bins : 0u);
+        const uint32_t nch = 5u + n_aov, m2off = n_aov + 3u, qch = 8u + 2u * n_aov;
+        float nX = 0.f, nY = 0.f, nZ = 0.f, qX = 0.f, qY = 0.f, qZ = 0.f;
+        bool mfin = true;
+        if (mom) {
+            if (lp.color_mode == BF_COLOR_RGB)
+                srgb_to_xyz_grey(s.result, nX, nY, nZ);
+            else
+                nX = nY = nZ = s.result;
+            qX = nX * nX;
+            qY = nY * nY;
+            qZ = nZ * nZ;
+            // ImageBlock::put refuses a sample with ANY non-finite channel: also one whose square overflows
+            mfin = __builtin_isfinite(nX) && __builtin_isfinite(nY) && __builtin_isfinite(nZ) && __builtin_isfinite(qX) &&
+                   __builtin_isfinite(qY) && __builtin_isfinite(qZ);
+            if (is_range || is_time) mfin = mfin && __builtin_isfinite(a0 * a0) && __builtin_isfinite(a1 * a1) && __builtin_isfinite(a2 * a2);
+            ok = ok && mfin;
+        }
         // multi-pixel film: every channel of the sample goes to its pixel's block of the histogram; the 1 x 1 film
         // keeps the five base channels in registers until film_flush
         uint32_t pix = 0u;
@@ -1099,6 +1157,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
             // the filtered branch takes every finite sample (where it lands is decided cell by cell)
             bool fin = __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z);
             if (is_range || is_time) fin = fin && __builtin_isfinite(a0) && __builtin_isfinite(a1) && __builtin_isfinite(a2);
+            if (mom) fin = fin && mfin;
             if (fin) {
                 WideSample ws;
                 uint32_t qx, qy;
@@ -1129,6 +1188,13 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 ws.e0 = a0;
                 ws.e1 = a1;
                 ws.e2 = a2;
+                ws.m2off = m2off;
+                ws.nch = nch;
+                ws.qch = qch;
+                ws.n0 = nX;
+                ws.n1 = nY;
+                ws.n2 = nZ;
+                ws.q2 = false;
                 if (is_range || is_time) {
                     float w = lp.bin_width;
                     int k = (int) __builtin_floorf(s.aux / w);
@@ -1139,7 +1205,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                         if (s.aux >= lo && s.aux < hi) ws.emask |= 1u << (i - (k - 1));
                     }
                 }
-                put_wide(c_sensor(sc), ws, hd);
+                put_wide<mom>(c_sensor(sc), ws, hd);
             } else {
                 ++acc.invalid;
             }
@@ -1150,6 +1216,14 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 if (Z != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 2u, Z);
                 if (valid) hist_add(s_hist, g_hist, lds_hist, pix + 3u, 1.f);
                 hist_add(s_hist, g_hist, lds_hist, pix + 4u, 1.f);
+                if (mom) {
+                    if (nX != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + nch + 0u, nX);
+                    if (nY != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + nch + 1u, nY);
+                    if (nZ != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + nch + 2u, nZ);
+                    if (qX != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + qch + 0u, qX);
+                    if (qY != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + qch + 1u, qY);
+                    if (qZ != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + qch + 2u, qZ);
+                }
             } else if (!use_acc) {
                 // batched launch: the wave's lanes hold paths of different renders, so the base channels cannot be
                 // summed in registers; each sample goes to its render's block.  A rolling sequence's older renders (behind
@@ -1157,21 +1231,40 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 // workgroup's base-channel table instead (kRollBase renders; film_flush adds it up)
                 float *bs = s_hist;
                 bool bl = lds_hist;
+                uint32_t bn = nch, bq = qch;       // kMoment: where nested.XYZ and their squares go (the table keeps its eleven entries together)
                 if (lp.roll && !lds_hist && lp.roll_newest - s.render < kRollBase) {
-                    bs = s_base + 5u * (lp.roll_newest - s.render);
+                    bs = s_base + (mom ? kRollBaseChMoment : kRollBaseCh) * (lp.roll_newest - s.render);
                     bl = true;
+                    bn = 5u;
+                    bq = 8u;
                 }
                 if (X != 0.f) hist_add(bs, g_hist, bl, 0u, X);
                 if (Y != 0.f) hist_add(bs, g_hist, bl, 1u, Y);
                 if (Z != 0.f) hist_add(bs, g_hist, bl, 2u, Z);
                 if (valid) hist_add(bs, g_hist, bl, 3u, 1.f);
                 hist_add(bs, g_hist, bl, 4u, 1.f);
+                if (mom) {
+                    if (nX != 0.f) hist_add(bs, g_hist, bl, bn + 0u, nX);
+                    if (nY != 0.f) hist_add(bs, g_hist, bl, bn + 1u, nY);
+                    if (nZ != 0.f) hist_add(bs, g_hist, bl, bn + 2u, nZ);
+                    if (qX != 0.f) hist_add(bs, g_hist, bl, bq + 0u, qX);
+                    if (qY != 0.f) hist_add(bs, g_hist, bl, bq + 1u, qY);
+                    if (qZ != 0.f) hist_add(bs, g_hist, bl, bq + 2u, qZ);
+                }
             } else {
                 acc.X += X;
                 acc.Y += Y;
                 acc.Z += Z;
                 acc.A += valid ? 1.f : 0.f;
                 acc.W += 1.f;
+                if (mom) {
+                    acc.nX += nX;
+                    acc.nY += nY;
+                    acc.nZ += nZ;
+                    acc.qX += qX;
+                    acc.qY += qY;
+                    acc.qZ += qZ;
+                }
             }
             if (is_range || is_time) {
                 // range.cpp:141-161 / time.cpp:134-153: bin i takes the sample iff
@@ -1185,10 +1278,16 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                     if (s.aux >= lo && s.aux < hi) {
                         if (is_range) {
                             if (a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 5u + (uint32_t) i, a0);
+                            if (mom && a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 5u + (uint32_t) i + m2off, a0 * a0);
                         } else if (a0 != 0.f || a1 != 0.f || a2 != 0.f) {
                             hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + 0u, a0);
                             hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + 1u, a1);
                             hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + 2u, a2);
+                            if (mom) {
+                                hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + m2off + 0u, a0 * a0);
+                                hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + m2off + 1u, a1 * a1);
+                                hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + m2off + 2u, a2 * a2);
+                            }
                         }
                     }
                 }
@@ -1230,6 +1329,14 @@ template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, fl
             acc.Z += __shfl_down(acc.Z, off);
             acc.A += __shfl_down(acc.A, off);
             acc.W += __shfl_down(acc.W, off);
+            if (RX & kMoment) {
+                acc.nX += __shfl_down(acc.nX, off);
+                acc.nY += __shfl_down(acc.nY, off);
+                acc.nZ += __shfl_down(acc.nZ, off);
+                acc.qX += __shfl_down(acc.qX, off);
+                acc.qY += __shfl_down(acc.qY, off);
+                acc.qZ += __shfl_down(acc.qZ, off);
+            }
         }
         if (lane == 0 && acc.W != 0.f && !lp.spp && (lp.batch == 0u || lp.roll != nullptr)) {
             const HistDst hd = hist_dst(lp, lp.roll ? lp.roll_newest : 0u, s_hist, g_hist, lds_hist);
@@ -1238,6 +1345,16 @@ template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, fl
             hist_add(hd.s, hd.g, hd.lds, 2, acc.Z);
             hist_add(hd.s, hd.g, hd.lds, 3, acc.A);
             hist_add(hd.s, hd.g, hd.lds, 4, acc.W);
+            if (RX & kMoment) {
+                // the 1 x 1 film: chan_px = 5 + 2 (A + 3) channels; nested.XYZ behind the A nested AOVs, their squares last
+                const uint32_t nch = (lp.chan_px - 1u) / 2u, qch = lp.chan_px - 3u;
+                if (acc.nX != 0.f) hist_add(hd.s, hd.g, hd.lds, nch + 0u, acc.nX);
+                if (acc.nY != 0.f) hist_add(hd.s, hd.g, hd.lds, nch + 1u, acc.nY);
+                if (acc.nZ != 0.f) hist_add(hd.s, hd.g, hd.lds, nch + 2u, acc.nZ);
+                if (acc.qX != 0.f) hist_add(hd.s, hd.g, hd.lds, qch + 0u, acc.qX);
+                if (acc.qY != 0.f) hist_add(hd.s, hd.g, hd.lds, qch + 1u, acc.qY);
+                if (acc.qZ != 0.f) hist_add(hd.s, hd.g, hd.lds, qch + 2u, acc.qZ);
+            }
         }
     }
     if (lds_hist) {
@@ -1263,10 +1380,14 @@ template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, fl
         // base-channel table of the renders behind the window: entry [age][channel], age = roll_newest - render
         if (!lds_hist) __syncthreads();
         const float *s_base = s_hist + lp.base_off;
-        for (uint32_t i = tid; i < 5u * kRollBase; i += kBlock) {
+        constexpr uint32_t kB = (RX & kMoment) ? kRollBaseChMoment : kRollBaseCh;
+        for (uint32_t i = tid; i < kB * kRollBase; i += kBlock) {
             const float v = s_base[i];
-            const uint32_t age = i / 5u;
-            if (v != 0.f && age <= lp.roll_newest) glb_add(lp.roll[(lp.roll_newest - age) & (kRollRing - 1u)].hist + (i - 5u * age), v);
+            const uint32_t age = i / kB;
+            uint32_t ch = i - kB * age;
+            // moment sequences: entries 5-7 are nested.XYZ, 8-10 their squares (film_put): back to their channels of the 1 x 1 film
+            if ((RX & kMoment) && ch >= 5u) ch = ch < 8u ? (lp.chan_px - 1u) / 2u + (ch - 5u) : lp.chan_px - 3u + (ch - 8u);
+            if (v != 0.f && age <= lp.roll_newest) glb_add(lp.roll[(lp.roll_newest - age) & (kRollRing - 1u)].hist + ch, v);
         }
     }
 }

@@ -728,9 +728,10 @@ extern "C" int bfdbg_shade_lane_profile(unsigned long long *out, int clear) {
 }
 #endif
 
-extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                   hipStream_t stream, int waves) {
+// moment: the kMoment variants (BF_FLAG_MOMENT; bfk_wf_shade_moment below)
+static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                  float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                  hipStream_t stream, int waves, bool moment) {
     // `waves`: register budget of the shading kernel (waves per SIMD); 3 is the sweet spot (168 VGPRs)
     const bool rx = lp->mode == BF_MODE_RECEIVE_RAW;
 #define BF_SHADE_LAUNCH_RX(F, W, RX_)                                                                                              \
@@ -754,6 +755,46 @@ extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd
     if (lp->lean && !lp->wide) { BF_SHADE_LAUNCH_GEOM(F, bfd::kLean); }    \
     else if (lp->wide) { BF_SHADE_LAUNCH_GEOM(F, bfd::kWide); }            \
     else { BF_SHADE_LAUNCH_GEOM(F, 0); }
+#if !BF_FAST
+    // BF_FLAG_MOMENT (never with BF_FLAG_FAST): the kMoment variants, three waves per SIMD, in the forms the other launches
+    // come in — per-render geometry, per-path tables, lean, wide, general
+#define BF_SHADE_LAUNCH_MOM(F, V)                                \
+    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kMoment | (V));    \
+    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kMoment | (V))
+#define BF_SHADE_LAUNCH_MOM_F(V)                         \
+    if (first == 3) { BF_SHADE_LAUNCH_MOM(3, V); }       \
+    else if (first == 2) { BF_SHADE_LAUNCH_MOM(2, V); }  \
+    else if (first) { BF_SHADE_LAUNCH_MOM(1, V); }       \
+    else { BF_SHADE_LAUNCH_MOM(0, V); }
+    if (moment) {
+        if (lp->geom_stride) {
+            if (first >= 2) return hipErrorInvalidValue;
+            if (lp->lean && !lp->wide) {
+                if (first) { BF_SHADE_LAUNCH_MOM(1, bfd::kGeom | bfd::kLean); }
+                else { BF_SHADE_LAUNCH_MOM(0, bfd::kGeom | bfd::kLean); }
+            } else if (lp->wide) {
+                if (first) { BF_SHADE_LAUNCH_MOM(1, bfd::kGeom | bfd::kWide); }
+                else { BF_SHADE_LAUNCH_MOM(0, bfd::kGeom | bfd::kWide); }
+            } else {
+                if (first) { BF_SHADE_LAUNCH_MOM(1, bfd::kGeom); }
+                else { BF_SHADE_LAUNCH_MOM(0, bfd::kGeom); }
+            }
+        } else if (lp->multi) {
+            BF_SHADE_LAUNCH_MOM_F(bfd::kMulti)
+        } else if (lp->lean && !lp->wide) {
+            BF_SHADE_LAUNCH_MOM_F(bfd::kLean)
+        } else if (lp->wide) {
+            BF_SHADE_LAUNCH_MOM_F(bfd::kWide)
+        } else {
+            BF_SHADE_LAUNCH_MOM_F(0)
+        }
+        return hipGetLastError();
+    }
+#undef BF_SHADE_LAUNCH_MOM_F
+#undef BF_SHADE_LAUNCH_MOM
+#else
+    if (moment) return hipErrorInvalidValue;
+#endif
     if (lp->geom_stride) {
         // per-render geometry versions (bf_render_motion_batch_device): three waves per SIMD; never a rolling sequence, so
         // neither its evicting (3) nor its wake (2) launch
@@ -801,6 +842,18 @@ extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd
 #undef BF_SHADE_LAUNCH_RX
     return hipGetLastError();
 }
+extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                   hipStream_t stream, int waves) {
+    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false);
+}
+#if !BF_FAST
+extern "C" hipError_t bfk_wf_shade_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                          float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                          hipStream_t stream, int waves) {
+    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, true);
+}
+#endif
 
 extern "C" hipError_t BF_LAUNCHER(bfk_wf_trace)(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
                                    hipStream_t stream, int waves) {

@@ -189,6 +189,20 @@ int bfh_integrator_launch(void *integrator, void *endpoint, bf_launch *out) {
         }
     })
 }
+/// SamplingIntegrator::aov_names(), newline-separated, into buf (truncated to cap); *need = the length of the whole list
+int bfh_integrator_aov_names(void *integrator, char *buf, int cap, int *need) {
+    BFH_TRY({
+        auto *in = dynamic_cast<SamplingIntegrator *>((Object *) integrator);
+        if (!in) Throw("object is not a SamplingIntegrator");
+        std::string s;
+        for (auto &n : in->aov_names()) s += n + "\n";
+        if (cap > 0) {
+            std::strncpy(buf, s.c_str(), (size_t) cap - 1);
+            buf[cap - 1] = 0;
+        }
+        if (need) *need = (int) s.size();
+    })
+}
 int bfh_integrator_render(void *integrator, void *scene, void *sensor) {
     BFH_TRY({
         auto *in = dynamic_cast<Integrator *>((Object *) integrator);

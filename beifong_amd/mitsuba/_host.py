@@ -58,6 +58,7 @@ def lib():
     l.bfh_scene_device.argtypes = [vp, vp]
     l.bfh_scene_device.restype = vp
     l.bfh_integrator_launch.argtypes = [vp, vp, C.POINTER(capi.bf_launch)]
+    l.bfh_integrator_aov_names.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
     l.bfh_integrator_render.argtypes = [vp, vp, vp]
     l.bfh_integrator_receive.argtypes = [vp, vp, vp]
     l.bfh_integrator_stats.argtypes = [vp, C.POINTER(capi.bf_stats), C.POINTER(C.c_double)]
@@ -530,6 +531,14 @@ class Integrator(_Handle):
         lp = capi.bf_launch()
         check(lib().bfh_integrator_launch(self._ptr, endpoint._ptr, C.byref(lp)))
         return lp
+
+    def aov_names(self):
+        """SamplingIntegrator::aov_names(): the channels the integrator adds behind X Y Z A W (Y A W of an ADC)."""
+        need = C.c_int()
+        check(lib().bfh_integrator_aov_names(self._ptr, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value + 1)
+        check(lib().bfh_integrator_aov_names(self._ptr, buf, need.value + 1, C.byref(need)))
+        return [n for n in buf.value.decode().split("\n") if n]
 
     def stats(self):
         st, ms = capi.bf_stats(), C.c_double()

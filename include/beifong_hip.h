@@ -317,6 +317,27 @@ enum {
                                   Implied by BF_FLAG_STATS and by a non-NULL stats_out; without any of them the counters stay
                                   zero — adding them up costs every shading launch ~10 same-line atomics per wave.  Set it on
                                   every render of a sequence. */
+    BF_FLAG_MOMENT = 512u,     /* moment integrator (src/integrators/moment.cpp:33-53,87-91 around the launch's mode): next to
+                                  every first-moment channel the histogram carries the sum of the SQUARED samples, so one
+                                  render gives the variance of every bin.  Channel layout per pixel (render modes; A nested
+                                  AOVs: 0 path, bins range, 3 bins time):
+                                    X Y Z A W | nested AOVs | nested.X nested.Y nested.Z | m2_(nested AOVs) | m2_nested.X .Y .Z
+                                  = 5 + 2 (A + 3) channels.  nested.XYZ is the XYZ of the UNWEIGHTED nested result (what the
+                                  range / time AOVs see: no sensor weight); each m2_ addend is the fp32 product x * x of the
+                                  value its first-moment channel received from that sample.  A sample whose square is not
+                                  finite is dropped from ALL channels and counted in n_invalid (ImageBlock::put refuses a
+                                  sample with any non-finite channel).  Under a reconstruction filter wider than a pixel the
+                                  m2_ channels are filtered like every other channel (addend w * x * x).
+                                  Receive modes have no counterpart in the reference; per ADC cell:
+                                    RAW  Y A W [phase bins] m2_Y          IQ  I Q W m2_I m2_Q
+                                  with the squares of the values added to Y, I and Q.
+                                  Combines with batches, motion / deform batches, rolling sequences (also across endpoint
+                                  updates), sharded renders and bf_allreduce_device (second moments add linearly),
+                                  BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL, multi-pixel films, crop and ADC windows.  LDS
+                                  privatisation is decided on the moment channel count.  Refused (BF_ERR_INVALID) together
+                                  with BF_FLAG_FAST: the fast contract says nothing about squares.  A rolling render whose
+                                  BF_FLAG_MOMENT differs from the open sequence's fails with BF_ERR_INVALID and leaves the
+                                  sequence intact.  bf_stats.kernel_variant carries BF_VARIANT_MOMENT. */
     BF_FLAG_DOPPLER = 8u       /* receive modes: the Doppler hook the reference carries commented out
                                   ("Took doppler out to test", pathtimefrequency.cpp:124-126,141-144,180-183):
                                   the path's wavelength is shifted by Shape::doppler(si) =
@@ -372,10 +393,11 @@ typedef struct bf_stats {
                                   film, ...: every radar scene of the reference) and everything else is compiled out of the
                                   kernels; BF_VARIANT_WIDE = reconstruction filter wider than a pixel; 0 = general kernels.
                                   Same results either way (BF_LEAN=0 in the environment forces the general ones).  ORed with
-                                  BF_VARIANT_FAST when the fast-arithmetic build ran (BF_FLAG_FAST)                           */
+                                  BF_VARIANT_FAST when the fast-arithmetic build ran (BF_FLAG_FAST) and with BF_VARIANT_MOMENT
+                                  when the kernels' second-moment variants ran (BF_FLAG_MOMENT)                                */
     uint32_t reserved_;
 } bf_stats;
-enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4 };
+enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4, BF_VARIANT_MOMENT = 8 };
 
 typedef struct bf_scene_info {
     uint32_t n_shapes, n_rects, n_triangles, n_bvh_nodes;
@@ -552,7 +574,9 @@ bf_status bf_scene_get_info(const bf_scene *scene, bf_scene_info *info);
 bf_status bf_scene_clone(const bf_scene *scene, bf_scene **out);
 
 /* number of floats the given launch accumulates into: 5 (+bins | +3*bins) for
- * the 1x1 film modes, f_bins*t_bins*3 ([y=f][x=t][Y,A,W]) for receive */
+ * the 1x1 film modes, f_bins*t_bins*3 ([y=f][x=t][Y,A,W]) for receive; with
+ * BF_FLAG_MOMENT the layout documented at the flag: 5 + 2 (A + 3) per pixel,
+ * 4 + phase_bins (RAW) or 5 (IQ) per ADC cell */
 uint32_t bf_launch_channels(const bf_launch *launch);
 
 /* Render into a DEVICE buffer hist_dev[film_h*film_w*channels] (accumulates;
