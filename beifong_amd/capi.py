@@ -233,6 +233,10 @@ def load_library(path=None):
     lib.bf_ray_intersect_device.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bf_trace_any_device.argtypes = [vp, C.c_uint64, vp, vp, vp]
     lib.bf_eval_microfacet.argtypes = [C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint64, vp, vp]
+    # test hooks (not in include/beifong_hip.h, not part of the ABI)
+    if hasattr(lib, "bfdbg_scene_read_tree"):
+        lib.bfdbg_scene_origin_scale.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.bfdbg_scene_read_tree.argtypes = [vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp]
     if path is None:
         _lib = lib
     return lib
@@ -571,6 +575,38 @@ class Scene:
         check(self.lib, self.lib.bf_scene_read_bvh(self.handle, width, _ptr(nodes) if n else None, nodes.nbytes,
                                                    _ptr(rows) if rows.size else None, C.byref(root)), "bf_scene_read_bvh")
         return nodes, rows, int(root.value)
+
+    def debug_origin_scale(self):
+        """test hook bfdbg_scene_origin_scale: the ray-origin bound the handle's boxes are padded for, as a numpy float32"""
+        out = C.c_float(0.0)
+        check(self.lib, self.lib.bfdbg_scene_origin_scale(self.handle, C.byref(out)), "bfdbg_scene_origin_scale")
+        return np.float32(out.value)
+
+    def debug_read_tree(self, which, version=-1):
+        """test hook bfdbg_scene_read_tree: (nodes, rows, normals) as the device holds them.  which = 4 / 16: NODE4_DTYPE /
+        NODE16_DTYPE nodes, 64: the quantised nodes as uint32[n, 16]; version = -1: the handle's own arrays, k >= 0: geometry
+        version k of its last motion / deform batch.  rows, normals: float32[n_triangles, 3, 4] (normals: None if the scene
+        has none)."""
+        which, version = int(which), int(version)
+        if which not in (4, 16, 64):
+            raise ValueError(f"debug_read_tree: which {which} (4, 16 or 64)")
+        item = {4: NODE4_DTYPE.itemsize, 16: NODE16_DTYPE.itemsize, 64: 64}[which]
+        n = 0
+        st = self.lib.bfdbg_scene_read_tree(self.handle, which, version, None, 1, None, None)      # learns the size, as read_bvh
+        if st != BF_OK:
+            m = re.search(r"needs (\d+) bytes", self.lib.bf_last_error().decode())
+            if st != BF_ERR_INVALID or not m:
+                check(self.lib, st, "bfdbg_scene_read_tree")
+            n = int(m.group(1)) // item
+        nodes = np.zeros(n, dtype=NODE4_DTYPE if which == 4 else NODE16_DTYPE) if which != 64 else np.zeros((n, 16), np.uint32)
+        nt = self.info().n_triangles
+        rows = np.zeros((nt, 3, 4), np.float32)
+        normals = np.full((nt, 3, 4), np.nan, np.float32)
+        check(self.lib, self.lib.bfdbg_scene_read_tree(self.handle, which, version, _ptr(nodes) if n else None, nodes.nbytes,
+                                                       _ptr(rows) if nt else None, _ptr(normals) if nt else None), "bfdbg_scene_read_tree")
+        if nt == 0 or np.isnan(normals[0, 0, 0]):      # (left alone: the scene has no vertex normals; the library refuses NaN normals)
+            normals = None
+        return nodes, rows, normals
 
     def info(self):
         i = bf_scene_info()

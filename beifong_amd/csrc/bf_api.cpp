@@ -313,6 +313,10 @@ struct bf_scene {
     // of the previous call like every other write of the handle (order_after_last)
     float4 *motion_arena = nullptr;
     size_t motion_cap = 0;                      // float4 rows allocated
+    // the versions the last motion / deform batch left in the arena, for bfdbg_scene_read_tree: 0 if that batch was chunked (the
+    // arena then holds its last chunk only), failed, or a rebuild has changed the layout since
+    uint32_t batch_versions = 0;
+    size_t batch_rows = 0;                      // float4 rows per version of that batch
     // bf_scene_update_vertices: the update writes the handle's BASE rows (tris0 / normals0), which must then be the
     // handle's own allocations, and runs the handle's latest pose on top of them.  pose_kind: 0 none, 1 a translation, 2 a rigid
     // table; pose_xf: the table as bfk_launch_rigid reads it (16 floats per shape).  Once `deformed`, the boxes of nodes0 / wnodes0
@@ -975,8 +979,11 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     const bool use_wide = !btris.empty() && 16u * std::max(1u, bvh16.max_depth) <= (uint32_t) bfd::kWideStack &&
                           btris.size() < (1u << 27) && !sc->tun.no_wide;
     if (sc->tun.wide_rows_log >= 0) wide_rlog = std::min<uint32_t>(wide_rlog, (uint32_t) sc->tun.wide_rows_log);
-    for (int k = 0; k < 3 && !btris.empty(); ++k)
-        sc->origin_scale_built = std::max({sc->origin_scale_built, std::fabs(bvh.lo[k]), std::fabs(bvh.hi[k])});
+    // ray origins also lie on the meshes: the largest |coordinate| of a vertex (the vertices themselves, as bf_scene_rebuild_bvh
+    // takes them: the builder's padded scene box would overstate the bound by its own padding)
+    for (const bf::BuildTri &t : btris)
+        for (int k = 0; k < 3; ++k)
+            sc->origin_scale_built = std::max({sc->origin_scale_built, std::fabs(t.p0[k]), std::fabs(t.p1[k]), std::fabs(t.p2[k])});
     // (+ kTriPad rows of padding behind the last triangle)
     std::vector<float4> tri_data(bfd::kTriStride * btris.size() + (btris.empty() ? 0 : kTriPad), make_float4(0, 0, 0, 0)), nrm_data;
     if (any_normals) nrm_data.resize(3 * btris.size());
@@ -1973,6 +1980,7 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
     if (posed) scene->deformed = true;
     // the level lists follow the topology: rebuilt at the next refit; the per-mesh boxes and the transform table do not depend on it
     scene->refit.ready = false;
+    scene->batch_versions = 0;
     scene->refit.lvl4 = scene->refit.lvl16 = nullptr;
     scene->refit.ubox4 = scene->refit.ubox16 = nullptr;
     scene->refit.off4.clear();
@@ -3207,6 +3215,7 @@ static bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint3
     view.wnodes = scene->d.wnodes ? a + L.wnodes : nullptr;
     view.qnodes = scene->d.qnodes ? a + L.qnodes : nullptr;
     if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+    scene->batch_versions = 0;
     for (uint32_t k0 = 0; k0 < n_renders; k0 += per_chunk) {
         const uint32_t kc = std::min(per_chunk, n_renders - k0);
         bf_status st = prepare(k0, kc, a, L);
@@ -3221,6 +3230,7 @@ static bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint3
         if (st != BF_OK) return st;
         if (stats_out) add_stats(*stats_out, cs);
     }
+    if (n_renders <= per_chunk) scene->batch_versions = n_renders, scene->batch_rows = L.rows;
     return BF_OK;
 }
 
@@ -3465,6 +3475,62 @@ bf_status bfdbg_preload_guard(bf_scene *scene, unsigned long long n) {
     if (!scene) return fail(BF_ERR_INVALID, "null argument");
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(scene->counters + bfd::CTR_GUARD, &n, sizeof(n), hipMemcpyHostToDevice));
+    return BF_OK;
+}
+
+/* test hook (not part of the ABI): the ray-origin bound the handle's boxes are padded for (bf_bvh.h) */
+bf_status bfdbg_scene_origin_scale(const bf_scene *scene, float *out) {
+    if (!scene || !out) return fail(BF_ERR_INVALID, "bfdbg_scene_origin_scale: null argument");
+    *out = scene->origin_scale_built;
+    return BF_OK;
+}
+
+/* test hook (not part of the ABI): what the device wrote, read back.  which = 4 / 16: the Node4 / Node16 array; 64: the Node4Q
+   array (BF_ERR_UNSUPPORTED unless the scene was created under BF_QUANT_BVH=1).  version = -1: the handle's own arrays; k >= 0:
+   geometry version k of the handle's last motion / deform batch, from the arena (BF_ERR_INVALID if that batch was chunked or k
+   is out of range).  nodes_out (`bytes` of it, at least the array's size; a call with too few fails with the text "needs <n>
+   bytes", as bf_scene_read_bvh), rows_out (float4[n_triangles][3]) and normals_out (float4[n_triangles][3], the posed vertex
+   normals; left alone if the scene has none) may each be NULL.  Finishes the open sequence and waits for the handle's last work. */
+bf_status bfdbg_scene_read_tree(const bf_scene *scene, uint32_t which, int32_t version, void *nodes_out, uint64_t bytes, float *rows_out,
+                                float *normals_out) {
+    if (!scene) return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: null scene");
+    if (which != 4u && which != 16u && which != 64u) return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: which = %u (4, 16 or 64)", which);
+    BF_ENTER(scene);
+    {
+        bf_status cst = close_sequence(scene, scene->roll.stream);
+        if (cst != BF_OK) return cst;
+    }
+    if (scene->has_last) HIP_TRY(hipEventSynchronize(scene->last_done));
+    const bfd::DScene &d = scene->d;
+    if (which == 16u && !d.wnodes) return fail(BF_ERR_UNSUPPORTED, "bfdbg_scene_read_tree: the scene has no sixteen-wide tree");
+    if (which == 64u && !d.qnodes) return fail(BF_ERR_UNSUPPORTED, "bfdbg_scene_read_tree: the scene has no quantised nodes (BF_QUANT_BVH=1)");
+    const float4 *tris = d.tris, *normals = d.normals, *nodes = d.nodes, *wnodes = d.wnodes, *qnodes = d.qnodes;
+    if (version >= 0) {
+        const MotionLayout L = motion_layout(scene);
+        if (!scene->motion_arena || (uint32_t) version >= scene->batch_versions || L.rows != scene->batch_rows)
+            return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: version %d: the handle's last batch left %u whole versions in its arena "
+                                        "(none if it was chunked)", version, scene->batch_versions);
+        const float4 *a = scene->motion_arena + (size_t) version * L.rows;
+        tris = a + L.tris;
+        normals = d.normals ? a + L.normals : nullptr;
+        nodes = a + L.nodes;
+        wnodes = d.wnodes ? a + L.wnodes : nullptr;
+        qnodes = d.qnodes ? a + L.qnodes : nullptr;
+    } else if (version != -1) {
+        return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: version %d", version);
+    }
+    const uint64_t need = which == 4u ? (uint64_t) d.n_nodes * sizeof(bf::Node4)
+                        : which == 16u ? (uint64_t) d.n_wnodes * sizeof(bf::Node16) : (uint64_t) d.n_nodes * sizeof(bf::Node4Q);
+    if (nodes_out || bytes) {
+        if (bytes < need || (need && !nodes_out))
+            return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: nodes_out needs %llu bytes (%llu given)", (unsigned long long) need,
+                        (unsigned long long) bytes);
+        if (need) HIP_TRY(hipMemcpy(nodes_out, which == 4u ? nodes : (which == 16u ? wnodes : qnodes), need, hipMemcpyDeviceToHost));
+    }
+    const size_t row_bytes = (size_t) d.n_tris * 3 * sizeof(float4);
+    static_assert(bfd::kTriStride == 3, "rows_out is float4[n_triangles][3]");
+    if (rows_out && d.n_tris) HIP_TRY(hipMemcpy(rows_out, tris, row_bytes, hipMemcpyDeviceToHost));
+    if (normals_out && normals && d.n_tris) HIP_TRY(hipMemcpy(normals_out, normals, row_bytes, hipMemcpyDeviceToHost));
     return BF_OK;
 }
 

@@ -833,8 +833,10 @@ __global__ void bf_translate_kernel(const float4 *__restrict__ tris0, float4 *__
         float4 lx = s[0], ly = s[1], lz = s[2], hx = s[3], hy = s[4], hz = s[5];
         // shifted vertices are rounded to fp32 again (half an ulp each) and the fma slab test allows for
         // 2^-24 |origin| (bf_bvh.h): re-pad every box by 2.4e-7 of its largest shifted coordinate
+        // an unused slot (kNoNode) keeps its inverted box (+inf, -inf) as it is: inf - 2.4e-7 inf would be NaN
+        const float4 refs = s[6];
 #define BF_SHIFT(L, H, D, K)                                                                                  \
-    {                                                                                                         \
+    if (__float_as_int(refs.K) != kNoNode) {                                                                  \
         float lo = L.K + D, hi = H.K + D;                                                                     \
         float e = 2.4e-7f * __builtin_fmaxf(__builtin_fabsf(lo), __builtin_fabsf(hi));                        \
         L.K = lo - e;                                                                                         \
@@ -845,14 +847,18 @@ __global__ void bf_translate_kernel(const float4 *__restrict__ tris0, float4 *__
         BF_SHIFT(lz, hz, dz, x) BF_SHIFT(lz, hz, dz, y) BF_SHIFT(lz, hz, dz, z) BF_SHIFT(lz, hz, dz, w)
 #undef BF_SHIFT
         o[0] = lx; o[1] = ly; o[2] = lz; o[3] = hx; o[4] = hy; o[5] = hz;
-        o[6] = s[6];
+        o[6] = refs;
         o[7] = s[7];
-        if (qnodes) quantise_node4_dev(lx, ly, lz, hx, hy, hz, s[6], qnodes + 4u * i);      // re-quantised for wf_trace
+        if (qnodes) quantise_node4_dev(lx, ly, lz, hx, hy, hz, refs, qnodes + 4u * i);      // re-quantised for wf_trace
     }
     if (i < n_wchildren) {                      // one child record of a sixteen-wide node (bf_bvh.h: Node16), same re-padding
         const float4 a = wnodes0[2u * i], b = wnodes0[2u * i + 1u];
-        float lo[3] = {a.x + dx, a.y + dy, a.z + dz}, hi[3] = {a.w + dx, b.x + dy, b.y + dz};
-        for (int k = 0; k < 3; ++k) {
+        const bool used = __float_as_int(b.z) != kNoNode;      // (an unused slot stays inverted, as above)
+        float lo[3] = {a.x, a.y, a.z}, hi[3] = {a.w, b.x, b.y};
+        const float d[3] = {dx, dy, dz};
+        for (int k = 0; used && k < 3; ++k) {
+            lo[k] += d[k];
+            hi[k] += d[k];
             const float e = 2.4e-7f * __builtin_fmaxf(__builtin_fabsf(lo[k]), __builtin_fabsf(hi[k]));
             lo[k] -= e;
             hi[k] += e;

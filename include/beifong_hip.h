@@ -554,7 +554,9 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream);
  * width 4: bf_scene_info::n_bvh_nodes nodes of 128 bytes (lo.x[4], lo.y[4], lo.z[4], hi.x[4], hi.y[4], hi.z[4], child[4], pad[4]);
  * width 16: the tail kernel's nodes of 512 bytes (16 child records of 8 words: lo.xyz, hi.xyz, reference, 0).  A child reference
  * >= 0 is a node index; < 0 is a leaf, ~ref = (first_slot << 3 | count - 1) for width 4, (first_slot << 4 | count - 1) for
- * width 16; INT32_MIN marks an unused slot (inverted box).  tri_rows_out (or NULL): the 12 floats of every triangle slot in
+ * width 16; INT32_MIN marks an unused slot.  An unused slot's box is inverted, exactly lo = +inf and hi = -inf on every axis, in the
+ * tree as created and after every call that rewrites the boxes (translate, transform, vertex update, rebuild): a kernel may rely on
+ * the box alone to reject it.  tri_rows_out (or NULL): the 12 floats of every triangle slot in
  * leaf order (three rows of x, y, z and a word: primitive, shape, tag).  *root_child: the root's child reference.
  * nodes_bytes too small: BF_ERR_INVALID, and bf_last_error() says "needs <n> bytes"; width 16 on a scene without the
  * sixteen-wide tree (BF_NO_WIDE_BVH, no triangles): BF_ERR_UNSUPPORTED. */
