@@ -1,19 +1,14 @@
 // C ABI of libbeifong_hip.so (include/beifong_hip.h): scene flattening, BVH
 // build, device upload and kernel launches.  Plain pointers and sizes in,
 // integer status out; no exceptions cross the boundary.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <limits>
-#include <memory>
 #include <new>
 #include <string>
-#include <vector>
 
 #include <dlfcn.h>
 // RCCL is dlopen'ed on first use (bf_allreduce_device); only the handful of types and prototypes below are needed, so a ROCm
@@ -40,30 +35,12 @@ const char *ncclGetErrorString(ncclResult_t result);
 #include <map>
 #include <mutex>
 
-#include "bf_build.h"
-#include "bf_bvh.h"
-#include "bf_device.h"
-#include "bf_wavefront.h"
+#include "bf_scene.h"
 
 extern "C" hipError_t bfk_launch_render(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
                                         unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
                                         hipStream_t stream);
 extern "C" float bfk_host_cos(float x);
-extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, uint32_t n_tri_rows, const float4 *nodes0,
-                                           float4 *nodes, float4 *qnodes, uint32_t n_nodes, const float4 *wnodes0, float4 *wnodes,
-                                           uint32_t n_wchildren, const float *d, hipStream_t stream);
-extern "C" hipError_t bfk_launch_deform_tris(const uint4 *corners, const bfd::DDeformSrc *src, const float4 *tris0, float4 *tris, const float4 *nrm0,
-                                             float4 *nrm, uint32_t n_tris, const float *xf, uint32_t n_versions, uint64_t vstride,
-                                             uint32_t xf_stride, float bound, uint32_t *bad, hipStream_t stream);
-extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
-                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes,
-                                       const uint32_t *lvl16, const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad,
-                                       uint32_t n_versions, uint64_t vstride, hipStream_t stream);
-extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
-                                       const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
-                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
-                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
-                                       uint64_t vstride, uint32_t xf_stride, hipStream_t stream);
 extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y);
 extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const float *rays, int any_hit, float *out_t,
                                        uint32_t *out_prim, uint32_t *out_shape, float *out_uv, uint8_t *out_hit,
@@ -123,9 +100,7 @@ const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_t
 const Kernels &kernels_for(uint32_t flags) { return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : kExact); }
 }  // namespace
 
-namespace {
-
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 bf_status fail(bf_status st, const char *fmt, ...) {
     char buf[512];
@@ -137,12 +112,7 @@ bf_status fail(bf_status st, const char *fmt, ...) {
     return st;
 }
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(BF_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
+namespace {
 template <typename T> bf_status upload(const std::vector<T> &v, const T **out, std::vector<void *> &owned, uint64_t &bytes) {
     *out = nullptr;
     if (v.empty()) return BF_OK;
@@ -179,48 +149,6 @@ inline V3 normalize(V3 a) {
 
 }  // namespace
 
-// The big read-only arrays of a scene (BVH nodes, triangles, normals, texture coordinates): shared by a scene and its
-// clones (bf_scene_clone), freed with the last of them.
-struct bf_geometry {
-    std::vector<void *> owned;
-    // vertex updates (bf_scene_update_vertices): what every mesh shape was created with, and the device corner
-    // table built from it at the first update of any handle that shares these arrays (one uint4 per triangle slot in leaf order:
-    // the slot's three vertex indices within its shape, then the shape)
-    struct MeshTopo {
-        uint32_t n_vertices = 0, n_faces = 0, prim0 = 0;
-        bool has_normals = false;
-        std::vector<uint32_t> indices;
-    };
-    std::vector<MeshTopo> topo;            // per shape (non-mesh shapes: empty)
-    uint4 *corners = nullptr;
-    ~bf_geometry() {
-        for (void *p : owned) (void) hipFree(p);
-    }
-};
-
-// Developer overrides, read from the environment ONCE, when a scene is created; clones inherit them.
-struct bf_tunables {
-    uint32_t pool = 1u << 24;                // BF_WF_POOL
-    int64_t tail = -1;                       // BF_WF_TAIL (-1: by pool size)
-    uint32_t trace_refill = bfd::kTraceRefill, trace_stragglers = bfd::kTraceStragglers;
-    uint32_t shade_chain = bfd::kShadeChain, row_jobs = bfd::kTailRowJobs;
-    int shade_waves = 3, trace_waves = 5, tail_waves = 3;
-    unsigned tail_spread = 1, tail_blocks = 0;
-    int tail_share = -1;                     // BF_TAIL_SHARE: waves per batch in a stand-alone render's tail (-1: by pool size)
-    bool allow_plan = true;                  // BF_WF_SYNC=1 turns launch plans off
-    uint32_t roll_iters = 0;                 // BF_ROLL_ITERS: bounce iterations per call of a rolling sequence (0: adaptive)
-    uint32_t roll_live = 0;                  // BF_ROLL_LIVE: a rolling call stops iterating once at most this many slots are alive (0: max(1.5 x 2^20, main slots / 4))
-    bool no_wide = false, quant = false;
-    int wide_rows_log = -1;
-    bool lean = true;                        // BF_LEAN=0: never use the kernels' lean variants (bf_device.h: kLean)
-    bool tab_cache = true;                   // BF_TAB_CACHE=0: materials / rectangles stay in device memory (no LDS copies)
-    bool shade_split = false;                // BF_SHADE_SPLIT=1: wf_shade walks the alive masks twice: slots without a real hit first, real hits second (measured: no net gain)
-    uint32_t chain_min = 16;                 // BF_CHAIN_MIN: resolved real hits chain only while at least this many lanes hold one (0: always)
-    uint32_t grid_share = 3;                 // BF_GRID_SHARE: small pools (< grid_small slots) of handles that roll side by side launch 1 / min(peers, this) of the persistent grids (0 / 1: off)
-    uint32_t grid_small = 1u << 22;          // BF_GRID_SMALL
-    bool roll_join = true;                   // BF_ROLL_JOIN=0: bf_scene_update_endpoints flushes an open rolling sequence (round 3's behaviour)
-    uint32_t debug_surv_batches = 0;         // BF_DEBUG_SURV_BATCHES (tests): size of the survivor area in batches, sizing rule off
-};
 static bf_tunables read_tunables() {
     bf_tunables t;
     auto num = [](const char *name, long long dflt) -> long long {
@@ -258,206 +186,6 @@ static bf_tunables read_tunables() {
     t.debug_surv_batches = (uint32_t) std::max<long long>(0, std::min<long long>(num("BF_DEBUG_SURV_BATCHES", 0), 1 << 14));
     return t;
 }
-
-struct bf_scene {
-    bfd::DScene d;
-    bf_tunables tun;
-    std::shared_ptr<bf_geometry> geom;     // nodes / wnodes / tris / normals / uvs as created
-    // handles that render the SAME triangle / node arrays hold the same token (a clone that took its own snapshot of a
-    // translated scene does not): bf_scene_translate_meshes copies on write only while the token is shared
-    std::shared_ptr<char> geom_token;
-    // handles cloned from one another are meant to be in flight together (one per stream): how many of them have a rolling sequence
-    // open right now — small pools then launch a share of the persistent grids each (wf_setup: grid_share)
-    std::shared_ptr<std::atomic<int>> peers_rolling;
-    bool geom_private = false;             // d.tris / d.nodes / d.wnodes point at this handle's own translated copies
-    // one host thread at a time per handle (the handle owns the path pool its render's state lives in)
-    mutable std::atomic_flag busy = ATOMIC_FLAG_INIT;
-    // stream order between successive renders of the handle: a render on another stream than the previous one waits for it
-    mutable hipStream_t last_stream = nullptr;
-    mutable hipEvent_t last_done = nullptr;
-    mutable bool has_last = false;
-    std::vector<void *> owned;             // this handle's own allocations (small tables, spill columns, private geometry)
-    bf_scene_info info;
-    int device = 0;
-    int n_cus = 256;
-    std::vector<uint32_t> emitter_types;
-    // per-scene scratch for bf_render_device (counters), allocated once
-    unsigned long long *counters = nullptr;
-    // wavefront workspace, allocated on first use (mutable: lazily grown cache)
-    mutable bfd::WF wf;
-    mutable std::vector<void *> wf_owned;
-    uint32_t n_materials = 0;
-    bool any_back_material = false;        // some twosided material has a second nested BSDF (general kernels)
-    bool any_resample = false;             // some transmitter re-samples the path's wavelength (resample_freq: general kernels, DLaunch::resample)
-    bfd::DSensor sensor_host;              // host copy of the device sensor record
-    mutable uint32_t last_variant = 0;     // BF_VARIANT_* of the latest render (bf_stats.kernel_variant)
-    uint32_t film_w = 1, film_h = 1;       // the sensor's film (bf_sensor.film_width / film_height)
-    uint32_t adc_t = 0, adc_f = 0;         // what a receive-mode launch bins into: the ADC's window, or the whole ADC
-    float4 *tris0 = nullptr, *nodes0 = nullptr, *wnodes0 = nullptr;   // pristine geometry, kept once bf_scene_translate_meshes is used
-    // bf_scene_transform_meshes: the pristine vertex normals once a transform has moved them, whether d.normals is
-    // this handle's own array (copy on write, as geom_private for the rest) and whether it holds moved normals now
-    float4 *normals0 = nullptr;
-    bool normals_private = false, normals_moved = false;
-    // the refit's state, built on the handle's first transform (nothing of it costs bf_scene_create anything)
-    struct Refit {
-        bool ready = false;
-        bool have_boxes = false;                 // xf and mesh_box exist (they survive bf_scene_rebuild_bvh: neither depends on the slot order)
-        std::vector<uint32_t> off4, off16;       // level d of the four- / sixteen-wide tree: [off[d], off[d + 1]) of lvl4 / lvl16
-        uint32_t *lvl4 = nullptr, *lvl16 = nullptr;
-        float4 *ubox4 = nullptr, *ubox16 = nullptr;      // unpadded bounds of every child record (two float4 each)
-        float *xf = nullptr;                     // device: 16 floats per shape (bfk_launch_rigid)
-        std::vector<float> mesh_box;             // per shape: lo.xyz, hi.xyz of its pristine triangles (inverted: none)
-    } refit;
-    // bf_render_motion_batch_device: the geometry versions of a batch's renders, one every `motion_rows` float4 rows.
-    // The handle's own (never shared with clones), grown on demand, freed with the handle; stream-ordered behind the renders
-    // of the previous call like every other write of the handle (order_after_last)
-    float4 *motion_arena = nullptr;
-    size_t motion_cap = 0;                      // float4 rows allocated
-    // the versions the last motion / deform batch left in the arena, for bfdbg_scene_read_tree: 0 if that batch was chunked (the
-    // arena then holds its last chunk only), failed, or a rebuild has changed the layout since
-    uint32_t batch_versions = 0;
-    size_t batch_rows = 0;                      // float4 rows per version of that batch
-    // bf_scene_update_vertices: the update writes the handle's BASE rows (tris0 / normals0), which must then be the
-    // handle's own allocations, and runs the handle's latest pose on top of them.  pose_kind: 0 none, 1 a translation, 2 a rigid
-    // table; pose_xf: the table as bfk_launch_rigid reads it (16 floats per shape).  Once `deformed`, the boxes of nodes0 / wnodes0
-    // no longer bound the base rows (only their topology is read), so translations run through the refit too.
-    bool base_private = false, normals0_private = false, deformed = false;
-    int pose_kind = 0;
-    std::vector<float> pose_xf;
-    // the device forms' violation counter ([0] slots refused, [1] a refused shape + 1), its pinned mirror and the event behind the
-    // copy that follows every device-form gather
-    uint32_t *deform_bad = nullptr, *deform_bad_host = nullptr;
-    hipEvent_t deform_ev = nullptr;
-    mutable bool deform_pending = false;
-    mutable uint32_t deform_reported = 0;       // of the device count, how much has been reported already
-    // the host form's upload buffer (pinned + device mirror), grown on demand; vtx_ev: behind the gather that read it last
-    void *vtx_host = nullptr, *vtx_dev = nullptr;
-    size_t vtx_cap = 0;
-    hipEvent_t vtx_ev = nullptr;
-    // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
-    std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
-    std::vector<float *> array_dev;
-    std::vector<uint32_t> array_n;
-    float *sensor_array_dev = nullptr;
-    uint32_t sensor_array_n = 0;
-    float origin_scale_built = 0.f;        // ray-origin bound the BVH boxes were padded for (bf_bvh.h)
-    mutable uint32_t *wf_host = nullptr;   // pinned read-back of queue counters
-    mutable hipEvent_t wf_event = nullptr;
-    mutable unsigned long long *wf_masks = nullptr;
-    mutable std::vector<hipEvent_t> wf_timing;   // event pool for per-kernel timing (stats only): pair k = events 2k, 2k + 1
-    mutable std::vector<int> wf_ev_kind;         // kind of every recorded pair: 0 trace, 1 shade, 2 tail
-    mutable float wf_ms[3] = {0, 0, 0};          // trace, shade, tail of the last stats render / rolling sequence
-    mutable uint32_t wf_iters = 0, wf_trace_launches = 0, wf_tail_launches = 0, wf_shade_launches = 0;
-    // Rolling sequence (bf_render_device with BF_FLAG_ROLLING, bf_scene_flush): see wf_roll_render
-    struct Roll {
-        bool open = false;
-        uint32_t count = 0;                      // renders issued since the sequence was opened
-        uint32_t it = 0;                         // bounce-iteration counter (mask parity runs on across calls)
-        bf_launch shape;                         // launch of the first render: later ones may differ in seed / path_offset only
-        bfd::DLaunch lp;                         // device launch of the sequence (n_paths = supply so far)
-        hipStream_t stream = nullptr;
-        bool count_nodes = false, timed = false;
-        uint32_t per_call = 1;                   // renders every call adds (bf_render_batch_device: the batch size)
-        bool offsets = false;                    // the renders carry mesh offsets (batched calls with moving meshes)
-        float dmax = 0.f;                        // largest |offset component| so far (box slack of the SHIFT traversal)
-        uint32_t window = 1;                     // renders of the LDS histogram window
-        uint32_t iters = 0;                      // bounce iterations per call (adapted from the live counts)
-        uint32_t flush_iters = 0;                // planned bounce iterations of a flush before its tail (learned)
-        uint32_t flush_live = 0;                 // slots alive at the flush's tail (learned: sizes its grid)
-        bool multi = false;                      // the endpoints moved between the renders of the sequence (kMulti kernels from then on)
-        uint32_t fb_call_iters = 0;              // iterations of the call whose live counts are in flight to wf_feedback
-        bool fb_is_flush = false;
-    };
-    mutable Roll roll;
-    // Endpoint-table versions of an open rolling sequence: bf_scene_update_endpoints writes the new tables into the next block of
-    // a pool instead of flushing the sequence (the renders issued so far keep reading theirs through the descriptor ring:
-    // bf_device.h: DRoll, kMulti); the home buffers (as created) hold the tables whenever no sequence is open.
-    struct TabLayout {
-        size_t o_rects = 0, o_shapes = 0, o_emit = 0, o_mat = 0, o_sensor = 0, stride = 0;
-    };
-    mutable TabLayout tab;
-    mutable char *tab_pool = nullptr;            // device: kRollRing blocks of tab.stride bytes (allocated on first use)
-    mutable uint32_t tab_next = 0;               // next free block
-    mutable bool tables_in_pool = false;         // d.rects ... d.sensor point into the pool
-    const bfd::DRect *home_rects = nullptr;
-    const bfd::DShape *home_shapes = nullptr;
-    const bfd::DEmitter *home_emitters = nullptr;
-    const bfd::DMaterial *home_materials = nullptr;
-    const bfd::DSensor *home_sensor = nullptr;
-    mutable bfd::DRoll *roll_ring = nullptr;     // device [kRollRing]
-    mutable float4 *roll_offsets = nullptr;      // device [kRollRing]: mesh offset of every render of the sequence
-    // Launch plan learned from the previous render of the same shape (wf_render): how many bounce
-    // iterations precede the tail and how many slots are then alive.  With a plan the whole render is
-    // enqueued without a host round trip; the live counts come back through a pinned buffer afterwards.
-    struct WfPlan {
-        bool valid = false;
-        uint64_t n_paths = 0;
-        uint32_t mode = 0, max_depth = 0, n_slots = 0, tail_max = 0;
-        uint32_t iters = 0, tail_live = 0;
-    };
-    mutable WfPlan wf_plan;
-    // Pinned staging for small host tables that travel with a launch (batch seeds / mesh offsets, endpoint records):
-    // a ring of slots, each with its own device mirror and an event recorded behind the copy, so the caller's arrays
-    // and our stack locals are free again when the call returns and nothing blocks unless kStageSlots launches are in
-    // flight on this scene.
-    static constexpr int kStageSlots = 8;
-    struct Stage {
-        void *host = nullptr, *dev = nullptr;
-        size_t cap = 0;
-        hipEvent_t ev = nullptr;
-        bool busy = false;
-    };
-    mutable Stage stage[kStageSlots];
-    mutable int stage_next = 0;
-    mutable uint32_t *wf_feedback = nullptr;     // pinned: n_live[0 .. wf_fb_iters) of the last planned render
-    mutable hipEvent_t wf_fb_event = nullptr;
-    mutable bool wf_fb_pending = false;
-    mutable uint32_t wf_fb_iters = 0;
-};
-
-// One host thread at a time per handle: the second one gets BF_ERR_INVALID instead of a race on the handle's pool.
-namespace {
-struct BusyGuard {
-    const bf_scene *s;
-    bool ok;
-    int prev_device = -1;
-    // ... and every call runs on the handle's own device, whatever the caller's current one is (one host thread may
-    // drive the handles of several GPUs: bf_render_sharded_device), restored on return
-    explicit BusyGuard(const bf_scene *sc) : s(sc), ok(sc && !sc->busy.test_and_set(std::memory_order_acquire)) {
-        if (ok) {
-            int cur = -1;
-            if (hipGetDevice(&cur) == hipSuccess && cur != sc->device && hipSetDevice(sc->device) == hipSuccess) prev_device = cur;
-        }
-    }
-    ~BusyGuard() {
-        if (prev_device >= 0) (void) hipSetDevice(prev_device);
-        if (ok) s->busy.clear(std::memory_order_release);
-    }
-};
-// the handle's device for the calls that allocate or launch before (or without) taking the busy flag
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int device) {
-        int cur = -1;
-        if (hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess) prev = cur;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void) hipSetDevice(prev);
-    }
-};
-#define BF_ENTER(scene)                                                                                                   \
-    BusyGuard busy_guard_(scene);                                                                                         \
-    if (!busy_guard_.ok)                                                                                                  \
-        return fail(BF_ERR_INVALID, "%s: the scene handle is in use by another host thread (one call at a time per handle; " \
-                                    "bf_scene_clone gives every thread / stream its own)", __func__)
-}  // namespace
-
-static bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
-static bf_status mark_last(const bf_scene *scene, hipStream_t stream);
-static bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
-static bf_status apply_pose(bf_scene *scene, hipStream_t stream);
-static bf_status refit_prepare(bf_scene *scene, hipStream_t stream);
-static bf_status deform_report(const bf_scene *scene, bool wait);
 
 extern "C" {
 
@@ -525,16 +253,6 @@ bf_status bf_scene_destroy(bf_scene *s) {
     for (hipEvent_t e : s->wf_timing) (void) hipEventDestroy(e);
     if (s->counters) (void) hipFree(s->counters);
     if (s->tab_pool) (void) hipFree(s->tab_pool);
-    if (s->motion_arena) (void) hipFree(s->motion_arena);
-    if (s->deform_bad) (void) hipFree(s->deform_bad);
-    if (s->deform_bad_host) (void) hipHostFree(s->deform_bad_host);
-    if (s->deform_ev) (void) hipEventDestroy(s->deform_ev);
-    if (s->vtx_ev) {
-        (void) hipEventSynchronize(s->vtx_ev);
-        (void) hipEventDestroy(s->vtx_ev);
-    }
-    if (s->vtx_host) (void) hipHostFree(s->vtx_host);
-    if (s->vtx_dev) (void) hipFree(s->vtx_dev);
     for (auto &st : s->stage) {
         if (st.ev) {
             (void) hipEventSynchronize(st.ev);
@@ -549,7 +267,7 @@ bf_status bf_scene_destroy(bf_scene *s) {
 
 // Next staging slot with room for `bytes` (see bf_scene::Stage): *host is pinned memory the caller fills, *dev its
 // device mirror; stage_commit() enqueues the copy and the slot's event.
-static bf_status stage_acquire(const bf_scene *sc, size_t bytes, bf_scene::Stage **out) {
+bf_status stage_acquire(const bf_scene *sc, size_t bytes, bf_scene::Stage **out) {
     bf_scene::Stage &st = sc->stage[sc->stage_next];
     sc->stage_next = (sc->stage_next + 1) % bf_scene::kStageSlots;
     if (st.busy) {
@@ -570,21 +288,19 @@ static bf_status stage_acquire(const bf_scene *sc, size_t bytes, bf_scene::Stage
     *out = &st;
     return BF_OK;
 }
-static bf_status stage_commit(bf_scene::Stage *st, size_t bytes, hipStream_t stream) {
+bf_status stage_commit(bf_scene::Stage *st, size_t bytes, hipStream_t stream) {
     HIP_TRY(hipMemcpyAsync(st->dev, st->host, bytes, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(st->ev, stream));
     st->busy = true;
     return BF_OK;
 }
 // the slot only lends its pinned buffer: copies to other device addresses were enqueued by the caller
-static bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream) {
+bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream) {
     HIP_TRY(hipEventRecord(st->ev, stream));
     st->busy = true;
     return BF_OK;
 }
 
-static int32_t bfd_no_node() { return INT32_MIN; }
-static constexpr size_t kTriPad = 4;      // float4 rows of padding behind the triangle array (read by no kernel; part of the geometry layout)
 static_assert(bf::kTopNodes == bfd::kTopNodes, "the builder's breadth-first prefix is what wf_trace caches");
 static_assert(bfd::CTR_GUARD + 2 == bfd::CTR_COUNT && bfd::CTR_SURV_GUARD + 1 == bfd::CTR_COUNT,
               "the two sticky guard words are the last counters: renders clear the ones before them");
@@ -952,7 +668,7 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     sc->adc_t = flat.window_t ? flat.window_t : flat.sensor.t_bins;
     sc->adc_f = flat.window_f ? flat.window_f : flat.sensor.f_bins;
     sc->film_h = desc->sensor.film_height;
-    sc->origin_scale_built = origin_scale;
+    sc->mesh.origin_scale_built = origin_scale;
     // what a vertex update needs of the description later (bf_scene_update_vertices): every mesh's sizes, first primitive and indices
     sc->geom->topo.resize(desc->n_shapes);
     for (uint32_t i = 0; i < desc->n_shapes; ++i) {
@@ -983,7 +699,7 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     // takes them: the builder's padded scene box would overstate the bound by its own padding)
     for (const bf::BuildTri &t : btris)
         for (int k = 0; k < 3; ++k)
-            sc->origin_scale_built = std::max({sc->origin_scale_built, std::fabs(t.p0[k]), std::fabs(t.p1[k]), std::fabs(t.p2[k])});
+            sc->mesh.origin_scale_built = std::max({sc->mesh.origin_scale_built, std::fabs(t.p0[k]), std::fabs(t.p1[k]), std::fabs(t.p2[k])});
     // (+ kTriPad rows of padding behind the last triangle)
     std::vector<float4> tri_data(bfd::kTriStride * btris.size() + (btris.empty() ? 0 : kTriPad), make_float4(0, 0, 0, 0)), nrm_data;
     if (any_normals) nrm_data.resize(3 * btris.size());
@@ -1163,10 +879,10 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
         if (f.shapes[i].rect < 0 && (f.shapes[i].material != scene->shapes_host[i].material || f.shapes[i].emitter != scene->shapes_host[i].emitter))
             return fail(BF_ERR_UNSUPPORTED, "bf_scene_update_endpoints: mesh shape %zu changed its material / emitter index (the "
                                             "triangle records carry them); create a new scene", i);
-    if (scene->d.n_tris && f.origin_scale > scene->origin_scale_built)
+    if (scene->d.n_tris && f.origin_scale > scene->mesh.origin_scale_built)
         return fail(BF_ERR_UNSUPPORTED, "bf_scene_update_endpoints: an endpoint moved to |coordinate| %g, outside the bound %g the "
                                         "BVH boxes were padded for; create a new scene", (double) f.origin_scale,
-                    (double) scene->origin_scale_built);
+                    (double) scene->mesh.origin_scale_built);
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
     // The paths of an open rolling sequence belong to the endpoints as they are.  Round 3 finished them first (a flush: one
@@ -1273,734 +989,6 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
     return mark_last(scene, stream);
 }
 
-// The geometry a handle moves (bf_scene_translate_meshes, bf_scene_transform_meshes): make d.tris / d.nodes / d.wnodes / d.qnodes
-// writable by this handle and keep the pristine rows in tris0 / nodes0 / wnodes0, which every later call starts from (both
-// calls are absolute).
-static bf_status own_geometry(bf_scene *scene, hipStream_t stream, const char *who) {
-    const size_t tri_bytes = ((size_t) scene->d.n_tris * bfd::kTriStride + kTriPad) * sizeof(float4), node_bytes = (size_t) scene->d.n_nodes * 8 * sizeof(float4);
-    const size_t wnode_bytes = scene->d.wnodes ? (size_t) scene->d.n_wnodes * 32 * sizeof(float4) : 0;
-    const bool shared = scene->geom_token.use_count() > 1 && !scene->geom_private;
-    // all-or-nothing allocation: the handle's pointers change only once every copy exists (a failed hipMalloc half way
-    // must not leave tris0 set and nodes0 null for the next call to trip over)
-    struct Copies {
-        float4 *p[4] = {nullptr, nullptr, nullptr, nullptr};
-    } cp;
-    auto alloc_all = [&](const size_t (&bytes)[4]) -> bf_status {
-        for (int k = 0; k < 4; ++k) {
-            if (!bytes[k]) continue;
-            void *q = nullptr;
-            hipError_t he = hipMalloc(&q, bytes[k]);
-            if (he != hipSuccess) {
-                for (int j = 0; j < k; ++j)
-                    if (cp.p[j]) (void) hipFree(cp.p[j]);
-                return fail(BF_ERR_NOMEM, "%s: hipMalloc(%zu bytes): %s", who, bytes[k], hipGetErrorString(he));
-            }
-            cp.p[k] = (float4 *) q;
-        }
-        for (int k = 0; k < 4; ++k)
-            if (cp.p[k]) scene->owned.push_back(cp.p[k]);
-        return BF_OK;
-    };
-    if (shared) {
-        // copy on write: the arrays are shared with clones (bf_scene_clone) — this handle gets its own moved
-        // copies; the source of the motion is the geometry as created if this handle has it (it translated in
-        // place before it was cloned), else the shared arrays themselves
-        const size_t bytes[4] = {tri_bytes, node_bytes, wnode_bytes, scene->d.qnodes ? node_bytes / 2 : 0};
-        bf_status cst = alloc_all(bytes);
-        if (cst != BF_OK) return cst;
-        if (!scene->tris0) {
-            scene->tris0 = const_cast<float4 *>(scene->d.tris);
-            scene->nodes0 = const_cast<float4 *>(scene->d.nodes);
-            scene->wnodes0 = const_cast<float4 *>(scene->d.wnodes);
-            scene->base_private = false;
-        }
-        scene->d.tris = cp.p[0];
-        scene->d.nodes = cp.p[1];
-        scene->d.wnodes = cp.p[2];
-        if (scene->d.qnodes) scene->d.qnodes = cp.p[3];       // re-quantised from the moved fp32 nodes by the caller's kernels
-        scene->geom_private = true;       // (the token stays shared: tris0 / nodes0 may still READ the shared arrays)
-    } else if (!scene->tris0) {
-        // first use: keep the geometry as created, so that every later offset is applied to it (no drift)
-        const size_t bytes[4] = {tri_bytes, node_bytes, wnode_bytes, 0};
-        bf_status cst = alloc_all(bytes);
-        if (cst != BF_OK) return cst;
-        HIP_TRY(hipMemcpyAsync(cp.p[0], scene->d.tris, tri_bytes, hipMemcpyDeviceToDevice, stream));
-        if (node_bytes) HIP_TRY(hipMemcpyAsync(cp.p[1], scene->d.nodes, node_bytes, hipMemcpyDeviceToDevice, stream));
-        if (wnode_bytes) HIP_TRY(hipMemcpyAsync(cp.p[2], scene->d.wnodes, wnode_bytes, hipMemcpyDeviceToDevice, stream));
-        scene->tris0 = cp.p[0];
-        scene->nodes0 = cp.p[1];
-        scene->wnodes0 = cp.p[2];
-        scene->base_private = true;
-    }
-    return BF_OK;
-}
-
-bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void *stream_) {
-    if (!scene || !offset) return fail(BF_ERR_INVALID, "null argument");
-    if (!(std::isfinite(offset[0]) && std::isfinite(offset[1]) && std::isfinite(offset[2])))
-        return fail(BF_ERR_INVALID, "bf_scene_translate_meshes: non-finite offset");
-    if (scene->d.n_tris == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
-    if (scene->deformed && !scene->refit.ready) {
-        bf_status rst = refit_prepare(scene, stream);
-        if (rst != BF_OK) return rst;
-    }
-    bf_status gst = own_geometry(scene, stream, __func__);
-    if (gst != BF_OK) return gst;
-    // the pose a later vertex update runs on top of its new base rows: [I | offset] for every shape
-    scene->pose_kind = 1;
-    scene->pose_xf.assign((size_t) scene->info.n_shapes * 16, 0.f);
-    for (uint32_t k = 0; k < scene->info.n_shapes; ++k) {
-        float *m = &scene->pose_xf[16 * (size_t) k];
-        m[0] = m[5] = m[10] = m[12] = 1.f;
-        m[3] = offset[0], m[7] = offset[1], m[11] = offset[2];
-    }
-    if (scene->deformed) {
-        // the boxes of nodes0 / wnodes0 are those of the geometry as created, not of the updated base: the same vertices
-        // (fl(v + offset) either way) under re-fitted boxes
-        bf_status pst = apply_pose(scene, stream);
-        return pst != BF_OK ? pst : mark_last(scene, stream);
-    }
-    if (scene->normals_moved) {
-        // a rigid transform moved the vertex normals: a translation applies to the geometry as created
-        HIP_TRY(hipMemcpyAsync(const_cast<float4 *>(scene->d.normals), scene->normals0, (size_t) scene->d.n_tris * 3 * sizeof(float4),
-                               hipMemcpyDeviceToDevice, stream));
-        scene->normals_moved = false;
-    }
-    const size_t wnode_bytes = scene->d.wnodes ? (size_t) scene->d.n_wnodes * 32 * sizeof(float4) : 0;
-    HIP_TRY(bfk_launch_translate(scene->tris0, const_cast<float4 *>(scene->d.tris), scene->d.n_tris * bfd::kTriStride, scene->nodes0,
-                                 const_cast<float4 *>(scene->d.nodes), const_cast<float4 *>(scene->d.qnodes), scene->d.n_nodes, scene->wnodes0,
-                                 const_cast<float4 *>(scene->d.wnodes), wnode_bytes ? scene->d.n_wnodes * 16u : 0u, offset, stream));
-    return mark_last(scene, stream);
-}
-
-// First transform of a handle: the level lists of both trees (from the child references of the pristine nodes, read back once),
-// the unpadded-bound scratch, the device transform table and every mesh's pristine box (read back once).  Runs before
-// own_geometry, so that a failure here leaves the handle's arrays as they were.
-static bf_status refit_prepare(bf_scene *scene, hipStream_t stream) {
-    bf_scene::Refit &rf = scene->refit;
-    HIP_TRY(hipStreamSynchronize(stream));      // the rows may still be written by work enqueued on `stream`
-    // the pristine rows: the handle's own copies once it has moved, else the arrays it renders
-    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
-    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
-    // levels by breadth-first order from the root: children reference deeper nodes only
-    auto levels = [](const std::vector<int32_t> &refs, uint32_t width, int32_t root, std::vector<uint32_t> &off, std::vector<uint32_t> &flat) {
-        off.assign(1, 0u);
-        flat.clear();
-        if (root < 0) return;
-        flat.push_back((uint32_t) root);
-        for (size_t begin = 0; begin < flat.size();) {
-            const size_t end = flat.size();
-            off.push_back((uint32_t) end);
-            for (size_t i = begin; i < end; ++i)
-                for (uint32_t k = 0; k < width; ++k) {
-                    const int32_t r = refs[(size_t) flat[i] * width + k];
-                    if (r >= 0) flat.push_back((uint32_t) r);
-                }
-            begin = end;
-        }
-    };
-    auto upload_u32 = [&](const std::vector<uint32_t> &v, uint32_t **out) -> bf_status {
-        *out = nullptr;
-        if (v.empty()) return BF_OK;
-        HIP_TRY(hipMalloc((void **) out, v.size() * sizeof(uint32_t)));
-        scene->owned.push_back(*out);
-        HIP_TRY(hipMemcpy(*out, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        return BF_OK;
-    };
-    auto alloc = [&](size_t bytes, void **out) -> bf_status {
-        *out = nullptr;
-        if (!bytes) return BF_OK;
-        HIP_TRY(hipMalloc(out, bytes));
-        scene->owned.push_back(*out);
-        return BF_OK;
-    };
-    bf_status st;
-    std::vector<uint32_t> flat;
-    if (scene->d.n_nodes) {
-        std::vector<int32_t> refs((size_t) scene->d.n_nodes * 4);       // row 6 of every Node4
-        HIP_TRY(hipMemcpy2D(refs.data(), 16, (const char *) nodes0 + 6 * sizeof(float4), 8 * sizeof(float4), 16, scene->d.n_nodes,
-                            hipMemcpyDeviceToHost));
-        levels(refs, 4, scene->d.root, rf.off4, flat);
-        if ((st = upload_u32(flat, &rf.lvl4)) != BF_OK) return st;
-        if ((st = alloc((size_t) scene->d.n_nodes * 8 * sizeof(float4), (void **) &rf.ubox4)) != BF_OK) return st;
-    } else {
-        rf.off4.assign(1, 0u);
-    }
-    if (scene->d.wnodes && scene->d.n_wnodes) {
-        std::vector<int32_t> refs((size_t) scene->d.n_wnodes * 16);     // word 6 of every Node16 child record
-        HIP_TRY(hipMemcpy2D(refs.data(), 4, (const char *) wnodes0 + 6 * sizeof(float), 8 * sizeof(float), 4, refs.size(),
-                            hipMemcpyDeviceToHost));
-        levels(refs, 16, scene->d.wroot, rf.off16, flat);
-        if ((st = upload_u32(flat, &rf.lvl16)) != BF_OK) return st;
-        if ((st = alloc((size_t) scene->d.n_wnodes * 32 * sizeof(float4), (void **) &rf.ubox16)) != BF_OK) return st;
-    } else {
-        rf.off16.assign(1, 0u);
-    }
-    if (rf.have_boxes) {
-        rf.ready = true;
-        return BF_OK;
-    }
-    if ((st = alloc((size_t) scene->info.n_shapes * 16 * sizeof(float), (void **) &rf.xf)) != BF_OK) return st;
-    std::vector<float4> tris((size_t) scene->d.n_tris * bfd::kTriStride);
-    HIP_TRY(hipMemcpy(tris.data(), tris0, tris.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    const float inf = std::numeric_limits<float>::infinity();
-    rf.mesh_box.assign((size_t) scene->info.n_shapes * 6, 0.f);
-    for (uint32_t k = 0; k < scene->info.n_shapes; ++k)
-        for (int a = 0; a < 3; ++a) rf.mesh_box[6 * k + a] = inf, rf.mesh_box[6 * k + 3 + a] = -inf;
-    for (size_t t = 0; t < scene->d.n_tris; ++t) {
-        const float4 *r = &tris[t * bfd::kTriStride];
-        uint32_t shape;
-        std::memcpy(&shape, &r[1].w, 4);
-        float *b = &rf.mesh_box[6 * (size_t) shape];
-        for (int j = 0; j < 3; ++j) {
-            const float p[3] = {r[j].x, r[j].y, r[j].z};
-            for (int a = 0; a < 3; ++a) b[a] = std::min(b[a], p[a]), b[3 + a] = std::max(b[3 + a], p[a]);
-        }
-    }
-    rf.have_boxes = true;
-    rf.ready = true;
-    return BF_OK;
-}
-
-// The checks of one transform table ([n_shapes][12], bf_scene_transform_meshes' rules): moves[k] = 1 if shape k's entry is not
-// exactly the identity.  `who` names the call (and the render, for a batch) in the error text, which also names the shape.
-static bf_status check_rigid_table(const bf_scene *scene, uint32_t n_shapes, const float *to_world, const char *who, uint8_t *moves) {
-    for (uint32_t k = 0; k < n_shapes; ++k) {
-        const float *m = to_world + 12 * (size_t) k;
-        moves[k] = 0;
-        for (int j = 0; j < 12; ++j)
-            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "%s shape %u: non-finite entry", who, k);
-        for (int j = 0; j < 12; ++j) moves[k] |= m[j] != ((j % 5 == 0) ? 1.f : 0.f);
-        if (!moves[k]) continue;
-        double e = 0.0;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                double d = a == b ? -1.0 : 0.0;
-                for (int r = 0; r < 3; ++r) d += (double) m[4 * r + a] * (double) m[4 * r + b];
-                e = std::max(e, std::fabs(d));
-            }
-        const double det = (double) m[0] * ((double) m[5] * m[10] - (double) m[6] * m[9]) - (double) m[1] * ((double) m[4] * m[10] - (double) m[6] * m[8]) +
-                           (double) m[2] * ((double) m[4] * m[9] - (double) m[5] * m[8]);
-        if (!(e <= 1e-5) || !(det > 0.0))
-            return fail(BF_ERR_INVALID, "%s shape %u: not a rigid motion (|R^T R - I| = %g, det R = %g)", who, k, e, det);
-        const bfd::DShape &sh = scene->shapes_host[k];
-        if (sh.type != BF_SHAPE_MESH)
-            return fail(BF_ERR_INVALID, "%s shape %u is not a mesh: its entry must be the identity", who, k);
-        if (sh.emitter >= 0)
-            return fail(BF_ERR_UNSUPPORTED, "%s mesh shape %u carries emitter %d (its sampling tables are built "
-                                            "from the triangles as created); create a new scene", who, k, sh.emitter);
-    }
-    return BF_OK;
-}
-
-// The bound on ray origins the boxes must be padded for once the meshes stand at to_world: `oscale` raised to cover every
-// moved mesh (its pristine box through |R| plus |t|, with a little margin)
-static float moved_origin_scale(const bf_scene *scene, uint32_t n_shapes, const float *to_world, const uint8_t *moves, float oscale) {
-    const bf_scene::Refit &rf = scene->refit;
-    for (uint32_t k = 0; k < n_shapes; ++k) {
-        const float *b = &rf.mesh_box[6 * (size_t) k];
-        if (!moves[k] || !(b[0] <= b[3])) continue;
-        const float *m = to_world + 12 * (size_t) k;
-        for (int r = 0; r < 3; ++r) {
-            double v = std::fabs((double) m[4 * r + 3]);
-            for (int c = 0; c < 3; ++c) v += std::fabs((double) m[4 * r + c]) * std::max(std::fabs((double) b[c]), std::fabs((double) b[3 + c]));
-            oscale = std::max(oscale, (float) (v * (1.0 + 1e-5)));
-        }
-    }
-    return oscale;
-}
-
-bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const float *to_world, void *stream_) {
-    if (!scene || !to_world) return fail(BF_ERR_INVALID, "null argument");
-    if (n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "bf_scene_transform_meshes: %u transforms for a scene of %u shapes", n_shapes, scene->info.n_shapes);
-    // everything is checked before anything changes: a failed call leaves the scene as it was
-    std::vector<uint8_t> moves(n_shapes, 0);
-    {
-        bf_status cst = check_rigid_table(scene, n_shapes, to_world, "bf_scene_transform_meshes:", moves.data());
-        if (cst != BF_OK) return cst;
-    }
-    if (scene->d.n_tris == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
-    bf_status st = BF_OK;
-    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
-    if ((st = own_geometry(scene, stream, __func__)) != BF_OK) return st;
-    if (scene->d.normals && !scene->normals_private) {
-        // the vertex normals move too: into an array of the handle's own; the rows it rendered so far (shared with clones, or a
-        // clone's snapshot) stay untouched as the pristine normals0
-        const size_t bytes = (size_t) scene->d.n_tris * 3 * sizeof(float4);
-        void *q = nullptr;
-        hipError_t he = hipMalloc(&q, bytes);
-        if (he != hipSuccess) return fail(BF_ERR_NOMEM, "bf_scene_transform_meshes: hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(he));
-        scene->owned.push_back(q);
-        if (!scene->normals0) scene->normals0 = const_cast<float4 *>(scene->d.normals);
-        scene->d.normals = (const float4 *) q;
-        scene->normals_private = true;
-    }
-    bf_scene::Refit &rf = scene->refit;
-    // ray origins now lie on the moved meshes: raise the bound the boxes are padded for (bf_bvh.h) to cover them — never lowered
-    const float oscale = moved_origin_scale(scene, n_shapes, to_world, moves.data(), scene->origin_scale_built);
-    scene->origin_scale_built = oscale;
-    {
-        const size_t bytes = (size_t) n_shapes * 16 * sizeof(float);
-        bf_scene::Stage *stg = nullptr;
-        if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
-        float *h = (float *) stg->host;
-        for (uint32_t k = 0; k < n_shapes; ++k) {
-            std::memcpy(h + 16 * (size_t) k, to_world + 12 * (size_t) k, 12 * sizeof(float));
-            h[16 * k + 12] = moves[k] ? 1.f : 0.f;
-            h[16 * k + 13] = h[16 * k + 14] = h[16 * k + 15] = 0.f;
-        }
-        HIP_TRY(hipMemcpyAsync(rf.xf, h, bytes, hipMemcpyHostToDevice, stream));
-        scene->pose_kind = 2;       // (what a later vertex update runs on top of its new base rows)
-        scene->pose_xf.assign(h, h + (size_t) n_shapes * 16);
-        if ((st = stage_release_after(stg, stream)) != BF_OK) return st;
-    }
-    HIP_TRY(bfk_launch_rigid(scene->tris0, const_cast<float4 *>(scene->d.tris), scene->normals0, const_cast<float4 *>(scene->d.normals),
-                             scene->d.n_tris, rf.xf, scene->nodes0, const_cast<float4 *>(scene->d.nodes), const_cast<float4 *>(scene->d.qnodes),
-                             scene->d.n_nodes, rf.lvl4, rf.off4.data(), (uint32_t) rf.off4.size() - 1u, rf.ubox4, scene->wnodes0,
-                             const_cast<float4 *>(scene->d.wnodes), rf.lvl16, rf.off16.data(), (uint32_t) rf.off16.size() - 1u, rf.ubox16,
-                             2e-7f * oscale, 1u, 0u, 0u, stream));
-    scene->normals_moved = scene->d.normals != nullptr;
-    return mark_last(scene, stream);
-}
-
-// ---- vertex updates -------------------------------------------------------------------------------------------
-// The handle's latest pose (pose_kind / pose_xf) over its base rows, by the kernels of bf_scene_transform_meshes.  A translation
-// leaves the vertex normals as the base has them (bf_scene_translate_meshes does).
-static bf_status apply_pose(bf_scene *scene, hipStream_t stream) {
-    bf_scene::Refit &rf = scene->refit;
-    const uint32_t n_shapes = scene->info.n_shapes;
-    if (scene->pose_xf.size() != (size_t) n_shapes * 16) {
-        scene->pose_xf.assign((size_t) n_shapes * 16, 0.f);
-        for (uint32_t k = 0; k < n_shapes; ++k) scene->pose_xf[16 * (size_t) k] = scene->pose_xf[16 * (size_t) k + 5] = scene->pose_xf[16 * (size_t) k + 10] = 1.f;
-    }
-    // ray origins lie on the posed meshes: raise (never lower) the bound the boxes are padded for
-    float oscale = scene->origin_scale_built;
-    for (uint32_t k = 0; k < n_shapes; ++k) {
-        const float *b = &rf.mesh_box[6 * (size_t) k], *m = &scene->pose_xf[16 * (size_t) k];
-        if (!(b[0] <= b[3])) continue;
-        for (int r = 0; r < 3; ++r) {
-            double v = std::fabs((double) m[4 * r + 3]);
-            for (int c = 0; c < 3; ++c) v += std::fabs((double) m[4 * r + c]) * std::max(std::fabs((double) b[c]), std::fabs((double) b[3 + c]));
-            oscale = std::max(oscale, (float) (v * (1.0 + 1e-5)));
-        }
-    }
-    scene->origin_scale_built = oscale;
-    const size_t bytes = (size_t) n_shapes * 16 * sizeof(float);
-    bf_scene::Stage *stg = nullptr;
-    bf_status st = stage_acquire(scene, bytes, &stg);
-    if (st != BF_OK) return st;
-    std::memcpy(stg->host, scene->pose_xf.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(rf.xf, stg->host, bytes, hipMemcpyHostToDevice, stream));
-    if ((st = stage_release_after(stg, stream)) != BF_OK) return st;
-    const bool turn_normals = scene->pose_kind != 1 && scene->normals0 != nullptr;
-    if (!turn_normals && scene->normals0)
-        HIP_TRY(hipMemcpyAsync(const_cast<float4 *>(scene->d.normals), scene->normals0, (size_t) scene->d.n_tris * 3 * sizeof(float4),
-                               hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(bfk_launch_rigid(scene->tris0, const_cast<float4 *>(scene->d.tris), turn_normals ? scene->normals0 : nullptr,
-                             turn_normals ? const_cast<float4 *>(scene->d.normals) : nullptr, scene->d.n_tris, rf.xf, scene->nodes0,
-                             const_cast<float4 *>(scene->d.nodes), const_cast<float4 *>(scene->d.qnodes), scene->d.n_nodes, rf.lvl4, rf.off4.data(),
-                             (uint32_t) rf.off4.size() - 1u, rf.ubox4, scene->wnodes0, const_cast<float4 *>(scene->d.wnodes), rf.lvl16,
-                             rf.off16.data(), (uint32_t) rf.off16.size() - 1u, rf.ubox16, 2e-7f * oscale, 1u, 0u, 0u, stream));
-    scene->normals_moved = scene->pose_kind == 2 && scene->d.normals != nullptr;
-    return BF_OK;
-}
-
-// The corner table (shared with clones, built once from the indices the scene was created with and the prim / shape words of
-// the triangle rows) and this handle's violation counter.
-static bf_status deform_prepare(bf_scene *scene, hipStream_t stream) {
-    bf_geometry &g = *scene->geom;
-    if (!g.corners) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        const float4 *rows = scene->tris0 ? scene->tris0 : scene->d.tris;
-        std::vector<uint32_t> w((size_t) scene->d.n_tris * bfd::kTriStride);       // the .w words: prim, shape, tag per slot
-        HIP_TRY(hipMemcpy2D(w.data(), 4, (const char *) rows + 12, sizeof(float4), 4, w.size(), hipMemcpyDeviceToHost));
-        std::vector<uint4> corners(scene->d.n_tris);
-        for (size_t t = 0; t < corners.size(); ++t) {
-            const uint32_t prim = w[3 * t], shape = w[3 * t + 1];
-            if (shape >= g.topo.size() || prim < g.topo[shape].prim0 || prim - g.topo[shape].prim0 >= g.topo[shape].n_faces)
-                return fail(BF_ERR_DEVICE, "bf_scene_update_vertices: triangle slot %zu names primitive %u of shape %u, which the scene "
-                                           "description does not have", t, prim, shape);
-            const uint32_t *ix = &g.topo[shape].indices[3 * (size_t) (prim - g.topo[shape].prim0)];
-            corners[t] = make_uint4(ix[0], ix[1], ix[2], shape);
-        }
-        void *q = nullptr;
-        HIP_TRY(hipMalloc(&q, corners.size() * sizeof(uint4)));
-        g.owned.push_back(q);
-        HIP_TRY(hipMemcpy(q, corners.data(), corners.size() * sizeof(uint4), hipMemcpyHostToDevice));
-        g.corners = (uint4 *) q;
-        for (bf_geometry::MeshTopo &tp : g.topo) std::vector<uint32_t>().swap(tp.indices);      // the table holds them now
-    }
-    if (!scene->deform_bad) {
-        HIP_TRY(hipMalloc((void **) &scene->deform_bad, 2 * sizeof(uint32_t)));
-        HIP_TRY(hipMemset(scene->deform_bad, 0, 2 * sizeof(uint32_t)));
-        HIP_TRY(hipHostMalloc((void **) &scene->deform_bad_host, 2 * sizeof(uint32_t)));
-        scene->deform_bad_host[0] = scene->deform_bad_host[1] = 0u;
-        HIP_TRY(hipEventCreateWithFlags(&scene->deform_ev, hipEventDisableTiming));
-    }
-    return BF_OK;
-}
-
-// Behind every gather of a device form: the counter on its way to the host.  deform_report() turns a non-zero count into
-// BF_ERR_DEVICE once (bf_scene_sync and renders with stats wait for the copy; a plain render looks only if it has landed).
-static bf_status deform_watch(bf_scene *scene, hipStream_t stream) {
-    HIP_TRY(hipMemcpyAsync(scene->deform_bad_host, scene->deform_bad, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(scene->deform_ev, stream));
-    scene->deform_pending = true;
-    return BF_OK;
-}
-static bf_status deform_report(const bf_scene *scene, bool wait) {
-    if (!scene->deform_pending) return BF_OK;
-    if (wait) {
-        HIP_TRY(hipEventSynchronize(scene->deform_ev));
-    } else if (hipEventQuery(scene->deform_ev) != hipSuccess) {
-        (void) hipGetLastError();
-        return BF_OK;
-    }
-    scene->deform_pending = false;
-    // the device counter only ever grows (nothing clears it under a gather in flight): what is new since the last report
-    const uint32_t total = scene->deform_bad_host[0], shape1 = scene->deform_bad_host[1];
-    const uint32_t n = total - scene->deform_reported;
-    scene->deform_reported = total;
-    if (!n) return BF_OK;
-    return fail(BF_ERR_DEVICE, "a device-form vertex update of this scene gave %u triangles (of shape %u, if not of others too) a corner "
-                               "that is not finite or lies beyond the declared bound: those triangles kept their previous vertices, "
-                               "and every render issued since that update is invalid", n, shape1 ? shape1 - 1u : 0u);
-}
-
-// the checks of one shape of a vertex update; *topo_out = its topology
-static bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who,
-                                    const bf_geometry::MeshTopo **topo_out) {
-    if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", who, shape, scene->info.n_shapes);
-    const bfd::DShape &sh = scene->shapes_host[shape];
-    if (sh.type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", who, shape);
-    if (sh.emitter >= 0)
-        return fail(BF_ERR_UNSUPPORTED, "%s mesh shape %u carries emitter %d (its sampling tables are built from the triangles as "
-                                        "created); create a new scene", who, shape, sh.emitter);
-    const bf_geometry::MeshTopo &tp = scene->geom->topo[shape];
-    if (with_normals && !tp.has_normals)
-        return fail(BF_ERR_INVALID, "%s shape %u was created without vertex normals: it cannot take any", who, shape);
-    *topo_out = &tp;
-    return BF_OK;
-}
-
-// one update with the arrays on the device already; box6: the new base box of the shape
-static bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geometry::MeshTopo &tp, const float *pos_dev,
-                                        const float *nrm_dev, float bound, const float *box6, bool watch, hipStream_t stream) {
-    bf_status st = BF_OK;
-    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
-    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
-    if ((st = own_geometry(scene, stream, "bf_scene_update_vertices")) != BF_OK) return st;
-    const size_t tri_bytes = ((size_t) scene->d.n_tris * bfd::kTriStride + kTriPad) * sizeof(float4), nrm_bytes = (size_t) scene->d.n_tris * 3 * sizeof(float4);
-    auto fresh = [&](size_t bytes, const void *from, float4 **out) -> bf_status {
-        void *q = nullptr;
-        hipError_t he = hipMalloc(&q, bytes);
-        if (he != hipSuccess) return fail(BF_ERR_NOMEM, "bf_scene_update_vertices: hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(he));
-        scene->owned.push_back(q);
-        if (from) HIP_TRY(hipMemcpyAsync(q, from, bytes, hipMemcpyDeviceToDevice, stream));
-        *out = (float4 *) q;
-        return BF_OK;
-    };
-    if (!scene->base_private) {
-        // the base rows are still the arrays shared with clones: this handle's own copy from now on
-        float4 *q = nullptr;
-        if ((st = fresh(tri_bytes, scene->tris0, &q)) != BF_OK) return st;
-        scene->tris0 = q;
-        scene->base_private = true;
-    }
-    if (scene->d.normals && !scene->normals_private) {
-        // as bf_scene_transform_meshes: the rendered normals in an array of the handle's own, the base ones kept beside them
-        float4 *q = nullptr;
-        if ((st = fresh(nrm_bytes, nullptr, &q)) != BF_OK) return st;
-        if (!scene->normals0) scene->normals0 = const_cast<float4 *>(scene->d.normals);
-        scene->d.normals = q;
-        scene->normals_private = true;
-    }
-    if (nrm_dev && !scene->normals0_private) {
-        float4 *q = nullptr;
-        if ((st = fresh(nrm_bytes, scene->normals0, &q)) != BF_OK) return st;
-        scene->normals0 = q;
-        scene->normals0_private = true;
-    }
-    // the per-shape source table: this shape alone deforms
-    const size_t bytes = (size_t) scene->info.n_shapes * sizeof(bfd::DDeformSrc);
-    bf_scene::Stage *stg = nullptr;
-    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
-    std::memset(stg->host, 0, bytes);
-    bfd::DDeformSrc &e = ((bfd::DDeformSrc *) stg->host)[shape];
-    e.pos = pos_dev;
-    e.nrm = nrm_dev;
-    e.nv = tp.n_vertices;
-    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
-    HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, scene->tris0, scene->tris0,
-                                   nrm_dev ? scene->normals0 : nullptr, nrm_dev ? scene->normals0 : nullptr, scene->d.n_tris, nullptr, 1u, 0u, 0u,
-                                   bound, scene->deform_bad, stream));
-    HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel, not only by the copy
-    if (watch && (st = deform_watch(scene, stream)) != BF_OK) return st;
-    std::memcpy(&scene->refit.mesh_box[6 * (size_t) shape], box6, 6 * sizeof(float));
-    scene->deformed = true;
-    return apply_pose(scene, stream);
-}
-
-static bf_status update_enter(bf_scene *scene, hipStream_t stream) {
-    bf_status ost = order_after_last(scene, stream);
-    if (ost == BF_OK) ost = close_sequence(scene, stream);
-    return ost;
-}
-
-bf_status bf_scene_update_vertices(bf_scene *scene, uint32_t shape, const float *positions, const float *normals, void *stream_) {
-    if (!scene || !positions) return fail(BF_ERR_INVALID, "bf_scene_update_vertices: null argument");
-    const bf_geometry::MeshTopo *tp = nullptr;
-    bf_status st = check_deform_shape(scene, shape, normals != nullptr, "bf_scene_update_vertices:", &tp);
-    if (st != BF_OK) return st;
-    const size_t n = 3 * (size_t) tp->n_vertices;
-    const float inf = std::numeric_limits<float>::infinity();
-    float box[6] = {inf, inf, inf, -inf, -inf, -inf};
-    for (size_t i = 0; i < n; ++i) {
-        if (!std::isfinite(positions[i]) || (normals && !std::isfinite(normals[i])))
-            return fail(BF_ERR_INVALID, "bf_scene_update_vertices: shape %u: non-finite value at vertex %zu", shape, i / 3);
-        box[i % 3] = std::min(box[i % 3], positions[i]);
-        box[3 + i % 3] = std::max(box[3 + i % 3], positions[i]);
-    }
-    if (scene->d.n_tris == 0 || n == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    if ((st = update_enter(scene, stream)) != BF_OK) return st;
-    // the caller's arrays through the handle's upload buffer (the staging ring is for small tables): free again on return
-    const size_t bytes = n * sizeof(float) * (normals ? 2 : 1);
-    if (scene->vtx_ev) HIP_TRY(hipEventSynchronize(scene->vtx_ev));      // the previous update's gather may still read it
-    if (scene->vtx_cap < bytes) {
-        if (scene->vtx_host) (void) hipHostFree(scene->vtx_host);
-        if (scene->vtx_dev) (void) hipFree(scene->vtx_dev);
-        scene->vtx_host = scene->vtx_dev = nullptr;
-        scene->vtx_cap = 0;
-        HIP_TRY(hipHostMalloc(&scene->vtx_host, bytes));
-        HIP_TRY(hipMalloc(&scene->vtx_dev, bytes));
-        scene->vtx_cap = bytes;
-    }
-    if (!scene->vtx_ev) HIP_TRY(hipEventCreateWithFlags(&scene->vtx_ev, hipEventDisableTiming));
-    std::memcpy(scene->vtx_host, positions, n * sizeof(float));
-    if (normals) std::memcpy((float *) scene->vtx_host + n, normals, n * sizeof(float));
-    HIP_TRY(hipMemcpyAsync(scene->vtx_dev, scene->vtx_host, bytes, hipMemcpyHostToDevice, stream));
-    st = update_vertices_locked(scene, shape, *tp, (const float *) scene->vtx_dev, normals ? (const float *) scene->vtx_dev + n : nullptr, inf,
-                                box, false, stream);
-    HIP_TRY(hipEventRecord(scene->vtx_ev, stream));
-    if (st != BF_OK) return st;
-    return mark_last(scene, stream);
-}
-
-bf_status bf_scene_update_vertices_device(bf_scene *scene, uint32_t shape, const float *positions_dev, const float *normals_dev, float bound,
-                                          void *stream_) {
-    if (!scene || !positions_dev) return fail(BF_ERR_INVALID, "bf_scene_update_vertices_device: null argument");
-    if (!(bound > 0.f) || !std::isfinite(bound)) return fail(BF_ERR_INVALID, "bf_scene_update_vertices_device: shape %u: bound must be positive and finite", shape);
-    const bf_geometry::MeshTopo *tp = nullptr;
-    bf_status st = check_deform_shape(scene, shape, normals_dev != nullptr, "bf_scene_update_vertices_device:", &tp);
-    if (st != BF_OK) return st;
-    if (scene->d.n_tris == 0 || tp->n_vertices == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    if ((st = update_enter(scene, stream)) != BF_OK) return st;
-    const float box[6] = {-bound, -bound, -bound, bound, bound, bound};
-    if ((st = update_vertices_locked(scene, shape, *tp, positions_dev, normals_dev, bound, box, true, stream)) != BF_OK) return st;
-    return mark_last(scene, stream);
-}
-
-// ---- rebuild of both trees on the device (bf_build.hip) ---------------------------------------------------------------
-static int g_rebuild_fail_alloc = 0;      // test hook: the n-th allocation of the swap phase fails
-/* test hook (not part of the ABI): nth > 0: the builder's nth device allocation fails; nth < 0: the |nth|-th allocation of the
-   rebuild's own arrays fails; 0: off */
-bf_status bfdbg_rebuild_fail_alloc(int nth) {
-    bfk_build_fail_alloc(nth > 0 ? nth : 0);
-    g_rebuild_fail_alloc = nth < 0 ? -nth : 0;
-    return BF_OK;
-}
-
-// one of the handle's own allocations, freed now (arrays the shared geometry owns are not in the list: they go with its last user)
-static void release_owned(bf_scene *scene, const void *p) {
-    if (!p) return;
-    for (size_t i = 0; i < scene->owned.size(); ++i)
-        if (scene->owned[i] == p) {
-            (void) hipFree(scene->owned[i]);
-            scene->owned.erase(scene->owned.begin() + (long) i);
-            return;
-        }
-}
-
-bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
-    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_rebuild_bvh: null scene");
-    if (scene->d.n_tris == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    const uint32_t n = scene->d.n_tris;
-    const bool want_wide = scene->d.wnodes != nullptr, want_quant = scene->d.qnodes != nullptr, posed = scene->tris0 != nullptr;
-    bfk_build_in bin = {scene->d.tris, n, scene->origin_scale_built, want_wide ? 1 : 0, stream};
-    bfk_build_out bo;
-    {
-        char text[384];
-        text[0] = 0;
-        const int bst = bfk_build_bvh(&bin, &bo, text, sizeof(text));
-        if (bst) return fail(bst == 1 ? BF_ERR_NOMEM : (bst == 3 ? BF_ERR_UNSUPPORTED : BF_ERR_DEVICE), "bf_scene_rebuild_bvh: %s", text);
-    }
-    // everything the new tree needs is allocated and filled before the handle changes: a failure frees it and leaves the scene as it was
-    std::vector<void *> fresh = {bo.nodes, bo.wnodes};
-    int n_alloc = 0;
-    auto drop = [&]() {
-        for (void *p : fresh)
-            if (p) (void) hipFree(p);
-        if (bo.order) (void) hipFree(bo.order);
-    };
-    auto take = [&](size_t bytes, float4 **out) -> bf_status {
-        void *q = nullptr;
-        const bool inject = g_rebuild_fail_alloc && ++n_alloc == g_rebuild_fail_alloc;
-        hipError_t he = inject ? hipErrorOutOfMemory : hipMalloc(&q, bytes);
-        if (he != hipSuccess) {
-            (void) hipGetLastError();
-            drop();
-            return fail(BF_ERR_NOMEM, "bf_scene_rebuild_bvh: hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(he));
-        }
-        fresh.push_back(q);
-        *out = (float4 *) q;
-        return BF_OK;
-    };
-    if (want_wide && 16u * std::max(1u, bo.depth16) > (uint32_t) bfd::kWideStack) {
-        drop();
-        return fail(BF_ERR_UNSUPPORTED, "bf_scene_rebuild_bvh: the rebuilt sixteen-wide tree is %u levels deep: its row stack (%u entries) "
-                                        "exceeds %d", bo.depth16, 16u * bo.depth16, bfd::kWideStack);
-    }
-    const size_t tri_rows = (size_t) n * bfd::kTriStride, tri_bytes = (tri_rows + kTriPad) * sizeof(float4), nrm_bytes = (size_t) n * 3 * sizeof(float4);
-    const size_t node_bytes = (size_t) bo.n_nodes * 8 * sizeof(float4), wnode_bytes = want_wide ? ((size_t) bo.n_wnodes + 1) * 32 * sizeof(float4) : 0;
-    const float4 *old_normals0 = scene->normals0 && scene->normals0 != scene->d.normals ? scene->normals0 : nullptr;
-    float4 *tris = nullptr, *tris0 = nullptr, *normals = nullptr, *normals0 = nullptr, *uvs = nullptr, *corners = nullptr, *qnodes = nullptr;
-    float4 *nodes0 = nullptr, *wnodes0 = nullptr, *spill = nullptr;
-    bf_status st = BF_OK;
-    if ((st = take(tri_bytes, &tris)) != BF_OK) return st;
-    if (posed && (st = take(tri_bytes, &tris0)) != BF_OK) return st;
-    if (scene->d.normals && (st = take(nrm_bytes, &normals)) != BF_OK) return st;
-    if (old_normals0 && (st = take(nrm_bytes, &normals0)) != BF_OK) return st;
-    if (scene->d.uvs && (st = take((size_t) n * sizeof(float4), &uvs)) != BF_OK) return st;
-    if (scene->geom->corners && (st = take((size_t) n * sizeof(uint4), &corners)) != BF_OK) return st;
-    if (want_quant && bo.n_nodes && (st = take(node_bytes / 2, &qnodes)) != BF_OK) return st;
-    if (posed && node_bytes && (st = take(node_bytes, &nodes0)) != BF_OK) return st;
-    if (posed && wnode_bytes && (st = take(wnode_bytes, &wnodes0)) != BF_OK) return st;
-    const uint32_t old_spill = scene->d.stack_need > 16 ? scene->d.stack_need - 16 : 1, new_spill = bo.stack4 > 16 ? bo.stack4 - 16 : 1;
-    if (new_spill > old_spill && (st = take((size_t) scene->d.spill_stride * new_spill * sizeof(int), &spill)) != BF_OK) return st;
-    auto enqueue = [&]() -> hipError_t {
-        hipError_t e = bfk_build_gather(bo.order, n, scene->d.tris, tris, bfd::kTriStride, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(tris + tri_rows, 0, kTriPad * sizeof(float4), stream);
-        if (e == hipSuccess && tris0) e = bfk_build_gather(bo.order, n, scene->tris0, tris0, bfd::kTriStride, stream);
-        if (e == hipSuccess && tris0) e = hipMemsetAsync(tris0 + tri_rows, 0, kTriPad * sizeof(float4), stream);
-        if (e == hipSuccess && normals) e = bfk_build_gather(bo.order, n, scene->d.normals, normals, 3, stream);
-        if (e == hipSuccess && normals0) e = bfk_build_gather(bo.order, n, old_normals0, normals0, 3, stream);
-        if (e == hipSuccess && uvs) e = bfk_build_gather(bo.order, n, scene->d.uvs, uvs, 1, stream);
-        if (e == hipSuccess && corners) e = bfk_build_gather(bo.order, n, (const float4 *) scene->geom->corners, corners, 1, stream);
-        // the quantised copies by the refit's own kernel (no levels to re-fit: the boxes are the builder's)
-        const uint32_t no_levels[1] = {0u};
-        if (e == hipSuccess && qnodes)
-            e = bfk_launch_refit(tris, bo.nodes, bo.nodes, qnodes, bo.n_nodes, nullptr, no_levels, 0u, nullptr, nullptr, nullptr, nullptr, no_levels, 0u,
-                                 nullptr, 0.f, 1u, 0u, stream);
-        if (e == hipSuccess && nodes0) e = hipMemcpyAsync(nodes0, bo.nodes, node_bytes, hipMemcpyDeviceToDevice, stream);
-        if (e == hipSuccess && wnodes0) e = hipMemcpyAsync(wnodes0, bo.wnodes, wnode_bytes, hipMemcpyDeviceToDevice, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        return e;
-    };
-    {
-        const hipError_t e = enqueue();
-        if (e != hipSuccess) {
-            drop();
-            return fail(BF_ERR_DEVICE, "bf_scene_rebuild_bvh: %s", hipGetErrorString(e));
-        }
-    }
-    (void) hipFree(bo.order);
-    bo.order = nullptr;
-
-    // the swap.  The new arrays belong to a geometry object of the handle's own (copy on write: clones keep the old one alive and
-    // unchanged; a clone taken from now on shares the new one as it would share a created scene's)
-    auto g2 = std::make_shared<bf_geometry>();
-    g2->topo = scene->geom->topo;
-    g2->corners = (uint4 *) corners;
-    for (void *p : fresh)
-        if (p && p != spill) g2->owned.push_back(p);
-    const void *gone[] = {scene->tris0, scene->nodes0, scene->wnodes0, scene->d.tris, scene->d.nodes, scene->d.wnodes, scene->d.qnodes, scene->d.normals,
-                          scene->normals0, scene->refit.lvl4, scene->refit.lvl16, scene->refit.ubox4, scene->refit.ubox16, spill ? scene->d.spill : nullptr};
-    for (const void *p : gone) release_owned(scene, p);
-    scene->geom = g2;
-    scene->geom_token = std::make_shared<char>(0);
-    bfd::DScene &d = scene->d;
-    d.tris = tris;
-    d.nodes = bo.nodes;
-    d.qnodes = qnodes;
-    d.wnodes = want_wide ? bo.wnodes : nullptr;
-    d.normals = normals;
-    d.uvs = uvs;
-    d.n_nodes = bo.n_nodes;
-    d.root = bo.root;
-    d.wroot = want_wide ? bo.wroot : bfd_no_node();
-    d.n_wnodes = want_wide ? bo.n_wnodes : 0u;
-    if (want_wide) {
-        uint32_t rlog = 2;
-        while (rlog > 0 && (16u << rlog) * std::max(1u, bo.depth16) > (uint32_t) bfd::kWideStack) --rlog;
-        if (scene->tun.wide_rows_log >= 0) rlog = std::min<uint32_t>(rlog, (uint32_t) scene->tun.wide_rows_log);
-        d.wrows_log = rlog;
-    }
-    d.stack_need = bo.stack4;
-    if (spill) {
-        d.spill = (int *) spill;
-        scene->owned.push_back(spill);
-    }
-    scene->tris0 = tris0;
-    scene->nodes0 = posed ? nodes0 : nullptr;
-    scene->wnodes0 = posed ? wnodes0 : nullptr;
-    scene->normals0 = normals0;
-    // the handle's own arrays throughout; the boxes kept beside a pose are the POSED geometry's (only their topology is read from now
-    // on, as after a vertex update), so the pose stays absolute from the permuted base rows
-    scene->geom_private = posed;
-    scene->base_private = posed;
-    scene->normals_private = normals0 != nullptr;
-    scene->normals0_private = normals0 != nullptr;
-    if (posed) scene->deformed = true;
-    // the level lists follow the topology: rebuilt at the next refit; the per-mesh boxes and the transform table do not depend on it
-    scene->refit.ready = false;
-    scene->batch_versions = 0;
-    scene->refit.lvl4 = scene->refit.lvl16 = nullptr;
-    scene->refit.ubox4 = scene->refit.ubox16 = nullptr;
-    scene->refit.off4.clear();
-    scene->refit.off16.clear();
-    float oscale = scene->origin_scale_built;
-    for (int k = 0; k < 3; ++k) oscale = std::max({oscale, std::fabs(bo.lo[k]), std::fabs(bo.hi[k])});
-    scene->origin_scale_built = oscale;      // (what the builder padded for: kept, never lowered)
-    bf_scene_info &inf = scene->info;
-    inf.n_bvh_nodes = bo.n_nodes;
-    inf.bvh_depth = bo.depth4;
-    inf.bvh_stack_need = bo.stack4;
-    {
-        float m = 0.f;
-        for (int k = 0; k < 3; ++k) m = std::max({m, bo.hi[k] - bo.lo[k], std::fabs(bo.lo[k]), std::fabs(bo.hi[k])});
-        const float e = 2e-6f * m + 2e-7f * oscale + 1e-30f;
-        for (int k = 0; k < 3; ++k) inf.bbox_min[k] = bo.lo[k] - e, inf.bbox_max[k] = bo.hi[k] + e;
-    }
-    return mark_last(scene, stream);
-}
-
 bf_status bf_scene_read_bvh(const bf_scene *scene, uint32_t width, void *nodes_out, uint64_t nodes_bytes, float *tri_rows_out, int32_t *root_child) {
     if (!scene) return fail(BF_ERR_INVALID, "bf_scene_read_bvh: null scene");
     if (width != 4u && width != 16u) return fail(BF_ERR_INVALID, "bf_scene_read_bvh: width %u (4 or 16)", width);
@@ -2058,7 +1046,6 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
     sc->adc_f = src->adc_f;
     sc->film_h = src->film_h;
     sc->shapes_host = src->shapes_host;
-    sc->origin_scale_built = src->origin_scale_built;
     bf_status st = BF_OK;
     auto fail_out = [&](bf_status s) {
         bf_scene_destroy(sc);
@@ -2075,22 +1062,7 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
         *to = p;
         return BF_OK;
     };
-    if (src->tris0 || src->geom_private) {
-        // `src` has been translated (in place, or into its own copies): the clone takes a snapshot of the geometry
-        // src renders now as ITS geometry "as created"; texture coordinates (and normals no transform moved) stay shared
-        const size_t tri_bytes = ((size_t) src->d.n_tris * bfd::kTriStride + kTriPad) * sizeof(float4), node_bytes = (size_t) src->d.n_nodes * 8 * sizeof(float4);
-        const size_t wnode_bytes = src->d.wnodes ? (size_t) src->d.n_wnodes * 32 * sizeof(float4) : 0;
-        if ((st = dup(src->d.tris, tri_bytes, (const void **) &sc->d.tris)) != BF_OK) return fail_out(st);
-        if ((st = dup(src->d.nodes, node_bytes, (const void **) &sc->d.nodes)) != BF_OK) return fail_out(st);
-        if ((st = dup(src->d.wnodes, wnode_bytes, (const void **) &sc->d.wnodes)) != BF_OK) return fail_out(st);
-        if (src->d.qnodes && (st = dup(src->d.qnodes, node_bytes / 2, (const void **) &sc->d.qnodes)) != BF_OK) return fail_out(st);
-        // normals a rigid transform moved are part of the snapshot (the clone's own copy is never written: its first transform
-        // moves them into another array, as for any handle)
-        if (src->normals_private && (st = dup(src->d.normals, (size_t) src->d.n_tris * 3 * sizeof(float4), (const void **) &sc->d.normals)) != BF_OK)
-            return fail_out(st);
-        sc->geom_private = true;
-        sc->geom_token = std::make_shared<char>(0);      // the snapshot is the clone's alone: `src` keeps translating in place
-    }
+    if ((st = mesh_clone_snapshot(src, sc)) != BF_OK) return fail_out(st);      // the padding bound; the geometry `src` renders now, if it has moved
     if ((st = dup(src->d.rects, sizeof(bfd::DRect) * src->d.n_rects, (const void **) &sc->d.rects)) != BF_OK) return fail_out(st);
     if ((st = dup(src->d.shapes, sizeof(bfd::DShape) * src->info.n_shapes, (const void **) &sc->d.shapes)) != BF_OK) return fail_out(st);
     if ((st = dup(src->d.materials, sizeof(bfd::DMaterial) * src->n_materials, (const void **) &sc->d.materials)) != BF_OK) return fail_out(st);
@@ -2600,7 +1572,7 @@ static bf_status wf_roll_render(const bf_scene *scene, const bf_launch *launch, 
                 r.dmax = std::max(r.dmax, std::fabs(q));
             }
         // bf_device_core.h: Shift — slack for the largest offset of the sequence so far (older paths just get wider boxes)
-        lp.box_slack = 1e-6f * (scene->origin_scale_built + 2.f * r.dmax);
+        lp.box_slack = 1e-6f * (scene->mesh.origin_scale_built + 2.f * r.dmax);
     }
     if ((st = wf_setup(scene, kernels_for(r.shape.flags), lp, (uint64_t) K * lp.batch_paths, nullptr, nullptr, stream, r.count_nodes, r.timed, c, true)) != BF_OK) return st;
     lp.roll = scene->roll_ring;           // wf_setup may have (re)allocated the pool and the ring with it
@@ -2822,11 +1794,11 @@ static void fill_stats(const bf_scene *scene, const unsigned long long *c, uint6
 
 // Stream order between the successive uses of a handle's pool: work enqueued on another stream than the previous
 // call's waits for it (an event wait on the device, never on the host).
-static bf_status order_after_last(const bf_scene *scene, hipStream_t stream) {
+bf_status order_after_last(const bf_scene *scene, hipStream_t stream) {
     if (scene->has_last && scene->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, scene->last_done, 0));
     return BF_OK;
 }
-static bf_status mark_last(const bf_scene *scene, hipStream_t stream) {
+bf_status mark_last(const bf_scene *scene, hipStream_t stream) {
     if (!scene->last_done) HIP_TRY(hipEventCreateWithFlags(&scene->last_done, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(scene->last_done, stream));
     scene->last_stream = stream;
@@ -2834,7 +1806,7 @@ static bf_status mark_last(const bf_scene *scene, hipStream_t stream) {
     return BF_OK;
 }
 // anything but another render of the open rolling sequence needs the pool (or the scene tables) to itself
-static bf_status close_sequence(const bf_scene *scene, hipStream_t stream) {
+bf_status close_sequence(const bf_scene *scene, hipStream_t stream) {
     if (!scene->roll.open) return BF_OK;
     bf_status st = wf_roll_flush(scene, stream, false);
     if (st != BF_OK) return st;
@@ -2860,9 +1832,9 @@ static bool lean_profile(const bf_scene *scene, const bf_launch *launch, bool re
 }
 
 // A render or batch on a handle its caller holds (BF_ENTER).  geom_stride != 0: the batch's renders read per-render geometry
-// versions, geom_stride float4 rows apart from the arrays scene->d points at (bf_render_motion_batch_device; kGeom kernels).
-static bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
-                               bf_path_record *records_dev, void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0) {
+// versions, geom_stride float4 rows apart from the arrays scene->d points at (bf_mesh.cpp: render_versions; kGeom kernels).
+bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
+                        bf_path_record *records_dev, void *stream_, bf_stats *stats_out, uint32_t geom_stride) {
     const uint32_t n_renders = batch ? batch->n_renders : 1u;
     {
         // a device-form vertex update whose gather refused triangles (bf_scene_update_vertices_device) is reported by the handle's
@@ -3028,7 +2000,7 @@ static bf_status render_locked(const bf_scene *scene, const bf_launch *launch, c
                     lp.batch_offsets = (const float4 *) ((char *) stg->dev + seed_bytes);
                     // bf_device_core.h: Shift — the roundings of o - d and p + d move a box plane by at most
                     // 1.8e-7 (S + 2 |d|), S = the bound the boxes were padded for
-                    lp.box_slack = 1e-6f * (scene->origin_scale_built + 2.f * dmax);
+                    lp.box_slack = 1e-6f * (scene->mesh.origin_scale_built + 2.f * dmax);
                 }
             }
             sst = stage_commit(stg, seed_bytes + off_bytes, stream);
@@ -3102,318 +2074,6 @@ static bf_status render_common(const bf_scene *scene, const bf_launch *launch, c
     return render_locked(scene, launch, batch, hist_dev, records_dev, stream_, stats_out);
 }
 
-// bf_render_motion_batch_device.  Render k reads geometry version k: the pristine rows moved by to_world[k] and
-// both trees re-fitted, by the kernels and the arithmetic of bf_scene_transform_meshes, for all renders of a chunk at once
-// (grid y = version).  Layout of one version, in float4 rows from its start: triangles (+ the kTriPad rows behind them),
-// vertex normals, four-wide nodes, sixteen-wide nodes, quantised nodes, then the refit's scratch (unpadded child bounds of
-// both trees).  The handle's own geometry, pose, padding bound and clones are not touched.
-namespace {
-struct MotionLayout {
-    size_t tris = 0, normals = 0, nodes = 0, wnodes = 0, qnodes = 0, ubox4 = 0, ubox16 = 0, rows = 0;
-};
-// while a chunk renders, the handle's kernel arguments point at version 0 of the arena; restored on every return path
-struct GeomSwap {
-    bf_scene *s;
-    bfd::DScene saved;
-    GeomSwap(bf_scene *sc, const bfd::DScene &view) : s(sc), saved(sc->d) { sc->d = view; }
-    ~GeomSwap() { s->d = saved; }
-};
-}  // namespace
-static MotionLayout motion_layout(const bf_scene *scene) {
-    const bfd::DScene &d = scene->d;
-    MotionLayout L;
-    size_t r = 0;
-    auto take = [&](size_t &at, size_t rows) {
-        at = r;
-        r += (rows + 7) & ~size_t(7);      // every array on a 128-byte line
-    };
-    take(L.tris, (size_t) d.n_tris * bfd::kTriStride + kTriPad);
-    take(L.normals, d.normals ? (size_t) d.n_tris * 3 : 0);
-    take(L.nodes, (size_t) d.n_nodes * 8);
-    take(L.wnodes, d.wnodes ? (size_t) d.n_wnodes * 32 : 0);
-    take(L.qnodes, d.qnodes ? (size_t) d.n_nodes * 4 : 0);
-    take(L.ubox4, (size_t) d.n_nodes * 8);
-    take(L.ubox16, d.wnodes ? (size_t) d.n_wnodes * 32 : 0);
-    L.rows = r;
-    return L;
-}
-
-// default arena budget of bf_render_motion_batch_device (BF_MOTION_BATCH_MB overrides it at call time)
-static constexpr size_t kMotionBatchMB = 2048;
-
-static void add_stats(bf_stats &a, const bf_stats &b) {
-    a.n_paths += b.n_paths;
-    a.n_rays_closest += b.n_rays_closest;
-    a.n_rays_shadow += b.n_rays_shadow;
-    a.n_nodes_visited += b.n_nodes_visited;
-    a.n_tris_tested += b.n_tris_tested;
-    a.n_invalid += b.n_invalid;
-    a.n_bounces += b.n_bounces;
-    a.kernel_ms += b.kernel_ms;
-    a.trace_ms += b.trace_ms;
-    a.shade_ms += b.shade_ms;
-    a.tail_ms += b.tail_ms;
-    a.n_launches_trace += b.n_launches_trace;
-    a.n_bounce_iters += b.n_bounce_iters;
-    a.n_rays_tail += b.n_rays_tail;
-    a.n_rays_traced += b.n_rays_traced;
-    a.n_nodes_lds += b.n_nodes_lds;
-    a.n_nodes_tail += b.n_nodes_tail;
-    a.n_wnodes_tail += b.n_wnodes_tail;
-    a.n_tris_tail += b.n_tris_tail;
-    a.n_bounces_tail += b.n_bounces_tail;
-    a.n_shade_loads += b.n_shade_loads;
-    a.n_shade_stores += b.n_shade_stores;
-    a.n_shade_shadow += b.n_shade_shadow;
-    a.n_shade_rays += b.n_shade_rays;
-    a.n_guard += b.n_guard;
-    a.kernel_variant |= b.kernel_variant;      // (the chunks of one batch run the same kernels)
-}
-
-// The part every batch of geometry versions shares (motion batches, deform batches): chunks of renders whose versions fit the arena
-// budget (BF_MOTION_BATCH_MB; at least one render per chunk), the arena grown on demand, and per chunk prepare(k0, kc, a, L) — which
-// enqueues the chunk's versions into the arena `a` — followed by the chunk's renders with the handle's kernel arguments pointing
-// at version 0.  `fn` names the caller in error text.
-extern "C++" template <class Prepare>
-static bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, float *hist_dev,
-                                 bf_path_record *records_dev, void *stream_, bf_stats *stats_out, const char *fn, Prepare &&prepare) {
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const uint64_t n_chan = bf_launch_channels(launch);
-    const MotionLayout L = motion_layout(scene);
-    if (L.rows > UINT32_MAX)
-        return fail(BF_ERR_UNSUPPORTED, "%s: one geometry version of this scene is %zu float4 rows (at most 2^32 - 1)", fn, L.rows);
-    size_t budget_mb = kMotionBatchMB;
-    if (const char *e = getenv("BF_MOTION_BATCH_MB")) {
-        char *end = nullptr;
-        const unsigned long long v = strtoull(e, &end, 10);
-        if (end != e && *end == '\0') budget_mb = (size_t) v;
-    }
-    const size_t version_bytes = L.rows * sizeof(float4);
-    const uint32_t per_chunk = (uint32_t) std::max<size_t>(1, std::min<size_t>({(size_t) n_renders, 65535, (budget_mb << 20) / version_bytes}));
-    const size_t need = (size_t) per_chunk * L.rows;
-    if (scene->motion_cap < need) {
-        // the old arena may still be read by the renders of an earlier call: wait for them before it goes
-        if (scene->motion_arena) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            HIP_TRY(hipFree(scene->motion_arena));
-            scene->motion_arena = nullptr;
-            scene->motion_cap = 0;
-        }
-        void *q = nullptr;
-        hipError_t he = hipMalloc(&q, need * sizeof(float4));
-        if (he != hipSuccess)
-            return fail(BF_ERR_NOMEM, "%s: hipMalloc(%zu bytes) for %u geometry versions: %s (BF_MOTION_BATCH_MB caps the arena)", fn,
-                        need * sizeof(float4), per_chunk, hipGetErrorString(he));
-        scene->motion_arena = (float4 *) q;
-        scene->motion_cap = need;
-    }
-    float4 *const a = scene->motion_arena;
-    bfd::DScene view = scene->d;
-    view.tris = a + L.tris;
-    view.normals = scene->d.normals ? a + L.normals : nullptr;
-    view.nodes = a + L.nodes;
-    view.wnodes = scene->d.wnodes ? a + L.wnodes : nullptr;
-    view.qnodes = scene->d.qnodes ? a + L.qnodes : nullptr;
-    if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-    scene->batch_versions = 0;
-    for (uint32_t k0 = 0; k0 < n_renders; k0 += per_chunk) {
-        const uint32_t kc = std::min(per_chunk, n_renders - k0);
-        bf_status st = prepare(k0, kc, a, L);
-        if (st != BF_OK) return st;
-        bf_batch b = {kc, seeds ? seeds + k0 : nullptr, nullptr};
-        bf_stats cs;
-        {
-            GeomSwap swap(scene, view);
-            st = render_locked(scene, launch, &b, hist_dev + (size_t) k0 * n_chan, records_dev ? records_dev + (size_t) k0 * launch->n_paths : nullptr,
-                               stream_, stats_out ? &cs : nullptr, (uint32_t) L.rows);
-        }
-        if (st != BF_OK) return st;
-        if (stats_out) add_stats(*stats_out, cs);
-    }
-    if (n_renders <= per_chunk) scene->batch_versions = n_renders, scene->batch_rows = L.rows;
-    return BF_OK;
-}
-
-bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_shapes,
-                                        const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
-    if (!scene || !launch || !to_world || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
-    if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: n_renders is 0");
-    if (n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: %u transforms per render for a scene of %u shapes", n_shapes, scene->info.n_shapes);
-    if (launch->flags & BF_FLAG_ROLLING)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: BF_FLAG_ROLLING: a motion batch is one launch sequence of its own");
-    if (launch->spp && launch->film_width && launch->film_height)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: multi-pixel films are rendered one launch at a time");
-    // every render's table is checked before anything is enqueued: a failed call leaves the scene as it was
-    std::vector<uint8_t> moves((size_t) n_renders * n_shapes, 0);
-    for (uint32_t k = 0; k < n_renders; ++k) {
-        char who[96];
-        std::snprintf(who, sizeof(who), "bf_render_motion_batch_device: render %u,", k);
-        bf_status cst = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves.data() + (size_t) n_shapes * k);
-        if (cst != BF_OK) return cst;
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    if (scene->d.n_tris == 0) {
-        // nothing to move: an ordinary batch
-        bf_batch b = {n_renders, seeds, nullptr};
-        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
-    }
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
-    bf_status st = BF_OK;
-    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
-    // the pristine rows: the handle's own copies once it has moved, else the arrays it renders (a clone's snapshot included)
-    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
-    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
-    const float4 *normals0 = scene->normals0 ? scene->normals0 : scene->d.normals;
-    // one padding bound for every version of the call: the handle's, raised to cover all moved meshes of all renders
-    float oscale = scene->origin_scale_built;
-    for (uint32_t k = 0; k < n_renders; ++k)
-        oscale = moved_origin_scale(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, moves.data() + (size_t) n_shapes * k, oscale);
-    const bf_scene::Refit &rf = scene->refit;
-    return render_versions(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, "bf_render_motion_batch_device",
-                           [&](uint32_t k0, uint32_t kc, float4 *a, const MotionLayout &L) -> bf_status {
-        // the chunk's transform tables (bfk_launch_rigid: 16 floats per shape, word 12 = the shape moves)
-        const size_t bytes = (size_t) kc * n_shapes * 16 * sizeof(float);
-        bf_scene::Stage *stg = nullptr;
-        bf_status pst = stage_acquire(scene, bytes, &stg);
-        if (pst != BF_OK) return pst;
-        float *h = (float *) stg->host;
-        for (uint32_t v = 0; v < kc; ++v)
-            for (uint32_t k = 0; k < n_shapes; ++k) {
-                const size_t r = (size_t) (k0 + v) * n_shapes + k;
-                float *o = h + 16 * ((size_t) v * n_shapes + k);
-                std::memcpy(o, to_world + 12 * r, 12 * sizeof(float));
-                o[12] = moves[r] ? 1.f : 0.f;
-                o[13] = o[14] = o[15] = 0.f;
-            }
-        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
-        HIP_TRY(bfk_launch_rigid(tris0, a + L.tris, normals0, scene->d.normals ? a + L.normals : nullptr, scene->d.n_tris, (const float *) stg->dev,
-                                 nodes0, a + L.nodes, scene->d.qnodes ? a + L.qnodes : nullptr, scene->d.n_nodes, rf.lvl4, rf.off4.data(),
-                                 (uint32_t) rf.off4.size() - 1u, a + L.ubox4, wnodes0, scene->d.wnodes ? a + L.wnodes : nullptr, rf.lvl16,
-                                 rf.off16.data(), (uint32_t) rf.off16.size() - 1u, a + L.ubox16, 2e-7f * oscale, kc, L.rows, n_shapes * 16u,
-                                 stream));
-        return BF_OK;
-    });
-}
-
-// bf_render_deform_batch_device: the motion batch with a vertex gather in front.  Version k = the deforming shapes
-// from slice k of their arrays, every other mesh from the handle's base rows, then to_world[k] (absolute; NULL: none), in ONE pass
-// over the rows (bf_deform_tris_kernel applies rigid_apply to what it gathered: the arithmetic of an update followed by a
-// transform call), then the level kernels with the version dimension.  Arena, chunking and rendering as the motion batch.
-bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_deform,
-                                        const uint32_t *shapes, const float *const *positions_dev, const float *const *normals_dev, float bound,
-                                        uint32_t n_shapes, const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_,
-                                        bf_stats *stats_out) {
-    const char *fn = "bf_render_deform_batch_device:";
-    if (!scene || !launch || !hist_dev || (n_deform && (!shapes || !positions_dev))) return fail(BF_ERR_INVALID, "%s null argument", fn);
-    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
-    if (to_world && n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
-    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a deform batch is one launch sequence of its own", fn);
-    if (launch->spp && launch->film_width && launch->film_height)
-        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
-    if (n_deform && (!(bound > 0.f) || !std::isfinite(bound))) return fail(BF_ERR_INVALID, "%s bound must be positive and finite", fn);
-    n_shapes = scene->info.n_shapes;
-    std::vector<bfd::DDeformSrc> src(n_shapes);
-    std::memset(src.data(), 0, src.size() * sizeof(bfd::DDeformSrc));
-    for (uint32_t j = 0; j < n_deform; ++j) {
-        const bf_geometry::MeshTopo *tp = nullptr;
-        const float *nj = normals_dev ? normals_dev[j] : nullptr;
-        bf_status cst = check_deform_shape(scene, shapes[j], nj != nullptr, fn, &tp);
-        if (cst != BF_OK) return cst;
-        if (!positions_dev[j]) return fail(BF_ERR_INVALID, "%s shape %u: null positions", fn, shapes[j]);
-        if (src[shapes[j]].pos) return fail(BF_ERR_INVALID, "%s shape %u is listed twice", fn, shapes[j]);
-        src[shapes[j]].pos = positions_dev[j];
-        src[shapes[j]].nrm = nj;
-        src[shapes[j]].nv = tp->n_vertices;
-    }
-    std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
-    for (uint32_t k = 0; to_world && k < n_renders; ++k) {
-        char who[96];
-        std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
-        bf_status cst = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves.data() + (size_t) n_shapes * k);
-        if (cst != BF_OK) return cst;
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    if (scene->d.n_tris == 0) {
-        bf_batch b = {n_renders, seeds, nullptr};
-        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
-    }
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
-    bf_status st = BF_OK;
-    if (!scene->refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
-    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
-    const float4 *tris0 = scene->tris0 ? scene->tris0 : scene->d.tris, *nodes0 = scene->tris0 ? scene->nodes0 : scene->d.nodes;
-    const float4 *wnodes0 = scene->tris0 ? scene->wnodes0 : scene->d.wnodes;
-    const float4 *normals0 = scene->normals0 ? scene->normals0 : scene->d.normals;
-    // one padding bound for every version: the handle's, raised to cover every mesh of every render where it stands then (a
-    // deforming shape's base box is [-bound, bound]^3 for the call)
-    bf_scene::Refit &rf = scene->refit;
-    float oscale = scene->origin_scale_built;
-    {
-        const std::vector<float> kept = rf.mesh_box;
-        std::vector<uint8_t> all(n_shapes, 1);
-        static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-        std::vector<float> id((size_t) 12 * n_shapes);
-        for (uint32_t k = 0; k < n_shapes; ++k) std::memcpy(&id[12 * (size_t) k], ident, sizeof(ident));
-        for (uint32_t k = 0; k < n_shapes; ++k)
-            if (src[k].pos)
-                for (int a = 0; a < 3; ++a) rf.mesh_box[6 * (size_t) k + a] = -bound, rf.mesh_box[6 * (size_t) k + 3 + a] = bound;
-        oscale = moved_origin_scale(scene, n_shapes, id.data(), all.data(), oscale);
-        for (uint32_t k = 0; to_world && k < n_renders; ++k)
-            oscale = moved_origin_scale(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, moves.data() + (size_t) n_shapes * k, oscale);
-        rf.mesh_box = kept;      // the handle's own base is not touched
-    }
-    st = render_versions(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, "bf_render_deform_batch_device",
-                         [&](uint32_t k0, uint32_t kc, float4 *a, const MotionLayout &L) -> bf_status {
-        // the chunk's tables: the sources advanced to slice k0, then (if any) the transforms as bfk_launch_rigid reads them
-        const size_t src_bytes = (src.size() * sizeof(bfd::DDeformSrc) + 15) & ~size_t(15);
-        const size_t bytes = src_bytes + (to_world ? (size_t) kc * n_shapes * 16 * sizeof(float) : 0);
-        bf_scene::Stage *stg = nullptr;
-        bf_status pst = stage_acquire(scene, bytes, &stg);
-        if (pst != BF_OK) return pst;
-        bfd::DDeformSrc *hs = (bfd::DDeformSrc *) stg->host;
-        for (uint32_t k = 0; k < n_shapes; ++k) {
-            hs[k] = src[k];
-            if (hs[k].pos) hs[k].pos += (size_t) k0 * 3 * hs[k].nv;
-            if (hs[k].nrm) hs[k].nrm += (size_t) k0 * 3 * hs[k].nv;
-        }
-        float *h = (float *) ((char *) stg->host + src_bytes);
-        for (uint32_t v = 0; to_world && v < kc; ++v)
-            for (uint32_t k = 0; k < n_shapes; ++k) {
-                const size_t r = (size_t) (k0 + v) * n_shapes + k;
-                float *o = h + 16 * ((size_t) v * n_shapes + k);
-                std::memcpy(o, to_world + 12 * r, 12 * sizeof(float));
-                o[12] = moves[r] ? 1.f : 0.f;
-                o[13] = o[14] = o[15] = 0.f;
-            }
-        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
-        HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, tris0, a + L.tris, normals0,
-                                       scene->d.normals ? a + L.normals : nullptr, scene->d.n_tris,
-                                       to_world ? (const float *) ((const char *) stg->dev + src_bytes) : nullptr, kc, L.rows, n_shapes * 16u,
-                                       bound, scene->deform_bad, stream));
-        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernel
-        HIP_TRY(bfk_launch_refit(a + L.tris, nodes0, a + L.nodes, scene->d.qnodes ? a + L.qnodes : nullptr, scene->d.n_nodes, rf.lvl4,
-                                 rf.off4.data(), (uint32_t) rf.off4.size() - 1u, a + L.ubox4, wnodes0, scene->d.wnodes ? a + L.wnodes : nullptr,
-                                 rf.lvl16, rf.off16.data(), (uint32_t) rf.off16.size() - 1u, a + L.ubox16, 2e-7f * oscale, kc, L.rows, stream));
-        return BF_OK;
-    });
-    if (st != BF_OK || !n_deform) return st;
-    // the violation count of all chunks travels to the host behind the last one; a batch with stats waits for it and reports itself
-    if ((st = deform_watch(scene, stream)) != BF_OK) return st;
-    return stats_out ? deform_report(scene, true) : BF_OK;
-}
-
 bf_status bf_render_device(const bf_scene *scene, const bf_launch *launch, float *hist_dev, bf_path_record *records_dev,
                            void *stream, bf_stats *stats_out) {
     return render_common(scene, launch, nullptr, hist_dev, records_dev, stream, stats_out);
@@ -3475,62 +2135,6 @@ bf_status bfdbg_preload_guard(bf_scene *scene, unsigned long long n) {
     if (!scene) return fail(BF_ERR_INVALID, "null argument");
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(scene->counters + bfd::CTR_GUARD, &n, sizeof(n), hipMemcpyHostToDevice));
-    return BF_OK;
-}
-
-/* test hook (not part of the ABI): the ray-origin bound the handle's boxes are padded for (bf_bvh.h) */
-bf_status bfdbg_scene_origin_scale(const bf_scene *scene, float *out) {
-    if (!scene || !out) return fail(BF_ERR_INVALID, "bfdbg_scene_origin_scale: null argument");
-    *out = scene->origin_scale_built;
-    return BF_OK;
-}
-
-/* test hook (not part of the ABI): what the device wrote, read back.  which = 4 / 16: the Node4 / Node16 array; 64: the Node4Q
-   array (BF_ERR_UNSUPPORTED unless the scene was created under BF_QUANT_BVH=1).  version = -1: the handle's own arrays; k >= 0:
-   geometry version k of the handle's last motion / deform batch, from the arena (BF_ERR_INVALID if that batch was chunked or k
-   is out of range).  nodes_out (`bytes` of it, at least the array's size; a call with too few fails with the text "needs <n>
-   bytes", as bf_scene_read_bvh), rows_out (float4[n_triangles][3]) and normals_out (float4[n_triangles][3], the posed vertex
-   normals; left alone if the scene has none) may each be NULL.  Finishes the open sequence and waits for the handle's last work. */
-bf_status bfdbg_scene_read_tree(const bf_scene *scene, uint32_t which, int32_t version, void *nodes_out, uint64_t bytes, float *rows_out,
-                                float *normals_out) {
-    if (!scene) return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: null scene");
-    if (which != 4u && which != 16u && which != 64u) return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: which = %u (4, 16 or 64)", which);
-    BF_ENTER(scene);
-    {
-        bf_status cst = close_sequence(scene, scene->roll.stream);
-        if (cst != BF_OK) return cst;
-    }
-    if (scene->has_last) HIP_TRY(hipEventSynchronize(scene->last_done));
-    const bfd::DScene &d = scene->d;
-    if (which == 16u && !d.wnodes) return fail(BF_ERR_UNSUPPORTED, "bfdbg_scene_read_tree: the scene has no sixteen-wide tree");
-    if (which == 64u && !d.qnodes) return fail(BF_ERR_UNSUPPORTED, "bfdbg_scene_read_tree: the scene has no quantised nodes (BF_QUANT_BVH=1)");
-    const float4 *tris = d.tris, *normals = d.normals, *nodes = d.nodes, *wnodes = d.wnodes, *qnodes = d.qnodes;
-    if (version >= 0) {
-        const MotionLayout L = motion_layout(scene);
-        if (!scene->motion_arena || (uint32_t) version >= scene->batch_versions || L.rows != scene->batch_rows)
-            return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: version %d: the handle's last batch left %u whole versions in its arena "
-                                        "(none if it was chunked)", version, scene->batch_versions);
-        const float4 *a = scene->motion_arena + (size_t) version * L.rows;
-        tris = a + L.tris;
-        normals = d.normals ? a + L.normals : nullptr;
-        nodes = a + L.nodes;
-        wnodes = d.wnodes ? a + L.wnodes : nullptr;
-        qnodes = d.qnodes ? a + L.qnodes : nullptr;
-    } else if (version != -1) {
-        return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: version %d", version);
-    }
-    const uint64_t need = which == 4u ? (uint64_t) d.n_nodes * sizeof(bf::Node4)
-                        : which == 16u ? (uint64_t) d.n_wnodes * sizeof(bf::Node16) : (uint64_t) d.n_nodes * sizeof(bf::Node4Q);
-    if (nodes_out || bytes) {
-        if (bytes < need || (need && !nodes_out))
-            return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: nodes_out needs %llu bytes (%llu given)", (unsigned long long) need,
-                        (unsigned long long) bytes);
-        if (need) HIP_TRY(hipMemcpy(nodes_out, which == 4u ? nodes : (which == 16u ? wnodes : qnodes), need, hipMemcpyDeviceToHost));
-    }
-    const size_t row_bytes = (size_t) d.n_tris * 3 * sizeof(float4);
-    static_assert(bfd::kTriStride == 3, "rows_out is float4[n_triangles][3]");
-    if (rows_out && d.n_tris) HIP_TRY(hipMemcpy(rows_out, tris, row_bytes, hipMemcpyDeviceToHost));
-    if (normals_out && normals && d.n_tris) HIP_TRY(hipMemcpy(normals_out, normals, row_bytes, hipMemcpyDeviceToHost));
     return BF_OK;
 }
 
@@ -3598,7 +2202,7 @@ void bf_shard_range(uint64_t n_paths, uint32_t shard, uint32_t n_shards, uint64_
     if (count) *count = hi - lo;
 }
 
-extern "C++" {
+}  // extern "C"
 namespace {
 struct Rccl {
     void *lib = nullptr;
@@ -3649,7 +2253,7 @@ Rccl &rccl() {
 std::mutex g_comm_mutex;
 std::map<std::vector<int>, std::vector<ncclComm_t>> g_comms;
 }  // namespace
-}  // extern "C++"
+extern "C" {
 
 bf_status bf_allreduce_device(const int *devices, uint32_t n_devices, float *const *bufs, uint64_t count, void *const *streams) {
     if (!devices || !bufs || n_devices == 0) return fail(BF_ERR_INVALID, "bf_allreduce_device: null argument");
@@ -3827,8 +2431,9 @@ bf_status bf_render_sharded(bf_scene *const *scenes, uint32_t n_devices, const b
     return st;
 }
 
+}  // extern "C"
 // host buffers around a device render: `run(d_hist, d_rec, stats)` renders n_renders renders of `launch` into them
-extern "C++" template <class Run>
+template <class Run>
 static bf_status render_host_with(const bf_scene *scene, const bf_launch *launch, uint64_t n_renders, float *hist_out,
                                   bf_path_record *records_out, bf_stats *stats_out, Run &&run) {
     if (!scene || !launch || !hist_out) return fail(BF_ERR_INVALID, "null argument");
@@ -3858,6 +2463,7 @@ static bf_status render_host_with(const bf_scene *scene, const bf_launch *launch
     if (d_rec) (void) hipFree(d_rec);
     return st;
 }
+extern "C" {
 
 static bf_status render_host(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_out,
                              bf_path_record *records_out, bf_stats *stats_out) {

@@ -1,0 +1,318 @@
+// What bf_api.cpp and bf_mesh.cpp share: the scene handle, its guards and the few functions of either file the other one calls.
+// Internal to libbeifong_hip.so: the functions and guards declared here have hidden visibility (the C ABI is include/beifong_hip.h alone).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <memory>
+#include <vector>
+
+#include "bf_build.h"
+#include "bf_bvh.h"
+#include "bf_device.h"
+#include "bf_wavefront.h"
+
+// the launchers of bf_kernels.hip that move geometry (bf_mesh.cpp)
+extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, uint32_t n_tri_rows, const float4 *nodes0,
+                                           float4 *nodes, float4 *qnodes, uint32_t n_nodes, const float4 *wnodes0, float4 *wnodes,
+                                           uint32_t n_wchildren, const float *d, hipStream_t stream);
+extern "C" hipError_t bfk_launch_deform_tris(const uint4 *corners, const bfd::DDeformSrc *src, const float4 *tris0, float4 *tris, const float4 *nrm0,
+                                             float4 *nrm, uint32_t n_tris, const float *xf, uint32_t n_versions, uint64_t vstride,
+                                             uint32_t xf_stride, float bound, uint32_t *bad, hipStream_t stream);
+extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
+                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes,
+                                       const uint32_t *lvl16, const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad,
+                                       uint32_t n_versions, uint64_t vstride, hipStream_t stream);
+extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
+                                       const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
+                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
+                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
+                                       uint64_t vstride, uint32_t xf_stride, hipStream_t stream);
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail(BF_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+inline int32_t bfd_no_node() { return INT32_MIN; }
+constexpr size_t kTriPad = 4;      // float4 rows of padding behind the triangle array (read by no kernel; part of the geometry layout)
+
+// The big read-only arrays of a scene (BVH nodes, triangles, normals, texture coordinates): shared by a scene and its
+// clones (bf_scene_clone), freed with the last of them.
+struct bf_geometry {
+    std::vector<void *> owned;
+    // vertex updates (bf_scene_update_vertices): what every mesh shape was created with, and the device corner
+    // table built from it at the first update of any handle that shares these arrays (one uint4 per triangle slot in leaf order:
+    // the slot's three vertex indices within its shape, then the shape)
+    struct MeshTopo {
+        uint32_t n_vertices = 0, n_faces = 0, prim0 = 0;
+        bool has_normals = false;
+        std::vector<uint32_t> indices;
+    };
+    std::vector<MeshTopo> topo;            // per shape (non-mesh shapes: empty)
+    uint4 *corners = nullptr;
+    ~bf_geometry() {
+        for (void *p : owned) (void) hipFree(p);
+    }
+};
+
+// Developer overrides, read from the environment ONCE, when a scene is created; clones inherit them.
+struct bf_tunables {
+    uint32_t pool = 1u << 24;                // BF_WF_POOL
+    int64_t tail = -1;                       // BF_WF_TAIL (-1: by pool size)
+    uint32_t trace_refill = bfd::kTraceRefill, trace_stragglers = bfd::kTraceStragglers;
+    uint32_t shade_chain = bfd::kShadeChain, row_jobs = bfd::kTailRowJobs;
+    int shade_waves = 3, trace_waves = 5, tail_waves = 3;
+    unsigned tail_spread = 1, tail_blocks = 0;
+    int tail_share = -1;                     // BF_TAIL_SHARE: waves per batch in a stand-alone render's tail (-1: by pool size)
+    bool allow_plan = true;                  // BF_WF_SYNC=1 turns launch plans off
+    uint32_t roll_iters = 0;                 // BF_ROLL_ITERS: bounce iterations per call of a rolling sequence (0: adaptive)
+    uint32_t roll_live = 0;                  // BF_ROLL_LIVE: a rolling call stops iterating once at most this many slots are alive (0: max(1.5 x 2^20, main slots / 4))
+    bool no_wide = false, quant = false;
+    int wide_rows_log = -1;
+    bool lean = true;                        // BF_LEAN=0: never use the kernels' lean variants (bf_device.h: kLean)
+    bool tab_cache = true;                   // BF_TAB_CACHE=0: materials / rectangles stay in device memory (no LDS copies)
+    bool shade_split = false;                // BF_SHADE_SPLIT=1: wf_shade walks the alive masks twice: slots without a real hit first, real hits second (measured: no net gain)
+    uint32_t chain_min = 16;                 // BF_CHAIN_MIN: resolved real hits chain only while at least this many lanes hold one (0: always)
+    uint32_t grid_share = 3;                 // BF_GRID_SHARE: small pools (< grid_small slots) of handles that roll side by side launch 1 / min(peers, this) of the persistent grids (0 / 1: off)
+    uint32_t grid_small = 1u << 22;          // BF_GRID_SMALL
+    bool roll_join = true;                   // BF_ROLL_JOIN=0: bf_scene_update_endpoints flushes an open rolling sequence (round 3's behaviour)
+    uint32_t debug_surv_batches = 0;         // BF_DEBUG_SURV_BATCHES (tests): size of the survivor area in batches, sizing rule off
+};
+
+// "The meshes of this handle have moved" (DESIGN.md 6d): the state bf_mesh.cpp keeps per handle, each flag's meaning stated here alone.
+// Every moving call is ABSOLUTE: from the BASE rows (as created, until a vertex update rewrites them) to the rows bf_scene::d renders.
+struct __attribute__((visibility("hidden"))) MeshState {
+    // the base rows; all null until the handle's first move (own_geometry sets the three together), then never null again
+    float4 *tris0 = nullptr, *nodes0 = nullptr, *wnodes0 = nullptr;
+    float4 *normals0 = nullptr;          // the base vertex normals, once d.normals is the handle's own array (own_normals)
+    bool geom_private = false;           // d.tris / d.nodes / d.wnodes / d.qnodes are this handle's own moved copies, not the arrays shared with clones
+    bool base_private = false;           // tris0 is this handle's own allocation, so a vertex update may write it (false: it READS the shared rows)
+    bool normals_private = false;        // d.normals is this handle's own array (copy on write, as geom_private for the rest)
+    bool normals0_private = false;       // normals0 is this handle's own allocation, so a vertex update with normals may write it
+    bool normals_moved = false;          // d.normals holds normals a rigid table has turned: a translation restores normals0 first
+    bool deformed = false;               // nodes0 / wnodes0 no longer bound the base rows (vertex update, rebuild under a pose): only their topology is read, and translations refit too
+    int pose_kind = 0;                   // the latest pose, run again after a vertex update: 0 none, 1 a translation, 2 a rigid table
+    std::vector<float> pose_xf;          // that pose as bfk_launch_rigid reads it (16 floats per shape)
+    float origin_scale_built = 0.f;      // ray-origin bound the BVH boxes were padded for (bf_bvh.h): raised by moves, never lowered
+    // the refit's state, built on the handle's first transform (nothing of it costs bf_scene_create anything)
+    struct Refit {
+        bool ready = false;
+        bool have_boxes = false;                 // xf and mesh_box exist (they survive bf_scene_rebuild_bvh: neither depends on the slot order)
+        std::vector<uint32_t> off4, off16;       // level d of the four- / sixteen-wide tree: [off[d], off[d + 1]) of lvl4 / lvl16
+        uint32_t *lvl4 = nullptr, *lvl16 = nullptr;
+        float4 *ubox4 = nullptr, *ubox16 = nullptr;      // unpadded bounds of every child record (two float4 each)
+        float *xf = nullptr;                     // device: 16 floats per shape (bfk_launch_rigid)
+        std::vector<float> mesh_box;             // per shape: lo.xyz, hi.xyz of its base triangles (inverted: none)
+    } refit;
+    // motion / deform batches: the geometry versions of a batch's renders, MotionLayout::rows float4 rows each.  Never shared with
+    // clones, grown on demand; stream-ordered behind the previous call's renders like every write of the handle (order_after_last)
+    float4 *arena = nullptr;
+    size_t arena_cap = 0;                        // float4 rows allocated
+    // the versions the last batch left in the arena, for bfdbg_scene_read_tree: 0 if that batch was chunked (the arena then holds
+    // its last chunk only), failed, or a rebuild has changed the layout since
+    uint32_t batch_versions = 0;
+    size_t batch_rows = 0;                       // float4 rows per version of that batch
+    // the device forms' violation counter ([0] slots refused, [1] a refused shape + 1), its pinned mirror and the event behind the
+    // copy that follows every device-form gather
+    uint32_t *bad = nullptr, *bad_host = nullptr;
+    hipEvent_t bad_ev = nullptr;
+    mutable bool bad_pending = false;
+    mutable uint32_t bad_reported = 0;           // of the device count, how much has been reported already
+    // the host form's upload buffer (pinned + device mirror), grown on demand; vtx_ev: behind the gather that read it last
+    void *vtx_host = nullptr, *vtx_dev = nullptr;
+    size_t vtx_cap = 0;
+    hipEvent_t vtx_ev = nullptr;
+
+    // what to read as the base rows: the handle's own once it has moved, else the arrays it renders (a clone's snapshot included)
+    struct Base { const float4 *tris, *nodes, *wnodes, *normals; };
+    Base base(const bfd::DScene &d) const {
+        return {tris0 ? tris0 : d.tris, tris0 ? nodes0 : d.nodes, tris0 ? wnodes0 : d.wnodes, normals0 ? normals0 : d.normals};
+    }
+    // byte sizes of the arrays of n_tris triangles, n_nodes Node4 and wide_nodes Node16 (0: no such tree); quantised nodes: nodes / 2
+    struct Bytes { size_t tris, normals, nodes, wnodes; };
+    static Bytes bytes(uint32_t n_tris, uint32_t n_nodes, size_t wide_nodes) {
+        return {((size_t) n_tris * bfd::kTriStride + kTriPad) * sizeof(float4), (size_t) n_tris * 3 * sizeof(float4), (size_t) n_nodes * 8 * sizeof(float4),
+                wide_nodes * 32 * sizeof(float4)};
+    }
+    static Bytes bytes(const bfd::DScene &d) { return bytes(d.n_tris, d.n_nodes, d.wnodes ? d.n_wnodes : 0); }
+    // copy on write of the rendered normals: d.normals becomes the handle's own array (the caller fills it), the old one stays as normals0
+    bf_status own_normals(bfd::DScene &d, std::vector<void *> &owned, const char *who);
+    // after bf_scene_rebuild_bvh's swap: the permuted base arrays (all null unless the handle was posed) and what follows from them
+    void reset_after_rebuild(float4 *tris0_, float4 *nodes0_, float4 *wnodes0_, float4 *normals0_);
+    // arena, violation counter and upload buffer go with the handle (the base arrays and the refit's are on bf_scene::owned)
+    ~MeshState();
+};
+
+struct bf_scene {
+    bfd::DScene d;
+    bf_tunables tun;
+    std::shared_ptr<bf_geometry> geom;     // nodes / wnodes / tris / normals / uvs as created
+    // handles that render the SAME triangle / node arrays hold the same token (a clone that took its own snapshot of a
+    // translated scene does not): bf_scene_translate_meshes copies on write only while the token is shared
+    std::shared_ptr<char> geom_token;
+    // handles cloned from one another are meant to be in flight together (one per stream): how many of them have a rolling sequence
+    // open right now — small pools then launch a share of the persistent grids each (wf_setup: grid_share)
+    std::shared_ptr<std::atomic<int>> peers_rolling;
+    // one host thread at a time per handle (the handle owns the path pool its render's state lives in)
+    mutable std::atomic_flag busy = ATOMIC_FLAG_INIT;
+    // stream order between successive renders of the handle: a render on another stream than the previous one waits for it
+    mutable hipStream_t last_stream = nullptr;
+    mutable hipEvent_t last_done = nullptr;
+    mutable bool has_last = false;
+    std::vector<void *> owned;             // this handle's own allocations (small tables, spill columns, private geometry)
+    bf_scene_info info;
+    int device = 0;
+    int n_cus = 256;
+    std::vector<uint32_t> emitter_types;
+    // per-scene scratch for bf_render_device (counters), allocated once
+    unsigned long long *counters = nullptr;
+    // wavefront workspace, allocated on first use (mutable: lazily grown cache)
+    mutable bfd::WF wf;
+    mutable std::vector<void *> wf_owned;
+    uint32_t n_materials = 0;
+    bool any_back_material = false;        // some twosided material has a second nested BSDF (general kernels)
+    bool any_resample = false;             // some transmitter re-samples the path's wavelength (resample_freq: general kernels, DLaunch::resample)
+    bfd::DSensor sensor_host;              // host copy of the device sensor record
+    mutable uint32_t last_variant = 0;     // BF_VARIANT_* of the latest render (bf_stats.kernel_variant)
+    uint32_t film_w = 1, film_h = 1;       // the sensor's film (bf_sensor.film_width / film_height)
+    uint32_t adc_t = 0, adc_f = 0;         // what a receive-mode launch bins into: the ADC's window, or the whole ADC
+    MeshState mesh;                        // everything about moved meshes (bf_mesh.cpp)
+    // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
+    std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
+    std::vector<float *> array_dev;
+    std::vector<uint32_t> array_n;
+    float *sensor_array_dev = nullptr;
+    uint32_t sensor_array_n = 0;
+    mutable uint32_t *wf_host = nullptr;   // pinned read-back of queue counters
+    mutable hipEvent_t wf_event = nullptr;
+    mutable unsigned long long *wf_masks = nullptr;
+    mutable std::vector<hipEvent_t> wf_timing;   // event pool for per-kernel timing (stats only): pair k = events 2k, 2k + 1
+    mutable std::vector<int> wf_ev_kind;         // kind of every recorded pair: 0 trace, 1 shade, 2 tail
+    mutable float wf_ms[3] = {0, 0, 0};          // trace, shade, tail of the last stats render / rolling sequence
+    mutable uint32_t wf_iters = 0, wf_trace_launches = 0, wf_tail_launches = 0, wf_shade_launches = 0;
+    // Rolling sequence (bf_render_device with BF_FLAG_ROLLING, bf_scene_flush): see wf_roll_render
+    struct Roll {
+        bool open = false;
+        uint32_t count = 0;                      // renders issued since the sequence was opened
+        uint32_t it = 0;                         // bounce-iteration counter (mask parity runs on across calls)
+        bf_launch shape;                         // launch of the first render: later ones may differ in seed / path_offset only
+        bfd::DLaunch lp;                         // device launch of the sequence (n_paths = supply so far)
+        hipStream_t stream = nullptr;
+        bool count_nodes = false, timed = false;
+        uint32_t per_call = 1;                   // renders every call adds (bf_render_batch_device: the batch size)
+        bool offsets = false;                    // the renders carry mesh offsets (batched calls with moving meshes)
+        float dmax = 0.f;                        // largest |offset component| so far (box slack of the SHIFT traversal)
+        uint32_t window = 1;                     // renders of the LDS histogram window
+        uint32_t iters = 0;                      // bounce iterations per call (adapted from the live counts)
+        uint32_t flush_iters = 0;                // planned bounce iterations of a flush before its tail (learned)
+        uint32_t flush_live = 0;                 // slots alive at the flush's tail (learned: sizes its grid)
+        bool multi = false;                      // the endpoints moved between the renders of the sequence (kMulti kernels from then on)
+        uint32_t fb_call_iters = 0;              // iterations of the call whose live counts are in flight to wf_feedback
+        bool fb_is_flush = false;
+    };
+    mutable Roll roll;
+    // Endpoint-table versions of an open rolling sequence: bf_scene_update_endpoints writes the new tables into the next block of
+    // a pool instead of flushing the sequence (the renders issued so far keep reading theirs through the descriptor ring:
+    // bf_device.h: DRoll, kMulti); the home buffers (as created) hold the tables whenever no sequence is open.
+    struct TabLayout {
+        size_t o_rects = 0, o_shapes = 0, o_emit = 0, o_mat = 0, o_sensor = 0, stride = 0;
+    };
+    mutable TabLayout tab;
+    mutable char *tab_pool = nullptr;            // device: kRollRing blocks of tab.stride bytes (allocated on first use)
+    mutable uint32_t tab_next = 0;               // next free block
+    mutable bool tables_in_pool = false;         // d.rects ... d.sensor point into the pool
+    const bfd::DRect *home_rects = nullptr;
+    const bfd::DShape *home_shapes = nullptr;
+    const bfd::DEmitter *home_emitters = nullptr;
+    const bfd::DMaterial *home_materials = nullptr;
+    const bfd::DSensor *home_sensor = nullptr;
+    mutable bfd::DRoll *roll_ring = nullptr;     // device [kRollRing]
+    mutable float4 *roll_offsets = nullptr;      // device [kRollRing]: mesh offset of every render of the sequence
+    // Launch plan learned from the previous render of the same shape (wf_render): how many bounce
+    // iterations precede the tail and how many slots are then alive.  With a plan the whole render is
+    // enqueued without a host round trip; the live counts come back through a pinned buffer afterwards.
+    struct WfPlan {
+        bool valid = false;
+        uint64_t n_paths = 0;
+        uint32_t mode = 0, max_depth = 0, n_slots = 0, tail_max = 0;
+        uint32_t iters = 0, tail_live = 0;
+    };
+    mutable WfPlan wf_plan;
+    // Pinned staging for small host tables that travel with a launch (batch seeds / mesh offsets, endpoint records):
+    // a ring of slots, each with its own device mirror and an event recorded behind the copy, so the caller's arrays
+    // and our stack locals are free again when the call returns and nothing blocks unless kStageSlots launches are in
+    // flight on this scene.
+    static constexpr int kStageSlots = 8;
+    struct Stage {
+        void *host = nullptr, *dev = nullptr;
+        size_t cap = 0;
+        hipEvent_t ev = nullptr;
+        bool busy = false;
+    };
+    mutable Stage stage[kStageSlots];
+    mutable int stage_next = 0;
+    mutable uint32_t *wf_feedback = nullptr;     // pinned: n_live[0 .. wf_fb_iters) of the last planned render
+    mutable hipEvent_t wf_fb_event = nullptr;
+    mutable bool wf_fb_pending = false;
+    mutable uint32_t wf_fb_iters = 0;
+};
+
+#pragma GCC visibility push(hidden)      // from here on: internal to the library
+// One host thread at a time per handle: the second one gets BF_ERR_INVALID instead of a race on the handle's pool.
+struct BusyGuard {
+    const bf_scene *s;
+    bool ok;
+    int prev_device = -1;
+    // ... and every call runs on the handle's own device, whatever the caller's current one is (one host thread may
+    // drive the handles of several GPUs: bf_render_sharded_device), restored on return
+    explicit BusyGuard(const bf_scene *sc) : s(sc), ok(sc && !sc->busy.test_and_set(std::memory_order_acquire)) {
+        if (ok) {
+            int cur = -1;
+            if (hipGetDevice(&cur) == hipSuccess && cur != sc->device && hipSetDevice(sc->device) == hipSuccess) prev_device = cur;
+        }
+    }
+    ~BusyGuard() {
+        if (prev_device >= 0) (void) hipSetDevice(prev_device);
+        if (ok) s->busy.clear(std::memory_order_release);
+    }
+};
+// the handle's device for the calls that allocate or launch before (or without) taking the busy flag
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int device) {
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur != device && hipSetDevice(device) == hipSuccess) prev = cur;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void) hipSetDevice(prev);
+    }
+};
+#define BF_ENTER(scene)                                                                                                   \
+    BusyGuard busy_guard_(scene);                                                                                         \
+    if (!busy_guard_.ok)                                                                                                  \
+        return fail(BF_ERR_INVALID, "%s: the scene handle is in use by another host thread (one call at a time per handle; " \
+                                    "bf_scene_clone gives every thread / stream its own)", __func__)
+
+// ---- bf_api.cpp's, called by bf_mesh.cpp and documented where they are defined (C names: that file is one extern "C" block) ----
+extern "C" {
+bf_status fail(bf_status st, const char *fmt, ...);      // sets bf_last_error's text
+bf_status stage_acquire(const bf_scene *sc, size_t bytes, bf_scene::Stage **out);
+bf_status stage_commit(bf_scene::Stage *st, size_t bytes, hipStream_t stream);
+bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream);
+bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
+bf_status mark_last(const bf_scene *scene, hipStream_t stream);
+bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
+bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev, bf_path_record *records_dev,
+                        void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0);
+
+// ---- bf_mesh.cpp, called by bf_api.cpp ----
+// a device-form vertex update whose gather refused triangles: BF_ERR_DEVICE, once (wait: for the count; else only if it has landed)
+bf_status deform_report(const bf_scene *scene, bool wait);
+bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who, const bf_geometry::MeshTopo **topo_out);
+// bf_scene_clone: if `src` has moved, `sc` (a copy of src's kernel arguments so far) takes its own snapshot of what src renders now
+bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc);
+}
+
+#pragma GCC visibility pop

@@ -293,7 +293,7 @@ def check_quantised(qnodes, nodes):
 def origin_scale_bounds(sd, poses_seen=()):
     """(S_lo, S_hi) in float64 for the bound a handle of `sd` pads its boxes for.  S_lo: the largest |coordinate| of any sensor or
     emitter position, rectangle corner or mesh vertex of the description.  S_hi: S_lo raised, for every pose the handle has been
-    given, by the bound bf_api.cpp: moved_origin_scale documents: per row |t| + sum_c |R_rc| max(|box lo_c|, |box hi_c|), times
+    given, by the bound bf_mesh.cpp: origin_bound documents: per row |t| + sum_c |R_rc| max(|box lo_c|, |box hi_c|), times
     1 + 1e-5.  An entry of `poses_seen` is a float[n_shapes, 3, 4] table (a transform call: a mesh whose entry is the identity is
     not moved and does not count) or a dict {"xf": table, "all": True, "boxes": {shape: (lo, hi)}}: "all" counts every mesh (the
     pose re-applied after a vertex update), "boxes" replaces the base box of those meshes from this entry on (a vertex update: the
