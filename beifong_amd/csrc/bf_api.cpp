@@ -37,9 +37,6 @@ const char *ncclGetErrorString(ncclResult_t result);
 
 #include "bf_scene.h"
 
-extern "C" hipError_t bfk_launch_render(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
-                                        unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
-                                        hipStream_t stream);
 extern "C" float bfk_host_cos(float x);
 extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y);
 extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const float *rays, int any_hit, float *out_t,
@@ -52,53 +49,6 @@ extern "C" hipError_t bfk_launch_query(int op, const bfd::DScene *sc, uint64_t n
 extern "C" hipError_t bfk_launch_microfacet(int op, uint32_t type, float alpha_u, float alpha_v, uint32_t sample_visible, uint64_t n,
                                             const float *in, float *out, hipStream_t stream);
 
-extern "C" hipError_t bfk_wf_shade(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                   hipStream_t stream, int waves);
-extern "C" hipError_t bfk_wf_trace(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
-                                   hipStream_t stream, int waves);
-extern "C" hipError_t bfk_launch_tail(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
-                                      uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
-                                      hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap);
-extern "C" hipError_t bfk_roll_set(bfd::DRoll *ring, float4 *offsets, uint32_t idx, const bfd::DRoll *d, const float *offset3, hipStream_t stream);
-// BF_FLAG_FAST: the same launchers from the fast-arithmetic build of bf_kernels.hip / bf_wavefront.hip (bf_ns.h)
-extern "C" hipError_t bfk_launch_render_fast(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
-                                             unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
-                                             hipStream_t stream);
-extern "C" hipError_t bfk_wf_shade_fast(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                        float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                        hipStream_t stream, int waves);
-extern "C" hipError_t bfk_wf_trace_fast(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
-                                        hipStream_t stream, int waves);
-extern "C" hipError_t bfk_launch_tail_fast(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
-                                           uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
-                                           hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap);
-
-// BF_FLAG_MOMENT: the launchers of the kernels' second-moment variants (bf_device.h: kMoment; exact build only, same wf_trace)
-extern "C" hipError_t bfk_launch_render_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
-                                               unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
-                                               hipStream_t stream);
-extern "C" hipError_t bfk_wf_shade_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                          float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                          hipStream_t stream, int waves);
-extern "C" hipError_t bfk_launch_tail_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
-                                             uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
-                                             hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap);
-
-namespace {
-// the kernels one render runs: the exact build, the fast-arithmetic one (BF_FLAG_FAST) or the second-moment variants (BF_FLAG_MOMENT)
-struct Kernels {
-    decltype(&bfk_launch_render) render;
-    decltype(&bfk_wf_shade) shade;
-    decltype(&bfk_wf_trace) trace;
-    decltype(&bfk_launch_tail) tail;
-};
-const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail};
-const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast};
-const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment};
-// (BF_FLAG_MOMENT | BF_FLAG_FAST is refused before any kernel is chosen: render_locked)
-const Kernels &kernels_for(uint32_t flags) { return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : kExact); }
-}  // namespace
 
 static thread_local std::string g_err;
 
@@ -241,18 +191,9 @@ bf_status bf_scene_destroy(bf_scene *s) {
     if (!s) return BF_OK;
     // kernels of this handle that are still in flight read the arrays freed below (an open rolling sequence is simply
     // abandoned: its histograms stay incomplete, as documented)
-    if (s->has_last) (void) hipEventSynchronize(s->last_done);
-    if (s->roll.open && s->peers_rolling) s->peers_rolling->fetch_sub(1, std::memory_order_relaxed);
+    (void) s->run.last.wait();
+    if (s->run.roll.open && s->peers_rolling) s->peers_rolling->fetch_sub(1, std::memory_order_relaxed);
     for (void *p : s->owned) (void) hipFree(p);
-    for (void *p : s->wf_owned) (void) hipFree(p);
-    if (s->wf_host) (void) hipHostFree(s->wf_host);
-    if (s->wf_event) (void) hipEventDestroy(s->wf_event);
-    if (s->wf_feedback) (void) hipHostFree(s->wf_feedback);
-    if (s->wf_fb_event) (void) hipEventDestroy(s->wf_fb_event);
-    if (s->last_done) (void) hipEventDestroy(s->last_done);
-    for (hipEvent_t e : s->wf_timing) (void) hipEventDestroy(e);
-    if (s->counters) (void) hipFree(s->counters);
-    if (s->tab_pool) (void) hipFree(s->tab_pool);
     for (auto &st : s->stage) {
         if (st.ev) {
             (void) hipEventSynchronize(st.ev);
@@ -261,7 +202,7 @@ bf_status bf_scene_destroy(bf_scene *s) {
         if (st.host) (void) hipHostFree(st.host);
         if (st.dev) (void) hipFree(st.dev);
     }
-    delete s;
+    delete s;      // (~RenderState, ~MeshState: what renders and moved meshes allocated)
     return BF_OK;
 }
 
@@ -651,7 +592,6 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     if (!sc) return fail(BF_ERR_NOMEM, "out of host memory");
     std::memset(&sc->d, 0, sizeof(sc->d));
     std::memset(&sc->info, 0, sizeof(sc->info));
-    std::memset(&sc->wf, 0, sizeof(sc->wf));
     sc->tun = read_tunables();
     sc->geom = std::make_shared<bf_geometry>();
     sc->geom_token = std::make_shared<char>(0);
@@ -808,11 +748,7 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     std::vector<bfd::DSensor> sensor_vec(1, flat.sensor);
     UP(sensor_vec, sensor);
 #undef UP
-    sc->home_rects = sc->d.rects;
-    sc->home_shapes = sc->d.shapes;
-    sc->home_emitters = sc->d.emitters;
-    sc->home_materials = sc->d.materials;
-    sc->home_sensor = sc->d.sensor;
+    sc->run.tab.set_home(sc->d);
     sc->n_materials = desc->n_materials;
     sc->d.n_materials = desc->n_materials;
     sc->d.tab_cache = (sc->tun.tab_cache && desc->n_materials <= bfd::kTabMaxMaterials && rects.size() <= bfd::kTabMaxRects) ? 1u : 0u;
@@ -833,8 +769,8 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     sc->d.lambda_min = desc->physics.lambda_min_nm;
     sc->d.lambda_max = desc->physics.lambda_max_nm;
 
-    hipError_t e = hipMalloc((void **) &sc->counters, sizeof(unsigned long long) * bfd::CTR_COUNT);
-    if (e == hipSuccess) e = hipMemset(sc->counters, 0, sizeof(unsigned long long) * bfd::CTR_COUNT);
+    hipError_t e = hipMalloc((void **) &sc->run.counters, sizeof(unsigned long long) * bfd::CTR_COUNT);
+    if (e == hipSuccess) e = hipMemset(sc->run.counters, 0, sizeof(unsigned long long) * bfd::CTR_COUNT);
     if (e != hipSuccess) {
         bf_scene_destroy(sc);
         return fail(BF_ERR_DEVICE, "hipMalloc(counters): %s", hipGetErrorString(e));
@@ -895,8 +831,8 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
     for (float *p : scene->array_dev) phased = phased || p != nullptr;
     bool resample_new = false;
     for (const auto &e : f.emitters) resample_new = resample_new || e.resample != 0u;
-    const bool join = scene->roll.open && scene->roll.stream == stream && !phased && scene->sensor_host.filt_n == 0u && f.sensor.filt_n == 0u &&
-                      scene->tab_next + 1u < bfd::kRollRing && scene->tun.roll_join && resample_new == scene->any_resample;
+    const bool join = scene->run.roll.open && scene->run.roll.stream == stream && !phased && scene->sensor_host.filt_n == 0u && f.sensor.filt_n == 0u &&
+                      scene->run.tab.next + 1u < bfd::kRollRing && scene->tun.roll_join && resample_new == scene->any_resample;
     {
         bf_status ost = order_after_last(scene, stream);
         if (ost == BF_OK && !join) ost = close_sequence(scene, stream);
@@ -918,19 +854,13 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
                      o_sensor = o_mat + up16(b_mat), total = o_sensor + up16(b_sensor);
         // where the tables go: the home buffers, or — joining an open sequence — the next block of the pool (same layout as the
         // staging slot)
-        char *dst_rects = (char *) scene->home_rects, *dst_shapes = (char *) scene->home_shapes, *dst_emit = (char *) scene->home_emitters,
-             *dst_mat = (char *) scene->home_materials, *dst_sensor = (char *) scene->home_sensor;
+        RenderState::Tables &tab = scene->run.tab;
+        char *dst_rects = (char *) tab.rects, *dst_shapes = (char *) tab.shapes, *dst_emit = (char *) tab.emitters,
+             *dst_mat = (char *) tab.materials, *dst_sensor = (char *) tab.sensor;
         if (join) {
-            if (!scene->tab_pool) {
-                scene->tab.o_rects = o_rects;
-                scene->tab.o_shapes = o_shapes;
-                scene->tab.o_emit = o_emit;
-                scene->tab.o_mat = o_mat;
-                scene->tab.o_sensor = o_sensor;
-                scene->tab.stride = (total + 255) & ~size_t(255);
-                HIP_TRY(hipMalloc((void **) &scene->tab_pool, scene->tab.stride * bfd::kRollRing));
-            }
-            char *blk = scene->tab_pool + scene->tab.stride * scene->tab_next;
+            char *blk = nullptr;
+            bf_status cst = tab.claim({o_rects, o_shapes, o_emit, o_mat, o_sensor, total}, &blk);
+            if (cst != BF_OK) return cst;
             dst_rects = blk + o_rects;
             dst_shapes = blk + o_shapes;
             dst_emit = blk + o_emit;
@@ -968,9 +898,8 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
         scene->d.materials = b_mat ? (const bfd::DMaterial *) dst_mat : scene->d.materials;
         scene->d.sensor = (const bfd::DSensor *) dst_sensor;
         if (join) {
-            ++scene->tab_next;
-            scene->tables_in_pool = true;
-            scene->roll.multi = true;
+            tab.joined();
+            scene->run.roll.multi = true;
         }
     }
     // every profile bit bf_scene_create derived from the tables just replaced (lean_profile reads them at the next render)
@@ -994,10 +923,10 @@ bf_status bf_scene_read_bvh(const bf_scene *scene, uint32_t width, void *nodes_o
     if (width != 4u && width != 16u) return fail(BF_ERR_INVALID, "bf_scene_read_bvh: width %u (4 or 16)", width);
     BF_ENTER(scene);
     {
-        bf_status cst = close_sequence(scene, scene->roll.stream);
+        bf_status cst = close_sequence(scene, scene->run.roll.stream);
         if (cst != BF_OK) return cst;
     }
-    if (scene->has_last) HIP_TRY(hipEventSynchronize(scene->last_done));
+    HIP_TRY(scene->run.last.wait());
     if (width == 16u && !scene->d.wnodes) return fail(BF_ERR_UNSUPPORTED, "bf_scene_read_bvh: the scene has no sixteen-wide tree");
     const uint64_t need = width == 4u ? (uint64_t) scene->d.n_nodes * sizeof(bf::Node4) : (uint64_t) scene->d.n_wnodes * sizeof(bf::Node16);
     if (nodes_bytes < need || (need && !nodes_out))
@@ -1021,7 +950,7 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
     *out = nullptr;
     BF_ENTER(src);
     {
-        bf_status cst = close_sequence(src, src->roll.stream);
+        bf_status cst = close_sequence(src, src->run.roll.stream);
         if (cst != BF_OK) return cst;
     }
     HIP_TRY(hipDeviceSynchronize());      // pending endpoint updates / translations of `src` are part of what is cloned
@@ -1032,7 +961,6 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
     sc->geom = src->geom;
     sc->geom_token = src->geom_token;      // replaced below if the clone takes its own snapshot
     sc->peers_rolling = src->peers_rolling;
-    std::memset(&sc->wf, 0, sizeof(sc->wf));
     sc->info = src->info;
     sc->device = src->device;
     sc->n_cus = src->n_cus;
@@ -1111,1032 +1039,15 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
         sc->d.spill = (int *) p;
     }
     {
-        hipError_t e = hipMalloc((void **) &sc->counters, sizeof(unsigned long long) * bfd::CTR_COUNT);
-        if (e == hipSuccess) e = hipMemset(sc->counters, 0, sizeof(unsigned long long) * bfd::CTR_COUNT);
+        hipError_t e = hipMalloc((void **) &sc->run.counters, sizeof(unsigned long long) * bfd::CTR_COUNT);
+        if (e == hipSuccess) e = hipMemset(sc->run.counters, 0, sizeof(unsigned long long) * bfd::CTR_COUNT);
         if (e != hipSuccess) return fail_out(fail(BF_ERR_DEVICE, "bf_scene_clone: counters: %s", hipGetErrorString(e)));
     }
-    sc->home_rects = sc->d.rects;
-    sc->home_shapes = sc->d.shapes;
-    sc->home_emitters = sc->d.emitters;
-    sc->home_materials = sc->d.materials;
-    sc->home_sensor = sc->d.sensor;
+    sc->run.tab.set_home(sc->d);
     *out = sc;
     return BF_OK;
 }
 
-
-// ---------------------------------------------------------------------------
-// wavefront driver
-// ---------------------------------------------------------------------------
-static bf_status wf_ensure(const bf_scene *scene, uint32_t capacity) {
-    bfd::WF &wf = scene->wf;
-    if (wf.capacity >= capacity) return BF_OK;
-    for (void *p : scene->wf_owned) (void) hipFree(p);
-    scene->wf_owned.clear();
-    std::memset(&wf, 0, sizeof(wf));
-    scene->roll_ring = nullptr;
-    scene->roll_offsets = nullptr;
-    auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-        hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) scene->wf_owned.push_back(*p);
-        return e;
-    };
-    size_t n = capacity, nb = capacity / 64;
-    HIP_TRY(alloc((void **) &wf.recA, n * 64));
-    HIP_TRY(alloc((void **) &wf.recB, n * 64));
-    HIP_TRY(alloc((void **) &wf.recC, n * 64));
-    HIP_TRY(alloc((void **) &scene->wf_masks, 8 * nb * sizeof(unsigned long long)));
-    HIP_TRY(alloc((void **) &wf.n_live, (bfd::kWfMaxIter + 2) * sizeof(uint32_t)));
-    HIP_TRY(alloc((void **) &scene->roll_ring, bfd::kRollRing * sizeof(bfd::DRoll)));
-    HIP_TRY(alloc((void **) &scene->roll_offsets, bfd::kRollRing * sizeof(float4)));
-    HIP_TRY(alloc((void **) &wf.surv_cursor, 64));
-    wf.counters = scene->counters;
-    wf.capacity = capacity;
-    if (!scene->wf_host) HIP_TRY(hipHostMalloc((void **) &scene->wf_host, 64));
-    if (!scene->wf_event) HIP_TRY(hipEventCreateWithFlags(&scene->wf_event, hipEventDisableTiming));
-    if (!scene->wf_feedback) HIP_TRY(hipHostMalloc((void **) &scene->wf_feedback, (bfd::kWfMaxIter + 2) * sizeof(uint32_t)));
-    if (!scene->wf_fb_event) HIP_TRY(hipEventCreateWithFlags(&scene->wf_fb_event, hipEventDisableTiming));
-    scene->wf_plan.valid = false;
-    scene->wf_fb_pending = false;
-    return BF_OK;
-}
-
-// Live slots at which the wavefront iterations hand over to the tail kernel.  A bounce iteration of a nearly empty pool
-// costs ~0.5 ms of launch and latency floor whatever it holds, the tail ~25 us per bounce: large pools (the pipelined
-// bench step, sweeps) switch at 2^17 live slots — more would keep the tail's 168-VGPR waves on the CUs the next renders'
-// kernels want (measured: 2^18 costs 12 % of the pipelined C2 rate) — small pools, whose kernels never fill the chip,
-// switch as soon as half the pool is done (C3: 1.21 -> 0.98 ms per render, C4 shard: 1.71 -> 1.30).
-static uint32_t wf_tail_threshold(const bf_scene *scene, uint32_t n_slots) {
-    if (scene->tun.tail >= 0) return (uint32_t) scene->tun.tail;
-    if (n_slots >= bfd::kTailSmallPool) return 1u << 17;
-    return std::max<uint32_t>(1u << 17, std::min<uint32_t>(1u << 19, n_slots / 2));
-}
-
-namespace {
-// Everything the launches of one render (or of one call of a rolling sequence) share.
-struct WfCtx {
-    const bf_scene *scene;
-    const Kernels *k;
-    const bfd::DLaunch *lp;
-    float *hist;
-    bf_path_record *rec;
-    hipStream_t stream;
-    bool count_nodes, timed;
-    size_t mask_bytes, lds_shade, lds_tail;
-    unsigned grid_shade, grid_trace;
-    uint32_t tail_max;
-};
-}  // namespace
-
-// per-kernel timing (stats renders, BF_FLAG_TIMING sequences): one event pair around every launch
-static hipError_t wf_tic(const WfCtx &c, int kind) {
-    if (!c.timed) return hipSuccess;
-    const bf_scene *sc = c.scene;
-    while (sc->wf_timing.size() < 2 * (sc->wf_ev_kind.size() + 1)) {
-        hipEvent_t e;
-        hipError_t he = hipEventCreate(&e);
-        if (he != hipSuccess) return he;
-        sc->wf_timing.push_back(e);
-    }
-    sc->wf_ev_kind.push_back(kind);
-    return hipEventRecord(sc->wf_timing[2 * (sc->wf_ev_kind.size() - 1)], c.stream);
-}
-static hipError_t wf_toc(const WfCtx &c) {
-    if (!c.timed) return hipSuccess;
-    return hipEventRecord(c.scene->wf_timing[2 * (c.scene->wf_ev_kind.size() - 1) + 1], c.stream);
-}
-// wait for the stream and add the recorded pairs up by kind (wf_ms), then forget them
-static bf_status wf_collect_timing(const bf_scene *scene, hipStream_t stream) {
-    scene->wf_ms[0] = scene->wf_ms[1] = scene->wf_ms[2] = 0.f;
-    scene->wf_tail_launches = scene->wf_shade_launches = 0;
-    if (scene->wf_ev_kind.empty()) return BF_OK;
-    HIP_TRY(hipStreamSynchronize(stream));
-    for (size_t k = 0; k < scene->wf_ev_kind.size(); ++k) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, scene->wf_timing[2 * k], scene->wf_timing[2 * k + 1]));
-        scene->wf_ms[scene->wf_ev_kind[k]] += ms;
-        if (scene->wf_ev_kind[k] == 2) ++scene->wf_tail_launches;
-        if (scene->wf_ev_kind[k] == 1) ++scene->wf_shade_launches;
-    }
-    scene->wf_ev_kind.clear();
-    return BF_OK;
-}
-
-// pool size, masks, scheduling knobs and grids for `lp` on this handle
-static bf_status wf_setup(const bf_scene *scene, const Kernels &k, const bfd::DLaunch &lp, uint64_t pool_paths, float *hist_dev,
-                          bf_path_record *records_dev, hipStream_t stream, bool count_nodes, bool timed, WfCtx &c, bool rolling = false) {
-    uint64_t want = std::min<uint64_t>(scene->tun.pool, std::max<uint64_t>(pool_paths, 64));
-    uint32_t n_main = (uint32_t) ((want + 63) & ~uint64_t(63)), n_surv = 0;
-    if (rolling) {
-        // two renders' worth of main slots (a slot's next path is supplied two calls after its current one) + the
-        // survivor area for the paths that are still alive by then (bf_wavefront.h)
-        n_main = (uint32_t) ((std::max<uint64_t>(2 * pool_paths, 128) + 63) & ~uint64_t(63));
-        // at least one survivor batch per shading wave: a wave claims whole batches (surv_claims_max each per launch) and
-        // all the claims of one launch must be distinct batches (wf_shade: surv_take)
-        const uint32_t surv_min = (uint32_t) scene->n_cus * 4u * (uint32_t) std::max(2, scene->tun.shade_waves) * 64u;
-        n_surv = std::max<uint32_t>(surv_min, std::min<uint32_t>(1u << 21, (n_main / 8 + 63) & ~63u));
-        // test hook (BF_DEBUG_SURV_BATCHES): a survivor area far too small for the claims its waves may make, to see the loud
-        // check of surv_take fire (tests/test_gpu_rolling.py)
-        if (scene->tun.debug_surv_batches) n_surv = scene->tun.debug_surv_batches * 64u;
-    }
-    bf_status st = wf_ensure(scene, n_main + n_surv);
-    if (st != BF_OK) return st;
-    bfd::WF &wf = scene->wf;
-    wf.n_main = rolling ? n_main : (uint32_t) ((std::min<uint64_t>(wf.capacity, pool_paths) + 63) & ~uint64_t(63));
-    wf.n_surv = n_surv;
-    wf.n_slots = wf.n_main + wf.n_surv;
-    wf.trace_refill = scene->tun.trace_refill;
-    wf.trace_stragglers = scene->tun.trace_stragglers;
-    wf.shade_chain = scene->tun.shade_chain;
-    wf.row_jobs = scene->tun.row_jobs;
-    wf.iq = lp.iq;
-    wf.has_render = lp.batch != 0u ? 1u : 0u;
-    wf.offsets = lp.batch_offsets;
-    wf.has_dop = (lp.doppler || lp.resample) ? 1u : 0u;
-    wf.box_slack = lp.box_slack;
-    wf.geom_stride = lp.geom_stride;
-    const size_t nb = wf.n_slots / 64;
-    for (int b = 0; b < 2; ++b) {      // alive | trace | shadow of one parity are contiguous: one memset per bounce
-        wf.m_alive[b] = scene->wf_masks + (4 * b + 0) * nb;
-        wf.m_trace[b] = scene->wf_masks + (4 * b + 1) * nb;
-        wf.m_shadow[b] = scene->wf_masks + (4 * b + 2) * nb;
-        wf.m_hit[b] = scene->wf_masks + (4 * b + 3) * nb;
-    }
-    c.scene = scene;
-    c.k = &k;
-    c.lp = &lp;
-    c.hist = hist_dev;
-    c.rec = records_dev;
-    c.stream = stream;
-    c.count_nodes = count_nodes;
-    c.timed = timed;
-    c.mask_bytes = 4 * nb * sizeof(unsigned long long);
-    wf.hit_split = scene->tun.shade_split ? 1u : 0u;
-    wf.chain_min = scene->tun.chain_min;
-    c.lds_shade = ((sizeof(float) * lp.lds_floats + 15) & ~size_t(15)) + (scene->d.tab_cache ? bfd::kTabBytes : 0u);      // histogram | tables
-    c.lds_tail = sizeof(int) * bfd::kStackDepth * bfd::kBlock + c.lds_shade;
-    // persistent grids: shade is register-heavy (3 workgroups per CU at 168 VGPRs), trace runs
-    // 5 workgroups per CU (28.6 KiB of LDS each: stacks + the tree's top levels; 96 VGPRs)
-    const unsigned batches_per_block = bfd::kBlock / 64;
-    const unsigned max_blocks = (unsigned) ((nb + batches_per_block - 1) / batches_per_block);
-    c.grid_shade = std::max(1u, std::min((unsigned) scene->n_cus * (unsigned) std::max(2, scene->tun.shade_waves), max_blocks));
-    c.grid_trace = std::max(1u, std::min((unsigned) scene->n_cus * (unsigned) scene->tun.trace_waves, max_blocks));
-    // Small pools never fill the chip: their launches sit at latency floors with nearly idle waves, and a grid sized for the whole GPU
-    // keeps the next handle's launch out until it has drained.  Handles that roll side by side (clones of one scene, one per stream)
-    // therefore launch a SHARE of the persistent grids each, so that their launches overlap: C3 0.50 -> 0.45 ms per step, a C4 shard
-    // 0.62 -> 0.57 with four handles (profiles/r04_grid_share_ab.txt); a handle that rolls alone keeps the full grids (a lone launch
-    // is 20 % slower on a third of them).
-    if (rolling && scene->tun.grid_share > 1u && wf.n_slots < scene->tun.grid_small) {
-        const unsigned peers = (unsigned) std::max(1, scene->peers_rolling->load(std::memory_order_relaxed));
-        const unsigned share = std::min(peers, (unsigned) scene->tun.grid_share);
-        c.grid_shade = std::max(1u, c.grid_shade / share);
-        c.grid_trace = std::max(1u, c.grid_trace / share);
-    }
-    c.tail_max = wf_tail_threshold(scene, rolling ? wf.n_main / 2 : wf.n_slots);
-    wf.surv_claims_max = (wf.n_surv / 64u) / std::max(1u, c.grid_shade * batches_per_block);      // >= 1 by the sizing above
-    if (rolling && scene->tun.debug_surv_batches) {                                                   // (the test hook: no rule at all)
-        const char *e = getenv("BF_DEBUG_SURV_CLAIMS");
-        wf.surv_claims_max = e ? (uint32_t) strtoul(e, nullptr, 10) : 1u << 20;
-    }
-    return BF_OK;
-}
-// One bounce iteration `it`: clear the next parity's masks, shade (first: 0 alive masks, 1 first bounce of a pool, 2 alive
-// masks then the wake launch of a rolling call), trace.
-static bf_status wf_iteration(const WfCtx &c, uint32_t it, int first) {
-    const bf_scene *scene = c.scene;
-    const bfd::WF &wf = scene->wf;
-    const int nxt = (it & 1) ^ 1;
-    HIP_TRY(hipMemsetAsync(wf.m_alive[nxt], 0, c.mask_bytes, c.stream));     // alive, trace, shadow, hit are contiguous
-    if (first != 1) {
-        // first launch of a rolling call (first == 2): the evicting variant — long paths make room for the new render's
-        HIP_TRY(wf_tic(c, 1));
-        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first == 2 ? 3 : 0, c.hist, c.rec, c.grid_shade, c.lds_shade, c.stream,
-                           scene->tun.shade_waves));
-        HIP_TRY(wf_toc(c));
-    }
-    if (first != 0) {
-        HIP_TRY(wf_tic(c, 1));
-        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first, c.hist, c.rec, c.grid_shade, c.lds_shade, c.stream, scene->tun.shade_waves));
-        HIP_TRY(wf_toc(c));
-    }
-    return BF_OK;
-}
-static bf_status wf_trace_launch(const WfCtx &c, uint32_t it) {
-    HIP_TRY(wf_tic(c, 0));
-    HIP_TRY(c.k->trace(&c.scene->d, &c.scene->wf, it, c.count_nodes ? 1 : 0, c.grid_trace, c.stream, c.scene->tun.trace_waves));
-    HIP_TRY(wf_toc(c));
-    return BF_OK;
-}
-static bf_status wf_tail_launch(const WfCtx &c, uint32_t it, uint32_t est_live, bool alone = false) {
-    const bf_scene *scene = c.scene;
-    // `alone`: nothing else wants the CUs (the flush of a rolling sequence): spread the paths thinly — up to four waves
-    // share a batch, so a wave starts with <= 16 paths and walks four lanes per ray from its first bounce instead of
-    // waiting for the longest of 64 lane-per-ray walks (half of a tail's cycles are those dense iterations)
-    uint32_t share = 1;
-    if (!alone && scene->tun.tail_share > 1) {
-        share = scene->tun.tail_share >= 4 ? 4u : 2u;
-        est_live = (uint32_t) std::min<uint64_t>((uint64_t) est_live * share, 1u << 30);
-    }
-    if (alone) {
-        const uint32_t resident = (uint32_t) scene->n_cus * 4u * 3u;          // waves at 3 per SIMD
-        while (share < 4u && (uint64_t) est_live * (share * 2u) / 64u <= resident) share *= 2u;
-        est_live = (uint32_t) std::min<uint64_t>((uint64_t) est_live * share, 1u << 30);
-    }
-    scene->wf.tail_share = share;
-    HIP_TRY(wf_tic(c, 2));
-    HIP_TRY(c.k->tail(&scene->d, c.lp, &scene->wf, it, est_live, c.hist, c.rec, c.count_nodes ? 1 : 0, c.lds_tail, c.stream,
-                      scene->tun.tail_waves, scene->tun.tail_spread, scene->tun.tail_blocks));
-    HIP_TRY(wf_toc(c));
-    return BF_OK;
-}
-// The guard word of wf_trace (CTR_GUARD) is never cleared by a render, so it is sticky across the renders of a handle.
-// So is the survivor-area word of rolling sequences (CTR_SURV_GUARD: wf_shade: surv_take refused a claim).
-static bf_status wf_guard_error(unsigned long long lost, unsigned long long refused = 0) {
-    if (lost)
-        return fail(BF_ERR_DEVICE, "wf_trace's iteration guard dropped %llu rays in an earlier render of this scene: that render's "
-                                   "histogram is wrong (a traversal bug; please report the scene)", lost);
-    return fail(BF_ERR_DEVICE, "a launch of a rolling sequence of this scene tried to claim %llu survivor batches beyond the size of "
-                               "its survivor area (the claims were refused: no path was lost, but the sizing rule of wf_setup is "
-                               "violated; please report the scene and the launch)", refused);
-}
-// every path of a completed render / sequence was binned exactly once (CTR_FILM counts film_put calls): the loud form of the
-// tests' "sum of the weight channel + invalid samples == paths"
-static bf_status check_film_count(const unsigned long long *c, uint64_t n_paths) {
-    if (c[bfd::CTR_FILM] != n_paths)
-        return fail(BF_ERR_DEVICE, "%llu of %llu paths were binned: paths were lost or binned twice (a scheduling bug; please report the "
-                                   "scene and the launch)", (unsigned long long) c[bfd::CTR_FILM], (unsigned long long) n_paths);
-    return BF_OK;
-}
-// read + clear the sticky words of a handle whose work has completed; *lost / *refused as found
-static bf_status read_guards(const bf_scene *scene, unsigned long long *lost, unsigned long long *refused) {
-    unsigned long long g[2] = {0, 0};
-    HIP_TRY(hipMemcpy(g, scene->counters + bfd::CTR_GUARD, sizeof(g), hipMemcpyDeviceToHost));
-    if (g[0] || g[1]) {
-        HIP_TRY(hipMemset(scene->counters + bfd::CTR_GUARD, 0, sizeof(g)));
-        scene->wf_fb_pending = false;       // (a copy of the words may be in flight to the next planned render's feedback)
-    }
-    *lost = g[0];
-    *refused = g[1];
-    return BF_OK;
-}
-
-// Host control loop.  Per bounce `it`: [zero the next masks] -> wf_shade(it) ->
-// [copy the live-slot counter] -> wf_trace(it).  The host waits for the counter of
-// bounce `it` while wf_trace(it) is still running, so the device never idles on
-// the decision; once at most wf_tail_threshold() slots are live, one tail launch
-// finishes them (including the paths those slots still have to start).
-static bf_status wf_render(const bf_scene *scene, const Kernels &k, const bfd::DLaunch &lp, float *hist_dev, bf_path_record *records_dev,
-                           hipStream_t stream, bool count_nodes, bool stats) {
-    WfCtx c;
-    bf_status st = wf_setup(scene, k, lp, lp.n_paths, hist_dev, records_dev, stream, count_nodes, stats, c);
-    if (st != BF_OK) return st;
-    bfd::WF &wf = scene->wf;
-    HIP_TRY(hipMemsetAsync(wf.n_live, 0, (bfd::kWfMaxIter + 2) * sizeof(uint32_t), stream));
-    const uint32_t tail_max = c.tail_max;
-    volatile uint32_t *hq = scene->wf_host;      // [0] = n_live[it]
-    scene->wf_ev_kind.clear();
-    auto finish = [&](uint32_t iters, uint32_t traces) -> bf_status {
-        scene->wf_iters = iters;
-        scene->wf_trace_launches = traces;
-        if (!stats) {
-            scene->wf_ms[0] = scene->wf_ms[1] = scene->wf_ms[2] = 0.f;
-            return BF_OK;
-        }
-        return wf_collect_timing(scene, stream);
-    };
-    // ---- planned render: no host round trip ------------------------------------------------------
-    bf_scene::WfPlan &plan = scene->wf_plan;
-    const uint32_t depth_key = (uint32_t) lp.max_depth;
-    const bool fb_ready = scene->wf_fb_pending && hipEventQuery(scene->wf_fb_event) == hipSuccess;
-    (void) hipGetLastError();      // hipErrorNotReady from the query must not leak into the launch checks below
-    if (fb_ready && scene->roll.fb_call_iters) {      // the counts in flight belong to a rolling call: not this plan's
-        scene->wf_fb_pending = false;
-        scene->roll.fb_call_iters = 0;
-    } else if (fb_ready) {
-        // live counts of the last planned render: move the switch to the tail to where it belongs
-        scene->wf_fb_pending = false;
-        const unsigned long long lost = reinterpret_cast<volatile unsigned long long *>(scene->wf_host)[1];
-        const unsigned long long refused = reinterpret_cast<volatile unsigned long long *>(scene->wf_host)[2];
-        if (lost || refused) {
-            HIP_TRY(hipMemsetAsync(scene->counters + bfd::CTR_GUARD, 0, 2 * sizeof(unsigned long long), stream));
-            return wf_guard_error(lost, refused);
-        }
-        const uint32_t *nl = scene->wf_feedback;
-        uint32_t k = 0;
-        while (k < scene->wf_fb_iters && nl[k] > plan.tail_max) ++k;
-        if (k < scene->wf_fb_iters) {
-            plan.iters = k + 1;
-            plan.tail_live = nl[k];
-        } else {                       // still above the threshold after the planned iterations: extend
-            plan.iters = std::min<uint32_t>(scene->wf_fb_iters + 2, bfd::kWfMaxIter - 1);
-            plan.tail_live = nl[scene->wf_fb_iters - 1];
-        }
-    }
-    if (scene->tun.allow_plan && plan.valid && plan.n_paths == lp.n_paths && plan.mode == lp.mode &&
-        plan.max_depth == depth_key && plan.n_slots == wf.n_slots && plan.tail_max == tail_max && plan.iters > 0) {
-        for (uint32_t it = 0; it < plan.iters; ++it) {
-            if ((st = wf_iteration(c, it, it == 0 ? 1 : 0)) != BF_OK) return st;
-            if ((st = wf_trace_launch(c, it)) != BF_OK) return st;
-        }
-        // the tail kernel finishes whatever is alive, whatever the estimate: the estimate only sizes its grid
-        const uint32_t est = std::max<uint32_t>(plan.tail_live + plan.tail_live / 4, 64u * bfd::kBlock);
-        if ((st = wf_tail_launch(c, plan.iters, est)) != BF_OK) return st;
-        if (!scene->wf_fb_pending) {
-            HIP_TRY(hipMemcpyAsync(scene->wf_feedback, wf.n_live, plan.iters * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(reinterpret_cast<unsigned long long *>(scene->wf_host) + 1, wf.counters + bfd::CTR_GUARD,
-                                   2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipEventRecord(scene->wf_fb_event, stream));
-            scene->wf_fb_pending = true;
-            scene->wf_fb_iters = plan.iters;
-            scene->roll.fb_call_iters = 0;
-        }
-        return finish(plan.iters, plan.iters);
-    }
-    auto learn = [&](uint32_t iters, uint32_t live) {
-        plan.valid = true;
-        plan.n_paths = lp.n_paths;
-        plan.mode = lp.mode;
-        plan.max_depth = depth_key;
-        plan.n_slots = wf.n_slots;
-        plan.tail_max = tail_max;
-        plan.iters = iters;
-        plan.tail_live = live;
-        scene->wf_fb_pending = false;
-    };
-
-    // ---- synchronous render (first render of a shape, or per-kernel statistics requested) ----------
-    for (uint32_t it = 0; it < bfd::kWfMaxIter; ++it) {
-        if ((st = wf_iteration(c, it, it == 0 ? 1 : 0)) != BF_OK) return st;
-        HIP_TRY(hipMemcpyAsync((void *) &hq[0], wf.n_live + it, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(scene->wf_event, stream));
-        if ((st = wf_trace_launch(c, it)) != BF_OK) return st;
-        HIP_TRY(hipEventSynchronize(scene->wf_event));
-        uint32_t n_live = hq[0];
-        if (n_live == 0) {
-            learn(it + 1, 0);
-            return finish(it + 1, it + 1);
-        }
-        if (n_live <= tail_max) {
-            learn(it + 1, n_live);
-            if ((st = wf_tail_launch(c, it + 1, n_live)) != BF_OK) return st;
-            return finish(it + 1, it + 1);
-        }
-    }
-    return fail(BF_ERR_UNSUPPORTED, "path depth exceeded the wavefront iteration limit (%u bounces)", bfd::kWfMaxIter);
-}
-
-// ---------------------------------------------------------------------------
-// Rolling sequences (BF_FLAG_ROLLING).  Every render ends in a latency-bound tail of a few long Russian-roulette
-// survivors (126-174 bounces among 2^20 paths) that costs a quarter of a 2^24-path step and three quarters of a 2^20-path
-// one.  Consecutive renders of one handle that only differ in seed / shard offset / output buffer — the steps of a
-// Monte-Carlo accumulation, the pulses of a coherent interval (python_scripts/animated_trans_rad.py:307-384,
-// Receive.ipynb cell 30 run such loops one render() / receive() per frame) — therefore form ONE batched launch whose
-// path supply grows by one render per call: slot i renders global paths i, i + n_slots, ... (render = g / n_paths), a
-// call enqueues a few bounce iterations over the whole pool (first the slots still alive, then a "wake" launch that
-// starts the next path of every idle slot), and the survivors of render k simply ride along with the launches of
-// renders k + 1, k + 2, ... .  One tail runs per sequence: bf_scene_flush (or anything that needs the pool: another kind
-// of render, an endpoint update, a clone).  Every path is the path a stand-alone render would trace (own PCG32 stream).
-// ---------------------------------------------------------------------------
-static bool roll_same_shape(const bf_launch &a, const bf_launch &b) {
-    return a.mode == b.mode && a.color_mode == b.color_mode && a.n_paths == b.n_paths && a.max_depth == b.max_depth &&
-           a.rr_depth == b.rr_depth && a.bins == b.bins && a.bins_y == b.bins_y && a.bin_width == b.bin_width &&
-           a.time_c == b.time_c && a.flags == b.flags && a.phase_bins == b.phase_bins;
-}
-
-static bf_status wf_roll_flush(const bf_scene *scene, hipStream_t stream, bool sync_timing);
-
-static bf_status wf_roll_render(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, const bfd::DLaunch &lp_in,
-                                float *hist_dev, bf_path_record *records_dev, hipStream_t stream) {
-    bf_scene::Roll &r = scene->roll;
-    bf_status st;
-    const uint32_t K = batch ? batch->n_renders : 1u;          // renders this call adds to the sequence
-    const bool with_offsets = batch && batch->mesh_offsets && scene->d.n_tris != 0;
-    if (r.open && (!roll_same_shape(r.shape, *launch) || r.per_call != K || r.offsets != with_offsets ||
-                   r.count + K > bfd::kRollRing || r.stream != stream)) {
-        if ((st = wf_roll_flush(scene, r.stream, false)) != BF_OK) return st;
-        if (r.stream != stream) {
-            // the flush ran on the old stream: the new sequence's first launches reuse the pool behind it
-            HIP_TRY(hipEventRecord(scene->wf_event, r.stream));
-            HIP_TRY(hipStreamWaitEvent(stream, scene->wf_event, 0));
-        }
-    }
-    const bool opening = !r.open;
-    if (opening) {
-        // what the previous sequence of this handle learned (iterations per call, the flush's plan) only fits its shape
-        if (!roll_same_shape(r.shape, *launch) || r.per_call != K) r.iters = r.flush_iters = r.flush_live = 0;
-        r.shape = *launch;
-        r.lp = lp_in;
-        r.lp.batch = 1u;
-        r.lp.batch_paths = launch->n_paths;
-        r.lp.batch_seeds = nullptr;              // seeds, offsets and buffers of a rolling render live in its descriptor
-        r.lp.batch_offsets = nullptr;
-        r.lp.box_slack = 0.f;
-        r.lp.has_records = 0u;
-        r.per_call = K;
-        r.multi = false;
-        r.offsets = with_offsets;
-        r.dmax = 0.f;
-        r.count = 0;
-        r.it = 0;
-        r.stream = stream;
-        r.count_nodes = (launch->flags & BF_FLAG_STATS) != 0;
-        r.timed = (launch->flags & BF_FLAG_TIMING) != 0;
-        // LDS window: the newest renders' histogram blocks, as many as fit
-        r.window = 1;
-        r.lp.lds_hist = (lp_in.n_chan <= (uint32_t) bfd::kMaxLdsHist && !(launch->flags & BF_FLAG_GLOBAL_ATOMICS)) ? 1u : 0u;
-        if (r.lp.lds_hist) r.window = std::max<uint32_t>(1u, std::min<uint32_t>(bfd::kRollWindow, (uint32_t) bfd::kMaxLdsHist / std::max(1u, lp_in.n_chan)));
-        HIP_TRY(hipMemsetAsync(scene->counters, 0, sizeof(unsigned long long) * bfd::CTR_GUARD, stream));
-        scene->wf_ev_kind.clear();
-        scene->wf_iters = scene->wf_trace_launches = 0;
-    }
-    const bool fresh_pool = opening;
-    const uint32_t k = r.count, newest = k + K - 1u;
-    bfd::DLaunch &lp = r.lp;
-    lp.n_paths = (uint64_t) (k + K) * lp.batch_paths;
-    if (r.multi) {                 // the endpoints moved since the sequence was opened: per-path tables from now on (general kernels)
-        lp.multi = 1u;
-        lp.lean = 0u;
-        scene->last_variant &= (uint32_t) (BF_VARIANT_FAST | BF_VARIANT_MOMENT);
-    }
-    lp.roll_newest = newest;
-    lp.roll_lo = newest + 1u > r.window ? newest + 1u - r.window : 0u;
-    lp.n_chan_all = (lp.roll_newest - lp.roll_lo + 1u) * lp.n_chan;
-    lp.base_off = lp.lds_hist ? r.window * lp.n_chan : 0u;        // fixed for the sequence: behind the full window
-    lp.lds_floats = lp.base_off + ((r.shape.flags & BF_FLAG_MOMENT) ? bfd::kRollBaseChMoment : bfd::kRollBaseCh) * bfd::kRollBase;
-    WfCtx c;
-    if (with_offsets) {
-        for (uint32_t j = 0; j < K; ++j)
-            for (int a = 0; a < 3; ++a) {
-                const float q = batch->mesh_offsets[3 * j + a];
-                if (!std::isfinite(q)) return fail(BF_ERR_INVALID, "bf_render_batch: non-finite mesh offset of render %u", j);
-                r.dmax = std::max(r.dmax, std::fabs(q));
-            }
-        // bf_device_core.h: Shift — slack for the largest offset of the sequence so far (older paths just get wider boxes)
-        lp.box_slack = 1e-6f * (scene->mesh.origin_scale_built + 2.f * r.dmax);
-    }
-    if ((st = wf_setup(scene, kernels_for(r.shape.flags), lp, (uint64_t) K * lp.batch_paths, nullptr, nullptr, stream, r.count_nodes, r.timed, c, true)) != BF_OK) return st;
-    lp.roll = scene->roll_ring;           // wf_setup may have (re)allocated the pool and the ring with it
-    lp.batch_offsets = with_offsets ? scene->roll_offsets : nullptr;
-    scene->wf.offsets = lp.batch_offsets;
-    {
-        // the slots due for this call's paths: global paths [k P, (k + K) P) live in slots g mod n_main
-        const uint32_t n_main = scene->wf.n_main, lo = (uint32_t) (((uint64_t) k * lp.batch_paths) % n_main);
-        scene->wf.wake_b0 = lo / 64u;
-        scene->wf.wake_nb = (uint32_t) std::min<uint64_t>(n_main / 64u, ((uint64_t) (lo % 64u) + (uint64_t) K * lp.batch_paths + 63u) / 64u);
-    }
-    if (fresh_pool) HIP_TRY(hipMemsetAsync(scene->wf.surv_cursor, 0, 2 * sizeof(uint32_t), stream));
-    const uint32_t n_chan1 = lp.n_chan;
-    if (records_dev) lp.has_records = 1u;
-    for (uint32_t j = 0; j < K; ++j) {
-        bfd::DRoll d;
-        d.seed = (batch && batch->seeds) ? batch->seeds[j] : launch->seed;
-        d.path_offset = launch->path_offset;
-        d.hist = hist_dev + (size_t) j * n_chan1;
-        d.records = records_dev ? records_dev + (size_t) j * lp.batch_paths : nullptr;
-        d.rects = scene->d.rects;                 // the endpoint tables as they stand for THIS render (kMulti kernels)
-        d.shapes = scene->d.shapes;
-        d.emitters = scene->d.emitters;
-        d.materials = scene->d.materials;
-        d.sensor = scene->d.sensor;
-        d.c = scene->d.c;
-        d.lambda_min = scene->d.lambda_min;
-        d.lambda_max = scene->d.lambda_max;
-        d.pad = 0u;
-        HIP_TRY(bfk_roll_set(scene->roll_ring, scene->roll_offsets, (k + j) & (bfd::kRollRing - 1u), &d,
-                             with_offsets ? batch->mesh_offsets + 3 * j : nullptr, stream));
-    }
-    // ---- how many bounce iterations this call enqueues ------------------------------------------------
-    // A launch that finds fewer live slots than fill the chip a few times over runs at its latency floor whatever it
-    // holds, so a call stops iterating once that few are left (roll_live, 1.5 x 2^20 by default: tools/r03_probe9.sh) and leaves them to the next
-    // call's launches: too few iterations and too many paths have to move to the survivor area, too many and the late ones
-    // run over a nearly empty pool.  Steered by the live counts that come back (without ever waiting for them).
-    const bool fb_ready = scene->wf_fb_pending && hipEventQuery(scene->wf_fb_event) == hipSuccess;
-    (void) hipGetLastError();
-    if (fb_ready) {
-        scene->wf_fb_pending = false;
-        const uint32_t n = r.fb_call_iters;
-        if (n && !r.fb_is_flush && !scene->tun.roll_iters) {
-            const uint32_t *nl = scene->wf_feedback;
-            uint32_t k = 0;
-            // round 4: with the shading launches' fixed costs gone (the statistics atomics) a launch over a FULL pool is what
-            // pays: a call of a big render stops after its first iteration as long as at most a quarter of the main slots
-            // is alive (C2 / C5: one iteration per call instead of three: wf_trace 3.80 -> 3.27 ms per step, profiles/
-            // r04_roll_iterations.txt); what is still alive two calls later moves to the survivor area as before
-            const uint32_t live_max = scene->tun.roll_live ? scene->tun.roll_live : std::max<uint32_t>(3u << 19, scene->wf.n_main / 4u);
-            while (k < n && nl[k] > live_max) ++k;
-            r.iters = std::min<uint32_t>(k < n ? k + 1u : n + 1u, 16u);
-        }
-        r.fb_call_iters = 0;
-    }
-    if (scene->tun.roll_iters) r.iters = scene->tun.roll_iters;
-    if (r.iters == 0) r.iters = 2;
-    if (r.it + 2u * 64u > bfd::kWfMaxIter) r.it &= 1u;       // the live-counter ring: keep the parity, restart the index
-    const uint32_t it0 = r.it, I = r.iters;
-    HIP_TRY(hipMemsetAsync(scene->wf.n_live + it0, 0, I * sizeof(uint32_t), stream));
-    for (uint32_t j = 0; j < I; ++j) {
-        const uint32_t it = r.it;
-        if ((st = wf_iteration(c, it, j == 0 ? (opening ? 1 : 2) : 0)) != BF_OK) return st;
-        if ((st = wf_trace_launch(c, it)) != BF_OK) return st;
-        ++r.it;
-    }
-    scene->wf_iters += I;
-    scene->wf_trace_launches += I;
-    if (!scene->wf_fb_pending) {
-        HIP_TRY(hipMemcpyAsync(scene->wf_feedback, scene->wf.n_live + it0, I * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(scene->wf_fb_event, stream));
-        scene->wf_fb_pending = true;
-        r.fb_call_iters = I;
-        r.fb_is_flush = false;
-    }
-    if (!r.open) scene->peers_rolling->fetch_add(1, std::memory_order_relaxed);
-    r.open = true;
-    r.count += K;
-    return BF_OK;
-}
-
-// Finish every path of the open sequence: bounce iterations until few slots are alive, then ONE tail launch.  The first
-// flush of a sequence shape runs synchronously (the host reads the live count per iteration, as the first render of a
-// shape does) and learns how many iterations that takes; later ones enqueue that many without a host round trip — the
-// tail finishes whatever is alive, the estimate only sizes its grid.
-static bf_status wf_roll_flush(const bf_scene *scene, hipStream_t stream, bool sync_timing) {
-    bf_scene::Roll &r = scene->roll;
-    if (!r.open) return BF_OK;
-    bf_status st;
-    if (stream != r.stream) {
-        HIP_TRY(hipEventRecord(scene->wf_event, r.stream));
-        HIP_TRY(hipStreamWaitEvent(stream, scene->wf_event, 0));
-    }
-    bfd::DLaunch &lp = r.lp;
-    WfCtx c;
-    if ((st = wf_setup(scene, kernels_for(r.shape.flags), lp, (uint64_t) r.per_call * lp.batch_paths, nullptr, nullptr, stream, r.count_nodes, r.timed, c, true)) != BF_OK) return st;
-    bfd::WF &wf = scene->wf;
-    volatile uint32_t *hq = scene->wf_host;
-    const bool fb_ready = scene->wf_fb_pending && hipEventQuery(scene->wf_fb_event) == hipSuccess;
-    (void) hipGetLastError();
-    if (fb_ready) {
-        scene->wf_fb_pending = false;
-        if (r.fb_is_flush && r.fb_call_iters) {
-            // live counts of the last planned flush: first iteration after which the tail threshold was met
-            const uint32_t *nl = scene->wf_feedback, n = r.fb_call_iters;
-            uint32_t k = 0;
-            while (k < n && nl[k] > c.tail_max) ++k;
-            if (k < n) {
-                r.flush_iters = k + 1;
-                r.flush_live = nl[k];
-            } else {
-                r.flush_iters = std::min<uint32_t>(n + 2, 48u);
-                r.flush_live = nl[n - 1];
-            }
-        }
-        r.fb_call_iters = 0;
-    }
-    if (r.it + 2u * 64u > bfd::kWfMaxIter) r.it &= 1u;
-    const uint32_t it0 = r.it;
-    HIP_TRY(hipMemsetAsync(wf.n_live + it0, 0, 64 * sizeof(uint32_t), stream));
-    uint32_t done_iters = 0;
-    if (scene->tun.allow_plan && r.flush_iters > 0) {
-        for (uint32_t j = 0; j < r.flush_iters; ++j) {
-            if ((st = wf_iteration(c, r.it, 0)) != BF_OK) return st;
-            if ((st = wf_trace_launch(c, r.it)) != BF_OK) return st;
-            ++r.it;
-            ++done_iters;
-        }
-        const uint32_t est = std::max<uint32_t>(r.flush_live + r.flush_live / 4, 64u * bfd::kBlock);
-        if ((st = wf_tail_launch(c, r.it, est, true)) != BF_OK) return st;
-        if (!scene->wf_fb_pending && done_iters) {
-            HIP_TRY(hipMemcpyAsync(scene->wf_feedback, wf.n_live + it0, done_iters * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipEventRecord(scene->wf_fb_event, stream));
-            scene->wf_fb_pending = true;
-            r.fb_call_iters = done_iters;
-            r.fb_is_flush = true;
-        }
-    } else {
-        uint32_t n_live = 0;
-        for (uint32_t j = 0; j < 48u; ++j) {
-            if ((st = wf_iteration(c, r.it, 0)) != BF_OK) return st;
-            HIP_TRY(hipMemcpyAsync((void *) &hq[0], wf.n_live + r.it, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipEventRecord(scene->wf_event, stream));
-            if ((st = wf_trace_launch(c, r.it)) != BF_OK) return st;
-            HIP_TRY(hipEventSynchronize(scene->wf_event));
-            ++r.it;
-            ++done_iters;
-            n_live = hq[0];
-            if (n_live <= c.tail_max) break;
-        }
-        r.flush_iters = done_iters;
-        r.flush_live = n_live;
-        if (n_live) {
-            if ((st = wf_tail_launch(c, r.it, n_live, true)) != BF_OK) return st;
-        }
-    }
-    scene->wf_iters += done_iters;
-    scene->wf_trace_launches += done_iters;
-    r.open = false;
-    scene->peers_rolling->fetch_sub(1, std::memory_order_relaxed);
-    r.multi = false;
-    lp.multi = 0u;
-    if (scene->tables_in_pool) {
-        // the sequence's last table version becomes the handle's tables again (home buffers), behind the flush's kernels.
-        // The block is found from the sensor record, the one table every update repoints (d.rects stays at the home
-        // buffer of a scene without rectangles).  The handle's state is back home before any copy can fail.
-        const bf_scene::TabLayout &t = scene->tab;
-        const char *blk = (const char *) scene->d.sensor - t.o_sensor;
-        bfd::DScene &d = const_cast<bf_scene *>(scene)->d;
-        d.rects = scene->home_rects;
-        d.shapes = scene->home_shapes;
-        d.emitters = scene->home_emitters;
-        d.materials = scene->home_materials;
-        d.sensor = scene->home_sensor;
-        scene->tables_in_pool = false;
-        scene->tab_next = 0;
-        const uint32_t nr = scene->d.n_rects, ne = scene->d.n_emitters, ns = scene->info.n_shapes, nm = scene->n_materials;
-        if (nr) HIP_TRY(hipMemcpyAsync((void *) scene->home_rects, blk + t.o_rects, nr * sizeof(bfd::DRect), hipMemcpyDeviceToDevice, stream));
-        if (ns) HIP_TRY(hipMemcpyAsync((void *) scene->home_shapes, blk + t.o_shapes, ns * sizeof(bfd::DShape), hipMemcpyDeviceToDevice, stream));
-        if (ne) HIP_TRY(hipMemcpyAsync((void *) scene->home_emitters, blk + t.o_emit, ne * sizeof(bfd::DEmitter), hipMemcpyDeviceToDevice, stream));
-        if (nm) HIP_TRY(hipMemcpyAsync((void *) scene->home_materials, blk + t.o_mat, nm * sizeof(bfd::DMaterial), hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync((void *) scene->home_sensor, blk + t.o_sensor, sizeof(bfd::DSensor), hipMemcpyDeviceToDevice, stream));
-    }
-    if (sync_timing) return wf_collect_timing(scene, stream);
-    return BF_OK;
-}
-
-// counters -> bf_stats (+ the per-kernel times of the last timed render / sequence)
-static void fill_stats(const bf_scene *scene, const unsigned long long *c, uint64_t n_paths, bf_stats *st) {
-    std::memset(st, 0, sizeof(*st));
-    st->n_paths = n_paths;
-    st->n_rays_closest = c[bfd::CTR_CLOSEST];
-    st->n_rays_shadow = c[bfd::CTR_SHADOW];
-    st->n_nodes_visited = c[bfd::CTR_NODES];
-    st->n_nodes_lds = c[bfd::CTR_NODES_LDS];
-    st->n_tris_tested = c[bfd::CTR_TRIS];
-    st->n_invalid = c[bfd::CTR_INVALID];
-    st->n_bounces = c[bfd::CTR_BOUNCES];
-    st->n_rays_tail = c[bfd::CTR_TAIL_RAYS];
-    st->n_rays_traced = c[bfd::CTR_TRACED];
-    st->n_nodes_tail = c[bfd::CTR_TAIL_NODES];
-    st->n_wnodes_tail = c[bfd::CTR_TAIL_WNODES];
-    st->n_tris_tail = c[bfd::CTR_TAIL_TRIS];
-    st->n_bounces_tail = c[bfd::CTR_TAIL_BOUNCES];
-    st->n_shade_loads = c[bfd::CTR_SHADE_LOADS];
-    st->n_shade_stores = c[bfd::CTR_SHADE_STORES];
-    st->n_shade_shadow = c[bfd::CTR_SHADE_SHADOW];
-    st->n_shade_rays = c[bfd::CTR_SHADE_RAYS];
-    st->n_guard = c[bfd::CTR_GUARD];
-    st->trace_ms = scene->wf_ms[0];
-    st->shade_ms = scene->wf_ms[1];
-    st->tail_ms = scene->wf_ms[2];
-    st->n_launches_trace = scene->wf_trace_launches;
-    st->n_bounce_iters = scene->wf_iters;
-    st->n_launches_tail = scene->wf_tail_launches;
-    st->n_launches_shade = scene->wf_shade_launches;
-    st->kernel_variant = scene->last_variant;
-}
-
-// Stream order between the successive uses of a handle's pool: work enqueued on another stream than the previous
-// call's waits for it (an event wait on the device, never on the host).
-bf_status order_after_last(const bf_scene *scene, hipStream_t stream) {
-    if (scene->has_last && scene->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, scene->last_done, 0));
-    return BF_OK;
-}
-bf_status mark_last(const bf_scene *scene, hipStream_t stream) {
-    if (!scene->last_done) HIP_TRY(hipEventCreateWithFlags(&scene->last_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(scene->last_done, stream));
-    scene->last_stream = stream;
-    scene->has_last = true;
-    return BF_OK;
-}
-// anything but another render of the open rolling sequence needs the pool (or the scene tables) to itself
-bf_status close_sequence(const bf_scene *scene, hipStream_t stream) {
-    if (!scene->roll.open) return BF_OK;
-    bf_status st = wf_roll_flush(scene, stream, false);
-    if (st != BF_OK) return st;
-    return mark_last(scene, stream);
-}
-
-// The lean profile (bf_device.h: kLean): what the scene and the launch must look like for the kernels that have everything else
-// compiled out.  Every radar scene of the reference's scripts and every BASELINE config fits; anything else runs the
-// general kernels (same results: tests/test_gpu_parity.py::test_lean_and_general_kernels_agree).
-static bool lean_profile(const bf_scene *scene, const bf_launch *launch, bool receive_mode, bool multi_pixel) {
-    // lean builds exist of the default register budgets only (three waves per SIMD), and not of the one-kernel variant
-    if ((launch->flags & BF_FLAG_MEGAKERNEL) || scene->tun.shade_waves != 3 || scene->tun.tail_waves != 3) return false;
-    if (!scene->tun.lean || scene->d.n_emitters != 1 || scene->d.uvs != nullptr || scene->sensor_host.filt_n != 0u) return false;
-    if (scene->sensor_host.win_off_t || scene->sensor_host.win_off_f) return false;      // ADC window away from the origin
-    if (scene->sensor_host.crop_x || scene->sensor_host.crop_y) return false;            // film crop window away from the origin
-    if (scene->any_back_material) return false;                                            // twosided with two nested BSDFs
-    if (scene->any_resample) return false;                                                 // resample_freq transmitters
-    const uint32_t et = scene->emitter_types[0];
-    if (receive_mode)
-        return (et == BF_TRANSMITTER_AREA || et == BF_TRANSMITTER_WIGNER) && scene->sensor_host.type == BF_RECEIVER_OMNI &&
-               launch->phase_bins == 0 && !(launch->flags & (BF_FLAG_DOPPLER | BF_FLAG_MIX_RESAMPLE));
-    return et == BF_EMITTER_AREA && scene->sensor_host.type == BF_SENSOR_PERSPECTIVE && !multi_pixel && launch->mode != BF_MODE_TIME;
-}
-
-// A render or batch on a handle its caller holds (BF_ENTER).  geom_stride != 0: the batch's renders read per-render geometry
-// versions, geom_stride float4 rows apart from the arrays scene->d points at (bf_mesh.cpp: render_versions; kGeom kernels).
-bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
-                        bf_path_record *records_dev, void *stream_, bf_stats *stats_out, uint32_t geom_stride) {
-    const uint32_t n_renders = batch ? batch->n_renders : 1u;
-    {
-        // a device-form vertex update whose gather refused triangles (bf_scene_update_vertices_device) is reported by the handle's
-        // next render, once: the render waits for that gather's count (one event, a few bytes) before it enqueues anything
-        bf_status dst = deform_report(scene, true);
-        if (dst != BF_OK) return dst;
-    }
-    if (batch) {
-        if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
-        if (launch->spp && launch->film_width && launch->film_height)
-            return fail(BF_ERR_UNSUPPORTED, "bf_render_batch: multi-pixel films are rendered one launch at a time");
-        if ((uint64_t) n_renders * bf_launch_channels(launch) > (1ull << 31) || (uint64_t) n_renders * launch->n_paths >= (1ull << 48))
-            return fail(BF_ERR_UNSUPPORTED, "bf_render_batch: %u renders x %llu paths is too large", n_renders, (unsigned long long) launch->n_paths);
-    }
-    const bool is_rx = scene->sensor_host.type == BF_RECEIVER_OMNI || scene->sensor_host.type == BF_RECEIVER_WIGNER ||
-                       scene->sensor_host.type == BF_RECEIVER_PHASED;
-    const bool receive_mode = launch->mode == BF_MODE_RECEIVE_RAW || launch->mode == BF_MODE_RECEIVE_IQ;
-    if (receive_mode) {
-        if (!is_rx) return fail(BF_ERR_INVALID, "receive mode needs a receiver (omnidirectional / wigner)");
-        if (launch->bins != scene->adc_t || launch->bins_y != scene->adc_f)
-            return fail(BF_ERR_INVALID, "receive mode: launch bins (%u x %u) must equal the ADC size — its window, if it has one — (%u x %u)",
-                        launch->bins, launch->bins_y, scene->adc_t, scene->adc_f);
-        for (uint32_t i = 0; i < scene->d.n_emitters; ++i)
-            if (scene->emitter_types[i] != BF_TRANSMITTER_AREA && scene->emitter_types[i] != BF_TRANSMITTER_WIGNER &&
-                scene->emitter_types[i] != BF_TRANSMITTER_PHASED)
-                return fail(BF_ERR_INVALID, "receive mode: emitter %u is not a transmitter", i);
-        // the Wigner and phased receivers sample their own local-oscillator signal under "mix_resample" (wignerreceiver.cpp:72-110,
-        // 172-189): a delta signal's instantaneous frequency at the receive time (sample_delta_frequency :149-166: a chirp's or a
-        // carrier's; "pulse" leaves it uninitialised there: refused), or a uniform frequency weighted with eval_signal
-        if ((launch->flags & BF_FLAG_MIX_RESAMPLE) && scene->sensor_host.type != BF_RECEIVER_OMNI) {
-            if (scene->sensor_host.rx_sig_is_delta && scene->sensor_host.rx_signal == BF_SIGNAL_PULSE)
-                return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_MIX_RESAMPLE on the Wigner / phased receiver: a \"pulse\" local oscillator that is a delta "
-                                                "signal reads an uninitialised frequency in the reference (wignerreceiver.cpp:149-166)");
-            if (scene->sensor_host.rx_signal != BF_SIGNAL_CW && !(scene->sensor_host.rx_pulse_len > 0.f && scene->sensor_host.rx_prf > 0.f))
-                return fail(BF_ERR_INVALID, "BF_FLAG_MIX_RESAMPLE: the receiver's chirp / pulse needs rx_pulse_len > 0 and rx_prf > 0");
-        }
-    } else {
-        if (launch->flags & BF_FLAG_MIX_RESAMPLE) return fail(BF_ERR_INVALID, "BF_FLAG_MIX_RESAMPLE is a receive-mode flag");
-        if (is_rx) return fail(BF_ERR_INVALID, "render modes need a sensor (fluxmeter / perspective), not a receiver");
-        for (uint32_t i = 0; i < scene->d.n_emitters; ++i)
-            if (scene->emitter_types[i] != BF_EMITTER_SPOT && scene->emitter_types[i] != BF_EMITTER_AREA &&
-                scene->emitter_types[i] != BF_EMITTER_POINT)
-                return fail(BF_ERR_INVALID, "render modes: emitter %u is a transmitter (use receive mode)", i);
-    }
-    if (launch->mode > BF_MODE_RECEIVE_IQ) return fail(BF_ERR_INVALID, "unknown mode %u", launch->mode);
-    if (launch->mode != BF_MODE_RECEIVE_RAW && launch->phase_bins)
-        return fail(BF_ERR_INVALID, "phase_bins needs receive mode (PhaseIntegrator wraps pathtimefrequency)");
-    if (launch->phase_bins > 4096) return fail(BF_ERR_INVALID, "phase_bins %u out of range", launch->phase_bins);
-    if ((launch->mode == BF_MODE_RANGE || launch->mode == BF_MODE_TIME) && (launch->bins == 0 || !(launch->bin_width > 0.f)))
-        return fail(BF_ERR_INVALID, "range/time mode needs bins > 0 and bin_width > 0");
-    const bool multi_pixel = launch->spp && launch->film_width && launch->film_height;
-    if (multi_pixel ? (launch->film_width != scene->film_w || launch->film_height != scene->film_h)
-                    : (scene->film_w != 1 || scene->film_h != 1) && !is_rx)
-        return fail(BF_ERR_INVALID, "the sensor's film is %u x %u: the launch must name the same film and spp > 0 (it has %u x %u, spp %u)",
-                    scene->film_w, scene->film_h, launch->film_width, launch->film_height, launch->spp);
-    if (multi_pixel) {
-        if (launch->mode == BF_MODE_RECEIVE_RAW || launch->mode == BF_MODE_RECEIVE_IQ)
-            return fail(BF_ERR_INVALID, "receive modes bin into the ADC: film_width / film_height / spp must be 0");
-        const uint64_t px = (uint64_t) launch->film_width * launch->film_height;
-        if (px > (1u << 24) || px * (5ull + 3ull * launch->bins) > (1ull << 31))
-            return fail(BF_ERR_UNSUPPORTED, "film %u x %u with %u bins is too large", launch->film_width, launch->film_height, launch->bins);
-        if (launch->path_offset + launch->n_paths > px * launch->spp)
-            return fail(BF_ERR_INVALID, "path_offset + n_paths = %llu exceeds film_width * film_height * spp = %llu",
-                        (unsigned long long) (launch->path_offset + launch->n_paths), (unsigned long long) (px * launch->spp));
-    }
-    if ((launch->flags & BF_FLAG_MOMENT) && (launch->flags & BF_FLAG_FAST))
-        return fail(BF_ERR_INVALID, "BF_FLAG_MOMENT | BF_FLAG_FAST: the fast-arithmetic tolerance contract says nothing about squared "
-                                    "samples; render second moments with the exact kernels");
-    if (multi_pixel && (launch->flags & BF_FLAG_MOMENT) && (uint64_t) launch->film_width * launch->film_height * (11ull + 6ull * launch->bins) > (1ull << 31))
-        return fail(BF_ERR_UNSUPPORTED, "film %u x %u with %u bins and BF_FLAG_MOMENT is too large", launch->film_width, launch->film_height, launch->bins);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const bool rolling = (launch->flags & BF_FLAG_ROLLING) != 0u && launch->n_paths != 0u &&
-                         (uint64_t) n_renders * launch->n_paths <= scene->tun.pool && n_renders <= bfd::kRollRing;
-    if (launch->flags & BF_FLAG_ROLLING) {
-        // one sequence, one arithmetic: its long paths are finished by the kernels of the mode it was opened with
-        if (scene->roll.open && ((launch->flags ^ scene->roll.shape.flags) & BF_FLAG_FAST))
-            return fail(BF_ERR_INVALID, "BF_FLAG_ROLLING: the open rolling sequence of this handle was started %s BF_FLAG_FAST; "
-                                        "flush it (bf_scene_flush) before rolling renders of the other mode",
-                        (scene->roll.shape.flags & BF_FLAG_FAST) ? "with" : "without");
-        // ... and one channel layout: its histograms' base-channel table has five or eleven entries per render
-        if (scene->roll.open && ((launch->flags ^ scene->roll.shape.flags) & BF_FLAG_MOMENT))
-            return fail(BF_ERR_INVALID, "BF_FLAG_ROLLING: the open rolling sequence of this handle was started %s BF_FLAG_MOMENT; "
-                                        "flush it (bf_scene_flush) before rolling renders of the other layout",
-                        (scene->roll.shape.flags & BF_FLAG_MOMENT) ? "with" : "without");
-        if (multi_pixel || (launch->flags & BF_FLAG_MEGAKERNEL))
-            return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_ROLLING: multi-pixel films and the one-kernel variant do not roll");
-        if (stats_out)
-            return fail(BF_ERR_INVALID, "BF_FLAG_ROLLING: a rolling render returns before its paths have ended, so it has no statistics "
-                                        "of its own (pass stats_out = NULL; bf_scene_flush reports the sequence's)");
-    }
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost != BF_OK) return ost;
-        if (!rolling && (ost = close_sequence(scene, stream)) != BF_OK) return ost;
-    }
-    bfd::DLaunch lp;
-    std::memset(&lp, 0, sizeof(lp));
-    lp.film_w = multi_pixel ? launch->film_width : 1u;
-    lp.film_h = multi_pixel ? launch->film_height : 1u;
-    lp.spp = multi_pixel ? launch->spp : 0u;
-    lp.mode = launch->mode;
-    lp.color_mode = launch->color_mode;
-    lp.n_paths = launch->n_paths;
-    lp.path_offset = launch->path_offset;
-    lp.seed = launch->seed;
-    lp.max_depth = launch->max_depth;
-    lp.rr_depth = launch->rr_depth;
-    lp.bins = launch->bins;
-    lp.bins_y = launch->bins_y;
-    lp.phase_bins = launch->mode == BF_MODE_RECEIVE_RAW ? launch->phase_bins : 0u;
-    lp.iq = launch->mode == BF_MODE_RECEIVE_IQ ? 1u : 0u;
-    if (lp.iq) lp.mode = BF_MODE_RECEIVE_RAW;          // the kernels see receive mode + the iq flag
-    lp.bin_width = launch->bin_width;
-    lp.time_c = launch->time_c;
-    lp.n_chan = bf_launch_channels(launch);
-    lp.chan_px = lp.n_chan / (lp.film_w * lp.film_h);
-    lp.lean = lean_profile(scene, launch, receive_mode, multi_pixel) ? 1u : 0u;
-    lp.wide = scene->sensor_host.filt_n != 0u ? 1u : 0u;
-    scene->last_variant = (lp.lean ? (uint32_t) BF_VARIANT_LEAN : 0u) | (lp.wide ? (uint32_t) BF_VARIANT_WIDE : 0u);      // reconstruction filter wider than a pixel: the kernels' kWide variants
-    if (launch->flags & BF_FLAG_FAST) scene->last_variant |= (uint32_t) BF_VARIANT_FAST;
-    if (launch->flags & BF_FLAG_MOMENT) scene->last_variant |= (uint32_t) BF_VARIANT_MOMENT;
-    const Kernels &kern = kernels_for(launch->flags);
-    lp.count = ((launch->flags & (BF_FLAG_STATS | BF_FLAG_COUNT)) || stats_out) ? 1u : 0u;
-    lp.doppler = (receive_mode && (launch->flags & BF_FLAG_DOPPLER)) ? 1u : 0u;
-    lp.resample = (receive_mode && scene->any_resample) ? 1u : 0u;
-    if (lp.resample && lp.doppler)
-        return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_DOPPLER with a resample_freq transmitter: both rewrite the path's wavelength (one slot of path state)");
-    lp.mix = (receive_mode && (launch->flags & BF_FLAG_MIX_RESAMPLE)) ? 1u : 0u;
-    lp.n_chan_all = lp.n_chan * n_renders;
-    lp.geom_stride = geom_stride;
-    lp.lds_hist = (lp.n_chan_all <= (uint32_t) bfd::kMaxLdsHist && !(launch->flags & BF_FLAG_GLOBAL_ATOMICS)) ? 1u : 0u;
-    lp.lds_floats = lp.lds_hist ? lp.n_chan_all : 0u;
-    size_t lds = sizeof(int) * bfd::kStackDepth * bfd::kBlock + (lp.lds_hist ? sizeof(float) * lp.n_chan_all : 0);
-    lds = ((lds + 15) & ~size_t(15)) + (scene->d.tab_cache ? bfd::kTabBytes : 0u);      // stacks | histogram | tables (bf_device_core.h: load_tables_lds)
-    if (batch && !rolling) {
-        // one launch sequence over n_renders * n_paths global path indices (DLaunch::batch); the per-render seeds and
-        // mesh offsets travel through the scene's pinned staging ring, so the caller's arrays are free on return
-        lp.batch = n_renders;
-        lp.batch_paths = launch->n_paths;
-        lp.n_paths = launch->n_paths * n_renders;
-        // the offsets are read as float4 on both sides: keep them 16-byte aligned behind the seeds
-        const size_t seed_bytes = batch->seeds ? ((sizeof(uint64_t) * n_renders + 15) & ~size_t(15)) : 0;
-        const size_t off_bytes = batch->mesh_offsets ? sizeof(float4) * n_renders : 0;
-        if (seed_bytes + off_bytes) {
-            bf_scene::Stage *stg = nullptr;
-            bf_status sst = stage_acquire(scene, seed_bytes + off_bytes, &stg);
-            if (sst != BF_OK) return sst;
-            if (seed_bytes) {
-                std::memcpy(stg->host, batch->seeds, sizeof(uint64_t) * n_renders);
-                lp.batch_seeds = (const uint64_t *) stg->dev;
-            }
-            if (off_bytes) {
-                float4 *o = (float4 *) ((char *) stg->host + seed_bytes);
-                float dmax = 0.f;
-                for (uint32_t k = 0; k < n_renders; ++k) {
-                    const float *q = batch->mesh_offsets + 3 * k;
-                    if (!(std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2])))
-                        return fail(BF_ERR_INVALID, "bf_render_batch: non-finite mesh offset of render %u", k);
-                    o[k] = make_float4(q[0], q[1], q[2], 0.f);
-                    dmax = std::max({dmax, std::fabs(q[0]), std::fabs(q[1]), std::fabs(q[2])});
-                }
-                if (scene->d.n_tris) {
-                    lp.batch_offsets = (const float4 *) ((char *) stg->dev + seed_bytes);
-                    // bf_device_core.h: Shift — the roundings of o - d and p + d move a box plane by at most
-                    // 1.8e-7 (S + 2 |d|), S = the bound the boxes were padded for
-                    lp.box_slack = 1e-6f * (scene->mesh.origin_scale_built + 2.f * dmax);
-                }
-            }
-            sst = stage_commit(stg, seed_bytes + off_bytes, stream);
-            if (sst != BF_OK) return sst;
-        }
-    }
-
-    // persistent grid: enough workgroups to fill the chip, never more than the work
-    uint64_t want = (lp.n_paths + bfd::kBlock - 1) / bfd::kBlock;
-    unsigned blocks_per_cu = (unsigned) std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
-    unsigned grid = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t) scene->n_cus * blocks_per_cu));
-
-    if (rolling) {
-        // more paths than the pool has slots would need several paths per slot and render: not a rolling shape (above)
-        bf_status rst = wf_roll_render(scene, launch, batch, lp, hist_dev, records_dev, stream);
-        if (rst != BF_OK) return rst;
-        return mark_last(scene, stream);
-    }
-    // every counter but the sticky guard word (the last one)
-    HIP_TRY(hipMemsetAsync(scene->counters, 0, sizeof(unsigned long long) * bfd::CTR_GUARD, stream));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (stats_out) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        HIP_TRY(hipEventRecord(ev0, stream));
-    }
-    if (launch->n_paths) {
-        if (launch->flags & BF_FLAG_MEGAKERNEL) {
-            HIP_TRY(kern.render(&scene->d, &lp, hist_dev, records_dev, scene->counters,
-                                (launch->flags & BF_FLAG_STATS) ? 1 : 0, grid, lds, stream));
-        } else {
-            bf_status wst = wf_render(scene, kern, lp, hist_dev, records_dev, stream, (launch->flags & BF_FLAG_STATS) != 0,
-                                      stats_out != nullptr);
-            if (wst != BF_OK) return wst;
-        }
-    }
-    if (stats_out) {
-        HIP_TRY(hipEventRecord(ev1, stream));
-        HIP_TRY(hipEventSynchronize(ev1));
-        unsigned long long c[bfd::CTR_COUNT];
-        HIP_TRY(hipMemcpy(c, scene->counters, sizeof(c), hipMemcpyDeviceToHost));
-        if ((launch->flags & BF_FLAG_MEGAKERNEL) || !launch->n_paths) {
-            scene->wf_ms[0] = scene->wf_ms[1] = scene->wf_ms[2] = 0.f;
-            scene->wf_trace_launches = scene->wf_iters = scene->wf_tail_launches = scene->wf_shade_launches = 0;
-        }
-        fill_stats(scene, c, lp.n_paths, stats_out);
-        float ms = 0.f;
-        hipError_t he = hipEventElapsedTime(&ms, ev0, ev1);
-        (void) hipEventDestroy(ev0);
-        (void) hipEventDestroy(ev1);
-        if (he != hipSuccess) return fail(BF_ERR_DEVICE, "hipEventElapsedTime: %s", hipGetErrorString(he));
-        stats_out->kernel_ms = ms;
-        if (c[bfd::CTR_GUARD] || c[bfd::CTR_SURV_GUARD]) {
-            // reported here: clear the sticky words and the copy of them that may be in flight to the next planned render
-            HIP_TRY(hipMemset(scene->counters + bfd::CTR_GUARD, 0, 2 * sizeof(unsigned long long)));
-            scene->wf_fb_pending = false;
-            return wf_guard_error(c[bfd::CTR_GUARD], c[bfd::CTR_SURV_GUARD]);
-        }
-        if (launch->n_paths && !(launch->flags & BF_FLAG_MEGAKERNEL)) {
-            bf_status fst = check_film_count(c, lp.n_paths);
-            if (fst != BF_OK) return fst;
-        }
-    }
-    return mark_last(scene, stream);
-}
-
-static bf_status render_common(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
-                               bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
-    if (!scene || !launch || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
-    BF_ENTER(scene);
-    return render_locked(scene, launch, batch, hist_dev, records_dev, stream_, stats_out);
-}
-
-bf_status bf_render_device(const bf_scene *scene, const bf_launch *launch, float *hist_dev, bf_path_record *records_dev,
-                           void *stream, bf_stats *stats_out) {
-    return render_common(scene, launch, nullptr, hist_dev, records_dev, stream, stats_out);
-}
-
-bf_status bf_render_batch_device(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
-                                 bf_path_record *records_dev, void *stream, bf_stats *stats_out) {
-    if (!batch) return fail(BF_ERR_INVALID, "bf_render_batch_device: null batch");
-    return render_common(scene, launch, batch, hist_dev, records_dev, stream, stats_out);
-}
-
-bf_status bf_scene_flush(bf_scene *scene, void *stream_, bf_stats *stats_out) {
-    if (!scene) return fail(BF_ERR_INVALID, "null argument");
-    BF_ENTER(scene);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const bool was_open = scene->roll.open;
-    const uint64_t n_paths = was_open ? scene->roll.lp.n_paths : 0;
-    bf_status st = order_after_last(scene, stream);
-    if (st != BF_OK) return st;
-    if (was_open) {
-        if ((st = wf_roll_flush(scene, stream, stats_out != nullptr)) != BF_OK) return st;
-        if ((st = mark_last(scene, stream)) != BF_OK) return st;
-    }
-    if (stats_out) {
-        std::memset(stats_out, 0, sizeof(*stats_out));
-        if (!was_open) return BF_OK;
-        HIP_TRY(hipStreamSynchronize(stream));
-        unsigned long long c[bfd::CTR_COUNT];
-        HIP_TRY(hipMemcpy(c, scene->counters, sizeof(c), hipMemcpyDeviceToHost));
-        fill_stats(scene, c, n_paths, stats_out);
-        stats_out->kernel_ms = scene->wf_ms[0] + scene->wf_ms[1] + scene->wf_ms[2];
-        if (c[bfd::CTR_GUARD] || c[bfd::CTR_SURV_GUARD]) {
-            HIP_TRY(hipMemset(scene->counters + bfd::CTR_GUARD, 0, 2 * sizeof(unsigned long long)));
-            scene->wf_fb_pending = false;
-            return wf_guard_error(c[bfd::CTR_GUARD], c[bfd::CTR_SURV_GUARD]);
-        }
-        return scene->roll.lp.count ? check_film_count(c, n_paths) : BF_OK;       // every path of every render of a COUNTED sequence
-    }
-    return BF_OK;
-}
-
-bf_status bf_scene_sync(bf_scene *scene) {
-    if (!scene) return fail(BF_ERR_INVALID, "null argument");
-    BF_ENTER(scene);
-    bf_status st = close_sequence(scene, scene->roll.stream);
-    if (st != BF_OK) return st;
-    if (scene->has_last) HIP_TRY(hipEventSynchronize(scene->last_done));
-    scene->wf_fb_pending = false;         // whatever feedback was in flight has landed; the next render re-learns from its own
-    scene->roll.fb_call_iters = 0;
-    unsigned long long lost = 0, refused = 0;
-    bf_status gst = read_guards(scene, &lost, &refused);
-    if (gst != BF_OK) return gst;
-    if (lost || refused) return wf_guard_error(lost, refused);
-    return deform_report(scene, true);
-}
-
-/* test hook (not part of the ABI): pre-load the sticky guard word, as if wf_trace had dropped `n` rays */
-bf_status bfdbg_preload_guard(bf_scene *scene, unsigned long long n) {
-    if (!scene) return fail(BF_ERR_INVALID, "null argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(scene->counters + bfd::CTR_GUARD, &n, sizeof(n), hipMemcpyHostToDevice));
-    return BF_OK;
-}
 
 /* developer probe (tools/fetch_probe.py): `reps` launches of the gather pattern `mode` over a table of 2^log2_rows 16-byte rows
    (a second buffer of the same size is streamed in between, so every launch starts with a cold L2); returns the mean ms */
@@ -2355,7 +1266,7 @@ bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, 
             BF_ENTER(scenes[g]);                 // (this handle's device; the counters are the handle's)
             hipError_t he = hipEventSynchronize(ev[2 * g + 1]);
             unsigned long long c[bfd::CTR_COUNT];
-            if (he == hipSuccess) he = hipMemcpy(c, scenes[g]->counters, sizeof(c), hipMemcpyDeviceToHost);
+            if (he == hipSuccess) he = hipMemcpy(c, scenes[g]->run.counters, sizeof(c), hipMemcpyDeviceToHost);
             float ms = 0.f;
             if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev[2 * g], ev[2 * g + 1]);
             if (he != hipSuccess) {
@@ -2377,15 +1288,14 @@ bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, 
             stats_out->kernel_variant = p.kernel_variant;
             // the devices run side by side: the slowest one's span (the per-kernel times need a synchronous render: 0 here)
             stats_out->kernel_ms = std::max(stats_out->kernel_ms, ms);
-            if (c[bfd::CTR_GUARD] || c[bfd::CTR_SURV_GUARD]) {
+            if (c[bfd::CTR_GUARD] || c[bfd::CTR_SURV_GUARD]) {      // cleared per handle, reported once for all of them below
                 lost += c[bfd::CTR_GUARD];
                 refused += c[bfd::CTR_SURV_GUARD];
-                (void) hipMemset(scenes[g]->counters + bfd::CTR_GUARD, 0, 2 * sizeof(unsigned long long));
-                scenes[g]->wf_fb_pending = false;
+                (void) report_guards(scenes[g], c[bfd::CTR_GUARD], c[bfd::CTR_SURV_GUARD]);
             }
         }
         drop_events();
-        if (rst == BF_OK && (lost || refused)) rst = wf_guard_error(lost, refused);
+        if (rst == BF_OK && (lost || refused)) rst = guard_error(lost, refused);
     }
     return rst;
 }
@@ -2468,7 +1378,9 @@ extern "C" {
 static bf_status render_host(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_out,
                              bf_path_record *records_out, bf_stats *stats_out) {
     return render_host_with(scene, launch, batch ? batch->n_renders : 1u, hist_out, records_out, stats_out,
-                            [&](float *h, bf_path_record *r, bf_stats *st) { return render_common(scene, launch, batch, h, r, nullptr, st); });
+                            [&](float *h, bf_path_record *r, bf_stats *st) {
+                                return batch ? bf_render_batch_device(scene, launch, batch, h, r, nullptr, st) : bf_render_device(scene, launch, h, r, nullptr, st);
+                            });
 }
 
 bf_status bf_render_motion_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_shapes,

@@ -1,4 +1,4 @@
-// Device-resident scene layout shared by the host API (bf_api) and the
+// Device-resident scene layout shared by the host API (bf_api, bf_render) and the
 // kernels (bf_kernels.hip).  Everything is read-only during a render.
 //
 // HBM layout (DESIGN.md "Data layout"):
@@ -78,7 +78,7 @@ struct DEmitter {
 // Kernel variant word V — the template parameter (`RX`) of the path logic and of the kernels built on it:
 //   bits 0-1  mode class: 0 render modes (path / range / time), 1 receive modes, 2 decided at run time (tail, one-kernel variant)
 //   kWide     the sensor's reconstruction filter is wider than a pixel (DLaunch::wide)
-//   kLean     scene and launch fit the LEAN PROFILE (DLaunch::lean, bf_api.cpp: lean_profile) — what every radar scene of the
+//   kLean     scene and launch fit the LEAN PROFILE (DLaunch::lean, bf_render.cpp: lean_profile) — what every radar scene of the
 //             reference's scripts and all BASELINE configs use: ONE emitter of an area type (area light, area / Wigner
 //             transmitter: no spot, point or phased-array source), no texture coordinates, a perspective camera (render
 //             modes) or the omnidirectional receiver (receive modes), the 1 x 1 film, no time-resolved mode, no phase bins, no
@@ -275,7 +275,7 @@ enum {
     // the STICKY words (never cleared by a render, reported once): keep them last
     CTR_GUARD,             // rays dropped by wf_trace's iteration guard (a bug if ever non-zero: bf_render reports BF_ERR_DEVICE)
     CTR_SURV_GUARD,        // survivor batches a launch of a rolling sequence tried to claim beyond the area's size (surv_take: the
-                           // claim is refused, so nothing is lost, and reported: the sizing rule of bf_api.cpp: wf_setup was violated)
+                           // claim is refused, so nothing is lost, and reported: the sizing rule of bf_render.cpp: wf_setup was violated)
     CTR_COUNT
 };
 

@@ -549,7 +549,7 @@ __global__ __launch_bounds__(kBlock) void bf_trace_kernel(DScene sc, uint64_t n,
 
 BF_NS_END  // namespace bfd
 
-// host-callable launchers (used by bf_api.cpp and bf_mesh.cpp, which are plain C++)
+// host-callable launchers (used by bf_api.cpp, bf_render.cpp and bf_mesh.cpp, which are plain C++)
 // moment: the kMoment variants (BF_FLAG_MOMENT; the *_moment launchers below)
 static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
                                 unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream,

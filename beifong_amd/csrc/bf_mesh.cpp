@@ -1039,10 +1039,10 @@ bf_status bfdbg_scene_read_tree(const bf_scene *scene, uint32_t which, int32_t v
     if (which != 4u && which != 16u && which != 64u) return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: which = %u (4, 16 or 64)", which);
     BF_ENTER(scene);
     {
-        bf_status cst = close_sequence(scene, scene->roll.stream);
+        bf_status cst = close_sequence(scene, scene->run.roll.stream);
         if (cst != BF_OK) return cst;
     }
-    if (scene->has_last) HIP_TRY(hipEventSynchronize(scene->last_done));
+    HIP_TRY(scene->run.last.wait());
     const bfd::DScene &d = scene->d;
     const MeshState &m = scene->mesh;
     if (which == 16u && !d.wnodes) return fail(BF_ERR_UNSUPPORTED, "bfdbg_scene_read_tree: the scene has no sixteen-wide tree");

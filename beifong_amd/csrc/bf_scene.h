@@ -1,4 +1,4 @@
-// What bf_api.cpp and bf_mesh.cpp share: the scene handle, its guards and the few functions of either file the other one calls.
+// What bf_api.cpp, bf_render.cpp and bf_mesh.cpp share: the scene handle, its guards and the few functions of each file the others call.
 // Internal to libbeifong_hip.so: the functions and guards declared here have hidden visibility (the C ABI is include/beifong_hip.h alone).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -145,54 +145,27 @@ struct __attribute__((visibility("hidden"))) MeshState {
     ~MeshState();
 };
 
-struct bf_scene {
-    bfd::DScene d;
-    bf_tunables tun;
-    std::shared_ptr<bf_geometry> geom;     // nodes / wnodes / tris / normals / uvs as created
-    // handles that render the SAME triangle / node arrays hold the same token (a clone that took its own snapshot of a
-    // translated scene does not): bf_scene_translate_meshes copies on write only while the token is shared
-    std::shared_ptr<char> geom_token;
-    // handles cloned from one another are meant to be in flight together (one per stream): how many of them have a rolling sequence
-    // open right now — small pools then launch a share of the persistent grids each (wf_setup: grid_share)
-    std::shared_ptr<std::atomic<int>> peers_rolling;
-    // one host thread at a time per handle (the handle owns the path pool its render's state lives in)
-    mutable std::atomic_flag busy = ATOMIC_FLAG_INIT;
-    // stream order between successive renders of the handle: a render on another stream than the previous one waits for it
-    mutable hipStream_t last_stream = nullptr;
-    mutable hipEvent_t last_done = nullptr;
-    mutable bool has_last = false;
-    std::vector<void *> owned;             // this handle's own allocations (small tables, spill columns, private geometry)
-    bf_scene_info info;
-    int device = 0;
-    int n_cus = 256;
-    std::vector<uint32_t> emitter_types;
-    // per-scene scratch for bf_render_device (counters), allocated once
-    unsigned long long *counters = nullptr;
-    // wavefront workspace, allocated on first use (mutable: lazily grown cache)
-    mutable bfd::WF wf;
-    mutable std::vector<void *> wf_owned;
-    uint32_t n_materials = 0;
-    bool any_back_material = false;        // some twosided material has a second nested BSDF (general kernels)
-    bool any_resample = false;             // some transmitter re-samples the path's wavelength (resample_freq: general kernels, DLaunch::resample)
-    bfd::DSensor sensor_host;              // host copy of the device sensor record
-    mutable uint32_t last_variant = 0;     // BF_VARIANT_* of the latest render (bf_stats.kernel_variant)
-    uint32_t film_w = 1, film_h = 1;       // the sensor's film (bf_sensor.film_width / film_height)
-    uint32_t adc_t = 0, adc_f = 0;         // what a receive-mode launch bins into: the ADC's window, or the whole ADC
-    MeshState mesh;                        // everything about moved meshes (bf_mesh.cpp)
-    // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
-    std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
-    std::vector<float *> array_dev;
-    std::vector<uint32_t> array_n;
-    float *sensor_array_dev = nullptr;
-    uint32_t sensor_array_n = 0;
-    mutable uint32_t *wf_host = nullptr;   // pinned read-back of queue counters
-    mutable hipEvent_t wf_event = nullptr;
-    mutable unsigned long long *wf_masks = nullptr;
-    mutable std::vector<hipEvent_t> wf_timing;   // event pool for per-kernel timing (stats only): pair k = events 2k, 2k + 1
-    mutable std::vector<int> wf_ev_kind;         // kind of every recorded pair: 0 trace, 1 shade, 2 tail
-    mutable float wf_ms[3] = {0, 0, 0};          // trace, shade, tail of the last stats render / rolling sequence
-    mutable uint32_t wf_iters = 0, wf_trace_launches = 0, wf_tail_launches = 0, wf_shade_launches = 0;
-    // Rolling sequence (bf_render_device with BF_FLAG_ROLLING, bf_scene_flush): see wf_roll_render
+// Everything a render of this handle leaves behind for the next one (bf_render.cpp): the path pool and its read-back buffers, the
+// launch statistics, the open rolling sequence, the learned launch plan, the live-count feedback, the endpoint-table versions and the
+// stream order between calls.  Each field's meaning is stated here alone.  Renders take const bf_scene *, hence the keyword on bf_scene::run.
+struct __attribute__((visibility("hidden"))) RenderState {
+    // ---- the path pool, allocated on first use and grown on demand (wf_ensure) ----
+    bfd::WF wf{};
+    std::vector<void *> pool;                   // every device allocation of the pool (masks, ring and offsets included)
+    unsigned long long *masks = nullptr;        // the batch masks wf.m_* point into
+    bfd::DRoll *roll_ring = nullptr;            // device [kRollRing]: the descriptors of a rolling sequence's renders
+    float4 *roll_offsets = nullptr;             // device [kRollRing]: mesh offset of every render of the sequence
+    unsigned long long *counters = nullptr;     // device CTR_* (bf_device.h), allocated with the handle; the last two are the sticky guard words
+    // pinned read-back: word [0] = n_live[it] of a synchronous drive loop, 64-bit words [1], [2] = the guard words a plan's feedback carries
+    uint32_t *host = nullptr;
+    hipEvent_t event = nullptr;                 // behind the copy into host[0]; also the cross-stream hand-over (hand_over)
+    // ---- launch statistics of the last stats render / rolling sequence (bf_stats) ----
+    std::vector<hipEvent_t> timing;             // event pool for per-kernel timing: pair k = events 2k, 2k + 1
+    std::vector<int> ev_kind;                   // kind of every recorded pair: 0 trace, 1 shade, 2 tail
+    float ms[3] = {0, 0, 0};                    // trace, shade, tail
+    uint32_t iters = 0, trace_launches = 0, tail_launches = 0, shade_launches = 0;
+    uint32_t last_variant = 0;                  // BF_VARIANT_* of the latest render (bf_stats.kernel_variant)
+    // ---- rolling sequence (bf_render_device with BF_FLAG_ROLLING, bf_scene_flush): see wf_roll_render ----
     struct Roll {
         bool open = false;
         uint32_t count = 0;                      // renders issued since the sequence was opened
@@ -209,37 +182,104 @@ struct bf_scene {
         uint32_t flush_iters = 0;                // planned bounce iterations of a flush before its tail (learned)
         uint32_t flush_live = 0;                 // slots alive at the flush's tail (learned: sizes its grid)
         bool multi = false;                      // the endpoints moved between the renders of the sequence (kMulti kernels from then on)
-        uint32_t fb_call_iters = 0;              // iterations of the call whose live counts are in flight to wf_feedback
-        bool fb_is_flush = false;
-    };
-    mutable Roll roll;
-    // Endpoint-table versions of an open rolling sequence: bf_scene_update_endpoints writes the new tables into the next block of
-    // a pool instead of flushing the sequence (the renders issued so far keep reading theirs through the descriptor ring:
-    // bf_device.h: DRoll, kMulti); the home buffers (as created) hold the tables whenever no sequence is open.
-    struct TabLayout {
-        size_t o_rects = 0, o_shapes = 0, o_emit = 0, o_mat = 0, o_sensor = 0, stride = 0;
-    };
-    mutable TabLayout tab;
-    mutable char *tab_pool = nullptr;            // device: kRollRing blocks of tab.stride bytes (allocated on first use)
-    mutable uint32_t tab_next = 0;               // next free block
-    mutable bool tables_in_pool = false;         // d.rects ... d.sensor point into the pool
-    const bfd::DRect *home_rects = nullptr;
-    const bfd::DShape *home_shapes = nullptr;
-    const bfd::DEmitter *home_emitters = nullptr;
-    const bfd::DMaterial *home_materials = nullptr;
-    const bfd::DSensor *home_sensor = nullptr;
-    mutable bfd::DRoll *roll_ring = nullptr;     // device [kRollRing]
-    mutable float4 *roll_offsets = nullptr;      // device [kRollRing]: mesh offset of every render of the sequence
-    // Launch plan learned from the previous render of the same shape (wf_render): how many bounce
-    // iterations precede the tail and how many slots are then alive.  With a plan the whole render is
-    // enqueued without a host round trip; the live counts come back through a pinned buffer afterwards.
-    struct WfPlan {
+    } roll;
+    // Launch plan learned from the previous render of the same shape (wf_render): how many bounce iterations precede the tail and
+    // how many slots are then alive.  With a plan the whole render is enqueued without a host round trip.
+    struct Plan {
         bool valid = false;
         uint64_t n_paths = 0;
         uint32_t mode = 0, max_depth = 0, n_slots = 0, tail_max = 0;
         uint32_t iters = 0, tail_live = 0;
-    };
-    mutable WfPlan wf_plan;
+    } plan;
+    // The live-count feedback channel: a planned drive loop never waits for n_live, it posts a copy of the counts behind an event
+    // and whoever drives the handle next takes them if they have landed (never waiting) and learns from them.  One copy is in
+    // flight at most: a post while one is pending is skipped.  `owner` says whose counts they are; it is written by post() and read
+    // by take() alone, that is only while `pending` is set, so nothing has to reset it when the counts are dropped.
+    struct Feedback {
+        enum Owner { kNone, kPlan, kRollCall, kRollFlush };      // wf_render's plan, a call of a rolling sequence, its flush
+        uint32_t *counts = nullptr;              // pinned [kWfMaxIter + 2]
+        volatile unsigned long long *guards = nullptr;   // the two guard words of a kPlan post (RenderState::host, words [1], [2])
+        hipEvent_t event = nullptr;
+        bool pending = false;
+        uint32_t n = 0;                          // counts in flight
+        Owner owner = kNone;
+        struct Landed {
+            const uint32_t *counts;
+            uint32_t n;
+            Owner owner;                         // kNone: nothing has landed
+        };
+        // src[0 .. n) -> counts behind `stream` (guards_src: and the two sticky guard words); nothing if a copy is in flight already
+        hipError_t post(const uint32_t *src, uint32_t n, Owner owner, hipStream_t stream, const unsigned long long *guards_src = nullptr);
+        Landed take();                           // the counts, once, if their copy has completed
+        void drop() { pending = false; }         // whatever is in flight is nobody's
+        // index of the first count <= threshold (n: none)
+        static uint32_t first_at_most(const uint32_t *counts, uint32_t n, uint32_t threshold);
+    } fb;
+    // Endpoint-table versions of an open rolling sequence: bf_scene_update_endpoints writes the new tables into the next block of
+    // a pool instead of flushing the sequence (the renders issued so far keep reading theirs through the descriptor ring:
+    // bf_device.h: DRoll, kMulti); the home buffers (as created) hold the tables whenever no sequence is open.
+    struct Tables {
+        struct Layout {                          // byte offsets of the five tables within a block (and within the staging slot)
+            size_t o_rects = 0, o_shapes = 0, o_emit = 0, o_mat = 0, o_sensor = 0, total = 0;
+        } lay;
+        size_t stride = 0;                       // bytes per block (lay.total rounded up to 256)
+        char *pool = nullptr;                    // device: kRollRing blocks (allocated on first use)
+        uint32_t next = 0;                       // next free block
+        bool in_pool = false;                    // d.rects ... d.sensor point into the pool
+        const bfd::DRect *rects = nullptr;       // the home buffers
+        const bfd::DShape *shapes = nullptr;
+        const bfd::DEmitter *emitters = nullptr;
+        const bfd::DMaterial *materials = nullptr;
+        const bfd::DSensor *sensor = nullptr;
+        bfd::DScene *d = nullptr;                // the handle's kernel arguments, whose five table pointers move between home and pool
+        void set_home(bfd::DScene &d_);          // d_'s tables as they stand are the home buffers (create, clone)
+        bf_status claim(const Layout &l, char **blk);     // the next free block (the first claim allocates the pool for layout l)
+        void joined() { ++next, in_pool = true; }         // ... which now holds the handle's tables
+        // the last version becomes the home buffers' content again, behind `stream`; the pointers are home before any copy can fail
+        bf_status go_home(uint32_t n_rects, uint32_t n_shapes, uint32_t n_emitters, uint32_t n_materials, hipStream_t stream);
+    } tab;
+    // Stream order between the successive uses of the handle: order_after_last / mark_last
+    struct LastUse {
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr;               // recorded behind the handle's latest work
+        bool has = false;
+        hipError_t wait() const { return has ? hipEventSynchronize(done) : hipSuccess; }      // the host waits for that work
+    } last;
+    // pool, pinned buffers, events, timing events, table pool and counters go with the handle
+    ~RenderState();
+};
+
+struct bf_scene {
+    bfd::DScene d;
+    bf_tunables tun;
+    std::shared_ptr<bf_geometry> geom;     // nodes / wnodes / tris / normals / uvs as created
+    // handles that render the SAME triangle / node arrays hold the same token (a clone that took its own snapshot of a
+    // translated scene does not): bf_scene_translate_meshes copies on write only while the token is shared
+    std::shared_ptr<char> geom_token;
+    // handles cloned from one another are meant to be in flight together (one per stream): how many of them have a rolling sequence
+    // open right now — small pools then launch a share of the persistent grids each (wf_setup: grid_share)
+    std::shared_ptr<std::atomic<int>> peers_rolling;
+    // one host thread at a time per handle (the handle owns the path pool its render's state lives in)
+    mutable std::atomic_flag busy = ATOMIC_FLAG_INIT;
+    std::vector<void *> owned;             // this handle's own allocations (small tables, spill columns, private geometry)
+    bf_scene_info info;
+    int device = 0;
+    int n_cus = 256;
+    std::vector<uint32_t> emitter_types;
+    uint32_t n_materials = 0;
+    bool any_back_material = false;        // some twosided material has a second nested BSDF (general kernels)
+    bool any_resample = false;             // some transmitter re-samples the path's wavelength (resample_freq: general kernels, DLaunch::resample)
+    bfd::DSensor sensor_host;              // host copy of the device sensor record
+    uint32_t film_w = 1, film_h = 1;       // the sensor's film (bf_sensor.film_width / film_height)
+    uint32_t adc_t = 0, adc_f = 0;         // what a receive-mode launch bins into: the ADC's window, or the whole ADC
+    MeshState mesh;                        // everything about moved meshes (bf_mesh.cpp)
+    mutable RenderState run;               // everything about renders (bf_render.cpp)
+    // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
+    std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
+    std::vector<float *> array_dev;
+    std::vector<uint32_t> array_n;
+    float *sensor_array_dev = nullptr;
+    uint32_t sensor_array_n = 0;
     // Pinned staging for small host tables that travel with a launch (batch seeds / mesh offsets, endpoint records):
     // a ring of slots, each with its own device mirror and an event recorded behind the copy, so the caller's arrays
     // and our stack locals are free again when the call returns and nothing blocks unless kStageSlots launches are in
@@ -253,10 +293,6 @@ struct bf_scene {
     };
     mutable Stage stage[kStageSlots];
     mutable int stage_next = 0;
-    mutable uint32_t *wf_feedback = nullptr;     // pinned: n_live[0 .. wf_fb_iters) of the last planned render
-    mutable hipEvent_t wf_fb_event = nullptr;
-    mutable bool wf_fb_pending = false;
-    mutable uint32_t wf_fb_iters = 0;
 };
 
 #pragma GCC visibility push(hidden)      // from here on: internal to the library
@@ -295,19 +331,24 @@ struct DeviceGuard {
         return fail(BF_ERR_INVALID, "%s: the scene handle is in use by another host thread (one call at a time per handle; " \
                                     "bf_scene_clone gives every thread / stream its own)", __func__)
 
-// ---- bf_api.cpp's, called by bf_mesh.cpp and documented where they are defined (C names: that file is one extern "C" block) ----
+// ---- bf_api.cpp's, called by the other two and documented where they are defined (C names: those files are one extern "C" block each) ----
 extern "C" {
 bf_status fail(bf_status st, const char *fmt, ...);      // sets bf_last_error's text
 bf_status stage_acquire(const bf_scene *sc, size_t bytes, bf_scene::Stage **out);
 bf_status stage_commit(bf_scene::Stage *st, size_t bytes, hipStream_t stream);
 bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream);
+
+// ---- bf_render.cpp, called by the other two ----
 bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
 bf_status mark_last(const bf_scene *scene, hipStream_t stream);
 bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
 bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev, bf_path_record *records_dev,
                         void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0);
+void fill_stats(const bf_scene *scene, const unsigned long long *c, uint64_t n_paths, bf_stats *st);
+bf_status guard_error(unsigned long long lost, unsigned long long refused);
+bf_status report_guards(const bf_scene *scene, unsigned long long lost, unsigned long long refused, const hipStream_t *async_on = nullptr);
 
-// ---- bf_mesh.cpp, called by bf_api.cpp ----
+// ---- bf_mesh.cpp, called by the other two ----
 // a device-form vertex update whose gather refused triangles: BF_ERR_DEVICE, once (wait: for the count; else only if it has landed)
 bf_status deform_report(const bf_scene *scene, bool wait);
 bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who, const bf_geometry::MeshTopo **topo_out);

@@ -27,7 +27,7 @@ constexpr uint32_t kShadeChain = 8;        // wf_shade: vertices per visit while
 constexpr uint32_t kTraceRefill = 32;      // wf_trace refills idle lanes once at most this many still hold a ray (44 until round 4: -2 % at 32, profiles/r04_knob_resweep.txt)
 constexpr uint32_t kTraceStragglers = 12;  // ... and postpones node steps of fewer lanes than this while leaves wait
 constexpr uint32_t kTraceBlocksPerCU = 8;
-constexpr uint32_t kTailSmallPool = 1u << 22;   // pools below this never fill the chip: earlier hand-over to the tail (bf_api.cpp: wf_tail_threshold)
+constexpr uint32_t kTailSmallPool = 1u << 22;   // pools below this never fill the chip: earlier hand-over to the tail (bf_render.cpp: wf_tail_threshold)
 constexpr uint32_t kTailRowJobs = 12;      // tail: up to three passes of four row-traversed rays beat one quad pass of sixteen
 
 // Per-slot state layout: three 64-byte RECORDS per slot,

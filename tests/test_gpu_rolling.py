@@ -468,7 +468,7 @@ def test_rolling_fuzz_scenes(hiplib, seed, receive):
 
 @pytest.mark.parametrize("share", ["", "1", "8"])
 def test_clones_rolling_side_by_side_share_the_grids(hiplib, share, monkeypatch):
-    """Small pools of handles that roll at the same time launch a share of the persistent grids each (bf_api.cpp: wf_setup,
+    """Small pools of handles that roll at the same time launch a share of the persistent grids each (bf_render.cpp: wf_setup,
     BF_GRID_SHARE: default 3, 1 = off, 8 = an eighth of the grids with eight peers... here four): three clones and their source,
     one stream and one rolling sequence each, renders issued round-robin — every per-path record equals the oracle's whatever
     grid a launch ran on, and every path of every render lands."""
