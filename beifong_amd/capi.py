@@ -155,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "bf_bsdf_eval_pdf", "bf_bsdf_eval_pdf_device", "bf_bsdf_sample", "bf_bsdf_sample_device",
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
     "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
+    "bf_render_converge_device", "bf_render_converge", "bf_converge_statistic_device",
 ]
 
 _lib = None
@@ -233,6 +234,11 @@ def load_library(path=None):
     lib.bf_ray_intersect_device.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bf_trace_any_device.argtypes = [vp, C.c_uint64, vp, vp, vp]
     lib.bf_eval_microfacet.argtypes = [C.c_int, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint64, vp, vp]
+    lib.bf_render_converge_device.argtypes = [vp, C.POINTER(bf_launch), C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp,
+                                              C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint64), C.POINTER(bf_stats)]
+    lib.bf_render_converge.argtypes = [vp, C.POINTER(bf_launch), C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, vp,
+                                       C.POINTER(C.c_uint32), vp, C.POINTER(C.c_uint64), C.POINTER(bf_stats)]
+    lib.bf_converge_statistic_device.argtypes = [C.POINTER(bf_launch), vp, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_uint64), vp]
     # test hooks (not in include/beifong_hip.h, not part of the ABI)
     if hasattr(lib, "bfdbg_scene_read_tree"):
         lib.bfdbg_scene_origin_scale.argtypes = [vp, C.POINTER(C.c_float)]
@@ -354,6 +360,63 @@ def moment_estimate(hist, lp):
     bad = np.broadcast_to(n < 2.0, mean.shape)
     mean, var, rel = (np.where(bad, np.nan, x) for x in (mean, var, rel))
     return mean, var, rel
+
+
+def converge_layout(lp):
+    """(first, second, w): the WATCHED pairs of a BF_FLAG_MOMENT launch, flat histogram indices of shape [cells, pairs], and the
+    index of every cell's W, shape [cells, 1].  The pairs of moment_layout restricted by mode: range / time the A nested AOVs
+    (not nested.X .Y .Z), path nested.Y, receive RAW Y, receive IQ I and Q."""
+    lp = bf_launch.from_buffer_copy(lp)
+    lp.flags |= BF_FLAG_MOMENT                 # (the converge entries force the flag on)
+    cells, c, _, _, w_off = _moment_shape(lp)
+    first, second = moment_layout(lp)
+    if lp.mode == BF_MODE_PATH:
+        first, second = first[:, 1:2], second[:, 1:2]
+    elif lp.mode in (BF_MODE_RANGE, BF_MODE_TIME):
+        first, second = first[:, :-3], second[:, :-3]
+    return first, second, (np.arange(cells, dtype=np.int64) * c + w_off)[:, None]
+
+
+def converge_seeds(lp, n_renders):
+    """uint64[n_renders]: the seeds of the renders of a converge call on `lp`, render k = round * round_renders + j of the call
+    with lp.seed + k * lp.n_paths (mod 2^64).  Path p of a render draws from the stream seed + path_offset + p, so seeds
+    n_paths apart give disjoint sample sets where consecutive seeds would share all but one path (include/beifong_hip.h)."""
+    return np.array([(lp.seed + k * lp.n_paths) % (1 << 64) for k in range(n_renders)], dtype=np.uint64)
+
+
+def converge_statistic(hist, lp, floor=0.01):
+    """(stat, n_significant) of an accumulated BF_FLAG_MOMENT histogram: the float64 statement of what
+    bf_converge_statistic_device computes, and the specification its kernels are held to (include/beifong_hip.h).
+
+    Per watched pair (converge_layout) moment_estimate's definitions with n = the pixel's or cell's W (on a 1 x 1 film the paths
+    accumulated so far; moment_estimate itself takes the launch's n_paths there, which is one render's): mean = m1 / n,
+    var_of_mean = max(m2 / n - mean^2, 0) / (n - 1), rel = sqrt(var_of_mean) / |mean|.  A pair is significant when
+    |m1| >= floor * max |m1| (the maximum over all watched pairs; floor in [0, 1], rounded to fp32 as the C ABI carries it);
+    stat = max rel over the significant pairs, n_significant their number.  stat is +inf, never NaN, when no pair is
+    significant (max |m1| == 0), when a significant pair has n < 2 (or mean 0, which floor = 0 admits), or when any cell of
+    the histogram is not finite (n_significant is then 0)."""
+    if not 0.0 <= floor <= 1.0:
+        raise ValueError(f"floor {floor} is outside [0, 1]")
+    first, second, w = converge_layout(lp)
+    cells, c = first.shape[0], {BF_MODE_RECEIVE_RAW: 4 + lp.phase_bins, BF_MODE_RECEIVE_IQ: 5, BF_MODE_PATH: 11, BF_MODE_RANGE: 11 + 2 * lp.bins,
+                                BF_MODE_TIME: 11 + 6 * lp.bins}[lp.mode]
+    h = np.asarray(hist, np.float32).astype(np.float64).reshape(-1)
+    if h.size != cells * c:
+        raise ValueError(f"histogram of {h.size} floats, the launch has {cells * c}")
+    if not np.all(np.isfinite(h)):
+        return np.inf, 0
+    m1, m2, n = h[first], h[second], h[w]
+    top = np.abs(m1).max()
+    sig = (np.abs(m1) >= float(np.float32(floor)) * top) & (top > 0.0)
+    n_sig = int(np.count_nonzero(sig))
+    if n_sig == 0:
+        return np.inf, 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = m1 / n
+        var = np.maximum(m2 / n - mean * mean, 0.0) / (n - 1.0)
+        rel = np.where(mean != 0.0, np.sqrt(var) / np.abs(mean), np.inf)
+    rel = np.where(np.broadcast_to(n < 2.0, rel.shape), np.inf, rel)
+    return float(rel[sig].max()), n_sig
 
 
 def shard_range(n_paths, shard, n_shards, lib=None):
@@ -633,6 +696,41 @@ class Scene:
                                                   C.c_void_p(stream) if stream else None,
                                                   C.byref(st) if st is not None else None), "bf_render_device")
         return st
+
+    def render_converge(self, launch, target, floor=0.01, round_renders=4, min_rounds=1, max_rounds=64, want_stats=True):
+        """bf_render_converge: rounds of round_renders moment renders of `launch` (seeds converge_seeds(launch, ...): disjoint paths),
+        accumulated on the device until the statistic (converge_statistic) of a round is at or below `target`, plus the one
+        round that was in flight by then -> (hist float32[channels with BF_FLAG_MOMENT], rounds, stat_history float64[rounds],
+        n_significant, stats).  want_stats=False: stats is None and no round waits for its own statistics."""
+        lm = bf_launch.from_buffer_copy(launch)
+        lm.flags |= BF_FLAG_MOMENT
+        hist = np.zeros(self.channels(lm), dtype=np.float32)
+        out = self._converge(self.lib.bf_render_converge, "bf_render_converge", launch, target, floor, round_renders, min_rounds, max_rounds,
+                             want_stats, _ptr(hist))
+        return (hist,) + out
+
+    def render_converge_device(self, launch, hist_ptr, target, floor=0.01, round_renders=4, min_rounds=1, max_rounds=64, stream=0,
+                               want_stats=False):
+        """bf_render_converge_device: the same into device memory hist_ptr[channels with BF_FLAG_MOMENT] (zeroed by the call),
+        stream-ordered; returns (rounds, stat_history, n_significant, stats) once the last round's statistic has been read."""
+        return self._converge(self.lib.bf_render_converge_device, "bf_render_converge_device", launch, target, floor, round_renders, min_rounds,
+                              max_rounds, want_stats, _dev(hist_ptr, "hist_ptr"), _stream(stream))
+
+    def _converge(self, fn, what, launch, target, floor, round_renders, min_rounds, max_rounds, want_stats, *buffers):
+        rounds, n_sig = C.c_uint32(0), C.c_uint64(0)
+        history = np.full(max(int(max_rounds), 1), np.nan)
+        st = bf_stats() if want_stats else None
+        check(self.lib, fn(self.handle, C.byref(launch), float(target), float(floor), int(round_renders), int(min_rounds), int(max_rounds),
+                           *buffers, C.byref(rounds), _ptr(history), C.byref(n_sig), C.byref(st) if st is not None else None), what)
+        return rounds.value, history[:rounds.value].copy(), n_sig.value, st
+
+    def converge_statistic_device(self, launch, hist_ptr, floor=0.01, stream=0):
+        """bf_converge_statistic_device: the statistic kernels alone on a device histogram in the moment layout of `launch`
+        -> (stat, n_significant); waits for the result."""
+        stat, n_sig = C.c_double(0.0), C.c_uint64(0)
+        check(self.lib, self.lib.bf_converge_statistic_device(C.byref(launch), _dev(hist_ptr, "hist_ptr"), float(floor), C.byref(stat),
+                                                              C.byref(n_sig), _stream(stream)), "bf_converge_statistic_device")
+        return stat.value, n_sig.value
 
     def flush(self, stream=0, want_stats=False):
         """bf_scene_flush: finish the paths the handle's rolling renders (BF_FLAG_ROLLING) left alive; with want_stats the

@@ -419,35 +419,6 @@ struct GeomSwap {
 // default arena budget of the batches (BF_MOTION_BATCH_MB overrides it at call time)
 constexpr size_t kMotionBatchMB = 2048;
 
-void add_stats(bf_stats &a, const bf_stats &b) {
-    a.n_paths += b.n_paths;
-    a.n_rays_closest += b.n_rays_closest;
-    a.n_rays_shadow += b.n_rays_shadow;
-    a.n_nodes_visited += b.n_nodes_visited;
-    a.n_tris_tested += b.n_tris_tested;
-    a.n_invalid += b.n_invalid;
-    a.n_bounces += b.n_bounces;
-    a.kernel_ms += b.kernel_ms;
-    a.trace_ms += b.trace_ms;
-    a.shade_ms += b.shade_ms;
-    a.tail_ms += b.tail_ms;
-    a.n_launches_trace += b.n_launches_trace;
-    a.n_bounce_iters += b.n_bounce_iters;
-    a.n_rays_tail += b.n_rays_tail;
-    a.n_rays_traced += b.n_rays_traced;
-    a.n_nodes_lds += b.n_nodes_lds;
-    a.n_nodes_tail += b.n_nodes_tail;
-    a.n_wnodes_tail += b.n_wnodes_tail;
-    a.n_tris_tail += b.n_tris_tail;
-    a.n_bounces_tail += b.n_bounces_tail;
-    a.n_shade_loads += b.n_shade_loads;
-    a.n_shade_stores += b.n_shade_stores;
-    a.n_shade_shadow += b.n_shade_shadow;
-    a.n_shade_rays += b.n_shade_rays;
-    a.n_guard += b.n_guard;
-    a.kernel_variant |= b.kernel_variant;      // (the chunks of one batch run the same kernels)
-}
-
 // What motion and deform batches share: chunks of renders whose versions fit the arena budget (BF_MOTION_BATCH_MB; at least one render
 // per chunk), the arena grown on demand, and per chunk prepare(k0, kc, a, L), which enqueues the chunk's versions into the arena `a`,
 // then the chunk's renders with the handle's kernel arguments pointing at version 0.  `fn` names the caller in error text.

@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
+#include <vector>
 
 // The launchers of bf_kernels.hip / bf_wavefront.hip a render goes through, once per build of the kernels: the exact one (no suffix),
 // the fast-arithmetic one (_fast, BF_FLAG_FAST: bf_ns.h) and the second-moment variants (_moment, BF_FLAG_MOMENT; bf_device.h: kMoment;
@@ -116,6 +118,12 @@ RenderState::~RenderState() {
     for (hipEvent_t e : timing) (void) hipEventDestroy(e);
     if (counters) (void) hipFree(counters);
     if (tab.pool) (void) hipFree(tab.pool);
+    for (float *q : conv.scratch)
+        if (q) (void) hipFree(q);
+    if (conv.ws) (void) hipFree(conv.ws);
+    if (conv.ring) (void) hipHostFree(conv.ring);
+    for (hipEvent_t e : conv.ev)
+        if (e) (void) hipEventDestroy(e);
 }
 
 extern "C" {
@@ -701,6 +709,35 @@ void fill_stats(const bf_scene *scene, const unsigned long long *c, uint64_t n_p
     st->kernel_variant = scene->run.last_variant;
 }
 
+void add_stats(bf_stats &a, const bf_stats &b) {
+    a.n_paths += b.n_paths;
+    a.n_rays_closest += b.n_rays_closest;
+    a.n_rays_shadow += b.n_rays_shadow;
+    a.n_nodes_visited += b.n_nodes_visited;
+    a.n_tris_tested += b.n_tris_tested;
+    a.n_invalid += b.n_invalid;
+    a.n_bounces += b.n_bounces;
+    a.kernel_ms += b.kernel_ms;
+    a.trace_ms += b.trace_ms;
+    a.shade_ms += b.shade_ms;
+    a.tail_ms += b.tail_ms;
+    a.n_launches_trace += b.n_launches_trace;
+    a.n_bounce_iters += b.n_bounce_iters;
+    a.n_rays_tail += b.n_rays_tail;
+    a.n_rays_traced += b.n_rays_traced;
+    a.n_nodes_lds += b.n_nodes_lds;
+    a.n_nodes_tail += b.n_nodes_tail;
+    a.n_wnodes_tail += b.n_wnodes_tail;
+    a.n_tris_tail += b.n_tris_tail;
+    a.n_bounces_tail += b.n_bounces_tail;
+    a.n_shade_loads += b.n_shade_loads;
+    a.n_shade_stores += b.n_shade_stores;
+    a.n_shade_shadow += b.n_shade_shadow;
+    a.n_shade_rays += b.n_shade_rays;
+    a.n_guard += b.n_guard;
+    a.kernel_variant |= b.kernel_variant;      // (the chunks of a batch, the rounds of a converge call, run the same kernels)
+}
+
 // Stream order between the successive uses of a handle's pool: work enqueued on another stream than the previous
 // call's waits for it (an event wait on the device, never on the host).
 bf_status order_after_last(const bf_scene *scene, hipStream_t stream) {
@@ -1030,6 +1067,192 @@ bf_status bf_scene_sync(bf_scene *scene) {
     HIP_TRY(hipMemcpy(g, scene->run.counters + bfd::CTR_GUARD, sizeof(g), hipMemcpyDeviceToHost));
     if (g[0] || g[1]) return report_guards(scene, g[0], g[1]);
     return deform_report(scene, true);
+}
+
+// ---------------------------------------------------------------------------
+// Render until a relative standard error is reached (include/beifong_hip.h: bf_render_converge_device): rounds of
+// moment renders accumulated on the device, the statistic of the accumulator after every round (bf_converge.hip), and a stop
+// rule that keeps one round in flight ahead of the statistic the host waits for.
+// ---------------------------------------------------------------------------
+// where the watched pairs of `lm` (BF_FLAG_MOMENT set) sit: the (first, second) pairs of capi.moment_layout, restricted by mode
+static bf_status conv_layout(const bf_launch *lm, bfd::ConvLayout &L) {
+    std::memset(&L, 0, sizeof(L));
+    uint64_t cells = 0;
+    if (lm->mode == BF_MODE_RECEIVE_RAW || lm->mode == BF_MODE_RECEIVE_IQ) {
+        const bool iq = lm->mode == BF_MODE_RECEIVE_IQ;
+        cells = (uint64_t) lm->bins * lm->bins_y;
+        L.chan = iq ? 5u : 4u + lm->phase_bins;
+        L.pairs = iq ? 2u : 1u;                      // I and Q | Y
+        L.first0 = 0u;
+        L.second0 = iq ? 3u : 3u + lm->phase_bins;
+        L.w_off = 2u;
+    } else if (lm->mode <= BF_MODE_TIME) {
+        const uint32_t a = lm->mode == BF_MODE_PATH ? 0u : (lm->mode == BF_MODE_RANGE ? lm->bins : 3u * lm->bins);
+        cells = multi_pixel_of(lm) ? (uint64_t) lm->film_width * lm->film_height : 1u;
+        L.chan = 11u + 2u * a;
+        L.pairs = a ? a : 1u;                        // the nested AOVs | nested.Y
+        L.first0 = a ? 5u : 6u;
+        L.second0 = L.first0 + a + 3u;
+        L.w_off = 4u;
+    } else {
+        return fail(BF_ERR_INVALID, "unknown mode %u", lm->mode);
+    }
+    L.total = cells * L.chan;
+    L.n_pairs = cells * L.pairs;
+    if (!L.total || !L.n_pairs) return fail(BF_ERR_INVALID, "the launch has no histogram cells (bins / ADC size 0)");
+    // every index the kernels form stays inside a cell, and the cells are the launch's histogram
+    if (L.second0 + L.pairs > L.chan || L.total != bf_launch_channels(lm))
+        return fail(BF_ERR_DEVICE, "internal: the watched pairs do not fit the moment layout (%u channels per cell)", L.chan);
+    return BF_OK;
+}
+
+static bool floor_ok(float floor) { return floor >= 0.f && floor <= 1.f; }      // (NaN fails both)
+
+bf_status bf_converge_statistic_device(const bf_launch *launch, const float *hist_dev, float floor, double *stat_out,
+                                       uint64_t *n_significant_out, void *stream_) {
+    if (!launch || !hist_dev || !stat_out) return fail(BF_ERR_INVALID, "null argument");
+    if (!floor_ok(floor)) return fail(BF_ERR_INVALID, "bf_converge_statistic_device: floor %g is outside [0, 1]", (double) floor);
+    bf_launch lm = *launch;
+    lm.flags |= BF_FLAG_MOMENT;
+    bfd::ConvLayout L;
+    bf_status st = conv_layout(&lm, L);
+    if (st != BF_OK) return st;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    bfd::ConvWork *ws = nullptr;
+    bfd::ConvResult *slot = nullptr;
+    hipError_t e = hipMalloc((void **) &ws, sizeof(*ws));
+    if (e == hipSuccess) e = hipHostMalloc((void **) &slot, sizeof(*slot));
+    if (e == hipSuccess) {
+        slot->round = ~0u;
+        e = bfk_converge_round(const_cast<float *>(hist_dev), nullptr, 0u, &L, (double) floor, ws, slot, 0u, stream);      // (n_blocks 0: read only)
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess && slot->round != 0u) e = hipErrorUnknown;
+    if (e == hipSuccess) {
+        *stat_out = slot->stat;
+        if (n_significant_out) *n_significant_out = slot->n_significant;
+    }
+    if (slot) (void) hipHostFree(slot);
+    if (ws) (void) hipFree(ws);
+    if (e != hipSuccess) return fail(BF_ERR_DEVICE, "bf_converge_statistic_device: %s", hipGetErrorString(e));
+    return BF_OK;
+}
+
+// the handle's converge state, for rounds of `floats` floats each
+static bf_status conv_ensure(const bf_scene *scene, size_t floats) {
+    RenderState::Converge &cv = scene->run.conv;
+    if (!cv.ws) HIP_TRY(hipMalloc((void **) &cv.ws, sizeof(bfd::ConvWork)));
+    if (!cv.ring) HIP_TRY(hipHostMalloc((void **) &cv.ring, RenderState::Converge::kRing * sizeof(bfd::ConvResult)));
+    for (hipEvent_t &e : cv.ev)
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (cv.cap < floats) {
+        // (every earlier converge call has returned behind its last round: nothing reads the old buffers)
+        for (float *&q : cv.scratch) {
+            if (q) HIP_TRY(hipFree(q));
+            q = nullptr;
+        }
+        cv.cap = 0;
+        for (float *&q : cv.scratch) HIP_TRY(hipMalloc((void **) &q, floats * sizeof(float)));
+        cv.cap = floats;
+    }
+    return BF_OK;
+}
+
+bf_status bf_render_converge_device(bf_scene *scene, const bf_launch *launch, float target, float floor, uint32_t round_renders,
+                                    uint32_t min_rounds, uint32_t max_rounds, float *hist_dev, void *stream_, uint32_t *rounds_out,
+                                    double *stat_history_out, uint64_t *n_significant_out, bf_stats *stats_out) {
+    const char *fn = "bf_render_converge:";
+    if (!scene || !launch || !hist_dev || !rounds_out) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (launch->flags & BF_FLAG_FAST)
+        return fail(BF_ERR_INVALID, "%s BF_FLAG_FAST: the rounds are moment renders, and BF_FLAG_MOMENT | BF_FLAG_FAST is refused", fn);
+    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: the rounds are batches, which do not roll", fn);
+    if (!(target >= 0.f)) return fail(BF_ERR_INVALID, "%s target %g is negative or NaN", fn, (double) target);
+    if (!floor_ok(floor)) return fail(BF_ERR_INVALID, "%s floor %g is outside [0, 1]", fn, (double) floor);
+    if (round_renders == 0 || max_rounds == 0) return fail(BF_ERR_INVALID, "%s round_renders and max_rounds must be at least 1", fn);
+    if (min_rounds > max_rounds) return fail(BF_ERR_INVALID, "%s min_rounds %u exceeds max_rounds %u", fn, min_rounds, max_rounds);
+    if (launch->n_paths == 0) return fail(BF_ERR_INVALID, "%s n_paths is 0", fn);
+    const bool multi_pixel = multi_pixel_of(launch);
+    if (multi_pixel && round_renders > 1)
+        return fail(BF_ERR_INVALID, "%s a multi-pixel film is rendered one launch per round (round_renders %u must be 1)", fn, round_renders);
+    bf_launch lm = *launch;
+    lm.flags |= BF_FLAG_MOMENT;
+    BF_ENTER(scene);
+    const uint32_t R = round_renders;
+    bf_batch batch = {R, nullptr, nullptr};
+    // What a render does before it enqueues anything (render_locked), done here before the caller's buffer is touched: a pending
+    // report of a device-form vertex update fails the call with hist_dev as it was (it is reported once, so the rounds find none).
+    bf_status st = deform_report(scene, true);
+    if (st != BF_OK || (st = check_launch(scene, &lm, multi_pixel ? nullptr : &batch, R, nullptr)) != BF_OK) return st;
+    bfd::ConvLayout L;
+    if ((st = conv_layout(&lm, L)) != BF_OK || (st = conv_ensure(scene, (size_t) R * L.total)) != BF_OK) return st;
+    RenderState::Converge &cv = scene->run.conv;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if ((st = order_after_last(scene, stream)) != BF_OK || (st = close_sequence(scene, stream)) != BF_OK) return st;
+    if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+    HIP_TRY(hipMemsetAsync(hist_dev, 0, L.total * sizeof(float), stream));
+    std::vector<uint64_t> seeds(R);
+    // round r: its renders into the zeroed scratch, the scratch into the accumulator, the accumulator's statistic into ring slot r
+    auto issue = [&](uint32_t r) -> bf_status {
+        float *scratch = cv.scratch[r & 1u];
+        HIP_TRY(hipMemsetAsync(scratch, 0, (size_t) R * L.total * sizeof(float), stream));
+        // Render k = r R + j of the call takes seed launch->seed + k n_paths.  The kernels give path p of a render the stream
+        // seed + path_offset + p (bf_path_logic.h), so consecutive seeds would render all but one path again; n_paths apart, the
+        // renders' streams are the consecutive, disjoint ranges of one render of rounds R n_paths paths (mod 2^64).
+        for (uint32_t j = 0; j < R; ++j) seeds[j] = launch->seed + ((uint64_t) r * R + j) * launch->n_paths;
+        batch.seeds = seeds.data();
+        lm.seed = seeds[0];
+        bf_stats rs;
+        bf_status s = render_locked(scene, &lm, multi_pixel ? nullptr : &batch, scratch, nullptr, stream_, stats_out ? &rs : nullptr);
+        if (s != BF_OK) return s;
+        if (stats_out) add_stats(*stats_out, rs);
+        HIP_TRY(bfk_converge_round(hist_dev, scratch, R, &L, (double) floor, cv.ws, &cv.ring[r % RenderState::Converge::kRing], r, stream));
+        HIP_TRY(hipEventRecord(cv.ev[r & 1u], stream));
+        return mark_last(scene, stream);      // (the handle's scratch is in use until here)
+    };
+    // `limit` rounds are performed: max_rounds until the first statistic at or below the target (round k*, not before round
+    // min_rounds - 1) cuts it to k* + 2.  Round r + 1 is in flight whenever stat_r is waited for, so it is part of the result.
+    uint32_t limit = max_rounds, issued = 0;
+    bool found = false;
+    for (; issued < std::min(2u, limit); ++issued)
+        if ((st = issue(issued)) != BF_OK) return st;
+    for (uint32_t r = 0; r < limit; ++r) {
+        HIP_TRY(hipEventSynchronize(cv.ev[r & 1u]));
+        const bfd::ConvResult res = cv.ring[r % RenderState::Converge::kRing];
+        if (res.round != r) return fail(BF_ERR_DEVICE, "%s the statistic of round %u did not arrive (slot holds round %u)", fn, r, res.round);
+        if (stat_history_out) stat_history_out[r] = res.stat;
+        if (n_significant_out) *n_significant_out = res.n_significant;
+        if (!found && r + 1u >= min_rounds && res.stat <= (double) target) {
+            found = true;
+            limit = std::min(r + 2u, max_rounds);
+        }
+        if (issued < limit) {
+            if ((st = issue(issued)) != BF_OK) return st;
+            ++issued;
+        }
+    }
+    *rounds_out = limit;
+    return BF_OK;
+}
+
+bf_status bf_render_converge(bf_scene *scene, const bf_launch *launch, float target, float floor, uint32_t round_renders,
+                             uint32_t min_rounds, uint32_t max_rounds, float *hist_out, uint32_t *rounds_out,
+                             double *stat_history_out, uint64_t *n_significant_out, bf_stats *stats_out) {
+    if (!scene || !launch || !hist_out || !rounds_out) return fail(BF_ERR_INVALID, "bf_render_converge: null argument");
+    bf_launch lm = *launch;
+    lm.flags |= BF_FLAG_MOMENT;
+    const size_t bytes = (size_t) bf_launch_channels(&lm) * sizeof(float);
+    if (!bytes) return fail(BF_ERR_INVALID, "bf_render_converge: the launch has no histogram cells");
+    DeviceGuard on_device(scene->device);
+    float *hist_dev = nullptr;
+    hipError_t e = hipMalloc((void **) &hist_dev, bytes);
+    if (e != hipSuccess) return fail(BF_ERR_NOMEM, "bf_render_converge: hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
+    bf_status st = bf_render_converge_device(scene, launch, target, floor, round_renders, min_rounds, max_rounds, hist_dev, nullptr, rounds_out,
+                                             stat_history_out, n_significant_out, stats_out);
+    // (the last round's statistic has been read, so the accumulator is complete; a refused call enqueued nothing)
+    if (st == BF_OK) e = hipMemcpy(hist_out, hist_dev, bytes, hipMemcpyDeviceToHost);
+    (void) hipFree(hist_dev);
+    if (st == BF_OK && e != hipSuccess) return fail(BF_ERR_DEVICE, "bf_render_converge: hipMemcpy: %s", hipGetErrorString(e));
+    return st;
 }
 
 /* test hook (not part of the ABI): pre-load the sticky guard word, as if wf_trace had dropped `n` rays */

@@ -9,6 +9,7 @@
 
 #include "bf_build.h"
 #include "bf_bvh.h"
+#include "bf_converge.h"
 #include "bf_device.h"
 #include "bf_wavefront.h"
 
@@ -245,7 +246,17 @@ struct __attribute__((visibility("hidden"))) RenderState {
         bool has = false;
         hipError_t wait() const { return has ? hipEventSynchronize(done) : hipSuccess; }      // the host waits for that work
     } last;
-    // pool, pinned buffers, events, timing events, table pool and counters go with the handle
+    // bf_render_converge_device, allocated on first use: the rounds' scratch histograms (double-buffered, [R][channels]
+    // each), the statistic kernels' hand-over words, the pinned ring their results land in and one event per round in flight
+    struct Converge {
+        static constexpr uint32_t kRing = 4;     // slot r % kRing: at most two rounds are in flight
+        float *scratch[2] = {nullptr, nullptr};
+        size_t cap = 0;                          // floats per scratch buffer
+        bfd::ConvWork *ws = nullptr;             // device
+        bfd::ConvResult *ring = nullptr;         // pinned [kRing]
+        hipEvent_t ev[2] = {nullptr, nullptr};   // behind round r's statistic: ev[r & 1]
+    } conv;
+    // pool, pinned buffers, events, timing events, table pool, counters and the converge state go with the handle
     ~RenderState();
 };
 
@@ -345,6 +356,7 @@ bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
 bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev, bf_path_record *records_dev,
                         void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0);
 void fill_stats(const bf_scene *scene, const unsigned long long *c, uint64_t n_paths, bf_stats *st);
+void add_stats(bf_stats &a, const bf_stats &b);      // a += b (the chunks of a batch, the rounds of a converge call)
 bf_status guard_error(unsigned long long lost, unsigned long long refused);
 bf_status report_guards(const bf_scene *scene, unsigned long long lost, unsigned long long refused, const hipStream_t *async_on = nullptr);
 

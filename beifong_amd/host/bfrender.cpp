@@ -109,6 +109,10 @@ int main(int argc, char **argv) {
         printf("rendered %llu paths, %llu rays in %.3f ms (kernels %.3f ms) -> [%u, %u, %u]\n",
                (unsigned long long) st->n_paths, (unsigned long long) (st->n_rays_closest + st->n_rays_shadow),
                in->last_stats().wall_ms, st->kernel_ms, rows, cols, ch);
+        if (auto *si = dynamic_cast<SamplingIntegrator *>(in))
+            if (si->last_converge().rounds)
+                printf("converged: %u rounds, relative standard error %.6g over %llu significant bins\n", si->last_converge().rounds,
+                       si->last_converge().stat, (unsigned long long) si->last_converge().n_significant);
         std::string out = output;
         if (out.empty()) {
             size_t k = scene_file.find_last_of('.');

@@ -227,6 +227,16 @@ int bfh_integrator_stats(void *integrator, bf_stats *out, double *wall_ms) {
         *wall_ms = in->last_stats().wall_ms;
     })
 }
+/// what the last render() / receive() of a converging integrator (moment with rel_stderr > 0) did; rounds = 0: it rendered once
+int bfh_integrator_converge(void *integrator, unsigned *rounds, double *stat, unsigned long long *n_significant) {
+    BFH_TRY({
+        auto *in = dynamic_cast<SamplingIntegrator *>((Object *) integrator);
+        if (!in) Throw("object is not a SamplingIntegrator");
+        *rounds = in->last_converge().rounds;
+        *stat = in->last_converge().stat;
+        *n_significant = in->last_converge().n_significant;
+    })
+}
 int bfh_sensor_sample_count(void *endpoint, unsigned long long *n) {
     BFH_TRY({
         if (auto *se = dynamic_cast<Sensor *>((Object *) endpoint)) *n = se->sampler()->sample_count();

@@ -20,7 +20,23 @@ public:
         if (fast_math())
             Throw("moment: \"fast_math\" on the moment integrator or below it is refused: the fast-arithmetic tolerance contract "
                   "says nothing about squared samples (BF_FLAG_MOMENT | BF_FLAG_FAST)");
+        // render until converged (not reference properties; bf_render_converge).  rel_stderr = 0: one render, as ever
+        m_converge.rel_stderr = props.float_("rel_stderr", 0.f);
+        if (!(m_converge.rel_stderr >= 0.f)) Throw("moment: \"rel_stderr\" must not be negative (0 = off)");
+        const bool on = m_converge.rel_stderr > 0.f;
+        for (const char *name : {"significance", "max_passes", "passes_per_round"})
+            if (!on && props.has_property(name)) Throw("moment: \"%s\" without \"rel_stderr\" > 0 has nothing to act on", name);
+        m_converge.significance = props.float_("significance", m_converge.significance);
+        if (!(m_converge.significance >= 0.f && m_converge.significance <= 1.f)) Throw("moment: \"significance\" must lie in [0, 1]");
+        const int64_t per_round = props.int_("passes_per_round", 0), max_passes = props.int_("max_passes", m_converge.max_passes);
+        if (per_round < 0 || per_round > 65535) Throw("moment: \"passes_per_round\" must lie in [0, 65535] (0: 4, or 1 for a multi-pixel film)");
+        if (max_passes < 1 || max_passes > (1 << 24)) Throw("moment: \"max_passes\" must lie in [1, 2^24]");
+        if (per_round > 0 && max_passes % per_round != 0)
+            Throw("moment: \"max_passes\" (%lld) must be a multiple of \"passes_per_round\" (%lld)", (long long) max_passes, (long long) per_round);
+        m_converge.passes_per_round = (uint32_t) per_round;
+        m_converge.max_passes = (uint32_t) max_passes;
     }
+    const ConvergeSpec *converge() const override { return m_converge.rel_stderr > 0.f ? &m_converge : nullptr; }
     std::vector<std::string> aov_names() const override {
         bf_launch lp{};
         m_integrator->configure(lp);
@@ -50,5 +66,6 @@ public:
 private:
     ref<SamplingIntegrator> m_integrator;
     std::string m_name;
+    ConvergeSpec m_converge;
 };
 BF_EXPORT_PLUGIN(MomentIntegrator, "SamplingIntegrator", "moment", "Moment integrator")

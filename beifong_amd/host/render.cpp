@@ -671,6 +671,32 @@ SamplingIntegrator::SamplingIntegrator(const Properties &props) : Integrator(pro
     m_fast_math = props.bool_("fast_math", false);
 }
 
+void SamplingIntegrator::run(Scene *scene, const Endpoint *endpoint, const bf_launch &lp, float *hist) {
+    m_converge = ConvergeResult();
+    const ConvergeSpec *cs = converge();
+    auto t0 = std::chrono::steady_clock::now();
+    if (!cs || !(cs->rel_stderr > 0.f)) {
+        bf_status st = render_on_gpus(scene, endpoint, lp, hist, &m_stats.stats);
+        if (st != BF_OK) Throw("bf_render failed (status %d): %s", st, bf_last_error());
+    } else {
+        if (gpu_count() > 1) Throw("\"rel_stderr\" renders on one GPU: the rounds are accumulated on the device that renders them (gpu_count is %d)", gpu_count());
+        const bool film = lp.spp && lp.film_width && lp.film_height;
+        const uint32_t per_round = cs->passes_per_round ? cs->passes_per_round : (film ? 1u : 4u);
+        if (film && per_round != 1)
+            Throw("\"passes_per_round\" = %u with a %u x %u film: multi-pixel films are not batched, a round is one render", per_round,
+                  lp.film_width, lp.film_height);
+        if (cs->max_passes % per_round != 0)
+            Throw("\"max_passes\" (%u) must be a multiple of \"passes_per_round\" (%u)", cs->max_passes, per_round);
+        std::vector<double> history(cs->max_passes / per_round);
+        bf_status st = bf_render_converge(scene->device_scene(endpoint), &lp, cs->rel_stderr, cs->significance, per_round, 1u,
+                                          (uint32_t) history.size(), hist, &m_converge.rounds, history.data(), &m_converge.n_significant,
+                                          &m_stats.stats);
+        if (st != BF_OK) Throw("bf_render_converge failed (status %d): %s", st, bf_last_error());
+        m_converge.stat = history[m_converge.rounds - 1];      // the last round's: the one of the histogram returned
+    }
+    m_stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 static uint32_t color_mode_of_variant() {
     // scalar_rgb converts through srgb_to_xyz (integrator.cpp:292-294); mono and
     // spectral-with-uniform-spectra replicate the lane (CIE tables are out of scope)
@@ -712,10 +738,7 @@ bool SamplingIntegrator::render(Scene *scene, Sensor *sensor) {
     if (n != channels.size() * film->width() * film->height())
         Throw("internal error: channel count mismatch (%u vs %zu)", n, channels.size() * film->width() * film->height());
     std::vector<float> hist(n);
-    auto t0 = std::chrono::steady_clock::now();
-    bf_status st = render_on_gpus(scene, sensor, lp, hist.data(), &m_stats.stats);
-    if (st != BF_OK) Throw("bf_render failed (status %d): %s", st, bf_last_error());
-    m_stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    run(scene, sensor, lp, hist.data());
     film->put(hist.data(), hist.size());
     return !m_stop;
 }
@@ -755,10 +778,7 @@ bool SamplingIntegrator::receive(Scene *scene, Receiver *receiver) {
     receive_launch(receiver, lp);
     uint32_t n = bf_launch_channels(&lp);
     std::vector<float> hist(n);
-    auto t0 = std::chrono::steady_clock::now();
-    bf_status st = render_on_gpus(scene, receiver, lp, hist.data(), &m_stats.stats);
-    if (st != BF_OK) Throw("bf_render failed (status %d): %s", st, bf_last_error());
-    m_stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    run(scene, receiver, lp, hist.data());
     adc->put(hist.data(), hist.size());
     return !m_stop;
 }

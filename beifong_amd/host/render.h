@@ -277,6 +277,20 @@ protected:
     RenderStats m_stats{};
 };
 
+/// "rel_stderr" of the moment integrator: render() / receive() then run bf_render_converge — rounds of
+/// passes_per_round renders of the sample count each, until every significant bin is known to rel_stderr — instead of one render
+struct ConvergeSpec {
+    float rel_stderr = 0.f;            // target; 0 = off
+    float significance = 0.01f;        // the statistic's floor: bins below this share of the largest are not watched
+    uint32_t max_passes = 256;         // renders at most (a multiple of passes_per_round)
+    uint32_t passes_per_round = 0;     // renders per round; 0 = 4, or 1 for a multi-pixel film (films are not batched)
+};
+struct ConvergeResult {
+    uint32_t rounds = 0;               // rounds performed by the last render() / receive() (0: it did not converge-render)
+    double stat = 0.0;                 // the statistic of the histogram the film / ADC received
+    uint64_t n_significant = 0;
+};
+
 /// integrator.h:116-158.  `sample()` lives in the HIP kernels; subclasses only
 /// say which estimator they are and what AOVs they add.
 class SamplingIntegrator : public Integrator {
@@ -297,6 +311,9 @@ public:
     /// bit-equality with the oracle
     virtual bool fast_math() const { return m_fast_math; }
     void set_fast_math(bool on) { m_fast_math = on; }
+    /// non-null with rel_stderr > 0: render until converged (the moment integrator alone offers it)
+    virtual const ConvergeSpec *converge() const { return nullptr; }
+    const ConvergeResult &last_converge() const { return m_converge; }
     /// SamplingIntegrator properties (integrator.cpp:27-43): edge of the image blocks (0: MTS_BLOCK_SIZE) and samples per pass
     uint32_t block_size() const { return m_block_size; }
     size_t samples_per_pass() const { return m_samples_per_pass; }
@@ -310,6 +327,11 @@ protected:
     bool m_fast_math = false;
     uint32_t m_block_size = 0;
     size_t m_samples_per_pass = (size_t) -1;
+    ConvergeResult m_converge;
+
+private:
+    /// the one render of render() / receive(), or the converge call in its place
+    void run(Scene *scene, const Endpoint *endpoint, const bf_launch &lp, float *hist);
 };
 
 /// src/librender/scene.cpp:22-120

@@ -62,6 +62,7 @@ def lib():
     l.bfh_integrator_render.argtypes = [vp, vp, vp]
     l.bfh_integrator_receive.argtypes = [vp, vp, vp]
     l.bfh_integrator_stats.argtypes = [vp, C.POINTER(capi.bf_stats), C.POINTER(C.c_double)]
+    l.bfh_integrator_converge.argtypes = [vp, C.POINTER(C.c_uint), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
     l.bfh_sensor_sample_count.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     l.bfh_develop.argtypes = [vp, cp]
     l.bfh_write_exr.argtypes = [cp, C.c_uint, C.c_uint, C.c_uint, C.POINTER(cp), C.POINTER(C.c_float)]
@@ -544,6 +545,13 @@ class Integrator(_Handle):
         st, ms = capi.bf_stats(), C.c_double()
         check(lib().bfh_integrator_stats(self._ptr, C.byref(st), C.byref(ms)))
         return st, ms.value
+
+    def converge_stats(self):
+        """(rounds, statistic, n_significant) of the last render() / receive() of a converging integrator (moment with
+        rel_stderr > 0); rounds = 0: it rendered once"""
+        rounds, stat, n_sig = C.c_uint(), C.c_double(), C.c_ulonglong()
+        check(lib().bfh_integrator_converge(self._ptr, C.byref(rounds), C.byref(stat), C.byref(n_sig)))
+        return rounds.value, stat.value, n_sig.value
 
 
 class Scene(_Handle):

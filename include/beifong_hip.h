@@ -677,6 +677,57 @@ bf_status bf_render_batch(const bf_scene *scene, const bf_launch *launch,
                           const bf_batch *batch, float *hist_out,
                           bf_path_record *records_out, bf_stats *stats_out);
 
+/* RENDER UNTIL A RELATIVE STANDARD ERROR IS REACHED.  Every product of the engine is a Monte-Carlo histogram;
+ * BF_FLAG_MOMENT gives every bin its error bar, and these entries close the loop on the device: rounds of moment renders are
+ * accumulated into hist_dev until the worst significant bin is known to `target`.
+ *
+ *   The statistic of a BF_FLAG_MOMENT histogram (the launch's layout, flag forced on), fp64 on the device from the fp32 cells:
+ *     watched pairs (m1, m2)   range / time: the A nested-AOV channels and their m2_; path: nested.Y; receive RAW: Y of every
+ *                              ADC cell; receive IQ: I and Q of every cell
+ *     per pair                 n = the pixel's or cell's W (a 1 x 1 film: the paths accumulated so far), mean = m1 / n,
+ *                              var_of_mean = max(m2 / n - mean^2, 0) / (n - 1), rel = sqrt(var_of_mean) / |mean|
+ *     significant              |m1| >= floor * max |m1| (the maximum over all watched pairs of the histogram; floor in [0, 1])
+ *     stat                     max rel over the significant pairs; +inf, never NaN, when no pair is significant (max |m1| == 0),
+ *                              when a significant pair has n < 2 or mean 0, or when any cell of the histogram is not finite
+ *                              (n_significant is then 0)
+ *   capi.converge_statistic (Python) is the same definition in float64 numpy and the specification the kernels are held to.
+ *
+ *   Rounds: round r (from 0) is round_renders (= R) ordinary renders of `launch` with BF_FLAG_MOMENT forced on, render j with seed
+ *     launch->seed + (r R + j) * launch->n_paths (mod 2^64): ONE bf_render_batch_device call into a zeroed scratch [R][channels]
+ *     of the handle for a 1 x 1 film or a receive mode (one launch sequence and one tail per round), one plain render for a
+ *     multi-pixel film (R must be 1).  The seeds are n_paths apart, NOT consecutive: path p of a render draws from the stream
+ *     seed + path_offset + p, so renders of seeds s and s + 1 share all but one of their paths, and an error bar over them would
+ *     shrink without a new sample behind it.  n_paths apart, the renders of a call are disjoint: together they draw from the streams
+ *     of paths path_offset .. path_offset + rounds R n_paths of seed launch->seed, and n, m1 and m2 of the accumulator are sums over
+ *     independent samples, which is what var_of_mean assumes.  (Two calls are disjoint when their seeds are at least
+ *     rounds R n_paths apart.)  The
+ *     scratch blocks are then added to hist_dev in block order, one thread per cell, so the accumulator is a deterministic
+ *     function of the renders, and the statistic of the accumulator after round r is written to a pinned host ring.  hist_dev
+ *     [bf_launch_channels(launch | BF_FLAG_MOMENT)] is zeroed by the callee.
+ *   Stop rule: the host always has one round in flight ahead of the statistic it waits for (round r + 1 is issued before stat_r
+ *     is read, so the GPU never idles on the decision).  With k* the first r >= min_rounds - 1 whose stat_r <= target, the call
+ *     performs exactly min(k* + 2, max_rounds) rounds (max_rounds if there is no k*), whatever the timing.  *rounds_out is that
+ *     number, stat_history_out[r] (optional, [max_rounds]) the statistic after every round performed; the last entry and
+ *     *n_significant_out belong to the returned histogram, which is the sum of ALL rounds performed, the look-ahead round included.
+ *   The call returns when the last round's statistic has been read: it waits on that round's event (never on the device), like
+ *     bf_scene_rebuild_bvh.  stats_out (optional) adds up the rounds; each round then waits for its own statistics, as a render
+ *     with stats_out does.
+ *   BF_ERR_INVALID before anything is enqueued (a failed call leaves the scene as it was): BF_FLAG_FAST (refused together with
+ *     moments), BF_FLAG_ROLLING, target negative or NaN (+inf: stop as early as the rule permits), floor outside [0, 1],
+ *     round_renders == 0, max_rounds == 0, min_rounds > max_rounds, a multi-pixel film with round_renders > 1, n_paths == 0.
+ *     Launch checks are bf_render_batch_device's.  An open rolling sequence on the handle is finished first.
+ *   bf_render_converge is the host-buffer form.  bf_converge_statistic_device is the statistic alone, of any moment histogram
+ *     on the current device: it enqueues the kernels on `stream` and waits for their result. */
+bf_status bf_render_converge_device(bf_scene *scene, const bf_launch *launch, float target, float floor, uint32_t round_renders,
+                                    uint32_t min_rounds, uint32_t max_rounds, float *hist_dev, void *stream, uint32_t *rounds_out,
+                                    double *stat_history_out /* [max_rounds] or NULL */, uint64_t *n_significant_out,
+                                    bf_stats *stats_out);
+bf_status bf_render_converge(bf_scene *scene, const bf_launch *launch, float target, float floor, uint32_t round_renders,
+                             uint32_t min_rounds, uint32_t max_rounds, float *hist_out, uint32_t *rounds_out,
+                             double *stat_history_out /* [max_rounds] or NULL */, uint64_t *n_significant_out, bf_stats *stats_out);
+bf_status bf_converge_statistic_device(const bf_launch *launch, const float *hist_dev, float floor, double *stat_out,
+                                       uint64_t *n_significant_out, void *stream);
+
 /* A batch whose renders each move the meshes by their OWN rigid transforms: render k of n_renders renders the scene with
  * every mesh shape s at to_world[k][s] (3x4 row-major [R | t], bf_scene_transform_meshes' convention), seed seeds[k]
  * (NULL: launch->seed for every render) into hist_dev + k * bf_launch_channels(launch) and, if records_dev is not NULL,
