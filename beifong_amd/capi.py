@@ -26,6 +26,8 @@ BF_MODE_PATH, BF_MODE_RANGE, BF_MODE_TIME, BF_MODE_RECEIVE_RAW, BF_MODE_RECEIVE_
 BF_COLOR_RGB, BF_COLOR_MONO = range(2)
 BF_FLAG_STATS, BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL, BF_FLAG_DOPPLER, BF_FLAG_MIX_RESAMPLE = 1, 2, 4, 8, 16
 BF_FLAG_ROLLING, BF_FLAG_TIMING, BF_FLAG_COUNT, BF_FLAG_FAST, BF_FLAG_MOMENT = 32, 64, 128, 256, 512
+BF_FLAG_CLASSES = 1024
+BF_MAX_CLASSES = 256
 
 M16 = C.c_float * 16
 
@@ -58,7 +60,7 @@ class bf_emitter(C.Structure):
 
 
 BF_FILTER_RESOLUTION = 31
-BF_VARIANT_LEAN, BF_VARIANT_WIDE, BF_VARIANT_FAST, BF_VARIANT_MOMENT = 1, 2, 4, 8
+BF_VARIANT_LEAN, BF_VARIANT_WIDE, BF_VARIANT_FAST, BF_VARIANT_MOMENT, BF_VARIANT_CLASS = 1, 2, 4, 8, 16
 
 
 class bf_rfilter(C.Structure):
@@ -156,6 +158,7 @@ EXPORTED_SYMBOLS = [
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
     "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
     "bf_render_converge_device", "bf_render_converge", "bf_converge_statistic_device",
+    "bf_scene_set_classes", "bf_scene_launch_channels",
 ]
 
 _lib = None
@@ -199,6 +202,9 @@ def load_library(path=None):
     lib.bf_scene_transform_meshes.argtypes = [vp, C.c_uint32, vp, vp]
     lib.bf_launch_channels.argtypes = [C.POINTER(bf_launch)]
     lib.bf_launch_channels.restype = C.c_uint32
+    lib.bf_scene_set_classes.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp]
+    lib.bf_scene_launch_channels.argtypes = [vp, C.POINTER(bf_launch)]
+    lib.bf_scene_launch_channels.restype = C.c_uint32
     lib.bf_render_device.argtypes = [vp, C.POINTER(bf_launch), vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_render.argtypes = [vp, C.POINTER(bf_launch), vp, vp, C.POINTER(bf_stats)]
     lib.bf_scene_flush.argtypes = [vp, vp, C.POINTER(bf_stats)]
@@ -417,6 +423,18 @@ def converge_statistic(hist, lp, floor=0.01):
         rel = np.where(mean != 0.0, np.sqrt(var) / np.abs(mean), np.inf)
     rel = np.where(np.broadcast_to(n < 2.0, rel.shape), np.inf, rel)
     return float(rel[sig].max()), n_sig
+
+
+def split_classes(hist, launch, n_classes, lib=None):
+    """A BF_FLAG_CLASSES histogram ([classes * channels], or [..., classes * channels] of a batch) as a view of shape
+    [..., n_classes, channels]: block k is the plain layout of `launch` (bf_launch_channels) for the paths of class k."""
+    lib = lib or load_library()
+    n = lib.bf_launch_channels(C.byref(launch))
+    hist = np.asarray(hist)
+    n_classes = int(n_classes)
+    if n_classes < 1 or hist.shape[-1] != n_classes * n:
+        raise ValueError(f"a histogram of {hist.shape[-1]} floats per render is not {n_classes} classes x {n} channels")
+    return hist.reshape(hist.shape[:-1] + (n_classes, n))
 
 
 def shard_range(n_paths, shard, n_shards, lib=None):
@@ -677,7 +695,26 @@ class Scene:
         return i
 
     def channels(self, launch):
-        return self.lib.bf_launch_channels(C.byref(launch))
+        """bf_scene_launch_channels: floats one render of `launch` writes on this handle (bf_launch_channels, times the handle's
+        number of classes under BF_FLAG_CLASSES)."""
+        return self.lib.bf_scene_launch_channels(self.handle, C.byref(launch))
+
+    def set_classes(self, shape_class, n_classes=None, miss_class=0, stream=0):
+        """bf_scene_set_classes: shape_class[s] is the class of the paths whose first intersection is shape s (rectangles
+        included), miss_class the class of the paths whose first ray leaves the scene; n_classes=None: the largest class
+        named + 1.  Stream-ordered; BF_FLAG_CLASSES renders then write [n_classes, channels] (split_classes)."""
+        sc = np.ascontiguousarray(shape_class, dtype=np.uint32).reshape(-1)
+        n_shapes = self.info().n_shapes
+        if sc.size != n_shapes:
+            raise ValueError(f"shape_class has {sc.size} entries, the scene {n_shapes} shapes")
+        if n_classes is None:
+            n_classes = max(int(sc.max()) if sc.size else 0, int(miss_class)) + 1
+        check(self.lib, self.lib.bf_scene_set_classes(self.handle, int(n_classes), _ptr(sc), int(miss_class), _stream(stream)),
+              "bf_scene_set_classes")
+
+    def clear_classes(self, stream=0):
+        """bf_scene_set_classes with n_classes = 0: the handle has no class table again."""
+        check(self.lib, self.lib.bf_scene_set_classes(self.handle, 0, None, 0, _stream(stream)), "bf_scene_set_classes")
 
     def render(self, launch, records=False):
         """bf_render: host histogram float32[channels] (+ per-path records, stats)."""

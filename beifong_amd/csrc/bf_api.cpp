@@ -187,6 +187,13 @@ uint32_t bf_launch_channels(const bf_launch *lp) {
     return 0;
 }
 
+uint32_t bf_scene_launch_channels(const bf_scene *scene, const bf_launch *lp) {
+    const uint32_t n = bf_launch_channels(lp);
+    if (!scene || !lp || !(lp->flags & BF_FLAG_CLASSES)) return n;
+    const uint64_t all = (uint64_t) n * std::max(1u, bfd::scene_n_classes(scene->d));
+    return all > UINT32_MAX ? 0u : (uint32_t) all;      // (0: as for an unknown mode; check_launch refuses such a launch by name)
+}
+
 bf_status bf_scene_destroy(bf_scene *s) {
     if (!s) return BF_OK;
     // kernels of this handle that are still in flight read the arrays freed below (an open rolling sequence is simply
@@ -918,6 +925,50 @@ bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, 
     return mark_last(scene, stream);
 }
 
+// The handle's class table (BF_FLAG_CLASSES): shape_class[n_shapes] in a device array of the handle's own, allocated at the first call and
+// rewritten in stream order through the staging ring; the array's address, the number of classes and the miss class travel in the
+// kernel arguments (bf_device.h: DScene::class_lo / class_hi / class_info), which every later render of the handle reads.
+bf_status bf_scene_set_classes(bf_scene *scene, uint32_t n_classes, const uint32_t *shape_class, uint32_t miss_class, void *stream_) {
+    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_set_classes: null scene");
+    const uint32_t n_shapes = scene->info.n_shapes;
+    if (n_classes > BF_MAX_CLASSES) return fail(BF_ERR_INVALID, "bf_scene_set_classes: n_classes %u exceeds BF_MAX_CLASSES (%u)", n_classes, (unsigned) BF_MAX_CLASSES);
+    if (n_classes) {
+        if (n_shapes && !shape_class) return fail(BF_ERR_INVALID, "bf_scene_set_classes: shape_class is null");
+        if (miss_class >= n_classes) return fail(BF_ERR_INVALID, "bf_scene_set_classes: miss_class %u is not below n_classes %u", miss_class, n_classes);
+        for (uint32_t i = 0; i < n_shapes; ++i)
+            if (shape_class[i] >= n_classes)
+                return fail(BF_ERR_INVALID, "bf_scene_set_classes: shape_class[%u] = %u is not below n_classes %u", i, shape_class[i], n_classes);
+    }
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    // an open rolling sequence ends here (its renders were issued without classes; the table is not theirs to see change)
+    bf_status st = order_after_last(scene, stream);
+    if (st == BF_OK) st = close_sequence(scene, stream);
+    if (st != BF_OK) return st;
+    if (!n_classes) {
+        scene->d.class_info = 0u;      // (the device array stays with the handle)
+        return BF_OK;
+    }
+    uint32_t *dev = const_cast<uint32_t *>(bfd::scene_classes(scene->d));
+    if (!dev) {
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, sizeof(uint32_t) * std::max(1u, n_shapes)));
+        scene->owned.push_back(p);
+        dev = (uint32_t *) p;
+        scene->d.class_lo = (uint32_t) (uintptr_t) dev;
+        scene->d.class_hi = (uint32_t) ((uint64_t) (uintptr_t) dev >> 32);
+    }
+    if (n_shapes) {
+        bf_scene::Stage *stg = nullptr;
+        if ((st = stage_acquire(scene, sizeof(uint32_t) * n_shapes, &stg)) != BF_OK) return st;
+        std::memcpy(stg->host, shape_class, sizeof(uint32_t) * n_shapes);
+        HIP_TRY(hipMemcpyAsync(dev, stg->host, sizeof(uint32_t) * n_shapes, hipMemcpyHostToDevice, stream));
+        if ((st = stage_release_after(stg, stream)) != BF_OK) return st;
+    }
+    scene->d.class_info = n_classes | (miss_class << 16);
+    return mark_last(scene, stream);
+}
+
 bf_status bf_scene_read_bvh(const bf_scene *scene, uint32_t width, void *nodes_out, uint64_t nodes_bytes, float *tri_rows_out, int32_t *root_child) {
     if (!scene) return fail(BF_ERR_INVALID, "bf_scene_read_bvh: null scene");
     if (width != 4u && width != 16u) return fail(BF_ERR_INVALID, "bf_scene_read_bvh: width %u (4 or 16)", width);
@@ -995,6 +1046,13 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
     if ((st = dup(src->d.shapes, sizeof(bfd::DShape) * src->info.n_shapes, (const void **) &sc->d.shapes)) != BF_OK) return fail_out(st);
     if ((st = dup(src->d.materials, sizeof(bfd::DMaterial) * src->n_materials, (const void **) &sc->d.materials)) != BF_OK) return fail_out(st);
     if ((st = dup(src->d.sensor, sizeof(bfd::DSensor), (const void **) &sc->d.sensor)) != BF_OK) return fail_out(st);
+    {   // the class table (bf_scene_set_classes): the clone's own copy; class_info came with src->d
+        const void *p = nullptr;
+        if ((st = dup(bfd::scene_classes(src->d), sizeof(uint32_t) * std::max(1u, src->info.n_shapes), &p)) != BF_OK) return fail_out(st);
+        sc->d.class_lo = (uint32_t) (uintptr_t) p;
+        sc->d.class_hi = (uint32_t) ((uint64_t) (uintptr_t) p >> 32);
+        if (!p) sc->d.class_info = 0u;
+    }
     // emitters carry device pointers to their phased-array tables: duplicate the tables and re-point the records
     std::vector<bfd::DEmitter> em(src->d.n_emitters);
     if (!em.empty()) {
@@ -1207,6 +1265,9 @@ bf_status bf_allreduce_device(const int *devices, uint32_t n_devices, float *con
 bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, const bf_launch *launch, float *const *hist_dev,
                                    void *const *streams, bf_stats *stats_out) {
     if (!scenes || !launch || !hist_dev || n_devices == 0) return fail(BF_ERR_INVALID, "bf_render_sharded_device: null argument");
+    if (launch->flags & BF_FLAG_CLASSES)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded_device: BF_FLAG_CLASSES is not supported (the shards' handles each carry a class table "
+                                        "of their own; render the classes per device)");
     std::vector<int> devices(n_devices);
     for (uint32_t g = 0; g < n_devices; ++g) {
         if (!scenes[g] || !hist_dev[g]) return fail(BF_ERR_INVALID, "bf_render_sharded_device: scene / histogram %u is null", g);
@@ -1302,6 +1363,9 @@ bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, 
 
 bf_status bf_render_sharded(bf_scene *const *scenes, uint32_t n_devices, const bf_launch *launch, float *hist_out, bf_stats *stats_out) {
     if (!scenes || !launch || !hist_out || n_devices == 0) return fail(BF_ERR_INVALID, "bf_render_sharded: null argument");
+    if (launch->flags & BF_FLAG_CLASSES)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded: BF_FLAG_CLASSES is not supported (the shards' handles each carry a class table of "
+                                        "their own; render the classes per device)");
     if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "bf_render_sharded: host-buffer renders are synchronous (no BF_FLAG_ROLLING)");
     const uint64_t n = bf_launch_channels(launch);
     if (n == 0) return fail(BF_ERR_INVALID, "unknown mode");
@@ -1348,7 +1412,7 @@ static bf_status render_host_with(const bf_scene *scene, const bf_launch *launch
                                   bf_path_record *records_out, bf_stats *stats_out, Run &&run) {
     if (!scene || !launch || !hist_out) return fail(BF_ERR_INVALID, "null argument");
     if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
-    const uint64_t nchan = (uint64_t) bf_launch_channels(launch) * n_renders, n_rec = launch->n_paths * n_renders;
+    const uint64_t nchan = (uint64_t) bf_scene_launch_channels(scene, launch) * n_renders, n_rec = launch->n_paths * n_renders;
     if (nchan == 0) return fail(BF_ERR_INVALID, "unknown mode");
     DeviceGuard on_device(scene->device);      // the staging buffers live where the kernels run, whatever the caller's current device
     float *d_hist = nullptr;

@@ -93,7 +93,10 @@ struct DEmitter {
 //             (path_scene below) — per-lane pointers, so geometry reads of the root node become vector loads
 //   kMoment   the launch carries second moments (BF_FLAG_MOMENT; chosen by the host through the *_moment launchers): film_put adds nested.XYZ and the square of every
 //             first-moment addend (the channel layout at the flag in beifong_hip.h); every other variant has none of that code
-constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64;
+//   kClass    the launch splits its histogram by the class of each path's first intersection (BF_FLAG_CLASSES; chosen by the host through
+//             the *_class launchers): the path state carries the class (PathState::cls, WF::cls), hist_dst adds the class block's offset
+//             and the 1 x 1 film's base channels take the per-cell route of a W x H film; every other variant has none of that code
+constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64, kClass = 128;
 // rare<V>(c): a condition the lean profile guarantees to be false
 template <int V> __device__ __forceinline__ constexpr bool rare(bool c) { return (V & kLean) ? false : c; }
 
@@ -141,12 +144,17 @@ struct DScene {
     uint32_t spill_stride;
     uint32_t stack_need;      // BVH4::stack_need: kernels whose LDS stack holds that many entries compile the overflow path out
     float c, lambda_min, lambda_max;   // MTS_C, MTS_WAVELENGTH_MIN/MAX as run-time physics
+    // The class table of the handle (bf_scene_set_classes; read by the kClass kernels alone).  The three words sit in what was the
+    // struct's padding — before wnodes, before sensor, at its end — so the other kernels' argument layout stays as it was; that is
+    // also why the device pointer to shape_class[n_shapes] travels as two halves (scene_classes below)
+    uint32_t class_lo;
     // sixteen-wide collapse of the same tree (bf_bvh.h: Node16, 32 float4 per node) for the tail kernel's row traversal;
     // nullptr when the scene has no triangles or its worst-case stack exceeds kWideStack
     const float4 *wnodes;
     int32_t wroot;
     uint32_t n_wnodes;
     uint32_t wrows_log;       // log2 of the most rows a gang may have: 16 * rows * depth stack entries must fit kWideStack
+    uint32_t class_hi;        // (class_lo above)
     const DSensor *sensor;    // device copy (kept out of the kernel arguments: 44 dwords of scalar registers)
     // LDS copies of the tables a vertex reads through a PER-LANE index (its material; the rectangle it hit): wf_shade and the
     // tail kernel copy them behind their histogram when the scene is small enough (tab_cache, set by the host, reserves
@@ -155,7 +163,11 @@ struct DScene {
     uint32_t tab_cache;       // host: 1 = n_materials <= kTabMaxMaterials and n_rects <= kTabMaxRects
     uint32_t tab_on;          // device only: the tables are in LDS at byte offsets lds_mat / lds_rect of the dynamic segment
     uint32_t lds_mat, lds_rect;
+    uint32_t class_info;      // n_classes | miss_class << 16; 0: the handle has no class table
 };
+static_assert(sizeof(DScene) == 184 && offsetof(DScene, class_lo) == 124 && offsetof(DScene, wnodes) == 128 && offsetof(DScene, class_hi) == 148 &&
+                  offsetof(DScene, sensor) == 152 && offsetof(DScene, class_info) == 180,
+              "DScene is a kernel argument: the class words fill its padding, nothing moves");
 constexpr uint32_t kTabMaxMaterials = 16, kTabMaxRects = 8;
 constexpr uint32_t kRectDwords = sizeof(DRect) / 4;       // 39: an odd stride, lanes at different rectangles fall into different banks
 constexpr uint32_t kTabBytes = (kTabMaxMaterials * 48u + kTabMaxRects * (uint32_t) sizeof(DRect) + 15u) & ~15u;
@@ -176,6 +188,12 @@ __device__ __forceinline__ CRect *c_rects(const DScene &sc) { return as_const(sc
 __device__ __forceinline__ CShape *c_shapes(const DScene &sc) { return as_const(sc.shapes); }
 __device__ __forceinline__ CEmitter *c_emitters(const DScene &sc) { return as_const(sc.emitters); }
 __device__ __forceinline__ CSensor &c_sensor(const DScene &sc) { return *as_const(sc.sensor); }
+// the class table: shape_class[n_shapes] on the device, the number of classes, the class of a path whose first ray leaves the scene
+__host__ __device__ __forceinline__ const uint32_t *scene_classes(const DScene &sc) {
+    return (const uint32_t *) (uintptr_t) (((uint64_t) sc.class_hi << 32) | sc.class_lo);
+}
+__host__ __device__ __forceinline__ uint32_t scene_n_classes(const DScene &sc) { return sc.class_info & 0xffffu; }
+__host__ __device__ __forceinline__ uint32_t scene_miss_class(const DScene &sc) { return sc.class_info >> 16; }
 
 // One render of a ROLLING SEQUENCE (bf_render_device with BF_FLAG_ROLLING): what differs between the renders of a
 // sequence.  The sequence is one batched launch whose path supply grows by one render per call: global path index
@@ -219,7 +237,7 @@ struct DLaunch {
     int32_t max_depth, rr_depth;
     uint32_t bins, bins_y, phase_bins;
     float bin_width, time_c;
-    uint32_t n_chan;
+    uint32_t n_chan;          // floats of one histogram block (bf_launch_channels): a class launch writes n_classes such blocks per render
     uint32_t lds_hist;        // 1: histogram privatised in LDS
     uint32_t iq;              // 1: BF_MODE_RECEIVE_IQ (mode is RECEIVE_RAW inside the kernels): contributions are phasors
     uint32_t film_w, film_h;  // render modes: film size in pixels (>= 1)
@@ -229,7 +247,7 @@ struct DLaunch {
     // n_paths = batch * batch_paths global path indices g; render k = g / batch_paths renders its local path
     // g - k * batch_paths with seed batch_seeds[k] into g_hist + k * n_chan, its meshes shifted by batch_offsets[k].
     uint32_t batch;                 // 0: a plain launch
-    uint32_t n_chan_all;            // batch * n_chan (the LDS-privatised histogram covers all renders when it fits)
+    uint32_t n_chan_all;            // batch * n_chan (x n_classes in a class launch): the LDS-privatised histogram covers all renders when it fits
     uint64_t batch_paths;
     const uint64_t *batch_seeds;    // device [batch], or nullptr: `seed` for every render (common random numbers)
     const float4 *batch_offsets;    // device [batch] (x, y, z, -), or nullptr: meshes as built

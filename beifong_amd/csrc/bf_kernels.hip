@@ -124,7 +124,7 @@ __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DSce
             const uint32_t got = cursor_take(rcur, (uint32_t) __popcll(need), !alive && !done, rank, slot, lane);
             if (!alive && !done) {
                 if (rank < got) {
-                    load_state(wf, slot, receive, s);
+                    load_state(wf, slot, receive, s, (kRX & kClass) != 0);
                     regen_ok = slot < wf.n_main;
                     alive = true;
                     need_closest = false;          // traced (and counted) by wf_trace already
@@ -550,10 +550,10 @@ __global__ __launch_bounds__(kBlock) void bf_trace_kernel(DScene sc, uint64_t n,
 BF_NS_END  // namespace bfd
 
 // host-callable launchers (used by bf_api.cpp, bf_render.cpp and bf_mesh.cpp, which are plain C++)
-// moment: the kMoment variants (BF_FLAG_MOMENT; the *_moment launchers below)
+// moment: the kMoment variants (BF_FLAG_MOMENT; the *_moment launchers below); classed: the kClass variants (BF_FLAG_CLASSES; *_class)
 static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
                                 unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream,
-                                bool moment) {
+                                bool moment, bool classed = false) {
     bfd::WF none;
     memset(&none, 0, sizeof(none));
     const bool spill = sc->stack_need > (uint32_t) bfd::kStackDepth;
@@ -579,8 +579,29 @@ static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, f
 #undef BF_RENDER_MOM2
         return hipGetLastError();
     }
+    if (classed) {
+        // BF_FLAG_CLASSES (never with BF_FLAG_FAST or BF_FLAG_MOMENT): the kClass variants of the forms below
+#define BF_RENDER_CLS2(S, P, V)                                                                                                       \
+    hipLaunchKernelGGL((bfd::bf_render_kernel<S, false, P, BF_TAIL_WAVES, bfd::kClass | (V)>), dim3(grid), dim3(bfd::kBlock), lds_bytes, \
+                       stream, *sc, *lp, g_hist, records, counters, none, 0u)
+#define BF_RENDER_CLS(S, P)                                                                   \
+    if (lp->geom_stride && lp->wide) BF_RENDER_CLS2(S, P, bfd::kWide | bfd::kGeom);           \
+    else if (lp->geom_stride) BF_RENDER_CLS2(S, P, bfd::kGeom);                               \
+    else if (lp->wide) BF_RENDER_CLS2(S, P, bfd::kWide);                                      \
+    else BF_RENDER_CLS2(S, P, 0)
+        if (stats) {
+            if (spill) { BF_RENDER_CLS(true, true); }
+            else { BF_RENDER_CLS(true, false); }
+        } else {
+            if (spill) { BF_RENDER_CLS(false, true); }
+            else { BF_RENDER_CLS(false, false); }
+        }
+#undef BF_RENDER_CLS
+#undef BF_RENDER_CLS2
+        return hipGetLastError();
+    }
 #else
-    if (moment) return hipErrorInvalidValue;
+    if (moment || classed) return hipErrorInvalidValue;
 #endif
 #define BF_RENDER_LAUNCH(S, R, P, WF_, IT_)                                                                                              \
     if (lp->wide)                                                                                                                        \
@@ -627,7 +648,7 @@ static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, f
 //   block_cap  : at most this many workgroups (0: no cap)
 static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, uint32_t n_slots,
                               float *g_hist, bf_path_record *records, int stats, size_t lds_bytes, hipStream_t stream,
-                              int tail_waves, unsigned spread, unsigned block_cap, bool moment) {
+                              int tail_waves, unsigned spread, unsigned block_cap, bool moment, bool classed = false) {
     // one lane per live slot (gathered from the alive masks), at most one thread per pool slot
     // (any grid finishes the job: waves loop over their segment of the alive masks; the cap keeps the
     // launch within the scene's traversal-spill columns)
@@ -667,8 +688,30 @@ static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, con
 #undef BF_TAIL_MOM2
         return hipGetLastError();
     }
+    if (classed) {
+        // BF_FLAG_CLASSES: the kClass variants of the general forms (a lean scene runs the general kernel), three waves per SIMD
+        if (lp->multi || lp->roll) return hipErrorInvalidValue;
+#define BF_TAIL_CLS2(S, P, V)                                                                                                         \
+    hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kClass | (V)>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, \
+                       *lp, g_hist, records, counters, *wf, it)
+#define BF_TAIL_CLS(S, P)                                                                     \
+    if (lp->geom_stride && lp->wide) BF_TAIL_CLS2(S, P, bfd::kWide | bfd::kGeom);             \
+    else if (lp->geom_stride) BF_TAIL_CLS2(S, P, bfd::kGeom);                                 \
+    else if (lp->wide) BF_TAIL_CLS2(S, P, bfd::kWide);                                        \
+    else BF_TAIL_CLS2(S, P, 0)
+        if (stats) {
+            if (spill) { BF_TAIL_CLS(true, true); }
+            else { BF_TAIL_CLS(true, false); }
+        } else {
+            if (spill) { BF_TAIL_CLS(false, true); }
+            else { BF_TAIL_CLS(false, false); }
+        }
+#undef BF_TAIL_CLS
+#undef BF_TAIL_CLS2
+        return hipGetLastError();
+    }
 #else
-    if (moment) return hipErrorInvalidValue;
+    if (moment || classed) return hipErrorInvalidValue;
 #endif
 #define BF_TAIL_LAUNCH(S, P)                                                                                                           \
     if (lp->geom_stride && lp->wide)                                                                                                   \
@@ -725,6 +768,16 @@ extern "C" hipError_t bfk_launch_tail_moment(const bfd::DScene *sc, const bfd::D
                                              uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
                                              hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
     return tail_launch(sc, lp, wf, it, n_slots, g_hist, records, stats, lds_bytes, stream, tail_waves, spread, block_cap, true);
+}
+extern "C" hipError_t bfk_launch_render_class(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+                                              unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
+                                              hipStream_t stream) {
+    return render_launch(sc, lp, g_hist, records, counters, stats, grid, lds_bytes, stream, false, true);
+}
+extern "C" hipError_t bfk_launch_tail_class(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
+                                            uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
+                                            hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
+    return tail_launch(sc, lp, wf, it, n_slots, g_hist, records, stats, lds_bytes, stream, tail_waves, spread, block_cap, false, true);
 }
 #endif
 

@@ -427,7 +427,7 @@ bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
                           bf_path_record *records_dev, void *stream_, bf_stats *stats_out, const char *fn, Prepare &&prepare) {
     MeshState &m = scene->mesh;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const uint64_t n_chan = bf_launch_channels(launch);
+    const uint64_t n_chan = bf_scene_launch_channels(scene, launch);      // floats per render (x n_classes under BF_FLAG_CLASSES)
     const MotionLayout L = motion_layout(scene->d);
     if (L.rows > UINT32_MAX)
         return fail(BF_ERR_UNSUPPORTED, "%s: one geometry version of this scene is %zu float4 rows (at most 2^32 - 1)", fn, L.rows);
@@ -877,6 +877,8 @@ bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch
     if (st != BF_OK) return st;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
+    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
+    if ((st = check_classes(scene, launch, n_renders)) != BF_OK) return st;
     if (scene->d.n_tris == 0) {
         // nothing to move: an ordinary batch
         bf_batch b = {n_renders, seeds, nullptr};
@@ -939,6 +941,8 @@ bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch
     if (st != BF_OK) return st;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
+    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
+    if ((st = check_classes(scene, launch, n_renders)) != BF_OK) return st;
     if (scene->d.n_tris == 0) {
         bf_batch b = {n_renders, seeds, nullptr};
         return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);

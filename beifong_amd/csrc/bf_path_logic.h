@@ -43,9 +43,11 @@ struct PathState {
     float lambda0;       // ray.wavelengths[0] in nm
     float phase;         // ray.phase of the working ray: last traced segment only (ray.h:89-93, interaction.h:61-64)
     float dlambda;       // BF_FLAG_DOPPLER: what the Doppler hook has added to the caller's ray.wavelengths[0] (nm)
+    uint32_t cls;        // kClass: shape_class of the path's first intersection, miss_class until then (the other variants never touch it: no register)
 };
 
-BF_DEV void load_state(const WF &wf, uint32_t i, bool receive, PathState &s) {
+// `classed`: a compile-time constant at every call site ((V & kClass) != 0)
+BF_DEV void load_state(const WF &wf, uint32_t i, bool receive, PathState &s, bool classed = false) {
     float4 r0 = wf.ray0(i), r1 = wf.ray1(i), a = wf.sa(i), bb = wf.sb(i);
     uint4 d = wf.sd(i);
     s.ro = mk(r0.x, r0.y, r0.z);
@@ -66,6 +68,7 @@ BF_DEV void load_state(const WF &wf, uint32_t i, bool receive, PathState &s) {
     s.time = s.t_rx = s.lambda0 = s.phase = 0.f;
     s.render = wf.has_render ? wf.render(i) : 0u;
     s.dlambda = wf.has_dop ? wf.dop(i) : 0.f;
+    if (classed) s.cls = wf.cls(i);
     if (receive) {
         float4 e = wf.se(i);
         s.time = e.x;
@@ -74,7 +77,7 @@ BF_DEV void load_state(const WF &wf, uint32_t i, bool receive, PathState &s) {
         s.phase = e.w;
     }
 }
-BF_DEV void store_state(const WF &wf, uint32_t j, bool receive, const PathState &s) {
+BF_DEV void store_state(const WF &wf, uint32_t j, bool receive, const PathState &s, bool classed = false) {
     wf.ray0(j) = make_float4(s.ro.x, s.ro.y, s.ro.z, s.rmint);
     wf.ray1(j) = make_float4(s.rd.x, s.rd.y, s.rd.z, s.rmaxt);
     wf.sa(j) = make_float4(s.throughput, s.eta, s.emission_weight, s.result);
@@ -84,6 +87,7 @@ BF_DEV void store_state(const WF &wf, uint32_t j, bool receive, const PathState 
     if (receive) wf.se(j) = make_float4(s.time, s.t_rx, s.lambda0, s.phase);
     if (wf.has_render) wf.render(j) = s.render;
     if (wf.has_dop) wf.dop(j) = s.dlambda;
+    if (classed) wf.cls(j) = s.cls;
 }
 // Shape::doppler — src/librender/shape.cpp:375-389 (call sites commented out at the reference's HEAD:
 // pathtimefrequency.cpp:141-144, 180-183): 2 dot(si.wi, m_velocity * Point3f(si.to_local(si.p))) / MTS_C * wavelength
@@ -516,6 +520,7 @@ template <int RX = 2> BF_DEV void generate_path(const DScene &sc0, const DLaunch
     const bool receive = mode_receive<RX>(lp);
     s.path_i = path_i;
     s.render = 0u;
+    if (RX & kClass) s.cls = scene_miss_class(sc0);      // until the first intersection says otherwise (a slot's previous path leaves nothing behind)
     uint64_t seed = lp.seed, path_offset = lp.path_offset;
     if (lp.batch != 0u) {
         // batched launch: global index -> (render, local path); every render is an ordinary render of its own seed
@@ -684,6 +689,7 @@ BF_DEV bool shade_vertex(const DScene &sc0, const DLaunch &lp, PathState &s, con
         // first intersection — path.cpp:115-117, pathlength.cpp:138-146,
         // pathtime.cpp:136-140, pathtimefrequency.cpp:131-153
         if (si_valid) s.flags |= kFlagValid;
+        if ((RX & kClass) && si_valid) s.cls = scene_classes(sc)[si.shape];      // the class of the path: its first intersection's shape
         if (is_range) s.aux += si_valid ? si.t : 0.f;
         if (is_time) s.aux = si_valid ? si.t / lp.time_c : 0.f;
         if (si_valid && doppler) s.dlambda += shape_doppler(sc, si, s.lambda0);   // :141-144
@@ -853,19 +859,21 @@ BF_DEV void hist_add(float *s_hist, float *g_hist, bool lds, uint32_t idx, float
 }
 // Where the samples of render `render` go: plain launch = the histogram; batched launch = block `render` of it (LDS and
 // global alike); rolling sequence = the render's own histogram (DRoll::hist), privatised in LDS only for the newest
-// kRollWindow renders (the few stragglers of older renders take global atomics).
+// kRollWindow renders (the few stragglers of older renders take global atomics).  Class launches (kClass; never rolling): block `cls`
+// of the render's n_cls blocks, [render][class][n_chan]; n_cls = 0 elsewhere.
 struct HistDst {
     float *s, *g;
     bool lds;
 };
-BF_DEV HistDst hist_dst(const DLaunch &lp, uint32_t render, float *s_hist, float *g_hist, bool lds_hist) {
+BF_DEV HistDst hist_dst(const DLaunch &lp, uint32_t render, float *s_hist, float *g_hist, bool lds_hist, uint32_t n_cls = 0u, uint32_t cls = 0u) {
     HistDst h;
     if (lp.roll) {
         h.lds = lds_hist && render >= lp.roll_lo;
         h.g = h.lds ? nullptr : lp.roll[render & (kRollRing - 1u)].hist;      // (no descriptor fetch for the samples that stay in LDS)
         h.s = s_hist + (h.lds ? (render - lp.roll_lo) * lp.n_chan : 0u);
     } else {
-        const uint32_t hb = lp.batch != 0u ? render * lp.n_chan : 0u;
+        uint32_t hb = lp.batch != 0u ? render * lp.n_chan : 0u;
+        if (n_cls) hb = hb * n_cls + cls * lp.n_chan;
         h.g = g_hist + hb;
         h.s = s_hist + hb;
         h.lds = lds_hist;
@@ -1008,7 +1016,9 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
     ++acc.n_put;
     float rec_L, rec_aux;
     float *const s_base = s_hist + lp.base_off;                               // rolling launches: base-channel table (DLaunch::base_off)
-    const HistDst hd = hist_dst(lp, s.render, s_hist, g_hist, lds_hist);      // this render's block of the histogram
+    constexpr bool classed = (RX & kClass) != 0;   // BF_FLAG_CLASSES: one histogram block per class of the path's first intersection
+    // this render's block of the histogram (classed: the block of the path's class within it)
+    const HistDst hd = hist_dst(lp, s.render, s_hist, g_hist, lds_hist, classed ? scene_n_classes(sc0) : 0u, classed ? s.cls : 0u);
     s_hist = hd.s;
     g_hist = hd.g;
     lds_hist = hd.lds;
@@ -1145,8 +1155,9 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
         // keeps the five base channels in registers until film_flush
         uint32_t pix = 0u;
         // the five base channels of a 1 x 1 film are summed in registers while every lane of the wave feeds the same
-        // histogram: a plain launch, or the newest render of a rolling sequence
-        const bool use_acc = lp.batch == 0u || (lp.roll != nullptr && s.render == lp.roll_newest);
+        // histogram: a plain launch, or the newest render of a rolling sequence.  Never in a class launch: the lanes' paths belong to
+        // different class blocks, so the base channels go cell by cell like a W x H film's (the class is one more film axis)
+        const bool use_acc = !classed && (lp.batch == 0u || (lp.roll != nullptr && s.render == lp.roll_newest));
         if (rare<RX>(lp.spp != 0u)) {
             const uint64_t q = (lp.path_offset + s.path_i) / lp.spp;
             const uint32_t px = (uint32_t) (q % lp.film_w) - ((s.flags & kFlagFilmLeft) ? 1u : 0u);
@@ -1232,6 +1243,12 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 float *bs = s_hist;
                 bool bl = lds_hist;
                 uint32_t bn = nch, bq = qch;       // kMoment: where nested.XYZ and their squares go (the table keeps its eleven entries together)
+                // a class launch too large for an LDS histogram: every wave would hit the same five GLOBAL addresses per class, so
+                // the base channels go through the workgroup's class table [render][class][5] (DLaunch::lds_floats; film_flush adds it up)
+                if (classed && !lds_hist && lp.lds_floats != 0u) {
+                    bs = s_base + kRollBaseCh * ((lp.batch != 0u ? s.render * scene_n_classes(sc0) : 0u) + s.cls);
+                    bl = true;
+                }
                 if (lp.roll && !lds_hist && lp.roll_newest - s.render < kRollBase) {
                     bs = s_base + (mom ? kRollBaseChMoment : kRollBaseCh) * (lp.roll_newest - s.render);
                     bl = true;
@@ -1338,6 +1355,7 @@ template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, fl
                 acc.qZ += __shfl_down(acc.qZ, off);
             }
         }
+        // (kClass: film_put has written the base channels already, acc.W is 0)
         if (lane == 0 && acc.W != 0.f && !lp.spp && (lp.batch == 0u || lp.roll != nullptr)) {
             const HistDst hd = hist_dst(lp, lp.roll ? lp.roll_newest : 0u, s_hist, g_hist, lds_hist);
             hist_add(hd.s, hd.g, hd.lds, 0, acc.X);
@@ -1374,6 +1392,15 @@ template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, fl
                 float v = s_hist[i];
                 if (v != 0.f) glb_add(g_hist + i, v);
             }
+        }
+    }
+    if ((RX & kClass) && !lds_hist && lp.lds_floats != 0u) {
+        // the class table of a launch without an LDS histogram (film_put): entry [render][class][channel] -> the block's base channels
+        __syncthreads();
+        for (uint32_t i = tid; i < lp.lds_floats; i += kBlock) {
+            const float v = s_hist[i];
+            const uint32_t blk = i / kRollBaseCh;
+            if (v != 0.f) glb_add(g_hist + (size_t) blk * lp.n_chan + (i - kRollBaseCh * blk), v);
         }
     }
     if (lp.roll && !mode_receive<RX>(lp)) {

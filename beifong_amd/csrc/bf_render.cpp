@@ -11,8 +11,8 @@
 #include <vector>
 
 // The launchers of bf_kernels.hip / bf_wavefront.hip a render goes through, once per build of the kernels: the exact one (no suffix),
-// the fast-arithmetic one (_fast, BF_FLAG_FAST: bf_ns.h) and the second-moment variants (_moment, BF_FLAG_MOMENT; bf_device.h: kMoment;
-// exact build only, same wf_trace)
+// the fast-arithmetic one (_fast, BF_FLAG_FAST: bf_ns.h), the second-moment variants (_moment, BF_FLAG_MOMENT; bf_device.h: kMoment;
+// exact build only, same wf_trace) and the class variants (_class, BF_FLAG_CLASSES; bf_device.h: kClass; likewise)
 #define BF_LAUNCHERS(sfx)                                                                                                                       \
     extern "C" hipError_t bfk_launch_render##sfx(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,         \
                                                  unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream); \
@@ -25,13 +25,15 @@
 BF_LAUNCHERS()
 BF_LAUNCHERS(_fast)
 BF_LAUNCHERS(_moment)
+BF_LAUNCHERS(_class)
 #undef BF_LAUNCHERS
 extern "C" hipError_t bfk_wf_trace(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
 extern "C" hipError_t bfk_wf_trace_fast(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
 extern "C" hipError_t bfk_roll_set(bfd::DRoll *ring, float4 *offsets, uint32_t idx, const bfd::DRoll *d, const float *offset3, hipStream_t stream);
 
 namespace {
-// the kernels one render runs: the exact build, the fast-arithmetic one (BF_FLAG_FAST) or the second-moment variants (BF_FLAG_MOMENT)
+// the kernels one render runs: the exact build, the fast-arithmetic one (BF_FLAG_FAST), the second-moment variants (BF_FLAG_MOMENT) or
+// the class variants (BF_FLAG_CLASSES)
 struct Kernels {
     decltype(&bfk_launch_render) render;
     decltype(&bfk_wf_shade) shade;
@@ -41,8 +43,11 @@ struct Kernels {
 const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail};
 const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast};
 const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment};
-// (BF_FLAG_MOMENT | BF_FLAG_FAST is refused before any kernel is chosen: render_locked)
-const Kernels &kernels_for(uint32_t flags) { return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : kExact); }
+const Kernels kClass = {bfk_launch_render_class, bfk_wf_shade_class, bfk_wf_trace, bfk_launch_tail_class};
+// (BF_FLAG_MOMENT | BF_FLAG_FAST, and BF_FLAG_CLASSES with either, are refused before any kernel is chosen: check_launch)
+const Kernels &kernels_for(uint32_t flags) {
+    return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : ((flags & BF_FLAG_CLASSES) ? kClass : kExact));
+}
 }  // namespace
 
 // ---- RenderState's sub-objects (bf_scene.h) ----
@@ -800,9 +805,29 @@ static bool lean_profile(const bf_scene *scene, const bf_launch *launch, bool re
 static bool receive_mode_of(const bf_launch *launch) { return launch->mode == BF_MODE_RECEIVE_RAW || launch->mode == BF_MODE_RECEIVE_IQ; }
 static bool multi_pixel_of(const bf_launch *launch) { return launch->spp && launch->film_width && launch->film_height; }
 
+// What a BF_FLAG_CLASSES launch (of n_renders renders) is refused for; the motion / deform batches ask before they enqueue their
+// geometry versions, every launch asks again in check_launch
+bf_status check_classes(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders) {
+    if (launch->flags & BF_FLAG_CLASSES) {
+        const uint32_t n_classes = bfd::scene_n_classes(scene->d);
+        if (!n_classes) return fail(BF_ERR_INVALID, "BF_FLAG_CLASSES: the scene has no class table (bf_scene_set_classes)");
+        if (launch->flags & (BF_FLAG_FAST | BF_FLAG_MOMENT))
+            return fail(BF_ERR_INVALID, "BF_FLAG_CLASSES with %s: the class variants exist of the exact first-moment kernels only",
+                        (launch->flags & BF_FLAG_FAST) ? "BF_FLAG_FAST" : "BF_FLAG_MOMENT");
+        if (launch->flags & BF_FLAG_ROLLING)
+            return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_CLASSES with BF_FLAG_ROLLING: a rolling sequence's histogram window and base-channel "
+                                            "table hold one block per render; render the classes without BF_FLAG_ROLLING");
+        if ((uint64_t) n_renders * n_classes * bf_launch_channels(launch) > (1ull << 31))
+            return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_CLASSES: %u renders x %u classes x %u channels is too large", n_renders, n_classes,
+                        bf_launch_channels(launch));
+    }
+    return BF_OK;
+}
+
 // Everything a launch (of n_renders renders, if a batch) is refused for on its own or against the scene and its open rolling sequence:
 // nothing is enqueued before these
 static bf_status check_launch(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, uint32_t n_renders, const bf_stats *stats_out) {
+    if (bf_status cst = check_classes(scene, launch, n_renders)) return cst;
     if (batch) {
         if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
         if (launch->spp && launch->film_width && launch->film_height)
@@ -916,16 +941,26 @@ static bf_status make_dlaunch(const bf_scene *scene, const bf_launch *launch, ui
     scene->run.last_variant = (lp.lean ? (uint32_t) BF_VARIANT_LEAN : 0u) | (lp.wide ? (uint32_t) BF_VARIANT_WIDE : 0u);
     if (launch->flags & BF_FLAG_FAST) scene->run.last_variant |= (uint32_t) BF_VARIANT_FAST;
     if (launch->flags & BF_FLAG_MOMENT) scene->run.last_variant |= (uint32_t) BF_VARIANT_MOMENT;
+    // the class variants exist of the general forms only: a lean scene runs them too, and says so
+    const uint32_t n_classes = (launch->flags & BF_FLAG_CLASSES) ? bfd::scene_n_classes(scene->d) : 0u;
+    if (n_classes) {
+        lp.lean = 0u;
+        scene->run.last_variant = (scene->run.last_variant & ~(uint32_t) BF_VARIANT_LEAN) | (uint32_t) BF_VARIANT_CLASS;
+    }
     lp.count = ((launch->flags & (BF_FLAG_STATS | BF_FLAG_COUNT)) || count) ? 1u : 0u;
     lp.doppler = (receive_mode && (launch->flags & BF_FLAG_DOPPLER)) ? 1u : 0u;
     lp.resample = (receive_mode && scene->any_resample) ? 1u : 0u;
     if (lp.resample && lp.doppler)
         return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_DOPPLER with a resample_freq transmitter: both rewrite the path's wavelength (one slot of path state)");
     lp.mix = (receive_mode && (launch->flags & BF_FLAG_MIX_RESAMPLE)) ? 1u : 0u;
-    lp.n_chan_all = lp.n_chan * n_renders;
+    lp.n_chan_all = lp.n_chan * n_renders * std::max(1u, n_classes);      // [render][class][n_chan]: LDS privatisation is decided on all of it
     lp.geom_stride = geom_stride;
     lp.lds_hist = lds_hist(lp.n_chan_all, launch->flags);
     lp.lds_floats = lp.lds_hist ? lp.n_chan_all : 0u;
+    // a class launch of a 1 x 1 film that cannot privatise its histogram still sums the five base channels of every class block per
+    // workgroup: without that every path of the launch adds to the same 5 n_classes global addresses (tools/class_ab.py: C4)
+    if (n_classes && !lp.lds_hist && !receive_mode && !multi_pixel && (uint64_t) n_renders * n_classes * bfd::kRollBaseCh <= (uint64_t) bfd::kMaxLdsHist)
+        lp.lds_floats = n_renders * n_classes * bfd::kRollBaseCh;
     return BF_OK;
 }
 
@@ -1166,6 +1201,8 @@ bf_status bf_render_converge_device(bf_scene *scene, const bf_launch *launch, fl
     if (launch->flags & BF_FLAG_FAST)
         return fail(BF_ERR_INVALID, "%s BF_FLAG_FAST: the rounds are moment renders, and BF_FLAG_MOMENT | BF_FLAG_FAST is refused", fn);
     if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: the rounds are batches, which do not roll", fn);
+    if (launch->flags & BF_FLAG_CLASSES)
+        return fail(BF_ERR_UNSUPPORTED, "%s BF_FLAG_CLASSES: the rounds are moment renders, which have no class variants (per-class error bars are a follow-up)", fn);
     if (!(target >= 0.f)) return fail(BF_ERR_INVALID, "%s target %g is negative or NaN", fn, (double) target);
     if (!floor_ok(floor)) return fail(BF_ERR_INVALID, "%s floor %g is outside [0, 1]", fn, (double) floor);
     if (round_renders == 0 || max_rounds == 0) return fail(BF_ERR_INVALID, "%s round_renders and max_rounds must be at least 1", fn);
@@ -1238,6 +1275,8 @@ bf_status bf_render_converge(bf_scene *scene, const bf_launch *launch, float tar
                              uint32_t min_rounds, uint32_t max_rounds, float *hist_out, uint32_t *rounds_out,
                              double *stat_history_out, uint64_t *n_significant_out, bf_stats *stats_out) {
     if (!scene || !launch || !hist_out || !rounds_out) return fail(BF_ERR_INVALID, "bf_render_converge: null argument");
+    if (launch->flags & BF_FLAG_CLASSES)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_converge: BF_FLAG_CLASSES: the rounds are moment renders, which have no class variants (per-class error bars are a follow-up)");
     bf_launch lm = *launch;
     lm.flags |= BF_FLAG_MOMENT;
     const size_t bytes = (size_t) bf_launch_channels(&lm) * sizeof(float);

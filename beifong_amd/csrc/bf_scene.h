@@ -353,6 +353,7 @@ bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream);
 bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
 bf_status mark_last(const bf_scene *scene, hipStream_t stream);
 bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
+bf_status check_classes(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders);      // BF_FLAG_CLASSES refusals, before any device work
 bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev, bf_path_record *records_dev,
                         void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0);
 void fill_stats(const bf_scene *scene, const unsigned long long *c, uint64_t n_paths, bf_stats *st);

@@ -31,7 +31,7 @@ constexpr uint32_t kTailSmallPool = 1u << 22;   // pools below this never fill t
 constexpr uint32_t kTailRowJobs = 12;      // tail: up to three passes of four row-traversed rays beat one quad pass of sixteen
 
 // Per-slot state layout: three 64-byte RECORDS per slot,
-//   A = ray0, ray1, hit, (hit_prim, render, dop, -)      what wf_trace reads / writes for a closest-hit ray: ONE line
+//   A = ray0, ray1, hit, (hit_prim, render, dop, cls)    what wf_trace reads / writes for a closest-hit ray: ONE line
 //   B = sa, sb, sd, se                                   the rest of the path state (wf_shade; wf_trace adds a released
 //                                                        NEE contribution to sa.w / se.w)
 //   C = sh0, sh1, (sh2, sh3, -, -), -                    the NEE shadow request
@@ -47,6 +47,8 @@ struct WF {
     BF_HD uint32_t &hit_prim(uint32_t i) const { return reinterpret_cast<uint32_t *>(recA + 4 * (size_t) i + 3)[0]; }
     BF_HD uint32_t &render(uint32_t i) const { return reinterpret_cast<uint32_t *>(recA + 4 * (size_t) i + 3)[1]; }
     BF_HD float &dop(uint32_t i) const { return reinterpret_cast<float *>(recA + 4 * (size_t) i + 3)[2]; }
+    // kClass kernels only (a compile-time switch where has_render / has_dop are run-time ones: the other kernels neither read nor write the word)
+    BF_HD uint32_t &cls(uint32_t i) const { return reinterpret_cast<uint32_t *>(recA + 4 * (size_t) i + 3)[3]; }
     BF_HD float4 &sa(uint32_t i) const { return recB[4 * (size_t) i + 0]; }         // throughput, eta, emission_weight, result
     BF_HD float4 &sb(uint32_t i) const { return recB[4 * (size_t) i + 1]; }         // aux, bs_pdf, depth|flags (bits), n_rays (bits)
     BF_HD uint4 &sd(uint32_t i) const { return reinterpret_cast<uint4 *>(recB)[4 * (size_t) i + 2]; }   // rng state lo/hi, path index lo/hi

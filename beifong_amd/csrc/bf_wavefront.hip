@@ -258,7 +258,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
                     s.path_i = ((uint64_t) d.w << 32) | d.z;
                 }
             } else {
-                load_state(wf, slot, receive, s);
+                load_state(wf, slot, receive, s, (RX & kClass) != 0);
                 ++c_loads;
                 SLP(1, (s.flags & kFlagTermPending) != 0);
                 if (s.flags & kFlagTermPending) {
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
                 wf.hit(dst) = make_float4(hit.t, hit.u, hit.v, __int_as_float(hit.slot));
                 wf.hit_prim(dst) = hit.prim;
             }
-            store_state(wf, dst, receive, s);
+            store_state(wf, dst, receive, s, (RX & kClass) != 0);
             ++c_live;
             if (shadowing) {
                 wf.sh0(dst) = make_float4(sh.o.x, sh.o.y, sh.o.z, sh.mint);
@@ -728,10 +728,10 @@ extern "C" int bfdbg_shade_lane_profile(unsigned long long *out, int clear) {
 }
 #endif
 
-// moment: the kMoment variants (BF_FLAG_MOMENT; bfk_wf_shade_moment below)
+// moment: the kMoment variants (BF_FLAG_MOMENT; bfk_wf_shade_moment below); classed: the kClass variants (BF_FLAG_CLASSES; bfk_wf_shade_class)
 static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                  hipStream_t stream, int waves, bool moment) {
+                                  hipStream_t stream, int waves, bool moment, bool classed = false) {
     // `waves`: register budget of the shading kernel (waves per SIMD); 3 is the sweet spot (168 VGPRs)
     const bool rx = lp->mode == BF_MODE_RECEIVE_RAW;
 #define BF_SHADE_LAUNCH_RX(F, W, RX_)                                                                                              \
@@ -792,8 +792,26 @@ static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp,
     }
 #undef BF_SHADE_LAUNCH_MOM_F
 #undef BF_SHADE_LAUNCH_MOM
+    // BF_FLAG_CLASSES (never with BF_FLAG_FAST, BF_FLAG_MOMENT or a rolling sequence): the kClass variants, three waves per SIMD, of
+    // the general forms only — a lean scene runs the general kernel — with or without per-render geometry and a wide filter
+#define BF_SHADE_LAUNCH_CLS(F, V)                               \
+    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kClass | (V));    \
+    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kClass | (V))
+#define BF_SHADE_LAUNCH_CLS_F(V)                     \
+    if (first) { BF_SHADE_LAUNCH_CLS(1, V); }        \
+    else { BF_SHADE_LAUNCH_CLS(0, V); }
+    if (classed) {
+        if (first >= 2 || lp->multi || lp->roll) return hipErrorInvalidValue;
+        if (lp->geom_stride && lp->wide) { BF_SHADE_LAUNCH_CLS_F(bfd::kGeom | bfd::kWide) }
+        else if (lp->geom_stride) { BF_SHADE_LAUNCH_CLS_F(bfd::kGeom) }
+        else if (lp->wide) { BF_SHADE_LAUNCH_CLS_F(bfd::kWide) }
+        else { BF_SHADE_LAUNCH_CLS_F(0) }
+        return hipGetLastError();
+    }
+#undef BF_SHADE_LAUNCH_CLS_F
+#undef BF_SHADE_LAUNCH_CLS
 #else
-    if (moment) return hipErrorInvalidValue;
+    if (moment || classed) return hipErrorInvalidValue;
 #endif
     if (lp->geom_stride) {
         // per-render geometry versions (bf_render_motion_batch_device): three waves per SIMD; never a rolling sequence, so
@@ -852,6 +870,11 @@ extern "C" hipError_t bfk_wf_shade_moment(const bfd::DScene *sc, const bfd::DLau
                                           float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
                                           hipStream_t stream, int waves) {
     return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, true);
+}
+extern "C" hipError_t bfk_wf_shade_class(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                         float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                         hipStream_t stream, int waves) {
+    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, true);
 }
 #endif
 

@@ -183,7 +183,19 @@ def render_pulse_sweep(sd, launch, offsets, n_streams=2, lib=None, device=None, 
         sw.close()
 
 
-def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None, per_pulse=False):
+def _classed(first, launch, classes):
+    """classes = (shape_class, n_classes, miss_class) or None -> (the launch to render, n_classes or 0): the table goes onto
+    `first` (its clones inherit it) and the launch carries BF_FLAG_CLASSES."""
+    if classes is None:
+        return launch, 0
+    shape_class, n_classes, miss_class = classes
+    first.set_classes(shape_class, n_classes, miss_class)
+    lc = capi.bf_launch.from_buffer_copy(launch)
+    lc.flags |= capi.BF_FLAG_CLASSES
+    return lc, first.channels(lc) // first.channels(launch)
+
+
+def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None, per_pulse=False, classes=None):
     """Coherent pulse sweep in which every mesh moves on its own: two targets at different speeds, a
     turning car.
 
@@ -196,7 +208,11 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
     and stream.  Each group is ONE motion batch (bf_render_motion_batch_device: a geometry version per pulse, one launch
     sequence and one tail for the group).  per_pulse=True is the reference path: the pulses rotate over the handles, one
     transform (bf_scene_transform_meshes: a BVH refit on the device) and one render per pulse; per-path results are the
-    same.  Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), as render_pulse_sweep does."""
+    same.  Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), as render_pulse_sweep does.
+
+    classes=(shape_class, n_classes, miss_class): the returns split by the target each path hit first (BF_FLAG_CLASSES,
+    Scene.set_classes); the cube is then float32[n_pulses, n_classes, f_bins * t_bins, 3] and range_doppler(cube[:, k]) the
+    range-Doppler map of class k."""
     import torch
     xf = np.asarray(transforms, dtype=np.float32)
     if xf.ndim != 4 or xf.shape[2:] != (3, 4):
@@ -207,8 +223,10 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
     n_streams = max(1, min(int(n_streams), n))
     streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
     first = capi.Scene(sd, lib)
-    handles = [first] + [first.clone() for _ in range(n_streams - 1)]
+    handles = [first]
     try:
+        launch, n_classes = _classed(first, launch, classes)
+        handles += [first.clone() for _ in range(n_streams - 1)]
         cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
         for s in streams:           # the cube was zero-filled on the current stream
             s.wait_stream(torch.cuda.current_stream(dev))
@@ -227,13 +245,14 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
                         handles[j].render_motion_batch_device(launch, xf[lo:hi], cube[lo].data_ptr(), stream=streams[j].cuda_stream)
         for s in streams:
             s.synchronize()
-        return cube.cpu().numpy().reshape(n, -1, 3)
+        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
     finally:
         for h in reversed(handles):
             h.close()
 
 
-def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False, rebuild_every=None):
+def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False, rebuild_every=None,
+                        classes=None):
     """Coherent pulse sweep in which meshes DEFORM between the pulses: a walking pedestrian, a vibrating
     panel.  The deforming counterpart of render_motion_sweep.
 
@@ -247,7 +266,8 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
     rebuild_every=k (an integer): a working handle's trees are rebuilt on the device (bf_scene_rebuild_bvh) after every k-th
     frame's update of that handle, so a mesh that drifts far from its first frame keeps a tree made for where it is; the
     batched path then renders its group in batches of k frames, the handle's base vertices set to the frame before each.
-    Results do not change.  Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W)."""
+    Results do not change.  Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W); with
+    classes=(shape_class, n_classes, miss_class), as in render_motion_sweep, float32[n_pulses, n_classes, f_bins * t_bins, 3]."""
     import torch
     if rebuild_every is not None and int(rebuild_every) < 1:
         raise ValueError("rebuild_every must be a positive integer or None")
@@ -267,8 +287,10 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
     n_streams = max(1, min(int(n_streams), n))
     streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
     first = capi.Scene(sd, lib)
-    handles = [first] + [first.clone() for _ in range(n_streams - 1)]
+    handles = [first]
     try:
+        launch, n_classes = _classed(first, launch, classes)
+        handles += [first.clone() for _ in range(n_streams - 1)]
         cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
         dpos = [torch.from_numpy(p).to(dev) for p in pos]
         for s in streams:           # the cube and the vertex arrays were written on the current stream
@@ -305,7 +327,7 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
             s.synchronize()
         for h in handles:
             h.sync()                # a vertex beyond `bound` (there is none: it was computed above) would be reported here
-        return cube.cpu().numpy().reshape(n, -1, 3)
+        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
     finally:
         for h in reversed(handles):
             h.close()

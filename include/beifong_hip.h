@@ -338,6 +338,27 @@ enum {
                                   with BF_FLAG_FAST: the fast contract says nothing about squares.  A rolling render whose
                                   BF_FLAG_MOMENT differs from the open sequence's fails with BF_ERR_INVALID and leaves the
                                   sequence intact.  bf_stats.kernel_variant carries BF_VARIANT_MOMENT. */
+    BF_FLAG_CLASSES = 1024u,   /* returns by target class: the render writes one histogram per class of the handle's class table
+                                  (bf_scene_set_classes) instead of one.  The class of a path is shape_class[s], s the shape of
+                                  its FIRST intersection (the one bf_path_record.valid reports; rectangles count: the ground, the
+                                  antenna apertures), or miss_class if its first ray leaves the scene.  Every sample the plain
+                                  render adds to cell c goes, same addend and same binning rule, to cell c of its path's class
+                                  block.  Layout [class][plain layout], each block exactly what bf_launch_channels describes;
+                                  batches [render][class][plain layout]; bf_scene_launch_channels gives the floats per render.
+                                  The per-path records are bit-equal to the plain render's, the blocks sum to the plain histogram
+                                  up to fp32 summation order, and their A and W channels sum to the plain ones exactly.
+                                  Honoured by bf_render / bf_render_batch / bf_render_motion_batch / bf_render_deform_batch and
+                                  their _device forms, in all five modes, on 1 x 1 and W x H films, with crop and ADC windows
+                                  and wide reconstruction filters, with BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL,
+                                  BF_FLAG_STATS, BF_FLAG_DOPPLER and BF_FLAG_MIX_RESAMPLE.  LDS privatisation is decided on
+                                  n_renders * n_classes * channels.  The class variants exist of the general kernels only:
+                                  bf_stats.kernel_variant carries BF_VARIANT_CLASS and never BF_VARIANT_LEAN.
+                                  Refused before anything is enqueued, an open rolling sequence staying intact: without a class
+                                  table, or with BF_FLAG_FAST or BF_FLAG_MOMENT (per-class error bars are a follow-up):
+                                  BF_ERR_INVALID; with BF_FLAG_ROLLING, by the sharded renders and by the converge renders:
+                                  BF_ERR_UNSUPPORTED (deliberately out of scope: a rolling sequence's LDS window and base-channel
+                                  table hold one block per render; shards and converge rounds are built on those and on moment
+                                  renders). */
     BF_FLAG_DOPPLER = 8u       /* receive modes: the Doppler hook the reference carries commented out
                                   ("Took doppler out to test", pathtimefrequency.cpp:124-126,141-144,180-183):
                                   the path's wavelength is shifted by Shape::doppler(si) =
@@ -394,10 +415,11 @@ typedef struct bf_stats {
                                   kernels; BF_VARIANT_WIDE = reconstruction filter wider than a pixel; 0 = general kernels.
                                   Same results either way (BF_LEAN=0 in the environment forces the general ones).  ORed with
                                   BF_VARIANT_FAST when the fast-arithmetic build ran (BF_FLAG_FAST) and with BF_VARIANT_MOMENT
-                                  when the kernels' second-moment variants ran (BF_FLAG_MOMENT)                                */
+                                  when the kernels' second-moment variants ran (BF_FLAG_MOMENT); BF_VARIANT_CLASS = the class
+                                  variants ran (BF_FLAG_CLASSES: general kernels, so never with BF_VARIANT_LEAN)                */
     uint32_t reserved_;
 } bf_stats;
-enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4, BF_VARIANT_MOMENT = 8 };
+enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4, BF_VARIANT_MOMENT = 8, BF_VARIANT_CLASS = 16 };
 
 typedef struct bf_scene_info {
     uint32_t n_shapes, n_rects, n_triangles, n_bvh_nodes;
@@ -580,6 +602,20 @@ bf_status bf_scene_clone(const bf_scene *scene, bf_scene **out);
  * BF_FLAG_MOMENT the layout documented at the flag: 5 + 2 (A + 3) per pixel,
  * 4 + phase_bins (RAW) or 5 (IQ) per ADC cell */
 uint32_t bf_launch_channels(const bf_launch *launch);
+
+/* Returns by target class (BF_FLAG_CLASSES).  A scene handle carries an optional class table: n_classes, one class per shape
+ * (shape_class: host array [n_shapes], shapes in the order of the scene description, rectangles included) and the class of a
+ * path whose first ray leaves the scene.
+ *   bf_scene_set_classes is stream-ordered like bf_scene_update_endpoints: renders enqueued afterwards on that stream see the new
+ *   table; the caller's array is free on return.  It flushes an open rolling sequence.  n_classes = 0 clears the table.
+ *   BF_ERR_INVALID for an entry or miss_class >= n_classes, or n_classes > BF_MAX_CLASSES.  bf_scene_clone copies the table;
+ *   endpoint updates, mesh transforms, vertex updates and BVH rebuilds leave it alone.
+ *   bf_scene_launch_channels returns the floats ONE render of `launch` writes on this handle: n_classes times what
+ *   bf_launch_channels returns if the launch carries BF_FLAG_CLASSES and the handle a table, what bf_launch_channels returns otherwise. */
+#define BF_MAX_CLASSES 256
+bf_status bf_scene_set_classes(bf_scene *scene, uint32_t n_classes, const uint32_t *shape_class /* host [n_shapes] */, uint32_t miss_class,
+                               void *stream);
+uint32_t bf_scene_launch_channels(const bf_scene *scene, const bf_launch *launch);
 
 /* Render into a DEVICE buffer hist_dev[film_h*film_w*channels] (accumulates;
  * caller zeroes).  stream is a hipStream_t (NULL = default stream).  The call
