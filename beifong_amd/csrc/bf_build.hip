@@ -22,6 +22,9 @@
 // triangle j in lane j (the deep levels: hundreds of thousands of tiny nodes).
 // Minima, maxima and counts are order-independent, the positions come from scans: the tree is a pure function of the rows,
 // and a rebuild of rebuilt rows reproduces the arrays byte for byte.
+//
+// The split rule, the adoption rule and the padding are restated in numpy by tests/sah_ref.py, which recovers the binary tree from
+// the four-wide arrays and holds every node of it to them (tests/test_gpu_build_splits.py; the host builder: tests/test_sah_ref_host.py).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 

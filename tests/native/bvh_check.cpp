@@ -1,5 +1,6 @@
 // Test harness (tests/ only): builds the product's host-side BVH (beifong_amd/csrc/bf_bvh.cpp) for a triangle soup
-// and checks its structural invariants on the CPU.  Compiled by tests/test_bvh_host.py with g++.
+// and checks its structural invariants on the CPU.  Compiled by tests/test_bvh_host.py with g++; bvh_export, at the end, hands the
+// trees themselves to tests/test_sah_ref_host.py.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -254,5 +255,33 @@ extern "C" int bvh4q_check(uint32_t n, const float *verts /* n*9 */, uint32_t ou
     }
     out[0] = (uint32_t) q.size();
     out[1] = (uint32_t) (worst * 1e6);
+    return 0;
+}
+
+// The trees themselves, for tests/sah_ref.py (the split rule and the adoption rule, checked in numpy): bf::build_bvh, collapse_bvh4 and
+// collapse_bvh16 of the soup; order[n], at most cap4 Node4 and cap16 Node16, out = {n4, n16, root4 (as bits), root16 (as bits)}.
+// Returns 0, or 31 if an array is too small.
+extern "C" int bvh_export(uint32_t n, const float *verts /* n*9 */, uint32_t *order, void *nodes4, uint32_t cap4, void *nodes16, uint32_t cap16,
+                          uint32_t out[4]) {
+    std::vector<bf::BuildTri> tris(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        std::memcpy(tris[i].p0, verts + 9 * i, 12);
+        std::memcpy(tris[i].p1, verts + 9 * i + 3, 12);
+        std::memcpy(tris[i].p2, verts + 9 * i + 6, 12);
+    }
+    bf::BVH bvh2;
+    bf::build_bvh(tris, bvh2, 0.f);
+    bf::BVH4 bvh4;
+    bf::collapse_bvh4(bvh2, bvh4);
+    bf::BVH16 w;
+    bf::collapse_bvh16(bvh2, w);
+    if (bvh4.nodes.size() > cap4 || w.nodes.size() > cap16) return 31;
+    if (n) std::memcpy(order, bvh2.order.data(), (size_t) n * 4);
+    if (!bvh4.nodes.empty()) std::memcpy(nodes4, bvh4.nodes.data(), bvh4.nodes.size() * sizeof(bf::Node4));
+    if (!w.nodes.empty()) std::memcpy(nodes16, w.nodes.data(), w.nodes.size() * sizeof(bf::Node16));
+    out[0] = (uint32_t) bvh4.nodes.size();
+    out[1] = (uint32_t) w.nodes.size();
+    out[2] = (uint32_t) bvh4.root_child;
+    out[3] = (uint32_t) w.root_child;
     return 0;
 }
