@@ -1,5 +1,5 @@
-// C ABI of libbeifong_hip.so (include/beifong_hip.h): scene flattening, BVH
-// build, device upload and kernel launches.  Plain pointers and sizes in,
+// C ABI of libbeifong_hip.so (include/beifong_hip.h): handle lifetime, BVH
+// build, device upload, queries and the multi-GPU entry points.  Plain pointers and sizes in,
 // integer status out; no exceptions cross the boundary.
 #include <algorithm>
 #include <cmath>
@@ -37,7 +37,6 @@ const char *ncclGetErrorString(ncclResult_t result);
 
 #include "bf_scene.h"
 
-extern "C" float bfk_host_cos(float x);
 extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y);
 extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const float *rays, int any_hit, float *out_t,
                                        uint32_t *out_prim, uint32_t *out_shape, float *out_uv, uint8_t *out_hit,
@@ -74,29 +73,6 @@ template <typename T> bf_status upload(const std::vector<T> &v, const T **out, s
     *out = reinterpret_cast<const T *>(p);
     return BF_OK;
 }
-
-void m34(const float *m16, float *out12) { std::memcpy(out12, m16, 12 * sizeof(float)); }
-
-inline float fmaf_(float a, float b, float c) { return std::fmaf(a, b, c); }
-struct V3 {
-    float x, y, z;
-};
-// same conventions as the device code (bf_device_math.h)
-inline V3 xf_vector(const float *m, V3 v) {
-    V3 r = {m[0] * v.x, m[4] * v.x, m[8] * v.x};
-    r = {fmaf_(m[1], v.y, r.x), fmaf_(m[5], v.y, r.y), fmaf_(m[9], v.y, r.z)};
-    r = {fmaf_(m[2], v.z, r.x), fmaf_(m[6], v.z, r.y), fmaf_(m[10], v.z, r.z)};
-    return r;
-}
-inline float dot(V3 a, V3 b) { return fmaf_(a.z, b.z, fmaf_(a.y, b.y, a.x * b.x)); }
-inline V3 cross(V3 a, V3 b) {
-    return {fmaf_(a.y, b.z, -(a.z * b.y)), fmaf_(a.z, b.x, -(a.x * b.z)), fmaf_(a.x, b.y, -(a.y * b.x))};
-}
-inline V3 normalize(V3 a) {
-    float s = 1.f / std::sqrt(dot(a, a));
-    return {a.x * s, a.y * s, a.z * s};
-}
-
 }  // namespace
 
 static bf_tunables read_tunables() {
@@ -209,7 +185,7 @@ bf_status bf_scene_destroy(bf_scene *s) {
         if (st.host) (void) hipHostFree(st.host);
         if (st.dev) (void) hipFree(st.dev);
     }
-    delete s;      // (~RenderState, ~MeshState: what renders and moved meshes allocated)
+    delete s;      // (~RenderState, ~MeshState, ~EndpointState: what renders, moved meshes and the endpoint tables allocated)
     return BF_OK;
 }
 
@@ -259,341 +235,65 @@ struct TriMeta {
     const float *n0, *n1, *n2;
     const float *uv0, *uv1, *uv2;
 };
-// Everything of a scene description except the BVH: shape / rectangle / emitter tables and the sensor record.
-struct Flat {
-    std::vector<bfd::DShape> shapes;
-    std::vector<bfd::DRect> rects;
-    std::vector<bf::BuildTri> btris;      // filled only when with_meshes
-    std::vector<TriMeta> meta;
-    bool any_normals = false, any_uvs = false;
-    uint32_t window_t = 0, window_f = 0;      // ADC window size (0: the whole ADC)
-    std::vector<bfd::DEmitter> emitters;
-    bfd::DSensor sensor;
-    uint32_t n_tris = 0;
-    float origin_scale = 0.f;             // largest |coordinate| of a rectangle corner, emitter or sensor position
-};
 }  // namespace
 
-// Phased-array tables arrive as host pointers inside the flattened records: copy them to the device (allocating on
-// scene creation, in place — same sizes required — on bf_scene_update_endpoints: beam steering between frames) and
-// patch the records with the device addresses.
-static bf_status bind_arrays(bf_scene *sc, Flat &f, hipStream_t stream, bool creating) {
-    auto put = [&](const float *host, uint32_t n, float *&dev, uint32_t &dev_n) -> bf_status {
-        const size_t bytes = (size_t) n * BF_VELEM_FLOATS * sizeof(float);
-        if (creating) {
-            void *p = nullptr;
-            HIP_TRY(hipMalloc(&p, bytes));
-            sc->owned.push_back(p);
-            dev = (float *) p;
-            dev_n = n;
-        } else if (!dev || dev_n != n) {
-            return fail(BF_ERR_INVALID, "bf_scene_update_endpoints: phased array size changed (%u -> %u virtual elements)", dev_n, n);
-        }
-        if (creating) {
-            HIP_TRY(hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice));
-        } else {
-            // the caller's table goes through the scene's pinned staging ring: free again when the call returns
-            bf_scene::Stage *stg = nullptr;
-            bf_status sst = stage_acquire(sc, bytes, &stg);
-            if (sst != BF_OK) return sst;
-            std::memcpy(stg->host, host, bytes);
-            HIP_TRY(hipMemcpyAsync(dev, stg->host, bytes, hipMemcpyHostToDevice, stream));
-            if ((sst = stage_release_after(stg, stream)) != BF_OK) return sst;
-        }
-        return BF_OK;
-    };
-    if (creating) {
-        sc->array_dev.assign(f.emitters.size(), nullptr);
-        sc->array_n.assign(f.emitters.size(), 0u);
-    }
-    for (size_t i = 0; i < f.emitters.size(); ++i) {
-        if (f.emitters[i].type != BF_TRANSMITTER_PHASED) continue;
-        if (i >= sc->array_dev.size()) return fail(BF_ERR_INVALID, "emitter layout changed");
-        bf_status st = put(f.emitters[i].velems, f.emitters[i].n_velems, sc->array_dev[i], sc->array_n[i]);
-        if (st != BF_OK) return st;
-        f.emitters[i].velems = sc->array_dev[i];
-    }
-    if (f.sensor.type == BF_RECEIVER_PHASED) {
-        bf_status st = put(f.sensor.velems, f.sensor.n_velems, sc->sensor_array_dev, sc->sensor_array_n);
-        if (st != BF_OK) return st;
-        f.sensor.velems = sc->sensor_array_dev;
-    }
-    return BF_OK;
-}
-
-static bf_status flatten(const bf_scene_desc *desc, Flat &f, bool with_meshes) {
-    std::vector<bfd::DShape> &shapes = f.shapes;
-    std::vector<bfd::DRect> &rects = f.rects;
-    std::vector<bf::BuildTri> &btris = f.btris;
-    std::vector<TriMeta> &meta = f.meta;
-    bool &any_normals = f.any_normals;
-    bool &f_any_uvs = f.any_uvs;
-    any_normals = false;
-    f.any_uvs = false;
+// The triangle half of a description (endpoints_flatten has accepted its shapes): every mesh triangle for the BVH builder, in
+// description order, and what its record carries besides the corners.
+static bf_status gather_triangles(const bf_scene_desc *desc, std::vector<bf::BuildTri> &btris, std::vector<TriMeta> &meta, bool &any_normals,
+                                  bool &any_uvs) {
+    any_normals = any_uvs = false;
     uint32_t prim = 0;
-    uint64_t n_tris_total = 0;
     for (uint32_t i = 0; i < desc->n_shapes; ++i) {
         const bf_shape &s = desc->shapes[i];
-        if (s.material >= desc->n_materials) return fail(BF_ERR_INVALID, "shape %u: material index out of range", i);
-        if (s.emitter >= (int32_t) desc->n_emitters) return fail(BF_ERR_INVALID, "shape %u: emitter index out of range", i);
-        bfd::DShape ds;
-        ds.type = s.type;
-        ds.material = s.material;
-        ds.emitter = s.emitter;
-        ds.rect = -1;
-        {
-            bool any = false;
-            for (int k = 0; k < 16; ++k) any = any || s.velocity[k] != 0.f;
-            for (int k = 0; k < 12; ++k) ds.velocity[k] = any ? s.velocity[k] : ((k % 5 == 0) ? 1.f : 0.f);    // all zeros = identity
+        if (s.type != BF_SHAPE_MESH) {
+            prim += 1;      // a rectangle
+            continue;
         }
-        if (s.type == BF_SHAPE_RECTANGLE) {
-            bfd::DRect rc;
-            m34(s.to_world, rc.to_world);
-            m34(s.to_object, rc.to_object);
-            // Rectangle::update — src/shapes/rectangle.cpp:83-92
-            V3 dp_du = xf_vector(rc.to_world, V3{2.f, 0.f, 0.f});
-            V3 dp_dv = xf_vector(rc.to_world, V3{0.f, 2.f, 0.f});
-            V3 n = normalize(V3{s.to_object[8], s.to_object[9], s.to_object[10]});   // inverse-transpose * (0,0,1)
-            rc.s[0] = dp_du.x; rc.s[1] = dp_du.y; rc.s[2] = dp_du.z;
-            rc.t[0] = dp_dv.x; rc.t[1] = dp_dv.y; rc.t[2] = dp_dv.z;
-            rc.n[0] = n.x; rc.n[1] = n.y; rc.n[2] = n.z;
-            V3 c = cross(dp_du, dp_dv);
-            float area = std::sqrt(dot(c, c));
-            if (!(area > 0.f) || !std::isfinite(area)) return fail(BF_ERR_INVALID, "shape %u: degenerate rectangle", i);
-            rc.inv_area = 1.f / area;
-            rc.area = area;
-            rc.shape = i;
-            rc.prim = prim;
-            rc.material = s.material;
-            rc.emitter = s.emitter;
-            ds.rect = (int32_t) rects.size();
-            rects.push_back(rc);
-            prim += 1;
-        } else if (s.type == BF_SHAPE_MESH) {
-            if (s.n_faces && (!s.positions || !s.indices)) return fail(BF_ERR_INVALID, "shape %u: null mesh arrays", i);
-            n_tris_total += s.n_faces;
-            for (uint32_t f = 0; with_meshes && f < s.n_faces; ++f) {
-                uint32_t i0 = s.indices[3 * f], i1 = s.indices[3 * f + 1], i2 = s.indices[3 * f + 2];
-                if (i0 >= s.n_vertices || i1 >= s.n_vertices || i2 >= s.n_vertices)
-                    return fail(BF_ERR_INVALID, "shape %u face %u: vertex index out of range", i, f);
-                bf::BuildTri t;
-                std::memcpy(t.p0, s.positions + 3 * i0, 12);
-                std::memcpy(t.p1, s.positions + 3 * i1, 12);
-                std::memcpy(t.p2, s.positions + 3 * i2, 12);
-                btris.push_back(t);
-                TriMeta m{prim + f, i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-                if (s.texcoords) {
-                    m.uv0 = s.texcoords + 2 * i0;
-                    m.uv1 = s.texcoords + 2 * i1;
-                    m.uv2 = s.texcoords + 2 * i2;
-                    f_any_uvs = true;
-                }
-                if (s.normals) {
-                    m.n0 = s.normals + 3 * i0;
-                    m.n1 = s.normals + 3 * i1;
-                    m.n2 = s.normals + 3 * i2;
-                    any_normals = true;
-                }
-                meta.push_back(m);
+        for (uint32_t f = 0; f < s.n_faces; ++f) {
+            uint32_t i0 = s.indices[3 * f], i1 = s.indices[3 * f + 1], i2 = s.indices[3 * f + 2];
+            if (i0 >= s.n_vertices || i1 >= s.n_vertices || i2 >= s.n_vertices)
+                return fail(BF_ERR_INVALID, "shape %u face %u: vertex index out of range", i, f);
+            bf::BuildTri t;
+            std::memcpy(t.p0, s.positions + 3 * i0, 12);
+            std::memcpy(t.p1, s.positions + 3 * i1, 12);
+            std::memcpy(t.p2, s.positions + 3 * i2, 12);
+            btris.push_back(t);
+            TriMeta m{prim + f, i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+            if (s.texcoords) {
+                m.uv0 = s.texcoords + 2 * i0;
+                m.uv1 = s.texcoords + 2 * i1;
+                m.uv2 = s.texcoords + 2 * i2;
+                any_uvs = true;
             }
-            prim += s.n_faces;
-        } else {
-            return fail(BF_ERR_UNSUPPORTED, "shape %u: unknown type %u", i, s.type);
-        }
-        shapes.push_back(ds);
-    }
-    if (n_tris_total >= (1u << 28)) return fail(BF_ERR_UNSUPPORTED, "too many triangles");
-    f.n_tris = (uint32_t) n_tris_total;
-
-    std::vector<bfd::DEmitter> &emitters = f.emitters;
-    for (uint32_t i = 0; i < desc->n_emitters; ++i) {
-        const bf_emitter &e = desc->emitters[i];
-        bfd::DEmitter de;
-        std::memset(&de, 0, sizeof(de));
-        de.type = e.type;
-        de.rect = -1;
-        de.radiance = e.radiance;
-        if (e.type == BF_EMITTER_POINT) {
-            m34(e.to_world, de.to_world);
-        } else if (e.type == BF_EMITTER_SPOT) {
-            m34(e.to_world, de.to_world);
-            m34(e.to_object, de.to_object);
-            // SpotLight ctor — src/emitters/spot.cpp:83-93
-            const float pi = 3.14159265358979323846f;
-            de.cutoff = e.cutoff_angle_deg * (pi / 180.f);
-            de.beam = e.beam_width_deg * (pi / 180.f);
-            de.inv_transition = 1.0f / (de.cutoff - de.beam);
-            de.cos_cutoff = bfk_host_cos(de.cutoff);
-            de.cos_beam = bfk_host_cos(de.beam);
-        } else if (e.type == BF_EMITTER_AREA || e.type == BF_TRANSMITTER_AREA || e.type == BF_TRANSMITTER_WIGNER ||
-                   e.type == BF_TRANSMITTER_PHASED) {
-            if (e.shape < 0 || e.shape >= (int32_t) desc->n_shapes || desc->shapes[e.shape].type != BF_SHAPE_RECTANGLE)
-                return fail(BF_ERR_UNSUPPORTED, "emitter %u: area emitters / transmitters must sit on a rectangle", i);
-            de.rect = shapes[e.shape].rect;
-            if (e.type == BF_TRANSMITTER_PHASED) {
-                if (!e.array.velems || e.array.n_velems == 0) return fail(BF_ERR_INVALID, "emitter %u: phased transmitter without array elements", i);
-                de.velems = e.array.velems;          // host pointer for now; replaced by the device copy on upload
-                de.n_velems = e.array.n_velems;
-                for (int k = 0; k < 3; ++k) de.wid[k] = e.array.elem_dims[k];
+            if (s.normals) {
+                m.n0 = s.normals + 3 * i0;
+                m.n1 = s.normals + 3 * i1;
+                m.n2 = s.normals + 3 * i2;
+                any_normals = true;
             }
-            if (e.type == BF_TRANSMITTER_WIGNER || e.type == BF_TRANSMITTER_PHASED) {
-                if (e.signal_type > BF_SIGNAL_LINFMCW) return fail(BF_ERR_INVALID, "emitter %u: unknown signal type", i);
-                // sample_delta_frequency (wignertransmitter.cpp:152-168) defines the frequency for "linfmcw" and "cw" only
-                if (e.resample_freq && e.signal_type == BF_SIGNAL_PULSE)
-                    return fail(BF_ERR_UNSUPPORTED, "emitter %u: resample_freq=true with signaltype \"pulse\" reads an uninitialised frequency in the "
-                                                    "reference (wignertransmitter.cpp:152-168); use \"linfmcw\" or \"cw\"", i);
-                de.resample = e.resample_freq ? 1u : 0u;
-                de.signal_type = e.signal_type;
-                de.amplitude = e.amplitude;
-                de.freq_centre = e.freq_centre;
-                de.freq_ext = e.freq_ext;
-                de.pulse_len = e.pulse_len;
-                de.prf = e.prf;
-                de.gain = e.gain;
-            }
-        } else {
-            return fail(BF_ERR_UNSUPPORTED, "emitter %u: type %u not supported by this build", i, e.type);
+            meta.push_back(m);
         }
-        emitters.push_back(de);
+        prim += s.n_faces;
     }
-
-    bfd::DSensor &sen = f.sensor;
-    std::memset(&sen, 0, sizeof(sen));
-    sen.type = desc->sensor.type;
-    sen.rect = -1;
-    if (desc->sensor.type == BF_SENSOR_FLUXMETER || desc->sensor.type == BF_SENSOR_IRRADIANCEMETER || desc->sensor.type == BF_RECEIVER_OMNI ||
-        desc->sensor.type == BF_RECEIVER_WIGNER || desc->sensor.type == BF_RECEIVER_PHASED) {
-        int32_t sh = desc->sensor.shape;
-        if (sh < 0 || sh >= (int32_t) desc->n_shapes || desc->shapes[sh].type != BF_SHAPE_RECTANGLE) {
-            return fail(BF_ERR_UNSUPPORTED, "fluxmeter / receiver must sit on a rectangle");
-        }
-        sen.rect = shapes[sh].rect;
-        sen.adc_sampling_start = desc->sensor.adc_sampling_start;
-        sen.adc_sampling_time = desc->sensor.adc_sampling_time;
-        sen.t_bins = desc->sensor.t_bins;
-        sen.f_bins = desc->sensor.f_bins;
-        sen.t_bandwidth = desc->sensor.t_bandwidth;
-        sen.f_bandwidth = desc->sensor.f_bandwidth;
-        sen.freq_centre = desc->sensor.freq_centre;
-        sen.freq_ext = desc->sensor.freq_ext;
-        sen.gain = desc->sensor.gain;
-        sen.rx_sig_is_delta = desc->sensor.rx_sig_is_delta;
-        if (desc->sensor.rx_signal_type > BF_SIGNAL_LINFMCW) return fail(BF_ERR_INVALID, "sensor: unknown rx_signal_type %u", desc->sensor.rx_signal_type);
-        sen.rx_signal = desc->sensor.rx_signal_type;
-        sen.rx_pulse_len = desc->sensor.rx_pulse_len;
-        sen.rx_prf = desc->sensor.rx_prf;
-        sen.rx_amplitude = desc->sensor.rx_amplitude;
-        {
-            const bf_sensor &ds = desc->sensor;
-            if (ds.window_t_bins || ds.window_f_bins || ds.window_offset_t || ds.window_offset_f) {      // adc.cpp:80-91
-                if (ds.window_t_bins == 0 || ds.window_f_bins == 0 || (uint64_t) ds.window_offset_t + ds.window_t_bins > ds.t_bins ||
-                    (uint64_t) ds.window_offset_f + ds.window_f_bins > ds.f_bins)
-                    return fail(BF_ERR_INVALID, "Invalid window specification! offset (%u, %u) + window size (%u, %u) vs full size (%u, %u)",
-                                ds.window_offset_t, ds.window_offset_f, ds.window_t_bins, ds.window_f_bins, ds.t_bins, ds.f_bins);
-                sen.win_off_t = ds.window_offset_t;
-                sen.win_off_f = ds.window_offset_f;
-                f.window_t = ds.window_t_bins;
-                f.window_f = ds.window_f_bins;
-            }
-        }
-        if (desc->sensor.type == BF_RECEIVER_PHASED) {
-            if (!desc->sensor.array.velems || desc->sensor.array.n_velems == 0)
-                return fail(BF_ERR_INVALID, "phased receiver without array elements");
-            sen.velems = desc->sensor.array.velems;      // host pointer for now (see bind_arrays)
-            sen.n_velems = desc->sensor.array.n_velems;
-            for (int k = 0; k < 3; ++k) sen.wid[k] = desc->sensor.array.elem_dims[k];
-        }
-    } else if (desc->sensor.type == BF_SENSOR_RADIANCEMETER) {
-        m34(desc->sensor.to_world, sen.to_world);
-    } else if (desc->sensor.type == BF_SENSOR_PERSPECTIVE) {
-        m34(desc->sensor.to_world, sen.to_world);
-        std::memcpy(sen.sample_to_camera, desc->sensor.sample_to_camera, 16 * sizeof(float));
-    } else {
-        return fail(BF_ERR_UNSUPPORTED, "sensor type %u not supported by this build", desc->sensor.type);
-    }
-    {
-        // ImageBlock::put / SignalBlock::put take the filtered branch iff radius > 0.5 + RayEpsilon (imageblock.cpp:115)
-        const bf_rfilter &rf = desc->sensor.rfilter;
-        const float ray_eps = 1500.f * 5.9604644775390625e-8f;          // math::RayEpsilon<float> = Epsilon * 1500
-        if (!(rf.radius >= 0.f) || !std::isfinite(rf.radius) || rf.radius > 64.f) return fail(BF_ERR_INVALID, "reconstruction filter radius %g", rf.radius);
-        if (rf.radius > .5f + ray_eps) {
-            sen.filt_n = (uint32_t) std::ceil((rf.radius - 2.f * ray_eps) * 2.f);
-            sen.filt_border = rf.border;
-            sen.filt_block = rf.block_size;
-            sen.filt_radius = rf.radius;
-            sen.filt_scale = rf.scale;
-            for (int k = 0; k <= BF_FILTER_RESOLUTION; ++k) sen.filt_tab[k] = rf.values[k];
-            if (rf.border > 64u || !(rf.scale > 0.f)) return fail(BF_ERR_INVALID, "reconstruction filter: border %u, scale %g", rf.border, rf.scale);
-        }
-    }
-    sen.crop_x = desc->sensor.crop_offset_x;
-    sen.crop_y = desc->sensor.crop_offset_y;
-    if (sen.crop_x > (1u << 20) || sen.crop_y > (1u << 20)) return fail(BF_ERR_INVALID, "film crop offset (%u, %u) out of range", sen.crop_x, sen.crop_y);
-    sen.near_clip = desc->sensor.near_clip;
-    sen.far_clip = desc->sensor.far_clip;
-    sen.shutter_open = desc->sensor.shutter_open;
-    sen.shutter_open_time = desc->sensor.shutter_open_time;
-
-    // BVH over all mesh triangles; triangles stored in leaf order
-    // rays start on scene surfaces, sensors or emitters: bound |origin| for the builder's padding
-    float &origin_scale = f.origin_scale;
-    origin_scale = 0.f;
-    auto grow_scale = [&](const float *m /* 3x4 */, float ex, float ey) {
-        for (int r = 0; r < 3; ++r)
-            origin_scale = std::max(origin_scale, std::fabs(m[4 * r + 3]) + std::fabs(m[4 * r + 0]) * ex + std::fabs(m[4 * r + 1]) * ey);
-    };
-    for (const auto &r : rects) grow_scale(r.to_world, 1.f, 1.f);
-    for (const auto &e : emitters) grow_scale(e.to_world, 0.f, 0.f);
-    grow_scale(sen.to_world, 0.f, 0.f);
     return BF_OK;
-}
-
-// what bf_scene_create and bf_scene_update_endpoints both require of the material table and the film (a back_material out of
-// range would send the kernels' load_material past the device table)
-static bf_status check_materials_and_film(const bf_scene_desc *desc) {
-    if (desc->n_materials == 0 || !desc->materials) return fail(BF_ERR_INVALID, "at least one material is required");
-    for (uint32_t i = 0; i < desc->n_materials; ++i) {
-        const uint32_t b = desc->materials[i].back_material;
-        if (b == 0) continue;
-        if (b > desc->n_materials || !desc->materials[i].twosided || !desc->materials[b - 1].twosided || desc->materials[b - 1].back_material != 0)
-            return fail(BF_ERR_INVALID, "material %u: back_material %u must name a twosided table entry without a back side of its own", i, b);
-    }
-    if (desc->sensor.film_width == 0 || desc->sensor.film_height == 0)
-        return fail(BF_ERR_INVALID, "sensor film is %u x %u", desc->sensor.film_width, desc->sensor.film_height);
-    return BF_OK;
-}
-
-// the kernel-profile bits a scene derives from its material table (lean_profile: the lean kernels have one BSDF per material)
-static bool materials_have_back(const bf_scene_desc *desc) {
-    for (uint32_t i = 0; i < desc->n_materials; ++i)
-        if (desc->materials[i].back_material != 0) return true;
-    return false;
 }
 
 bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     if (!desc || !out) return fail(BF_ERR_INVALID, "null argument");
     *out = nullptr;
-    if (desc->n_shapes && !desc->shapes) return fail(BF_ERR_INVALID, "shapes is null");
+    EndpointState::Image ends;
+    std::vector<bf::BuildTri> btris;
+    std::vector<TriMeta> meta;
+    bool any_normals = false, any_uvs = false;
     {
-        bf_status mst = check_materials_and_film(desc);
-        if (mst != BF_OK) return mst;
+        bf_status fst = endpoints_flatten(desc, ends);
+        if (fst == BF_OK) fst = gather_triangles(desc, btris, meta, any_normals, any_uvs);
+        if (fst != BF_OK) return fst;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(BF_ERR_DEVICE, "no HIP device available: the HIP path has no CPU fallback");
-
-    Flat flat;
-    {
-        bf_status fst = flatten(desc, flat, true);
-        if (fst != BF_OK) return fst;
-    }
-    std::vector<bfd::DShape> &shapes = flat.shapes;
-    std::vector<bfd::DRect> &rects = flat.rects;
-    std::vector<bf::BuildTri> &btris = flat.btris;
-    std::vector<TriMeta> &meta = flat.meta;
-    const bool any_normals = flat.any_normals;
-    std::vector<bfd::DEmitter> &emitters = flat.emitters;
-    const float origin_scale = flat.origin_scale;
+    const float origin_scale = ends.origin_scale;
 
     bf_scene *sc = new (std::nothrow) bf_scene();
     if (!sc) return fail(BF_ERR_NOMEM, "out of host memory");
@@ -603,18 +303,6 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     sc->geom = std::make_shared<bf_geometry>();
     sc->geom_token = std::make_shared<char>(0);
     sc->peers_rolling = std::make_shared<std::atomic<int>>(0);
-    {
-        bf_status ast = bind_arrays(sc, flat, nullptr, true);
-        if (ast != BF_OK) {
-            bf_scene_destroy(sc);
-            return ast;
-        }
-    }
-    sc->sensor_host = flat.sensor;
-    sc->film_w = desc->sensor.film_width;
-    sc->adc_t = flat.window_t ? flat.window_t : flat.sensor.t_bins;
-    sc->adc_f = flat.window_f ? flat.window_f : flat.sensor.f_bins;
-    sc->film_h = desc->sensor.film_height;
     sc->mesh.origin_scale_built = origin_scale;
     // what a vertex update needs of the description later (bf_scene_update_vertices): every mesh's sizes, first primitive and indices
     sc->geom->topo.resize(desc->n_shapes);
@@ -651,7 +339,7 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     std::vector<float4> tri_data(bfd::kTriStride * btris.size() + (btris.empty() ? 0 : kTriPad), make_float4(0, 0, 0, 0)), nrm_data;
     if (any_normals) nrm_data.resize(3 * btris.size());
     std::vector<float4> uv_data;
-    if (flat.any_uvs) uv_data.assign(btris.size(), make_float4(0, 0, 0, 0));
+    if (any_uvs) uv_data.assign(btris.size(), make_float4(0, 0, 0, 0));
     for (size_t slot = 0; slot < btris.size(); ++slot) {
         uint32_t src = bvh.order[slot];
         const bf::BuildTri &t = btris[src];
@@ -702,12 +390,6 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
         wnode_data.assign(32 * (bvh16.nodes.size() + 1), make_float4(0, 0, 0, 0));
         if (!bvh16.nodes.empty()) std::memcpy(wnode_data.data(), bvh16.nodes.data(), bvh16.nodes.size() * sizeof(bf::Node16));
     }
-    std::vector<bfd::DMaterial> mats(desc->n_materials);      // 48-byte device records (bf_device.h: DMaterial)
-    for (uint32_t i = 0; i < desc->n_materials; ++i) {
-        mats[i].m = desc->materials[i];
-        mats[i].pad = 0u;
-    }
-
     (void) hipGetDevice(&sc->device);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, sc->device) == hipSuccess) sc->n_cus = prop.multiProcessorCount;
@@ -731,50 +413,20 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
         sc->d.spill_stride = stride;
         sc->d.stack_need = bvh4.stack_need;
     }
-#define UP(vec, field)                                              \
-    if ((st = upload(vec, &sc->d.field, sc->owned, bytes)) != BF_OK) { \
-        bf_scene_destroy(sc);                                       \
-        return st;                                                  \
+    std::vector<void *> &gown = sc->geom->owned;
+    if ((st = upload(node_data, &sc->d.nodes, gown, bytes)) != BF_OK || (st = upload(qnode_data, &sc->d.qnodes, gown, bytes)) != BF_OK ||
+        (st = upload(wnode_data, &sc->d.wnodes, gown, bytes)) != BF_OK || (st = upload(tri_data, &sc->d.tris, gown, bytes)) != BF_OK ||
+        (st = upload(nrm_data, &sc->d.normals, gown, bytes)) != BF_OK || (st = upload(uv_data, &sc->d.uvs, gown, bytes)) != BF_OK ||
+        (st = endpoints_create(sc, ends, &bytes)) != BF_OK) {      // (the endpoint tables and the profile: bf_endpoints.cpp)
+        bf_scene_destroy(sc);
+        return st;
     }
-#define UPG(vec, field)                                                   \
-    if ((st = upload(vec, &sc->d.field, sc->geom->owned, bytes)) != BF_OK) { \
-        bf_scene_destroy(sc);                                             \
-        return st;                                                        \
-    }
-    UPG(node_data, nodes);
-    UPG(qnode_data, qnodes);
-    UPG(wnode_data, wnodes);
-    UPG(tri_data, tris);
-    UPG(nrm_data, normals);
-    UPG(uv_data, uvs);
-#undef UPG
-    UP(rects, rects);
-    UP(shapes, shapes);
-    UP(mats, materials);
-    UP(emitters, emitters);
-    std::vector<bfd::DSensor> sensor_vec(1, flat.sensor);
-    UP(sensor_vec, sensor);
-#undef UP
-    sc->run.tab.set_home(sc->d);
-    sc->n_materials = desc->n_materials;
-    sc->d.n_materials = desc->n_materials;
-    sc->d.tab_cache = (sc->tun.tab_cache && desc->n_materials <= bfd::kTabMaxMaterials && rects.size() <= bfd::kTabMaxRects) ? 1u : 0u;
-    sc->any_back_material = materials_have_back(desc);
-    sc->any_resample = false;
-    for (const auto &e : emitters) sc->any_resample = sc->any_resample || e.resample != 0u;
-    sc->shapes_host = shapes;
     sc->d.n_tris = (uint32_t) btris.size();
-    sc->d.n_rects = (uint32_t) rects.size();
-    sc->d.n_emitters = (uint32_t) emitters.size();
-    for (const auto &e : emitters) sc->emitter_types.push_back(e.type);
     sc->d.n_nodes = (uint32_t) bvh4.nodes.size();
     sc->d.root = bvh4.root_child;
     sc->d.wroot = use_wide ? bvh16.root_child : bfd_no_node();
     sc->d.n_wnodes = use_wide ? (uint32_t) bvh16.nodes.size() : 0u;
     sc->d.wrows_log = wide_rlog;
-    sc->d.c = desc->physics.c;
-    sc->d.lambda_min = desc->physics.lambda_min_nm;
-    sc->d.lambda_max = desc->physics.lambda_max_nm;
 
     hipError_t e = hipMalloc((void **) &sc->run.counters, sizeof(unsigned long long) * bfd::CTR_COUNT);
     if (e == hipSuccess) e = hipMemset(sc->run.counters, 0, sizeof(unsigned long long) * bfd::CTR_COUNT);
@@ -800,173 +452,6 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     }
     *out = sc;
     return BF_OK;
-}
-
-bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, void *stream_) {
-    if (!scene || !desc) return fail(BF_ERR_INVALID, "null argument");
-    if (desc->n_shapes && !desc->shapes) return fail(BF_ERR_INVALID, "shapes is null");
-    {
-        bf_status mst = check_materials_and_film(desc);
-        if (mst != BF_OK) return mst;
-    }
-    Flat f;
-    bf_status st = flatten(desc, f, false);
-    if (st != BF_OK) return st;
-    if (f.shapes.size() != scene->info.n_shapes || f.rects.size() != scene->d.n_rects || f.emitters.size() != scene->d.n_emitters ||
-        f.n_tris != scene->d.n_tris || desc->n_materials != scene->n_materials)
-        return fail(BF_ERR_INVALID, "bf_scene_update_endpoints: the description has a different layout than the scene "
-                                    "(shapes %zu/%u, rectangles %zu/%u, emitters %zu/%u, triangles %u/%u)",
-                    f.shapes.size(), scene->info.n_shapes, f.rects.size(), scene->d.n_rects, f.emitters.size(),
-                    scene->d.n_emitters, f.n_tris, scene->d.n_tris);
-    for (size_t i = 0; i < f.shapes.size(); ++i)
-        if (f.shapes[i].rect < 0 && (f.shapes[i].material != scene->shapes_host[i].material || f.shapes[i].emitter != scene->shapes_host[i].emitter))
-            return fail(BF_ERR_UNSUPPORTED, "bf_scene_update_endpoints: mesh shape %zu changed its material / emitter index (the "
-                                            "triangle records carry them); create a new scene", i);
-    if (scene->d.n_tris && f.origin_scale > scene->mesh.origin_scale_built)
-        return fail(BF_ERR_UNSUPPORTED, "bf_scene_update_endpoints: an endpoint moved to |coordinate| %g, outside the bound %g the "
-                                        "BVH boxes were padded for; create a new scene", (double) f.origin_scale,
-                    (double) scene->mesh.origin_scale_built);
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    // The paths of an open rolling sequence belong to the endpoints as they are.  Round 3 finished them first (a flush: one
-    // tail per frame of a sweep whose radar turns — the loop the reference ships).  Now the update JOINS the sequence: the
-    // new tables go into the next block of the handle's pool, the renders issued so far keep reading theirs through the
-    // descriptor ring (kMulti kernels).  Phased arrays (their element tables are replaced in place), wide reconstruction
-    // filters (no kMulti | kWide kernels), another stream or a full pool fall back to the flush.
-    bool phased = f.sensor.type == BF_RECEIVER_PHASED || scene->sensor_array_dev != nullptr;
-    for (const auto &e : f.emitters) phased = phased || e.type == BF_TRANSMITTER_PHASED;
-    for (float *p : scene->array_dev) phased = phased || p != nullptr;
-    bool resample_new = false;
-    for (const auto &e : f.emitters) resample_new = resample_new || e.resample != 0u;
-    const bool join = scene->run.roll.open && scene->run.roll.stream == stream && !phased && scene->sensor_host.filt_n == 0u && f.sensor.filt_n == 0u &&
-                      scene->run.tab.next + 1u < bfd::kRollRing && scene->tun.roll_join && resample_new == scene->any_resample;
-    {
-        bf_status ost = order_after_last(scene, stream);
-        if (ost == BF_OK && !join) ost = close_sequence(scene, stream);
-        if (ost != BF_OK) return ost;
-    }
-    {
-        bf_status ast = bind_arrays(scene, f, stream, false);
-        if (ast != BF_OK) return ast;
-    }
-    // small tables: packed into one pinned staging slot owned by the scene (the flattened records above are stack
-    // locals and `desc` is the caller's), then copied to their device tables in stream order — no host-blocking copy,
-    // nothing read after this call returns
-    {
-        const size_t b_rects = f.rects.size() * sizeof(bfd::DRect), b_shapes = f.shapes.size() * sizeof(bfd::DShape);
-        const size_t b_emit = f.emitters.size() * sizeof(bfd::DEmitter), b_mat = (size_t) desc->n_materials * sizeof(bfd::DMaterial);
-        const size_t b_sensor = sizeof(bfd::DSensor);
-        auto up16 = [](size_t v) { return (v + 15) & ~size_t(15); };
-        const size_t o_rects = 0, o_shapes = o_rects + up16(b_rects), o_emit = o_shapes + up16(b_shapes), o_mat = o_emit + up16(b_emit),
-                     o_sensor = o_mat + up16(b_mat), total = o_sensor + up16(b_sensor);
-        // where the tables go: the home buffers, or — joining an open sequence — the next block of the pool (same layout as the
-        // staging slot)
-        RenderState::Tables &tab = scene->run.tab;
-        char *dst_rects = (char *) tab.rects, *dst_shapes = (char *) tab.shapes, *dst_emit = (char *) tab.emitters,
-             *dst_mat = (char *) tab.materials, *dst_sensor = (char *) tab.sensor;
-        if (join) {
-            char *blk = nullptr;
-            bf_status cst = tab.claim({o_rects, o_shapes, o_emit, o_mat, o_sensor, total}, &blk);
-            if (cst != BF_OK) return cst;
-            dst_rects = blk + o_rects;
-            dst_shapes = blk + o_shapes;
-            dst_emit = blk + o_emit;
-            dst_mat = blk + o_mat;
-            dst_sensor = blk + o_sensor;
-        }
-        bf_scene::Stage *stg = nullptr;
-        bf_status sst = stage_acquire(scene, total, &stg);
-        if (sst != BF_OK) return sst;
-        char *h = (char *) stg->host;
-        if (b_rects) std::memcpy(h + o_rects, f.rects.data(), b_rects);
-        if (b_shapes) std::memcpy(h + o_shapes, f.shapes.data(), b_shapes);
-        if (b_emit) std::memcpy(h + o_emit, f.emitters.data(), b_emit);
-        for (uint32_t i = 0; i < desc->n_materials; ++i) {
-            bfd::DMaterial dm;
-            dm.m = desc->materials[i];
-            dm.pad = 0u;
-            std::memcpy(h + o_mat + (size_t) i * sizeof(dm), &dm, sizeof(dm));
-        }
-        std::memcpy(h + o_sensor, &f.sensor, b_sensor);
-        if (join) {
-            HIP_TRY(hipMemcpyAsync(dst_rects, h, total, hipMemcpyHostToDevice, stream));      // one block, the staging slot's layout
-        } else {
-            if (b_rects) HIP_TRY(hipMemcpyAsync(dst_rects, h + o_rects, b_rects, hipMemcpyHostToDevice, stream));
-            if (b_shapes) HIP_TRY(hipMemcpyAsync(dst_shapes, h + o_shapes, b_shapes, hipMemcpyHostToDevice, stream));
-            if (b_emit) HIP_TRY(hipMemcpyAsync(dst_emit, h + o_emit, b_emit, hipMemcpyHostToDevice, stream));
-            if (b_mat) HIP_TRY(hipMemcpyAsync(dst_mat, h + o_mat, b_mat, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(dst_sensor, h + o_sensor, b_sensor, hipMemcpyHostToDevice, stream));
-        }
-        sst = stage_release_after(stg, stream);
-        if (sst != BF_OK) return sst;
-        scene->d.rects = b_rects ? (const bfd::DRect *) dst_rects : scene->d.rects;
-        scene->d.shapes = b_shapes ? (const bfd::DShape *) dst_shapes : scene->d.shapes;
-        scene->d.emitters = b_emit ? (const bfd::DEmitter *) dst_emit : scene->d.emitters;
-        scene->d.materials = b_mat ? (const bfd::DMaterial *) dst_mat : scene->d.materials;
-        scene->d.sensor = (const bfd::DSensor *) dst_sensor;
-        if (join) {
-            tab.joined();
-            scene->run.roll.multi = true;
-        }
-    }
-    // every profile bit bf_scene_create derived from the tables just replaced (lean_profile reads them at the next render)
-    scene->sensor_host = f.sensor;
-    scene->any_resample = resample_new;
-    scene->any_back_material = materials_have_back(desc);
-    scene->film_w = desc->sensor.film_width;
-    scene->adc_t = f.window_t ? f.window_t : f.sensor.t_bins;
-    scene->adc_f = f.window_f ? f.window_f : f.sensor.f_bins;
-    scene->film_h = desc->sensor.film_height;
-    scene->emitter_types.clear();
-    for (const auto &e : f.emitters) scene->emitter_types.push_back(e.type);
-    scene->d.c = desc->physics.c;
-    scene->d.lambda_min = desc->physics.lambda_min_nm;
-    scene->d.lambda_max = desc->physics.lambda_max_nm;
-    return mark_last(scene, stream);
-}
-
-// The handle's class table (BF_FLAG_CLASSES): shape_class[n_shapes] in a device array of the handle's own, allocated at the first call and
-// rewritten in stream order through the staging ring; the array's address, the number of classes and the miss class travel in the
-// kernel arguments (bf_device.h: DScene::class_lo / class_hi / class_info), which every later render of the handle reads.
-bf_status bf_scene_set_classes(bf_scene *scene, uint32_t n_classes, const uint32_t *shape_class, uint32_t miss_class, void *stream_) {
-    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_set_classes: null scene");
-    const uint32_t n_shapes = scene->info.n_shapes;
-    if (n_classes > BF_MAX_CLASSES) return fail(BF_ERR_INVALID, "bf_scene_set_classes: n_classes %u exceeds BF_MAX_CLASSES (%u)", n_classes, (unsigned) BF_MAX_CLASSES);
-    if (n_classes) {
-        if (n_shapes && !shape_class) return fail(BF_ERR_INVALID, "bf_scene_set_classes: shape_class is null");
-        if (miss_class >= n_classes) return fail(BF_ERR_INVALID, "bf_scene_set_classes: miss_class %u is not below n_classes %u", miss_class, n_classes);
-        for (uint32_t i = 0; i < n_shapes; ++i)
-            if (shape_class[i] >= n_classes)
-                return fail(BF_ERR_INVALID, "bf_scene_set_classes: shape_class[%u] = %u is not below n_classes %u", i, shape_class[i], n_classes);
-    }
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    // an open rolling sequence ends here (its renders were issued without classes; the table is not theirs to see change)
-    bf_status st = order_after_last(scene, stream);
-    if (st == BF_OK) st = close_sequence(scene, stream);
-    if (st != BF_OK) return st;
-    if (!n_classes) {
-        scene->d.class_info = 0u;      // (the device array stays with the handle)
-        return BF_OK;
-    }
-    uint32_t *dev = const_cast<uint32_t *>(bfd::scene_classes(scene->d));
-    if (!dev) {
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, sizeof(uint32_t) * std::max(1u, n_shapes)));
-        scene->owned.push_back(p);
-        dev = (uint32_t *) p;
-        scene->d.class_lo = (uint32_t) (uintptr_t) dev;
-        scene->d.class_hi = (uint32_t) ((uint64_t) (uintptr_t) dev >> 32);
-    }
-    if (n_shapes) {
-        bf_scene::Stage *stg = nullptr;
-        if ((st = stage_acquire(scene, sizeof(uint32_t) * n_shapes, &stg)) != BF_OK) return st;
-        std::memcpy(stg->host, shape_class, sizeof(uint32_t) * n_shapes);
-        HIP_TRY(hipMemcpyAsync(dev, stg->host, sizeof(uint32_t) * n_shapes, hipMemcpyHostToDevice, stream));
-        if ((st = stage_release_after(stg, stream)) != BF_OK) return st;
-    }
-    scene->d.class_info = n_classes | (miss_class << 16);
-    return mark_last(scene, stream);
 }
 
 bf_status bf_scene_read_bvh(const bf_scene *scene, uint32_t width, void *nodes_out, uint64_t nodes_bytes, float *tri_rows_out, int32_t *root_child) {
@@ -1015,79 +500,14 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
     sc->info = src->info;
     sc->device = src->device;
     sc->n_cus = src->n_cus;
-    sc->emitter_types = src->emitter_types;
-    sc->n_materials = src->n_materials;
-    sc->any_back_material = src->any_back_material;
-    sc->any_resample = src->any_resample;
-    sc->sensor_host = src->sensor_host;
-    sc->film_w = src->film_w;
-    sc->adc_t = src->adc_t;
-    sc->adc_f = src->adc_f;
-    sc->film_h = src->film_h;
-    sc->shapes_host = src->shapes_host;
     bf_status st = BF_OK;
     auto fail_out = [&](bf_status s) {
         bf_scene_destroy(sc);
         return s;
     };
     // own small tables (endpoints may differ per clone), own spill columns and counters
-    auto dup = [&](const void *from, size_t bytes, const void **to) -> bf_status {
-        *to = nullptr;
-        if (!from || !bytes) return BF_OK;
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, bytes));
-        sc->owned.push_back(p);
-        HIP_TRY(hipMemcpy(p, from, bytes, hipMemcpyDeviceToDevice));
-        *to = p;
-        return BF_OK;
-    };
     if ((st = mesh_clone_snapshot(src, sc)) != BF_OK) return fail_out(st);      // the padding bound; the geometry `src` renders now, if it has moved
-    if ((st = dup(src->d.rects, sizeof(bfd::DRect) * src->d.n_rects, (const void **) &sc->d.rects)) != BF_OK) return fail_out(st);
-    if ((st = dup(src->d.shapes, sizeof(bfd::DShape) * src->info.n_shapes, (const void **) &sc->d.shapes)) != BF_OK) return fail_out(st);
-    if ((st = dup(src->d.materials, sizeof(bfd::DMaterial) * src->n_materials, (const void **) &sc->d.materials)) != BF_OK) return fail_out(st);
-    if ((st = dup(src->d.sensor, sizeof(bfd::DSensor), (const void **) &sc->d.sensor)) != BF_OK) return fail_out(st);
-    {   // the class table (bf_scene_set_classes): the clone's own copy; class_info came with src->d
-        const void *p = nullptr;
-        if ((st = dup(bfd::scene_classes(src->d), sizeof(uint32_t) * std::max(1u, src->info.n_shapes), &p)) != BF_OK) return fail_out(st);
-        sc->d.class_lo = (uint32_t) (uintptr_t) p;
-        sc->d.class_hi = (uint32_t) ((uint64_t) (uintptr_t) p >> 32);
-        if (!p) sc->d.class_info = 0u;
-    }
-    // emitters carry device pointers to their phased-array tables: duplicate the tables and re-point the records
-    std::vector<bfd::DEmitter> em(src->d.n_emitters);
-    if (!em.empty()) {
-        hipError_t e = hipMemcpy(em.data(), src->d.emitters, sizeof(bfd::DEmitter) * em.size(), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return fail_out(fail(BF_ERR_DEVICE, "bf_scene_clone: %s", hipGetErrorString(e)));
-    }
-    sc->array_dev.assign(em.size(), nullptr);
-    sc->array_n = src->array_n;
-    sc->array_n.resize(em.size(), 0u);
-    for (size_t i = 0; i < em.size(); ++i) {
-        if (em[i].type != BF_TRANSMITTER_PHASED || i >= src->array_dev.size() || !src->array_dev[i]) continue;
-        const void *p = nullptr;
-        if ((st = dup(src->array_dev[i], sizeof(float) * BF_VELEM_FLOATS * src->array_n[i], &p)) != BF_OK) return fail_out(st);
-        sc->array_dev[i] = (float *) const_cast<void *>(p);
-        em[i].velems = sc->array_dev[i];
-    }
-    if (!em.empty()) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, sizeof(bfd::DEmitter) * em.size());
-        if (e == hipSuccess) {
-            sc->owned.push_back(p);
-            e = hipMemcpy(p, em.data(), sizeof(bfd::DEmitter) * em.size(), hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) return fail_out(fail(BF_ERR_DEVICE, "bf_scene_clone: %s", hipGetErrorString(e)));
-        sc->d.emitters = (const bfd::DEmitter *) p;
-    }
-    if (src->sensor_array_dev) {
-        const void *p = nullptr;
-        if ((st = dup(src->sensor_array_dev, sizeof(float) * BF_VELEM_FLOATS * src->sensor_array_n, &p)) != BF_OK) return fail_out(st);
-        sc->sensor_array_dev = (float *) const_cast<void *>(p);
-        sc->sensor_array_n = src->sensor_array_n;
-        sc->sensor_host.velems = sc->sensor_array_dev;
-        hipError_t e = hipMemcpy((void *) sc->d.sensor, &sc->sensor_host, sizeof(bfd::DSensor), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail_out(fail(BF_ERR_DEVICE, "bf_scene_clone: %s", hipGetErrorString(e)));
-    }
+    if ((st = endpoints_clone(src, sc)) != BF_OK) return fail_out(st);
     {
         const uint32_t depth = src->d.stack_need > 16 ? src->d.stack_need - 16 : 1;
         void *p = nullptr;
@@ -1101,7 +521,6 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
         if (e == hipSuccess) e = hipMemset(sc->run.counters, 0, sizeof(unsigned long long) * bfd::CTR_COUNT);
         if (e != hipSuccess) return fail_out(fail(BF_ERR_DEVICE, "bf_scene_clone: counters: %s", hipGetErrorString(e)));
     }
-    sc->run.tab.set_home(sc->d);
     *out = sc;
     return BF_OK;
 }
@@ -1613,14 +1032,14 @@ static bf_status query_device(const bf_scene *scene, int op, uint64_t n, const u
     if (n > kQueryMax) return fail(BF_ERR_INVALID, "%s: %llu queries (at most %llu per call)", who, (unsigned long long) n, (unsigned long long) kQueryMax);
     BF_ENTER(scene);
     if (op == kQueryEmitter) {
-        if (emitter >= scene->emitter_types.size())
-            return fail(BF_ERR_INVALID, "%s: emitter %u out of range (%zu emitters)", who, emitter, scene->emitter_types.size());
-        const uint32_t t = scene->emitter_types[emitter];
+        if (emitter >= scene->ends.emitter_types.size())
+            return fail(BF_ERR_INVALID, "%s: emitter %u out of range (%zu emitters)", who, emitter, scene->ends.emitter_types.size());
+        const uint32_t t = scene->ends.emitter_types[emitter];
         if (t != BF_EMITTER_SPOT && t != BF_EMITTER_AREA && t != BF_EMITTER_POINT)
             return fail(BF_ERR_UNSUPPORTED, "%s: emitter %u is a transmitter (type %u): no probe", who, emitter, t);
     }
     if (op == kQuerySensor) {
-        const uint32_t t = scene->sensor_host.type;
+        const uint32_t t = scene->ends.sensor_host.type;
         if (t != BF_SENSOR_FLUXMETER && t != BF_SENSOR_PERSPECTIVE && t != BF_SENSOR_IRRADIANCEMETER && t != BF_SENSOR_RADIANCEMETER)
             return fail(BF_ERR_UNSUPPORTED, "%s: the scene's endpoint is a receiver (type %u): no probe", who, t);
     }
@@ -1643,9 +1062,9 @@ static bf_status query_host(const bf_scene *scene, int op, uint64_t n, const uin
     if (n > kQueryMax) return fail(BF_ERR_INVALID, "%s: %llu queries (at most %llu per call)", who, (unsigned long long) n, (unsigned long long) kQueryMax);
     if (per_material)
         for (uint64_t i = 0; i < n; ++i)
-            if (materials[i] >= scene->n_materials)
+            if (materials[i] >= scene->ends.n_materials)
                 return fail(BF_ERR_INVALID, "%s: query %llu: material %u out of range (%u materials)", who, (unsigned long long) i, materials[i],
-                            scene->n_materials);
+                            scene->ends.n_materials);
     if (n == 0) return BF_OK;
     DeviceGuard on_device(scene->device);
     float *d_in = nullptr, *d_out = nullptr;

@@ -265,7 +265,7 @@ bf_status check_rigid_table(const bf_scene *scene, uint32_t n_shapes, const floa
                            (double) m[2] * ((double) m[4] * m[9] - (double) m[5] * m[8]);
         if (!(e <= 1e-5) || !(det > 0.0))
             return fail(BF_ERR_INVALID, "%s shape %u: not a rigid motion (|R^T R - I| = %g, det R = %g)", who, k, e, det);
-        const bfd::DShape &sh = scene->shapes_host[k];
+        const bfd::DShape &sh = scene->ends.shapes_host[k];
         if (sh.type != BF_SHAPE_MESH)
             return fail(BF_ERR_INVALID, "%s shape %u is not a mesh: its entry must be the identity", who, k);
         if (sh.emitter >= 0)
@@ -549,7 +549,7 @@ bf_status deform_report(const bf_scene *scene, bool wait) {
 
 bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who, const bf_geometry::MeshTopo **topo_out) {
     if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", who, shape, scene->info.n_shapes);
-    const bfd::DShape &sh = scene->shapes_host[shape];
+    const bfd::DShape &sh = scene->ends.shapes_host[shape];
     if (sh.type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", who, shape);
     if (sh.emitter >= 0)
         return fail(BF_ERR_UNSUPPORTED, "%s mesh shape %u carries emitter %d (its sampling tables are built from the triangles as "

@@ -76,43 +76,6 @@ uint32_t RenderState::Feedback::first_at_most(const uint32_t *counts, uint32_t n
     return k;
 }
 
-void RenderState::Tables::set_home(bfd::DScene &d_) {
-    d = &d_;
-    rects = d_.rects;
-    shapes = d_.shapes;
-    emitters = d_.emitters;
-    materials = d_.materials;
-    sensor = d_.sensor;
-}
-bf_status RenderState::Tables::claim(const Layout &l, char **blk) {
-    if (!pool) {
-        lay = l;
-        stride = (l.total + 255) & ~size_t(255);
-        HIP_TRY(hipMalloc((void **) &pool, stride * bfd::kRollRing));
-    }
-    *blk = pool + stride * next;
-    return BF_OK;
-}
-bf_status RenderState::Tables::go_home(uint32_t nr, uint32_t ns, uint32_t ne, uint32_t nm, hipStream_t stream) {
-    if (!in_pool) return BF_OK;
-    // The block is found from the sensor record, the one table every update repoints (d->rects stays at the home buffer of a
-    // scene without rectangles).
-    const char *blk = (const char *) d->sensor - lay.o_sensor;
-    d->rects = rects;
-    d->shapes = shapes;
-    d->emitters = emitters;
-    d->materials = materials;
-    d->sensor = sensor;
-    in_pool = false;
-    next = 0;
-    if (nr) HIP_TRY(hipMemcpyAsync((void *) rects, blk + lay.o_rects, nr * sizeof(bfd::DRect), hipMemcpyDeviceToDevice, stream));
-    if (ns) HIP_TRY(hipMemcpyAsync((void *) shapes, blk + lay.o_shapes, ns * sizeof(bfd::DShape), hipMemcpyDeviceToDevice, stream));
-    if (ne) HIP_TRY(hipMemcpyAsync((void *) emitters, blk + lay.o_emit, ne * sizeof(bfd::DEmitter), hipMemcpyDeviceToDevice, stream));
-    if (nm) HIP_TRY(hipMemcpyAsync((void *) materials, blk + lay.o_mat, nm * sizeof(bfd::DMaterial), hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(hipMemcpyAsync((void *) sensor, blk + lay.o_sensor, sizeof(bfd::DSensor), hipMemcpyDeviceToDevice, stream));
-    return BF_OK;
-}
-
 RenderState::~RenderState() {
     for (void *p : pool) (void) hipFree(p);
     if (host) (void) hipHostFree(host);
@@ -122,7 +85,6 @@ RenderState::~RenderState() {
     if (last.done) (void) hipEventDestroy(last.done);
     for (hipEvent_t e : timing) (void) hipEventDestroy(e);
     if (counters) (void) hipFree(counters);
-    if (tab.pool) (void) hipFree(tab.pool);
     for (float *q : conv.scratch)
         if (q) (void) hipFree(q);
     if (conv.ws) (void) hipFree(conv.ws);
@@ -554,7 +516,7 @@ static bf_status wf_roll_flush(const bf_scene *scene, hipStream_t stream, bool s
     r.multi = false;
     lp.multi = 0u;
     // the sequence's last table version becomes the handle's tables again, behind the flush's kernels
-    if ((st = run.tab.go_home(scene->d.n_rects, scene->info.n_shapes, scene->d.n_emitters, scene->n_materials, stream)) != BF_OK) return st;
+    if ((st = scene->ends.go_home(stream)) != BF_OK) return st;
     if (sync_timing) return wf_collect_timing(scene, stream);
     return BF_OK;
 }
@@ -788,18 +750,19 @@ static bf_status read_stats(const bf_scene *scene, uint64_t n_paths, bf_stats *s
 // compiled out.  Every radar scene of the reference's scripts and every BASELINE config fits; anything else runs the
 // general kernels (same results: tests/test_gpu_parity.py::test_lean_and_general_kernels_agree).
 static bool lean_profile(const bf_scene *scene, const bf_launch *launch, bool receive_mode, bool multi_pixel) {
+    const EndpointState &ends = scene->ends;
     // lean builds exist of the default register budgets only (three waves per SIMD), and not of the one-kernel variant
     if ((launch->flags & BF_FLAG_MEGAKERNEL) || scene->tun.shade_waves != 3 || scene->tun.tail_waves != 3) return false;
-    if (!scene->tun.lean || scene->d.n_emitters != 1 || scene->d.uvs != nullptr || scene->sensor_host.filt_n != 0u) return false;
-    if (scene->sensor_host.win_off_t || scene->sensor_host.win_off_f) return false;      // ADC window away from the origin
-    if (scene->sensor_host.crop_x || scene->sensor_host.crop_y) return false;            // film crop window away from the origin
-    if (scene->any_back_material) return false;                                            // twosided with two nested BSDFs
-    if (scene->any_resample) return false;                                                 // resample_freq transmitters
-    const uint32_t et = scene->emitter_types[0];
+    if (!scene->tun.lean || scene->d.n_emitters != 1 || scene->d.uvs != nullptr || ends.sensor_host.filt_n != 0u) return false;
+    if (ends.sensor_host.win_off_t || ends.sensor_host.win_off_f) return false;      // ADC window away from the origin
+    if (ends.sensor_host.crop_x || ends.sensor_host.crop_y) return false;            // film crop window away from the origin
+    if (ends.any_back_material) return false;                                        // twosided with two nested BSDFs
+    if (ends.any_resample) return false;                                             // resample_freq transmitters
+    const uint32_t et = ends.emitter_types[0];
     if (receive_mode)
-        return (et == BF_TRANSMITTER_AREA || et == BF_TRANSMITTER_WIGNER) && scene->sensor_host.type == BF_RECEIVER_OMNI &&
+        return (et == BF_TRANSMITTER_AREA || et == BF_TRANSMITTER_WIGNER) && ends.sensor_host.type == BF_RECEIVER_OMNI &&
                launch->phase_bins == 0 && !(launch->flags & (BF_FLAG_DOPPLER | BF_FLAG_MIX_RESAMPLE));
-    return et == BF_EMITTER_AREA && scene->sensor_host.type == BF_SENSOR_PERSPECTIVE && !multi_pixel && launch->mode != BF_MODE_TIME;
+    return et == BF_EMITTER_AREA && ends.sensor_host.type == BF_SENSOR_PERSPECTIVE && !multi_pixel && launch->mode != BF_MODE_TIME;
 }
 
 static bool receive_mode_of(const bf_launch *launch) { return launch->mode == BF_MODE_RECEIVE_RAW || launch->mode == BF_MODE_RECEIVE_IQ; }
@@ -827,6 +790,7 @@ bf_status check_classes(const bf_scene *scene, const bf_launch *launch, uint32_t
 // Everything a launch (of n_renders renders, if a batch) is refused for on its own or against the scene and its open rolling sequence:
 // nothing is enqueued before these
 static bf_status check_launch(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, uint32_t n_renders, const bf_stats *stats_out) {
+    const EndpointState &ends = scene->ends;
     if (bf_status cst = check_classes(scene, launch, n_renders)) return cst;
     if (batch) {
         if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
@@ -835,34 +799,34 @@ static bf_status check_launch(const bf_scene *scene, const bf_launch *launch, co
         if ((uint64_t) n_renders * bf_launch_channels(launch) > (1ull << 31) || (uint64_t) n_renders * launch->n_paths >= (1ull << 48))
             return fail(BF_ERR_UNSUPPORTED, "bf_render_batch: %u renders x %llu paths is too large", n_renders, (unsigned long long) launch->n_paths);
     }
-    const bool is_rx = scene->sensor_host.type == BF_RECEIVER_OMNI || scene->sensor_host.type == BF_RECEIVER_WIGNER ||
-                       scene->sensor_host.type == BF_RECEIVER_PHASED;
+    const bool is_rx = ends.sensor_host.type == BF_RECEIVER_OMNI || ends.sensor_host.type == BF_RECEIVER_WIGNER ||
+                       ends.sensor_host.type == BF_RECEIVER_PHASED;
     const bool receive_mode = receive_mode_of(launch);
     if (receive_mode) {
         if (!is_rx) return fail(BF_ERR_INVALID, "receive mode needs a receiver (omnidirectional / wigner)");
-        if (launch->bins != scene->adc_t || launch->bins_y != scene->adc_f)
+        if (launch->bins != ends.adc_t || launch->bins_y != ends.adc_f)
             return fail(BF_ERR_INVALID, "receive mode: launch bins (%u x %u) must equal the ADC size — its window, if it has one — (%u x %u)",
-                        launch->bins, launch->bins_y, scene->adc_t, scene->adc_f);
+                        launch->bins, launch->bins_y, ends.adc_t, ends.adc_f);
         for (uint32_t i = 0; i < scene->d.n_emitters; ++i)
-            if (scene->emitter_types[i] != BF_TRANSMITTER_AREA && scene->emitter_types[i] != BF_TRANSMITTER_WIGNER &&
-                scene->emitter_types[i] != BF_TRANSMITTER_PHASED)
+            if (ends.emitter_types[i] != BF_TRANSMITTER_AREA && ends.emitter_types[i] != BF_TRANSMITTER_WIGNER &&
+                ends.emitter_types[i] != BF_TRANSMITTER_PHASED)
                 return fail(BF_ERR_INVALID, "receive mode: emitter %u is not a transmitter", i);
         // the Wigner and phased receivers sample their own local-oscillator signal under "mix_resample" (wignerreceiver.cpp:72-110,
         // 172-189): a delta signal's instantaneous frequency at the receive time (sample_delta_frequency :149-166: a chirp's or a
         // carrier's; "pulse" leaves it uninitialised there: refused), or a uniform frequency weighted with eval_signal
-        if ((launch->flags & BF_FLAG_MIX_RESAMPLE) && scene->sensor_host.type != BF_RECEIVER_OMNI) {
-            if (scene->sensor_host.rx_sig_is_delta && scene->sensor_host.rx_signal == BF_SIGNAL_PULSE)
+        if ((launch->flags & BF_FLAG_MIX_RESAMPLE) && ends.sensor_host.type != BF_RECEIVER_OMNI) {
+            if (ends.sensor_host.rx_sig_is_delta && ends.sensor_host.rx_signal == BF_SIGNAL_PULSE)
                 return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_MIX_RESAMPLE on the Wigner / phased receiver: a \"pulse\" local oscillator that is a delta "
                                                 "signal reads an uninitialised frequency in the reference (wignerreceiver.cpp:149-166)");
-            if (scene->sensor_host.rx_signal != BF_SIGNAL_CW && !(scene->sensor_host.rx_pulse_len > 0.f && scene->sensor_host.rx_prf > 0.f))
+            if (ends.sensor_host.rx_signal != BF_SIGNAL_CW && !(ends.sensor_host.rx_pulse_len > 0.f && ends.sensor_host.rx_prf > 0.f))
                 return fail(BF_ERR_INVALID, "BF_FLAG_MIX_RESAMPLE: the receiver's chirp / pulse needs rx_pulse_len > 0 and rx_prf > 0");
         }
     } else {
         if (launch->flags & BF_FLAG_MIX_RESAMPLE) return fail(BF_ERR_INVALID, "BF_FLAG_MIX_RESAMPLE is a receive-mode flag");
         if (is_rx) return fail(BF_ERR_INVALID, "render modes need a sensor (fluxmeter / perspective), not a receiver");
         for (uint32_t i = 0; i < scene->d.n_emitters; ++i)
-            if (scene->emitter_types[i] != BF_EMITTER_SPOT && scene->emitter_types[i] != BF_EMITTER_AREA &&
-                scene->emitter_types[i] != BF_EMITTER_POINT)
+            if (ends.emitter_types[i] != BF_EMITTER_SPOT && ends.emitter_types[i] != BF_EMITTER_AREA &&
+                ends.emitter_types[i] != BF_EMITTER_POINT)
                 return fail(BF_ERR_INVALID, "render modes: emitter %u is a transmitter (use receive mode)", i);
     }
     if (launch->mode > BF_MODE_RECEIVE_IQ) return fail(BF_ERR_INVALID, "unknown mode %u", launch->mode);
@@ -872,10 +836,10 @@ static bf_status check_launch(const bf_scene *scene, const bf_launch *launch, co
     if ((launch->mode == BF_MODE_RANGE || launch->mode == BF_MODE_TIME) && (launch->bins == 0 || !(launch->bin_width > 0.f)))
         return fail(BF_ERR_INVALID, "range/time mode needs bins > 0 and bin_width > 0");
     const bool multi_pixel = multi_pixel_of(launch);
-    if (multi_pixel ? (launch->film_width != scene->film_w || launch->film_height != scene->film_h)
-                    : (scene->film_w != 1 || scene->film_h != 1) && !is_rx)
+    if (multi_pixel ? (launch->film_width != ends.film_w || launch->film_height != ends.film_h)
+                    : (ends.film_w != 1 || ends.film_h != 1) && !is_rx)
         return fail(BF_ERR_INVALID, "the sensor's film is %u x %u: the launch must name the same film and spp > 0 (it has %u x %u, spp %u)",
-                    scene->film_w, scene->film_h, launch->film_width, launch->film_height, launch->spp);
+                    ends.film_w, ends.film_h, launch->film_width, launch->film_height, launch->spp);
     if (multi_pixel) {
         if (launch->mode == BF_MODE_RECEIVE_RAW || launch->mode == BF_MODE_RECEIVE_IQ)
             return fail(BF_ERR_INVALID, "receive modes bin into the ADC: film_width / film_height / spp must be 0");
@@ -936,7 +900,7 @@ static bf_status make_dlaunch(const bf_scene *scene, const bf_launch *launch, ui
     lp.n_chan = bf_launch_channels(launch);
     lp.chan_px = lp.n_chan / (lp.film_w * lp.film_h);
     lp.lean = lean_profile(scene, launch, receive_mode, multi_pixel) ? 1u : 0u;
-    lp.wide = scene->sensor_host.filt_n != 0u ? 1u : 0u;
+    lp.wide = scene->ends.sensor_host.filt_n != 0u ? 1u : 0u;
     // (wide: reconstruction filter wider than a pixel: the kernels' kWide variants)
     scene->run.last_variant = (lp.lean ? (uint32_t) BF_VARIANT_LEAN : 0u) | (lp.wide ? (uint32_t) BF_VARIANT_WIDE : 0u);
     if (launch->flags & BF_FLAG_FAST) scene->run.last_variant |= (uint32_t) BF_VARIANT_FAST;
@@ -949,7 +913,7 @@ static bf_status make_dlaunch(const bf_scene *scene, const bf_launch *launch, ui
     }
     lp.count = ((launch->flags & (BF_FLAG_STATS | BF_FLAG_COUNT)) || count) ? 1u : 0u;
     lp.doppler = (receive_mode && (launch->flags & BF_FLAG_DOPPLER)) ? 1u : 0u;
-    lp.resample = (receive_mode && scene->any_resample) ? 1u : 0u;
+    lp.resample = (receive_mode && scene->ends.any_resample) ? 1u : 0u;
     if (lp.resample && lp.doppler)
         return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_DOPPLER with a resample_freq transmitter: both rewrite the path's wavelength (one slot of path state)");
     lp.mix = (receive_mode && (launch->flags & BF_FLAG_MIX_RESAMPLE)) ? 1u : 0u;

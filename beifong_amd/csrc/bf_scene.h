@@ -1,4 +1,4 @@
-// What bf_api.cpp, bf_render.cpp and bf_mesh.cpp share: the scene handle, its guards and the few functions of each file the others call.
+// What bf_api.cpp, bf_render.cpp, bf_mesh.cpp and bf_endpoints.cpp share: the scene handle, its guards and the few functions of each file the others call.
 // Internal to libbeifong_hip.so: the functions and guards declared here have hidden visibility (the C ABI is include/beifong_hip.h alone).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -147,8 +147,7 @@ struct __attribute__((visibility("hidden"))) MeshState {
 };
 
 // Everything a render of this handle leaves behind for the next one (bf_render.cpp): the path pool and its read-back buffers, the
-// launch statistics, the open rolling sequence, the learned launch plan, the live-count feedback, the endpoint-table versions and the
-// stream order between calls.  Each field's meaning is stated here alone.  Renders take const bf_scene *, hence the keyword on bf_scene::run.
+// launch statistics, the open rolling sequence, the learned launch plan, the live-count feedback and the stream order between calls.  Each field's meaning is stated here alone.  Renders take const bf_scene *, hence the keyword on bf_scene::run.
 struct __attribute__((visibility("hidden"))) RenderState {
     // ---- the path pool, allocated on first use and grown on demand (wf_ensure) ----
     bfd::WF wf{};
@@ -216,29 +215,6 @@ struct __attribute__((visibility("hidden"))) RenderState {
         // index of the first count <= threshold (n: none)
         static uint32_t first_at_most(const uint32_t *counts, uint32_t n, uint32_t threshold);
     } fb;
-    // Endpoint-table versions of an open rolling sequence: bf_scene_update_endpoints writes the new tables into the next block of
-    // a pool instead of flushing the sequence (the renders issued so far keep reading theirs through the descriptor ring:
-    // bf_device.h: DRoll, kMulti); the home buffers (as created) hold the tables whenever no sequence is open.
-    struct Tables {
-        struct Layout {                          // byte offsets of the five tables within a block (and within the staging slot)
-            size_t o_rects = 0, o_shapes = 0, o_emit = 0, o_mat = 0, o_sensor = 0, total = 0;
-        } lay;
-        size_t stride = 0;                       // bytes per block (lay.total rounded up to 256)
-        char *pool = nullptr;                    // device: kRollRing blocks (allocated on first use)
-        uint32_t next = 0;                       // next free block
-        bool in_pool = false;                    // d.rects ... d.sensor point into the pool
-        const bfd::DRect *rects = nullptr;       // the home buffers
-        const bfd::DShape *shapes = nullptr;
-        const bfd::DEmitter *emitters = nullptr;
-        const bfd::DMaterial *materials = nullptr;
-        const bfd::DSensor *sensor = nullptr;
-        bfd::DScene *d = nullptr;                // the handle's kernel arguments, whose five table pointers move between home and pool
-        void set_home(bfd::DScene &d_);          // d_'s tables as they stand are the home buffers (create, clone)
-        bf_status claim(const Layout &l, char **blk);     // the next free block (the first claim allocates the pool for layout l)
-        void joined() { ++next, in_pool = true; }         // ... which now holds the handle's tables
-        // the last version becomes the home buffers' content again, behind `stream`; the pointers are home before any copy can fail
-        bf_status go_home(uint32_t n_rects, uint32_t n_shapes, uint32_t n_emitters, uint32_t n_materials, hipStream_t stream);
-    } tab;
     // Stream order between the successive uses of the handle: order_after_last / mark_last
     struct LastUse {
         hipStream_t stream = nullptr;
@@ -256,8 +232,68 @@ struct __attribute__((visibility("hidden"))) RenderState {
         bfd::ConvResult *ring = nullptr;         // pinned [kRing]
         hipEvent_t ev[2] = {nullptr, nullptr};   // behind round r's statistic: ev[r & 1]
     } conv;
-    // pool, pinned buffers, events, timing events, table pool, counters and the converge state go with the handle
+    // pool, pinned buffers, events, timing events, counters and the converge state go with the handle
     ~RenderState();
+};
+
+// The endpoint tables of a handle (bf_endpoints.cpp): rectangles, shapes, emitters, materials and the sensor record in ONE device block,
+// the phased-array element tables, the class table, and everything the host derives from them (which kernel variant a render launches,
+// what a launch is refused for).  Each field's meaning is stated here alone.  close_sequence takes const bf_scene *, hence the keyword on
+// bf_scene::ends.
+struct __attribute__((visibility("hidden"))) EndpointState {
+    // The host image of a description's endpoint half (endpoints_flatten): the five tables as the kernels read them, and what the
+    // profile needs that the tables do not carry.  apply() derives everything else from it.
+    struct Image {
+        std::vector<bfd::DRect> rects;
+        std::vector<bfd::DShape> shapes;
+        std::vector<bfd::DEmitter> emitters;     // velems of phased ones: the caller's host table until bind_arrays has run, the device copy then
+        std::vector<bfd::DMaterial> materials;
+        bfd::DSensor sensor;                     // (velems likewise)
+        uint32_t n_tris = 0;                     // triangles of all mesh shapes
+        uint32_t window_t = 0, window_f = 0;     // ADC window size (0: the whole ADC)
+        uint32_t film_w = 1, film_h = 1;
+        float c = 0.f, lambda_min = 0.f, lambda_max = 0.f;      // the physics band (bf_scene_desc::physics)
+        float origin_scale = 0.f;                // largest |coordinate| of a rectangle corner, emitter or sensor position
+    };
+    // ---- the profile: set by apply() alone (shapes_host: by endpoints_create), copied by a clone ----
+    uint32_t n_rects = 0, n_shapes = 0, n_emitters = 0, n_materials = 0;      // the tables' sizes, fixed when the handle is created
+    std::vector<uint32_t> emitter_types;
+    bool any_back_material = false;        // some twosided material has a second nested BSDF (general kernels)
+    bool any_resample = false;             // some transmitter re-samples the path's wavelength (resample_freq: general kernels, DLaunch::resample)
+    bfd::DSensor sensor_host;              // host copy of the device sensor record
+    uint32_t film_w = 1, film_h = 1;       // the sensor's film (bf_sensor.film_width / film_height)
+    uint32_t adc_t = 0, adc_f = 0;         // what a receive-mode launch bins into: the ADC's window, or the whole ADC
+    std::vector<bfd::DShape> shapes_host;  // as created, whatever later updates bring: mesh triangles carry their shape's material / emitter index
+    // ---- the tables on the device ----
+    // One block holds the five tables: the home block (as created) whenever no rolling sequence is open, and every block of the pool.
+    // bf_scene_update_endpoints writes the new tables into the next block of the pool instead of flushing an open sequence (the
+    // renders issued so far keep reading theirs through the descriptor ring: bf_device.h: DRoll, kMulti).  The staging slot of an
+    // update has the same layout.
+    struct Layout {                          // byte offsets of the five tables within a block, 16-byte aligned
+        size_t o_rects = 0, o_shapes = 0, o_emit = 0, o_mat = 0, o_sensor = 0, total = 0;
+    } lay;
+    char *home = nullptr;                    // device: the home block (lay.total bytes)
+    size_t stride = 0;                       // bytes per block of the pool (lay.total rounded up to 256)
+    char *pool = nullptr;                    // device: kRollRing blocks (allocated on first use)
+    uint32_t next = 0;                       // next free block
+    bool in_pool = false;                    // d->rects ... d->sensor point into the pool
+    bfd::DScene *d = nullptr;                // the handle's kernel arguments, whose five table pointers move between home and pool
+    // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
+    std::vector<float *> array_dev;
+    std::vector<uint32_t> array_n;
+    float *sensor_array_dev = nullptr;
+    uint32_t sensor_array_n = 0;
+    uint32_t *classes = nullptr;             // device: shape_class[max(1, n_shapes)] once bf_scene_set_classes has given one (d->class_lo / class_hi)
+
+    void apply(const Image &img, bool tab_cache);      // every count and profile bit, here and in *d, from a flattened description (tab_cache: bf_tunables)
+    void pack(const Image &img, char *blk) const;      // the five tables into a host block of this layout
+    void point_at(const char *blk);                    // *d reads its tables from this device block (an empty table: a null pointer)
+    bf_status claim(char **blk);                       // the next free block of the pool (the first claim allocates it)
+    void joined() { ++next, in_pool = true; }          // ... which now holds the handle's tables
+    // the last version becomes the home block's content again, behind `stream`; the pointers are home before the copy can fail
+    bf_status go_home(hipStream_t stream);
+    // home block, pool, element tables and class table go with the handle
+    ~EndpointState();
 };
 
 struct bf_scene {
@@ -272,25 +308,13 @@ struct bf_scene {
     std::shared_ptr<std::atomic<int>> peers_rolling;
     // one host thread at a time per handle (the handle owns the path pool its render's state lives in)
     mutable std::atomic_flag busy = ATOMIC_FLAG_INIT;
-    std::vector<void *> owned;             // this handle's own allocations (small tables, spill columns, private geometry)
+    std::vector<void *> owned;             // this handle's own allocations (spill columns, private geometry)
     bf_scene_info info;
     int device = 0;
     int n_cus = 256;
-    std::vector<uint32_t> emitter_types;
-    uint32_t n_materials = 0;
-    bool any_back_material = false;        // some twosided material has a second nested BSDF (general kernels)
-    bool any_resample = false;             // some transmitter re-samples the path's wavelength (resample_freq: general kernels, DLaunch::resample)
-    bfd::DSensor sensor_host;              // host copy of the device sensor record
-    uint32_t film_w = 1, film_h = 1;       // the sensor's film (bf_sensor.film_width / film_height)
-    uint32_t adc_t = 0, adc_f = 0;         // what a receive-mode launch bins into: the ADC's window, or the whole ADC
     MeshState mesh;                        // everything about moved meshes (bf_mesh.cpp)
     mutable RenderState run;               // everything about renders (bf_render.cpp)
-    // device copies of the phased-array element tables: one per emitter (nullptr if none) + the receiver's
-    std::vector<bfd::DShape> shapes_host;         // as created: mesh triangles carry their shape's material / emitter index
-    std::vector<float *> array_dev;
-    std::vector<uint32_t> array_n;
-    float *sensor_array_dev = nullptr;
-    uint32_t sensor_array_n = 0;
+    mutable EndpointState ends;            // everything about the endpoint tables (bf_endpoints.cpp)
     // Pinned staging for small host tables that travel with a launch (batch seeds / mesh offsets, endpoint records):
     // a ring of slots, each with its own device mirror and an event recorded behind the copy, so the caller's arrays
     // and our stack locals are free again when the call returns and nothing blocks unless kStageSlots launches are in
@@ -342,14 +366,14 @@ struct DeviceGuard {
         return fail(BF_ERR_INVALID, "%s: the scene handle is in use by another host thread (one call at a time per handle; " \
                                     "bf_scene_clone gives every thread / stream its own)", __func__)
 
-// ---- bf_api.cpp's, called by the other two and documented where they are defined (C names: those files are one extern "C" block each) ----
+// ---- bf_api.cpp's, called by the other three and documented where they are defined (C names: those files are one extern "C" block each) ----
 extern "C" {
 bf_status fail(bf_status st, const char *fmt, ...);      // sets bf_last_error's text
 bf_status stage_acquire(const bf_scene *sc, size_t bytes, bf_scene::Stage **out);
 bf_status stage_commit(bf_scene::Stage *st, size_t bytes, hipStream_t stream);
 bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream);
 
-// ---- bf_render.cpp, called by the other two ----
+// ---- bf_render.cpp, called by the other three ----
 bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
 bf_status mark_last(const bf_scene *scene, hipStream_t stream);
 bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
@@ -361,12 +385,20 @@ void add_stats(bf_stats &a, const bf_stats &b);      // a += b (the chunks of a 
 bf_status guard_error(unsigned long long lost, unsigned long long refused);
 bf_status report_guards(const bf_scene *scene, unsigned long long lost, unsigned long long refused, const hipStream_t *async_on = nullptr);
 
-// ---- bf_mesh.cpp, called by the other two ----
+// ---- bf_mesh.cpp, called by the other three ----
 // a device-form vertex update whose gather refused triangles: BF_ERR_DEVICE, once (wait: for the count; else only if it has landed)
 bf_status deform_report(const bf_scene *scene, bool wait);
 bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who, const bf_geometry::MeshTopo **topo_out);
 // bf_scene_clone: if `src` has moved, `sc` (a copy of src's kernel arguments so far) takes its own snapshot of what src renders now
 bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc);
+
+// ---- bf_endpoints.cpp, called by the other three ----
+// the endpoint half of a description (every refusal it has for one), before any device work
+bf_status endpoints_flatten(const bf_scene_desc *desc, EndpointState::Image &img);
+// bf_scene_create: the element tables and the home block of `sc` from `img`, and its profile; *bytes grows by the block's size
+bf_status endpoints_create(bf_scene *sc, EndpointState::Image &img, uint64_t *bytes);
+// bf_scene_clone: `sc` (whose kernel arguments are a copy of src's) takes src's profile and its own copies of src's tables
+bf_status endpoints_clone(const bf_scene *src, bf_scene *sc);
 }
 
 #pragma GCC visibility pop

@@ -193,6 +193,35 @@ def test_clone_shares_geometry_and_keeps_its_own_endpoints(hiplib):
     _same_records(rc6, rc2)
 
 
+def test_clone_of_a_phased_array_scene_steers_its_own_element_tables(hiplib):
+    """A clone of a scene that is phased on both ends owns its element tables: its emitter and sensor records point at them, not
+    at the source's.  Were they still pointing at the source's tables, steering the clone would not move the clone's beam
+    (and steering the source would)."""
+    n = 1 << 14
+    (sd0, lp), (sd1, _), (sd2, _) = (scenes.phased_receive(n_tris=20000, n_paths=n, n_elems=2, steer_deg=(a, 0.0, 0.0)) for a in (0.0, 15.0, -10.0))
+    g = capi.Scene(sd0)
+    c = g.clone()
+    _, r0, _ = g.render(lp, records=True)
+    _, rc0, _ = c.render(lp, records=True)
+    _same_records(r0, rc0)
+    # the clone is steered: it renders like a fresh scene of the steered description, the source as before
+    c.update_endpoints(sd1)
+    _, rc1, _ = c.render(lp, records=True)
+    _, rf1, _ = capi.Scene(sd1).render(lp, records=True)
+    _same_records(rc1, rf1)
+    assert not np.array_equal(rc1["L"].view(np.uint32), r0["L"].view(np.uint32))          # steering is seen at all
+    _, r0b, _ = g.render(lp, records=True)
+    _same_records(r0b, r0)
+    # the source is steered to a third angle: the clone keeps its own
+    g.update_endpoints(sd2)
+    _, r2, _ = g.render(lp, records=True)
+    _, rf2, _ = capi.Scene(sd2).render(lp, records=True)
+    _same_records(r2, rf2)
+    assert not np.array_equal(r2["L"].view(np.uint32), r0["L"].view(np.uint32))
+    _, rc2, _ = c.render(lp, records=True)
+    _same_records(rc2, rc1)
+
+
 def test_clone_allocates_no_second_copy_of_the_geometry(hiplib):
     """C2's bus: triangles + vertex normals + four-wide nodes are ~26 MB; a clone pays for its small tables and its
     traversal-spill columns only."""

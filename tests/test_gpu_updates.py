@@ -371,3 +371,63 @@ def test_update_rejects_a_bad_back_material(hiplib):
     _, r, _ = g.render(_launch_like(lp, 3), records=True)
     _, rf, _ = capi.Scene(sd0).render(_launch_like(lp, 3), records=True)
     _same_records(r, rf)
+
+
+def test_clone_while_a_joined_sequence_is_open(hiplib):
+    """bf_scene_clone of a handle whose rolling sequence an endpoint update has joined: the clone ends the sequence (the last
+    table version goes home), then copies the home block.  Both frames of the source are held to their rebuilt scenes, and the
+    clone renders like a fresh scene of the second description.  Nothing but a flush's statistics tells whether an update
+    joined, and the clone is what flushes here; so the same two frames are issued twice: the first time the flush's statistics
+    show that this handle's update joins, the second time the clone ends the sequence the update joined likewise."""
+    import torch
+    mesh = _mesh(20000)
+    frames = [_radar(mesh, "range", yaw=0.0), _radar(mesh, "range", yaw=12.0)]
+    g = capi.Scene(frames[0][0])
+    K, n, nch = len(frames), N_PATHS, g.channels(frames[0][1])
+    hist = torch.zeros((K, nch), dtype=torch.float32, device="cuda")
+    rec = torch.zeros((K, n, 4), dtype=torch.int32, device="cuda")
+
+    def issue():
+        hist.zero_()
+        torch.cuda.synchronize()
+        for k, (sd, lp) in enumerate(frames):
+            if k:
+                g.update_endpoints(sd)
+            g.render_device(_launch_like(lp, 1000 + k, flags=capi.BF_FLAG_ROLLING | capi.BF_FLAG_COUNT), hist[k].data_ptr(),
+                            records_ptr=rec[k].data_ptr())
+
+    issue()
+    st = g.flush(want_stats=True)
+    assert st.n_paths == K * n and st.n_launches_tail <= 1          # the update joined ONE sequence
+    g.update_endpoints(frames[0][0])
+    issue()
+    c = g.clone()
+    assert g.flush(want_stats=True).n_paths == 0                    # the clone has ended the sequence
+    torch.cuda.synchronize()
+    h = hist.cpu().numpy()
+    r = rec.cpu().numpy().view(np.uint32).reshape(K, -1, 4)
+    for k, (sd, lp) in enumerate(frames):
+        _check_frame(k, sd, lp, 1000 + k, h[k], np.ascontiguousarray(r[k]).view(capi.PATH_RECORD_DTYPE).reshape(-1), "clone in a joined sequence")
+    sdl, lpl = frames[-1]
+    _, rc, _ = c.render(_launch_like(lpl, 77), records=True)
+    _, rf, _ = capi.Scene(sdl).render(_launch_like(lpl, 77), records=True)
+    _same_records(rc, rf)
+    _, rg, _ = g.render(_launch_like(lpl, 77), records=True)          # ... and so does the source, its tables home again
+    _same_records(rg, rf)
+
+
+def test_profile_follows_an_update_on_a_clone(hiplib):
+    """A clone takes the source's kernel profile and an update of the clone changes the clone's alone: the clone gains a
+    back-BSDF link (general kernels), the source keeps rendering with the lean ones; each matches the oracle on its own
+    description."""
+    mesh = _mesh(20000)
+    (sd0, lp), (sd1, _) = _radar(mesh, "range"), _radar(mesh, "range", back=True)
+    g = capi.Scene(sd0)
+    c = g.clone()
+    c.update_endpoints(sd1)
+    hc, rc, stc = c.render(_launch_like(lp, 1000), records=True)
+    hg, rg, stg = g.render(_launch_like(lp, 1000), records=True)
+    assert stc.kernel_variant == 0 and stg.kernel_variant == capi.BF_VARIANT_LEAN
+    ro0 = _check_frame(0, sd0, lp, 1000, hg, rg, "profile of the source")
+    ro1 = _check_frame(1, sd1, lp, 1000, hc, rc, "profile of the clone")
+    assert np.count_nonzero(ro0["L"].view(np.uint32) != ro1["L"].view(np.uint32)) > 100          # paths do meet the plate from behind
