@@ -28,6 +28,13 @@ BF_FLAG_STATS, BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL, BF_FLAG_DOPPLER, BF_F
 BF_FLAG_ROLLING, BF_FLAG_TIMING, BF_FLAG_COUNT, BF_FLAG_FAST, BF_FLAG_MOMENT = 32, 64, 128, 256, 512
 BF_FLAG_CLASSES = 1024
 BF_MAX_CLASSES = 256
+BF_FLAG_AOV = 2048
+BF_MAX_AOVS = 16
+(BF_AOV_DEPTH, BF_AOV_POSITION, BF_AOV_UV, BF_AOV_GEO_NORMAL, BF_AOV_SH_NORMAL, BF_AOV_DP_DU, BF_AOV_DP_DV, BF_AOV_DUV_DX,
+ BF_AOV_DUV_DY, BF_AOV_TYPES) = range(10)
+# the reference's type names (aov.cpp:96-127) in BF_AOV_* order, and the floats of each
+AOV_TYPE_NAMES = ("depth", "position", "uv", "geo_normal", "sh_normal", "dp_du", "dp_dv", "duv_dx", "duv_dy")
+AOV_TYPE_FLOATS = (1, 3, 2, 3, 3, 3, 3, 2, 2)
 
 M16 = C.c_float * 16
 
@@ -61,6 +68,7 @@ class bf_emitter(C.Structure):
 
 BF_FILTER_RESOLUTION = 31
 BF_VARIANT_LEAN, BF_VARIANT_WIDE, BF_VARIANT_FAST, BF_VARIANT_MOMENT, BF_VARIANT_CLASS = 1, 2, 4, 8, 16
+BF_VARIANT_AOV = 32
 
 
 class bf_rfilter(C.Structure):
@@ -158,7 +166,7 @@ EXPORTED_SYMBOLS = [
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
     "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
     "bf_render_converge_device", "bf_render_converge", "bf_converge_statistic_device",
-    "bf_scene_set_classes", "bf_scene_launch_channels",
+    "bf_scene_set_classes", "bf_scene_launch_channels", "bf_aov_floats", "bf_scene_set_aovs",
 ]
 
 _lib = None
@@ -205,6 +213,9 @@ def load_library(path=None):
     lib.bf_scene_set_classes.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp]
     lib.bf_scene_launch_channels.argtypes = [vp, C.POINTER(bf_launch)]
     lib.bf_scene_launch_channels.restype = C.c_uint32
+    lib.bf_aov_floats.argtypes = [C.c_uint32, vp]
+    lib.bf_aov_floats.restype = C.c_uint32
+    lib.bf_scene_set_aovs.argtypes = [vp, C.c_uint32, vp, vp]
     lib.bf_render_device.argtypes = [vp, C.POINTER(bf_launch), vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_render.argtypes = [vp, C.POINTER(bf_launch), vp, vp, C.POINTER(bf_stats)]
     lib.bf_scene_flush.argtypes = [vp, vp, C.POINTER(bf_stats)]
@@ -435,6 +446,51 @@ def split_classes(hist, launch, n_classes, lib=None):
     if n_classes < 1 or hist.shape[-1] != n_classes * n:
         raise ValueError(f"a histogram of {hist.shape[-1]} floats per render is not {n_classes} classes x {n} channels")
     return hist.reshape(hist.shape[:-1] + (n_classes, n))
+
+
+def aov_types(types):
+    """A list of BF_AOV_* numbers or of the reference's type names ("depth", "sh_normal", ...) as a uint32 array."""
+    out = []
+    for t in types:
+        if isinstance(t, str):
+            if t not in AOV_TYPE_NAMES:
+                raise ValueError(f"unknown AOV type {t!r} (one of {', '.join(AOV_TYPE_NAMES)})")
+            t = AOV_TYPE_NAMES.index(t)
+        out.append(int(t))
+    return np.asarray(out, dtype=np.uint32)
+
+
+def aov_floats(types, lib=None):
+    """bf_aov_floats: K, the floats the list occupies in a pixel; 0 for an invalid list."""
+    lib = lib or load_library()
+    t = np.ascontiguousarray(types, dtype=np.uint32)
+    return int(lib.bf_aov_floats(len(t), _ptr(t) if len(t) else None))
+
+
+def aov_layout(launch, types, lib=None):
+    """The pixel of a BF_FLAG_AOV render of `launch` with the AOV table `types` (beifong_hip.h, at the flag):
+    {"aovs": [slice per table entry, in table order], "names": {type name: slice of its first entry}, "K": K,
+     "nested": slice of the nested integrator's own AOVs (range / time bins), "nested_rgba": slice of nested.R G B A,
+     "chan_px": channels per pixel}."""
+    lib = lib or load_library()
+    t = aov_types(types)
+    K = aov_floats(t, lib)
+    if K == 0:
+        raise ValueError("invalid AOV list")
+    px = 1
+    if launch.spp and launch.film_width and launch.film_height:
+        px = launch.film_width * launch.film_height
+    plain = bf_launch(**{f: getattr(launch, f) for f, _ in bf_launch._fields_})
+    plain.flags &= ~BF_FLAG_AOV
+    n_nested = lib.bf_launch_channels(C.byref(plain)) // px - 5
+    slices, names, at = [], {}, 5
+    for ty in t:
+        sl = slice(at, at + AOV_TYPE_FLOATS[ty])
+        slices.append(sl)
+        names.setdefault(AOV_TYPE_NAMES[ty], sl)
+        at = sl.stop
+    return {"aovs": slices, "names": names, "K": K, "nested": slice(5 + K, 5 + K + n_nested),
+            "nested_rgba": slice(5 + K + n_nested, 9 + K + n_nested), "chan_px": 9 + K + n_nested}
 
 
 def shard_range(n_paths, shard, n_shards, lib=None):
@@ -696,7 +752,7 @@ class Scene:
 
     def channels(self, launch):
         """bf_scene_launch_channels: floats one render of `launch` writes on this handle (bf_launch_channels, times the handle's
-        number of classes under BF_FLAG_CLASSES)."""
+        number of classes under BF_FLAG_CLASSES; the AOV layout under BF_FLAG_AOV)."""
         return self.lib.bf_scene_launch_channels(self.handle, C.byref(launch))
 
     def set_classes(self, shape_class, n_classes=None, miss_class=0, stream=0):
@@ -711,6 +767,12 @@ class Scene:
             n_classes = max(int(sc.max()) if sc.size else 0, int(miss_class)) + 1
         check(self.lib, self.lib.bf_scene_set_classes(self.handle, int(n_classes), _ptr(sc), int(miss_class), _stream(stream)),
               "bf_scene_set_classes")
+
+    def set_aovs(self, types, stream=0):
+        """bf_scene_set_aovs: the AOVs every pixel of a BF_FLAG_AOV render carries behind X Y Z A W, in this order (BF_AOV_*
+        numbers or names such as "depth", "sh_normal"; aov_layout names the channels).  An empty list clears the table."""
+        t = aov_types(types)
+        check(self.lib, self.lib.bf_scene_set_aovs(self.handle, len(t), _ptr(t) if len(t) else None, _stream(stream)), "bf_scene_set_aovs")
 
     def clear_classes(self, stream=0):
         """bf_scene_set_classes with n_classes = 0: the handle has no class table again."""

@@ -165,6 +165,11 @@ uint32_t bf_launch_channels(const bf_launch *lp) {
 
 uint32_t bf_scene_launch_channels(const bf_scene *scene, const bf_launch *lp) {
     const uint32_t n = bf_launch_channels(lp);
+    if (scene && lp && (lp->flags & BF_FLAG_AOV) && scene->run.aov.n && lp->mode <= BF_MODE_TIME && !(lp->flags & (BF_FLAG_MOMENT | BF_FLAG_CLASSES))) {
+        // beifong_hip.h, BF_FLAG_AOV: the table's K floats behind X Y Z A W, nested.R G B A last (aov.cpp:83-150)
+        const uint64_t all = (uint64_t) n + (uint64_t) film_pixels(lp) * (bf_aov_floats(scene->run.aov.n, scene->run.aov.types) + 4u);
+        return all > UINT32_MAX ? 0u : (uint32_t) all;
+    }
     if (!scene || !lp || !(lp->flags & BF_FLAG_CLASSES)) return n;
     const uint64_t all = (uint64_t) n * std::max(1u, bfd::scene_n_classes(scene->d));
     return all > UINT32_MAX ? 0u : (uint32_t) all;      // (0: as for an unknown mode; check_launch refuses such a launch by name)
@@ -339,7 +344,7 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
     std::vector<float4> tri_data(bfd::kTriStride * btris.size() + (btris.empty() ? 0 : kTriPad), make_float4(0, 0, 0, 0)), nrm_data;
     if (any_normals) nrm_data.resize(3 * btris.size());
     std::vector<float4> uv_data;
-    if (any_uvs) uv_data.assign(btris.size(), make_float4(0, 0, 0, 0));
+    if (any_uvs) uv_data.assign(3 * btris.size(), make_float4(0, 0, 0, 0));      // differences | (uv0, uv1) | (uv2, -, -): bf_device.h
     for (size_t slot = 0; slot < btris.size(); ++slot) {
         uint32_t src = bvh.order[slot];
         const bf::BuildTri &t = btris[src];
@@ -353,7 +358,11 @@ bf_status bf_scene_create(const bf_scene_desc *desc, bf_scene **out) {
         const bf_shape &msh = desc->shapes[m.shape];
         uint32_t has_n = (m.n0 ? 1u : 0u) | (m.uv0 ? 2u : 0u) | ((uint32_t) msh.material << 8) | ((uint32_t) (msh.emitter + 1) << 20);
         if (m.uv0)   // mesh.cpp:494-499: duv0 = uv1 - uv0, duv1 = uv2 - uv0
+        {
             uv_data[slot] = make_float4(m.uv1[0] - m.uv0[0], m.uv1[1] - m.uv0[1], m.uv2[0] - m.uv0[0], m.uv2[1] - m.uv0[1]);
+            uv_data[btris.size() + slot] = make_float4(m.uv0[0], m.uv0[1], m.uv1[0], m.uv1[1]);
+            uv_data[2 * btris.size() + slot] = make_float4(m.uv2[0], m.uv2[1], 0.f, 0.f);
+        }
         float w0, w1, w2;
         std::memcpy(&w0, &m.prim, 4);
         std::memcpy(&w1, &m.shape, 4);
@@ -500,6 +509,8 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
     sc->info = src->info;
     sc->device = src->device;
     sc->n_cus = src->n_cus;
+    sc->run.aov.n = src->run.aov.n;        // the AOV table (bf_scene_set_aovs); the side rows are each handle's own
+    std::memcpy(sc->run.aov.types, src->run.aov.types, sizeof(sc->run.aov.types));
     bf_status st = BF_OK;
     auto fail_out = [&](bf_status s) {
         bf_scene_destroy(sc);
@@ -684,6 +695,9 @@ bf_status bf_allreduce_device(const int *devices, uint32_t n_devices, float *con
 bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, const bf_launch *launch, float *const *hist_dev,
                                    void *const *streams, bf_stats *stats_out) {
     if (!scenes || !launch || !hist_dev || n_devices == 0) return fail(BF_ERR_INVALID, "bf_render_sharded_device: null argument");
+    if (launch->flags & BF_FLAG_AOV)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded_device: BF_FLAG_AOV is not supported (the shards' handles each carry an AOV table "
+                                        "of their own; render the AOVs per device)");
     if (launch->flags & BF_FLAG_CLASSES)
         return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded_device: BF_FLAG_CLASSES is not supported (the shards' handles each carry a class table "
                                         "of their own; render the classes per device)");
@@ -782,6 +796,9 @@ bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, 
 
 bf_status bf_render_sharded(bf_scene *const *scenes, uint32_t n_devices, const bf_launch *launch, float *hist_out, bf_stats *stats_out) {
     if (!scenes || !launch || !hist_out || n_devices == 0) return fail(BF_ERR_INVALID, "bf_render_sharded: null argument");
+    if (launch->flags & BF_FLAG_AOV)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded: BF_FLAG_AOV is not supported (the shards' handles each carry an AOV table of "
+                                        "their own; render the AOVs per device)");
     if (launch->flags & BF_FLAG_CLASSES)
         return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded: BF_FLAG_CLASSES is not supported (the shards' handles each carry a class table of "
                                         "their own; render the classes per device)");

@@ -10,7 +10,9 @@
 //             (64-byte records, so that none straddles a sector, measured no faster on any config —
 //              profiles/r03_tri_record_ab.txt — so the 48-byte records of SURVEY 8d stay)
 //   normals : float4[3 * n_tris]     only if some mesh carries vertex normals
-//   uvs     : float4[n_tris]         (uv1 - uv0, uv2 - uv0), only if some mesh carries texture coordinates
+//   uvs     : float4[3 * n_tris]     row t: (uv1 - uv0, uv2 - uv0); row n_tris + t: (uv0, uv1); row 2 n_tris + t: (uv2, 0, 0) — the
+//                                    vertices' own coordinates, read by the FULL surface interaction alone (si.uv); only if some mesh
+//                                    carries texture coordinates
 //   rects, shapes, materials, emitters : small tables (scenes hold a handful)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -96,7 +98,11 @@ struct DEmitter {
 //   kClass    the launch splits its histogram by the class of each path's first intersection (BF_FLAG_CLASSES; chosen by the host through
 //             the *_class launchers): the path state carries the class (PathState::cls, WF::cls), hist_dst adds the class block's offset
 //             and the 1 x 1 film's base channels take the per-cell route of a W x H film; every other variant has none of that code
-constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64, kClass = 128;
+//   kAov      every pixel carries the AOVs of the handle's table (BF_FLAG_AOV; chosen by the host through the *_aov launchers; render modes
+//             only, never with kMoment / kClass / kLean / kMulti): shade_vertex writes the first intersection's values into the side
+//             rows of the path's slot (AovCtx below), film_put reads them back and adds them with the sample; every other variant
+//             has none of that code
+constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64, kClass = 128, kAov = 256;
 // rare<V>(c): a condition the lean profile guarantees to be false
 template <int V> __device__ __forceinline__ constexpr bool rare(bool c) { return (V & kLean) ? false : c; }
 
@@ -131,7 +137,7 @@ struct DScene {
     const float4 *nodes;      // 8 float4 per node
     const float4 *tris;       // 3 float4 per triangle
     const float4 *normals;    // 3 float4 per triangle or nullptr
-    const float4 *uvs;        // 1 float4 per triangle or nullptr
+    const float4 *uvs;        // 3 n_tris float4 (one row per triangle, three times: the layout above) or nullptr
     const DRect *rects;
     const DShape *shapes;
     const DMaterial *materials;
@@ -275,6 +281,53 @@ struct DLaunch {
                                     // tris / normals / nodes / wnodes / qnodes to the next render's; 0: one geometry for all renders
                                     // (in the struct's tail padding: the other kernels' argument layout stays as it was)
 };
+
+// BF_FLAG_AOV.  An AOV launch never rolls, so its five words travel in the DLaunch fields only a rolling sequence reads (no kernel
+// argument moves, the other variants never look):
+//   roll_newest | roll_lo << 32    the SIDE ROWS (device floats, below)
+//   base_off | has_records << 32   the table: entry i in bits 4 i .. 4 i + 3 as BF_AOV_* + 1, 0 behind the last entry
+//   multi                          the row stride in slots
+// Side rows: the first intersection's values wait, from the visit that shades the first vertex to the visit that puts the sample,
+// in rows of one float per slot — row r of slot s at rows[r * stride + s], COMPONENT-major, so the 64 lanes of a wave that holds a
+// dense batch write and read 256 contiguous bytes per component (K floats back to back per slot would make every component store a
+// 64-line scatter).  Only the components of the types the table names have a row, in the order depth, position.xyz, uv.xy, geo
+// normal.xyz, shading normal.xyz, dp_du.xyz, dp_dv.xyz (at most kAovMaxRows; a type named twice is carried once; duv_dx / duv_dy
+// are constants).  A slot is a pool slot (wf_shade, the tail) or a thread of the grid (the one-kernel variant).
+constexpr uint32_t kAovMaxRows = 18;
+constexpr uint32_t kAovStored = 7;      // the types BF_AOV_DEPTH .. BF_AOV_DP_DV have rows
+__host__ __device__ __forceinline__ uint32_t aov_type_floats(uint32_t type) {      // BF_AOV_*: 1 3 2 3 3 3 3 2 2
+    return type == 0u ? 1u : ((type == 2u || type >= 7u) ? 2u : 3u);
+}
+struct AovCtx {
+    float *rows;         // nullptr: not an AOV launch
+    uint32_t stride;
+    uint32_t slot;       // per lane: the slot its path lives in
+    uint32_t mask;       // bit t: the table names type t (t < kAovStored)
+    uint32_t K;          // floats the table occupies in a pixel
+    uint64_t types;
+};
+__host__ __device__ __forceinline__ AovCtx aov_ctx(const DLaunch &lp) {
+    AovCtx a;
+    a.rows = (float *) (uintptr_t) (((uint64_t) lp.roll_lo << 32) | lp.roll_newest);
+    a.types = ((uint64_t) lp.has_records << 32) | lp.base_off;
+    a.stride = lp.multi;
+    a.slot = 0u;
+    a.mask = 0u;
+    a.K = 0u;
+    for (uint64_t t = a.types; t & 15u; t >>= 4) {
+        const uint32_t type = (uint32_t) (t & 15u) - 1u;
+        if (type < kAovStored) a.mask |= 1u << type;
+        a.K += aov_type_floats(type);
+    }
+    return a;
+}
+__host__ __device__ __forceinline__ AovCtx aov_none() {
+    AovCtx a;
+    a.rows = nullptr;
+    a.stride = a.slot = a.mask = a.K = 0u;
+    a.types = 0ull;
+    return a;
+}
 
 // device counters (uint64 each)
 enum {

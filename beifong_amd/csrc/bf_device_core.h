@@ -761,6 +761,7 @@ BF_DEV int32_t tri_tag_emitter(uint32_t tag) { return (int32_t) (tag >> 20) - 1;
 // the parts of a SurfaceInteraction the estimator never reads (bf_ray_intersect reports them)
 struct SIGeom {
     V3 n, dp_du, dp_dv;
+    float u, v;      // si.uv: prim_uv, or the interpolated texture coordinates of a mesh that has them (mesh.cpp:470-500)
 };
 
 template <bool FULL = false, int V = 0> BF_DEV void make_si(const DScene &sc, V3 o, V3 d, const Hit &h, SI &si, SIGeom *geom = nullptr,
@@ -789,6 +790,8 @@ template <bool FULL = false, int V = 0> BF_DEV void make_si(const DScene &sc, V3
                 geom->n = si.sh.n;
                 geom->dp_du = dp_du;
                 geom->dp_dv = mk(rc.t[0], rc.t[1], rc.t[2]);
+                geom->u = h.u;
+                geom->v = h.v;
             }
         }
     } else {
@@ -829,6 +832,14 @@ template <bool FULL = false, int V = 0> BF_DEV void make_si(const DScene &sc, V3
             geom->n = n;
             geom->dp_du = dp_du;
             geom->dp_dv = dp_dv;
+            geom->u = b1;
+            geom->v = b2;
+            if (rare<V>((tag & 2u) != 0u)) {
+                // the vertices' own texture coordinates: rows n_tris + slot = (uv0, uv1), 2 n_tris + slot = (uv2, -, -) behind the differences
+                const float4 q01 = sc.uvs[(size_t) sc.n_tris + h.slot], q2 = sc.uvs[2 * (size_t) sc.n_tris + h.slot];
+                geom->u = (q01.x * b0 + q01.z * b1) + q2.x * b2;
+                geom->v = (q01.y * b0 + q01.w * b1) + q2.y * b2;
+            }
         }
         if (tag & 1u) {
             si.sh.n = normalize(mk(na.x, na.y, na.z) * b0 + mk(nb.x, nb.y, nb.z) * b1 + mk(nc.x, nc.y, nc.z) * b2);

@@ -82,6 +82,9 @@ __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DSce
     s.rmint = 0.f;
     s.rmaxt = 0.f;
     FilmAcc acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0u, 0u};
+    // kAov: the side rows of the lane's slot — the pool slot it adopts (RESUME), else its own thread of the grid
+    AovCtx av = (kRX & kAov) ? aov_ctx(lp) : aov_none();
+    if ((kRX & kAov) && !RESUME) av.slot = blockIdx.x * kBlock + (uint32_t) tid;
     uint32_t c_closest = 0, c_shadow = 0, c_nodes = 0, c_wnodes = 0, c_tris = 0, c_bounces = 0;
     // wave-local pool of path indices (uniform across the wave)
     uint64_t pool_next = 0, pool_end = 0;
@@ -125,6 +128,7 @@ __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DSce
             if (!alive && !done) {
                 if (rank < got) {
                     load_state(wf, slot, receive, s, (kRX & kClass) != 0);
+                    if (kRX & kAov) av.slot = slot;
                     regen_ok = slot < wf.n_main;
                     alive = true;
                     need_closest = false;          // traced (and counted) by wf_trace already
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DSce
         // ---- 3. film: paths that ended at the vertex shaded last iteration (their last shadow ray
         //         has resolved by now) ---------------------------------------------------------------
         if (alive && (film || term_pending)) {
-            film_put<kRX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records);
+            film_put<kRX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records, av);
             alive = false;
             film = false;
             if (RESUME) {
@@ -376,7 +380,7 @@ __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DSce
         BF_PROF_STAMP(pf_t3);
         // ---- 4. vertex logic for the lanes that hold a fresh hit ---------------------------------
         if (alive && !need_closest) {
-            if (!shade_vertex<kRX>(sc, lp, s, hit, sh, c_bounces
+            if (!shade_vertex<kRX>(sc, lp, s, hit, sh, c_bounces, av
 #ifdef BF_TAIL_PROF
                               , &pf_sp
 #endif
@@ -553,7 +557,7 @@ BF_NS_END  // namespace bfd
 // moment: the kMoment variants (BF_FLAG_MOMENT; the *_moment launchers below); classed: the kClass variants (BF_FLAG_CLASSES; *_class)
 static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
                                 unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream,
-                                bool moment, bool classed = false) {
+                                bool moment, bool classed = false, bool aov = false) {
     bfd::WF none;
     memset(&none, 0, sizeof(none));
     const bool spill = sc->stack_need > (uint32_t) bfd::kStackDepth;
@@ -600,8 +604,30 @@ static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, f
 #undef BF_RENDER_CLS2
         return hipGetLastError();
     }
+    if (aov) {
+        // BF_FLAG_AOV (render modes; never with BF_FLAG_FAST, BF_FLAG_MOMENT or BF_FLAG_CLASSES): the kAov variants of the same forms
+        if (lp->mode == BF_MODE_RECEIVE_RAW || lp->roll) return hipErrorInvalidValue;
+#define BF_RENDER_AOV2(S, P, V)                                                                                                     \
+    hipLaunchKernelGGL((bfd::bf_render_kernel<S, false, P, BF_TAIL_WAVES, bfd::kAov | (V)>), dim3(grid), dim3(bfd::kBlock), lds_bytes, \
+                       stream, *sc, *lp, g_hist, records, counters, none, 0u)
+#define BF_RENDER_AOV(S, P)                                                                   \
+    if (lp->geom_stride && lp->wide) BF_RENDER_AOV2(S, P, bfd::kWide | bfd::kGeom);           \
+    else if (lp->geom_stride) BF_RENDER_AOV2(S, P, bfd::kGeom);                               \
+    else if (lp->wide) BF_RENDER_AOV2(S, P, bfd::kWide);                                      \
+    else BF_RENDER_AOV2(S, P, 0)
+        if (stats) {
+            if (spill) { BF_RENDER_AOV(true, true); }
+            else { BF_RENDER_AOV(true, false); }
+        } else {
+            if (spill) { BF_RENDER_AOV(false, true); }
+            else { BF_RENDER_AOV(false, false); }
+        }
+#undef BF_RENDER_AOV
+#undef BF_RENDER_AOV2
+        return hipGetLastError();
+    }
 #else
-    if (moment || classed) return hipErrorInvalidValue;
+    if (moment || classed || aov) return hipErrorInvalidValue;
 #endif
 #define BF_RENDER_LAUNCH(S, R, P, WF_, IT_)                                                                                              \
     if (lp->wide)                                                                                                                        \
@@ -648,7 +674,7 @@ static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, f
 //   block_cap  : at most this many workgroups (0: no cap)
 static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, uint32_t n_slots,
                               float *g_hist, bf_path_record *records, int stats, size_t lds_bytes, hipStream_t stream,
-                              int tail_waves, unsigned spread, unsigned block_cap, bool moment, bool classed = false) {
+                              int tail_waves, unsigned spread, unsigned block_cap, bool moment, bool classed = false, bool aov = false) {
     // one lane per live slot (gathered from the alive masks), at most one thread per pool slot
     // (any grid finishes the job: waves loop over their segment of the alive masks; the cap keeps the
     // launch within the scene's traversal-spill columns)
@@ -710,8 +736,30 @@ static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, con
 #undef BF_TAIL_CLS2
         return hipGetLastError();
     }
+    if (aov) {
+        // BF_FLAG_AOV: the kAov variants of the general forms, three waves per SIMD
+        if (lp->mode == BF_MODE_RECEIVE_RAW || lp->roll) return hipErrorInvalidValue;
+#define BF_TAIL_AOV2(S, P, V)                                                                                                       \
+    hipLaunchKernelGGL((bfd::bf_render_kernel<S, true, P, 3, bfd::kAov | (V)>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, \
+                       *lp, g_hist, records, counters, *wf, it)
+#define BF_TAIL_AOV(S, P)                                                                     \
+    if (lp->geom_stride && lp->wide) BF_TAIL_AOV2(S, P, bfd::kWide | bfd::kGeom);             \
+    else if (lp->geom_stride) BF_TAIL_AOV2(S, P, bfd::kGeom);                                 \
+    else if (lp->wide) BF_TAIL_AOV2(S, P, bfd::kWide);                                        \
+    else BF_TAIL_AOV2(S, P, 0)
+        if (stats) {
+            if (spill) { BF_TAIL_AOV(true, true); }
+            else { BF_TAIL_AOV(true, false); }
+        } else {
+            if (spill) { BF_TAIL_AOV(false, true); }
+            else { BF_TAIL_AOV(false, false); }
+        }
+#undef BF_TAIL_AOV
+#undef BF_TAIL_AOV2
+        return hipGetLastError();
+    }
 #else
-    if (moment || classed) return hipErrorInvalidValue;
+    if (moment || classed || aov) return hipErrorInvalidValue;
 #endif
 #define BF_TAIL_LAUNCH(S, P)                                                                                                           \
     if (lp->geom_stride && lp->wide)                                                                                                   \
@@ -778,6 +826,16 @@ extern "C" hipError_t bfk_launch_tail_class(const bfd::DScene *sc, const bfd::DL
                                             uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
                                             hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
     return tail_launch(sc, lp, wf, it, n_slots, g_hist, records, stats, lds_bytes, stream, tail_waves, spread, block_cap, false, true);
+}
+extern "C" hipError_t bfk_launch_render_aov(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
+                                            unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,
+                                            hipStream_t stream) {
+    return render_launch(sc, lp, g_hist, records, counters, stats, grid, lds_bytes, stream, false, false, true);
+}
+extern "C" hipError_t bfk_launch_tail_aov(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it,
+                                          uint32_t n_slots, float *g_hist, bf_path_record *records, int stats, size_t lds_bytes,
+                                          hipStream_t stream, int tail_waves, unsigned spread, unsigned block_cap) {
+    return tail_launch(sc, lp, wf, it, n_slots, g_hist, records, stats, lds_bytes, stream, tail_waves, spread, block_cap, false, false, true);
 }
 #endif
 

@@ -427,7 +427,7 @@ bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
                           bf_path_record *records_dev, void *stream_, bf_stats *stats_out, const char *fn, Prepare &&prepare) {
     MeshState &m = scene->mesh;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const uint64_t n_chan = bf_scene_launch_channels(scene, launch);      // floats per render (x n_classes under BF_FLAG_CLASSES)
+    const uint64_t n_chan = bf_scene_launch_channels(scene, launch);      // floats per render (x n_classes under BF_FLAG_CLASSES; the AOV layout under BF_FLAG_AOV)
     const MotionLayout L = motion_layout(scene->d);
     if (L.rows > UINT32_MAX)
         return fail(BF_ERR_UNSUPPORTED, "%s: one geometry version of this scene is %zu float4 rows (at most 2^32 - 1)", fn, L.rows);
@@ -761,7 +761,7 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
     take(posed, B.tris, &tris0);
     take(scene->d.normals != nullptr, B.normals, &normals);
     take(old_normals0 != nullptr, B.normals, &normals0);
-    take(scene->d.uvs != nullptr, (size_t) n * sizeof(float4), &uvs);
+    take(scene->d.uvs != nullptr, 3 * (size_t) n * sizeof(float4), &uvs);      // three rows per triangle, n apart (bf_device.h)
     take(scene->geom->corners != nullptr, (size_t) n * sizeof(uint4), &corners);
     take(want_quant && bo.n_nodes, B.nodes / 2, &qnodes);
     take(posed && B.nodes, B.nodes, &nodes0);
@@ -779,7 +779,8 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
         if (e == hipSuccess && tris0) e = hipMemsetAsync(tris0 + tri_rows, 0, kTriPad * sizeof(float4), stream);
         if (e == hipSuccess && normals) e = bfk_build_gather(bo.order, n, scene->d.normals, normals, 3, stream);
         if (e == hipSuccess && normals0) e = bfk_build_gather(bo.order, n, old_normals0, normals0, 3, stream);
-        if (e == hipSuccess && uvs) e = bfk_build_gather(bo.order, n, scene->d.uvs, uvs, 1, stream);
+        for (size_t part = 0; part < 3; ++part)
+            if (e == hipSuccess && uvs) e = bfk_build_gather(bo.order, n, scene->d.uvs + part * n, uvs + part * n, 1, stream);
         if (e == hipSuccess && corners) e = bfk_build_gather(bo.order, n, (const float4 *) scene->geom->corners, corners, 1, stream);
         // the quantised copies by the refit's own kernel (no levels to re-fit: the boxes are the builder's)
         const uint32_t no_levels[1] = {0u};
@@ -878,7 +879,7 @@ bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
     // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
-    if ((st = check_classes(scene, launch, n_renders)) != BF_OK) return st;
+    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
     if (scene->d.n_tris == 0) {
         // nothing to move: an ordinary batch
         bf_batch b = {n_renders, seeds, nullptr};
@@ -942,7 +943,7 @@ bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
     // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
-    if ((st = check_classes(scene, launch, n_renders)) != BF_OK) return st;
+    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
     if (scene->d.n_tris == 0) {
         bf_batch b = {n_renders, seeds, nullptr};
         return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);

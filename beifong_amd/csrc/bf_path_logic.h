@@ -656,9 +656,62 @@ static __device__ unsigned long long g_lane_prof[2 * kShadeProfSections];      /
 #define BF_LANEPROF_ARG
 #define SLP(sec, cond)
 #endif
+// kAov: the first intersection's values into the side rows of the path's slot (bf_device.h: AovCtx), zeros for a miss.  Every path
+// passes here exactly once, at its first vertex (a miss included), so this store is also what clears a regenerated slot's rows.
+BF_DEV void aov_store(const AovCtx &av, bool valid, const SI &si, const SIGeom &g) {
+    typedef __attribute__((address_space(1))) float *glb_f_ptr;
+    glb_f_ptr q = (glb_f_ptr) av.rows + av.slot;
+    const uint32_t n = av.stride;
+    uint32_t r = 0u;
+    const float z = 0.f;
+#define BF_AOV_ROW(x) q[(size_t) (r++) * n] = valid ? (x) : z
+    if (av.mask & 1u) { BF_AOV_ROW(si.t); }
+    if (av.mask & 2u) { BF_AOV_ROW(si.p.x); BF_AOV_ROW(si.p.y); BF_AOV_ROW(si.p.z); }
+    if (av.mask & 4u) { BF_AOV_ROW(g.u); BF_AOV_ROW(g.v); }
+    if (av.mask & 8u) { BF_AOV_ROW(g.n.x); BF_AOV_ROW(g.n.y); BF_AOV_ROW(g.n.z); }
+    if (av.mask & 16u) { BF_AOV_ROW(si.sh.n.x); BF_AOV_ROW(si.sh.n.y); BF_AOV_ROW(si.sh.n.z); }
+    if (av.mask & 32u) { BF_AOV_ROW(g.dp_du.x); BF_AOV_ROW(g.dp_du.y); BF_AOV_ROW(g.dp_du.z); }
+    if (av.mask & 64u) { BF_AOV_ROW(g.dp_dv.x); BF_AOV_ROW(g.dp_dv.y); BF_AOV_ROW(g.dp_dv.z); }
+#undef BF_AOV_ROW
+}
+// ... and back, when the path's sample is put: the stored components by type (0 where the table names none of the type)
+struct AovVals {
+    float t, px, py, pz, u, v, nx, ny, nz, sx, sy, sz, ux, uy, uz, vx, vy, vz;
+};
+BF_DEV AovVals aov_load(const AovCtx &av) {
+    typedef const __attribute__((address_space(1))) float *glb_cf_ptr;
+    glb_cf_ptr q = (glb_cf_ptr) av.rows + av.slot;
+    const uint32_t n = av.stride;
+    uint32_t r = 0u;
+    AovVals a = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#define BF_AOV_ROW(x) x = q[(size_t) (r++) * n]
+    if (av.mask & 1u) { BF_AOV_ROW(a.t); }
+    if (av.mask & 2u) { BF_AOV_ROW(a.px); BF_AOV_ROW(a.py); BF_AOV_ROW(a.pz); }
+    if (av.mask & 4u) { BF_AOV_ROW(a.u); BF_AOV_ROW(a.v); }
+    if (av.mask & 8u) { BF_AOV_ROW(a.nx); BF_AOV_ROW(a.ny); BF_AOV_ROW(a.nz); }
+    if (av.mask & 16u) { BF_AOV_ROW(a.sx); BF_AOV_ROW(a.sy); BF_AOV_ROW(a.sz); }
+    if (av.mask & 32u) { BF_AOV_ROW(a.ux); BF_AOV_ROW(a.uy); BF_AOV_ROW(a.uz); }
+    if (av.mask & 64u) { BF_AOV_ROW(a.vx); BF_AOV_ROW(a.vy); BF_AOV_ROW(a.vz); }
+#undef BF_AOV_ROW
+    return a;
+}
+// the (up to three) floats of one table entry; duv_dx / duv_dy: zeros (interaction.h:635)
+BF_DEV void aov_entry(const AovVals &a, uint32_t type, float &x, float &y, float &z) {
+    x = y = z = 0.f;
+    switch (type) {
+        case BF_AOV_DEPTH: x = a.t; break;
+        case BF_AOV_POSITION: x = a.px, y = a.py, z = a.pz; break;
+        case BF_AOV_UV: x = a.u, y = a.v; break;
+        case BF_AOV_GEO_NORMAL: x = a.nx, y = a.ny, z = a.nz; break;
+        case BF_AOV_SH_NORMAL: x = a.sx, y = a.sy, z = a.sz; break;
+        case BF_AOV_DP_DU: x = a.ux, y = a.uy, z = a.uz; break;
+        case BF_AOV_DP_DV: x = a.vx, y = a.vy, z = a.vz; break;
+        default: break;
+    }
+}
 template <int RX = 2>
 BF_DEV bool shade_vertex(const DScene &sc0, const DLaunch &lp, PathState &s, const Hit &hit, ShadowReq &sh,
-                         uint32_t &c_bounces BF_SHADEPROF_ARG BF_LANEPROF_ARG) {
+                         uint32_t &c_bounces, const AovCtx &av BF_SHADEPROF_ARG BF_LANEPROF_ARG) {
     BF_SHADEPROF_STAMP(spf_t0);
     const DScene sc = path_scene<RX>(sc0, lp, s.render);
     const bool receive = mode_receive<RX>(lp);
@@ -675,8 +728,12 @@ BF_DEV bool shade_vertex(const DScene &sc0, const DLaunch &lp, PathState &s, con
     bf_material mat;
     mat.type = ~0u;
     mat.back_material = 0u;
+    SIGeom aov_g;      // kAov: the parts of the interaction only the AOVs read (the full surface interaction computes the same si)
     if (si_valid) {
-        make_si<false, RX>(sc, s.ro, s.rd, hit, si, nullptr, path_shift(lp, s.render));
+        if (RX & kAov)
+            make_si<true, RX>(sc, s.ro, s.rd, hit, si, &aov_g, path_shift(lp, s.render));
+        else
+            make_si<false, RX>(sc, s.ro, s.rd, hit, si, nullptr, path_shift(lp, s.render));
         emitter = si.emitter;
         mat = load_material(sc, si.material);      // issued here, waited for where NEE / BSDF sampling first read it
     }
@@ -690,6 +747,7 @@ BF_DEV bool shade_vertex(const DScene &sc0, const DLaunch &lp, PathState &s, con
         // pathtime.cpp:136-140, pathtimefrequency.cpp:131-153
         if (si_valid) s.flags |= kFlagValid;
         if ((RX & kClass) && si_valid) s.cls = scene_classes(sc)[si.shape];      // the class of the path: its first intersection's shape
+        if (RX & kAov) aov_store(av, si_valid, si, aov_g);      // ... or zeros: a miss never sees the values of the slot's previous path
         if (is_range) s.aux += si_valid ? si.t : 0.f;
         if (is_time) s.aux = si_valid ? si.t / lp.time_c : 0.f;
         if (si_valid && doppler) s.dlambda += shape_doppler(sc, si, s.lambda0);   // :141-144
@@ -983,6 +1041,47 @@ template <bool MOM = false> BF_DEV void put_wide(CSensor &se, const WideSample &
         }
     }
 }
+// kAov: the AOV channels of a sample under a wide filter — the same cells and weights as put_wide gives its base channels (the
+// footprint arithmetic is put_wide's, statement by statement), value * weight per channel: the table's entries from channel 5 on,
+// nested.R G B A at channel `nch`
+BF_DEV void put_wide_aov(CSensor &se, const WideSample &ws, const HistDst &hd, const AovCtx &av, const AovVals &a, uint32_t nch, float nested,
+                         float alpha) {
+    const int border = (int) se.filt_border, n = (int) se.filt_n;
+    const float r = se.filt_radius;
+    const float px = ws.posx - ((float) (ws.offx - border) + .5f), py = ws.posy - ((float) (ws.offy - border) + .5f);
+    const int sx = ws.bw + 2 * border, sy = ws.bh + 2 * border;
+    const int lox = max((int) __builtin_ceilf(px - r), 0), loy = max((int) __builtin_ceilf(py - r), 0);
+    const int hix = min((int) __builtin_floorf(px + r), sx - 1), hiy = min((int) __builtin_floorf(py + r), sy - 1);
+    const float basex = (float) lox - px, basey = (float) loy - py;
+    for (int yr = 0; yr < n; ++yr) {
+        const int y = loy + yr;
+        if (y > hiy) break;
+        const float wy = filt_eval(se, basey + (float) yr);
+        const int gy = ws.offy + y - border - ws.cropy;
+        for (int xr = 0; xr < n; ++xr) {
+            const int x = lox + xr;
+            if (x > hix) break;
+            const float w = wy * filt_eval(se, basex + (float) xr);
+            const int gx = ws.offx + x - border - ws.cropx;
+            if (gx < 0 || gx >= ws.W || gy < 0 || gy >= ws.H) continue;
+            const uint32_t cell = ws.C * ((uint32_t) gy * (uint32_t) ws.W + (uint32_t) gx);
+            uint32_t ch = cell + 5u;
+            for (uint64_t t = av.types; t & 15u; t >>= 4) {
+                const uint32_t type = (uint32_t) (t & 15u) - 1u, nf = aov_type_floats(type);
+                float vx, vy, vz;
+                aov_entry(a, type, vx, vy, vz);
+                put_wide_add(hd, ch, vx, w);
+                if (nf > 1u) put_wide_add(hd, ch + 1u, vy, w);
+                if (nf > 2u) put_wide_add(hd, ch + 2u, vz, w);
+                ch += nf;
+            }
+            put_wide_add(hd, cell + nch + 0u, nested, w);
+            put_wide_add(hd, cell + nch + 1u, nested, w);
+            put_wide_add(hd, cell + nch + 2u, nested, w);
+            put_wide_add(hd, cell + nch + 3u, alpha, w);
+        }
+    }
+}
 // position_sample of a path's render_sample (integrator.cpp:263): the pixel it was drawn for and the first next_2d of its stream
 BF_DEV void film_position(const DLaunch &lp, const PathState &s, uint32_t &px, uint32_t &py, float &fx, float &fy) {
     uint64_t seed = lp.seed, path_offset = lp.path_offset, path_i = s.path_i;
@@ -1010,12 +1109,13 @@ BF_DEV void film_position(const DLaunch &lp, const PathState &s, uint32_t &px, u
 
 template <int RX = 2>
 BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, float *s_hist, float *g_hist, bool lds_hist,
-                     FilmAcc &acc, bf_path_record *records) {
+                     FilmAcc &acc, bf_path_record *records, const AovCtx &av = aov_none()) {
     const DScene sc = path_scene<RX>(sc0, lp, s.render);
     const bool valid = (s.flags & kFlagValid) != 0;
     ++acc.n_put;
     float rec_L, rec_aux;
-    float *const s_base = s_hist + lp.base_off;                               // rolling launches: base-channel table (DLaunch::base_off)
+    constexpr bool aov = (RX & kAov) != 0;         // BF_FLAG_AOV: the first intersection's AOVs behind the base channels, nested.RGBA last
+    float *const s_base = s_hist + (aov ? 0u : lp.base_off);                  // rolling launches: base-channel table (DLaunch::base_off; an AOV launch keeps its table word there)
     constexpr bool classed = (RX & kClass) != 0;   // BF_FLAG_CLASSES: one histogram block per class of the path's first intersection
     // this render's block of the histogram (classed: the block of the path's class within it)
     const HistDst hd = hist_dst(lp, s.render, s_hist, g_hist, lds_hist, classed ? scene_n_classes(sc0) : 0u, classed ? s.cls : 0u);
@@ -1131,6 +1231,20 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
         if (is_time && lp.color_mode == BF_COLOR_RGB) srgb_to_xyz_grey(s.result, a0, a1, a2);
         bool ok = (s.flags & kFlagFilmOk) && __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z);
         if (is_range || is_time) ok = ok && __builtin_isfinite(a0) && __builtin_isfinite(a1) && __builtin_isfinite(a2);
+        // aov.cpp:170-251: per pixel X Y Z A W | the table's K floats | nested AOVs from channel eb | nested.R G B A at rch.  The values wait
+        // in the slot's side rows since the first vertex; one of them that is not finite drops the sample like any other channel
+        const uint32_t eb = 5u + (aov ? av.K : 0u);
+        AovVals avv;
+        bool afin = true;
+        if (aov) {
+            avv = aov_load(av);
+            afin = __builtin_isfinite(s.result) && __builtin_isfinite(avv.t) && __builtin_isfinite(avv.px) && __builtin_isfinite(avv.py) &&
+                   __builtin_isfinite(avv.pz) && __builtin_isfinite(avv.u) && __builtin_isfinite(avv.v) && __builtin_isfinite(avv.nx) &&
+                   __builtin_isfinite(avv.ny) && __builtin_isfinite(avv.nz) && __builtin_isfinite(avv.sx) && __builtin_isfinite(avv.sy) &&
+                   __builtin_isfinite(avv.sz) && __builtin_isfinite(avv.ux) && __builtin_isfinite(avv.uy) && __builtin_isfinite(avv.uz) &&
+                   __builtin_isfinite(avv.vx) && __builtin_isfinite(avv.vy) && __builtin_isfinite(avv.vz);
+            ok = ok && afin;
+        }
         // moment.cpp:72-91: nested.XYZ = the XYZ of the nested (unweighted) result, then the square of every nested channel.
         // A nested AOVs; per pixel: X Y Z A W | AOVs | nested.XYZ at nch | m2_ AOVs (m2off behind each) | m2_ nested.XYZ at qch
         const uint32_t n_aov = is_range ? lp.bins : (is_time ? 3u * lp.bins : 0u);
@@ -1169,6 +1283,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
             bool fin = __builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z);
             if (is_range || is_time) fin = fin && __builtin_isfinite(a0) && __builtin_isfinite(a1) && __builtin_isfinite(a2);
             if (mom) fin = fin && mfin;
+            if (aov) fin = fin && afin;
             if (fin) {
                 WideSample ws;
                 uint32_t qx, qy;
@@ -1195,7 +1310,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 ws.five = true;
                 ws.emask = 0u;
                 ws.e3 = is_time;
-                ws.ech = 5;
+                ws.ech = (int) eb;
                 ws.e0 = a0;
                 ws.e1 = a1;
                 ws.e2 = a2;
@@ -1209,7 +1324,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                 if (is_range || is_time) {
                     float w = lp.bin_width;
                     int k = (int) __builtin_floorf(s.aux / w);
-                    ws.ech = 5 + (k - 1) * (is_time ? 3 : 1);
+                    ws.ech = (int) eb + (k - 1) * (is_time ? 3 : 1);
                     for (int i = k - 1; i <= k + 1; ++i) {
                         if (i < 0 || i >= (int) lp.bins) continue;
                         float lo = (float) i * w, hi = (float) i * w + w;
@@ -1217,6 +1332,7 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                     }
                 }
                 put_wide<mom>(c_sensor(sc), ws, hd);
+                if (aov) put_wide_aov(c_sensor(sc), ws, hd, av, avv, eb + n_aov, s.result, valid ? 1.f : 0.f);
             } else {
                 ++acc.invalid;
             }
@@ -1283,6 +1399,26 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                     acc.qZ += qZ;
                 }
             }
+            if (aov) {
+                // box filter: the value itself (a 1 x 1 film's paths all feed the same K + 4 cells, like the bins below)
+                uint32_t ch = pix + 5u;
+                for (uint64_t t = av.types; t & 15u; t >>= 4) {
+                    const uint32_t type = (uint32_t) (t & 15u) - 1u, nf = aov_type_floats(type);
+                    float vx, vy, vz;
+                    aov_entry(avv, type, vx, vy, vz);
+                    if (vx != 0.f) hist_add(s_hist, g_hist, lds_hist, ch, vx);
+                    if (nf > 1u && vy != 0.f) hist_add(s_hist, g_hist, lds_hist, ch + 1u, vy);
+                    if (nf > 2u && vz != 0.f) hist_add(s_hist, g_hist, lds_hist, ch + 2u, vz);
+                    ch += nf;
+                }
+                const uint32_t rch = pix + eb + n_aov;
+                if (s.result != 0.f) {
+                    hist_add(s_hist, g_hist, lds_hist, rch + 0u, s.result);
+                    hist_add(s_hist, g_hist, lds_hist, rch + 1u, s.result);
+                    hist_add(s_hist, g_hist, lds_hist, rch + 2u, s.result);
+                }
+                if (valid) hist_add(s_hist, g_hist, lds_hist, rch + 3u, 1.f);
+            }
             if (is_range || is_time) {
                 // range.cpp:141-161 / time.cpp:134-153: bin i takes the sample iff
                 // (float)i*w <= aux < (float)i*w + w, evaluated exactly as written
@@ -1294,16 +1430,16 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                     float lo = (float) i * w, hi = (float) i * w + w;
                     if (s.aux >= lo && s.aux < hi) {
                         if (is_range) {
-                            if (a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 5u + (uint32_t) i, a0);
-                            if (mom && a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 5u + (uint32_t) i + m2off, a0 * a0);
+                            if (a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + eb + (uint32_t) i, a0);
+                            if (mom && a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + eb + (uint32_t) i + m2off, a0 * a0);
                         } else if (a0 != 0.f || a1 != 0.f || a2 != 0.f) {
-                            hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + 0u, a0);
-                            hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + 1u, a1);
-                            hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + 2u, a2);
+                            hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 0u, a0);
+                            hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 1u, a1);
+                            hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 2u, a2);
                             if (mom) {
-                                hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + m2off + 0u, a0 * a0);
-                                hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + m2off + 1u, a1 * a1);
-                                hist_add(s_hist, g_hist, lds_hist, pix + 5u + 3u * (uint32_t) i + m2off + 2u, a2 * a2);
+                                hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 0u, a0 * a0);
+                                hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 1u, a1 * a1);
+                                hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 2u, a2 * a2);
                             }
                         }
                     }

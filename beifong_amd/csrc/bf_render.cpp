@@ -26,6 +26,7 @@ BF_LAUNCHERS()
 BF_LAUNCHERS(_fast)
 BF_LAUNCHERS(_moment)
 BF_LAUNCHERS(_class)
+BF_LAUNCHERS(_aov)      // (_aov, BF_FLAG_AOV; bf_device.h: kAov; exact build only, same wf_trace)
 #undef BF_LAUNCHERS
 extern "C" hipError_t bfk_wf_trace(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
 extern "C" hipError_t bfk_wf_trace_fast(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
@@ -44,9 +45,10 @@ const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launc
 const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast};
 const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment};
 const Kernels kClass = {bfk_launch_render_class, bfk_wf_shade_class, bfk_wf_trace, bfk_launch_tail_class};
+const Kernels kAov = {bfk_launch_render_aov, bfk_wf_shade_aov, bfk_wf_trace, bfk_launch_tail_aov};      // (BF_FLAG_AOV: with none of the three above, check_aov)
 // (BF_FLAG_MOMENT | BF_FLAG_FAST, and BF_FLAG_CLASSES with either, are refused before any kernel is chosen: check_launch)
 const Kernels &kernels_for(uint32_t flags) {
-    return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : ((flags & BF_FLAG_CLASSES) ? kClass : kExact));
+    return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : ((flags & BF_FLAG_CLASSES) ? kClass : ((flags & BF_FLAG_AOV) ? kAov : kExact)));
 }
 }  // namespace
 
@@ -85,6 +87,7 @@ RenderState::~RenderState() {
     if (last.done) (void) hipEventDestroy(last.done);
     for (hipEvent_t e : timing) (void) hipEventDestroy(e);
     if (counters) (void) hipFree(counters);
+    if (aov.rows) (void) hipFree(aov.rows);
     for (float *q : conv.scratch)
         if (q) (void) hipFree(q);
     if (conv.ws) (void) hipFree(conv.ws);
@@ -398,14 +401,19 @@ static bf_status drive_sync(const WfCtx &c, uint32_t &it, uint32_t max_iters, in
 
 // A stand-alone render.  Its first render of a shape (or any with launch plans off) is driven synchronously and learns how many
 // iterations precede the tail; later ones are planned, and the live counts that come back move the switch to where it belongs.
-static bf_status wf_render(const bf_scene *scene, const Kernels &k, const bfd::DLaunch &lp, float *hist_dev, bf_path_record *records_dev,
-                           hipStream_t stream, bool count_nodes, bool stats) {
+static bf_status aov_attach(const bf_scene *scene, uint64_t slots, bfd::DLaunch &lp);
+static bf_status wf_render(const bf_scene *scene, const Kernels &k, const bfd::DLaunch &lp_in, float *hist_dev, bf_path_record *records_dev,
+                           hipStream_t stream, bool count_nodes, bool stats, bool aov = false) {
     using Feedback = RenderState::Feedback;
     RenderState &run = scene->run;
     WfCtx c;
+    bfd::DLaunch lp = lp_in;      // (the launches read this copy: an AOV render completes it below)
     bf_status st = wf_setup(scene, k, lp, lp.n_paths, hist_dev, records_dev, stream, count_nodes, stats, c);
     if (st != BF_OK) return st;
     bfd::WF &wf = run.wf;
+    // BF_FLAG_AOV: one side-row slot per slot of the pool AS SET UP — the pool only grows, and a rolling sequence sizes it beyond
+    // tun.pool, so the slots in use are wf_setup's to say, not this launch's
+    if (aov && (st = aov_attach(scene, wf.n_slots, lp)) != BF_OK) return st;
     HIP_TRY(hipMemsetAsync(wf.n_live, 0, (bfd::kWfMaxIter + 2) * sizeof(uint32_t), stream));
     run.ev_kind.clear();
     RenderState::Plan &plan = run.plan;
@@ -787,11 +795,31 @@ bf_status check_classes(const bf_scene *scene, const bf_launch *launch, uint32_t
     return BF_OK;
 }
 
+// What a BF_FLAG_AOV launch is refused for; asked where check_classes is
+bf_status check_aov(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders) {
+    if (!(launch->flags & BF_FLAG_AOV)) return BF_OK;
+    if (!scene->run.aov.n) return fail(BF_ERR_INVALID, "BF_FLAG_AOV: the scene has no AOV table (bf_scene_set_aovs)");
+    if (launch->mode == BF_MODE_RECEIVE_RAW || launch->mode == BF_MODE_RECEIVE_IQ)
+        return fail(BF_ERR_INVALID, "BF_FLAG_AOV in a receive mode: the aov integrator wraps a sampling integrator and writes a film; the ADC has no AOV channels");
+    if (launch->flags & (BF_FLAG_FAST | BF_FLAG_MOMENT | BF_FLAG_CLASSES))
+        return fail(BF_ERR_INVALID, "BF_FLAG_AOV with %s: the AOV variants exist of the exact first-moment kernels only",
+                    (launch->flags & BF_FLAG_FAST) ? "BF_FLAG_FAST" : ((launch->flags & BF_FLAG_MOMENT) ? "BF_FLAG_MOMENT" : "BF_FLAG_CLASSES"));
+    if (launch->flags & BF_FLAG_ROLLING)
+        return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_AOV with BF_FLAG_ROLLING: a rolling sequence's histogram window and base-channel table are "
+                                        "laid out for the plain channels; render the AOVs without BF_FLAG_ROLLING");
+    const uint64_t px = multi_pixel_of(launch) ? (uint64_t) launch->film_width * launch->film_height : 1u;
+    const uint32_t K = bf_aov_floats(scene->run.aov.n, scene->run.aov.types);
+    if ((uint64_t) n_renders * (bf_launch_channels(launch) + px * (K + 4u)) > (1ull << 31))
+        return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_AOV: %u renders x %llu pixels x %u AOV floats is too large", n_renders, (unsigned long long) px, K);
+    return BF_OK;
+}
+
 // Everything a launch (of n_renders renders, if a batch) is refused for on its own or against the scene and its open rolling sequence:
 // nothing is enqueued before these
 static bf_status check_launch(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, uint32_t n_renders, const bf_stats *stats_out) {
     const EndpointState &ends = scene->ends;
     if (bf_status cst = check_classes(scene, launch, n_renders)) return cst;
+    if (bf_status ast = check_aov(scene, launch, n_renders)) return ast;
     if (batch) {
         if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_batch: n_renders is 0");
         if (launch->spp && launch->film_width && launch->film_height)
@@ -897,7 +925,7 @@ static bf_status make_dlaunch(const bf_scene *scene, const bf_launch *launch, ui
     if (lp.iq) lp.mode = BF_MODE_RECEIVE_RAW;          // the kernels see receive mode + the iq flag
     lp.bin_width = launch->bin_width;
     lp.time_c = launch->time_c;
-    lp.n_chan = bf_launch_channels(launch);
+    lp.n_chan = (launch->flags & BF_FLAG_AOV) ? bf_scene_launch_channels(scene, launch) : bf_launch_channels(launch);
     lp.chan_px = lp.n_chan / (lp.film_w * lp.film_h);
     lp.lean = lean_profile(scene, launch, receive_mode, multi_pixel) ? 1u : 0u;
     lp.wide = scene->ends.sensor_host.filt_n != 0u ? 1u : 0u;
@@ -910,6 +938,10 @@ static bf_status make_dlaunch(const bf_scene *scene, const bf_launch *launch, ui
     if (n_classes) {
         lp.lean = 0u;
         scene->run.last_variant = (scene->run.last_variant & ~(uint32_t) BF_VARIANT_LEAN) | (uint32_t) BF_VARIANT_CLASS;
+    }
+    if (launch->flags & BF_FLAG_AOV) {      // likewise; the table and the side rows join the launch in render_locked (aov_attach)
+        lp.lean = 0u;
+        scene->run.last_variant = (scene->run.last_variant & ~(uint32_t) BF_VARIANT_LEAN) | (uint32_t) BF_VARIANT_AOV;
     }
     lp.count = ((launch->flags & (BF_FLAG_STATS | BF_FLAG_COUNT)) || count) ? 1u : 0u;
     lp.doppler = (receive_mode && (launch->flags & BF_FLAG_DOPPLER)) ? 1u : 0u;
@@ -959,6 +991,40 @@ static bf_status stage_batch(const bf_scene *scene, const bf_launch *launch, con
     return stage_commit(stg, seed_bytes + off_bytes, stream);
 }
 
+// BF_FLAG_AOV: the handle's table and side rows for `slots` slots into the launch's five words (bf_device.h: AovCtx).  The rows are the
+// handle's own, grown on demand; the renders of one handle are ordered on the device (order_after_last), so one set serves them all.
+static bf_status aov_attach(const bf_scene *scene, uint64_t slots, bfd::DLaunch &lp) {
+    // (called after wf_setup / with the one-kernel variant's grid: `slots` is what the kernels index the rows with, exactly)
+    RenderState::Aov &a = scene->run.aov;
+    uint64_t types = 0;
+    uint32_t mask = 0, rows = 0;
+    for (uint32_t i = 0; i < a.n; ++i) {
+        types |= (uint64_t) (a.types[i] + 1u) << (4u * i);
+        if (a.types[i] < bfd::kAovStored && !(mask >> a.types[i] & 1u)) {
+            mask |= 1u << a.types[i];
+            rows += bfd::aov_type_floats(a.types[i]);
+        }
+    }
+    if (slots >= (1ull << 32)) return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_AOV: %llu path slots", (unsigned long long) slots);
+    const uint64_t need = std::max<uint64_t>(1, (uint64_t) rows * slots);
+    if (a.rows_floats < need) {
+        if (a.rows) {
+            // as wf_ensure grows the pool: hipFree waits for the device, so an earlier launch that reads the old rows has ended
+            (void) hipFree(a.rows);
+            a.rows = nullptr;
+            a.rows_floats = 0;
+        }
+        HIP_TRY(hipMalloc((void **) &a.rows, need * sizeof(float)));
+        a.rows_floats = need;
+    }
+    lp.roll_newest = (uint32_t) (uintptr_t) a.rows;
+    lp.roll_lo = (uint32_t) ((uint64_t) (uintptr_t) a.rows >> 32);
+    lp.base_off = (uint32_t) types;
+    lp.has_records = (uint32_t) (types >> 32);
+    lp.multi = (uint32_t) slots;
+    return BF_OK;
+}
+
 // A render or batch on a handle its caller holds (BF_ENTER).  geom_stride != 0: the batch's renders read per-render geometry
 // versions, geom_stride float4 rows apart from the arrays scene->d points at (bf_mesh.cpp: render_versions; kGeom kernels).
 bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
@@ -996,11 +1062,13 @@ bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf
         const uint64_t want = (lp.n_paths + bfd::kBlock - 1) / bfd::kBlock;
         const unsigned blocks_per_cu = (unsigned) std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / lds));
         const unsigned grid = (unsigned) std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t) scene->n_cus * blocks_per_cu));
+        // (one side-row slot per thread of the grid)
+        if ((launch->flags & BF_FLAG_AOV) && (st = aov_attach(scene, (uint64_t) grid * bfd::kBlock, lp)) != BF_OK) return st;
         HIP_TRY(kernels_for(launch->flags).render(&scene->d, &lp, hist_dev, records_dev, scene->run.counters, (launch->flags & BF_FLAG_STATS) ? 1 : 0,
                                                   grid, lds, stream));
     } else if (launch->n_paths) {
         if ((st = wf_render(scene, kernels_for(launch->flags), lp, hist_dev, records_dev, stream, (launch->flags & BF_FLAG_STATS) != 0,
-                            stats_out != nullptr)) != BF_OK) return st;
+                            stats_out != nullptr, (launch->flags & BF_FLAG_AOV) != 0u)) != BF_OK) return st;
     }
     if (stats_out) {
         HIP_TRY(hipEventRecord(ev1, stream));
@@ -1031,6 +1099,36 @@ bf_status bf_render_batch_device(const bf_scene *scene, const bf_launch *launch,
                                  bf_path_record *records_dev, void *stream, bf_stats *stats_out) {
     if (!batch) return fail(BF_ERR_INVALID, "bf_render_batch_device: null batch");
     return render_common(scene, launch, batch, hist_dev, records_dev, stream, stats_out);
+}
+
+// The handle's AOV table (BF_FLAG_AOV).  It lives on the host alone: every AOV launch carries it in its kernel arguments (aov_attach), so
+// "stream-ordered" is the order of the calls that enqueue.
+uint32_t bf_aov_floats(uint32_t n_aovs, const uint32_t *types) {
+    if (!types || n_aovs == 0 || n_aovs > BF_MAX_AOVS) return 0u;
+    uint32_t K = 0;
+    for (uint32_t i = 0; i < n_aovs; ++i) {
+        if (types[i] >= (uint32_t) BF_AOV_TYPES) return 0u;
+        K += bfd::aov_type_floats(types[i]);
+    }
+    return K;
+}
+
+bf_status bf_scene_set_aovs(bf_scene *scene, uint32_t n_aovs, const uint32_t *types, void *stream_) {
+    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_set_aovs: null scene");
+    if (n_aovs > BF_MAX_AOVS) return fail(BF_ERR_INVALID, "bf_scene_set_aovs: n_aovs %u exceeds BF_MAX_AOVS (%u)", n_aovs, (unsigned) BF_MAX_AOVS);
+    if (n_aovs && !types) return fail(BF_ERR_INVALID, "bf_scene_set_aovs: types is null");
+    for (uint32_t i = 0; i < n_aovs; ++i)
+        if (types[i] >= (uint32_t) BF_AOV_TYPES)
+            return fail(BF_ERR_INVALID, "bf_scene_set_aovs: types[%u] = %u is not a BF_AOV_* type (below %u)", i, types[i], (unsigned) BF_AOV_TYPES);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    // an open rolling sequence ends here, as for bf_scene_set_classes
+    bf_status st = order_after_last(scene, stream);
+    if (st == BF_OK) st = close_sequence(scene, stream);
+    if (st != BF_OK) return st;
+    scene->run.aov.n = n_aovs;
+    for (uint32_t i = 0; i < n_aovs; ++i) scene->run.aov.types[i] = types[i];
+    return BF_OK;
 }
 
 bf_status bf_scene_flush(bf_scene *scene, void *stream_, bf_stats *stats_out) {
@@ -1167,6 +1265,8 @@ bf_status bf_render_converge_device(bf_scene *scene, const bf_launch *launch, fl
     if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: the rounds are batches, which do not roll", fn);
     if (launch->flags & BF_FLAG_CLASSES)
         return fail(BF_ERR_UNSUPPORTED, "%s BF_FLAG_CLASSES: the rounds are moment renders, which have no class variants (per-class error bars are a follow-up)", fn);
+    if (launch->flags & BF_FLAG_AOV)
+        return fail(BF_ERR_UNSUPPORTED, "%s BF_FLAG_AOV: the rounds are moment renders, which have no AOV variants", fn);
     if (!(target >= 0.f)) return fail(BF_ERR_INVALID, "%s target %g is negative or NaN", fn, (double) target);
     if (!floor_ok(floor)) return fail(BF_ERR_INVALID, "%s floor %g is outside [0, 1]", fn, (double) floor);
     if (round_renders == 0 || max_rounds == 0) return fail(BF_ERR_INVALID, "%s round_renders and max_rounds must be at least 1", fn);
@@ -1241,6 +1341,8 @@ bf_status bf_render_converge(bf_scene *scene, const bf_launch *launch, float tar
     if (!scene || !launch || !hist_out || !rounds_out) return fail(BF_ERR_INVALID, "bf_render_converge: null argument");
     if (launch->flags & BF_FLAG_CLASSES)
         return fail(BF_ERR_UNSUPPORTED, "bf_render_converge: BF_FLAG_CLASSES: the rounds are moment renders, which have no class variants (per-class error bars are a follow-up)");
+    if (launch->flags & BF_FLAG_AOV)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_converge: BF_FLAG_AOV: the rounds are moment renders, which have no AOV variants");
     bf_launch lm = *launch;
     lm.flags |= BF_FLAG_MOMENT;
     const size_t bytes = (size_t) bf_launch_channels(&lm) * sizeof(float);

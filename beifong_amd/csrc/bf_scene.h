@@ -165,6 +165,13 @@ struct __attribute__((visibility("hidden"))) RenderState {
     float ms[3] = {0, 0, 0};                    // trace, shade, tail
     uint32_t iters = 0, trace_launches = 0, tail_launches = 0, shade_launches = 0;
     uint32_t last_variant = 0;                  // BF_VARIANT_* of the latest render (bf_stats.kernel_variant)
+    // ---- the AOV table of the handle (bf_scene_set_aovs; BF_FLAG_AOV) and the side rows its launches carry the values in ----
+    struct Aov {
+        uint32_t n = 0;                          // entries; 0: no table
+        uint32_t types[BF_MAX_AOVS] = {};        // BF_AOV_*, in channel order
+        float *rows = nullptr;                   // device side rows (bf_device.h: AovCtx), allocated by the first AOV launch, grown on demand
+        uint64_t rows_floats = 0;
+    } aov;
     // ---- rolling sequence (bf_render_device with BF_FLAG_ROLLING, bf_scene_flush): see wf_roll_render ----
     struct Roll {
         bool open = false;
@@ -378,6 +385,7 @@ bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
 bf_status mark_last(const bf_scene *scene, hipStream_t stream);
 bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
 bf_status check_classes(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders);      // BF_FLAG_CLASSES refusals, before any device work
+bf_status check_aov(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders);          // BF_FLAG_AOV refusals, likewise
 bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev, bf_path_record *records_dev,
                         void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0);
 void fill_stats(const bf_scene *scene, const unsigned long long *c, uint64_t n_paths, bf_stats *st);

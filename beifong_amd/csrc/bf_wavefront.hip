@@ -185,6 +185,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
     SurvAlloc sv = {0ull, 0u, 0u, EVICT ? wf.surv_cursor[0] : 0u};
 
     FilmAcc acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0u, 0u};
+    AovCtx av = (RX & kAov) ? aov_ctx(lp) : aov_none();      // kAov: the side rows of the lane's slot (an AOV launch never evicts: the slot is the path's for life)
     uint32_t c_closest = 0, c_shadow = 0, c_bounces = 0, c_live = 0, c_traced = 0, c_loads = 0, c_shq = 0;
 #ifdef BF_SHADE_PROF
     const bool lpf = BF_SHADE_PROF >= 2;      // -DBF_SHADE_PROF=2: lane counts per section too (an atomic pair per entry: the cycle shares are then perturbed)
@@ -229,6 +230,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
             aligned = __all(aligned);
         }
         bool has = (uint32_t) lane < got;
+        if (RX & kAov) av.slot = slot;
         const uint32_t batch0 = slot >> 6;
         // wake: only the slots without a live path — as of NOW: wf_shade<0> of this iteration has run, so a slot whose path
         // ended there, or moved to the survivor area, is free
@@ -263,7 +265,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
                 SLP(1, (s.flags & kFlagTermPending) != 0);
                 if (s.flags & kFlagTermPending) {
                     // ended after last bounce's BSDF sample; its NEE shadow ray has resolved by now
-                    film_put<RX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records);
+                    film_put<RX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records, av);
                     need_gen = true;
                 } else {
                     float4 hq = wf.hit(slot);
@@ -295,14 +297,14 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
             if (!settled && have_hit) {
                 have_hit = false;
 #ifdef BF_SHADE_PROF
-                cont = shade_vertex<RX>(sc, lp, s, hit, sh, c_bounces, &spf, lpf);
+                cont = shade_vertex<RX>(sc, lp, s, hit, sh, c_bounces, av, &spf, lpf);
 #else
-                cont = shade_vertex<RX>(sc, lp, s, hit, sh, c_bounces);
+                cont = shade_vertex<RX>(sc, lp, s, hit, sh, c_bounces, av);
 #endif
                 SLT(7);
                 SLP(5, !cont);
                 if (!cont) {
-                    film_put<RX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records);
+                    film_put<RX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records, av);
                     need_gen = true;
                 } else if (!(s.flags & kFlagTermPending)) {
                     ++c_closest;
@@ -366,7 +368,7 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
             if (chain) {
                 if (s.flags & kFlagTermPending) {
                     // the path ended at its last BSDF sample and its NEE ray is answered: bin it now
-                    film_put<RX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records);
+                    film_put<RX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records, av);
                     need_gen = true;
                     cont = false;
                 } else {
@@ -731,7 +733,7 @@ extern "C" int bfdbg_shade_lane_profile(unsigned long long *out, int clear) {
 // moment: the kMoment variants (BF_FLAG_MOMENT; bfk_wf_shade_moment below); classed: the kClass variants (BF_FLAG_CLASSES; bfk_wf_shade_class)
 static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                  hipStream_t stream, int waves, bool moment, bool classed = false) {
+                                  hipStream_t stream, int waves, bool moment, bool classed = false, bool aov = false) {
     // `waves`: register budget of the shading kernel (waves per SIMD); 3 is the sweet spot (168 VGPRs)
     const bool rx = lp->mode == BF_MODE_RECEIVE_RAW;
 #define BF_SHADE_LAUNCH_RX(F, W, RX_)                                                                                              \
@@ -810,8 +812,22 @@ static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp,
     }
 #undef BF_SHADE_LAUNCH_CLS_F
 #undef BF_SHADE_LAUNCH_CLS
+    // BF_FLAG_AOV (render modes; never with BF_FLAG_FAST, BF_FLAG_MOMENT, BF_FLAG_CLASSES or a rolling sequence, whose DLaunch words
+    // carry the AOV table here): the kAov variants of the same general forms
+#define BF_SHADE_LAUNCH_AOV_F(V)                                  \
+    if (first) { BF_SHADE_LAUNCH_RX(1, 3, 0 | bfd::kAov | (V)); } \
+    else { BF_SHADE_LAUNCH_RX(0, 3, 0 | bfd::kAov | (V)); }
+    if (aov) {
+        if (first >= 2 || rx || lp->roll) return hipErrorInvalidValue;
+        if (lp->geom_stride && lp->wide) { BF_SHADE_LAUNCH_AOV_F(bfd::kGeom | bfd::kWide) }
+        else if (lp->geom_stride) { BF_SHADE_LAUNCH_AOV_F(bfd::kGeom) }
+        else if (lp->wide) { BF_SHADE_LAUNCH_AOV_F(bfd::kWide) }
+        else { BF_SHADE_LAUNCH_AOV_F(0) }
+        return hipGetLastError();
+    }
+#undef BF_SHADE_LAUNCH_AOV_F
 #else
-    if (moment || classed) return hipErrorInvalidValue;
+    if (moment || classed || aov) return hipErrorInvalidValue;
 #endif
     if (lp->geom_stride) {
         // per-render geometry versions (bf_render_motion_batch_device): three waves per SIMD; never a rolling sequence, so
@@ -875,6 +891,11 @@ extern "C" hipError_t bfk_wf_shade_class(const bfd::DScene *sc, const bfd::DLaun
                                          float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
                                          hipStream_t stream, int waves) {
     return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, true);
+}
+extern "C" hipError_t bfk_wf_shade_aov(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                       float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                       hipStream_t stream, int waves) {
+    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, false, true);
 }
 #endif
 

@@ -675,7 +675,15 @@ void SamplingIntegrator::run(Scene *scene, const Endpoint *endpoint, const bf_la
     m_converge = ConvergeResult();
     const ConvergeSpec *cs = converge();
     auto t0 = std::chrono::steady_clock::now();
-    if (!cs || !(cs->rel_stderr > 0.f)) {
+    if (lp.flags & BF_FLAG_AOV) {
+        // the aov integrator: its table goes to the handle first; one GPU (the sharded render has no AOV form)
+        if (cs) Throw("aov: \"rel_stderr\" renders are refused: the rounds are moment renders, which have no AOV form (bf_render_converge)");
+        const std::vector<uint32_t> types = aov_types();
+        bf_scene *dev = scene->device_scene(endpoint);
+        bf_status st = bf_scene_set_aovs(dev, (uint32_t) types.size(), types.data(), nullptr);
+        if (st == BF_OK) st = bf_render(dev, &lp, hist, nullptr, &m_stats.stats);
+        if (st != BF_OK) Throw("bf_render failed (status %d): %s", st, bf_last_error());
+    } else if (!cs || !(cs->rel_stderr > 0.f)) {
         bf_status st = render_on_gpus(scene, endpoint, lp, hist, &m_stats.stats);
         if (st != BF_OK) Throw("bf_render failed (status %d): %s", st, bf_last_error());
     } else {
@@ -734,7 +742,12 @@ bool SamplingIntegrator::render(Scene *scene, Sensor *sensor) {
     configure(lp);
     if (fast_math()) lp.flags |= BF_FLAG_FAST;
     if (lp.mode == BF_MODE_RECEIVE_RAW) Throw("this integrator only supports receive(), not render()");
+    // (BF_FLAG_AOV: the K AOV floats and nested.R G B A on top — the same count bf_scene_launch_channels gives once the table is set)
     uint32_t n = bf_launch_channels(&lp);
+    if (lp.flags & BF_FLAG_AOV) {
+        const std::vector<uint32_t> types = aov_types();
+        n += (bf_aov_floats((uint32_t) types.size(), types.data()) + 4u) * film->width() * film->height();
+    }
     if (n != channels.size() * film->width() * film->height())
         Throw("internal error: channel count mismatch (%u vs %zu)", n, channels.size() * film->width() * film->height());
     std::vector<float> hist(n);

@@ -299,6 +299,9 @@ public:
     bool render(Scene *scene, Sensor *sensor) override;
     bool receive(Scene *scene, Receiver *receiver) override;
     virtual std::vector<std::string> aov_names() const { return {}; }
+    /// the BF_AOV_* table of a launch that carries BF_FLAG_AOV (the aov integrator alone names one): render() hands it to
+    /// bf_scene_set_aovs before the render
+    virtual std::vector<uint32_t> aov_types() const { return {}; }
     /// BF_MODE_* + binning parameters for bf_launch
     virtual void configure(bf_launch &launch) const = 0;
     /// MonteCarloIntegrator parameters; AOV wrappers (range, time, phase) forward to their sub-integrator

@@ -14,7 +14,7 @@ _OBJECT_TAGS = {
 # plugin type -> XML tag (class aliases, xml.cpp:153-161)
 _PLUGIN_TAG = {
     "path": "integrator", "pathlength": "integrator", "pathtime": "integrator", "range": "integrator", "time": "integrator",
-    "pathtimefrequency": "integrator", "phase": "integrator", "moment": "integrator", "rectangle": "shape", "obj": "shape", "ply": "shape", "diffuse": "bsdf",
+    "pathtimefrequency": "integrator", "phase": "integrator", "moment": "integrator", "aov": "integrator", "rectangle": "shape", "obj": "shape", "ply": "shape", "diffuse": "bsdf",
     "twosided": "bsdf", "roughconductor": "bsdf", "spot": "emitter", "point": "emitter", "area": "emitter",
     "areatransmitter": "transmitter", "wignertransmitter": "transmitter", "phasedtransmitter": "transmitter",
     "fluxmeter": "sensor", "irradiancemeter": "sensor", "radiancemeter": "sensor", "perspective": "sensor",

@@ -359,6 +359,35 @@ enum {
                                   BF_ERR_UNSUPPORTED (deliberately out of scope: a rolling sequence's LDS window and base-channel
                                   table hold one block per render; shards and converge rounds are built on those and on moment
                                   renders). */
+    BF_FLAG_AOV = 2048u,       /* aov integrator (src/integrators/aov.cpp:83-150,170-251 around the launch's mode, one nested
+                                  integrator): every pixel also carries the arbitrary output variables of the handle's AOV table
+                                  (bf_scene_set_aovs), taken from the SurfaceInteraction of the path's FIRST intersection (the one
+                                  bf_path_record.valid reports and shading starts from); all of them are zero when the first ray
+                                  leaves the scene (aov.cpp:167).  Per pixel, K = bf_aov_floats(table):
+                                    X Y Z A W | the K AOV floats in table order | nested AOVs (0 path, bins range, 3 bins time) |
+                                    nested.R nested.G nested.B nested.A
+                                  X Y Z A W and the nested AOVs are the plain render's; nested.R = nested.G = nested.B is the
+                                  unweighted nested result (what the range bins receive; one grey lane, replicated in both colour
+                                  modes), nested.A is 1 for a valid first hit, else 0.  si.uv is prim_uv for rectangles and for
+                                  meshes without texture coordinates; with them it is (uv0 * b0 + uv1 * b1) + uv2 * b2 per
+                                  component, b0 = 1 - b1 - b2 (mesh.cpp:470-500), in plain fp32: three roundings of the products,
+                                  two of the sums in that order, no contraction — the order si.p is interpolated in.  DUV_DX and
+                                  DUV_DY are always 0 (interaction.h:635; aov.cpp never computes partials).
+                                  Addends: the value itself under the box filter, the fp32 product w * x under a wider one, as
+                                  for every other channel.  ImageBlock::put takes or drops a sample as a whole: a sample with ANY
+                                  non-finite channel (an AOV value, or a radiance that turns non-finite bounces later) adds to no
+                                  channel and counts in bf_stats.n_invalid.  Per-path records are bit-equal to the plain render's.
+                                  bf_scene_launch_channels gives the floats per render; batches [render][that layout].
+                                  Honoured by bf_render / bf_render_batch / bf_render_motion_batch / bf_render_deform_batch and
+                                  their _device forms, in modes PATH, RANGE and TIME, on 1 x 1 and W x H films, with crop windows
+                                  and wide filters, with BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL and BF_FLAG_STATS.  LDS
+                                  privatisation is decided on the new channel count.  The AOV variants exist of the general
+                                  kernels only: bf_stats.kernel_variant carries BF_VARIANT_AOV and never BF_VARIANT_LEAN.
+                                  Refused before anything is enqueued, an open rolling sequence staying intact: without an AOV
+                                  table, in a receive mode, or with BF_FLAG_FAST, BF_FLAG_MOMENT or BF_FLAG_CLASSES:
+                                  BF_ERR_INVALID; with BF_FLAG_ROLLING, by the sharded renders and by the converge renders:
+                                  BF_ERR_UNSUPPORTED (a rolling sequence's LDS window and base-channel table are laid out for the
+                                  plain channels; shards and converge rounds are built on those and on moment renders). */
     BF_FLAG_DOPPLER = 8u       /* receive modes: the Doppler hook the reference carries commented out
                                   ("Took doppler out to test", pathtimefrequency.cpp:124-126,141-144,180-183):
                                   the path's wavelength is shifted by Shape::doppler(si) =
@@ -416,10 +445,11 @@ typedef struct bf_stats {
                                   Same results either way (BF_LEAN=0 in the environment forces the general ones).  ORed with
                                   BF_VARIANT_FAST when the fast-arithmetic build ran (BF_FLAG_FAST) and with BF_VARIANT_MOMENT
                                   when the kernels' second-moment variants ran (BF_FLAG_MOMENT); BF_VARIANT_CLASS = the class
-                                  variants ran (BF_FLAG_CLASSES: general kernels, so never with BF_VARIANT_LEAN)                */
+                                  variants ran (BF_FLAG_CLASSES: general kernels, so never with BF_VARIANT_LEAN); BF_VARIANT_AOV =
+                                  the AOV variants ran (BF_FLAG_AOV: likewise)                                                 */
     uint32_t reserved_;
 } bf_stats;
-enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4, BF_VARIANT_MOMENT = 8, BF_VARIANT_CLASS = 16 };
+enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4, BF_VARIANT_MOMENT = 8, BF_VARIANT_CLASS = 16, BF_VARIANT_AOV = 32 };
 
 typedef struct bf_scene_info {
     uint32_t n_shapes, n_rects, n_triangles, n_bvh_nodes;
@@ -616,6 +646,32 @@ uint32_t bf_launch_channels(const bf_launch *launch);
 bf_status bf_scene_set_classes(bf_scene *scene, uint32_t n_classes, const uint32_t *shape_class /* host [n_shapes] */, uint32_t miss_class,
                                void *stream);
 uint32_t bf_scene_launch_channels(const bf_scene *scene, const bf_launch *launch);
+
+/* Arbitrary output variables (BF_FLAG_AOV).  A scene handle carries an optional AOV table: a list of BF_AOV_* types, in the order
+ * their channels follow X Y Z A W in every pixel; a type may appear more than once.
+ *   bf_aov_floats returns K, the floats the list occupies per pixel (0 for an invalid list: no entry, more than BF_MAX_AOVS, an
+ *   unknown type, or a null pointer); it needs no device.
+ *   bf_scene_set_aovs is stream-ordered like bf_scene_set_classes: renders enqueued afterwards see the new table; the caller's
+ *   array is free on return.  It flushes an open rolling sequence.  n_aovs = 0 clears the table.  BF_ERR_INVALID for an unknown
+ *   type or n_aovs > BF_MAX_AOVS.  bf_scene_clone copies the table; endpoint updates, mesh transforms, vertex updates and BVH
+ *   rebuilds leave it alone.
+ *   bf_scene_launch_channels returns film_w * film_h * (5 + K + nested AOVs + 4) for a launch that carries BF_FLAG_AOV in a render
+ *   mode on a handle with a table (the layout at the flag).
+ *   An AOV launch carries its values from each path's first vertex to its end in device rows of the handle's own: the first AOV
+ *   launch of a handle, and any later one that needs more of them (more path slots, a table with more components), allocates —
+ *   and, growing, frees, which waits for the device — exactly as a render that grows the handle's path pool does.  Such a call
+ *   is not asynchronous and cannot be captured into a graph; repeated launches of one shape are. */
+enum { BF_AOV_DEPTH = 0,   /* 1 float : si.t                    */
+       BF_AOV_POSITION,    /* 3       : si.p                    */
+       BF_AOV_UV,          /* 2       : si.uv                   */
+       BF_AOV_GEO_NORMAL,  /* 3       : si.n                    */
+       BF_AOV_SH_NORMAL,   /* 3       : si.sh_frame.n           */
+       BF_AOV_DP_DU, BF_AOV_DP_DV,   /* 3 each                  */
+       BF_AOV_DUV_DX, BF_AOV_DUV_DY, /* 2 each: always 0 (interaction.h:635; aov.cpp never computes partials) */
+       BF_AOV_TYPES };
+#define BF_MAX_AOVS 16
+uint32_t bf_aov_floats(uint32_t n_aovs, const uint32_t *types);
+bf_status bf_scene_set_aovs(bf_scene *scene, uint32_t n_aovs, const uint32_t *types /* host [n_aovs] */, void *stream);
 
 /* Render into a DEVICE buffer hist_dev[film_h*film_w*channels] (accumulates;
  * caller zeroes).  stream is a hipStream_t (NULL = default stream).  The call
