@@ -127,14 +127,14 @@ __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DSce
             const uint32_t got = cursor_take(rcur, (uint32_t) __popcll(need), !alive && !done, rank, slot, lane);
             if (!alive && !done) {
                 if (rank < got) {
-                    load_state(wf, slot, receive, s, (kRX & kClass) != 0);
+                    float4 hq;
+                    load_state(wf, slot, receive, s, hq, (kRX & kClass) != 0);
                     if (kRX & kAov) av.slot = slot;
                     regen_ok = slot < wf.n_main;
                     alive = true;
                     need_closest = false;          // traced (and counted) by wf_trace already
                     film = false;
                     if (!(s.flags & kFlagTermPending)) {
-                        float4 hq = wf.hit(slot);
                         hit.t = hq.x;
                         hit.u = hq.y;
                         hit.v = hq.z;

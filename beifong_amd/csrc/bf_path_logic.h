@@ -25,6 +25,8 @@ BF_NS_BEGIN
 constexpr uint32_t kFlagValid = 1u << 24, kFlagFilmOk = 1u << 25, kFlagTermPending = 1u << 26, kDepthMask = 0xffffffu;
 // multi-pixel films: the sample landed in the left / upper neighbour of the pixel it was drawn in (ImageBlock::put)
 constexpr uint32_t kFlagFilmLeft = 1u << 27, kFlagFilmUp = 1u << 28;
+// the stored state lacks the term of the NEE shadow ray wf_shade handed to wf_trace with it: load_state adds it (stored states only)
+constexpr uint32_t kFlagShadowPending = 1u << 29;
 
 struct PathState {
     V3 ro, rd;
@@ -46,10 +48,15 @@ struct PathState {
     uint32_t cls;        // kClass: shape_class of the path's first intersection, miss_class until then (the other variants never touch it: no register)
 };
 
-// `classed`: a compile-time constant at every call site ((V & kClass) != 0)
-BF_DEV void load_state(const WF &wf, uint32_t i, bool receive, PathState &s, bool classed = false) {
+// `classed`: a compile-time constant at every call site ((V & kClass) != 0).  `hq`: the slot's hit row — the same 64-byte record as
+// the ray, fetched with the state (the caller reads it unless the path's film write is pending).
+// Two round trips: the state rows and the hit; then, only for a state stored with kFlagShadowPending, the row that holds the
+// shadow request's contribution and wf_trace's answer — the round trip the hit used to take, and no third cache line for the
+// states that wait for no shadow ray.
+BF_DEV void load_state(const WF &wf, uint32_t i, bool receive, PathState &s, float4 &hq, bool classed = false) {
     float4 r0 = wf.ray0(i), r1 = wf.ray1(i), a = wf.sa(i), bb = wf.sb(i);
     uint4 d = wf.sd(i);
+    hq = wf.hit(i);
     s.ro = mk(r0.x, r0.y, r0.z);
     s.rmint = r0.w;
     s.rd = mk(r1.x, r1.y, r1.z);
@@ -75,6 +82,17 @@ BF_DEV void load_state(const WF &wf, uint32_t i, bool receive, PathState &s, boo
         s.t_rx = e.y;
         s.lambda0 = e.z;
         s.phase = e.w;
+    }
+    if (s.flags & kFlagShadowPending) {
+        // wf_trace has answered the shadow ray stored with this state (q.z: occluded).  Scene::sample_emitter_direction zeroes
+        // the VALUE of an occluded sample (scene.cpp:220-224) and the integrator still adds mis * throughput * bsdf * 0: a
+        // NaN / inf BSDF value survives that product.  c * 0 is that term (+-0 for every finite c).  Applied before anything
+        // else touches the state: the same fp32 add wf_shade does for a ray it answers itself.
+        const float4 q = wf.sh23(i);
+        const bool occ = __float_as_uint(q.z) != 0u;
+        s.result += occ ? q.x * 0.f : q.x;
+        if (receive && wf.iq) s.phase += occ ? q.y * 0.f : q.y;      // BF_MODE_RECEIVE_IQ: the imaginary accumulator
+        s.flags &= ~kFlagShadowPending;
     }
 }
 BF_DEV void store_state(const WF &wf, uint32_t j, bool receive, const PathState &s, bool classed = false) {

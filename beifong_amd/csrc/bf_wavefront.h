@@ -32,9 +32,11 @@ constexpr uint32_t kTailRowJobs = 12;      // tail: up to three passes of four r
 
 // Per-slot state layout: three 64-byte RECORDS per slot,
 //   A = ray0, ray1, hit, (hit_prim, render, dop, cls)    what wf_trace reads / writes for a closest-hit ray: ONE line
-//   B = sa, sb, sd, se                                   the rest of the path state (wf_shade; wf_trace adds a released
-//                                                        NEE contribution to sa.w / se.w)
-//   C = sh0, sh1, (sh2, sh3, -, -), -                    the NEE shadow request
+//   B = sa, sb, sd, se                                   the rest of the path state (wf_shade alone reads and writes it)
+//   C = sh0, sh1, (sh2, sh3, occ, -), -                  the NEE shadow request and its answer: wf_shade stores the ray, its
+//                                                        contribution and occ = 0 (and sets kFlagShadowPending in sb); wf_trace
+//                                                        stores occ = 1 for an occluded ray and nothing else; the slot's next
+//                                                        reader adds the term (bf_path_logic.h: load_state)
 // Most launches GATHER sparse slots through the mask cursor (a few per cent to a third of a batch alive): with one
 // array per row (rounds 1-2: "a wave touching one dense batch reads 1 KiB contiguous per array") a gathered lane touches seven cache lines for its state and six more to write it back; with records, two and two.
 #define BF_HD __host__ __device__ __forceinline__
@@ -57,6 +59,8 @@ struct WF {
     BF_HD float4 &sh1(uint32_t i) const { return recC[4 * (size_t) i + 1]; }        // d.xyz, maxt
     BF_HD float &sh2(uint32_t i) const { return reinterpret_cast<float *>(recC + 4 * (size_t) i + 2)[0]; }   // contribution released when unoccluded
     BF_HD float &sh3(uint32_t i) const { return reinterpret_cast<float *>(recC + 4 * (size_t) i + 2)[1]; }   // BF_MODE_RECEIVE_IQ: its imaginary part
+    BF_HD uint32_t &occ(uint32_t i) const { return reinterpret_cast<uint32_t *>(recC + 4 * (size_t) i + 2)[2]; }   // 1: wf_trace found the shadow ray occluded
+    BF_HD float4 &sh23(uint32_t i) const { return recC[4 * (size_t) i + 2]; }       // (sh2, sh3, occ, -) as one row
     uint32_t has_render;     // batched / rolling launches: render(i) = render index of the slot's current path (selects seed, histogram, mesh offset)
     uint32_t has_dop;        // BF_FLAG_DOPPLER: dop(i) = wavelength shift accumulated by the slot's path (nm)
     const float4 *offsets;   // batched launches with moving meshes: DLaunch::batch_offsets (wf_trace has no DLaunch)
@@ -78,7 +82,7 @@ struct WF {
     uint32_t *n_live;               // [kWfMaxIter + 2] live slots after shading bounce `it`
     unsigned long long *counters;   // CTR_* (bf_device.h)
     uint32_t trace_refill, trace_stragglers;   // wf_trace scheduling thresholds (see bf_wavefront.hip)
-    uint32_t iq;                               // BF_MODE_RECEIVE_IQ
+    uint32_t iq;                               // BF_MODE_RECEIVE_IQ (load_state: the pending shadow term has an imaginary part)
     uint32_t shade_chain;                      // wf_shade: vertices a lane may shade per visit while its rays resolve early
     uint32_t row_jobs;                         // tail: waves holding at most this many rays trace them one per 16-lane row (traverse_row16)
     uint32_t n_slots;               // slots in use this render (multiple of 64): n_main + n_surv

@@ -13,8 +13,9 @@
 //              rays are all answered that way shades its next vertex in the same visit (up to kShadeChain).
 //   wf_trace : persistent waves with dynamic ray replacement walk the four-wide BVH for the rays that do enter
 //              the mesh: while-while traversal, 16-entry LDS stack per lane (+ HBM spill), the tree's top 85 nodes
-//              in LDS.  Closest hits go to hit[slot]; an unoccluded shadow ray releases its NEE contribution into
-//              the slot's result.
+//              in LDS.  Closest hits go to hit[slot]; an occluded shadow ray sets occ[slot].  It reads and writes no
+//              other path state: the NEE contribution a shadow ray gates is added by the slot's next reader
+//              (kFlagShadowPending, load_state), which loads the state anyway.
 //
 // The tail of a render (few, long paths) is finished by bf_render_kernel<.., RESUME = true> (bf_kernels.hip).
 // All arithmetic is fp32 (the transcendentals are the engine's own fp32 specification, bf_device_math.h; the few
@@ -260,15 +261,15 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
                     s.path_i = ((uint64_t) d.w << 32) | d.z;
                 }
             } else {
-                load_state(wf, slot, receive, s, (RX & kClass) != 0);
+                float4 hq;
+                load_state(wf, slot, receive, s, hq, (RX & kClass) != 0);
                 ++c_loads;
                 SLP(1, (s.flags & kFlagTermPending) != 0);
                 if (s.flags & kFlagTermPending) {
-                    // ended after last bounce's BSDF sample; its NEE shadow ray has resolved by now
+                    // ended after last bounce's BSDF sample; its NEE shadow ray has resolved by now (load_state has added its term)
                     film_put<RX>(sc, lp, s, s_hist, g_hist, lds_hist, acc, records, av);
                     need_gen = true;
                 } else {
-                    float4 hq = wf.hit(slot);
                     hit.t = hq.x;
                     hit.u = hq.y;
                     hit.v = hq.z;
@@ -406,13 +407,15 @@ __global__ __launch_bounds__(kBlock, W) void wf_shade(DScene sc_arg, DLaunch lp,
                 wf.hit(dst) = make_float4(hit.t, hit.u, hit.v, __int_as_float(hit.slot));
                 wf.hit_prim(dst) = hit.prim;
             }
+            // a shadow ray handed to wf_trace: its term is still missing from s.result (/ s.phase); whoever loads the state next
+            // adds it (load_state), with the answer wf_trace leaves in occ
+            if (shadowing) s.flags |= kFlagShadowPending;
             store_state(wf, dst, receive, s, (RX & kClass) != 0);
             ++c_live;
             if (shadowing) {
                 wf.sh0(dst) = make_float4(sh.o.x, sh.o.y, sh.o.z, sh.mint);
                 wf.sh1(dst) = make_float4(sh.d.x, sh.d.y, sh.d.z, sh.maxt);
-                wf.sh2(dst) = sh.c;
-                if (receive && lp.iq) wf.sh3(dst) = sh.c_im;
+                wf.sh23(dst) = make_float4(sh.c, (receive && lp.iq) ? sh.c_im : 0.f, __uint_as_float(0u), 0.f);      // sh2, sh3, occ = 0
             }
         } else if (has && rolling && touched) {
             // the slot has run out of paths for now: remember the last one it rendered, so that the wake launch of the
@@ -671,22 +674,8 @@ __global__ __launch_bounds__(kBlock, W) void wf_trace(DScene sc, WF wf, uint32_t
             // (c) retire finished rays
             if (has && node == kNoNode) {
                 if (any) {
-                    // Scene::ray_test resolved: an unoccluded shadow ray releases its NEE contribution
-                    // (an occluded sample contributes c * 0, scene.cpp:220-224: only a non-finite c leaves a trace)
-                    const float c = wf.sh2(job);
-                    if (!found || !__builtin_isfinite(c)) {
-                        float4 a = wf.sa(job);
-                        a.w += found ? c * 0.f : c;
-                        wf.sa(job) = a;
-                    }
-                    if (wf.iq) {                     // BF_MODE_RECEIVE_IQ: imaginary accumulator lives in se.w
-                        const float ci = wf.sh3(job);
-                        if (!found || !__builtin_isfinite(ci)) {
-                            float4 e = wf.se(job);
-                            e.w += found ? ci * 0.f : ci;
-                            wf.se(job) = e;
-                        }
-                    }
+                    // Scene::ray_test resolved: the one thing the slot's next reader needs to know (load_state adds the term)
+                    if (found) wf.occ(job) = 1u;
                 } else {
                     wf.hit(job) = make_float4(best.t, best.u, best.v, __int_as_float(best.slot));
                     if (wf.hit_split && best.t != BF_INF) atomicOr(&wf.m_hit[nxt][job >> 6], 1ull << (job & 63u));
