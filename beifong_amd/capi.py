@@ -160,6 +160,7 @@ EXPORTED_SYMBOLS = [
     "bf_scene_flush", "bf_scene_sync", "bf_shard_range", "bf_render_sharded_device", "bf_render_sharded", "bf_allreduce_device",
     "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
     "bf_scene_update_vertices", "bf_scene_update_vertices_device", "bf_render_deform_batch_device", "bf_render_deform_batch",
+    "bf_scene_set_skin", "bf_scene_pose_skin", "bf_render_skin_batch_device", "bf_render_skin_batch",
     "bf_scene_rebuild_bvh", "bf_scene_read_bvh",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
     "bf_bsdf_eval_pdf", "bf_bsdf_eval_pdf_device", "bf_bsdf_sample", "bf_bsdf_sample_device",
@@ -237,6 +238,11 @@ def load_library(path=None):
                                                   vp, vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_render_deform_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp,
                                            C.POINTER(bf_stats)]
+    lib.bf_scene_set_skin.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    lib.bf_scene_pose_skin.argtypes = [vp, C.c_uint32, vp, vp]
+    lib.bf_render_skin_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp,
+                                                C.POINTER(bf_stats)]
+    lib.bf_render_skin_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_trace_closest.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bf_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bf_ray_intersect.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
@@ -617,6 +623,45 @@ def deform_tables(positions, normals=None, n_vertices=None):
     return n_renders, np.asarray(shapes, np.uint32), pos, nrm
 
 
+def bone_array(a, name, n_bones=None, n_renders=None):
+    """A float32 bone table for a skin pose, checked: [n_bones, 3, 4] for one pose, [K, n_bones, 3, 4] for a batch (a trailing
+    12 instead of 3, 4 is taken too).  float32 only, as vertex_array."""
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise TypeError(f"{name} must be float32, got {a.dtype}")
+    if a.ndim >= 1 and a.shape[-1] == 12:
+        a = a.reshape(a.shape[:-1] + (3, 4))
+    want = 3 if n_renders is None else 4
+    if a.ndim != want or a.shape[-2:] != (3, 4):
+        raise ValueError(f"{name} must be [{'' if n_renders is None else 'n_renders, '}n_bones, 3, 4], got {a.shape}")
+    if n_renders is not None and a.shape[0] != n_renders:
+        raise ValueError(f"{name}: {a.shape[0]} slices for {n_renders} renders")
+    if n_bones is not None and a.shape[-3] != n_bones:
+        raise ValueError(f"{name}: {a.shape[-3]} bones for a skin of {n_bones}")
+    return np.ascontiguousarray(a)
+
+
+def skin_tables(bones, n_bones=None):
+    """What bf_render_skin_batch reads, from {shape: bones[K, n_bones, 3, 4]} or a list of (shape, array) pairs:
+    (n_renders, uint32 shapes, [bone arrays]).  A shape listed twice is refused here.  n_bones: {shape: count} to check against."""
+    items = list(bones.items()) if isinstance(bones, dict) else [(k, v) for k, v in bones]
+    if not items:
+        raise ValueError("bones: no skinned shape")
+    shapes = [int(k) for k, _ in items]
+    if len(set(shapes)) != len(shapes):
+        raise ValueError(f"a shape is listed twice: {shapes}")
+    if any(k < 0 for k in shapes):
+        raise ValueError(f"negative shape index in {shapes}")
+    first = np.asarray(items[0][1])
+    if first.ndim < 3:
+        raise ValueError(f"bones of shape {shapes[0]} must be [n_renders, n_bones, 3, 4], got {first.shape}")
+    n_renders = first.shape[0]
+    if n_renders == 0:
+        raise ValueError("bones: no renders")
+    nb = n_bones or {}
+    return n_renders, np.asarray(shapes, np.uint32), [bone_array(v, f"bones of shape {k}", nb.get(k), n_renders) for k, v in items]
+
+
 class Scene:
     """Device-resident immutable scene (bf_scene)."""
 
@@ -651,6 +696,7 @@ class Scene:
         h = C.c_void_p()
         check(self.lib, self.lib.bf_scene_clone(self.handle, C.byref(h)), "bf_scene_clone")
         other.handle = h
+        other._skin_bones = dict(getattr(self, "_skin_bones", {}))      # skins are shared with clones taken afterwards
         return other
 
     def __del__(self):
@@ -978,6 +1024,71 @@ class Scene:
                                                                C.c_void_p(records_ptr) if records_ptr else None,
                                                                C.c_void_p(stream) if stream else None,
                                                                C.byref(st) if st is not None else None), "bf_render_deform_batch_device")
+        return st
+
+    def set_skin(self, shape, n_bones, rest_positions=None, index=None, weight=None, rest_normals=None):
+        """bf_scene_set_skin: attach a skin to mesh shape `shape`: rest positions float32[nv, 3] (and rest normals, for a mesh with
+        vertex normals), bone indices uint32[nv, 4] and weights float32[nv, 4]; deep-copied.  n_bones = 0 removes the skin."""
+        shape, n_bones = int(shape), int(n_bones)
+        if shape < 0 or n_bones < 0:
+            raise ValueError(f"shape index {shape}, {n_bones} bones")
+        p = n = ix = w = None
+        if n_bones:
+            p = vertex_array(rest_positions, "rest_positions", self.mesh_vertex_count(shape))
+            n = vertex_array(rest_normals, "rest_normals", p.shape[0]) if rest_normals is not None else None
+            ix, w = np.asarray(index), np.asarray(weight)
+            if ix.dtype != np.uint32:
+                raise TypeError(f"index must be uint32, got {ix.dtype}")
+            if w.dtype != np.float32:
+                raise TypeError(f"weight must be float32, got {w.dtype}")
+            if ix.shape != (p.shape[0], 4) or w.shape != (p.shape[0], 4):
+                raise ValueError(f"index and weight must be [{p.shape[0]}, 4], got {ix.shape} and {w.shape}")
+            ix, w = np.ascontiguousarray(ix), np.ascontiguousarray(w)
+        check(self.lib, self.lib.bf_scene_set_skin(self.handle, shape, n_bones, _ptr(p), _ptr(n), _ptr(ix), _ptr(w)), "bf_scene_set_skin")
+        counts = self.__dict__.setdefault("_skin_bones", {})
+        counts[shape] = n_bones
+
+    def _skin_bone_count(self, shape):
+        return getattr(self, "_skin_bones", {}).get(int(shape)) or None
+
+    def pose_skin(self, shape, bones, stream=0):
+        """bf_scene_pose_skin: the base of skinned mesh shape `shape` becomes its rest pose under `bones` (float32[n_bones, 3, 4],
+        motion.apply_skin's arithmetic); the handle's pose is applied on top, the BVHs are re-fitted on the device."""
+        shape = int(shape)
+        if shape < 0:
+            raise ValueError(f"shape index {shape}")
+        b = bone_array(bones, "bones", self._skin_bone_count(shape))
+        check(self.lib, self.lib.bf_scene_pose_skin(self.handle, shape, _ptr(b), _stream(stream)), "bf_scene_pose_skin")
+
+    def _skin_args(self, bones):
+        keys = bones.keys() if isinstance(bones, dict) else [k for k, _ in bones]
+        nb = {int(k): self._skin_bone_count(k) for k in keys}
+        n_renders, shapes, tabs = skin_tables(bones, {k: v for k, v in nb.items() if v is not None})
+        return n_renders, shapes, tabs, (C.c_void_p * len(tabs))(*[t.ctypes.data for t in tabs])
+
+    def render_skin_batch(self, launch, bones, transforms=None, seeds=None, records=False):
+        """bf_render_skin_batch: render k sees skinned shape s posed by bones[s][k] ([K, n_bones, 3, 4] float32 each), then every
+        mesh at transforms[k] (None: none) -> float32[K, channels] (+ records, stats).  The handle itself does not change."""
+        n_renders, shapes, tabs, bp = self._skin_args(bones)
+        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
+        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
+        st = bf_stats()
+        check(self.lib, self.lib.bf_render_skin_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), len(tabs), _ptr(shapes), bp,
+                                                      xf.shape[1] if xf is not None else 0, _ptr(xf), _ptr(hist), _ptr(rec), C.byref(st)),
+              "bf_render_skin_batch")
+        return hist, rec, st
+
+    def render_skin_batch_device(self, launch, bones, hist_ptr, transforms=None, seeds=None, stream=0, records_ptr=None, want_stats=False):
+        """bf_render_skin_batch_device: the same (the bone tables stay host arrays) with render k accumulated into
+        hist_ptr[k * channels ..] (device)."""
+        n_renders, shapes, tabs, bp = self._skin_args(bones)
+        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        st = bf_stats() if want_stats else None
+        check(self.lib, self.lib.bf_render_skin_batch_device(self.handle, C.byref(launch), n_renders, _ptr(sa), len(tabs), _ptr(shapes), bp,
+                                                             xf.shape[1] if xf is not None else 0, _ptr(xf), C.c_void_p(hist_ptr),
+                                                             C.c_void_p(records_ptr) if records_ptr else None, _stream(stream),
+                                                             C.byref(st) if st is not None else None), "bf_render_skin_batch_device")
         return st
 
     def trace_closest(self, rays):

@@ -1297,6 +1297,68 @@ extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0,
                                ubox16, abs_pad, n_versions, vstride, stream);
 }
 
+BF_NS_BEGIN
+// bf_scene_pose_skin / bf_render_skin_batch_device: linear-blend skinning of one mesh shape.  One thread per vertex,
+// grid y = version: version v reads its bone table (n_bones 3x4 matrices, at most 256: 12 KiB) `bone_stride` floats further and
+// writes its vertices `vstride` floats further.  With q_k = rigid_apply(bone[index_k], rest) for the vertex's four slots,
+//   p' = fl(fl(fl(fl(w0 q_0) + fl(w1 q_1)) + fl(w2 q_2)) + fl(w3 q_3))   per coordinate, every product and sum rounded (no FMA)
+//   n' = the same without the bones' translations, on the rest normal, not renormalised
+// All four terms are always evaluated: a zero weight still multiplies its bone's result.  The output is a plain [nv][3] array per
+// version, which bf_deform_tris_kernel gathers (and checks against the bound the host derived) like a caller's own.
+BF_DEV float3 skin_blend(const float *sb, uint4 ix, float4 w, float x, float y, float z, bool with_t) {
+    const float3 q0 = rigid_apply(sb + 12u * ix.x, x, y, z, with_t), q1 = rigid_apply(sb + 12u * ix.y, x, y, z, with_t);
+    const float3 q2 = rigid_apply(sb + 12u * ix.z, x, y, z, with_t), q3 = rigid_apply(sb + 12u * ix.w, x, y, z, with_t);
+    const float a[3][4] = {{q0.x, q1.x, q2.x, q3.x}, {q0.y, q1.y, q2.y, q3.y}, {q0.z, q1.z, q2.z, q3.z}};
+    float r[3];
+    for (int c = 0; c < 3; ++c)
+        r[c] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(w.x, a[c][0]), __fmul_rn(w.y, a[c][1])), __fmul_rn(w.z, a[c][2])), __fmul_rn(w.w, a[c][3]));
+    return make_float3(r[0], r[1], r[2]);
+}
+
+__global__ __launch_bounds__(256) void bf_skin_vertices_kernel(const float *__restrict__ rest_pos, const float *__restrict__ rest_nrm,
+                                                               const uint4 *__restrict__ index, const float4 *__restrict__ weight, uint32_t nv,
+                                                               const float *__restrict__ bones, uint32_t n_bones, uint32_t bone_stride,
+                                                               float *__restrict__ pos, float *__restrict__ nrm, uint64_t vstride) {
+    __shared__ float sb[256 * 12];
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x, ver = blockIdx.y;
+    const bool live = v < nv;
+    // the lane's own loads are issued before the table's, all of them before the barrier
+    uint4 ix = make_uint4(0u, 0u, 0u, 0u);
+    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+    float x[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
+    if (live) {
+        ix = index[v];        // one 16-byte load each
+        w = weight[v];
+        for (int c = 0; c < 3; ++c) x[c] = rest_pos[3u * (size_t) v + c];
+        if (rest_nrm)
+            for (int c = 0; c < 3; ++c) n[c] = rest_nrm[3u * (size_t) v + c];
+    }
+    const float *b = bones + (size_t) bone_stride * ver;
+    for (uint32_t i = threadIdx.x; i < n_bones * 12u; i += 256u) sb[i] = b[i];
+    __syncthreads();
+    if (!live) return;
+    const size_t o = (size_t) vstride * ver + 3u * (size_t) v;
+    const float3 p = skin_blend(sb, ix, w, x[0], x[1], x[2], true);
+    pos[o] = p.x, pos[o + 1] = p.y, pos[o + 2] = p.z;
+    if (rest_nrm) {
+        const float3 r = skin_blend(sb, ix, w, n[0], n[1], n[2], false);
+        nrm[o] = r.x, nrm[o + 1] = r.y, nrm[o + 2] = r.z;
+    }
+}
+BF_NS_END  // namespace bfd
+
+// n_versions poses of one skinned shape: bones [n_versions][n_bones][12] (device) -> pos (and nrm, if the skin has rest normals),
+// [n_versions][nv][3] each
+extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const float *rest_nrm, const uint4 *index, const float4 *weight, uint32_t nv,
+                                               const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
+                                               hipStream_t stream) {
+    if (nv == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u || n_bones == 0 || n_bones > 256u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bfd::bf_skin_vertices_kernel, dim3((nv + 255u) / 256u, n_versions), dim3(256), 0, stream, rest_pos, rest_nrm, index, weight,
+                       nv, bones, n_bones, n_bones * 12u, pos, nrm, (uint64_t) 3u * nv);
+    return hipGetLastError();
+}
+
 #ifdef BF_TAIL_PROF
 extern "C" int bfdbg_tail_profile(unsigned long long *out, int n_waves) {
     if (n_waves > 8192) n_waves = 8192;

@@ -483,6 +483,139 @@ bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
     return BF_OK;
 }
 
+// What deform and skin batches share behind their checks: version k = the shapes of `src` (pos != nullptr; one entry per shape of the
+// scene) gathered from their arrays, every other mesh from the handle's base rows, then to_world[k] (absolute; NULL: none; `moves` from
+// check_rigid_tables), both trees re-fitted.  slice(k0, kc, hs) turns the copy `hs` of `src` into the table of renders k0 .. k0 + kc (it
+// may enqueue what fills the arrays first); `bound` covers every array of the call.  `who` names the caller in error text.
+template <class Slice>
+bf_status deform_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, const std::vector<bfd::DDeformSrc> &src,
+                          float bound, const float *to_world, const std::vector<uint8_t> &moves, float *hist_dev, bf_path_record *records_dev,
+                          void *stream_, bf_stats *stats_out, const char *who, Slice &&slice) {
+    MeshState &m = scene->mesh;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    const uint32_t n_shapes = scene->info.n_shapes;
+    bool any = false;
+    for (const bfd::DDeformSrc &e : src) any = any || e.pos != nullptr;
+    bf_status st = BF_OK;
+    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
+    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
+    // one padding bound for all versions: the handle's, raised over every mesh of every render (a deforming shape's box: [-bound, bound]^3)
+    float oscale = m.origin_scale_built;
+    {
+        std::vector<float> box = m.refit.mesh_box, id((size_t) 12 * n_shapes);
+        for (uint32_t k = 0; k < n_shapes; ++k) {
+            id[12 * (size_t) k] = id[12 * (size_t) k + 5] = id[12 * (size_t) k + 10] = 1.f;
+            if (src[k].pos)
+                for (int a = 0; a < 3; ++a) box[6 * (size_t) k + a] = -bound, box[6 * (size_t) k + 3 + a] = bound;
+        }
+        oscale = origin_bound(box, n_shapes, id.data(), 12, nullptr, oscale);
+        for (uint32_t k = 0; to_world && k < n_renders; ++k)
+            oscale = origin_bound(box, n_shapes, to_world + (size_t) 12 * n_shapes * k, 12, moves.data() + (size_t) n_shapes * k, oscale);
+    }
+    st = render_versions(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, who,
+                         [&](uint32_t k0, uint32_t kc, float4 *a, const MotionLayout &L) -> bf_status {
+        // the chunk's tables: the sources as `slice` leaves them for renders k0 .. k0 + kc, then (if any) the transforms
+        const size_t src_bytes = (src.size() * sizeof(bfd::DDeformSrc) + 15) & ~size_t(15), n = to_world ? (size_t) kc * n_shapes : 0;
+        const size_t bytes = src_bytes + n * 16 * sizeof(float);
+        bf_scene::Stage *stg = nullptr;
+        bf_status pst = stage_acquire(scene, bytes, &stg);
+        if (pst != BF_OK) return pst;
+        bfd::DDeformSrc *hs = (bfd::DDeformSrc *) stg->host;
+        for (uint32_t k = 0; k < n_shapes; ++k) hs[k] = src[k];
+        if ((pst = slice(k0, kc, hs)) != BF_OK) return pst;
+        if (n) pack_rigid((float *) ((char *) stg->host + src_bytes), to_world + 12 * (size_t) k0 * n_shapes, moves.data() + (size_t) k0 * n_shapes, n);
+        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
+        const MeshState::Base b = m.base(scene->d);
+        const RefitDst o = arena_dst(scene, a, L, kc);
+        HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, b.tris, o.tris, b.normals, o.normals, scene->d.n_tris,
+                                       to_world ? (const float *) ((const char *) stg->dev + src_bytes) : nullptr, kc, L.rows, n_shapes * 16u, bound,
+                                       m.bad, stream));
+        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernel
+        HIP_TRY(launch_refit(scene, oscale, o, stream));
+        return BF_OK;
+    });
+    if (st != BF_OK || !any) return st;
+    // the violation count of all chunks travels to the host behind the last one; a batch with stats waits for it and reports itself
+    if ((st = deform_watch(scene, stream)) != BF_OK) return st;
+    return stats_out ? deform_report(scene, true) : BF_OK;
+}
+
+// ---- skins (bf_scene_set_skin, bf_scene_pose_skin, bf_render_skin_batch_device) ---------------------------------------
+// The checks of a skinned shape common to a pose and a batch: what a vertex update refuses of the shape, and a shape without a skin.
+bf_status check_skinned_shape(const bf_scene *scene, uint32_t shape, const char *who, const bf_geometry::MeshTopo **tp, const MeshSkin **skin) {
+    const bf_status st = check_deform_shape(scene, shape, false, who, tp);
+    if (st != BF_OK) return st;
+    const MeshState &m = scene->mesh;
+    if (shape >= m.skins.size() || !m.skins[shape])
+        return fail(BF_ERR_INVALID, "%s shape %u has no skin (bf_scene_set_skin attaches one)", who, shape);
+    *skin = m.skins[shape].get();
+    return BF_OK;
+}
+
+// One bone table ([n_bones][12]) of skin `sk`: every entry finite, and per axis r the bound B[r] >= |posed coordinate r| of every
+// vertex raised to cover it.  Derivation (u = 2^-24, X_c = max |rest coordinate c|, W = the largest float64 sum of a weight row):
+//   q_k[r] = fl(fl(fl(fl(m_r0 x) + fl(m_r1 y)) + fl(m_r2 z)) + m_r3) of bone b = i_k: each product carries one rounding and the
+//     three sums one each, so |q_k[r]| <= Q_b[r] (1 + u)^4 with Q_b[r] = |m_r0| X_0 + |m_r1| X_1 + |m_r2| X_2 + |m_r3|;
+//   p'[r] = fl(fl(fl(fl(w0 q_0) + fl(w1 q_1)) + fl(w2 q_2)) + fl(w3 q_3)): again one rounding per product and three sums, so
+//     |p'[r]| <= (sum_k w_k |q_k[r]|) (1 + u)^4 <= W max_b Q_b[r] (1 + u)^8, the maximum over the bones some vertex gives a non-zero
+//     weight (a zero-weight slot adds fl(0 q) = +-0 exactly, whatever its bone's finite matrix holds).
+//   (1 + u)^8 < 1 + 5e-7; results that round into the subnormal range err by at most 2^-150 per operation instead.  The factor
+//   1 + 1e-5 below (origin_bound's margin) covers both, the evaluation of Q in float64 and the rounding of B to float.
+// `who` ends in ':' or ','.
+bf_status skin_bound(const MeshSkin &sk, uint32_t shape, const float *bones, const char *who, double B[3]) {
+    for (uint32_t b = 0; b < sk.n_bones; ++b) {
+        const float *m = bones + 12 * (size_t) b;
+        for (int j = 0; j < 12; ++j)
+            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "%s shape %u: bone %u has a non-finite entry", who, shape, b);
+        if (!sk.bone_used[b]) continue;
+        for (int r = 0; r < 3; ++r) {
+            double q = std::fabs((double) m[4 * r + 3]);
+            for (int c = 0; c < 3; ++c) q += std::fabs((double) m[4 * r + c]) * (double) sk.rest_abs[c];
+            B[r] = std::max(B[r], sk.weight_sum * q * (1.0 + 1e-5) + 1e-37);
+        }
+    }
+    return BF_OK;
+}
+// ... as the float the gather checks against (and the shape's base box takes); a bound float cannot hold is refused
+bf_status skin_bound_float(const double B[3], uint32_t shape, const char *who, float *bound, float box6[6]) {
+    float mx = std::numeric_limits<float>::min();
+    for (int r = 0; r < 3; ++r) {
+        const bool fits = B[r] < 0.5 * (double) std::numeric_limits<float>::max();
+        const float f = fits ? std::nextafter((float) B[r], std::numeric_limits<float>::infinity()) : 0.f;
+        if (!fits)
+            return fail(BF_ERR_INVALID, "%s shape %u: the bound on the posed coordinates is not finite (bones too large for the rest pose)", who, shape);
+        if (box6) box6[r] = -f, box6[3 + r] = f;
+        mx = std::max(mx, f);
+    }
+    *bound = mx;
+    return BF_OK;
+}
+
+// the handle's scratch for posed vertices, at least `bytes` (the gathers that read the old one are behind `stream` or before it: mesh_enter)
+bf_status skin_scratch(bf_scene *scene, size_t bytes, hipStream_t stream, const char *who) {
+    MeshState &m = scene->mesh;
+    if (m.skin_vtx_cap >= bytes) return BF_OK;
+    if (m.skin_vtx) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipFree(m.skin_vtx));
+        m.skin_vtx = nullptr;
+        m.skin_vtx_cap = 0;
+    }
+    void *q = nullptr;
+    const hipError_t he = hipMalloc(&q, bytes);
+    if (he != hipSuccess) {
+        (void) hipGetLastError();
+        return fail(BF_ERR_NOMEM, "%s hipMalloc(%zu bytes) for the posed vertices: %s", who, bytes, hipGetErrorString(he));
+    }
+    m.skin_vtx = (float *) q;
+    m.skin_vtx_cap = bytes;
+    return BF_OK;
+}
+
+// floats of one version of a skinned shape in the scratch: positions, then normals if the skin has them
+size_t skin_floats(const MeshSkin &sk) { return (size_t) sk.n_vertices * 3 * (sk.rest_nrm ? 2 : 1); }
+
 }  // namespace
 
 bf_status MeshState::own_normals(bfd::DScene &d, std::vector<void *> &owned, const char *who) {
@@ -523,6 +656,7 @@ MeshState::~MeshState() {
     }
     if (vtx_host) (void) hipHostFree(vtx_host);
     if (vtx_dev) (void) hipFree(vtx_dev);
+    if (skin_vtx) (void) hipFree(skin_vtx);
 }
 
 extern "C" {
@@ -564,6 +698,7 @@ bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_no
 bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
     const MeshState &m = src->mesh;
     sc->mesh.origin_scale_built = m.origin_scale_built;
+    sc->mesh.skins = m.skins;      // shared, never written: bf_scene_set_skin on either handle replaces that handle's pointer alone
     if (!m.tris0 && !m.geom_private) return BF_OK;
     // `src` has moved: the clone snapshots what src renders now as ITS geometry "as created"; uvs (and normals no transform moved) stay shared
     const MeshState::Bytes B = MeshState::bytes(src->d);
@@ -940,6 +1075,161 @@ bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch
     std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
     bf_status st = to_world ? check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data()) : BF_OK;
     if (st != BF_OK) return st;
+    BF_ENTER(scene);
+    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
+    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
+    if (scene->d.n_tris == 0) {
+        bf_batch b = {n_renders, seeds, nullptr};
+        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
+    }
+    return deform_versions(scene, launch, n_renders, seeds, src, bound, to_world, moves, hist_dev, records_dev, stream_, stats_out,
+                           "bf_render_deform_batch_device", [&](uint32_t k0, uint32_t, bfd::DDeformSrc *hs) -> bf_status {
+        // the sources advanced to slice k0
+        for (uint32_t k = 0; k < n_shapes; ++k) {
+            if (hs[k].pos) hs[k].pos += (size_t) k0 * 3 * hs[k].nv;
+            if (hs[k].nrm) hs[k].nrm += (size_t) k0 * 3 * hs[k].nv;
+        }
+        return BF_OK;
+    });
+}
+
+// ---- skinned meshes: a pose is n_bones 3x4 matrices, bf_skin_vertices_kernel computes the vertices into the handle's
+// scratch, and from there on a pose is a device-form vertex update and a batch a device-form deform batch, bound computed here ----
+bf_status bf_scene_set_skin(bf_scene *scene, uint32_t shape, uint32_t n_bones, const float *rest_positions, const float *rest_normals,
+                            const uint32_t *bone_index, const float *bone_weight) {
+    const char *fn = "bf_scene_set_skin:";
+    if (!scene) return fail(BF_ERR_INVALID, "%s null scene", fn);
+    const bf_geometry::MeshTopo *tp = nullptr;
+    bf_status st = check_deform_shape(scene, shape, n_bones && rest_normals, fn, &tp);
+    if (st != BF_OK) return st;
+    if (n_bones == 0) {
+        BF_ENTER(scene);
+        if (shape < scene->mesh.skins.size()) scene->mesh.skins[shape].reset();
+        return BF_OK;
+    }
+    if (n_bones > 256u) return fail(BF_ERR_INVALID, "%s shape %u: %u bones (at most 256 per shape)", fn, shape, n_bones);
+    if (!rest_positions || !bone_index || !bone_weight) return fail(BF_ERR_INVALID, "%s shape %u: null array", fn, shape);
+    if (tp->has_normals && !rest_normals)
+        return fail(BF_ERR_INVALID, "%s shape %u was created with vertex normals: its skin needs rest normals", fn, shape);
+    const uint32_t nv = tp->n_vertices;
+    auto skin = std::make_shared<MeshSkin>();
+    skin->n_bones = n_bones;
+    skin->n_vertices = nv;
+    skin->bone_used.assign(n_bones, 0);
+    for (uint32_t v = 0; v < nv; ++v) {
+        for (int c = 0; c < 3; ++c) {
+            const float x = rest_positions[3 * (size_t) v + c];
+            if (!std::isfinite(x) || (rest_normals && !std::isfinite(rest_normals[3 * (size_t) v + c])))
+                return fail(BF_ERR_INVALID, "%s shape %u: non-finite rest value at vertex %u", fn, shape, v);
+            skin->rest_abs[c] = std::max(skin->rest_abs[c], std::fabs(x));
+        }
+        double sum = 0.0;
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t b = bone_index[4 * (size_t) v + k];
+            const float w = bone_weight[4 * (size_t) v + k];
+            if (b >= n_bones) return fail(BF_ERR_INVALID, "%s shape %u: vertex %u names bone %u of %u", fn, shape, v, b, n_bones);
+            if (!std::isfinite(w) || w < 0.f) return fail(BF_ERR_INVALID, "%s shape %u: vertex %u has weight %g for bone %u", fn, shape, v, (double) w, b);
+            if (w > 0.f) skin->bone_used[b] = 1;
+            sum += (double) w;
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-3)) return fail(BF_ERR_INVALID, "%s shape %u: the weights of vertex %u sum to %.9g, not 1", fn, shape, v, sum);
+        skin->weight_sum = std::max(skin->weight_sum, sum);
+    }
+    BF_ENTER(scene);
+    if (nv) {
+        // one block: weights, indices (16-byte rows first), rest positions, rest normals
+        const size_t row = (size_t) nv * 16, vec = (size_t) nv * 12, bytes = 2 * row + vec * (rest_normals ? 2 : 1);
+        std::vector<char> host(bytes);
+        std::memcpy(host.data(), bone_weight, row);
+        std::memcpy(host.data() + row, bone_index, row);
+        std::memcpy(host.data() + 2 * row, rest_positions, vec);
+        if (rest_normals) std::memcpy(host.data() + 2 * row + vec, rest_normals, vec);
+        const hipError_t he = hipMalloc(&skin->block, bytes);
+        if (he != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(BF_ERR_NOMEM, "%s shape %u: hipMalloc(%zu bytes): %s", fn, shape, bytes, hipGetErrorString(he));
+        }
+        HIP_TRY(hipMemcpy(skin->block, host.data(), bytes, hipMemcpyHostToDevice));
+        const char *blk = (const char *) skin->block;
+        skin->weight = (const float4 *) blk;
+        skin->index = (const uint4 *) (blk + row);
+        skin->rest_pos = (const float *) (blk + 2 * row);
+        skin->rest_nrm = rest_normals ? (const float *) (blk + 2 * row + vec) : nullptr;
+    }
+    MeshState &m = scene->mesh;
+    if (m.skins.size() < scene->info.n_shapes) m.skins.resize(scene->info.n_shapes);
+    m.skins[shape] = std::move(skin);      // (the skin it replaces goes with its last handle; hipFree waits for the kernels that read it)
+    return BF_OK;
+}
+
+bf_status bf_scene_pose_skin(bf_scene *scene, uint32_t shape, const float *bones, void *stream_) {
+    const char *fn = "bf_scene_pose_skin:";
+    if (!scene || !bones) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    const bf_geometry::MeshTopo *tp = nullptr;
+    const MeshSkin *sk = nullptr;
+    bf_status st = check_skinned_shape(scene, shape, fn, &tp, &sk);
+    if (st != BF_OK) return st;
+    double B[3] = {0.0, 0.0, 0.0};
+    float bound = 0.f, box[6];
+    if ((st = skin_bound(*sk, shape, bones, fn, B)) != BF_OK || (st = skin_bound_float(B, shape, fn, &bound, box)) != BF_OK) return st;
+    if (scene->d.n_tris == 0 || sk->n_vertices == 0) return BF_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    MeshState &m = scene->mesh;
+    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if ((st = skin_scratch(scene, skin_floats(*sk) * sizeof(float), stream, fn)) != BF_OK) return st;
+    const size_t bytes = (size_t) sk->n_bones * 12 * sizeof(float);
+    bf_scene::Stage *stg = nullptr;
+    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
+    std::memcpy(stg->host, bones, bytes);
+    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
+    float *pos = m.skin_vtx, *nrm = sk->rest_nrm ? m.skin_vtx + 3 * (size_t) sk->n_vertices : nullptr;
+    HIP_TRY(bfk_launch_skin_vertices(sk->rest_pos, sk->rest_nrm, sk->index, sk->weight, sk->n_vertices, (const float *) stg->dev, sk->n_bones, pos, nrm,
+                                     1u, stream));
+    HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel
+    if ((st = update_vertices_locked(scene, shape, *tp, pos, nrm, bound, box, true, stream)) != BF_OK) return st;
+    return mark_last(scene, stream);
+}
+
+bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_skinned,
+                                      const uint32_t *shapes, const float *const *bones, uint32_t n_shapes, const float *to_world, float *hist_dev,
+                                      bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
+    const char *fn = "bf_render_skin_batch_device:";
+    if (!scene || !launch || !hist_dev || (n_skinned && (!shapes || !bones))) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
+    if (to_world && n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
+    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a skin batch is one launch sequence of its own", fn);
+    if (launch->spp && launch->film_width && launch->film_height)
+        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
+    n_shapes = scene->info.n_shapes;
+    // the gather's table: a skinned shape's entry is marked here and pointed at the chunk's posed vertices below
+    std::vector<bfd::DDeformSrc> src(n_shapes);
+    std::memset(src.data(), 0, src.size() * sizeof(bfd::DDeformSrc));
+    std::vector<const MeshSkin *> skins(n_skinned, nullptr);
+    size_t version_floats = 0, version_bones = 0;      // of all skinned shapes, per render
+    double B[3] = {0.0, 0.0, 0.0};
+    for (uint32_t j = 0; j < n_skinned; ++j) {
+        const bf_geometry::MeshTopo *tp = nullptr;
+        bf_status cst = check_skinned_shape(scene, shapes[j], fn, &tp, &skins[j]);
+        if (cst != BF_OK) return cst;
+        if (!bones[j]) return fail(BF_ERR_INVALID, "%s shape %u: null bones", fn, shapes[j]);
+        if (src[shapes[j]].pos) return fail(BF_ERR_INVALID, "%s shape %u is listed twice", fn, shapes[j]);
+        src[shapes[j]].pos = (const float *) (uintptr_t) 16;      // (marks the shape; never read)
+        src[shapes[j]].nv = tp->n_vertices;
+        for (uint32_t k = 0; k < n_renders; ++k) {
+            char who[96];
+            std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
+            if ((cst = skin_bound(*skins[j], shapes[j], bones[j] + (size_t) k * skins[j]->n_bones * 12, who, B)) != BF_OK) return cst;
+        }
+        version_floats += skin_floats(*skins[j]);
+        version_bones += (size_t) skins[j]->n_bones * 12;
+    }
+    float bound = std::numeric_limits<float>::min();
+    bf_status st = n_skinned ? skin_bound_float(B, shapes[0], fn, &bound, nullptr) : BF_OK;
+    if (st != BF_OK) return st;
+    std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
+    if (to_world && (st = check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data())) != BF_OK) return st;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
     // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
@@ -949,51 +1239,37 @@ bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch
         return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
     }
     MeshState &m = scene->mesh;
-    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
-    if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
-    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
-    // one padding bound for all versions: the handle's, raised over every mesh of every render (a deforming shape's box: [-bound, bound]^3)
-    float oscale = m.origin_scale_built;
-    {
-        std::vector<float> box = m.refit.mesh_box, id((size_t) 12 * n_shapes);
-        for (uint32_t k = 0; k < n_shapes; ++k) {
-            id[12 * (size_t) k] = id[12 * (size_t) k + 5] = id[12 * (size_t) k + 10] = 1.f;
-            if (src[k].pos)
-                for (int a = 0; a < 3; ++a) box[6 * (size_t) k + a] = -bound, box[6 * (size_t) k + 3 + a] = bound;
-        }
-        oscale = origin_bound(box, n_shapes, id.data(), 12, nullptr, oscale);
-        for (uint32_t k = 0; to_world && k < n_renders; ++k)
-            oscale = origin_bound(box, n_shapes, to_world + (size_t) 12 * n_shapes * k, 12, moves.data() + (size_t) n_shapes * k, oscale);
-    }
-    st = render_versions(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, "bf_render_deform_batch_device",
-                         [&](uint32_t k0, uint32_t kc, float4 *a, const MotionLayout &L) -> bf_status {
-        // the chunk's tables: the sources advanced to slice k0, then (if any) the transforms
-        const size_t src_bytes = (src.size() * sizeof(bfd::DDeformSrc) + 15) & ~size_t(15), n = to_world ? (size_t) kc * n_shapes : 0;
-        const size_t bytes = src_bytes + n * 16 * sizeof(float);
+    return deform_versions(scene, launch, n_renders, seeds, src, bound, to_world, moves, hist_dev, records_dev, stream_, stats_out,
+                           "bf_render_skin_batch_device", [&](uint32_t k0, uint32_t kc, bfd::DDeformSrc *hs) -> bf_status {
+        // the chunk's bone tables ([kc][n_bones][12] per shape, one shape after the other) and, from them, its posed vertices in the scratch
+        // (per shape [kc][nv][3] positions, then its normals): version v of the gather reads slice v
+        bf_status pst = skin_scratch(scene, (size_t) kc * version_floats * sizeof(float), stream, fn);
+        if (pst != BF_OK || !version_bones) return pst;
+        const size_t bytes = (size_t) kc * version_bones * sizeof(float);
         bf_scene::Stage *stg = nullptr;
-        bf_status pst = stage_acquire(scene, bytes, &stg);
-        if (pst != BF_OK) return pst;
-        bfd::DDeformSrc *hs = (bfd::DDeformSrc *) stg->host;
-        for (uint32_t k = 0; k < n_shapes; ++k) {
-            hs[k] = src[k];
-            if (hs[k].pos) hs[k].pos += (size_t) k0 * 3 * hs[k].nv;
-            if (hs[k].nrm) hs[k].nrm += (size_t) k0 * 3 * hs[k].nv;
+        if ((pst = stage_acquire(scene, bytes, &stg)) != BF_OK) return pst;
+        float *hb = (float *) stg->host;
+        for (uint32_t j = 0; j < n_skinned; ++j) {
+            const size_t n = (size_t) kc * skins[j]->n_bones * 12;
+            std::memcpy(hb, bones[j] + (size_t) k0 * skins[j]->n_bones * 12, n * sizeof(float));
+            hb += n;
         }
-        if (n) pack_rigid((float *) ((char *) stg->host + src_bytes), to_world + 12 * (size_t) k0 * n_shapes, moves.data() + (size_t) k0 * n_shapes, n);
         if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
-        const MeshState::Base b = m.base(scene->d);
-        const RefitDst o = arena_dst(scene, a, L, kc);
-        HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, b.tris, o.tris, b.normals, o.normals, scene->d.n_tris,
-                                       to_world ? (const float *) ((const char *) stg->dev + src_bytes) : nullptr, kc, L.rows, n_shapes * 16u, bound,
-                                       m.bad, stream));
-        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernel
-        HIP_TRY(launch_refit(scene, oscale, o, stream));
+        const float *db = (const float *) stg->dev;
+        float *out = m.skin_vtx;
+        for (uint32_t j = 0; j < n_skinned; ++j) {
+            const MeshSkin &sk = *skins[j];
+            const size_t n = (size_t) kc * sk.n_vertices * 3;
+            float *pos = out, *nrm = sk.rest_nrm ? out + n : nullptr;
+            HIP_TRY(bfk_launch_skin_vertices(sk.rest_pos, sk.rest_nrm, sk.index, sk.weight, sk.n_vertices, db, sk.n_bones, pos, nrm, kc, stream));
+            hs[shapes[j]].pos = pos;
+            hs[shapes[j]].nrm = nrm;
+            db += (size_t) kc * sk.n_bones * 12;
+            out += (size_t) kc * skin_floats(sk);
+        }
+        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernels
         return BF_OK;
     });
-    if (st != BF_OK || !n_deform) return st;
-    // the violation count of all chunks travels to the host behind the last one; a batch with stats waits for it and reports itself
-    if ((st = deform_watch(scene, stream)) != BF_OK) return st;
-    return stats_out ? deform_report(scene, true) : BF_OK;
 }
 
 /* test hook (not part of the ABI): the ray-origin bound the handle's boxes are padded for (bf_bvh.h) */

@@ -30,6 +30,10 @@ extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const 
                                        const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
                                        uint64_t vstride, uint32_t xf_stride, hipStream_t stream);
 
+extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const float *rest_nrm, const uint4 *index, const float4 *weight, uint32_t nv,
+                                               const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
+                                               hipStream_t stream);
+
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -82,6 +86,25 @@ struct bf_tunables {
     uint32_t debug_surv_batches = 0;         // BF_DEBUG_SURV_BATCHES (tests): size of the survivor area in batches, sizing rule off
 };
 
+// The skin of one mesh shape (bf_scene_set_skin): rest pose and four bone slots per vertex in ONE device block, never
+// written after it is made.  Handles share it through MeshState::skins (a clone copies the pointers; bf_scene_set_skin replaces this
+// handle's pointer alone: copy on write); the block goes with the last of them.
+struct __attribute__((visibility("hidden"))) MeshSkin {
+    uint32_t n_bones = 0, n_vertices = 0;
+    void *block = nullptr;                // device: what the four pointers below point into
+    const float4 *weight = nullptr;       // [n_vertices]: w0..w3
+    const uint4 *index = nullptr;         // [n_vertices]: i0..i3, each < n_bones
+    const float *rest_pos = nullptr;      // [n_vertices][3]
+    const float *rest_nrm = nullptr;      // [n_vertices][3], or null: the mesh has no vertex normals
+    // what the bound on the posed coordinates is derived from (bf_mesh.cpp: skin_bound)
+    float rest_abs[3] = {0.f, 0.f, 0.f};  // max |rest coordinate| per axis
+    double weight_sum = 0.0;              // largest float64 sum of a weight row (validated: within 1e-3 of 1)
+    std::vector<uint8_t> bone_used;       // [n_bones]: some vertex gives the bone a non-zero weight
+    ~MeshSkin() {
+        if (block) (void) hipFree(block);
+    }
+};
+
 // "The meshes of this handle have moved" (DESIGN.md 6d): the state bf_mesh.cpp keeps per handle, each flag's meaning stated here alone.
 // Every moving call is ABSOLUTE: from the BASE rows (as created, until a vertex update rewrites them) to the rows bf_scene::d renders.
 struct __attribute__((visibility("hidden"))) MeshState {
@@ -125,6 +148,12 @@ struct __attribute__((visibility("hidden"))) MeshState {
     void *vtx_host = nullptr, *vtx_dev = nullptr;
     size_t vtx_cap = 0;
     hipEvent_t vtx_ev = nullptr;
+    // skins (bf_scene_set_skin): per shape, empty until the first one is attached; shared with clones taken afterwards.  skin_vtx:
+    // where bf_skin_vertices_kernel writes the posed vertices (and normals) of a pose or of a batch chunk, for the gather to read;
+    // the handle's own, grown on demand, never shrunk
+    std::vector<std::shared_ptr<const MeshSkin>> skins;
+    float *skin_vtx = nullptr;
+    size_t skin_vtx_cap = 0;                     // bytes
 
     // what to read as the base rows: the handle's own once it has moved, else the arrays it renders (a clone's snapshot included)
     struct Base { const float4 *tris, *nodes, *wnodes, *normals; };

@@ -223,6 +223,43 @@ def motorbike(n_tris=300_000, seed=5):
     return v, f
 
 
+def jointed_bar(n_bones, n_around=8, n_along=6, radius=0.15, blend=0.25):
+    """The smallest skinned mesh that exercises blending (bf_scene_set_skin): a closed bar along x, one segment of length 1
+    per bone (x in [k, k + 1] belongs to bone k), `n_around` sides, `n_along` rings per segment, a fan cap at either end.
+    Across joint j (x = j) the weights of bones j - 1 and j are blended linearly over x in [j - blend, j + blend]: two
+    influences, the other two slots name bone 0 with weight 0.  Returns (positions float32[nv, 3], faces uint32[nf, 3],
+    index uint32[nv, 4], weight float32[nv, 4]); 2 n_around (n_bones n_along + 1) triangles."""
+    n_bones, n_around, n_along = int(n_bones), int(n_around), int(n_along)
+    if n_bones < 1 or n_around < 3 or n_along < 1 or not 0.0 < blend <= 0.5:
+        raise ValueError("jointed_bar: n_bones >= 1, n_around >= 3, n_along >= 1, 0 < blend <= 0.5")
+    n_rings = n_bones * n_along + 1
+    xs = np.arange(n_rings, dtype=np.float64) / n_along
+    ang = 2.0 * np.pi * np.arange(n_around) / n_around
+    ring = np.stack([np.zeros(n_around), radius * np.cos(ang), radius * np.sin(ang)], -1)
+    v = np.concatenate([(ring + [x, 0.0, 0.0]) for x in xs] + [np.array([[0.0, 0.0, 0.0], [float(n_bones), 0.0, 0.0]])])
+    vx = np.concatenate([np.repeat(xs, n_around), [0.0, float(n_bones)]])
+    faces = []
+    for i in range(n_rings - 1):
+        for j in range(n_around):
+            a, b = i * n_around + j, i * n_around + (j + 1) % n_around
+            faces += [[a, b, b + n_around], [a, b + n_around, a + n_around]]
+    c0, c1, last = n_rings * n_around, n_rings * n_around + 1, (n_rings - 1) * n_around
+    for j in range(n_around):
+        faces += [[c0, (j + 1) % n_around, j], [c1, last + j, last + (j + 1) % n_around]]
+    own = np.clip(np.floor(vx), 0, n_bones - 1).astype(np.int64)
+    joint = np.clip(np.rint(vx), 1, max(1, n_bones - 1))                 # the nearest joint
+    other = np.where(joint > own, own + 1, own - 1)
+    d = np.abs(vx - joint)                                               # distance to it: 0.5 at the joint, 1 from `blend` on
+    w_own = np.where((n_bones > 1) & (d < blend), 0.5 + 0.5 * d / blend, 1.0)
+    other = np.where(w_own < 1.0, other, 0)
+    index = np.zeros((v.shape[0], 4), np.uint32)
+    weight = np.zeros((v.shape[0], 4), f32)
+    index[:, 0], index[:, 1] = own, other
+    weight[:, 0] = w_own.astype(f32)
+    weight[:, 1] = f32(1.0) - weight[:, 0]
+    return v.astype(f32), np.asarray(faces, np.uint32), index, weight
+
+
 def vertex_normals(verts, faces):
     """Angle-weighted vertex normals (Thuermer & Wuethrich) — what Mesh::recompute_vertex_normals
     (mesh.cpp:201-249) gives an OBJ / PLY file that carries none, e.g. a raw 3-D scan."""

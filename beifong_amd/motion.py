@@ -72,6 +72,45 @@ def apply_rigid(positions, normals, m):
     return p2, None if n is None else rot(n)
 
 
+def apply_skin(positions, normals, index, weight, bones):
+    """Rest positions (and rest normals, or None) of a mesh posed by linear-blend skinning as the device poses them
+    (bf_scene_pose_skin): index uint[nv, 4] and weight float32[nv, 4] name four bones per vertex, bones is float32[n_bones, 3, 4].
+
+        q_k = apply_rigid's formula for bones[index[:, k]] on the vertex        k = 0..3, every product and sum rounded
+        p'  = fl(fl(fl(fl(w0 q_0) + fl(w1 q_1)) + fl(w2 q_2)) + fl(w3 q_3))     per coordinate
+        n'  = the same without the translations, not renormalised
+
+    All four terms are always evaluated (a zero weight still multiplies its bone's result) and an identity bone takes no
+    shortcut, so a -0.0 may come out as +0.0.  Returns (positions', normals')."""
+    p = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, dtype=f32).reshape(-1, 3)
+    ix = np.asarray(index).reshape(-1, 4).astype(np.int64)
+    w = np.ascontiguousarray(weight, dtype=f32).reshape(-1, 4)
+    b = np.ascontiguousarray(bones, dtype=f32).reshape(-1, 3, 4)
+    if ix.shape[0] != p.shape[0] or w.shape[0] != p.shape[0]:
+        raise ValueError(f"{p.shape[0]} vertices, {ix.shape[0]} index rows, {w.shape[0]} weight rows")
+    if ix.size and (ix.min() < 0 or ix.max() >= b.shape[0]):
+        raise ValueError(f"bone index out of range for {b.shape[0]} bones")
+
+    def blend(v, with_t):
+        out = np.empty_like(v)
+        x, y, z = v[:, 0], v[:, 1], v[:, 2]
+        for k in range(4):                           # the slots in order: per coordinate, ((w0 q0 + w1 q1) + w2 q2) + w3 q3
+            m = b[ix[:, k]]                          # [nv, 3, 4] float32: every operation below is float32 on float32
+            for r in range(3):
+                q = m[:, r, 0] * x
+                q = q + m[:, r, 1] * y
+                q = q + m[:, r, 2] * z
+                if with_t:
+                    q = q + m[:, r, 3]
+                t = w[:, k] * q
+                out[:, r] = t if k == 0 else out[:, r] + t
+        return out
+
+    with np.errstate(over="ignore", invalid="ignore"):
+        return blend(p, True), None if n is None else blend(n, False)
+
+
 def moved_description(sd, transforms):
     """A new SceneDesc equal to `sd` with every mesh's positions and normals replaced by apply_rigid(..., transforms[k]):
     the scene bf_scene_create would have to rebuild for the pose bf_scene_transform_meshes gives a handle of `sd`.

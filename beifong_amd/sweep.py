@@ -333,6 +333,95 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
             h.close()
 
 
+def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None, classes=None, lib=None,
+                      device=None):
+    """Coherent pulse sweep in which SKINNED meshes are posed by a few bones per pulse: the counterpart of
+    render_deform_sweep whose per-pulse input is [n_bones, 3, 4] floats per mesh, not its vertices.
+
+    `skins`       {shape: (index uint32[n_vertices, 4], weight float32[n_vertices, 4])}: the skin of every posed mesh; its
+                  rest pose is the mesh as `sd` describes it (positions, and vertex normals if it has any);
+    `bones`       {shape: float32[n_pulses, n_bones, 3, 4]}: the bone matrices of every pulse (motion.apply_skin's arithmetic);
+    `transforms`  None, or float[n_pulses, n_shapes, 3, 4] as in render_motion_sweep, applied on top.
+
+    The scene is built once and the skins attached before it is cloned; the pulses are split into `n_streams` contiguous
+    groups, one per handle and stream, each ONE skin batch (bf_render_skin_batch_device).  per_pulse=True is the reference
+    path: the pulses rotate over the handles, one bf_scene_pose_skin (+ one bf_scene_transform_meshes) and one render per
+    pulse; per-path results are the same.  rebuild_every and classes as in render_deform_sweep.  Returns the cube
+    float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3] with classes."""
+    import torch
+    if rebuild_every is not None and int(rebuild_every) < 1:
+        raise ValueError("rebuild_every must be a positive integer or None")
+    every = None if rebuild_every is None else int(rebuild_every)
+    n, shapes, tabs = capi.skin_tables(bones)
+    skins = {int(k): v for k, v in skins.items()}
+    if set(skins) != set(int(k) for k in shapes):
+        raise ValueError(f"skins for shapes {sorted(skins)}, bones for shapes {sorted(int(k) for k in shapes)}")
+    for k in shapes:
+        if not 0 <= int(k) < len(sd.shapes) or sd.shapes[int(k)].type != capi.BF_SHAPE_MESH:
+            raise ValueError(f"shape {int(k)} is not a mesh of this scene")
+    xf = None
+    if transforms is not None:
+        xf = np.asarray(transforms, dtype=np.float32)
+        if xf.ndim != 4 or xf.shape[2:] != (3, 4) or xf.shape[0] != n:
+            raise ValueError(f"transforms must be [{n}, n_shapes, 3, 4], got {xf.shape}")
+    lib = lib or capi.load_library()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    n_streams = max(1, min(int(n_streams), n))
+    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
+    first = capi.Scene(sd, lib)
+    handles = [first]
+    try:
+        for sh, tab in zip(shapes, tabs):
+            s = sd.shapes[int(sh)]
+            index, weight = skins[int(sh)]
+            rest = np.ctypeslib.as_array(s.positions, shape=(s.n_vertices, 3))
+            rest_n = np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None
+            first.set_skin(int(sh), tab.shape[1], rest, index, weight, rest_normals=rest_n)
+        launch, n_classes = _classed(first, launch, classes)
+        handles += [first.clone() for _ in range(n_streams - 1)]
+        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
+        for s in streams:           # the cube was zero-filled on the current stream
+            s.wait_stream(torch.cuda.current_stream(dev))
+        updates = [0] * n_streams
+
+        def pose(h, k, stream):
+            for sh, tab in zip(shapes, tabs):
+                h.pose_skin(int(sh), tab[k], stream=stream)
+
+        if per_pulse:
+            for k in range(n):
+                j = k % n_streams
+                with torch.cuda.stream(streams[j]):
+                    pose(handles[j], k, streams[j].cuda_stream)
+                    if xf is not None:
+                        handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
+                    updates[j] += 1
+                    if every and updates[j] % every == 0:
+                        handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
+                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
+        else:
+            bounds = np.linspace(0, n, n_streams + 1).astype(int)
+            for j in range(n_streams):
+                lo, hi = int(bounds[j]), int(bounds[j + 1])
+                for c0 in range(lo, hi, every or max(1, hi - lo)):
+                    c1 = min(hi, c0 + every) if every else hi
+                    with torch.cuda.stream(streams[j]):
+                        if every and c0 > lo:
+                            # the k-th frame since the last rebuild has just been rendered: the trees follow the meshes to it
+                            pose(handles[j], c0 - 1, streams[j].cuda_stream)
+                            handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
+                        handles[j].render_skin_batch_device(launch, {int(sh): tab[c0:c1] for sh, tab in zip(shapes, tabs)}, cube[c0].data_ptr(),
+                                                            transforms=None if xf is None else xf[c0:c1], stream=streams[j].cuda_stream)
+        for s in streams:
+            s.synchronize()
+        for h in handles:
+            h.sync()                # a posed vertex beyond the bound the library derived (there is none) would be reported here
+        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
+    finally:
+        for h in reversed(handles):
+            h.close()
+
+
 def range_doppler(cube, window=True):
     """Slow-time FFT of a pulse-sweep cube: complex64[n_doppler, cells], zero Doppler at row 0 (numpy.fft order)."""
     z = cube[:, :, 0].astype(np.complex64) + 1j * cube[:, :, 1].astype(np.complex64)

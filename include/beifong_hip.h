@@ -879,6 +879,55 @@ bf_status bf_render_deform_batch(bf_scene *scene, const bf_launch *launch, uint3
                                  const float *const *normals, uint32_t n_shapes, const float *to_world, float *hist_out,
                                  bf_path_record *records_out, bf_stats *stats_out);
 
+/* Skinned meshes: linear-blend skinning on the device, the layer between rigid transforms and vertex updates.  A skin is
+ * attached to a mesh shape once (rest pose, four bone indices and weights per vertex); after that a pose is n_bones 3x4
+ * matrices ([R | t] row-major, any finite affine map) and the device computes the vertices.  DESIGN.md 6d.
+ *   Arithmetic, fp32, every product and sum rounded (no FMA).  For a vertex with rest position x, bones i0..i3, weights w0..w3:
+ *       q_k = B[i_k] x                 as bf_scene_transform_meshes evaluates a 3x4 on a point (with the translation)
+ *       p'  = fl(fl(fl(fl(w0 q_0) + fl(w1 q_1)) + fl(w2 q_2)) + fl(w3 q_3))                      per coordinate
+ *       n'  = the same without the translations, on the rest normal, not renormalised
+ *     All four terms are always evaluated: a zero-weight slot's index must still name a bone, and there is no shortcut for
+ *     an identity bone.  beifong_amd.motion.apply_skin is the numpy statement of it.
+ *   bf_scene_set_skin: host arrays, deep-copied to the device.  One skin per shape; a second call replaces it, n_bones == 0
+ *     removes it (the arrays are then not read).  rest_normals: given exactly if the mesh was created with vertex normals.
+ *     Clones taken afterwards share the skin; a later call on either handle changes that handle alone.  The mesh itself does
+ *     not move.  bf_scene_rebuild_bvh keeps skins valid (they are per vertex).
+ *   bf_scene_pose_skin: the mesh's BASE becomes the skinned vertices (computed from the skin's rest arrays, whatever the base
+ *     held before); the handle's pose goes on top.  Semantics, ordering, copy on write and "an open rolling sequence is
+ *     finished first" are bf_scene_update_vertices': after the call every path is bit-identical to a bf_scene_create of the
+ *     description with the shape carrying apply_skin's arrays, followed by the same transform call.  `bones` is a host array,
+ *     free again when the call returns.
+ *   bf_render_skin_batch(_device): bf_render_deform_batch with bones[j] = host [n_renders][n_bones(shapes[j])][12] in place
+ *     of the vertex arrays.  Render k is bit-identical to bf_scene_pose_skin(slice k) + bf_scene_transform_meshes(to_world[k])
+ *     + a stand-alone render with seeds[k] on a second handle.  Arena, chunking (BF_MOTION_BATCH_MB) and launch flags
+ *     (BF_FLAG_CLASSES, BF_FLAG_AOV, BF_FLAG_MOMENT, BF_FLAG_FAST) as a deform batch; the handle's base, pose and clones do
+ *     not change.
+ *   Scratch: the posed vertices of a pose or of a batch chunk are written to a buffer of the handle's own before they are
+ *     gathered into triangle rows: 12 bytes per vertex and version, 24 for a mesh with vertex normals, over the skinned
+ *     shapes of the call and the renders of the largest chunk.  It grows only, is freed with the handle, and lies OUTSIDE
+ *     the BF_MOTION_BATCH_MB budget.
+ *   Bound: the library derives bound >= max |posed coordinate| on the host, from the rest pose's extent, the bone tables and
+ *     the weight sums, and uses it where the device forms of vertex updates take the caller's; the gather checks it as a
+ *     safety net (bf_scene_sync reports a violation).  Bones so large that the bound is not finite are refused.
+ *   Validation, before anything is enqueued (a failed call leaves the scene as it was; the text names shape, vertex or bone):
+ *     BF_ERR_INVALID      a shape index out of range or not a mesh; NULL arrays; n_bones > 256; a non-finite rest, weight or
+ *                         bone value; a bone index >= n_bones; a negative weight; a weight row whose float64 sum differs from
+ *                         1 by more than 1e-3; rest normals for a mesh without vertex normals, or none for a mesh with them;
+ *                         posing a shape that has no skin; a shape listed twice; and what a deform batch refuses
+ *                         (n_renders == 0, BF_FLAG_ROLLING, a multi-pixel film, a bad to_world)
+ *     BF_ERR_UNSUPPORTED  a mesh that carries an emitter / transmitter */
+bf_status bf_scene_set_skin(bf_scene *scene, uint32_t shape, uint32_t n_bones, const float *rest_positions /* host [n_vertices][3] */,
+                            const float *rest_normals /* host [n_vertices][3] or NULL */, const uint32_t *bone_index /* host [n_vertices][4] */,
+                            const float *bone_weight /* host [n_vertices][4] */);
+bf_status bf_scene_pose_skin(bf_scene *scene, uint32_t shape, const float *bones /* host [n_bones][12] */, void *stream);
+bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds,
+                                      uint32_t n_skinned, const uint32_t *shapes, const float *const *bones /* [n_skinned] host pointers */,
+                                      uint32_t n_shapes, const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream,
+                                      bf_stats *stats_out);
+bf_status bf_render_skin_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_skinned,
+                               const uint32_t *shapes, const float *const *bones, uint32_t n_shapes, const float *to_world, float *hist_out,
+                               bf_path_record *records_out, bf_stats *stats_out);
+
 /* Scene::ray_intersect / ray_test over a batch of HOST rays (tests, tools).
  * rays: [n][8] = o.xyz, mint, d.xyz, maxt.  Outputs may be NULL.
  * out_t = +inf on miss; out_prim = global primitive index (shape prefix sum,
