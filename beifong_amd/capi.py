@@ -30,6 +30,7 @@ BF_FLAG_CLASSES = 1024
 BF_MAX_CLASSES = 256
 BF_FLAG_AOV = 2048
 BF_MAX_AOVS = 16
+BF_NORMALS_GIVEN, BF_NORMALS_RECOMPUTE = range(2)
 (BF_AOV_DEPTH, BF_AOV_POSITION, BF_AOV_UV, BF_AOV_GEO_NORMAL, BF_AOV_SH_NORMAL, BF_AOV_DP_DU, BF_AOV_DP_DV, BF_AOV_DUV_DX,
  BF_AOV_DUV_DY, BF_AOV_TYPES) = range(10)
 # the reference's type names (aov.cpp:96-127) in BF_AOV_* order, and the floats of each
@@ -161,6 +162,7 @@ EXPORTED_SYMBOLS = [
     "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
     "bf_scene_update_vertices", "bf_scene_update_vertices_device", "bf_render_deform_batch_device", "bf_render_deform_batch",
     "bf_scene_set_skin", "bf_scene_pose_skin", "bf_render_skin_batch_device", "bf_render_skin_batch",
+    "bf_vertex_normals", "bf_scene_set_normal_mode", "bf_scene_get_normal_mode",
     "bf_scene_rebuild_bvh", "bf_scene_read_bvh",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
     "bf_bsdf_eval_pdf", "bf_bsdf_eval_pdf_device", "bf_bsdf_sample", "bf_bsdf_sample_device",
@@ -243,6 +245,9 @@ def load_library(path=None):
     lib.bf_render_skin_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp,
                                                 C.POINTER(bf_stats)]
     lib.bf_render_skin_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(bf_stats)]
+    lib.bf_vertex_normals.argtypes = [C.c_uint32, vp, C.c_uint32, vp, vp]
+    lib.bf_scene_set_normal_mode.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.bf_scene_get_normal_mode.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.bf_trace_closest.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bf_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bf_ray_intersect.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
@@ -310,6 +315,22 @@ def _dev(ptr, what):
     if not isinstance(ptr, int) or isinstance(ptr, bool):
         raise ValueError(f"{what}: a device pointer (int, e.g. tensor.data_ptr()) is expected, got {type(ptr).__name__}")
     return C.c_void_p(ptr) if ptr else None
+
+
+def vertex_normals(positions, faces, lib=None):
+    """bf_vertex_normals: the fp32 statement of recomputed vertex normals (include/beifong_hip.h) on the host, bit for bit what the
+    device computes under BF_NORMALS_RECOMPUTE.  positions float32[nv, 3], faces uint32[nf, 3] -> float32[nv, 3].  No device."""
+    p = vertex_array(positions, "positions")
+    f = np.asarray(faces)
+    if f.dtype != np.uint32:
+        raise TypeError(f"faces must be uint32, got {f.dtype}")
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"faces must be [nf, 3], got {f.shape}")
+    f = np.ascontiguousarray(f)
+    out = np.empty_like(p)
+    lib = lib or load_library()
+    check(lib, lib.bf_vertex_normals(p.shape[0], _ptr(p), f.shape[0], _ptr(f), _ptr(out)), "bf_vertex_normals")
+    return out
 
 
 MF_EVAL, MF_PDF, MF_SMITH_G1, MF_SAMPLE = range(4)
@@ -975,6 +996,23 @@ class Scene:
         check(self.lib, self.lib.bf_scene_update_vertices_device(self.handle, int(shape), C.c_void_p(int(positions_ptr)),
                                                                  C.c_void_p(int(normals_ptr)) if normals_ptr else None, float(bound),
                                                                  C.c_void_p(stream) if stream else None), "bf_scene_update_vertices_device")
+
+    def set_normal_mode(self, shape, mode):
+        """bf_scene_set_normal_mode: BF_NORMALS_RECOMPUTE makes every later position update of mesh shape `shape` that carries no
+        normals recompute them on the device (vertex_normals' arithmetic); BF_NORMALS_GIVEN (the default) keeps or replaces them."""
+        shape, mode = int(shape), int(mode)
+        if shape < 0 or mode < 0:
+            raise ValueError(f"shape index {shape}, mode {mode}")
+        check(self.lib, self.lib.bf_scene_set_normal_mode(self.handle, shape, mode), "bf_scene_set_normal_mode")
+
+    def normal_mode(self, shape):
+        """bf_scene_get_normal_mode: BF_NORMALS_GIVEN or BF_NORMALS_RECOMPUTE of mesh shape `shape` on this handle."""
+        shape = int(shape)
+        if shape < 0:
+            raise ValueError(f"shape index {shape}")
+        mode = C.c_uint32(0)
+        check(self.lib, self.lib.bf_scene_get_normal_mode(self.handle, shape, C.byref(mode)), "bf_scene_get_normal_mode")
+        return int(mode.value)
 
     def _deform_args(self, n_renders, transforms, seeds):
         xf = sa = None

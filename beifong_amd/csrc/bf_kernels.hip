@@ -1359,6 +1359,158 @@ extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const floa
     return hipGetLastError();
 }
 
+BF_NS_BEGIN
+// Recomputed vertex normals (BF_NORMALS_RECOMPUTE, bf_vertex_normals): angle-weighted face normals summed per vertex.
+// The arithmetic is stated ONCE, here, for the kernel and for the host entry alike: fp32, every product, sum, difference, quotient
+// and square root rounded (IEEE division and square root), no FMA outside bf_acos.  The device spells the operations __fmul_rn /
+// __fadd_rn / ..., the host as plain operators of this object (compiled with -ffp-contract=off).  For face (p0, p1, p2):
+//   n  = cross(p1 - p0, p2 - p0), each component fl(fl(a b) - fl(c d));  l2 = fl(fl(fl(nx^2) + fl(ny^2)) + fl(nz^2))
+//   the face contributes nothing unless l2 > 0;  nh = n / sqrt(l2) per component
+//   corner j: a = p[j+1] - p[j], b = p[j+2] - p[j], la = sqrt(dot(a, a)), lb likewise (dot = (x + y) + z of the rounded products);
+//     the corner contributes nothing unless la > 0 and lb > 0 (an edge whose squared length underflows to zero while l2 > 0);
+//     c = dot(a / la, b / lb) clamped to [-1, 1] by comparisons (a NaN stays one), theta = bf_acos(c), contribution fl(nh theta)
+// and per vertex: s = +0, plus its contributions in increasing face index, one add per component each; len = sqrt(dot(s, s));
+// s / len if len != 0, else (1, 0, 0).
+BF_HD float vn_mul(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmul_rn(a, b);
+#else
+    return a * b;
+#endif
+}
+BF_HD float vn_add(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fadd_rn(a, b);
+#else
+    return a + b;
+#endif
+}
+BF_HD float vn_sub(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fsub_rn(a, b);
+#else
+    return a - b;
+#endif
+}
+BF_HD float vn_div(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fdiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+// (not __fsqrt_rn: HIP defines it as the NATIVE square root, v_sqrt_f32's 1 ulp, unless OCML_BASIC_ROUNDED_OPERATIONS is set; the
+// builtin is the correctly rounded one in this object, as in bf_acos, and sqrtss on the host)
+BF_HD float vn_sqrt(float a) { return __builtin_sqrtf(a); }
+BF_HD float vn_acos(float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return acos_cr(c);
+#else
+    return bf_acos(c);
+#endif
+}
+BF_HD float vn_dot(const float *a, const float *b) { return vn_add(vn_add(vn_mul(a[0], b[0]), vn_mul(a[1], b[1])), vn_mul(a[2], b[2])); }
+
+// what face (p0, p1, p2) contributes to its corner j; false: nothing
+BF_HD bool vn_corner(const float *p0, const float *p1, const float *p2, uint32_t j, float out[3]) {
+    float e1[3], e2[3], n[3], a[3], b[3];
+    for (int c = 0; c < 3; ++c) e1[c] = vn_sub(p1[c], p0[c]), e2[c] = vn_sub(p2[c], p0[c]);
+    n[0] = vn_sub(vn_mul(e1[1], e2[2]), vn_mul(e1[2], e2[1]));
+    n[1] = vn_sub(vn_mul(e1[2], e2[0]), vn_mul(e1[0], e2[2]));
+    n[2] = vn_sub(vn_mul(e1[0], e2[1]), vn_mul(e1[1], e2[0]));
+    const float l2 = vn_dot(n, n);
+    if (!(l2 > 0.f)) return false;
+    const float l = vn_sqrt(l2);
+    const float *q = j == 0u ? p0 : (j == 1u ? p1 : p2), *qa = j == 0u ? p1 : (j == 1u ? p2 : p0), *qb = j == 0u ? p2 : (j == 1u ? p0 : p1);
+    for (int c = 0; c < 3; ++c) a[c] = vn_sub(qa[c], q[c]), b[c] = vn_sub(qb[c], q[c]);
+    const float la = vn_sqrt(vn_dot(a, a)), lb = vn_sqrt(vn_dot(b, b));
+    if (!(la > 0.f) || !(lb > 0.f)) return false;
+    for (int c = 0; c < 3; ++c) a[c] = vn_div(a[c], la), b[c] = vn_div(b[c], lb);
+    const float d = vn_dot(a, b);
+    const float theta = vn_acos(d < -1.f ? -1.f : (d > 1.f ? 1.f : d));
+    for (int c = 0; c < 3; ++c) out[c] = vn_mul(vn_div(n[c], l), theta);
+    return true;
+}
+BF_HD void vn_finish(const float s[3], float out[3]) {
+    const float len = vn_sqrt(vn_dot(s, s));
+    if (len != 0.f) {
+        for (int c = 0; c < 3; ++c) out[c] = vn_div(s[c], len);
+    } else {
+        out[0] = 1.f, out[1] = 0.f, out[2] = 0.f;
+    }
+}
+
+// One lane per vertex, grid y = geometry version (version v reads and writes `vstride` floats further, as bf_skin_vertices_kernel).
+// offset[nv + 1] / entries: the inverted index of the shape's faces (bf_mesh.cpp: normal_index), one uint4 per incident corner, sorted
+// by face: the face's three vertex indices in the order the scene gave them (each < nv, checked where the index is built), then the
+// corner number.  The lane recomputes every incident face's normal and its own corner's angle from the version's positions and sums
+// in list order: no atomics (their arrival order would make the sum irreproducible), no LDS.  The next entry's positions (and the
+// entry behind it) are loaded before the arithmetic of the current one.  A vertex of very high valence makes its lane loop that
+// long while the rest of its wave waits: correct, not fast.
+__global__ __launch_bounds__(256) void bf_vertex_normals_kernel(const uint32_t *__restrict__ offset, const uint4 *__restrict__ entries, uint32_t nv,
+                                                                const float *__restrict__ pos, float *__restrict__ nrm, uint64_t vstride) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    const float *p = pos + vstride * blockIdx.y;
+    uint32_t k = offset[v];
+    const uint32_t end = offset[v + 1u];
+    float s[3] = {0.f, 0.f, 0.f}, g[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    uint4 e = make_uint4(0u, 0u, 0u, 0u), e_next = e;
+    if (k < end) {
+        e = entries[k];
+        if (k + 1u < end) e_next = entries[k + 1u];
+        const float *p0 = p + 3u * (size_t) e.x, *p1 = p + 3u * (size_t) e.y, *p2 = p + 3u * (size_t) e.z;
+        for (int c = 0; c < 3; ++c) g[c] = p0[c], g[3 + c] = p1[c], g[6 + c] = p2[c];
+    }
+    for (; k < end; ++k) {
+        float cur[9];
+        for (int c = 0; c < 9; ++c) cur[c] = g[c];
+        const uint32_t j = e.w;
+        if (k + 1u < end) {
+            e = e_next;
+            const float *p0 = p + 3u * (size_t) e.x, *p1 = p + 3u * (size_t) e.y, *p2 = p + 3u * (size_t) e.z;
+            for (int c = 0; c < 3; ++c) g[c] = p0[c], g[3 + c] = p1[c], g[6 + c] = p2[c];
+            if (k + 2u < end) e_next = entries[k + 2u];
+        }
+        float t[3];
+        if (vn_corner(cur, cur + 3, cur + 6, j, t))
+            for (int c = 0; c < 3; ++c) s[c] = vn_add(s[c], t[c]);
+    }
+    float r[3];
+    vn_finish(s, r);
+    float *o = nrm + vstride * blockIdx.y + 3u * (size_t) v;
+    o[0] = r[0], o[1] = r[1], o[2] = r[2];
+}
+BF_NS_END  // namespace bfd
+
+// n_versions position arrays [n_versions][nv][3] (device) of one shape -> its vertex normals, the same layout
+extern "C" hipError_t bfk_launch_vertex_normals(const uint32_t *offset, const uint4 *entries, uint32_t nv, const float *pos, float *nrm,
+                                                uint32_t n_versions, hipStream_t stream) {
+    if (nv == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bfd::bf_vertex_normals_kernel, dim3((nv + 255u) / 256u, n_versions), dim3(256), 0, stream, offset, entries, nv, pos, nrm,
+                       (uint64_t) 3u * nv);
+    return hipGetLastError();
+}
+
+/* bf_vertex_normals (bf_mesh.cpp checks the arguments): the statement above on the host, faces in order, no device. */
+extern "C" void bfk_host_vertex_normals(uint32_t nv, const float *pos, uint32_t nf, const uint32_t *idx, float *out) {
+    for (size_t i = 0; i < 3 * (size_t) nv; ++i) out[i] = 0.f;
+    for (uint32_t f = 0; f < nf; ++f) {
+        const uint32_t *ix = idx + 3 * (size_t) f;
+        for (uint32_t j = 0; j < 3u; ++j) {
+            float t[3];
+            if (!bfd::vn_corner(pos + 3 * (size_t) ix[0], pos + 3 * (size_t) ix[1], pos + 3 * (size_t) ix[2], j, t)) continue;
+            float *s = out + 3 * (size_t) ix[j];
+            for (int c = 0; c < 3; ++c) s[c] = bfd::vn_add(s[c], t[c]);
+        }
+    }
+    for (uint32_t v = 0; v < nv; ++v) {
+        const float s[3] = {out[3 * (size_t) v], out[3 * (size_t) v + 1], out[3 * (size_t) v + 2]};
+        bfd::vn_finish(s, out + 3 * (size_t) v);
+    }
+}
+
 #ifdef BF_TAIL_PROF
 extern "C" int bfdbg_tail_profile(unsigned long long *out, int n_waves) {
     if (n_waves > 8192) n_waves = 8192;

@@ -341,7 +341,9 @@ bf_status deform_prepare(bf_scene *scene, hipStream_t stream) {
         if (st != BF_OK) return st;
         HIP_TRY(hipMemcpy(q, corners.data(), corners.size() * sizeof(uint4), hipMemcpyHostToDevice));
         g.corners = q;
-        for (bf_geometry::MeshTopo &tp : g.topo) std::vector<uint32_t>().swap(tp.indices);      // the table holds them now
+        // the table holds them now; a mesh with vertex normals keeps its own (normal_index builds the inverted index from them)
+        for (bf_geometry::MeshTopo &tp : g.topo)
+            if (!tp.has_normals) std::vector<uint32_t>().swap(tp.indices);
     }
     if (!m.bad) {
         HIP_TRY(hipMalloc((void **) &m.bad, 2 * sizeof(uint32_t)));
@@ -362,6 +364,68 @@ bf_status deform_watch(bf_scene *scene, hipStream_t stream) {
     return BF_OK;
 }
 
+// A scratch buffer of the handle's own (posed vertices, recomputed normals), at least `bytes`: grown on demand, never shrunk (the
+// gathers that read the old one are behind `stream` or before it: mesh_enter).  `what` names its content in the error text.
+bf_status vertex_scratch(float *&buf, size_t &cap, size_t bytes, hipStream_t stream, const char *who, const char *what) {
+    if (cap >= bytes) return BF_OK;
+    if (buf) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipFree(buf));
+        buf = nullptr;
+        cap = 0;
+    }
+    void *q = nullptr;
+    const hipError_t he = hipMalloc(&q, bytes);
+    if (he != hipSuccess) {
+        (void) hipGetLastError();
+        return fail(BF_ERR_NOMEM, "%s hipMalloc(%zu bytes) for the %s: %s", who, bytes, what, hipGetErrorString(he));
+    }
+    buf = (float *) q;
+    cap = bytes;
+    return BF_OK;
+}
+
+// ---- recomputed normals (bf_scene_set_normal_mode) ---------------------------------------------------------------------
+// The inverted index of shape `shape` (bf_scene.h: NormalIndex), built from the indices the scene was created with at the first use
+// by any handle that shares the geometry: per vertex its incident corners, faces in increasing order — the order of the sum.
+bf_status normal_index(bf_scene *scene, uint32_t shape, const char *who, const bf_geometry::NormalIndex **out) {
+    bf_geometry &g = *scene->geom;
+    if (g.normal_index.size() < g.topo.size()) g.normal_index.resize(g.topo.size());
+    if (!g.normal_index[shape]) {
+        const bf_geometry::MeshTopo &tp = g.topo[shape];
+        const uint32_t nv = tp.n_vertices;
+        const size_t n_corners = 3 * (size_t) tp.n_faces;
+        if (tp.indices.size() != n_corners)
+            return fail(BF_ERR_DEVICE, "%s shape %u: the scene no longer holds the indices of this mesh", who, shape);
+        if (n_corners > UINT32_MAX) return fail(BF_ERR_UNSUPPORTED, "%s shape %u: %zu corners (at most 2^32 - 1)", who, shape, n_corners);
+        std::vector<uint32_t> off((size_t) nv + 1, 0u);
+        for (size_t i = 0; i < n_corners; ++i) {
+            if (tp.indices[i] >= nv) return fail(BF_ERR_INVALID, "%s shape %u: face %zu names vertex %u of %u", who, shape, i / 3, tp.indices[i], nv);
+            ++off[(size_t) tp.indices[i] + 1];
+        }
+        for (uint32_t v = 0; v < nv; ++v) off[(size_t) v + 1] += off[v];
+        std::vector<uint32_t> at(off.begin(), off.end() - 1);
+        std::vector<uint4> ent(n_corners);
+        for (uint32_t f = 0; f < tp.n_faces; ++f) {
+            const uint32_t *ix = &tp.indices[3 * (size_t) f];
+            for (uint32_t j = 0; j < 3u; ++j) ent[at[ix[j]]++] = make_uint4(ix[0], ix[1], ix[2], j);
+        }
+        auto idx = std::make_shared<bf_geometry::NormalIndex>();
+        hipError_t he = hipMalloc((void **) &idx->offset, off.size() * sizeof(uint32_t));
+        if (he == hipSuccess && n_corners) he = hipMalloc((void **) &idx->entries, n_corners * sizeof(uint4));
+        if (he != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(BF_ERR_NOMEM, "%s shape %u: hipMalloc(%zu bytes) for the normal index: %s", who, shape,
+                        off.size() * sizeof(uint32_t) + n_corners * sizeof(uint4), hipGetErrorString(he));
+        }
+        HIP_TRY(hipMemcpy(idx->offset, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (n_corners) HIP_TRY(hipMemcpy(idx->entries, ent.data(), n_corners * sizeof(uint4), hipMemcpyHostToDevice));
+        g.normal_index[shape] = std::move(idx);
+    }
+    *out = g.normal_index[shape].get();
+    return BF_OK;
+}
+
 // one update with the arrays on the device already; box6: the new base box of the shape
 bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geometry::MeshTopo &tp, const float *pos_dev, const float *nrm_dev,
                                  float bound, const float *box6, bool watch, hipStream_t stream) {
@@ -370,7 +434,20 @@ bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geome
     bf_status st = BF_OK;
     if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
     if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
+    // BF_NORMALS_RECOMPUTE and no normals in the call: the statement of the new positions into the handle's scratch, gathered below
+    // as if the caller had given them (and watched like a device form: finite positions may have cross products that are not)
+    const bool recompute = !nrm_dev && scene->d.normals && m.recomputes(shape);
+    const bf_geometry::NormalIndex *nidx = nullptr;
+    if (recompute) {
+        if ((st = normal_index(scene, shape, who, &nidx)) != BF_OK) return st;
+        if ((st = vertex_scratch(m.nrm_vtx, m.nrm_vtx_cap, (size_t) tp.n_vertices * 3 * sizeof(float), stream, who, "recomputed normals")) != BF_OK) return st;
+    }
     if ((st = own_geometry(scene, stream, who)) != BF_OK) return st;
+    if (recompute) {
+        HIP_TRY(bfk_launch_vertex_normals(nidx->offset, nidx->entries, tp.n_vertices, pos_dev, m.nrm_vtx, 1u, stream));
+        nrm_dev = m.nrm_vtx;
+        watch = true;
+    }
     const MeshState::Bytes B = MeshState::bytes(scene->d);
     DevAlloc take{scene->owned, who};
     if (!m.base_private) {
@@ -500,6 +577,15 @@ bf_status deform_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
     if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
     if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
     if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
+    // BF_NORMALS_RECOMPUTE: a listed shape without normals of its own in this call gets them from each version's (untransformed)
+    // positions, behind `slice` below; its index is built here, before anything is enqueued
+    std::vector<const bf_geometry::NormalIndex *> nidx(n_shapes, nullptr);
+    size_t nrm_floats = 0;      // per render, over the recomputing shapes
+    for (uint32_t k = 0; k < n_shapes; ++k) {
+        if (!src[k].pos || src[k].nrm || !scene->d.normals || !m.recomputes(k)) continue;
+        if ((st = normal_index(scene, k, who, &nidx[k])) != BF_OK) return st;
+        nrm_floats += (size_t) src[k].nv * 3;
+    }
     // one padding bound for all versions: the handle's, raised over every mesh of every render (a deforming shape's box: [-bound, bound]^3)
     float oscale = m.origin_scale_built;
     {
@@ -524,6 +610,18 @@ bf_status deform_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
         bfd::DDeformSrc *hs = (bfd::DDeformSrc *) stg->host;
         for (uint32_t k = 0; k < n_shapes; ++k) hs[k] = src[k];
         if ((pst = slice(k0, kc, hs)) != BF_OK) return pst;
+        if (nrm_floats) {
+            // the chunk's recomputed normals: per shape [kc][nv][3], one shape after the other, version v of the gather reads slice v
+            if ((pst = vertex_scratch(m.nrm_vtx, m.nrm_vtx_cap, (size_t) kc * nrm_floats * sizeof(float), stream, who, "recomputed normals")) != BF_OK)
+                return pst;
+            float *out = m.nrm_vtx;
+            for (uint32_t k = 0; k < n_shapes; ++k) {
+                if (!nidx[k]) continue;
+                HIP_TRY(bfk_launch_vertex_normals(nidx[k]->offset, nidx[k]->entries, hs[k].nv, hs[k].pos, out, kc, stream));
+                hs[k].nrm = out;
+                out += (size_t) kc * hs[k].nv * 3;
+            }
+        }
         if (n) pack_rigid((float *) ((char *) stg->host + src_bytes), to_world + 12 * (size_t) k0 * n_shapes, moves.data() + (size_t) k0 * n_shapes, n);
         if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
         const MeshState::Base b = m.base(scene->d);
@@ -592,29 +690,14 @@ bf_status skin_bound_float(const double B[3], uint32_t shape, const char *who, f
     return BF_OK;
 }
 
-// the handle's scratch for posed vertices, at least `bytes` (the gathers that read the old one are behind `stream` or before it: mesh_enter)
+// the handle's scratch for posed vertices, at least `bytes`
 bf_status skin_scratch(bf_scene *scene, size_t bytes, hipStream_t stream, const char *who) {
-    MeshState &m = scene->mesh;
-    if (m.skin_vtx_cap >= bytes) return BF_OK;
-    if (m.skin_vtx) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipFree(m.skin_vtx));
-        m.skin_vtx = nullptr;
-        m.skin_vtx_cap = 0;
-    }
-    void *q = nullptr;
-    const hipError_t he = hipMalloc(&q, bytes);
-    if (he != hipSuccess) {
-        (void) hipGetLastError();
-        return fail(BF_ERR_NOMEM, "%s hipMalloc(%zu bytes) for the posed vertices: %s", who, bytes, hipGetErrorString(he));
-    }
-    m.skin_vtx = (float *) q;
-    m.skin_vtx_cap = bytes;
-    return BF_OK;
+    return vertex_scratch(scene->mesh.skin_vtx, scene->mesh.skin_vtx_cap, bytes, stream, who, "posed vertices");
 }
 
-// floats of one version of a skinned shape in the scratch: positions, then normals if the skin has them
-size_t skin_floats(const MeshSkin &sk) { return (size_t) sk.n_vertices * 3 * (sk.rest_nrm ? 2 : 1); }
+// floats of one version of a skinned shape in the scratch: positions, then normals if the skin has them and they are wanted
+// (not under BF_NORMALS_RECOMPUTE: the blended normals are then not computed)
+size_t skin_floats(const MeshSkin &sk, bool with_normals) { return (size_t) sk.n_vertices * 3 * (sk.rest_nrm && with_normals ? 2 : 1); }
 
 }  // namespace
 
@@ -657,6 +740,7 @@ MeshState::~MeshState() {
     if (vtx_host) (void) hipHostFree(vtx_host);
     if (vtx_dev) (void) hipFree(vtx_dev);
     if (skin_vtx) (void) hipFree(skin_vtx);
+    if (nrm_vtx) (void) hipFree(nrm_vtx);
 }
 
 extern "C" {
@@ -699,6 +783,7 @@ bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
     const MeshState &m = src->mesh;
     sc->mesh.origin_scale_built = m.origin_scale_built;
     sc->mesh.skins = m.skins;      // shared, never written: bf_scene_set_skin on either handle replaces that handle's pointer alone
+    sc->mesh.normal_mode = m.normal_mode;      // the source's modes at this moment; the clone's own from now on
     if (!m.tris0 && !m.geom_private) return BF_OK;
     // `src` has moved: the clone snapshots what src renders now as ITS geometry "as created"; uvs (and normals no transform moved) stay shared
     const MeshState::Bytes B = MeshState::bytes(src->d);
@@ -839,6 +924,41 @@ bf_status bf_scene_update_vertices_device(bf_scene *scene, uint32_t shape, const
     return mark_last(scene, stream);
 }
 
+// ---- recomputed normals: the host statement and the per-shape mode ---------------------------------------------------
+bf_status bf_vertex_normals(uint32_t n_vertices, const float *positions, uint32_t n_faces, const uint32_t *indices, float *normals_out) {
+    if ((n_vertices && (!positions || !normals_out)) || (n_faces && !indices)) return fail(BF_ERR_INVALID, "bf_vertex_normals: null array");
+    for (size_t i = 0; i < 3 * (size_t) n_faces; ++i)
+        if (indices[i] >= n_vertices)
+            return fail(BF_ERR_INVALID, "bf_vertex_normals: face %zu names vertex %u of %u", i / 3, indices[i], n_vertices);
+    bfk_host_vertex_normals(n_vertices, positions, n_faces, indices, normals_out);
+    return BF_OK;
+}
+
+bf_status bf_scene_set_normal_mode(bf_scene *scene, uint32_t shape, uint32_t mode) {
+    const char *fn = "bf_scene_set_normal_mode:";
+    if (!scene) return fail(BF_ERR_INVALID, "%s null scene", fn);
+    if (mode != BF_NORMALS_GIVEN && mode != BF_NORMALS_RECOMPUTE)
+        return fail(BF_ERR_INVALID, "%s shape %u: unknown mode %u (BF_NORMALS_GIVEN or BF_NORMALS_RECOMPUTE)", fn, shape, mode);
+    const bf_geometry::MeshTopo *tp = nullptr;
+    const bf_status st = check_deform_shape(scene, shape, true, fn, &tp);
+    if (st != BF_OK) return st;
+    BF_ENTER(scene);
+    MeshState &m = scene->mesh;
+    if (m.normal_mode.size() < scene->info.n_shapes) m.normal_mode.resize(scene->info.n_shapes, (uint8_t) BF_NORMALS_GIVEN);
+    m.normal_mode[shape] = (uint8_t) mode;      // read by the next position update; nothing moves now
+    return BF_OK;
+}
+
+bf_status bf_scene_get_normal_mode(const bf_scene *scene, uint32_t shape, uint32_t *mode_out) {
+    const char *fn = "bf_scene_get_normal_mode:";
+    if (!scene || !mode_out) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", fn, shape, scene->info.n_shapes);
+    if (scene->ends.shapes_host[shape].type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", fn, shape);
+    BF_ENTER(scene);
+    *mode_out = scene->mesh.recomputes(shape) ? BF_NORMALS_RECOMPUTE : BF_NORMALS_GIVEN;
+    return BF_OK;
+}
+
 // ---- rebuild of both trees on the device (bf_build.hip) ---------------------------------------------------------------
 /* test hook (not part of the ABI): nth > 0: the builder's nth device allocation fails; nth < 0: the |nth|-th allocation of the
    rebuild's own arrays fails; 0: off */
@@ -942,6 +1062,7 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
     auto g2 = std::make_shared<bf_geometry>();
     g2->topo = scene->geom->topo;
     g2->corners = (uint4 *) corners;
+    g2->normal_index = scene->geom->normal_index;      // per vertex and face, not per slot: shared as they are
     for (void *p : fresh)
         if (p && p != spill) g2->owned.push_back(p);
     const MeshState::Refit &rf = m.refit;
@@ -1177,14 +1298,15 @@ bf_status bf_scene_pose_skin(bf_scene *scene, uint32_t shape, const float *bones
     BF_ENTER(scene);
     MeshState &m = scene->mesh;
     if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
-    if ((st = skin_scratch(scene, skin_floats(*sk) * sizeof(float), stream, fn)) != BF_OK) return st;
+    const float *rest_nrm = m.recomputes(shape) ? nullptr : sk->rest_nrm;      // BF_NORMALS_RECOMPUTE: update_vertices_locked computes them
+    if ((st = skin_scratch(scene, skin_floats(*sk, rest_nrm != nullptr) * sizeof(float), stream, fn)) != BF_OK) return st;
     const size_t bytes = (size_t) sk->n_bones * 12 * sizeof(float);
     bf_scene::Stage *stg = nullptr;
     if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
     std::memcpy(stg->host, bones, bytes);
     if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
-    float *pos = m.skin_vtx, *nrm = sk->rest_nrm ? m.skin_vtx + 3 * (size_t) sk->n_vertices : nullptr;
-    HIP_TRY(bfk_launch_skin_vertices(sk->rest_pos, sk->rest_nrm, sk->index, sk->weight, sk->n_vertices, (const float *) stg->dev, sk->n_bones, pos, nrm,
+    float *pos = m.skin_vtx, *nrm = rest_nrm ? m.skin_vtx + 3 * (size_t) sk->n_vertices : nullptr;
+    HIP_TRY(bfk_launch_skin_vertices(sk->rest_pos, rest_nrm, sk->index, sk->weight, sk->n_vertices, (const float *) stg->dev, sk->n_bones, pos, nrm,
                                      1u, stream));
     HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel
     if ((st = update_vertices_locked(scene, shape, *tp, pos, nrm, bound, box, true, stream)) != BF_OK) return st;
@@ -1222,7 +1344,7 @@ bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, 
             std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
             if ((cst = skin_bound(*skins[j], shapes[j], bones[j] + (size_t) k * skins[j]->n_bones * 12, who, B)) != BF_OK) return cst;
         }
-        version_floats += skin_floats(*skins[j]);
+        version_floats += skin_floats(*skins[j], !scene->mesh.recomputes(shapes[j]));
         version_bones += (size_t) skins[j]->n_bones * 12;
     }
     float bound = std::numeric_limits<float>::min();
@@ -1260,12 +1382,14 @@ bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, 
         for (uint32_t j = 0; j < n_skinned; ++j) {
             const MeshSkin &sk = *skins[j];
             const size_t n = (size_t) kc * sk.n_vertices * 3;
-            float *pos = out, *nrm = sk.rest_nrm ? out + n : nullptr;
-            HIP_TRY(bfk_launch_skin_vertices(sk.rest_pos, sk.rest_nrm, sk.index, sk.weight, sk.n_vertices, db, sk.n_bones, pos, nrm, kc, stream));
+            // (BF_NORMALS_RECOMPUTE: no blended normals; deform_versions computes the posed surface's behind this)
+            const float *rest_nrm = m.recomputes(shapes[j]) ? nullptr : sk.rest_nrm;
+            float *pos = out, *nrm = rest_nrm ? out + n : nullptr;
+            HIP_TRY(bfk_launch_skin_vertices(sk.rest_pos, rest_nrm, sk.index, sk.weight, sk.n_vertices, db, sk.n_bones, pos, nrm, kc, stream));
             hs[shapes[j]].pos = pos;
             hs[shapes[j]].nrm = nrm;
             db += (size_t) kc * sk.n_bones * 12;
-            out += (size_t) kc * skin_floats(sk);
+            out += (size_t) kc * skin_floats(sk, rest_nrm != nullptr);
         }
         HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernels
         return BF_OK;

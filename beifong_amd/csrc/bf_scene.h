@@ -33,6 +33,9 @@ extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const 
 extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const float *rest_nrm, const uint4 *index, const float4 *weight, uint32_t nv,
                                                const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
                                                hipStream_t stream);
+extern "C" hipError_t bfk_launch_vertex_normals(const uint32_t *offset, const uint4 *entries, uint32_t nv, const float *pos, float *nrm,
+                                                uint32_t n_versions, hipStream_t stream);
+extern "C" void bfk_host_vertex_normals(uint32_t nv, const float *pos, uint32_t nf, const uint32_t *idx, float *out);
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
@@ -49,7 +52,8 @@ struct bf_geometry {
     std::vector<void *> owned;
     // vertex updates (bf_scene_update_vertices): what every mesh shape was created with, and the device corner
     // table built from it at the first update of any handle that shares these arrays (one uint4 per triangle slot in leaf order:
-    // the slot's three vertex indices within its shape, then the shape)
+    // the slot's three vertex indices within its shape, then the shape).  `indices` goes once the corner table holds it, except
+    // for a mesh with vertex normals: its normal index (below) may still have to be built from it.
     struct MeshTopo {
         uint32_t n_vertices = 0, n_faces = 0, prim0 = 0;
         bool has_normals = false;
@@ -57,6 +61,19 @@ struct bf_geometry {
     };
     std::vector<MeshTopo> topo;            // per shape (non-mesh shapes: empty)
     uint4 *corners = nullptr;
+    // recomputed normals (BF_NORMALS_RECOMPUTE): the inverted index of one shape's faces, built at the first
+    // recomputation of the shape by any handle that shares this geometry: offset[n_vertices + 1], and per incident corner one uint4
+    // (the face's three vertex indices, then the corner number), sorted by face.  Per vertex and face, not per slot:
+    // bf_scene_rebuild_bvh hands the same objects to the geometry it makes.
+    struct NormalIndex {
+        uint32_t *offset = nullptr;
+        uint4 *entries = nullptr;
+        ~NormalIndex() {
+            if (offset) (void) hipFree(offset);
+            if (entries) (void) hipFree(entries);
+        }
+    };
+    std::vector<std::shared_ptr<const NormalIndex>> normal_index;      // per shape, null until built
     ~bf_geometry() {
         for (void *p : owned) (void) hipFree(p);
     }
@@ -154,6 +171,13 @@ struct __attribute__((visibility("hidden"))) MeshState {
     std::vector<std::shared_ptr<const MeshSkin>> skins;
     float *skin_vtx = nullptr;
     size_t skin_vtx_cap = 0;                     // bytes
+    // normal modes (bf_scene_set_normal_mode): BF_NORMALS_* per shape, empty until the first call (every shape BF_NORMALS_GIVEN);
+    // a clone copies them.  nrm_vtx: where bf_vertex_normals_kernel writes the normals of an update or of a batch chunk, for the
+    // gather to read; the skin scratch's rules
+    std::vector<uint8_t> normal_mode;
+    float *nrm_vtx = nullptr;
+    size_t nrm_vtx_cap = 0;                      // bytes
+    bool recomputes(uint32_t shape) const { return shape < normal_mode.size() && normal_mode[shape] == BF_NORMALS_RECOMPUTE; }
 
     // what to read as the base rows: the handle's own once it has moved, else the arrays it renders (a clone's snapshot included)
     struct Base { const float4 *tris, *nodes, *wnodes, *normals; };

@@ -136,6 +136,14 @@ int bfh_scene_mesh_changed(void *scene, void *shape) {
         as_scene(scene)->mesh_changed(s);
     })
 }
+/// parameters_changed(recompute_normals=True): Scene::mesh_changed with the normals recomputed on host and device
+int bfh_scene_mesh_changed_recompute(void *scene, void *shape) {
+    BFH_TRY({
+        auto *s = dynamic_cast<Shape *>((Object *) shape);
+        if (!s) Throw("object is not a Shape");
+        as_scene(scene)->mesh_changed(s, true);
+    })
+}
 /// bf_scene_create calls this Scene has made so far (a test's proof that parameters_changed updated the cached handle)
 int bfh_scene_device_creations(void *scene, unsigned long long *out) { BFH_TRY(*out = as_scene(scene)->device_creations()) }
 /// flattened description the integrator hands to bf_scene_create (for tests: the

@@ -387,6 +387,13 @@ void Mesh::set_vertex_normals(const float *data, size_t n) {
     if (m_normals.empty()) Throw("Mesh: the mesh has no vertex normals: it cannot take any");
     write_vertices(m_normals, data, n, "vertex normals");
 }
+void Mesh::recompute_vertex_normals_f32() {
+    if (m_normals.empty()) Throw("Mesh: the mesh has no vertex normals: none can be recomputed");      // mesh.cpp:202-204
+    std::vector<float> nrm(m_positions.size());
+    const bf_status st = bf_vertex_normals(vertex_count(), m_positions.data(), primitive_count(), m_faces.data(), nrm.data());
+    if (st != BF_OK) Throw("bf_vertex_normals failed (status %d): %s", st, bf_last_error());
+    std::memcpy(m_normals.data(), nrm.data(), nrm.size() * sizeof(float));      // in place, as write_vertices
+}
 
 // ---- scene --------------------------------------------------------------------
 struct Scene::Flat {
@@ -612,12 +619,19 @@ std::vector<bf_scene *> Scene::device_scenes(const Endpoint *endpoint, int n) {
     return r;
 }
 
-void Scene::mesh_changed(const Shape *shape) {
+void Scene::mesh_changed(const Shape *shape, bool recompute_normals) {
     size_t index = m_shapes.size();
     for (size_t i = 0; i < m_shapes.size(); ++i)
         if (m_shapes[i].get() == shape) index = i;
     if (index == m_shapes.size()) Throw("parameters_changed: the shape does not belong to this scene");
     if (shape->is_rectangle() || !shape->positions()) Throw("parameters_changed: shape %zu is not a mesh: it has no vertex buffers", index);
+    if (recompute_normals) {
+        // Mesh::parameters_changed -> recompute_vertex_normals (mesh.cpp:852-871): the host buffer by bf_vertex_normals, the cached
+        // handles by the device under BF_NORMALS_RECOMPUTE from the same positions: bit for bit the same normals, none uploaded
+        Mesh *mesh = dynamic_cast<Mesh *>(m_shapes[index].get());
+        if (!mesh) Throw("parameters_changed: shape %zu is not a mesh: it has no vertex buffers", index);
+        mesh->recompute_vertex_normals_f32();
+    }
     if (!m_flat) return;      // nothing cached: the next flatten reads the new arrays
     std::vector<bf_scene *> handles;
     if (m_flat->device) handles.push_back(m_flat->device);
@@ -628,8 +642,10 @@ void Scene::mesh_changed(const Shape *shape) {
         if (bf_scene_get_info(h, &info) != BF_OK) Throw("bf_scene_get_info: %s", bf_last_error());
         if (h == handles.front()) home = info.device;
         if (bf_set_device(info.device) != BF_OK) Throw("bf_set_device(%d): %s", info.device, bf_last_error());
-        bf_status st = bf_scene_update_vertices(h, (uint32_t) index, shape->positions()->data(),
-                                                shape->normals() ? shape->normals()->data() : nullptr, nullptr);
+        bf_status st = recompute_normals ? bf_scene_set_normal_mode(h, (uint32_t) index, BF_NORMALS_RECOMPUTE) : BF_OK;
+        if (st == BF_OK)
+            st = bf_scene_update_vertices(h, (uint32_t) index, shape->positions()->data(),
+                                          !recompute_normals && shape->normals() ? shape->normals()->data() : nullptr, nullptr);
         (void) bf_set_device(home);
         if (st != BF_OK) Throw("bf_scene_update_vertices failed (status %d): %s", st, bf_last_error());
     }

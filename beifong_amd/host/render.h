@@ -249,6 +249,9 @@ public:
     /// finite; the topology is fixed.  Normals only on a mesh that has them.  Scene::mesh_changed pushes them to the device.
     void set_vertex_positions(const float *data, size_t n);
     void set_vertex_normals(const float *data, size_t n);
+    /// the normal buffer rewritten from the current positions by bf_vertex_normals (fp32, bit for bit what the device computes under
+    /// BF_NORMALS_RECOMPUTE); throws for a mesh without vertex normals
+    void recompute_vertex_normals_f32();
     const Class *class_() const override;
 
 protected:
@@ -359,7 +362,9 @@ public:
     /// Mesh::parameters_changed (mesh.h:243): the vertices of `shape` were written.  The cached device scenes are UPDATED through
     /// bf_scene_update_vertices (a BVH refit on the device), not created again; without a cached device scene nothing is to
     /// be done, the next flatten reads the new arrays.  Throws for a shape that is not a mesh of this scene.
-    void mesh_changed(const Shape *shape);
+    /// recompute_normals: the mesh's normal buffer is rewritten first (Mesh::recompute_vertex_normals_f32) and the cached handles
+    /// get BF_NORMALS_RECOMPUTE and a position-only update: no normal array is uploaded.  Throws for a mesh without normals.
+    void mesh_changed(const Shape *shape, bool recompute_normals = false);
     /// how many times this Scene has called bf_scene_create so far (all endpoints, all GPUs)
     uint64_t device_creations() const { return m_device_creations; }
     const Class *class_() const override;

@@ -52,6 +52,9 @@ def lib():
     l.bfh_shape_vertices.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_ulonglong)]
     l.bfh_shape_set_vertices.argtypes = [vp, C.c_int, vp, C.c_ulonglong]
     l.bfh_scene_mesh_changed.argtypes = [vp, vp]
+    if not hasattr(l, "bfh_scene_mesh_changed_recompute"):
+        raise HostError(f"{LIB_PATH} is stale (no bfh_scene_mesh_changed_recompute): rebuild the host layer (make -C beifong_amd/host)")
+    l.bfh_scene_mesh_changed_recompute.argtypes = [vp, vp]
     l.bfh_scene_device_creations.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     l.bfh_scene_flat_desc.argtypes = [vp, vp]
     l.bfh_scene_flat_desc.restype = C.POINTER(capi.bf_scene_desc)
@@ -505,13 +508,17 @@ class Shape(_Handle):
     def set_vertex_normals(self, array):
         self._set_buffer(1, array, "vertex normals")
 
-    def parameters_changed(self):
+    def parameters_changed(self, recompute_normals=False):
         """The vertex buffers were written: the scene's cached device handles are updated through bf_scene_update_vertices (a
-        BVH refit on the device), not rebuilt; a scene without one flattens the new vertices at its next render."""
+        BVH refit on the device), not rebuilt; a scene without one flattens the new vertices at its next render.
+        recompute_normals=True (Mesh::parameters_changed -> recompute_vertex_normals): the mesh's normal buffer is rewritten from
+        the positions by bf_vertex_normals, and every cached handle gets BF_NORMALS_RECOMPUTE and a position-only update, so the
+        device computes the same normals bit for bit and none is uploaded.  HostError for a mesh without vertex normals."""
         scene = self._owner
         if not isinstance(scene, Scene):
             raise HostError("parameters_changed: the shape is not bound to a loaded scene")
-        check(lib().bfh_scene_mesh_changed(scene._ptr, self._ptr))
+        fn = lib().bfh_scene_mesh_changed_recompute if recompute_normals else lib().bfh_scene_mesh_changed
+        check(fn(scene._ptr, self._ptr))
 
 
 def _bound(obj):

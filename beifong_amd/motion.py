@@ -111,6 +111,16 @@ def apply_skin(positions, normals, index, weight, bones):
         return blend(p, True), None if n is None else blend(n, False)
 
 
+def vertex_normals_f32(positions, faces):
+    """The vertex normals the device computes under BF_NORMALS_RECOMPUTE (Scene.set_normal_mode), bit for bit, on the host:
+    angle-weighted face normals summed per vertex in increasing face index, every operation fp32 (the statement is in
+    include/beifong_hip.h; this is bf_vertex_normals, which needs no device).  Put them into a description so that frame 0
+    matches the frames the device recomputes.  A vertex of no face, or of degenerate faces only, gets (1, 0, 0).
+    positions float32[nv, 3], faces uint32[nf, 3] -> float32[nv, 3]."""
+    from . import capi
+    return capi.vertex_normals(positions, faces)
+
+
 def moved_description(sd, transforms):
     """A new SceneDesc equal to `sd` with every mesh's positions and normals replaced by apply_rigid(..., transforms[k]):
     the scene bf_scene_create would have to rebuild for the pose bf_scene_transform_meshes gives a handle of `sd`.

@@ -251,8 +251,16 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
             h.close()
 
 
+def _recompute(first, recompute_normals):
+    """recompute_normals=(shapes...) of the deform and skin sweeps: BF_NORMALS_RECOMPUTE on the first handle, before it is cloned
+    (clones inherit the modes), so every handle of the sweep, per_pulse=True included, recomputes those shapes' vertex normals on
+    the device from each pulse's positions."""
+    for k in (recompute_normals or ()):
+        first.set_normal_mode(int(k), capi.BF_NORMALS_RECOMPUTE)
+
+
 def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False, rebuild_every=None,
-                        classes=None):
+                        classes=None, recompute_normals=None):
     """Coherent pulse sweep in which meshes DEFORM between the pulses: a walking pedestrian, a vibrating
     panel.  The deforming counterpart of render_motion_sweep.
 
@@ -266,7 +274,10 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
     rebuild_every=k (an integer): a working handle's trees are rebuilt on the device (bf_scene_rebuild_bvh) after every k-th
     frame's update of that handle, so a mesh that drifts far from its first frame keeps a tree made for where it is; the
     batched path then renders its group in batches of k frames, the handle's base vertices set to the frame before each.
-    Results do not change.  Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W); with
+    Results do not change.  recompute_normals=(shapes...): those meshes (which must have vertex normals) get the angle-weighted
+    normals of every pulse's positions, computed on the device (Scene.set_normal_mode; motion.vertex_normals_f32 is the
+    statement), where by default they keep the normals of the description.
+    Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W); with
     classes=(shape_class, n_classes, miss_class), as in render_motion_sweep, float32[n_pulses, n_classes, f_bins * t_bins, 3]."""
     import torch
     if rebuild_every is not None and int(rebuild_every) < 1:
@@ -290,6 +301,7 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
     handles = [first]
     try:
         launch, n_classes = _classed(first, launch, classes)
+        _recompute(first, recompute_normals)
         handles += [first.clone() for _ in range(n_streams - 1)]
         cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
         dpos = [torch.from_numpy(p).to(dev) for p in pos]
@@ -334,7 +346,7 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
 
 
 def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None, classes=None, lib=None,
-                      device=None):
+                      device=None, recompute_normals=None):
     """Coherent pulse sweep in which SKINNED meshes are posed by a few bones per pulse: the counterpart of
     render_deform_sweep whose per-pulse input is [n_bones, 3, 4] floats per mesh, not its vertices.
 
@@ -346,7 +358,8 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
     The scene is built once and the skins attached before it is cloned; the pulses are split into `n_streams` contiguous
     groups, one per handle and stream, each ONE skin batch (bf_render_skin_batch_device).  per_pulse=True is the reference
     path: the pulses rotate over the handles, one bf_scene_pose_skin (+ one bf_scene_transform_meshes) and one render per
-    pulse; per-path results are the same.  rebuild_every and classes as in render_deform_sweep.  Returns the cube
+    pulse; per-path results are the same.  rebuild_every, classes and recompute_normals (the normals of the POSED surface in
+    place of the blended rest normals) as in render_deform_sweep.  Returns the cube
     float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3] with classes."""
     import torch
     if rebuild_every is not None and int(rebuild_every) < 1:
@@ -378,6 +391,7 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
             rest_n = np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None
             first.set_skin(int(sh), tab.shape[1], rest, index, weight, rest_normals=rest_n)
         launch, n_classes = _classed(first, launch, classes)
+        _recompute(first, recompute_normals)
         handles += [first.clone() for _ in range(n_streams - 1)]
         cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
         for s in streams:           # the cube was zero-filled on the current stream

@@ -553,7 +553,9 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
  *     bf_trace_* result is bit-identical to a bf_scene_create of the same description with shape `shape` carrying
  *     `positions` (and `normals`), followed by the same transform call.
  *   Normals: NULL keeps the base normals the mesh has; non-NULL on a mesh created without normals is BF_ERR_INVALID.
- *     Normals are not recomputed.  Texture coordinates and the rows' prim / shape / tag words are untouched.
+ *     Normals are not recomputed unless the shape's normal mode is BF_NORMALS_RECOMPUTE (bf_scene_set_normal_mode, below): then
+ *     a call with normals == NULL computes them on the device from `positions`, and the equivalence above holds with `normals`
+ *     = bf_vertex_normals(positions).  Texture coordinates and the rows' prim / shape / tag words are untouched.
  *   Origin bound: the host form computes the shape's new box and raises (never lowers) the bound on ray origins the boxes
  *     are padded for.  The device form cannot see the values: the caller declares bound >= max |coordinate| of the
  *     vertices passed and [-bound, bound]^3 is taken as the shape's base box.  The gather kernel checks every corner it
@@ -865,6 +867,8 @@ bf_status bf_render_motion_batch(bf_scene *scene, const bf_launch *launch, uint3
  *     bf_scene_transform_meshes(to_world[k]) + a stand-alone render with seeds[k] on a second handle.
  *   bound: as bf_scene_update_vertices_device, for all arrays of the call (the host form computes it); a violation is
  *     counted and reported the same way, the triangle keeping the handle's base row in that version.
+ *   Normals: a listed shape whose normals entry is NULL keeps the handle's base normals, or, under BF_NORMALS_RECOMPUTE
+ *     (bf_scene_set_normal_mode), gets those of each version's untransformed positions, which to_world[k] then turns.
  *   BF_ERR_INVALID before anything is enqueued: what bf_scene_update_vertices refuses, a shape listed twice,
  *     n_renders == 0, a multi-pixel film, BF_FLAG_ROLLING, and what a motion batch refuses of to_world.  The error text
  *     names render and shape. */
@@ -896,7 +900,8 @@ bf_status bf_render_deform_batch(bf_scene *scene, const bf_launch *launch, uint3
  *     held before); the handle's pose goes on top.  Semantics, ordering, copy on write and "an open rolling sequence is
  *     finished first" are bf_scene_update_vertices': after the call every path is bit-identical to a bf_scene_create of the
  *     description with the shape carrying apply_skin's arrays, followed by the same transform call.  `bones` is a host array,
- *     free again when the call returns.
+ *     free again when the call returns.  Under BF_NORMALS_RECOMPUTE (bf_scene_set_normal_mode) the blended normals n' are not
+ *     computed: the shape carries bf_vertex_normals of apply_skin's positions instead, in a pose and in every version of a batch.
  *   bf_render_skin_batch(_device): bf_render_deform_batch with bones[j] = host [n_renders][n_bones(shapes[j])][12] in place
  *     of the vertex arrays.  Render k is bit-identical to bf_scene_pose_skin(slice k) + bf_scene_transform_meshes(to_world[k])
  *     + a stand-alone render with seeds[k] on a second handle.  Arena, chunking (BF_MOTION_BATCH_MB) and launch flags
@@ -927,6 +932,48 @@ bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, 
 bf_status bf_render_skin_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_skinned,
                                const uint32_t *shapes, const float *const *bones, uint32_t n_shapes, const float *to_world, float *hist_out,
                                bf_path_record *records_out, bf_stats *stats_out);
+
+/* Recomputed vertex normals: angle-weighted face normals, computed on the device wherever a mesh's base positions are
+ * replaced, so that a smooth-shaded mesh that deforms or is skinned needs no normal array per frame.  DESIGN.md 6d.
+ *   Arithmetic, fp32, every product, sum, difference, quotient and square root rounded (IEEE division and square root), no
+ *   FMA outside the engine's fp32 arc cosine (bf_device_math.h, as bf_eval_elementary evaluates it).  For each face f with corners p0, p1, p2:
+ *       n  = cross(p1 - p0, p2 - p0), each component fl(fl(a b) - fl(c d));   l2 = fl(fl(fl(nx^2) + fl(ny^2)) + fl(nz^2))
+ *       the face contributes nothing unless l2 > 0;   nh = n / sqrt(l2) per component
+ *       at corner j:  a = p[j+1] - p[j], b = p[j+2] - p[j], la = sqrt(dot(a, a)), lb = sqrt(dot(b, b)), dot = (x + y) + z of
+ *         the rounded products; the corner contributes nothing unless la > 0 and lb > 0 (an edge whose squared length underflows
+ *         to zero while l2 > 0); c = dot(a / la, b / lb) clamped to [-1, 1]; theta = that arc cosine of c; contribution fl(nh theta)
+ *     and for each vertex: s = +0, plus its contributions IN INCREASING FACE INDEX (one add per component each);
+ *     len = sqrt(dot(s, s)); the normal is s / len if len != 0, else (1, 0, 0): a vertex of no face, or of degenerate faces only.
+ *   bf_vertex_normals: that statement on the host, bit for bit what the device computes.  It needs no device and no scene: it
+ *     is what a caller puts into a description so that frame 0 matches the frames the device recomputes.  BF_ERR_INVALID for a
+ *     NULL array (with a non-zero count) or an index >= n_vertices.  beifong_amd.motion.vertex_normals_f32 is its Python face.
+ *   bf_scene_set_normal_mode: per handle and mesh shape.  BF_NORMALS_GIVEN (the default): normals are replaced when a call
+ *     gives them, kept when not, never recomputed.  BF_NORMALS_RECOMPUTE: wherever the shape's base positions are replaced and
+ *     the call carries no normals for it, its base normals become the statement above of the new base positions —
+ *     bf_scene_update_vertices(_device), bf_scene_pose_skin (the skin's blended normals are then not computed),
+ *     bf_render_deform_batch(_device) for a listed shape whose normals entry is NULL, bf_render_skin_batch(_device).  Explicit
+ *     normals in a call win for that call.  In a batch the normals of version k are those of its UNTRANSFORMED positions;
+ *     to_world[k] then turns them as it turns given ones (n' = R n, not renormalised).
+ *     Contract: after such a call every path and every bf_ray_intersect / bf_trace_* result is bit-identical to a
+ *     bf_scene_create of the description with the shape carrying `positions` and bf_vertex_normals(positions), followed by the
+ *     same transform call.  Setting the mode changes nothing until the next position update; switching back to GIVEN keeps the
+ *     normals last computed.  A clone inherits the source's modes when it is taken and owns them from then on.
+ *     The device forms' bound contract is unchanged: a normal that is not finite is refused by the gather and counted like a
+ *     given one (the host form of an update under RECOMPUTE is watched the same way: positions may be finite and their cross
+ *     products not).
+ *   Cost: the first recomputation of a shape builds its inverted index on the host (per vertex, its incident corners in face
+ *     order: 48 bytes per face + 4 per vertex on the device), shared by clones and kept across bf_scene_rebuild_bvh.  The
+ *     normals are written to a scratch buffer of the handle's own before the gather reads them, 12 bytes per vertex and
+ *     version over the recomputing shapes of the call and the renders of the largest chunk; it grows only, is freed with the
+ *     handle and lies OUTSIDE the BF_MOTION_BATCH_MB budget, as the skin scratch.
+ *   Refusals, nothing enqueued and the scene as it was: BF_ERR_INVALID for a NULL scene, a shape out of range or not a mesh,
+ *     an unknown mode, a mesh created without vertex normals; BF_ERR_UNSUPPORTED for a mesh that carries an emitter /
+ *     transmitter.  bf_scene_get_normal_mode: BF_ERR_INVALID for a NULL argument, a shape out of range or not a mesh. */
+enum { BF_NORMALS_GIVEN = 0, BF_NORMALS_RECOMPUTE = 1 };
+bf_status bf_vertex_normals(uint32_t n_vertices, const float *positions /* host [n_vertices][3] */, uint32_t n_faces,
+                            const uint32_t *indices /* host [n_faces][3] */, float *normals_out /* host [n_vertices][3] */);
+bf_status bf_scene_set_normal_mode(bf_scene *scene, uint32_t shape, uint32_t mode);
+bf_status bf_scene_get_normal_mode(const bf_scene *scene, uint32_t shape, uint32_t *mode_out);
 
 /* Scene::ray_intersect / ray_test over a batch of HOST rays (tests, tools).
  * rays: [n][8] = o.xyz, mint, d.xyz, maxt.  Outputs may be NULL.
