@@ -162,6 +162,7 @@ EXPORTED_SYMBOLS = [
     "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
     "bf_scene_update_vertices", "bf_scene_update_vertices_device", "bf_render_deform_batch_device", "bf_render_deform_batch",
     "bf_scene_set_skin", "bf_scene_pose_skin", "bf_render_skin_batch_device", "bf_render_skin_batch",
+    "bf_scene_set_morph", "bf_scene_pose_morph", "bf_render_morph_batch_device", "bf_render_morph_batch",
     "bf_vertex_normals", "bf_scene_set_normal_mode", "bf_scene_get_normal_mode",
     "bf_scene_rebuild_bvh", "bf_scene_read_bvh",
     "bf_trace_closest", "bf_trace_any", "bf_ray_intersect", "bf_eval_elementary",
@@ -248,6 +249,12 @@ def load_library(path=None):
     lib.bf_vertex_normals.argtypes = [C.c_uint32, vp, C.c_uint32, vp, vp]
     lib.bf_scene_set_normal_mode.argtypes = [vp, C.c_uint32, C.c_uint32]
     lib.bf_scene_get_normal_mode.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.bf_scene_set_morph.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    lib.bf_scene_pose_morph.argtypes = [vp, C.c_uint32, vp, vp, vp]
+    lib.bf_render_morph_batch_device.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, vp,
+                                                 C.POINTER(bf_stats)]
+    lib.bf_render_morph_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp,
+                                          C.POINTER(bf_stats)]
     lib.bf_trace_closest.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
     lib.bf_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bf_ray_intersect.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
@@ -683,6 +690,43 @@ def skin_tables(bones, n_bones=None):
     return n_renders, np.asarray(shapes, np.uint32), [bone_array(v, f"bones of shape {k}", nb.get(k), n_renders) for k, v in items]
 
 
+def weight_array(a, name, n_targets=None, n_renders=None):
+    """A float32 weight table for a morph pose, checked: [n_targets] for one pose, [K, n_targets] for a batch.  float32 only, as
+    vertex_array."""
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise TypeError(f"{name} must be float32, got {a.dtype}")
+    want = 1 if n_renders is None else 2
+    if a.ndim != want:
+        raise ValueError(f"{name} must be [{'' if n_renders is None else 'n_renders, '}n_targets], got {a.shape}")
+    if n_renders is not None and a.shape[0] != n_renders:
+        raise ValueError(f"{name}: {a.shape[0]} slices for {n_renders} renders")
+    if n_targets is not None and a.shape[-1] != n_targets:
+        raise ValueError(f"{name}: {a.shape[-1]} weights for a morph of {n_targets} targets")
+    return np.ascontiguousarray(a)
+
+
+def morph_tables(weights, n_targets=None):
+    """What bf_render_morph_batch reads, from {shape: weights[K, n_targets]} or a list of (shape, array) pairs:
+    (n_renders, uint32 shapes, [weight arrays]).  A shape listed twice is refused here.  n_targets: {shape: count} to check against."""
+    items = list(weights.items()) if isinstance(weights, dict) else [(k, v) for k, v in weights]
+    if not items:
+        raise ValueError("weights: no morphed shape")
+    shapes = [int(k) for k, _ in items]
+    if len(set(shapes)) != len(shapes):
+        raise ValueError(f"a shape is listed twice: {shapes}")
+    if any(k < 0 for k in shapes):
+        raise ValueError(f"negative shape index in {shapes}")
+    first = np.asarray(items[0][1])
+    if first.ndim != 2:
+        raise ValueError(f"weights of shape {shapes[0]} must be [n_renders, n_targets], got {first.shape}")
+    n_renders = first.shape[0]
+    if n_renders == 0:
+        raise ValueError("weights: no renders")
+    nt = n_targets or {}
+    return n_renders, np.asarray(shapes, np.uint32), [weight_array(v, f"weights of shape {k}", nt.get(k), n_renders) for k, v in items]
+
+
 class Scene:
     """Device-resident immutable scene (bf_scene)."""
 
@@ -718,6 +762,7 @@ class Scene:
         check(self.lib, self.lib.bf_scene_clone(self.handle, C.byref(h)), "bf_scene_clone")
         other.handle = h
         other._skin_bones = dict(getattr(self, "_skin_bones", {}))      # skins are shared with clones taken afterwards
+        other._morph_targets = dict(getattr(self, "_morph_targets", {}))    # and so are morphs
         return other
 
     def __del__(self):
@@ -1127,6 +1172,79 @@ class Scene:
                                                              xf.shape[1] if xf is not None else 0, _ptr(xf), C.c_void_p(hist_ptr),
                                                              C.c_void_p(records_ptr) if records_ptr else None, _stream(stream),
                                                              C.byref(st) if st is not None else None), "bf_render_skin_batch_device")
+        return st
+
+    def set_morph(self, shape, n_targets, rest_positions=None, delta_positions=None, rest_normals=None, delta_normals=None):
+        """bf_scene_set_morph: attach morph targets to mesh shape `shape`: rest positions float32[nv, 3] (and rest normals, for a mesh
+        with vertex normals), position deltas float32[n_targets, nv, 3] and optionally normal deltas of the same shape; deep-copied.
+        n_targets = 0 removes the morph."""
+        shape, n_targets = int(shape), int(n_targets)
+        if shape < 0 or n_targets < 0:
+            raise ValueError(f"shape index {shape}, {n_targets} targets")
+        p = n = dp = dn = None
+        if n_targets:
+            p = vertex_array(rest_positions, "rest_positions", self.mesh_vertex_count(shape))
+            n = vertex_array(rest_normals, "rest_normals", p.shape[0]) if rest_normals is not None else None
+            dp = vertex_array(delta_positions, "delta_positions", p.shape[0], n_targets)
+            dn = vertex_array(delta_normals, "delta_normals", p.shape[0], n_targets) if delta_normals is not None else None
+        check(self.lib, self.lib.bf_scene_set_morph(self.handle, shape, n_targets, _ptr(p), _ptr(n), _ptr(dp), _ptr(dn)), "bf_scene_set_morph")
+        counts = self.__dict__.setdefault("_morph_targets", {})
+        counts[shape] = n_targets
+
+    def _morph_target_count(self, shape):
+        return getattr(self, "_morph_targets", {}).get(int(shape)) or None
+
+    def pose_morph(self, shape, weights, bones=None, stream=0):
+        """bf_scene_pose_morph: the base of morphed mesh shape `shape` becomes its rest shape plus the targets weighted by `weights`
+        (float32[n_targets], motion.apply_morph's arithmetic), skinned by `bones` (float32[n_bones, 3, 4]) behind that if given;
+        the handle's pose is applied on top, the BVHs are re-fitted on the device."""
+        shape = int(shape)
+        if shape < 0:
+            raise ValueError(f"shape index {shape}")
+        w = weight_array(weights, "weights", self._morph_target_count(shape))
+        b = bone_array(bones, "bones", self._skin_bone_count(shape)) if bones is not None else None
+        check(self.lib, self.lib.bf_scene_pose_morph(self.handle, shape, _ptr(w), _ptr(b), _stream(stream)), "bf_scene_pose_morph")
+
+    def _morph_args(self, weights, bones):
+        keys = [int(k) for k in (weights.keys() if isinstance(weights, dict) else [k for k, _ in weights])]
+        nt = {k: self._morph_target_count(k) for k in keys}
+        n_renders, shapes, tabs = morph_tables(weights, {k: v for k, v in nt.items() if v is not None})
+        wp = (C.c_void_p * len(tabs))(*[t.ctypes.data for t in tabs])
+        btabs, bp = [], None
+        if bones:
+            bones = {int(k): v for k, v in (bones.items() if isinstance(bones, dict) else bones)}
+            if not set(bones) <= set(keys):
+                raise ValueError(f"bones for shapes {sorted(bones)}, weights for shapes {sorted(keys)}")
+            btabs = [bone_array(bones[k], f"bones of shape {k}", self._skin_bone_count(k), n_renders) if bones.get(k) is not None else None
+                     for k in keys]
+            bp = (C.c_void_p * len(btabs))(*[t.ctypes.data if t is not None else None for t in btabs])
+        return n_renders, shapes, (tabs, btabs), wp, bp
+
+    def render_morph_batch(self, launch, weights, bones=None, transforms=None, seeds=None, records=False):
+        """bf_render_morph_batch: render k sees morphed shape s posed by weights[s][k] ([K, n_targets] float32 each) and, for the shapes
+        `bones` lists ({shape: [K, n_bones, 3, 4]}), skinned behind that; then every mesh at transforms[k] (None: none)
+        -> float32[K, channels] (+ records, stats).  The handle itself does not change."""
+        n_renders, shapes, keep, wp, bp = self._morph_args(weights, bones)
+        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
+        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
+        st = bf_stats()
+        check(self.lib, self.lib.bf_render_morph_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), len(shapes), _ptr(shapes), wp, bp,
+                                                       xf.shape[1] if xf is not None else 0, _ptr(xf), _ptr(hist), _ptr(rec), C.byref(st)),
+              "bf_render_morph_batch")
+        return hist, rec, st
+
+    def render_morph_batch_device(self, launch, weights, hist_ptr, bones=None, transforms=None, seeds=None, stream=0, records_ptr=None,
+                                  want_stats=False):
+        """bf_render_morph_batch_device: the same (weights and bone tables stay host arrays) with render k accumulated into
+        hist_ptr[k * channels ..] (device)."""
+        n_renders, shapes, keep, wp, bp = self._morph_args(weights, bones)
+        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        st = bf_stats() if want_stats else None
+        check(self.lib, self.lib.bf_render_morph_batch_device(self.handle, C.byref(launch), n_renders, _ptr(sa), len(shapes), _ptr(shapes), wp, bp,
+                                                              xf.shape[1] if xf is not None else 0, _ptr(xf), C.c_void_p(hist_ptr),
+                                                              C.c_void_p(records_ptr) if records_ptr else None, _stream(stream),
+                                                              C.byref(st) if st is not None else None), "bf_render_morph_batch_device")
         return st
 
     def trace_closest(self, rays):

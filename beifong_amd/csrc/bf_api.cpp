@@ -959,6 +959,16 @@ bf_status bf_render_skin_batch(bf_scene *scene, const bf_launch *launch, uint32_
     });
 }
 
+bf_status bf_render_morph_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_morphed,
+                                const uint32_t *shapes, const float *const *weights, const float *const *bones, uint32_t n_shapes,
+                                const float *to_world, float *hist_out, bf_path_record *records_out, bf_stats *stats_out) {
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_morph_batch: n_renders is 0");
+    // the weights and the bone tables are host arrays in both forms: only the histogram and the records differ
+    return render_host_with(scene, launch, n_renders, hist_out, records_out, stats_out, [&](float *h, bf_path_record *r, bf_stats *st) {
+        return bf_render_morph_batch_device(scene, launch, n_renders, seeds, n_morphed, shapes, weights, bones, n_shapes, to_world, h, r, nullptr, st);
+    });
+}
+
 bf_status bf_render(const bf_scene *scene, const bf_launch *launch, float *hist_out, bf_path_record *records_out,
                     bf_stats *stats_out) {
     return render_host(scene, launch, nullptr, hist_out, records_out, stats_out);

@@ -1360,6 +1360,104 @@ extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const floa
 }
 
 BF_NS_BEGIN
+// bf_scene_pose_morph / bf_render_morph_batch_device: morph targets (blend shapes) of one mesh shape, and the skin
+// behind them in the same registers.  One thread per vertex, grid y = version: version v reads its n_targets weights `n_targets`
+// floats further (and its bone table `bone_stride` floats further) and writes its vertices `vstride` floats further.
+//   p = rest;  for k = 0 .. n_targets-1 in increasing k:  p_c = fl(p_c + fl(w_k d_k,c))    per coordinate, no FMA
+//   n likewise from the rest normal and the normal deltas (dnrm == nullptr: the rest normal, bit for bit), not renormalised
+//   SKIN: (p, n) then go through skin_blend in place of the skin's own rest arrays
+// Every target is always evaluated: a zero weight takes no shortcut.  The deltas lie [target][vertex][3], so a wave's loads for one
+// target are contiguous; the weights are indexed by blockIdx.y and the loop counter alone (uniform: scalar loads).  The target loop
+// is unrolled four times to keep four targets' loads in flight; the sums are taken in increasing k all the same.  A lane past the
+// end computes vertex nv - 1 again and stores nothing, so control flow is uniform up to the barrier.
+template <bool SKIN>
+__global__ __launch_bounds__(256) void bf_morph_vertices_kernel(const float *__restrict__ rest_pos, const float *__restrict__ rest_nrm,
+                                                                const float *__restrict__ dpos, const float *__restrict__ dnrm, uint32_t nv,
+                                                                uint32_t n_targets, const float *__restrict__ wts,
+                                                                const uint4 *__restrict__ index, const float4 *__restrict__ weight,
+                                                                const float *__restrict__ bones, uint32_t n_bones, uint32_t bone_stride,
+                                                                float *__restrict__ pos, float *__restrict__ nrm, uint64_t vstride) {
+    __shared__ float sb[SKIN ? 256 * 12 : 1];
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x, ver = blockIdx.y;
+    const bool live = v < nv;
+    const size_t vc = 3u * (size_t) (live ? v : nv - 1u), tstride = 3u * (size_t) nv;
+    uint4 ix = make_uint4(0u, 0u, 0u, 0u);
+    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (SKIN) {
+        ix = index[vc / 3u];
+        w = weight[vc / 3u];
+        const float *b = bones + (size_t) bone_stride * ver;
+        for (uint32_t i = threadIdx.x; i < n_bones * 12u; i += 256u) sb[i] = b[i];
+    }
+    float x[3], n[3] = {0.f, 0.f, 0.f};
+    for (int c = 0; c < 3; ++c) x[c] = rest_pos[vc + c];
+    if (rest_nrm)
+        for (int c = 0; c < 3; ++c) n[c] = rest_nrm[vc + c];
+    const float *wv = wts + (size_t) n_targets * ver;
+    const float *dp = dpos + vc, *dn = rest_nrm && dnrm ? dnrm + vc : nullptr;
+    uint32_t k = 0;
+    for (; k + 4u <= n_targets; k += 4u) {
+        float d[4][3], e[4][3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            for (int c = 0; c < 3; ++c) d[j][c] = dp[(size_t) (k + j) * tstride + c];
+        if (dn) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                for (int c = 0; c < 3; ++c) e[j][c] = dn[(size_t) (k + j) * tstride + c];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float wk = wv[k + j];
+            for (int c = 0; c < 3; ++c) x[c] = __fadd_rn(x[c], __fmul_rn(wk, d[j][c]));
+            if (dn)
+                for (int c = 0; c < 3; ++c) n[c] = __fadd_rn(n[c], __fmul_rn(wk, e[j][c]));
+        }
+    }
+    for (; k < n_targets; ++k) {
+        const float wk = wv[k];
+        for (int c = 0; c < 3; ++c) x[c] = __fadd_rn(x[c], __fmul_rn(wk, dp[(size_t) k * tstride + c]));
+        if (dn)
+            for (int c = 0; c < 3; ++c) n[c] = __fadd_rn(n[c], __fmul_rn(wk, dn[(size_t) k * tstride + c]));
+    }
+    if (SKIN) __syncthreads();
+    if (!live) return;
+    const size_t o = (size_t) vstride * ver + vc;
+    if (SKIN) {
+        const float3 p = skin_blend(sb, ix, w, x[0], x[1], x[2], true);
+        pos[o] = p.x, pos[o + 1] = p.y, pos[o + 2] = p.z;
+        if (rest_nrm) {
+            const float3 r = skin_blend(sb, ix, w, n[0], n[1], n[2], false);
+            nrm[o] = r.x, nrm[o + 1] = r.y, nrm[o + 2] = r.z;
+        }
+    } else {
+        pos[o] = x[0], pos[o + 1] = x[1], pos[o + 2] = x[2];
+        if (rest_nrm) nrm[o] = n[0], nrm[o + 1] = n[1], nrm[o + 2] = n[2];
+    }
+}
+BF_NS_END  // namespace bfd
+
+// n_versions poses of one morphed shape: weights [n_versions][n_targets] (device) -> pos (and nrm, if rest_nrm is given),
+// [n_versions][nv][3] each.  bones != nullptr ([n_versions][n_bones][12], device): skinned behind the morph, with `index` and `weight`
+extern "C" hipError_t bfk_launch_morph_vertices(const float *rest_pos, const float *rest_nrm, const float *dpos, const float *dnrm, uint32_t nv,
+                                                uint32_t n_targets, const float *wts, const uint4 *index, const float4 *weight,
+                                                const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
+                                                hipStream_t stream) {
+    if (nv == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u || n_targets == 0 || n_targets > 256u) return hipErrorInvalidValue;
+    const dim3 grid((nv + 255u) / 256u, n_versions);
+    if (bones) {
+        if (n_bones == 0 || n_bones > 256u || !index || !weight) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(bfd::bf_morph_vertices_kernel<true>, grid, dim3(256), 0, stream, rest_pos, rest_nrm, dpos, dnrm, nv, n_targets, wts, index,
+                           weight, bones, n_bones, n_bones * 12u, pos, nrm, (uint64_t) 3u * nv);
+    } else {
+        hipLaunchKernelGGL(bfd::bf_morph_vertices_kernel<false>, grid, dim3(256), 0, stream, rest_pos, rest_nrm, dpos, dnrm, nv, n_targets, wts, index,
+                           weight, bones, 0u, 0u, pos, nrm, (uint64_t) 3u * nv);
+    }
+    return hipGetLastError();
+}
+
+BF_NS_BEGIN
 // Recomputed vertex normals (BF_NORMALS_RECOMPUTE, bf_vertex_normals): angle-weighted face normals summed per vertex.
 // The arithmetic is stated ONCE, here, for the kernel and for the host entry alike: fp32, every product, sum, difference, quotient
 // and square root rounded (IEEE division and square root), no FMA outside bf_acos.  The device spells the operations __fmul_rn /

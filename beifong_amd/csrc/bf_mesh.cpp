@@ -652,7 +652,8 @@ bf_status check_skinned_shape(const bf_scene *scene, uint32_t shape, const char 
 }
 
 // One bone table ([n_bones][12]) of skin `sk`: every entry finite, and per axis r the bound B[r] >= |posed coordinate r| of every
-// vertex raised to cover it.  Derivation (u = 2^-24, X_c = max |rest coordinate c|, W = the largest float64 sum of a weight row):
+// vertex raised to cover it.  X_c >= |coordinate c| of everything the bones are applied to: the skin's rest extent (skin_extent), or
+// what morph_extent derives for a morph ahead of the skin.  Derivation (u = 2^-24, W = the largest float64 sum of a weight row):
 //   q_k[r] = fl(fl(fl(fl(m_r0 x) + fl(m_r1 y)) + fl(m_r2 z)) + m_r3) of bone b = i_k: each product carries one rounding and the
 //     three sums one each, so |q_k[r]| <= Q_b[r] (1 + u)^4 with Q_b[r] = |m_r0| X_0 + |m_r1| X_1 + |m_r2| X_2 + |m_r3|;
 //   p'[r] = fl(fl(fl(fl(w0 q_0) + fl(w1 q_1)) + fl(w2 q_2)) + fl(w3 q_3)): again one rounding per product and three sums, so
@@ -661,7 +662,7 @@ bf_status check_skinned_shape(const bf_scene *scene, uint32_t shape, const char 
 //   (1 + u)^8 < 1 + 5e-7; results that round into the subnormal range err by at most 2^-150 per operation instead.  The factor
 //   1 + 1e-5 below (origin_bound's margin) covers both, the evaluation of Q in float64 and the rounding of B to float.
 // `who` ends in ':' or ','.
-bf_status skin_bound(const MeshSkin &sk, uint32_t shape, const float *bones, const char *who, double B[3]) {
+bf_status skin_bound(const MeshSkin &sk, const double X[3], uint32_t shape, const float *bones, const char *who, double B[3]) {
     for (uint32_t b = 0; b < sk.n_bones; ++b) {
         const float *m = bones + 12 * (size_t) b;
         for (int j = 0; j < 12; ++j)
@@ -669,20 +670,25 @@ bf_status skin_bound(const MeshSkin &sk, uint32_t shape, const float *bones, con
         if (!sk.bone_used[b]) continue;
         for (int r = 0; r < 3; ++r) {
             double q = std::fabs((double) m[4 * r + 3]);
-            for (int c = 0; c < 3; ++c) q += std::fabs((double) m[4 * r + c]) * (double) sk.rest_abs[c];
+            for (int c = 0; c < 3; ++c) q += std::fabs((double) m[4 * r + c]) * X[c];
             B[r] = std::max(B[r], sk.weight_sum * q * (1.0 + 1e-5) + 1e-37);
         }
     }
     return BF_OK;
 }
+struct SkinExtent {
+    double X[3];
+    explicit SkinExtent(const MeshSkin &sk) : X{(double) sk.rest_abs[0], (double) sk.rest_abs[1], (double) sk.rest_abs[2]} {}
+};
 // ... as the float the gather checks against (and the shape's base box takes); a bound float cannot hold is refused
-bf_status skin_bound_float(const double B[3], uint32_t shape, const char *who, float *bound, float box6[6]) {
+bf_status skin_bound_float(const double B[3], uint32_t shape, const char *who, float *bound, float box6[6],
+                           const char *why = "bones too large for the rest pose") {
     float mx = std::numeric_limits<float>::min();
     for (int r = 0; r < 3; ++r) {
         const bool fits = B[r] < 0.5 * (double) std::numeric_limits<float>::max();
         const float f = fits ? std::nextafter((float) B[r], std::numeric_limits<float>::infinity()) : 0.f;
         if (!fits)
-            return fail(BF_ERR_INVALID, "%s shape %u: the bound on the posed coordinates is not finite (bones too large for the rest pose)", who, shape);
+            return fail(BF_ERR_INVALID, "%s shape %u: the bound on the posed coordinates is not finite (%s)", who, shape, why);
         if (box6) box6[r] = -f, box6[3 + r] = f;
         mx = std::max(mx, f);
     }
@@ -698,6 +704,47 @@ bf_status skin_scratch(bf_scene *scene, size_t bytes, hipStream_t stream, const 
 // floats of one version of a skinned shape in the scratch: positions, then normals if the skin has them and they are wanted
 // (not under BF_NORMALS_RECOMPUTE: the blended normals are then not computed)
 size_t skin_floats(const MeshSkin &sk, bool with_normals) { return (size_t) sk.n_vertices * 3 * (sk.rest_nrm && with_normals ? 2 : 1); }
+
+// ---- morph targets (bf_scene_set_morph, bf_scene_pose_morph, bf_render_morph_batch_device) ----------------------------
+// The checks of a morphed shape common to a pose and a batch: what a vertex update refuses of the shape, a shape without a morph,
+// and (with_bones) a shape without the skin its bones need.
+bf_status check_morphed_shape(const bf_scene *scene, uint32_t shape, bool with_bones, const char *who, const bf_geometry::MeshTopo **tp,
+                              const MeshMorph **morph, const MeshSkin **skin) {
+    const bf_status st = check_deform_shape(scene, shape, false, who, tp);
+    if (st != BF_OK) return st;
+    const MeshState &m = scene->mesh;
+    if (shape >= m.morphs.size() || !m.morphs[shape])
+        return fail(BF_ERR_INVALID, "%s shape %u has no morph (bf_scene_set_morph attaches one)", who, shape);
+    *morph = m.morphs[shape].get();
+    *skin = nullptr;
+    if (!with_bones) return BF_OK;
+    if (shape >= m.skins.size() || !m.skins[shape])
+        return fail(BF_ERR_INVALID, "%s bones for shape %u, which has no skin (bf_scene_set_skin attaches one)", who, shape);
+    *skin = m.skins[shape].get();
+    return BF_OK;
+}
+
+// One pose's weights ([n_targets]) of morph `mo`: every weight finite, and per axis c the extent X[c] >= |morphed coordinate c| of every
+// vertex raised to cover it.  Derivation (u = 2^-24, K = n_targets, R_c = max |rest coordinate c|, D_k,c = max |delta coordinate c| of
+// target k): t_k = fl(w_k d_k) has |t_k| <= |w_k| D_k,c (1 + u), and p_k = fl(p_{k-1} + t_k) has |p_k| <= (|p_{k-1}| + |t_k|)(1 + u), so
+//   |p_K| <= (R_c + sum_k |w_k| D_k,c) (1 + u)^(K + 1),   and (1 + u)^(K + 1) < 1 + 2 (K + 1) u for K <= 256 (1.6e-5 at the most: more
+// than origin_bound's 1e-5, hence a factor of its own).  A result that rounds into the subnormal range errs by at most 2^-150 per
+// operation instead, 2 K of them: below the 1e-37 added.  A zero weight contributes |0| D = 0 however large its target's deltas are,
+// as fl(0 d) = +-0 does on the device.  The sum is taken in float64, whose own rounding the factor 2 covers.  `who` ends in ':' or ','.
+bf_status morph_extent(const MeshMorph &mo, uint32_t shape, const float *weights, const char *who, double X[3]) {
+    double s[3] = {(double) mo.rest_abs[0], (double) mo.rest_abs[1], (double) mo.rest_abs[2]};
+    for (uint32_t k = 0; k < mo.n_targets; ++k) {
+        if (!std::isfinite(weights[k])) return fail(BF_ERR_INVALID, "%s shape %u: the weight of target %u is not finite", who, shape, k);
+        for (int c = 0; c < 3; ++c) s[c] += std::fabs((double) weights[k]) * (double) mo.delta_abs[3 * (size_t) k + c];
+    }
+    for (int c = 0; c < 3; ++c) X[c] = std::max(X[c], s[c] * (1.0 + 2.0 * (mo.n_targets + 1.0) * 0x1p-24) + 1e-37);
+    return BF_OK;
+}
+
+// floats of one version of a morphed shape in the scratch: positions, then normals if the morph has them and they are wanted
+size_t morph_floats(const MeshMorph &mo, bool with_normals) { return (size_t) mo.n_vertices * 3 * (mo.rest_nrm && with_normals ? 2 : 1); }
+// floats of `n_versions` poses' weights in a staged table ([n_versions][n_targets]), padded to 16 bytes so that the bone tables behind stay aligned
+size_t morph_weight_floats(const MeshMorph &mo, uint32_t n_versions) { return ((size_t) n_versions * mo.n_targets + 3) & ~size_t(3); }
 
 }  // namespace
 
@@ -783,6 +830,7 @@ bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
     const MeshState &m = src->mesh;
     sc->mesh.origin_scale_built = m.origin_scale_built;
     sc->mesh.skins = m.skins;      // shared, never written: bf_scene_set_skin on either handle replaces that handle's pointer alone
+    sc->mesh.morphs = m.morphs;    // likewise (bf_scene_set_morph)
     sc->mesh.normal_mode = m.normal_mode;      // the source's modes at this moment; the clone's own from now on
     if (!m.tris0 && !m.geom_private) return BF_OK;
     // `src` has moved: the clone snapshots what src renders now as ITS geometry "as created"; uvs (and normals no transform moved) stay shared
@@ -1292,7 +1340,7 @@ bf_status bf_scene_pose_skin(bf_scene *scene, uint32_t shape, const float *bones
     if (st != BF_OK) return st;
     double B[3] = {0.0, 0.0, 0.0};
     float bound = 0.f, box[6];
-    if ((st = skin_bound(*sk, shape, bones, fn, B)) != BF_OK || (st = skin_bound_float(B, shape, fn, &bound, box)) != BF_OK) return st;
+    if ((st = skin_bound(*sk, SkinExtent(*sk).X, shape, bones, fn, B)) != BF_OK || (st = skin_bound_float(B, shape, fn, &bound, box)) != BF_OK) return st;
     if (scene->d.n_tris == 0 || sk->n_vertices == 0) return BF_OK;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
@@ -1342,7 +1390,7 @@ bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, 
         for (uint32_t k = 0; k < n_renders; ++k) {
             char who[96];
             std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
-            if ((cst = skin_bound(*skins[j], shapes[j], bones[j] + (size_t) k * skins[j]->n_bones * 12, who, B)) != BF_OK) return cst;
+            if ((cst = skin_bound(*skins[j], SkinExtent(*skins[j]).X, shapes[j], bones[j] + (size_t) k * skins[j]->n_bones * 12, who, B)) != BF_OK) return cst;
         }
         version_floats += skin_floats(*skins[j], !scene->mesh.recomputes(shapes[j]));
         version_bones += (size_t) skins[j]->n_bones * 12;
@@ -1390,6 +1438,215 @@ bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, 
             hs[shapes[j]].nrm = nrm;
             db += (size_t) kc * sk.n_bones * 12;
             out += (size_t) kc * skin_floats(sk, rest_nrm != nullptr);
+        }
+        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernels
+        return BF_OK;
+    });
+}
+
+// ---- morph targets: a pose is n_targets weights (and, for a shape that also carries a skin, its bones);
+// bf_morph_vertices_kernel computes the vertices into the handle's posed-vertex scratch, and from there on everything is a skin pose's ----
+bf_status bf_scene_set_morph(bf_scene *scene, uint32_t shape, uint32_t n_targets, const float *rest_positions, const float *rest_normals,
+                             const float *delta_positions, const float *delta_normals) {
+    const char *fn = "bf_scene_set_morph:";
+    if (!scene) return fail(BF_ERR_INVALID, "%s null scene", fn);
+    const bf_geometry::MeshTopo *tp = nullptr;
+    bf_status st = check_deform_shape(scene, shape, n_targets && rest_normals, fn, &tp);
+    if (st != BF_OK) return st;
+    if (n_targets == 0) {
+        BF_ENTER(scene);
+        if (shape < scene->mesh.morphs.size()) scene->mesh.morphs[shape].reset();
+        return BF_OK;
+    }
+    if (n_targets > 256u) return fail(BF_ERR_INVALID, "%s shape %u: %u targets (at most 256 per shape)", fn, shape, n_targets);
+    if (!rest_positions || !delta_positions) return fail(BF_ERR_INVALID, "%s shape %u: null array", fn, shape);
+    if (tp->has_normals && !rest_normals)
+        return fail(BF_ERR_INVALID, "%s shape %u was created with vertex normals: its morph needs rest normals", fn, shape);
+    if (delta_normals && !rest_normals) return fail(BF_ERR_INVALID, "%s shape %u: normal deltas without rest normals", fn, shape);
+    const uint32_t nv = tp->n_vertices;
+    auto morph = std::make_shared<MeshMorph>();
+    morph->n_targets = n_targets;
+    morph->n_vertices = nv;
+    morph->delta_abs.assign((size_t) 3 * n_targets, 0.f);
+    for (uint32_t v = 0; v < nv; ++v)
+        for (int c = 0; c < 3; ++c) {
+            const float x = rest_positions[3 * (size_t) v + c];
+            if (!std::isfinite(x) || (rest_normals && !std::isfinite(rest_normals[3 * (size_t) v + c])))
+                return fail(BF_ERR_INVALID, "%s shape %u: non-finite rest value at vertex %u", fn, shape, v);
+            morph->rest_abs[c] = std::max(morph->rest_abs[c], std::fabs(x));
+        }
+    for (uint32_t k = 0; k < n_targets; ++k)
+        for (uint32_t v = 0; v < nv; ++v)
+            for (int c = 0; c < 3; ++c) {
+                const size_t i = 3 * ((size_t) k * nv + v) + c;
+                if (!std::isfinite(delta_positions[i]) || (delta_normals && !std::isfinite(delta_normals[i])))
+                    return fail(BF_ERR_INVALID, "%s shape %u: non-finite delta of target %u at vertex %u", fn, shape, k, v);
+                morph->delta_abs[3 * (size_t) k + c] = std::max(morph->delta_abs[3 * (size_t) k + c], std::fabs(delta_positions[i]));
+            }
+    BF_ENTER(scene);
+    if (nv) {
+        // one block: rest positions, rest normals, position deltas, normal deltas
+        const size_t vec = (size_t) nv * 12, del = vec * n_targets;
+        const size_t bytes = vec * (rest_normals ? 2 : 1) + del * (delta_normals ? 2 : 1);
+        const hipError_t he = hipMalloc(&morph->block, bytes);
+        if (he != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(BF_ERR_NOMEM, "%s shape %u: hipMalloc(%zu bytes): %s", fn, shape, bytes, hipGetErrorString(he));
+        }
+        char *blk = (char *) morph->block;
+        size_t at = 0;
+        auto put = [&](const float *src, size_t n) -> const float * {
+            if (!src) return nullptr;
+            char *dst = blk + at;
+            at += n;
+            return hipMemcpy(dst, src, n, hipMemcpyHostToDevice) == hipSuccess ? (const float *) dst : nullptr;
+        };
+        morph->rest_pos = put(rest_positions, vec);
+        morph->rest_nrm = put(rest_normals, vec);
+        morph->dpos = put(delta_positions, del);
+        morph->dnrm = put(delta_normals, del);
+        if (!morph->rest_pos || !morph->dpos || (rest_normals && !morph->rest_nrm) || (delta_normals && !morph->dnrm))
+            return fail(BF_ERR_DEVICE, "%s shape %u: hipMemcpy of %zu bytes: %s", fn, shape, bytes, hipGetErrorString(hipGetLastError()));
+    }
+    MeshState &m = scene->mesh;
+    if (m.morphs.size() < scene->info.n_shapes) m.morphs.resize(scene->info.n_shapes);
+    m.morphs[shape] = std::move(morph);      // (the morph it replaces goes with its last handle; hipFree waits for the kernels that read it)
+    return BF_OK;
+}
+
+bf_status bf_scene_pose_morph(bf_scene *scene, uint32_t shape, const float *weights, const float *bones, void *stream_) {
+    const char *fn = "bf_scene_pose_morph:";
+    if (!scene || !weights) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    const bf_geometry::MeshTopo *tp = nullptr;
+    const MeshMorph *mo = nullptr;
+    const MeshSkin *sk = nullptr;
+    bf_status st = check_morphed_shape(scene, shape, bones != nullptr, fn, &tp, &mo, &sk);
+    if (st != BF_OK) return st;
+    // the morph's extent is the bound, or what the skin bound takes in place of the skin's rest extent
+    double X[3] = {0.0, 0.0, 0.0}, B[3] = {0.0, 0.0, 0.0};
+    float bound = 0.f, box[6];
+    if ((st = morph_extent(*mo, shape, weights, fn, X)) != BF_OK) return st;
+    if (sk && (st = skin_bound(*sk, X, shape, bones, fn, B)) != BF_OK) return st;
+    if ((st = skin_bound_float(sk ? B : X, shape, fn, &bound, box, "weights or bones too large for the targets")) != BF_OK) return st;
+    if (scene->d.n_tris == 0 || mo->n_vertices == 0) return BF_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    MeshState &m = scene->mesh;
+    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    const float *rest_nrm = m.recomputes(shape) ? nullptr : mo->rest_nrm;      // BF_NORMALS_RECOMPUTE: update_vertices_locked computes them
+    if ((st = skin_scratch(scene, morph_floats(*mo, rest_nrm != nullptr) * sizeof(float), stream, fn)) != BF_OK) return st;
+    const size_t wf = morph_weight_floats(*mo, 1u), bytes = (wf + (sk ? (size_t) sk->n_bones * 12 : 0)) * sizeof(float);
+    bf_scene::Stage *stg = nullptr;
+    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
+    std::memset(stg->host, 0, wf * sizeof(float));
+    std::memcpy(stg->host, weights, (size_t) mo->n_targets * sizeof(float));
+    if (sk) std::memcpy((float *) stg->host + wf, bones, (size_t) sk->n_bones * 12 * sizeof(float));
+    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
+    float *pos = m.skin_vtx, *nrm = rest_nrm ? m.skin_vtx + 3 * (size_t) mo->n_vertices : nullptr;
+    HIP_TRY(bfk_launch_morph_vertices(mo->rest_pos, rest_nrm, mo->dpos, mo->dnrm, mo->n_vertices, mo->n_targets, (const float *) stg->dev,
+                                      sk ? sk->index : nullptr, sk ? sk->weight : nullptr, sk ? (const float *) stg->dev + wf : nullptr,
+                                      sk ? sk->n_bones : 0u, pos, nrm, 1u, stream));
+    HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernel
+    if ((st = update_vertices_locked(scene, shape, *tp, pos, nrm, bound, box, true, stream)) != BF_OK) return st;
+    return mark_last(scene, stream);
+}
+
+bf_status bf_render_morph_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_morphed,
+                                       const uint32_t *shapes, const float *const *weights, const float *const *bones, uint32_t n_shapes,
+                                       const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
+    const char *fn = "bf_render_morph_batch_device:";
+    if (!scene || !launch || !hist_dev || (n_morphed && (!shapes || !weights))) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
+    if (to_world && n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
+    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a morph batch is one launch sequence of its own", fn);
+    if (launch->spp && launch->film_width && launch->film_height)
+        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
+    n_shapes = scene->info.n_shapes;
+    // the gather's table: a morphed shape's entry is marked here and pointed at the chunk's posed vertices below
+    std::vector<bfd::DDeformSrc> src(n_shapes);
+    std::memset(src.data(), 0, src.size() * sizeof(bfd::DDeformSrc));
+    std::vector<const MeshMorph *> morphs(n_morphed, nullptr);
+    std::vector<const MeshSkin *> skins(n_morphed, nullptr);      // null: morphed only
+    size_t version_floats = 0;      // posed vertices of all morphed shapes, per render
+    double B[3] = {0.0, 0.0, 0.0};
+    for (uint32_t j = 0; j < n_morphed; ++j) {
+        const bf_geometry::MeshTopo *tp = nullptr;
+        const float *bj = bones ? bones[j] : nullptr;
+        bf_status cst = check_morphed_shape(scene, shapes[j], bj != nullptr, fn, &tp, &morphs[j], &skins[j]);
+        if (cst != BF_OK) return cst;
+        if (!weights[j]) return fail(BF_ERR_INVALID, "%s shape %u: null weights", fn, shapes[j]);
+        if (src[shapes[j]].pos) return fail(BF_ERR_INVALID, "%s shape %u is listed twice", fn, shapes[j]);
+        src[shapes[j]].pos = (const float *) (uintptr_t) 16;      // (marks the shape; never read)
+        src[shapes[j]].nv = tp->n_vertices;
+        for (uint32_t k = 0; k < n_renders; ++k) {
+            char who[96];
+            std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
+            double X[3] = {0.0, 0.0, 0.0};
+            if ((cst = morph_extent(*morphs[j], shapes[j], weights[j] + (size_t) k * morphs[j]->n_targets, who, X)) != BF_OK) return cst;
+            if (skins[j]) {
+                if ((cst = skin_bound(*skins[j], X, shapes[j], bj + (size_t) k * skins[j]->n_bones * 12, who, B)) != BF_OK) return cst;
+            } else {
+                for (int c = 0; c < 3; ++c) B[c] = std::max(B[c], X[c]);
+            }
+        }
+        version_floats += morph_floats(*morphs[j], !scene->mesh.recomputes(shapes[j]));
+    }
+    float bound = std::numeric_limits<float>::min();
+    bf_status st = n_morphed ? skin_bound_float(B, shapes[0], fn, &bound, nullptr, "weights or bones too large for the targets") : BF_OK;
+    if (st != BF_OK) return st;
+    std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
+    if (to_world && (st = check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data())) != BF_OK) return st;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
+    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
+    if (scene->d.n_tris == 0) {
+        bf_batch b = {n_renders, seeds, nullptr};
+        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
+    }
+    MeshState &m = scene->mesh;
+    return deform_versions(scene, launch, n_renders, seeds, src, bound, to_world, moves, hist_dev, records_dev, stream_, stats_out,
+                           "bf_render_morph_batch_device", [&](uint32_t k0, uint32_t kc, bfd::DDeformSrc *hs) -> bf_status {
+        // the chunk's tables (per shape [kc][n_targets] weights, padded to 16 bytes, then [kc][n_bones][12] bones if it is skinned; one shape
+        // after the other) and, from them, its posed vertices in the scratch (per shape [kc][nv][3] positions, then its normals)
+        bf_status pst = skin_scratch(scene, (size_t) kc * version_floats * sizeof(float), stream, fn);
+        if (pst != BF_OK || !n_morphed) return pst;
+        size_t floats = 0;
+        for (uint32_t j = 0; j < n_morphed; ++j)
+            floats += morph_weight_floats(*morphs[j], kc) + (skins[j] ? (size_t) kc * skins[j]->n_bones * 12 : 0);
+        const size_t bytes = floats * sizeof(float);
+        bf_scene::Stage *stg = nullptr;
+        if ((pst = stage_acquire(scene, bytes, &stg)) != BF_OK) return pst;
+        float *hb = (float *) stg->host;
+        std::memset(hb, 0, bytes);
+        for (uint32_t j = 0; j < n_morphed; ++j) {
+            const uint32_t nt = morphs[j]->n_targets;
+            std::memcpy(hb, weights[j] + (size_t) k0 * nt, (size_t) kc * nt * sizeof(float));
+            hb += morph_weight_floats(*morphs[j], kc);
+            if (skins[j]) {
+                const size_t n = (size_t) kc * skins[j]->n_bones * 12;
+                std::memcpy(hb, bones[j] + (size_t) k0 * skins[j]->n_bones * 12, n * sizeof(float));
+                hb += n;
+            }
+        }
+        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
+        const float *db = (const float *) stg->dev;
+        float *out = m.skin_vtx;
+        for (uint32_t j = 0; j < n_morphed; ++j) {
+            const MeshMorph &mo = *morphs[j];
+            const MeshSkin *sk = skins[j];
+            const size_t n = (size_t) kc * mo.n_vertices * 3;
+            // (BF_NORMALS_RECOMPUTE: no morphed or blended normals; deform_versions computes the posed surface's behind this)
+            const float *rest_nrm = m.recomputes(shapes[j]) ? nullptr : mo.rest_nrm;
+            float *pos = out, *nrm = rest_nrm ? out + n : nullptr;
+            const float *dw = db, *dbones = sk ? db + morph_weight_floats(mo, kc) : nullptr;
+            HIP_TRY(bfk_launch_morph_vertices(mo.rest_pos, rest_nrm, mo.dpos, mo.dnrm, mo.n_vertices, mo.n_targets, dw, sk ? sk->index : nullptr,
+                                              sk ? sk->weight : nullptr, dbones, sk ? sk->n_bones : 0u, pos, nrm, kc, stream));
+            hs[shapes[j]].pos = pos;
+            hs[shapes[j]].nrm = nrm;
+            db += morph_weight_floats(mo, kc) + (sk ? (size_t) kc * sk->n_bones * 12 : 0);
+            out += (size_t) kc * morph_floats(mo, rest_nrm != nullptr);
         }
         HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernels
         return BF_OK;

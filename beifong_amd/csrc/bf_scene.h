@@ -33,6 +33,10 @@ extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const 
 extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const float *rest_nrm, const uint4 *index, const float4 *weight, uint32_t nv,
                                                const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
                                                hipStream_t stream);
+extern "C" hipError_t bfk_launch_morph_vertices(const float *rest_pos, const float *rest_nrm, const float *dpos, const float *dnrm, uint32_t nv,
+                                                uint32_t n_targets, const float *wts, const uint4 *index, const float4 *weight,
+                                                const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
+                                                hipStream_t stream);
 extern "C" hipError_t bfk_launch_vertex_normals(const uint32_t *offset, const uint4 *entries, uint32_t nv, const float *pos, float *nrm,
                                                 uint32_t n_versions, hipStream_t stream);
 extern "C" void bfk_host_vertex_normals(uint32_t nv, const float *pos, uint32_t nf, const uint32_t *idx, float *out);
@@ -122,6 +126,23 @@ struct __attribute__((visibility("hidden"))) MeshSkin {
     }
 };
 
+// The morph targets of one mesh shape (bf_scene_set_morph): rest pose and dense per-target deltas in ONE device block,
+// never written after it is made; held and shared as MeshSkin is, through MeshState::morphs.
+struct __attribute__((visibility("hidden"))) MeshMorph {
+    uint32_t n_targets = 0, n_vertices = 0;
+    void *block = nullptr;                // device: what the four pointers below point into
+    const float *rest_pos = nullptr;      // [n_vertices][3]
+    const float *rest_nrm = nullptr;      // [n_vertices][3], or null: the mesh has no vertex normals
+    const float *dpos = nullptr;          // [n_targets][n_vertices][3]
+    const float *dnrm = nullptr;          // [n_targets][n_vertices][3], or null: the rest normals are copied
+    // what the bound on the morphed coordinates is derived from (bf_mesh.cpp: morph_extent)
+    float rest_abs[3] = {0.f, 0.f, 0.f};  // max |rest coordinate| per axis
+    std::vector<float> delta_abs;         // [n_targets][3]: max |delta coordinate| per target and axis
+    ~MeshMorph() {
+        if (block) (void) hipFree(block);
+    }
+};
+
 // "The meshes of this handle have moved" (DESIGN.md 6d): the state bf_mesh.cpp keeps per handle, each flag's meaning stated here alone.
 // Every moving call is ABSOLUTE: from the BASE rows (as created, until a vertex update rewrites them) to the rows bf_scene::d renders.
 struct __attribute__((visibility("hidden"))) MeshState {
@@ -169,6 +190,7 @@ struct __attribute__((visibility("hidden"))) MeshState {
     // where bf_skin_vertices_kernel writes the posed vertices (and normals) of a pose or of a batch chunk, for the gather to read;
     // the handle's own, grown on demand, never shrunk
     std::vector<std::shared_ptr<const MeshSkin>> skins;
+    std::vector<std::shared_ptr<const MeshMorph>> morphs;      // bf_scene_set_morph: the same rules; bf_morph_vertices_kernel writes skin_vtx too
     float *skin_vtx = nullptr;
     size_t skin_vtx_cap = 0;                     // bytes
     // normal modes (bf_scene_set_normal_mode): BF_NORMALS_* per shape, empty until the first call (every shape BF_NORMALS_GIVEN);

@@ -260,6 +260,30 @@ def jointed_bar(n_bones, n_around=8, n_along=6, radius=0.15, blend=0.25):
     return v.astype(f32), np.asarray(faces, np.uint32), index, weight
 
 
+def bar_swell_targets(positions, n_bones, n_targets, amplitude=0.1, reach=0.75):
+    """Dense morph targets (bf_scene_set_morph) for jointed_bar's vertices, as jointed_bar returns them (the bar along x from 0 to
+    n_bones): target k swells the bar radially around station x_k = (k + 0.5) n_bones / n_targets.  A vertex at axial distance
+    a = |x - x_k| below h = reach * spacing (spacing = n_bones / n_targets) moves outwards along its radius by
+    amplitude (1 - (a / h)^2)^2; every other vertex, and the two cap centres on the axis, have an exactly zero delta.  With
+    0.5 < reach < 1 each target is non-zero on a strict subset of the vertices and neighbouring targets overlap (vertices between
+    two stations are moved by both), but a vertex is never moved by three.  Deterministic: no random numbers.
+    Returns float32[n_targets, nv, 3]."""
+    n_bones, n_targets = int(n_bones), int(n_targets)
+    if n_bones < 1 or n_targets < 1 or not 0.5 < reach < 1.0:
+        raise ValueError("bar_swell_targets: n_bones >= 1, n_targets >= 1, 0.5 < reach < 1")
+    v = np.asarray(positions, np.float64).reshape(-1, 3)
+    radial = v * [0.0, 1.0, 1.0]
+    r = np.linalg.norm(radial, axis=1)
+    unit = np.where(r[:, None] > 0.0, radial / np.maximum(r, 1e-300)[:, None], 0.0)
+    spacing = n_bones / n_targets
+    h = reach * spacing
+    out = np.zeros((n_targets, v.shape[0], 3))
+    for k in range(n_targets):
+        a = np.abs(v[:, 0] - (k + 0.5) * spacing)
+        out[k] = unit * (amplitude * np.where(a < h, (1.0 - (a / h) ** 2) ** 2, 0.0))[:, None]
+    return out.astype(f32)
+
+
 def vertex_normals(verts, faces):
     """Angle-weighted vertex normals (Thuermer & Wuethrich) — what Mesh::recompute_vertex_normals
     (mesh.cpp:201-249) gives an OBJ / PLY file that carries none, e.g. a raw 3-D scan."""

@@ -121,6 +121,37 @@ def vertex_normals_f32(positions, faces):
     return capi.vertex_normals(positions, faces)
 
 
+def apply_morph(rest, rest_normals, delta_positions, delta_normals, weights):
+    """Rest positions (and rest normals, or None) of a mesh moved by morph targets as the device moves them (bf_scene_pose_morph):
+    delta_positions float32[n_targets, nv, 3], delta_normals the same shape or None, weights float32[n_targets].
+
+        p = rest;  for k in increasing order:  p = fl(p + fl(w_k d_k))        per coordinate, every product and sum rounded
+        n likewise from the rest normal and the normal deltas, not renormalised
+
+    Every target is always evaluated (a zero weight takes no shortcut, so a -0.0 may come out as +0.0).  With no normal deltas
+    the rest normals are returned as they are, bit for bit.  Returns (positions', normals'); the composition with a skin is
+    apply_skin(*apply_morph(...), index, weight, bones)."""
+    p = np.ascontiguousarray(rest, dtype=f32).reshape(-1, 3).copy()
+    n = None if rest_normals is None else np.ascontiguousarray(rest_normals, dtype=f32).reshape(-1, 3).copy()
+    w = np.ascontiguousarray(weights, dtype=f32).reshape(-1)
+    dp = np.ascontiguousarray(delta_positions, dtype=f32).reshape(w.shape[0], -1, 3)
+    if dp.shape[1] != p.shape[0]:
+        raise ValueError(f"{p.shape[0]} vertices, deltas for {dp.shape[1]}")
+    dn = None
+    if delta_normals is not None:
+        if n is None:
+            raise ValueError("normal deltas without rest normals")
+        dn = np.ascontiguousarray(delta_normals, dtype=f32).reshape(w.shape[0], -1, 3)
+        if dn.shape != dp.shape:
+            raise ValueError(f"delta_normals {dn.shape}, delta_positions {dp.shape}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in range(w.shape[0]):                  # float32 on float32: each product and each sum is rounded once
+            p = p + w[k] * dp[k]
+            if dn is not None:
+                n = n + w[k] * dn[k]
+    return p, n
+
+
 def moved_description(sd, transforms):
     """A new SceneDesc equal to `sd` with every mesh's positions and normals replaced by apply_rigid(..., transforms[k]):
     the scene bf_scene_create would have to rebuild for the pose bf_scene_transform_meshes gives a handle of `sd`.

@@ -436,6 +436,114 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
             h.close()
 
 
+def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None,
+                       classes=None, recompute_normals=(), lib=None, device=None):
+    """Coherent pulse sweep in which meshes are moved by MORPH TARGETS (blend shapes), a few weights per pulse: the
+    counterpart of render_skin_sweep for surfaces that bones describe badly, a breathing chest wall or a panel vibrating in a
+    few modes.  A mesh may be skinned behind its morph.
+
+    `morphs`      {shape: delta_positions float32[n_targets, n_vertices, 3]} or {shape: (delta_positions, delta_normals)}: the
+                  targets of every morphed mesh; its rest shape is the mesh as `sd` describes it (positions, and vertex
+                  normals if it has any);
+    `weights`     {shape: float32[n_pulses, n_targets]}: the weights of every pulse (motion.apply_morph's arithmetic);
+    `skins`       None, or {shape: (index, weight)} as in render_skin_sweep for some of the morphed meshes, with
+    `bones`       {shape: float32[n_pulses, n_bones, 3, 4]} for exactly those;
+    `transforms`  None, or float[n_pulses, n_shapes, 3, 4] as in render_motion_sweep, applied on top.
+
+    The scene is built once and the morphs and skins attached before it is cloned; the pulses are split into `n_streams`
+    contiguous groups, one per handle and stream, each ONE morph batch (bf_render_morph_batch_device).  per_pulse=True is the
+    reference path: the pulses rotate over the handles, one bf_scene_pose_morph (+ one bf_scene_transform_meshes) and one
+    render per pulse; per-path results are the same.  rebuild_every, classes and recompute_normals as in render_skin_sweep.
+    Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3]
+    with classes."""
+    import torch
+    if rebuild_every is not None and int(rebuild_every) < 1:
+        raise ValueError("rebuild_every must be a positive integer or None")
+    every = None if rebuild_every is None else int(rebuild_every)
+    n, shapes, tabs = capi.morph_tables(weights)
+    morphs = {int(k): (v if isinstance(v, tuple) else (v, None)) for k, v in morphs.items()}
+    if set(morphs) != set(int(k) for k in shapes):
+        raise ValueError(f"morphs for shapes {sorted(morphs)}, weights for shapes {sorted(int(k) for k in shapes)}")
+    skins = {int(k): v for k, v in (skins or {}).items()}
+    btabs = {}
+    if skins or bones:
+        nb, bshapes, bt = capi.skin_tables(bones or {})
+        btabs = {int(k): t for k, t in zip(bshapes, bt)}
+        if set(skins) != set(btabs) or not set(skins) <= set(morphs) or nb != n:
+            raise ValueError(f"skins for shapes {sorted(skins)}, bones for shapes {sorted(btabs)} over {nb} pulses, morphs for shapes "
+                             f"{sorted(morphs)} over {n}")
+    for k in shapes:
+        if not 0 <= int(k) < len(sd.shapes) or sd.shapes[int(k)].type != capi.BF_SHAPE_MESH:
+            raise ValueError(f"shape {int(k)} is not a mesh of this scene")
+    xf = None
+    if transforms is not None:
+        xf = np.asarray(transforms, dtype=np.float32)
+        if xf.ndim != 4 or xf.shape[2:] != (3, 4) or xf.shape[0] != n:
+            raise ValueError(f"transforms must be [{n}, n_shapes, 3, 4], got {xf.shape}")
+    lib = lib or capi.load_library()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    n_streams = max(1, min(int(n_streams), n))
+    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
+    first = capi.Scene(sd, lib)
+    handles = [first]
+    try:
+        for sh, tab in zip(shapes, tabs):
+            s = sd.shapes[int(sh)]
+            rest = np.ctypeslib.as_array(s.positions, shape=(s.n_vertices, 3))
+            rest_n = np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None
+            dp, dn = morphs[int(sh)]
+            first.set_morph(int(sh), tab.shape[1], rest, dp, rest_normals=rest_n, delta_normals=dn)
+            if int(sh) in skins:
+                index, weight = skins[int(sh)]
+                first.set_skin(int(sh), btabs[int(sh)].shape[1], rest, index, weight, rest_normals=rest_n)
+        launch, n_classes = _classed(first, launch, classes)
+        _recompute(first, recompute_normals)
+        handles += [first.clone() for _ in range(n_streams - 1)]
+        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
+        for s in streams:           # the cube was zero-filled on the current stream
+            s.wait_stream(torch.cuda.current_stream(dev))
+        updates = [0] * n_streams
+
+        def pose(h, k, stream):
+            for sh, tab in zip(shapes, tabs):
+                b = btabs.get(int(sh))
+                h.pose_morph(int(sh), tab[k], bones=None if b is None else b[k], stream=stream)
+
+        if per_pulse:
+            for k in range(n):
+                j = k % n_streams
+                with torch.cuda.stream(streams[j]):
+                    pose(handles[j], k, streams[j].cuda_stream)
+                    if xf is not None:
+                        handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
+                    updates[j] += 1
+                    if every and updates[j] % every == 0:
+                        handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
+                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
+        else:
+            bounds = np.linspace(0, n, n_streams + 1).astype(int)
+            for j in range(n_streams):
+                lo, hi = int(bounds[j]), int(bounds[j + 1])
+                for c0 in range(lo, hi, every or max(1, hi - lo)):
+                    c1 = min(hi, c0 + every) if every else hi
+                    with torch.cuda.stream(streams[j]):
+                        if every and c0 > lo:
+                            # the k-th frame since the last rebuild has just been rendered: the trees follow the meshes to it
+                            pose(handles[j], c0 - 1, streams[j].cuda_stream)
+                            handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
+                        handles[j].render_morph_batch_device(launch, {int(sh): tab[c0:c1] for sh, tab in zip(shapes, tabs)}, cube[c0].data_ptr(),
+                                                             bones={k: t[c0:c1] for k, t in btabs.items()} or None,
+                                                             transforms=None if xf is None else xf[c0:c1], stream=streams[j].cuda_stream)
+        for s in streams:
+            s.synchronize()
+        for h in handles:
+            h.sync()                # a posed vertex beyond the bound the library derived (there is none) would be reported here
+        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
+    finally:
+        for h in reversed(handles):
+            h.close()
+
+
 def range_doppler(cube, window=True):
     """Slow-time FFT of a pulse-sweep cube: complex64[n_doppler, cells], zero Doppler at row 0 (numpy.fft order)."""
     z = cube[:, :, 0].astype(np.complex64) + 1j * cube[:, :, 1].astype(np.complex64)

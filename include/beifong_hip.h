@@ -933,6 +933,61 @@ bf_status bf_render_skin_batch(bf_scene *scene, const bf_launch *launch, uint32_
                                const uint32_t *shapes, const float *const *bones, uint32_t n_shapes, const float *to_world, float *hist_out,
                                bf_path_record *records_out, bf_stats *stats_out);
 
+/* Morph targets (blend shapes): the moved vertices are a rest shape plus a weighted sum of per-vertex displacement fields,
+ * evaluated on the device AHEAD of the skin, as glTF-style pipelines order the two.  A morph is attached to a mesh shape once
+ * (rest positions, rest normals for a mesh with vertex normals, n_targets <= 256 dense position deltas [n_targets][n_vertices][3]
+ * and optionally normal deltas of the same shape); after that a pose is n_targets weights, any finite floats (negative weights
+ * and weights above 1 are legal).  DESIGN.md 6d.
+ *   Arithmetic, fp32, every product and sum rounded (no FMA).  For a vertex with rest position r and deltas d_k:
+ *       p = r;  for k = 0 .. n_targets-1 in increasing k:  p_c = fl(p_c + fl(w_k d_k,c))                  per coordinate
+ *       n likewise from the rest normal and the normal deltas, not renormalised
+ *     Every target is always evaluated: a zero weight takes no shortcut, so a -0.0 may come out as +0.0.  With no normal deltas
+ *     n is the rest normal copied bit for bit.  If the call also gives bones, the shape must carry a skin (bf_scene_set_skin) and
+ *     the result is the skin's arithmetic (above) applied to (p, n) in place of the skin's own rest arrays: its indices and
+ *     weights are used, its rest arrays are not read.  Under BF_NORMALS_RECOMPUTE (bf_scene_set_normal_mode) neither morph
+ *     normals nor skin normals are computed: the shape gets bf_vertex_normals of the final positions, as after a skin pose.
+ *     beifong_amd.motion.apply_morph is the numpy statement; the composition is apply_skin(*apply_morph(...), index, weight, bones).
+ *   bf_scene_set_morph: host arrays, deep-copied into one immutable device block.  One morph per shape; a second call replaces
+ *     this handle's, n_targets == 0 removes it (the arrays are then not read).  rest_normals: given exactly if the mesh was created
+ *     with vertex normals; delta_normals: NULL, or given together with rest_normals.  Clones taken afterwards share the block; a
+ *     later call on either handle changes that handle alone.  The mesh itself does not move.  bf_scene_rebuild_bvh keeps morphs.
+ *   bf_scene_pose_morph: bf_scene_pose_skin's semantics word for word: the mesh's BASE becomes the computed vertices, whatever it
+ *     held before; the handle's pose goes on top; an open rolling sequence is finished first; ordering and copy on write are
+ *     unchanged.  bones: NULL, or the host bone table of the shape's skin.  After the call every path and every bf_ray_intersect /
+ *     bf_trace_* result is bit-identical to a bf_scene_create of the description with the shape carrying the numpy statement's
+ *     arrays, followed by the same transform call.  weights and bones are free again when the call returns.
+ *   bf_render_morph_batch(_device): bf_render_skin_batch with weights[j] = host [n_renders][n_targets(shapes[j])] and bones
+ *     either NULL (no shape is skinned) or [n_morphed] host pointers, entry j NULL (shape j is morphed only) or
+ *     [n_renders][n_bones(shapes[j])][12].  Render k is bit-identical to bf_scene_pose_morph(slice k) +
+ *     bf_scene_transform_meshes(to_world[k]) + a stand-alone render with seeds[k] on a second handle.  Arena, chunking
+ *     (BF_MOTION_BATCH_MB) and launch flags as a skin batch; the handle's base, pose and clones do not change.
+ *   Scratch: the posed vertices go to the skin's posed-vertex buffer, under its sizing rules, OUTSIDE BF_MOTION_BATCH_MB.
+ *   Bound: derived on the host, per axis max |rest| + sum_k |w_k| max |d_k| with the roundings accounted for; with bones it is
+ *     fed through the skin bound in place of the skin's rest extent.  A zero weight keeps its target out of the bound however
+ *     large its deltas.  A bound float cannot hold is refused; the gather's check stays as the safety net.
+ *   Validation, before anything is enqueued (a failed call leaves the scene as it was; the text names shape, vertex, target or bone):
+ *     BF_ERR_INVALID      a shape index out of range or not a mesh; NULL arrays; n_targets > 256; a non-finite rest, delta,
+ *                         weight or bone value; rest normals for a mesh without vertex normals, or none for a mesh with them;
+ *                         normal deltas without rest normals; posing a shape that has no morph; bones for a shape that has no
+ *                         skin; a shape listed twice; and what a skin batch refuses (n_renders == 0, BF_FLAG_ROLLING, a
+ *                         multi-pixel film, a bad to_world)
+ *     BF_ERR_UNSUPPORTED  a mesh that carries an emitter / transmitter
+ *     BF_ERR_NOMEM        the device block cannot be allocated */
+bf_status bf_scene_set_morph(bf_scene *scene, uint32_t shape, uint32_t n_targets, const float *rest_positions /* host [n_vertices][3] */,
+                             const float *rest_normals /* host [n_vertices][3] or NULL */,
+                             const float *delta_positions /* host [n_targets][n_vertices][3] */,
+                             const float *delta_normals /* host [n_targets][n_vertices][3] or NULL */);
+bf_status bf_scene_pose_morph(bf_scene *scene, uint32_t shape, const float *weights /* host [n_targets] */,
+                              const float *bones /* host [n_bones][12] or NULL */, void *stream);
+bf_status bf_render_morph_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds,
+                                       uint32_t n_morphed, const uint32_t *shapes, const float *const *weights /* [n_morphed] host pointers */,
+                                       const float *const *bones /* NULL, or [n_morphed] host pointers (entries may be NULL) */,
+                                       uint32_t n_shapes, const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream,
+                                       bf_stats *stats_out);
+bf_status bf_render_morph_batch(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_morphed,
+                                const uint32_t *shapes, const float *const *weights, const float *const *bones, uint32_t n_shapes,
+                                const float *to_world, float *hist_out, bf_path_record *records_out, bf_stats *stats_out);
+
 /* Recomputed vertex normals: angle-weighted face normals, computed on the device wherever a mesh's base positions are
  * replaced, so that a smooth-shaded mesh that deforms or is skinned needs no normal array per frame.  DESIGN.md 6d.
  *   Arithmetic, fp32, every product, sum, difference, quotient and square root rounded (IEEE division and square root), no
