@@ -622,33 +622,43 @@ def vertex_array(a, name, n_vertices=None, n_renders=None):
     return np.ascontiguousarray(a)
 
 
-def deform_tables(positions, normals=None, n_vertices=None):
-    """What bf_render_deform_batch reads, from {shape: positions[K, nv, 3]} (and {shape: normals[K, nv, 3]} for some or all
-    of them): (n_renders, uint32 shapes, [positions arrays], [normals arrays or None] or None).  `positions` may also be a
-    list of (shape, array) pairs; a shape listed twice is refused here.  n_vertices: {shape: count} to check against."""
-    items = list(positions.items()) if isinstance(positions, dict) else [(k, v) for k, v in positions]
+def _keyed_tables(items, noun, kind, layout, rank_ok, check_one):
+    """The check deform_tables, skin_tables and morph_tables share: `items` ({shape: array[K, ...]} or a list of (shape, array) pairs)
+    -> (n_renders, uint32 shapes, [check_one(array, name, shape, n_renders)]).  noun ("positions"), kind ("deforming") and layout
+    ("[n_renders, n_vertices, 3]") word the refusals; rank_ok(ndim) says whether the first array can be a batch at all."""
+    items = list(items.items()) if isinstance(items, dict) else [(k, v) for k, v in items]
     if not items:
-        raise ValueError("positions: no deforming shape")
+        raise ValueError(f"{noun}: no {kind} shape")
     shapes = [int(k) for k, _ in items]
     if len(set(shapes)) != len(shapes):
         raise ValueError(f"a shape is listed twice: {shapes}")
     if any(k < 0 for k in shapes):
         raise ValueError(f"negative shape index in {shapes}")
     first = np.asarray(items[0][1])
-    if first.ndim != 3:
-        raise ValueError(f"positions of shape {shapes[0]} must be [n_renders, n_vertices, 3], got {first.shape}")
+    if not rank_ok(first.ndim):
+        raise ValueError(f"{noun} of shape {shapes[0]} must be {layout}, got {first.shape}")
     n_renders = first.shape[0]
     if n_renders == 0:
-        raise ValueError("positions: no renders")
+        raise ValueError(f"{noun}: no renders")
+    tabs = [check_one(v, f"{noun} of shape {k}", k, n_renders) for k, (_, v) in zip(shapes, items)]
+    return n_renders, np.asarray(shapes, np.uint32), tabs
+
+
+def deform_tables(positions, normals=None, n_vertices=None):
+    """What bf_render_deform_batch reads, from {shape: positions[K, nv, 3]} (and {shape: normals[K, nv, 3]} for some or all
+    of them): (n_renders, uint32 shapes, [positions arrays], [normals arrays or None] or None).  `positions` may also be a
+    list of (shape, array) pairs; a shape listed twice is refused here.  n_vertices: {shape: count} to check against."""
     nv = n_vertices or {}
-    pos = [vertex_array(v, f"positions of shape {k}", nv.get(k), n_renders) for k, v in zip(shapes, (v for _, v in items))]
+    n_renders, shape_arr, pos = _keyed_tables(positions, "positions", "deforming", "[n_renders, n_vertices, 3]", lambda d: d == 3,
+                                              lambda v, name, k, n: vertex_array(v, name, nv.get(k), n))
+    shapes = shape_arr.tolist()
     nrm = None
     if normals is not None:
         for k in normals:
             if int(k) not in shapes:
                 raise ValueError(f"normals for shape {k}, which has no positions in this call")
         nrm = [vertex_array(normals[k], f"normals of shape {k}", p.shape[1], n_renders) if k in normals else None for k, p in zip(shapes, pos)]
-    return n_renders, np.asarray(shapes, np.uint32), pos, nrm
+    return n_renders, shape_arr, pos, nrm
 
 
 def bone_array(a, name, n_bones=None, n_renders=None):
@@ -672,22 +682,9 @@ def bone_array(a, name, n_bones=None, n_renders=None):
 def skin_tables(bones, n_bones=None):
     """What bf_render_skin_batch reads, from {shape: bones[K, n_bones, 3, 4]} or a list of (shape, array) pairs:
     (n_renders, uint32 shapes, [bone arrays]).  A shape listed twice is refused here.  n_bones: {shape: count} to check against."""
-    items = list(bones.items()) if isinstance(bones, dict) else [(k, v) for k, v in bones]
-    if not items:
-        raise ValueError("bones: no skinned shape")
-    shapes = [int(k) for k, _ in items]
-    if len(set(shapes)) != len(shapes):
-        raise ValueError(f"a shape is listed twice: {shapes}")
-    if any(k < 0 for k in shapes):
-        raise ValueError(f"negative shape index in {shapes}")
-    first = np.asarray(items[0][1])
-    if first.ndim < 3:
-        raise ValueError(f"bones of shape {shapes[0]} must be [n_renders, n_bones, 3, 4], got {first.shape}")
-    n_renders = first.shape[0]
-    if n_renders == 0:
-        raise ValueError("bones: no renders")
     nb = n_bones or {}
-    return n_renders, np.asarray(shapes, np.uint32), [bone_array(v, f"bones of shape {k}", nb.get(k), n_renders) for k, v in items]
+    return _keyed_tables(bones, "bones", "skinned", "[n_renders, n_bones, 3, 4]", lambda d: d >= 3,
+                         lambda v, name, k, n: bone_array(v, name, nb.get(k), n))
 
 
 def weight_array(a, name, n_targets=None, n_renders=None):
@@ -709,22 +706,9 @@ def weight_array(a, name, n_targets=None, n_renders=None):
 def morph_tables(weights, n_targets=None):
     """What bf_render_morph_batch reads, from {shape: weights[K, n_targets]} or a list of (shape, array) pairs:
     (n_renders, uint32 shapes, [weight arrays]).  A shape listed twice is refused here.  n_targets: {shape: count} to check against."""
-    items = list(weights.items()) if isinstance(weights, dict) else [(k, v) for k, v in weights]
-    if not items:
-        raise ValueError("weights: no morphed shape")
-    shapes = [int(k) for k, _ in items]
-    if len(set(shapes)) != len(shapes):
-        raise ValueError(f"a shape is listed twice: {shapes}")
-    if any(k < 0 for k in shapes):
-        raise ValueError(f"negative shape index in {shapes}")
-    first = np.asarray(items[0][1])
-    if first.ndim != 2:
-        raise ValueError(f"weights of shape {shapes[0]} must be [n_renders, n_targets], got {first.shape}")
-    n_renders = first.shape[0]
-    if n_renders == 0:
-        raise ValueError("weights: no renders")
     nt = n_targets or {}
-    return n_renders, np.asarray(shapes, np.uint32), [weight_array(v, f"weights of shape {k}", nt.get(k), n_renders) for k, v in items]
+    return _keyed_tables(weights, "weights", "morphed", "[n_renders, n_targets]", lambda d: d == 2,
+                         lambda v, name, k, n: weight_array(v, name, nt.get(k), n))
 
 
 class Scene:
@@ -994,27 +978,40 @@ class Scene:
                                                         C.byref(st) if st is not None else None), "bf_render_batch_device")
         return st
 
+    # The batches with a geometry version per render (motion, deform, skin, morph) end alike: the host form returns hist / rec / stats
+    # of its own, the device form takes the caller's buffers; either way the library's arguments are (handle, launch, n_renders,
+    # seeds, the call's own tables, n_shapes, transforms, the outputs).
+    def _host_outputs(self, launch, n_renders, records):
+        """(hist, rec, bf_stats) of a host-form batch, and the outputs of its call."""
+        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
+        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
+        st = bf_stats()
+        return (hist, rec, st), (_ptr(hist), _ptr(rec), C.byref(st))
+
+    @staticmethod
+    def _device_outputs(hist_ptr, records_ptr, stream, want_stats):
+        """bf_stats (or None) of a device-form batch, and the outputs of its call."""
+        st = bf_stats() if want_stats else None
+        return st, (C.c_void_p(hist_ptr), C.c_void_p(records_ptr) if records_ptr else None, _stream(stream), C.byref(st) if st is not None else None)
+
+    def _version_batch(self, name, launch, n_renders, sa, tables, xf, outputs):
+        check(self.lib, getattr(self.lib, name)(self.handle, C.byref(launch), n_renders, _ptr(sa), *tables, xf.shape[1] if xf is not None else 0,
+                                                _ptr(xf), *outputs), name)
+
     def render_motion_batch(self, launch, transforms, seeds=None, records=False):
         """bf_render_motion_batch: render k moves every mesh shape s to transforms[k, s] (absolute from the geometry as
         created; the handle's own pose is untouched) -> float32[n_renders, channels] (+ records [n_renders, n_paths], stats).
         `transforms`: [n_renders, n_shapes, 3, 4]; `seeds`: one per render, or None for launch.seed everywhere."""
         xf, sa = motion_tables(transforms, self.info().n_shapes, seeds)
-        n_renders = xf.shape[0]
-        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
-        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
-        st = bf_stats()
-        check(self.lib, self.lib.bf_render_motion_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), xf.shape[1], _ptr(xf),
-                                                        _ptr(hist), _ptr(rec), C.byref(st)), "bf_render_motion_batch")
-        return hist, rec, st
+        ret, out = self._host_outputs(launch, xf.shape[0], records)
+        self._version_batch("bf_render_motion_batch", launch, xf.shape[0], sa, (), xf, out)
+        return ret
 
     def render_motion_batch_device(self, launch, transforms, hist_ptr, seeds=None, stream=0, records_ptr=None, want_stats=False):
         """bf_render_motion_batch_device: accumulate render k of the motion batch into hist_ptr[k * channels ..] (device)."""
         xf, sa = motion_tables(transforms, self.info().n_shapes, seeds)
-        st = bf_stats() if want_stats else None
-        check(self.lib, self.lib.bf_render_motion_batch_device(self.handle, C.byref(launch), xf.shape[0], _ptr(sa), xf.shape[1], _ptr(xf),
-                                                               C.c_void_p(hist_ptr), C.c_void_p(records_ptr) if records_ptr else None,
-                                                               C.c_void_p(stream) if stream else None,
-                                                               C.byref(st) if st is not None else None), "bf_render_motion_batch_device")
+        st, out = self._device_outputs(hist_ptr, records_ptr, stream, want_stats)
+        self._version_batch("bf_render_motion_batch_device", launch, xf.shape[0], sa, (), xf, out)
         return st
 
     def mesh_vertex_count(self, shape):
@@ -1059,7 +1056,8 @@ class Scene:
         check(self.lib, self.lib.bf_scene_get_normal_mode(self.handle, shape, C.byref(mode)), "bf_scene_get_normal_mode")
         return int(mode.value)
 
-    def _deform_args(self, n_renders, transforms, seeds):
+    def _version_args(self, n_renders, transforms, seeds):
+        """The optional transforms and seeds of a deform, skin or morph batch of n_renders, checked against that count."""
         xf = sa = None
         if transforms is not None:
             xf, sa = motion_tables(transforms, self.info().n_shapes, seeds)
@@ -1076,16 +1074,12 @@ class Scene:
         some or all of them), then every mesh at transforms[k] (None: none) -> float32[K, channels] (+ records, stats)."""
         nv = {int(k): self.mesh_vertex_count(k) for k in (positions.keys() if isinstance(positions, dict) else [k for k, _ in positions])}
         n_renders, shapes, pos, nrm = deform_tables(positions, normals, {k: v for k, v in nv.items() if v is not None})
-        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        xf, sa = self._version_args(n_renders, transforms, seeds)
         pp = (C.c_void_p * len(pos))(*[p.ctypes.data for p in pos])
         np_ = (C.c_void_p * len(pos))(*[(q.ctypes.data if q is not None else None) for q in nrm]) if nrm is not None else None
-        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
-        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
-        st = bf_stats()
-        check(self.lib, self.lib.bf_render_deform_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), len(pos), _ptr(shapes), pp, np_,
-                                                        xf.shape[1] if xf is not None else 0, _ptr(xf), _ptr(hist), _ptr(rec), C.byref(st)),
-              "bf_render_deform_batch")
-        return hist, rec, st
+        ret, out = self._host_outputs(launch, n_renders, records)
+        self._version_batch("bf_render_deform_batch", launch, n_renders, sa, (len(pos), _ptr(shapes), pp, np_), xf, out)
+        return ret
 
     def render_deform_batch_device(self, launch, n_renders, positions_ptrs, hist_ptr, bound, normals_ptrs=None, transforms=None, seeds=None,
                                    stream=0, records_ptr=None, want_stats=False):
@@ -1095,18 +1089,14 @@ class Scene:
         if len(set(shapes)) != len(shapes):
             raise ValueError(f"a shape is listed twice: {shapes}")
         n_renders = int(n_renders)
-        xf, sa = self._deform_args(n_renders, transforms, seeds)
+        xf, sa = self._version_args(n_renders, transforms, seeds)
         sh = np.asarray(shapes, np.uint32)
         pp = (C.c_void_p * len(shapes))(*[int(positions_ptrs[k]) for k in positions_ptrs])
         np_ = None
         if normals_ptrs:
             np_ = (C.c_void_p * len(shapes))(*[(int(normals_ptrs[k]) if normals_ptrs.get(k) else None) for k in positions_ptrs])
-        st = bf_stats() if want_stats else None
-        check(self.lib, self.lib.bf_render_deform_batch_device(self.handle, C.byref(launch), n_renders, _ptr(sa), len(shapes), _ptr(sh), pp, np_,
-                                                               float(bound), xf.shape[1] if xf is not None else 0, _ptr(xf), C.c_void_p(hist_ptr),
-                                                               C.c_void_p(records_ptr) if records_ptr else None,
-                                                               C.c_void_p(stream) if stream else None,
-                                                               C.byref(st) if st is not None else None), "bf_render_deform_batch_device")
+        st, out = self._device_outputs(hist_ptr, records_ptr, stream, want_stats)
+        self._version_batch("bf_render_deform_batch_device", launch, n_renders, sa, (len(shapes), _ptr(sh), pp, np_, float(bound)), xf, out)
         return st
 
     def set_skin(self, shape, n_bones, rest_positions=None, index=None, weight=None, rest_normals=None):
@@ -1153,25 +1143,18 @@ class Scene:
         """bf_render_skin_batch: render k sees skinned shape s posed by bones[s][k] ([K, n_bones, 3, 4] float32 each), then every
         mesh at transforms[k] (None: none) -> float32[K, channels] (+ records, stats).  The handle itself does not change."""
         n_renders, shapes, tabs, bp = self._skin_args(bones)
-        xf, sa = self._deform_args(n_renders, transforms, seeds)
-        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
-        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
-        st = bf_stats()
-        check(self.lib, self.lib.bf_render_skin_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), len(tabs), _ptr(shapes), bp,
-                                                      xf.shape[1] if xf is not None else 0, _ptr(xf), _ptr(hist), _ptr(rec), C.byref(st)),
-              "bf_render_skin_batch")
-        return hist, rec, st
+        xf, sa = self._version_args(n_renders, transforms, seeds)
+        ret, out = self._host_outputs(launch, n_renders, records)
+        self._version_batch("bf_render_skin_batch", launch, n_renders, sa, (len(tabs), _ptr(shapes), bp), xf, out)
+        return ret
 
     def render_skin_batch_device(self, launch, bones, hist_ptr, transforms=None, seeds=None, stream=0, records_ptr=None, want_stats=False):
         """bf_render_skin_batch_device: the same (the bone tables stay host arrays) with render k accumulated into
         hist_ptr[k * channels ..] (device)."""
         n_renders, shapes, tabs, bp = self._skin_args(bones)
-        xf, sa = self._deform_args(n_renders, transforms, seeds)
-        st = bf_stats() if want_stats else None
-        check(self.lib, self.lib.bf_render_skin_batch_device(self.handle, C.byref(launch), n_renders, _ptr(sa), len(tabs), _ptr(shapes), bp,
-                                                             xf.shape[1] if xf is not None else 0, _ptr(xf), C.c_void_p(hist_ptr),
-                                                             C.c_void_p(records_ptr) if records_ptr else None, _stream(stream),
-                                                             C.byref(st) if st is not None else None), "bf_render_skin_batch_device")
+        xf, sa = self._version_args(n_renders, transforms, seeds)
+        st, out = self._device_outputs(hist_ptr, records_ptr, stream, want_stats)
+        self._version_batch("bf_render_skin_batch_device", launch, n_renders, sa, (len(tabs), _ptr(shapes), bp), xf, out)
         return st
 
     def set_morph(self, shape, n_targets, rest_positions=None, delta_positions=None, rest_normals=None, delta_normals=None):
@@ -1225,26 +1208,19 @@ class Scene:
         `bones` lists ({shape: [K, n_bones, 3, 4]}), skinned behind that; then every mesh at transforms[k] (None: none)
         -> float32[K, channels] (+ records, stats).  The handle itself does not change."""
         n_renders, shapes, keep, wp, bp = self._morph_args(weights, bones)
-        xf, sa = self._deform_args(n_renders, transforms, seeds)
-        hist = np.zeros((n_renders, self.channels(launch)), dtype=np.float32)
-        rec = np.zeros((n_renders, launch.n_paths), dtype=PATH_RECORD_DTYPE) if records else None
-        st = bf_stats()
-        check(self.lib, self.lib.bf_render_morph_batch(self.handle, C.byref(launch), n_renders, _ptr(sa), len(shapes), _ptr(shapes), wp, bp,
-                                                       xf.shape[1] if xf is not None else 0, _ptr(xf), _ptr(hist), _ptr(rec), C.byref(st)),
-              "bf_render_morph_batch")
-        return hist, rec, st
+        xf, sa = self._version_args(n_renders, transforms, seeds)
+        ret, out = self._host_outputs(launch, n_renders, records)
+        self._version_batch("bf_render_morph_batch", launch, n_renders, sa, (len(shapes), _ptr(shapes), wp, bp), xf, out)
+        return ret
 
     def render_morph_batch_device(self, launch, weights, hist_ptr, bones=None, transforms=None, seeds=None, stream=0, records_ptr=None,
                                   want_stats=False):
         """bf_render_morph_batch_device: the same (weights and bone tables stay host arrays) with render k accumulated into
         hist_ptr[k * channels ..] (device)."""
         n_renders, shapes, keep, wp, bp = self._morph_args(weights, bones)
-        xf, sa = self._deform_args(n_renders, transforms, seeds)
-        st = bf_stats() if want_stats else None
-        check(self.lib, self.lib.bf_render_morph_batch_device(self.handle, C.byref(launch), n_renders, _ptr(sa), len(shapes), _ptr(shapes), wp, bp,
-                                                              xf.shape[1] if xf is not None else 0, _ptr(xf), C.c_void_p(hist_ptr),
-                                                              C.c_void_p(records_ptr) if records_ptr else None, _stream(stream),
-                                                              C.byref(st) if st is not None else None), "bf_render_morph_batch_device")
+        xf, sa = self._version_args(n_renders, transforms, seeds)
+        st, out = self._device_outputs(hist_ptr, records_ptr, stream, want_stats)
+        self._version_batch("bf_render_morph_batch_device", launch, n_renders, sa, (len(shapes), _ptr(shapes), wp, bp), xf, out)
         return st
 
     def trace_closest(self, rays):

@@ -1,5 +1,6 @@
 // "The meshes of this handle have moved" (DESIGN.md 6d): translations, rigid transforms, vertex updates, the rebuild of both trees
 // and the batches with a geometry version per render.  State: bf_scene::mesh (bf_scene.h); kernels: bf_kernels.hip, bf_build.hip.
+// Skins and morph targets, which end in a vertex update or a deform batch of this file: bf_pose.cpp.
 #include "bf_scene.h"
 
 #include <algorithm>
@@ -34,12 +35,6 @@ struct DevAlloc {
         return BF_OK;
     }
 };
-
-// the prologue of every call that moves meshes: behind the handle's previous work, with its open rolling sequence ended
-bf_status mesh_enter(const bf_scene *scene, hipStream_t stream) {
-    const bf_status st = order_after_last(scene, stream);
-    return st == BF_OK ? close_sequence(scene, stream) : st;
-}
 
 // n entries of a [..][12] transform table as the 16-float records bfk_launch_rigid reads: word 12 = the shape moves, 13..15 = 0
 void pack_rigid(float *out, const float *to_world, const uint8_t *moves, size_t n) {
@@ -274,16 +269,6 @@ bf_status check_rigid_table(const bf_scene *scene, uint32_t n_shapes, const floa
     }
     return BF_OK;
 }
-// ... of every render of a batch (to_world: [n_renders][n_shapes][12]); `fn` ends in ':'
-bf_status check_rigid_tables(const bf_scene *scene, const char *fn, uint32_t n_renders, uint32_t n_shapes, const float *to_world, uint8_t *moves) {
-    for (uint32_t k = 0; k < n_renders; ++k) {
-        char who[96];
-        std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
-        const bf_status st = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves + (size_t) n_shapes * k);
-        if (st != BF_OK) return st;
-    }
-    return BF_OK;
-}
 
 // The pose table (pose_kind / pose_xf) over the base rows into the arrays the handle renders; a translation leaves the base normals as they are.
 bf_status run_pose(bf_scene *scene, hipStream_t stream) {
@@ -364,27 +349,6 @@ bf_status deform_watch(bf_scene *scene, hipStream_t stream) {
     return BF_OK;
 }
 
-// A scratch buffer of the handle's own (posed vertices, recomputed normals), at least `bytes`: grown on demand, never shrunk (the
-// gathers that read the old one are behind `stream` or before it: mesh_enter).  `what` names its content in the error text.
-bf_status vertex_scratch(float *&buf, size_t &cap, size_t bytes, hipStream_t stream, const char *who, const char *what) {
-    if (cap >= bytes) return BF_OK;
-    if (buf) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipFree(buf));
-        buf = nullptr;
-        cap = 0;
-    }
-    void *q = nullptr;
-    const hipError_t he = hipMalloc(&q, bytes);
-    if (he != hipSuccess) {
-        (void) hipGetLastError();
-        return fail(BF_ERR_NOMEM, "%s hipMalloc(%zu bytes) for the %s: %s", who, bytes, what, hipGetErrorString(he));
-    }
-    buf = (float *) q;
-    cap = bytes;
-    return BF_OK;
-}
-
 // ---- recomputed normals (bf_scene_set_normal_mode) ---------------------------------------------------------------------
 // The inverted index of shape `shape` (bf_scene.h: NormalIndex), built from the indices the scene was created with at the first use
 // by any handle that shares the geometry: per vertex its incident corners, faces in increasing order — the order of the sum.
@@ -424,65 +388,6 @@ bf_status normal_index(bf_scene *scene, uint32_t shape, const char *who, const b
     }
     *out = g.normal_index[shape].get();
     return BF_OK;
-}
-
-// one update with the arrays on the device already; box6: the new base box of the shape
-bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geometry::MeshTopo &tp, const float *pos_dev, const float *nrm_dev,
-                                 float bound, const float *box6, bool watch, hipStream_t stream) {
-    const char *who = "bf_scene_update_vertices";
-    MeshState &m = scene->mesh;
-    bf_status st = BF_OK;
-    if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
-    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
-    // BF_NORMALS_RECOMPUTE and no normals in the call: the statement of the new positions into the handle's scratch, gathered below
-    // as if the caller had given them (and watched like a device form: finite positions may have cross products that are not)
-    const bool recompute = !nrm_dev && scene->d.normals && m.recomputes(shape);
-    const bf_geometry::NormalIndex *nidx = nullptr;
-    if (recompute) {
-        if ((st = normal_index(scene, shape, who, &nidx)) != BF_OK) return st;
-        if ((st = vertex_scratch(m.nrm_vtx, m.nrm_vtx_cap, (size_t) tp.n_vertices * 3 * sizeof(float), stream, who, "recomputed normals")) != BF_OK) return st;
-    }
-    if ((st = own_geometry(scene, stream, who)) != BF_OK) return st;
-    if (recompute) {
-        HIP_TRY(bfk_launch_vertex_normals(nidx->offset, nidx->entries, tp.n_vertices, pos_dev, m.nrm_vtx, 1u, stream));
-        nrm_dev = m.nrm_vtx;
-        watch = true;
-    }
-    const MeshState::Bytes B = MeshState::bytes(scene->d);
-    DevAlloc take{scene->owned, who};
-    if (!m.base_private) {
-        // the base rows are still the arrays shared with clones: this handle's own copy from now on
-        float4 *q = nullptr;
-        if ((st = take(B.tris, &q)) != BF_OK) return st;
-        HIP_TRY(hipMemcpyAsync(q, m.tris0, B.tris, hipMemcpyDeviceToDevice, stream));
-        m.tris0 = q;
-        m.base_private = true;
-    }
-    if ((st = m.own_normals(scene->d, scene->owned, who)) != BF_OK) return st;
-    if (nrm_dev && !m.normals0_private) {
-        float4 *q = nullptr;
-        if ((st = take(B.normals, &q)) != BF_OK) return st;
-        HIP_TRY(hipMemcpyAsync(q, m.normals0, B.normals, hipMemcpyDeviceToDevice, stream));
-        m.normals0 = q;
-        m.normals0_private = true;
-    }
-    // the per-shape source table: this shape alone deforms
-    const size_t bytes = (size_t) scene->info.n_shapes * sizeof(bfd::DDeformSrc);
-    bf_scene::Stage *stg = nullptr;
-    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
-    std::memset(stg->host, 0, bytes);
-    bfd::DDeformSrc &e = ((bfd::DDeformSrc *) stg->host)[shape];
-    e.pos = pos_dev;
-    e.nrm = nrm_dev;
-    e.nv = tp.n_vertices;
-    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
-    HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, m.tris0, m.tris0, nrm_dev ? m.normals0 : nullptr,
-                                   nrm_dev ? m.normals0 : nullptr, scene->d.n_tris, nullptr, 1u, 0u, 0u, bound, m.bad, stream));
-    HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel, not only by the copy
-    if (watch && (st = deform_watch(scene, stream)) != BF_OK) return st;
-    std::memcpy(&m.refit.mesh_box[6 * (size_t) shape], box6, 6 * sizeof(float));
-    m.deformed = true;
-    return apply_pose(scene, stream);
 }
 
 // while a chunk renders, the handle's kernel arguments point at version 0 of the arena; restored on every return path
@@ -560,14 +465,220 @@ bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
     return BF_OK;
 }
 
-// What deform and skin batches share behind their checks: version k = the shapes of `src` (pos != nullptr; one entry per shape of the
+}  // namespace
+
+bf_status MeshState::own_normals(bfd::DScene &d, std::vector<void *> &owned, const char *who) {
+    if (!d.normals || normals_private) return BF_OK;
+    float4 *q = nullptr;
+    const bf_status st = DevAlloc{owned, who}(bytes(d).normals, &q);
+    if (st != BF_OK) return st;
+    if (!normals0) normals0 = const_cast<float4 *>(d.normals);
+    d.normals = q;
+    normals_private = true;
+    return BF_OK;
+}
+
+void MeshState::reset_after_rebuild(float4 *tris0_, float4 *nodes0_, float4 *wnodes0_, float4 *normals0_) {
+    const bool posed = tris0_ != nullptr;
+    tris0 = tris0_, nodes0 = nodes0_, wnodes0 = wnodes0_, normals0 = normals0_;
+    // the handle's own arrays throughout; the boxes kept beside a pose are the POSED geometry's: only their topology is read from now on
+    geom_private = base_private = posed;
+    normals_private = normals0_private = normals0_ != nullptr;
+    if (posed) deformed = true;
+    // the level lists follow the topology: rebuilt at the next refit (mesh boxes and transform table stay); the arena's layout has changed
+    refit.ready = false;
+    refit.lvl4 = refit.lvl16 = nullptr;
+    refit.ubox4 = refit.ubox16 = nullptr;
+    refit.off4.clear();
+    refit.off16.clear();
+    batch_versions = 0;
+}
+
+MeshState::~MeshState() {
+    if (arena) (void) hipFree(arena);
+    if (bad) (void) hipFree(bad);
+    if (bad_host) (void) hipHostFree(bad_host);
+    if (bad_ev) (void) hipEventDestroy(bad_ev);
+    if (vtx_ev) {
+        (void) hipEventSynchronize(vtx_ev);
+        (void) hipEventDestroy(vtx_ev);
+    }
+    if (vtx_host) (void) hipHostFree(vtx_host);
+    if (vtx_dev) (void) hipFree(vtx_dev);
+    if (pose_vtx) (void) hipFree(pose_vtx);
+    if (nrm_vtx) (void) hipFree(nrm_vtx);
+}
+
+extern "C" {
+
+bf_status deform_report(const bf_scene *scene, bool wait) {
+    const MeshState &m = scene->mesh;
+    if (!m.bad_pending) return BF_OK;
+    if (wait) {
+        HIP_TRY(hipEventSynchronize(m.bad_ev));
+    } else if (hipEventQuery(m.bad_ev) != hipSuccess) {
+        (void) hipGetLastError();
+        return BF_OK;
+    }
+    m.bad_pending = false;
+    // the device counter only ever grows (nothing clears it under a gather in flight): what is new since the last report
+    const uint32_t total = m.bad_host[0], shape1 = m.bad_host[1];
+    const uint32_t n = total - m.bad_reported;
+    m.bad_reported = total;
+    if (!n) return BF_OK;
+    return fail(BF_ERR_DEVICE, "a device-form vertex update of this scene gave %u triangles (of shape %u, if not of others too) a corner "
+                               "that is not finite or lies beyond the declared bound: those triangles kept their previous vertices, "
+                               "and every render issued since that update is invalid", n, shape1 ? shape1 - 1u : 0u);
+}
+
+bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who, const bf_geometry::MeshTopo **topo_out) {
+    if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", who, shape, scene->info.n_shapes);
+    const bfd::DShape &sh = scene->ends.shapes_host[shape];
+    if (sh.type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", who, shape);
+    if (sh.emitter >= 0)
+        return fail(BF_ERR_UNSUPPORTED, "%s mesh shape %u carries emitter %d (its sampling tables are built from the triangles as "
+                                        "created); create a new scene", who, shape, sh.emitter);
+    const bf_geometry::MeshTopo &tp = scene->geom->topo[shape];
+    if (with_normals && !tp.has_normals)
+        return fail(BF_ERR_INVALID, "%s shape %u was created without vertex normals: it cannot take any", who, shape);
+    *topo_out = &tp;
+    return BF_OK;
+}
+
+bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
+    const MeshState &m = src->mesh;
+    sc->mesh.origin_scale_built = m.origin_scale_built;
+    sc->mesh.skins = m.skins;      // shared, never written: bf_scene_set_skin on either handle replaces that handle's pointer alone
+    sc->mesh.morphs = m.morphs;    // likewise (bf_scene_set_morph)
+    sc->mesh.normal_mode = m.normal_mode;      // the source's modes at this moment; the clone's own from now on
+    if (!m.tris0 && !m.geom_private) return BF_OK;
+    // `src` has moved: the clone snapshots what src renders now as ITS geometry "as created"; uvs (and normals no transform moved) stay shared
+    const MeshState::Bytes B = MeshState::bytes(src->d);
+    DevAlloc take{sc->owned, "bf_scene_clone"};
+    auto dup = [&](const float4 *from, size_t bytes, const float4 **to) -> bf_status {
+        float4 *p = nullptr;
+        const bf_status st = take(from ? bytes : 0, &p);
+        if (p) HIP_TRY(hipMemcpy(p, from, bytes, hipMemcpyDeviceToDevice));
+        *to = p;
+        return st;
+    };
+    bf_status st = BF_OK;
+    if ((st = dup(src->d.tris, B.tris, &sc->d.tris)) != BF_OK) return st;
+    if ((st = dup(src->d.nodes, B.nodes, &sc->d.nodes)) != BF_OK) return st;
+    if ((st = dup(src->d.wnodes, B.wnodes, &sc->d.wnodes)) != BF_OK) return st;
+    if (src->d.qnodes && (st = dup(src->d.qnodes, B.nodes / 2, &sc->d.qnodes)) != BF_OK) return st;
+    // normals a rigid transform moved are part of the snapshot (never written: the clone's first transform moves them into another array)
+    if (m.normals_private && (st = dup(src->d.normals, B.normals, &sc->d.normals)) != BF_OK) return st;
+    sc->mesh.geom_private = true;
+    sc->geom_token = std::make_shared<char>(0);      // the snapshot is the clone's alone: `src` keeps translating in place
+    return BF_OK;
+}
+
+// ---- what bf_pose.cpp calls too (bf_scene.h) ----------------------------------------------------------------------------------------
+// the prologue of every call that moves meshes: behind the handle's previous work, with its open rolling sequence ended
+bf_status mesh_enter(const bf_scene *scene, hipStream_t stream) {
+    const bf_status st = order_after_last(scene, stream);
+    return st == BF_OK ? close_sequence(scene, stream) : st;
+}
+
+// check_rigid_table of every render of a batch (to_world: [n_renders][n_shapes][12]); `fn` ends in ':'
+bf_status check_rigid_tables(const bf_scene *scene, const char *fn, uint32_t n_renders, uint32_t n_shapes, const float *to_world, uint8_t *moves) {
+    for (uint32_t k = 0; k < n_renders; ++k) {
+        char who[96];
+        std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
+        const bf_status st = check_rigid_table(scene, n_shapes, to_world + (size_t) 12 * n_shapes * k, who, moves + (size_t) n_shapes * k);
+        if (st != BF_OK) return st;
+    }
+    return BF_OK;
+}
+
+// A scratch buffer of the handle's own (posed vertices, recomputed normals), at least `bytes`: grown on demand, never shrunk (the
+// gathers that read the old one are behind `stream` or before it: mesh_enter).  `what` names its content in the error text.
+bf_status vertex_scratch(float *&buf, size_t &cap, size_t bytes, hipStream_t stream, const char *who, const char *what) {
+    if (cap >= bytes) return BF_OK;
+    if (buf) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipFree(buf));
+        buf = nullptr;
+        cap = 0;
+    }
+    void *q = nullptr;
+    const hipError_t he = hipMalloc(&q, bytes);
+    if (he != hipSuccess) {
+        (void) hipGetLastError();
+        return fail(BF_ERR_NOMEM, "%s hipMalloc(%zu bytes) for the %s: %s", who, bytes, what, hipGetErrorString(he));
+    }
+    buf = (float *) q;
+    cap = bytes;
+    return BF_OK;
+}
+
+// one update with the arrays on the device already; box6: the new base box of the shape
+bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geometry::MeshTopo &tp, const float *pos_dev, const float *nrm_dev,
+                                 float bound, const float *box6, bool watch, hipStream_t stream) {
+    const char *who = "bf_scene_update_vertices";
+    MeshState &m = scene->mesh;
+    bf_status st = BF_OK;
+    if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
+    if ((st = deform_prepare(scene, stream)) != BF_OK) return st;
+    // BF_NORMALS_RECOMPUTE and no normals in the call: the statement of the new positions into the handle's scratch, gathered below
+    // as if the caller had given them (and watched like a device form: finite positions may have cross products that are not)
+    const bool recompute = !nrm_dev && scene->d.normals && m.recomputes(shape);
+    const bf_geometry::NormalIndex *nidx = nullptr;
+    if (recompute) {
+        if ((st = normal_index(scene, shape, who, &nidx)) != BF_OK) return st;
+        if ((st = vertex_scratch(m.nrm_vtx, m.nrm_vtx_cap, (size_t) tp.n_vertices * 3 * sizeof(float), stream, who, "recomputed normals")) != BF_OK) return st;
+    }
+    if ((st = own_geometry(scene, stream, who)) != BF_OK) return st;
+    if (recompute) {
+        HIP_TRY(bfk_launch_vertex_normals(nidx->offset, nidx->entries, tp.n_vertices, pos_dev, m.nrm_vtx, 1u, stream));
+        nrm_dev = m.nrm_vtx;
+        watch = true;
+    }
+    const MeshState::Bytes B = MeshState::bytes(scene->d);
+    DevAlloc take{scene->owned, who};
+    if (!m.base_private) {
+        // the base rows are still the arrays shared with clones: this handle's own copy from now on
+        float4 *q = nullptr;
+        if ((st = take(B.tris, &q)) != BF_OK) return st;
+        HIP_TRY(hipMemcpyAsync(q, m.tris0, B.tris, hipMemcpyDeviceToDevice, stream));
+        m.tris0 = q;
+        m.base_private = true;
+    }
+    if ((st = m.own_normals(scene->d, scene->owned, who)) != BF_OK) return st;
+    if (nrm_dev && !m.normals0_private) {
+        float4 *q = nullptr;
+        if ((st = take(B.normals, &q)) != BF_OK) return st;
+        HIP_TRY(hipMemcpyAsync(q, m.normals0, B.normals, hipMemcpyDeviceToDevice, stream));
+        m.normals0 = q;
+        m.normals0_private = true;
+    }
+    // the per-shape source table: this shape alone deforms
+    const size_t bytes = (size_t) scene->info.n_shapes * sizeof(bfd::DDeformSrc);
+    bf_scene::Stage *stg = nullptr;
+    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
+    std::memset(stg->host, 0, bytes);
+    bfd::DDeformSrc &e = ((bfd::DDeformSrc *) stg->host)[shape];
+    e.pos = pos_dev;
+    e.nrm = nrm_dev;
+    e.nv = tp.n_vertices;
+    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
+    HIP_TRY(bfk_launch_deform_tris(scene->geom->corners, (const bfd::DDeformSrc *) stg->dev, m.tris0, m.tris0, nrm_dev ? m.normals0 : nullptr,
+                                   nrm_dev ? m.normals0 : nullptr, scene->d.n_tris, nullptr, 1u, 0u, 0u, bound, m.bad, stream));
+    HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel, not only by the copy
+    if (watch && (st = deform_watch(scene, stream)) != BF_OK) return st;
+    std::memcpy(&m.refit.mesh_box[6 * (size_t) shape], box6, 6 * sizeof(float));
+    m.deformed = true;
+    return apply_pose(scene, stream);
+}
+
+// What deform and posed batches share behind their checks: version k = the shapes of `src` (pos != nullptr; one entry per shape of the
 // scene) gathered from their arrays, every other mesh from the handle's base rows, then to_world[k] (absolute; NULL: none; `moves` from
 // check_rigid_tables), both trees re-fitted.  slice(k0, kc, hs) turns the copy `hs` of `src` into the table of renders k0 .. k0 + kc (it
 // may enqueue what fills the arrays first); `bound` covers every array of the call.  `who` names the caller in error text.
-template <class Slice>
 bf_status deform_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, const std::vector<bfd::DDeformSrc> &src,
                           float bound, const float *to_world, const std::vector<uint8_t> &moves, float *hist_dev, bf_path_record *records_dev,
-                          void *stream_, bf_stats *stats_out, const char *who, Slice &&slice) {
+                          void *stream_, bf_stats *stats_out, const char *who, const DeformSlice &slice) {
     MeshState &m = scene->mesh;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const uint32_t n_shapes = scene->info.n_shapes;
@@ -639,220 +750,30 @@ bf_status deform_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
     return stats_out ? deform_report(scene, true) : BF_OK;
 }
 
-// ---- skins (bf_scene_set_skin, bf_scene_pose_skin, bf_render_skin_batch_device) ---------------------------------------
-// The checks of a skinned shape common to a pose and a batch: what a vertex update refuses of the shape, and a shape without a skin.
-bf_status check_skinned_shape(const bf_scene *scene, uint32_t shape, const char *who, const bf_geometry::MeshTopo **tp, const MeshSkin **skin) {
-    const bf_status st = check_deform_shape(scene, shape, false, who, tp);
-    if (st != BF_OK) return st;
-    const MeshState &m = scene->mesh;
-    if (shape >= m.skins.size() || !m.skins[shape])
-        return fail(BF_ERR_INVALID, "%s shape %u has no skin (bf_scene_set_skin attaches one)", who, shape);
-    *skin = m.skins[shape].get();
+// The refusals every batch with a geometry version per render has before it looks at its tables: `fn` ends in ':', `kind` is "motion",
+// "deform", "skin" or "morph"; to_world may be NULL (then n_shapes is not looked at).
+bf_status check_batch_call(const char *fn, const char *kind, const bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const float *to_world,
+                           uint32_t n_shapes, const float *hist_dev) {
+    if (!scene || !launch || !hist_dev) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
+    if (to_world && n_shapes != scene->info.n_shapes)
+        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
+    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a %s batch is one launch sequence of its own", fn, kind);
+    if (launch->spp && launch->film_width && launch->film_height)
+        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
     return BF_OK;
 }
 
-// One bone table ([n_bones][12]) of skin `sk`: every entry finite, and per axis r the bound B[r] >= |posed coordinate r| of every
-// vertex raised to cover it.  X_c >= |coordinate c| of everything the bones are applied to: the skin's rest extent (skin_extent), or
-// what morph_extent derives for a morph ahead of the skin.  Derivation (u = 2^-24, W = the largest float64 sum of a weight row):
-//   q_k[r] = fl(fl(fl(fl(m_r0 x) + fl(m_r1 y)) + fl(m_r2 z)) + m_r3) of bone b = i_k: each product carries one rounding and the
-//     three sums one each, so |q_k[r]| <= Q_b[r] (1 + u)^4 with Q_b[r] = |m_r0| X_0 + |m_r1| X_1 + |m_r2| X_2 + |m_r3|;
-//   p'[r] = fl(fl(fl(fl(w0 q_0) + fl(w1 q_1)) + fl(w2 q_2)) + fl(w3 q_3)): again one rounding per product and three sums, so
-//     |p'[r]| <= (sum_k w_k |q_k[r]|) (1 + u)^4 <= W max_b Q_b[r] (1 + u)^8, the maximum over the bones some vertex gives a non-zero
-//     weight (a zero-weight slot adds fl(0 q) = +-0 exactly, whatever its bone's finite matrix holds).
-//   (1 + u)^8 < 1 + 5e-7; results that round into the subnormal range err by at most 2^-150 per operation instead.  The factor
-//   1 + 1e-5 below (origin_bound's margin) covers both, the evaluation of Q in float64 and the rounding of B to float.
-// `who` ends in ':' or ','.
-bf_status skin_bound(const MeshSkin &sk, const double X[3], uint32_t shape, const float *bones, const char *who, double B[3]) {
-    for (uint32_t b = 0; b < sk.n_bones; ++b) {
-        const float *m = bones + 12 * (size_t) b;
-        for (int j = 0; j < 12; ++j)
-            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "%s shape %u: bone %u has a non-finite entry", who, shape, b);
-        if (!sk.bone_used[b]) continue;
-        for (int r = 0; r < 3; ++r) {
-            double q = std::fabs((double) m[4 * r + 3]);
-            for (int c = 0; c < 3; ++c) q += std::fabs((double) m[4 * r + c]) * X[c];
-            B[r] = std::max(B[r], sk.weight_sum * q * (1.0 + 1e-5) + 1e-37);
-        }
-    }
-    return BF_OK;
-}
-struct SkinExtent {
-    double X[3];
-    explicit SkinExtent(const MeshSkin &sk) : X{(double) sk.rest_abs[0], (double) sk.rest_abs[1], (double) sk.rest_abs[2]} {}
-};
-// ... as the float the gather checks against (and the shape's base box takes); a bound float cannot hold is refused
-bf_status skin_bound_float(const double B[3], uint32_t shape, const char *who, float *bound, float box6[6],
-                           const char *why = "bones too large for the rest pose") {
-    float mx = std::numeric_limits<float>::min();
-    for (int r = 0; r < 3; ++r) {
-        const bool fits = B[r] < 0.5 * (double) std::numeric_limits<float>::max();
-        const float f = fits ? std::nextafter((float) B[r], std::numeric_limits<float>::infinity()) : 0.f;
-        if (!fits)
-            return fail(BF_ERR_INVALID, "%s shape %u: the bound on the posed coordinates is not finite (%s)", who, shape, why);
-        if (box6) box6[r] = -f, box6[3 + r] = f;
-        mx = std::max(mx, f);
-    }
-    *bound = mx;
-    return BF_OK;
-}
-
-// the handle's scratch for posed vertices, at least `bytes`
-bf_status skin_scratch(bf_scene *scene, size_t bytes, hipStream_t stream, const char *who) {
-    return vertex_scratch(scene->mesh.skin_vtx, scene->mesh.skin_vtx_cap, bytes, stream, who, "posed vertices");
-}
-
-// floats of one version of a skinned shape in the scratch: positions, then normals if the skin has them and they are wanted
-// (not under BF_NORMALS_RECOMPUTE: the blended normals are then not computed)
-size_t skin_floats(const MeshSkin &sk, bool with_normals) { return (size_t) sk.n_vertices * 3 * (sk.rest_nrm && with_normals ? 2 : 1); }
-
-// ---- morph targets (bf_scene_set_morph, bf_scene_pose_morph, bf_render_morph_batch_device) ----------------------------
-// The checks of a morphed shape common to a pose and a batch: what a vertex update refuses of the shape, a shape without a morph,
-// and (with_bones) a shape without the skin its bones need.
-bf_status check_morphed_shape(const bf_scene *scene, uint32_t shape, bool with_bones, const char *who, const bf_geometry::MeshTopo **tp,
-                              const MeshMorph **morph, const MeshSkin **skin) {
-    const bf_status st = check_deform_shape(scene, shape, false, who, tp);
-    if (st != BF_OK) return st;
-    const MeshState &m = scene->mesh;
-    if (shape >= m.morphs.size() || !m.morphs[shape])
-        return fail(BF_ERR_INVALID, "%s shape %u has no morph (bf_scene_set_morph attaches one)", who, shape);
-    *morph = m.morphs[shape].get();
-    *skin = nullptr;
-    if (!with_bones) return BF_OK;
-    if (shape >= m.skins.size() || !m.skins[shape])
-        return fail(BF_ERR_INVALID, "%s bones for shape %u, which has no skin (bf_scene_set_skin attaches one)", who, shape);
-    *skin = m.skins[shape].get();
-    return BF_OK;
-}
-
-// One pose's weights ([n_targets]) of morph `mo`: every weight finite, and per axis c the extent X[c] >= |morphed coordinate c| of every
-// vertex raised to cover it.  Derivation (u = 2^-24, K = n_targets, R_c = max |rest coordinate c|, D_k,c = max |delta coordinate c| of
-// target k): t_k = fl(w_k d_k) has |t_k| <= |w_k| D_k,c (1 + u), and p_k = fl(p_{k-1} + t_k) has |p_k| <= (|p_{k-1}| + |t_k|)(1 + u), so
-//   |p_K| <= (R_c + sum_k |w_k| D_k,c) (1 + u)^(K + 1),   and (1 + u)^(K + 1) < 1 + 2 (K + 1) u for K <= 256 (1.6e-5 at the most: more
-// than origin_bound's 1e-5, hence a factor of its own).  A result that rounds into the subnormal range errs by at most 2^-150 per
-// operation instead, 2 K of them: below the 1e-37 added.  A zero weight contributes |0| D = 0 however large its target's deltas are,
-// as fl(0 d) = +-0 does on the device.  The sum is taken in float64, whose own rounding the factor 2 covers.  `who` ends in ':' or ','.
-bf_status morph_extent(const MeshMorph &mo, uint32_t shape, const float *weights, const char *who, double X[3]) {
-    double s[3] = {(double) mo.rest_abs[0], (double) mo.rest_abs[1], (double) mo.rest_abs[2]};
-    for (uint32_t k = 0; k < mo.n_targets; ++k) {
-        if (!std::isfinite(weights[k])) return fail(BF_ERR_INVALID, "%s shape %u: the weight of target %u is not finite", who, shape, k);
-        for (int c = 0; c < 3; ++c) s[c] += std::fabs((double) weights[k]) * (double) mo.delta_abs[3 * (size_t) k + c];
-    }
-    for (int c = 0; c < 3; ++c) X[c] = std::max(X[c], s[c] * (1.0 + 2.0 * (mo.n_targets + 1.0) * 0x1p-24) + 1e-37);
-    return BF_OK;
-}
-
-// floats of one version of a morphed shape in the scratch: positions, then normals if the morph has them and they are wanted
-size_t morph_floats(const MeshMorph &mo, bool with_normals) { return (size_t) mo.n_vertices * 3 * (mo.rest_nrm && with_normals ? 2 : 1); }
-// floats of `n_versions` poses' weights in a staged table ([n_versions][n_targets]), padded to 16 bytes so that the bone tables behind stay aligned
-size_t morph_weight_floats(const MeshMorph &mo, uint32_t n_versions) { return ((size_t) n_versions * mo.n_targets + 3) & ~size_t(3); }
-
-}  // namespace
-
-bf_status MeshState::own_normals(bfd::DScene &d, std::vector<void *> &owned, const char *who) {
-    if (!d.normals || normals_private) return BF_OK;
-    float4 *q = nullptr;
-    const bf_status st = DevAlloc{owned, who}(bytes(d).normals, &q);
-    if (st != BF_OK) return st;
-    if (!normals0) normals0 = const_cast<float4 *>(d.normals);
-    d.normals = q;
-    normals_private = true;
-    return BF_OK;
-}
-
-void MeshState::reset_after_rebuild(float4 *tris0_, float4 *nodes0_, float4 *wnodes0_, float4 *normals0_) {
-    const bool posed = tris0_ != nullptr;
-    tris0 = tris0_, nodes0 = nodes0_, wnodes0 = wnodes0_, normals0 = normals0_;
-    // the handle's own arrays throughout; the boxes kept beside a pose are the POSED geometry's: only their topology is read from now on
-    geom_private = base_private = posed;
-    normals_private = normals0_private = normals0_ != nullptr;
-    if (posed) deformed = true;
-    // the level lists follow the topology: rebuilt at the next refit (mesh boxes and transform table stay); the arena's layout has changed
-    refit.ready = false;
-    refit.lvl4 = refit.lvl16 = nullptr;
-    refit.ubox4 = refit.ubox16 = nullptr;
-    refit.off4.clear();
-    refit.off16.clear();
-    batch_versions = 0;
-}
-
-MeshState::~MeshState() {
-    if (arena) (void) hipFree(arena);
-    if (bad) (void) hipFree(bad);
-    if (bad_host) (void) hipHostFree(bad_host);
-    if (bad_ev) (void) hipEventDestroy(bad_ev);
-    if (vtx_ev) {
-        (void) hipEventSynchronize(vtx_ev);
-        (void) hipEventDestroy(vtx_ev);
-    }
-    if (vtx_host) (void) hipHostFree(vtx_host);
-    if (vtx_dev) (void) hipFree(vtx_dev);
-    if (skin_vtx) (void) hipFree(skin_vtx);
-    if (nrm_vtx) (void) hipFree(nrm_vtx);
-}
-
-extern "C" {
-
-bf_status deform_report(const bf_scene *scene, bool wait) {
-    const MeshState &m = scene->mesh;
-    if (!m.bad_pending) return BF_OK;
-    if (wait) {
-        HIP_TRY(hipEventSynchronize(m.bad_ev));
-    } else if (hipEventQuery(m.bad_ev) != hipSuccess) {
-        (void) hipGetLastError();
-        return BF_OK;
-    }
-    m.bad_pending = false;
-    // the device counter only ever grows (nothing clears it under a gather in flight): what is new since the last report
-    const uint32_t total = m.bad_host[0], shape1 = m.bad_host[1];
-    const uint32_t n = total - m.bad_reported;
-    m.bad_reported = total;
-    if (!n) return BF_OK;
-    return fail(BF_ERR_DEVICE, "a device-form vertex update of this scene gave %u triangles (of shape %u, if not of others too) a corner "
-                               "that is not finite or lies beyond the declared bound: those triangles kept their previous vertices, "
-                               "and every render issued since that update is invalid", n, shape1 ? shape1 - 1u : 0u);
-}
-
-bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who, const bf_geometry::MeshTopo **topo_out) {
-    if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", who, shape, scene->info.n_shapes);
-    const bfd::DShape &sh = scene->ends.shapes_host[shape];
-    if (sh.type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", who, shape);
-    if (sh.emitter >= 0)
-        return fail(BF_ERR_UNSUPPORTED, "%s mesh shape %u carries emitter %d (its sampling tables are built from the triangles as "
-                                        "created); create a new scene", who, shape, sh.emitter);
-    const bf_geometry::MeshTopo &tp = scene->geom->topo[shape];
-    if (with_normals && !tp.has_normals)
-        return fail(BF_ERR_INVALID, "%s shape %u was created without vertex normals: it cannot take any", who, shape);
-    *topo_out = &tp;
-    return BF_OK;
-}
-
-bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
-    const MeshState &m = src->mesh;
-    sc->mesh.origin_scale_built = m.origin_scale_built;
-    sc->mesh.skins = m.skins;      // shared, never written: bf_scene_set_skin on either handle replaces that handle's pointer alone
-    sc->mesh.morphs = m.morphs;    // likewise (bf_scene_set_morph)
-    sc->mesh.normal_mode = m.normal_mode;      // the source's modes at this moment; the clone's own from now on
-    if (!m.tris0 && !m.geom_private) return BF_OK;
-    // `src` has moved: the clone snapshots what src renders now as ITS geometry "as created"; uvs (and normals no transform moved) stay shared
-    const MeshState::Bytes B = MeshState::bytes(src->d);
-    DevAlloc take{sc->owned, "bf_scene_clone"};
-    auto dup = [&](const float4 *from, size_t bytes, const float4 **to) -> bf_status {
-        float4 *p = nullptr;
-        const bf_status st = take(from ? bytes : 0, &p);
-        if (p) HIP_TRY(hipMemcpy(p, from, bytes, hipMemcpyDeviceToDevice));
-        *to = p;
-        return st;
-    };
-    bf_status st = BF_OK;
-    if ((st = dup(src->d.tris, B.tris, &sc->d.tris)) != BF_OK) return st;
-    if ((st = dup(src->d.nodes, B.nodes, &sc->d.nodes)) != BF_OK) return st;
-    if ((st = dup(src->d.wnodes, B.wnodes, &sc->d.wnodes)) != BF_OK) return st;
-    if (src->d.qnodes && (st = dup(src->d.qnodes, B.nodes / 2, &sc->d.qnodes)) != BF_OK) return st;
-    // normals a rigid transform moved are part of the snapshot (never written: the clone's first transform moves them into another array)
-    if (m.normals_private && (st = dup(src->d.normals, B.normals, &sc->d.normals)) != BF_OK) return st;
-    sc->mesh.geom_private = true;
-    sc->geom_token = std::make_shared<char>(0);      // the snapshot is the clone's alone: `src` keeps translating in place
-    return BF_OK;
+// ... and what each does first behind the lock.  A refused class or AOV launch does no device work (the refit's preparation and the
+// geometry versions would come first), and a scene without triangles has nothing to move: an ordinary batch.  True: the call ends
+// here with *st; false: the caller goes on to its versions.
+bool batch_ends_early(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, float *hist_dev,
+                      bf_path_record *records_dev, void *stream_, bf_stats *stats_out, bf_status *st) {
+    if ((*st = check_classes(scene, launch, n_renders)) != BF_OK || (*st = check_aov(scene, launch, n_renders)) != BF_OK) return true;
+    if (scene->d.n_tris != 0) return false;
+    bf_batch b = {n_renders, seeds, nullptr};
+    *st = render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
+    return true;
 }
 
 bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void *stream_) {
@@ -1168,27 +1089,16 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
 // for all renders of a chunk at once (grid y = version).  The handle's own geometry, pose, padding bound and clones are not touched.
 bf_status bf_render_motion_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_shapes,
                                         const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
-    if (!scene || !launch || !to_world || !hist_dev) return fail(BF_ERR_INVALID, "null argument");
-    if (n_renders == 0) return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: n_renders is 0");
-    if (n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: %u transforms per render for a scene of %u shapes", n_shapes, scene->info.n_shapes);
-    if (launch->flags & BF_FLAG_ROLLING)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: BF_FLAG_ROLLING: a motion batch is one launch sequence of its own");
-    if (launch->spp && launch->film_width && launch->film_height)
-        return fail(BF_ERR_INVALID, "bf_render_motion_batch_device: multi-pixel films are rendered one launch at a time");
+    const char *fn = "bf_render_motion_batch_device:";
+    if (!to_world) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    bf_status st = check_batch_call(fn, "motion", scene, launch, n_renders, to_world, n_shapes, hist_dev);
+    if (st != BF_OK) return st;
     // every render's table is checked before anything is enqueued: a failed call leaves the scene as it was
     std::vector<uint8_t> moves((size_t) n_renders * n_shapes, 0);
-    bf_status st = check_rigid_tables(scene, "bf_render_motion_batch_device:", n_renders, n_shapes, to_world, moves.data());
-    if (st != BF_OK) return st;
+    if ((st = check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data())) != BF_OK) return st;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
-    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
-    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
-    if (scene->d.n_tris == 0) {
-        // nothing to move: an ordinary batch
-        bf_batch b = {n_renders, seeds, nullptr};
-        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
-    }
+    if (batch_ends_early(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, &st)) return st;
     MeshState &m = scene->mesh;
     if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
     if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
@@ -1219,13 +1129,9 @@ bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch
                                         uint32_t n_shapes, const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_,
                                         bf_stats *stats_out) {
     const char *fn = "bf_render_deform_batch_device:";
-    if (!scene || !launch || !hist_dev || (n_deform && (!shapes || !positions_dev))) return fail(BF_ERR_INVALID, "%s null argument", fn);
-    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
-    if (to_world && n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
-    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a deform batch is one launch sequence of its own", fn);
-    if (launch->spp && launch->film_width && launch->film_height)
-        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
+    if (n_deform && (!shapes || !positions_dev)) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    bf_status st = check_batch_call(fn, "deform", scene, launch, n_renders, to_world, n_shapes, hist_dev);
+    if (st != BF_OK) return st;
     if (n_deform && (!(bound > 0.f) || !std::isfinite(bound))) return fail(BF_ERR_INVALID, "%s bound must be positive and finite", fn);
     n_shapes = scene->info.n_shapes;
     std::vector<bfd::DDeformSrc> src(n_shapes);
@@ -1242,15 +1148,9 @@ bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch
         src[shapes[j]].nv = tp->n_vertices;
     }
     std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
-    bf_status st = to_world ? check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data()) : BF_OK;
-    if (st != BF_OK) return st;
+    if (to_world && (st = check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data())) != BF_OK) return st;
     BF_ENTER(scene);
-    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
-    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
-    if (scene->d.n_tris == 0) {
-        bf_batch b = {n_renders, seeds, nullptr};
-        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
-    }
+    if (batch_ends_early(scene, launch, n_renders, seeds, hist_dev, records_dev, stream_, stats_out, &st)) return st;
     return deform_versions(scene, launch, n_renders, seeds, src, bound, to_world, moves, hist_dev, records_dev, stream_, stats_out,
                            "bf_render_deform_batch_device", [&](uint32_t k0, uint32_t, bfd::DDeformSrc *hs) -> bf_status {
         // the sources advanced to slice k0
@@ -1258,397 +1158,6 @@ bf_status bf_render_deform_batch_device(bf_scene *scene, const bf_launch *launch
             if (hs[k].pos) hs[k].pos += (size_t) k0 * 3 * hs[k].nv;
             if (hs[k].nrm) hs[k].nrm += (size_t) k0 * 3 * hs[k].nv;
         }
-        return BF_OK;
-    });
-}
-
-// ---- skinned meshes: a pose is n_bones 3x4 matrices, bf_skin_vertices_kernel computes the vertices into the handle's
-// scratch, and from there on a pose is a device-form vertex update and a batch a device-form deform batch, bound computed here ----
-bf_status bf_scene_set_skin(bf_scene *scene, uint32_t shape, uint32_t n_bones, const float *rest_positions, const float *rest_normals,
-                            const uint32_t *bone_index, const float *bone_weight) {
-    const char *fn = "bf_scene_set_skin:";
-    if (!scene) return fail(BF_ERR_INVALID, "%s null scene", fn);
-    const bf_geometry::MeshTopo *tp = nullptr;
-    bf_status st = check_deform_shape(scene, shape, n_bones && rest_normals, fn, &tp);
-    if (st != BF_OK) return st;
-    if (n_bones == 0) {
-        BF_ENTER(scene);
-        if (shape < scene->mesh.skins.size()) scene->mesh.skins[shape].reset();
-        return BF_OK;
-    }
-    if (n_bones > 256u) return fail(BF_ERR_INVALID, "%s shape %u: %u bones (at most 256 per shape)", fn, shape, n_bones);
-    if (!rest_positions || !bone_index || !bone_weight) return fail(BF_ERR_INVALID, "%s shape %u: null array", fn, shape);
-    if (tp->has_normals && !rest_normals)
-        return fail(BF_ERR_INVALID, "%s shape %u was created with vertex normals: its skin needs rest normals", fn, shape);
-    const uint32_t nv = tp->n_vertices;
-    auto skin = std::make_shared<MeshSkin>();
-    skin->n_bones = n_bones;
-    skin->n_vertices = nv;
-    skin->bone_used.assign(n_bones, 0);
-    for (uint32_t v = 0; v < nv; ++v) {
-        for (int c = 0; c < 3; ++c) {
-            const float x = rest_positions[3 * (size_t) v + c];
-            if (!std::isfinite(x) || (rest_normals && !std::isfinite(rest_normals[3 * (size_t) v + c])))
-                return fail(BF_ERR_INVALID, "%s shape %u: non-finite rest value at vertex %u", fn, shape, v);
-            skin->rest_abs[c] = std::max(skin->rest_abs[c], std::fabs(x));
-        }
-        double sum = 0.0;
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t b = bone_index[4 * (size_t) v + k];
-            const float w = bone_weight[4 * (size_t) v + k];
-            if (b >= n_bones) return fail(BF_ERR_INVALID, "%s shape %u: vertex %u names bone %u of %u", fn, shape, v, b, n_bones);
-            if (!std::isfinite(w) || w < 0.f) return fail(BF_ERR_INVALID, "%s shape %u: vertex %u has weight %g for bone %u", fn, shape, v, (double) w, b);
-            if (w > 0.f) skin->bone_used[b] = 1;
-            sum += (double) w;
-        }
-        if (!(std::fabs(sum - 1.0) <= 1e-3)) return fail(BF_ERR_INVALID, "%s shape %u: the weights of vertex %u sum to %.9g, not 1", fn, shape, v, sum);
-        skin->weight_sum = std::max(skin->weight_sum, sum);
-    }
-    BF_ENTER(scene);
-    if (nv) {
-        // one block: weights, indices (16-byte rows first), rest positions, rest normals
-        const size_t row = (size_t) nv * 16, vec = (size_t) nv * 12, bytes = 2 * row + vec * (rest_normals ? 2 : 1);
-        std::vector<char> host(bytes);
-        std::memcpy(host.data(), bone_weight, row);
-        std::memcpy(host.data() + row, bone_index, row);
-        std::memcpy(host.data() + 2 * row, rest_positions, vec);
-        if (rest_normals) std::memcpy(host.data() + 2 * row + vec, rest_normals, vec);
-        const hipError_t he = hipMalloc(&skin->block, bytes);
-        if (he != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(BF_ERR_NOMEM, "%s shape %u: hipMalloc(%zu bytes): %s", fn, shape, bytes, hipGetErrorString(he));
-        }
-        HIP_TRY(hipMemcpy(skin->block, host.data(), bytes, hipMemcpyHostToDevice));
-        const char *blk = (const char *) skin->block;
-        skin->weight = (const float4 *) blk;
-        skin->index = (const uint4 *) (blk + row);
-        skin->rest_pos = (const float *) (blk + 2 * row);
-        skin->rest_nrm = rest_normals ? (const float *) (blk + 2 * row + vec) : nullptr;
-    }
-    MeshState &m = scene->mesh;
-    if (m.skins.size() < scene->info.n_shapes) m.skins.resize(scene->info.n_shapes);
-    m.skins[shape] = std::move(skin);      // (the skin it replaces goes with its last handle; hipFree waits for the kernels that read it)
-    return BF_OK;
-}
-
-bf_status bf_scene_pose_skin(bf_scene *scene, uint32_t shape, const float *bones, void *stream_) {
-    const char *fn = "bf_scene_pose_skin:";
-    if (!scene || !bones) return fail(BF_ERR_INVALID, "%s null argument", fn);
-    const bf_geometry::MeshTopo *tp = nullptr;
-    const MeshSkin *sk = nullptr;
-    bf_status st = check_skinned_shape(scene, shape, fn, &tp, &sk);
-    if (st != BF_OK) return st;
-    double B[3] = {0.0, 0.0, 0.0};
-    float bound = 0.f, box[6];
-    if ((st = skin_bound(*sk, SkinExtent(*sk).X, shape, bones, fn, B)) != BF_OK || (st = skin_bound_float(B, shape, fn, &bound, box)) != BF_OK) return st;
-    if (scene->d.n_tris == 0 || sk->n_vertices == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    MeshState &m = scene->mesh;
-    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
-    const float *rest_nrm = m.recomputes(shape) ? nullptr : sk->rest_nrm;      // BF_NORMALS_RECOMPUTE: update_vertices_locked computes them
-    if ((st = skin_scratch(scene, skin_floats(*sk, rest_nrm != nullptr) * sizeof(float), stream, fn)) != BF_OK) return st;
-    const size_t bytes = (size_t) sk->n_bones * 12 * sizeof(float);
-    bf_scene::Stage *stg = nullptr;
-    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
-    std::memcpy(stg->host, bones, bytes);
-    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
-    float *pos = m.skin_vtx, *nrm = rest_nrm ? m.skin_vtx + 3 * (size_t) sk->n_vertices : nullptr;
-    HIP_TRY(bfk_launch_skin_vertices(sk->rest_pos, rest_nrm, sk->index, sk->weight, sk->n_vertices, (const float *) stg->dev, sk->n_bones, pos, nrm,
-                                     1u, stream));
-    HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel
-    if ((st = update_vertices_locked(scene, shape, *tp, pos, nrm, bound, box, true, stream)) != BF_OK) return st;
-    return mark_last(scene, stream);
-}
-
-bf_status bf_render_skin_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_skinned,
-                                      const uint32_t *shapes, const float *const *bones, uint32_t n_shapes, const float *to_world, float *hist_dev,
-                                      bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
-    const char *fn = "bf_render_skin_batch_device:";
-    if (!scene || !launch || !hist_dev || (n_skinned && (!shapes || !bones))) return fail(BF_ERR_INVALID, "%s null argument", fn);
-    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
-    if (to_world && n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
-    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a skin batch is one launch sequence of its own", fn);
-    if (launch->spp && launch->film_width && launch->film_height)
-        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
-    n_shapes = scene->info.n_shapes;
-    // the gather's table: a skinned shape's entry is marked here and pointed at the chunk's posed vertices below
-    std::vector<bfd::DDeformSrc> src(n_shapes);
-    std::memset(src.data(), 0, src.size() * sizeof(bfd::DDeformSrc));
-    std::vector<const MeshSkin *> skins(n_skinned, nullptr);
-    size_t version_floats = 0, version_bones = 0;      // of all skinned shapes, per render
-    double B[3] = {0.0, 0.0, 0.0};
-    for (uint32_t j = 0; j < n_skinned; ++j) {
-        const bf_geometry::MeshTopo *tp = nullptr;
-        bf_status cst = check_skinned_shape(scene, shapes[j], fn, &tp, &skins[j]);
-        if (cst != BF_OK) return cst;
-        if (!bones[j]) return fail(BF_ERR_INVALID, "%s shape %u: null bones", fn, shapes[j]);
-        if (src[shapes[j]].pos) return fail(BF_ERR_INVALID, "%s shape %u is listed twice", fn, shapes[j]);
-        src[shapes[j]].pos = (const float *) (uintptr_t) 16;      // (marks the shape; never read)
-        src[shapes[j]].nv = tp->n_vertices;
-        for (uint32_t k = 0; k < n_renders; ++k) {
-            char who[96];
-            std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
-            if ((cst = skin_bound(*skins[j], SkinExtent(*skins[j]).X, shapes[j], bones[j] + (size_t) k * skins[j]->n_bones * 12, who, B)) != BF_OK) return cst;
-        }
-        version_floats += skin_floats(*skins[j], !scene->mesh.recomputes(shapes[j]));
-        version_bones += (size_t) skins[j]->n_bones * 12;
-    }
-    float bound = std::numeric_limits<float>::min();
-    bf_status st = n_skinned ? skin_bound_float(B, shapes[0], fn, &bound, nullptr) : BF_OK;
-    if (st != BF_OK) return st;
-    std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
-    if (to_world && (st = check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data())) != BF_OK) return st;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
-    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
-    if (scene->d.n_tris == 0) {
-        bf_batch b = {n_renders, seeds, nullptr};
-        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
-    }
-    MeshState &m = scene->mesh;
-    return deform_versions(scene, launch, n_renders, seeds, src, bound, to_world, moves, hist_dev, records_dev, stream_, stats_out,
-                           "bf_render_skin_batch_device", [&](uint32_t k0, uint32_t kc, bfd::DDeformSrc *hs) -> bf_status {
-        // the chunk's bone tables ([kc][n_bones][12] per shape, one shape after the other) and, from them, its posed vertices in the scratch
-        // (per shape [kc][nv][3] positions, then its normals): version v of the gather reads slice v
-        bf_status pst = skin_scratch(scene, (size_t) kc * version_floats * sizeof(float), stream, fn);
-        if (pst != BF_OK || !version_bones) return pst;
-        const size_t bytes = (size_t) kc * version_bones * sizeof(float);
-        bf_scene::Stage *stg = nullptr;
-        if ((pst = stage_acquire(scene, bytes, &stg)) != BF_OK) return pst;
-        float *hb = (float *) stg->host;
-        for (uint32_t j = 0; j < n_skinned; ++j) {
-            const size_t n = (size_t) kc * skins[j]->n_bones * 12;
-            std::memcpy(hb, bones[j] + (size_t) k0 * skins[j]->n_bones * 12, n * sizeof(float));
-            hb += n;
-        }
-        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
-        const float *db = (const float *) stg->dev;
-        float *out = m.skin_vtx;
-        for (uint32_t j = 0; j < n_skinned; ++j) {
-            const MeshSkin &sk = *skins[j];
-            const size_t n = (size_t) kc * sk.n_vertices * 3;
-            // (BF_NORMALS_RECOMPUTE: no blended normals; deform_versions computes the posed surface's behind this)
-            const float *rest_nrm = m.recomputes(shapes[j]) ? nullptr : sk.rest_nrm;
-            float *pos = out, *nrm = rest_nrm ? out + n : nullptr;
-            HIP_TRY(bfk_launch_skin_vertices(sk.rest_pos, rest_nrm, sk.index, sk.weight, sk.n_vertices, db, sk.n_bones, pos, nrm, kc, stream));
-            hs[shapes[j]].pos = pos;
-            hs[shapes[j]].nrm = nrm;
-            db += (size_t) kc * sk.n_bones * 12;
-            out += (size_t) kc * skin_floats(sk, rest_nrm != nullptr);
-        }
-        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernels
-        return BF_OK;
-    });
-}
-
-// ---- morph targets: a pose is n_targets weights (and, for a shape that also carries a skin, its bones);
-// bf_morph_vertices_kernel computes the vertices into the handle's posed-vertex scratch, and from there on everything is a skin pose's ----
-bf_status bf_scene_set_morph(bf_scene *scene, uint32_t shape, uint32_t n_targets, const float *rest_positions, const float *rest_normals,
-                             const float *delta_positions, const float *delta_normals) {
-    const char *fn = "bf_scene_set_morph:";
-    if (!scene) return fail(BF_ERR_INVALID, "%s null scene", fn);
-    const bf_geometry::MeshTopo *tp = nullptr;
-    bf_status st = check_deform_shape(scene, shape, n_targets && rest_normals, fn, &tp);
-    if (st != BF_OK) return st;
-    if (n_targets == 0) {
-        BF_ENTER(scene);
-        if (shape < scene->mesh.morphs.size()) scene->mesh.morphs[shape].reset();
-        return BF_OK;
-    }
-    if (n_targets > 256u) return fail(BF_ERR_INVALID, "%s shape %u: %u targets (at most 256 per shape)", fn, shape, n_targets);
-    if (!rest_positions || !delta_positions) return fail(BF_ERR_INVALID, "%s shape %u: null array", fn, shape);
-    if (tp->has_normals && !rest_normals)
-        return fail(BF_ERR_INVALID, "%s shape %u was created with vertex normals: its morph needs rest normals", fn, shape);
-    if (delta_normals && !rest_normals) return fail(BF_ERR_INVALID, "%s shape %u: normal deltas without rest normals", fn, shape);
-    const uint32_t nv = tp->n_vertices;
-    auto morph = std::make_shared<MeshMorph>();
-    morph->n_targets = n_targets;
-    morph->n_vertices = nv;
-    morph->delta_abs.assign((size_t) 3 * n_targets, 0.f);
-    for (uint32_t v = 0; v < nv; ++v)
-        for (int c = 0; c < 3; ++c) {
-            const float x = rest_positions[3 * (size_t) v + c];
-            if (!std::isfinite(x) || (rest_normals && !std::isfinite(rest_normals[3 * (size_t) v + c])))
-                return fail(BF_ERR_INVALID, "%s shape %u: non-finite rest value at vertex %u", fn, shape, v);
-            morph->rest_abs[c] = std::max(morph->rest_abs[c], std::fabs(x));
-        }
-    for (uint32_t k = 0; k < n_targets; ++k)
-        for (uint32_t v = 0; v < nv; ++v)
-            for (int c = 0; c < 3; ++c) {
-                const size_t i = 3 * ((size_t) k * nv + v) + c;
-                if (!std::isfinite(delta_positions[i]) || (delta_normals && !std::isfinite(delta_normals[i])))
-                    return fail(BF_ERR_INVALID, "%s shape %u: non-finite delta of target %u at vertex %u", fn, shape, k, v);
-                morph->delta_abs[3 * (size_t) k + c] = std::max(morph->delta_abs[3 * (size_t) k + c], std::fabs(delta_positions[i]));
-            }
-    BF_ENTER(scene);
-    if (nv) {
-        // one block: rest positions, rest normals, position deltas, normal deltas
-        const size_t vec = (size_t) nv * 12, del = vec * n_targets;
-        const size_t bytes = vec * (rest_normals ? 2 : 1) + del * (delta_normals ? 2 : 1);
-        const hipError_t he = hipMalloc(&morph->block, bytes);
-        if (he != hipSuccess) {
-            (void) hipGetLastError();
-            return fail(BF_ERR_NOMEM, "%s shape %u: hipMalloc(%zu bytes): %s", fn, shape, bytes, hipGetErrorString(he));
-        }
-        char *blk = (char *) morph->block;
-        size_t at = 0;
-        auto put = [&](const float *src, size_t n) -> const float * {
-            if (!src) return nullptr;
-            char *dst = blk + at;
-            at += n;
-            return hipMemcpy(dst, src, n, hipMemcpyHostToDevice) == hipSuccess ? (const float *) dst : nullptr;
-        };
-        morph->rest_pos = put(rest_positions, vec);
-        morph->rest_nrm = put(rest_normals, vec);
-        morph->dpos = put(delta_positions, del);
-        morph->dnrm = put(delta_normals, del);
-        if (!morph->rest_pos || !morph->dpos || (rest_normals && !morph->rest_nrm) || (delta_normals && !morph->dnrm))
-            return fail(BF_ERR_DEVICE, "%s shape %u: hipMemcpy of %zu bytes: %s", fn, shape, bytes, hipGetErrorString(hipGetLastError()));
-    }
-    MeshState &m = scene->mesh;
-    if (m.morphs.size() < scene->info.n_shapes) m.morphs.resize(scene->info.n_shapes);
-    m.morphs[shape] = std::move(morph);      // (the morph it replaces goes with its last handle; hipFree waits for the kernels that read it)
-    return BF_OK;
-}
-
-bf_status bf_scene_pose_morph(bf_scene *scene, uint32_t shape, const float *weights, const float *bones, void *stream_) {
-    const char *fn = "bf_scene_pose_morph:";
-    if (!scene || !weights) return fail(BF_ERR_INVALID, "%s null argument", fn);
-    const bf_geometry::MeshTopo *tp = nullptr;
-    const MeshMorph *mo = nullptr;
-    const MeshSkin *sk = nullptr;
-    bf_status st = check_morphed_shape(scene, shape, bones != nullptr, fn, &tp, &mo, &sk);
-    if (st != BF_OK) return st;
-    // the morph's extent is the bound, or what the skin bound takes in place of the skin's rest extent
-    double X[3] = {0.0, 0.0, 0.0}, B[3] = {0.0, 0.0, 0.0};
-    float bound = 0.f, box[6];
-    if ((st = morph_extent(*mo, shape, weights, fn, X)) != BF_OK) return st;
-    if (sk && (st = skin_bound(*sk, X, shape, bones, fn, B)) != BF_OK) return st;
-    if ((st = skin_bound_float(sk ? B : X, shape, fn, &bound, box, "weights or bones too large for the targets")) != BF_OK) return st;
-    if (scene->d.n_tris == 0 || mo->n_vertices == 0) return BF_OK;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    MeshState &m = scene->mesh;
-    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
-    const float *rest_nrm = m.recomputes(shape) ? nullptr : mo->rest_nrm;      // BF_NORMALS_RECOMPUTE: update_vertices_locked computes them
-    if ((st = skin_scratch(scene, morph_floats(*mo, rest_nrm != nullptr) * sizeof(float), stream, fn)) != BF_OK) return st;
-    const size_t wf = morph_weight_floats(*mo, 1u), bytes = (wf + (sk ? (size_t) sk->n_bones * 12 : 0)) * sizeof(float);
-    bf_scene::Stage *stg = nullptr;
-    if ((st = stage_acquire(scene, bytes, &stg)) != BF_OK) return st;
-    std::memset(stg->host, 0, wf * sizeof(float));
-    std::memcpy(stg->host, weights, (size_t) mo->n_targets * sizeof(float));
-    if (sk) std::memcpy((float *) stg->host + wf, bones, (size_t) sk->n_bones * 12 * sizeof(float));
-    if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
-    float *pos = m.skin_vtx, *nrm = rest_nrm ? m.skin_vtx + 3 * (size_t) mo->n_vertices : nullptr;
-    HIP_TRY(bfk_launch_morph_vertices(mo->rest_pos, rest_nrm, mo->dpos, mo->dnrm, mo->n_vertices, mo->n_targets, (const float *) stg->dev,
-                                      sk ? sk->index : nullptr, sk ? sk->weight : nullptr, sk ? (const float *) stg->dev + wf : nullptr,
-                                      sk ? sk->n_bones : 0u, pos, nrm, 1u, stream));
-    HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernel
-    if ((st = update_vertices_locked(scene, shape, *tp, pos, nrm, bound, box, true, stream)) != BF_OK) return st;
-    return mark_last(scene, stream);
-}
-
-bf_status bf_render_morph_batch_device(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, uint32_t n_morphed,
-                                       const uint32_t *shapes, const float *const *weights, const float *const *bones, uint32_t n_shapes,
-                                       const float *to_world, float *hist_dev, bf_path_record *records_dev, void *stream_, bf_stats *stats_out) {
-    const char *fn = "bf_render_morph_batch_device:";
-    if (!scene || !launch || !hist_dev || (n_morphed && (!shapes || !weights))) return fail(BF_ERR_INVALID, "%s null argument", fn);
-    if (n_renders == 0) return fail(BF_ERR_INVALID, "%s n_renders is 0", fn);
-    if (to_world && n_shapes != scene->info.n_shapes)
-        return fail(BF_ERR_INVALID, "%s %u transforms per render for a scene of %u shapes", fn, n_shapes, scene->info.n_shapes);
-    if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: a morph batch is one launch sequence of its own", fn);
-    if (launch->spp && launch->film_width && launch->film_height)
-        return fail(BF_ERR_INVALID, "%s multi-pixel films are rendered one launch at a time", fn);
-    n_shapes = scene->info.n_shapes;
-    // the gather's table: a morphed shape's entry is marked here and pointed at the chunk's posed vertices below
-    std::vector<bfd::DDeformSrc> src(n_shapes);
-    std::memset(src.data(), 0, src.size() * sizeof(bfd::DDeformSrc));
-    std::vector<const MeshMorph *> morphs(n_morphed, nullptr);
-    std::vector<const MeshSkin *> skins(n_morphed, nullptr);      // null: morphed only
-    size_t version_floats = 0;      // posed vertices of all morphed shapes, per render
-    double B[3] = {0.0, 0.0, 0.0};
-    for (uint32_t j = 0; j < n_morphed; ++j) {
-        const bf_geometry::MeshTopo *tp = nullptr;
-        const float *bj = bones ? bones[j] : nullptr;
-        bf_status cst = check_morphed_shape(scene, shapes[j], bj != nullptr, fn, &tp, &morphs[j], &skins[j]);
-        if (cst != BF_OK) return cst;
-        if (!weights[j]) return fail(BF_ERR_INVALID, "%s shape %u: null weights", fn, shapes[j]);
-        if (src[shapes[j]].pos) return fail(BF_ERR_INVALID, "%s shape %u is listed twice", fn, shapes[j]);
-        src[shapes[j]].pos = (const float *) (uintptr_t) 16;      // (marks the shape; never read)
-        src[shapes[j]].nv = tp->n_vertices;
-        for (uint32_t k = 0; k < n_renders; ++k) {
-            char who[96];
-            std::snprintf(who, sizeof(who), "%s render %u,", fn, k);
-            double X[3] = {0.0, 0.0, 0.0};
-            if ((cst = morph_extent(*morphs[j], shapes[j], weights[j] + (size_t) k * morphs[j]->n_targets, who, X)) != BF_OK) return cst;
-            if (skins[j]) {
-                if ((cst = skin_bound(*skins[j], X, shapes[j], bj + (size_t) k * skins[j]->n_bones * 12, who, B)) != BF_OK) return cst;
-            } else {
-                for (int c = 0; c < 3; ++c) B[c] = std::max(B[c], X[c]);
-            }
-        }
-        version_floats += morph_floats(*morphs[j], !scene->mesh.recomputes(shapes[j]));
-    }
-    float bound = std::numeric_limits<float>::min();
-    bf_status st = n_morphed ? skin_bound_float(B, shapes[0], fn, &bound, nullptr, "weights or bones too large for the targets") : BF_OK;
-    if (st != BF_OK) return st;
-    std::vector<uint8_t> moves(to_world ? (size_t) n_renders * n_shapes : 0, 0);
-    if (to_world && (st = check_rigid_tables(scene, fn, n_renders, n_shapes, to_world, moves.data())) != BF_OK) return st;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    BF_ENTER(scene);
-    // a refused class launch does no device work (the refit's preparation and the geometry versions below would come first)
-    if ((st = check_classes(scene, launch, n_renders)) != BF_OK || (st = check_aov(scene, launch, n_renders)) != BF_OK) return st;
-    if (scene->d.n_tris == 0) {
-        bf_batch b = {n_renders, seeds, nullptr};
-        return render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);
-    }
-    MeshState &m = scene->mesh;
-    return deform_versions(scene, launch, n_renders, seeds, src, bound, to_world, moves, hist_dev, records_dev, stream_, stats_out,
-                           "bf_render_morph_batch_device", [&](uint32_t k0, uint32_t kc, bfd::DDeformSrc *hs) -> bf_status {
-        // the chunk's tables (per shape [kc][n_targets] weights, padded to 16 bytes, then [kc][n_bones][12] bones if it is skinned; one shape
-        // after the other) and, from them, its posed vertices in the scratch (per shape [kc][nv][3] positions, then its normals)
-        bf_status pst = skin_scratch(scene, (size_t) kc * version_floats * sizeof(float), stream, fn);
-        if (pst != BF_OK || !n_morphed) return pst;
-        size_t floats = 0;
-        for (uint32_t j = 0; j < n_morphed; ++j)
-            floats += morph_weight_floats(*morphs[j], kc) + (skins[j] ? (size_t) kc * skins[j]->n_bones * 12 : 0);
-        const size_t bytes = floats * sizeof(float);
-        bf_scene::Stage *stg = nullptr;
-        if ((pst = stage_acquire(scene, bytes, &stg)) != BF_OK) return pst;
-        float *hb = (float *) stg->host;
-        std::memset(hb, 0, bytes);
-        for (uint32_t j = 0; j < n_morphed; ++j) {
-            const uint32_t nt = morphs[j]->n_targets;
-            std::memcpy(hb, weights[j] + (size_t) k0 * nt, (size_t) kc * nt * sizeof(float));
-            hb += morph_weight_floats(*morphs[j], kc);
-            if (skins[j]) {
-                const size_t n = (size_t) kc * skins[j]->n_bones * 12;
-                std::memcpy(hb, bones[j] + (size_t) k0 * skins[j]->n_bones * 12, n * sizeof(float));
-                hb += n;
-            }
-        }
-        if ((pst = stage_commit(stg, bytes, stream)) != BF_OK) return pst;
-        const float *db = (const float *) stg->dev;
-        float *out = m.skin_vtx;
-        for (uint32_t j = 0; j < n_morphed; ++j) {
-            const MeshMorph &mo = *morphs[j];
-            const MeshSkin *sk = skins[j];
-            const size_t n = (size_t) kc * mo.n_vertices * 3;
-            // (BF_NORMALS_RECOMPUTE: no morphed or blended normals; deform_versions computes the posed surface's behind this)
-            const float *rest_nrm = m.recomputes(shapes[j]) ? nullptr : mo.rest_nrm;
-            float *pos = out, *nrm = rest_nrm ? out + n : nullptr;
-            const float *dw = db, *dbones = sk ? db + morph_weight_floats(mo, kc) : nullptr;
-            HIP_TRY(bfk_launch_morph_vertices(mo.rest_pos, rest_nrm, mo.dpos, mo.dnrm, mo.n_vertices, mo.n_targets, dw, sk ? sk->index : nullptr,
-                                              sk ? sk->weight : nullptr, dbones, sk ? sk->n_bones : 0u, pos, nrm, kc, stream));
-            hs[shapes[j]].pos = pos;
-            hs[shapes[j]].nrm = nrm;
-            db += morph_weight_floats(mo, kc) + (sk ? (size_t) kc * sk->n_bones * 12 : 0);
-            out += (size_t) kc * morph_floats(mo, rest_nrm != nullptr);
-        }
-        HIP_TRY(hipEventRecord(stg->ev, stream));      // the tables are read by the kernels
         return BF_OK;
     });
 }

@@ -1,9 +1,10 @@
-// What bf_api.cpp, bf_render.cpp, bf_mesh.cpp and bf_endpoints.cpp share: the scene handle, its guards and the few functions of each file the others call.
+// What bf_api.cpp, bf_render.cpp, bf_mesh.cpp, bf_pose.cpp and bf_endpoints.cpp share: the scene handle, its guards and the few functions of each file the others call.
 // Internal to libbeifong_hip.so: the functions and guards declared here have hidden visibility (the C ABI is include/beifong_hip.h alone).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -13,7 +14,7 @@
 #include "bf_device.h"
 #include "bf_wavefront.h"
 
-// the launchers of bf_kernels.hip that move geometry (bf_mesh.cpp)
+// the launchers of bf_kernels.hip that move geometry (bf_mesh.cpp, bf_pose.cpp)
 extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, uint32_t n_tri_rows, const float4 *nodes0,
                                            float4 *nodes, float4 *qnodes, uint32_t n_nodes, const float4 *wnodes0, float4 *wnodes,
                                            uint32_t n_wchildren, const float *d, hipStream_t stream);
@@ -117,7 +118,7 @@ struct __attribute__((visibility("hidden"))) MeshSkin {
     const uint4 *index = nullptr;         // [n_vertices]: i0..i3, each < n_bones
     const float *rest_pos = nullptr;      // [n_vertices][3]
     const float *rest_nrm = nullptr;      // [n_vertices][3], or null: the mesh has no vertex normals
-    // what the bound on the posed coordinates is derived from (bf_mesh.cpp: skin_bound)
+    // what the bound on the posed coordinates is derived from (bf_pose.cpp: skin_bound)
     float rest_abs[3] = {0.f, 0.f, 0.f};  // max |rest coordinate| per axis
     double weight_sum = 0.0;              // largest float64 sum of a weight row (validated: within 1e-3 of 1)
     std::vector<uint8_t> bone_used;       // [n_bones]: some vertex gives the bone a non-zero weight
@@ -135,7 +136,7 @@ struct __attribute__((visibility("hidden"))) MeshMorph {
     const float *rest_nrm = nullptr;      // [n_vertices][3], or null: the mesh has no vertex normals
     const float *dpos = nullptr;          // [n_targets][n_vertices][3]
     const float *dnrm = nullptr;          // [n_targets][n_vertices][3], or null: the rest normals are copied
-    // what the bound on the morphed coordinates is derived from (bf_mesh.cpp: morph_extent)
+    // what the bound on the morphed coordinates is derived from (bf_pose.cpp: morph_extent)
     float rest_abs[3] = {0.f, 0.f, 0.f};  // max |rest coordinate| per axis
     std::vector<float> delta_abs;         // [n_targets][3]: max |delta coordinate| per target and axis
     ~MeshMorph() {
@@ -186,16 +187,16 @@ struct __attribute__((visibility("hidden"))) MeshState {
     void *vtx_host = nullptr, *vtx_dev = nullptr;
     size_t vtx_cap = 0;
     hipEvent_t vtx_ev = nullptr;
-    // skins (bf_scene_set_skin): per shape, empty until the first one is attached; shared with clones taken afterwards.  skin_vtx:
-    // where bf_skin_vertices_kernel writes the posed vertices (and normals) of a pose or of a batch chunk, for the gather to read;
-    // the handle's own, grown on demand, never shrunk
+    // skins (bf_scene_set_skin) and morph targets (bf_scene_set_morph), bf_pose.cpp's: per shape, empty until the first one is
+    // attached; shared with clones taken afterwards.  pose_vtx: where bf_skin_vertices_kernel or bf_morph_vertices_kernel writes the
+    // posed vertices (and normals) of a pose or of a batch chunk, for the gather to read; the handle's own, grown on demand, never shrunk
     std::vector<std::shared_ptr<const MeshSkin>> skins;
-    std::vector<std::shared_ptr<const MeshMorph>> morphs;      // bf_scene_set_morph: the same rules; bf_morph_vertices_kernel writes skin_vtx too
-    float *skin_vtx = nullptr;
-    size_t skin_vtx_cap = 0;                     // bytes
+    std::vector<std::shared_ptr<const MeshMorph>> morphs;
+    float *pose_vtx = nullptr;
+    size_t pose_vtx_cap = 0;                     // bytes
     // normal modes (bf_scene_set_normal_mode): BF_NORMALS_* per shape, empty until the first call (every shape BF_NORMALS_GIVEN);
     // a clone copies them.  nrm_vtx: where bf_vertex_normals_kernel writes the normals of an update or of a batch chunk, for the
-    // gather to read; the skin scratch's rules
+    // gather to read; the posed-vertex scratch's rules
     std::vector<uint8_t> normal_mode;
     float *nrm_vtx = nullptr;
     size_t nrm_vtx_cap = 0;                      // bytes
@@ -394,7 +395,7 @@ struct bf_scene {
     bf_scene_info info;
     int device = 0;
     int n_cus = 256;
-    MeshState mesh;                        // everything about moved meshes (bf_mesh.cpp)
+    MeshState mesh;                        // everything about moved meshes (bf_mesh.cpp, bf_pose.cpp)
     mutable RenderState run;               // everything about renders (bf_render.cpp)
     mutable EndpointState ends;            // everything about the endpoint tables (bf_endpoints.cpp)
     // Pinned staging for small host tables that travel with a launch (batch seeds / mesh offsets, endpoint records):
@@ -442,20 +443,21 @@ struct DeviceGuard {
         if (prev >= 0) (void) hipSetDevice(prev);
     }
 };
-#define BF_ENTER(scene)                                                                                                   \
+#define BF_ENTER_AS(scene, name)                                                                                          \
     BusyGuard busy_guard_(scene);                                                                                         \
     if (!busy_guard_.ok)                                                                                                  \
         return fail(BF_ERR_INVALID, "%s: the scene handle is in use by another host thread (one call at a time per handle; " \
-                                    "bf_scene_clone gives every thread / stream its own)", __func__)
+                                    "bf_scene_clone gives every thread / stream its own)", name)
+#define BF_ENTER(scene) BF_ENTER_AS(scene, __func__)      // (..._AS: for a body that several entries share)
 
-// ---- bf_api.cpp's, called by the other three and documented where they are defined (C names: those files are one extern "C" block each) ----
+// ---- bf_api.cpp's, called by the others and documented where they are defined (C names: those files are one extern "C" block each) ----
 extern "C" {
 bf_status fail(bf_status st, const char *fmt, ...);      // sets bf_last_error's text
 bf_status stage_acquire(const bf_scene *sc, size_t bytes, bf_scene::Stage **out);
 bf_status stage_commit(bf_scene::Stage *st, size_t bytes, hipStream_t stream);
 bf_status stage_release_after(bf_scene::Stage *st, hipStream_t stream);
 
-// ---- bf_render.cpp, called by the other three ----
+// ---- bf_render.cpp, called by the others ----
 bf_status order_after_last(const bf_scene *scene, hipStream_t stream);
 bf_status mark_last(const bf_scene *scene, hipStream_t stream);
 bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
@@ -468,14 +470,31 @@ void add_stats(bf_stats &a, const bf_stats &b);      // a += b (the chunks of a 
 bf_status guard_error(unsigned long long lost, unsigned long long refused);
 bf_status report_guards(const bf_scene *scene, unsigned long long lost, unsigned long long refused, const hipStream_t *async_on = nullptr);
 
-// ---- bf_mesh.cpp, called by the other three ----
+// ---- bf_mesh.cpp, called by the others ----
 // a device-form vertex update whose gather refused triangles: BF_ERR_DEVICE, once (wait: for the count; else only if it has landed)
 bf_status deform_report(const bf_scene *scene, bool wait);
 bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_normals, const char *who, const bf_geometry::MeshTopo **topo_out);
 // bf_scene_clone: if `src` has moved, `sc` (a copy of src's kernel arguments so far) takes its own snapshot of what src renders now
 bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc);
 
-// ---- bf_endpoints.cpp, called by the other three ----
+// ---- bf_mesh.cpp, called by bf_pose.cpp (a pose ends in a device-form vertex update, a posed batch in a deform batch) ----
+bf_status mesh_enter(const bf_scene *scene, hipStream_t stream);
+bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geometry::MeshTopo &tp, const float *pos_dev, const float *nrm_dev,
+                                 float bound, const float *box6, bool watch, hipStream_t stream);
+// slice(k0, kc, hs): the copy `hs` of the source table becomes that of renders k0 .. k0 + kc; run once per chunk of the arena
+using DeformSlice = std::function<bf_status(uint32_t k0, uint32_t kc, bfd::DDeformSrc *hs)>;
+bf_status deform_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, const std::vector<bfd::DDeformSrc> &src,
+                          float bound, const float *to_world, const std::vector<uint8_t> &moves, float *hist_dev, bf_path_record *records_dev,
+                          void *stream_, bf_stats *stats_out, const char *who, const DeformSlice &slice);
+bf_status vertex_scratch(float *&buf, size_t &cap, size_t bytes, hipStream_t stream, const char *who, const char *what);
+bf_status check_rigid_tables(const bf_scene *scene, const char *fn, uint32_t n_renders, uint32_t n_shapes, const float *to_world, uint8_t *moves);
+// the preamble of the motion, deform, skin and morph batches: before the lock, and first thing behind it
+bf_status check_batch_call(const char *fn, const char *kind, const bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const float *to_world,
+                           uint32_t n_shapes, const float *hist_dev);
+bool batch_ends_early(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, float *hist_dev,
+                      bf_path_record *records_dev, void *stream_, bf_stats *stats_out, bf_status *st);
+
+// ---- bf_endpoints.cpp, called by the others ----
 // the endpoint half of a description (every refusal it has for one), before any device work
 bf_status endpoints_flatten(const bf_scene_desc *desc, EndpointState::Image &img);
 // bf_scene_create: the element tables and the home block of `sc` from `img`, and its profile; *bytes grows by the block's size

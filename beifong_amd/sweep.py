@@ -195,6 +195,100 @@ def _classed(first, launch, classes):
     return lc, first.channels(lc) // first.channels(launch)
 
 
+def _every(rebuild_every):
+    if rebuild_every is not None and int(rebuild_every) < 1:
+        raise ValueError("rebuild_every must be a positive integer or None")
+    return None if rebuild_every is None else int(rebuild_every)
+
+
+def _transforms(transforms, n):
+    """The optional `transforms` of a sweep of n pulses as float32[n, n_shapes, 3, 4], or None."""
+    if transforms is None:
+        return None
+    xf = np.asarray(transforms, dtype=np.float32)
+    if xf.ndim != 4 or xf.shape[2:] != (3, 4) or xf.shape[0] != n:
+        raise ValueError(f"transforms must be [{n}, n_shapes, 3, 4], got {xf.shape}")
+    return xf
+
+
+def _meshes_of(sd, shapes):
+    for k in shapes:
+        if not 0 <= int(k) < len(sd.shapes) or sd.shapes[int(k)].type != capi.BF_SHAPE_MESH:
+            raise ValueError(f"shape {int(k)} is not a mesh of this scene")
+
+
+def _rest_pose(sd, shape):
+    """(positions [nv, 3], vertex normals [nv, 3] or None) of mesh `shape` as `sd` describes it: views of the description's arrays."""
+    s = sd.shapes[int(shape)]
+    return (np.ctypeslib.as_array(s.positions, shape=(s.n_vertices, 3)),
+            np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None)
+
+
+def _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch):
+    """The driver behind the motion, deform, skin and morph sweeps: `n` pulses of `sd` whose meshes stand at xf[k] (None: as posed)
+    on top of what the three callables make of pulse k.
+
+      prepare(first, dev)                          attaches to the first handle, or uploads, what the other two need, before the
+                                                   handle is cloned and before the streams wait for the current one;
+      pose(handle, k, stream)                      puts the handle's base at pulse k (None: the meshes only move by xf);
+      batch(handle, launch, c0, c1, cube_ptr, stream)   the one batched call that renders pulses c0 .. c1 into cube_ptr.
+
+    per_pulse: the pulses rotate over the handles, one pose (+ one bf_scene_transform_meshes) and one render each; else every handle
+    renders one contiguous group, in batches of `every` pulses with a rebuild between them if `every` is set.  Returns the cube
+    float32[n, f_bins * t_bins, 3], or float32[n, n_classes, f_bins * t_bins, 3] with classes."""
+    import torch
+    lib = lib or capi.load_library()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    n_streams = max(1, min(int(n_streams), n))
+    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
+    first = capi.Scene(sd, lib)
+    handles = [first]
+    try:
+        prepare(first, dev)
+        launch, n_classes = _classed(first, launch, classes)
+        _recompute(first, recompute_normals)
+        handles += [first.clone() for _ in range(n_streams - 1)]
+        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
+        for s in streams:           # the cube was zero-filled (and prepare's arrays written) on the current stream
+            s.wait_stream(torch.cuda.current_stream(dev))
+        updates = [0] * n_streams
+        if per_pulse:
+            for k in range(n):
+                j = k % n_streams
+                h, stream = handles[j], streams[j].cuda_stream
+                with torch.cuda.stream(streams[j]):
+                    if pose is not None:
+                        pose(h, k, stream)
+                    if xf is not None:
+                        h.transform_meshes(xf[k], stream=stream)
+                    updates[j] += 1
+                    if every and updates[j] % every == 0:
+                        h.rebuild_bvh(stream=stream)
+                    h.render_device(launch, cube[k].data_ptr(), stream=stream)
+        else:
+            bounds = np.linspace(0, n, n_streams + 1).astype(int)
+            for j in range(n_streams):
+                lo, hi = int(bounds[j]), int(bounds[j + 1])
+                h, stream = handles[j], streams[j].cuda_stream
+                for c0 in range(lo, hi, every or max(1, hi - lo)):
+                    c1 = min(hi, c0 + every) if every else hi
+                    with torch.cuda.stream(streams[j]):
+                        if every and c0 > lo:
+                            # the k-th frame since the last rebuild has just been rendered: the trees follow the meshes to it
+                            pose(h, c0 - 1, stream)
+                            h.rebuild_bvh(stream=stream)
+                        batch(h, launch, c0, c1, cube[c0].data_ptr(), stream)
+        for s in streams:
+            s.synchronize()
+        if pose is not None:
+            for h in handles:
+                h.sync()            # a vertex beyond the bound given or derived for it (there is none) would be reported here
+        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
+    finally:
+        for h in reversed(handles):
+            h.close()
+
+
 def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None, per_pulse=False, classes=None):
     """Coherent pulse sweep in which every mesh moves on its own: two targets at different speeds, a
     turning car.
@@ -213,42 +307,15 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
     classes=(shape_class, n_classes, miss_class): the returns split by the target each path hit first (BF_FLAG_CLASSES,
     Scene.set_classes); the cube is then float32[n_pulses, n_classes, f_bins * t_bins, 3] and range_doppler(cube[:, k]) the
     range-Doppler map of class k."""
-    import torch
     xf = np.asarray(transforms, dtype=np.float32)
     if xf.ndim != 4 or xf.shape[2:] != (3, 4):
         raise ValueError(f"transforms must be [n_pulses, n_shapes, 3, 4], got {xf.shape}")
-    n = xf.shape[0]
-    lib = lib or capi.load_library()
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    n_streams = max(1, min(int(n_streams), n))
-    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
-    first = capi.Scene(sd, lib)
-    handles = [first]
-    try:
-        launch, n_classes = _classed(first, launch, classes)
-        handles += [first.clone() for _ in range(n_streams - 1)]
-        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
-        for s in streams:           # the cube was zero-filled on the current stream
-            s.wait_stream(torch.cuda.current_stream(dev))
-        if per_pulse:
-            for k in range(n):
-                j = k % n_streams
-                with torch.cuda.stream(streams[j]):
-                    handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
-                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
-        else:
-            bounds = np.linspace(0, n, n_streams + 1).astype(int)
-            for j in range(n_streams):
-                lo, hi = int(bounds[j]), int(bounds[j + 1])
-                if hi > lo:
-                    with torch.cuda.stream(streams[j]):
-                        handles[j].render_motion_batch_device(launch, xf[lo:hi], cube[lo].data_ptr(), stream=streams[j].cuda_stream)
-        for s in streams:
-            s.synchronize()
-        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
-    finally:
-        for h in reversed(handles):
-            h.close()
+
+    def batch(h, lp, c0, c1, cube_ptr, stream):
+        h.render_motion_batch_device(lp, xf[c0:c1], cube_ptr, stream=stream)
+
+    return _version_sweep(sd, launch, xf.shape[0], xf, n_streams, per_pulse, None, classes, None, lib, device,
+                          lambda first, dev: None, None, batch)
 
 
 def _recompute(first, recompute_normals):
@@ -280,69 +347,27 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
     Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W); with
     classes=(shape_class, n_classes, miss_class), as in render_motion_sweep, float32[n_pulses, n_classes, f_bins * t_bins, 3]."""
     import torch
-    if rebuild_every is not None and int(rebuild_every) < 1:
-        raise ValueError("rebuild_every must be a positive integer or None")
-    every = None if rebuild_every is None else int(rebuild_every)
+    every = _every(rebuild_every)
     n, shapes, pos, _ = capi.deform_tables(positions, None, {k: int(sd.shapes[int(k)].n_vertices) for k in positions if 0 <= int(k) < len(sd.shapes)})
-    xf = None
-    if transforms is not None:
-        xf = np.asarray(transforms, dtype=np.float32)
-        if xf.ndim != 4 or xf.shape[2:] != (3, 4) or xf.shape[0] != n:
-            raise ValueError(f"transforms must be [{n}, n_shapes, 3, 4], got {xf.shape}")
+    xf = _transforms(transforms, n)
     bound = max(float(np.abs(p).max()) for p in pos)
     if not np.isfinite(bound):
         raise ValueError("positions: non-finite value")
     bound = max(bound, float(np.finfo(np.float32).tiny))
-    lib = lib or capi.load_library()
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    n_streams = max(1, min(int(n_streams), n))
-    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
-    first = capi.Scene(sd, lib)
-    handles = [first]
-    try:
-        launch, n_classes = _classed(first, launch, classes)
-        _recompute(first, recompute_normals)
-        handles += [first.clone() for _ in range(n_streams - 1)]
-        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
-        dpos = [torch.from_numpy(p).to(dev) for p in pos]
-        for s in streams:           # the cube and the vertex arrays were written on the current stream
-            s.wait_stream(torch.cuda.current_stream(dev))
-        updates = [0] * n_streams
-        if per_pulse:
-            for k in range(n):
-                j = k % n_streams
-                with torch.cuda.stream(streams[j]):
-                    for sh, d in zip(shapes, dpos):
-                        handles[j].update_vertices_device(int(sh), d[k].data_ptr(), None, bound, stream=streams[j].cuda_stream)
-                    if xf is not None:
-                        handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
-                    updates[j] += 1
-                    if every and updates[j] % every == 0:
-                        handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
-                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
-        else:
-            bounds = np.linspace(0, n, n_streams + 1).astype(int)
-            for j in range(n_streams):
-                lo, hi = int(bounds[j]), int(bounds[j + 1])
-                for c0 in range(lo, hi, every or max(1, hi - lo)):
-                    c1 = min(hi, c0 + every) if every else hi
-                    with torch.cuda.stream(streams[j]):
-                        if every and c0 > lo:
-                            # the k-th frame since the last rebuild has just been rendered: the trees follow the meshes to it
-                            for sh, d in zip(shapes, dpos):
-                                handles[j].update_vertices_device(int(sh), d[c0 - 1].data_ptr(), None, bound, stream=streams[j].cuda_stream)
-                            handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
-                        handles[j].render_deform_batch_device(launch, c1 - c0, {int(sh): d[c0].data_ptr() for sh, d in zip(shapes, dpos)},
-                                                              cube[c0].data_ptr(), bound, transforms=None if xf is None else xf[c0:c1],
-                                                              stream=streams[j].cuda_stream)
-        for s in streams:
-            s.synchronize()
-        for h in handles:
-            h.sync()                # a vertex beyond `bound` (there is none: it was computed above) would be reported here
-        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
-    finally:
-        for h in reversed(handles):
-            h.close()
+    dpos = []       # the vertex arrays on the device, uploaded once
+
+    def prepare(first, dev):
+        dpos.extend(torch.from_numpy(p).to(dev) for p in pos)
+
+    def pose(h, k, stream):
+        for sh, d in zip(shapes, dpos):
+            h.update_vertices_device(int(sh), d[k].data_ptr(), None, bound, stream=stream)
+
+    def batch(h, lp, c0, c1, cube_ptr, stream):
+        h.render_deform_batch_device(lp, c1 - c0, {int(sh): d[c0].data_ptr() for sh, d in zip(shapes, dpos)}, cube_ptr, bound,
+                                     transforms=None if xf is None else xf[c0:c1], stream=stream)
+
+    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch)
 
 
 def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None, classes=None, lib=None,
@@ -361,79 +386,29 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
     pulse; per-path results are the same.  rebuild_every, classes and recompute_normals (the normals of the POSED surface in
     place of the blended rest normals) as in render_deform_sweep.  Returns the cube
     float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3] with classes."""
-    import torch
-    if rebuild_every is not None and int(rebuild_every) < 1:
-        raise ValueError("rebuild_every must be a positive integer or None")
-    every = None if rebuild_every is None else int(rebuild_every)
+    every = _every(rebuild_every)
     n, shapes, tabs = capi.skin_tables(bones)
     skins = {int(k): v for k, v in skins.items()}
     if set(skins) != set(int(k) for k in shapes):
         raise ValueError(f"skins for shapes {sorted(skins)}, bones for shapes {sorted(int(k) for k in shapes)}")
-    for k in shapes:
-        if not 0 <= int(k) < len(sd.shapes) or sd.shapes[int(k)].type != capi.BF_SHAPE_MESH:
-            raise ValueError(f"shape {int(k)} is not a mesh of this scene")
-    xf = None
-    if transforms is not None:
-        xf = np.asarray(transforms, dtype=np.float32)
-        if xf.ndim != 4 or xf.shape[2:] != (3, 4) or xf.shape[0] != n:
-            raise ValueError(f"transforms must be [{n}, n_shapes, 3, 4], got {xf.shape}")
-    lib = lib or capi.load_library()
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    n_streams = max(1, min(int(n_streams), n))
-    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
-    first = capi.Scene(sd, lib)
-    handles = [first]
-    try:
+    _meshes_of(sd, shapes)
+    xf = _transforms(transforms, n)
+
+    def prepare(first, dev):
         for sh, tab in zip(shapes, tabs):
-            s = sd.shapes[int(sh)]
+            rest, rest_n = _rest_pose(sd, sh)
             index, weight = skins[int(sh)]
-            rest = np.ctypeslib.as_array(s.positions, shape=(s.n_vertices, 3))
-            rest_n = np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None
             first.set_skin(int(sh), tab.shape[1], rest, index, weight, rest_normals=rest_n)
-        launch, n_classes = _classed(first, launch, classes)
-        _recompute(first, recompute_normals)
-        handles += [first.clone() for _ in range(n_streams - 1)]
-        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
-        for s in streams:           # the cube was zero-filled on the current stream
-            s.wait_stream(torch.cuda.current_stream(dev))
-        updates = [0] * n_streams
 
-        def pose(h, k, stream):
-            for sh, tab in zip(shapes, tabs):
-                h.pose_skin(int(sh), tab[k], stream=stream)
+    def pose(h, k, stream):
+        for sh, tab in zip(shapes, tabs):
+            h.pose_skin(int(sh), tab[k], stream=stream)
 
-        if per_pulse:
-            for k in range(n):
-                j = k % n_streams
-                with torch.cuda.stream(streams[j]):
-                    pose(handles[j], k, streams[j].cuda_stream)
-                    if xf is not None:
-                        handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
-                    updates[j] += 1
-                    if every and updates[j] % every == 0:
-                        handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
-                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
-        else:
-            bounds = np.linspace(0, n, n_streams + 1).astype(int)
-            for j in range(n_streams):
-                lo, hi = int(bounds[j]), int(bounds[j + 1])
-                for c0 in range(lo, hi, every or max(1, hi - lo)):
-                    c1 = min(hi, c0 + every) if every else hi
-                    with torch.cuda.stream(streams[j]):
-                        if every and c0 > lo:
-                            # the k-th frame since the last rebuild has just been rendered: the trees follow the meshes to it
-                            pose(handles[j], c0 - 1, streams[j].cuda_stream)
-                            handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
-                        handles[j].render_skin_batch_device(launch, {int(sh): tab[c0:c1] for sh, tab in zip(shapes, tabs)}, cube[c0].data_ptr(),
-                                                            transforms=None if xf is None else xf[c0:c1], stream=streams[j].cuda_stream)
-        for s in streams:
-            s.synchronize()
-        for h in handles:
-            h.sync()                # a posed vertex beyond the bound the library derived (there is none) would be reported here
-        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
-    finally:
-        for h in reversed(handles):
-            h.close()
+    def batch(h, lp, c0, c1, cube_ptr, stream):
+        h.render_skin_batch_device(lp, {int(sh): tab[c0:c1] for sh, tab in zip(shapes, tabs)}, cube_ptr,
+                                   transforms=None if xf is None else xf[c0:c1], stream=stream)
+
+    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch)
 
 
 def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None,
@@ -456,10 +431,7 @@ def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, tran
     render per pulse; per-path results are the same.  rebuild_every, classes and recompute_normals as in render_skin_sweep.
     Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3]
     with classes."""
-    import torch
-    if rebuild_every is not None and int(rebuild_every) < 1:
-        raise ValueError("rebuild_every must be a positive integer or None")
-    every = None if rebuild_every is None else int(rebuild_every)
+    every = _every(rebuild_every)
     n, shapes, tabs = capi.morph_tables(weights)
     morphs = {int(k): (v if isinstance(v, tuple) else (v, None)) for k, v in morphs.items()}
     if set(morphs) != set(int(k) for k in shapes):
@@ -472,76 +444,29 @@ def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, tran
         if set(skins) != set(btabs) or not set(skins) <= set(morphs) or nb != n:
             raise ValueError(f"skins for shapes {sorted(skins)}, bones for shapes {sorted(btabs)} over {nb} pulses, morphs for shapes "
                              f"{sorted(morphs)} over {n}")
-    for k in shapes:
-        if not 0 <= int(k) < len(sd.shapes) or sd.shapes[int(k)].type != capi.BF_SHAPE_MESH:
-            raise ValueError(f"shape {int(k)} is not a mesh of this scene")
-    xf = None
-    if transforms is not None:
-        xf = np.asarray(transforms, dtype=np.float32)
-        if xf.ndim != 4 or xf.shape[2:] != (3, 4) or xf.shape[0] != n:
-            raise ValueError(f"transforms must be [{n}, n_shapes, 3, 4], got {xf.shape}")
-    lib = lib or capi.load_library()
-    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-    n_streams = max(1, min(int(n_streams), n))
-    streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
-    first = capi.Scene(sd, lib)
-    handles = [first]
-    try:
+    _meshes_of(sd, shapes)
+    xf = _transforms(transforms, n)
+
+    def prepare(first, dev):
         for sh, tab in zip(shapes, tabs):
-            s = sd.shapes[int(sh)]
-            rest = np.ctypeslib.as_array(s.positions, shape=(s.n_vertices, 3))
-            rest_n = np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None
+            rest, rest_n = _rest_pose(sd, sh)
             dp, dn = morphs[int(sh)]
             first.set_morph(int(sh), tab.shape[1], rest, dp, rest_normals=rest_n, delta_normals=dn)
             if int(sh) in skins:
                 index, weight = skins[int(sh)]
                 first.set_skin(int(sh), btabs[int(sh)].shape[1], rest, index, weight, rest_normals=rest_n)
-        launch, n_classes = _classed(first, launch, classes)
-        _recompute(first, recompute_normals)
-        handles += [first.clone() for _ in range(n_streams - 1)]
-        cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
-        for s in streams:           # the cube was zero-filled on the current stream
-            s.wait_stream(torch.cuda.current_stream(dev))
-        updates = [0] * n_streams
 
-        def pose(h, k, stream):
-            for sh, tab in zip(shapes, tabs):
-                b = btabs.get(int(sh))
-                h.pose_morph(int(sh), tab[k], bones=None if b is None else b[k], stream=stream)
+    def pose(h, k, stream):
+        for sh, tab in zip(shapes, tabs):
+            b = btabs.get(int(sh))
+            h.pose_morph(int(sh), tab[k], bones=None if b is None else b[k], stream=stream)
 
-        if per_pulse:
-            for k in range(n):
-                j = k % n_streams
-                with torch.cuda.stream(streams[j]):
-                    pose(handles[j], k, streams[j].cuda_stream)
-                    if xf is not None:
-                        handles[j].transform_meshes(xf[k], stream=streams[j].cuda_stream)
-                    updates[j] += 1
-                    if every and updates[j] % every == 0:
-                        handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
-                    handles[j].render_device(launch, cube[k].data_ptr(), stream=streams[j].cuda_stream)
-        else:
-            bounds = np.linspace(0, n, n_streams + 1).astype(int)
-            for j in range(n_streams):
-                lo, hi = int(bounds[j]), int(bounds[j + 1])
-                for c0 in range(lo, hi, every or max(1, hi - lo)):
-                    c1 = min(hi, c0 + every) if every else hi
-                    with torch.cuda.stream(streams[j]):
-                        if every and c0 > lo:
-                            # the k-th frame since the last rebuild has just been rendered: the trees follow the meshes to it
-                            pose(handles[j], c0 - 1, streams[j].cuda_stream)
-                            handles[j].rebuild_bvh(stream=streams[j].cuda_stream)
-                        handles[j].render_morph_batch_device(launch, {int(sh): tab[c0:c1] for sh, tab in zip(shapes, tabs)}, cube[c0].data_ptr(),
-                                                             bones={k: t[c0:c1] for k, t in btabs.items()} or None,
-                                                             transforms=None if xf is None else xf[c0:c1], stream=streams[j].cuda_stream)
-        for s in streams:
-            s.synchronize()
-        for h in handles:
-            h.sync()                # a posed vertex beyond the bound the library derived (there is none) would be reported here
-        return cube.cpu().numpy().reshape((n, n_classes, -1, 3) if n_classes else (n, -1, 3))
-    finally:
-        for h in reversed(handles):
-            h.close()
+    def batch(h, lp, c0, c1, cube_ptr, stream):
+        h.render_morph_batch_device(lp, {int(sh): tab[c0:c1] for sh, tab in zip(shapes, tabs)}, cube_ptr,
+                                    bones={k: t[c0:c1] for k, t in btabs.items()} or None,
+                                    transforms=None if xf is None else xf[c0:c1], stream=stream)
+
+    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch)
 
 
 def range_doppler(cube, window=True):
