@@ -37,17 +37,6 @@ const char *ncclGetErrorString(ncclResult_t result);
 
 #include "bf_scene.h"
 
-extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y);
-extern "C" hipError_t bfk_launch_trace(const bfd::DScene *sc, uint64_t n, const float *rays, int any_hit, float *out_t,
-                                       uint32_t *out_prim, uint32_t *out_shape, float *out_uv, uint8_t *out_hit,
-                                       float *out_si, hipStream_t stream);
-// plugin-level queries (bf_kernels.hip: bf_query_kernel, bf_microfacet_kernel); op 0 BSDF eval + pdf, 1 BSDF sample, 2 emitter
-// sample_direction, 3 sensor sample_ray
-extern "C" hipError_t bfk_launch_query(int op, const bfd::DScene *sc, uint64_t n, const uint32_t *materials, uint32_t emitter,
-                                       const float *in, float *out, hipStream_t stream);
-extern "C" hipError_t bfk_launch_microfacet(int op, uint32_t type, float alpha_u, float alpha_v, uint32_t sample_visible, uint64_t n,
-                                            const float *in, float *out, hipStream_t stream);
-
 
 static thread_local std::string g_err;
 
@@ -539,7 +528,6 @@ bf_status bf_scene_clone(const bf_scene *src, bf_scene **out) {
 
 /* developer probe (tools/fetch_probe.py): `reps` launches of the gather pattern `mode` over a table of 2^log2_rows 16-byte rows
    (a second buffer of the same size is streamed in between, so every launch starts with a cold L2); returns the mean ms */
-extern "C" hipError_t bfk_gather_probe(int mode, const float4 *table, uint32_t n_rows, float4 *out, hipStream_t stream);
 bf_status bfdbg_gather_probe(int mode, uint32_t log2_rows, uint32_t reps, float *ms_out) {
     if (mode < 0 || mode > 2 || log2_rows < 10 || log2_rows > 28 || reps == 0) return fail(BF_ERR_INVALID, "bfdbg_gather_probe: bad arguments");
     const uint32_t n = 1u << log2_rows;

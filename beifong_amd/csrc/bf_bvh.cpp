@@ -477,7 +477,7 @@ void collapse_bvh16(const BVH &in, BVH16 &out) {
 }
 
 // Quantisation of one four-wide node (bf_bvh.h: Node4Q).  Plain fp32 operations in a fixed order — the device repeats
-// them when it re-quantises the tree after a mesh translation or a rigid-motion refit (bf_kernels.hip: quantise_node4_dev).
+// them when it re-quantises the tree after a mesh translation or a rigid-motion refit (bf_geom.hip: quantise_node4_dev).
 void quantise_node4(const Node4 &in, Node4Q &out) {
     const float inf = std::numeric_limits<float>::infinity();
     float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};

@@ -8,8 +8,6 @@
 #include <cstddef>
 #include <cstring>
 
-extern "C" float bfk_host_cos(float x);
-
 namespace {
 void m34(const float *m16, float *out12) { std::memcpy(out12, m16, 12 * sizeof(float)); }
 

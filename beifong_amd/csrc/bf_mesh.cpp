@@ -1,5 +1,5 @@
 // "The meshes of this handle have moved" (DESIGN.md 6d): translations, rigid transforms, vertex updates, the rebuild of both trees
-// and the batches with a geometry version per render.  State: bf_scene::mesh (bf_scene.h); kernels: bf_kernels.hip, bf_build.hip.
+// and the batches with a geometry version per render.  State: bf_scene::mesh (bf_scene.h); kernels: bf_geom.hip, bf_build.hip.
 // Skins and morph targets, which end in a vertex update or a deform batch of this file: bf_pose.cpp.
 #include "bf_scene.h"
 

@@ -6,6 +6,9 @@
 // inline template or __host__ __device__ helper of the same mangled name in both would be merged by the linker, and one
 // mode would silently run the other's code.  The fast build therefore puts everything into the inline namespace
 // bfd::fast (the structs keep their layouts: same source text) and renames its launchers with a _fast suffix.
+// What is built how (Makefile): bf_kernels.hip (the one-kernel render and the tail) and bf_wavefront.hip (wf_shade, wf_trace) in
+// both modes; bf_geom.hip (the kernels that move geometry), bf_query.hip (ray and plugin queries, probes), bf_build.hip and
+// bf_converge.hip once, exact: what they compute is shared by both modes.  bf_launch.h declares every launcher of the first four.
 #pragma once
 
 #ifndef BF_FAST

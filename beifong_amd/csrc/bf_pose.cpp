@@ -1,7 +1,7 @@
 // Meshes posed by a few numbers per render: skins (a pose is n_bones 3x4 matrices) and morph targets (a pose is n_targets
 // weights, and the bones of a skin behind them).  bf_skin_vertices_kernel or bf_morph_vertices_kernel computes the vertices into the
 // handle's scratch, and from there on a pose is a device-form vertex update and a batch a device-form deform batch of bf_mesh.cpp, with the
-// bound on the coordinates derived here.  State: MeshState::skins / morphs / pose_vtx (bf_scene.h); kernels: bf_kernels.hip.
+// bound on the coordinates derived here.  State: MeshState::skins / morphs / pose_vtx (bf_scene.h); kernels: bf_geom.hip.
 #include "bf_scene.h"
 
 #include <algorithm>

@@ -10,28 +10,6 @@
 #include <limits>
 #include <vector>
 
-// The launchers of bf_kernels.hip / bf_wavefront.hip a render goes through, once per build of the kernels: the exact one (no suffix),
-// the fast-arithmetic one (_fast, BF_FLAG_FAST: bf_ns.h), the second-moment variants (_moment, BF_FLAG_MOMENT; bf_device.h: kMoment;
-// exact build only, same wf_trace) and the class variants (_class, BF_FLAG_CLASSES; bf_device.h: kClass; likewise)
-#define BF_LAUNCHERS(sfx)                                                                                                                       \
-    extern "C" hipError_t bfk_launch_render##sfx(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,         \
-                                                 unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream); \
-    extern "C" hipError_t bfk_wf_shade##sfx(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,           \
-                                            float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes, hipStream_t stream,       \
-                                            int waves);                                                                                         \
-    extern "C" hipError_t bfk_launch_tail##sfx(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, uint32_t n_slots, \
-                                               float *g_hist, bf_path_record *records, int stats, size_t lds_bytes, hipStream_t stream,        \
-                                               int tail_waves, unsigned spread, unsigned block_cap);
-BF_LAUNCHERS()
-BF_LAUNCHERS(_fast)
-BF_LAUNCHERS(_moment)
-BF_LAUNCHERS(_class)
-BF_LAUNCHERS(_aov)      // (_aov, BF_FLAG_AOV; bf_device.h: kAov; exact build only, same wf_trace)
-#undef BF_LAUNCHERS
-extern "C" hipError_t bfk_wf_trace(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
-extern "C" hipError_t bfk_wf_trace_fast(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
-extern "C" hipError_t bfk_roll_set(bfd::DRoll *ring, float4 *offsets, uint32_t idx, const bfd::DRoll *d, const float *offset3, hipStream_t stream);
-
 namespace {
 // the kernels one render runs: the exact build, the fast-arithmetic one (BF_FLAG_FAST), the second-moment variants (BF_FLAG_MOMENT) or
 // the class variants (BF_FLAG_CLASSES)

@@ -12,35 +12,8 @@
 #include "bf_bvh.h"
 #include "bf_converge.h"
 #include "bf_device.h"
+#include "bf_launch.h"
 #include "bf_wavefront.h"
-
-// the launchers of bf_kernels.hip that move geometry (bf_mesh.cpp, bf_pose.cpp)
-extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, uint32_t n_tri_rows, const float4 *nodes0,
-                                           float4 *nodes, float4 *qnodes, uint32_t n_nodes, const float4 *wnodes0, float4 *wnodes,
-                                           uint32_t n_wchildren, const float *d, hipStream_t stream);
-extern "C" hipError_t bfk_launch_deform_tris(const uint4 *corners, const bfd::DDeformSrc *src, const float4 *tris0, float4 *tris, const float4 *nrm0,
-                                             float4 *nrm, uint32_t n_tris, const float *xf, uint32_t n_versions, uint64_t vstride,
-                                             uint32_t xf_stride, float bound, uint32_t *bad, hipStream_t stream);
-extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
-                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes,
-                                       const uint32_t *lvl16, const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad,
-                                       uint32_t n_versions, uint64_t vstride, hipStream_t stream);
-extern "C" hipError_t bfk_launch_rigid(const float4 *tris0, float4 *tris, const float4 *nrm0, float4 *nrm, uint32_t n_tris,
-                                       const float *xf, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
-                                       const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes, const uint32_t *lvl16,
-                                       const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad, uint32_t n_versions,
-                                       uint64_t vstride, uint32_t xf_stride, hipStream_t stream);
-
-extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const float *rest_nrm, const uint4 *index, const float4 *weight, uint32_t nv,
-                                               const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
-                                               hipStream_t stream);
-extern "C" hipError_t bfk_launch_morph_vertices(const float *rest_pos, const float *rest_nrm, const float *dpos, const float *dnrm, uint32_t nv,
-                                                uint32_t n_targets, const float *wts, const uint4 *index, const float4 *weight,
-                                                const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
-                                                hipStream_t stream);
-extern "C" hipError_t bfk_launch_vertex_normals(const uint32_t *offset, const uint4 *entries, uint32_t nv, const float *pos, float *nrm,
-                                                uint32_t n_versions, hipStream_t stream);
-extern "C" void bfk_host_vertex_normals(uint32_t nv, const float *pos, uint32_t nf, const uint32_t *idx, float *out);
 
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \

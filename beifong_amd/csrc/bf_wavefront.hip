@@ -23,6 +23,7 @@
 // freq_of).  Results are bit-identical per path to the one-kernel variant and to the oracle: same draws, same
 // operations in the same order.
 #include "bf_path_logic.h"
+#include "bf_launch.h"
 
 BF_NS_BEGIN
 

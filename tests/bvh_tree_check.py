@@ -9,7 +9,7 @@ tests/test_bvh_host.py states (binary depth <= 31, four-wide stack <= 93, sixtee
 For what a translate, a refit or a requantise writes (tests/test_gpu_refit_trees.py) three more checks, each a restatement of a
 documented rule and none with a tolerance of its own:
   check_padding        every used box equals, bit for bit, the exact union of the triangle rows beneath it padded by the rule of the
-                       call that wrote it (bf_kernels.hip: refit_pad / bf_translate_kernel, every operation a singly rounded float32
+                       call that wrote it (bf_geom.hip: refit_pad / bf_translate_kernel, every operation a singly rounded float32
                        one, which numpy float32 reproduces); unused slots are exactly (+inf, -inf)
   check_quantised      the Node4Q array against the fp32 nodes, by the contract tests/test_bvh_host.py states for the host quantiser
   origin_scale_bounds  a float64 bracket, from the description and the poses a handle was given, for the ray-origin bound the boxes
@@ -186,7 +186,7 @@ def child_unions(nodes, rows, width):
 
 
 def refit_pad(ulo, uhi, origin_scale):
-    """bf_kernels.hip: refit_pad == bf_bvh.cpp: Builder::pad of an unpadded box [..., 3], in float32, every operation rounded singly:
+    """bf_geom.hip: refit_pad == bf_bvh.cpp: Builder::pad of an unpadded box [..., 3], in float32, every operation rounded singly:
     m = max over axes of max(hi - lo, |lo|, |hi|);  e = 2e-6f m + (2e-7f origin_scale) + 1e-30f;  (lo - e, hi + e)"""
     ulo, uhi = np.asarray(ulo, f32), np.asarray(uhi, f32)
     with np.errstate(invalid="ignore", over="ignore"):
@@ -197,7 +197,7 @@ def refit_pad(ulo, uhi, origin_scale):
 
 
 def translate_pad(lo0, hi0, d):
-    """bf_kernels.hip: bf_translate_kernel's box rule, in float32: lo' = fl(lo0 + d), hi' = fl(hi0 + d),
+    """bf_geom.hip: bf_translate_kernel's box rule, in float32: lo' = fl(lo0 + d), hi' = fl(hi0 + d),
     e = fl(2.4e-7f max(|lo'|, |hi'|)) per axis; (lo' - e, hi' + e)"""
     d = np.asarray(d, f32).reshape(3)
     with np.errstate(invalid="ignore"):

@@ -1,6 +1,6 @@
 """What does rocprofv3's FETCH_SIZE count for THIS engine's access patterns?  (MI355X_MICROARCH.md: the x2
 correction is measured for wide coalesced streaming reads only.)  Three kernels read a 64 MiB table of 16-byte rows exactly
-once per launch (bf_kernels.hip: bf_gather_probe<MODE>): 0 streaming, 1 scattered rows (every row once, a line's eight rows by
+once per launch (bf_query.hip: bf_gather_probe<MODE>): 0 streaming, 1 scattered rows (every row once, a line's eight rows by
 eight different waves), 2 one row per 128-byte line.  Run it directly under the profiler, once per counter set:
 
   rocprofv3 --pmc FETCH_SIZE -d OUT/f -o c -- python3 tools/fetch_probe.py
