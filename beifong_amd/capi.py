@@ -31,6 +31,7 @@ BF_MAX_CLASSES = 256
 BF_FLAG_AOV = 2048
 BF_MAX_AOVS = 16
 BF_NORMALS_GIVEN, BF_NORMALS_RECOMPUTE = range(2)
+BF_SKIN_LINEAR, BF_SKIN_DUAL_QUATERNION = range(2)
 (BF_AOV_DEPTH, BF_AOV_POSITION, BF_AOV_UV, BF_AOV_GEO_NORMAL, BF_AOV_SH_NORMAL, BF_AOV_DP_DU, BF_AOV_DP_DV, BF_AOV_DUV_DX,
  BF_AOV_DUV_DY, BF_AOV_TYPES) = range(10)
 # the reference's type names (aov.cpp:96-127) in BF_AOV_* order, and the floats of each
@@ -162,6 +163,7 @@ EXPORTED_SYMBOLS = [
     "bf_render_batch_device", "bf_render_batch", "bf_render_motion_batch_device", "bf_render_motion_batch",
     "bf_scene_update_vertices", "bf_scene_update_vertices_device", "bf_render_deform_batch_device", "bf_render_deform_batch",
     "bf_scene_set_skin", "bf_scene_pose_skin", "bf_render_skin_batch_device", "bf_render_skin_batch",
+    "bf_scene_set_skin_mode", "bf_scene_get_skin_mode", "bf_bone_dual_quaternions",
     "bf_scene_set_morph", "bf_scene_pose_morph", "bf_render_morph_batch_device", "bf_render_morph_batch",
     "bf_vertex_normals", "bf_scene_set_normal_mode", "bf_scene_get_normal_mode",
     "bf_scene_rebuild_bvh", "bf_scene_read_bvh",
@@ -247,6 +249,9 @@ def load_library(path=None):
                                                 C.POINTER(bf_stats)]
     lib.bf_render_skin_batch.argtypes = [vp, C.POINTER(bf_launch), C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.POINTER(bf_stats)]
     lib.bf_vertex_normals.argtypes = [C.c_uint32, vp, C.c_uint32, vp, vp]
+    lib.bf_scene_set_skin_mode.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.bf_scene_get_skin_mode.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.bf_bone_dual_quaternions.argtypes = [C.c_uint32, vp, vp]
     lib.bf_scene_set_normal_mode.argtypes = [vp, C.c_uint32, C.c_uint32]
     lib.bf_scene_get_normal_mode.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.bf_scene_set_morph.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
@@ -337,6 +342,19 @@ def vertex_normals(positions, faces, lib=None):
     out = np.empty_like(p)
     lib = lib or load_library()
     check(lib, lib.bf_vertex_normals(p.shape[0], _ptr(p), f.shape[0], _ptr(f), _ptr(out)), "bf_vertex_normals")
+    return out
+
+
+def bone_dual_quaternions(bones, lib=None):
+    """bf_bone_dual_quaternions: the conversion the library applies to a bone table of a shape in BF_SKIN_DUAL_QUATERNION, on the
+    host (include/beifong_hip.h; motion.bone_dual_quaternions is its numpy restatement, bit for bit).  bones float32[n_bones, 3, 4],
+    every one rigid -> float32[n_bones, 8]: (w, x, y, z) of the rotation, then of the dual part.  No device."""
+    b = np.ascontiguousarray(bones, dtype=np.float32)
+    if b.ndim != 3 or b.shape[1:] != (3, 4):
+        raise ValueError(f"bones must be [n_bones, 3, 4], got {b.shape}")
+    out = np.empty((b.shape[0], 8), np.float32)
+    lib = lib or load_library()
+    check(lib, lib.bf_bone_dual_quaternions(b.shape[0], _ptr(b), _ptr(out)), "bf_bone_dual_quaternions")
     return out
 
 
@@ -1054,6 +1072,24 @@ class Scene:
             raise ValueError(f"shape index {shape}")
         mode = C.c_uint32(0)
         check(self.lib, self.lib.bf_scene_get_normal_mode(self.handle, shape, C.byref(mode)), "bf_scene_get_normal_mode")
+        return int(mode.value)
+
+    def set_skin_mode(self, shape, mode):
+        """bf_scene_set_skin_mode: BF_SKIN_DUAL_QUATERNION makes every later call that takes bones for mesh shape `shape` blend them
+        as unit dual quaternions (motion.apply_skin_dq's arithmetic; the bones must then be rigid); BF_SKIN_LINEAR (the default) is
+        motion.apply_skin.  Nothing moves until the next pose."""
+        shape, mode = int(shape), int(mode)
+        if shape < 0 or mode < 0:
+            raise ValueError(f"shape index {shape}, mode {mode}")
+        check(self.lib, self.lib.bf_scene_set_skin_mode(self.handle, shape, mode), "bf_scene_set_skin_mode")
+
+    def skin_mode(self, shape):
+        """bf_scene_get_skin_mode: BF_SKIN_LINEAR or BF_SKIN_DUAL_QUATERNION of mesh shape `shape` on this handle."""
+        shape = int(shape)
+        if shape < 0:
+            raise ValueError(f"shape index {shape}")
+        mode = C.c_uint32(0)
+        check(self.lib, self.lib.bf_scene_get_skin_mode(self.handle, shape, C.byref(mode)), "bf_scene_get_skin_mode")
         return int(mode.value)
 
     def _version_args(self, n_renders, transforms, seeds):

@@ -488,24 +488,136 @@ extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const floa
 }
 
 BF_NS_BEGIN
+// Dual-quaternion skinning (BF_SKIN_DUAL_QUATERNION): bf_skin_vertices_kernel's layout with another blend.  The bone
+// table holds one unit dual quaternion per bone, 8 floats (real w x y z, dual w x y z: bf_pose.cpp converts the caller's 3x4 on the
+// host), at most 256: 8 KiB of LDS, read as two 16-byte rows per slot.  fp32, every operation rounded (no FMA, IEEE division and
+// square root; the square root is the builtin for vn_sqrt's reason, below).  Per vertex, with slots k = 0..3:
+//   p   = the slot of largest weight, the first among equals;   s_k = -1 if dot(D_k.real, D_p.real) < 0, else +1
+//   b   = ((s0 w0 D_0 + s1 w1 D_1) + s2 w2 D_2) + s3 w3 D_3     per component over all eight, all four terms always evaluated
+//   r   = b.real / |b.real|,  e = b.dual / |b.real|             (dot and |.|^2 are ((a0 b0 + a1 b1) + a2 b2) + a3 b3)
+//   rotate(r, v) = (v + rw t) + cross(r.xyz, t)  with  t = 2 cross(r.xyz, v),   cross(a, b).x = fl(fl(ay bz) - fl(az by))
+//   x'  = rotate(r, x) + 2 ((rw e.xyz - ew r.xyz) + cross(r.xyz, e.xyz))
+//   n'  = rotate(r, n)                                          no translation, not renormalised
+// s_k w_k is exact (a sign), and so are the products by 2.
+struct DqBlend {
+    float r[4], e[4];
+};
+BF_DEV float dq_dot4(float4 a, float4 b) {
+    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fmul_rn(a.z, b.z)), __fmul_rn(a.w, b.w));
+}
+BF_DEV float dq_sum4(const float c[4], float d0, float d1, float d2, float d3) {
+    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(c[0], d0), __fmul_rn(c[1], d1)), __fmul_rn(c[2], d2)), __fmul_rn(c[3], d3));
+}
+BF_DEV DqBlend dq_blend(const float4 *sq, uint4 ix, float4 w) {
+    const float4 R0 = sq[2u * ix.x], R1 = sq[2u * ix.y], R2 = sq[2u * ix.z], R3 = sq[2u * ix.w];
+    const float4 E0 = sq[2u * ix.x + 1u], E1 = sq[2u * ix.y + 1u], E2 = sq[2u * ix.z + 1u], E3 = sq[2u * ix.w + 1u];
+    float4 P = R0;
+    float wp = w.x;
+    if (w.y > wp) P = R1, wp = w.y;
+    if (w.z > wp) P = R2, wp = w.z;
+    if (w.w > wp) P = R3, wp = w.w;
+    const float c[4] = {dq_dot4(R0, P) < 0.f ? -w.x : w.x, dq_dot4(R1, P) < 0.f ? -w.y : w.y, dq_dot4(R2, P) < 0.f ? -w.z : w.z,
+                        dq_dot4(R3, P) < 0.f ? -w.w : w.w};
+    const float4 br = make_float4(dq_sum4(c, R0.x, R1.x, R2.x, R3.x), dq_sum4(c, R0.y, R1.y, R2.y, R3.y), dq_sum4(c, R0.z, R1.z, R2.z, R3.z),
+                                  dq_sum4(c, R0.w, R1.w, R2.w, R3.w));
+    const float bd[4] = {dq_sum4(c, E0.x, E1.x, E2.x, E3.x), dq_sum4(c, E0.y, E1.y, E2.y, E3.y), dq_sum4(c, E0.z, E1.z, E2.z, E3.z),
+                         dq_sum4(c, E0.w, E1.w, E2.w, E3.w)};
+    const float len = __builtin_sqrtf(dq_dot4(br, br));
+    DqBlend q;
+    q.r[0] = __fdiv_rn(br.x, len), q.r[1] = __fdiv_rn(br.y, len), q.r[2] = __fdiv_rn(br.z, len), q.r[3] = __fdiv_rn(br.w, len);
+    for (int j = 0; j < 4; ++j) q.e[j] = __fdiv_rn(bd[j], len);
+    return q;
+}
+// cross(a, b), each component fl(fl(ay bz) - fl(az by))
+BF_DEV float3 dq_cross(float ax, float ay, float az, float bx, float by, float bz) {
+    return make_float3(__fsub_rn(__fmul_rn(ay, bz), __fmul_rn(az, by)), __fsub_rn(__fmul_rn(az, bx), __fmul_rn(ax, bz)),
+                       __fsub_rn(__fmul_rn(ax, by), __fmul_rn(ay, bx)));
+}
+BF_DEV float3 dq_rotate(const DqBlend &q, float x, float y, float z) {
+    const float3 h = dq_cross(q.r[1], q.r[2], q.r[3], x, y, z);
+    const float3 t = make_float3(__fmul_rn(2.f, h.x), __fmul_rn(2.f, h.y), __fmul_rn(2.f, h.z));
+    const float3 u = dq_cross(q.r[1], q.r[2], q.r[3], t.x, t.y, t.z);
+    return make_float3(__fadd_rn(__fadd_rn(x, __fmul_rn(q.r[0], t.x)), u.x), __fadd_rn(__fadd_rn(y, __fmul_rn(q.r[0], t.y)), u.y),
+                       __fadd_rn(__fadd_rn(z, __fmul_rn(q.r[0], t.z)), u.z));
+}
+BF_DEV float3 dq_point(const DqBlend &q, float x, float y, float z) {
+    const float3 p = dq_rotate(q, x, y, z), u = dq_cross(q.r[1], q.r[2], q.r[3], q.e[1], q.e[2], q.e[3]);
+    const float tx = __fmul_rn(2.f, __fadd_rn(__fsub_rn(__fmul_rn(q.r[0], q.e[1]), __fmul_rn(q.e[0], q.r[1])), u.x));
+    const float ty = __fmul_rn(2.f, __fadd_rn(__fsub_rn(__fmul_rn(q.r[0], q.e[2]), __fmul_rn(q.e[0], q.r[2])), u.y));
+    const float tz = __fmul_rn(2.f, __fadd_rn(__fsub_rn(__fmul_rn(q.r[0], q.e[3]), __fmul_rn(q.e[0], q.r[3])), u.z));
+    return make_float3(__fadd_rn(p.x, tx), __fadd_rn(p.y, ty), __fadd_rn(p.z, tz));
+}
+// the bone table of version `ver` into LDS: n_bones rows of two float4 (the staged table is 16-byte aligned: bf_pose.cpp)
+BF_DEV void dq_table_load(float4 *sq, const float *bones, uint32_t n_bones, uint32_t bone_stride, uint32_t ver) {
+    const float4 *b = reinterpret_cast<const float4 *>(bones + (size_t) bone_stride * ver);
+    for (uint32_t i = threadIdx.x; i < n_bones * 2u; i += 256u) sq[i] = b[i];
+}
+
+// bf_skin_vertices_kernel with the blend above: `bones` is [n_versions][n_bones][8], bone_stride = 8 n_bones.  A lane past the end
+// holds index 0 and weight 0 and leaves at the barrier's far side; control flow is uniform up to it.
+__global__ __launch_bounds__(256) void bf_skin_vertices_dq_kernel(const float *__restrict__ rest_pos, const float *__restrict__ rest_nrm,
+                                                                  const uint4 *__restrict__ index, const float4 *__restrict__ weight, uint32_t nv,
+                                                                  const float *__restrict__ bones, uint32_t n_bones, uint32_t bone_stride,
+                                                                  float *__restrict__ pos, float *__restrict__ nrm, uint64_t vstride) {
+    __shared__ float4 sq[256 * 2];
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x, ver = blockIdx.y;
+    const bool live = v < nv;
+    uint4 ix = make_uint4(0u, 0u, 0u, 0u);
+    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+    float x[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
+    if (live) {
+        ix = index[v];        // one 16-byte load each
+        w = weight[v];
+        for (int c = 0; c < 3; ++c) x[c] = rest_pos[3u * (size_t) v + c];
+        if (rest_nrm)
+            for (int c = 0; c < 3; ++c) n[c] = rest_nrm[3u * (size_t) v + c];
+    }
+    dq_table_load(sq, bones, n_bones, bone_stride, ver);
+    __syncthreads();
+    if (!live) return;
+    const size_t o = (size_t) vstride * ver + 3u * (size_t) v;
+    const DqBlend q = dq_blend(sq, ix, w);
+    const float3 p = dq_point(q, x[0], x[1], x[2]);
+    pos[o] = p.x, pos[o + 1] = p.y, pos[o + 2] = p.z;
+    if (rest_nrm) {
+        const float3 r = dq_rotate(q, n[0], n[1], n[2]);
+        nrm[o] = r.x, nrm[o + 1] = r.y, nrm[o + 2] = r.z;
+    }
+}
+BF_NS_END  // namespace bfd
+
+// bfk_launch_skin_vertices for a shape in BF_SKIN_DUAL_QUATERNION: bones [n_versions][n_bones][8] (device, 16-byte aligned)
+extern "C" hipError_t bfk_launch_skin_vertices_dq(const float *rest_pos, const float *rest_nrm, const uint4 *index, const float4 *weight,
+                                                  uint32_t nv, const float *bones, uint32_t n_bones, float *pos, float *nrm,
+                                                  uint32_t n_versions, hipStream_t stream) {
+    if (nv == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u || n_bones == 0 || n_bones > 256u || ((uintptr_t) bones & 15u)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bfd::bf_skin_vertices_dq_kernel, dim3((nv + 255u) / 256u, n_versions), dim3(256), 0, stream, rest_pos, rest_nrm, index,
+                       weight, nv, bones, n_bones, n_bones * 8u, pos, nrm, (uint64_t) 3u * nv);
+    return hipGetLastError();
+}
+
+BF_NS_BEGIN
 // bf_scene_pose_morph / bf_render_morph_batch_device: morph targets (blend shapes) of one mesh shape, and the skin
 // behind them in the same registers.  One thread per vertex, grid y = version: version v reads its n_targets weights `n_targets`
 // floats further (and its bone table `bone_stride` floats further) and writes its vertices `vstride` floats further.
 //   p = rest;  for k = 0 .. n_targets-1 in increasing k:  p_c = fl(p_c + fl(w_k d_k,c))    per coordinate, no FMA
 //   n likewise from the rest normal and the normal deltas (dnrm == nullptr: the rest normal, bit for bit), not renormalised
-//   SKIN: (p, n) then go through skin_blend in place of the skin's own rest arrays
+//   SKIN: (p, n) then go through skin_blend (1, BF_SKIN_LINEAR) or dq_blend (2, BF_SKIN_DUAL_QUATERNION: the bone table is then
+//   bf_skin_vertices_dq_kernel's) in place of the skin's own rest arrays; 0: no skin
 // Every target is always evaluated: a zero weight takes no shortcut.  The deltas lie [target][vertex][3], so a wave's loads for one
 // target are contiguous; the weights are indexed by blockIdx.y and the loop counter alone (uniform: scalar loads).  The target loop
 // is unrolled four times to keep four targets' loads in flight; the sums are taken in increasing k all the same.  A lane past the
 // end computes vertex nv - 1 again and stores nothing, so control flow is uniform up to the barrier.
-template <bool SKIN>
+template <int SKIN>
 __global__ __launch_bounds__(256) void bf_morph_vertices_kernel(const float *__restrict__ rest_pos, const float *__restrict__ rest_nrm,
                                                                 const float *__restrict__ dpos, const float *__restrict__ dnrm, uint32_t nv,
                                                                 uint32_t n_targets, const float *__restrict__ wts,
                                                                 const uint4 *__restrict__ index, const float4 *__restrict__ weight,
                                                                 const float *__restrict__ bones, uint32_t n_bones, uint32_t bone_stride,
                                                                 float *__restrict__ pos, float *__restrict__ nrm, uint64_t vstride) {
-    __shared__ float sb[SKIN ? 256 * 12 : 1];
+    __shared__ float4 sb4[SKIN == 1 ? 256 * 3 : (SKIN == 2 ? 256 * 2 : 1)];
+    float *sb = reinterpret_cast<float *>(sb4);
     const uint32_t v = blockIdx.x * 256u + threadIdx.x, ver = blockIdx.y;
     const bool live = v < nv;
     const size_t vc = 3u * (size_t) (live ? v : nv - 1u), tstride = 3u * (size_t) nv;
@@ -514,8 +626,12 @@ __global__ __launch_bounds__(256) void bf_morph_vertices_kernel(const float *__r
     if (SKIN) {
         ix = index[vc / 3u];
         w = weight[vc / 3u];
-        const float *b = bones + (size_t) bone_stride * ver;
-        for (uint32_t i = threadIdx.x; i < n_bones * 12u; i += 256u) sb[i] = b[i];
+        if (SKIN == 2) {
+            dq_table_load(sb4, bones, n_bones, bone_stride, ver);
+        } else {
+            const float *b = bones + (size_t) bone_stride * ver;
+            for (uint32_t i = threadIdx.x; i < n_bones * 12u; i += 256u) sb[i] = b[i];
+        }
     }
     float x[3], n[3] = {0.f, 0.f, 0.f};
     for (int c = 0; c < 3; ++c) x[c] = rest_pos[vc + c];
@@ -551,7 +667,15 @@ __global__ __launch_bounds__(256) void bf_morph_vertices_kernel(const float *__r
     if (SKIN) __syncthreads();
     if (!live) return;
     const size_t o = (size_t) vstride * ver + vc;
-    if (SKIN) {
+    if (SKIN == 2) {
+        const DqBlend q = dq_blend(sb4, ix, w);
+        const float3 p = dq_point(q, x[0], x[1], x[2]);
+        pos[o] = p.x, pos[o + 1] = p.y, pos[o + 2] = p.z;
+        if (rest_nrm) {
+            const float3 r = dq_rotate(q, n[0], n[1], n[2]);
+            nrm[o] = r.x, nrm[o + 1] = r.y, nrm[o + 2] = r.z;
+        }
+    } else if (SKIN == 1) {
         const float3 p = skin_blend(sb, ix, w, x[0], x[1], x[2], true);
         pos[o] = p.x, pos[o + 1] = p.y, pos[o + 2] = p.z;
         if (rest_nrm) {
@@ -566,20 +690,26 @@ __global__ __launch_bounds__(256) void bf_morph_vertices_kernel(const float *__r
 BF_NS_END  // namespace bfd
 
 // n_versions poses of one morphed shape: weights [n_versions][n_targets] (device) -> pos (and nrm, if rest_nrm is given),
-// [n_versions][nv][3] each.  bones != nullptr ([n_versions][n_bones][12], device): skinned behind the morph, with `index` and `weight`
+// [n_versions][nv][3] each.  bones != nullptr ([n_versions][n_bones][12], device; dq: [n_versions][n_bones][8], 16-byte aligned, the
+// shape is in BF_SKIN_DUAL_QUATERNION): skinned behind the morph, with `index` and `weight`
 extern "C" hipError_t bfk_launch_morph_vertices(const float *rest_pos, const float *rest_nrm, const float *dpos, const float *dnrm, uint32_t nv,
                                                 uint32_t n_targets, const float *wts, const uint4 *index, const float4 *weight,
-                                                const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
+                                                const float *bones, uint32_t n_bones, int dq, float *pos, float *nrm, uint32_t n_versions,
                                                 hipStream_t stream) {
     if (nv == 0 || n_versions == 0) return hipSuccess;
     if (n_versions > 65535u || n_targets == 0 || n_targets > 256u) return hipErrorInvalidValue;
     const dim3 grid((nv + 255u) / 256u, n_versions);
     if (bones) {
         if (n_bones == 0 || n_bones > 256u || !index || !weight) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(bfd::bf_morph_vertices_kernel<true>, grid, dim3(256), 0, stream, rest_pos, rest_nrm, dpos, dnrm, nv, n_targets, wts, index,
-                           weight, bones, n_bones, n_bones * 12u, pos, nrm, (uint64_t) 3u * nv);
+        if (dq && ((uintptr_t) bones & 15u)) return hipErrorInvalidValue;
+        if (dq)
+            hipLaunchKernelGGL(bfd::bf_morph_vertices_kernel<2>, grid, dim3(256), 0, stream, rest_pos, rest_nrm, dpos, dnrm, nv, n_targets, wts, index,
+                               weight, bones, n_bones, n_bones * 8u, pos, nrm, (uint64_t) 3u * nv);
+        else
+            hipLaunchKernelGGL(bfd::bf_morph_vertices_kernel<1>, grid, dim3(256), 0, stream, rest_pos, rest_nrm, dpos, dnrm, nv, n_targets, wts, index,
+                               weight, bones, n_bones, n_bones * 12u, pos, nrm, (uint64_t) 3u * nv);
     } else {
-        hipLaunchKernelGGL(bfd::bf_morph_vertices_kernel<false>, grid, dim3(256), 0, stream, rest_pos, rest_nrm, dpos, dnrm, nv, n_targets, wts, index,
+        hipLaunchKernelGGL(bfd::bf_morph_vertices_kernel<0>, grid, dim3(256), 0, stream, rest_pos, rest_nrm, dpos, dnrm, nv, n_targets, wts, index,
                            weight, bones, 0u, 0u, pos, nrm, (uint64_t) 3u * nv);
     }
     return hipGetLastError();

@@ -62,8 +62,11 @@ extern "C" hipError_t bfk_launch_skin_vertices(const float *rest_pos, const floa
                                                hipStream_t stream);
 extern "C" hipError_t bfk_launch_morph_vertices(const float *rest_pos, const float *rest_nrm, const float *dpos, const float *dnrm, uint32_t nv,
                                                 uint32_t n_targets, const float *wts, const uint4 *index, const float4 *weight,
-                                                const float *bones, uint32_t n_bones, float *pos, float *nrm, uint32_t n_versions,
+                                                const float *bones, uint32_t n_bones, int dq, float *pos, float *nrm, uint32_t n_versions,
                                                 hipStream_t stream);
+extern "C" hipError_t bfk_launch_skin_vertices_dq(const float *rest_pos, const float *rest_nrm, const uint4 *index, const float4 *weight,
+                                                  uint32_t nv, const float *bones, uint32_t n_bones, float *pos, float *nrm,
+                                                  uint32_t n_versions, hipStream_t stream);
 extern "C" hipError_t bfk_launch_vertex_normals(const uint32_t *offset, const uint4 *entries, uint32_t nv, const float *pos, float *nrm,
                                                 uint32_t n_versions, hipStream_t stream);
 extern "C" void bfk_host_vertex_normals(uint32_t nv, const float *pos, uint32_t nf, const uint32_t *idx, float *out);

@@ -551,6 +551,7 @@ bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
     sc->mesh.skins = m.skins;      // shared, never written: bf_scene_set_skin on either handle replaces that handle's pointer alone
     sc->mesh.morphs = m.morphs;    // likewise (bf_scene_set_morph)
     sc->mesh.normal_mode = m.normal_mode;      // the source's modes at this moment; the clone's own from now on
+    sc->mesh.skin_mode = m.skin_mode;          // likewise (bf_scene_set_skin_mode)
     if (!m.tris0 && !m.geom_private) return BF_OK;
     // `src` has moved: the clone snapshots what src renders now as ITS geometry "as created"; uvs (and normals no transform moved) stay shared
     const MeshState::Bytes B = MeshState::bytes(src->d);

@@ -1,5 +1,6 @@
 // Meshes posed by a few numbers per render: skins (a pose is n_bones 3x4 matrices) and morph targets (a pose is n_targets
-// weights, and the bones of a skin behind them).  bf_skin_vertices_kernel or bf_morph_vertices_kernel computes the vertices into the
+// weights, and the bones of a skin behind them).  bf_skin_vertices_kernel (bf_skin_vertices_dq_kernel for a shape whose skin mode is
+// BF_SKIN_DUAL_QUATERNION: the bones are then converted to dual quaternions here) or bf_morph_vertices_kernel computes the vertices into the
 // handle's scratch, and from there on a pose is a device-form vertex update and a batch a device-form deform batch of bf_mesh.cpp, with the
 // bound on the coordinates derived here.  State: MeshState::skins / morphs / pose_vtx (bf_scene.h); kernels: bf_geom.hip.
 #include "bf_scene.h"
@@ -38,7 +39,105 @@ bf_status skin_bound(const MeshSkin &sk, const double X[3], uint32_t shape, cons
     }
     return BF_OK;
 }
-// ... as the float the gather checks against (and the shape's base box takes); a bound float cannot hold is refused
+
+// ---- dual-quaternion skinning (BF_SKIN_DUAL_QUATERNION): what the host does to a bone table ----------------------------------------
+// A bone is rigid if, in float64, max |R^T R - I| <= 1e-4 and det R > 0 (entries finite: checked before).
+bool bone_rigid(const float *m) {
+    double R[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[r][c] = (double) m[4 * r + c];
+    double dev = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            dev = std::max(dev, std::fabs(R[0][i] * R[0][j] + R[1][i] * R[1][j] + R[2][i] * R[2][j] - (i == j ? 1.0 : 0.0)));
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    return dev <= 1e-4 && det > 0.0;
+}
+// The conversion of one rigid bone [R | t] to a unit dual quaternion, stated ONCE, here (this object is compiled with
+// -ffp-contract=off, so motion.bone_dual_quaternions restates it in numpy bit for bit).  float64, rounded to float once at the end:
+//   tr = (m00 + m11) + m22;  the branch is the largest of (tr, m00, m11, m22), the first among equals in that order
+//   branch tr:   s = sqrt(((1 + m00) + m11) + m22), w = s / 2, f = 0.5 / s, x = (m21 - m12) f, y = (m02 - m20) f, z = (m10 - m01) f
+//   branch m00:  s = sqrt(((1 + m00) - m11) - m22), x = s / 2, f = 0.5 / s, w = (m21 - m12) f, y = (m01 + m10) f, z = (m02 + m20) f
+//   branch m11:  s = sqrt(((1 - m00) + m11) - m22), y = s / 2, f = 0.5 / s, w = (m02 - m20) f, x = (m01 + m10) f, z = (m12 + m21) f
+//   branch m22:  s = sqrt(((1 - m00) - m11) + m22), z = s / 2, f = 0.5 / s, w = (m10 - m01) f, x = (m02 + m20) f, y = (m12 + m21) f
+//   q = (w, x, y, z) / sqrt(((w w + x x) + y y) + z z), each component divided
+//   dual = (0, t) q / 2:  dw = -0.5 ((tx x + ty y) + tz z),  dx = 0.5 ((tx w + ty z) - tz y),  dy = 0.5 ((ty w + tz x) - tx z),
+//                         dz = 0.5 ((tz w + tx y) - ty x)
+//   out = (w, x, y, z, dw, dx, dy, dz)
+void bone_dq(const float *m, float out[8]) {
+    const double m00 = m[0], m01 = m[1], m02 = m[2], tx = m[3], m10 = m[4], m11 = m[5], m12 = m[6], ty = m[7], m20 = m[8], m21 = m[9],
+                 m22 = m[10], tz = m[11];
+    const double tr = (m00 + m11) + m22;
+    int branch = 0;
+    double best = tr;
+    if (m00 > best) branch = 1, best = m00;
+    if (m11 > best) branch = 2, best = m11;
+    if (m22 > best) branch = 3, best = m22;
+    double w, x, y, z;
+    if (branch == 0) {
+        const double s = std::sqrt(((1.0 + m00) + m11) + m22), f = 0.5 / s;
+        w = s / 2.0, x = (m21 - m12) * f, y = (m02 - m20) * f, z = (m10 - m01) * f;
+    } else if (branch == 1) {
+        const double s = std::sqrt(((1.0 + m00) - m11) - m22), f = 0.5 / s;
+        x = s / 2.0, w = (m21 - m12) * f, y = (m01 + m10) * f, z = (m02 + m20) * f;
+    } else if (branch == 2) {
+        const double s = std::sqrt(((1.0 - m00) + m11) - m22), f = 0.5 / s;
+        y = s / 2.0, w = (m02 - m20) * f, x = (m01 + m10) * f, z = (m12 + m21) * f;
+    } else {
+        const double s = std::sqrt(((1.0 - m00) - m11) + m22), f = 0.5 / s;
+        z = s / 2.0, w = (m10 - m01) * f, x = (m02 + m20) * f, y = (m12 + m21) * f;
+    }
+    const double len = std::sqrt(((w * w + x * x) + y * y) + z * z);
+    w = w / len, x = x / len, y = y / len, z = z / len;
+    out[0] = (float) w, out[1] = (float) x, out[2] = (float) y, out[3] = (float) z;
+    out[4] = (float) (-0.5 * ((tx * x + ty * y) + tz * z));
+    out[5] = (float) (0.5 * ((tx * w + ty * z) - tz * y));
+    out[6] = (float) (0.5 * ((ty * w + tz * x) - tx * z));
+    out[7] = (float) (0.5 * ((tz * w + tx * y) - ty * x));
+}
+// skin_bound for a shape in BF_SKIN_DUAL_QUATERNION: every entry finite, every bone some vertex weighs rigid, and B raised (all
+// three axes alike) over the posed coordinates.  Derivation (u = 2^-24, W = sk.weight_sum, kappa = sk.pivot_min, T = the largest
+// |t|_2 over the bones some vertex weighs, |X| = the 2-norm of X, |.| of a quaternion its 4-norm):
+//   the table: q_k = D_k.real has |q_k| = 1 and D_k.dual = (0, t_k) q_k / 2 has |D_k.dual| = |t_k| / 2 <= T / 2, each within a
+//     factor 1 +- 2u (normalised in float64, rounded once); a bone no vertex weighs is the identity and adds fl(+-0 D) = +-0;
+//   b.real . q_p = sum_k s_k w_k (q_k . q_p) = sum_k w_k |q_k . q_p| >= w_p |q_p|^2 >= kappa (1 - 4u): s_k is the sign of the
+//     ROUNDED dot, which can differ from the true one only where |q_k . q_p| <= 4u, and then the term is off by at most 8u w_k; the
+//     seven roundings of a component of b add at most 4u W more.  So |b.real| >= b.real . q_p / |q_p| >= kappa - 16u W, and with
+//     kappa >= 0.2497 (the largest of four weights that sum to at least 1 - 1e-3), |b.real| >= kappa (1 - 1e-5);
+//   |b.dual| <= sum_k w_k |D_k.dual| (1 + 4u) <= W T / 2 (1 + 6u), hence |e| = |b.dual| / |b.real| <= W T / (2 kappa) (1 + 2e-5) and
+//     the translation 2 vec(e r*) has 2-norm 2 |e| |r| <= W T / kappa (1 + 3e-5), |r| = 1 +- 4u;
+//   rotate(r, x) is the rotation by r / |r| of x up to (|r|^2 - 1) terms and nine roundings of magnitudes <= 4 |x|: at most
+//     |X| (1 + 64u) per coordinate; the translation's evaluation and the final sum add five roundings more.
+//   Together |x'_c| <= (|X| + W T / kappa) (1 + 5e-5): the factor 1 + 1e-4 below covers it, the evaluation in float64 and the
+//   rounding of B to float; results in the subnormal range err by 2^-150 per operation instead, below the 1e-37 added.
+// The normal has no bound of its own: the gather refuses one that is not finite, as ever.  `who` ends in ':' or ','.
+bf_status skin_bound_dq(const MeshSkin &sk, const double X[3], uint32_t shape, const float *bones, const char *who, double B[3]) {
+    double T = 0.0;
+    for (uint32_t b = 0; b < sk.n_bones; ++b) {
+        const float *m = bones + 12 * (size_t) b;
+        for (int j = 0; j < 12; ++j)
+            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "%s shape %u: bone %u has a non-finite entry", who, shape, b);
+        if (!sk.bone_used[b]) continue;
+        if (!bone_rigid(m))
+            return fail(BF_ERR_INVALID, "%s shape %u: bone %u is not rigid (BF_SKIN_DUAL_QUATERNION takes rotations and translations only: "
+                                        "max |R^T R - I| <= 1e-4, det R > 0)", who, shape, b);
+        T = std::max(T, std::sqrt((double) m[3] * m[3] + (double) m[7] * m[7] + (double) m[11] * m[11]));
+    }
+    const double bound = (std::sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]) + sk.weight_sum * T / (double) sk.pivot_min) * (1.0 + 1e-4) + 1e-37;
+    for (int r = 0; r < 3; ++r) B[r] = std::max(B[r], bound);
+    return BF_OK;
+}
+// one render's bone table as the DQ kernels read it: [n_bones][8], a bone no vertex weighs as the identity
+void skin_table_dq(const MeshSkin &sk, const float *bones, float *out) {
+    static const float identity[8] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (uint32_t b = 0; b < sk.n_bones; ++b) {
+        if (sk.bone_used[b]) bone_dq(bones + 12 * (size_t) b, out + 8 * (size_t) b);
+        else std::memcpy(out + 8 * (size_t) b, identity, sizeof(identity));
+    }
+}
+
+// ... a bound as the float the gather checks against (and the shape's base box takes); a bound float cannot hold is refused
 bf_status skin_bound_float(const double B[3], uint32_t shape, const char *who, float *bound, float box6[6], const char *why) {
     float mx = std::numeric_limits<float>::min();
     for (int r = 0; r < 3; ++r) {
@@ -81,9 +180,11 @@ struct PosedShape {
     const MeshMorph *mo;
     const MeshSkin *sk;
     const float *weights, *bones;
+    bool dq;                                                                         // sk in BF_SKIN_DUAL_QUATERNION on this handle
     uint32_t n_vertices() const { return mo ? mo->n_vertices : sk->n_vertices; }
     const float *rest_nrm() const { return mo ? mo->rest_nrm : sk->rest_nrm; }      // the morph's, blended by the skin behind it
-    size_t n_bone_floats() const { return sk ? (size_t) sk->n_bones * 12 : 0; }     // of one render
+    const float *bones_of(uint32_t k) const { return bones + (size_t) k * sk->n_bones * 12; }      // render k's, in the caller's table
+    size_t n_bone_floats() const { return sk ? (size_t) sk->n_bones * (dq ? 8 : 12) : 0; }         // of one render, in the staged table
     const char *why() const { return mo ? "weights or bones too large for the targets" : "bones too large for the rest pose"; }
 };
 
@@ -101,7 +202,7 @@ bf_status check_posed_shape(const bf_scene *scene, uint32_t shape, bool morph, c
     if (!morph && !sk) return fail(BF_ERR_INVALID, "%s shape %u has no skin (bf_scene_set_skin attaches one)", who, shape);
     if (morph && bones && !sk)
         return fail(BF_ERR_INVALID, "%s bones for shape %u, which has no skin (bf_scene_set_skin attaches one)", who, shape);
-    *out = {shape, tp, mo, sk, weights, bones};
+    *out = {shape, tp, mo, sk, weights, bones, sk && m.skins_dq(shape)};
     return BF_OK;
 }
 
@@ -115,7 +216,7 @@ bf_status pose_bound(const PosedShape &p, uint32_t k, const char *who, double B[
     } else {
         for (int c = 0; c < 3; ++c) X[c] = (double) p.sk->rest_abs[c];
     }
-    if (p.sk) return skin_bound(*p.sk, X, p.shape, p.bones + k * p.n_bone_floats(), who, B);
+    if (p.sk) return (p.dq ? skin_bound_dq : skin_bound)(*p.sk, X, p.shape, p.bones_of(k), who, B);
     for (int c = 0; c < 3; ++c) B[c] = std::max(B[c], X[c]);
     return BF_OK;
 }
@@ -125,7 +226,7 @@ bf_status pose_bound(const PosedShape &p, uint32_t k, const char *who, double B[
 size_t pose_floats(const PosedShape &p, bool with_normals) { return (size_t) p.n_vertices() * 3 * (p.rest_nrm() && with_normals ? 2 : 1); }
 
 // The staged table of renders k0 .. k0 + kc: [kc][n_targets] weights, padded to 16 bytes (none without a morph), then [kc][n_bones][12]
-// bones if the shape is skinned.
+// bones if the shape is skinned ([kc][n_bones][8] dual quaternions, converted here, if it is in BF_SKIN_DUAL_QUATERNION).
 size_t pose_table_floats(const PosedShape &p, uint32_t kc) { return (p.mo ? morph_weight_floats(*p.mo, kc) : 0) + kc * p.n_bone_floats(); }
 void pose_table_pack(const PosedShape &p, uint32_t k0, uint32_t kc, float *host) {
     if (p.mo) {
@@ -134,7 +235,11 @@ void pose_table_pack(const PosedShape &p, uint32_t k0, uint32_t kc, float *host)
         std::memset(host + n, 0, (wf - n) * sizeof(float));
         host += wf;
     }
-    if (p.sk) std::memcpy(host, p.bones + k0 * p.n_bone_floats(), kc * p.n_bone_floats() * sizeof(float));
+    if (p.sk && p.dq) {
+        for (uint32_t k = 0; k < kc; ++k) skin_table_dq(*p.sk, p.bones_of(k0 + k), host + k * p.n_bone_floats());
+    } else if (p.sk) {
+        std::memcpy(host, p.bones_of(k0), kc * p.n_bone_floats() * sizeof(float));
+    }
 }
 
 // The launch: kc versions of the shape from its table on the device into the scratch at `out` ([kc][nv][3] positions, then the
@@ -148,9 +253,9 @@ bf_status pose_vertices(const PosedShape &p, bool with_normals, const float *tab
         const MeshMorph &mo = *p.mo;
         HIP_TRY(bfk_launch_morph_vertices(mo.rest_pos, rest_nrm, mo.dpos, mo.dnrm, mo.n_vertices, mo.n_targets, table, sk ? sk->index : nullptr,
                                           sk ? sk->weight : nullptr, sk ? table + morph_weight_floats(mo, kc) : nullptr, sk ? sk->n_bones : 0u,
-                                          pos, nrm, kc, stream));
+                                          p.dq ? 1 : 0, pos, nrm, kc, stream));
     } else {
-        HIP_TRY(bfk_launch_skin_vertices(sk->rest_pos, rest_nrm, sk->index, sk->weight, sk->n_vertices, table, sk->n_bones, pos, nrm, kc, stream));
+        HIP_TRY((p.dq ? bfk_launch_skin_vertices_dq : bfk_launch_skin_vertices)(sk->rest_pos, rest_nrm, sk->index, sk->weight, sk->n_vertices, table, sk->n_bones, pos, nrm, kc, stream));
     }
     src->pos = pos;
     src->nrm = nrm;
@@ -300,6 +405,8 @@ bf_status bf_scene_set_skin(bf_scene *scene, uint32_t shape, uint32_t n_bones, c
         }
         if (!(std::fabs(sum - 1.0) <= 1e-3)) return fail(BF_ERR_INVALID, "%s shape %u: the weights of vertex %u sum to %.9g, not 1", fn, shape, v, sum);
         skin->weight_sum = std::max(skin->weight_sum, sum);
+        const float *wr = bone_weight + 4 * (size_t) v;
+        skin->pivot_min = std::min(skin->pivot_min, std::max(std::max(wr[0], wr[1]), std::max(wr[2], wr[3])));
     }
     BF_ENTER(scene);
     if (nv) {
@@ -325,6 +432,44 @@ bf_status bf_scene_set_skin(bf_scene *scene, uint32_t shape, uint32_t n_bones, c
     MeshState &m = scene->mesh;
     if (m.skins.size() < scene->info.n_shapes) m.skins.resize(scene->info.n_shapes);
     m.skins[shape] = std::move(skin);      // (the skin it replaces goes with its last handle; hipFree waits for the kernels that read it)
+    return BF_OK;
+}
+
+bf_status bf_scene_set_skin_mode(bf_scene *scene, uint32_t shape, uint32_t mode) {
+    const char *fn = "bf_scene_set_skin_mode:";
+    if (!scene) return fail(BF_ERR_INVALID, "%s null scene", fn);
+    if (mode != BF_SKIN_LINEAR && mode != BF_SKIN_DUAL_QUATERNION)
+        return fail(BF_ERR_INVALID, "%s shape %u: unknown mode %u (BF_SKIN_LINEAR or BF_SKIN_DUAL_QUATERNION)", fn, shape, mode);
+    const bf_geometry::MeshTopo *tp = nullptr;
+    const bf_status st = check_deform_shape(scene, shape, false, fn, &tp);
+    if (st != BF_OK) return st;
+    BF_ENTER(scene);
+    MeshState &m = scene->mesh;
+    if (m.skin_mode.size() < scene->info.n_shapes) m.skin_mode.resize(scene->info.n_shapes, (uint8_t) BF_SKIN_LINEAR);
+    m.skin_mode[shape] = (uint8_t) mode;      // read by the next call that takes bones for the shape; nothing moves now
+    return BF_OK;
+}
+
+bf_status bf_scene_get_skin_mode(const bf_scene *scene, uint32_t shape, uint32_t *mode_out) {
+    const char *fn = "bf_scene_get_skin_mode:";
+    if (!scene || !mode_out) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", fn, shape, scene->info.n_shapes);
+    if (scene->ends.shapes_host[shape].type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", fn, shape);
+    BF_ENTER(scene);
+    *mode_out = scene->mesh.skins_dq(shape) ? BF_SKIN_DUAL_QUATERNION : BF_SKIN_LINEAR;
+    return BF_OK;
+}
+
+bf_status bf_bone_dual_quaternions(uint32_t n_bones, const float *bones, float *out) {
+    const char *fn = "bf_bone_dual_quaternions:";
+    if (n_bones && (!bones || !out)) return fail(BF_ERR_INVALID, "%s null array", fn);
+    for (uint32_t b = 0; b < n_bones; ++b) {
+        const float *m = bones + 12 * (size_t) b;
+        for (int j = 0; j < 12; ++j)
+            if (!std::isfinite(m[j])) return fail(BF_ERR_INVALID, "%s bone %u has a non-finite entry", fn, b);
+        if (!bone_rigid(m)) return fail(BF_ERR_INVALID, "%s bone %u is not rigid (max |R^T R - I| <= 1e-4, det R > 0)", fn, b);
+    }
+    for (uint32_t b = 0; b < n_bones; ++b) bone_dq(bones + 12 * (size_t) b, out + 8 * (size_t) b);
     return BF_OK;
 }
 

@@ -94,6 +94,7 @@ struct __attribute__((visibility("hidden"))) MeshSkin {
     // what the bound on the posed coordinates is derived from (bf_pose.cpp: skin_bound)
     float rest_abs[3] = {0.f, 0.f, 0.f};  // max |rest coordinate| per axis
     double weight_sum = 0.0;              // largest float64 sum of a weight row (validated: within 1e-3 of 1)
+    float pivot_min = 1.f;                // smallest over the rows of the row's largest weight (skin_bound_dq's kappa; >= 0.24975 by the row sums)
     std::vector<uint8_t> bone_used;       // [n_bones]: some vertex gives the bone a non-zero weight
     ~MeshSkin() {
         if (block) (void) hipFree(block);
@@ -174,6 +175,10 @@ struct __attribute__((visibility("hidden"))) MeshState {
     float *nrm_vtx = nullptr;
     size_t nrm_vtx_cap = 0;                      // bytes
     bool recomputes(uint32_t shape) const { return shape < normal_mode.size() && normal_mode[shape] == BF_NORMALS_RECOMPUTE; }
+    // skin modes (bf_scene_set_skin_mode): BF_SKIN_* per shape, held as the normal modes are (empty: every shape BF_SKIN_LINEAR; a
+    // clone copies them); kept apart from `skins`, so a mode outlives the skin it was set for.  Read by every call that takes bones
+    std::vector<uint8_t> skin_mode;
+    bool skins_dq(uint32_t shape) const { return shape < skin_mode.size() && skin_mode[shape] == BF_SKIN_DUAL_QUATERNION; }
 
     // what to read as the base rows: the handle's own once it has moved, else the arrays it renders (a clone's snapshot included)
     struct Base { const float4 *tris, *nodes, *wnodes, *normals; };

@@ -111,6 +111,116 @@ def apply_skin(positions, normals, index, weight, bones):
         return blend(p, True), None if n is None else blend(n, False)
 
 
+def bone_dual_quaternions(bones):
+    """float32[n_bones, 8]: the unit dual quaternions of rigid bones float32[n_bones, 3, 4], as the library converts the bone table of a
+    shape in BF_SKIN_DUAL_QUATERNION (bf_bone_dual_quaternions / capi.bone_dual_quaternions, bit for bit).  float64, rounded to float
+    once at the end:
+
+        tr = (m00 + m11) + m22;  the branch is the largest of (tr, m00, m11, m22), the first among equals in that order
+        branch tr:   s = sqrt(((1 + m00) + m11) + m22), w = s / 2, f = 0.5 / s, x = (m21 - m12) f, y = (m02 - m20) f, z = (m10 - m01) f
+        branch m00:  s = sqrt(((1 + m00) - m11) - m22), x = s / 2, f = 0.5 / s, w = (m21 - m12) f, y = (m01 + m10) f, z = (m02 + m20) f
+        branch m11:  s = sqrt(((1 - m00) + m11) - m22), y = s / 2, f = 0.5 / s, w = (m02 - m20) f, x = (m01 + m10) f, z = (m12 + m21) f
+        branch m22:  s = sqrt(((1 - m00) - m11) + m22), z = s / 2, f = 0.5 / s, w = (m10 - m01) f, x = (m02 + m20) f, y = (m12 + m21) f
+        q = (w, x, y, z) / sqrt(((w w + x x) + y y) + z z), each component divided
+        dual = (0, t) q / 2:  dw = -0.5 ((tx x + ty y) + tz z),  dx = 0.5 ((tx w + ty z) - tz y),  dy = 0.5 ((ty w + tz x) - tx z),
+                              dz = 0.5 ((tz w + tx y) - ty x)
+        out = (w, x, y, z, dw, dx, dy, dz)
+
+    A bone that is not rigid (in float64, max |R^T R - I| <= 1e-4 and det R > 0) or not finite is a ValueError naming it."""
+    b = np.ascontiguousarray(bones, dtype=f32).reshape(-1, 3, 4)
+    out = np.empty((b.shape[0], 8), f32)
+    for k, m in enumerate(b.astype(np.float64)):
+        r, t = m[:, :3], m[:, 3]
+        if not np.all(np.isfinite(m)):
+            raise ValueError(f"bone {k} has a non-finite entry")
+        if not (np.abs(r.T @ r - np.eye(3)).max() <= 1e-4 and np.linalg.det(r) > 0.0):
+            raise ValueError(f"bone {k} is not rigid")
+        (m00, m01, m02), (m10, m11, m12), (m20, m21, m22) = r
+        tx, ty, tz = t
+        one, half = np.float64(1.0), np.float64(0.5)
+        branch = int(np.argmax([(m00 + m11) + m22, m00, m11, m22]))      # argmax: the first among equals
+        if branch == 0:
+            s = np.sqrt(((one + m00) + m11) + m22)
+            f = half / s
+            w, x, y, z = s / 2.0, (m21 - m12) * f, (m02 - m20) * f, (m10 - m01) * f
+        elif branch == 1:
+            s = np.sqrt(((one + m00) - m11) - m22)
+            f = half / s
+            x, w, y, z = s / 2.0, (m21 - m12) * f, (m01 + m10) * f, (m02 + m20) * f
+        elif branch == 2:
+            s = np.sqrt(((one - m00) + m11) - m22)
+            f = half / s
+            y, w, x, z = s / 2.0, (m02 - m20) * f, (m01 + m10) * f, (m12 + m21) * f
+        else:
+            s = np.sqrt(((one - m00) - m11) + m22)
+            f = half / s
+            z, w, x, y = s / 2.0, (m10 - m01) * f, (m02 + m20) * f, (m12 + m21) * f
+        n = np.sqrt(((w * w + x * x) + y * y) + z * z)
+        w, x, y, z = w / n, x / n, y / n, z / n
+        out[k] = [w, x, y, z, -half * ((tx * x + ty * y) + tz * z), half * ((tx * w + ty * z) - tz * y),
+                  half * ((ty * w + tz * x) - tx * z), half * ((tz * w + tx * y) - ty * x)]
+    return out
+
+
+def apply_skin_dq(positions, normals, index, weight, bones):
+    """Rest positions (and rest normals, or None) of a mesh posed by dual-quaternion skinning as the device poses a shape in
+    BF_SKIN_DUAL_QUATERNION (Scene.set_skin_mode): apply_skin's arguments, every bone that some vertex weighs rigid.  The table is
+    bone_dual_quaternions of those bones and the identity (1, 0, 0, 0; 0, 0, 0, 0) for a bone no vertex weighs.  fp32, every
+    operation rounded (no FMA, IEEE division and square root).  Per vertex, with slots k = 0..3:
+
+        p   = the slot of largest weight, the first among equals;   s_k = -1 if dot(D_k.real, D_p.real) < 0, else +1
+        b   = ((s0 w0 D_0 + s1 w1 D_1) + s2 w2 D_2) + s3 w3 D_3     per component over all eight, all four terms always evaluated
+        r   = b.real / |b.real|,  e = b.dual / |b.real|             (dot and |.|^2 are ((a0 b0 + a1 b1) + a2 b2) + a3 b3)
+        rotate(r, v) = (v + rw t) + cross(r.xyz, t)  with  t = 2 cross(r.xyz, v),   cross(a, b).x = fl(fl(ay bz) - fl(az by))
+        x'  = rotate(r, x) + 2 ((rw e.xyz - ew r.xyz) + cross(r.xyz, e.xyz))
+        n'  = rotate(r, n)                                          no translation, not renormalised
+
+    s_k w_k is exact (a sign), and so are the products by 2.  Returns (positions', normals')."""
+    p = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
+    n = None if normals is None else np.ascontiguousarray(normals, dtype=f32).reshape(-1, 3)
+    ix = np.asarray(index).reshape(-1, 4).astype(np.int64)
+    w = np.ascontiguousarray(weight, dtype=f32).reshape(-1, 4)
+    b = np.ascontiguousarray(bones, dtype=f32).reshape(-1, 3, 4)
+    if ix.shape[0] != p.shape[0] or w.shape[0] != p.shape[0]:
+        raise ValueError(f"{p.shape[0]} vertices, {ix.shape[0]} index rows, {w.shape[0]} weight rows")
+    if ix.size and (ix.min() < 0 or ix.max() >= b.shape[0]):
+        raise ValueError(f"bone index out of range for {b.shape[0]} bones")
+    if not np.all(np.isfinite(b)):
+        raise ValueError("bones: non-finite entry")
+    used = np.zeros(b.shape[0], bool)
+    used[ix[w > 0]] = True
+    table = np.zeros((b.shape[0], 8), f32)
+    table[:, 0] = 1.0
+    if used.any():
+        try:
+            table[used] = bone_dual_quaternions(b[used])
+        except ValueError as e:
+            raise ValueError(f"{e} (numbered among the bones some vertex weighs: {np.nonzero(used)[0].tolist()})") from None
+    rows = np.arange(p.shape[0])
+    d = table[ix]                                            # [nv, 4 slots, 8] float32: every operation below is float32 on float32
+
+    def dot4(a, c):
+        return ((a[:, 0] * c[:, 0] + a[:, 1] * c[:, 1]) + a[:, 2] * c[:, 2]) + a[:, 3] * c[:, 3]
+
+    def cross(a, c):
+        return np.stack([a[:, 1] * c[:, 2] - a[:, 2] * c[:, 1], a[:, 2] * c[:, 0] - a[:, 0] * c[:, 2], a[:, 0] * c[:, 1] - a[:, 1] * c[:, 0]], -1)
+
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        pivot = d[rows, np.argmax(w, axis=1), :4]            # argmax: the first among equals
+        c = np.stack([np.where(dot4(d[:, k, :4], pivot) < 0, -w[:, k], w[:, k]) for k in range(4)], -1)
+        blend = np.stack([((c[:, 0] * d[:, 0, j] + c[:, 1] * d[:, 1, j]) + c[:, 2] * d[:, 2, j]) + c[:, 3] * d[:, 3, j] for j in range(8)], -1)
+        length = np.sqrt(dot4(blend[:, :4], blend[:, :4]))
+        r, e = blend[:, :4] / length[:, None], blend[:, 4:] / length[:, None]
+        two, rw, ew, ru, eu = f32(2.0), r[:, :1], e[:, :1], r[:, 1:], e[:, 1:]
+
+        def rotate(v):
+            t = two * cross(ru, v)
+            return (v + rw * t) + cross(ru, t)
+
+        p2 = rotate(p) + two * ((rw * eu - ew * ru) + cross(ru, eu))
+        return p2.astype(f32, copy=False), None if n is None else rotate(n)
+
+
 def vertex_normals_f32(positions, faces):
     """The vertex normals the device computes under BF_NORMALS_RECOMPUTE (Scene.set_normal_mode), bit for bit, on the host:
     angle-weighted face normals summed per vertex in increasing face index, every operation fp32 (the statement is in

@@ -326,6 +326,16 @@ def _recompute(first, recompute_normals):
         first.set_normal_mode(int(k), capi.BF_NORMALS_RECOMPUTE)
 
 
+def _dual_quaternion(first, dual_quaternion, skinned):
+    """dual_quaternion=(shapes...) of the skin and morph sweeps: BF_SKIN_DUAL_QUATERNION on the first handle, before it is cloned
+    (clones inherit the modes), so every handle of the sweep blends those shapes' bones as dual quaternions (Scene.set_skin_mode;
+    motion.apply_skin_dq is the statement).  The shapes must be among the `skinned` ones."""
+    for k in (dual_quaternion or ()):
+        if int(k) not in skinned:
+            raise ValueError(f"dual_quaternion names shape {int(k)}, which the sweep does not skin")
+        first.set_skin_mode(int(k), capi.BF_SKIN_DUAL_QUATERNION)
+
+
 def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False, rebuild_every=None,
                         classes=None, recompute_normals=None):
     """Coherent pulse sweep in which meshes DEFORM between the pulses: a walking pedestrian, a vibrating
@@ -371,7 +381,7 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
 
 
 def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None, classes=None, lib=None,
-                      device=None, recompute_normals=None):
+                      device=None, recompute_normals=None, dual_quaternion=None):
     """Coherent pulse sweep in which SKINNED meshes are posed by a few bones per pulse: the counterpart of
     render_deform_sweep whose per-pulse input is [n_bones, 3, 4] floats per mesh, not its vertices.
 
@@ -384,7 +394,9 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
     groups, one per handle and stream, each ONE skin batch (bf_render_skin_batch_device).  per_pulse=True is the reference
     path: the pulses rotate over the handles, one bf_scene_pose_skin (+ one bf_scene_transform_meshes) and one render per
     pulse; per-path results are the same.  rebuild_every, classes and recompute_normals (the normals of the POSED surface in
-    place of the blended rest normals) as in render_deform_sweep.  Returns the cube
+    place of the blended rest normals) as in render_deform_sweep.  dual_quaternion=(shapes...): those skinned meshes are blended
+    as unit dual quaternions (Scene.set_skin_mode, motion.apply_skin_dq; their bones must be rigid), which keeps the volume of a
+    twisting joint, where by default they are blended linearly.  Returns the cube
     float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3] with classes."""
     every = _every(rebuild_every)
     n, shapes, tabs = capi.skin_tables(bones)
@@ -399,6 +411,7 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
             rest, rest_n = _rest_pose(sd, sh)
             index, weight = skins[int(sh)]
             first.set_skin(int(sh), tab.shape[1], rest, index, weight, rest_normals=rest_n)
+        _dual_quaternion(first, dual_quaternion, set(skins))
 
     def pose(h, k, stream):
         for sh, tab in zip(shapes, tabs):
@@ -412,7 +425,7 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
 
 
 def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None,
-                       classes=None, recompute_normals=(), lib=None, device=None):
+                       classes=None, recompute_normals=(), lib=None, device=None, dual_quaternion=None):
     """Coherent pulse sweep in which meshes are moved by MORPH TARGETS (blend shapes), a few weights per pulse: the
     counterpart of render_skin_sweep for surfaces that bones describe badly, a breathing chest wall or a panel vibrating in a
     few modes.  A mesh may be skinned behind its morph.
@@ -428,7 +441,8 @@ def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, tran
     The scene is built once and the morphs and skins attached before it is cloned; the pulses are split into `n_streams`
     contiguous groups, one per handle and stream, each ONE morph batch (bf_render_morph_batch_device).  per_pulse=True is the
     reference path: the pulses rotate over the handles, one bf_scene_pose_morph (+ one bf_scene_transform_meshes) and one
-    render per pulse; per-path results are the same.  rebuild_every, classes and recompute_normals as in render_skin_sweep.
+    render per pulse; per-path results are the same.  rebuild_every, classes, recompute_normals and dual_quaternion (for skinned
+    meshes) as in render_skin_sweep.
     Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3]
     with classes."""
     every = _every(rebuild_every)
@@ -455,6 +469,7 @@ def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, tran
             if int(sh) in skins:
                 index, weight = skins[int(sh)]
                 first.set_skin(int(sh), btabs[int(sh)].shape[1], rest, index, weight, rest_normals=rest_n)
+        _dual_quaternion(first, dual_quaternion, set(skins))
 
     def pose(h, k, stream):
         for sh, tab in zip(shapes, tabs):

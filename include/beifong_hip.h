@@ -933,6 +933,43 @@ bf_status bf_render_skin_batch(bf_scene *scene, const bf_launch *launch, uint32_
                                const uint32_t *shapes, const float *const *bones, uint32_t n_shapes, const float *to_world, float *hist_out,
                                bf_path_record *records_out, bf_stats *stats_out);
 
+/* Dual-quaternion skinning (Kavan et al.): a skin MODE per handle and mesh shape.  Linear blending averages matrices, so a joint
+ * that twists loses volume (its cross-section is halved at 120 degrees of twist and gone at 180); blending unit dual quaternions
+ * keeps every vertex at its rest distance from the twist axis.  Storage, bone tables, batches and sweeps are the skin's: only the
+ * blend differs, and callers pass the same [n_bones][3][4] tables.  DESIGN.md 6d.
+ *   bf_scene_set_skin_mode: BF_SKIN_LINEAR (the default) or BF_SKIN_DUAL_QUATERNION for mesh shape `shape` of this handle.  It
+ *     needs a mesh, not a skin, and outlives bf_scene_set_skin; a clone inherits the source's modes when it is taken and owns them
+ *     from then on.  Setting it moves nothing: every call that takes bones reads the mode of each skinned shape it poses
+ *     (bf_scene_pose_skin, bf_scene_pose_morph with bones, bf_render_skin_batch(_device), bf_render_morph_batch(_device) with bones).
+ *   Bones in this mode must be rigid: evaluated in float64, max |R^T R - I| <= 1e-4 and det R > 0.  Anything else is refused with
+ *     BF_ERR_INVALID naming the bone, before anything is enqueued; the scene and an open rolling sequence stay as they were.  A
+ *     bone that no vertex weighs is checked for finite entries only and enters the table as the identity (1, 0, 0, 0; 0, 0, 0, 0).
+ *   bf_bone_dual_quaternions: the conversion the library applies to a bone table, on the host (no device, no scene).  float64,
+ *     rounded to float once at the end.  R becomes a quaternion by Shepperd's method: of (trace, m00, m11, m22) the largest, the
+ *     first among equals in that order, names the component computed as half a square root (and so positive), the other three are
+ *     the matching off-diagonal sums or differences divided by four times it; the quaternion q is then divided by its norm.  The
+ *     dual part is (0, t) q / 2.  out = (w, x, y, z) of q, then (w, x, y, z) of the dual part.  EVERY bone must be rigid here.
+ *     beifong_amd.motion.bone_dual_quaternions is the numpy restatement, bit for bit.
+ *   The blend, fp32, every operation rounded (no FMA, IEEE division and square root).  For a vertex with slots k = 0..3, weights
+ *     w_k and the dual quaternions D_k of its bones:
+ *       p   = the slot of largest weight, the first among equals;   s_k = -1 if dot(D_k.real, D_p.real) < 0, else +1
+ *       b   = ((s0 w0 D_0 + s1 w1 D_1) + s2 w2 D_2) + s3 w3 D_3     per component over all eight, all four terms always evaluated
+ *       r   = b.real / |b.real|,  e = b.dual / |b.real|             (dot and |.|^2 are ((a0 b0 + a1 b1) + a2 b2) + a3 b3)
+ *       rotate(r, v) = (v + rw t) + cross(r.xyz, t)  with  t = 2 cross(r.xyz, v),   cross(a, b).x = fl(fl(ay bz) - fl(az by))
+ *       x'  = rotate(r, x) + 2 ((rw e.xyz - ew r.xyz) + cross(r.xyz, e.xyz))
+ *       n'  = rotate(r, n)                                          no translation, not renormalised
+ *     beifong_amd.motion.apply_skin_dq is the numpy statement; a morph ahead of the skin feeds (x, n) as in linear mode, and
+ *     BF_NORMALS_RECOMPUTE replaces n' as it replaces the linear blend's.
+ *   Bound: |x'| <= |X|_2 + W T / kappa per coordinate with the roundings accounted for: X the extent of what is posed, W the
+ *     largest weight-row sum, T the largest |t|_2 over the bones some vertex weighs, kappa the smallest over the vertices of the
+ *     row's largest weight (|b.real| >= kappa).  The gather's check stays as the safety net.
+ *   Refusals: BF_ERR_INVALID for a NULL argument, a shape out of range or not a mesh, an unknown mode; BF_ERR_UNSUPPORTED for
+ *     setting the mode of a mesh that carries an emitter / transmitter. */
+enum { BF_SKIN_LINEAR = 0, BF_SKIN_DUAL_QUATERNION = 1 };
+bf_status bf_scene_set_skin_mode(bf_scene *scene, uint32_t shape, uint32_t mode);
+bf_status bf_scene_get_skin_mode(const bf_scene *scene, uint32_t shape, uint32_t *mode_out);
+bf_status bf_bone_dual_quaternions(uint32_t n_bones, const float *bones /* host [n_bones][12] */, float *out /* host [n_bones][8] */);
+
 /* Morph targets (blend shapes): the moved vertices are a rest shape plus a weighted sum of per-vertex displacement fields,
  * evaluated on the device AHEAD of the skin, as glTF-style pipelines order the two.  A morph is attached to a mesh shape once
  * (rest positions, rest normals for a mesh with vertex normals, n_targets <= 256 dense position deltas [n_targets][n_vertices][3]
