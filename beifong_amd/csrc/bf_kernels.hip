@@ -21,7 +21,8 @@
 #include <algorithm>
 #include <cstring>
 
-#include "bf_path_logic.h"
+#include "bf_film.h"
+#include "bf_mask_cursor.h"
 #include "bf_launch.h"
 #include "bf_variant.h"
 

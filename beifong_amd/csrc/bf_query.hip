@@ -5,7 +5,7 @@
 // Built with -ffp-contract=off like every object here: bfk_host_cos is held bit for bit to the kernels' cosine.
 #include <algorithm>
 
-#include "bf_path_logic.h"
+#include "bf_device_core.h"
 #include "bf_launch.h"
 
 #if BF_FAST
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void bf_query_kernel(DScene sc, uint64_t n, co
         V3 ro, rd;
         float mint, maxt;
         float w = sensor_sample_ray<0>(sc, q[0], q[1], q[2], q[3], ro, rd, mint, maxt);
-        // irradiancemeter.cpp:82: the path's sensor weight divides by the surface area (bf_path_logic.h, the same expression)
+        // irradiancemeter.cpp:82: the path's sensor weight divides by the surface area (bf_film.h: film_put, the same expression)
         if (c_sensor(sc).type == BF_SENSOR_IRRADIANCEMETER) w = 1.f * kPi / c_rects(sc)[c_sensor(sc).rect].area;
         float *o = out + 9 * i;
         o[0] = ro.x;

@@ -1275,7 +1275,7 @@ bf_status bf_render_converge_device(bf_scene *scene, const bf_launch *launch, fl
         float *scratch = cv.scratch[r & 1u];
         HIP_TRY(hipMemsetAsync(scratch, 0, (size_t) R * L.total * sizeof(float), stream));
         // Render k = r R + j of the call takes seed launch->seed + k n_paths.  The kernels give path p of a render the stream
-        // seed + path_offset + p (bf_path_logic.h), so consecutive seeds would render all but one path again; n_paths apart, the
+        // seed + path_offset + p (bf_path_logic.h: generate_path), so consecutive seeds would render all but one path again; n_paths apart, the
         // renders' streams are the consecutive, disjoint ranges of one render of rounds R n_paths paths (mod 2^64).
         for (uint32_t j = 0; j < R; ++j) seeds[j] = launch->seed + ((uint64_t) r * R + j) * launch->n_paths;
         batch.seeds = seeds.data();

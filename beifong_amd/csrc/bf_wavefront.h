@@ -36,7 +36,7 @@ constexpr uint32_t kTailRowJobs = 12;      // tail: up to three passes of four r
 //   C = sh0, sh1, (sh2, sh3, occ, -), -                  the NEE shadow request and its answer: wf_shade stores the ray, its
 //                                                        contribution and occ = 0 (and sets kFlagShadowPending in sb); wf_trace
 //                                                        stores occ = 1 for an occluded ray and nothing else; the slot's next
-//                                                        reader adds the term (bf_path_logic.h: load_state)
+//                                                        reader adds the term (bf_path_state.h: load_state)
 // Most launches GATHER sparse slots through the mask cursor (a few per cent to a third of a batch alive): with one
 // array per row (rounds 1-2: "a wave touching one dense batch reads 1 KiB contiguous per array") a gathered lane touches seven cache lines for its state and six more to write it back; with records, two and two.
 #define BF_HD __host__ __device__ __forceinline__

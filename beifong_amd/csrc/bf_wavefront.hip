@@ -1,7 +1,7 @@
 // Wavefront path tracer for gfx950: the radar hot path as two persistent kernels per bounce iteration over a
 // pool of path SLOTS whose state stays in place in HBM (bf_wavefront.h).  There are no queues and no device-wide
 // counters on the data path: which slots need work is three 64-bit masks per 64-slot batch (alive / trace /
-// shadow), every wave owns a contiguous segment of batches, and a MaskCursor (bf_path_logic.h) packs the set bits
+// shadow), every wave owns a contiguous segment of batches, and a MaskCursor (bf_mask_cursor.h) packs the set bits
 // of its segment into full waves on the fly.
 //
 //   wf_shade : one lane per live slot.  Coalesced state load -> the integrator's vertex logic (emitter hit,
@@ -22,7 +22,8 @@
 // double operations are where the reference itself multiplies by a double literal, e.g. 1e-9 in phase_update and
 // freq_of).  Results are bit-identical per path to the one-kernel variant and to the oracle: same draws, same
 // operations in the same order.
-#include "bf_path_logic.h"
+#include "bf_film.h"
+#include "bf_mask_cursor.h"
 #include "bf_launch.h"
 
 BF_NS_BEGIN
