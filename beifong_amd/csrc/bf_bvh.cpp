@@ -104,7 +104,7 @@ struct Builder {
         constexpr int NB = BF_SAH_BINS;
         float best_cost = std::numeric_limits<float>::infinity();
         int best_axis = -1, best_bin = -1;
-        // The traversal kernels keep a kStackDepth-entry stack per lane in LDS:
+        // The four-wide stack need, hence the kernels' spill columns, grows with the depth (bf_bvh.h: kMaxDepth):
         // once the remaining budget only fits a balanced subtree, fall back to
         // median splits so the depth bound holds by construction.
         uint32_t need = 0;

@@ -39,7 +39,10 @@ static_assert(sizeof(Node) == 64, "node must be 64 bytes");
 #define BF_MAX_LEAF 2
 #endif
 constexpr int kMaxLeaf = BF_MAX_LEAF;
-constexpr int kMaxDepth = 31;   // tree depth bound == traversal stack bound (kStackDepth 32)
+// Depth bound of the binary tree.  It is NOT the traversal stack bound: a four-wide node keeps up to three children waiting per level
+// (BVH4::stack_need <= 3 * kMaxDepth = 93), the kernels hold 16 or 32 entries in LDS (kStackDepth) and the rest in the scene's
+// spill columns (bf_device_core.h: LaneStack), which bf_api.cpp / bf_mesh.cpp size from stack_need.
+constexpr int kMaxDepth = 31;
 
 struct BVH {
     std::vector<Node> nodes;          // nodes[0] is the root (if any triangles)

@@ -457,7 +457,7 @@ typedef struct bf_scene_info {
     uint64_t device_bytes;
     float bbox_min[3], bbox_max[3];
     uint32_t bvh_depth;       /* levels of the four-wide tree                  */
-    uint32_t bvh_stack_need;  /* worst-case traversal stack entries (<= 31)    */
+    uint32_t bvh_stack_need;  /* worst-case traversal stack entries (<= 93)    */
     uint32_t trace_node_bytes; /* bytes per node as the throughput traversal kernel (wf_trace) reads them: node_bytes (128,
                                   fp32 child boxes) by default, 64 with the opt-in quantised nodes (BF_QUANT_BVH=1) */
     int32_t  device;          /* HIP device the scene lives on (the current device when it was created)              */
