@@ -4,6 +4,7 @@ This is plumbing: the product is the HIP library behind the C ABI.  Loading
 fails loudly when the extension is missing — there is no CPU fallback.
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -30,6 +31,7 @@ BF_FLAG_CLASSES = 1024
 BF_MAX_CLASSES = 256
 BF_FLAG_AOV = 2048
 BF_MAX_AOVS = 16
+BF_FLAG_EXACT_SUM = 4096
 BF_NORMALS_GIVEN, BF_NORMALS_RECOMPUTE = range(2)
 BF_SKIN_LINEAR, BF_SKIN_DUAL_QUATERNION = range(2)
 (BF_AOV_DEPTH, BF_AOV_POSITION, BF_AOV_UV, BF_AOV_GEO_NORMAL, BF_AOV_SH_NORMAL, BF_AOV_DP_DU, BF_AOV_DP_DV, BF_AOV_DUV_DX,
@@ -71,6 +73,7 @@ class bf_emitter(C.Structure):
 BF_FILTER_RESOLUTION = 31
 BF_VARIANT_LEAN, BF_VARIANT_WIDE, BF_VARIANT_FAST, BF_VARIANT_MOMENT, BF_VARIANT_CLASS = 1, 2, 4, 8, 16
 BF_VARIANT_AOV = 32
+BF_VARIANT_EXACT_SUM = 64
 
 
 class bf_rfilter(C.Structure):
@@ -173,6 +176,7 @@ EXPORTED_SYMBOLS = [
     "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
     "bf_render_converge_device", "bf_render_converge", "bf_converge_statistic_device",
     "bf_scene_set_classes", "bf_scene_launch_channels", "bf_aov_floats", "bf_scene_set_aovs",
+    "bf_exact_sum_host", "bf_exact_sum",
 ]
 
 _lib = None
@@ -264,6 +268,8 @@ def load_library(path=None):
     lib.bf_trace_any.argtypes = [vp, C.c_uint64, vp, vp]
     lib.bf_ray_intersect.argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
     lib.bf_eval_elementary.argtypes = [C.c_int, C.c_uint64, vp, vp]
+    lib.bf_exact_sum_host.argtypes = [C.c_uint64, vp, vp, C.c_uint32, vp]
+    lib.bf_exact_sum.argtypes = [C.c_uint64, vp, vp, C.c_uint32, C.c_uint32, vp]
     for f in ("bf_bsdf_eval_pdf", "bf_bsdf_sample"):
         getattr(lib, f).argtypes = [vp, C.c_uint64, vp, vp, vp]
         getattr(lib, f + "_device").argtypes = [vp, C.c_uint64, vp, vp, vp, vp]
@@ -543,6 +549,81 @@ def aov_layout(launch, types, lib=None):
         at = sl.stop
     return {"aovs": slices, "names": names, "K": K, "nested": slice(5 + K, 5 + K + n_nested),
             "nested_rgba": slice(5 + K + n_nested, 9 + K + n_nested), "chan_px": 9 + K + n_nested}
+
+
+def _exact_sum_args(cell, value, n_cells):
+    c = np.asarray(cell)
+    v = np.asarray(value)
+    if c.dtype != np.uint32:
+        raise ValueError(f"cell: dtype {c.dtype}, expected uint32")
+    if v.dtype != np.float32:
+        raise ValueError(f"value: dtype {v.dtype}, expected float32")
+    c = np.ascontiguousarray(c.reshape(-1))
+    v = np.ascontiguousarray(v.reshape(-1))
+    if c.size != v.size:
+        raise ValueError(f"{c.size} cell indices for {v.size} values")
+    return c, v, int(n_cells)
+
+
+def exact_sum(cell, value, n_cells):
+    """The specification of BF_FLAG_EXACT_SUM and of bf_exact_sum(_host): out[c] = fl(sum of value[i] over cell[i] == c), the EXACT sum
+    rounded once to fp32, nearest-even, +0.0 for a cell without addends.  Integer arithmetic throughout: every finite fp32 is an integer
+    multiple of 2^-149, K[c] = sum of int(value * 2^149) is summed as Python integers (grouped by exponent first: (-1)^s M << shift,
+    the same integer), K is rounded to 24 significant bits by shifts and comparisons, and math.ldexp scales the result; a magnitude at
+    or above 2^128 - 2^103 is +-inf.  No floating-point addition anywhere.  cell uint32[n], value float32[n] (finite) -> float32[n_cells]."""
+    c, v, n_cells = _exact_sum_args(cell, value, n_cells)
+    if c.size and int(c.max()) >= n_cells:
+        raise ValueError(f"cell index {int(c.max())} is not below n_cells {n_cells}")
+    bits = v.view(np.uint32)
+    e = (bits >> np.uint32(23)) & np.uint32(0xff)
+    if np.any(e == 0xff):
+        raise ValueError("value: a non-finite addend")
+    f = (bits & np.uint32(0x7fffff)).astype(np.int64)
+    M = np.where(e != 0, f | np.int64(0x800000), f)
+    M = np.where(bits >> np.uint32(31) != 0, -M, M)
+    shift = np.maximum(e, 1).astype(np.int64) - 1      # value = M * 2^(shift - 149) exactly
+    # integer sums of the mantissas per (cell, shift): below 2^24 * n, exact in int64 for n < 2^39
+    key, inv = np.unique(c.astype(np.int64) * 254 + shift, return_inverse=True)
+    part = np.zeros(key.size, np.int64)
+    np.add.at(part, inv.reshape(-1), M)
+    K = [0] * n_cells
+    for k, s in zip(key.tolist(), part.tolist()):
+        K[k // 254] += s << (k % 254)
+    out = np.zeros(n_cells, np.float32)
+    for i, k in enumerate(K):
+        a = abs(k)
+        if a == 0:
+            continue
+        sh = max(a.bit_length() - 24, 0)
+        m = a >> sh
+        if sh:
+            rem, half = a & ((1 << sh) - 1), 1 << (sh - 1)
+            if rem > half or (rem == half and (m & 1)):
+                m += 1
+        x = math.ldexp(m, sh - 149)      # exact: m <= 2^24
+        if x >= math.ldexp(1.0, 128):
+            x = math.inf
+        out[i] = np.float32(-x if k < 0 else x)
+    return out
+
+
+def exact_sum_host(cell, value, n_cells, lib=None):
+    """bf_exact_sum_host: exact_sum through the engine's accumulator (csrc/bf_sum.h) on the CPU.  No device."""
+    c, v, n_cells = _exact_sum_args(cell, value, n_cells)
+    out = np.empty(n_cells, np.float32)
+    lib = lib or load_library()
+    check(lib, lib.bf_exact_sum_host(c.size, _ptr(c), _ptr(v), n_cells, _ptr(out)), "bf_exact_sum_host")
+    return out
+
+
+def exact_sum_device(cell, value, n_cells, in_lds=False, lib=None):
+    """bf_exact_sum: exact_sum on the device, through the device functions the BF_FLAG_EXACT_SUM kernels add with and their resolve
+    kernel.  in_lds: the workgroups privatise the cells in LDS and flush limbs (where n_cells cells fit), else global limbs."""
+    c, v, n_cells = _exact_sum_args(cell, value, n_cells)
+    out = np.empty(n_cells, np.float32)
+    lib = lib or load_library()
+    check(lib, lib.bf_exact_sum(c.size, _ptr(c), _ptr(v), n_cells, 1 if in_lds else 0, _ptr(out)), "bf_exact_sum")
+    return out
 
 
 def shard_range(n_paths, shard, n_shards, lib=None):

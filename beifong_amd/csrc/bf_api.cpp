@@ -36,6 +36,7 @@ const char *ncclGetErrorString(ncclResult_t result);
 #include <mutex>
 
 #include "bf_scene.h"
+#include "bf_sum.h"
 
 
 static thread_local std::string g_err;
@@ -683,6 +684,9 @@ bf_status bf_allreduce_device(const int *devices, uint32_t n_devices, float *con
 bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, const bf_launch *launch, float *const *hist_dev,
                                    void *const *streams, bf_stats *stats_out) {
     if (!scenes || !launch || !hist_dev || n_devices == 0) return fail(BF_ERR_INVALID, "bf_render_sharded_device: null argument");
+    if (launch->flags & BF_FLAG_EXACT_SUM)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded_device: BF_FLAG_EXACT_SUM is not supported (an all-reduce of floats would round once per shard; "
+                                        "reducing the limbs across devices is a follow-up)");
     if (launch->flags & BF_FLAG_AOV)
         return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded_device: BF_FLAG_AOV is not supported (the shards' handles each carry an AOV table "
                                         "of their own; render the AOVs per device)");
@@ -784,6 +788,9 @@ bf_status bf_render_sharded_device(bf_scene *const *scenes, uint32_t n_devices, 
 
 bf_status bf_render_sharded(bf_scene *const *scenes, uint32_t n_devices, const bf_launch *launch, float *hist_out, bf_stats *stats_out) {
     if (!scenes || !launch || !hist_out || n_devices == 0) return fail(BF_ERR_INVALID, "bf_render_sharded: null argument");
+    if (launch->flags & BF_FLAG_EXACT_SUM)
+        return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded: BF_FLAG_EXACT_SUM is not supported (an all-reduce of floats would round once per shard; "
+                                        "reducing the limbs across devices is a follow-up)");
     if (launch->flags & BF_FLAG_AOV)
         return fail(BF_ERR_UNSUPPORTED, "bf_render_sharded: BF_FLAG_AOV is not supported (the shards' handles each carry an AOV table of "
                                         "their own; render the AOVs per device)");
@@ -1039,6 +1046,65 @@ bf_status bf_eval_elementary(int op, uint64_t n, const float *x, float *y) {
     (void) hipFree(d_x);
     (void) hipFree(d_y);
     if (e != hipSuccess) return fail(BF_ERR_DEVICE, "bf_eval_elementary: %s", hipGetErrorString(e));
+    return BF_OK;
+}
+
+// ---- the exact accumulator on caller-given addends (include/beifong_hip.h; bf_sum.h) ----
+static bf_status exact_sum_check(const char *fn, uint64_t n, const uint32_t *cell, const float *value, uint32_t n_cells, const float *out) {
+    if (!out || !n_cells || (n && (!cell || !value))) return fail(BF_ERR_INVALID, "%s: null argument", fn);
+    if (n >= bfs::kMaxAddends) return fail(BF_ERR_INVALID, "%s: n %llu is not below 2^31, the addends a cell is exact for", fn, (unsigned long long) n);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (cell[i] >= n_cells) return fail(BF_ERR_INVALID, "%s: cell[%llu] = %u is not below n_cells %u", fn, (unsigned long long) i, cell[i], n_cells);
+        if (!std::isfinite(value[i])) return fail(BF_ERR_INVALID, "%s: value[%llu] is not finite", fn, (unsigned long long) i);
+    }
+    return BF_OK;
+}
+
+bf_status bf_exact_sum_host(uint64_t n, const uint32_t *cell, const float *value, uint32_t n_cells, float *out) {
+    bf_status st = exact_sum_check("bf_exact_sum_host", n, cell, value, n_cells, out);
+    if (st != BF_OK) return st;
+    std::vector<int64_t> limbs((size_t) n_cells * bfs::kLimbs, 0);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t bits;
+        std::memcpy(&bits, &value[i], sizeof(bits));
+        bfs::add(&limbs[(size_t) cell[i] * bfs::kLimbs], bits);
+    }
+    for (uint32_t c = 0; c < n_cells; ++c) {
+        const uint32_t bits = bfs::resolve(&limbs[(size_t) c * bfs::kLimbs]).bits;
+        std::memcpy(&out[c], &bits, sizeof(bits));
+    }
+    return BF_OK;
+}
+
+bf_status bf_exact_sum(uint64_t n, const uint32_t *cell, const float *value, uint32_t n_cells, uint32_t in_lds, float *out) {
+    bf_status st = exact_sum_check("bf_exact_sum", n, cell, value, n_cells, out);
+    if (st != BF_OK) return st;
+    uint32_t *d_cell = nullptr;
+    float *d_value = nullptr, *d_out = nullptr;
+    void *d_limbs = nullptr;
+    const size_t limb_bytes = (size_t) n_cells * bfs::kLimbs * sizeof(int64_t);
+    // privatised like a render's histogram: when the cells fit what kMaxLdsHist stands for
+    const bool lds = in_lds && (uint64_t) n_cells * bfs::kCellFloats <= (uint64_t) bfd::kMaxLdsHist;
+    hipError_t e = hipMalloc(&d_limbs, limb_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **) &d_out, (size_t) n_cells * 4);
+    if (e == hipSuccess && n) e = hipMalloc((void **) &d_cell, n * 4);
+    if (e == hipSuccess && n) e = hipMalloc((void **) &d_value, n * 4);
+    if (e == hipSuccess && n) e = hipMemcpy(d_cell, cell, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(d_value, value, n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_limbs, 0, limb_bytes);
+    if (e == hipSuccess) e = hipMemset(d_out, 0, (size_t) n_cells * 4);
+    if (e == hipSuccess && n) {
+        const unsigned grid = (unsigned) std::min<uint64_t>((n + bfd::kBlock - 1) / bfd::kBlock, 1024);
+        e = bfk_sum_probe(n, d_cell, d_value, n_cells, lds ? 1 : 0, d_limbs, grid, nullptr);
+    }
+    if (e == hipSuccess) e = bfk_sum_resolve(d_limbs, d_out, n_cells, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t) n_cells * 4, hipMemcpyDeviceToHost);
+    (void) hipFree(d_cell);
+    (void) hipFree(d_value);
+    (void) hipFree(d_out);
+    (void) hipFree(d_limbs);
+    if (e != hipSuccess) return fail(BF_ERR_DEVICE, "bf_exact_sum: %s", hipGetErrorString(e));
     return BF_OK;
 }
 

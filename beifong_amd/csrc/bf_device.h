@@ -102,7 +102,11 @@ struct DEmitter {
 //             only, never with kMoment / kClass / kLean / kMulti): shade_vertex writes the first intersection's values into the side
 //             rows of the path's slot (AovCtx below), film_put reads them back and adds them with the sample; every other variant
 //             has none of that code
-constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64, kClass = 128, kAov = 256;
+//   kSum      the launch's histogram is accumulated exactly (BF_FLAG_EXACT_SUM; chosen by the host through the *_sum launchers; general
+//             forms only, never with kMoment / kClass / kAov / kLean / kMulti): a cell is nine int64 limbs (bf_sum.h), the kernels'
+//             s_hist and g_hist address limb arrays, hist_add and the flushes add integer pieces, and the 1 x 1 film's base channels take
+//             the per-cell route (a register sum is an fp32 sum in lane order); every other variant has none of that code
+constexpr int kModeMask = 3, kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64, kClass = 128, kAov = 256, kSum = 512;
 // rare<V>(c): a condition the lean profile guarantees to be false
 template <int V> __device__ __forceinline__ constexpr bool rare(bool c) { return (V & kLean) ? false : c; }
 

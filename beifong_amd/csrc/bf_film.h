@@ -8,12 +8,13 @@
 //                The receive modes' half is film_put_receive, the path's record record_put
 //   film_flush : the end of a workgroup's launch: the base channels a wave kept in registers, the LDS-privatised histogram
 //                and the workgroup's base-channel tables go to the global histogram (ImageBlock::put(block), imageblock.cpp:56-74)
-//                (flush_wave_acc, flush_lds_hist, flush_class_table, flush_roll_base, in that order)
+//                (flush_wave_acc, flush_lds_hist, flush_class_table, flush_sum_table, flush_roll_base, in that order)
 #pragma once
 #include "bf_device_core.h"
 #include "bf_endpoint_logic.h"
 #include "bf_path_logic.h"
 #include "bf_path_state.h"
+#include "bf_sum.h"
 
 BF_NS_BEGIN
 
@@ -31,7 +32,32 @@ BF_DEV void lds_add(float *p, float v) {          // ds_add_f32
 BF_DEV void glb_add(float *p, float v) {          // global_atomic_add_f32
     (void) __hip_atomic_fetch_add((glb_float_ptr) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-BF_DEV void hist_add(float *s_hist, float *g_hist, bool lds, uint32_t idx, float v) {
+// kSum (BF_FLAG_EXACT_SUM): a histogram cell is nine int64 limbs (bf_sum.h) and an addend is at most two integer pieces, each added by
+// a relaxed vector atomic — ds_add_u64 / global_atomic_add_x2.  Integer addition is associative: whatever order the pieces land in and
+// however they are split between LDS and global memory, the limbs hold the exact sum.
+typedef __attribute__((address_space(3))) long long *lds_i64_ptr;
+typedef __attribute__((address_space(1))) long long *glb_i64_ptr;
+BF_DEV void lds_add_i64(long long *p, long long v) {          // ds_add_u64
+    (void) __hip_atomic_fetch_add((lds_i64_ptr) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+BF_DEV void glb_add_i64(long long *p, long long v) {          // global_atomic_add_x2
+    (void) __hip_atomic_fetch_add((glb_i64_ptr) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// SUM: s_hist and g_hist address limb arrays, idx counts cells
+template <bool SUM = false> BF_DEV void hist_add(float *s_hist, float *g_hist, bool lds, uint32_t idx, float v) {
+    if (SUM) {
+        const bfs::Pieces p = bfs::split(__float_as_uint(v));
+        if (lds) {
+            long long *c = reinterpret_cast<long long *>(s_hist) + idx * (uint32_t) bfs::kLimbs + p.limb;
+            if (p.lo) lds_add_i64(c, p.lo);
+            if (p.hi) lds_add_i64(c + 1, p.hi);
+        } else {
+            long long *c = reinterpret_cast<long long *>(g_hist) + (size_t) idx * bfs::kLimbs + p.limb;
+            if (p.lo) glb_add_i64(c, p.lo);
+            if (p.hi) glb_add_i64(c + 1, p.hi);
+        }
+        return;
+    }
     if (lds)
         lds_add(s_hist + idx, v);
     else
@@ -45,6 +71,8 @@ struct HistDst {
     float *s, *g;
     bool lds;
 };
+// kSum launches (SUM; never rolling): the block offset counts cells of bfs::kCellFloats floats each.
+template <bool SUM = false>
 BF_DEV HistDst hist_dst(const DLaunch &lp, uint32_t render, float *s_hist, float *g_hist, bool lds_hist, uint32_t n_cls = 0u, uint32_t cls = 0u) {
     HistDst h;
     if (lp.roll) {
@@ -54,8 +82,13 @@ BF_DEV HistDst hist_dst(const DLaunch &lp, uint32_t render, float *s_hist, float
     } else {
         uint32_t hb = lp.batch != 0u ? render * lp.n_chan : 0u;
         if (n_cls) hb = hb * n_cls + cls * lp.n_chan;
-        h.g = g_hist + hb;
-        h.s = s_hist + hb;
+        if (SUM) {
+            h.g = g_hist + (size_t) hb * bfs::kCellFloats;
+            h.s = s_hist + hb * (uint32_t) bfs::kCellFloats;
+        } else {
+            h.g = g_hist + hb;
+            h.s = s_hist + hb;
+        }
         h.lds = lds_hist;
     }
     return h;
@@ -98,11 +131,12 @@ BF_DEV float filt_eval(CSensor &se, float x) {
     const int idx = min((int) __builtin_fabsf(x * se.filt_scale), 31);
     return se.filt_tab[idx];
 }
-BF_DEV void put_wide_add(const HistDst &hd, uint32_t idx, float v, float w) {
+template <bool SUM = false> BF_DEV void put_wide_add(const HistDst &hd, uint32_t idx, float v, float w) {
     const float a = v * w;          // value[k] * weight (imageblock.cpp:160)
-    if (a != 0.f) hist_add(hd.s, hd.g, hd.lds, idx, a);
+    if (a != 0.f) hist_add<SUM>(hd.s, hd.g, hd.lds, idx, a);
 }
-template <bool MOM = false> BF_DEV void put_wide(CSensor &se, const WideSample &ws, const HistDst &hd) {
+// (SUM: the kSum variants; never with MOM)
+template <bool MOM = false, bool SUM = false> BF_DEV void put_wide(CSensor &se, const WideSample &ws, const HistDst &hd) {
     const int border = (int) se.filt_border, n = (int) se.filt_n;
     const float r = se.filt_radius;
     // pos = pos_ - (m_offset - m_border_size + .5f)
@@ -124,40 +158,40 @@ template <bool MOM = false> BF_DEV void put_wide(CSensor &se, const WideSample &
             const int gx = ws.offx + x - border - ws.cropx;
             if (gx < 0 || gx >= ws.W || gy < 0 || gy >= ws.H) continue;
             const uint32_t cell = ws.C * ((uint32_t) gy * (uint32_t) ws.W + (uint32_t) gx);
-            put_wide_add(hd, cell + 0u, ws.v0, w);
-            put_wide_add(hd, cell + 1u, ws.v1, w);
-            put_wide_add(hd, cell + 2u, ws.v2, w);
+            put_wide_add<SUM>(hd, cell + 0u, ws.v0, w);
+            put_wide_add<SUM>(hd, cell + 1u, ws.v1, w);
+            put_wide_add<SUM>(hd, cell + 2u, ws.v2, w);
             if (ws.five) {
-                put_wide_add(hd, cell + 3u, ws.v3, w);
-                put_wide_add(hd, cell + 4u, ws.v4, w);
+                put_wide_add<SUM>(hd, cell + 3u, ws.v3, w);
+                put_wide_add<SUM>(hd, cell + 4u, ws.v4, w);
             }
             for (int i = 0; i < 3; ++i) {
                 if (!(ws.emask >> i & 1u)) continue;
                 const uint32_t c = cell + (uint32_t) (ws.ech + i * estep);
-                put_wide_add(hd, c, ws.e0, w);
+                put_wide_add<SUM>(hd, c, ws.e0, w);
                 if (ws.e3) {
-                    put_wide_add(hd, c + 1u, ws.e1, w);
-                    put_wide_add(hd, c + 2u, ws.e2, w);
+                    put_wide_add<SUM>(hd, c + 1u, ws.e1, w);
+                    put_wide_add<SUM>(hd, c + 2u, ws.e2, w);
                 }
                 if (MOM && ws.five) {          // render modes only: an ADC cell's phase bins have no m2_ channel (Y A W [phase bins] m2_Y)
-                    put_wide_add(hd, c + ws.m2off, ws.e0 * ws.e0, w);
+                    put_wide_add<SUM>(hd, c + ws.m2off, ws.e0 * ws.e0, w);
                     if (ws.e3) {
-                        put_wide_add(hd, c + ws.m2off + 1u, ws.e1 * ws.e1, w);
-                        put_wide_add(hd, c + ws.m2off + 2u, ws.e2 * ws.e2, w);
+                        put_wide_add<SUM>(hd, c + ws.m2off + 1u, ws.e1 * ws.e1, w);
+                        put_wide_add<SUM>(hd, c + ws.m2off + 2u, ws.e2 * ws.e2, w);
                     }
                 }
             }
             if (MOM) {
                 if (ws.five) {
-                    put_wide_add(hd, cell + ws.nch + 0u, ws.n0, w);
-                    put_wide_add(hd, cell + ws.nch + 1u, ws.n1, w);
-                    put_wide_add(hd, cell + ws.nch + 2u, ws.n2, w);
-                    put_wide_add(hd, cell + ws.qch + 0u, ws.n0 * ws.n0, w);
-                    put_wide_add(hd, cell + ws.qch + 1u, ws.n1 * ws.n1, w);
-                    put_wide_add(hd, cell + ws.qch + 2u, ws.n2 * ws.n2, w);
+                    put_wide_add<SUM>(hd, cell + ws.nch + 0u, ws.n0, w);
+                    put_wide_add<SUM>(hd, cell + ws.nch + 1u, ws.n1, w);
+                    put_wide_add<SUM>(hd, cell + ws.nch + 2u, ws.n2, w);
+                    put_wide_add<SUM>(hd, cell + ws.qch + 0u, ws.n0 * ws.n0, w);
+                    put_wide_add<SUM>(hd, cell + ws.qch + 1u, ws.n1 * ws.n1, w);
+                    put_wide_add<SUM>(hd, cell + ws.qch + 2u, ws.n2 * ws.n2, w);
                 } else {
-                    put_wide_add(hd, cell + ws.qch, ws.v0 * ws.v0, w);
-                    if (ws.q2) put_wide_add(hd, cell + ws.qch + 1u, ws.v1 * ws.v1, w);
+                    put_wide_add<SUM>(hd, cell + ws.qch, ws.v0 * ws.v0, w);
+                    if (ws.q2) put_wide_add<SUM>(hd, cell + ws.qch + 1u, ws.v1 * ws.v1, w);
                 }
             }
         }
@@ -168,6 +202,7 @@ template <bool MOM = false> BF_DEV void put_wide(CSensor &se, const WideSample &
 // nested.R G B A at channel `nch`
 BF_DEV void put_wide_aov(CSensor &se, const WideSample &ws, const HistDst &hd, const AovCtx &av, const AovVals &a, uint32_t nch, float nested,
                          float alpha) {
+    constexpr bool SUM = false;      // (no kAov | kSum kernels)
     const int border = (int) se.filt_border, n = (int) se.filt_n;
     const float r = se.filt_radius;
     const float px = ws.posx - ((float) (ws.offx - border) + .5f), py = ws.posy - ((float) (ws.offy - border) + .5f);
@@ -192,15 +227,15 @@ BF_DEV void put_wide_aov(CSensor &se, const WideSample &ws, const HistDst &hd, c
                 const uint32_t type = (uint32_t) (t & 15u) - 1u, nf = aov_type_floats(type);
                 float vx, vy, vz;
                 aov_entry(a, type, vx, vy, vz);
-                put_wide_add(hd, ch, vx, w);
-                if (nf > 1u) put_wide_add(hd, ch + 1u, vy, w);
-                if (nf > 2u) put_wide_add(hd, ch + 2u, vz, w);
+                put_wide_add<SUM>(hd, ch, vx, w);
+                if (nf > 1u) put_wide_add<SUM>(hd, ch + 1u, vy, w);
+                if (nf > 2u) put_wide_add<SUM>(hd, ch + 2u, vz, w);
                 ch += nf;
             }
-            put_wide_add(hd, cell + nch + 0u, nested, w);
-            put_wide_add(hd, cell + nch + 1u, nested, w);
-            put_wide_add(hd, cell + nch + 2u, nested, w);
-            put_wide_add(hd, cell + nch + 3u, alpha, w);
+            put_wide_add<SUM>(hd, cell + nch + 0u, nested, w);
+            put_wide_add<SUM>(hd, cell + nch + 1u, nested, w);
+            put_wide_add<SUM>(hd, cell + nch + 2u, nested, w);
+            put_wide_add<SUM>(hd, cell + nch + 3u, alpha, w);
         }
     }
 }
@@ -237,6 +272,7 @@ BF_DEV void film_put_receive(const DScene &sc, const DLaunch &lp, const PathStat
     const bool lds_hist = hd.lds;
     constexpr bool wide = (RX & kWide) != 0;       // reconstruction filter wider than a pixel (uniform; the radar scenes use box)
     constexpr bool mom = (RX & kMoment) != 0;      // BF_FLAG_MOMENT: second moments next to every first-moment channel (beifong_hip.h)
+    constexpr bool sum = (RX & kSum) != 0;         // BF_FLAG_EXACT_SUM: the cells are limbs (hist_add)
     // receive_sample tail — integrator.cpp:1625-1665; SignalBlock::put — signalblock.cpp:162-169
     CSensor &se = c_sensor(sc);
     float tf0 = s.t_rx - se.adc_sampling_start;
@@ -305,21 +341,21 @@ BF_DEV void film_put_receive(const DScene &sc, const DLaunch &lp, const PathStat
             ws.e3 = false;
             ws.e0 = pv;
             ws.e1 = ws.e2 = 0.f;
-            put_wide<mom>(se, ws, hd);
+            put_wide<mom, sum>(se, ws, hd);
         } else {
             ++acc.invalid;
         }
     } else if ((ok = ok && lx >= 0.f && lx < (float) lp.bins && ly >= 0.f && ly < (float) lp.bins_y)) {
         uint32_t off = (3u + P + (mom ? (lp.iq ? 2u : 1u) : 0u)) * ((uint32_t) ly * lp.bins + (uint32_t) lx);
-        if (a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 0u, a0);
-        if (a1 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 1u, a1);
-        hist_add(s_hist, g_hist, lds_hist, off + 2u, 1.f);
+        if (a0 != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, off + 0u, a0);
+        if (a1 != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, off + 1u, a1);
+        hist_add<sum>(s_hist, g_hist, lds_hist, off + 2u, 1.f);
         if (mom) {
-            if (q0 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 3u + P, q0);
-            if (lp.iq && q1 != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 4u, q1);
+            if (q0 != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, off + 3u + P, q0);
+            if (lp.iq && q1 != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, off + 4u, q1);
         }
         for (int i = 0; i < 3; ++i)
-            if ((pmask >> i & 1u) && pv != 0.f) hist_add(s_hist, g_hist, lds_hist, off + 3u + (uint32_t) (pk0 - 1 + i), pv);
+            if ((pmask >> i & 1u) && pv != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, off + 3u + (uint32_t) (pk0 - 1 + i), pv);
         acc.W += 1.f;
     } else {
         ++acc.invalid;
@@ -363,7 +399,8 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
     constexpr bool classed = (RX & kClass) != 0;   // BF_FLAG_CLASSES: one histogram block per class of the path's first intersection
     // this render's block of the histogram (classed: the block of the path's class within it)
     const uint32_t n_cls = classed ? scene_n_classes(sc0) : 0u;
-    const HistDst hd = hist_dst(lp, s.render, s_hist, g_hist, lds_hist, n_cls, classed ? s.cls : 0u);
+    constexpr bool sum = (RX & kSum) != 0;         // BF_FLAG_EXACT_SUM: the cells are limbs (hist_add), s_hist and g_hist limb arrays
+    const HistDst hd = hist_dst<sum>(lp, s.render, s_hist, g_hist, lds_hist, n_cls, classed ? s.cls : 0u);
     s_hist = hd.s;
     g_hist = hd.g;
     lds_hist = hd.lds;
@@ -428,7 +465,8 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
         // the five base channels of a 1 x 1 film are summed in registers while every lane of the wave feeds the same
         // histogram: a plain launch, or the newest render of a rolling sequence.  Never in a class launch: the lanes' paths belong to
         // different class blocks, so the base channels go cell by cell like a W x H film's (the class is one more film axis)
-        const bool use_acc = !classed && (lp.batch == 0u || (lp.roll != nullptr && s.render == lp.roll_newest));
+        // Nor in an exact-sum launch: a register sum is an fp32 sum in lane order
+        const bool use_acc = !classed && !sum && (lp.batch == 0u || (lp.roll != nullptr && s.render == lp.roll_newest));
         if (rare<RX>(lp.spp != 0u)) {
             const uint64_t q = (lp.path_offset + s.path_i) / lp.spp;
             const uint32_t px = (uint32_t) (q % lp.film_w) - ((s.flags & kFlagFilmLeft) ? 1u : 0u);
@@ -488,25 +526,25 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                         if (s.aux >= lo && s.aux < hi) ws.emask |= 1u << (i - (k - 1));
                     }
                 }
-                put_wide<mom>(c_sensor(sc), ws, hd);
+                put_wide<mom, sum>(c_sensor(sc), ws, hd);
                 if (aov) put_wide_aov(c_sensor(sc), ws, hd, av, avv, eb + n_aov, s.result, valid ? 1.f : 0.f);
             } else {
                 ++acc.invalid;
             }
         } else if (ok) {
             if (rare<RX>(lp.spp != 0u)) {
-                    if (X != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 0u, X);
-                    if (Y != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 1u, Y);
-                    if (Z != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + 2u, Z);
-                    if (valid) hist_add(s_hist, g_hist, lds_hist, pix + 3u, 1.f);
-                    hist_add(s_hist, g_hist, lds_hist, pix + 4u, 1.f);
+                    if (X != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + 0u, X);
+                    if (Y != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + 1u, Y);
+                    if (Z != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + 2u, Z);
+                    if (valid) hist_add<sum>(s_hist, g_hist, lds_hist, pix + 3u, 1.f);
+                    hist_add<sum>(s_hist, g_hist, lds_hist, pix + 4u, 1.f);
                     if (mom) {
-                        if (nX != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + nch + 0u, nX);
-                        if (nY != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + nch + 1u, nY);
-                        if (nZ != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + nch + 2u, nZ);
-                        if (qX != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + qch + 0u, qX);
-                        if (qY != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + qch + 1u, qY);
-                        if (qZ != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + qch + 2u, qZ);
+                        if (nX != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + nch + 0u, nX);
+                        if (nY != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + nch + 1u, nY);
+                        if (nZ != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + nch + 2u, nZ);
+                        if (qX != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + qch + 0u, qX);
+                        if (qY != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + qch + 1u, qY);
+                        if (qZ != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + qch + 2u, qZ);
                     }
             } else if (!use_acc) {
                 // batched launch: the wave's lanes hold paths of different renders, so the base channels cannot be
@@ -522,24 +560,29 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                     bs = s_base + kRollBaseCh * ((lp.batch != 0u ? s.render * n_cls : 0u) + s.cls);
                     bl = true;
                 }
+                // likewise an exact-sum launch too large for LDS limbs: the workgroup's table [render][5] of limb cells
+                if (sum && !lds_hist && lp.lds_floats != 0u) {
+                    bs = s_base + (uint32_t) bfs::kCellFloats * kRollBaseCh * (lp.batch != 0u ? s.render : 0u);
+                    bl = true;
+                }
                 if (lp.roll && !lds_hist && lp.roll_newest - s.render < kRollBase) {
                     bs = s_base + (mom ? kRollBaseChMoment : kRollBaseCh) * (lp.roll_newest - s.render);
                     bl = true;
                     bn = 5u;
                     bq = 8u;
                 }
-                    if (X != 0.f) hist_add(bs, g_hist, bl, 0u, X);
-                    if (Y != 0.f) hist_add(bs, g_hist, bl, 1u, Y);
-                    if (Z != 0.f) hist_add(bs, g_hist, bl, 2u, Z);
-                    if (valid) hist_add(bs, g_hist, bl, 3u, 1.f);
-                    hist_add(bs, g_hist, bl, 4u, 1.f);
+                    if (X != 0.f) hist_add<sum>(bs, g_hist, bl, 0u, X);
+                    if (Y != 0.f) hist_add<sum>(bs, g_hist, bl, 1u, Y);
+                    if (Z != 0.f) hist_add<sum>(bs, g_hist, bl, 2u, Z);
+                    if (valid) hist_add<sum>(bs, g_hist, bl, 3u, 1.f);
+                    hist_add<sum>(bs, g_hist, bl, 4u, 1.f);
                     if (mom) {
-                        if (nX != 0.f) hist_add(bs, g_hist, bl, bn + 0u, nX);
-                        if (nY != 0.f) hist_add(bs, g_hist, bl, bn + 1u, nY);
-                        if (nZ != 0.f) hist_add(bs, g_hist, bl, bn + 2u, nZ);
-                        if (qX != 0.f) hist_add(bs, g_hist, bl, bq + 0u, qX);
-                        if (qY != 0.f) hist_add(bs, g_hist, bl, bq + 1u, qY);
-                        if (qZ != 0.f) hist_add(bs, g_hist, bl, bq + 2u, qZ);
+                        if (nX != 0.f) hist_add<sum>(bs, g_hist, bl, bn + 0u, nX);
+                        if (nY != 0.f) hist_add<sum>(bs, g_hist, bl, bn + 1u, nY);
+                        if (nZ != 0.f) hist_add<sum>(bs, g_hist, bl, bn + 2u, nZ);
+                        if (qX != 0.f) hist_add<sum>(bs, g_hist, bl, bq + 0u, qX);
+                        if (qY != 0.f) hist_add<sum>(bs, g_hist, bl, bq + 1u, qY);
+                        if (qZ != 0.f) hist_add<sum>(bs, g_hist, bl, bq + 2u, qZ);
                     }
             } else {
                 acc.X += X;
@@ -563,18 +606,18 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                         const uint32_t type = (uint32_t) (t & 15u) - 1u, nf = aov_type_floats(type);
                         float vx, vy, vz;
                         aov_entry(avv, type, vx, vy, vz);
-                        if (vx != 0.f) hist_add(s_hist, g_hist, lds_hist, ch, vx);
-                        if (nf > 1u && vy != 0.f) hist_add(s_hist, g_hist, lds_hist, ch + 1u, vy);
-                        if (nf > 2u && vz != 0.f) hist_add(s_hist, g_hist, lds_hist, ch + 2u, vz);
+                        if (vx != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, ch, vx);
+                        if (nf > 1u && vy != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, ch + 1u, vy);
+                        if (nf > 2u && vz != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, ch + 2u, vz);
                         ch += nf;
                     }
                     const uint32_t rch = pix + eb + n_aov;
                     if (s.result != 0.f) {
-                        hist_add(s_hist, g_hist, lds_hist, rch + 0u, s.result);
-                        hist_add(s_hist, g_hist, lds_hist, rch + 1u, s.result);
-                        hist_add(s_hist, g_hist, lds_hist, rch + 2u, s.result);
+                        hist_add<sum>(s_hist, g_hist, lds_hist, rch + 0u, s.result);
+                        hist_add<sum>(s_hist, g_hist, lds_hist, rch + 1u, s.result);
+                        hist_add<sum>(s_hist, g_hist, lds_hist, rch + 2u, s.result);
                     }
-                    if (valid) hist_add(s_hist, g_hist, lds_hist, rch + 3u, 1.f);
+                    if (valid) hist_add<sum>(s_hist, g_hist, lds_hist, rch + 3u, 1.f);
                 }
             if (is_range || is_time) {
                 // range.cpp:141-161 / time.cpp:134-153: bin i takes the sample iff
@@ -587,16 +630,16 @@ BF_DEV void film_put(const DScene &sc0, const DLaunch &lp, const PathState &s, f
                     float lo = (float) i * w, hi = (float) i * w + w;
                     if (s.aux >= lo && s.aux < hi) {
                         if (is_range) {
-                            if (a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + eb + (uint32_t) i, a0);
-                            if (mom && a0 != 0.f) hist_add(s_hist, g_hist, lds_hist, pix + eb + (uint32_t) i + m2off, a0 * a0);
+                            if (a0 != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + (uint32_t) i, a0);
+                            if (mom && a0 != 0.f) hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + (uint32_t) i + m2off, a0 * a0);
                         } else if (a0 != 0.f || a1 != 0.f || a2 != 0.f) {
-                            hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 0u, a0);
-                            hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 1u, a1);
-                            hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 2u, a2);
+                            hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 0u, a0);
+                            hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 1u, a1);
+                            hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + 2u, a2);
                             if (mom) {
-                                hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 0u, a0 * a0);
-                                hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 1u, a1 * a1);
-                                hist_add(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 2u, a2 * a2);
+                                hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 0u, a0 * a0);
+                                hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 1u, a1 * a1);
+                                hist_add<sum>(s_hist, g_hist, lds_hist, pix + eb + 3u * (uint32_t) i + m2off + 2u, a2 * a2);
                             }
                         }
                     }
@@ -649,8 +692,22 @@ template <int RX> BF_DEV void flush_wave_acc(const DLaunch &lp, FilmAcc &acc, fl
         }
     }
 }
+// kSum: n_cells limb cells of LDS into the same cells of global memory, one global atomic per non-zero limb
+BF_DEV void flush_limbs(float *s_limbs, float *g_limbs, uint32_t n_cells, int tid) {
+    __syncthreads();
+    const lds_i64_ptr s = (lds_i64_ptr) reinterpret_cast<long long *>(s_limbs);
+    long long *const g = reinterpret_cast<long long *>(g_limbs);
+    for (uint32_t i = tid; i < n_cells * (uint32_t) bfs::kLimbs; i += kBlock) {
+        const long long v = s[i];
+        if (v != 0) glb_add_i64(g + i, v);
+    }
+}
 // film_flush: the LDS-privatised histogram, one global atomic per non-empty bin
-BF_DEV void flush_lds_hist(const DLaunch &lp, float *s_hist, float *g_hist, int tid) {
+template <bool SUM = false> BF_DEV void flush_lds_hist(const DLaunch &lp, float *s_hist, float *g_hist, int tid) {
+    if (SUM) {      // (never rolling)
+        flush_limbs(s_hist, g_hist, lp.n_chan_all, tid);
+        return;
+    }
     __syncthreads();
     if (lp.roll) {
         // one block per render of the LDS window, each flushed into that render's own histogram
@@ -679,6 +736,18 @@ BF_DEV void flush_class_table(const DLaunch &lp, float *s_hist, float *g_hist, i
         if (v != 0.f) glb_add(g_hist + (size_t) blk * lp.n_chan + (i - kRollBaseCh * blk), v);
     }
 }
+// film_flush: the base-channel table of an exact-sum launch without LDS limbs (film_put): limb [render][channel][limb] -> the same limb
+// of the render's base cells
+BF_DEV void flush_sum_table(const DLaunch &lp, float *s_hist, float *g_hist, int tid) {
+    __syncthreads();
+    const lds_i64_ptr s = (lds_i64_ptr) reinterpret_cast<long long *>(s_hist);
+    long long *const g = reinterpret_cast<long long *>(g_hist);
+    for (uint32_t i = tid; i < lp.lds_floats / 2u; i += kBlock) {
+        const long long v = s[i];
+        const uint32_t cell = i / (uint32_t) bfs::kLimbs, render = cell / kRollBaseCh;
+        if (v != 0) glb_add_i64(g + ((size_t) render * lp.n_chan + (cell - kRollBaseCh * render)) * bfs::kLimbs + (i - (uint32_t) bfs::kLimbs * cell), v);
+    }
+}
 // film_flush: the base-channel table of the renders behind the window: entry [age][channel], age = roll_newest - render
 template <int RX> BF_DEV void flush_roll_base(const DLaunch &lp, float *s_hist, bool lds_hist, int tid) {
     if (!lds_hist) __syncthreads();
@@ -698,9 +767,11 @@ template <int RX> BF_DEV void flush_roll_base(const DLaunch &lp, float *s_hist, 
 // flush the LDS-privatised histogram: one global atomic per non-empty bin
 template <int RX = 2> BF_DEV void film_flush(const DLaunch &lp, FilmAcc &acc, float *s_hist, float *g_hist, bool lds_hist, int tid) {
     const int lane = tid & 63;
-    if (!mode_receive<RX>(lp)) flush_wave_acc<RX>(lp, acc, s_hist, g_hist, lds_hist, lane);
-    if (lds_hist) flush_lds_hist(lp, s_hist, g_hist, tid);
+    // (kSum: film_put has written the base channels as limbs, no lane holds a register sum)
+    if (!(RX & kSum) && !mode_receive<RX>(lp)) flush_wave_acc<RX>(lp, acc, s_hist, g_hist, lds_hist, lane);
+    if (lds_hist) flush_lds_hist<(RX & kSum) != 0>(lp, s_hist, g_hist, tid);
     if ((RX & kClass) && !lds_hist && lp.lds_floats != 0u) flush_class_table(lp, s_hist, g_hist, tid);
+    if ((RX & kSum) && !lds_hist && lp.lds_floats != 0u) flush_sum_table(lp, s_hist, g_hist, tid);
     if (lp.roll && !mode_receive<RX>(lp)) flush_roll_base<RX>(lp, s_hist, lds_hist, tid);
 }
 

@@ -500,7 +500,7 @@ __global__ __launch_bounds__(kBlock, RESUME ? TW : 3) void bf_render_kernel(DSce
 BF_NS_END  // namespace bfd
 
 static_assert(bfv::kWide == bfd::kWide && bfv::kLean == bfd::kLean && bfv::kMulti == bfd::kMulti && bfv::kGeom == bfd::kGeom &&
-                  bfv::kMoment == bfd::kMoment && bfv::kClass == bfd::kClass && bfv::kAov == bfd::kAov,
+                  bfv::kMoment == bfd::kMoment && bfv::kClass == bfd::kClass && bfv::kAov == bfd::kAov && bfv::kSum == bfd::kSum,
               "bf_variant.h restates the variant word of bf_device.h");
 
 // host-callable launchers (bf_launch.h; used by bf_render.cpp, which is plain C++)
@@ -540,7 +540,7 @@ bfv::Shape launch_shape(const bfd::DLaunch *lp, int tail_waves) {
 
 // The one-kernel render.  The cases are the instantiations this object holds: the general kernel with or without per-render geometry
 // (bf_render_motion_batch_device) and a wide filter, and in the exact build the same four forms of the kMoment (BF_FLAG_MOMENT),
-// kClass (BF_FLAG_CLASSES) and kAov (BF_FLAG_AOV) kernels; none of the three exists in the fast build.
+// kClass (BF_FLAG_CLASSES), kAov (BF_FLAG_AOV) and kSum (BF_FLAG_EXACT_SUM) kernels; none of the four exists in the fast build.
 static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,
                                 unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream,
                                 bfv::Feature feature) {
@@ -566,6 +566,10 @@ static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, f
         case kAov | kWide: launch_form<false, BF_TAIL_WAVES, kAov | kWide>(k, stats); break;
         case kAov | kGeom: launch_form<false, BF_TAIL_WAVES, kAov | kGeom>(k, stats); break;
         case kAov | kWide | kGeom: launch_form<false, BF_TAIL_WAVES, kAov | kWide | kGeom>(k, stats); break;
+        case kSum: launch_form<false, BF_TAIL_WAVES, kSum>(k, stats); break;
+        case kSum | kWide: launch_form<false, BF_TAIL_WAVES, kSum | kWide>(k, stats); break;
+        case kSum | kGeom: launch_form<false, BF_TAIL_WAVES, kSum | kGeom>(k, stats); break;
+        case kSum | kWide | kGeom: launch_form<false, BF_TAIL_WAVES, kSum | kWide | kGeom>(k, stats); break;
 #endif
         default: return hipErrorInvalidValue;
     }
@@ -581,7 +585,7 @@ static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, f
 //   block_cap  : at most this many workgroups (0: no cap)
 // The cases: the general, lean, wide and per-path-table (kMulti) kernels, the first three also with per-render geometry, all three
 // waves per SIMD, and the general kernel at two; in the exact build the same seven forms of the kMoment kernels and the four
-// general forms of the kClass and kAov kernels (bf_variant.h: tail_variant).
+// general forms of the kClass, kAov and kSum kernels (bf_variant.h: tail_variant).
 static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, uint32_t n_slots,
                               float *g_hist, bf_path_record *records, int stats, size_t lds_bytes, hipStream_t stream,
                               int tail_waves, unsigned spread, unsigned block_cap, bfv::Feature feature) {
@@ -623,14 +627,18 @@ static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, con
         case kAov | kWide: launch_form<true, 3, kAov | kWide>(k, stats); break;
         case kAov | kGeom: launch_form<true, 3, kAov | kGeom>(k, stats); break;
         case kAov | kWide | kGeom: launch_form<true, 3, kAov | kWide | kGeom>(k, stats); break;
+        case kSum: launch_form<true, 3, kSum>(k, stats); break;
+        case kSum | kWide: launch_form<true, 3, kSum | kWide>(k, stats); break;
+        case kSum | kGeom: launch_form<true, 3, kSum | kGeom>(k, stats); break;
+        case kSum | kWide | kGeom: launch_form<true, 3, kSum | kWide | kGeom>(k, stats); break;
 #endif
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
-// the families of bf_launch.h this object defines: its own build's (no suffix, or _fast) and, in the exact build, the kMoment, kClass
-// and kAov kernels'
+// the families of bf_launch.h this object defines: its own build's (no suffix, or _fast) and, in the exact build, the kMoment, kClass,
+// kAov and kSum kernels'
 #define BF_DEFINE_LAUNCHERS(name, feature)                                                                                              \
     extern "C" hipError_t bfk_launch_render##name(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records, \
                                                   unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes,            \
@@ -649,6 +657,7 @@ BF_DEFINE_LAUNCHERS(, bfv::kPlain)
 BF_DEFINE_LAUNCHERS(_moment, bfv::kFeatMoment)
 BF_DEFINE_LAUNCHERS(_class, bfv::kFeatClass)
 BF_DEFINE_LAUNCHERS(_aov, bfv::kFeatAov)
+BF_DEFINE_LAUNCHERS(_sum, bfv::kFeatSum)
 #endif
 #undef BF_DEFINE_LAUNCHERS
 

@@ -10,7 +10,8 @@
 
 // The launchers a render goes through, once per family of kernels: the exact build (no suffix), the fast-arithmetic build (_fast,
 // BF_FLAG_FAST: bf_ns.h) and, in the exact build only, the second-moment (_moment, BF_FLAG_MOMENT; bf_device.h: kMoment), class
-// (_class, BF_FLAG_CLASSES; kClass) and AOV (_aov, BF_FLAG_AOV; kAov) variants, which share the exact wf_trace.
+// (_class, BF_FLAG_CLASSES; kClass), AOV (_aov, BF_FLAG_AOV; kAov) and exact-sum (_sum, BF_FLAG_EXACT_SUM; kSum) variants, which share
+// the exact wf_trace.
 #define BF_RENDER_LAUNCHERS(sfx)                                                                                                                \
     extern "C" hipError_t bfk_launch_render##sfx(const bfd::DScene *sc, const bfd::DLaunch *lp, float *g_hist, bf_path_record *records,         \
                                                  unsigned long long *counters, int stats, unsigned grid, size_t lds_bytes, hipStream_t stream); \
@@ -29,11 +30,12 @@
 BF_RENDER_LAUNCHERS(_fast)
 BF_TRACE_LAUNCHER(_fast)
 #else
-// An exact device file (which defines the first four families) or a host file (which calls all five)
+// An exact device file (which defines the first five families) or a host file (which calls all six)
 BF_RENDER_LAUNCHERS()
 BF_RENDER_LAUNCHERS(_moment)
 BF_RENDER_LAUNCHERS(_class)
 BF_RENDER_LAUNCHERS(_aov)
+BF_RENDER_LAUNCHERS(_sum)
 BF_RENDER_LAUNCHERS(_fast)
 BF_TRACE_LAUNCHER()
 BF_TRACE_LAUNCHER(_fast)
@@ -84,6 +86,13 @@ extern "C" hipError_t bfk_launch_microfacet(int op, uint32_t type, float alpha_u
 extern "C" hipError_t bfk_launch_elementary(int op, uint64_t n, const float *x, float *y);
 extern "C" hipError_t bfk_gather_probe(int mode, const float4 *table, uint32_t n_rows, float4 *out, hipStream_t stream);
 extern "C" float bfk_host_cos(float x);
+
+// bf_sum.hip (BF_FLAG_EXACT_SUM): the limb cells of a launch into its histogram, hist[i] = fl(hist[i] + cell i) for every cell that
+// received an addend; and the probe behind bf_exact_sum: n (cell, value) pairs into n_cells limb cells (zeroed by the caller), in LDS
+// per workgroup first with in_lds (n_cells * 72 bytes of dynamic LDS)
+extern "C" hipError_t bfk_sum_resolve(const void *limbs, float *hist, uint32_t n_cells, hipStream_t stream);
+extern "C" hipError_t bfk_sum_probe(uint64_t n, const uint32_t *cell, const float *value, uint32_t n_cells, int in_lds, void *limbs,
+                                    unsigned grid, hipStream_t stream);
 #endif
 
 #undef BF_RENDER_LAUNCHERS

@@ -765,12 +765,14 @@ bf_status check_batch_call(const char *fn, const char *kind, const bf_scene *sce
     return BF_OK;
 }
 
-// ... and what each does first behind the lock.  A refused class or AOV launch does no device work (the refit's preparation and the
+// ... and what each does first behind the lock.  A refused class, AOV or exact-sum launch does no device work (the refit's preparation and the
 // geometry versions would come first), and a scene without triangles has nothing to move: an ordinary batch.  True: the call ends
 // here with *st; false: the caller goes on to its versions.
 bool batch_ends_early(bf_scene *scene, const bf_launch *launch, uint32_t n_renders, const uint64_t *seeds, float *hist_dev,
                       bf_path_record *records_dev, void *stream_, bf_stats *stats_out, bf_status *st) {
-    if ((*st = check_classes(scene, launch, n_renders)) != BF_OK || (*st = check_aov(scene, launch, n_renders)) != BF_OK) return true;
+    if ((*st = check_classes(scene, launch, n_renders)) != BF_OK || (*st = check_aov(scene, launch, n_renders)) != BF_OK ||
+        (*st = check_sum(scene, launch, n_renders)) != BF_OK)
+        return true;
     if (scene->d.n_tris != 0) return false;
     bf_batch b = {n_renders, seeds, nullptr};
     *st = render_locked(scene, launch, &b, hist_dev, records_dev, stream_, stats_out);

@@ -2,6 +2,7 @@
 // wavefront control loops, launch plans, rolling sequences, guard words and statistics.  State: bf_scene::run (bf_scene.h: RenderState);
 // kernels: bf_kernels.hip, bf_wavefront.hip.
 #include "bf_scene.h"
+#include "bf_sum.h"
 
 #include <algorithm>
 #include <cmath>
@@ -11,8 +12,8 @@
 #include <vector>
 
 namespace {
-// the kernels one render runs: the exact build, the fast-arithmetic one (BF_FLAG_FAST), the second-moment variants (BF_FLAG_MOMENT) or
-// the class variants (BF_FLAG_CLASSES)
+// the kernels one render runs: the exact build, the fast-arithmetic one (BF_FLAG_FAST), the second-moment variants (BF_FLAG_MOMENT),
+// the class variants (BF_FLAG_CLASSES), the AOV variants (BF_FLAG_AOV) or the exact-sum variants (BF_FLAG_EXACT_SUM)
 struct Kernels {
     decltype(&bfk_launch_render) render;
     decltype(&bfk_wf_shade) shade;
@@ -24,8 +25,10 @@ const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_f
 const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment};
 const Kernels kClass = {bfk_launch_render_class, bfk_wf_shade_class, bfk_wf_trace, bfk_launch_tail_class};
 const Kernels kAov = {bfk_launch_render_aov, bfk_wf_shade_aov, bfk_wf_trace, bfk_launch_tail_aov};      // (BF_FLAG_AOV: with none of the three above, check_aov)
+const Kernels kSum = {bfk_launch_render_sum, bfk_wf_shade_sum, bfk_wf_trace, bfk_launch_tail_sum};      // (BF_FLAG_EXACT_SUM: with none of the four above, check_sum)
 // (BF_FLAG_MOMENT | BF_FLAG_FAST, and BF_FLAG_CLASSES with either, are refused before any kernel is chosen: check_launch)
 const Kernels &kernels_for(uint32_t flags) {
+    if (flags & BF_FLAG_EXACT_SUM) return kSum;
     return (flags & BF_FLAG_FAST) ? kFast : ((flags & BF_FLAG_MOMENT) ? kMoment : ((flags & BF_FLAG_CLASSES) ? kClass : ((flags & BF_FLAG_AOV) ? kAov : kExact)));
 }
 }  // namespace
@@ -66,6 +69,7 @@ RenderState::~RenderState() {
     for (hipEvent_t e : timing) (void) hipEventDestroy(e);
     if (counters) (void) hipFree(counters);
     if (aov.rows) (void) hipFree(aov.rows);
+    if (sum.limbs) (void) hipFree(sum.limbs);
     for (float *q : conv.scratch)
         if (q) (void) hipFree(q);
     if (conv.ws) (void) hipFree(conv.ws);
@@ -792,10 +796,29 @@ bf_status check_aov(const bf_scene *scene, const bf_launch *launch, uint32_t n_r
     return BF_OK;
 }
 
+// What a BF_FLAG_EXACT_SUM launch is refused for; asked where check_classes is
+bf_status check_sum(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders) {
+    (void) scene;
+    (void) n_renders;
+    if (!(launch->flags & BF_FLAG_EXACT_SUM)) return BF_OK;
+    if (launch->flags & (BF_FLAG_FAST | BF_FLAG_MOMENT | BF_FLAG_CLASSES | BF_FLAG_AOV))
+        return fail(BF_ERR_INVALID, "BF_FLAG_EXACT_SUM with %s: the exact-sum variants exist of the exact first-moment kernels only",
+                    (launch->flags & BF_FLAG_FAST) ? "BF_FLAG_FAST"
+                                                   : ((launch->flags & BF_FLAG_MOMENT) ? "BF_FLAG_MOMENT" : ((launch->flags & BF_FLAG_CLASSES) ? "BF_FLAG_CLASSES" : "BF_FLAG_AOV")));
+    if (launch->flags & BF_FLAG_ROLLING)
+        return fail(BF_ERR_UNSUPPORTED, "BF_FLAG_EXACT_SUM with BF_FLAG_ROLLING: the LDS window of a rolling sequence is laid out in floats; "
+                                        "render exact sums without BF_FLAG_ROLLING");
+    // a cell takes at most one addend per path of its render, and a limb holds the pieces of fewer than 2^31 addends (bf_sum.h)
+    if (launch->n_paths >= bfs::kMaxAddends)
+        return fail(BF_ERR_INVALID, "BF_FLAG_EXACT_SUM: n_paths %llu is not below 2^31, the addends a cell is exact for", (unsigned long long) launch->n_paths);
+    return BF_OK;
+}
+
 // Everything a launch (of n_renders renders, if a batch) is refused for on its own or against the scene and its open rolling sequence:
 // nothing is enqueued before these
 static bf_status check_launch(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, uint32_t n_renders, const bf_stats *stats_out) {
     const EndpointState &ends = scene->ends;
+    if (bf_status sst = check_sum(scene, launch, n_renders)) return sst;
     if (bf_status cst = check_classes(scene, launch, n_renders)) return cst;
     if (bf_status ast = check_aov(scene, launch, n_renders)) return ast;
     if (batch) {
@@ -921,6 +944,11 @@ static bf_status make_dlaunch(const bf_scene *scene, const bf_launch *launch, ui
         lp.lean = 0u;
         scene->run.last_variant = (scene->run.last_variant & ~(uint32_t) BF_VARIANT_LEAN) | (uint32_t) BF_VARIANT_AOV;
     }
+    const bool exact_sum = (launch->flags & BF_FLAG_EXACT_SUM) != 0u;
+    if (exact_sum) {                        // likewise; the limb cells join the launch in render_locked (sum_attach)
+        lp.lean = 0u;
+        scene->run.last_variant = (scene->run.last_variant & ~(uint32_t) BF_VARIANT_LEAN) | (uint32_t) BF_VARIANT_EXACT_SUM;
+    }
     lp.count = ((launch->flags & (BF_FLAG_STATS | BF_FLAG_COUNT)) || count) ? 1u : 0u;
     lp.doppler = (receive_mode && (launch->flags & BF_FLAG_DOPPLER)) ? 1u : 0u;
     lp.resample = (receive_mode && scene->ends.any_resample) ? 1u : 0u;
@@ -935,6 +963,16 @@ static bf_status make_dlaunch(const bf_scene *scene, const bf_launch *launch, ui
     // workgroup: without that every path of the launch adds to the same 5 n_classes global addresses (tools/class_ab.py: C4)
     if (n_classes && !lp.lds_hist && !receive_mode && !multi_pixel && (uint64_t) n_renders * n_classes * bfd::kRollBaseCh <= (uint64_t) bfd::kMaxLdsHist)
         lp.lds_floats = n_renders * n_classes * bfd::kRollBaseCh;
+    if (exact_sum) {
+        // limb cells of bfs::kCellFloats floats each (bf_sum.h): privatised when n_chan_all of them fit what kMaxLdsHist stands for; a
+        // 1 x 1 film that cannot still sums its five base channels per workgroup, in a table [render][5] of cells: without that every
+        // path of the launch adds to the same five global cells (the class precedent above)
+        const uint64_t cell_floats = (uint64_t) bfs::kCellFloats;
+        lp.lds_hist = ((uint64_t) lp.n_chan_all * cell_floats <= (uint64_t) bfd::kMaxLdsHist && !(launch->flags & BF_FLAG_GLOBAL_ATOMICS)) ? 1u : 0u;
+        lp.lds_floats = lp.lds_hist ? lp.n_chan_all * (uint32_t) cell_floats : 0u;
+        if (!lp.lds_hist && !receive_mode && !multi_pixel && (uint64_t) n_renders * bfd::kRollBaseCh * cell_floats <= (uint64_t) bfd::kMaxLdsHist)
+            lp.lds_floats = n_renders * bfd::kRollBaseCh * (uint32_t) cell_floats;
+    }
     return BF_OK;
 }
 
@@ -1003,6 +1041,31 @@ static bf_status aov_attach(const bf_scene *scene, uint64_t slots, bfd::DLaunch 
     return BF_OK;
 }
 
+// BF_FLAG_EXACT_SUM: the handle's limb cells for a launch of `cells` cells, zeroed on `stream` ahead of the launch's first kernel.  The
+// buffer is the handle's own and only grows; the renders of one handle are ordered on the device (order_after_last), so one buffer
+// serves them all.  The first such launch, or a larger one, allocates: it is then not asynchronous and cannot be captured into a graph.
+static bf_status sum_attach(const bf_scene *scene, uint64_t cells, hipStream_t stream) {
+    RenderState::Sum &m = scene->run.sum;
+    const uint64_t need = std::max<uint64_t>(1, cells);
+    if (m.cells < need) {
+        if (m.limbs) {
+            // as aov_attach grows the side rows: hipFree waits for the device, so an earlier launch that adds to the old cells has ended
+            (void) hipFree(m.limbs);
+            m.limbs = nullptr;
+            m.cells = 0;
+        }
+        if (hipMalloc(&m.limbs, need * sizeof(int64_t) * bfs::kLimbs) != hipSuccess) {
+            (void) hipGetLastError();
+            m.limbs = nullptr;
+            return fail(BF_ERR_NOMEM, "BF_FLAG_EXACT_SUM: %llu limb cells of %zu bytes cannot be allocated", (unsigned long long) need,
+                        sizeof(int64_t) * bfs::kLimbs);
+        }
+        m.cells = need;
+    }
+    HIP_TRY(hipMemsetAsync(m.limbs, 0, need * sizeof(int64_t) * bfs::kLimbs, stream));
+    return BF_OK;
+}
+
 // A render or batch on a handle its caller holds (BF_ENTER).  geom_stride != 0: the batch's renders read per-render geometry
 // versions, geom_stride float4 rows apart from the arrays scene->d points at (bf_mesh.cpp: render_versions; kGeom kernels).
 bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev,
@@ -1026,6 +1089,14 @@ bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf
         return mark_last(scene, stream);
     }
     const bool mega = (launch->flags & BF_FLAG_MEGAKERNEL) != 0u;
+    // BF_FLAG_EXACT_SUM: the kernels add to the handle's limb cells in place of the caller's floats; the resolve kernel behind the last
+    // of them rounds every cell once into hist_dev
+    float *const hist_out = hist_dev;
+    const bool exact_sum = (launch->flags & BF_FLAG_EXACT_SUM) != 0u;
+    if (exact_sum) {
+        if ((st = sum_attach(scene, lp.n_chan_all, stream)) != BF_OK) return st;
+        hist_dev = reinterpret_cast<float *>(scene->run.sum.limbs);
+    }
     // every counter but the sticky guard words (the last ones)
     HIP_TRY(hipMemsetAsync(scene->run.counters, 0, sizeof(unsigned long long) * bfd::CTR_GUARD, stream));
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1048,6 +1119,7 @@ bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf
         if ((st = wf_render(scene, kernels_for(launch->flags), lp, hist_dev, records_dev, stream, (launch->flags & BF_FLAG_STATS) != 0,
                             stats_out != nullptr, (launch->flags & BF_FLAG_AOV) != 0u)) != BF_OK) return st;
     }
+    if (exact_sum && launch->n_paths) HIP_TRY(bfk_sum_resolve(scene->run.sum.limbs, hist_out, lp.n_chan_all, stream));
     if (stats_out) {
         HIP_TRY(hipEventRecord(ev1, stream));
         HIP_TRY(hipEventSynchronize(ev1));
@@ -1240,6 +1312,8 @@ bf_status bf_render_converge_device(bf_scene *scene, const bf_launch *launch, fl
     if (!scene || !launch || !hist_dev || !rounds_out) return fail(BF_ERR_INVALID, "%s null argument", fn);
     if (launch->flags & BF_FLAG_FAST)
         return fail(BF_ERR_INVALID, "%s BF_FLAG_FAST: the rounds are moment renders, and BF_FLAG_MOMENT | BF_FLAG_FAST is refused", fn);
+    if (launch->flags & BF_FLAG_EXACT_SUM)
+        return fail(BF_ERR_INVALID, "%s BF_FLAG_EXACT_SUM: the rounds are moment renders, and the exact-sum variants exist of the exact first-moment kernels only", fn);
     if (launch->flags & BF_FLAG_ROLLING) return fail(BF_ERR_INVALID, "%s BF_FLAG_ROLLING: the rounds are batches, which do not roll", fn);
     if (launch->flags & BF_FLAG_CLASSES)
         return fail(BF_ERR_UNSUPPORTED, "%s BF_FLAG_CLASSES: the rounds are moment renders, which have no class variants (per-class error bars are a follow-up)", fn);
@@ -1317,6 +1391,8 @@ bf_status bf_render_converge(bf_scene *scene, const bf_launch *launch, float tar
                              uint32_t min_rounds, uint32_t max_rounds, float *hist_out, uint32_t *rounds_out,
                              double *stat_history_out, uint64_t *n_significant_out, bf_stats *stats_out) {
     if (!scene || !launch || !hist_out || !rounds_out) return fail(BF_ERR_INVALID, "bf_render_converge: null argument");
+    if (launch->flags & BF_FLAG_EXACT_SUM)
+        return fail(BF_ERR_INVALID, "bf_render_converge: BF_FLAG_EXACT_SUM: the rounds are moment renders, and the exact-sum variants exist of the exact first-moment kernels only");
     if (launch->flags & BF_FLAG_CLASSES)
         return fail(BF_ERR_UNSUPPORTED, "bf_render_converge: BF_FLAG_CLASSES: the rounds are moment renders, which have no class variants (per-class error bars are a follow-up)");
     if (launch->flags & BF_FLAG_AOV)

@@ -226,6 +226,12 @@ struct __attribute__((visibility("hidden"))) RenderState {
         float *rows = nullptr;                   // device side rows (bf_device.h: AovCtx), allocated by the first AOV launch, grown on demand
         uint64_t rows_floats = 0;
     } aov;
+    // ---- the limb cells of the handle's BF_FLAG_EXACT_SUM launches (bf_sum.h): n_chan_all cells of 72 bytes, allocated by the first such
+    // launch, grown on demand, freed with the handle; zeroed ahead of a launch's first kernel, resolved into hist_dev behind its last ----
+    struct Sum {
+        void *limbs = nullptr;
+        uint64_t cells = 0;
+    } sum;
     // ---- rolling sequence (bf_render_device with BF_FLAG_ROLLING, bf_scene_flush): see wf_roll_render ----
     struct Roll {
         bool open = false;
@@ -441,6 +447,7 @@ bf_status mark_last(const bf_scene *scene, hipStream_t stream);
 bf_status close_sequence(const bf_scene *scene, hipStream_t stream);
 bf_status check_classes(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders);      // BF_FLAG_CLASSES refusals, before any device work
 bf_status check_aov(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders);          // BF_FLAG_AOV refusals, likewise
+bf_status check_sum(const bf_scene *scene, const bf_launch *launch, uint32_t n_renders);          // BF_FLAG_EXACT_SUM refusals, likewise
 bf_status render_locked(const bf_scene *scene, const bf_launch *launch, const bf_batch *batch, float *hist_dev, bf_path_record *records_dev,
                         void *stream_, bf_stats *stats_out, uint32_t geom_stride = 0);
 void fill_stats(const bf_scene *scene, const unsigned long long *c, uint64_t n_paths, bf_stats *st);

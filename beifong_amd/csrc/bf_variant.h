@@ -5,12 +5,12 @@
 
 namespace bfv {
 // the bits of bf_device.h's variant word (bf_kernels.hip asserts that they are the same numbers)
-constexpr int kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64, kClass = 128, kAov = 256;
+constexpr int kWide = 4, kLean = 8, kMulti = 16, kGeom = 32, kMoment = 64, kClass = 128, kAov = 256, kSum = 512;
 // tail only: the two-waves-per-SIMD build of the general kernel, <S, true, P, 2>; never with a variant bit
 constexpr int kTailTwo = 1 << 16;
 constexpr int kInvalid = -1;      // the launch is refused (hipErrorInvalidValue)
 
-enum Feature { kPlain = 0, kFeatMoment = 1, kFeatClass = 2, kFeatAov = 3 };      // which family of launchers was called
+enum Feature { kPlain = 0, kFeatMoment = 1, kFeatClass = 2, kFeatAov = 3, kFeatSum = 4 };      // which family of launchers was called
 
 struct Shape {
     bool geom;             // DLaunch::geom_stride != 0
@@ -28,6 +28,7 @@ inline int render_variant(Feature f, const Shape &s) {
         case kFeatMoment: return kMoment | general_form(s);
         case kFeatClass: return kClass | general_form(s);
         case kFeatAov: return (s.receive_raw || s.roll) ? kInvalid : (kAov | general_form(s));
+        case kFeatSum: return (s.multi || s.roll) ? kInvalid : (kSum | general_form(s));
         default: return general_form(s);
     }
 }
@@ -38,6 +39,7 @@ inline int render_variant(Feature f, const Shape &s) {
 inline int tail_variant(Feature f, const Shape &s) {
     if (f == kFeatClass) return (s.multi || s.roll) ? kInvalid : (kClass | general_form(s));
     if (f == kFeatAov) return (s.receive_raw || s.roll) ? kInvalid : (kAov | general_form(s));
+    if (f == kFeatSum) return (s.multi || s.roll) ? kInvalid : (kSum | general_form(s));
     const int m = f == kFeatMoment ? kMoment : 0;
     if (s.geom) return m | kGeom | (s.wide ? kWide : (s.lean ? kLean : 0));
     if (s.multi) return m | kMulti;

@@ -721,10 +721,11 @@ extern "C" int bfdbg_shade_lane_profile(unsigned long long *out, int clear) {
 }
 #endif
 
-// moment: the kMoment variants (BF_FLAG_MOMENT; bfk_wf_shade_moment below); classed: the kClass variants (BF_FLAG_CLASSES; bfk_wf_shade_class)
+// moment: the kMoment variants (BF_FLAG_MOMENT; bfk_wf_shade_moment below); classed: the kClass variants (BF_FLAG_CLASSES; bfk_wf_shade_class);
+// aov: the kAov variants (BF_FLAG_AOV; bfk_wf_shade_aov); sum: the kSum variants (BF_FLAG_EXACT_SUM; bfk_wf_shade_sum)
 static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                  hipStream_t stream, int waves, bool moment, bool classed = false, bool aov = false) {
+                                  hipStream_t stream, int waves, bool moment, bool classed = false, bool aov = false, bool sum = false) {
     // `waves`: register budget of the shading kernel (waves per SIMD); 3 is the sweet spot (168 VGPRs)
     const bool rx = lp->mode == BF_MODE_RECEIVE_RAW;
 #define BF_SHADE_LAUNCH_RX(F, W, RX_)                                                                                              \
@@ -817,8 +818,26 @@ static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp,
         return hipGetLastError();
     }
 #undef BF_SHADE_LAUNCH_AOV_F
+    // BF_FLAG_EXACT_SUM (never with BF_FLAG_FAST, BF_FLAG_MOMENT, BF_FLAG_CLASSES, BF_FLAG_AOV or a rolling sequence): the kSum variants
+    // of the same general forms, both mode classes
+#define BF_SHADE_LAUNCH_SUM(F, V)                             \
+    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kSum | (V));    \
+    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kSum | (V))
+#define BF_SHADE_LAUNCH_SUM_F(V)                     \
+    if (first) { BF_SHADE_LAUNCH_SUM(1, V); }        \
+    else { BF_SHADE_LAUNCH_SUM(0, V); }
+    if (sum) {
+        if (first >= 2 || lp->multi || lp->roll) return hipErrorInvalidValue;
+        if (lp->geom_stride && lp->wide) { BF_SHADE_LAUNCH_SUM_F(bfd::kGeom | bfd::kWide) }
+        else if (lp->geom_stride) { BF_SHADE_LAUNCH_SUM_F(bfd::kGeom) }
+        else if (lp->wide) { BF_SHADE_LAUNCH_SUM_F(bfd::kWide) }
+        else { BF_SHADE_LAUNCH_SUM_F(0) }
+        return hipGetLastError();
+    }
+#undef BF_SHADE_LAUNCH_SUM_F
+#undef BF_SHADE_LAUNCH_SUM
 #else
-    if (moment || classed || aov) return hipErrorInvalidValue;
+    if (moment || classed || aov || sum) return hipErrorInvalidValue;
 #endif
     if (lp->geom_stride) {
         // per-render geometry versions (bf_render_motion_batch_device): three waves per SIMD; never a rolling sequence, so
@@ -887,6 +906,11 @@ extern "C" hipError_t bfk_wf_shade_aov(const bfd::DScene *sc, const bfd::DLaunch
                                        float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
                                        hipStream_t stream, int waves) {
     return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, false, true);
+}
+extern "C" hipError_t bfk_wf_shade_sum(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
+                                       float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
+                                       hipStream_t stream, int waves) {
+    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, false, false, true);
 }
 #endif
 

@@ -31,7 +31,7 @@ int main(int argc, char **argv) {
     // options of src/mitsuba/mitsuba.cpp:171-183 (short and long forms); --gpus is ours
     std::string variant_name = "scalar_rgb", output;
     std::vector<std::string> scene_files;
-    bool do_receive = false, fast = false;
+    bool do_receive = false, fast = false, exact_sum = false;
     int n_gpus = 1;
     size_t endpoint_i = 0;                      // -s: index into scene->sensors() (with -r: scene->receivers())
     xml::ParameterList params;
@@ -42,6 +42,7 @@ int main(int argc, char **argv) {
         else if (is("-o", "--output") && i + 1 < argc) output = argv[++i];
         else if (is("-r", "--receiver")) do_receive = true;
         else if (a == "--fast") fast = true;                                 // BF_FLAG_FAST: the fast-arithmetic kernels (ours)
+        else if (a == "--exact-sum") exact_sum = true;                       // BF_FLAG_EXACT_SUM: exact, bit-reproducible sums (ours)
         else if (is("-s", "--sensor") && i + 1 < argc) endpoint_i = (size_t) std::max(0, atoi(argv[++i]));
         else if (is("-v", "--verbose")) set_log_level(Debug);
         else if (is("-u", "--update")) {}                                    // scene version upgrade: the loader takes any version
@@ -57,7 +58,7 @@ int main(int argc, char **argv) {
             }
             params.emplace_back(kv.substr(0, k), kv.substr(k + 1));
         } else if (is("-h", "--help")) {
-            printf("usage: bfrender [-m variant] [-D name=value]... [-s index] [-r] [--gpus N] [--fast] [-o out.exr|out.npy] [-v] scene.xml...\n");
+            printf("usage: bfrender [-m variant] [-D name=value]... [-s index] [-r] [--gpus N] [--fast] [--exact-sum] [-o out.exr|out.npy] [-v] scene.xml...\n");
             return 0;
         } else {
             scene_files.push_back(a);
@@ -79,6 +80,12 @@ int main(int argc, char **argv) {
             auto *si = dynamic_cast<SamplingIntegrator *>(in);
             if (!si) Throw("--fast: the scene's integrator does not render on the GPU kernels");
             si->set_fast_math(true);
+        }
+        if (exact_sum) {
+            auto *si = dynamic_cast<SamplingIntegrator *>(in);
+            if (!si) Throw("--exact-sum: the scene's integrator does not render on the GPU kernels");
+            si->set_exact_sum(true);
+            si->check_exact_sum();      // what the option is refused with, by name, before anything renders
         }
         const float *data;
         unsigned rows, cols, ch;

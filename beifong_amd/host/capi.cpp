@@ -185,6 +185,8 @@ int bfh_integrator_launch(void *integrator, void *endpoint, bf_launch *out) {
         out->time_c = 3.0e8f;
         in->configure(*out);
         if (in->fast_math()) out->flags |= BF_FLAG_FAST;
+        in->check_exact_sum();
+        if (in->exact_sum()) out->flags |= BF_FLAG_EXACT_SUM;
         if (auto *se = dynamic_cast<Sensor *>((Object *) endpoint)) {
             out->n_paths = se->sampler()->sample_count();
             out->seed = se->sampler()->base_seed();

@@ -59,6 +59,7 @@ public:
         m_integrator->configure(lp);
         if (lp.flags & BF_FLAG_MOMENT) Throw("aov: a nested \"moment\" integrator is refused: the AOV kernels carry no second moments (BF_FLAG_AOV | BF_FLAG_MOMENT)");
         if (lp.flags & BF_FLAG_AOV) Throw("aov: a nested \"aov\" integrator is refused: one table per render");
+        check_exact_sum();      // "exact_sum" on the aov integrator or below it: refused by name
     }
     std::vector<std::string> aov_names() const override {
         std::vector<std::string> r = m_names;
@@ -77,6 +78,7 @@ public:
     int max_depth() const override { return m_integrator->max_depth(); }
     bool doppler() const override { return m_integrator->doppler(); }
     bool fast_math() const override { return SamplingIntegrator::fast_math() || m_integrator->fast_math(); }
+    bool exact_sum() const override { return SamplingIntegrator::exact_sum() || m_integrator->exact_sum(); }
     int rr_depth() const override { return m_integrator->rr_depth(); }
 private:
     ref<SamplingIntegrator> m_integrator;

@@ -20,6 +20,7 @@ public:
         if (fast_math())
             Throw("moment: \"fast_math\" on the moment integrator or below it is refused: the fast-arithmetic tolerance contract "
                   "says nothing about squared samples (BF_FLAG_MOMENT | BF_FLAG_FAST)");
+        check_exact_sum();      // "exact_sum" on the moment integrator or below it: refused by name
         // render until converged (not reference properties; bf_render_converge).  rel_stderr = 0: one render, as ever
         m_converge.rel_stderr = props.float_("rel_stderr", 0.f);
         if (!(m_converge.rel_stderr >= 0.f)) Throw("moment: \"rel_stderr\" must not be negative (0 = off)");
@@ -62,6 +63,7 @@ public:
     int max_depth() const override { return m_integrator->max_depth(); }
     bool doppler() const override { return m_integrator->doppler(); }
     bool fast_math() const override { return SamplingIntegrator::fast_math() || m_integrator->fast_math(); }
+    bool exact_sum() const override { return SamplingIntegrator::exact_sum() || m_integrator->exact_sum(); }
     int rr_depth() const override { return m_integrator->rr_depth(); }
 private:
     ref<SamplingIntegrator> m_integrator;

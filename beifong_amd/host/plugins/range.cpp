@@ -15,6 +15,7 @@ public:
         m_dr = props.float_("dr", -1.f);
         m_bins = (int) props.int_("bins", -1);
         if (m_bins <= 0 || !(m_dr > 0.f)) Throw("range: 'dr' and 'bins' must be positive");
+        check_exact_sum();
     }
     std::vector<std::string> aov_names() const override {
         std::vector<std::string> r = m_integrator->aov_names();
@@ -29,6 +30,7 @@ public:
     int max_depth() const override { return m_integrator->max_depth(); }
     bool doppler() const override { return m_integrator->doppler(); }
     bool fast_math() const override { return SamplingIntegrator::fast_math() || m_integrator->fast_math(); }
+    bool exact_sum() const override { return SamplingIntegrator::exact_sum() || m_integrator->exact_sum(); }
     int rr_depth() const override { return m_integrator->rr_depth(); }
 private:
     ref<SamplingIntegrator> m_integrator;

@@ -12,6 +12,7 @@ public:
             m_integrator = in;
         }
         if (!m_integrator) Throw("Must specify a sub-integrator!");
+        check_exact_sum();
     }
     std::vector<std::string> aov_names() const override {
         std::vector<std::string> r = m_integrator->aov_names();
@@ -28,6 +29,7 @@ public:
     int max_depth() const override { return m_integrator->max_depth(); }
     bool doppler() const override { return m_integrator->doppler(); }
     bool fast_math() const override { return SamplingIntegrator::fast_math() || m_integrator->fast_math(); }
+    bool exact_sum() const override { return SamplingIntegrator::exact_sum() || m_integrator->exact_sum(); }
     int rr_depth() const override { return m_integrator->rr_depth(); }
 private:
     ref<SamplingIntegrator> m_integrator;

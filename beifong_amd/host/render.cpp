@@ -685,6 +685,29 @@ SamplingIntegrator::SamplingIntegrator(const Properties &props) : Integrator(pro
     m_doppler = props.bool_("doppler", false);
     // not a reference property: the kernels' fast-arithmetic build (BF_FLAG_FAST); false = bit-identical to the oracle
     m_fast_math = props.bool_("fast_math", false);
+    // not a reference property: exact, bit-reproducible sums in the film / ADC (BF_FLAG_EXACT_SUM)
+    m_exact_sum = props.bool_("exact_sum", false);
+    if (m_exact_sum && m_fast_math)
+        Throw("\"exact_sum\" with \"fast_math\" is refused: the exact-sum kernels exist of the exact build only (BF_FLAG_EXACT_SUM | BF_FLAG_FAST)");
+    if (m_exact_sum && gpu_count() > 1)
+        Throw("\"exact_sum\" renders on one GPU: the shards' all-reduce of floats would round once per shard (gpu_count is %d)", gpu_count());
+}
+
+void SamplingIntegrator::check_exact_sum() const {
+    if (!exact_sum()) return;
+    if (fast_math())
+        Throw("\"exact_sum\" with \"fast_math\" on the same integrator, above or below it, is refused: the exact-sum kernels exist of the "
+              "exact build only (BF_FLAG_EXACT_SUM | BF_FLAG_FAST)");
+    bf_launch lp{};
+    configure(lp);
+    if (lp.flags & BF_FLAG_MOMENT)
+        Throw("\"exact_sum\" with a \"moment\" integrator above or below it is refused: the exact-sum kernels carry no second moments "
+              "(BF_FLAG_EXACT_SUM | BF_FLAG_MOMENT)");
+    if (lp.flags & BF_FLAG_AOV)
+        Throw("\"exact_sum\" with an \"aov\" integrator above or below it is refused: the exact-sum kernels carry no AOV channels "
+              "(BF_FLAG_EXACT_SUM | BF_FLAG_AOV)");
+    if (gpu_count() > 1)
+        Throw("\"exact_sum\" renders on one GPU: the shards' all-reduce of floats would round once per shard (gpu_count is %d)", gpu_count());
 }
 
 void SamplingIntegrator::run(Scene *scene, const Endpoint *endpoint, const bf_launch &lp, float *hist) {
@@ -757,6 +780,8 @@ bool SamplingIntegrator::render(Scene *scene, Sensor *sensor) {
     lp.time_c = 3.0e8f;
     configure(lp);
     if (fast_math()) lp.flags |= BF_FLAG_FAST;
+    check_exact_sum();
+    if (exact_sum()) lp.flags |= BF_FLAG_EXACT_SUM;
     if (lp.mode == BF_MODE_RECEIVE_RAW) Throw("this integrator only supports receive(), not render()");
     // (BF_FLAG_AOV: the K AOV floats and nested.R G B A on top — the same count bf_scene_launch_channels gives once the table is set)
     uint32_t n = bf_launch_channels(&lp);
@@ -780,6 +805,8 @@ void SamplingIntegrator::receive_launch(const Receiver *receiver, bf_launch &lp)
     if (rt == "mix_resample") lp.flags |= BF_FLAG_MIX_RESAMPLE;
     if (doppler()) lp.flags |= BF_FLAG_DOPPLER;
     if (fast_math()) lp.flags |= BF_FLAG_FAST;
+    check_exact_sum();
+    if (exact_sum()) lp.flags |= BF_FLAG_EXACT_SUM;
     lp.color_mode = BF_COLOR_MONO;
     lp.n_paths = receiver->sampler()->sample_count();
     lp.seed = receiver->sampler()->base_seed();

@@ -317,6 +317,13 @@ public:
     /// bit-equality with the oracle
     virtual bool fast_math() const { return m_fast_math; }
     void set_fast_math(bool on) { m_fast_math = on; }
+    /// "exact_sum" (not a reference property, default false): BF_FLAG_EXACT_SUM for render() and receive() — every cell of the film /
+    /// ADC is the exact sum of its samples rounded once, bit-reproducible from run to run (include/beifong_hip.h at the flag)
+    virtual bool exact_sum() const { return m_exact_sum; }
+    void set_exact_sum(bool on) { m_exact_sum = on; }
+    /// what the library would refuse an exact-sum launch for, refused here by the option's name: "fast_math", a "moment" or "aov"
+    /// integrator above or below, more than one GPU.  Wrappers call it once their sub-integrator is known; render() / receive() again
+    void check_exact_sum() const;
     /// non-null with rel_stderr > 0: render until converged (the moment integrator alone offers it)
     virtual const ConvergeSpec *converge() const { return nullptr; }
     const ConvergeResult &last_converge() const { return m_converge; }
@@ -331,6 +338,7 @@ protected:
     int m_max_depth = -1, m_rr_depth = 5;
     bool m_doppler = false;
     bool m_fast_math = false;
+    bool m_exact_sum = false;
     uint32_t m_block_size = 0;
     size_t m_samples_per_pass = (size_t) -1;
     ConvergeResult m_converge;

@@ -388,6 +388,36 @@ enum {
                                   BF_ERR_INVALID; with BF_FLAG_ROLLING, by the sharded renders and by the converge renders:
                                   BF_ERR_UNSUPPORTED (a rolling sequence's LDS window and base-channel table are laid out for the
                                   plain channels; shards and converge rounds are built on those and on moment renders). */
+    BF_FLAG_EXACT_SUM = 4096u, /* exact-sum render: every histogram cell is fl(sum of its addends), the EXACT sum rounded once to fp32,
+                                  nearest-even, instead of an fp32 sum in the order the atomics land.  The addends and the binning
+                                  rule are the plain render's; the value of a cell is a pure function of the launch: the same bits
+                                  on every run and on every route (tail or no tail, any pool size, BF_FLAG_MEGAKERNEL,
+                                  BF_FLAG_GLOBAL_ATOMICS, LDS or global accumulation), and a batch is bit-identical to its
+                                  stand-alone renders.  A cell is accumulated as a 576-bit fixed-point integer (nine 64-bit limbs,
+                                  bit i weighs 2^(i - 149): every finite fp32 is an integer there) by relaxed integer atomics and
+                                  rounded by a resolve kernel behind the launch's last kernel: subnormal results are kept, a
+                                  magnitude at or above 2^128 - 2^103 is +-inf, an exact zero is +0.0.  hist_dev is accumulated
+                                  into, as ever: a cell that received an addend comes back as fl(old + sum), one rounding; a cell
+                                  without (non-zero) addends is not written.  Counting is exact too: W of a 1 x 1 film at 2^25
+                                  paths is 33554432, where the fp32 sum stops at 16777216.  capi.exact_sum is the specification;
+                                  bf_exact_sum / bf_exact_sum_host below run the same accumulator on caller-given addends.
+                                  The limb cells (72 bytes per float of the launch's histogram) belong to the handle, grow on
+                                  demand and are freed with it; the first exact-sum launch of a handle, or a larger one, allocates
+                                  and is then not asynchronous and cannot be captured into a graph.  LDS privatisation is decided
+                                  on n_renders * channels CELLS: 682 fit (C2's 261 do, a C4 shard's 4101 take global limbs, their
+                                  five base channels a per-workgroup table).  Per-path records are unchanged.
+                                  Honoured by bf_render / bf_render_batch / bf_render_motion_batch / bf_render_deform_batch /
+                                  bf_render_skin_batch / bf_render_morph_batch and their _device forms, in all five modes, on
+                                  1 x 1 and W x H films and on ADCs, with crop and ADC windows and wide filters, with
+                                  BF_FLAG_GLOBAL_ATOMICS, BF_FLAG_MEGAKERNEL, BF_FLAG_STATS, BF_FLAG_COUNT, BF_FLAG_DOPPLER and
+                                  BF_FLAG_MIX_RESAMPLE.  The exact-sum variants exist of the general kernels only:
+                                  bf_stats.kernel_variant carries BF_VARIANT_EXACT_SUM and never BF_VARIANT_LEAN.
+                                  Refused before anything is enqueued, an open rolling sequence staying intact: with BF_FLAG_FAST,
+                                  BF_FLAG_MOMENT (the converge renders force it), BF_FLAG_CLASSES or BF_FLAG_AOV, or with
+                                  n_paths >= 2^31 per render (the limbs' headroom): BF_ERR_INVALID; with BF_FLAG_ROLLING (the
+                                  LDS window of a rolling sequence is laid out in floats) and by the sharded renders (an
+                                  all-reduce of floats would round once per shard; reducing limbs is the follow-up):
+                                  BF_ERR_UNSUPPORTED; limb cells that cannot be allocated: BF_ERR_NOMEM. */
     BF_FLAG_DOPPLER = 8u       /* receive modes: the Doppler hook the reference carries commented out
                                   ("Took doppler out to test", pathtimefrequency.cpp:124-126,141-144,180-183):
                                   the path's wavelength is shifted by Shape::doppler(si) =
@@ -446,10 +476,12 @@ typedef struct bf_stats {
                                   BF_VARIANT_FAST when the fast-arithmetic build ran (BF_FLAG_FAST) and with BF_VARIANT_MOMENT
                                   when the kernels' second-moment variants ran (BF_FLAG_MOMENT); BF_VARIANT_CLASS = the class
                                   variants ran (BF_FLAG_CLASSES: general kernels, so never with BF_VARIANT_LEAN); BF_VARIANT_AOV =
-                                  the AOV variants ran (BF_FLAG_AOV: likewise)                                                 */
+                                  the AOV variants ran (BF_FLAG_AOV: likewise); BF_VARIANT_EXACT_SUM = the exact-sum variants ran
+                                  (BF_FLAG_EXACT_SUM: likewise)                                                                */
     uint32_t reserved_;
 } bf_stats;
-enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4, BF_VARIANT_MOMENT = 8, BF_VARIANT_CLASS = 16, BF_VARIANT_AOV = 32 };
+enum { BF_VARIANT_LEAN = 1, BF_VARIANT_WIDE = 2, BF_VARIANT_FAST = 4, BF_VARIANT_MOMENT = 8, BF_VARIANT_CLASS = 16, BF_VARIANT_AOV = 32,
+       BF_VARIANT_EXACT_SUM = 64 };
 
 typedef struct bf_scene_info {
     uint32_t n_shapes, n_rects, n_triangles, n_bvh_nodes;
@@ -1094,6 +1126,19 @@ bf_status bf_ray_intersect(const bf_scene *scene, uint64_t n, const float *rays,
  * wignertransmitter.cpp signal models).  op: 0 sin, 1 cos, 2 acos, 3 exp, 4 log,
  * 5 erf, 6 tan.  Needs no scene. */
 bf_status bf_eval_elementary(int op, uint64_t n, const float *x, float *y);
+
+/* The exact accumulator of BF_FLAG_EXACT_SUM on caller-given addends (conformance checks; needs no scene).  Host arrays:
+ * out[c] = fl(sum of value[i] over cell[i] == c), the exact sum rounded once to fp32 (nearest-even; subnormals kept; +-inf from
+ * 2^128 - 2^103 on), and +0.0 for a cell without addends.
+ *   bf_exact_sum_host  the accumulator's arithmetic (csrc/bf_sum.h) on the CPU; needs no device.
+ *   bf_exact_sum       on the device, through the device functions the exact-sum render kernels add with and their resolve kernel:
+ *                      a grid-stride launch over the addends.  in_lds != 0: the workgroups privatise the cells in LDS and flush
+ *                      limbs, where n_cells cells fit the 48 KiB a render privatises in (682); otherwise, and with in_lds = 0,
+ *                      every addend goes to the global limbs.  Synchronous.
+ * BF_ERR_INVALID for a null pointer (n_cells = 0 included), a cell index that is not below n_cells, a non-finite value, or
+ * n >= 2^31 (the limbs' headroom). */
+bf_status bf_exact_sum_host(uint64_t n, const uint32_t *cell, const float *value, uint32_t n_cells, float *out);
+bf_status bf_exact_sum(uint64_t n, const uint32_t *cell, const float *value, uint32_t n_cells, uint32_t in_lds, float *out);
 
 /* ---------------- plugin-level queries on the device ------------------------------------------------------------------
  * The BSDF, emitter and sensor functions the render kernels call, one query per lane, general kernels (every material,
