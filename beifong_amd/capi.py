@@ -155,6 +155,11 @@ class bf_batch(C.Structure):
     _fields_ = [("n_renders", C.c_uint32), ("seeds", C.POINTER(C.c_uint64)), ("mesh_offsets", C.POINTER(C.c_float))]
 
 
+class bf_arrival_bins(C.Structure):
+    _fields_ = [("axis_u", C.c_float * 3), ("axis_v", C.c_float * 3), ("u0", C.c_float), ("u1", C.c_float), ("v0", C.c_float),
+                ("v1", C.c_float), ("n_u", C.c_uint32), ("n_v", C.c_uint32)]
+
+
 # include/beifong_hip.h: BF_ABI_MATERIAL .. BF_ABI_BATCH, in that order
 ABI_STRUCTS = [bf_material, bf_shape, bf_emitter, bf_sensor, bf_scene_desc, bf_launch, bf_path_record, bf_stats, bf_scene_info, bf_batch]
 
@@ -175,7 +180,7 @@ EXPORTED_SYMBOLS = [
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
     "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
     "bf_render_converge_device", "bf_render_converge", "bf_converge_statistic_device",
-    "bf_scene_set_classes", "bf_scene_launch_channels", "bf_aov_floats", "bf_scene_set_aovs",
+    "bf_scene_set_classes", "bf_scene_set_arrival_classes", "bf_scene_launch_channels", "bf_aov_floats", "bf_scene_set_aovs",
     "bf_exact_sum_host", "bf_exact_sum",
 ]
 
@@ -221,6 +226,7 @@ def load_library(path=None):
     lib.bf_launch_channels.argtypes = [C.POINTER(bf_launch)]
     lib.bf_launch_channels.restype = C.c_uint32
     lib.bf_scene_set_classes.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp]
+    lib.bf_scene_set_arrival_classes.argtypes = [vp, C.POINTER(bf_arrival_bins), vp]
     lib.bf_scene_launch_channels.argtypes = [vp, C.POINTER(bf_launch)]
     lib.bf_scene_launch_channels.restype = C.c_uint32
     lib.bf_aov_floats.argtypes = [C.c_uint32, vp]
@@ -504,6 +510,60 @@ def split_classes(hist, launch, n_classes, lib=None):
     if n_classes < 1 or hist.shape[-1] != n_classes * n:
         raise ValueError(f"a histogram of {hist.shape[-1]} floats per render is not {n_classes} classes x {n} channels")
     return hist.reshape(hist.shape[:-1] + (n_classes, n))
+
+
+def arrival_bins(axis_u, axis_v, n_u, n_v, window):
+    """bf_arrival_bins: the arrival table of Scene.set_arrival_classes.  axis_u, axis_v: world-space axes, used as given;
+    window = (u0, u1, v0, v1): the bins cut [u0, u1) x [v0, v1) into n_u x n_v; n_u * n_v + 1 classes, the last one for the
+    directions outside the window."""
+    b = bf_arrival_bins()
+    au, av = (np.asarray(a, np.float32).reshape(3) for a in (axis_u, axis_v))
+    b.axis_u, b.axis_v = (C.c_float * 3)(*au.tolist()), (C.c_float * 3)(*av.tolist())
+    b.u0, b.u1, b.v0, b.v1 = (float(np.float32(x)) for x in window)
+    b.n_u, b.n_v = int(n_u), int(n_v)
+    return b
+
+
+def arrival_n_classes(bins):
+    return int(bins.n_u) * int(bins.n_v) + 1
+
+
+def arrival_classes(d, bins):
+    """The class of a path whose primary ray has direction d (float32[n, 3], world space) under the arrival table `bins`
+    (arrival_bins): THE SPECIFICATION of bf_scene_set_arrival_classes, in numpy float32 — every product and sum rounded on its
+    own, no FMA:
+        u  = (d.x a.x + d.y a.y) + d.z a.z            a = axis_u; v likewise with axis_v
+        su = float32(n_u) / (u1 - u0)                 sv likewise
+        tu = (u - u0) * su, tv = (v - v0) * sv
+        inside = 0 <= tu < n_u and 0 <= tv < n_v      (a NaN is outside)
+        class  = uint32(tv) * n_u + uint32(tu) if inside else n_u * n_v
+    Returns int64[n]."""
+    f = np.float32
+    d = np.asarray(d, f).reshape(-1, 3)
+    n_u, n_v = int(bins.n_u), int(bins.n_v)
+    with np.errstate(all="ignore"):
+        def coordinate(axis, lo, hi, n):
+            a = [f(x) for x in axis]
+            u = (d[:, 0] * a[0] + d[:, 1] * a[1]) + d[:, 2] * a[2]
+            s = f(n) / (f(hi) - f(lo))
+            return (u - f(lo)) * s
+        tu = coordinate(bins.axis_u, bins.u0, bins.u1, n_u)
+        tv = coordinate(bins.axis_v, bins.v0, bins.v1, n_v)
+        assert tu.dtype == f and tv.dtype == f
+        inside = (tu >= f(0)) & (tu < f(n_u)) & (tv >= f(0)) & (tv < f(n_v))
+    iu = np.where(inside, tu, f(0)).astype(np.int64)      # (truncation: the values are in [0, n))
+    iv = np.where(inside, tv, f(0)).astype(np.int64)
+    return np.where(inside, iv * n_u + iu, n_u * n_v)
+
+
+def arrival_bins_for(sd, n_u, n_v, window):
+    """The arrival table whose axes are the sensor's own tangents: the normalised first two columns of the to_world of its
+    rectangle (flux meters, receivers) or of the camera itself, computed in float64 and rounded once.  u and v are then the
+    direction cosines of the arriving ray against the sensor's x and y axes: 0, 0 is the boresight.  `sd`: a SceneDesc."""
+    s = sd.sensor
+    m = np.asarray(list(sd.shapes[int(s.shape)].to_world if int(s.shape) >= 0 else s.to_world), np.float64).reshape(4, 4)
+    cols = [m[:3, k] / np.linalg.norm(m[:3, k]) for k in (0, 1)]
+    return arrival_bins(cols[0].astype(np.float32), cols[1].astype(np.float32), n_u, n_v, window)
 
 
 def aov_types(types):
@@ -962,6 +1022,16 @@ class Scene:
             n_classes = max(int(sc.max()) if sc.size else 0, int(miss_class)) + 1
         check(self.lib, self.lib.bf_scene_set_classes(self.handle, int(n_classes), _ptr(sc), int(miss_class), _stream(stream)),
               "bf_scene_set_classes")
+
+    def set_arrival_classes(self, axis_u, axis_v=None, n_u=None, n_v=None, window=None, stream=0):
+        """bf_scene_set_arrival_classes: the class of a path is the bin of its primary ray's direction d in the window
+        (u0, u1, v0, v1) of (d . axis_u, d . axis_v), cut into n_u x n_v bins; the last of the n_u * n_v + 1 classes takes the
+        directions outside (arrival_classes is the rule).  World-space axes: they do not follow update_endpoints.  The first
+        argument may be a bf_arrival_bins (arrival_bins, arrival_bins_for) instead.  Replaces a set_classes table and is
+        replaced by one; clear_classes clears either.  Returns the number of classes."""
+        b = axis_u if isinstance(axis_u, bf_arrival_bins) else arrival_bins(axis_u, axis_v, n_u, n_v, window)
+        check(self.lib, self.lib.bf_scene_set_arrival_classes(self.handle, C.byref(b), _stream(stream)), "bf_scene_set_arrival_classes")
+        return arrival_n_classes(b)
 
     def set_aovs(self, types, stream=0):
         """bf_scene_set_aovs: the AOVs every pixel of a BF_FLAG_AOV render carries behind X Y Z A W, in this order (BF_AOV_*

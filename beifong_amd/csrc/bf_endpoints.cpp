@@ -41,6 +41,8 @@ void set_classes_ptr(bfd::DScene &d, const uint32_t *p) {
     d.class_lo = (uint32_t) (uintptr_t) p;
     d.class_hi = (uint32_t) ((uint64_t) (uintptr_t) p >> 32);
 }
+// words of the handle's class array: shape_class[n_shapes] or the arrival table (bf_arrival.h), whichever form is installed
+size_t class_words(uint32_t n_shapes) { return std::max<size_t>(bfa::kWords, n_shapes); }
 
 // what bf_scene_create and bf_scene_update_endpoints both require of the material table and the film (a back_material out of
 // range would send the kernels' load_material past the device table)
@@ -66,6 +68,26 @@ bf_status stage_copy(const bf_scene *sc, void *dst, const void *src, size_t byte
     std::memcpy(stg->host, src, bytes);
     HIP_TRY(hipMemcpyAsync(dst, stg->host, bytes, hipMemcpyHostToDevice, stream));
     return stage_release_after(stg, stream);
+}
+
+// what bf_scene_set_classes and bf_scene_set_arrival_classes share: the open rolling sequence ends (its renders were issued without
+// classes; the table is not theirs to see change), the handle's device array exists, `words` go into it in stream order
+bf_status install_classes(bf_scene *scene, const void *words, size_t bytes, uint32_t class_info, hipStream_t stream) {
+    bf_status st = order_after_last(scene, stream);
+    if (st == BF_OK) st = close_sequence(scene, stream);
+    if (st != BF_OK) return st;
+    if (!class_info) {
+        scene->d.class_info = 0u;      // (the device array stays with the handle)
+        return BF_OK;
+    }
+    EndpointState &e = scene->ends;
+    if (!e.classes) {
+        HIP_TRY(hipMalloc((void **) &e.classes, sizeof(uint32_t) * class_words(e.n_shapes)));
+        set_classes_ptr(scene->d, e.classes);
+    }
+    if (bytes && (st = stage_copy(scene, e.classes, words, bytes, stream)) != BF_OK) return st;
+    scene->d.class_info = class_info;
+    return mark_last(scene, stream);
 }
 
 // Phased-array tables arrive as host pointers inside the flattened records: copy them to the device (allocating on
@@ -440,7 +462,7 @@ bf_status endpoints_clone(const bf_scene *src, bf_scene *sc) {
     if ((st = repoint(s.sensor_array_dev, s.sensor_array_n, &e.sensor_array_dev, e.lay.o_sensor + offsetof(bfd::DSensor, velems))) != BF_OK) return st;
     if (e.sensor_array_dev) e.sensor_host.velems = e.sensor_array_dev;
     // the class table (bf_scene_set_classes): the clone's own copy; class_info came with src->d
-    if ((st = dup(s.classes, sizeof(uint32_t) * std::max(1u, s.n_shapes), &e.classes)) != BF_OK) return st;
+    if ((st = dup(s.classes, sizeof(uint32_t) * class_words(s.n_shapes), &e.classes)) != BF_OK) return st;
     set_classes_ptr(sc->d, e.classes);
     if (!e.classes) sc->d.class_info = 0u;
     return BF_OK;
@@ -515,22 +537,42 @@ bf_status bf_scene_set_classes(bf_scene *scene, uint32_t n_classes, const uint32
     }
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
-    // an open rolling sequence ends here (its renders were issued without classes; the table is not theirs to see change)
-    bf_status st = order_after_last(scene, stream);
-    if (st == BF_OK) st = close_sequence(scene, stream);
-    if (st != BF_OK) return st;
-    if (!n_classes) {
-        scene->d.class_info = 0u;      // (the device array stays with the handle)
-        return BF_OK;
-    }
-    EndpointState &e = scene->ends;
-    if (!e.classes) {
-        HIP_TRY(hipMalloc((void **) &e.classes, sizeof(uint32_t) * std::max(1u, n_shapes)));
-        set_classes_ptr(scene->d, e.classes);
-    }
-    if (n_shapes && (st = stage_copy(scene, e.classes, shape_class, sizeof(uint32_t) * n_shapes, stream)) != BF_OK) return st;
-    scene->d.class_info = n_classes | (miss_class << 16);
-    return mark_last(scene, stream);
+    return install_classes(scene, shape_class, n_classes ? sizeof(uint32_t) * n_shapes : 0u, n_classes ? (n_classes | (miss_class << 16)) : 0u, stream);
+}
+
+// The table's arrival form: the twelve words of bfa::Table (bf_arrival.h) in the same device array, the form in bit 31 of class_info;
+// miss_class is the class outside the window.  The scales are computed here, once.
+bf_status bf_scene_set_arrival_classes(bf_scene *scene, const bf_arrival_bins *bins, void *stream_) {
+    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: null scene");
+    if (!bins) return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: null bins");
+    if (bins->n_u == 0 || bins->n_v == 0) return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: n_u = %u, n_v = %u: both must be at least 1", bins->n_u, bins->n_v);
+    if ((uint64_t) bins->n_u * bins->n_v + 1u > BF_MAX_CLASSES)
+        return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: %u x %u bins and the class outside the window exceed BF_MAX_CLASSES (%u)", bins->n_u,
+                    bins->n_v, (unsigned) BF_MAX_CLASSES);
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(bins->axis_u[i]) || !std::isfinite(bins->axis_v[i]))
+            return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: an axis component is not finite");
+    if (!std::isfinite(bins->u0) || !std::isfinite(bins->u1) || !std::isfinite(bins->v0) || !std::isfinite(bins->v1))
+        return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: a window edge is not finite");
+    if (!(bins->u1 > bins->u0) || !(bins->v1 > bins->v0))
+        return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: the window [%g, %g) x [%g, %g) is empty", (double) bins->u0, (double) bins->u1,
+                    (double) bins->v0, (double) bins->v1);
+    bfa::Table t;
+    std::memcpy(t.axis_u, bins->axis_u, sizeof(t.axis_u));
+    std::memcpy(t.axis_v, bins->axis_v, sizeof(t.axis_v));
+    t.u0 = bins->u0;
+    t.v0 = bins->v0;
+    t.su = bfa::scale(bins->n_u, bins->u0, bins->u1);
+    t.sv = bfa::scale(bins->n_v, bins->v0, bins->v1);
+    t.n_u = bins->n_u;
+    t.n_v = bins->n_v;
+    if (!std::isfinite(t.su) || !std::isfinite(t.sv))
+        return fail(BF_ERR_INVALID, "bf_scene_set_arrival_classes: the scale n / (upper - lower) of a window axis is not finite (%g, %g)", (double) t.su,
+                    (double) t.sv);
+    const uint32_t outside = bins->n_u * bins->n_v;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    return install_classes(scene, &t, sizeof(t), (outside + 1u) | (outside << 16) | bfd::kClassArrival, stream);
 }
 
 }  // extern "C"

@@ -108,6 +108,8 @@ template <int RX = 2> BF_DEV void generate_path(const DScene &sc0, const DLaunch
         film_up = ly < (float) py;
         s.aux = 0.f;
     }
+    // the table's arrival form: the class of the path is its primary ray's direction's, whatever the ray goes on to hit (bf_arrival.h)
+    if ((RX & kClass) && scene_class_arrival(sc0)) s.cls = scene_arrival_class(sc0, s.rd.x, s.rd.y, s.rd.z);
     s.throughput = 1.f;
     s.eta = 1.f;
     s.emission_weight = 1.f;
@@ -274,7 +276,8 @@ BF_DEV bool shade_vertex(const DScene &sc0, const DLaunch &lp, PathState &s, con
         // first intersection — path.cpp:115-117, pathlength.cpp:138-146,
         // pathtime.cpp:136-140, pathtimefrequency.cpp:131-153
         if (si_valid) s.flags |= kFlagValid;
-        if ((RX & kClass) && si_valid) s.cls = scene_classes(sc)[si.shape];      // the class of the path: its first intersection's shape
+        // the class of the path: its first intersection's shape (the arrival form gave the path its class when it was generated)
+        if ((RX & kClass) && si_valid && !scene_class_arrival(sc)) s.cls = scene_classes(sc)[si.shape];
         if (RX & kAov) aov_store(av, si_valid, si, aov_g);      // ... or zeros: a miss never sees the values of the slot's previous path
         if (is_range) s.aux += si_valid ? si.t : 0.f;
         if (is_time) s.aux = si_valid ? si.t / lp.time_c : 0.f;

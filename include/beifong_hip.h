@@ -341,7 +341,8 @@ enum {
     BF_FLAG_CLASSES = 1024u,   /* returns by target class: the render writes one histogram per class of the handle's class table
                                   (bf_scene_set_classes) instead of one.  The class of a path is shape_class[s], s the shape of
                                   its FIRST intersection (the one bf_path_record.valid reports; rectangles count: the ground, the
-                                  antenna apertures), or miss_class if its first ray leaves the scene.  Every sample the plain
+                                  antenna apertures), or miss_class if its first ray leaves the scene; or, with an arrival table
+                                  (bf_scene_set_arrival_classes), the bin of its primary ray's direction.  Every sample the plain
                                   render adds to cell c goes, same addend and same binning rule, to cell c of its path's class
                                   block.  Layout [class][plain layout], each block exactly what bf_launch_channels describes;
                                   batches [render][class][plain layout]; bf_scene_launch_channels gives the floats per render.
@@ -680,6 +681,34 @@ uint32_t bf_launch_channels(const bf_launch *launch);
 bf_status bf_scene_set_classes(bf_scene *scene, uint32_t n_classes, const uint32_t *shape_class /* host [n_shapes] */, uint32_t miss_class,
                                void *stream);
 uint32_t bf_scene_launch_channels(const bf_scene *scene, const bf_launch *launch);
+
+/* Returns by direction of arrival: the class table's second form, the ARRIVAL TABLE.  A path starts at the receiver, so the direction d
+ * of its primary ray (what the sensor or receiver hands to the path, world space) is the direction its return arrives from; the class of
+ * a path is the bin of (d . axis_u, d . axis_v) in the window [u0, u1) x [v0, v1), cut into n_u x n_v bins, and n_u n_v, the LAST class,
+ * for a direction outside the window: n_classes = n_u n_v + 1.  In fp32, every product and sum rounded on its own, no FMA:
+ *     u  = fl(fl(fl(d.x a.x) + fl(d.y a.y)) + fl(d.z a.z))       a = axis_u; v likewise with axis_v
+ *     su = fl(fl((float) n_u) / fl(u1 - u0))                      once, when the table is set; sv likewise
+ *     tu = fl(fl(u - u0) * su),  tv = fl(fl(v - v0) * sv)
+ *     inside = tu >= 0 && tu < (float) n_u && tv >= 0 && tv < (float) n_v          (a NaN is outside)
+ *     class  = inside ? (uint32) tv * n_u + (uint32) tu : n_u * n_v
+ * (csrc/bf_arrival.h is that arithmetic, capi.arrival_classes its statement in numpy.)  The axes are used as given, without
+ * normalisation, and they are WORLD-SPACE: they do not follow the sensor when bf_scene_update_endpoints turns the radar; set the table
+ * again for the new boresight.  The class is fixed when the path is generated: the first intersection does not change it and a path that
+ * leaves the scene keeps it (there is no miss class in this form).  With the class known per path BF_FLAG_CLASSES does what it does with
+ * shape classes: same layout [class][plain layout], same records, same sums, honoured and refused by the same entries with the same
+ * status and message; range_doppler of block k of a sweep's cube is the range-Doppler map of angle bin k.
+ *   A handle has ONE table: bf_scene_set_arrival_classes behaves as bf_scene_set_classes does (stream-ordered, the caller's struct free
+ *   on return, flushes an open rolling sequence, copied by bf_scene_clone, left alone by endpoint updates, mesh transforms, vertex
+ *   updates and BVH rebuilds) and each of the two calls replaces what the other installed; bf_scene_set_classes with n_classes = 0
+ *   clears either.
+ *   BF_ERR_INVALID for a null pointer, n_u or n_v = 0, n_u n_v + 1 > BF_MAX_CLASSES, an axis or window value that is not finite,
+ *   u1 <= u0 or v1 <= v0, or a scale su / sv that is not finite. */
+typedef struct bf_arrival_bins {
+    float axis_u[3], axis_v[3];
+    float u0, u1, v0, v1;
+    uint32_t n_u, n_v;
+} bf_arrival_bins;
+bf_status bf_scene_set_arrival_classes(bf_scene *scene, const bf_arrival_bins *bins, void *stream);
 
 /* Arbitrary output variables (BF_FLAG_AOV).  A scene handle carries an optional AOV table: a list of BF_AOV_* types, in the order
  * their channels follow X Y Z A W in every pixel; a type may appear more than once.

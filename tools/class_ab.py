@@ -1,11 +1,12 @@
 """Developer A/B: renders with and without returns by target class (BF_FLAG_CLASSES, 5 classes) on the full-size bench scenes,
 interleaved run by run, with the per-kernel times of BF_FLAG_STATS.
 
-    python tools/class_ab.py [--runs 5] [--steps 6] [--configs c4,c2]
+    python tools/class_ab.py [--runs 5] [--steps 6] [--configs c4,c2] [--arrival]
 
 c4 : one C4 shard (bus + car + motorbike, 4096 range bins, 2^19 paths) per render.  5 classes x 4101 floats = 20505 >
      kMaxLdsHist: the classed render takes global atomics BY SIZE, the plain one privatises its histogram in LDS.
 c2 : C2 (bus, 256 range bins).  5 x 261 floats: both renders privatise in LDS.
+c4full : the whole of C4 (2^22 paths) per render, otherwise c4.
 Classes do not roll, so every render is a stand-alone one on one handle (bench.py's "iso" probe), timed by the library
 (bf_stats: whole render, wf_shade, wf_trace, tail).  Four modes per config, so that the cost of the flag can be told from what
 it brings along:
@@ -13,6 +14,9 @@ it brings along:
     general     the plain render on a handle created under BF_LEAN=0 (the general kernels: what the class variants are built from)
     general_ga  ... with BF_FLAG_GLOBAL_ATOMICS (what a classed C4 render is forced into by size)
     classed     BF_FLAG_CLASSES, ground / bus / car / motorbike / miss
+    arrival     (--arrival) BF_FLAG_CLASSES under an arrival table of as many classes (Scene.set_arrival_classes: 4 x 1 azimuth bins
+                over the camera's field of view and the class outside), on a handle of its own: the cost of the class from the
+                primary ray's direction against the class from the first intersection, at equal n_classes
 Prints one line per config and mode: medians over runs x steps of kernel_ms, shade_ms, trace_ms, tail_ms, the spread of kernel_ms
 and kernel_ms relative to `lean`."""
 import argparse
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--configs", default="c4,c2")
+    ap.add_argument("--arrival", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -57,6 +62,12 @@ def main():
         general = capi.Scene(w.sd, lib)          # the tunables are read when a scene is created
         del os.environ["BF_LEAN"]
         modes = {"lean": (lean, 0), "general": (general, 0), "general_ga": (general, GA), "classed": (lean, CLS)}
+        handles = [lean, general]
+        if args.arrival:
+            by_angle = capi.Scene(w.sd, lib)
+            assert by_angle.set_arrival_classes(capi.arrival_bins_for(w.sd, 4, 1, (-0.3, 0.3, -2.0, 2.0))) == 5
+            modes["arrival"] = (by_angle, CLS)
+            handles.append(by_angle)
         hist = torch.zeros(lean.channels(w.launch(0, CLS)), dtype=torch.float32, device=dev)
         keys = ("kernel_ms", "shade_ms", "trace_ms", "tail_ms")
         ms = {m: {k: [] for k in keys} for m in modes}
@@ -86,14 +97,16 @@ def main():
             k = ms[m]["kernel_ms"]
             print(f"  {m:11s} variant {variant[m]:2d}  kernel {np.median(k):8.3f} ms ({min(k):.3f}..{max(k):.3f})  shade {np.median(ms[m]['shade_ms']):8.3f}"
                   f"  trace {np.median(ms[m]['trace_ms']):8.3f}  tail {np.median(ms[m]['tail_ms']):8.3f}  kernel / lean {np.median(k) / base:.3f}", flush=True)
-        lean.close()
-        general.close()
+        for g in handles:
+            g.close()
 
     for cfg in args.configs.split(","):
         if cfg == "c4":
             run_config(cfg, "c4shard")
         elif cfg == "c2":
             run_config(cfg, "c2")
+        elif cfg == "c4full":
+            run_config(cfg, "c4")
         else:
             raise SystemExit(f"unknown config {cfg}")
 
