@@ -160,6 +160,14 @@ class bf_arrival_bins(C.Structure):
                 ("v1", C.c_float), ("n_u", C.c_uint32), ("n_v", C.c_uint32)]
 
 
+class bf_twist(C.Structure):
+    _fields_ = [("lin", C.c_float * 3), ("ang", C.c_float * 3), ("pivot", C.c_float * 3)]
+
+
+class bf_range_rate_bins(C.Structure):
+    _fields_ = [("sensor_lin", C.c_float * 3), ("r0", C.c_float), ("r1", C.c_float), ("n_bins", C.c_uint32)]
+
+
 # include/beifong_hip.h: BF_ABI_MATERIAL .. BF_ABI_BATCH, in that order
 ABI_STRUCTS = [bf_material, bf_shape, bf_emitter, bf_sensor, bf_scene_desc, bf_launch, bf_path_record, bf_stats, bf_scene_info, bf_batch]
 
@@ -180,7 +188,7 @@ EXPORTED_SYMBOLS = [
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
     "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
     "bf_render_converge_device", "bf_render_converge", "bf_converge_statistic_device",
-    "bf_scene_set_classes", "bf_scene_set_arrival_classes", "bf_scene_launch_channels", "bf_aov_floats", "bf_scene_set_aovs",
+    "bf_scene_set_classes", "bf_scene_set_arrival_classes", "bf_scene_set_range_rate_classes", "bf_scene_launch_channels", "bf_aov_floats", "bf_scene_set_aovs",
     "bf_exact_sum_host", "bf_exact_sum",
 ]
 
@@ -227,6 +235,7 @@ def load_library(path=None):
     lib.bf_launch_channels.restype = C.c_uint32
     lib.bf_scene_set_classes.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp]
     lib.bf_scene_set_arrival_classes.argtypes = [vp, C.POINTER(bf_arrival_bins), vp]
+    lib.bf_scene_set_range_rate_classes.argtypes = [vp, C.POINTER(bf_range_rate_bins), vp, vp]
     lib.bf_scene_launch_channels.argtypes = [vp, C.POINTER(bf_launch)]
     lib.bf_scene_launch_channels.restype = C.c_uint32
     lib.bf_aov_floats.argtypes = [C.c_uint32, vp]
@@ -564,6 +573,82 @@ def arrival_bins_for(sd, n_u, n_v, window):
     m = np.asarray(list(sd.shapes[int(s.shape)].to_world if int(s.shape) >= 0 else s.to_world), np.float64).reshape(4, 4)
     cols = [m[:3, k] / np.linalg.norm(m[:3, k]) for k in (0, 1)]
     return arrival_bins(cols[0].astype(np.float32), cols[1].astype(np.float32), n_u, n_v, window)
+
+
+def range_rate_bins(window, n_bins, sensor_lin=(0, 0, 0)):
+    """bf_range_rate_bins: the range-rate table of Scene.set_range_rate_classes.  window = (r0, r1) in m/s: the bins cut [r0, r1)
+    into n_bins; sensor_lin: the radar's own velocity, world space, m/s.  n_bins + 2 classes: the bins, one class for the rates
+    outside the window and one for the paths whose first ray leaves the scene."""
+    b = bf_range_rate_bins()
+    b.sensor_lin = (C.c_float * 3)(*np.asarray(sensor_lin, np.float32).reshape(3).tolist())
+    b.r0, b.r1 = (float(np.float32(x)) for x in window)
+    b.n_bins = int(n_bins)
+    return b
+
+
+def range_rate_n_classes(bins):
+    return int(bins.n_bins) + 2
+
+
+def range_rate_twists(twists, n_shapes=None):
+    """float32[n_shapes, 9]: a list of motion.twist (or an array of them) as one contiguous table [lin | ang | pivot] per shape"""
+    t = np.ascontiguousarray(np.asarray(twists, np.float32).reshape(-1, 9))
+    if n_shapes is not None and len(t) != int(n_shapes):
+        raise ValueError(f"{len(t)} twists for a scene of {int(n_shapes)} shapes")
+    return t
+
+
+def range_rates(d, p, shape, bins, twists):
+    """float32[n]: rr of range_rate_classes, the range rate of every path's first intersection along its primary ray (whatever
+    the row of shape 0 gives where shape < 0: range_rate_classes never looks at it)."""
+    f = np.float32
+    d = np.asarray(d, f).reshape(-1, 3)
+    p = np.asarray(p, f).reshape(-1, 3)
+    shape = np.asarray(shape, np.int64).reshape(-1)
+    tw = range_rate_twists(twists)
+    hit = shape >= 0
+    row = tw[np.where(hit, shape, 0)] if len(tw) else np.zeros((len(shape), 9), f)
+    lin, ang, pivot = row[:, 0:3], row[:, 3:6], row[:, 6:9]
+    sl = [f(x) for x in bins.sensor_lin]
+    with np.errstate(all="ignore"):
+        q = np.where(hit[:, None], p, f(0)) - pivot
+        c = [ang[:, 1] * q[:, 2] - ang[:, 2] * q[:, 1], ang[:, 2] * q[:, 0] - ang[:, 0] * q[:, 2], ang[:, 0] * q[:, 1] - ang[:, 1] * q[:, 0]]
+        w = [(lin[:, k] + c[k]) - sl[k] for k in range(3)]
+        rr = (d[:, 0] * w[0] + d[:, 1] * w[1]) + d[:, 2] * w[2]
+    assert rr.dtype == f and q.dtype == f and all(x.dtype == f for x in c + w)
+    return rr
+
+
+def range_rate_classes(d, p, shape, bins, twists):
+    """The class of a path whose primary ray has direction d (float32[n, 3]) and first meets shape `shape` (int[n]; < 0: the ray
+    leaves the scene) at p (float32[n, 3], world space) under the range-rate table `bins` (range_rate_bins) and `twists`
+    (float32[n_shapes, 9], motion.twist): THE SPECIFICATION of bf_scene_set_range_rate_classes, in numpy float32 — every product,
+    sum and difference rounded on its own, no FMA:
+        q   = p - pivot
+        c   = (ang.y q.z - ang.z q.y, ang.z q.x - ang.x q.z, ang.x q.y - ang.y q.x)
+        w   = (lin + c) - sensor_lin
+        rr  = (d.x w.x + d.y w.y) + d.z w.z               positive: an opening range (range_rates)
+        sr  = float32(n_bins) / (r1 - r0)
+        t   = (rr - r0) * sr
+        class = uint32(t) if 0 <= t < n_bins else n_bins  (a NaN is outside); n_bins + 1 for a miss
+    Returns int64[n]."""
+    f = np.float32
+    hit = np.asarray(shape, np.int64).reshape(-1) >= 0
+    n_bins = int(bins.n_bins)
+    rr = range_rates(d, p, shape, bins, twists)
+    with np.errstate(all="ignore"):
+        sr = f(n_bins) / (f(bins.r1) - f(bins.r0))
+        t = (rr - f(bins.r0)) * sr
+        assert t.dtype == f
+        inside = (t >= f(0)) & (t < f(n_bins))
+    k = np.where(inside, t, f(0)).astype(np.int64)      # (truncation: the values are in [0, n_bins))
+    return np.where(hit, np.where(inside, k, n_bins), n_bins + 1)
+
+
+def range_rate_centres(bins):
+    """float64[n_bins]: the centre of every bin of the table, in m/s (the monostatic Doppler shift of a centre rr is -2 rr / lambda)"""
+    n = int(bins.n_bins)
+    return float(bins.r0) + (np.arange(n, dtype=np.float64) + 0.5) * ((float(bins.r1) - float(bins.r0)) / n)
 
 
 def aov_types(types):
@@ -1032,6 +1117,17 @@ class Scene:
         b = axis_u if isinstance(axis_u, bf_arrival_bins) else arrival_bins(axis_u, axis_v, n_u, n_v, window)
         check(self.lib, self.lib.bf_scene_set_arrival_classes(self.handle, C.byref(b), _stream(stream)), "bf_scene_set_arrival_classes")
         return arrival_n_classes(b)
+
+    def set_range_rate_classes(self, bins, twists, stream=0):
+        """bf_scene_set_range_rate_classes: the class of a path is the bin of the range rate of its first intersection along its
+        primary ray (range_rate_classes is the rule).  bins: range_rate_bins; twists: one motion.twist per shape, in
+        scene-description order (world space: they do not follow transform_meshes or a motion batch).  Classes [bins..., outside,
+        miss].  Replaces a set_classes or set_arrival_classes table and is replaced by one; clear_classes clears any.  Returns the
+        number of classes."""
+        tw = range_rate_twists(twists, self.info().n_shapes)
+        check(self.lib, self.lib.bf_scene_set_range_rate_classes(self.handle, C.byref(bins), _ptr(tw), _stream(stream)),
+              "bf_scene_set_range_rate_classes")
+        return range_rate_n_classes(bins)
 
     def set_aovs(self, types, stream=0):
         """bf_scene_set_aovs: the AOVs every pixel of a BF_FLAG_AOV render carries behind X Y Z A W, in this order (BF_AOV_*

@@ -23,6 +23,7 @@
 
 #include "../../include/beifong_hip.h"
 #include "bf_arrival.h"
+#include "bf_range_rate.h"
 
 BF_NS_BEGIN
 
@@ -96,8 +97,9 @@ struct DEmitter {
 //             (path_scene below) — per-lane pointers, so geometry reads of the root node become vector loads
 //   kMoment   the launch carries second moments (BF_FLAG_MOMENT; chosen by the host through the *_moment launchers): film_put adds nested.XYZ and the square of every
 //             first-moment addend (the channel layout at the flag in beifong_hip.h); every other variant has none of that code
-//   kClass    the launch splits its histogram by the class of each path: of its first intersection, or (the table's arrival form, a run-time
-//             bit of DScene::class_info) of its primary ray's direction (BF_FLAG_CLASSES; chosen by the host through
+//   kClass    the launch splits its histogram by the class of each path: of its first intersection's shape, or (the table's arrival and
+//             range-rate forms, run-time bits of DScene::class_info) of its primary ray's direction or of its first intersection's range
+//             rate (BF_FLAG_CLASSES; chosen by the host through
 //             the *_class launchers): the path state carries the class (PathState::cls, WF::cls), hist_dst adds the class block's offset
 //             and the 1 x 1 film's base channels take the per-cell route of a W x H film; every other variant has none of that code
 //   kAov      every pixel carries the AOVs of the handle's table (BF_FLAG_AOV; chosen by the host through the *_aov launchers; render modes
@@ -175,7 +177,7 @@ struct DScene {
     uint32_t tab_cache;       // host: 1 = n_materials <= kTabMaxMaterials and n_rects <= kTabMaxRects
     uint32_t tab_on;          // device only: the tables are in LDS at byte offsets lds_mat / lds_rect of the dynamic segment
     uint32_t lds_mat, lds_rect;
-    uint32_t class_info;      // n_classes | miss_class << 16 | kClassArrival; 0: the handle has no class table
+    uint32_t class_info;      // n_classes | miss_class << 16 | kClassArrival or kClassRangeRate; 0: the handle has no class table
 };
 static_assert(sizeof(DScene) == 184 && offsetof(DScene, class_lo) == 124 && offsetof(DScene, wnodes) == 128 && offsetof(DScene, class_hi) == 148 &&
                   offsetof(DScene, sensor) == 152 && offsetof(DScene, class_info) == 180,
@@ -205,7 +207,7 @@ __host__ __device__ __forceinline__ const uint32_t *scene_classes(const DScene &
     return (const uint32_t *) (uintptr_t) (((uint64_t) sc.class_hi << 32) | sc.class_lo);
 }
 __host__ __device__ __forceinline__ uint32_t scene_n_classes(const DScene &sc) { return sc.class_info & 0xffffu; }
-__host__ __device__ __forceinline__ uint32_t scene_miss_class(const DScene &sc) { return (sc.class_info >> 16) & 0x7fffu; }
+__host__ __device__ __forceinline__ uint32_t scene_miss_class(const DScene &sc) { return (sc.class_info >> 16) & 0x3fffu; }
 // The table's second form (bf_scene_set_arrival_classes): the class comes from the direction of the path's primary ray, and the device
 // array holds the twelve words of bfa::Table (bf_arrival.h) instead of shape_class[].  The form is a bit of class_info, so the switch is
 // wave-uniform; miss_class is then the class outside the window, which every path's own class replaces at generation.
@@ -216,6 +218,22 @@ __device__ __forceinline__ uint32_t scene_arrival_class(const DScene &sc, float 
     const BF_CAS bfa::Table *t = as_const((const bfa::Table *) scene_classes(sc));
     return bfa::classify(dx, dy, dz, t->axis_u[0], t->axis_u[1], t->axis_u[2], t->axis_v[0], t->axis_v[1], t->axis_v[2], t->u0, t->su, t->v0, t->sv,
                          t->n_u, t->n_v);
+}
+// The table's third form (bf_scene_set_range_rate_classes): the class comes from the range rate of the path's first intersection along its
+// primary ray, and the device array holds bfr::Header and one bfr::Row per shape (bf_range_rate.h).  Bit 30 of class_info, wave-uniform
+// like the arrival bit; miss_class is the class of a path whose first ray leaves the scene, n_bins + 1.
+constexpr uint32_t kClassRangeRate = 1u << 30;
+__host__ __device__ __forceinline__ bool scene_class_range_rate(const DScene &sc) { return (sc.class_info & kClassRangeRate) != 0u; }
+// the class of a path whose primary ray, direction d, first meets shape `shape` at p: the header by scalar loads through the constant
+// address space, the shape's row by three per-lane 16-byte loads
+__device__ __forceinline__ uint32_t scene_range_rate_class(const DScene &sc, uint32_t shape, float px, float py, float pz, float dx, float dy, float dz) {
+    const uint32_t *words = scene_classes(sc);
+    const BF_CAS bfr::Header *h = as_const((const bfr::Header *) words);
+    const float4 *row = (const float4 *) (words + bfr::kHeaderWords) + (size_t) shape * (bfr::kRowWords / 4u);
+    const float4 lin = row[0], ang = row[1], pivot = row[2];
+    return bfr::classify(bfr::rate(px, py, pz, dx, dy, dz, lin.x, lin.y, lin.z, ang.x, ang.y, ang.z, pivot.x, pivot.y, pivot.z, h->sensor_lin[0],
+                                   h->sensor_lin[1], h->sensor_lin[2]),
+                         h->r0, h->sr, h->n_bins);
 }
 
 // One render of a ROLLING SEQUENCE (bf_render_device with BF_FLAG_ROLLING): what differs between the renders of a

@@ -41,8 +41,9 @@ void set_classes_ptr(bfd::DScene &d, const uint32_t *p) {
     d.class_lo = (uint32_t) (uintptr_t) p;
     d.class_hi = (uint32_t) ((uint64_t) (uintptr_t) p >> 32);
 }
-// words of the handle's class array: shape_class[n_shapes] or the arrival table (bf_arrival.h), whichever form is installed
-size_t class_words(uint32_t n_shapes) { return std::max<size_t>(bfa::kWords, n_shapes); }
+// words of the handle's class array: shape_class[n_shapes], the arrival table (bf_arrival.h) or the range-rate table's header and rows
+// (bf_range_rate.h), whichever form is installed
+size_t class_words(uint32_t n_shapes) { return std::max<size_t>(bfa::kWords, (size_t) bfr::table_words(n_shapes)); }
 
 // what bf_scene_create and bf_scene_update_endpoints both require of the material table and the film (a back_material out of
 // range would send the kernels' load_material past the device table)
@@ -70,7 +71,7 @@ bf_status stage_copy(const bf_scene *sc, void *dst, const void *src, size_t byte
     return stage_release_after(stg, stream);
 }
 
-// what bf_scene_set_classes and bf_scene_set_arrival_classes share: the open rolling sequence ends (its renders were issued without
+// what bf_scene_set_classes, bf_scene_set_arrival_classes and bf_scene_set_range_rate_classes share: the open rolling sequence ends (its renders were issued without
 // classes; the table is not theirs to see change), the handle's device array exists, `words` go into it in stream order
 bf_status install_classes(bf_scene *scene, const void *words, size_t bytes, uint32_t class_info, hipStream_t stream) {
     bf_status st = order_after_last(scene, stream);
@@ -573,6 +574,49 @@ bf_status bf_scene_set_arrival_classes(bf_scene *scene, const bf_arrival_bins *b
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
     return install_classes(scene, &t, sizeof(t), (outside + 1u) | (outside << 16) | bfd::kClassArrival, stream);
+}
+
+// The table's range-rate form: bfr::Header and one bfr::Row per shape (bf_range_rate.h) in the same device array, the form in bit 30 of
+// class_info; miss_class is n_bins + 1, the class of a path whose first ray leaves the scene, and n_bins the class of a rate outside the
+// window.  The scale is computed here, once.
+bf_status bf_scene_set_range_rate_classes(bf_scene *scene, const bf_range_rate_bins *bins, const bf_twist *twists, void *stream_) {
+    if (!scene) return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: null scene");
+    if (!bins) return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: null bins");
+    const uint32_t n_shapes = scene->info.n_shapes;
+    if (n_shapes && !twists) return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: twists is null");
+    if (bins->n_bins == 0) return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: n_bins = 0: must be at least 1");
+    if ((uint64_t) bins->n_bins + 2u > BF_MAX_CLASSES)
+        return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: %u bins, the class outside the window and the miss class exceed BF_MAX_CLASSES (%u)",
+                    bins->n_bins, (unsigned) BF_MAX_CLASSES);
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(bins->sensor_lin[i])) return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: a sensor_lin component is not finite");
+    if (!std::isfinite(bins->r0) || !std::isfinite(bins->r1)) return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: a window edge is not finite");
+    if (!(bins->r1 > bins->r0))
+        return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: the window [%g, %g) is empty", (double) bins->r0, (double) bins->r1);
+    for (uint32_t k = 0; k < n_shapes; ++k)
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(twists[k].lin[i]) || !std::isfinite(twists[k].ang[i]) || !std::isfinite(twists[k].pivot[i]))
+                return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: twists[%u] has a component that is not finite", k);
+    std::vector<uint32_t> words((size_t) bfr::table_words(n_shapes), 0u);
+    bfr::Header h = {};
+    std::memcpy(h.sensor_lin, bins->sensor_lin, sizeof(h.sensor_lin));
+    h.r0 = bins->r0;
+    h.sr = bfa::scale(bins->n_bins, bins->r0, bins->r1);
+    h.n_bins = bins->n_bins;
+    if (!std::isfinite(h.sr))
+        return fail(BF_ERR_INVALID, "bf_scene_set_range_rate_classes: the scale n_bins / (r1 - r0) of the window is not finite (%g)", (double) h.sr);
+    std::memcpy(words.data(), &h, sizeof(h));
+    for (uint32_t k = 0; k < n_shapes; ++k) {
+        bfr::Row r = {};
+        std::memcpy(r.lin, twists[k].lin, sizeof(r.lin));
+        std::memcpy(r.ang, twists[k].ang, sizeof(r.ang));
+        std::memcpy(r.pivot, twists[k].pivot, sizeof(r.pivot));
+        std::memcpy(words.data() + bfr::kHeaderWords + (size_t) bfr::kRowWords * k, &r, sizeof(r));
+    }
+    const uint32_t outside = bins->n_bins;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    return install_classes(scene, words.data(), sizeof(uint32_t) * words.size(), (outside + 2u) | ((outside + 1u) << 16) | bfd::kClassRangeRate, stream);
 }
 
 }  // extern "C"

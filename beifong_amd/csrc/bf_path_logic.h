@@ -276,8 +276,14 @@ BF_DEV bool shade_vertex(const DScene &sc0, const DLaunch &lp, PathState &s, con
         // first intersection — path.cpp:115-117, pathlength.cpp:138-146,
         // pathtime.cpp:136-140, pathtimefrequency.cpp:131-153
         if (si_valid) s.flags |= kFlagValid;
-        // the class of the path: its first intersection's shape (the arrival form gave the path its class when it was generated)
-        if ((RX & kClass) && si_valid && !scene_class_arrival(sc)) s.cls = scene_classes(sc)[si.shape];
+        // the class of the path: its first intersection's shape, or the bin of that intersection's range rate along the primary ray, which
+        // s.rd still is (bf_range_rate.h); the arrival form gave the path its class when it was generated
+        if ((RX & kClass) && si_valid && !scene_class_arrival(sc)) {
+            if (scene_class_range_rate(sc))
+                s.cls = scene_range_rate_class(sc, si.shape, si.p.x, si.p.y, si.p.z, s.rd.x, s.rd.y, s.rd.z);
+            else
+                s.cls = scene_classes(sc)[si.shape];
+        }
         if (RX & kAov) aov_store(av, si_valid, si, aov_g);      // ... or zeros: a miss never sees the values of the slot's previous path
         if (is_range) s.aux += si_valid ? si.t : 0.f;
         if (is_time) s.aux = si_valid ? si.t / lp.time_c : 0.f;

@@ -34,7 +34,8 @@ struct PathState {
     float phase;         // ray.phase of the working ray: last traced segment only (ray.h:89-93, interaction.h:61-64)
     float dlambda;       // BF_FLAG_DOPPLER: what the Doppler hook has added to the caller's ray.wavelengths[0] (nm)
     uint32_t cls;        // kClass: shape_class of the path's first intersection, miss_class until then; under an arrival table the bin of the
-                         // primary ray's direction, from generation on (the other variants never touch it: no register)
+                         // primary ray's direction, from generation on; under a range-rate table the bin of the first intersection's
+                         // range rate (the other variants never touch it: no register)
 };
 
 // `classed`: a compile-time constant at every call site ((V & kClass) != 0).  `hq`: the slot's hit row — the same 64-byte record as

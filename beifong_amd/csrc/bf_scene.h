@@ -350,8 +350,9 @@ struct __attribute__((visibility("hidden"))) EndpointState {
     std::vector<uint32_t> array_n;
     float *sensor_array_dev = nullptr;
     uint32_t sensor_array_n = 0;
-    uint32_t *classes = nullptr;             // device: shape_class[n_shapes] or the arrival table's twelve words (room for either) once
-                                             // bf_scene_set_classes / bf_scene_set_arrival_classes has given one (d->class_lo / class_hi)
+    uint32_t *classes = nullptr;             // device: shape_class[n_shapes], the arrival table's twelve words or the range-rate table's
+                                             // 8 + 12 n_shapes (room for any) once bf_scene_set_classes / bf_scene_set_arrival_classes /
+                                             // bf_scene_set_range_rate_classes has given one (d->class_lo / class_hi)
 
     void apply(const Image &img, bool tab_cache);      // every count and profile bit, here and in *d, from a flattened description (tab_cache: bf_tunables)
     void pack(const Image &img, char *blk) const;      // the five tables into a host block of this layout

@@ -38,6 +38,13 @@ def about(r, pivot, t=(0.0, 0.0, 0.0)):
     return rigid(r.astype(f32), (pivot - r @ pivot + np.asarray(t, dtype=np.float64)).astype(f32))
 
 
+def twist(lin=(0.0, 0.0, 0.0), ang=(0.0, 0.0, 0.0), pivot=(0.0, 0.0, 0.0)):
+    """float32[9] = [lin | ang | pivot], one bf_twist: the instantaneous rigid motion of a shape in world space.  A point p of it has
+    velocity lin + ang x (p - pivot): lin in m/s, ang in rad/s, pivot in m.  A list of them, one per shape in scene-description
+    order, is the `twists` of Scene.set_range_rate_classes; the default is a shape at rest."""
+    return np.concatenate([np.asarray(v, dtype=f32).reshape(3) for v in (lin, ang, pivot)])
+
+
 def is_identity(m):
     m = np.asarray(m, dtype=f32).reshape(3, 4)
     return bool(np.array_equal(m, rigid()))

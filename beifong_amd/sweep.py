@@ -184,12 +184,15 @@ def render_pulse_sweep(sd, launch, offsets, n_streams=2, lib=None, device=None, 
 
 
 def _classed(first, launch, classes):
-    """classes = (shape_class, n_classes, miss_class), a capi.bf_arrival_bins (classes by direction of arrival) or None -> (the
-    launch to render, n_classes or 0): the table goes onto `first` (its clones inherit it) and the launch carries BF_FLAG_CLASSES."""
+    """classes = (shape_class, n_classes, miss_class), a capi.bf_arrival_bins (classes by direction of arrival), a pair
+    (capi.bf_range_rate_bins, twists) (classes by range rate) or None -> (the launch to render, n_classes or 0): the table goes
+    onto `first` (its clones inherit it) and the launch carries BF_FLAG_CLASSES."""
     if classes is None:
         return launch, 0
     if isinstance(classes, capi.bf_arrival_bins):
         first.set_arrival_classes(classes)
+    elif len(classes) == 2 and isinstance(classes[0], capi.bf_range_rate_bins):
+        first.set_range_rate_classes(*classes)
     else:
         shape_class, n_classes, miss_class = classes
         first.set_classes(shape_class, n_classes, miss_class)
@@ -311,7 +314,9 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
     Scene.set_classes); the cube is then float32[n_pulses, n_classes, f_bins * t_bins, 3] and range_doppler(cube[:, k]) the
     range-Doppler map of class k.  classes=capi.arrival_bins(...) or capi.arrival_bins_for(sd, ...): the returns split by the
     direction they arrive from (Scene.set_arrival_classes), same cube shape with n_classes = n_u * n_v + 1: cube[:, k] is the
-    range-Doppler map of angle bin k, the cube a range-Doppler-angle cube.  Every sweep of this module takes either form."""
+    range-Doppler map of angle bin k, the cube a range-Doppler-angle cube.  classes=(capi.range_rate_bins(...), twists): the
+    returns split by the range rate of the scatterer each path hit first (Scene.set_range_rate_classes), n_classes = n_bins + 2;
+    the twists are world-space and the same for every pulse.  Every sweep of this module takes any of the three forms."""
     xf = np.asarray(transforms, dtype=np.float32)
     if xf.ndim != 4 or xf.shape[2:] != (3, 4):
         raise ValueError(f"transforms must be [n_pulses, n_shapes, 3, 4], got {xf.shape}")

@@ -342,7 +342,9 @@ enum {
                                   (bf_scene_set_classes) instead of one.  The class of a path is shape_class[s], s the shape of
                                   its FIRST intersection (the one bf_path_record.valid reports; rectangles count: the ground, the
                                   antenna apertures), or miss_class if its first ray leaves the scene; or, with an arrival table
-                                  (bf_scene_set_arrival_classes), the bin of its primary ray's direction.  Every sample the plain
+                                  (bf_scene_set_arrival_classes), the bin of its primary ray's direction; or, with a range-rate
+                                  table (bf_scene_set_range_rate_classes), the bin of its first intersection's range rate along
+                                  that ray.  Every sample the plain
                                   render adds to cell c goes, same addend and same binning rule, to cell c of its path's class
                                   block.  Layout [class][plain layout], each block exactly what bf_launch_channels describes;
                                   batches [render][class][plain layout]; bf_scene_launch_channels gives the floats per render.
@@ -709,6 +711,46 @@ typedef struct bf_arrival_bins {
     uint32_t n_u, n_v;
 } bf_arrival_bins;
 bf_status bf_scene_set_arrival_classes(bf_scene *scene, const bf_arrival_bins *bins, void *stream);
+
+/* Returns by range rate: the class table's third form, the RANGE-RATE TABLE.  One render then gives a range-Doppler map: block k of the
+ * histogram holds the returns whose first scatterer opens its range to the radar at a rate inside bin k.
+ *   Motion model: every shape, rectangles included, moves rigidly; a point p of shape k has velocity lin_k + ang_k x (p - pivot_k)
+ *   (bf_twist, world space: m/s, rad/s, m), and the radar moves with sensor_lin.
+ *   Inputs: p, the world-space position of the path's FIRST intersection (what bf_ray_intersect returns for the primary ray; in a batch
+ *   with per-render geometry or mesh offsets, that render's geometry), and d, the direction of the primary ray, used as given.
+ *   Rule, in fp32, every product, sum and difference rounded on its own, no FMA:
+ *     q    = fl(p - pivot)                                          per component
+ *     c.x  = fl(fl(ang.y q.z) - fl(ang.z q.y))                      c.y, c.z cyclically
+ *     w    = fl(fl(lin + c) - sensor_lin)                           per component
+ *     rr   = fl(fl(fl(d.x w.x) + fl(d.y w.y)) + fl(d.z w.z))
+ *     sr   = fl(fl((float) n_bins) / fl(r1 - r0))                   once, when the table is set
+ *     t    = fl(fl(rr - r0) * sr)
+ *     class = (t >= 0 && t < (float) n_bins) ? (uint32) t : n_bins          (a NaN is outside; -0 >= 0 is inside)
+ *   and a path whose first ray leaves the scene has class n_bins + 1: n_classes = n_bins + 2, [bins..., outside, miss].
+ *   (csrc/bf_range_rate.h is that arithmetic, capi.range_rate_classes its statement in numpy.)  A positive rr is an OPENING range; the
+ *   monostatic Doppler shift of bin centre rr is -2 rr / lambda.  The rate is taken along the RECEIVE ray only: the leg from a bistatic
+ *   transmitter and every later bounce of the path do not enter; the class is fixed at the first intersection.
+ *   Not bf_shape.velocity: that field is the reference's Shape "velocity" transform, applied to a point in the local frame, and belongs
+ *   to BF_FLAG_DOPPLER alone; this table neither reads nor changes it.
+ *   Twists and pivots are WORLD-SPACE values at the time of the render: they do not follow bf_scene_transform_meshes or the transforms
+ *   of a motion batch (the point p does).
+ *   A handle has ONE table: this call behaves as the other two do (stream-ordered, the caller's memory free on return, flushes an open
+ *   rolling sequence, copied by bf_scene_clone, left alone by endpoint updates, mesh transforms, vertex updates and BVH rebuilds), each
+ *   of the three calls replaces what another installed, and bf_scene_set_classes with n_classes = 0 clears any form.  With the class
+ *   known per path BF_FLAG_CLASSES does what it does with shape classes, honoured and refused by the same entries with the same status
+ *   and message.
+ *   BF_ERR_INVALID for a null pointer (twists may be null only for a scene without shapes), n_bins = 0, n_bins + 2 > BF_MAX_CLASSES, a
+ *   table value that is not finite, r1 <= r0, or a scale sr that is not finite. */
+typedef struct bf_twist {
+    float lin[3], ang[3], pivot[3];
+} bf_twist;
+typedef struct bf_range_rate_bins {
+    float sensor_lin[3];
+    float r0, r1;
+    uint32_t n_bins;
+} bf_range_rate_bins;
+bf_status bf_scene_set_range_rate_classes(bf_scene *scene, const bf_range_rate_bins *bins,
+                                          const bf_twist *twists /* host [n_shapes], scene-description order */, void *stream);
 
 /* Arbitrary output variables (BF_FLAG_AOV).  A scene handle carries an optional AOV table: a list of BF_AOV_* types, in the order
  * their channels follow X Y Z A W in every pixel; a type may appear more than once.

@@ -1,7 +1,7 @@
 """Developer A/B: renders with and without returns by target class (BF_FLAG_CLASSES, 5 classes) on the full-size bench scenes,
 interleaved run by run, with the per-kernel times of BF_FLAG_STATS.
 
-    python tools/class_ab.py [--runs 5] [--steps 6] [--configs c4,c2] [--arrival]
+    python tools/class_ab.py [--runs 5] [--steps 6] [--configs c4,c2] [--arrival] [--range-rate]
 
 c4 : one C4 shard (bus + car + motorbike, 4096 range bins, 2^19 paths) per render.  5 classes x 4101 floats = 20505 >
      kMaxLdsHist: the classed render takes global atomics BY SIZE, the plain one privatises its histogram in LDS.
@@ -17,8 +17,12 @@ it brings along:
     arrival     (--arrival) BF_FLAG_CLASSES under an arrival table of as many classes (Scene.set_arrival_classes: 4 x 1 azimuth bins
                 over the camera's field of view and the class outside), on a handle of its own: the cost of the class from the
                 primary ray's direction against the class from the first intersection, at equal n_classes
+    range_rate  (--range-rate) BF_FLAG_CLASSES under a range-rate table of as many classes (Scene.set_range_rate_classes: 3 bins over
+                [-24, 0) m/s, the class outside and the miss class; the radar at 6 m/s along +x, aperture and ground at rest, mesh k closing at
+                4 (k + 1) m/s and yawing at 0.5 rad/s about the origin), on a handle of its own: the cost of the class from the first
+                intersection's range rate (a per-lane row of twelve words and some thirty fp32 operations) against one table word
 Prints one line per config and mode: medians over runs x steps of kernel_ms, shade_ms, trace_ms, tail_ms, the spread of kernel_ms
-and kernel_ms relative to `lean`."""
+and kernel_ms relative to `lean` and to `classed`."""
 import argparse
 import os
 import sys
@@ -33,10 +37,11 @@ def main():
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--configs", default="c4,c2")
     ap.add_argument("--arrival", action="store_true")
+    ap.add_argument("--range-rate", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
-    from beifong_amd import capi, scenes
+    from beifong_amd import capi, motion, scenes
     import bench
 
     dev = torch.device("cuda", 0)
@@ -68,6 +73,13 @@ def main():
             assert by_angle.set_arrival_classes(capi.arrival_bins_for(w.sd, 4, 1, (-0.3, 0.3, -2.0, 2.0))) == 5
             modes["arrival"] = (by_angle, CLS)
             handles.append(by_angle)
+        if args.range_rate:
+            by_rate = capi.Scene(w.sd, lib)
+            # the aperture and the ground at rest, as shape_class above has them; mesh k = shape 2 + k
+            twists = [motion.twist()] * 2 + [motion.twist(lin=(-4.0 * (k + 1), 0.0, 0.0), ang=(0.0, 0.0, 0.5)) for k in range(n_shapes - 2)]
+            assert by_rate.set_range_rate_classes(capi.range_rate_bins((-24.0, 0.0), 3, sensor_lin=(6.0, 0.0, 0.0)), twists) == 5
+            modes["range_rate"] = (by_rate, CLS)
+            handles.append(by_rate)
         hist = torch.zeros(lean.channels(w.launch(0, CLS)), dtype=torch.float32, device=dev)
         keys = ("kernel_ms", "shade_ms", "trace_ms", "tail_ms")
         ms = {m: {k: [] for k in keys} for m in modes}
@@ -90,13 +102,13 @@ def main():
         for r in range(args.runs):
             for m in (order if r % 2 == 0 else order[::-1]):
                 region(m, True)
-        base = np.median(ms["lean"]["kernel_ms"])
+        base, shape_form = np.median(ms["lean"]["kernel_ms"]), np.median(ms["classed"]["kernel_ms"])
         lp = w.launch(0, CLS)
         print(f"{name}: {int(lp.n_paths)} paths, {lean.channels(w.launch(0))} floats plain, {lean.channels(lp)} classed", flush=True)
         for m in modes:
             k = ms[m]["kernel_ms"]
             print(f"  {m:11s} variant {variant[m]:2d}  kernel {np.median(k):8.3f} ms ({min(k):.3f}..{max(k):.3f})  shade {np.median(ms[m]['shade_ms']):8.3f}"
-                  f"  trace {np.median(ms[m]['trace_ms']):8.3f}  tail {np.median(ms[m]['tail_ms']):8.3f}  kernel / lean {np.median(k) / base:.3f}", flush=True)
+                  f"  trace {np.median(ms[m]['trace_ms']):8.3f}  tail {np.median(ms[m]['tail_ms']):8.3f}  kernel / lean {np.median(k) / base:.3f}  / classed {np.median(k) / shape_form:.3f}", flush=True)
         for g in handles:
             g.close()
 
