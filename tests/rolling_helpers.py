@@ -1,6 +1,7 @@
 """Helpers shared by the rolling-sequence and endpoint-update tests (a plain module: no fixtures, no pytest settings).
 
-_same_records holds two sets of per-path records to each other bit for bit; _launch_like copies a launch with another
+_same_records holds two sets of per-path records to each other bit for bit, same_records_by_kind likewise up to the payload of
+a NaN; _launch_like copies a launch with another
 seed / flags / path count / offset; _Sequence issues K rolling renders of one handle into device buffers (torch)."""
 import numpy as np
 
@@ -11,6 +12,19 @@ def _same_records(a, b):
     for k in ("L", "aux"):
         assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
     assert np.array_equal(a["n_rays"], b["n_rays"]) and np.array_equal(a["valid"], b["valid"])
+
+
+def same_records_by_kind(a, b, what=""):
+    """_same_records for renders that return non-finite radiance: bit for bit where b's L is finite; where it is not, the same KIND
+    of non-finite in a (NaN for NaN, the same infinity); the sign and payload of a NaN are not part of the contract between the
+    oracle's and the device's arithmetic"""
+    assert np.array_equal(a["aux"].view(np.uint32), b["aux"].view(np.uint32)), what
+    assert np.array_equal(a["n_rays"], b["n_rays"]) and np.array_equal(a["valid"], b["valid"]), what
+    fin = np.isfinite(b["L"])
+    assert np.array_equal(np.isfinite(a["L"]), fin) and np.array_equal(np.isnan(a["L"]), np.isnan(b["L"])), what
+    assert np.array_equal(a["L"][fin].view(np.uint32), b["L"][fin].view(np.uint32)), what
+    inf = np.isinf(b["L"])
+    assert np.array_equal(a["L"][inf], b["L"][inf]), what
 
 
 def _launch_like(lp, seed, flags=0, n_paths=None, path_offset=0):
