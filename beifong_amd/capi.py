@@ -304,6 +304,8 @@ def load_library(path=None):
     if hasattr(lib, "bfdbg_scene_read_tree"):
         lib.bfdbg_scene_origin_scale.argtypes = [vp, C.POINTER(C.c_float)]
         lib.bfdbg_scene_read_tree.argtypes = [vp, C.c_uint32, C.c_int32, vp, C.c_uint64, vp, vp]
+    if hasattr(lib, "bfdbg_scene_generation_waves"):
+        lib.bfdbg_scene_generation_waves.argtypes = [vp, C.POINTER(C.c_int)]
     if path is None:
         _lib = lib
     return lib
@@ -1058,6 +1060,12 @@ class Scene:
         out = C.c_float(0.0)
         check(self.lib, self.lib.bfdbg_scene_origin_scale(self.handle, C.byref(out)), "bfdbg_scene_origin_scale")
         return np.float32(out.value)
+
+    def debug_generation_waves(self):
+        """test hook bfdbg_scene_generation_waves: waves per SIMD of the build the handle's latest generation launch of wf_shade ran"""
+        out = C.c_int(0)
+        check(self.lib, self.lib.bfdbg_scene_generation_waves(self.handle, C.byref(out)), "bfdbg_scene_generation_waves")
+        return int(out.value)
 
     def debug_read_tree(self, which, version=-1):
         """test hook bfdbg_scene_read_tree: (nodes, rows, normals) as the device holds them.  which = 4 / 16: NODE4_DTYPE /

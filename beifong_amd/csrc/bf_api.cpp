@@ -78,6 +78,7 @@ static bf_tunables read_tunables() {
     t.shade_chain = (uint32_t) std::max<long long>(1, num("BF_SHADE_CHAIN", bfd::kShadeChain));
     t.row_jobs = (uint32_t) num("BF_TAIL_ROWJOBS", bfd::kTailRowJobs);
     t.shade_waves = (int) std::max<long long>(1, std::min<long long>(4, num("BF_SHADE_WAVES", 3)));
+    if (getenv("BF_SHADE_WAVES")) t.gen_waves = t.shade_waves;      // an explicit budget is every shading launch's
     {
         const long long w = num("BF_TRACE_WAVES", 5);
         t.trace_waves = w < 5 ? 4 : (w > 5 ? 6 : 5);

@@ -24,6 +24,17 @@
 #define BF_TRACE_LAUNCHER(sfx) \
     extern "C" hipError_t bfk_wf_trace##sfx(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
 
+// The launches of wf_shade that START paths (first = 1: the first launch of a pool; 2: the wake launch of a rolling call) have a
+// second build, for four waves per SIMD, where that build is scratch-free in the exact AND the fast family
+// (profiles/no_slp_resource_usage.txt): the lean variants, except the wake launch of a receive-mode sequence (raw or I/Q: 20 B per lane in
+// the exact build).  The general, wide, per-path-table and per-render-geometry variants spill 16-140 B per lane there and stay at three,
+// and the _moment, _class, _aov and _sum families have no such build.  The launcher picks the build when the host asks for 4 waves,
+// and the host sizes that launch's grid by the same rule (bf_render.cpp: wf_setup).
+static inline bool bfk_shade_gen4(const bfd::DLaunch &lp, int first) {
+    if (!lp.lean || lp.wide || lp.multi || lp.geom_stride) return false;
+    return first == 1 || (first == 2 && lp.mode != BF_MODE_RECEIVE_RAW);      // (an I/Q launch is BF_MODE_RECEIVE_RAW + DLaunch::iq here)
+}
+
 #if BF_FAST
 // A fast device file: bfd::DScene, DLaunch and WF are bfd::fast:: types here, so it sees the family it defines and nothing else (the
 // other families' prototypes would name the same C functions with other parameter types)

@@ -19,9 +19,10 @@ struct Kernels {
     decltype(&bfk_wf_shade) shade;
     decltype(&bfk_wf_trace) trace;
     decltype(&bfk_launch_tail) tail;
+    bool gen4 = false;      // the family has four-wave builds of its generation launches (bf_launch.h: bfk_shade_gen4)
 };
-const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail};
-const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast};
+const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail, true};
+const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast, true};
 const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment};
 const Kernels kClass = {bfk_launch_render_class, bfk_wf_shade_class, bfk_wf_trace, bfk_launch_tail_class};
 const Kernels kAov = {bfk_launch_render_aov, bfk_wf_shade_aov, bfk_wf_trace, bfk_launch_tail_aov};      // (BF_FLAG_AOV: with none of the three above, check_aov)
@@ -141,6 +142,8 @@ struct WfCtx {
     bool count_nodes, timed;
     size_t mask_bytes, lds_shade, lds_tail;
     unsigned grid_shade, grid_trace;
+    unsigned grid_gen[2];   // grids of the launches of wf_shade that start paths ([0] first = 1, [1] the wake launch, first = 2) and
+    int gen_waves[2];       // their waves per SIMD
     uint32_t tail_max;
     bool alone;      // nothing else wants the CUs while the tail runs (the flush of a rolling sequence): wf_tail_launch
 };
@@ -148,6 +151,7 @@ struct WfCtx {
 // Dynamic LDS of a launch: [traversal stacks |] histogram, rounded up to 16 bytes | table cache (bf_device_core.h: load_tables_lds).
 // wf_shade has no stacks; the tail and the one-kernel variant have.
 static_assert(sizeof(int) * bfd::kStackDepth * bfd::kBlock % 16 == 0, "the stacks keep the histogram 16-byte aligned");
+constexpr size_t kLdsPerCU = 160u * 1024u;      // gfx950
 static size_t lds_bytes(const bfd::DLaunch &lp, uint32_t tab_cache, bool stacks) {
     return (stacks ? sizeof(int) * bfd::kStackDepth * bfd::kBlock : 0u) + ((sizeof(float) * lp.lds_floats + 15) & ~size_t(15)) +
            (tab_cache ? bfd::kTabBytes : 0u);
@@ -246,12 +250,21 @@ static bf_status wf_setup(const bf_scene *scene, const Kernels &k, const bfd::DL
     c.lds_shade = lds_bytes(lp, scene->d.tab_cache, false);
     c.lds_tail = lds_bytes(lp, scene->d.tab_cache, true);
     c.alone = false;
-    // persistent grids: shade is register-heavy (3 workgroups per CU at 168 VGPRs), trace runs
-    // 5 workgroups per CU (28.6 KiB of LDS each: stacks + the tree's top levels; 96 VGPRs)
+    // persistent grids: shade is register-heavy (its walk: 3 workgroups per CU at 147-153 VGPRs), trace runs
+    // 5 workgroups per CU (28.6 KiB of LDS each: stacks + the tree's top levels; 91 VGPRs)
     const unsigned batches_per_block = bfd::kBlock / 64;
     const unsigned max_blocks = (unsigned) ((nb + batches_per_block - 1) / batches_per_block);
     c.grid_shade = std::max(1u, std::min((unsigned) scene->n_cus * (unsigned) std::max(2, scene->tun.shade_waves), max_blocks));
     c.grid_trace = std::max(1u, std::min((unsigned) scene->n_cus * (unsigned) scene->tun.trace_waves, max_blocks));
+    // The launches that start paths (first / wake) need fewer registers than the walk: without packed fp32 their four-wave builds are
+    // scratch-free (128 VGPRs; profiles/no_slp_resource_usage.txt), so they run four workgroups per CU where such a build exists
+    // (bfk_shade_gen4) and four workgroups' dynamic LDS fit a CU; else, and under an explicit BF_SHADE_WAVES, they run as the walk does
+    const size_t lds_wg = (c.lds_shade + 16u + 1023u) & ~size_t(1023);      // + wf_shade's static words, in allocation granules (at most 1 KiB)
+    for (int first = 1; first <= 2; ++first) {
+        const bool four = scene->tun.gen_waves == 4 && k.gen4 && bfk_shade_gen4(lp, first) && 4 * lds_wg <= kLdsPerCU;
+        c.gen_waves[first - 1] = four ? 4 : scene->tun.shade_waves;
+        c.grid_gen[first - 1] = four ? std::max(1u, std::min((unsigned) scene->n_cus * 4u, max_blocks)) : c.grid_shade;
+    }
     // Small pools never fill the chip: their launches sit at latency floors with nearly idle waves, and a grid sized for the whole GPU
     // keeps the next handle's launch out until it has drained.  Handles that roll side by side (clones of one scene, one per stream)
     // therefore launch a SHARE of the persistent grids each, so that their launches overlap: C3 0.50 -> 0.45 ms per step, a C4 shard
@@ -261,6 +274,8 @@ static bf_status wf_setup(const bf_scene *scene, const Kernels &k, const bfd::DL
         const unsigned peers = (unsigned) std::max(1, scene->peers_rolling->load(std::memory_order_relaxed));
         const unsigned share = std::min(peers, (unsigned) scene->tun.grid_share);
         c.grid_shade = std::max(1u, c.grid_shade / share);
+        c.grid_gen[0] = std::max(1u, c.grid_gen[0] / share);
+        c.grid_gen[1] = std::max(1u, c.grid_gen[1] / share);
         c.grid_trace = std::max(1u, c.grid_trace / share);
     }
     c.tail_max = wf_tail_threshold(scene, rolling ? wf.n_main / 2 : wf.n_slots);
@@ -287,7 +302,9 @@ static bf_status wf_iteration(const WfCtx &c, uint32_t it, int first) {
     }
     if (first != 0) {
         HIP_TRY(wf_tic(c, 1));
-        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first, c.hist, c.rec, c.grid_shade, c.lds_shade, c.stream, scene->tun.shade_waves));
+        const int waves = c.gen_waves[first - 1];
+        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first, c.hist, c.rec, c.grid_gen[first - 1], c.lds_shade, c.stream, waves));
+        scene->run.gen_waves_last = waves == 4 ? 4 : 3;      // (the generation launches have no other builds)
         HIP_TRY(wf_toc(c));
     }
     return BF_OK;
@@ -741,7 +758,8 @@ static bf_status read_stats(const bf_scene *scene, uint64_t n_paths, bf_stats *s
 // general kernels (same results: tests/test_gpu_parity.py::test_lean_and_general_kernels_agree).
 static bool lean_profile(const bf_scene *scene, const bf_launch *launch, bool receive_mode, bool multi_pixel) {
     const EndpointState &ends = scene->ends;
-    // lean builds exist of the default register budgets only (three waves per SIMD), and not of the one-kernel variant
+    // lean builds exist of the default register budgets only (the walk launches and the tail at three waves per SIMD; the generation
+    // launches' budget, tun.gen_waves, is not a condition: they have lean builds at three and at four), and not of the one-kernel variant
     if ((launch->flags & BF_FLAG_MEGAKERNEL) || scene->tun.shade_waves != 3 || scene->tun.tail_waves != 3) return false;
     if (!scene->tun.lean || scene->d.n_emitters != 1 || scene->d.uvs != nullptr || ends.sensor_host.filt_n != 0u) return false;
     if (ends.sensor_host.win_off_t || ends.sensor_host.win_off_f) return false;      // ADC window away from the origin
@@ -1419,6 +1437,14 @@ bf_status bfdbg_preload_guard(bf_scene *scene, unsigned long long n) {
     if (!scene) return fail(BF_ERR_INVALID, "null argument");
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(scene->run.counters + bfd::CTR_GUARD, &n, sizeof(n), hipMemcpyHostToDevice));
+    return BF_OK;
+}
+
+/* test hook (not part of the ABI): waves per SIMD of the build the handle's latest generation launch (the first launch of a pool, the wake
+   launch of a rolling call) ran; 0 before any */
+bf_status bfdbg_scene_generation_waves(const bf_scene *scene, int *out) {
+    if (!scene || !out) return fail(BF_ERR_INVALID, "bfdbg_scene_generation_waves: null argument");
+    *out = scene->run.gen_waves_last;
     return BF_OK;
 }
 

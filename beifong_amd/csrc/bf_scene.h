@@ -64,6 +64,8 @@ struct bf_tunables {
     uint32_t trace_refill = bfd::kTraceRefill, trace_stragglers = bfd::kTraceStragglers;
     uint32_t shade_chain = bfd::kShadeChain, row_jobs = bfd::kTailRowJobs;
     int shade_waves = 3, trace_waves = 5, tail_waves = 3;
+    int gen_waves = 4;                       // waves per SIMD of the launches of wf_shade that start paths (first / wake), where a four-wave build exists
+                                             // and four workgroups' LDS fit a CU (bf_render.cpp: wf_setup); BF_SHADE_WAVES set: that budget, like every shading launch
     unsigned tail_spread = 1, tail_blocks = 0;
     int tail_share = -1;                     // BF_TAIL_SHARE: waves per batch in a stand-alone render's tail (-1: by pool size)
     bool allow_plan = true;                  // BF_WF_SYNC=1 turns launch plans off
@@ -219,6 +221,7 @@ struct __attribute__((visibility("hidden"))) RenderState {
     float ms[3] = {0, 0, 0};                    // trace, shade, tail
     uint32_t iters = 0, trace_launches = 0, tail_launches = 0, shade_launches = 0;
     uint32_t last_variant = 0;                  // BF_VARIANT_* of the latest render (bf_stats.kernel_variant)
+    int gen_waves_last = 0;                     // waves per SIMD of the build the latest generation launch (first / wake) ran (bfdbg_scene_generation_waves)
     // ---- the AOV table of the handle (bf_scene_set_aovs; BF_FLAG_AOV) and the side rows its launches carry the values in ----
     struct Aov {
         uint32_t n = 0;                          // entries; 0: no table

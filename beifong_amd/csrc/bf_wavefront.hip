@@ -726,8 +726,10 @@ extern "C" int bfdbg_shade_lane_profile(unsigned long long *out, int clear) {
 static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
                                   hipStream_t stream, int waves, bool moment, bool classed = false, bool aov = false, bool sum = false) {
-    // `waves`: register budget of the shading kernel (waves per SIMD); 3 is the sweet spot (168 VGPRs)
+    // `waves`: register budget of the shading kernel (waves per SIMD).  The walk launches (first 0 / 3): 3 is the sweet spot (their
+    // four-wave builds spill); the generation launches (first 1 / 2) run their scratch-free four-wave builds when the host asks for 4
     const bool rx = lp->mode == BF_MODE_RECEIVE_RAW;
+    const bool gen4 = waves == 4 && bfk_shade_gen4(*lp, first) && !(moment || classed || aov || sum);
 #define BF_SHADE_LAUNCH_RX(F, W, RX_)                                                                                              \
     hipLaunchKernelGGL((bfd::wf_shade<F, W, RX_>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, *lp, *wf, it, g_hist, records)
 #define BF_SHADE_LAUNCH(F, W)            \
@@ -736,9 +738,9 @@ static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp,
 #define BF_SHADE_LAUNCH_WIDE(F)                          \
     if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kWide);    \
     else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kWide)
-#define BF_SHADE_LAUNCH_LEAN(F)                          \
-    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kLean);    \
-    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kLean)
+#define BF_SHADE_LAUNCH_LEAN(F, W)                       \
+    if (rx) BF_SHADE_LAUNCH_RX(F, W, 1 | bfd::kLean);    \
+    else BF_SHADE_LAUNCH_RX(F, W, 0 | bfd::kLean)
 #define BF_SHADE_LAUNCH_MULTI(F)                         \
     if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kMulti);   \
     else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kMulti)
@@ -852,11 +854,14 @@ static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp,
         else if (first) { BF_SHADE_LAUNCH_MULTI(1); }
         else { BF_SHADE_LAUNCH_MULTI(0); }
     } else if (lp->lean && !lp->wide && (first || waves == 3)) {
-        // scene and launch fit the lean profile (bf_device.h: kLean; three waves per SIMD only)
-        if (first == 3) { BF_SHADE_LAUNCH_LEAN(3); }
-        else if (first == 2) { BF_SHADE_LAUNCH_LEAN(2); }
-        else if (first) { BF_SHADE_LAUNCH_LEAN(1); }
-        else { BF_SHADE_LAUNCH_LEAN(0); }
+        // scene and launch fit the lean profile (bf_device.h: kLean; the walk launches at three waves per SIMD only, the generation
+        // launches at three or, where bfk_shade_gen4 says so, four: never the wake launch of a receive-mode sequence)
+        if (first == 3) { BF_SHADE_LAUNCH_LEAN(3, 3); }
+        else if (first == 2 && gen4) { BF_SHADE_LAUNCH_RX(2, 4, 0 | bfd::kLean); }
+        else if (first == 2) { BF_SHADE_LAUNCH_LEAN(2, 3); }
+        else if (first && gen4) { BF_SHADE_LAUNCH_LEAN(1, 4); }
+        else if (first) { BF_SHADE_LAUNCH_LEAN(1, 3); }
+        else { BF_SHADE_LAUNCH_LEAN(0, 3); }
     } else if (lp->wide) {
         // reconstruction filter wider than a pixel: the kWide variants (three waves per SIMD only)
         if (first == 3) { BF_SHADE_LAUNCH_WIDE(3); }
