@@ -533,9 +533,6 @@ template <bool RESUME, int TW, int VX> void launch_form(const KernelLaunch &k, i
     }
 #undef BF_GO
 }
-bfv::Shape launch_shape(const bfd::DLaunch *lp, int tail_waves) {
-    return {lp->geom_stride != 0, lp->wide != 0, lp->lean != 0, lp->multi != 0, lp->roll != 0, lp->mode == BF_MODE_RECEIVE_RAW, tail_waves == 2};
-}
 }  // namespace
 
 // The one-kernel render.  The cases are the instantiations this object holds: the general kernel with or without per-render geometry
@@ -548,7 +545,7 @@ static hipError_t render_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, f
     bfd::WF none;
     memset(&none, 0, sizeof(none));
     const KernelLaunch k = {sc, lp, &none, 0u, g_hist, records, counters, grid, lds_bytes, stream};
-    switch (render_variant(feature, launch_shape(lp, 0))) {
+    switch (render_variant(feature, bfk_launch_shape(*lp))) {
         case 0: launch_form<false, BF_TAIL_WAVES, 0>(k, stats); break;
         case kWide: launch_form<false, BF_TAIL_WAVES, kWide>(k, stats); break;
         case kGeom: launch_form<false, BF_TAIL_WAVES, kGeom>(k, stats); break;
@@ -602,7 +599,7 @@ static hipError_t tail_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, con
     if (block_cap) grid = std::min(grid, block_cap);
     if (grid == 0) return hipSuccess;
     const KernelLaunch k = {sc, lp, wf, it, g_hist, records, wf->counters, grid, lds_bytes, stream};
-    switch (tail_variant(feature, launch_shape(lp, tail_waves))) {
+    switch (tail_variant(feature, bfk_launch_shape(*lp, tail_waves))) {
         case 0: launch_form<true, 3, 0>(k, stats); break;
         case kTailTwo: launch_form<true, 2, 0>(k, stats); break;
         case kLean: launch_form<true, 3, kLean>(k, stats); break;

@@ -1,11 +1,13 @@
 // Every host-callable launcher (bfk_*) of bf_kernels.hip, bf_wavefront.hip, bf_geom.hip and bf_query.hip, declared once.  The .hip
 // file that defines a launcher includes this header and so do the .cpp files that call it: the launchers have C linkage, so a
 // parameter list that differs between the two sides would still link; seen together it is the compile error "conflicting types".
-// (bf_build.h and bf_converge.h do the same for bf_build.hip and bf_converge.hip.)
+// (bf_build.h and bf_converge.h do the same for bf_build.hip and bf_converge.hip.)  Which instantiation a render launcher runs is
+// bf_variant.h, which takes the launch as bfk_launch_shape below describes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "bf_device.h"
+#include "bf_variant.h"
 #include "bf_wavefront.h"
 
 // The launchers a render goes through, once per family of kernels: the exact build (no suffix), the fast-arithmetic build (_fast,
@@ -24,15 +26,9 @@
 #define BF_TRACE_LAUNCHER(sfx) \
     extern "C" hipError_t bfk_wf_trace##sfx(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid, hipStream_t stream, int waves);
 
-// The launches of wf_shade that START paths (first = 1: the first launch of a pool; 2: the wake launch of a rolling call) have a
-// second build, for four waves per SIMD, where that build is scratch-free in the exact AND the fast family
-// (profiles/no_slp_resource_usage.txt): the lean variants, except the wake launch of a receive-mode sequence (raw or I/Q: 20 B per lane in
-// the exact build).  The general, wide, per-path-table and per-render-geometry variants spill 16-140 B per lane there and stay at three,
-// and the _moment, _class, _aov and _sum families have no such build.  The launcher picks the build when the host asks for 4 waves,
-// and the host sizes that launch's grid by the same rule (bf_render.cpp: wf_setup).
-static inline bool bfk_shade_gen4(const bfd::DLaunch &lp, int first) {
-    if (!lp.lean || lp.wide || lp.multi || lp.geom_stride) return false;
-    return first == 1 || (first == 2 && lp.mode != BF_MODE_RECEIVE_RAW);      // (an I/Q launch is BF_MODE_RECEIVE_RAW + DLaunch::iq here)
+// the shape of a launch as bf_variant.h's selectors take it (tail_waves: the tail's launchers alone)
+static inline bfv::Shape bfk_launch_shape(const bfd::DLaunch &lp, int tail_waves = 0) {
+    return {lp.geom_stride != 0, lp.wide != 0, lp.lean != 0, lp.multi != 0, lp.roll != 0, lp.mode == BF_MODE_RECEIVE_RAW, tail_waves == 2};
 }
 
 #if BF_FAST

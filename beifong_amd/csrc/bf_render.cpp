@@ -3,6 +3,7 @@
 // kernels: bf_kernels.hip, bf_wavefront.hip.
 #include "bf_scene.h"
 #include "bf_sum.h"
+#include "bf_variant.h"
 
 #include <algorithm>
 #include <cmath>
@@ -19,14 +20,15 @@ struct Kernels {
     decltype(&bfk_wf_shade) shade;
     decltype(&bfk_wf_trace) trace;
     decltype(&bfk_launch_tail) tail;
-    bool gen4 = false;      // the family has four-wave builds of its generation launches (bf_launch.h: bfk_shade_gen4)
+    bfv::Feature feature;      // what bf_variant.h's selectors call the family, and whether its kernels are the fast object's
+    bool fast;
 };
-const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail, true};
-const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast, true};
-const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment};
-const Kernels kClass = {bfk_launch_render_class, bfk_wf_shade_class, bfk_wf_trace, bfk_launch_tail_class};
-const Kernels kAov = {bfk_launch_render_aov, bfk_wf_shade_aov, bfk_wf_trace, bfk_launch_tail_aov};      // (BF_FLAG_AOV: with none of the three above, check_aov)
-const Kernels kSum = {bfk_launch_render_sum, bfk_wf_shade_sum, bfk_wf_trace, bfk_launch_tail_sum};      // (BF_FLAG_EXACT_SUM: with none of the four above, check_sum)
+const Kernels kExact = {bfk_launch_render, bfk_wf_shade, bfk_wf_trace, bfk_launch_tail, bfv::kPlain, false};
+const Kernels kFast = {bfk_launch_render_fast, bfk_wf_shade_fast, bfk_wf_trace_fast, bfk_launch_tail_fast, bfv::kPlain, true};
+const Kernels kMoment = {bfk_launch_render_moment, bfk_wf_shade_moment, bfk_wf_trace, bfk_launch_tail_moment, bfv::kFeatMoment, false};
+const Kernels kClass = {bfk_launch_render_class, bfk_wf_shade_class, bfk_wf_trace, bfk_launch_tail_class, bfv::kFeatClass, false};
+const Kernels kAov = {bfk_launch_render_aov, bfk_wf_shade_aov, bfk_wf_trace, bfk_launch_tail_aov, bfv::kFeatAov, false};      // (BF_FLAG_AOV: with none of the three above, check_aov)
+const Kernels kSum = {bfk_launch_render_sum, bfk_wf_shade_sum, bfk_wf_trace, bfk_launch_tail_sum, bfv::kFeatSum, false};      // (BF_FLAG_EXACT_SUM: with none of the four above, check_sum)
 // (BF_FLAG_MOMENT | BF_FLAG_FAST, and BF_FLAG_CLASSES with either, are refused before any kernel is chosen: check_launch)
 const Kernels &kernels_for(uint32_t flags) {
     if (flags & BF_FLAG_EXACT_SUM) return kSum;
@@ -143,7 +145,8 @@ struct WfCtx {
     size_t mask_bytes, lds_shade, lds_tail;
     unsigned grid_shade, grid_trace;
     unsigned grid_gen[2];   // grids of the launches of wf_shade that start paths ([0] first = 1, [1] the wake launch, first = 2) and
-    int gen_waves[2];       // their waves per SIMD
+    int gen_waves[2];       // the waves per SIMD they ask for, and
+    int gen_build[2];       // the W of the build that request gets (bf_variant.h: shade_variant)
     uint32_t tail_max;
     bool alone;      // nothing else wants the CUs while the tail runs (the flush of a rolling sequence): wf_tail_launch
 };
@@ -258,11 +261,14 @@ static bf_status wf_setup(const bf_scene *scene, const Kernels &k, const bfd::DL
     c.grid_trace = std::max(1u, std::min((unsigned) scene->n_cus * (unsigned) scene->tun.trace_waves, max_blocks));
     // The launches that start paths (first / wake) need fewer registers than the walk: without packed fp32 their four-wave builds are
     // scratch-free (128 VGPRs; profiles/no_slp_resource_usage.txt), so they run four workgroups per CU where such a build exists
-    // (bfk_shade_gen4) and four workgroups' dynamic LDS fit a CU; else, and under an explicit BF_SHADE_WAVES, they run as the walk does
+    // (bf_variant.h: the W shade_variant answers a request for four with) and four workgroups' dynamic LDS fit a CU; else, and under an
+    // explicit BF_SHADE_WAVES, they run as the walk does
     const size_t lds_wg = (c.lds_shade + 16u + 1023u) & ~size_t(1023);      // + wf_shade's static words, in allocation granules (at most 1 KiB)
     for (int first = 1; first <= 2; ++first) {
-        const bool four = scene->tun.gen_waves == 4 && k.gen4 && bfk_shade_gen4(lp, first) && 4 * lds_wg <= kLdsPerCU;
+        const bfv::Shape shape = bfk_launch_shape(lp);
+        const bool four = scene->tun.gen_waves == 4 && 4 * lds_wg <= kLdsPerCU && bfv::shade_variant(k.feature, k.fast, shape, first, 4).w == 4;
         c.gen_waves[first - 1] = four ? 4 : scene->tun.shade_waves;
+        c.gen_build[first - 1] = bfv::shade_variant(k.feature, k.fast, shape, first, c.gen_waves[first - 1]).w;
         c.grid_gen[first - 1] = four ? std::max(1u, std::min((unsigned) scene->n_cus * 4u, max_blocks)) : c.grid_shade;
     }
     // Small pools never fill the chip: their launches sit at latency floors with nearly idle waves, and a grid sized for the whole GPU
@@ -302,9 +308,8 @@ static bf_status wf_iteration(const WfCtx &c, uint32_t it, int first) {
     }
     if (first != 0) {
         HIP_TRY(wf_tic(c, 1));
-        const int waves = c.gen_waves[first - 1];
-        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first, c.hist, c.rec, c.grid_gen[first - 1], c.lds_shade, c.stream, waves));
-        scene->run.gen_waves_last = waves == 4 ? 4 : 3;      // (the generation launches have no other builds)
+        HIP_TRY(c.k->shade(&scene->d, c.lp, &wf, it, first, c.hist, c.rec, c.grid_gen[first - 1], c.lds_shade, c.stream, c.gen_waves[first - 1]));
+        scene->run.gen_waves_last = c.gen_build[first - 1];
         HIP_TRY(wf_toc(c));
     }
     return BF_OK;

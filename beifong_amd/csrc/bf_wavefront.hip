@@ -25,6 +25,9 @@
 #include "bf_film.h"
 #include "bf_mask_cursor.h"
 #include "bf_launch.h"
+#include "bf_variant.h"
+
+#include <utility>
 
 BF_NS_BEGIN
 
@@ -721,255 +724,71 @@ extern "C" int bfdbg_shade_lane_profile(unsigned long long *out, int clear) {
 }
 #endif
 
-// moment: the kMoment variants (BF_FLAG_MOMENT; bfk_wf_shade_moment below); classed: the kClass variants (BF_FLAG_CLASSES; bfk_wf_shade_class);
-// aov: the kAov variants (BF_FLAG_AOV; bfk_wf_shade_aov); sum: the kSum variants (BF_FLAG_EXACT_SUM; bfk_wf_shade_sum)
+static_assert(bfv::kWide == bfd::kWide && bfv::kLean == bfd::kLean && bfv::kMulti == bfd::kMulti && bfv::kGeom == bfd::kGeom &&
+                  bfv::kMoment == bfd::kMoment && bfv::kClass == bfd::kClass && bfv::kAov == bfd::kAov && bfv::kSum == bfd::kSum,
+              "bf_variant.h restates the variant word of bf_device.h");
+
+namespace {
+// f(std::integral_constant<int, C>()) for the one candidate C = AT(0), ..., AT(N - 1) that equals v; false if none does
+template <int (*AT)(int), int... Is, class F> bool pick(int v, std::integer_sequence<int, Is...>, F &&f) {
+    return ((v == AT(Is) && (f(std::integral_constant<int, AT(Is)>()), true)) || ...);
+}
+constexpr int itself(int i) { return i; }
+}  // namespace
+
+// Which <FIRST, W, V> a shading launch runs is bfv::shade_variant, which of them this object holds is bfv::shade_exists (bf_variant.h):
+// the launch's template arguments are the selector's triple, and a triple the object does not hold is refused as a refused launch is.
 static hipError_t wf_shade_launch(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                  hipStream_t stream, int waves, bool moment, bool classed = false, bool aov = false, bool sum = false) {
-    // `waves`: register budget of the shading kernel (waves per SIMD).  The walk launches (first 0 / 3): 3 is the sweet spot (their
-    // four-wave builds spill); the generation launches (first 1 / 2) run their scratch-free four-wave builds when the host asks for 4
-    const bool rx = lp->mode == BF_MODE_RECEIVE_RAW;
-    const bool gen4 = waves == 4 && bfk_shade_gen4(*lp, first) && !(moment || classed || aov || sum);
-#define BF_SHADE_LAUNCH_RX(F, W, RX_)                                                                                              \
-    hipLaunchKernelGGL((bfd::wf_shade<F, W, RX_>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, *lp, *wf, it, g_hist, records)
-#define BF_SHADE_LAUNCH(F, W)            \
-    if (rx) BF_SHADE_LAUNCH_RX(F, W, 1); \
-    else BF_SHADE_LAUNCH_RX(F, W, 0)
-#define BF_SHADE_LAUNCH_WIDE(F)                          \
-    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kWide);    \
-    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kWide)
-#define BF_SHADE_LAUNCH_LEAN(F, W)                       \
-    if (rx) BF_SHADE_LAUNCH_RX(F, W, 1 | bfd::kLean);    \
-    else BF_SHADE_LAUNCH_RX(F, W, 0 | bfd::kLean)
-#define BF_SHADE_LAUNCH_MULTI(F)                         \
-    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kMulti);   \
-    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kMulti)
-#define BF_SHADE_LAUNCH_GEOM(F, V)                           \
-    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kGeom | (V));  \
-    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kGeom | (V))
-#define BF_SHADE_LAUNCH_GEOM_V(F)                                          \
-    if (lp->lean && !lp->wide) { BF_SHADE_LAUNCH_GEOM(F, bfd::kLean); }    \
-    else if (lp->wide) { BF_SHADE_LAUNCH_GEOM(F, bfd::kWide); }            \
-    else { BF_SHADE_LAUNCH_GEOM(F, 0); }
-#if !BF_FAST
-    // BF_FLAG_MOMENT (never with BF_FLAG_FAST): the kMoment variants, three waves per SIMD, in the forms the other launches
-    // come in — per-render geometry, per-path tables, lean, wide, general
-#define BF_SHADE_LAUNCH_MOM(F, V)                                \
-    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kMoment | (V));    \
-    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kMoment | (V))
-#define BF_SHADE_LAUNCH_MOM_F(V)                         \
-    if (first == 3) { BF_SHADE_LAUNCH_MOM(3, V); }       \
-    else if (first == 2) { BF_SHADE_LAUNCH_MOM(2, V); }  \
-    else if (first) { BF_SHADE_LAUNCH_MOM(1, V); }       \
-    else { BF_SHADE_LAUNCH_MOM(0, V); }
-    if (moment) {
-        if (lp->geom_stride) {
-            if (first >= 2) return hipErrorInvalidValue;
-            if (lp->lean && !lp->wide) {
-                if (first) { BF_SHADE_LAUNCH_MOM(1, bfd::kGeom | bfd::kLean); }
-                else { BF_SHADE_LAUNCH_MOM(0, bfd::kGeom | bfd::kLean); }
-            } else if (lp->wide) {
-                if (first) { BF_SHADE_LAUNCH_MOM(1, bfd::kGeom | bfd::kWide); }
-                else { BF_SHADE_LAUNCH_MOM(0, bfd::kGeom | bfd::kWide); }
-            } else {
-                if (first) { BF_SHADE_LAUNCH_MOM(1, bfd::kGeom); }
-                else { BF_SHADE_LAUNCH_MOM(0, bfd::kGeom); }
-            }
-        } else if (lp->multi) {
-            BF_SHADE_LAUNCH_MOM_F(bfd::kMulti)
-        } else if (lp->lean && !lp->wide) {
-            BF_SHADE_LAUNCH_MOM_F(bfd::kLean)
-        } else if (lp->wide) {
-            BF_SHADE_LAUNCH_MOM_F(bfd::kWide)
-        } else {
-            BF_SHADE_LAUNCH_MOM_F(0)
-        }
-        return hipGetLastError();
+                                  hipStream_t stream, int waves, bfv::Feature feature) {
+    const bfv::ShadeForm s = bfv::shade_variant(feature, BF_FAST, bfk_launch_shape(*lp), first, waves);
+    bool launched = false;
+    pick<itself>(s.first, std::make_integer_sequence<int, bfv::kShadeFirsts>(), [&](auto F) {
+        pick<itself>(s.w, std::make_integer_sequence<int, bfv::kShadeWavesMax + 1>(), [&](auto W) {
+            pick<bfv::shade_word>(s.v, std::make_integer_sequence<int, bfv::kShadeWords>(), [&](auto V) {
+                constexpr int kF = decltype(F)::value, kW = decltype(W)::value, kV = decltype(V)::value;
+                if constexpr (bfv::shade_exists(BF_FAST, kF, kW, kV)) {
+                    hipLaunchKernelGGL((bfd::wf_shade<kF, kW, kV>), dim3(grid), dim3(bfd::kBlock), lds_bytes, stream, *sc, *lp, *wf, it, g_hist,
+                                       records);
+                    launched = true;
+                }
+            });
+        });
+    });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
+}
+// the families of bf_launch.h this object defines: its own build's (no suffix, or _fast) and, in the exact build, the kMoment
+// (BF_FLAG_MOMENT), kClass (BF_FLAG_CLASSES), kAov (BF_FLAG_AOV) and kSum (BF_FLAG_EXACT_SUM) kernels'
+#define BF_DEFINE_SHADE_LAUNCHER(name, feature)                                                                                          \
+    extern "C" hipError_t bfk_wf_shade##name(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,  \
+                                             float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes, hipStream_t stream, \
+                                             int waves) {                                                                                \
+        return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, feature);                        \
     }
-#undef BF_SHADE_LAUNCH_MOM_F
-#undef BF_SHADE_LAUNCH_MOM
-    // BF_FLAG_CLASSES (never with BF_FLAG_FAST, BF_FLAG_MOMENT or a rolling sequence): the kClass variants, three waves per SIMD, of
-    // the general forms only — a lean scene runs the general kernel — with or without per-render geometry and a wide filter
-#define BF_SHADE_LAUNCH_CLS(F, V)                               \
-    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kClass | (V));    \
-    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kClass | (V))
-#define BF_SHADE_LAUNCH_CLS_F(V)                     \
-    if (first) { BF_SHADE_LAUNCH_CLS(1, V); }        \
-    else { BF_SHADE_LAUNCH_CLS(0, V); }
-    if (classed) {
-        if (first >= 2 || lp->multi || lp->roll) return hipErrorInvalidValue;
-        if (lp->geom_stride && lp->wide) { BF_SHADE_LAUNCH_CLS_F(bfd::kGeom | bfd::kWide) }
-        else if (lp->geom_stride) { BF_SHADE_LAUNCH_CLS_F(bfd::kGeom) }
-        else if (lp->wide) { BF_SHADE_LAUNCH_CLS_F(bfd::kWide) }
-        else { BF_SHADE_LAUNCH_CLS_F(0) }
-        return hipGetLastError();
-    }
-#undef BF_SHADE_LAUNCH_CLS_F
-#undef BF_SHADE_LAUNCH_CLS
-    // BF_FLAG_AOV (render modes; never with BF_FLAG_FAST, BF_FLAG_MOMENT, BF_FLAG_CLASSES or a rolling sequence, whose DLaunch words
-    // carry the AOV table here): the kAov variants of the same general forms
-#define BF_SHADE_LAUNCH_AOV_F(V)                                  \
-    if (first) { BF_SHADE_LAUNCH_RX(1, 3, 0 | bfd::kAov | (V)); } \
-    else { BF_SHADE_LAUNCH_RX(0, 3, 0 | bfd::kAov | (V)); }
-    if (aov) {
-        if (first >= 2 || rx || lp->roll) return hipErrorInvalidValue;
-        if (lp->geom_stride && lp->wide) { BF_SHADE_LAUNCH_AOV_F(bfd::kGeom | bfd::kWide) }
-        else if (lp->geom_stride) { BF_SHADE_LAUNCH_AOV_F(bfd::kGeom) }
-        else if (lp->wide) { BF_SHADE_LAUNCH_AOV_F(bfd::kWide) }
-        else { BF_SHADE_LAUNCH_AOV_F(0) }
-        return hipGetLastError();
-    }
-#undef BF_SHADE_LAUNCH_AOV_F
-    // BF_FLAG_EXACT_SUM (never with BF_FLAG_FAST, BF_FLAG_MOMENT, BF_FLAG_CLASSES, BF_FLAG_AOV or a rolling sequence): the kSum variants
-    // of the same general forms, both mode classes
-#define BF_SHADE_LAUNCH_SUM(F, V)                             \
-    if (rx) BF_SHADE_LAUNCH_RX(F, 3, 1 | bfd::kSum | (V));    \
-    else BF_SHADE_LAUNCH_RX(F, 3, 0 | bfd::kSum | (V))
-#define BF_SHADE_LAUNCH_SUM_F(V)                     \
-    if (first) { BF_SHADE_LAUNCH_SUM(1, V); }        \
-    else { BF_SHADE_LAUNCH_SUM(0, V); }
-    if (sum) {
-        if (first >= 2 || lp->multi || lp->roll) return hipErrorInvalidValue;
-        if (lp->geom_stride && lp->wide) { BF_SHADE_LAUNCH_SUM_F(bfd::kGeom | bfd::kWide) }
-        else if (lp->geom_stride) { BF_SHADE_LAUNCH_SUM_F(bfd::kGeom) }
-        else if (lp->wide) { BF_SHADE_LAUNCH_SUM_F(bfd::kWide) }
-        else { BF_SHADE_LAUNCH_SUM_F(0) }
-        return hipGetLastError();
-    }
-#undef BF_SHADE_LAUNCH_SUM_F
-#undef BF_SHADE_LAUNCH_SUM
+#if BF_FAST
+BF_DEFINE_SHADE_LAUNCHER(_fast, bfv::kPlain)
 #else
-    if (moment || classed || aov || sum) return hipErrorInvalidValue;
+BF_DEFINE_SHADE_LAUNCHER(, bfv::kPlain)
+BF_DEFINE_SHADE_LAUNCHER(_moment, bfv::kFeatMoment)
+BF_DEFINE_SHADE_LAUNCHER(_class, bfv::kFeatClass)
+BF_DEFINE_SHADE_LAUNCHER(_aov, bfv::kFeatAov)
+BF_DEFINE_SHADE_LAUNCHER(_sum, bfv::kFeatSum)
 #endif
-    if (lp->geom_stride) {
-        // per-render geometry versions (bf_render_motion_batch_device): three waves per SIMD; never a rolling sequence, so
-        // neither its evicting (3) nor its wake (2) launch
-        if (first >= 2) return hipErrorInvalidValue;
-        if (first) { BF_SHADE_LAUNCH_GEOM_V(1); }
-        else { BF_SHADE_LAUNCH_GEOM_V(0); }
-    } else if (lp->multi) {
-        // the sequence's endpoints moved between its renders: per-path tables (bf_device.h: kMulti; general kernels, box filter)
-        if (first == 3) { BF_SHADE_LAUNCH_MULTI(3); }
-        else if (first == 2) { BF_SHADE_LAUNCH_MULTI(2); }
-        else if (first) { BF_SHADE_LAUNCH_MULTI(1); }
-        else { BF_SHADE_LAUNCH_MULTI(0); }
-    } else if (lp->lean && !lp->wide && (first || waves == 3)) {
-        // scene and launch fit the lean profile (bf_device.h: kLean; the walk launches at three waves per SIMD only, the generation
-        // launches at three or, where bfk_shade_gen4 says so, four: never the wake launch of a receive-mode sequence)
-        if (first == 3) { BF_SHADE_LAUNCH_LEAN(3, 3); }
-        else if (first == 2 && gen4) { BF_SHADE_LAUNCH_RX(2, 4, 0 | bfd::kLean); }
-        else if (first == 2) { BF_SHADE_LAUNCH_LEAN(2, 3); }
-        else if (first && gen4) { BF_SHADE_LAUNCH_LEAN(1, 4); }
-        else if (first) { BF_SHADE_LAUNCH_LEAN(1, 3); }
-        else { BF_SHADE_LAUNCH_LEAN(0, 3); }
-    } else if (lp->wide) {
-        // reconstruction filter wider than a pixel: the kWide variants (three waves per SIMD only)
-        if (first == 3) { BF_SHADE_LAUNCH_WIDE(3); }
-        else if (first == 2) { BF_SHADE_LAUNCH_WIDE(2); }
-        else if (first) { BF_SHADE_LAUNCH_WIDE(1); }
-        else { BF_SHADE_LAUNCH_WIDE(0); }
-    } else if (first == 3) {
-        BF_SHADE_LAUNCH(3, 3);
-    } else if (first == 2) {
-        BF_SHADE_LAUNCH(2, 3);
-    } else if (first) {
-        BF_SHADE_LAUNCH(1, 3);
-    } else {
-        switch (waves) {
-            case 2: BF_SHADE_LAUNCH(0, 2); break;
-            case 3: BF_SHADE_LAUNCH(0, 3); break;
-            case 4: BF_SHADE_LAUNCH(0, 4); break;
-            default: BF_SHADE_LAUNCH(0, 1); break;
-        }
-    }
-#undef BF_SHADE_LAUNCH
-#undef BF_SHADE_LAUNCH_WIDE
-#undef BF_SHADE_LAUNCH_LEAN
-#undef BF_SHADE_LAUNCH_MULTI
-#undef BF_SHADE_LAUNCH_GEOM
-#undef BF_SHADE_LAUNCH_GEOM_V
-#undef BF_SHADE_LAUNCH_RX
-    return hipGetLastError();
-}
-extern "C" hipError_t BF_LAUNCHER(bfk_wf_shade)(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                   float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                   hipStream_t stream, int waves) {
-    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false);
-}
-#if !BF_FAST
-extern "C" hipError_t bfk_wf_shade_moment(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                          float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                          hipStream_t stream, int waves) {
-    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, true);
-}
-extern "C" hipError_t bfk_wf_shade_class(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                         float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                         hipStream_t stream, int waves) {
-    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, true);
-}
-extern "C" hipError_t bfk_wf_shade_aov(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                       float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                       hipStream_t stream, int waves) {
-    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, false, true);
-}
-extern "C" hipError_t bfk_wf_shade_sum(const bfd::DScene *sc, const bfd::DLaunch *lp, const bfd::WF *wf, uint32_t it, int first,
-                                       float *g_hist, bf_path_record *records, unsigned grid, size_t lds_bytes,
-                                       hipStream_t stream, int waves) {
-    return wf_shade_launch(sc, lp, wf, it, first, g_hist, records, grid, lds_bytes, stream, waves, false, false, false, true);
-}
-#endif
+#undef BF_DEFINE_SHADE_LAUNCHER
 
+// bfv::trace_variant and bfv::trace_exists, the same way
 extern "C" hipError_t BF_LAUNCHER(bfk_wf_trace)(const bfd::DScene *sc, const bfd::WF *wf, uint32_t it, int stats, unsigned grid,
                                    hipStream_t stream, int waves) {
-    const bool shift = wf->offsets != nullptr, quant = sc->qnodes != nullptr;
-    if (wf->geom_stride) {
-        // per-render geometry versions (bf_render_motion_batch_device; never with mesh offsets): no LDS copy of the top nodes
-#define BF_TRACE_GEOM(S, W)                                                                                                   \
-    if (quant) hipLaunchKernelGGL((bfd::wf_trace<S, W, false, true, true>), dim3(grid), dim3(bfd::kBlock), 0, stream, *sc, *wf, it); \
-    else hipLaunchKernelGGL((bfd::wf_trace<S, W, false, false, true>), dim3(grid), dim3(bfd::kBlock), 0, stream, *sc, *wf, it)
-        if (stats) {
-            if (waves >= 5) { BF_TRACE_GEOM(true, 5); }
-            else { BF_TRACE_GEOM(true, 4); }
-        } else {
-            if (waves >= 5) { BF_TRACE_GEOM(false, 5); }
-            else { BF_TRACE_GEOM(false, 4); }
-        }
-#undef BF_TRACE_GEOM
-        return hipGetLastError();
-    }
-#define BF_TRACE_LAUNCH2(S, W, SH, Q) \
-    hipLaunchKernelGGL((bfd::wf_trace<S, W, SH, Q>), dim3(grid), dim3(bfd::kBlock), 0, stream, *sc, *wf, it)
-#define BF_TRACE_LAUNCH1(S, W)                      \
-    if (shift) {                                    \
-        if (quant) BF_TRACE_LAUNCH2(S, W, true, true);  \
-        else BF_TRACE_LAUNCH2(S, W, true, false);   \
-    } else {                                        \
-        if (quant) BF_TRACE_LAUNCH2(S, W, false, true); \
-        else BF_TRACE_LAUNCH2(S, W, false, false);  \
-    }
-#define BF_TRACE_LAUNCH(W)   \
-    if (stats) {             \
-        BF_TRACE_LAUNCH1(true, W)  \
-    } else {                 \
-        BF_TRACE_LAUNCH1(false, W) \
-    }
-    // 28.6 KiB of LDS per workgroup (stacks + the tree's top levels): five workgroups per CU is the most that fit
-    // (the quantised nodes' copy is 6.8 KiB: six workgroups per CU fit, if the register allocation follows)
-    if (waves >= 6 && quant) {
-        if (stats) {
-            if (shift) BF_TRACE_LAUNCH2(true, 6, true, true);
-            else BF_TRACE_LAUNCH2(true, 6, false, true);
-        } else {
-            if (shift) BF_TRACE_LAUNCH2(false, 6, true, true);
-            else BF_TRACE_LAUNCH2(false, 6, false, true);
-        }
-    } else if (waves >= 5) {
-        BF_TRACE_LAUNCH(5);
-    } else {
-        BF_TRACE_LAUNCH(4);
-    }
-#undef BF_TRACE_LAUNCH
-#undef BF_TRACE_LAUNCH1
-#undef BF_TRACE_LAUNCH2
-    return hipGetLastError();
+    const bfv::TraceForm t = bfv::trace_variant(stats != 0, waves, wf->offsets != nullptr, sc->qnodes != nullptr, wf->geom_stride != 0);
+    bool launched = false;
+    pick<itself>(t.w, std::make_integer_sequence<int, bfv::kTraceWavesMax + 1>(), [&](auto W) {
+        pick<itself>(t.flags(), std::make_integer_sequence<int, bfv::kTraceFlags>(), [&](auto B) {
+            constexpr bfv::TraceForm k = bfv::trace_form(decltype(W)::value, decltype(B)::value);
+            if constexpr (bfv::trace_exists(k)) {
+                hipLaunchKernelGGL((bfd::wf_trace<k.stats, k.w, k.shift, k.quant, k.geom>), dim3(grid), dim3(bfd::kBlock), 0, stream, *sc, *wf, it);
+                launched = true;
+            }
+        });
+    });
+    return launched ? hipGetLastError() : hipErrorInvalidValue;
 }

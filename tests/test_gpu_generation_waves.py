@@ -1,5 +1,5 @@
 """The launches of wf_shade that START paths — the first launch of a pool (wf_shade<1>) and the wake launch of a rolling call
-(wf_shade<2>) — run at four waves per SIMD where their four-wave build is scratch-free (bf_launch.h: bfk_shade_gen4:
+(wf_shade<2>) — run at four waves per SIMD where their four-wave build is scratch-free (bf_variant.h: shade_variant:
 the lean variants, except the wake launch of a receive-mode sequence), on a grid sized for four workgroups per CU (bf_render.cpp:
 wf_setup); the walk launches, and the generation launches of every other variant, stay at three.  A path must be the same path
 whatever launch generated it: every per-path record here is held bit for bit to the oracle's (and, for rolling sequences, to a
@@ -86,13 +86,15 @@ def _fresh(kind, n_paths, seed=SEEDS[0], bins=64):
 
 
 def _gen_waves(kind, wake=False):
-    """what bfk_shade_gen4 says: the general kernels (spot) stay at three, and so does the wake launch of the receive modes — and
-    every launch under the knobs that take the lean kernels or the default budget away (bf_render.cpp: lean_profile; the suite
-    also runs under each of them: tools/r04_knob_matrix.sh)"""
+    """bf_variant.h: shade_variant's rule for four waves — a LEAN launch that starts paths, asked for four: the first launch (first = 1)
+    of either mode class, the wake launch (first = 2) outside the receive modes; every other launch three.  The spot scene is outside the
+    lean profile, and so is every scene under the knobs that take the lean kernels away (bf_render.cpp: lean_profile: BF_LEAN=0, a walk
+    or tail budget other than three); an explicit BF_SHADE_WAVES is every shading launch's budget, so nothing asks for four."""
     e = os.environ
-    if "BF_SHADE_WAVES" in e or e.get("BF_LEAN", "1") == "0" or e.get("BF_TAIL_WAVES", "3") == "2":
-        return 3
-    return 3 if kind == "spot" or (wake and kind in ("receive", "receive_iq")) else 4
+    lean = kind != "spot" and e.get("BF_LEAN", "1") != "0" and e.get("BF_TAIL_WAVES", "3") != "2"
+    asked_four = "BF_SHADE_WAVES" not in e
+    receive = kind in ("receive", "receive_iq")
+    return 4 if asked_four and lean and (not wake or not receive) else 3
 
 
 def _rolling(kind, n_paths, n_handles=1):
