@@ -34,6 +34,7 @@ BF_MAX_AOVS = 16
 BF_FLAG_EXACT_SUM = 4096
 BF_NORMALS_GIVEN, BF_NORMALS_RECOMPUTE = range(2)
 BF_SKIN_LINEAR, BF_SKIN_DUAL_QUATERNION = range(2)
+BF_VELOCITY_TWIST, BF_VELOCITY_VERTEX, BF_VELOCITY_DIFFERENCE = range(3)
 (BF_AOV_DEPTH, BF_AOV_POSITION, BF_AOV_UV, BF_AOV_GEO_NORMAL, BF_AOV_SH_NORMAL, BF_AOV_DP_DU, BF_AOV_DP_DV, BF_AOV_DUV_DX,
  BF_AOV_DUV_DY, BF_AOV_TYPES) = range(10)
 # the reference's type names (aov.cpp:96-127) in BF_AOV_* order, and the floats of each
@@ -188,6 +189,7 @@ EXPORTED_SYMBOLS = [
     "bf_emitter_sample_direction", "bf_emitter_sample_direction_device", "bf_sensor_sample_ray", "bf_sensor_sample_ray_device",
     "bf_ray_intersect_device", "bf_trace_any_device", "bf_eval_microfacet",
     "bf_render_converge_device", "bf_render_converge", "bf_converge_statistic_device",
+    "bf_scene_set_velocity_mode", "bf_scene_get_velocity_mode", "bf_scene_set_vertex_velocities", "bf_scene_set_vertex_velocities_device",
     "bf_scene_set_classes", "bf_scene_set_arrival_classes", "bf_scene_set_range_rate_classes", "bf_scene_launch_channels", "bf_aov_floats", "bf_scene_set_aovs",
     "bf_exact_sum_host", "bf_exact_sum",
 ]
@@ -236,6 +238,10 @@ def load_library(path=None):
     lib.bf_scene_set_classes.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp]
     lib.bf_scene_set_arrival_classes.argtypes = [vp, C.POINTER(bf_arrival_bins), vp]
     lib.bf_scene_set_range_rate_classes.argtypes = [vp, C.POINTER(bf_range_rate_bins), vp, vp]
+    lib.bf_scene_set_velocity_mode.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_float]
+    lib.bf_scene_get_velocity_mode.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+    lib.bf_scene_set_vertex_velocities.argtypes = [vp, C.c_uint32, vp, vp]
+    lib.bf_scene_set_vertex_velocities_device.argtypes = [vp, C.c_uint32, vp, vp]
     lib.bf_scene_launch_channels.argtypes = [vp, C.POINTER(bf_launch)]
     lib.bf_scene_launch_channels.restype = C.c_uint32
     lib.bf_aov_floats.argtypes = [C.c_uint32, vp]
@@ -600,9 +606,41 @@ def range_rate_twists(twists, n_shapes=None):
     return t
 
 
-def range_rates(d, p, shape, bins, twists):
+def corner_velocities(p_prev, p_next, dt):
+    """float32, the shape of p_prev: the corner velocities of BF_VELOCITY_DIFFERENCE from two sets of rendered positions, THE
+    SPECIFICATION of the difference in numpy float32: (p_next - p_prev) / dt per component, the difference and the IEEE quotient
+    each rounded on its own.  dt: a positive finite float32 (a scalar, or anything that broadcasts)."""
+    f = np.float32
+    a, b, t = np.asarray(p_prev, f), np.asarray(p_next, f), np.asarray(dt, f)
+    with np.errstate(all="ignore"):
+        diff = b - a
+        v = diff / t
+    assert diff.dtype == f and v.dtype == f
+    return v
+
+
+def interpolate_velocity(uv, v0, v1, v2):
+    """float32[n, 3]: the velocity at a hit with barycentrics uv (float32[n, 2], bf_ray_intersect's prim_uv) of a triangle whose
+    corners, in face order, move with v0, v1, v2 (float32[n, 3] each), THE SPECIFICATION of the interpolation in numpy float32,
+    every product, sum and difference rounded on its own, no FMA:
+        b0 = (1 - u) - v
+        U  = (b0 v0 + u v1) + v v2                        per component"""
+    f = np.float32
+    uv = np.asarray(uv, f).reshape(-1, 2)
+    v0, v1, v2 = (np.asarray(x, f).reshape(-1, 3) for x in (v0, v1, v2))
+    u, v = uv[:, 0:1], uv[:, 1:2]
+    with np.errstate(all="ignore"):
+        b0 = (f(1) - u) - v
+        out = (b0 * v0 + u * v1) + v * v2
+    assert b0.dtype == f and out.dtype == f
+    return out
+
+
+def range_rates(d, p, shape, bins, twists, vertex_velocity=None, has_velocity=None):
     """float32[n]: rr of range_rate_classes, the range rate of every path's first intersection along its primary ray (whatever
-    the row of shape 0 gives where shape < 0: range_rate_classes never looks at it)."""
+    the row of shape 0 gives where shape < 0: range_rate_classes never looks at it).  vertex_velocity (float32[n, 3],
+    interpolate_velocity) and has_velocity (bool[n]): the paths whose first intersection lies on a shape in BF_VELOCITY_VERTEX or
+    BF_VELOCITY_DIFFERENCE, and the velocity U interpolated there; for those w = ((lin + c) + U) - sensor_lin."""
     f = np.float32
     d = np.asarray(d, f).reshape(-1, 3)
     p = np.asarray(p, f).reshape(-1, 3)
@@ -616,12 +654,16 @@ def range_rates(d, p, shape, bins, twists):
         q = np.where(hit[:, None], p, f(0)) - pivot
         c = [ang[:, 1] * q[:, 2] - ang[:, 2] * q[:, 1], ang[:, 2] * q[:, 0] - ang[:, 0] * q[:, 2], ang[:, 0] * q[:, 1] - ang[:, 1] * q[:, 0]]
         w = [(lin[:, k] + c[k]) - sl[k] for k in range(3)]
+        if vertex_velocity is not None:
+            U = np.asarray(vertex_velocity, f).reshape(-1, 3)
+            has = np.ones(len(shape), bool) if has_velocity is None else np.asarray(has_velocity, bool).reshape(-1)
+            w = [np.where(has, ((lin[:, k] + c[k]) + U[:, k]) - sl[k], w[k]) for k in range(3)]
         rr = (d[:, 0] * w[0] + d[:, 1] * w[1]) + d[:, 2] * w[2]
     assert rr.dtype == f and q.dtype == f and all(x.dtype == f for x in c + w)
     return rr
 
 
-def range_rate_classes(d, p, shape, bins, twists):
+def range_rate_classes(d, p, shape, bins, twists, vertex_velocity=None, has_velocity=None):
     """The class of a path whose primary ray has direction d (float32[n, 3]) and first meets shape `shape` (int[n]; < 0: the ray
     leaves the scene) at p (float32[n, 3], world space) under the range-rate table `bins` (range_rate_bins) and `twists`
     (float32[n_shapes, 9], motion.twist): THE SPECIFICATION of bf_scene_set_range_rate_classes, in numpy float32 — every product,
@@ -633,11 +675,14 @@ def range_rate_classes(d, p, shape, bins, twists):
         sr  = float32(n_bins) / (r1 - r0)
         t   = (rr - r0) * sr
         class = uint32(t) if 0 <= t < n_bins else n_bins  (a NaN is outside); n_bins + 1 for a miss
+    With vertex_velocity (float32[n, 3]: U of interpolate_velocity) the paths of has_velocity (bool[n]; absent: all), those whose
+    first intersection lies on a mesh in BF_VELOCITY_VERTEX or BF_VELOCITY_DIFFERENCE (Scene.set_velocity_mode), take
+        w   = ((lin + c) + U) - sensor_lin
     Returns int64[n]."""
     f = np.float32
     hit = np.asarray(shape, np.int64).reshape(-1) >= 0
     n_bins = int(bins.n_bins)
-    rr = range_rates(d, p, shape, bins, twists)
+    rr = range_rates(d, p, shape, bins, twists, vertex_velocity, has_velocity)
     with np.errstate(all="ignore"):
         sr = f(n_bins) / (f(bins.r1) - f(bins.r0))
         t = (rr - f(bins.r0)) * sr
@@ -1328,6 +1373,42 @@ class Scene:
         mode = C.c_uint32(0)
         check(self.lib, self.lib.bf_scene_get_normal_mode(self.handle, shape, C.byref(mode)), "bf_scene_get_normal_mode")
         return int(mode.value)
+
+    def set_velocity_mode(self, shape, mode, dt=0.0):
+        """bf_scene_set_velocity_mode: how mesh shape `shape` moves under a range-rate table (range_rate_classes with
+        vertex_velocity= is the rule).  BF_VELOCITY_TWIST (the default): with its twist alone; BF_VELOCITY_VERTEX: plus the
+        per-vertex field of set_vertex_velocities; BF_VELOCITY_DIFFERENCE: plus the differences of its rendered positions over
+        `dt` seconds (corner_velocities), backward between the moves of a handle, forward between the renders of a batch.  Every
+        call with a mode other than BF_VELOCITY_TWIST zeroes the shape's field, a call that repeats the mode (to change dt) included;
+        the call waits for the handle's work in flight."""
+        shape, mode = int(shape), int(mode)
+        if shape < 0 or mode < 0:
+            raise ValueError(f"shape index {shape}, mode {mode}")
+        check(self.lib, self.lib.bf_scene_set_velocity_mode(self.handle, shape, mode, float(dt)), "bf_scene_set_velocity_mode")
+
+    def get_velocity_mode(self, shape):
+        """bf_scene_get_velocity_mode: (BF_VELOCITY_* mode, dt) of mesh shape `shape` on this handle."""
+        shape = int(shape)
+        if shape < 0:
+            raise ValueError(f"shape index {shape}")
+        mode, dt = C.c_uint32(0), C.c_float(0)
+        check(self.lib, self.lib.bf_scene_get_velocity_mode(self.handle, shape, C.byref(mode), C.byref(dt)), "bf_scene_get_velocity_mode")
+        return int(mode.value), float(dt.value)
+
+    def set_vertex_velocities(self, shape, velocities, stream=0, device=False):
+        """bf_scene_set_vertex_velocities: the world-space velocity [nv, 3] float32 of every vertex of mesh shape `shape`, which must
+        be in BF_VELOCITY_VERTEX (None: zeros).  device=True: `velocities` is the address of a device array (a torch tensor's
+        data_ptr(), valid until `stream` has run the call)."""
+        shape = int(shape)
+        if shape < 0:
+            raise ValueError(f"shape index {shape}")
+        st = C.c_void_p(stream) if stream else None
+        if device:
+            check(self.lib, self.lib.bf_scene_set_vertex_velocities_device(self.handle, shape, C.c_void_p(int(velocities)) if velocities else None, st),
+                  "bf_scene_set_vertex_velocities_device")
+            return
+        v = vertex_array(velocities, "velocities", self.mesh_vertex_count(shape)) if velocities is not None else None
+        check(self.lib, self.lib.bf_scene_set_vertex_velocities(self.handle, shape, _ptr(v), st), "bf_scene_set_vertex_velocities")
 
     def set_skin_mode(self, shape, mode):
         """bf_scene_set_skin_mode: BF_SKIN_DUAL_QUATERNION makes every later call that takes bones for mesh shape `shape` blend them

@@ -23,7 +23,7 @@
 
 #include "../../include/beifong_hip.h"
 #include "bf_arrival.h"
-#include "bf_range_rate.h"
+#include "bf_velocity.h"
 
 BF_NS_BEGIN
 
@@ -225,15 +225,29 @@ __device__ __forceinline__ uint32_t scene_arrival_class(const DScene &sc, float 
 constexpr uint32_t kClassRangeRate = 1u << 30;
 __host__ __device__ __forceinline__ bool scene_class_range_rate(const DScene &sc) { return (sc.class_info & kClassRangeRate) != 0u; }
 // the class of a path whose primary ray, direction d, first meets shape `shape` at p: the header by scalar loads through the constant
-// address space, the shape's row by three per-lane 16-byte loads
-__device__ __forceinline__ uint32_t scene_range_rate_class(const DScene &sc, uint32_t shape, float px, float py, float pz, float dx, float dy, float dz) {
+// address space, the shape's row by three per-lane 16-byte loads.  A mesh shape whose row carries a velocity mode other than
+// BF_VELOCITY_TWIST (the word behind `lin`, stamped by the host: bf_mesh.cpp: velocity_stamp) adds the velocity interpolated at the hit
+// (u, v) from the three corner rows of triangle slot `slot` (bf_velocity.h): three more 16-byte loads, `version_rows` float4 rows
+// behind the address in the header's two spare words (a kGeom launch: the rows of the path's render; else 0).
+__device__ __forceinline__ uint32_t scene_range_rate_class(const DScene &sc, uint32_t shape, float px, float py, float pz, float dx, float dy, float dz,
+                                                           int32_t slot, float u, float v, uint64_t version_rows) {
     const uint32_t *words = scene_classes(sc);
     const BF_CAS bfr::Header *h = as_const((const bfr::Header *) words);
     const float4 *row = (const float4 *) (words + bfr::kHeaderWords) + (size_t) shape * (bfr::kRowWords / 4u);
     const float4 lin = row[0], ang = row[1], pivot = row[2];
-    return bfr::classify(bfr::rate(px, py, pz, dx, dy, dz, lin.x, lin.y, lin.z, ang.x, ang.y, ang.z, pivot.x, pivot.y, pivot.z, h->sensor_lin[0],
-                                   h->sensor_lin[1], h->sensor_lin[2]),
-                         h->r0, h->sr, h->n_bins);
+    float rr;
+    if (__float_as_uint(lin.w) != bfvel::kTwist && slot >= 0) {
+        const float4 *vel = (const float4 *) (uintptr_t) (((uint64_t) h->pad[1] << 32) | h->pad[0]) + version_rows + bfvel::kRowsPerSlot * (size_t) slot;
+        const float4 v0 = vel[0], v1 = vel[1], v2 = vel[2];
+        const float w0 = bfvel::b0(u, v);
+        rr = bfvel::rate(px, py, pz, dx, dy, dz, lin.x, lin.y, lin.z, ang.x, ang.y, ang.z, pivot.x, pivot.y, pivot.z, h->sensor_lin[0], h->sensor_lin[1],
+                       h->sensor_lin[2], bfvel::interpolate(w0, u, v, v0.x, v1.x, v2.x), bfvel::interpolate(w0, u, v, v0.y, v1.y, v2.y),
+                       bfvel::interpolate(w0, u, v, v0.z, v1.z, v2.z));
+    } else {
+        rr = bfr::rate(px, py, pz, dx, dy, dz, lin.x, lin.y, lin.z, ang.x, ang.y, ang.z, pivot.x, pivot.y, pivot.z, h->sensor_lin[0], h->sensor_lin[1],
+                       h->sensor_lin[2]);
+    }
+    return bfr::classify(rr, h->r0, h->sr, h->n_bins);
 }
 
 // One render of a ROLLING SEQUENCE (bf_render_device with BF_FLAG_ROLLING): what differs between the renders of a

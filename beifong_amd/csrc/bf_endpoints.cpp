@@ -71,12 +71,24 @@ bf_status stage_copy(const bf_scene *sc, void *dst, const void *src, size_t byte
     return stage_release_after(stg, stream);
 }
 
+// the spare words of a range-rate table (bf_range_rate.h) from the handle's velocity modes (bf_velocity.h): every shape's mode behind its
+// `lin`, the address `rows` of the velocity rows in the header; without rows every shape reads as BF_VELOCITY_TWIST
+void velocity_patch(const bf_scene *scene, std::vector<uint32_t> &words, const float4 *rows) {
+    const uint32_t n_shapes = scene->ends.n_shapes;
+    if (words.size() != (size_t) bfr::table_words(n_shapes)) return;
+    words[6] = (uint32_t) (uintptr_t) rows;
+    words[7] = (uint32_t) ((uint64_t) (uintptr_t) rows >> 32);
+    static_assert(offsetof(bfr::Header, pad) == 24 && offsetof(bfr::Row, pad0) == 12, "the spare words of the range-rate table");
+    for (uint32_t k = 0; k < n_shapes; ++k) words[bfr::kHeaderWords + (size_t) bfr::kRowWords * k + 3] = rows ? scene->mesh.velocity_mode(k) : 0u;
+}
+
 // what bf_scene_set_classes, bf_scene_set_arrival_classes and bf_scene_set_range_rate_classes share: the open rolling sequence ends (its renders were issued without
 // classes; the table is not theirs to see change), the handle's device array exists, `words` go into it in stream order
 bf_status install_classes(bf_scene *scene, const void *words, size_t bytes, uint32_t class_info, hipStream_t stream) {
     bf_status st = order_after_last(scene, stream);
     if (st == BF_OK) st = close_sequence(scene, stream);
     if (st != BF_OK) return st;
+    if (!(class_info & bfd::kClassRangeRate)) scene->ends.rr_words.clear();
     if (!class_info) {
         scene->d.class_info = 0u;      // (the device array stays with the handle)
         return BF_OK;
@@ -466,7 +478,19 @@ bf_status endpoints_clone(const bf_scene *src, bf_scene *sc) {
     if ((st = dup(s.classes, sizeof(uint32_t) * class_words(s.n_shapes), &e.classes)) != BF_OK) return st;
     set_classes_ptr(sc->d, e.classes);
     if (!e.classes) sc->d.class_info = 0u;
+    // a range-rate table names the velocity rows it reads: the clone's own (mesh_clone_snapshot has made them)
+    if (e.classes && !e.rr_words.empty()) {
+        velocity_patch(sc, e.rr_words, sc->mesh.vel);
+        HIP_TRY(hipMemcpy(e.classes, e.rr_words.data(), sizeof(uint32_t) * e.rr_words.size(), hipMemcpyHostToDevice));
+    }
     return BF_OK;
+}
+
+bf_status velocity_stamp(bf_scene *scene, const float4 *rows, hipStream_t stream) {
+    EndpointState &e = scene->ends;
+    if (!bfd::scene_class_range_rate(scene->d) || e.rr_words.empty() || !e.classes) return BF_OK;
+    velocity_patch(scene, e.rr_words, rows);
+    return install_classes(scene, e.rr_words.data(), sizeof(uint32_t) * e.rr_words.size(), scene->d.class_info, stream);
 }
 
 bf_status bf_scene_update_endpoints(bf_scene *scene, const bf_scene_desc *desc, void *stream_) {
@@ -616,7 +640,10 @@ bf_status bf_scene_set_range_rate_classes(bf_scene *scene, const bf_range_rate_b
     const uint32_t outside = bins->n_bins;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
-    return install_classes(scene, words.data(), sizeof(uint32_t) * words.size(), (outside + 2u) | ((outside + 1u) << 16) | bfd::kClassRangeRate, stream);
+    velocity_patch(scene, words, scene->mesh.vel);
+    const bf_status st = install_classes(scene, words.data(), sizeof(uint32_t) * words.size(), (outside + 2u) | ((outside + 1u) << 16) | bfd::kClassRangeRate, stream);
+    if (st == BF_OK) scene->ends.rr_words = std::move(words);
+    return st;
 }
 
 }  // extern "C"

@@ -413,6 +413,75 @@ extern "C" hipError_t bfk_launch_deform_tris(const uint4 *corners, const bfd::DD
                        nrm, n_tris, xf, vstride, xf_stride, bound, bad);
     return hipGetLastError();
 }
+BF_NS_BEGIN
+// The velocity rows of bf_scene_set_velocity_mode (bf_velocity.h): three float4 per triangle slot, the world-space
+// velocity of each corner in face order (.w = 0).  One thread per triangle slot, grid y = version, `vstride` as bf_deform_tris_kernel.
+// modes[shape] = (the bits of the shape's BF_VELOCITY_* mode, its dt).  Version v differences the triangle rows `prev` + vstride pv and
+// `next` + vstride nv, (pv, nv) = (v, v + 1), or (tail_prev, tail_next) for the last version of the launch:
+//   BF_VELOCITY_DIFFERENCE : fl(fl(next - prev) / dt) per component (bfvel::corner)
+//   BF_VELOCITY_VERTEX     : the slot's rows of `own`, the handle's explicit field (the same for every version)
+//   BF_VELOCITY_TWIST      : zeros (never read), or nothing where `own` is the output itself (the handle's rows: one version)
+__global__ __launch_bounds__(256) void bf_velocity_diff_kernel(const float4 *__restrict__ prev, const float4 *__restrict__ next, float4 *vel,
+                                                               const float4 *own, uint32_t n_tris, const float2 *__restrict__ modes,
+                                                               uint64_t vstride, uint32_t tail_prev, uint32_t tail_next) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, ver = blockIdx.y;
+    if (i >= n_tris) return;
+    const bool last = ver + 1u == gridDim.y;
+    const float4 *a = prev + vstride * (last ? tail_prev : ver) + kTriStride * (size_t) i;
+    const float4 *b = next + vstride * (last ? tail_next : ver + 1u) + kTriStride * (size_t) i;
+    float4 *o = vel + vstride * ver + bfvel::kRowsPerSlot * (size_t) i;
+    const float4 *w = own ? own + bfvel::kRowsPerSlot * (size_t) i : nullptr;
+    const float4 b0 = b[0], b1 = b[1], b2 = b[2];
+    const float2 md = modes[__float_as_uint(b1.w)];
+    const uint32_t mode = __float_as_uint(md.x);
+    if (mode == bfvel::kDifference) {
+        const float4 a0 = a[0], a1 = a[1], a2 = a[2];
+        const float dt = md.y;
+        o[0] = make_float4(bfvel::corner(a0.x, b0.x, dt), bfvel::corner(a0.y, b0.y, dt), bfvel::corner(a0.z, b0.z, dt), 0.f);
+        o[1] = make_float4(bfvel::corner(a1.x, b1.x, dt), bfvel::corner(a1.y, b1.y, dt), bfvel::corner(a1.z, b1.z, dt), 0.f);
+        o[2] = make_float4(bfvel::corner(a2.x, b2.x, dt), bfvel::corner(a2.y, b2.y, dt), bfvel::corner(a2.z, b2.z, dt), 0.f);
+    } else if (w != o) {
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool copy = mode == bfvel::kVertex && w;
+        const float4 r0 = copy ? w[0] : z, r1 = copy ? w[1] : z, r2 = copy ? w[2] : z;
+        o[0] = r0;
+        o[1] = r1;
+        o[2] = r2;
+    }
+}
+// bf_scene_set_vertex_velocities: the rows of every slot of shape `shape` from the per-vertex field `field` ([n_vertices][3]; nullptr:
+// zeros) through the corner table, as bf_deform_tris_kernel gathers positions; every other slot's rows stay.
+__global__ __launch_bounds__(256) void bf_velocity_gather_kernel(const uint4 *__restrict__ corners, const float4 *__restrict__ tris,
+                                                                 const float *__restrict__ field, uint32_t shape, float4 *vel, uint32_t n_tris) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_tris || __float_as_uint(tris[kTriStride * (size_t) i + 1].w) != shape) return;
+    float4 *o = vel + bfvel::kRowsPerSlot * (size_t) i;
+    float g[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (field) {
+        const uint4 c = corners[i];
+        const float *p0 = field + 3u * (size_t) c.x, *p1 = field + 3u * (size_t) c.y, *p2 = field + 3u * (size_t) c.z;
+        g[0] = p0[0], g[1] = p0[1], g[2] = p0[2], g[3] = p1[0], g[4] = p1[1], g[5] = p1[2], g[6] = p2[0], g[7] = p2[1], g[8] = p2[2];
+    }
+    for (int j = 0; j < 3; ++j) o[j] = make_float4(g[3 * j], g[3 * j + 1], g[3 * j + 2], 0.f);
+}
+BF_NS_END  // namespace bfd
+
+extern "C" hipError_t bfk_launch_velocity_diff(const float4 *prev, const float4 *next, float4 *vel, const float4 *own, uint32_t n_tris,
+                                               const float2 *modes, uint32_t n_versions, uint64_t vstride, uint32_t tail_prev, uint32_t tail_next,
+                                               hipStream_t stream) {
+    if (n_tris == 0 || n_versions == 0) return hipSuccess;
+    if (n_versions > 65535u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bfd::bf_velocity_diff_kernel, dim3((n_tris + 255u) / 256u, n_versions), dim3(256), 0, stream, prev, next, vel, own, n_tris,
+                       modes, vstride, tail_prev, tail_next);
+    return hipGetLastError();
+}
+extern "C" hipError_t bfk_launch_velocity_gather(const uint4 *corners, const float4 *tris, const float *field, uint32_t shape, float4 *vel,
+                                                 uint32_t n_tris, hipStream_t stream) {
+    if (n_tris == 0) return hipSuccess;
+    hipLaunchKernelGGL(bfd::bf_velocity_gather_kernel, dim3((n_tris + 255u) / 256u), dim3(256), 0, stream, corners, tris, field, shape, vel, n_tris);
+    return hipGetLastError();
+}
+
 // ... and the refit of both trees behind it (bf_render_deform_batch_device: gather + rigid transform in one pass over the rows, then
 // the level kernels with the version dimension, as bfk_launch_rigid runs them)
 extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,

@@ -57,6 +57,12 @@ extern "C" hipError_t bfk_launch_translate(const float4 *tris0, float4 *tris, ui
 extern "C" hipError_t bfk_launch_deform_tris(const uint4 *corners, const bfd::DDeformSrc *src, const float4 *tris0, float4 *tris, const float4 *nrm0,
                                              float4 *nrm, uint32_t n_tris, const float *xf, uint32_t n_versions, uint64_t vstride,
                                              uint32_t xf_stride, float bound, uint32_t *bad, hipStream_t stream);
+// the velocity rows (bf_velocity.h): differenced from two sets of triangle rows, and gathered from an explicit per-vertex field
+extern "C" hipError_t bfk_launch_velocity_diff(const float4 *prev, const float4 *next, float4 *vel, const float4 *own, uint32_t n_tris,
+                                               const float2 *modes, uint32_t n_versions, uint64_t vstride, uint32_t tail_prev, uint32_t tail_next,
+                                               hipStream_t stream);
+extern "C" hipError_t bfk_launch_velocity_gather(const uint4 *corners, const float4 *tris, const float *field, uint32_t shape, float4 *vel,
+                                                 uint32_t n_tris, hipStream_t stream);
 extern "C" hipError_t bfk_launch_refit(const float4 *tris, const float4 *nodes0, float4 *nodes, float4 *qnodes, uint32_t n_nodes, const uint32_t *lvl4,
                                        const uint32_t *lvl4_off, uint32_t n_lvl4, float4 *ubox4, const float4 *wnodes0, float4 *wnodes,
                                        const uint32_t *lvl16, const uint32_t *lvl16_off, uint32_t n_lvl16, float4 *ubox16, float abs_pad,

@@ -64,8 +64,10 @@ float origin_bound(const std::vector<float> &mesh_box, uint32_t n_shapes, const 
 
 // Layout of one geometry version of a batch, in float4 rows from its start: triangles (+ the kTriPad rows behind them), vertex
 // normals, four-wide nodes, sixteen-wide nodes, quantised nodes, then the refit's scratch (unpadded child bounds of both trees).
-struct MotionLayout { size_t tris = 0, normals = 0, nodes = 0, wnodes = 0, qnodes = 0, ubox4 = 0, ubox16 = 0, rows = 0; };
-MotionLayout motion_layout(const bfd::DScene &d) {
+// with_vel: the velocity rows of the version too (bf_velocity.h; three per triangle slot), last, so that the other arrays lie where
+// they lie without them
+struct MotionLayout { size_t tris = 0, normals = 0, nodes = 0, wnodes = 0, qnodes = 0, ubox4 = 0, ubox16 = 0, vel = 0, rows = 0; };
+MotionLayout motion_layout(const bfd::DScene &d, bool with_vel) {
     MotionLayout L;
     size_t r = 0;
     auto take = [&](size_t &at, size_t rows) {
@@ -79,6 +81,7 @@ MotionLayout motion_layout(const bfd::DScene &d) {
     take(L.qnodes, d.qnodes ? (size_t) d.n_nodes * 4 : 0);
     take(L.ubox4, (size_t) d.n_nodes * 8);
     take(L.ubox16, d.wnodes ? (size_t) d.n_wnodes * 32 : 0);
+    take(L.vel, with_vel ? (size_t) d.n_tris * bfvel::kRowsPerSlot : 0);
     L.rows = r;
     return L;
 }
@@ -410,7 +413,15 @@ bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
     MeshState &m = scene->mesh;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     const uint64_t n_chan = bf_scene_launch_channels(scene, launch);      // floats per render (x n_classes under BF_FLAG_CLASSES; the AOV layout under BF_FLAG_AOV)
-    const MotionLayout L = motion_layout(scene->d);
+    // Velocity modes (bf_velocity.h): a shape in BF_VELOCITY_DIFFERENCE takes its field from consecutive versions, so a chunk is
+    // prepared with the first version of the next chunk behind it; the rows are built (and count towards the budget) only for a
+    // launch that can read them, a class launch under a range-rate table.
+    const bool with_vel = m.velocities() && (launch->flags & BF_FLAG_CLASSES) && bfd::scene_class_range_rate(scene->d) && m.vel && m.vel_tab;
+    const bool diff = with_vel && m.differences();
+    if (diff && n_renders < 2)
+        return fail(BF_ERR_INVALID, "%s: n_renders is 1: a shape of this scene is in BF_VELOCITY_DIFFERENCE, whose velocities are the differences "
+                                    "of consecutive renders (at least 2)", fn);
+    const MotionLayout L = motion_layout(scene->d, with_vel);
     if (L.rows > UINT32_MAX)
         return fail(BF_ERR_UNSUPPORTED, "%s: one geometry version of this scene is %zu float4 rows (at most 2^32 - 1)", fn, L.rows);
     size_t budget_mb = kMotionBatchMB;
@@ -420,8 +431,8 @@ bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
         if (end != e && *end == '\0') budget_mb = (size_t) v;
     }
     const size_t version_bytes = L.rows * sizeof(float4);
-    const uint32_t per_chunk = (uint32_t) std::max<size_t>(1, std::min<size_t>({(size_t) n_renders, 65535, (budget_mb << 20) / version_bytes}));
-    const size_t need = (size_t) per_chunk * L.rows;
+    const uint32_t per_chunk = (uint32_t) std::max<size_t>(1, std::min<size_t>({(size_t) n_renders, (size_t) (diff ? 65534 : 65535),(budget_mb << 20) / version_bytes}));
+    const size_t need = ((size_t) per_chunk + (diff ? 1 : 0)) * L.rows;      // (diff: the next chunk's first version)
     if (m.arena_cap < need) {
         // the old arena may still be read by the renders of an earlier call: wait for them before it goes
         if (m.arena) {
@@ -447,10 +458,40 @@ bf_status render_versions(bf_scene *scene, const bf_launch *launch, uint32_t n_r
     view.qnodes = scene->d.qnodes ? a + L.qnodes : nullptr;
     if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
     m.batch_versions = 0;
+    m.batch_vel = with_vel;
+    // while the chunks render, the range-rate table names the arena's velocity rows; the handle's own again on every return path
+    struct VelStamp {
+        bf_scene *s;
+        hipStream_t stream;
+        bool on;
+        ~VelStamp() {
+            if (on) (void) velocity_stamp(s, s->mesh.vel, stream);
+        }
+    } vel_stamp{scene, stream, false};
+    if (with_vel) {
+        const bf_status vst = velocity_stamp(scene, a + L.vel, stream);
+        if (vst != BF_OK) return vst;
+        vel_stamp.on = true;
+    }
     for (uint32_t k0 = 0; k0 < n_renders; k0 += per_chunk) {
         const uint32_t kc = std::min(per_chunk, n_renders - k0);
-        bf_status st = prepare(k0, kc, a, L);
+        const bool final = k0 + kc == n_renders;
+        bf_status st = prepare(k0, diff && !final ? kc + 1u : kc, a, L);
         if (st != BF_OK) return st;
+        if (with_vel) {
+            // the last version of the chunk: against the next chunk's first; the batch's last render: the field of the one before it
+            uint32_t tail_prev = kc - 1u, tail_next = diff && !final ? kc : kc - 1u;
+            if (diff && final && kc >= 2u) tail_prev = kc - 2u;
+            // (a last chunk of one render prepares version n - 2 once more, whole, pose, gather and refit, for its triangle rows alone,
+            // and a batch cut to one render per chunk prepares every version twice: redundant work where the budget is that tight,
+            // accepted for one way of making a version)
+            if (diff && final && kc == 1u) {
+                if ((st = prepare(n_renders - 2u, 1u, a + L.rows, L)) != BF_OK) return st;
+                tail_prev = 1u, tail_next = 0u;
+            }
+            HIP_TRY(bfk_launch_velocity_diff(a + L.tris, a + L.tris, a + L.vel, m.vel, scene->d.n_tris, m.vel_tab, kc, L.rows, tail_prev, tail_next,
+                                             stream));
+        }
         bf_batch b = {kc, seeds ? seeds + k0 : nullptr, nullptr};
         bf_stats cs;
         {
@@ -507,6 +548,9 @@ MeshState::~MeshState() {
     if (vtx_dev) (void) hipFree(vtx_dev);
     if (pose_vtx) (void) hipFree(pose_vtx);
     if (nrm_vtx) (void) hipFree(nrm_vtx);
+    if (vel) (void) hipFree(vel);
+    if (vel_prev) (void) hipFree(vel_prev);
+    if (vel_tab) (void) hipFree(vel_tab);
 }
 
 extern "C" {
@@ -552,6 +596,20 @@ bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
     sc->mesh.morphs = m.morphs;    // likewise (bf_scene_set_morph)
     sc->mesh.normal_mode = m.normal_mode;      // the source's modes at this moment; the clone's own from now on
     sc->mesh.skin_mode = m.skin_mode;          // likewise (bf_scene_set_skin_mode)
+    // ... and the velocity modes, time steps and field (bf_scene_set_velocity_mode): the clone's own rows, in the slot order both share now
+    sc->mesh.vel_mode = m.vel_mode;
+    sc->mesh.vel_dt = m.vel_dt;
+    if (m.vel && m.vel_tab) {
+        const size_t vel_bytes = (size_t) src->d.n_tris * bfvel::kRowsPerSlot * sizeof(float4), tab_bytes = (size_t) src->info.n_shapes * sizeof(float2);
+        hipError_t he = hipMalloc((void **) &sc->mesh.vel, vel_bytes);
+        if (he == hipSuccess) he = hipMalloc((void **) &sc->mesh.vel_tab, tab_bytes);
+        if (he != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(BF_ERR_NOMEM, "bf_scene_clone: hipMalloc(%zu bytes) for the velocity rows: %s", vel_bytes + tab_bytes, hipGetErrorString(he));
+        }
+        HIP_TRY(hipMemcpy(sc->mesh.vel, m.vel, vel_bytes, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMemcpy(sc->mesh.vel_tab, m.vel_tab, tab_bytes, hipMemcpyDeviceToDevice));
+    }
     if (!m.tris0 && !m.geom_private) return BF_OK;
     // `src` has moved: the clone snapshots what src renders now as ITS geometry "as created"; uvs (and normals no transform moved) stay shared
     const MeshState::Bytes B = MeshState::bytes(src->d);
@@ -572,6 +630,49 @@ bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc) {
     if (m.normals_private && (st = dup(src->d.normals, B.normals, &sc->d.normals)) != BF_OK) return st;
     sc->mesh.geom_private = true;
     sc->geom_token = std::make_shared<char>(0);      // the snapshot is the clone's alone: `src` keeps translating in place
+    return BF_OK;
+}
+
+// ---- velocity rows (bf_scene_set_velocity_mode) -----------------------------------------------------------------------
+bf_status velocity_before(bf_scene *scene, hipStream_t stream) {
+    MeshState &m = scene->mesh;
+    if (!m.differences() || !m.vel) return BF_OK;
+    const size_t bytes = (size_t) scene->d.n_tris * bfd::kTriStride * sizeof(float4);
+    if (!m.vel_prev) {
+        const hipError_t he = hipMalloc((void **) &m.vel_prev, bytes);
+        if (he != hipSuccess) {
+            (void) hipGetLastError();
+            return fail(BF_ERR_NOMEM, "hipMalloc(%zu bytes) for the triangle rows a velocity difference starts from: %s", bytes, hipGetErrorString(he));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(m.vel_prev, scene->d.tris, bytes, hipMemcpyDeviceToDevice, stream));
+    return BF_OK;
+}
+bf_status velocity_after(bf_scene *scene, uint32_t shape, hipStream_t stream) {
+    MeshState &m = scene->mesh;
+    if (!m.differences() || !m.vel || !m.vel_prev) return BF_OK;
+    if (shape != kAllShapes && m.velocity_mode(shape) != BF_VELOCITY_DIFFERENCE) return BF_OK;
+    // One version, its output the handle's own rows: the kernel leaves the slots of every shape it is not told to difference as they
+    // are.  A call that moved one shape tells it that shape alone (a table of the call's own: every other shape reads as
+    // BF_VELOCITY_TWIST), so a shape the call did not move keeps its field, though the pose has rewritten its rows with what they held.
+    const float2 *tab = m.vel_tab;
+    if (shape != kAllShapes) {
+        const size_t bytes = (size_t) scene->info.n_shapes * sizeof(float2);
+        bf_scene::Stage *stg = nullptr;
+        bf_status st = stage_acquire(scene, bytes, &stg);
+        if (st != BF_OK) return st;
+        std::memset(stg->host, 0, bytes);
+        const uint32_t bits = BF_VELOCITY_DIFFERENCE;
+        float2 &e = ((float2 *) stg->host)[shape];
+        std::memcpy(&e.x, &bits, 4);
+        e.y = m.vel_dt[shape];
+        if ((st = stage_commit(stg, bytes, stream)) != BF_OK) return st;
+        tab = (const float2 *) stg->dev;
+        HIP_TRY(bfk_launch_velocity_diff(m.vel_prev, scene->d.tris, m.vel, m.vel, scene->d.n_tris, tab, 1u, 0u, 0u, 0u, stream));
+        HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel, not only by the copy
+        return BF_OK;
+    }
+    HIP_TRY(bfk_launch_velocity_diff(m.vel_prev, scene->d.tris, m.vel, m.vel, scene->d.n_tris, tab, 1u, 0u, 0u, 0u, stream));
     return BF_OK;
 }
 
@@ -790,6 +891,7 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
     const bfd::DScene &d = scene->d;
     bf_status st = mesh_enter(scene, stream);
     if (st != BF_OK) return st;
+    if ((st = velocity_before(scene, stream)) != BF_OK) return st;
     if (m.deformed && !m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
     if ((st = own_geometry(scene, stream, __func__)) != BF_OK) return st;
     m.pose_kind = 1;      // [I | offset] for every shape
@@ -801,8 +903,8 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
     }
     if (m.deformed) {
         // nodes0 / wnodes0 do not bound the base rows: the same vertices (fl(v + offset) either way) under re-fitted boxes
-        st = apply_pose(scene, stream);
-        return st != BF_OK ? st : mark_last(scene, stream);
+        if ((st = apply_pose(scene, stream)) != BF_OK || (st = velocity_after(scene, kAllShapes, stream)) != BF_OK) return st;
+        return mark_last(scene, stream);
     }
     if (m.normals_moved) {
         // a rigid transform moved the vertex normals: a translation applies to the geometry as created
@@ -812,6 +914,7 @@ bf_status bf_scene_translate_meshes(bf_scene *scene, const float offset[3], void
     HIP_TRY(bfk_launch_translate(m.tris0, const_cast<float4 *>(d.tris), d.n_tris * bfd::kTriStride, m.nodes0, const_cast<float4 *>(d.nodes),
                                  const_cast<float4 *>(d.qnodes), d.n_nodes, m.wnodes0, const_cast<float4 *>(d.wnodes),
                                  d.wnodes ? d.n_wnodes * 16u : 0u, offset, stream));
+    if ((st = velocity_after(scene, kAllShapes, stream)) != BF_OK) return st;
     return mark_last(scene, stream);
 }
 
@@ -828,6 +931,7 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
     BF_ENTER(scene);
     MeshState &m = scene->mesh;
     if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if ((st = velocity_before(scene, stream)) != BF_OK) return st;
     if (!m.refit.ready && (st = refit_prepare(scene, stream)) != BF_OK) return st;
     if ((st = own_geometry(scene, stream, __func__)) != BF_OK) return st;
     if ((st = m.own_normals(scene->d, scene->owned, __func__)) != BF_OK) return st;      // the vertex normals move too
@@ -836,7 +940,8 @@ bf_status bf_scene_transform_meshes(bf_scene *scene, uint32_t n_shapes, const fl
     m.pose_kind = 2;
     m.pose_xf.resize((size_t) n_shapes * 16);
     pack_rigid(m.pose_xf.data(), to_world, moves.data(), n_shapes);
-    return (st = run_pose(scene, stream)) != BF_OK ? st : mark_last(scene, stream);
+    if ((st = run_pose(scene, stream)) != BF_OK || (st = velocity_after(scene, kAllShapes, stream)) != BF_OK) return st;
+    return mark_last(scene, stream);
 }
 
 bf_status bf_scene_update_vertices(bf_scene *scene, uint32_t shape, const float *positions, const float *normals, void *stream_) {
@@ -858,6 +963,7 @@ bf_status bf_scene_update_vertices(bf_scene *scene, uint32_t shape, const float 
     BF_ENTER(scene);
     MeshState &m = scene->mesh;
     if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if ((st = velocity_before(scene, stream)) != BF_OK) return st;
     // the caller's arrays through the handle's upload buffer (the staging ring is for small tables): free again on return
     const size_t bytes = n * sizeof(float) * (normals ? 2 : 1);
     if (m.vtx_ev) HIP_TRY(hipEventSynchronize(m.vtx_ev));      // the previous update's gather may still read it
@@ -876,7 +982,7 @@ bf_status bf_scene_update_vertices(bf_scene *scene, uint32_t shape, const float 
     HIP_TRY(hipMemcpyAsync(m.vtx_dev, m.vtx_host, bytes, hipMemcpyHostToDevice, stream));
     st = update_vertices_locked(scene, shape, *tp, (const float *) m.vtx_dev, normals ? (const float *) m.vtx_dev + n : nullptr, inf, box, false, stream);
     HIP_TRY(hipEventRecord(m.vtx_ev, stream));
-    if (st != BF_OK) return st;
+    if (st != BF_OK || (st = velocity_after(scene, shape, stream)) != BF_OK) return st;
     return mark_last(scene, stream);
 }
 
@@ -891,8 +997,10 @@ bf_status bf_scene_update_vertices_device(bf_scene *scene, uint32_t shape, const
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     BF_ENTER(scene);
     if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if ((st = velocity_before(scene, stream)) != BF_OK) return st;
     const float box[6] = {-bound, -bound, -bound, bound, bound, bound};
     if ((st = update_vertices_locked(scene, shape, *tp, positions_dev, normals_dev, bound, box, true, stream)) != BF_OK) return st;
+    if ((st = velocity_after(scene, shape, stream)) != BF_OK) return st;
     return mark_last(scene, stream);
 }
 
@@ -929,6 +1037,134 @@ bf_status bf_scene_get_normal_mode(const bf_scene *scene, uint32_t shape, uint32
     BF_ENTER(scene);
     *mode_out = scene->mesh.recomputes(shape) ? BF_NORMALS_RECOMPUTE : BF_NORMALS_GIVEN;
     return BF_OK;
+}
+
+// ---- velocity modes and the explicit field (bf_velocity.h) ------------------------------------------------------------
+// what the four entries refuse first: `fn` ends in ':'
+static bf_status check_velocity_shape(const bf_scene *scene, uint32_t shape, const char *fn) {
+    if (!scene) return fail(BF_ERR_INVALID, "%s null scene", fn);
+    if (shape >= scene->info.n_shapes) return fail(BF_ERR_INVALID, "%s shape %u: the scene has %u shapes", fn, shape, scene->info.n_shapes);
+    if (scene->ends.shapes_host[shape].type != BF_SHAPE_MESH) return fail(BF_ERR_INVALID, "%s shape %u is not a mesh", fn, shape);
+    return BF_OK;
+}
+// bf_scene_set_vertex_velocities and its device form behind their checks: the field (nullptr: zeros) gathered to the shape's slots
+static bf_status gather_velocities(bf_scene *scene, uint32_t shape, const float *field_dev, hipStream_t stream) {
+    MeshState &m = scene->mesh;
+    bf_status st = BF_OK;
+    if (field_dev && (st = deform_prepare(scene, stream)) != BF_OK) return st;      // the corner table
+    HIP_TRY(bfk_launch_velocity_gather(scene->geom->corners, scene->d.tris, field_dev, shape, m.vel, scene->d.n_tris, stream));
+    return BF_OK;
+}
+
+bf_status bf_scene_set_velocity_mode(bf_scene *scene, uint32_t shape, uint32_t mode, float dt) {
+    const char *fn = "bf_scene_set_velocity_mode:";
+    bf_status st = check_velocity_shape(scene, shape, fn);
+    if (st != BF_OK) return st;
+    if (mode != BF_VELOCITY_TWIST && mode != BF_VELOCITY_VERTEX && mode != BF_VELOCITY_DIFFERENCE)
+        return fail(BF_ERR_INVALID, "%s shape %u: unknown mode %u (BF_VELOCITY_TWIST, BF_VELOCITY_VERTEX or BF_VELOCITY_DIFFERENCE)", fn, shape, mode);
+    if (mode == BF_VELOCITY_DIFFERENCE && !(std::isfinite(dt) && dt > 0.f))
+        return fail(BF_ERR_INVALID, "%s shape %u: dt = %g: the time step of BF_VELOCITY_DIFFERENCE must be finite and positive", fn, shape, (double) dt);
+    BF_ENTER(scene);
+    MeshState &m = scene->mesh;
+    const uint32_t n_shapes = scene->info.n_shapes;
+    if (mode == BF_VELOCITY_TWIST && !m.vel) return BF_OK;      // no shape has left the default yet
+    // the call has no stream: it waits for the handle's work in flight (an open rolling sequence ends, as for a class table), changes
+    // the tables, and is complete when it returns
+    if ((st = close_sequence(scene, scene->run.roll.stream)) != BF_OK) return st;
+    HIP_TRY(scene->run.last.wait());
+    if (!m.vel) {
+        // everything exists before any state changes: a failed call leaves the scene as it was
+        const size_t vel_bytes = (size_t) scene->d.n_tris * bfvel::kRowsPerSlot * sizeof(float4), tab_bytes = (size_t) n_shapes * sizeof(float2);
+        float4 *vel = nullptr;
+        float2 *tab = nullptr;
+        hipError_t he = hipMalloc((void **) &vel, vel_bytes);
+        if (he == hipSuccess) he = hipMalloc((void **) &tab, tab_bytes);
+        if (he == hipSuccess) he = hipMemset(vel, 0, vel_bytes);
+        if (he != hipSuccess) {
+            (void) hipGetLastError();
+            if (vel) (void) hipFree(vel);
+            if (tab) (void) hipFree(tab);
+            return fail(BF_ERR_NOMEM, "%s hipMalloc(%zu bytes) for the velocity rows: %s", fn, vel_bytes + tab_bytes, hipGetErrorString(he));
+        }
+        m.vel = vel;
+        m.vel_tab = tab;
+    }
+    if (m.vel_mode.size() < n_shapes) m.vel_mode.resize(n_shapes, (uint8_t) BF_VELOCITY_TWIST);
+    if (m.vel_dt.size() < n_shapes) m.vel_dt.resize(n_shapes, 0.f);
+    m.vel_mode[shape] = (uint8_t) mode;
+    m.vel_dt[shape] = mode == BF_VELOCITY_DIFFERENCE ? dt : 0.f;
+    std::vector<float2> tab(n_shapes);
+    for (uint32_t k = 0; k < n_shapes; ++k) {
+        const uint32_t bits = m.vel_mode[k];
+        std::memcpy(&tab[k].x, &bits, 4);
+        tab[k].y = m.vel_dt[k];
+    }
+    HIP_TRY(hipMemcpy(m.vel_tab, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice));
+    // the field is zero until one is given (BF_VELOCITY_VERTEX) or a move differences it (BF_VELOCITY_DIFFERENCE)
+    if (mode != BF_VELOCITY_TWIST && (st = gather_velocities(scene, shape, nullptr, nullptr)) != BF_OK) return st;
+    if ((st = velocity_stamp(scene, m.vel, nullptr)) != BF_OK) return st;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return BF_OK;
+}
+
+bf_status bf_scene_get_velocity_mode(const bf_scene *scene, uint32_t shape, uint32_t *mode_out, float *dt_out) {
+    const char *fn = "bf_scene_get_velocity_mode:";
+    const bf_status st = check_velocity_shape(scene, shape, fn);
+    if (st != BF_OK) return st;
+    if (!mode_out && !dt_out) return fail(BF_ERR_INVALID, "%s null argument", fn);
+    BF_ENTER(scene);
+    if (mode_out) *mode_out = scene->mesh.velocity_mode(shape);
+    if (dt_out) *dt_out = shape < scene->mesh.vel_dt.size() ? scene->mesh.vel_dt[shape] : 0.f;
+    return BF_OK;
+}
+
+bf_status bf_scene_set_vertex_velocities(bf_scene *scene, uint32_t shape, const float *vel, void *stream_) {
+    const char *fn = "bf_scene_set_vertex_velocities:";
+    bf_status st = check_velocity_shape(scene, shape, fn);
+    if (st != BF_OK) return st;
+    const size_t n = 3 * (size_t) scene->geom->topo[shape].n_vertices;
+    for (size_t i = 0; vel && i < n; ++i)
+        if (!std::isfinite(vel[i])) return fail(BF_ERR_INVALID, "%s shape %u: non-finite value at vertex %zu", fn, shape, i / 3);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    MeshState &m = scene->mesh;
+    if (m.velocity_mode(shape) != BF_VELOCITY_VERTEX || !m.vel)
+        return fail(BF_ERR_INVALID, "%s shape %u is not in BF_VELOCITY_VERTEX (bf_scene_set_velocity_mode)", fn, shape);
+    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if (!vel || n == 0) return (st = gather_velocities(scene, shape, nullptr, stream)) != BF_OK ? st : mark_last(scene, stream);
+    // the caller's array through the handle's upload buffer, as a vertex update's
+    const size_t bytes = n * sizeof(float);
+    if (m.vtx_ev) HIP_TRY(hipEventSynchronize(m.vtx_ev));      // the previous gather may still read it
+    if (m.vtx_cap < bytes) {
+        if (m.vtx_host) (void) hipHostFree(m.vtx_host);
+        if (m.vtx_dev) (void) hipFree(m.vtx_dev);
+        m.vtx_host = m.vtx_dev = nullptr;
+        m.vtx_cap = 0;
+        HIP_TRY(hipHostMalloc(&m.vtx_host, bytes));
+        HIP_TRY(hipMalloc(&m.vtx_dev, bytes));
+        m.vtx_cap = bytes;
+    }
+    if (!m.vtx_ev) HIP_TRY(hipEventCreateWithFlags(&m.vtx_ev, hipEventDisableTiming));
+    std::memcpy(m.vtx_host, vel, bytes);
+    HIP_TRY(hipMemcpyAsync(m.vtx_dev, m.vtx_host, bytes, hipMemcpyHostToDevice, stream));
+    st = gather_velocities(scene, shape, (const float *) m.vtx_dev, stream);
+    HIP_TRY(hipEventRecord(m.vtx_ev, stream));
+    if (st != BF_OK) return st;
+    return mark_last(scene, stream);
+}
+
+bf_status bf_scene_set_vertex_velocities_device(bf_scene *scene, uint32_t shape, const float *vel_dev, void *stream_) {
+    const char *fn = "bf_scene_set_vertex_velocities_device:";
+    bf_status st = check_velocity_shape(scene, shape, fn);
+    if (st != BF_OK) return st;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    BF_ENTER(scene);
+    MeshState &m = scene->mesh;
+    if (m.velocity_mode(shape) != BF_VELOCITY_VERTEX || !m.vel)
+        return fail(BF_ERR_INVALID, "%s shape %u is not in BF_VELOCITY_VERTEX (bf_scene_set_velocity_mode)", fn, shape);
+    if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if ((st = gather_velocities(scene, shape, scene->geom->topo[shape].n_vertices ? vel_dev : nullptr, stream)) != BF_OK) return st;
+    return mark_last(scene, stream);
 }
 
 // ---- rebuild of both trees on the device (bf_build.hip) ---------------------------------------------------------------
@@ -995,6 +1231,8 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
     take(posed && B.wnodes, B.wnodes, &wnodes0);
     const uint32_t old_spill = scene->d.stack_need > 16 ? scene->d.stack_need - 16 : 1, new_spill = bo.stack4 > 16 ? bo.stack4 - 16 : 1;
     take(new_spill > old_spill, (size_t) scene->d.spill_stride * new_spill * sizeof(int), &spill);
+    float4 *vel = nullptr;      // the velocity rows follow the slots (bf_scene_set_velocity_mode); the handle's own, like the spill columns
+    take(m.vel != nullptr, (size_t) n * bfvel::kRowsPerSlot * sizeof(float4), &vel);
     if (st != BF_OK) {
         drop();
         return st;
@@ -1009,6 +1247,7 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
         for (size_t part = 0; part < 3; ++part)
             if (e == hipSuccess && uvs) e = bfk_build_gather(bo.order, n, scene->d.uvs + part * n, uvs + part * n, 1, stream);
         if (e == hipSuccess && corners) e = bfk_build_gather(bo.order, n, (const float4 *) scene->geom->corners, corners, 1, stream);
+        if (e == hipSuccess && vel) e = bfk_build_gather(bo.order, n, m.vel, vel, bfvel::kRowsPerSlot, stream);
         // the quantised copies by the refit's own kernel (no levels to re-fit: the boxes are the builder's)
         const uint32_t no_levels[1] = {0u};
         if (e == hipSuccess && qnodes)
@@ -1036,7 +1275,7 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
     g2->corners = (uint4 *) corners;
     g2->normal_index = scene->geom->normal_index;      // per vertex and face, not per slot: shared as they are
     for (void *p : fresh)
-        if (p && p != spill) g2->owned.push_back(p);
+        if (p && p != spill && p != vel) g2->owned.push_back(p);
     const MeshState::Refit &rf = m.refit;
     const void *gone[] = {m.tris0, m.nodes0, m.wnodes0, scene->d.tris, scene->d.nodes, scene->d.wnodes, scene->d.qnodes, scene->d.normals,
                           m.normals0, rf.lvl4, rf.lvl16, rf.ubox4, rf.ubox16, spill ? scene->d.spill : nullptr};
@@ -1071,6 +1310,10 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
         scene->owned.push_back(spill);
     }
     m.reset_after_rebuild(tris0, posed ? nodes0 : nullptr, posed ? wnodes0 : nullptr, normals0);
+    if (vel) {
+        (void) hipFree(m.vel);      // (the gather has run: enqueue() waited for the stream)
+        m.vel = vel;
+    }
     float oscale = m.origin_scale_built;
     for (int k = 0; k < 3; ++k) oscale = std::max({oscale, std::fabs(bo.lo[k]), std::fabs(bo.hi[k])});
     m.origin_scale_built = oscale;      // (what the builder padded for: kept, never lowered)
@@ -1084,6 +1327,7 @@ bf_status bf_scene_rebuild_bvh(bf_scene *scene, void *stream_) {
         const float e = 2e-6f * mx + 2e-7f * oscale + 1e-30f;
         for (int k = 0; k < 3; ++k) inf.bbox_min[k] = bo.lo[k] - e, inf.bbox_max[k] = bo.hi[k] + e;
     }
+    if (vel && (st = velocity_stamp(scene, m.vel, stream)) != BF_OK) return st;      // a range-rate table names the rows it reads
     return mark_last(scene, stream);
 }
 
@@ -1194,7 +1438,7 @@ bf_status bfdbg_scene_read_tree(const bf_scene *scene, uint32_t which, int32_t v
     if (which == 64u && !d.qnodes) return fail(BF_ERR_UNSUPPORTED, "bfdbg_scene_read_tree: the scene has no quantised nodes (BF_QUANT_BVH=1)");
     const float4 *tris = d.tris, *normals = d.normals, *nodes = d.nodes, *wnodes = d.wnodes, *qnodes = d.qnodes;
     if (version >= 0) {
-        const MotionLayout L = motion_layout(d);
+        const MotionLayout L = motion_layout(d, m.batch_vel);
         if (!m.arena || (uint32_t) version >= m.batch_versions || L.rows != m.batch_rows)
             return fail(BF_ERR_INVALID, "bfdbg_scene_read_tree: version %d: the handle's last batch left %u whole versions in its arena "
                                         "(none if it was chunked)", version, m.batch_versions);

@@ -280,7 +280,8 @@ BF_DEV bool shade_vertex(const DScene &sc0, const DLaunch &lp, PathState &s, con
         // s.rd still is (bf_range_rate.h); the arrival form gave the path its class when it was generated
         if ((RX & kClass) && si_valid && !scene_class_arrival(sc)) {
             if (scene_class_range_rate(sc))
-                s.cls = scene_range_rate_class(sc, si.shape, si.p.x, si.p.y, si.p.z, s.rd.x, s.rd.y, s.rd.z);
+                s.cls = scene_range_rate_class(sc, si.shape, si.p.x, si.p.y, si.p.z, s.rd.x, s.rd.y, s.rd.z, hit.slot, hit.u, hit.v,
+                                               (RX & kGeom) ? (uint64_t) s.render * lp.geom_stride : 0ull);
             else
                 s.cls = scene_classes(sc)[si.shape];
         }

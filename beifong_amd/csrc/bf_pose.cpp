@@ -279,6 +279,7 @@ bf_status pose_shape(bf_scene *scene, const PosedShape &p, const char *name, hip
     BF_ENTER_AS(scene, name);
     MeshState &m = scene->mesh;
     if ((st = mesh_enter(scene, stream)) != BF_OK) return st;
+    if ((st = velocity_before(scene, stream)) != BF_OK) return st;
     const bool with_normals = !m.recomputes(p.shape);      // BF_NORMALS_RECOMPUTE: update_vertices_locked computes them
     if ((st = pose_scratch(scene, pose_floats(p, with_normals) * sizeof(float), stream, fn)) != BF_OK) return st;
     const size_t bytes = pose_table_floats(p, 1u) * sizeof(float);
@@ -290,6 +291,7 @@ bf_status pose_shape(bf_scene *scene, const PosedShape &p, const char *name, hip
     if ((st = pose_vertices(p, with_normals, (const float *) stg->dev, 1u, m.pose_vtx, &at, stream)) != BF_OK) return st;
     HIP_TRY(hipEventRecord(stg->ev, stream));      // the table is read by the kernel
     if ((st = update_vertices_locked(scene, p.shape, *p.tp, at.pos, at.nrm, bound, box, true, stream)) != BF_OK) return st;
+    if ((st = velocity_after(scene, p.shape, stream)) != BF_OK) return st;
     return mark_last(scene, stream);
 }
 

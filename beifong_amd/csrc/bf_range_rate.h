@@ -21,11 +21,11 @@ struct Header {
     float sensor_lin[3];
     float r0, sr;
     uint32_t n_bins;
-    uint32_t pad[2];
+    uint32_t pad[2];      // the address of the velocity rows, low and high half (bf_velocity.h); 0 while no shape has a velocity mode
 };
 // The twist of one shape, each vector in a 16-byte word of its own.
 struct Row {
-    float lin[3], pad0;
+    float lin[3], pad0;      // pad0: the bits of the shape's BF_VELOCITY_* mode (bf_velocity.h); 0: the twist alone
     float ang[3], pad1;
     float pivot[3], pad2;
 };

@@ -181,6 +181,28 @@ struct __attribute__((visibility("hidden"))) MeshState {
     // clone copies them); kept apart from `skins`, so a mode outlives the skin it was set for.  Read by every call that takes bones
     std::vector<uint8_t> skin_mode;
     bool skins_dq(uint32_t shape) const { return shape < skin_mode.size() && skin_mode[shape] == BF_SKIN_DUAL_QUATERNION; }
+    // velocity modes (bf_scene_set_velocity_mode): BF_VELOCITY_* and the time step per shape, held as the normal modes
+    // are (empty: every shape BF_VELOCITY_TWIST; a clone copies them and the rows).  vel: the velocity rows the handle's own renders
+    // read under a range-rate table, three float4 per triangle slot (bf_velocity.h), allocated by the first mode other than
+    // BF_VELOCITY_TWIST and zero until a field is given or a move differences it.  vel_prev: the rendered triangle rows as they were
+    // before the move in progress (scratch).  vel_tab: device [n_shapes] (mode bits, dt), what bf_velocity_diff_kernel reads.
+    // batch_vel: the versions of the last batch carried velocity rows (MotionLayout).  All four go with the handle.
+    std::vector<uint8_t> vel_mode;
+    std::vector<float> vel_dt;
+    float4 *vel = nullptr, *vel_prev = nullptr;
+    float2 *vel_tab = nullptr;
+    bool batch_vel = false;
+    uint32_t velocity_mode(uint32_t shape) const { return shape < vel_mode.size() ? vel_mode[shape] : (uint32_t) BF_VELOCITY_TWIST; }
+    bool velocities() const {          // some shape is in BF_VELOCITY_VERTEX or BF_VELOCITY_DIFFERENCE
+        for (uint8_t v : vel_mode)
+            if (v != BF_VELOCITY_TWIST) return true;
+        return false;
+    }
+    bool differences() const {         // some shape is in BF_VELOCITY_DIFFERENCE
+        for (uint8_t v : vel_mode)
+            if (v == BF_VELOCITY_DIFFERENCE) return true;
+        return false;
+    }
 
     // what to read as the base rows: the handle's own once it has moved, else the arrays it renders (a clone's snapshot included)
     struct Base { const float4 *tris, *nodes, *wnodes, *normals; };
@@ -356,6 +378,8 @@ struct __attribute__((visibility("hidden"))) EndpointState {
     uint32_t *classes = nullptr;             // device: shape_class[n_shapes], the arrival table's twelve words or the range-rate table's
                                              // 8 + 12 n_shapes (room for any) once bf_scene_set_classes / bf_scene_set_arrival_classes /
                                              // bf_scene_set_range_rate_classes has given one (d->class_lo / class_hi)
+    std::vector<uint32_t> rr_words;          // the range-rate table as installed, while that form is the handle's (else empty): what
+                                             // velocity_stamp patches and copies again when a velocity mode or the rows' address changes
 
     void apply(const Image &img, bool tab_cache);      // every count and profile bit, here and in *d, from a flattened description (tab_cache: bf_tunables)
     void pack(const Image &img, char *blk) const;      // the five tables into a host block of this layout
@@ -467,6 +491,13 @@ bf_status check_deform_shape(const bf_scene *scene, uint32_t shape, bool with_no
 // bf_scene_clone: if `src` has moved, `sc` (a copy of src's kernel arguments so far) takes its own snapshot of what src renders now
 bf_status mesh_clone_snapshot(const bf_scene *src, bf_scene *sc);
 
+// the velocity rows around a call that rewrites the rendered triangle rows (BF_VELOCITY_DIFFERENCE: the rows before the call are kept,
+// and differenced against the rows after it into the handle's field); both do nothing while no shape is in that mode.  shape: the one
+// shape the call moved (a vertex update, a pose: every other shape keeps its field), or kAllShapes (a transform, a translation)
+constexpr uint32_t kAllShapes = UINT32_MAX;
+bf_status velocity_before(bf_scene *scene, hipStream_t stream);
+bf_status velocity_after(bf_scene *scene, uint32_t shape, hipStream_t stream);
+
 // ---- bf_mesh.cpp, called by bf_pose.cpp (a pose ends in a device-form vertex update, a posed batch in a deform batch) ----
 bf_status mesh_enter(const bf_scene *scene, hipStream_t stream);
 bf_status update_vertices_locked(bf_scene *scene, uint32_t shape, const bf_geometry::MeshTopo &tp, const float *pos_dev, const float *nrm_dev,
@@ -491,6 +522,9 @@ bf_status endpoints_flatten(const bf_scene_desc *desc, EndpointState::Image &img
 bf_status endpoints_create(bf_scene *sc, EndpointState::Image &img, uint64_t *bytes);
 // bf_scene_clone: `sc` (whose kernel arguments are a copy of src's) takes src's profile and its own copies of src's tables
 bf_status endpoints_clone(const bf_scene *src, bf_scene *sc);
+// the handle's range-rate table (if that form is installed) with every shape's velocity mode and the address `rows` of the velocity
+// rows its kernels are to read (nullptr: every shape as BF_VELOCITY_TWIST), copied to the device again in stream order
+bf_status velocity_stamp(bf_scene *scene, const float4 *rows, hipStream_t stream);
 }
 
 #pragma GCC visibility pop

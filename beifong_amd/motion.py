@@ -45,6 +45,18 @@ def twist(lin=(0.0, 0.0, 0.0), ang=(0.0, 0.0, 0.0), pivot=(0.0, 0.0, 0.0)):
     return np.concatenate([np.asarray(v, dtype=f32).reshape(3) for v in (lin, ang, pivot)])
 
 
+def vertex_velocities(p_prev, p_next, dt):
+    """float32, the shape of p_prev: the world-space velocity of every vertex from its positions at two instants dt seconds apart,
+    (p_next - p_prev) / dt in float32 with the difference and the quotient rounded on their own: a field for
+    Scene.set_vertex_velocities (BF_VELOCITY_VERTEX), and what BF_VELOCITY_DIFFERENCE computes on the device from the rendered
+    corners (capi.corner_velocities is the same arithmetic)."""
+    a, b, t = np.asarray(p_prev, dtype=f32), np.asarray(p_next, dtype=f32), f32(dt)
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError(f"dt must be finite and positive, got {dt}")
+    with np.errstate(all="ignore"):
+        return ((b - a) / t).astype(f32, copy=False)
+
+
 def is_identity(m):
     m = np.asarray(m, dtype=f32).reshape(3, 4)
     return bool(np.array_equal(m, rigid()))

@@ -230,7 +230,7 @@ def _rest_pose(sd, shape):
             np.ctypeslib.as_array(s.normals, shape=(s.n_vertices, 3)) if s.normals else None)
 
 
-def _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch):
+def _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch, velocities=None):
     """The driver behind the motion, deform, skin and morph sweeps: `n` pulses of `sd` whose meshes stand at xf[k] (None: as posed)
     on top of what the three callables make of pulse k.
 
@@ -246,6 +246,8 @@ def _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, reco
     lib = lib or capi.load_library()
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
     n_streams = max(1, min(int(n_streams), n))
+    if velocities:
+        n_streams = 1       # differences are taken between what ONE handle renders: the sweep's own pulse order (_velocities)
     streams = [torch.cuda.Stream(dev) for _ in range(n_streams)]
     first = capi.Scene(sd, lib)
     handles = [first]
@@ -253,6 +255,7 @@ def _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, reco
         prepare(first, dev)
         launch, n_classes = _classed(first, launch, classes)
         _recompute(first, recompute_normals)
+        _velocities(first, velocities)
         handles += [first.clone() for _ in range(n_streams - 1)]
         cube = torch.zeros((n, handles[0].channels(launch)), dtype=torch.float32, device=dev)
         for s in streams:           # the cube was zero-filled (and prepare's arrays written) on the current stream
@@ -295,7 +298,7 @@ def _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, reco
             h.close()
 
 
-def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None, per_pulse=False, classes=None):
+def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=None, per_pulse=False, classes=None, velocities=None):
     """Coherent pulse sweep in which every mesh moves on its own: two targets at different speeds, a
     turning car.
 
@@ -316,7 +319,11 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
     direction they arrive from (Scene.set_arrival_classes), same cube shape with n_classes = n_u * n_v + 1: cube[:, k] is the
     range-Doppler map of angle bin k, the cube a range-Doppler-angle cube.  classes=(capi.range_rate_bins(...), twists): the
     returns split by the range rate of the scatterer each path hit first (Scene.set_range_rate_classes), n_classes = n_bins + 2;
-    the twists are world-space and the same for every pulse.  Every sweep of this module takes any of the three forms."""
+    the twists are world-space and the same for every pulse.  Every sweep of this module takes any of the three forms, and with
+    the third velocities={shape: dt}: those meshes add the differences of their rendered positions over dt to their twist
+    (Scene.set_velocity_mode, BF_VELOCITY_DIFFERENCE).  A sweep with velocities runs on ONE handle and stream, n_streams ignored: the
+    differences are forward between the pulses of the batch (the last pulse repeats the field before it; at least two pulses),
+    backward between consecutive pulses with per_pulse=True."""
     xf = np.asarray(transforms, dtype=np.float32)
     if xf.ndim != 4 or xf.shape[2:] != (3, 4):
         raise ValueError(f"transforms must be [n_pulses, n_shapes, 3, 4], got {xf.shape}")
@@ -325,7 +332,7 @@ def render_motion_sweep(sd, launch, transforms, n_streams=2, lib=None, device=No
         h.render_motion_batch_device(lp, xf[c0:c1], cube_ptr, stream=stream)
 
     return _version_sweep(sd, launch, xf.shape[0], xf, n_streams, per_pulse, None, classes, None, lib, device,
-                          lambda first, dev: None, None, batch)
+                          lambda first, dev: None, None, batch, velocities)
 
 
 def _recompute(first, recompute_normals):
@@ -334,6 +341,18 @@ def _recompute(first, recompute_normals):
     the device from each pulse's positions."""
     for k in (recompute_normals or ()):
         first.set_normal_mode(int(k), capi.BF_NORMALS_RECOMPUTE)
+
+
+def _velocities(first, velocities):
+    """velocities={shape: dt} of every sweep that takes classes=(bins, twists): BF_VELOCITY_DIFFERENCE with time step dt on the first
+    handle, before it is cloned (clones inherit the modes), so those meshes' range rates carry the differences of their rendered
+    positions (Scene.set_velocity_mode; capi.corner_velocities is the statement).  The differences are taken within what ONE handle
+    renders, so a sweep with velocities runs on one handle and one stream whatever n_streams says (two handles would each difference
+    pulses n_streams apart, or repeat a field at the end of every group): forward between the pulses of its one batch (the last pulse
+    repeats the field before it; the sweep needs two pulses), backward between consecutive pulses with per_pulse=True (pulse 0 from
+    the description's pose).  With rebuild_every the batched path renders several batches: the last pulse of each repeats a field."""
+    for k, dt in (velocities or {}).items():
+        first.set_velocity_mode(int(k), capi.BF_VELOCITY_DIFFERENCE, float(dt))
 
 
 def _dual_quaternion(first, dual_quaternion, skinned):
@@ -347,7 +366,7 @@ def _dual_quaternion(first, dual_quaternion, skinned):
 
 
 def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib=None, device=None, per_pulse=False, rebuild_every=None,
-                        classes=None, recompute_normals=None):
+                        classes=None, recompute_normals=None, velocities=None):
     """Coherent pulse sweep in which meshes DEFORM between the pulses: a walking pedestrian, a vibrating
     panel.  The deforming counterpart of render_motion_sweep.
 
@@ -365,7 +384,8 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
     normals of every pulse's positions, computed on the device (Scene.set_normal_mode; motion.vertex_normals_f32 is the
     statement), where by default they keep the normals of the description.
     Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W); with
-    classes=(shape_class, n_classes, miss_class), as in render_motion_sweep, float32[n_pulses, n_classes, f_bins * t_bins, 3]."""
+    classes=(shape_class, n_classes, miss_class), as in render_motion_sweep, float32[n_pulses, n_classes, f_bins * t_bins, 3];
+    velocities={shape: dt} with classes=(bins, twists), likewise (one handle and stream then, n_streams ignored)."""
     import torch
     every = _every(rebuild_every)
     n, shapes, pos, _ = capi.deform_tables(positions, None, {k: int(sd.shapes[int(k)].n_vertices) for k in positions if 0 <= int(k) < len(sd.shapes)})
@@ -387,11 +407,11 @@ def render_deform_sweep(sd, launch, positions, transforms=None, n_streams=2, lib
         h.render_deform_batch_device(lp, c1 - c0, {int(sh): d[c0].data_ptr() for sh, d in zip(shapes, dpos)}, cube_ptr, bound,
                                      transforms=None if xf is None else xf[c0:c1], stream=stream)
 
-    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch)
+    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch, velocities)
 
 
 def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None, classes=None, lib=None,
-                      device=None, recompute_normals=None, dual_quaternion=None):
+                      device=None, recompute_normals=None, dual_quaternion=None, velocities=None):
     """Coherent pulse sweep in which SKINNED meshes are posed by a few bones per pulse: the counterpart of
     render_deform_sweep whose per-pulse input is [n_bones, 3, 4] floats per mesh, not its vertices.
 
@@ -406,7 +426,8 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
     pulse; per-path results are the same.  rebuild_every, classes and recompute_normals (the normals of the POSED surface in
     place of the blended rest normals) as in render_deform_sweep.  dual_quaternion=(shapes...): those skinned meshes are blended
     as unit dual quaternions (Scene.set_skin_mode, motion.apply_skin_dq; their bones must be rigid), which keeps the volume of a
-    twisting joint, where by default they are blended linearly.  Returns the cube
+    twisting joint, where by default they are blended linearly.  velocities={shape: dt} with classes=(bins, twists) as in
+    render_motion_sweep (one handle and stream then, n_streams ignored).  Returns the cube
     float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3] with classes."""
     every = _every(rebuild_every)
     n, shapes, tabs = capi.skin_tables(bones)
@@ -431,11 +452,11 @@ def render_skin_sweep(sd, launch, skins, bones, transforms=None, n_streams=2, pe
         h.render_skin_batch_device(lp, {int(sh): tab[c0:c1] for sh, tab in zip(shapes, tabs)}, cube_ptr,
                                    transforms=None if xf is None else xf[c0:c1], stream=stream)
 
-    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch)
+    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch, velocities)
 
 
 def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, transforms=None, n_streams=2, per_pulse=False, rebuild_every=None,
-                       classes=None, recompute_normals=(), lib=None, device=None, dual_quaternion=None):
+                       classes=None, recompute_normals=(), lib=None, device=None, dual_quaternion=None, velocities=None):
     """Coherent pulse sweep in which meshes are moved by MORPH TARGETS (blend shapes), a few weights per pulse: the
     counterpart of render_skin_sweep for surfaces that bones describe badly, a breathing chest wall or a panel vibrating in a
     few modes.  A mesh may be skinned behind its morph.
@@ -452,7 +473,7 @@ def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, tran
     contiguous groups, one per handle and stream, each ONE morph batch (bf_render_morph_batch_device).  per_pulse=True is the
     reference path: the pulses rotate over the handles, one bf_scene_pose_morph (+ one bf_scene_transform_meshes) and one
     render per pulse; per-path results are the same.  rebuild_every, classes, recompute_normals and dual_quaternion (for skinned
-    meshes) as in render_skin_sweep.
+    meshes) as in render_skin_sweep, velocities={shape: dt} as in render_motion_sweep (one handle and stream then).
     Returns the cube float32[n_pulses, f_bins * t_bins, 3] of (I, Q, W), or float32[n_pulses, n_classes, f_bins * t_bins, 3]
     with classes."""
     every = _every(rebuild_every)
@@ -491,7 +512,7 @@ def render_morph_sweep(sd, launch, morphs, weights, skins=None, bones=None, tran
                                     bones={k: t[c0:c1] for k, t in btabs.items()} or None,
                                     transforms=None if xf is None else xf[c0:c1], stream=stream)
 
-    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch)
+    return _version_sweep(sd, launch, n, xf, n_streams, per_pulse, every, classes, recompute_normals, lib, device, prepare, pose, batch, velocities)
 
 
 def range_doppler(cube, window=True):

@@ -752,6 +752,47 @@ typedef struct bf_range_rate_bins {
 bf_status bf_scene_set_range_rate_classes(bf_scene *scene, const bf_range_rate_bins *bins,
                                           const bf_twist *twists /* host [n_shapes], scene-description order */, void *stream);
 
+/* Range rate from per-vertex velocities: micro-Doppler under the range-rate table.  A mesh that does not move rigidly (a skinned
+ * figure, a spinning wheel, a vibrating panel) carries a velocity per vertex on top of its shape's twist.
+ *   bf_scene_set_velocity_mode: per handle and mesh shape.
+ *     BF_VELOCITY_TWIST (the default): the rule above, bit for bit.  Rectangles are always in this mode.
+ *     BF_VELOCITY_VERTEX: an explicit per-vertex field, zero until bf_scene_set_vertex_velocities gives one; every render of a batch
+ *       sees the same field.
+ *     BF_VELOCITY_DIFFERENCE: the corner velocities are differences of the rendered positions over the time step dt (seconds, finite
+ *       and positive; ignored by the other two modes): fl(fl(P_next - P_prev) / dt) per component, IEEE fp32 division, P the
+ *       world-space corner exactly as the rendered triangle holds it (after the vertex update or pose, and after the handle's rigid
+ *       pose or a batch's per-render transform).
+ *       On a handle every call that rewrites the shape's rendered triangles (bf_scene_update_vertices*, bf_scene_pose_skin,
+ *       bf_scene_pose_morph, bf_scene_transform_meshes, bf_scene_translate_meshes) sets the field from the triangles before and after
+ *       the call: a frame-by-frame sweep carries backward differences, and before the first such call the field is zero.  A vertex
+ *       update or a pose moves one shape and sets that shape's field alone; a transform or a translation sets every shape's.
+ *       In a motion, deform, skin or morph batch render k < n_renders - 1 takes P_prev from version k and P_next from version k + 1,
+ *       and the last render takes the field of render n_renders - 2; such a batch needs n_renders >= 2 while any shape of the handle
+ *       is in this mode and the launch reads velocities (BF_FLAG_CLASSES under a range-rate table; BF_ERR_INVALID otherwise), gives
+ *       the same fields however BF_MOTION_BATCH_MB cuts it, and leaves the handle's own field alone, as it leaves its pose.
+ *     Setting a mode other than BF_VELOCITY_TWIST zeroes the shape's field.  The call waits for the handle's work in flight.
+ *   Rule: under a range-rate table, a path whose first intersection lies on a triangle of a shape in mode VERTEX or DIFFERENCE, at
+ *   barycentrics (u, v) (bf_ray_intersect's prim_uv) of a triangle with corner velocities V0, V1, V2 in face order, replaces w by
+ *     b0   = fl(fl(1 - u) - v)
+ *     U    = fl(fl(fl(b0 V0) + fl(u V1)) + fl(v V2))                per component
+ *     w    = fl(fl(fl(lin + c) + U) - sensor_lin)                   per component; lin, c: the shape's twist, as above
+ *   and goes on with rr, t and the class as above: the twist still applies underneath (a walking figure is a translating twist plus
+ *   a vertex field).  A field value that is not finite gives an rr that is not finite: the class outside the window.  Corner
+ *   velocities are WORLD-SPACE values used as given; like twists they are not rotated by anything.  (csrc/bf_velocity.h is that
+ *   arithmetic; capi.interpolate_velocity, capi.corner_velocities and capi.range_rate_classes state it in numpy.)
+ *   bf_scene_set_vertex_velocities (and its _device form, which reads a device array valid until `stream` has run the call) gathers
+ *   the field of a shape in BF_VELOCITY_VERTEX to its triangles: stream-ordered, the caller's memory free on return.
+ *   bf_scene_rebuild_bvh carries the field along; bf_scene_clone copies modes, time steps and field.
+ *   BF_ERR_INVALID for a null scene (or a null mode_out and dt_out), a shape that is not a mesh, an unknown mode, a dt that is not
+ *   finite and positive in BF_VELOCITY_DIFFERENCE, a field given to a shape that is not in BF_VELOCITY_VERTEX, and a value of the
+ *   host form that is not finite. */
+enum { BF_VELOCITY_TWIST = 0, BF_VELOCITY_VERTEX = 1, BF_VELOCITY_DIFFERENCE = 2 };
+bf_status bf_scene_set_velocity_mode(bf_scene *scene, uint32_t shape, uint32_t mode, float dt);
+bf_status bf_scene_get_velocity_mode(const bf_scene *scene, uint32_t shape, uint32_t *mode_out, float *dt_out /* either may be NULL */);
+bf_status bf_scene_set_vertex_velocities(bf_scene *scene, uint32_t shape, const float *vel /* host [n_vertices][3], NULL: zeros */, void *stream);
+bf_status bf_scene_set_vertex_velocities_device(bf_scene *scene, uint32_t shape, const float *vel_dev /* device [n_vertices][3], NULL: zeros */,
+                                                void *stream);
+
 /* Arbitrary output variables (BF_FLAG_AOV).  A scene handle carries an optional AOV table: a list of BF_AOV_* types, in the order
  * their channels follow X Y Z A W in every pixel; a type may appear more than once.
  *   bf_aov_floats returns K, the floats the list occupies per pixel (0 for an invalid list: no entry, more than BF_MAX_AOVS, an

@@ -1,7 +1,7 @@
 """Developer A/B: renders with and without returns by target class (BF_FLAG_CLASSES, 5 classes) on the full-size bench scenes,
 interleaved run by run, with the per-kernel times of BF_FLAG_STATS.
 
-    python tools/class_ab.py [--runs 5] [--steps 6] [--configs c4,c2] [--arrival] [--range-rate]
+    python tools/class_ab.py [--runs 5] [--steps 6] [--configs c4,c2] [--arrival] [--range-rate] [--vertex-velocity]
 
 c4 : one C4 shard (bus + car + motorbike, 4096 range bins, 2^19 paths) per render.  5 classes x 4101 floats = 20505 >
      kMaxLdsHist: the classed render takes global atomics BY SIZE, the plain one privatises its histogram in LDS.
@@ -21,6 +21,11 @@ it brings along:
                 [-24, 0) m/s, the class outside and the miss class; the radar at 6 m/s along +x, aperture and ground at rest, mesh k closing at
                 4 (k + 1) m/s and yawing at 0.5 rad/s about the origin), on a handle of its own: the cost of the class from the first
                 intersection's range rate (a per-lane row of twelve words and some thirty fp32 operations) against one table word
+    rr_vertex, rr_difference  (--vertex-velocity, with --range-rate) the same table and twists on two more handles whose meshes are in
+                BF_VELOCITY_VERTEX (an explicit field: every mesh spinning at 0.3 rad/s about its centroid's vertical) and in
+                BF_VELOCITY_DIFFERENCE (dt = 1/64 s, every mesh stepped 1 cm along -x by one bf_scene_transform_meshes and back, so
+                the geometry rendered is the description's and the field that of the step back): the cost of the three velocity
+                rows per hit and the interpolation against the twist alone (range_rate: BF_VELOCITY_TWIST)
 Prints one line per config and mode: medians over runs x steps of kernel_ms, shade_ms, trace_ms, tail_ms, the spread of kernel_ms
 and kernel_ms relative to `lean` and to `classed`."""
 import argparse
@@ -38,6 +43,7 @@ def main():
     ap.add_argument("--configs", default="c4,c2")
     ap.add_argument("--arrival", action="store_true")
     ap.add_argument("--range-rate", action="store_true")
+    ap.add_argument("--vertex-velocity", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -80,6 +86,27 @@ def main():
             assert by_rate.set_range_rate_classes(capi.range_rate_bins((-24.0, 0.0), 3, sensor_lin=(6.0, 0.0, 0.0)), twists) == 5
             modes["range_rate"] = (by_rate, CLS)
             handles.append(by_rate)
+            if args.vertex_velocity:
+                bins = capi.range_rate_bins((-24.0, 0.0), 3, sensor_lin=(6.0, 0.0, 0.0))
+                meshes = [k for k, s in enumerate(w.sd.shapes) if s.type == capi.BF_SHAPE_MESH]
+                by_vertex = capi.Scene(w.sd, lib)
+                assert by_vertex.set_range_rate_classes(bins, twists) == 5
+                for k in meshes:
+                    s = w.sd.shapes[k]
+                    p = np.ctypeslib.as_array(s.positions, shape=(s.n_vertices, 3)).astype(np.float32)
+                    by_vertex.set_velocity_mode(k, capi.BF_VELOCITY_VERTEX)
+                    by_vertex.set_vertex_velocities(k, np.cross(np.float32([0.0, 0.0, 0.3]), p - p.mean(0, dtype=np.float32)).astype(np.float32))
+                by_diff = capi.Scene(w.sd, lib)
+                assert by_diff.set_range_rate_classes(bins, twists) == 5
+                for k in meshes:
+                    by_diff.set_velocity_mode(k, capi.BF_VELOCITY_DIFFERENCE, 1.0 / 64.0)
+                xf = np.tile(motion.rigid(), (n_shapes, 1, 1)).astype(np.float32)
+                for k in meshes:
+                    xf[k] = motion.rigid(t=(-0.01, 0.0, 0.0))
+                by_diff.transform_meshes(xf)
+                by_diff.transform_meshes(np.tile(motion.rigid(), (n_shapes, 1, 1)).astype(np.float32))
+                modes["rr_vertex"], modes["rr_difference"] = (by_vertex, CLS), (by_diff, CLS)
+                handles += [by_vertex, by_diff]
         hist = torch.zeros(lean.channels(w.launch(0, CLS)), dtype=torch.float32, device=dev)
         keys = ("kernel_ms", "shade_ms", "trace_ms", "tail_ms")
         ms = {m: {k: [] for k in keys} for m in modes}
